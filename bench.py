@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the sketch-and-query hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sketch|request]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sketch|request] [--dump-outputs DIR]
 
 One rank per GPU. `python bench.py --gpus N` starts the N ranks itself (gsearch_amd.sharding.ensure_launched re-executes this
 script under torch.distributed.run on 127.0.0.1); when a launcher already set RANK/WORLD_SIZE the script is one of its ranks.
@@ -109,6 +109,41 @@ class Dist:
             import torch.distributed as td
             td.barrier()                      # rank 0 may still be timing the CPU baseline: leave together
             td.destroy_process_group()
+
+
+# ------------------------------------------------------------------------------------------------------
+DUMP_BUDGET = 64 << 20          # --dump-outputs: bytes of .npy payload at most, all arrays together
+
+
+def sample_rows(n, row_bytes, budget, seed):
+    """every row index when n rows of `row_bytes` fit in `budget`, else a fixed seeded sample (ascending) of as many as fit"""
+    k = min(n, max(budget // row_bytes, 1))
+    if k == n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def download_rows(ctx, d_ptr, rows, m, dtype):
+    """rows `rows` of a row-major (?, m) device array -> (len(rows), m) host array"""
+    row_bytes = m * np.dtype(dtype).itemsize
+    return np.stack([ctx.download(d_ptr + int(r) * row_bytes, (m,), dtype) for r in rows]) if len(rows) else np.empty((0, m), dtype)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: writes DIR/<name>.npy for every array (float32 / float64 only, DUMP_BUDGET bytes in all); returns the manifest of the JSON line"""
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, "outputs of %d bytes exceed the %d-byte dump budget" % (total, DUMP_BUDGET)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "bytes": total, "arrays": {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in arrays.items()}}
+
+
+def ids_as_f64(ids):
+    """neighbour ids (u64 bit patterns in an int64 tensor) -> float64: exact below 2^53, i.e. every id of a real database"""
+    return ids.cpu().numpy().view(np.uint64).astype(np.float64)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -319,6 +354,11 @@ def run_sketch(args, D):
                    "genomes_per_gpu": ng, "genome_len": L, "kmer_size": k, "sketch_size": m, "algo": "optdens"},
         "genomes_per_sec": ng * D.world * args.steps / dt,
     }
+    if D.rank == 0 and args.dump_outputs:
+        # the signatures of the last step (rank 0's genomes): all of them when they fit the budget, else a seeded sample of rows
+        rows = sample_rows(ng, m * 4 + 8, DUMP_BUDGET, args.seed)
+        out["dumped_outputs"] = dump_outputs(args.dump_outputs, {"signatures": download_rows(ctx, d_sig, rows, m, np.float32),
+                                                                 "signatures_rows": rows.astype(np.float64)})
     if D.rank == 0:
         # roofline of the dominant kernel (k_sketch_min): algorithmic bytes = ceil(L/4) + m*4 per genome
         alg_bytes_launch = (float((L + 3) // 4) + m * 4.0) * ng
@@ -520,6 +560,8 @@ def run_request(args, D):
         evals_steps.append(ev_t.clone())
     D.barrier_sync()
     dt = D.max(time.perf_counter() - t0)
+    dumped = request_dump(args, ctx, D, ex, db_shard, ids_t, dist_t, cnt_t, ev_t, (merged_ids, merged_dist), d_qsig) \
+        if (D.rank == 0 and args.dump_outputs) else None
     srch_ms, srch_n = ctx.profile_read(2, reset=True)
     tile_ms, tile_n = ctx.profile_read(1, reset=True)
     sk_ms, sk_n = ctx.profile_read(0, reset=True)
@@ -562,6 +604,8 @@ def run_request(args, D):
     }
     if db_shard:
         out["db_shard"] = {"genomes_of_this_rank": int(N_loc), "first_genome": int(g_lo), "merged_best_distance_sum": float(merged_dist[:, 0].sum().item())}
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if D.rank == 0:
         out.update(request_accounting(args, ctx, hn, lib, chk, torch, D, dict(
             srch=(srch_ms, srch_n), tile=(tile_ms, tile_n), sk=(sk_ms, sk_n), stats=st, evals_total=evals_total, d_qsig=d_qsig, ids_t=ids_t,
@@ -590,6 +634,30 @@ def run_request(args, D):
                 except Exception as e:                          # noqa: BLE001
                     out["request_skewed"] = {"error": repr(e)}
         print(json.dumps(out))
+
+
+def request_dump(args, ctx, D, ex, db_shard, ids_t, dist_t, cnt_t, ev_t, merged, d_qsig):
+    """--dump-outputs of `request`: the answers the last timed step handed back - the merged top-k (--shard db), the gathered top-k of
+    all ranks (--shard query, N > 1) or the top-k with its neighbour and evaluation counts (N = 1) - and a seeded sample of the query
+    signatures that step sketched (rank 0's batch). Answer rows beyond half the budget are sampled too."""
+    gathered = D.on and D.world > 1
+    if db_shard:
+        ids, dist = merged
+    elif gathered:
+        ids, dist = ex.gathered()
+    else:
+        ids, dist = ids_t, dist_t
+    nq, knbn, m = ids.shape[0], ids.shape[1], args.sketch_size
+    rows = sample_rows(nq, knbn * 12 + 24, DUMP_BUDGET // 2, args.seed)
+    arrays = {"ids": ids_as_f64(ids)[rows], "distances": dist.cpu().numpy()[rows], "answer_rows": rows.astype(np.float64)}
+    if not gathered:
+        arrays["counts"] = cnt_t.cpu().numpy()[rows].astype(np.float64)
+        arrays["dist_evals"] = ev_t.cpu().numpy().view(np.uint64)[rows].astype(np.float64)
+    used = sum(a.nbytes for a in arrays.values())
+    qrows = sample_rows(cnt_t.shape[0], m * 4 + 8, min(DUMP_BUDGET - used, 256 * (m * 4 + 8)), args.seed + 1)
+    arrays["query_signatures"] = download_rows(ctx, d_qsig, qrows, m, np.float32)
+    arrays["query_signatures_rows"] = qrows.astype(np.float64)
+    return dump_outputs(args.dump_outputs, arrays)
 
 
 def request_accounting(args, ctx, hn, lib, chk, torch, D, r):
@@ -1270,7 +1338,15 @@ def main():
     ap.add_argument("--ingest-files", type=int, default=4096, help="gz FASTA files of the file-inclusive ingest leg (0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle parity sample + CPU baseline leg (profiling passes: ~2 min of host work per run)")
     ap.add_argument("--selftest-launch", action="store_true", help="GPU-free check of the N-rank launch + single all-gather (gloo, stub searcher)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all; larger outputs "
+                         "as a fixed seeded sample of rows, with their row indices): same arguments, same inputs, so two builds compare output for output "
+                         "(`request` and `sketch` workloads)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.selftest_launch or args.workload == "c5dist"):
+        ap.error("--dump-outputs applies to the timed steps of the `request` and `sketch` workloads")
     from gsearch_amd import sharding as S
     rc = S.ensure_launched(args.gpus, os.path.abspath(__file__), sys.argv[1:])     # --gpus N without a launcher: start the N ranks ourselves
     if rc is not None:
