@@ -93,6 +93,10 @@ SYMBOLS = {
     "gs_index_parallel_search_dev": (_i, [_vp, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp]),
     "gs_index_count_matrix": (_i, [_vp, _vp, _u64, _vp]),
     "gs_index_bruteforce_search": (_i, [_vp, _vp, _u64, _u32, _vp, _vp]),
+    "gs_index_exact_search": (_i, [_vp, _vp, _u64, _u32, C.c_float, _vp, _vp, _vp]),
+    "gs_index_exact_search_dev": (_i, [_vp, _vp, _u64, _u32, C.c_float, _vp, _vp, _vp]),
+    "gs_index_knn_graph": (_i, [_vp, _u32, C.c_float, _u64, _u64, _vp, _vp, _vp]),
+    "gs_index_knn_graph_dev": (_i, [_vp, _u32, C.c_float, _u64, _u64, _vp, _vp, _vp]),
     "gs_index_import": (_i, [_vp, _vp, _u64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_index_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_index_get_data": (_i, [_vp, _u64, _u64, _vp]),

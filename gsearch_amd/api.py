@@ -540,6 +540,18 @@ class ReqAnswer:
         return nb_match
 
 
+def dump_knn_graph(seqdict, node_ids, ids, dist, cnt, out):
+    """hnsw2knn's neighbour-list text: one line per node, `path:` then per neighbour, in order, a tab, `path:` and the distance with six
+    decimals. node_ids[i] = the caller id of row i (Hnsw.get_ids), ids / dist / cnt = Hnsw.knn_graph's answer; `seqdict` = list of
+    (path, fasta_id, length) indexed by the caller id, as in ReqAnswer.dump. Returns the number of lines written."""
+    for i, nid in enumerate(node_ids):
+        out.write("%s:" % seqdict[int(nid)][0])
+        for j in range(int(cnt[i])):
+            out.write("\t%s:%.6f" % (seqdict[int(ids[i, j])][0], float(dist[i, j])))
+        out.write("\n")
+    return len(node_ids)
+
+
 def _rust_5e(x):
     """Rust's {:.5E}: mantissa with 5 decimals, exponent without padding or plus sign (6.07500E-1)"""
     mant, exp = ("%.5E" % x).split("E")
@@ -678,6 +690,35 @@ class Hnsw:
         dist = np.zeros((datas.shape[0], knbn), dtype=np.float32)
         check(self.ctx.L.gs_index_bruteforce_search(self.h, _p(datas), datas.shape[0], knbn, _p(ids), _p(dist)))
         return ids, dist
+
+    def exact_search_arrays(self, datas, knbn, max_dist=1.0):
+        """exact knbn nearest nodes of every query by exhaustive DistHamming (gs_index_exact_search), keeping distances <= max_dist:
+        (ids, dist, cnt) in the layout of search_arrays"""
+        datas = np.ascontiguousarray(datas, dtype=self.dtype)
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "exact search on an empty index")
+        nq = datas.shape[0]
+        ids, dist, cnt = np.zeros((nq, knbn), np.uint64), np.zeros((nq, knbn), np.float32), np.zeros(nq, np.uint32)
+        check(self.ctx.L.gs_index_exact_search(self.h, _p(datas), nq, knbn, float(max_dist), _p(ids), _p(dist), _p(cnt)))
+        return ids, dist, cnt
+
+    def exact_search_dev(self, d_queries, nq, knbn, d_ids, d_dist, d_count, max_dist=1.0):
+        """gs_index_exact_search_dev: every d_* is a device pointer (int)"""
+        check(self.ctx.L.gs_index_exact_search_dev(self.h, d_queries, nq, knbn, float(max_dist), d_ids, d_dist, d_count))
+
+    def knn_graph(self, knbn, max_dist=1.0, first=0, n=None):
+        """the database's own exact k-NN graph (hnsw2knn): for nodes first..first+n in insertion order, their knbn nearest OTHER nodes
+        (gs_index_knn_graph) -> (ids, dist, cnt) in the layout of search_arrays"""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "k-NN graph of an empty index")
+        n = self.get_nb_point() - first if n is None else n
+        ids, dist, cnt = np.zeros((n, knbn), np.uint64), np.zeros((n, knbn), np.float32), np.zeros(n, np.uint32)
+        check(self.ctx.L.gs_index_knn_graph(self.h, knbn, float(max_dist), first, n, _p(ids), _p(dist), _p(cnt)))
+        return ids, dist, cnt
+
+    def knn_graph_dev(self, knbn, first, n, d_ids, d_dist, d_count, max_dist=1.0):
+        """gs_index_knn_graph_dev: every d_* is a device pointer (int)"""
+        check(self.ctx.L.gs_index_knn_graph_dev(self.h, knbn, float(max_dist), first, n, d_ids, d_dist, d_count))
 
     # graph import/export in the library's dense layout (role of HnswIo::load_hnsw / file_dump)
     def import_graph(self, sigs, g):

@@ -3679,6 +3679,114 @@ int gs_index_bruteforce_search(gs_index *ix, const void *queries, uint64_t nq, u
     return GS_OK;
 }
 
+}  // extern "C"
+namespace gs {
+// arguments of the exact k-NN entry points; *c_max = the largest count c with (float)c / (float)m <= max_dist, the f32 distance DistHamming forms
+// (floor(max_dist * m) rounds differently at the boundary), so that the device compares integer counts only
+static int exact_args(const gs_index *ix, uint32_t knbn, float max_dist, uint32_t *c_max)
+{
+    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
+    GS_REQUIRE(knbn >= 1 && knbn <= (uint32_t)KNN_MAX, GS_ERR_INVALID, "knbn must be in 1..%d", (int)KNN_MAX);
+    GS_REQUIRE(max_dist >= 0.0f, GS_ERR_INVALID, "max_dist must be a non-negative number");
+    GS_REQUIRE(ix->n > 0, GS_ERR_STATE, "exact search on an empty index");
+    const uint32_t m = ix->prm.m;
+    GS_REQUIRE(m <= 65535, GS_ERR_UNSUPPORTED, "exact search needs the 16-bit count matrix: m <= 65535");
+    int64_t c = (int64_t)std::min<double>((double)m, std::floor((double)max_dist * (double)m));
+    while (c < (int64_t)m && (float)(c + 1) / (float)m <= max_dist) c++;
+    while (c > 0 && (float)c / (float)m > max_dist) c--;
+    *c_max = (uint32_t)c;
+    return GS_OK;
+}
+// exact k-NN of nq padded device rows (stride ix->stride) against every node, answers to device memory: blocks of rows through dense_counts into
+// ix->mat, the select of gs_knn.hip, then the caller's ids. diag0 != UINT64_MAX: row q drops node diag0 + q (the self graph).
+static int exact_dev(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint64_t *ids, float *dist, uint32_t *count)
+{
+    gs_ctx *c = ix->ctx;
+    // (dense_counts' feed hook is null here: gs_index_sketch_and_search_dev sets it only for its own search_dev, under the context lock this call holds)
+    const uint64_t ld = round_up(ix->n, 8);
+    // as many rows per block as one join pass takes (every pass streams the whole column store), at most 8 GB of counts
+    const uint64_t QB = std::min<uint64_t>(nq, std::min<uint64_t>(match_join_max_queries(), std::max<uint64_t>(64, ((uint64_t)8 << 30) / (2 * ld))));
+    int rc;
+    if (ix->mat.bytes < (size_t)2 * QB * ld && (rc = alloc_or_evict(ix, ix->mat, (size_t)2 * QB * ld))) return rc;
+    for (uint64_t q0 = 0; q0 < nq; q0 += QB) {
+        const uint64_t nb = std::min(QB, nq - q0);
+        if ((rc = dense_counts(ix, q + q0 * ix->stride, nb, ix->n, ix->mat.as<uint16_t>(), ld))) return rc;
+        if ((rc = knn_select(c, ix->mat.as<uint16_t>(), ld, nb, ix->n, knbn, c_max, diag0 == ~(uint64_t)0 ? diag0 : diag0 + q0, ix->prm.m,
+                             ids + q0 * knbn, dist + q0 * knbn, count + q0))) return rc;
+    }
+    return finish_ids(ix, ids, nq * knbn, nullptr, nullptr);
+}
+// host answers: the device ones in pooled buffers, then copied out
+static int exact_to_host(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint64_t *ids, float *dist, uint32_t *count)
+{
+    gs_ctx *c = ix->ctx;
+    PoolBuf dids(c, 33), ddist(c, 34), dcount(c, 35);
+    int rc;
+    if ((rc = dids.alloc(8 * nq * knbn)) || (rc = ddist.alloc(4 * nq * knbn)) || (rc = dcount.alloc(4 * nq))) return rc;
+    if ((rc = exact_dev(ix, q, nq, knbn, c_max, diag0, dids.as<uint64_t>(), ddist.as<float>(), dcount.as<uint32_t>()))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(ids, dids.p, 8 * nq * knbn, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(dist, ddist.p, 4 * nq * knbn, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(count, dcount.p, 4 * nq, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+static int exact_search_common(gs_index *ix, const void *queries, bool on_dev, uint64_t nq, uint32_t knbn, float max_dist, uint64_t *ids, float *dist, uint32_t *count)
+{
+    uint32_t c_max = 0;
+    int rc = exact_args(ix, knbn, max_dist, &c_max);
+    if (rc) return rc;
+    if (nq == 0) return GS_OK;
+    GS_REQUIRE(queries && ids && dist && count, GS_ERR_INVALID, "null argument");
+    gs_ctx *c = ix->ctx;
+    GS_CTX_LOCK(c);
+    PoolBuf dq(c, 32);
+    if ((rc = dq.alloc(ix->stride * nq))) return rc;
+    if ((rc = upload_user_rows(ix, dq.p, queries, nq, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
+    if (!on_dev) return exact_to_host(ix, dq.as<uint8_t>(), nq, knbn, c_max, ~(uint64_t)0, ids, dist, count);
+    if ((rc = exact_dev(ix, dq.as<uint8_t>(), nq, knbn, c_max, ~(uint64_t)0, ids, dist, count))) return rc;
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+// the self graph reads the index's own rows in place: no upload, no copy through the host
+static int knn_graph_common(gs_index *ix, bool on_dev, uint32_t knbn, float max_dist, uint64_t first, uint64_t n_rows, uint64_t *ids, float *dist, uint32_t *count)
+{
+    uint32_t c_max = 0;
+    int rc = exact_args(ix, knbn, max_dist, &c_max);
+    if (rc) return rc;
+    GS_REQUIRE(first <= ix->n && n_rows <= ix->n - first, GS_ERR_INVALID, "rows [%llu, +%llu) beyond nb_point %llu", (unsigned long long)first,
+               (unsigned long long)n_rows, (unsigned long long)ix->n);
+    if (n_rows == 0) return GS_OK;
+    GS_REQUIRE(ids && dist && count, GS_ERR_INVALID, "null argument");
+    gs_ctx *c = ix->ctx;
+    GS_CTX_LOCK(c);
+    const uint8_t *q = ix->data.as<uint8_t>() + first * ix->stride;
+    if (!on_dev) return exact_to_host(ix, q, n_rows, knbn, c_max, first, ids, dist, count);
+    if ((rc = exact_dev(ix, q, n_rows, knbn, c_max, first, ids, dist, count))) return rc;
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+}  // namespace gs
+extern "C" {
+
+int gs_index_exact_search(gs_index *ix, const void *queries, uint64_t nq, uint32_t knbn, float max_dist, uint64_t *ids_out, float *dist_out, uint32_t *count_out)
+{
+    return gs::exact_search_common(ix, queries, false, nq, knbn, max_dist, ids_out, dist_out, count_out);
+}
+int gs_index_exact_search_dev(gs_index *ix, const void *queries_dev, uint64_t nq, uint32_t knbn, float max_dist, uint64_t *ids_out_dev, float *dist_out_dev,
+                              uint32_t *count_out_dev)
+{
+    return gs::exact_search_common(ix, queries_dev, true, nq, knbn, max_dist, ids_out_dev, dist_out_dev, count_out_dev);
+}
+int gs_index_knn_graph(gs_index *ix, uint32_t knbn, float max_dist, uint64_t first, uint64_t n_rows, uint64_t *ids_out, float *dist_out, uint32_t *count_out)
+{
+    return gs::knn_graph_common(ix, false, knbn, max_dist, first, n_rows, ids_out, dist_out, count_out);
+}
+int gs_index_knn_graph_dev(gs_index *ix, uint32_t knbn, float max_dist, uint64_t first, uint64_t n_rows, uint64_t *ids_out_dev, float *dist_out_dev,
+                           uint32_t *count_out_dev)
+{
+    return gs::knn_graph_common(ix, true, knbn, max_dist, first, n_rows, ids_out_dev, dist_out_dev, count_out_dev);
+}
+
 /* own binary dump (role of Hnsw::file_dump / HnswIo::load_hnsw, dumpload.rs:31, reloadhnsw.rs:41-51):
  *   "GSAMDIX1" | gs_index_params | n, n_upper, entry, top (u64,u64,i64,i64) | signatures (dense rows) | levels | deg0 | nbr0 | cnt0 |
  *   upidx | degU | nbrU | cntU   (the export layout of gs_index_export) */

@@ -159,6 +159,13 @@ int hamming_blocks(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t stri
                    uint32_t n_items, const uint32_t *qlist_dev, const uint32_t *clist_dev, uint16_t *out_cnt16, uint64_t ld_out, uint32_t n_thin = 0);
 int rows_to_cols(gs_ctx *c, int kind, uint32_t m, const void *rows, uint64_t stride, uint64_t nrows, void *cols, uint64_t colcap, uint64_t first);
 
+// gs_knn.hip: the k smallest (count, node) keys of each of nrows count rows (n entries at leading dimension ld, 16-byte aligned), keeping
+// entries with count <= c_max; diag0 != UINT64_MAX: row r also drops node diag0 + r. ids (node numbers) / dist (count / m): nrows x knbn, ascending,
+// unused slots UINT64_MAX / +inf; count[r] = how many were kept. Queued on c's stream.
+enum { KNN_MAX = 1024 };
+int knn_select(gs_ctx *c, const uint16_t *mat, uint64_t ld, uint64_t nrows, uint64_t n, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint32_t m,
+               uint64_t *ids, float *dist, uint32_t *count);
+
 // gs_sketch.hip: the device sketch of a batch on context c's stream; sync_at_end = false leaves the results in flight (optdens / revoptdens only)
 int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
                     const uint64_t *genome_rec_off, uint64_t n_genomes, void *sig_out, bool sync_at_end);

@@ -238,6 +238,20 @@ int      gs_index_bruteforce_search(gs_index *, const void *queries, uint64_t nq
  * matrix the dense traversal looks its distances up in - match-join (with heavy blocks through the compare tile kernel) or compare tile kernel
  * as the search would choose. counts_out: HOST nq x nb_point, row-major. Needs m <= 65535. (bindash.rs:120-157 computes the same all-pairs) */
 int      gs_index_count_matrix(gs_index *, const void *queries, uint64_t nq, uint16_t *counts_out);
+/* exact k nearest nodes of each query by exhaustive DistHamming (count matrix + device top-k select); keeps neighbours with
+ * (float)count / (float)m <= max_dist (1.0f: no cut-off); 1 <= knbn <= 1024; needs m <= 65535 (GS_ERR_UNSUPPORTED otherwise).
+ * Same answer layout as gs_index_parallel_search: nq x knbn ids / distances ascending by (distance, node number), the caller's ids, unused slots
+ * UINT64_MAX / +inf, count_out[q] = neighbours kept. SPEC.md "Exact k-NN". */
+int      gs_index_exact_search(gs_index *, const void *queries, uint64_t nq, uint32_t knbn, float max_dist,
+                               uint64_t *ids_out, float *dist_out, uint32_t *count_out);
+int      gs_index_exact_search_dev(gs_index *, const void *queries_dev, uint64_t nq, uint32_t knbn, float max_dist,
+                                   uint64_t *ids_out_dev, float *dist_out_dev, uint32_t *count_out_dev);
+/* the database against itself (hnsw2knn.rs; exact instead of the layer-0 lists): for nodes [first, first + n_rows) in insertion order,
+ * their knbn nearest OTHER nodes. Only the node itself is excluded (by node number); duplicates of it at distance 0 stay. */
+int      gs_index_knn_graph(gs_index *, uint32_t knbn, float max_dist, uint64_t first, uint64_t n_rows,
+                            uint64_t *ids_out, float *dist_out, uint32_t *count_out);
+int      gs_index_knn_graph_dev(gs_index *, uint32_t knbn, float max_dist, uint64_t first, uint64_t n_rows,
+                                uint64_t *ids_out_dev, float *dist_out_dev, uint32_t *count_out_dev);
 /* Graph import / export (the role of hnswio::HnswIo::load_hnsw / Hnsw::file_dump, reloadhnsw.rs:41-51,
  * dumpload.rs:31, in this library's own dense layout): levels[n], entry id, layer 0: deg0[n], nbr0[n*2M],
  * cnt0[n*2M] (mismatch counts to the owner); upper layers: upidx[n] (-1 for level-0 nodes) and for the

@@ -255,10 +255,37 @@ public:
             for (uint32_t j = 0; j < cnt[i]; j++) out[i].push_back(Neighbour{(size_t)ids[i * knbn + j], dist[i * knbn + j], PointId{pl[i * knbn + j], pr[i * knbn + j]}});
         return out;
     }
+    // exact knbn nearest nodes by exhaustive DistHamming, distances <= max_dist (gs_index_exact_search); p_id is not filled
+    std::vector<std::vector<Neighbour>> exact_search(const std::vector<std::vector<T>> &datas, size_t knbn, float max_dist = 1.0f) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "search on an empty index");
+        const size_t nq = datas.size(), m = prm_.m;
+        std::vector<T> flat(nq * m);
+        for (size_t i = 0; i < nq; i++) { if (datas[i].size() != m) throw Error(GS_ERR_INVALID, "signature length mismatch"); std::copy(datas[i].begin(), datas[i].end(), flat.begin() + i * m); }
+        std::vector<uint64_t> ids(nq * knbn); std::vector<float> dist(nq * knbn); std::vector<uint32_t> cnt(nq);
+        check(gs_index_exact_search(h_, flat.data(), nq, (uint32_t)knbn, max_dist, ids.data(), dist.data(), cnt.data()));
+        return lists(ids, dist, cnt, knbn);
+    }
+    // hnsw2knn: the knbn nearest OTHER nodes of nodes [first, first + n) in insertion order, exact (gs_index_knn_graph)
+    std::vector<std::vector<Neighbour>> knn_graph(size_t knbn, float max_dist = 1.0f, size_t first = 0, size_t n = SIZE_MAX) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "k-NN graph of an empty index");
+        if (n == SIZE_MAX) n = get_nb_point() - std::min(first, get_nb_point());
+        std::vector<uint64_t> ids(n * knbn); std::vector<float> dist(n * knbn); std::vector<uint32_t> cnt(n);
+        check(gs_index_knn_graph(h_, (uint32_t)knbn, max_dist, first, n, ids.data(), dist.data(), cnt.data()));
+        return lists(ids, dist, cnt, knbn);
+    }
     void file_dump(const std::string &path) const { check(gs_index_save(h_, path.c_str())); }      // dumpload.rs:31 (own format)
 private:
     void frozen() const { if (h_) throw Error(GS_ERR_STATE, "index parameters are frozen once the index holds points"); }
     void ensure(size_t m) { if (!h_) { prm_.m = (uint32_t)m; check(gs_index_create(ctx_->get(), &prm_, &h_)); } }
+    static std::vector<std::vector<Neighbour>> lists(const std::vector<uint64_t> &ids, const std::vector<float> &dist, const std::vector<uint32_t> &cnt, size_t knbn)
+    {
+        std::vector<std::vector<Neighbour>> out(cnt.size());
+        for (size_t i = 0; i < cnt.size(); i++)
+            for (uint32_t j = 0; j < cnt[i]; j++) out[i].push_back(Neighbour{(size_t)ids[i * knbn + j], dist[i * knbn + j]});
+        return out;
+    }
     Context *ctx_;
     gs_index_params prm_;
     gs_index *h_ = nullptr;
