@@ -2199,7 +2199,6 @@ struct gs_index {
     gs::DevBuf blevels, cntmat, plan_keys, plan_n, inbox, inbox_cnt, touched, ntouched, evals_dev;
     gs::DevBuf wlog, w0_keys, w0_n, w0_evals, ep0; // insert pre-pass (plan_prepass)
     gs::DevBuf ext_keys;                           // candidate keys of the extended selection (extend_candidates with efc <= 2M)
-    hipStream_t jstream = nullptr; hipEvent_t jev = nullptr, jev_up = nullptr;      // insert: the match-join of batch i+1 runs here under plan / links of batch i
     uint64_t inbox_lists = 0;
     uint64_t insert_evals = 0;
     // dense mode: count matrix of a query / insert batch against every node, and the running
@@ -2232,17 +2231,8 @@ struct gs_index {
     // gs_index_sketch_and_search_dev: the padded query rows are produced batch by batch while the search is under way; dense_counts asks for
     // rows [q0, q0 + nb) of the buffer at feed_base just before it joins them
     std::function<int(uint64_t, uint64_t)> *feed = nullptr; const uint8_t *feed_base = nullptr;
-    // three-stage request pipeline (round 5, GS_REQUEST_PIPELINE=3): the traversal of join batch b runs on this stream beside the count matrix of batch b + 1
-    // and the sketch of batch b + 2 (search_dev, dense strategy)
-    hipStream_t tstream = nullptr; hipEvent_t tev = nullptr, tev_done = nullptr; bool pipe3 = false;
     ~gs_index()
     {
-        if (tstream) { (void)hipStreamSynchronize(tstream); (void)hipStreamDestroy(tstream); }
-        if (tev) (void)hipEventDestroy(tev);
-        if (tev_done) (void)hipEventDestroy(tev_done);
-        if (jstream) { (void)hipStreamSynchronize(jstream); (void)hipStreamDestroy(jstream); }
-        if (jev) (void)hipEventDestroy(jev);
-        if (jev_up) (void)hipEventDestroy(jev_up);
         for (auto *b : slabs) delete b;
     }
 };
@@ -2257,7 +2247,6 @@ static void drop_pair_cache(gs_index *ix)
 {
     (void)hipGetLastError();                                       // the failed hipMalloc left its error behind
     if (!ix->slabs.empty()) {
-        if (ix->jstream) (void)hipStreamSynchronize(ix->jstream);
         (void)hipStreamSynchronize(ix->ctx->stream);
         if (ix->rowptr.p) (void)hipMemsetAsync(ix->rowptr.p, 0, ix->rowptr.bytes, ix->ctx->stream);
         (void)hipStreamSynchronize(ix->ctx->stream);
@@ -2581,15 +2570,21 @@ static int search_launch_dense(gs_index *ix, uint64_t nq, uint32_t knbn, uint32_
     return GS_OK;
 }
 
+// the dense traversal (k_hnsw_search_dense) can take a search of this index with efs = max(ef, knbn): degree, ef, knbn and m within its
+// limits and its LDS fits (GS_DENSE_LEGACY forces the sorted-array traversal, k_hnsw_search)
+static bool dense_traversal_fits(const gs_index *ix, uint32_t knbn, uint32_t efs)
+{
+    const uint32_t maxdeg = 2 * ix->prm.max_nb_conn;
+    return maxdeg <= (uint32_t)DT && efs <= 65535u && knbn <= (uint32_t)(TMAXI * DT) && ix->prm.m <= 65535u &&
+           dense_lds_bytes(ix->prm.m, knbn, maxdeg, ix->n, false, maxdeg > (uint32_t)DT / 2 ? 512u : (uint32_t)DCN) <= 160 * 1024 - 1024 && !getenv("GS_DENSE_LEGACY");
+}
 static int search_launch(gs_index *ix, const uint8_t *q_padded_dev, uint64_t nq, uint32_t knbn, uint32_t ef, const uint16_t *mat, uint64_t mat_ld,
                          uint64_t *ids, float *dist, uint32_t *count, uint64_t *evals)
 {
     gs_ctx *c = ix->ctx;
     const uint32_t efs = std::max(ef, knbn);
     const uint32_t maxdeg = 2 * ix->prm.max_nb_conn;
-    if (mat && maxdeg <= (uint32_t)DT && efs <= 65535u && knbn <= (uint32_t)(TMAXI * DT) && ix->prm.m <= 65535u &&
-        dense_lds_bytes(ix->prm.m, knbn, maxdeg, ix->n, false, maxdeg > (uint32_t)DT / 2 ? 512u : (uint32_t)DCN) <= 160 * 1024 - 1024 && !getenv("GS_DENSE_LEGACY"))
-        return search_launch_dense(ix, nq, knbn, ef, mat, mat_ld, ids, dist, count, evals);
+    if (mat && dense_traversal_fits(ix, knbn, efs)) return search_launch_dense(ix, nq, knbn, ef, mat, mat_ld, ids, dist, count, evals);
     const size_t lds = search_lds_bytes(efs, maxdeg);
     const uint32_t vis_words = (uint32_t)((ix->n + 31) / 32);
     uint32_t grid = (uint32_t)std::min<uint64_t>(nq, (uint64_t)c->n_cu);
@@ -2634,8 +2629,7 @@ static int search_dev(gs_index *ix, const void *q_padded_dev, uint64_t nq, uint3
     // ef up to 65535 (hnsw_rs' parallel_search has no limit; gsearch itself asks for 5000, gsearch.rs:893): a larger ef goes that way whatever the cost
     // model says - when the index allows the dense traversal at all
     const bool fits_sorted = lds <= 160 * 1024 - 64 && 2 * (size_t)efs + maxdeg + 64 <= (size_t)SMAXI * ST;
-    const bool dense_able = ix->prm.m <= 65535 && maxdeg <= (uint32_t)DT && efs <= 65535u && knbn <= (uint32_t)(TMAXI * DT) && mode != MODE_GATHER && !getenv("GS_DENSE_LEGACY") &&
-                            dense_lds_bytes(ix->prm.m, knbn, maxdeg, ix->n, false, maxdeg > (uint32_t)DT / 2 ? 512u : (uint32_t)DCN) <= 160 * 1024 - 1024;
+    const bool dense_able = mode != MODE_GATHER && dense_traversal_fits(ix, knbn, efs);
     GS_REQUIRE(fits_sorted || dense_able, GS_ERR_UNSUPPORTED, "ef=%u needs %zu bytes of LDS in the sorted-array traversal (max ~%u with M=%u) and this index / mode does not admit the dense one (m <= 65535, ef <= 65535, GS_DIST_MODE != gather)",
                efs, lds, (unsigned)((160 * 1024 - 64 - 32 * maxdeg - 1024) / 24), ix->prm.max_nb_conn);
     const bool force_dense = !fits_sorted;
@@ -2705,30 +2699,6 @@ static int search_dev(gs_index *ix, const void *q_padded_dev, uint64_t nq, uint3
     if (ix->mat.bytes < (size_t)2 * QB * ld && (rc = alloc_or_evict(ix, ix->mat, (size_t)2 * QB * ld))) return rc;
     if (sv) fprintf(stderr, "[GS_SEARCH] count matrix ready after %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sv_t0).count());
     if (join && (rc = ensure_cols(ix, ix->n))) return rc;
-    if (ix->pipe3 && join && done == 0 && QB == nq) {
-        // three stages, batch by batch (the fused request): count matrix of batch b on this stream, its traversal on `tstream` - beside the count matrix of
-        // batch b + 1 here and the sketches the caller queued on its own stream. The traversal scratch (visited / candidate arrays / query counter) is per
-        // index: launches on tstream follow one another.
-        const uint64_t maxq = match_join_max_queries(), parts = (nq + maxq - 1) / maxq, jq = (nq + parts - 1) / parts;
-        // (leaving this scope - also through a failing dense_counts / search_launch - waits for what is queued on tstream: traversal kernels must not go on
-        // writing ids / dist / evals, nor use ix->visited / cbuf, after the call has returned an error; on success the wait is an event on the main stream below)
-        struct SGuard { gs_ctx *c; hipStream_t main; hipStream_t t; bool ok = false; ~SGuard() { c->stream = main; if (!ok) (void)hipStreamSynchronize(t); } } sg{c, c->stream, ix->tstream};
-        for (uint64_t q0 = 0; q0 < nq; q0 += jq) {
-            const uint64_t nb = std::min(jq, nq - q0);
-            if ((rc = dense_counts(ix, q + q0 * ix->stride, nb, ix->n, ix->mat.as<uint16_t>() + q0 * ld, ld))) return rc;
-            GS_HIP_CHECK(hipEventRecord(ix->tev, c->stream));
-            GS_HIP_CHECK(hipStreamWaitEvent(ix->tstream, ix->tev, 0));
-            c->stream = ix->tstream;
-            rc = search_launch(ix, q + q0 * ix->stride, nb, knbn, ef, ix->mat.as<uint16_t>() + q0 * ld, ld, ids + q0 * knbn, dist + q0 * knbn, count ? count + q0 : nullptr,
-                               evals ? evals + q0 : nullptr);
-            c->stream = sg.main;
-            if (rc) return rc;
-        }
-        GS_HIP_CHECK(hipEventRecord(ix->tev_done, ix->tstream));
-        GS_HIP_CHECK(hipStreamWaitEvent(c->stream, ix->tev_done, 0));
-        sg.ok = true;
-        return GS_OK;
-    }
     for (uint64_t q0 = done; q0 < nq; q0 += QB) {
         const uint64_t nb = std::min(QB, nq - q0);
         if ((rc = dense_counts(ix, q + q0 * ix->stride, nb, ix->n, ix->mat.as<uint16_t>(), ld))) return rc;
@@ -3075,7 +3045,6 @@ int gs_index_sketch_and_search_dev(gs_index *ix, const gs_sketch_params *p, cons
     const char *pe = getenv("GS_REQUEST_PIPELINE");
     const bool pipe = !(pe && !atoi(pe)) && parts >= 2 && (p->algo == GS_ALGO_OPTDENS || p->algo == GS_ALGO_REVOPTDENS) && gs::use_join(ix) &&
                       gs::search_goes_dense(ix, nq, knbn, ef);
-    const bool pipe3 = pipe && pe && atoi(pe) == 3;
     if (!pipe) {
         if ((rc = gs::sketch_dev_impl(c, p, seq_dev, seq_bytes, rec_start_dev, rec_len_dev, n_rec, genome_rec_off_dev, nq, sig, true))) return rc;
         if ((rc = gs::upload_user_rows(ix, dq.p, sig, nq, hipMemcpyDeviceToDevice))) return rc;
@@ -3106,21 +3075,6 @@ int gs_index_sketch_and_search_dev(gs_index *ix, const gs_sketch_params *p, cons
         gs::set_error("event setup failed"); GS_FUSED_FAIL(GS_ERR_HIP);
     }
     w->profile = c->profile;
-    if (pipe3) {
-        // launches shaped to SHARE a compute unit: a sketch workgroup that asks for more than half of the LDS stays alone of its kind on its CU and leaves
-        // room for a traversal workgroup (53.7 kB at 300 k nodes) beside it; the traversal stream gets the highest priority - its workgroups are the
-        // latency-bound ones -, the sketch stream the lowest
-        if (!ix->tstream) {
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            if (hipStreamCreateWithPriority(&ix->tstream, hipStreamNonBlocking, hi) != hipSuccess || hipEventCreateWithFlags(&ix->tev, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&ix->tev_done, hipEventDisableTiming) != hipSuccess) { gs::set_error("stream setup failed"); GS_FUSED_FAIL(GS_ERR_HIP); }
-        }
-        const char *sl = getenv("GS_PIPE_SKETCH_LDS");
-        w->sketch_min_lds = sl ? (uint32_t)atoi(sl) : 100u * 1024u;
-        ix->pipe3 = true;
-    }
-    struct P3Guard { gs_index *ix; gs_ctx *w; ~P3Guard() { ix->pipe3 = false; w->sketch_min_lds = 0; } } p3guard{ix, w};
     for (uint64_t b = 0; b < parts; b++) {
         const uint64_t g0 = b * jq, nb = std::min<uint64_t>(jq, nq - g0);
         // (seq_bytes only feeds the launch heuristics: this batch's share of it)
@@ -3302,25 +3256,6 @@ static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n
     if ((rc = gs::upload_user_rows(ix, ix->data.as<uint8_t>() + first * ix->stride, sigs, n, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(ix->levels.as<uint8_t>() + first, lv.data(), n, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(ix->upidx.as<int32_t>() + first, up.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
-    // Overlap (round 3, GS_INSERT_OVERLAP=1; OFF by default): the match-join of batch i+1 only needs signatures - not batch i's links - so it
-    // can run on a second stream under the pre-pass / plan / link kernels of batch i. Measured on the 300 k-genome build: 18.0 s with and
-    // without - the join's two 72 kB workgroups per CU and the plan kernel's 85 kB do not share a CU, the streams just take turns.
-    // Its rows were queued on the main stream just above.
-    const bool overlap = getenv("GS_INSERT_OVERLAP") && atoi(getenv("GS_INSERT_OVERLAP"));
-    if (overlap) {
-        if (!ix->jstream) {
-            GS_HIP_CHECK(hipStreamCreateWithFlags(&ix->jstream, hipStreamNonBlocking));
-            GS_HIP_CHECK(hipEventCreateWithFlags(&ix->jev, hipEventDisableTiming));
-            GS_HIP_CHECK(hipEventCreateWithFlags(&ix->jev_up, hipEventDisableTiming));
-        }
-        GS_HIP_CHECK(hipEventRecord(ix->jev_up, c->stream));
-        GS_HIP_CHECK(hipStreamWaitEvent(ix->jstream, ix->jev_up, 0));
-    }
-    struct JGuard {          // whatever way this function is left: nothing of it is still running on the second stream, and the context has its own stream back
-        gs_index *ix; gs_ctx *c; hipStream_t main;
-        ~JGuard() { c->stream = main; if (ix->jstream) (void)hipStreamSynchronize(ix->jstream); }
-    } jguard{ix, c, c->stream};
-    bool pf_have = false; uint64_t pf_b0 = 0;
     // scratch
     const uint32_t ef_lds = std::max(efc, B);
     const size_t lds = gs::search_lds_bytes(ef_lds, maxdeg);
@@ -3375,8 +3310,8 @@ static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n
     }
     const uint64_t slab_ld = gs::round_up(first + n, 8);
     // batches joined together (GS_INSERT_GROUP, default 8; 1 = every batch its own join): rows [grp_b0, grp_end) hold their counts against nodes [0, grp_b0)
-    uint32_t grp_n = overlap ? 1u : 8u;
-    if (const char *e = getenv("GS_INSERT_GROUP")) grp_n = overlap ? 1u : (uint32_t)std::max(1, std::min(12, atoi(e)));
+    uint32_t grp_n = 8;
+    if (const char *e = getenv("GS_INSERT_GROUP")) grp_n = (uint32_t)std::max(1, std::min(12, atoi(e)));
     uint64_t grp_b0 = 0, grp_end = 0;
     gs::DevBuf *slab = nullptr; uint64_t slab_first = 0;      // rows of this call's points, allocated at the first dense batch
     bool slab_tried = false;
@@ -3516,16 +3451,9 @@ static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n
                 // streamed once per group instead of once per batch
                 grp_b0 = b0; grp_end = std::min<uint64_t>(first + n, b0 + (uint64_t)grp_n * B);
                 if ((rc = gs::dense_counts(ix, rows, grp_end - grp_b0, b0, out16, mat_ld))) return rc;
-            } else if (slab && pf_have && pf_b0 == b0) {                    // its counts were produced on the second stream while the previous batch was planned
-                GS_HIP_CHECK(hipStreamWaitEvent(c->stream, ix->jev, 0));
-                pf_have = false;
             } else {
-                if (pf_have) { GS_HIP_CHECK(hipStreamSynchronize(ix->jstream)); pf_have = false; }
                 grp_b0 = grp_end = 0;
                 if ((rc = gs::dense_counts(ix, rows, nb, b0, out16, mat_ld))) return rc;
-                // a join produced on the main stream shares the query-column scratch and the column store with the next one on the second
-                // stream: that one must not start before this one is done
-                if (overlap) { GS_HIP_CHECK(hipEventRecord(ix->jev_up, c->stream)); GS_HIP_CHECK(hipStreamWaitEvent(ix->jstream, ix->jev_up, 0)); }
             }
             if (slab && ix->slabs.empty()) {                         // evicted under our feet after all: this batch's counts again, into ix->mat
                 slab = nullptr; grp_b0 = grp_end = 0;
@@ -3581,20 +3509,6 @@ static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n
         hipLaunchKernelGGL(gs::k_link_merge, dim3(std::min<uint32_t>(nb * 64u, (uint32_t)c->n_cu * 8u)), dim3(gs::LM_T), 0, c->stream, g, B, ix->inbox_cnt.as<uint32_t>(),
                            ix->inbox.as<uint64_t>(), ix->touched.as<uint32_t>(), ix->ntouched.as<uint32_t>());
         GS_HIP_CHECK(hipGetLastError());
-        // the next batch's match-join, on the second stream, while this batch's kernels run (same decision as the loop head will take)
-        if (overlap && slab && matp && gs::use_join(ix) && b0 + nb < first + n) {
-            const uint64_t b0n = b0 + nb;
-            const uint32_t nbn = (uint32_t)std::min<uint64_t>(B, first + n - b0n);
-            const bool dn = (mode == gs::MODE_DENSE) || (mode == gs::MODE_AUTO && b0n >= 4096 && nbn >= 64 && ix->insert_frac >= 0 && gs::dense_pays(ix, ix->insert_frac, nbn));
-            if (dn && !ix->slabs.empty()) {
-                c->stream = ix->jstream;
-                rc = gs::dense_counts(ix, ix->data.as<uint8_t>() + b0n * ix->stride, nbn, b0n, slab->as<uint16_t>() + (b0n - slab_first) * slab_ld, slab_ld);
-                c->stream = jguard.main;
-                if (rc) return rc;
-                GS_HIP_CHECK(hipEventRecord(ix->jev, ix->jstream));
-                pf_have = true; pf_b0 = b0n;
-            }
-        }
         // entry point: the first id of the highest new level (SPEC 5)
         for (uint32_t i = 0; i < nb; i++) if ((int)blv[i] > ix->top) { ix->top = blv[i]; ix->entry = (int64_t)(b0 + i); }
         ix->n = b0 + nb;

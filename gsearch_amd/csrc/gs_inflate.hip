@@ -57,7 +57,7 @@ struct InfLds {
     uint16_t lcnt[16], dcnt[16], ccnt[16], nextc[16], offs[16], lsorted[288], dsorted[32], csorted[20];
 };
 static __shared__ __attribute__((aligned(16))) InfLds g_inf;
-// history window of the LDS form, circular (the GWIN form of k_inflate reads its history back from the text it has written: no window)
+// history window of the LDS form, circular
 static __shared__ __attribute__((aligned(16))) uint8_t g_win[INF_WSIZE];
 
 // Canonical Huffman tables of one alphabet from its code lengths (RFC 1951 3.2.2): KIND 0 = literal/length (g_inf.lens[first ..]), 1 = distance,
@@ -202,10 +202,8 @@ __device__ __noinline__ InfBits inf_dynamic_header(InfBits B, const uint32_t *__
     return B;
 }
 
-// GWIN = false: the window in LDS (39.6 KB per member: four members per CU, ~1500 cycles per symbol). GWIN = true: no window - literals and
-// copies go straight to the text in HBM and a match reads its source back from there (through L2, past the non-coherent L1): ~2x the
-// latency per symbol, but 7.6 KB of LDS per member, so five times the members per CU interleave on the same issue slots.
-template <bool GWIN>
+// The LDS-window form: the history of a member in a circular window in LDS (39.6 KB of LDS per member: four members per CU, ~1500 cycles
+// per symbol).
 __global__ __launch_bounds__(64) void k_inflate(const uint32_t *__restrict__ comp, const InflateStream *__restrict__ sts, uint32_t n, uint8_t *__restrict__ out_all,
                                                 InflateResult *__restrict__ res)
 {
@@ -223,9 +221,7 @@ __global__ __launch_bounds__(64) void k_inflate(const uint32_t *__restrict__ com
     INF_REFILL(B);
     INF_TAKE(B, (uint32_t)(st.in_off & 3) * 8);
     uint32_t pos = 0, status = INF_OK, blocks = 0;
-    uint32_t synced = 0;                  // GWIN: every byte of the text below this position is known to have reached L2
     auto flush_half = [&](uint32_t base) {
-        if (GWIN) return;
 #pragma unroll 4
         for (uint32_t k = 0; k < INF_HALF / 1024; k++) {
             const uint32_t off = k * 1024 + lane * 16;
@@ -248,7 +244,7 @@ __global__ __launch_bounds__(64) void k_inflate(const uint32_t *__restrict__ com
             if (len > cap - pos) { status = INF_E_OUTPUT; break; }
             for (uint32_t i = 0; i < len; i++) {
                 INF_REFILL(B);
-                if (lane == 0) { if (GWIN) out[pos] = (uint8_t)B.buf; else win[pos & INF_WMASK] = (uint8_t)B.buf; }
+                if (lane == 0) win[pos & INF_WMASK] = (uint8_t)B.buf;
                 INF_TAKE(B, 8);
                 pos++;
                 if ((pos & (INF_HALF - 1)) == 0) flush_half(pos - INF_HALF);
@@ -282,7 +278,7 @@ __global__ __launch_bounds__(64) void k_inflate(const uint32_t *__restrict__ com
             const uint32_t kind = (e >> 4) & 3;
             if (kind == 0) {
                 if (pos >= cap) { status = INF_E_OUTPUT; break; }
-                if (lane == 0) { if (GWIN) out[pos] = (uint8_t)(e >> 8); else win[pos & INF_WMASK] = (uint8_t)(e >> 8); }
+                if (lane == 0) win[pos & INF_WMASK] = (uint8_t)(e >> 8);
                 pos++;
                 INF_REFILL(B);
                 e = inf_uni(g_inf.llut[(uint32_t)B.buf & ((1u << INF_LROOT) - 1)]);
@@ -307,17 +303,7 @@ __global__ __launch_bounds__(64) void k_inflate(const uint32_t *__restrict__ com
             INF_REFILL(B);
             const uint32_t e_next = g_inf.llut[(uint32_t)B.buf & ((1u << INF_LROOT) - 1)];      // in flight under the copy
             const uint32_t src0 = pos - dist;
-            if (GWIN) {
-                // the source may be bytes this wave stored a moment ago: a store is acknowledged (vmcnt) once L2 has it, and the load below
-                // goes to L2 (agent scope: not served by the CU's L1, which does not see L2 writes). Loads may overtake this wave's own stores,
-                // so every byte at or beyond `synced` (the text position at the last wait) counts as possibly in flight: wait exactly when the
-                // source reaches into that range
-                if (src0 + (dist >= len ? len : dist) > synced) { __builtin_amdgcn_s_waitcnt(0x0F70); synced = pos; }          // vmcnt(0)
-                for (uint32_t i = lane; i < len; i += 64) {
-                    const uint8_t b = __hip_atomic_load(out + src0 + (dist >= len ? i : i % dist), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    out[pos + i] = b;
-                }
-            } else if (dist >= len) {
+            if (dist >= len) {
                 for (uint32_t i = lane; i < len; i += 64) win[(pos + i) & INF_WMASK] = win[(src0 + i) & INF_WMASK];
             } else {                                          // the source runs into the target: the last `dist` bytes repeat
                 for (uint32_t i = lane; i < len; i += 64) win[(pos + i) & INF_WMASK] = win[(src0 + i % dist) & INF_WMASK];
@@ -329,7 +315,7 @@ __global__ __launch_bounds__(64) void k_inflate(const uint32_t *__restrict__ com
         }
     }
     // the tail of the text (the window half that never filled)
-    if (!GWIN && status == INF_OK) {
+    if (status == INF_OK) {
         const uint32_t base = pos & ~(INF_HALF - 1), rem = pos - base;
         for (uint32_t off = lane * 16; off < rem; off += 1024) *(uint4 *)(out + base + off) = *(const uint4 *)&win[(base + off) & INF_WMASK];
     }
@@ -340,7 +326,7 @@ __global__ __launch_bounds__(64) void k_inflate(const uint32_t *__restrict__ com
 }
 
 // ---- the window-less form with several matches in flight (round 4) ---------------------------------------------------------------------
-// What bounded k_inflate<true>: a member's 32 KB of history lives in the text it has written, 20 members per CU keep ~20 MB of history per
+// What bounded the one-match form: a member's 32 KB of history lives in the text it has written, 20 members per CU keep ~20 MB of history per
 // XCD alive against 4 MB of L2, so the source bytes of a match come back from the Infinity Cache / HBM (~1.5-2 us) - and the wave waited
 // for every one of them before it stored the copy and went on (gzip -6 of DNA is one match per ~5 bytes: ~1 460 cycles per symbol and wave
 // at the 1.5 waves per SIMD of a 6 x CUs group). Decoding does not depend on the copied bytes, only later copies may: here the wave decodes a
@@ -603,21 +589,19 @@ static bool inflate_needs_byte_stores(const InflateStream *st, uint32_t n)
     for (uint32_t i = 0; i < n; i++) if (st[i].out_off & 15) return true;
     return false;
 }
-// GS_INFLATE_WINDOW = lds | global | pipe picks the form (measurement aid / tests); by default up to four members per CU take the LDS-window form
+// GS_INFLATE_WINDOW = lds | pipe picks the form (measurement aid / tests); by default up to four members per CU take the LDS-window form
 // (lowest latency per symbol), more take the window-less form with several matches in flight, whose members interleave five times as densely
 constexpr int INF_PIPE = 8;
 static void inflate_launch_form(gs_ctx *c, hipStream_t stream, const uint32_t *comp, const InflateStream *streams_host, const InflateStream *ds, uint32_t n, uint8_t *out,
                                 InflateResult *dr)
 {
     const char *w = getenv("GS_INFLATE_WINDOW");
-    int form = n > 4u * (uint32_t)c->n_cu ? 2 : 0;                      // 0 = LDS window, 1 = window-less (one match at a time), 2 = window-less, pipelined
+    int form = n > 4u * (uint32_t)c->n_cu ? 2 : 0;                      // 0 = LDS window, 2 = window-less, pipelined
     if (w && !strcmp(w, "lds")) form = 0;
-    else if (w && !strcmp(w, "global")) form = 1;
     else if (w && !strcmp(w, "pipe")) form = 2;
     if (form == 0 && inflate_needs_byte_stores(streams_host, n)) form = 2;
     if (form == 2) hipLaunchKernelGGL(k_inflate_pipe<INF_PIPE>, dim3(n), dim3(64), 0, stream, comp, ds, n, out, dr);
-    else if (form == 1) hipLaunchKernelGGL(k_inflate<true>, dim3(n), dim3(64), 0, stream, comp, ds, n, out, dr);
-    else hipLaunchKernelGGL(k_inflate<false>, dim3(n), dim3(64), 0, stream, comp, ds, n, out, dr);
+    else hipLaunchKernelGGL(k_inflate, dim3(n), dim3(64), 0, stream, comp, ds, n, out, dr);
 }
 int inflate_streams_dev(gs_ctx *c, const void *comp_dev, const InflateStream *streams, uint32_t n, void *out_dev, InflateResult *results)
 {

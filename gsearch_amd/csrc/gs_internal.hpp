@@ -71,7 +71,6 @@ struct gs_ctx {
     // worker_unpin(): eviction only takes workers with pins == 0, and a worker whose thread exits while a snapshot still holds it is only marked
     // `orphan` - the last unpin destroys it (the LRU eviction could free a worker between worker_ctx() and the body's lock).
     int pins = 0; bool orphan = false;
-    uint32_t sketch_min_lds = 0;             // the slot-min sketch kernel asks for at least this much LDS per workgroup (co-residency shaping of the request pipeline; 0 = what it needs)
     uint32_t last_sketch[4] = {0, 0, 0, 0};   // gs_ctx_last_sketch_info: {filtered emitter, slot table in LDS, workgroups per genome, launches} of the last slot-min sketch call
     // One context = one stream and one scratch pool. The reference clones its sketcher into --nbthreads workers and calls it, DistHamming
     // and parallel_search through &self from many threads (dnasketch.rs:252,305,322): every entry point that touches the stream or the

@@ -634,7 +634,7 @@ static int launch_min(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, 
     do {                                                                                                                \
         auto kern = k_sketch_min<AAV, LDSV, ALGO, VBITS, T, FV, RC>;                                                    \
         const size_t l0_ = LDSV ? (FV ? lds_f : lds) : ((size_t)2 * m + 15) & ~(size_t)15;    /* slot table (+ survivor queues), or its 2-byte filter */  \
-        const size_t l = std::min<size_t>(std::max<size_t>(l0_, c->sketch_min_lds), 160 * 1024 - 256);                                       \
+        const size_t l = std::min<size_t>(l0_, 160 * 1024 - 256);                                                       \
         if (l > 48 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l)); \
         hipLaunchKernelGGL(kern, grid, block, l, c->stream, seq, rec_start, rec_len, rec_upre, gro, gu, kq_of(p), m, zone, tab, cap_c); \
     } while (0)
@@ -1522,7 +1522,6 @@ static int run_prob_buckets(gs_ctx *c, const gs_sketch_params *p, const uint8_t 
     GS_HIP_CHECK(hipMemsetAsync(ctr.p, 0, 64, c->stream));          // [0..1] work counter, [2] n_cand, [3] n_act, [4] n_active genomes
     uint32_t *ctr32 = ctr.as<uint32_t>();
     size_t lds = (size_t)4 * nbmax;
-    if (getenv("GS_PROB_LDS_PAD")) lds = std::max<size_t>(lds, (size_t)atoi(getenv("GS_PROB_LDS_PAD")) * 1024);     // experiment: fewer resident scatter workgroups
     {
         ProfScope ps(c, FAM_SKETCH);
         dim3 grid(parts, ng), block(PBK_T);

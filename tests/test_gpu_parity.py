@@ -988,11 +988,10 @@ def test_insert_prepass_with_split_bitmap(gpu_ctx, monkeypatch):
         assert np.array_equal(a, b)
 
 
-def test_insert_with_join_on_second_stream(gpu_ctx, monkeypatch):
-    """GS_INSERT_OVERLAP=1: the match-join of insert batch i+1 runs on a second stream under the plan / link kernels of batch i - same graph"""
+def test_dense_insert_in_two_calls_builds_the_oracle_graph(gpu_ctx, monkeypatch):
+    """dense mode, the points inserted in two calls (count rows of the insert batches produced group by group): the oracle's graph, counts included"""
     import gsearch_amd as G
     monkeypatch.setenv("GS_DIST_MODE", "dense")
-    monkeypatch.setenv("GS_INSERT_OVERLAP", "1")
     for dtype, m, M, efc, B in ((np.uint64, 120, 16, 20, 64), (np.float32, 200, 8, 40, 32)):
         db = H.synth_sig_db(30, 30, m, 8, dtype=dtype, jlo=0.05, jhi=0.95)
         oix = O.Index(dtype, m, M, efc, scale_modify=0.5, seed=3)

@@ -35,7 +35,7 @@ def separate():
     chk(lib.gs_index_parallel_search_dev(hn.h, d_qsig, nq, knbn, ef, *outs[0]))
 def fused():
     hn.sketch_and_search_dev(prm, d_seq, nq * gb + 64, d_rs, d_rl, nq, d_go, nq, knbn, ef, *outs[1], d_sig=d_qsig)
-# further arguments: environment variants of the one-call form ("GS_REQUEST_PIPELINE=3,GS_PIPE_SKETCH_LDS=102400" ...), each timed and compared with the two calls
+# further arguments: environment variants of the one-call form ("GS_REQUEST_PIPELINE=0", "GS_SEARCH_QB=4096,GS_DENSE_IMPL=tile" ...), each timed and compared with the two calls
 variants = sys.argv[4:] or [""]
 shapes = ((nq, knbn), (nq, knbn), (nq,), (nq,)); dts = (np.uint64, np.uint32, np.uint32, np.uint64)
 def timeit(fn):
