@@ -130,20 +130,29 @@ struct MinEmitF {
         two_draw(h, m, zone, o1, b);
         atomicMin(&table[b], key_of(o1));
     }
+    // key_of(o1) < thr. For the 23-bit keys, (o1 >> 41) < thr is hi32(o1) < thr << 9: one 32-bit compare instead of a shift and a compare.
+    // Only full() asks, and only while thr < direct_above() = 2^21, so thr << 9 cannot overflow.
+    static __device__ __forceinline__ bool key_below(uint64_t o1, T t)
+    {
+        if (ALGO == ALGO_SUPER2) return key_of(o1) < t;
+        return (uint32_t)(o1 >> 32) < ((uint32_t)t << 9);
+    }
     __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const { apply(elem_hash<ALGO, VBITS>(v)); }
     __device__ __forceinline__ void full(uint64_t v) const
     {
-        const uint64_t h = elem_hash<ALGO, VBITS>(v);
-        if (thr >= direct_above()) { apply(h); return; }            // wave-uniform
-        const uint64_t s0 = splitmix_mix(h + GS_GAMMA), s3 = splitmix_mix(h + 4 * GS_GAMMA);
-        const T key = key_of(rotl64(s0 + s3, 23) + s0);
-        const bool pass = key < thr;
+        // one hash chain: h + gamma straight from the element hash (gamma rides in the addend of its low v_mad_u64_u32), h + 4 gamma from
+        // that (one v_lshl_add_u64), and the queue holds h + gamma - instead of h, h + gamma and h + 4 gamma each from h (-1 mad, -1 add3)
+        uint64_t hg = elem_hash<ALGO, VBITS>(v) + GS_GAMMA;
+        asm("" : "+v"(hg));         // opaque: the compiler would otherwise rebuild h beside h + gamma and derive h + 4 gamma from h
+        if (thr >= direct_above()) { apply(hg - GS_GAMMA); return; }            // wave-uniform
+        const uint64_t s0 = splitmix_mix(hg), s3 = splitmix_mix(hg + 3 * GS_GAMMA);
+        const bool pass = key_below(rotl64(s0 + s3, 23) + s0, thr);
         const uint64_t bal = __ballot(pass);
         if (bal) {
-            if (pass) q[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = h;
+            if (pass) q[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = hg;
             qn += (uint32_t)__popcll(bal);
             if (qn >= 64) {
-                apply(q[lane]);
+                apply(q[lane] - GS_GAMMA);
                 const uint32_t rest = qn - 64;
                 const uint64_t mv = q[64 + lane];
                 if (lane < rest) q[lane] = mv;
@@ -164,13 +173,72 @@ struct MinEmitF {
     }
     __device__ __forceinline__ void finish() const
     {
-        if (lane < qn) apply(q[lane]);
+        if (lane < qn) apply(q[lane] - GS_GAMMA);
         qn = 0;
     }
 };
 template <int ALGO, int VBITS, typename T> __device__ __forceinline__ void emit_full_wave(const MinEmitF<ALGO, VBITS, T> &e, uint64_t v, uint64_t, uint64_t) { e.full(v); }
 template <int ALGO, int VBITS, typename T> __device__ __forceinline__ void emit_word_done(const MinEmitF<ALGO, VBITS, T> &e) { e.word_done(); }
 template <int ALGO, int VBITS, typename T> __device__ __forceinline__ void emit_finish(const MinEmitF<ALGO, VBITS, T> &e) { e.finish(); }
+
+// reverse complement of 32 packed bases: base i (bits 63-2i..62-2i) complemented at bits 2i+1..2i
+__device__ __forceinline__ uint64_t rc64(uint64_t x)
+{
+    const uint64_t br = __builtin_bitreverse64(x);
+    return ~(((br >> 1) & 0x5555555555555555ull) | ((br & 0x5555555555555555ull) << 1));
+}
+// The 32 windows of an interior word of a full wave by funnel shifts. With the previous word pw and the word w in front of
+// it, X = pw:w is a 64-base stream and the forward k-mer ending at base j of w is (X >> 2(31 - j)) & mask; with Y = rc(w):rc(pw) the
+// reverse-complement k-mer is (Y >> 2(33 + j - k)) & mask. Each is two v_alignbit_b32 (one per 32-bit half; one when k <= 16) and an AND,
+// with the wave-uniform shift in an SGPR, against the eight operations of the rolling update (two 64-bit shifts, the base extraction, two
+// ORs, two ANDs and the complement) - 33 instead of 42 issue cycles for window and canonical minimum at k > 16. The three 32-bit words a
+// window can touch change only at uniform points (j = 16 for the forward window, 33 + j - k crossing 16 or 32 for the reverse one): the
+// loop runs in up to four segments of fixed word roles, and the roles move down one word between segments, never per k-mer.
+// WIDE: k > 16 (a window spans both halves; the low half needs no mask). !WIDE: k <= 16 (the high half is zero).
+template <bool WIDE, int RCM, class Emit>
+__device__ __forceinline__ void walk_word_funnel(uint64_t w, uint64_t pw, uint32_t k, uint64_t mask, uint64_t rc_or, uint64_t rec, uint64_t a0,
+                                                 const Emit &emit)
+{
+    const uint32_t x0 = (uint32_t)w, x1 = (uint32_t)(w >> 32);
+    const uint64_t yl = rc64(pw), yh = rc64(w);
+    const uint32_t y0 = (uint32_t)yl, y1 = (uint32_t)(yl >> 32), y2 = (uint32_t)yh, y3 = (uint32_t)(yh >> 32);
+    const uint32_t mlo = (uint32_t)mask, mhi = (uint32_t)(mask >> 32), olo = (uint32_t)rc_or, ohi = (uint32_t)(rc_or >> 32);
+    // forward roles for j < 16: the window starts in word 1 of X (words 0..3 = low w, high w, low pw, high pw)
+    uint32_t f0 = x1, f1 = (uint32_t)pw, f2 = (uint32_t)(pw >> 32);
+    // reverse roles: the window at j starts in word (33 + j - k) >> 4 of Y (words 0..3 = low rc(pw) .. high rc(w), 4 and 5 zero)
+    uint32_t t = 33 - k, qy = t >> 4;                      // 1 <= t <= 32: qy in 0..2
+    uint32_t r0 = qy == 0 ? y0 : qy == 1 ? y1 : y2, r1 = qy == 0 ? y1 : qy == 1 ? y2 : y3, r2 = qy == 0 ? y2 : qy == 1 ? y3 : 0u;
+    uint32_t j = 0;
+    for (;;) {
+        const uint32_t je = min(j < 16 ? 16u : 32u, j + 16 - (t & 15));
+        for (; j < je; j++, t++) {
+            const uint32_t sf = 62 - 2 * j, sr = 2 * t;    // alignbit takes the shift mod 32
+            uint64_t v;
+            if (WIDE) {
+                const uint32_t fl = __builtin_amdgcn_alignbit(f1, f0, sf), fh = __builtin_amdgcn_alignbit(f2, f1, sf) & mhi;
+                if (RCM == 1) v = ((uint64_t)fh << 32) | fl;
+                else {
+                    uint32_t rl = __builtin_amdgcn_alignbit(r1, r0, sr), rh = __builtin_amdgcn_alignbit(r2, r1, sr) & mhi;
+                    if (RCM == 2) { rl |= olo; rh |= ohi; }
+                    const uint64_t fw = ((uint64_t)fh << 32) | fl, rc = ((uint64_t)rh << 32) | rl;
+                    v = fw < rc ? fw : rc;
+                }
+            } else {
+                const uint32_t fl = __builtin_amdgcn_alignbit(f1, f0, sf) & mlo;
+                if (RCM == 1) v = fl;
+                else {
+                    uint32_t rl = __builtin_amdgcn_alignbit(r1, r0, sr) & mlo;
+                    if (RCM == 2) rl |= olo;
+                    v = min(fl, rl);
+                }
+            }
+            emit_full_wave(emit, v, rec, a0 + j);
+        }
+        if (j == 32) break;
+        if (j == 16) { f2 = f1; f1 = f0; f0 = x0; }
+        if ((t & 15) == 0) { r0 = r1; r1 = r2; r2 = qy == 0 ? y3 : 0u; qy++; }
+    }
+}
 
 // The streaming part shared by every sketcher. walk_unit: flat unit f of a genome (32 symbols: one packed word of DNA, 32 bytes of AA) ->
 // emit(v) for each valid canonical k-mer value that starts... ends in it; walk_genome: the units of genome g assigned to this workgroup.
@@ -194,17 +262,15 @@ __device__ __forceinline__ void walk_unit(const uint8_t *__restrict__ seq, const
         if (!AA) {
             const uint64_t *w64 = (const uint64_t *)seq;
             uint64_t w = __builtin_bswap64(w64[u]);
-            uint64_t fwd = 0, rc = 0;
+            uint64_t fwd = 0, rc = 0, pw = 0;
             if (a0 > rb && k > 1) {
                 // the state after the k-1 bases in front of this word, in closed form (round 5: the loop over them - k-1 = 20 trips of ~9 instructions per 32 k-mers -
                 // was 5.6 of the ~82 VALU instructions per k-mer): the forward window is the low 2(k-1) bits of the previous word; the reverse-complement
                 // register holds base i of those k-1 at bit 2i, complemented - the 2-bit groups in reverse order, one group up
-                const uint64_t pw = __builtin_bswap64(w64[u - 1]);
+                pw = __builtin_bswap64(w64[u - 1]);
                 const uint64_t lowm = ((uint64_t)1 << (2 * (k - 1))) - 1;            // k - 1 <= 31
                 fwd = pw & lowm;
-                uint64_t br = __builtin_bitreverse64(fwd);
-                br = ((br >> 1) & 0x5555555555555555ull) | ((br & 0x5555555555555555ull) << 1);      // bit order inside each group back
-                rc = (((~(br >> (2 * (33 - k)))) & lowm) << 2) | rc_or;
+                rc = ((rc64(pw) >> (2 * (33 - k))) << 2) | rc_or;                    // the top 2(k - 1) bits of rc64(pw): the last k - 1 bases
             }
             // (rc never exceeds 2k bits and fwd is masked every step: the minimum needs no further mask.) When every lane of the wave
             // holds an interior word - all 32 windows inside its record, the case for all but the first and last word of a record - the
@@ -212,13 +278,9 @@ __device__ __forceinline__ void walk_unit(const uint8_t *__restrict__ seq, const
             const bool interior = a0 >= first_valid && a0 + 32 <= re;
             const uint64_t bint = __ballot(interior);
             if (bint == ~(uint64_t)0) {                      // all 64 lanes: emitters that compact across the wave may do so
-#pragma unroll 2
-                for (uint32_t j = 0; j < 32; j++) {
-                    uint64_t c = w >> 62; w <<= 2;
-                    fwd = ((fwd << 2) | c) & mask;
-                    rc = (rc >> 2) | ((3 - c) << rcshift) | rc_or;
-                    emit_full_wave(emit, fwd < rc ? fwd : rc, lo, a0 + j);
-                }
+                // (k > 1 here: pw is the previous word; k = 1: pw = 0, whose bases no window reaches)
+                if (k > 16) walk_word_funnel<true, RCM>(w, pw, k, mask, rc_or, lo, a0, emit);
+                else walk_word_funnel<false, RCM>(w, pw, k, mask, rc_or, lo, a0, emit);
                 emit_word_done(emit);
             } else if (bint == __ballot(true)) {
 #pragma unroll 2
@@ -1802,9 +1864,7 @@ __global__ __launch_bounds__(PT_T) void k_prob_part1_dna(const uint8_t *__restri
                 const uint64_t pw = __builtin_bswap64(cur.pw);
                 const uint64_t lowm = ((uint64_t)1 << (2 * (k - 1))) - 1;
                 fwd = pw & lowm;
-                uint64_t br = __builtin_bitreverse64(fwd);
-                br = ((br >> 1) & 0x5555555555555555ull) | ((br & 0x5555555555555555ull) << 1);
-                rc = (((~(br >> (2 * (33 - k)))) & lowm) << 2) | rc_or;
+                rc = ((rc64(pw) >> (2 * (33 - k))) << 2) | rc_or;
             }
             const bool have = cur.jhi > cur.jlo, full = cur.jlo == 0 && cur.jhi == 32;
             if (__ballot(full) == __ballot(true)) pt_walk_dna<false>(w, fwd, rc, mask, rcshift, rc_or, 0, 32, sh, lg, idmask, s_cnt, idr, pkr);      // (wavefront-uniform)

@@ -10,7 +10,21 @@
 
 namespace gs {
 
-GS_HD uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+GS_HD uint64_t rotl64(uint64_t x, int r)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    // two v_alignbit_b32 (one funnel shift per half) instead of the v_lshlrev_b64 + v_lshrrev_b32 + v_or_b32 the compiler picks for the
+    // constant rotates of xoshiro (23, 45)
+    if (__builtin_constant_p(r) && r > 0 && r < 64 && r != 32) {
+        const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+        const uint32_t a = r < 32 ? hi : lo, b = r < 32 ? lo : hi, s = 32 - (r & 31);
+        uint64_t y = ((uint64_t)__builtin_amdgcn_alignbit(a, b, s) << 32) | __builtin_amdgcn_alignbit(b, a, s);
+        asm("" : "+v"(y));          // keep the result one 64-bit value: otherwise `rotl64(x, r) + y` is split into a 32-bit add, a move and a 64-bit add
+        return y;
+    }
+#endif
+    return (x << r) | (x >> (64 - r));
+}
 GS_HD uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
 // fxhash::FxHasher64 over one integer write
