@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the sketch-and-query hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sketch|request] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sketch|request] [--dump-outputs DIR] [--full]
 
 One rank per GPU. `python bench.py --gpus N` starts the N ranks itself (gsearch_amd.sharding.ensure_launched re-executes this
 script under torch.distributed.run on 127.0.0.1); when a launcher already set RANK/WORLD_SIZE the script is one of its ranks.
@@ -11,7 +11,9 @@ A *step* is one pass of the hot path over one batch of synthetic input that is a
           against a 300k-genome OptDens HNSW built on the GPU from synthetic genomes during (untimed) setup.
   sketch  (BASELINE.json configs[1]): 10k synthetic 5 Mbp genomes, k=21, s=18000, --algo optdens, per rank.
 
-Rank 0 prints ONE JSON line (metric/value/... plus `roofline`, `kernels` and `cpu_baseline`; DESIGN.md "measurement").
+Rank 0 prints ONE JSON line (metric/value/... plus `roofline` and `kernels` of the timed steps; DESIGN.md "measurement").
+A plain run sets up, warms up, times the steps, dumps them when asked and prints that line. `--full` adds everything that takes runs
+of its own after the timed region: the oracle parity sample and `cpu_baseline`, the gather-mode roofline and the side legs.
 Every kernel is priced against the ceiling of its real class: HBM bytes for the row-gather distance kernel,
 memory-side atomics/s for the match-join, VALU issue for the sketch kernel, and for the latency-bound dense traversal its
 algorithmic bytes (adjacency rows + 2-byte count lookups) against HBM peak next to pops/s.
@@ -370,19 +372,22 @@ def run_sketch(args, D):
                            "algorithmic_bytes_per_launch": alg_bytes_launch, "kmers_per_sec_kernel": kps, "class": "valu",
                            "note": "hash-bound kernel: 0.264 B of HBM traffic per k-mer; the binding resource is VALU issue (valu_model)"}
         out["roofline"]["valu_model"] = sketch_valu_model(kps)
-        # parity spot check + CPU baseline (oracle = checker / baseline only, never the measured path)
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import oracle_lib as O
-        op = O.params(k, m, "optdens")
-        sig_dev = ctx.download(d_sig, (ng, m), np.float32)
-        chk = [0, ng - 1] if ng > 1 else [0]
-        ok = True
-        for g in chk:
-            pk = np.concatenate([synth_genome_packed(args.seed, first + g, L), np.zeros(16, np.uint8)])
-            ref = O.sketch_batch(op, pk, np.zeros(1, np.uint64), np.array([L], np.uint64), np.array([0, 1], np.uint64))
-            ok &= bool(np.array_equal(ref.view(np.uint32)[0], sig_dev.view(np.uint32)[g]))
-        out["parity_checked"] = {"genomes": chk, "bit_exact_vs_oracle": ok}
-        out["cpu_baseline"] = cpu_sketch_baseline(O, op, args, kmers_per_genome, words, host_cpu_budget()[1]) if (D.world == 1 and not args.no_cpu_baseline) else None
+        out["cpu_baseline"] = None
+        if args.full:
+            # parity spot check + CPU baseline (oracle = checker / baseline only, never the measured path)
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import oracle_lib as O
+            op = O.params(k, m, "optdens")
+            sig_dev = ctx.download(d_sig, (ng, m), np.float32)
+            chk = [0, ng - 1] if ng > 1 else [0]
+            ok = True
+            for g in chk:
+                pk = np.concatenate([synth_genome_packed(args.seed, first + g, L), np.zeros(16, np.uint8)])
+                ref = O.sketch_batch(op, pk, np.zeros(1, np.uint64), np.array([L], np.uint64), np.array([0, 1], np.uint64))
+                ok &= bool(np.array_equal(ref.view(np.uint32)[0], sig_dev.view(np.uint32)[g]))
+            out["parity_checked"] = {"genomes": chk, "bit_exact_vs_oracle": ok}
+            if D.world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_sketch_baseline(O, op, args, kmers_per_genome, words, host_cpu_budget()[1])
         print(json.dumps(out))
     for p in (d_seq, d_sig, d_rs, d_rl, d_goff):
         ctx.free(p)
@@ -610,7 +615,7 @@ def run_request(args, D):
         out.update(request_accounting(args, ctx, hn, lib, chk, torch, D, dict(
             srch=(srch_ms, srch_n), tile=(tile_ms, tile_n), sk=(sk_ms, sk_n), stats=st, evals_total=evals_total, d_qsig=d_qsig, ids_t=ids_t,
             dist_t=dist_t, cnt_t=cnt_t)))
-        if D.world > 1 or args.no_cpu_baseline:                # parity sample and CPU baseline: rank 0 at N=1 only
+        if not args.full or D.world > 1 or args.no_cpu_baseline:   # parity sample and CPU baseline: --full, rank 0 at N=1 only
             out["cpu_baseline"] = None
         else:
             par, oix = request_parity_and_cpu(args, ctx, hn, d_qsig, d_qseq, ids_t, dist_t, ev_t, nsteps_q, gbytes, words)
@@ -621,7 +626,7 @@ def run_request(args, D):
                 except Exception as e:                          # the headline line must survive a failing side leg
                     out["request_redundant"] = {"error": repr(e)}
             del oix
-        if D.world == 1 and not args.no_extra_legs:
+        if args.full and D.world == 1 and not args.no_extra_legs:
             try:
                 out["extra_legs"] = extra_legs(args, ctx, lib, chk, d_qseq, gbytes, words, d_rs, d_rl, d_goff)
             except Exception as e:                              # the headline line must survive a failing side leg
@@ -726,12 +731,14 @@ def request_accounting(args, ctx, hn, lib, chk, torch, D, r):
                        "traffic": dom.get("traffic"), "kernel": dom["kernel"], "class": dom.get("class"), "avg_launch_ms": dom["avg_launch_ms"], "launches": dom["launches"],
                        "algorithmic_bytes_per_launch": dom["algorithmic_bytes_per_launch"],
                        "note": "dominant kernel of the step by summed launch time; `achieved` = its algorithmic bytes / measured launch time (HIP events). "
-                               "`class` names the resource that really binds it (see `kernels`); the HBM-bound distance kernel of the north star is `roofline_gather_mode`"}
+                               "`class` names the resource that really binds it (see `kernels`); the HBM-bound distance kernel of the north star is `roofline_gather_mode` (--full)"}
     if dom.get("traffic"):
         out["roofline"]["traffic_GBps"] = dom["traffic"] / (dom["avg_launch_ms"] * 1e-3) / 1e9
         out["roofline"]["traffic_over_algorithmic"] = dom["traffic"] / dom["algorithmic_bytes_per_launch"] if dom["algorithmic_bytes_per_launch"] else None
     out["roofline"]["traffic_source"] = pmc_source()
     out["roofline"]["traffic_rule"] = dom.get("traffic_rule", "2 x FETCH_SIZE + WRITE_SIZE (coalesced streams are tallied at half: profiles/r03_fetchcal.txt)")
+    if not args.full:                                             # the gather-mode search below is a run of its own
+        return out
     # the row-streaming (gather) form of the same search on a sub-batch: the HBM-bound DistHamming kernel the north star prices
     # against the HBM roofline (>= 40 % target); results are identical, only the evaluation strategy differs
     ng_q = min(256, qps)
@@ -1334,9 +1341,11 @@ def main():
     ap.add_argument("--redundant-roots", type=int, default=30, help="families the queries of the `request_redundant` side leg are drawn from (0 = skip the leg)")
     ap.add_argument("--cpu-sample-queries", type=int, default=128)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the post-run legs (other sketchers, configs[4], gz ingest)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run what takes runs of its own: the oracle parity sample and CPU baseline, "
+                                                        "the gather-mode roofline and the side legs (redundant, other sketchers, configs[4], gz ingest, prob, skewed)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the post-run legs (other sketchers, configs[4], gz ingest)")
     ap.add_argument("--ingest-files", type=int, default=4096, help="gz FASTA files of the file-inclusive ingest leg (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle parity sample + CPU baseline leg (profiling passes: ~2 min of host work per run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle parity sample + CPU baseline leg (profiling passes: ~2 min of host work per run)")
     ap.add_argument("--selftest-launch", action="store_true", help="GPU-free check of the N-rank launch + single all-gather (gloo, stub searcher)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all; larger outputs "

@@ -76,10 +76,35 @@ def test_bench_request_dump_is_the_last_step_and_repeatable(tmp_path):
 def test_bench_sketch_dump_holds_the_signatures(tmp_path):
     d = str(tmp_path / "sk")
     out = _bench(["--gpus", "1", "--workload", "sketch", "--steps", "2", "--warmup", "1", "--genomes", "64", "--genome-len", "1000000",
-                  "--no-cpu-baseline", "--dump-outputs", d])
+                  "--full", "--no-cpu-baseline", "--dump-outputs", d])
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["parity_checked"]["bit_exact_vs_oracle"]
     z = _load(d)
     assert z["signatures"].dtype == np.float32 and z["signatures"].shape == (64, 18000) and np.array_equal(z["signatures_rows"], np.arange(64))
     assert np.all(np.isfinite(z["signatures"]))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_leaves_the_checks_to_full(tmp_path):
+    """a plain run times the steps and dumps them, nothing else: the oracle parity sample, the CPU baseline, the gather-mode roofline and the
+    side legs run with --full only, after the same timed steps (same dumped outputs)"""
+    small = [a for a in SMALL_REQUEST if a not in ("--no-extra-legs", "--no-cpu-baseline")]
+    res = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-extra-legs"])):
+        d = str(tmp_path / mode)
+        out = _bench(small + extra + ["--dump-outputs", d])
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-3000:]
+        res[mode] = (json.loads(lines[0]), _load(d))
+    (p, pz), (f, fz) = res["plain"], res["full"]
+    for r in (p, f):
+        assert r["metric"] == "query genomes/sec" and r["unit"] == "genomes/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+        assert r["steps"] == 3 and len(r["step_ms"]) == 3 and r["ms_per_step"] > 0 and r["value"] > 0 and r["kernels"]
+    assert p["cpu_baseline"] is None
+    assert not any(k in p for k in ("parity_checked", "roofline_gather_mode", "request_redundant", "extra_legs", "request_skewed"))
+    assert f["cpu_baseline"]["value"] > 0 and f["roofline_gather_mode"]["same_answers_as_dense"]
+    pc = f["parity_checked"]
+    assert pc["sketch_bit_exact_vs_oracle"] and pc["neighbour_ids_and_distances_equal_oracle"] and pc["dist_evaluation_counts_equal_oracle"]
+    assert sorted(pz) == sorted(fz) and all(np.array_equal(pz[k], fz[k]) for k in pz)
