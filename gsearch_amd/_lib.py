@@ -9,7 +9,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("GS_LIB_PATH") or os.path.join(_HERE, "libgsearch_amd.so")      # GS_LIB_PATH: A/B builds (tools/ only)
 
 GS_OK, GS_ERR_INVALID, GS_ERR_HIP, GS_ERR_UNSUPPORTED, GS_ERR_STATE, GS_ERR_IO = 0, -1, -2, -3, -4, -5
-ALGO = {"prob": 0, "super": 1, "super2": 2, "hll": 3, "optdens": 4, "revoptdens": 5}
+ALGO = {"prob": 0, "super": 1, "super2": 2, "hll": 3, "optdens": 4, "revoptdens": 5, "hmh": 6}   # hmh: HyperMinHash of hypermash (SPEC 7)
+HMH_REGISTERS = 16384
 DATA = {"dna": 0, "aa": 1, "dna_fwd": 2}   # dna_fwd: forward window, no reverse-complement minimum (bindash.rs:346-354, k <= 14)
 KIND_U16, KIND_U32, KIND_U64, KIND_F32 = 0, 1, 2, 3
 
@@ -76,6 +77,13 @@ SYMBOLS = {
     "gs_hamming_qxc_dev": (_i, [_vp, _i, _u32, _vp, _u64, _vp, _u64, _vp]),
     "gs_hamming_pairs": (_i, [_vp, _i, _u32, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp]),
     "gs_ani": (C.c_double, [C.c_double, _i, _i]),
+    "gs_hmh_cardinality": (_i, [_vp, _vp, _u64, _vp]),
+    "gs_hmh_cardinality_dev": (_i, [_vp, _vp, _u64, _vp]),
+    "gs_hmh_similarity_qxc": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
+    "gs_hmh_similarity_qxc_dev": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
+    "gs_hmh_distance": (C.c_double, [C.c_double, _i]),
+    "gs_fastq_scan": (_i, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "gs_hmh_sketch_files": (_i, [_vp, _u32, C.POINTER(C.c_char_p), _u64, _u32, _vp, _vp, _vp, _vp]),
     "gs_index_create": (_i, [_vp, C.POINTER(IndexParams), C.POINTER(_vp)]),
     "gs_index_destroy": (None, [_vp]),
     "gs_index_nb_point": (_u64, [_vp]),

@@ -458,11 +458,131 @@ class HyperLogLogSketch(_SeqSketcher):
     ALGO_NAME = "hll"
 
 
+class HyperMinHashSketch(_SeqSketcher):
+    """hyperminhash::Sketch as hypermash builds it (src/bin/hypermash.rs:115-250): 16384 u16 registers of canonical DNA k-mers, k in 1..32
+    (15 accepted). Arithmetic: SPEC 7. `HyperMinHashSketch.new(SeqSketcherParams(k, 16384, "hmh"))` or `HyperMinHashSketch.for_k(k)`."""
+    ALGO_NAME = "hmh"
+
+    @classmethod
+    def for_k(cls, k, ctx=None):
+        return cls(SeqSketcherParams(k, _lib.HMH_REGISTERS, "hmh"), ctx)
+
+    def sketch_files(self, paths, threads=0):
+        """one sketch per file with hypermash's reader rules: FASTA or FASTQ (plain / gz / bz2 / xz; zstd is refused), no capsid filter,
+        records of <= k bases skipped. -> ((n_files, 16384) uint16, records kept per file, bases sketched per file, stats dict)"""
+        paths = [str(x).encode() for x in paths]
+        n = len(paths)
+        arr = (C.c_char_p * max(n, 1))(*paths)
+        out = np.zeros((n, _lib.HMH_REGISTERS), dtype=np.uint16)
+        nrec, nb, st = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), np.zeros(4, np.float64)
+        check(self.ctx.L.gs_hmh_sketch_files(self.ctx.h, self.params.c.k, arr, n, int(threads), _p(out), _p(nrec), _p(nb), _p(st)))
+        return out, nrec[:n], nb[:n], {"host_read_decode_scan_s": st[0], "pcie_wait_s": st[1], "device_s": st[2], "wall_s": st[3]}
+
+
 def sketcher_for(params, ctx=None):
-    """(algo) dispatch of dna_process_tohnsw (dnasketch.rs:493-644)."""
+    """(algo) dispatch of dna_process_tohnsw (dnasketch.rs:493-644); hmh: hypermash's sketcher."""
     table = {ALGO["optdens"]: OptDensHashSketch, ALGO["revoptdens"]: RevOptDensHashSketch, ALGO["prob"]: ProbHash3aSketch,
-             ALGO["super"]: SuperHashSketch, ALGO["super2"]: SuperHash2Sketch, ALGO["hll"]: HyperLogLogSketch}
+             ALGO["super"]: SuperHashSketch, ALGO["super2"]: SuperHash2Sketch, ALGO["hll"]: HyperLogLogSketch, ALGO["hmh"]: HyperMinHashSketch}
     return table[params.c.algo](params, ctx)
+
+
+def _hmh_rows(a):
+    a = np.ascontiguousarray(a, dtype=np.uint16)
+    if a.ndim == 1:
+        a = a.reshape(1, -1)
+    if a.ndim != 2 or a.shape[1] != _lib.HMH_REGISTERS:
+        raise GsError(_lib.GS_ERR_INVALID, "HyperMinHash sketches have %d registers" % _lib.HMH_REGISTERS)
+    return a
+
+
+def hmh_cardinality(sigs, ctx=None):
+    """Sketch::cardinality of each row of an (n, 16384) uint16 array -> uint64 array (SPEC 7, bit-exact)"""
+    ctx = ctx or default_context()
+    a = _hmh_rows(sigs)
+    out = np.zeros(len(a), np.uint64)
+    check(ctx.L.gs_hmh_cardinality(ctx.h, _p(a), len(a), _p(out)))
+    return out
+
+
+def hmh_cardinality_dev(ctx, sigs_dev, n, card_out_dev):
+    check(ctx.L.gs_hmh_cardinality_dev(ctx.h, sigs_dev, int(n), card_out_dev))
+
+
+def hmh_similarity_qxc(Q, R, ctx=None):
+    """Sketch::similarity of every (query, reference) pair -> (nq, nr) float64 (SPEC 7)"""
+    ctx = ctx or default_context()
+    q, r = _hmh_rows(Q), _hmh_rows(R)
+    out = np.zeros((len(q), len(r)), np.float64)
+    check(ctx.L.gs_hmh_similarity_qxc(ctx.h, _p(q), len(q), _p(r), len(r), _p(out)))
+    return out
+
+
+def hmh_similarity_qxc_dev(ctx, Q_dev, nq, R_dev, nr, sim_out_dev):
+    check(ctx.L.gs_hmh_similarity_qxc_dev(ctx.h, Q_dev, int(nq), R_dev, int(nr), sim_out_dev))
+
+
+def hypermash_distance(sim, kmer_size):
+    """hypermash.rs:261-263: 1 - (2 sim / (1 + sim))^(1/k), f64"""
+    return _lib.load().gs_hmh_distance(float(sim), int(kmer_size))
+
+
+def fastq_scan(text):
+    """record boundaries of a FASTQ text (bytes): list of (id, seq_begin, seq_end); a truncated or malformed record raises (GS_ERR_IO)"""
+    L = _lib.load()
+    buf = np.frombuffer(text, dtype=np.uint8)
+    n = C.c_uint64()
+    check(L.gs_fastq_scan(_p(buf) if len(buf) else None, len(buf), 0, None, None, None, None, C.byref(n)))
+    nr = n.value
+    sb, se, ib = np.zeros(nr, np.uint64), np.zeros(nr, np.uint64), np.zeros(nr, np.uint64)
+    il = np.zeros(nr, np.uint32)
+    check(L.gs_fastq_scan(_p(buf) if len(buf) else None, len(buf), nr, _p(sb), _p(se), _p(ib), _p(il), C.byref(n)))
+    return [(bytes(text[int(ib[i]):int(ib[i]) + int(il[i])]).decode("ascii", "replace"), int(sb[i]), int(se[i])) for i in range(nr)]
+
+
+def read_path_list(path):
+    """hypermash.rs:103-108: the lines of a list file (line breaks stripped), blank lines dropped"""
+    with open(path, "rb") as f:
+        lines = f.read().decode("utf-8").split("\n")
+    lines = [x[:-1] if x.endswith("\r") else x for x in lines]
+    return [x for x in lines if x.strip()]
+
+
+def write_hypermash_tsv(query_paths, ref_paths, dist, out):
+    """hypermash.rs:265-275: `Query\tReference\tDistance`, then one row per pair with six decimals; 0 when the two paths share a file name.
+    Rows query-major in the order given [CHOICE: upstream's order is a HashMap's]."""
+    import os
+    out.write("Query\tReference\tDistance\n")
+    for i, q in enumerate(query_paths):
+        qb = os.path.basename(q)
+        for j, r in enumerate(ref_paths):
+            d = 0.0 if qb == os.path.basename(r) else float(dist[i, j])
+            out.write("%s\t%s\t%.6f\n" % (q, r, d))
+
+
+def hypermash(query_paths, ref_paths, k, out, threads=0, ctx=None):
+    """hypermash (src/bin/hypermash.rs): HyperMinHash sketches of every query and reference file, the similarity of every pair on the device,
+    distance 1 - (2 sim / (1 + sim))^(1/k), written as upstream's TSV to `out` (a path or a text stream). A path listed twice is sketched once,
+    as upstream's map does. Returns the (nq, nr) distance matrix."""
+    def uniq(xs):
+        seen, res = set(), []
+        for x in xs:
+            if x not in seen:
+                seen.add(x)
+                res.append(x)
+        return res
+    qp, rp = uniq([str(x) for x in query_paths]), uniq([str(x) for x in ref_paths])
+    sk = HyperMinHashSketch.for_k(k, ctx)
+    qs = sk.sketch_files(qp, threads=threads)[0]
+    rs = sk.sketch_files(rp, threads=threads)[0]
+    sim = hmh_similarity_qxc(qs, rs, sk.ctx) if len(qp) and len(rp) else np.zeros((len(qp), len(rp)))
+    with np.errstate(invalid="ignore"):
+        dist = 1.0 - np.power(2.0 * sim / (1.0 + sim), 1.0 / float(k))
+    if isinstance(out, (str, bytes)) or hasattr(out, "__fspath__"):
+        with open(out, "w") as f:
+            write_hypermash_tsv(qp, rp, dist, f)
+    else:
+        write_hypermash_tsv(qp, rp, dist, out)
+    return dist
 
 
 # ----------------------------------------------------------------------------------------------------------

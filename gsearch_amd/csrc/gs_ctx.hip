@@ -338,7 +338,14 @@ int gs_check_params(const gs_sketch_params *p)
 {
     GS_REQUIRE(p, GS_ERR_INVALID, "null params");
     GS_REQUIRE(p->sketch_size >= 2, GS_ERR_INVALID, "sketch_size must be >= 2");
-    GS_REQUIRE(p->algo <= GS_ALGO_REVOPTDENS, GS_ERR_INVALID, "unknown sketch algo %u", p->algo);
+    GS_REQUIRE(p->algo <= GS_ALGO_HMH, GS_ERR_INVALID, "unknown sketch algo %u", p->algo);
+    if (p->algo == GS_ALGO_HMH) {
+        // hypermash (src/bin/hypermash.rs:115-185): 16384 u16 registers of canonical DNA k-mers; k = 15 takes the Kmer64bit branch there (:160)
+        GS_REQUIRE(p->sketch_size == GS_HMH_REGISTERS, GS_ERR_INVALID, "hmh sketch_size must be %u", (unsigned)GS_HMH_REGISTERS);
+        GS_REQUIRE(p->data_t == GS_DATA_DNA, GS_ERR_INVALID, "hmh sketches canonical DNA only");
+        GS_REQUIRE(p->k >= 1 && p->k <= 32, GS_ERR_INVALID, "DNA kmer size must be in 1..32");
+        return GS_OK;
+    }
     if (p->data_t == GS_DATA_DNA || p->data_t == GS_DATA_DNA_FWD) {
         GS_REQUIRE(p->k >= 1 && p->k <= 32, GS_ERR_INVALID, "DNA kmer size must be in 1..32");
         GS_REQUIRE(p->k != 15, GS_ERR_INVALID, "kmer size 15 is rejected (dnarequest.rs:451-454)");
@@ -361,6 +368,7 @@ int gs_sig_kind(const gs_sketch_params *p)
     case GS_ALGO_PROB3A: return vb == 32 ? GS_KIND_U32 : GS_KIND_U64;
     case GS_ALGO_SUPER2: return vb == 32 ? GS_KIND_U32 : GS_KIND_U64;
     case GS_ALGO_HLL: return GS_KIND_U16;
+    case GS_ALGO_HMH: return GS_KIND_U16;
     default: return GS_KIND_F32;
     }
 }

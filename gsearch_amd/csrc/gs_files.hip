@@ -247,6 +247,7 @@ struct FileBlob {       // one file after the host stage
     struct GzBlock { uint32_t in_off, in_len, out_off, isize, trailer; };
     bool want_bgzf = false; std::vector<GzBlock> blocks;
     std::vector<uint64_t> sb, se; int rc = GS_OK; std::string err; double read_s = 0;
+    uint32_t hmh_k = 0;                   // != 0: hypermash's reader rules (scan_records_hmh) for k-mers of this size
 };
 static bool has_compressed_suffix(const char *path)
 {
@@ -265,6 +266,41 @@ static int scan_records(const uint8_t *text, size_t n, std::vector<uint64_t> &sb
         cap = nr;
     }
     sb.resize(nr); se.resize(nr);
+    return GS_OK;
+}
+// hypermash's reader (src/bin/hypermash.rs:115-185, needletail): FASTA or FASTQ by the first non-blank byte, no capsid filter, records whose
+// sequence (line breaks not counted) has <= k bytes skipped (:127). A zstd stream is refused: there is no zstd decoder here.
+static uint64_t seq_len_no_eol(const uint8_t *t, uint64_t b, uint64_t e)
+{
+    uint64_t len = 0;
+    while (b < e) {
+        const uint8_t *nl = (const uint8_t *)memchr(t + b, '\n', e - b);
+        const uint64_t le = nl ? (uint64_t)(nl - t) : e;
+        len += le - b - (le > b && t[le - 1] == '\r' ? 1 : 0);
+        b = nl ? le + 1 : e;
+    }
+    return len;
+}
+static int scan_records_hmh(const uint8_t *text, size_t n, uint32_t k, std::vector<uint64_t> &sb, std::vector<uint64_t> &se)
+{
+    GS_REQUIRE(!(n >= 4 && text[0] == 0x28 && text[1] == 0xB5 && text[2] == 0x2F && text[3] == 0xFD), GS_ERR_UNSUPPORTED, "zstd input is not supported");
+    size_t i = 0;
+    while (i < n && (text[i] == '\n' || text[i] == '\r' || text[i] == ' ' || text[i] == '\t')) i++;
+    uint64_t nr = 0;
+    int rc;
+    if (i < n && text[i] == '@') {
+        if ((rc = gs_fastq_scan((const char *)text, n, 0, nullptr, nullptr, nullptr, nullptr, &nr))) return rc;
+        sb.resize(nr); se.resize(nr);
+        if ((rc = gs_fastq_scan((const char *)text, n, nr, sb.data(), se.data(), nullptr, nullptr, &nr))) return rc;
+    } else {
+        if ((rc = gs_fasta_scan((const char *)text, n, 0, 0, nullptr, nullptr, nullptr, nullptr, &nr))) return rc;
+        sb.resize(nr); se.resize(nr);
+        if ((rc = gs_fasta_scan((const char *)text, n, 0, nr, sb.data(), se.data(), nullptr, nullptr, &nr))) return rc;
+    }
+    size_t w = 0;
+    for (size_t r = 0; r < nr; r++)
+        if (seq_len_no_eol(text, sb[r], se[r]) > k) { sb[w] = sb[r]; se[w] = se[r]; w++; }
+    sb.resize(w); se.resize(w);
     return GS_OK;
 }
 // BGZF signature of a gzip member header: FEXTRA set and a 'B','C' subfield of two bytes (SAM/BAM spec 4.1); returns the member's total size
@@ -365,7 +401,7 @@ static void host_stage(const char *path, FileBlob *b)
         b->rc = read_fasta(path, b->text);
         text = b->text.data(); n = b->text.size();
     }
-    if (b->rc == GS_OK) b->rc = scan_records(text, n, b->sb, b->se);
+    if (b->rc == GS_OK) b->rc = b->hmh_k ? scan_records_hmh(text, n, b->hmh_k, b->sb, b->se) : scan_records(text, n, b->sb, b->se);
     if (b->rc) b->err = gs_last_error();                          // thread-local: carry it to the caller's thread
     b->read_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -436,6 +472,7 @@ int gs_list_fasta_files(const char *dir, int data_t, char *paths_buf, uint64_t c
  * One signature per file, in input order, for n_files FASTA files (plain, .gz, .bz2, .xz):
  *   block_mode 0  by sequence: every record is its own sequence, k-mers never span records (process_file_by_sequence)
  *   block_mode 1  --block: the records of a file are concatenated, k-mers span the joins (process_file_in_one_block)
+ *   block_mode 2  (internal, gs_hmh_sketch_files) by sequence, with hypermash's reader rules: FASTA or FASTQ, no capsid filter, records of <= k bases skipped
  * `capsid` records are skipped in both (dnafiles.rs:62-67,245). pio = files per group (`--pio`, files.rs:258-341; 0 -> 64),
  * n_threads = host threads that read / decompress / scan (0 -> hardware concurrency).
  * sig_out: HOST, n_files x sketch_size elements. n_records_out / n_symbols_out (optional, HOST, per file): records kept and bases /
@@ -553,6 +590,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
             if (take < cnt) { f1 -= cnt - take; n_groups_eff = std::min<uint64_t>(n_groups_eff, f1 > f0 ? g + 1 : g); }
         }
         blobs[g].resize(f1 - f0);
+        if (block_mode == 2) for (auto &fb : blobs[g]) fb.hmh_k = p->k;
         if (f1 == f0) return;
         {   // size the plain files and give each its place in this group's pinned buffer (its previous user, group g-4, is long done)
             const int sl = (int)(g % NSLOT);
@@ -850,7 +888,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
         if ((rc2 = dout.ensure(out_bytes))) return rc2;
         GS_HIP_CHECK(hipMemsetAsync(dout.p, 0, out_bytes, c->stream));
         std::vector<uint64_t> rs(std::max<uint64_t>(nrec, 1)), rl(std::max<uint64_t>(nrec, 1)), goff(nf + 1), rs2, rl2;
-        if (!block_mode) {
+        if (block_mode != 1) {
             if ((rc2 = gs::ingest_records_dev(c, aa, false, dtext[b].p, S.bytes, S.sb.data(), S.se.data(), nrec, dout.p, 0, rs.data(), rl.data(), nullptr))) return rc2;
             for (uint64_t f = 0; f <= nf; f++) goff[f] = S.frec[f];
             rs2.assign(rs.begin(), rs.begin() + nrec); rl2.assign(rl.begin(), rl.begin() + nrec);
@@ -882,7 +920,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
         sub(3);
         for (uint64_t f = 0; f < nf; f++) {
             uint64_t sym = 0;
-            if (!block_mode) for (uint64_t r = S.frec[f]; r < S.frec[f + 1]; r++) sym += rl[r]; else sym = rl2[f];
+            if (block_mode != 1) for (uint64_t r = S.frec[f]; r < S.frec[f + 1]; r++) sym += rl[r]; else sym = rl2[f];
             const uint64_t row = out_index ? out_index[f0 + f] : f0 + f;
             if (out_index) memcpy((uint8_t *)sig_out + row * m * esz, rows_tmp.data() + f * m * esz, m * esz);
             if (n_records_out) n_records_out[row] = S.frec[f + 1] - S.frec[f];
@@ -986,6 +1024,22 @@ static int sketch_files_all(gs_ctx *c, const gs_sketch_params *p, const char *co
     }
     return GS_OK;
 }
+// hypermash's sketches (include/gsearch_amd.h): the host pipeline of gs_sketch_files in its hypermash mode (block_mode 2: by record, the reader
+// rules of scan_records_hmh); every .gz file through the host decoders, whose scan is the one that knows FASTQ
+int gs_hmh_sketch_files(gs_ctx *c, uint32_t k, const char *const *paths, uint64_t n_files, uint32_t n_threads, uint16_t *sig_out,
+                        uint64_t *n_records_out, uint64_t *n_bases_out, double *stats_out)
+{
+    const gs_sketch_params p = {k, GS_HMH_REGISTERS, GS_ALGO_HMH, GS_DATA_DNA};
+    int rc = gs_check_params(&p);
+    if (rc) return rc;
+    GS_REQUIRE(c && (n_files == 0 || (paths && sig_out)), GS_ERR_INVALID, "null argument");
+    for (uint64_t f = 0; f < n_files; f++) GS_REQUIRE(paths[f], GS_ERR_INVALID, "null path %llu", (unsigned long long)f);
+    double st[4] = {0, 0, 0, 0};
+    rc = sketch_files_impl(c, &p, paths, n_files, 2, 0, n_threads, sig_out, n_records_out, n_bases_out, st, false, nullptr, nullptr, 0, nullptr, false, 0);
+    if (rc) return rc;
+    if (stats_out) for (int i = 0; i < 4; i++) stats_out[i] = st[i];
+    return GS_OK;
+}
 // the round-1 contract: FOUR doubles (the array grew to six under the same symbol - a caller that passes double[4] was written out of bounds)
 int gs_sketch_files(gs_ctx *c, const gs_sketch_params *p, const char *const *paths, uint64_t n_files, int block_mode, uint32_t pio, uint32_t n_threads,
                     void *sig_out, uint64_t *n_records_out, uint64_t *n_symbols_out, double *stats_out)
@@ -997,7 +1051,7 @@ int gs_sketch_files_ex(gs_ctx *c, const gs_sketch_params *p, const char *const *
 {
     GS_REQUIRE(stats_out || stats_cap == 0, GS_ERR_INVALID, "gs_sketch_files_ex: stats_cap without stats_out");
     double st[GS_SKETCH_FILES_STATS] = {0, 0, 0, 0, 0, 0};
-    const int rc = sketch_files_all(c, p, paths, n_files, block_mode, pio, n_threads, sig_out, n_records_out, n_symbols_out, st);
+    const int rc = sketch_files_all(c, p, paths, n_files, block_mode ? 1 : 0, pio, n_threads, sig_out, n_records_out, n_symbols_out, st);   // (2 is the hypermash mode)
     for (uint32_t i = 0; i < stats_cap && i < (uint32_t)GS_SKETCH_FILES_STATS; i++) stats_out[i] = st[i];
     return rc;
 }

@@ -3031,6 +3031,7 @@ int gs_index_sketch_and_search_dev(gs_index *ix, const gs_sketch_params *p, cons
     GS_REQUIRE(ix->n > 0, GS_ERR_STATE, "search on an empty index");
     int rc = gs_check_params(p);
     if (rc) return rc;
+    GS_REQUIRE(p->algo != GS_ALGO_HMH, GS_ERR_UNSUPPORTED, "HyperMinHash signatures are not searched through the HNSW index");
     GS_REQUIRE(gs_sig_kind(p) == ix->prm.kind && p->sketch_size == ix->prm.m, GS_ERR_INVALID, "the sketcher's signatures (kind %d, length %u) are not the index's (kind %d, length %u)",
                gs_sig_kind(p), p->sketch_size, ix->prm.kind, ix->prm.m);
     gs_ctx *c = ix->ctx;

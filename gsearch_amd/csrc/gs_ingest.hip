@@ -230,6 +230,68 @@ int gs_fasta_scan(const char *buf, uint64_t n, int skip_capsid, uint64_t cap, ui
     return GS_OK;
 }
 
+/* host: FASTQ records (see include/gsearch_amd.h). A record is an '@' header line, sequence lines up to a line that starts with '+', then
+ * quality lines until as many quality bytes as sequence bytes (line breaks not counted; a '\r' before '\n' is a line break) have been read.
+ * Blank lines between records are skipped; anything else that is not a record, or a record cut short, is GS_ERR_IO. */
+int gs_fastq_scan(const char *buf, uint64_t n, uint64_t cap, uint64_t *seq_begin, uint64_t *seq_end, uint64_t *id_begin, uint32_t *id_len,
+                  uint64_t *n_rec_out)
+{
+    GS_REQUIRE(buf || n == 0, GS_ERR_INVALID, "null buffer");
+    GS_REQUIRE(n_rec_out, GS_ERR_INVALID, "null n_rec_out");
+    // line [i, end) with end at the '\n' (or n); content length without the line break; next = first byte after the line
+    auto line = [&](uint64_t i, uint64_t &end, uint64_t &next) -> uint64_t {
+        const char *nl = (const char *)memchr(buf + i, '\n', n - i);
+        end = nl ? (uint64_t)(nl - buf) : n;
+        next = nl ? end + 1 : n;
+        uint64_t len = end - i;
+        if (len && buf[end - 1] == '\r') len--;
+        return len;
+    };
+    uint64_t nr = 0, i = 0;
+    while (i < n) {
+        uint64_t end, next;
+        const uint64_t hl = line(i, end, next);
+        if (hl == 0) { i = next; continue; }                              // blank line between records
+        GS_REQUIRE(buf[i] == '@', GS_ERR_IO, "FASTQ: a record must start with '@' (byte %llu)", (unsigned long long)i);
+        GS_REQUIRE(next < n || end < n, GS_ERR_IO, "FASTQ: record at byte %llu is truncated after its header", (unsigned long long)i);
+        const uint64_t h0 = i + 1;
+        uint64_t idl = 0;
+        while (h0 + idl < i + hl && buf[h0 + idl] != ' ' && buf[h0 + idl] != '\t') idl++;
+        // sequence lines up to the '+' line
+        const uint64_t s0 = next;
+        uint64_t j = next, slen = 0;
+        bool plus = false;
+        while (j < n) {
+            if (buf[j] == '+') { plus = true; break; }
+            uint64_t e2, n2;
+            slen += line(j, e2, n2);
+            j = n2;
+        }
+        GS_REQUIRE(plus, GS_ERR_IO, "FASTQ: record at byte %llu has no '+' line", (unsigned long long)i);
+        const uint64_t s1 = j;
+        uint64_t e2, q = 0;
+        line(j, e2, j);                                                   // the '+' line (it may repeat the header)
+        // quality: exactly slen bytes over one or more lines
+        if (slen == 0) {
+            if (j < n) { uint64_t e3, n3; if (line(j, e3, n3) == 0) j = n3; }      // the empty quality line of an empty record
+        } else {
+            while (q < slen) {
+                GS_REQUIRE(j < n, GS_ERR_IO, "FASTQ: record at byte %llu is truncated in its quality", (unsigned long long)i);
+                uint64_t e3, n3;
+                q += line(j, e3, n3);
+                j = n3;
+            }
+            GS_REQUIRE(q == slen, GS_ERR_IO, "FASTQ: record at byte %llu has %llu quality bytes for %llu bases", (unsigned long long)i,
+                       (unsigned long long)q, (unsigned long long)slen);
+        }
+        if (nr < cap) { if (seq_begin) seq_begin[nr] = s0; if (seq_end) seq_end[nr] = s1; if (id_begin) id_begin[nr] = h0; if (id_len) id_len[nr] = (uint32_t)idl; }
+        nr++;
+        i = j;
+    }
+    *n_rec_out = nr;
+    return GS_OK;
+}
+
 /* device: pack the sequence text of n_rec records to 2 bits. text_dev: the raw text (n_bytes); seq_begin/seq_end: HOST arrays from
  * gs_fasta_scan (offsets into the text); packed_dev: ZEROED device buffer of at least n_bytes/4 + 8*n_rec + 64 bytes; every record
  * starts on a 32-base boundary. rec_start_out / rec_len_out (HOST) receive the base coordinates for gs_sketch_batch_dev. */

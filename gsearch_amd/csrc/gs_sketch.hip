@@ -2987,6 +2987,73 @@ static int run_hll(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
     return GS_OK;
 }
 
+// =====================================================================================================
+// hmh (HyperMinHash of hypermash, SPEC 7): per k-mer one hash chain (fx64, two SplitMix64 outputs) and a register max. The 16384 registers
+// live in LDS as u32 (64 KB: two workgroups per CU) and take ds_max_u32. A genome split over `parts` workgroups (fewer genomes than
+// 2 x CUs: a metagenome) merges its parts by max into a u32 table in global memory, narrowed to u16 by k_hmh_narrow.
+// =====================================================================================================
+struct HmhEmit {
+    uint32_t *table;
+    __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const
+    {
+        uint32_t idx, reg;
+        hmh_update(v, idx, reg);
+        atomicMax(&table[idx], reg);
+    }
+};
+__global__ __launch_bounds__(SK_THREADS) void k_sketch_hmh(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_start,
+                                                           const uint64_t *__restrict__ rec_len, const uint64_t *__restrict__ rec_upre,
+                                                           const uint64_t *__restrict__ genome_rec_off, const uint64_t *__restrict__ gen_units,
+                                                           uint32_t k, uint16_t *__restrict__ sig, uint32_t *__restrict__ gtab)
+{
+    __shared__ uint32_t s_tab[GS_HMH_M];
+    const uint64_t g = blockIdx.y;
+    const uint32_t part = blockIdx.x, parts = gridDim.x;
+    for (uint32_t i = threadIdx.x; i < GS_HMH_M; i += blockDim.x) s_tab[i] = 0;
+    __syncthreads();
+    HmhEmit emit{s_tab};
+    walk_genome<false, HmhEmit, 0>(seq, rec_start, rec_len, rec_upre, genome_rec_off[g], genome_rec_off[g + 1], gen_units[g], k, part, parts, emit);
+    __syncthreads();
+    if (parts == 1) {
+        uint16_t *o = sig + g * (uint64_t)GS_HMH_M;
+        for (uint32_t i = threadIdx.x; i < GS_HMH_M; i += blockDim.x) o[i] = (uint16_t)s_tab[i];
+    } else {
+        uint32_t *t = gtab + g * (uint64_t)GS_HMH_M;
+        for (uint32_t i = threadIdx.x; i < GS_HMH_M; i += blockDim.x) { const uint32_t v = s_tab[i]; if (v) atomicMax(&t[i], v); }
+    }
+}
+__global__ void k_hmh_narrow(const uint32_t *__restrict__ gtab, uint64_t n, uint16_t *__restrict__ sig)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) sig[i] = (uint16_t)gtab[i];
+}
+
+static int run_hmh(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, const uint64_t *rec_start, const uint64_t *rec_len,
+                   const uint64_t *rec_upre, const uint64_t *genome_rec_off, const uint64_t *gen_units, uint64_t n_genomes, uint64_t avg_units, uint16_t *sig_out)
+{
+    const MinGeom ge = min_geom(c, GS_HMH_M, 4, n_genomes, avg_units);
+    PoolBuf gt(c, 64);
+    int rc;
+    if (ge.parts > 1) {
+        if ((rc = gt.alloc((size_t)n_genomes * GS_HMH_M * 4))) return rc;
+        GS_HIP_CHECK(hipMemsetAsync(gt.p, 0, (size_t)n_genomes * GS_HMH_M * 4, c->stream));
+    }
+    c->last_sketch[0] = 0; c->last_sketch[1] = 1; c->last_sketch[2] = ge.parts; c->last_sketch[3] = 0;
+    for (uint64_t g0 = 0; g0 < n_genomes; g0 += 65535) {       // grid.y limit
+        const uint64_t ng = n_genomes - g0 < 65535 ? n_genomes - g0 : 65535;
+        c->last_sketch[3]++;
+        ProfScope ps(c, FAM_SKETCH);
+        hipLaunchKernelGGL(k_sketch_hmh, dim3(ge.parts, (uint32_t)ng), dim3(SK_THREADS), 0, c->stream, seq, rec_start, rec_len, rec_upre, genome_rec_off + g0,
+                           gen_units + g0, p->k, sig_out + g0 * GS_HMH_M, ge.parts > 1 ? gt.as<uint32_t>() + g0 * GS_HMH_M : (uint32_t *)nullptr);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    if (ge.parts > 1) {
+        const uint64_t n = n_genomes * GS_HMH_M;
+        hipLaunchKernelGGL(k_hmh_narrow, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, 65536)), dim3(256), 0, c->stream, gt.as<uint32_t>(), n, sig_out);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    return GS_OK;
+}
+
 int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start,
                     const uint64_t *rec_len, uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes, void *sig_out, bool sync_at_end)
 {
@@ -3044,6 +3111,19 @@ int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint6
         rc = run_hll(c, p, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(), genome_rec_off, gunits.as<uint64_t>(), n_genomes, (p->data_t == GS_DATA_AA ? seq_bytes / 32 : seq_bytes / 8) + n_rec + 1, (uint16_t *)sig_out);
         if (rc) return rc;
         GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return GS_OK;
+    }
+    if (p->algo == GS_ALGO_HMH) {
+        PoolBuf upre(c, 20), gunits(c, 21);
+        rc = upre.alloc(8 * (n_rec + 1)); if (rc) return rc;
+        rc = gunits.alloc(8 * n_genomes); if (rc) return rc;
+        hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len,
+                           genome_rec_off, n_genomes, p->k, upre.as<uint64_t>(), gunits.as<uint64_t>());
+        GS_HIP_CHECK(hipGetLastError());
+        rc = run_hmh(c, p, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(), genome_rec_off, gunits.as<uint64_t>(), n_genomes,
+                     seq_bytes / 8 / n_genomes + 1, (uint16_t *)sig_out);
+        if (rc) return rc;
+        if (sync_at_end) GS_HIP_CHECK(hipStreamSynchronize(c->stream));
         return GS_OK;
     }
     if (p->algo == GS_ALGO_PROB3A) {

@@ -4,6 +4,7 @@
 // (Cargo.toml:26,122 of the reference; crates not vendored).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #define GS_HD __host__ __device__ __forceinline__
@@ -160,6 +161,86 @@ GS_HD uint32_t hll_k(double x, double inv_lnb)
     if (y < 0.0) return 0;
     if (y >= (double)(GS_HLL_Q + 1)) return GS_HLL_Q + 1;
     return (uint32_t)y;
+}
+
+// ---- SPEC 7 hmh (HyperMinHash, Yu & Weber 2017, as axiomhq/hyperminhash implements it) [PUB, recalled, unverified]: every constant and the
+// element hash live here so that they can be re-aligned if the `hyperminhash` crate's source ever appears
+#define GS_HMH_P 14u                     // m = 2^p registers
+#define GS_HMH_Q 6u
+#define GS_HMH_R 10u
+#define GS_HMH_M 16384u
+#define GS_HMH_SMALL 524288.0            // 2^(p+5): above it the closed form of the expected collisions
+#define GS_HMH_NP 65536u                 // 2^q x 2^r terms of the small-set sum
+// [CHOICE] h1, h2 = the first two SplitMix64 outputs from state fx64(v); register = (lz << r) | (h2 & (2^r - 1)), lz in [1, 51]
+GS_HD void hmh_update(uint64_t v, uint32_t &idx, uint32_t &reg)
+{
+    const uint64_t x = fx64(v);
+    const uint64_t h1 = splitmix_mix(x + GS_GAMMA), h2 = splitmix_mix(x + 2 * GS_GAMMA);
+    idx = (uint32_t)(h1 >> (64 - GS_HMH_P));
+    const uint32_t lz = (uint32_t)__builtin_clzll((h1 << GS_HMH_P) ^ 0x3FFFull) + 1;   // the low p bits are ones: never all-zero
+    reg = (lz << GS_HMH_R) | (uint32_t)(h2 & ((1u << GS_HMH_R) - 1));
+}
+// a non-negative integer hi:lo (128 bits) rounded once (to nearest, ties to even) to f64
+GS_HD double u128_to_f64(uint64_t hi, uint64_t lo)
+{
+    if (hi == 0) {
+        // (double)lo with one rounding: the two 32-bit halves are exact, their sum is rounded once
+        return (double)(uint32_t)(lo >> 32) * 4294967296.0 + (double)(uint32_t)lo;
+    }
+    const int s = 64 - __builtin_clzll(hi);                    // 1..64: bits of hi
+    const uint64_t top = s == 64 ? hi : (hi << (64 - s)) | (lo >> s);
+    const bool sticky = s == 64 ? lo != 0 : (lo << (64 - s)) != 0;
+    uint64_t r = top >> 11;
+    const uint64_t rem = top & 0x7FF;
+    if (rem > 0x400 || (rem == 0x400 && (sticky || (r & 1)))) r++;
+    double d = (double)(uint32_t)(r >> 32) * 4294967296.0 + (double)(uint32_t)r;     // r <= 2^53: exact
+    d = d * 2048.0;
+    for (int i = 0; i < s; i += 16) d = d * (double)(1u << (s - i < 16 ? s - i : 16));   // exact powers of two
+    return d;
+}
+// cardinality from the number of empty registers ez and the exact register sum (units of 2^-51, 128-bit hi:lo)
+GS_HD uint64_t hmh_card(uint32_t ez, uint64_t sum_hi, uint64_t sum_lo)
+{
+    const double m = (double)GS_HMH_M;
+    const double sum = u128_to_f64(sum_hi, sum_lo) * 0x1.0p-51;
+    const double ezf = (double)ez;
+    const double zl = spec_ln(ezf + 1.0);
+    const double z2 = zl * zl, z3 = z2 * zl, z4 = z3 * zl, z5 = z4 * zl, z6 = z5 * zl, z7 = z6 * zl;
+    double beta = -0.370393911 * ezf;
+    beta = beta + 0.070471823 * zl;
+    beta = beta + 0.17393686 * z2;
+    beta = beta + 0.16339839 * z3;
+    beta = beta - 0.09237745 * z4;
+    beta = beta + 0.03738027 * z5;
+    beta = beta - 0.005384159 * z6;
+    beta = beta + 0.00042419 * z7;
+    const double alpha = 0.7213 / (1.0 + 1.079 / m);
+    const double c = ((alpha * m) * (m - ezf)) / (beta + sum);
+    return c >= 18446744073709551615.0 ? ~(uint64_t)0 : (uint64_t)c;
+}
+// the two parameters of the term index t in [0, 65536) of the small-set sum: i = t / 1024 + 1, j = t % 1024 + 1
+GS_HD void hmh_b(uint32_t t, double &b1, double &b2)
+{
+    const uint32_t i = t / (1u << GS_HMH_R) + 1, j = t % (1u << GS_HMH_R) + 1;
+    if (i < (1u << GS_HMH_Q)) {
+        const double inv = ldexp(1.0, -(int)(GS_HMH_P + GS_HMH_R + i));                     // 2^-(24+i), exact
+        b1 = (double)(1024 + j) * inv; b2 = (double)(1025 + j) * inv;
+    } else {
+        b1 = (double)j * 0x1.0p-87; b2 = (double)(j + 1) * 0x1.0p-87;
+    }
+}
+// expected collisions in the closed form (n = max card > 2^(p+5), mn = min card)
+GS_HD double hmh_ec_closed(double n, double mn)
+{
+    const double t = (1.0 + n) / mn;
+    const double d = (4.0 * n / mn) / (t * t);
+    return 0.169919487159739093975315012348 * 16.0 * d + 0.5;
+}
+GS_HD double hmh_sim_from(uint32_t C, uint32_t N, double ec)
+{
+    const double c = (double)C;
+    if (c < ec) return 0.0;
+    return (c - ec) / (double)N;
 }
 
 }  // namespace gs

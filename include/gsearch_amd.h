@@ -29,7 +29,9 @@ enum {
     GS_ERR_IO = -5
 };
 /* kmerutils::sketcharg::SketchAlgo / DataType as parsed at src/bin/gsearch.rs:181-196,258-263 */
-enum { GS_ALGO_PROB3A = 0, GS_ALGO_SUPER = 1, GS_ALGO_SUPER2 = 2, GS_ALGO_HLL = 3, GS_ALGO_OPTDENS = 4, GS_ALGO_REVOPTDENS = 5 };
+enum { GS_ALGO_PROB3A = 0, GS_ALGO_SUPER = 1, GS_ALGO_SUPER2 = 2, GS_ALGO_HLL = 3, GS_ALGO_OPTDENS = 4, GS_ALGO_REVOPTDENS = 5,
+       GS_ALGO_HMH = 6 /* HyperMinHash of hypermash (src/bin/hypermash.rs): sketch_size 16384, canonical DNA, k 1..32 (15 accepted), u16 (SPEC 7) */ };
+enum { GS_HMH_REGISTERS = 16384 };
 /* GS_DATA_DNA_FWD: DNA whose k-mer value is the forward window itself, WITHOUT the reverse-complement minimum - the closure bindash-rs passes
  * for k <= 14 (`kmer.get_compressed_value() & mask`, src/bin/bindash.rs:346-354; its k = 16 and k > 16 closures, :366-377,:388-397, and every
  * closure of gsearch itself, dnasketch.rs:164-169, are canonical = GS_DATA_DNA). Accepted for every k and algo; same (k -> Kmer::Val, Sig) table as DNA. */
@@ -67,7 +69,7 @@ int   gs_ctx_profile_read(gs_ctx *, int family, double *total_ms, uint64_t *laun
 
 /* which form of the slot-min sketch kernel (optdens / revoptdens / super / super2 level 0) the LAST sketch call on this context launched:
  * out[0] = 1 when the early-rejection ("filtered") emitter ran, out[1] = 1 when the slot table lived in LDS, out[2] = workgroups per
- * genome, out[3] = launches. Tests use it to prove that a parity case exercised the instantiation the bench times. */
+ * genome, out[3] = launches; GS_ALGO_HMH reports {0, 1, workgroups per genome, launches}. Tests use it to prove that a parity case exercised the instantiation the bench times. */
 int   gs_ctx_last_sketch_info(gs_ctx *, uint32_t out[4]);
 
 /* plain device-memory helpers so that hosts without a HIP binding can keep data resident in HBM */
@@ -84,7 +86,7 @@ int   gs_dev_memset(gs_ctx *, void *dst_dev, int byte, size_t bytes);
 /* mirrors kmerutils::sketcharg::SeqSketcherParams{kmer_size, sketch_size, algo, data_t}            */
 typedef struct { uint32_t k, sketch_size, algo, data_t; } gs_sketch_params;
 
-int    gs_check_params(const gs_sketch_params *);       /* k=15, k>32 (DNA) / k>12 (AA) -> error */
+int    gs_check_params(const gs_sketch_params *);       /* k=15, k>32 (DNA) / k>12 (AA) -> error; hmh: see GS_ALGO_HMH */
 int    gs_sig_kind(const gs_sketch_params *);           /* GS_KIND_* */
 size_t gs_sig_elem_bytes(const gs_sketch_params *);
 int    gs_value_bits(const gs_sketch_params *);         /* width of Kmer::Val: 32 or 64 */
@@ -170,6 +172,30 @@ int gs_hamming_pairs(gs_ctx *, int kind, uint32_t m, const void *A, uint64_t na,
                      const uint64_t *ia, const uint64_t *ib, uint64_t npairs, float *dist_out);
 /* reformat.rs:80-86 calculate_ani (model 1 Poisson, 2 binomial), host arithmetic in f64 */
 double gs_ani(double distance, int kmer_size, int model);
+
+/* ---------------------------------------------------------------------------------------------- */
+/* hypermash (src/bin/hypermash.rs; the `hyperminhash` crate): HyperMinHash sketches of 16384 u16 registers (gs_sketch_batch with   */
+/* GS_ALGO_HMH) and the similarity / distance of every query x reference pair. Arithmetic: SPEC 7.                                   */
+/* cardinality of each of n sketches (n x 16384 u16) -> card_out[n] (u64), bit-exact to SPEC 7 */
+int gs_hmh_cardinality(gs_ctx *, const uint16_t *sigs, uint64_t n, uint64_t *card_out);
+int gs_hmh_cardinality_dev(gs_ctx *, const uint16_t *sigs_dev, uint64_t n, uint64_t *card_out_dev);
+/* similarity of every (query, reference) pair -> sim_out[nq x nr] (f64, query-major). The _dev form queues on the context's stream but waits for it
+ * once, to learn which sketches take the small-set branch; rows must be 16-byte aligned. nr < 65535 x 128. */
+int gs_hmh_similarity_qxc(gs_ctx *, const uint16_t *Q, uint64_t nq, const uint16_t *R, uint64_t nr, double *sim_out);
+int gs_hmh_similarity_qxc_dev(gs_ctx *, const uint16_t *Q_dev, uint64_t nq, const uint16_t *R_dev, uint64_t nr, double *sim_out_dev);
+/* hypermash.rs:261-263: 1 - (2 sim / (1 + sim))^(1/k), host arithmetic in f64 */
+double gs_hmh_distance(double sim, int kmer_size);
+/* FASTQ records of a text: an '@' header line, sequence lines up to a '+' line, then as many quality bytes (line breaks not counted) as
+ * the sequence has. Multi-line records and CRLF are accepted; a truncated or malformed record is GS_ERR_IO. Record r: sequence text =
+ * bytes [seq_begin[r], seq_end[r]) (line breaks included), id = the header's first word. Arrays may be NULL / cap 0 to count only. */
+int gs_fastq_scan(const char *buf, uint64_t n, uint64_t cap, uint64_t *seq_begin, uint64_t *seq_end, uint64_t *id_begin, uint32_t *id_len,
+                  uint64_t *n_rec_out);
+/* One HyperMinHash sketch (16384 u16) per file, input order, with hypermash's reader rules: FASTA or FASTQ (by the first non-blank byte),
+ * plain / gz / bz2 / xz (a zstd file is GS_ERR_UNSUPPORTED), no capsid filter, records of <= k bases (line breaks not counted) skipped,
+ * k-mers never span records. The pipeline of gs_sketch_files (host threads read / decode / scan, PCIe copies, device pack + sketch).
+ * n_records_out / n_bases_out: optional per-file (records kept, bases sketched); stats_out: optional, the first four doubles of gs_sketch_files. */
+int gs_hmh_sketch_files(gs_ctx *, uint32_t k, const char *const *paths, uint64_t n_files, uint32_t n_threads, uint16_t *sig_out,
+                        uint64_t *n_records_out, uint64_t *n_bases_out, double *stats_out);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */

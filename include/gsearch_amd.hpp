@@ -38,7 +38,8 @@ private:
     gs_ctx *h_ = nullptr;
 };
 
-enum class SketchAlgo : uint32_t { PROB3A = GS_ALGO_PROB3A, SUPER = GS_ALGO_SUPER, SUPER2 = GS_ALGO_SUPER2, HLL = GS_ALGO_HLL, OPTDENS = GS_ALGO_OPTDENS, REVOPTDENS = GS_ALGO_REVOPTDENS };
+enum class SketchAlgo : uint32_t { PROB3A = GS_ALGO_PROB3A, SUPER = GS_ALGO_SUPER, SUPER2 = GS_ALGO_SUPER2, HLL = GS_ALGO_HLL, OPTDENS = GS_ALGO_OPTDENS, REVOPTDENS = GS_ALGO_REVOPTDENS,
+                                  HMH = GS_ALGO_HMH /* hypermash: sketch_size 16384, canonical DNA, u16 */ };
 enum class DataType : uint32_t { DNA = GS_DATA_DNA, AA = GS_DATA_AA, DNA_FWD = GS_DATA_DNA_FWD /* bindash.rs:346-354: k <= 14, no reverse-complement minimum */ };
 
 // kmerutils::sketcharg::SeqSketcherParams::new(kmer_size, sketch_size, algo, data_t)  (src/bin/gsearch.rs:258-263)
@@ -150,6 +151,31 @@ private:
 };
 // reformat.rs:80-86
 inline double calculate_ani(double distance, int kmer, int model) { return gs_ani(distance, kmer, model); }
+
+// hypermash (src/bin/hypermash.rs; hyperminhash::Sketch, SPEC 7): sketches of 16384 u16 registers (SeqSketcher<uint16_t> with SketchAlgo::HMH, or
+// hmh_sketch_files with hypermash's reader rules), their cardinality, the similarity of every query x reference pair and the distance
+inline std::vector<uint64_t> hmh_cardinality(Context &ctx, const std::vector<uint16_t> &sigs)
+{
+    std::vector<uint64_t> out(sigs.size() / GS_HMH_REGISTERS);
+    check(gs_hmh_cardinality(ctx.get(), sigs.data(), out.size(), out.data()));
+    return out;
+}
+inline std::vector<double> hmh_similarity_qxc(Context &ctx, const std::vector<uint16_t> &Q, const std::vector<uint16_t> &R)
+{
+    const uint64_t nq = Q.size() / GS_HMH_REGISTERS, nr = R.size() / GS_HMH_REGISTERS;
+    std::vector<double> out(nq * nr);
+    check(gs_hmh_similarity_qxc(ctx.get(), Q.data(), nq, R.data(), nr, out.data()));
+    return out;
+}
+inline std::vector<uint16_t> hmh_sketch_files(Context &ctx, uint32_t k, const std::vector<std::string> &paths, uint32_t n_threads = 0)
+{
+    std::vector<const char *> p;
+    for (const auto &x : paths) p.push_back(x.c_str());
+    std::vector<uint16_t> out(paths.size() * GS_HMH_REGISTERS);
+    check(gs_hmh_sketch_files(ctx.get(), k, p.data(), p.size(), n_threads, out.data(), nullptr, nullptr, nullptr));
+    return out;
+}
+inline double hypermash_distance(double sim, int kmer) { return gs_hmh_distance(sim, kmer); }
 
 // hnsw_rs::Neighbour{d_id, distance, p_id}: gsearch reads d_id (the DataId the point was inserted under: an index into its seqdict) and distance
 // (answer.rs:42,55-57); p_id = PointId(layer, rank in layer)
