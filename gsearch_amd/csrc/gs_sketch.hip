@@ -142,14 +142,16 @@ struct MinEmitF {
     {
         // one hash chain: h + gamma straight from the element hash (gamma rides in the addend of its low v_mad_u64_u32), h + 4 gamma from
         // that (one v_lshl_add_u64), and the queue holds h + gamma - instead of h, h + gamma and h + 4 gamma each from h (-1 mad, -1 add3)
-        uint64_t hg = elem_hash<ALGO, VBITS>(v) + GS_GAMMA;
+        uint64_t hg = elem_hash<ALGO, VBITS>(v, GS_GAMMA);
         asm("" : "+v"(hg));         // opaque: the compiler would otherwise rebuild h beside h + gamma and derive h + 4 gamma from h
         if (thr >= direct_above()) { apply(hg - GS_GAMMA); return; }            // wave-uniform
         const uint64_t s0 = splitmix_mix(hg), s3 = splitmix_mix(hg + 3 * GS_GAMMA);
         const bool pass = key_below(rotl64(s0 + s3, 23) + s0, thr);
         const uint64_t bal = __ballot(pass);
         if (bal) {
-            if (pass) q[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = hg;
+            // the slot is qn + the lanes below that pass: qn rides in the mbcnt pair's addend, and with the wave's queue base uniform
+            // (an SGPR) the LDS address is one v_lshl_add_u32 - instead of two shifts and a v_add3_u32
+            if (pass) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, qn))] = hg;
             qn += (uint32_t)__popcll(bal);
             if (qn >= 64) {
                 apply(q[lane] - GS_GAMMA);
@@ -383,7 +385,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_min(const uint8_t *__rest
             }
         }
         for (int pass = 0; pass < 2; pass++) {
-            MinEmitF<ALGO, VBITS, T> emit{table, m, zone, qbase + (threadIdx.x >> 6) * SKQ, threadIdx.x & 63, 0u, 0u, cap, cap};
+            MinEmitF<ALGO, VBITS, T> emit{table, m, zone, qbase + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * SKQ, threadIdx.x & 63, 0u, 0u, cap, cap};
             walk_genome<AA, MinEmitF<ALGO, VBITS, T>, RCM>(seq, rec_start, rec_len, rec_upre, genome_rec_off[g], genome_rec_off[g + 1], gen_units[g], k, part, parts, emit);
             if (cap == EMPTY) break;
             __syncthreads();

@@ -28,28 +28,50 @@ GS_HD uint64_t rotl64(uint64_t x, int r)
 }
 GS_HD uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 
-// fxhash::FxHasher64 over one integer write
-GS_HD uint64_t fx64(uint64_t v) { return v * 0x517cc1b727220a95ULL; }
+// x * c + a mod 2^64 for constants c and a. On the device hipcc selects v_mad_u64_u32 (x_lo c_lo + a) + 2 v_mul_lo_u32 (the cross terms) +
+// v_add3_u32. Here the cross sum lo32(x_hi c_lo + x_lo c_hi) is one v_mul_lo_u32 and the low half of a v_mad_u64_u32 that adds it; it then
+// enters the high half of the addend of the last v_mad_u64_u32 (x_lo c_lo + (cross << 32)): three multiplies and two moves, 171 instead of
+// 181 issue cycles per dropped k-mer of the whole hash chain (tools/ubench_valu). A non-zero a joins that addend as
+// a_lo : (a_hi + cross), so that its carry out of the low half stays inside the multiply-add.
+GS_HD uint64_t mulc64(uint64_t x, uint64_t c, uint64_t a = 0)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32), cl = (uint32_t)c, ch = (uint32_t)(c >> 32);
+    uint64_t cr = (uint64_t)xh * cl + (uint32_t)(xl * ch);
+    asm("" : "+v"(cr));         // keep the 64-bit multiply-add: narrowed to 32 bits it becomes a v_mul_lo_u32 that a v_add3_u32 takes back in
+    if (a == 0) return (uint64_t)xl * cl + ((uint64_t)(uint32_t)cr << 32);
+    uint32_t zh = (uint32_t)(a >> 32) + (uint32_t)cr;
+    asm("" : "+v"(zh));
+    uint64_t z = ((uint64_t)zh << 32) | (uint32_t)a;
+    asm("" : "+v"(z));          // one addend: otherwise a is split off and follows the multiply-add as a 64-bit add
+    return (uint64_t)xl * cl + z;
+#else
+    return x * c + a;
+#endif
+}
+
+// fxhash::FxHasher64 over one integer write (+ a: an offset the caller adds, folded into the multiply-add on the device)
+GS_HD uint64_t fx64(uint64_t v, uint64_t a = 0) { return mulc64(v, 0x517cc1b727220a95ULL, a); }
 // fxhash::FxHasher32: 32-bit words, low first
 GS_HD uint64_t fx32_w32(uint32_t v) { return (uint64_t)(uint32_t)(v * 0x9e3779b9u); }
 
 enum { ALGO_PROB3A = 0, ALGO_SUPER = 1, ALGO_SUPER2 = 2, ALGO_HLL = 3, ALGO_OPTDENS = 4, ALGO_REVOPTDENS = 5 };
 
-// SPEC 2 table "element hash"
+// SPEC 2 table "element hash" (+ a: an offset the caller adds, folded into fx64's multiply-add on the device)
 template <int ALGO, int VBITS>
-GS_HD uint64_t elem_hash(uint64_t v)
+GS_HD uint64_t elem_hash(uint64_t v, uint64_t a = 0)
 {
-    if (ALGO == ALGO_PROB3A) return v;
-    if (ALGO == ALGO_HLL) return fx64(v);
-    if (ALGO == ALGO_SUPER2 && VBITS == 32) return fx32_w32((uint32_t)v);
-    return fx64(v);
+    if (ALGO == ALGO_PROB3A) return v + a;
+    if (ALGO == ALGO_HLL) return fx64(v, a);
+    if (ALGO == ALGO_SUPER2 && VBITS == 32) return fx32_w32((uint32_t)v) + a;
+    return fx64(v, a);
 }
 
 // one SplitMix64 output for counter value x (already advanced)
 GS_HD uint64_t splitmix_mix(uint64_t z)
 {
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+    z = mulc64(z ^ (z >> 30), 0xbf58476d1ce4e5b9ULL);
+    z = mulc64(z ^ (z >> 27), 0x94d049bb133111ebULL);
     return z ^ (z >> 31);
 }
 #define GS_GAMMA 0x9e3779b97f4a7c15ULL
