@@ -33,6 +33,22 @@ class IndexParams(C.Structure):
                 ("insert_batch", C.c_uint32)]
 
 
+class EmbedParamsC(C.Structure):
+    """gs_embed_params (SPEC 8)"""
+    _fields_ = [("dim", C.c_uint32), ("epochs", C.c_uint32), ("neg_samples", C.c_uint32), ("neg_rate", C.c_float), ("lr", C.c_float),
+                ("seed", C.c_uint64)]
+
+
+class KnnStatsC(C.Structure):
+    """gs_knn_stats (SPEC 8)"""
+    _fields_ = [("n", C.c_uint64), ("n_edges", C.c_uint64), ("n_empty", C.c_uint64), ("knbn", C.c_uint32), ("max_occ", C.c_uint32),
+                ("occ_mean", C.c_double), ("occ_std", C.c_double), ("occ_skew", C.c_double), ("hub_ids", C.c_uint64 * 16),
+                ("hub_occ", C.c_uint32 * 16), ("q_first", C.c_float * 7), ("q_last", C.c_float * 7)]
+
+
+EMBED_HIST_BINS = 64
+EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
+
 # every symbol include/gsearch_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _u32, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 _PP = C.POINTER(SketchParams)
@@ -105,6 +121,12 @@ SYMBOLS = {
     "gs_index_exact_search_dev": (_i, [_vp, _vp, _u64, _u32, C.c_float, _vp, _vp, _vp]),
     "gs_index_knn_graph": (_i, [_vp, _u32, C.c_float, _u64, _u64, _vp, _vp, _vp]),
     "gs_index_knn_graph_dev": (_i, [_vp, _u32, C.c_float, _u64, _u64, _vp, _vp, _vp]),
+    "gs_embed_params_default": (EmbedParamsC, []),
+    "gs_embed_knn_graph": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(EmbedParamsC), _vp, _vp, _vp]),
+    "gs_embed_knn_graph_dev": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(EmbedParamsC), _vp, _vp, _vp]),
+    "gs_index_embed": (_i, [_vp, _u32, C.c_float, C.POINTER(EmbedParamsC), _vp, _vp]),
+    "gs_knn_graph_stats": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(KnnStatsC), _vp, _vp]),
+    "gs_index_knn_graph_stats": (_i, [_vp, _u32, C.c_float, C.POINTER(KnnStatsC), _vp, _vp]),
     "gs_index_import": (_i, [_vp, _vp, _u64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_index_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_index_get_data": (_i, [_vp, _u64, _u64, _vp]),

@@ -660,6 +660,117 @@ class ReqAnswer:
         return nb_match
 
 
+# ---- ann (embed.rs; SPEC 8): k-NN graph statistics and a UMAP-like embedding ----------------------------------------------------------
+GS_EMBED_KNBN = 8          # embed.rs:19 kgraph_from_hnsw_all(hnsw, 8)
+
+
+class EmbedParams:
+    """gs_embed_params: dim, epochs (E), neg_samples (S), neg_rate (r), lr, seed; the defaults come from the library (gs_embed_params_default)"""
+    FIELDS = ("dim", "epochs", "neg_samples", "neg_rate", "lr", "seed")
+
+    def __init__(self, **kw):
+        d = _lib.load().gs_embed_params_default()
+        for f in self.FIELDS:
+            setattr(self, f, kw.pop(f, getattr(d, f)))
+        if kw:
+            raise TypeError("unknown embedding parameters: %s" % ", ".join(sorted(kw)))
+
+    def c(self):
+        return _lib.EmbedParamsC(int(self.dim), int(self.epochs), int(self.neg_samples), float(self.neg_rate), float(self.lr), int(self.seed))
+
+    def __repr__(self):
+        return "EmbedParams(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f in self.FIELDS)
+
+
+def _embed_init(init, n, dim):
+    if init is None:
+        return None
+    init = np.ascontiguousarray(init, dtype=np.float32)
+    if init.shape != (n, dim):
+        raise GsError(_lib.GS_ERR_INVALID, "initial positions must be (%d, %d)" % (n, dim))
+    return init
+
+
+def _graph_arrays(ids, dist, cnt):
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    dist = np.ascontiguousarray(dist, dtype=np.float32)
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    if ids.ndim != 2 or dist.shape != ids.shape or cnt.shape != (ids.shape[0],):
+        raise GsError(_lib.GS_ERR_INVALID, "a graph is ids (n, knbn), dist (n, knbn) and cnt (n,)")
+    return ids, dist, cnt
+
+
+def embed_knn_graph(ids, dist, cnt, params=None, init=None, return_memb=False, ctx=None):
+    """SPEC 8 embedding of any k-NN graph in node numbers (e.g. Hnsw.knn_graph of an index without caller ids, or the layer-0 lists of
+    export_graph) -> (n, dim) float32 positions; return_memb: also the (n, knbn) calibrated memberships"""
+    ctx = ctx or default_context()
+    ids, dist, cnt = _graph_arrays(ids, dist, cnt)
+    n, knbn = ids.shape
+    prm = params or EmbedParams()
+    init = _embed_init(init, n, prm.dim)
+    out = np.zeros((n, prm.dim), np.float32)
+    memb = np.zeros((n, knbn), np.float32) if return_memb else None
+    check(ctx.L.gs_embed_knn_graph(ctx.h, n, knbn, _p(ids), _p(dist), _p(cnt), C.byref(prm.c()), _p(init), _p(out), _p(memb)))
+    return (out, memb) if return_memb else out
+
+
+def embed_knn_graph_dev(ctx, n, knbn, ids_dev, dist_dev, cnt_dev, pos_out_dev, params=None, init_dev=None, memb_out_dev=None):
+    """gs_embed_knn_graph_dev: every *_dev is a device pointer (int)"""
+    prm = params or EmbedParams()
+    check(ctx.L.gs_embed_knn_graph_dev(ctx.h, int(n), int(knbn), ids_dev, dist_dev, cnt_dev, C.byref(prm.c()), init_dev, pos_out_dev, memb_out_dev))
+
+
+def _stats_dict(st, occ, hist):
+    nh = min(int(st.n), 16)
+    return dict(n=int(st.n), knbn=int(st.knbn), n_edges=int(st.n_edges), n_empty=int(st.n_empty), max_occ=int(st.max_occ),
+                occ_mean=float(st.occ_mean), occ_std=float(st.occ_std), occ_skew=float(st.occ_skew),
+                hubs=[(int(st.hub_ids[h]), int(st.hub_occ[h])) for h in range(nh)],
+                quantiles=list(_lib.EMBED_QUANTILES), q_first=np.array(st.q_first[:], np.float32), q_last=np.array(st.q_last[:], np.float32),
+                occ=occ, hist=hist)
+
+
+def knn_graph_stats(ids, dist, cnt, ctx=None):
+    """SPEC 8 statistics of a k-NN graph in node numbers -> dict: n, knbn, n_edges, n_empty, max_occ, occ_mean / occ_std / occ_skew (k-occurrence
+    moments, occ_skew = hubness), hubs [(node, occ)] (16 largest, ties by node number), q_first / q_last (quantiles of the first / last kept
+    distance), occ (n,), hist (occ 0..63, then >= 64)"""
+    ctx = ctx or default_context()
+    ids, dist, cnt = _graph_arrays(ids, dist, cnt)
+    n, knbn = ids.shape
+    st, occ, hist = _lib.KnnStatsC(), np.zeros(n, np.uint32), np.zeros(_lib.EMBED_HIST_BINS + 1, np.uint64)
+    check(ctx.L.gs_knn_graph_stats(ctx.h, n, knbn, _p(ids), _p(dist), _p(cnt), C.byref(st), _p(occ), _p(hist)))
+    return _stats_dict(st, occ, hist)
+
+
+def write_embedding_csv(path, xy):
+    """database_embedded.csv: no header, one row per node in node order (= DataId order in gsearch), the coordinates comma-separated as the
+    shortest text that reads back to the same float32 ([CHOICE], SPEC 8)"""
+    xy = np.asarray(xy, dtype=np.float32)
+    with open(path, "w") as f:
+        for row in xy:
+            f.write(",".join(np.format_float_positional(v, unique=True, trim="-") for v in row) + "\n")
+    return len(xy)
+
+
+def ann(hnsw, stats=True, embed=False, params=None, csv_path="database_embedded.csv", knbn=GS_EMBED_KNBN, out=None):
+    """get_graph_stats_embed (embed.rs:15-66): --stats prints the k-NN graph statistics, --embed writes csv_path. Returns
+    {"stats": dict or None, "embedding": (n, dim) array or None}"""
+    res = {"stats": None, "embedding": None}
+    if stats:
+        st = res["stats"] = hnsw.knn_graph_stats(knbn)
+        if out is not None:
+            out.write("k-NN graph of %d nodes, knbn %d: %d edges, %d empty rows\n" % (st["n"], st["knbn"], st["n_edges"], st["n_empty"]))
+            out.write("first neighbour distance quantiles: %s\n" % " ".join("%g:%g" % (q, v) for q, v in zip(st["quantiles"], st["q_first"])))
+            out.write("last neighbour distance quantiles: %s\n" % " ".join("%g:%g" % (q, v) for q, v in zip(st["quantiles"], st["q_last"])))
+            out.write("k-occurrence mean %.6g std %.6g, hubness (standardised third moment) %.6g, max %d\n" % (st["occ_mean"], st["occ_std"],
+                                                                                                           st["occ_skew"], st["max_occ"]))
+            out.write("largest hubs: %s\n" % " ".join("%d:%d" % h for h in st["hubs"]))
+    if embed:
+        xy = res["embedding"] = hnsw.embed(knbn, params)
+        if csv_path:
+            write_embedding_csv(csv_path, xy)
+    return res
+
+
 def dump_knn_graph(seqdict, node_ids, ids, dist, cnt, out):
     """hnsw2knn's neighbour-list text: one line per node, `path:` then per neighbour, in order, a tab, `path:` and the distance with six
     decimals. node_ids[i] = the caller id of row i (Hnsw.get_ids), ids / dist / cnt = Hnsw.knn_graph's answer; `seqdict` = list of
@@ -839,6 +950,26 @@ class Hnsw:
     def knn_graph_dev(self, knbn, first, n, d_ids, d_dist, d_count, max_dist=1.0):
         """gs_index_knn_graph_dev: every d_* is a device pointer (int)"""
         check(self.ctx.L.gs_index_knn_graph_dev(self.h, knbn, float(max_dist), first, n, d_ids, d_dist, d_count))
+
+    def embed(self, knbn=GS_EMBED_KNBN, params=None, init=None, max_dist=1.0):
+        """ann --embed (embed.rs:34-64): the exact self graph of knbn neighbours (kept on the device) embedded by SPEC 8 -> (n, dim) float32,
+        one row per node in node (insertion) order, also when the index holds caller ids (map rows with get_ids)"""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "embedding of an empty index")
+        prm = params or EmbedParams()
+        n = self.get_nb_point()
+        init = _embed_init(init, n, prm.dim)
+        out = np.zeros((n, prm.dim), np.float32)
+        check(self.ctx.L.gs_index_embed(self.h, int(knbn), float(max_dist), C.byref(prm.c()), _p(init), _p(out)))
+        return out
+
+    def knn_graph_stats(self, knbn=GS_EMBED_KNBN, max_dist=1.0):
+        """ann --stats (embed.rs:26-33): statistics of the exact self graph of knbn neighbours (dict, see knn_graph_stats; hubs are node numbers)"""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "statistics of an empty index")
+        st, occ, hist = _lib.KnnStatsC(), np.zeros(self.get_nb_point(), np.uint32), np.zeros(_lib.EMBED_HIST_BINS + 1, np.uint64)
+        check(self.ctx.L.gs_index_knn_graph_stats(self.h, int(knbn), float(max_dist), C.byref(st), _p(occ), _p(hist)))
+        return _stats_dict(st, occ, hist)
 
     # graph import/export in the library's dense layout (role of HnswIo::load_hnsw / file_dump)
     def import_graph(self, sigs, g):

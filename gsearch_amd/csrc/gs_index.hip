@@ -3614,7 +3614,8 @@ static int exact_args(const gs_index *ix, uint32_t knbn, float max_dist, uint32_
 }
 // exact k-NN of nq padded device rows (stride ix->stride) against every node, answers to device memory: blocks of rows through dense_counts into
 // ix->mat, the select of gs_knn.hip, then the caller's ids. diag0 != UINT64_MAX: row q drops node diag0 + q (the self graph).
-static int exact_dev(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint64_t *ids, float *dist, uint32_t *count)
+static int exact_dev(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint64_t *ids, float *dist, uint32_t *count,
+                     bool node_numbers = false)
 {
     gs_ctx *c = ix->ctx;
     // (dense_counts' feed hook is null here: gs_index_sketch_and_search_dev sets it only for its own search_dev, under the context lock this call holds)
@@ -3629,7 +3630,7 @@ static int exact_dev(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn,
         if ((rc = knn_select(c, ix->mat.as<uint16_t>(), ld, nb, ix->n, knbn, c_max, diag0 == ~(uint64_t)0 ? diag0 : diag0 + q0, ix->prm.m,
                              ids + q0 * knbn, dist + q0 * knbn, count + q0))) return rc;
     }
-    return finish_ids(ix, ids, nq * knbn, nullptr, nullptr);
+    return node_numbers ? GS_OK : finish_ids(ix, ids, nq * knbn, nullptr, nullptr);
 }
 // host answers: the device ones in pooled buffers, then copied out
 static int exact_to_host(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint64_t *ids, float *dist, uint32_t *count)
@@ -3700,6 +3701,48 @@ int gs_index_knn_graph_dev(gs_index *ix, uint32_t knbn, float max_dist, uint64_t
                            uint32_t *count_out_dev)
 {
     return gs::knn_graph_common(ix, true, knbn, max_dist, first, n_rows, ids_out_dev, dist_out_dev, count_out_dev);
+}
+
+}  // extern "C"
+namespace gs {
+// ann (embed.rs:19-21): the index's exact self graph of every node in NODE numbers (no caller ids), in pooled buffers 100-102, validated (SPEC 8).
+// The caller holds the context lock.
+static int self_graph_dev(gs_index *ix, uint32_t knbn, float max_dist, uint64_t **ids, float **dist, uint32_t **cnt)
+{
+    uint32_t c_max = 0;
+    int rc = exact_args(ix, knbn, max_dist, &c_max);
+    if (rc) return rc;
+    GS_REQUIRE(ix->n < ((uint64_t)1 << 31) && ix->n * knbn < ((uint64_t)1 << 31), GS_ERR_UNSUPPORTED, "graph of more than 2^31 entries");
+    gs_ctx *c = ix->ctx;
+    PoolBuf dids(c, 100), ddist(c, 101), dcount(c, 102);
+    const uint64_t n = ix->n;
+    if ((rc = dids.alloc(8 * n * knbn)) || (rc = ddist.alloc(4 * n * knbn)) || (rc = dcount.alloc(4 * n))) return rc;
+    if ((rc = exact_dev(ix, ix->data.as<uint8_t>(), n, knbn, c_max, 0, dids.as<uint64_t>(), ddist.as<float>(), dcount.as<uint32_t>(), true))) return rc;
+    *ids = dids.as<uint64_t>(); *dist = ddist.as<float>(); *cnt = dcount.as<uint32_t>();
+    return embed_validate(c, n, knbn, *ids, *dist, *cnt);
+}
+}  // namespace gs
+extern "C" {
+
+int gs_index_embed(gs_index *ix, uint32_t knbn, float max_dist, const gs_embed_params *prm, const float *init, float *pos_out)
+{
+    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
+    GS_REQUIRE(pos_out || ix->n == 0, GS_ERR_INVALID, "null argument");
+    GS_CTX_LOCK(ix->ctx);
+    uint64_t *ids; float *dist; uint32_t *cnt;
+    int rc = gs::self_graph_dev(ix, knbn, max_dist, &ids, &dist, &cnt);
+    if (rc) return rc;
+    return gs::embed_common(ix->ctx, false, ix->n, knbn, ids, dist, cnt, prm, init, pos_out, nullptr);
+}
+int gs_index_knn_graph_stats(gs_index *ix, uint32_t knbn, float max_dist, gs_knn_stats *stats_out, uint32_t *occ_out, uint64_t *hist_out)
+{
+    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
+    GS_REQUIRE(stats_out, GS_ERR_INVALID, "null argument");
+    GS_CTX_LOCK(ix->ctx);
+    uint64_t *ids; float *dist; uint32_t *cnt;
+    int rc = gs::self_graph_dev(ix, knbn, max_dist, &ids, &dist, &cnt);
+    if (rc) return rc;
+    return gs::knn_stats_dev(ix->ctx, ix->n, knbn, ids, dist, cnt, stats_out, occ_out, hist_out);
 }
 
 /* own binary dump (role of Hnsw::file_dump / HnswIo::load_hnsw, dumpload.rs:31, reloadhnsw.rs:41-51):

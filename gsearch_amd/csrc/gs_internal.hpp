@@ -165,6 +165,14 @@ enum { KNN_MAX = 1024 };
 int knn_select(gs_ctx *c, const uint16_t *mat, uint64_t ld, uint64_t nrows, uint64_t n, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint32_t m,
                uint64_t *ids, float *dist, uint32_t *count);
 
+// gs_embed.hip (SPEC 8): the embedding of a device graph in node numbers (embed_common validates nothing: the caller has; on_dev = false: init, pos_out
+// and memb_out are host arrays), and the statistics of a validated device graph (host outputs)
+int embed_validate(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *cnt);
+int embed_common(gs_ctx *c, bool on_dev, uint64_t n, uint32_t knbn, const uint64_t *dids, const float *ddist, const uint32_t *dcnt, const gs_embed_params *prm,
+                 const float *init, float *pos_out, float *memb_out);
+int knn_stats_dev(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *cnt, gs_knn_stats *st, uint32_t *occ_out,
+                  uint64_t *hist_out);
+
 // gs_sketch.hip: the device sketch of a batch on context c's stream; sync_at_end = false leaves the results in flight (optdens / revoptdens only)
 int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
                     const uint64_t *genome_rec_off, uint64_t n_genomes, void *sig_out, bool sync_at_end);
@@ -264,7 +272,7 @@ struct VmArena {
 // Per-context scratch: a call's temporaries come from numbered grow-only slots instead of hipMalloc/hipFree (allocating and freeing
 // multi-GB buffers costs more than the kernels that use them). A context serves one call at a time (one stream), so slots are never
 // shared; gs_ctx_release_scratch / gs_ctx_destroy give the memory back.
-enum { SCRATCH_SLOTS = 80 };        // 48-52: staging of gs_sketch_batch, 53-57: of gs_hamming_qxc / gs_hamming_pairs (host-pointer calls), 64-79: hypermash
+enum { SCRATCH_SLOTS = 104 };       // 48-52: staging of gs_sketch_batch, 53-57: of gs_hamming_qxc / gs_hamming_pairs (host-pointer calls), 64-79: hypermash, 80-103: ann
 struct ScratchPool { DevBuf b[SCRATCH_SLOTS]; };
 enum { PINNED_SLOTS = 36 };      // 0-15 text, 16-31 compressed members, 32-33 inflate descriptors / results
 struct PinnedPool {

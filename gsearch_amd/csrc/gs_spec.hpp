@@ -265,4 +265,68 @@ GS_HD double hmh_sim_from(uint32_t C, uint32_t N, double ec)
     return (c - ec) / (double)N;
 }
 
+// ---- SPEC 2 EXP: e^x from IEEE f64 + - * / only (built with -ffp-contract=off, like spec_ln). Cody-Waite reduction x = k ln2 + r (ln2 split
+// so that k * GS_LN2_HI is exact for |k| < 2^11), a degree-13 Horner Taylor polynomial of e^r (|r| <= 0.35), and an exact power-of-two scale
+// (two factors below 2^-1022, so that a subnormal result is rounded once)
+#define GS_LN2_HI 6.93147180369123816490e-01
+#define GS_LN2_LO 1.90821492927058770002e-10
+#define GS_INV_LN2 1.44269504088896338700e+00
+GS_HD double pow2_int(long long k)        // 2^k for -1022 <= k <= 1023, built from its bits
+{
+    const uint64_t b = (uint64_t)(k + 1023) << 52;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __longlong_as_double((long long)b);
+#else
+    double d; __builtin_memcpy(&d, &b, 8); return d;
+#endif
+}
+GS_HD double spec_exp(double x)
+{
+    if (x != x) return x;
+    if (x < -745.2) return 0.0;
+    if (x > 709.7) return 1.0 / 0.0;
+    const long long k = (long long)(x * GS_INV_LN2 + (x < 0.0 ? -0.5 : 0.5));     // round half away from zero (the cast truncates)
+    const double r = (x - (double)k * GS_LN2_HI) - (double)k * GS_LN2_LO;
+    double p = 1.0 / 6227020800.0;
+    p = p * r + 1.0 / 479001600.0; p = p * r + 1.0 / 39916800.0; p = p * r + 1.0 / 3628800.0; p = p * r + 1.0 / 362880.0;
+    p = p * r + 1.0 / 40320.0; p = p * r + 1.0 / 5040.0; p = p * r + 1.0 / 720.0; p = p * r + 1.0 / 120.0; p = p * r + 1.0 / 24.0;
+    p = p * r + 1.0 / 6.0; p = p * r + 0.5; p = p * r + 1.0; p = p * r + 1.0;
+    if (k < -1022) return (p * pow2_int(k + 1000)) * pow2_int(-1000);
+    return p * pow2_int(k);
+}
+
+// ---- SPEC 8 ann (UMAP-like embedding of the k-NN graph, McInnes, Healy & Melville 2018, a = b = 1) [PUB] / [CHOICE]: every constant here
+#define GS_EMBED_KNBN 8u                  // [REF] embed.rs:19 kgraph_from_hnsw_all(hnsw, 8)
+#define GS_EMBED_DIM 2u                   // [REF] 2-D output
+#define GS_EMBED_DIM_MAX 4u
+#define GS_EMBED_EPOCHS 300u              // [CHOICE] E
+#define GS_EMBED_NEG 8u                   // [CHOICE] S negative samples per node and epoch
+#define GS_EMBED_NEG_RATE 1.0f            // [CHOICE] r
+#define GS_EMBED_LR 0.25f                 // [CHOICE] lr
+#define GS_EMBED_SEED 0x5eedULL           // [CHOICE]
+#define GS_EMBED_INIT_HALF 10.0f          // [CHOICE] seeded positions in [-10, 10)
+#define GS_EMBED_LIGHT 64u                // [CHOICE] L_H: a longer adjacency is summed by one wavefront
+#define GS_EMBED_CLAMP 4.0f               // [PUB] umap's gradient clip
+#define GS_EMBED_EPS 0.001f               // [PUB] umap's repulsion offset
+#define GS_EMBED_BISECT 64                // [PUB] umap smooth_knn_dist n_iter
+#define GS_EMBED_TOL 1e-5                 // [PUB] SMOOTH_K_TOLERANCE
+#define GS_EMBED_MIN_SCALE 1e-3           // [PUB] MIN_K_DIST_SCALE (floor of sigma, times the row's mean distance)
+#define GS_EMBED_HIST_BINS 64u            // [CHOICE] B: k-occurrence bins 0..B-1, then one overflow bin
+#define GS_EMBED_HUBS 16u
+#define GS_EMBED_TAG_INIT 0x696e6974ULL   // "init"
+#define GS_EMBED_TAG_NEG 0x6e6567ULL      // "neg"
+// initial coordinate t of node i: 24 bits of a counter-based hash, exact in f32, then * 2 * INIT_HALF - INIT_HALF
+GS_HD float embed_init_coord(uint64_t seed, uint64_t i, uint32_t dim, uint32_t t)
+{
+    const uint64_t h = splitmix_mix(splitmix_mix(seed ^ GS_EMBED_TAG_INIT) + GS_GAMMA * (i * dim + t + 1));
+    const float u = (float)(uint32_t)(h >> 40) * 0x1.0p-24f;
+    return u * (2.0f * GS_EMBED_INIT_HALF) - GS_EMBED_INIT_HALF;
+}
+// the per-epoch key of the negative samples, and the s-th sample of node i in [0, n): 64 x 64 -> high 64 multiply
+GS_HD uint64_t embed_epoch_key(uint64_t seed, uint32_t e) { return splitmix_mix(seed ^ GS_EMBED_TAG_NEG) + GS_GAMMA * ((uint64_t)e + 1); }
+GS_HD uint64_t embed_neg(uint64_t ekey, uint64_t i, uint32_t S, uint32_t s, uint64_t n)
+{
+    return mulhi64(splitmix_mix(splitmix_mix(ekey) + GS_GAMMA * (i * S + s + 1)), n);
+}
+
 }  // namespace gs

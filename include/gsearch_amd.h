@@ -278,6 +278,39 @@ int      gs_index_knn_graph(gs_index *, uint32_t knbn, float max_dist, uint64_t 
                             uint64_t *ids_out, float *dist_out, uint32_t *count_out);
 int      gs_index_knn_graph_dev(gs_index *, uint32_t knbn, float max_dist, uint64_t first, uint64_t n_rows,
                                 uint64_t *ids_out_dev, float *dist_out_dev, uint32_t *count_out_dev);
+/* ann (embed.rs): statistics and a UMAP-like embedding of a k-NN graph, bit-exact and reproducible (SPEC.md 8). A graph is n rows of knbn
+ * entries in the layout of gs_index_knn_graph, but in NODE NUMBERS: ids < n, count[i] kept entries ascending by distance, no self, no repeat,
+ * distances >= 0 and not NaN (GS_ERR_INVALID otherwise). n x knbn < 2^31, knbn <= 1024. */
+typedef struct {
+    uint32_t dim;            /* output dimension, 1..4 (2) */
+    uint32_t epochs;         /* E (0: the initial positions) */
+    uint32_t neg_samples;    /* S negative samples per node and epoch, 1..65535 */
+    float    neg_rate;       /* r: repulsion weight r * W_i / S per sample */
+    float    lr;             /* learning rate at epoch 0, decaying linearly */
+    uint64_t seed;           /* initial positions (when none are given) and negative samples */
+} gs_embed_params;
+gs_embed_params gs_embed_params_default(void);
+/* positions (n x dim f32, row-major) after E epochs; prm NULL: defaults; init (n x dim, optional): the initial positions instead of the seeded
+ * draw; memb_out (n x knbn f32, optional): the calibrated memberships p_it (0 in unused slots) */
+int      gs_embed_knn_graph(gs_ctx *, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *count,
+                            const gs_embed_params *prm, const float *init, float *pos_out, float *memb_out);
+int      gs_embed_knn_graph_dev(gs_ctx *, uint64_t n, uint32_t knbn, const uint64_t *ids_dev, const float *dist_dev, const uint32_t *count_dev,
+                                const gs_embed_params *prm, const float *init_dev, float *pos_out_dev, float *memb_out_dev);
+/* the index's own exact k-NN graph (gs_index_knn_graph, never leaving the device) embedded; rows in node (insertion) order, also with caller ids.
+ * init / pos_out: HOST. Empty index: GS_ERR_STATE; m > 65535: GS_ERR_UNSUPPORTED. */
+int      gs_index_embed(gs_index *, uint32_t knbn, float max_dist, const gs_embed_params *prm, const float *init, float *pos_out);
+typedef struct {
+    uint64_t n, n_edges, n_empty;   /* rows, kept entries (sum of counts), rows with count 0 */
+    uint32_t knbn, max_occ;
+    double   occ_mean, occ_std, occ_skew;   /* k-occurrence moments; occ_skew = hubness (standardised third moment) */
+    uint64_t hub_ids[16];           /* the 16 largest k-occurrences, ties by node number (node numbers; UINT64_MAX when n < 16) */
+    uint32_t hub_occ[16];
+    float    q_first[7], q_last[7]; /* quantiles 0.01 0.05 0.25 0.5 0.75 0.95 0.99 of the first / last kept distance (rows with count >= 1) */
+} gs_knn_stats;
+/* occ_out (n u32, optional): k-occurrence of every node; hist_out (65 u64, optional): nodes with occ 0..63, then >= 64. HOST arrays. */
+int      gs_knn_graph_stats(gs_ctx *, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *count,
+                            gs_knn_stats *stats_out, uint32_t *occ_out, uint64_t *hist_out);
+int      gs_index_knn_graph_stats(gs_index *, uint32_t knbn, float max_dist, gs_knn_stats *stats_out, uint32_t *occ_out, uint64_t *hist_out);
 /* Graph import / export (the role of hnswio::HnswIo::load_hnsw / Hnsw::file_dump, reloadhnsw.rs:41-51,
  * dumpload.rs:31, in this library's own dense layout): levels[n], entry id, layer 0: deg0[n], nbr0[n*2M],
  * cnt0[n*2M] (mismatch counts to the owner); upper layers: upidx[n] (-1 for level-0 nodes) and for the

@@ -301,6 +301,26 @@ public:
         check(gs_index_knn_graph(h_, (uint32_t)knbn, max_dist, first, n, ids.data(), dist.data(), cnt.data()));
         return lists(ids, dist, cnt, knbn);
     }
+    // ann --embed (embed.rs:34-64): the exact self graph embedded (SPEC 8); nb_point x prm.dim positions, row-major, in node order
+    std::vector<float> embed(size_t knbn = 8, const gs_embed_params *prm = nullptr, const std::vector<float> *init = nullptr, float max_dist = 1.0f) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "embedding of an empty index");
+        const gs_embed_params p = prm ? *prm : gs_embed_params_default();
+        std::vector<float> out(get_nb_point() * p.dim);
+        if (init && init->size() != out.size()) throw Error(GS_ERR_INVALID, "initial positions must be nb_point x dim");
+        check(gs_index_embed(h_, (uint32_t)knbn, max_dist, &p, init ? init->data() : nullptr, out.data()));
+        return out;
+    }
+    // ann --stats (embed.rs:26-33): statistics of the exact self graph; occ / hist (optional) receive the k-occurrences and their histogram
+    gs_knn_stats knn_graph_stats(size_t knbn = 8, float max_dist = 1.0f, std::vector<uint32_t> *occ = nullptr, std::vector<uint64_t> *hist = nullptr) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "statistics of an empty index");
+        gs_knn_stats st;
+        if (occ) occ->resize(get_nb_point());
+        if (hist) hist->resize(65);
+        check(gs_index_knn_graph_stats(h_, (uint32_t)knbn, max_dist, &st, occ ? occ->data() : nullptr, hist ? hist->data() : nullptr));
+        return st;
+    }
     void file_dump(const std::string &path) const { check(gs_index_save(h_, path.c_str())); }      // dumpload.rs:31 (own format)
 private:
     void frozen() const { if (h_) throw Error(GS_ERR_STATE, "index parameters are frozen once the index holds points"); }
