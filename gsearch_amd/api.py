@@ -586,6 +586,147 @@ def hypermash(query_paths, ref_paths, k, out, threads=0, ctx=None):
 
 
 # ----------------------------------------------------------------------------------------------------------
+# superaai (binaux/src/bin/superaai.rs): FracMinHash / bottom-k proteome sketches and AAI (SPEC 9)
+def _take_csr(L, hp, off):
+    """copy a library-allocated CSR into a list of uint64 arrays and release it"""
+    n = len(off) - 1
+    try:
+        tot = int(off[-1])
+        flat = np.ctypeslib.as_array(hp, shape=(tot,)).copy() if tot else np.zeros(0, np.uint64)
+    finally:
+        L.gs_host_free(C.cast(hp, C.c_void_p))
+    return [flat[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
+def _csr(sketches):
+    rows = [np.ascontiguousarray(x, dtype=np.uint64).ravel() for x in sketches]
+    off = np.zeros(len(rows) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in rows]) if rows else []
+    flat = np.concatenate(rows) if rows and off[-1] else np.zeros(1, np.uint64)
+    return flat, off
+
+
+class FracMinHashSketch:
+    """sourmash KmerMinHash as superaai builds it (superaai.rs:119-153): the `num` smallest distinct MurmurHash3 (seed 42) values of the
+    k-byte windows of a proteome that pass the `scaled` threshold (SPEC 9). scaled = 0: no threshold; num = 0: no bound."""
+
+    def __init__(self, k=7, scaled=100, num=5120, ctx=None):
+        self.k, self.scaled, self.num = int(k), int(scaled), int(num)
+        self.ctx = ctx or default_context()
+
+    def max_hash(self):
+        return frac_max_hash(self.scaled)
+
+    def sketch_genomes(self, genomes):
+        """genomes: list of lists of records (bytes; '\\n' and '\\r' are dropped, every other byte kept) -> list of ascending uint64 arrays"""
+        recs, goff = [], [0]
+        for g in genomes:
+            recs.extend(bytes(r) for r in g)
+            goff.append(len(recs))
+        lens = np.array([len(r) for r in recs], dtype=np.uint64)
+        end = np.cumsum(lens).astype(np.uint64) if len(recs) else np.zeros(0, np.uint64)
+        beg = (end - lens).astype(np.uint64)
+        text = np.frombuffer(b"".join(recs) + b"\0", dtype=np.uint8)
+        goff = np.array(goff, dtype=np.uint64)
+        off = np.zeros(len(goff), np.uint64)
+        hp = C.POINTER(C.c_uint64)()
+        check(self.ctx.L.gs_frac_sketch_batch(self.ctx.h, self.k, self.scaled, self.num, _p(text), len(text) - 1, _p(beg), _p(end), len(recs), _p(goff),
+                                              len(goff) - 1, C.byref(hp), _p(off)))
+        return _take_csr(self.ctx.L, hp, off)
+
+    def sketch_files(self, paths, threads=0, return_stats=False):
+        """one sketch per file with superaai's reader rules: FASTA or FASTQ (plain / gz / bz2 / xz; zstd is refused), no capsid or length
+        filter -> list of ascending uint64 arrays (and, with return_stats, records and residues per file and a stats dict)"""
+        paths = [str(x).encode() for x in paths]
+        n = len(paths)
+        arr = (C.c_char_p * max(n, 1))(*paths)
+        off = np.zeros(n + 1, np.uint64)
+        nrec, nb, st = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint64), np.zeros(4, np.float64)
+        hp = C.POINTER(C.c_uint64)()
+        check(self.ctx.L.gs_frac_sketch_files(self.ctx.h, self.k, self.scaled, self.num, arr, n, int(threads), C.byref(hp), _p(off), _p(nrec), _p(nb), _p(st)))
+        sk = _take_csr(self.ctx.L, hp, off)
+        if return_stats:
+            return sk, nrec[:n], nb[:n], {"host_read_decode_scan_s": st[0], "pcie_wait_s": st[1], "device_s": st[2], "wall_s": st[3]}
+        return sk
+
+
+def frac_max_hash(scaled):
+    """sourmash max_hash_for_scaled (SPEC 9)"""
+    return int(_lib.load().gs_frac_max_hash(int(scaled)))
+
+
+def frac_similarity_qxc(Q, R, num, return_counts=False, ctx=None):
+    """sourmash similarity of every (query, reference) pair of ascending sketches -> (nq, nr) float64; with return_counts also the
+    (nq, nr) uint32 arrays of |A n B n U| and |U| (SPEC 9)"""
+    ctx = ctx or default_context()
+    q, qo = _csr(Q)
+    r, ro = _csr(R)
+    nq, nr = len(qo) - 1, len(ro) - 1
+    sim = np.zeros((nq, nr), np.float64)
+    com = np.zeros((nq, nr), np.uint32) if return_counts else None
+    uni = np.zeros((nq, nr), np.uint32) if return_counts else None
+    check(ctx.L.gs_frac_similarity_qxc(ctx.h, int(num), _p(q), _p(qo), nq, _p(r), _p(ro), nr, _p(sim), _p(com), _p(uni)))
+    return (sim, com, uni) if return_counts else sim
+
+
+def frac_similarity_qxc_dev(ctx, num, Q_dev, q_off_dev, nq, R_dev, r_off_dev, nr, sim_out_dev, common_out_dev=None, union_out_dev=None):
+    check(ctx.L.gs_frac_similarity_qxc_dev(ctx.h, int(num), Q_dev, q_off_dev, int(nq), R_dev, r_off_dev, int(nr), sim_out_dev, common_out_dev, union_out_dev))
+
+
+def aai(sim, k):
+    """superaai.rs:159: 1 + ln(2 sim / (1 + sim)) / k, f64 with the C library's log"""
+    return _lib.load().gs_aai(float(sim), int(k))
+
+
+def read_list_lines(path):
+    """superaai.rs:97-113 (BufRead::lines().filter_map(Result::ok)): '\\n' or '\\r\\n' stripped, a last line without a terminator kept, a line
+    that is not UTF-8 dropped, a blank line KEPT"""
+    with open(path, "rb") as f:
+        data = f.read()
+    lines = data.split(b"\n")
+    last = lines.pop()                      # what follows the last '\\n': a line without a terminator, kept as it is (a '\\r' included)
+    out = []
+    for x in lines + ([last] if last else []):
+        if x is not last and x.endswith(b"\r"):
+            x = x[:-1]
+        try:
+            out.append(x.decode("utf-8"))
+        except UnicodeDecodeError:
+            continue
+    return out
+
+
+def write_superaai(out, query_paths, ref_paths, sim, k):
+    """superaai.rs:160,165: `q\\tr\\t{sim}\\t{aai}` per pair, query-major, joined by '\\n', no trailing newline, Rust Display of f64"""
+    qp = [str(x).encode() for x in query_paths]
+    rp = [str(x).encode() for x in ref_paths]
+    sim = np.ascontiguousarray(sim, dtype=np.float64).reshape(len(qp), len(rp))
+    qa, ra = (C.c_char_p * max(len(qp), 1))(*qp), (C.c_char_p * max(len(rp), 1))(*rp)
+    check(_lib.load().gs_superaai_write(str(out).encode(), qa, len(qp), ra, len(rp), _p(sim), int(k)))
+
+
+def superaai(query_list, ref_list, out, k=7, scaled=100, sketch=5120, threads=0, ctx=None):
+    """superaai (binaux/src/bin/superaai.rs): list files of query and reference proteomes in, upstream's text at `out` (a path). Each distinct
+    file is sketched once; the similarity of every pair runs on the device. A blank line of a list is a path: the call then fails with
+    GS_ERR_IO before anything is written. Returns the (nq, nr) similarity matrix."""
+    import os
+    qp, rp = read_list_lines(query_list), read_list_lines(ref_list)
+    for x in qp + rp:
+        if not os.path.isfile(x):
+            raise GsError(_lib.GS_ERR_IO, "cannot open %r" % x)
+    uniq = list(dict.fromkeys(qp + rp))
+    sk = FracMinHashSketch(k, scaled, sketch, ctx)
+    sks = sk.sketch_files(uniq, threads=threads) if uniq else []
+    at = {p: sks[i] for i, p in enumerate(uniq)}
+    if qp and rp:
+        sim = frac_similarity_qxc([at[x] for x in qp], [at[x] for x in rp], sketch, ctx=sk.ctx)
+    else:
+        sim = np.zeros((len(qp), len(rp)), np.float64)
+    write_superaai(out, qp, rp, sim, k)
+    return sim
+
+
+# ----------------------------------------------------------------------------------------------------------
 class DistHamming:
     """anndists::dist::DistHamming — eval(a, b) = count(a[i] != b[i]) / len, f32."""
 

@@ -30,7 +30,11 @@
 
 namespace gs {
 int ingest_records_dev(gs_ctx *c, bool aa, bool contiguous, const void *text_dev, uint64_t n_bytes, const uint64_t *seq_begin, const uint64_t *seq_end,
-                       uint64_t n_rec, void *out_dev, uint64_t out_base0, uint64_t *rec_start_out, uint64_t *rec_len_out, uint64_t *out_end);
+                       uint64_t n_rec, void *out_dev, uint64_t out_base0, uint64_t *rec_start_out, uint64_t *rec_len_out, uint64_t *out_end, bool raw = false);
+int frac_sketch_to_host(gs_ctx *c, uint32_t k, uint32_t scaled, uint32_t num, const uint8_t *seq_dev, const uint64_t *rec_start, const uint64_t *rec_len,
+                        uint64_t n_rec, const uint64_t *goff, uint64_t ng, std::vector<std::vector<uint64_t>> &rows);
+int frac_check_k(uint32_t k);
+struct FracFiles { uint32_t k, scaled, num; std::vector<std::vector<uint64_t>> rows; };   // block_mode 3 (gs_frac_sketch_files): parameters and per-file sketches
 
 // growable byte buffer WITHOUT value initialisation (std::vector::resize zero-fills: one wasted pass over every file)
 struct Bytes {
@@ -248,6 +252,7 @@ struct FileBlob {       // one file after the host stage
     bool want_bgzf = false; std::vector<GzBlock> blocks;
     std::vector<uint64_t> sb, se; int rc = GS_OK; std::string err; double read_s = 0;
     uint32_t hmh_k = 0;                   // != 0: hypermash's reader rules (scan_records_hmh) for k-mers of this size
+    bool frac = false;                    // superaai's reader rules: those of hypermash without the record-length filter
 };
 static bool has_compressed_suffix(const char *path)
 {
@@ -281,7 +286,7 @@ static uint64_t seq_len_no_eol(const uint8_t *t, uint64_t b, uint64_t e)
     }
     return len;
 }
-static int scan_records_hmh(const uint8_t *text, size_t n, uint32_t k, std::vector<uint64_t> &sb, std::vector<uint64_t> &se)
+static int scan_records_hmh(const uint8_t *text, size_t n, uint32_t k, std::vector<uint64_t> &sb, std::vector<uint64_t> &se, bool keep_all = false)
 {
     GS_REQUIRE(!(n >= 4 && text[0] == 0x28 && text[1] == 0xB5 && text[2] == 0x2F && text[3] == 0xFD), GS_ERR_UNSUPPORTED, "zstd input is not supported");
     size_t i = 0;
@@ -297,6 +302,7 @@ static int scan_records_hmh(const uint8_t *text, size_t n, uint32_t k, std::vect
         sb.resize(nr); se.resize(nr);
         if ((rc = gs_fasta_scan((const char *)text, n, 0, nr, sb.data(), se.data(), nullptr, nullptr, &nr))) return rc;
     }
+    if (keep_all) return GS_OK;
     size_t w = 0;
     for (size_t r = 0; r < nr; r++)
         if (seq_len_no_eol(text, sb[r], se[r]) > k) { sb[w] = sb[r]; se[w] = se[r]; w++; }
@@ -401,7 +407,8 @@ static void host_stage(const char *path, FileBlob *b)
         b->rc = read_fasta(path, b->text);
         text = b->text.data(); n = b->text.size();
     }
-    if (b->rc == GS_OK) b->rc = b->hmh_k ? scan_records_hmh(text, n, b->hmh_k, b->sb, b->se) : scan_records(text, n, b->sb, b->se);
+    if (b->rc == GS_OK) b->rc = b->frac ? scan_records_hmh(text, n, 0, b->sb, b->se, true)
+                                      : b->hmh_k ? scan_records_hmh(text, n, b->hmh_k, b->sb, b->se) : scan_records(text, n, b->sb, b->se);
     if (b->rc) b->err = gs_last_error();                          // thread-local: carry it to the caller's thread
     b->read_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -473,6 +480,8 @@ int gs_list_fasta_files(const char *dir, int data_t, char *paths_buf, uint64_t c
  *   block_mode 0  by sequence: every record is its own sequence, k-mers never span records (process_file_by_sequence)
  *   block_mode 1  --block: the records of a file are concatenated, k-mers span the joins (process_file_in_one_block)
  *   block_mode 2  (internal, gs_hmh_sketch_files) by sequence, with hypermash's reader rules: FASTA or FASTQ, no capsid filter, records of <= k bases skipped
+ *   block_mode 3  (internal, gs_frac_sketch_files) superaai's FracMinHash sketches (SPEC 9): FASTA or FASTQ, no capsid filter, no length filter,
+ *                 every byte but '\n' / '\r' kept; the variable-length sketches go to `frac->rows` instead of sig_out
  * `capsid` records are skipped in both (dnafiles.rs:62-67,245). pio = files per group (`--pio`, files.rs:258-341; 0 -> 64),
  * n_threads = host threads that read / decompress / scan (0 -> hardware concurrency).
  * sig_out: HOST, n_files x sketch_size elements. n_records_out / n_symbols_out (optional, HOST, per file): records kept and bases /
@@ -508,7 +517,8 @@ struct GzDeal {
 static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *const *paths, uint64_t n_files, int block_mode, uint32_t pio, uint32_t n_threads,
                              void *sig_out, uint64_t *n_records_out, uint64_t *n_symbols_out, double *stats_out, bool dev_gzip, std::vector<uint64_t> *redo,
                              const uint64_t *out_index /* row of file f in the outputs; NULL: f */, int lookahead /* groups read ahead; 0: default */,
-                             GzDeal *deal /* optional */, bool from_back, uint64_t n_free /* leading files of the list that need no claim */)
+                             GzDeal *deal /* optional */, bool from_back, uint64_t n_free /* leading files of the list that need no claim */,
+                             gs::FracFiles *frac = nullptr /* block_mode 3 */)
 {
     int rc = gs_check_params(p);
     if (rc) return rc;
@@ -517,7 +527,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
     const auto t_call = std::chrono::steady_clock::now();
-    const bool aa = p->data_t == GS_DATA_AA;
+    const bool aa = p->data_t == GS_DATA_AA || block_mode == 3;
     struct WaitMode { gs_ctx *c; bool prev; ~WaitMode() { c->wait_sleeping = prev; } } wait_mode{c, c->wait_sleeping};
     c->wait_sleeping = dev_gzip;     // the device pipeline waits for hundreds of milliseconds at a time: asleep; the host pipeline: spinning
     if (pio == 0) {                  // small groups overlap best on the host path (measured: 32 files per group 3200 genomes/s, 64: 2400, 256: 900);
@@ -591,6 +601,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
         }
         blobs[g].resize(f1 - f0);
         if (block_mode == 2) for (auto &fb : blobs[g]) fb.hmh_k = p->k;
+        if (block_mode == 3) for (auto &fb : blobs[g]) fb.frac = true;
         if (f1 == f0) return;
         {   // size the plain files and give each its place in this group's pinned buffer (its previous user, group g-4, is long done)
             const int sl = (int)(g % NSLOT);
@@ -889,7 +900,8 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
         GS_HIP_CHECK(hipMemsetAsync(dout.p, 0, out_bytes, c->stream));
         std::vector<uint64_t> rs(std::max<uint64_t>(nrec, 1)), rl(std::max<uint64_t>(nrec, 1)), goff(nf + 1), rs2, rl2;
         if (block_mode != 1) {
-            if ((rc2 = gs::ingest_records_dev(c, aa, false, dtext[b].p, S.bytes, S.sb.data(), S.se.data(), nrec, dout.p, 0, rs.data(), rl.data(), nullptr))) return rc2;
+            if ((rc2 = gs::ingest_records_dev(c, aa, false, dtext[b].p, S.bytes, S.sb.data(), S.se.data(), nrec, dout.p, 0, rs.data(), rl.data(), nullptr, block_mode == 3)))
+                return rc2;
             for (uint64_t f = 0; f <= nf; f++) goff[f] = S.frec[f];
             rs2.assign(rs.begin(), rs.begin() + nrec); rl2.assign(rl.begin(), rl.begin() + nrec);
         } else {   // one record per file: its records concatenated without gaps
@@ -905,6 +917,21 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
             goff[nf] = nf;
         }
         const uint64_t nr2 = rs2.size();
+        if (frac) {      // superaai: variable-length sketches, one per file of the group
+            std::vector<std::vector<uint64_t>> rows;
+            if ((rc2 = gs::frac_sketch_to_host(c, frac->k, frac->scaled, frac->num, (const uint8_t *)dout.p, rs2.data(), rl2.data(), nr2, goff.data(), nf, rows))) return rc2;
+            sub(3);
+            for (uint64_t f = 0; f < nf; f++) {
+                uint64_t sym = 0;
+                for (uint64_t r = S.frec[f]; r < S.frec[f + 1]; r++) sym += rl[r];
+                const uint64_t row = out_index ? out_index[f0 + f] : f0 + f;
+                frac->rows[row] = std::move(rows[f]);
+                if (n_records_out) n_records_out[row] = S.frec[f + 1] - S.frec[f];
+                if (n_symbols_out) n_symbols_out[row] = sym;
+            }
+            dev_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            return GS_OK;
+        }
         if ((rc2 = drs.ensure(8 * (nr2 + 1))) || (rc2 = drl.ensure(8 * (nr2 + 1))) || (rc2 = dgo.ensure(8 * (nf + 1))) || (rc2 = dsig.ensure(nf * m * esz))) return rc2;
         if (nr2) {
             GS_HIP_CHECK(hipMemcpyAsync(drs.p, rs2.data(), 8 * nr2, hipMemcpyHostToDevice, c->stream));
@@ -1038,6 +1065,33 @@ int gs_hmh_sketch_files(gs_ctx *c, uint32_t k, const char *const *paths, uint64_
     rc = sketch_files_impl(c, &p, paths, n_files, 2, 0, n_threads, sig_out, n_records_out, n_bases_out, st, false, nullptr, nullptr, 0, nullptr, false, 0);
     if (rc) return rc;
     if (stats_out) for (int i = 0; i < 4; i++) stats_out[i] = st[i];
+    return GS_OK;
+}
+// superaai's sketches (include/gsearch_amd.h): the host pipeline of gs_sketch_files in its superaai mode (block_mode 3), every .gz file through
+// the host decoders, whose scan is the one that knows FASTQ; the sketches come back as a library-allocated CSR
+int gs_frac_sketch_files(gs_ctx *c, uint32_t k, uint32_t scaled, uint32_t num, const char *const *paths, uint64_t n_files, uint32_t n_threads,
+                         uint64_t **hash_out, uint64_t *off_out, uint64_t *n_records_out, uint64_t *n_bytes_out, double *stats_out)
+{
+    int rc = gs::frac_check_k(k);
+    if (rc) return rc;
+    GS_REQUIRE(c && hash_out && off_out && (n_files == 0 || paths), GS_ERR_INVALID, "null argument");
+    for (uint64_t f = 0; f < n_files; f++) GS_REQUIRE(paths[f], GS_ERR_INVALID, "null path %llu", (unsigned long long)f);
+    *hash_out = nullptr;
+    const gs_sketch_params p = {7, 2, GS_ALGO_PROB3A, GS_DATA_AA};      // (only to pass the pipeline's parameter check: block_mode 3 reads `frac`)
+    gs::FracFiles fr{k, scaled, num, {}};
+    fr.rows.resize(n_files);
+    uint8_t dummy[16];
+    double st[4] = {0, 0, 0, 0};
+    rc = sketch_files_impl(c, &p, paths, n_files, 3, 0, n_threads, dummy, n_records_out, n_bytes_out, st, false, nullptr, nullptr, 0, nullptr, false, 0, &fr);
+    if (rc) return rc;
+    if (stats_out) for (int i = 0; i < 4; i++) stats_out[i] = st[i];
+    uint64_t tot = 0;
+    off_out[0] = 0;
+    for (uint64_t f = 0; f < n_files; f++) { tot += fr.rows[f].size(); off_out[f + 1] = tot; }
+    uint64_t *h = (uint64_t *)malloc(8 * std::max<uint64_t>(tot, 1));
+    GS_REQUIRE(h, GS_ERR_INVALID, "out of host memory (%llu values)", (unsigned long long)tot);
+    for (uint64_t f = 0; f < n_files; f++) if (!fr.rows[f].empty()) memcpy(h + off_out[f], fr.rows[f].data(), 8 * fr.rows[f].size());
+    *hash_out = h;
     return GS_OK;
 }
 // the round-1 contract: FOUR doubles (the array grew to six under the same symbol - a caller that passes double[4] was written out of bounds)

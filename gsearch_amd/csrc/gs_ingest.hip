@@ -92,6 +92,9 @@ __device__ __forceinline__ bool aa_valid(uint8_t c)
     // A C D E F G H I K L M N P Q R S T V W Y  (not B J O U X Z)
     return (0x016FBDFDu >> (u - 'A')) & 1u;
 }
+// superaai's reader (SPEC 9): a record's sequence is its bytes with '\n' and '\r' removed, nothing else changed
+__device__ __forceinline__ bool raw_valid(uint8_t c) { return c != '\n' && c != '\r'; }
+template <bool RAW>
 __global__ __launch_bounds__(PK_T) void k_aa_count(const uint8_t *__restrict__ text, const uint64_t *__restrict__ cb, const uint64_t *__restrict__ ce,
                                                     uint32_t *__restrict__ counts)
 {
@@ -100,12 +103,13 @@ __global__ __launch_bounds__(PK_T) void k_aa_count(const uint8_t *__restrict__ t
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
     uint32_t loc = 0;
-    for (uint64_t i = cb[c] + threadIdx.x; i < ce[c]; i += PK_T) loc += aa_valid(text[i]);
+    for (uint64_t i = cb[c] + threadIdx.x; i < ce[c]; i += PK_T) loc += RAW ? raw_valid(text[i]) : aa_valid(text[i]);
     for (int o = 32; o > 0; o >>= 1) loc += __shfl_down(loc, o);
     if ((threadIdx.x & 63) == 0 && loc) atomicAdd(&s_n, loc);
     __syncthreads();
     if (threadIdx.x == 0) counts[c] = s_n;
 }
+template <bool RAW>
 __global__ __launch_bounds__(PK_T) void k_aa_write(const uint8_t *__restrict__ text, const uint64_t *__restrict__ cb, const uint64_t *__restrict__ ce,
                                                     const uint64_t *__restrict__ out_base, uint8_t *__restrict__ out)
 {
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(PK_T) void k_aa_write(const uint8_t *__restrict__ t
     for (uint64_t i0 = b0; i0 < b1; i0 += PK_T) {
         const uint64_t i = i0 + threadIdx.x;
         const uint8_t ch = i < b1 ? text[i] : 0;
-        const bool ok = i < b1 && aa_valid(ch);
+        const bool ok = i < b1 && (RAW ? raw_valid(ch) : aa_valid(ch));
         const uint64_t bal = __ballot(ok);
         if (lane == 0) s_wave[wv] = (uint32_t)__popcll(bal);
         __syncthreads();
@@ -132,9 +136,10 @@ __global__ __launch_bounds__(PK_T) void k_aa_write(const uint8_t *__restrict__ t
 }
 
 // shared driver of the DNA pack and the AA filter. contiguous = the records follow one another without alignment gaps and form ONE
-// output record (--block: process_file_in_one_block appends every record to one Sequence, k-mers span the joins, dnafiles.rs:200-262)
+// output record (--block: process_file_in_one_block appends every record to one Sequence, k-mers span the joins, dnafiles.rs:200-262).
+// raw (with aa): superaai's reader - every byte but '\n' and '\r' kept as it is, one byte per residue
 int ingest_records_dev(gs_ctx *c, bool aa, bool contiguous, const void *text_dev, uint64_t n_bytes, const uint64_t *seq_begin, const uint64_t *seq_end,
-                       uint64_t n_rec, void *out_dev, uint64_t out_base0, uint64_t *rec_start_out, uint64_t *rec_len_out, uint64_t *out_end)
+                       uint64_t n_rec, void *out_dev, uint64_t out_base0, uint64_t *rec_start_out, uint64_t *rec_len_out, uint64_t *out_end, bool raw = false)
 {
     if (out_end) *out_end = out_base0;
     if (n_rec == 0) return GS_OK;
@@ -157,7 +162,8 @@ int ingest_records_dev(gs_ctx *c, bool aa, bool contiguous, const void *text_dev
     if ((rc = dbase.alloc(8 * nch))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(dcb.p, cb.data(), 8 * nch, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(dce.p, ce.data(), 8 * nch, hipMemcpyHostToDevice, c->stream));
-    if (aa) hipLaunchKernelGGL(k_aa_count, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dcnt.as<uint32_t>());
+    if (aa && raw) hipLaunchKernelGGL(k_aa_count<true>, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dcnt.as<uint32_t>());
+    else if (aa) hipLaunchKernelGGL(k_aa_count<false>, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dcnt.as<uint32_t>());
     else hipLaunchKernelGGL(k_pack_count, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dcnt.as<uint32_t>());
     GS_HIP_CHECK(hipGetLastError());
     std::vector<uint32_t> cnt(nch);
@@ -174,7 +180,8 @@ int ingest_records_dev(gs_ctx *c, bool aa, bool contiguous, const void *text_dev
     if (contiguous) { rec_len_out[0] = pos - rec_start_out[0]; for (uint64_t r = 1; r < n_rec; r++) { rec_start_out[r] = pos; rec_len_out[r] = 0; } }
     if (out_end) *out_end = pos;
     GS_HIP_CHECK(hipMemcpyAsync(dbase.p, base.data(), 8 * nch, hipMemcpyHostToDevice, c->stream));
-    if (aa) hipLaunchKernelGGL(k_aa_write, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dbase.as<uint64_t>(), (uint8_t *)out_dev);
+    if (aa && raw) hipLaunchKernelGGL(k_aa_write<true>, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dbase.as<uint64_t>(), (uint8_t *)out_dev);
+    else if (aa) hipLaunchKernelGGL(k_aa_write<false>, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dbase.as<uint64_t>(), (uint8_t *)out_dev);
     else hipLaunchKernelGGL(k_pack_write, dim3((uint32_t)nch), dim3(PK_T), 0, c->stream, (const uint8_t *)text_dev, dcb.as<uint64_t>(), dce.as<uint64_t>(), dbase.as<uint64_t>(), (uint32_t *)out_dev);
     GS_HIP_CHECK(hipGetLastError());
     GS_HIP_CHECK(gs::stream_wait(c));

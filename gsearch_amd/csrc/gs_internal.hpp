@@ -272,7 +272,7 @@ struct VmArena {
 // Per-context scratch: a call's temporaries come from numbered grow-only slots instead of hipMalloc/hipFree (allocating and freeing
 // multi-GB buffers costs more than the kernels that use them). A context serves one call at a time (one stream), so slots are never
 // shared; gs_ctx_release_scratch / gs_ctx_destroy give the memory back.
-enum { SCRATCH_SLOTS = 104 };       // 48-52: staging of gs_sketch_batch, 53-57: of gs_hamming_qxc / gs_hamming_pairs (host-pointer calls), 64-79: hypermash, 80-103: ann
+enum { SCRATCH_SLOTS = 136 };       // 48-52: staging of gs_sketch_batch, 53-57: of gs_hamming_qxc / gs_hamming_pairs (host-pointer calls), 64-79: hypermash, 80-103: ann, 104-135: superaai
 struct ScratchPool { DevBuf b[SCRATCH_SLOTS]; };
 enum { PINNED_SLOTS = 36 };      // 0-15 text, 16-31 compressed members, 32-33 inflate descriptors / results
 struct PinnedPool {

@@ -329,4 +329,47 @@ GS_HD uint64_t embed_neg(uint64_t ekey, uint64_t i, uint32_t S, uint32_t s, uint
     return mulhi64(splitmix_mix(splitmix_mix(ekey) + GS_GAMMA * (i * S + s + 1)), n);
 }
 
+// ---- SPEC 9: FracMinHash / bottom-k sketches of superaai (binaux/src/bin/superaai.rs) ------------------------------------------------
+#define GS_FRAC_SEED 42ULL               // [REF] superaai.rs:123,133,143,153: the literal seed of every hash
+#define GS_FRAC_KMAX 32u                 // [CHOICE] 1 <= k <= 32
+#define GS_MM3_C1 0x87c37b91114253d5ULL  // [PUB] SMHasher MurmurHash3_x64_128
+#define GS_MM3_C2 0x4cf5ad432745937fULL
+GS_HD uint64_t mm3_fmix64(uint64_t k)
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL;
+    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL;
+    k ^= k >> 33;
+    return k;
+}
+// h1 of MurmurHash3_x64_128 over len (<= 32) bytes held little-endian in w0..w3 (bytes past len are zero), seed GS_FRAC_SEED:
+// 16-byte blocks, then the tail (its bytes 8..14 into k2, 0..7 into k1), then the finalisation. sourmash's _hash_murmur keeps h1.
+GS_HD void mm3_block(uint64_t &h1, uint64_t &h2, uint64_t k1, uint64_t k2)
+{
+    k1 *= GS_MM3_C1; k1 = rotl64(k1, 31); k1 *= GS_MM3_C2; h1 ^= k1;
+    h1 = rotl64(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
+    k2 *= GS_MM3_C2; k2 = rotl64(k2, 33); k2 *= GS_MM3_C1; h2 ^= k2;
+    h2 = rotl64(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
+}
+GS_HD uint64_t mm3_h1_4(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t w3, uint32_t len)
+{
+    uint64_t h1 = GS_FRAC_SEED, h2 = GS_FRAC_SEED;
+    if (len >= 16) mm3_block(h1, h2, w0, w1);
+    if (len >= 32) mm3_block(h1, h2, w2, w3);
+    const uint32_t rem = len & 15;
+    const uint64_t t1 = len >= 16 ? w2 : w0, t2 = len >= 16 ? w3 : w1;
+    if (rem > 8) { uint64_t k2 = t2; k2 *= GS_MM3_C2; k2 = rotl64(k2, 33); k2 *= GS_MM3_C1; h2 ^= k2; }
+    if (rem > 0) { uint64_t k1 = t1; k1 *= GS_MM3_C1; k1 = rotl64(k1, 31); k1 *= GS_MM3_C2; h1 ^= k1; }
+    h1 ^= len; h2 ^= len;
+    h1 += h2; h2 += h1;
+    h1 = mm3_fmix64(h1); h2 = mm3_fmix64(h2);
+    return h1 + h2;
+}
+// sourmash max_hash_for_scaled (recalled): 0 -> 0 (no filter), 1 -> 2^64-1, else (u64)((f64)(2^64-1) / (f64)scaled), truncated
+inline uint64_t frac_max_hash(uint32_t scaled)
+{
+    if (scaled == 0) return 0;
+    if (scaled == 1) return ~0ULL;
+    return (uint64_t)((double)~0ULL / (double)scaled);
+}
+
 }  // namespace gs

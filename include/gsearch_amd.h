@@ -198,6 +198,42 @@ int gs_hmh_sketch_files(gs_ctx *, uint32_t k, const char *const *paths, uint64_t
                         uint64_t *n_records_out, uint64_t *n_bases_out, double *stats_out);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* superaai (binaux/src/bin/superaai.rs): FracMinHash / bottom-k sketches of proteomes (MurmurHash3_x64_128 h1, seed 42, of every k-byte
+ * window of a record) and the AAI of every query x reference pair. Arithmetic: SPEC 9. 1 <= k <= 32 (larger k: GS_ERR_UNSUPPORTED);
+ * scaled = 0: no threshold; num = 0: no bound on the sketch size. A sketch is the num smallest distinct hashes <= gs_frac_max_hash(scaled), ascending. */
+/* sourmash max_hash_for_scaled: 0 -> 0, 1 -> 2^64-1, else (u64)((f64)(2^64-1) / scaled) */
+uint64_t gs_frac_max_hash(uint32_t scaled);
+/* host text in, library-allocated host CSR out: record r = bytes [rec_begin[r], rec_end[r]) of text, '\n' and '\r' dropped, every other byte kept;
+ * genome g = records [genome_rec_off[g], genome_rec_off[g+1]). *hash_out (release with gs_host_free): the sketches end to end, genome g's at
+ * [off_out[g], off_out[g+1]); off_out: n_genomes + 1 entries. */
+int gs_frac_sketch_batch(gs_ctx *, uint32_t k, uint32_t scaled, uint32_t num, const void *text, uint64_t n_bytes, const uint64_t *rec_begin,
+                         const uint64_t *rec_end, uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes, uint64_t **hash_out, uint64_t *off_out);
+/* device form: residues (no line breaks) on the device, record r = [rec_start[r], rec_start[r] + rec_len[r]) of seq_dev, all arrays device memory.
+ * Genome g's sketch goes to hash_out_dev[g * cap ...], its true size to count_out_dev[g]; a sketch longer than cap is cut at cap and the call
+ * returns GS_ERR_INVALID (the counts are written first). */
+int gs_frac_sketch_batch_dev(gs_ctx *, uint32_t k, uint32_t scaled, uint32_t num, const void *seq_dev, uint64_t n_bytes, const uint64_t *rec_start_dev,
+                             const uint64_t *rec_len_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes, uint32_t cap,
+                             uint64_t *hash_out_dev, uint32_t *count_out_dev);
+/* sourmash similarity (jaccard with the union bounded to num) of every (query, reference) pair of ascending, distinct sketches in CSR form
+ * (Q[q_off[i] .. q_off[i+1]), R likewise) -> sim_out[nq x nr] (f64, query-major); common_out / union_out (optional, u32): |A n B n U| and |U|.
+ * The _dev form queues on the context's stream (it reads q_off_dev back once) and does not check that the sketches are ascending. */
+int gs_frac_similarity_qxc(gs_ctx *, uint32_t num, const uint64_t *Q, const uint64_t *q_off, uint64_t nq, const uint64_t *R, const uint64_t *r_off,
+                           uint64_t nr, double *sim_out, uint32_t *common_out, uint32_t *union_out);
+int gs_frac_similarity_qxc_dev(gs_ctx *, uint32_t num, const uint64_t *Q_dev, const uint64_t *q_off_dev, uint64_t nq, const uint64_t *R_dev,
+                               const uint64_t *r_off_dev, uint64_t nr, double *sim_out_dev, uint32_t *common_out_dev, uint32_t *union_out_dev);
+/* One sketch per file, input order, with superaai's reader rules: FASTA or FASTQ (by the first non-blank byte), plain / gz / bz2 / xz (zstd:
+ * GS_ERR_UNSUPPORTED), no capsid filter, no length filter; all records of a file feed its sketch, k-mers never span records. Output as
+ * gs_frac_sketch_batch (off_out: n_files + 1). n_records_out / n_bytes_out: optional per-file records and residues; stats_out: optional,
+ * the first four doubles of gs_sketch_files. */
+int gs_frac_sketch_files(gs_ctx *, uint32_t k, uint32_t scaled, uint32_t num, const char *const *paths, uint64_t n_files, uint32_t n_threads,
+                         uint64_t **hash_out, uint64_t *off_out, uint64_t *n_records_out, uint64_t *n_bytes_out, double *stats_out);
+/* superaai.rs:159: 1 + ln(2 sim / (1 + sim)) / k, f64, C library log; sim = 0 -> -inf */
+double gs_aai(double sim, uint32_t k);
+/* superaai.rs:160,165: writes `q\tr\t{sim}\t{aai}` for every pair, query-major, lines joined by '\n' (no trailing newline, no header), f64 as
+ * Rust's Display (shortest round-trip digits, never an exponent); sim: nq x nr. GS_ERR_IO when the file cannot be written. */
+int gs_superaai_write(const char *out_path, const char *const *q_paths, uint64_t nq, const char *const *r_paths, uint64_t nr, const double *sim, uint32_t k);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */
 /*   new/modify_level_scale/set_extend_candidates/set_keeping_pruned  dnasketch.rs:139-141,159-160  */
 /*   parallel_insert dnasketch.rs:435, aasketch.rs:407;  parallel_search dnarequest.rs:353, aarequest.rs:344 */

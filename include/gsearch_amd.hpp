@@ -177,6 +177,31 @@ inline std::vector<uint16_t> hmh_sketch_files(Context &ctx, uint32_t k, const st
 }
 inline double hypermash_distance(double sim, int kmer) { return gs_hmh_distance(sim, kmer); }
 
+// superaai (binaux/src/bin/superaai.rs; sourmash KmerMinHash, SPEC 9): FracMinHash / bottom-k sketches of proteome files (ascending u64 values per
+// file), the similarity of every query x reference pair (query-major) and the AAI
+struct FracSketches { std::vector<uint64_t> values, off; };        // file f: values[off[f] .. off[f+1])
+inline FracSketches frac_sketch_files(Context &ctx, const std::vector<std::string> &paths, uint32_t k = 7, uint32_t scaled = 100, uint32_t num = 5120,
+                                      uint32_t n_threads = 0)
+{
+    std::vector<const char *> p;
+    for (const auto &x : paths) p.push_back(x.c_str());
+    FracSketches out;
+    out.off.resize(paths.size() + 1);
+    uint64_t *h = nullptr;
+    check(gs_frac_sketch_files(ctx.get(), k, scaled, num, p.data(), p.size(), n_threads, &h, out.off.data(), nullptr, nullptr, nullptr));
+    out.values.assign(h, h + out.off.back());
+    gs_host_free(h);
+    return out;
+}
+inline std::vector<double> frac_similarity_qxc(Context &ctx, uint32_t num, const FracSketches &Q, const FracSketches &R)
+{
+    const uint64_t nq = Q.off.size() - 1, nr = R.off.size() - 1;
+    std::vector<double> out(nq * nr);
+    check(gs_frac_similarity_qxc(ctx.get(), num, Q.values.data(), Q.off.data(), nq, R.values.data(), R.off.data(), nr, out.data(), nullptr, nullptr));
+    return out;
+}
+inline double aai(double sim, uint32_t k) { return gs_aai(sim, k); }
+
 // hnsw_rs::Neighbour{d_id, distance, p_id}: gsearch reads d_id (the DataId the point was inserted under: an index into its seqdict) and distance
 // (answer.rs:42,55-57); p_id = PointId(layer, rank in layer)
 struct PointId { uint8_t layer; int32_t rank; };
