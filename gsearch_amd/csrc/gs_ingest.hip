@@ -84,7 +84,8 @@ __global__ __launch_bounds__(PK_T) void k_pack_write(const uint8_t *__restrict__
 }
 
 // amino acids: the same two-pass compaction with one byte per kept residue (aafiles.rs:11-28 filter_out_non_aa: letters outside the
-// 20-letter alphabet - '*', X, B, Z, ..., and here the newlines of the raw text - are dropped; either case is kept as read)
+// 20-letter alphabet - '*', X, B, Z, ..., and here the newlines of the raw text - are dropped; kept letters are written in upper case,
+// like gs_filter_aa on the host: the sketchers read either case, a host that compares residues gets one)
 __device__ __forceinline__ bool aa_valid(uint8_t c)
 {
     const uint32_t u = c & 0xDFu;                                // fold case
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(PK_T) void k_aa_write(const uint8_t *__restrict__ t
         __syncthreads();
         uint32_t off = s_run;
         for (uint32_t w = 0; w < wv; w++) off += s_wave[w];
-        if (ok) out[ob + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1))] = ch;
+        if (ok) out[ob + off + (uint32_t)__popcll(bal & ((1ull << lane) - 1))] = RAW ? ch : (uint8_t)(ch & 0xDFu);
         __syncthreads();
         if (threadIdx.x == 0) { uint32_t t = 0; for (uint32_t w = 0; w < PK_T / 64; w++) t += s_wave[w]; s_run += t; }
         __syncthreads();

@@ -123,7 +123,8 @@ int gs_fasta_scan(const char *buf, uint64_t n, int skip_capsid, uint64_t cap, ui
 int gs_pack_fasta_dev(gs_ctx *, const void *text_dev, uint64_t n_bytes, const uint64_t *seq_begin, const uint64_t *seq_end,
                       uint64_t n_rec, void *packed_dev, uint64_t *rec_start_out, uint64_t *rec_len_out);
 /* amino acids: drop everything outside the 20-letter alphabet (filter_out_non_aa, src/aa/aafiles.rs:11-28; newlines of the raw text go
- * with it) from the text of n_rec records. out_dev: >= n_bytes bytes; rec_start_out / rec_len_out: HOST, residue coordinates. */
+ * with it) from the text of n_rec records; kept letters come out in upper case, as from gs_filter_aa. out_dev: >= n_bytes bytes;
+ * rec_start_out / rec_len_out: HOST, residue coordinates. */
 int gs_filter_aa_dev(gs_ctx *, const void *text_dev, uint64_t n_bytes, const uint64_t *seq_begin, const uint64_t *seq_end,
                      uint64_t n_rec, void *out_dev, uint64_t *rec_start_out, uint64_t *rec_len_out);
 /* ---- files: the reader side of sketchandstore_dir_compressedkmer, src/dna/dnasketch.rs:240-300 ---- */
