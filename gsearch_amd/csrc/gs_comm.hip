@@ -280,7 +280,7 @@ int gs_topk_merge_dev(gs_ctx *c, const uint64_t *ids_dev, const float *dist_dev,
     GS_REQUIRE(N * 12 <= 96 * 1024, GS_ERR_UNSUPPORTED, "gs_topk_merge_dev: %llu keys per query do not fit the LDS", (unsigned long long)N);
     if (nq == 0) return GS_OK;
     GS_CTX_LOCK(c);
-    gs::PoolBuf off(c, 47);
+    gs::PoolBuf off(c, gs::SL_COMM_ID_OFFSET);
     const uint64_t *d_off = nullptr;
     if (id_offset) {
         int rc = off.alloc(8 * (size_t)n_shards); if (rc) return rc;

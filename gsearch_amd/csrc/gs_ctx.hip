@@ -134,7 +134,7 @@ void on_worker_failed(gs_ctx *c)
         if (w->mu.try_lock()) {
             (void)hipSetDevice(w->device);
             (void)hipStreamSynchronize(w->stream);
-            delete (ScratchPool *)w->scratch_pool; w->scratch_pool = nullptr;
+            drop_scratch_pool(w);            // (w may be the failing thread's own worker, with the PoolBufs of its call still alive: see drop_scratch_pool)
             w->mu.unlock();
         }
         worker_unpin(c, w);
@@ -192,7 +192,7 @@ void gs_ctx_destroy(gs_ctx *c)
     if (c->t0) (void)hipEventDestroy(c->t0);
     if (c->t1) (void)hipEventDestroy(c->t1);
     if (c->sync_ev) (void)hipEventDestroy(c->sync_ev);
-    delete (gs::ScratchPool *)c->scratch_pool;
+    gs::drop_scratch_pool(c);
     delete (gs::PinnedPool *)c->pinned_pool;
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -203,8 +203,7 @@ int gs_ctx_release_scratch(gs_ctx *c)
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
     GS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    delete (gs::ScratchPool *)c->scratch_pool;
-    c->scratch_pool = nullptr;
+    gs::drop_scratch_pool(c);
     delete (gs::PinnedPool *)c->pinned_pool;
     c->pinned_pool = nullptr;
     {

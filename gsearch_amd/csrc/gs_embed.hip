@@ -277,7 +277,7 @@ static int graph_args(uint64_t n, uint32_t knbn)
 // the input rules of SPEC 8 on device arrays (waits for the stream)
 int embed_validate(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *cnt)
 {
-    PoolBuf e(c, 80);
+    PoolBuf e(c, SL_EMB_FLAG);
     int rc;
     if ((rc = e.alloc(16))) return rc;
     GS_HIP_CHECK(hipMemsetAsync(e.p, 0, 16, c->stream));
@@ -301,8 +301,8 @@ static int embed_graph_dev(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t 
 {
     const uint32_t D = p->dim;
     int rc;
-    PoolBuf pm(c, 81), keys(c, 82), alt(c, 83), rs(c, 84), range(c, 85), deg(c, 86), off(c, 87), adj(c, 88), w(c, 89), W(c, 90), heavy(c, 91), y0(c, 92),
-        y1(c, 93), nh(c, 80);
+    PoolBuf pm(c, SL_EMB_PM), keys(c, SL_EMB_KEYS), alt(c, SL_EMB_ALT), rs(c, SL_EMB_RADIX), range(c, SL_EMB_RANGE), deg(c, SL_EMB_DEG), off(c, SL_EMB_OFF), adj(c, SL_EMB_ADJ), w(c, SL_EMB_W), W(c, SL_EMB_WSUM), heavy(c, SL_EMB_HEAVY), y0(c, SL_EMB_Y0),
+        y1(c, SL_EMB_Y1), nh(c, SL_EMB_FLAG);
     const uint64_t nk = n * knbn;
     if ((rc = nh.alloc(16)) || (rc = keys.alloc(8 * nk)) || (rc = alt.alloc(8 * nk)) || (rc = rs.alloc(radix_scratch_bytes(nk))) || (rc = range.alloc(16 * n)) ||
         (rc = deg.alloc(4 * n)) || (rc = off.alloc(8 * (n + 1))) || (rc = adj.alloc(8 * nk)) || (rc = w.alloc(8 * nk)) || (rc = W.alloc(4 * n)) ||
@@ -360,7 +360,7 @@ int knn_stats_dev(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t *ids, con
                   uint64_t *hist_out)
 {
     int rc;
-    PoolBuf docc(c, 84), dends(c, 85);
+    PoolBuf docc(c, SL_KST_OCC), dends(c, SL_KST_ENDS);
     if ((rc = docc.alloc(4 * n)) || (rc = dends.alloc(8 * n))) return rc;
     GS_HIP_CHECK(hipMemsetAsync(docc.p, 0, 4 * n, c->stream));
     hipLaunchKernelGGL(k_embed_occ, dim3(nblk(n)), dim3(256), 0, c->stream, ids, cnt, n, knbn, docc.as<uint32_t>());
@@ -418,7 +418,7 @@ static int graph_in(gs_ctx *c, bool on_dev, uint64_t n, uint32_t knbn, const uin
     int rc;
     if (on_dev) { *dids = ids; *ddist = dist; *dcnt = cnt; }
     else {
-        PoolBuf a(c, 94), b(c, 95), d(c, 96);
+        PoolBuf a(c, SL_EMBIN_IDS), b(c, SL_EMBIN_DIST), d(c, SL_EMBIN_COUNT);
         if ((rc = a.alloc(8 * n * knbn)) || (rc = b.alloc(4 * n * knbn)) || (rc = d.alloc(4 * n))) return rc;
         GS_HIP_CHECK(hipMemcpyAsync(a.p, ids, 8 * n * knbn, hipMemcpyHostToDevice, c->stream));
         GS_HIP_CHECK(hipMemcpyAsync(b.p, dist, 4 * n * knbn, hipMemcpyHostToDevice, c->stream));
@@ -436,7 +436,7 @@ int embed_common(gs_ctx *c, bool on_dev, uint64_t n, uint32_t knbn, const uint64
     int rc;
     if ((rc = embed_check_params(&p))) return rc;
     const uint64_t D = p.dim;
-    PoolBuf dinit(c, 97), dpos(c, 98), dmemb(c, 99);
+    PoolBuf dinit(c, SL_EMB_INIT), dpos(c, SL_EMB_POS), dmemb(c, SL_EMB_MEMB);
     const float *ip = init;
     float *pp = pos_out, *mp = memb_out;
     if (!on_dev) {

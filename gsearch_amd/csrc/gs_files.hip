@@ -563,13 +563,13 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
     const int NSLOT = LA + 2;
     // pinned staging buffers live in the context (gs::PinnedPool): they outlast the call, gs_ctx_release_scratch / gs_ctx_destroy free them
     gs::PinnedPool *pool = gs::pinned_pool(c);
-    static_assert(LA_MAX + 2 <= 16, "text slots 0-15, compressed slots 16-31 of the pinned pool");
+    static_assert(LA_MAX + 2 <= gs::PIN_TEXT_N && LA_MAX + 2 <= gs::PIN_COMP_N, "one text and one compressed slot of the pinned pool per group in flight");
     void *pinned[LA_MAX + 2] = {}; size_t pinned_cap[LA_MAX + 2] = {};
-    for (int i = 0; i < NSLOT; i++) { pinned[i] = pool->p[i]; pinned_cap[i] = pool->cap[i]; }
+    for (int i = 0; i < NSLOT; i++) { pinned[i] = pool->p[gs::PIN_TEXT + i]; pinned_cap[i] = pool->cap[gs::PIN_TEXT + i]; }
     std::vector<uint64_t> plain_total(n_groups, 0);
     gs::Bytes cbuf[LA_MAX + 2];                               // per slot: the compressed bytes of the group's .gz files
     void *cpin[LA_MAX + 2] = {}; size_t cpin_cap[LA_MAX + 2] = {};       // per slot, pinned: the members the DEVICE inflates
-    for (int i = 0; i < NSLOT; i++) { cpin[i] = pool->p[16 + i]; cpin_cap[i] = pool->cap[16 + i]; }
+    for (int i = 0; i < NSLOT; i++) { cpin[i] = pool->p[gs::PIN_COMP + i]; cpin_cap[i] = pool->cap[gs::PIN_COMP + i]; }
     std::vector<uint64_t> dev_ctot(n_groups, 0), dev_gtot(n_groups, 0);    // per group: bytes of those members / of their texts
     // A device group is also bounded in BYTES (a group of 6 x CUs eukaryote-sized or highly compressible members would ask for tens of GB): its
     // texts live twice on the device (two parities) next to the packed output, its compressed bytes twice there and NSLOT times in pinned memory.
@@ -653,14 +653,14 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
             }
             plain_total[g] = tot;
             if (tot + 64 > pinned_cap[sl]) {
-                pinned[sl] = pool->ensure(sl, (tot + 64) * 5 / 4);
-                pinned_cap[sl] = pool->cap[sl];
+                pinned[sl] = pool->ensure(gs::PIN_TEXT + sl, (tot + 64) * 5 / 4);
+                pinned_cap[sl] = pool->cap[gs::PIN_TEXT + sl];
                 if (!pinned[sl]) { pinned_cap[sl] = 0; start_rc = GS_ERR_HIP; gs::set_error("hipHostMalloc of %zu bytes failed", (size_t)((tot + 64) * 5 / 4)); }
             }
             dev_ctot[g] = dtot; dev_gtot[g] = gtot; (void)gtot_bgzf;
             if (dtot + 64 > cpin_cap[sl]) {
-                cpin[sl] = pool->ensure(16 + sl, (dtot + 64) * 5 / 4);
-                cpin_cap[sl] = pool->cap[16 + sl];
+                cpin[sl] = pool->ensure(gs::PIN_COMP + sl, (dtot + 64) * 5 / 4);
+                cpin_cap[sl] = pool->cap[gs::PIN_COMP + sl];
                 if (!cpin[sl]) {          // no pinned room for the members: they stay with this pipeline's host decoders (host_stage's general path)
                     cpin_cap[sl] = 0; (void)hipGetLastError();
                     dev_ctot[g] = dev_gtot[g] = 0;
@@ -765,7 +765,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
             GS_HIP_CHECK(hipHostMalloc(&np, ncap, hipHostMallocDefault));
             if (pinned[sl]) { memcpy(np, pinned[sl], plain_total[g]); (void)hipHostFree(pinned[sl]); }
             pinned[sl] = np; pinned_cap[sl] = ncap;
-            pool->p[sl] = np; pool->cap[sl] = ncap;
+            pool->p[gs::PIN_TEXT + sl] = np; pool->cap[gs::PIN_TEXT + sl] = ncap;
         }
         {   // a team of threads copies the decompressed texts in (one thread moves ~8 GB/s)
             std::atomic<size_t> next{0};
@@ -821,7 +821,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
         const size_t ns = ist[b].size();
         if (!ns) return GS_OK;
         int rc2;
-        uint8_t *pin = (uint8_t *)pool->ensure(32 + b, (sizeof(gs::InflateStream) + sizeof(gs::InflateResult)) * ns + 64);
+        uint8_t *pin = (uint8_t *)pool->ensure(gs::PIN_INFLATE + b, (sizeof(gs::InflateStream) + sizeof(gs::InflateResult)) * ns + 64);
         if (!pin) { gs::set_error("hipHostMalloc failed"); return GS_ERR_HIP; }
         memcpy(pin, ist[b].data(), sizeof(gs::InflateStream) * ns);
         if ((rc2 = ids[b].ensure(sizeof(gs::InflateStream) * ns)) || (rc2 = idr[b].ensure(sizeof(gs::InflateResult) * ns))) return rc2;

@@ -147,10 +147,10 @@ __global__ __launch_bounds__(256) void k_frac_gather(const uint64_t *const *__re
 struct FracCopies {
     std::vector<const uint64_t *> src; std::vector<uint64_t> dst; std::vector<uint32_t> n;
     void add(const uint64_t *s, uint64_t d, uint64_t m) { if (m) { src.push_back(s); dst.push_back(d); n.push_back((uint32_t)m); } }
-    int launch(gs_ctx *c, uint64_t *dst_base, int slot0)
+    int launch(gs_ctx *c, uint64_t *dst_base)
     {
         if (src.empty()) return GS_OK;
-        PoolBuf ds(c, slot0), dd(c, slot0 + 1), dn(c, slot0 + 2);
+        PoolBuf ds(c, SL_FRAC_COPY_SRC), dd(c, SL_FRAC_COPY_DST), dn(c, SL_FRAC_COPY_N);
         int rc;
         const size_t m = src.size();
         if ((rc = ds.alloc(8 * m)) || (rc = dd.alloc(8 * m)) || (rc = dn.alloc(4 * m))) return rc;
@@ -244,8 +244,8 @@ static int frac_sketch_core(gs_ctx *c, uint32_t k, uint32_t scaled, uint32_t num
             }
         }
     }
-    PoolBuf dcand(c, 104), dthr(c, 105), doff(c, 106), dcap(c, 107), dcnt(c, 108), dtask(c, 109), dsel(c, 110), ddist(c, 111);
-    PoolBuf dalt(c, 112), dlen(c, 113), dpos(c, 114), drs(c, 115), dnr(c, 116);
+    PoolBuf dcand(c, SL_FRAC_CAND), dthr(c, SL_FRAC_THR), doff(c, SL_FRAC_OFF), dcap(c, SL_FRAC_CAP), dcnt(c, SL_FRAC_CNT), dtask(c, SL_FRAC_TASK), dsel(c, SL_FRAC_SEL), ddist(c, SL_FRAC_DIST);
+    PoolBuf dalt(c, SL_FRAC_ALT), dlen(c, SL_FRAC_LEN), dpos(c, SL_FRAC_POS), drs(c, SL_FRAC_RADIX), dnr(c, SL_FRAC_NRUNS);
     std::vector<unsigned long long> cnt(ng);
     std::vector<uint32_t> dist(ng);
     std::vector<uint8_t> overflow(ng, 0);
@@ -355,7 +355,7 @@ int frac_sketch_to_host(gs_ctx *c, uint32_t k, uint32_t scaled, uint32_t num, co
     FracCopies cp;
     std::vector<uint64_t> done;
     uint64_t tot = 0;
-    PoolBuf dst(c, 119);
+    PoolBuf dst(c, SL_FRAC_HOST_ROWS);
     auto emit = [&](uint64_t g, const uint64_t *src, uint64_t n) -> int {
         rows[g].resize(n);
         if (n) { cp.add(src, tot, n); done.push_back(g); tot += n; }
@@ -364,7 +364,7 @@ int frac_sketch_to_host(gs_ctx *c, uint32_t k, uint32_t scaled, uint32_t num, co
     auto round_end = [&]() -> int {
         int r2;
         if (tot == 0) return GS_OK;
-        if ((r2 = dst.alloc(8 * tot)) || (r2 = cp.launch(c, dst.as<uint64_t>(), 120))) return r2;
+        if ((r2 = dst.alloc(8 * tot)) || (r2 = cp.launch(c, dst.as<uint64_t>()))) return r2;
         std::vector<uint64_t> h(tot);
         GS_HIP_CHECK(hipMemcpyAsync(h.data(), dst.p, 8 * tot, hipMemcpyDeviceToHost, c->stream));
         GS_HIP_CHECK(stream_wait(c));
@@ -436,7 +436,7 @@ int gs_frac_sketch_batch(gs_ctx *c, uint32_t k, uint32_t scaled, uint32_t num, c
     for (uint64_t r = 0; r < n_rec; r++) GS_REQUIRE(rec_begin[r] <= rec_end[r] && rec_end[r] <= n_bytes, GS_ERR_INVALID, "record %llu outside the text", (unsigned long long)r);
     *hash_out = nullptr;
     GS_CTX_LOCK(c);
-    gs::PoolBuf dtext(c, 117), dres(c, 118);
+    gs::PoolBuf dtext(c, gs::SL_FRACB_TEXT), dres(c, gs::SL_FRACB_RESIDUES);
     if ((rc = dtext.alloc(n_bytes + 64)) || (rc = dres.alloc(n_bytes + 64))) return rc;
     if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(dtext.p, text, n_bytes, hipMemcpyHostToDevice, c->stream));
     std::vector<uint64_t> rs(std::max<uint64_t>(n_rec, 1), 0), rl(std::max<uint64_t>(n_rec, 1), 0);
@@ -475,7 +475,7 @@ int gs_frac_sketch_batch_dev(gs_ctx *c, uint32_t k, uint32_t scaled, uint32_t nu
         cp.add(src, g * (uint64_t)cap, std::min<uint64_t>(n, cap));      // never more than cap values into a row
         return GS_OK;
     };
-    auto round_end = [&]() -> int { return cp.launch(c, hash_out_dev, 119); };
+    auto round_end = [&]() -> int { return cp.launch(c, hash_out_dev); };
     if ((rc = gs::frac_sketch_core(c, k, scaled, num, (const uint8_t *)seq_dev, rs.data(), rl.data(), n_rec, go.data(), n_genomes, emit, round_end))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(count_out_dev, counts.data(), 4 * n_genomes, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(gs::stream_wait(c));
@@ -495,7 +495,7 @@ int gs_frac_similarity_qxc(gs_ctx *c, uint32_t num, const uint64_t *Q, const uin
     uint64_t max_a = 0;
     for (uint64_t i = 0; i < nq; i++) max_a = std::max<uint64_t>(max_a, q_off[i + 1] - q_off[i]);
     const uint64_t nqv = q_off[nq], nrv = r_off[nr], np = nq * nr;
-    gs::PoolBuf dq(c, 122), dqo(c, 123), dr(c, 124), dro(c, 125), ds(c, 126), dc(c, 127), du(c, 128);
+    gs::PoolBuf dq(c, gs::SL_FRACS_Q), dqo(c, gs::SL_FRACS_QOFF), dr(c, gs::SL_FRACS_R), dro(c, gs::SL_FRACS_ROFF), ds(c, gs::SL_FRACS_SIM), dc(c, gs::SL_FRACS_COMMON), du(c, gs::SL_FRACS_UNION);
     if ((rc = dq.alloc(8 * nqv)) || (rc = dqo.alloc(8 * (nq + 1))) || (rc = dr.alloc(8 * nrv)) || (rc = dro.alloc(8 * (nr + 1))) || (rc = ds.alloc(8 * np)) ||
         (common_out && (rc = dc.alloc(4 * np))) || (union_out && (rc = du.alloc(4 * np))))
         return rc;

@@ -403,7 +403,7 @@ int narrow_u16_rows(gs_ctx *c, const void *src_dev, uint64_t src_stride_bytes, u
 static int hamming_qxc_dev(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq, const void *C, uint64_t nc, float *out)
 {
     if (kind == GS_KIND_U16) {
-        PoolBuf wq(c, 30), wc(c, 31);
+        PoolBuf wq(c, SL_HAM_WIDE_Q), wc(c, SL_HAM_WIDE_C);
         int rc;
         if ((rc = wq.alloc((size_t)4 * m * nq))) return rc;
         if ((rc = wc.alloc((size_t)4 * m * nc))) return rc;
@@ -439,7 +439,7 @@ int gs_hamming_qxc(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq, 
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
     const size_t row = gs::kind_bytes(kind) * (size_t)m;
-    gs::PoolBuf dq(c, 53), dc(c, 54), dout(c, 55);
+    gs::PoolBuf dq(c, gs::SL_HAM_Q), dc(c, gs::SL_HAM_C), dout(c, gs::SL_HAM_OUT);
     int rc;
     if ((rc = dq.alloc(row * nq))) return rc;
     if ((rc = dc.alloc(row * nc))) return rc;
@@ -465,7 +465,7 @@ int gs_hamming_pairs(gs_ctx *c, int kind, uint32_t m, const void *A, uint64_t na
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
     const size_t row = gs::kind_bytes(kind) * (size_t)m;
-    gs::PoolBuf da(c, 53), db(c, 54), dia(c, 55), dib(c, 56), dout(c, 57);
+    gs::PoolBuf da(c, gs::SL_HAMP_A), db(c, gs::SL_HAMP_B), dia(c, gs::SL_HAMP_IA), dib(c, gs::SL_HAMP_IB), dout(c, gs::SL_HAMP_OUT);
     int rc;
     if ((rc = da.alloc(row * na))) return rc;
     if ((rc = db.alloc(row * nb))) return rc;
@@ -476,7 +476,7 @@ int gs_hamming_pairs(gs_ctx *c, int kind, uint32_t m, const void *A, uint64_t na
     GS_HIP_CHECK(hipMemcpyAsync(db.p, B, row * nb, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(dia.p, ia, 8 * npairs, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(dib.p, ib, 8 * npairs, hipMemcpyHostToDevice, c->stream));
-    gs::PoolBuf wa(c, 58), wb(c, 59);
+    gs::PoolBuf wa(c, gs::SL_HAMP_WIDE_A), wb(c, gs::SL_HAMP_WIDE_B);
     if (kind == GS_KIND_U16) {                                   // widen once, then the u32 kernel (see k_widen_u16)
         if ((rc = wa.alloc((size_t)4 * m * na))) return rc;
         if ((rc = wb.alloc((size_t)4 * m * nb))) return rc;

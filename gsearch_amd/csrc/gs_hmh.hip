@@ -222,7 +222,7 @@ int hmh_cardinality_dev(gs_ctx *c, const uint16_t *sigs, uint64_t n, uint64_t *c
 static int hmh_similarity_dev(gs_ctx *c, const uint16_t *Q, uint64_t nq, const uint16_t *R, uint64_t nr, double *sim)
 {
     int rc;
-    PoolBuf cq(c, 65), cr(c, 66), cnb(c, 67), pq(c, 68), pr(c, 69), lst(c, 70);
+    PoolBuf cq(c, SL_HMH_CARD_Q), cr(c, SL_HMH_CARD_R), cnb(c, SL_HMH_NB), pq(c, SL_HMH_PACK_Q), pr(c, SL_HMH_PACK_R), lst(c, SL_HMH_LIST);
     if ((rc = cq.alloc(8 * nq)) || (rc = cr.alloc(8 * nr))) return rc;
     if ((rc = hmh_cardinality_dev(c, Q, nq, cq.as<uint64_t>())) || (rc = hmh_cardinality_dev(c, R, nr, cr.as<uint64_t>()))) return rc;
     // which sketches take the small-set branch with which: card in [1, 2^19]
@@ -267,7 +267,7 @@ static int hmh_similarity_dev(gs_ctx *c, const uint16_t *Q, uint64_t nq, const u
             // (rows of the pass: the lists hold absolute query numbers, the C | N matrix and `sim` are offset to the pass)
             std::vector<uint32_t> rel(sq_all.begin() + a0, sq_all.begin() + a0 + na);
             for (auto &x : rel) x -= (uint32_t)qa;
-            PoolBuf lrel(c, 71);
+            PoolBuf lrel(c, SL_HMH_LIST_REL);
             if ((rc = lrel.alloc(4 * (size_t)na))) return rc;
             GS_HIP_CHECK(hipMemcpyAsync(lrel.p, rel.data(), 4 * (size_t)na, hipMemcpyHostToDevice, c->stream));
             for (size_t b0 = 0; b0 < sr_all.size(); b0 += PB) {
@@ -279,7 +279,7 @@ static int hmh_similarity_dev(gs_ctx *c, const uint16_t *Q, uint64_t nq, const u
                                    pr.as<double>(), dlr + b0, nb, cnb.as<uint32_t>(), nr, sim + qa * nr);
                 GS_HIP_CHECK(hipGetLastError());
             }
-            // (lrel's slot is rewritten by the next block: wait for this block's kernels first)
+            // (lrel's lease ends with this iteration and the next block takes SL_HMH_LIST_REL again and rewrites it: wait for this block's kernels first)
             GS_HIP_CHECK(hipStreamSynchronize(c->stream));
         }
         s_lo = s_hi;
@@ -305,7 +305,7 @@ int gs_hmh_cardinality(gs_ctx *c, const uint16_t *sigs, uint64_t n, uint64_t *ca
     GS_CTX_LOCK(c);
     if (n == 0) return GS_OK;
     int rc;
-    gs::PoolBuf ds(c, 72), dc(c, 73);
+    gs::PoolBuf ds(c, gs::SL_HMHC_SIGS), dc(c, gs::SL_HMHC_CARD);
     if ((rc = ds.alloc((size_t)2 * GS_HMH_M * n)) || (rc = dc.alloc(8 * n))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(ds.p, sigs, (size_t)2 * GS_HMH_M * n, hipMemcpyHostToDevice, c->stream));
     if ((rc = gs::hmh_cardinality_dev(c, ds.as<uint16_t>(), n, dc.as<uint64_t>()))) return rc;
@@ -330,7 +330,7 @@ int gs_hmh_similarity_qxc(gs_ctx *c, const uint16_t *Q, uint64_t nq, const uint1
     GS_CTX_LOCK(c);
     if (nq == 0 || nr == 0) return GS_OK;
     int rc;
-    gs::PoolBuf dq(c, 74), dr(c, 75), ds(c, 76);
+    gs::PoolBuf dq(c, gs::SL_HMHS_Q), dr(c, gs::SL_HMHS_R), ds(c, gs::SL_HMHS_SIM);
     if ((rc = dq.alloc((size_t)2 * GS_HMH_M * nq)) || (rc = dr.alloc((size_t)2 * GS_HMH_M * nr)) || (rc = ds.alloc((size_t)8 * nq * nr))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(dq.p, Q, (size_t)2 * GS_HMH_M * nq, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(dr.p, R, (size_t)2 * GS_HMH_M * nr, hipMemcpyHostToDevice, c->stream));

@@ -2338,7 +2338,7 @@ static int upload_user_rows(gs_index *ix, void *dst, const void *src, uint64_t n
     if (nrows == 0) return GS_OK;
     GS_HIP_CHECK(hipMemsetAsync(dst, 0, ix->stride * nrows, c->stream));
     const void *dev = src;
-    PoolBuf stage(c, 39);
+    PoolBuf stage(c, SL_IX_ROW_STAGE);
     if (kind == hipMemcpyHostToDevice) {
         int rc = stage.alloc(ix->user_rowbytes * nrows); if (rc) return rc;
         GS_HIP_CHECK(hipMemcpyAsync(stage.p, src, ix->user_rowbytes * nrows, hipMemcpyHostToDevice, c->stream));
@@ -2354,7 +2354,7 @@ static int download_user_rows(gs_index *ix, uint64_t first, uint64_t n, void *ou
     if (ix->prm.kind != GS_KIND_U16) {
         GS_HIP_CHECK(hipMemcpy2DAsync(out_host, ix->rowbytes, ix->data.as<uint8_t>() + first * ix->stride, ix->stride, ix->rowbytes, n, hipMemcpyDeviceToHost, c->stream));
     } else {
-        PoolBuf stage(c, 39);
+        PoolBuf stage(c, SL_IX_ROW_STAGE);
         int rc = stage.alloc(ix->user_rowbytes * n); if (rc) return rc;
         if ((rc = narrow_u16_rows(c, ix->data.as<uint8_t>() + first * ix->stride, ix->stride, n, ix->prm.m, stage.p))) return rc;
         GS_HIP_CHECK(hipMemcpyAsync(out_host, stage.p, ix->user_rowbytes * n, hipMemcpyDeviceToHost, c->stream));
@@ -2946,7 +2946,7 @@ static int search_common(gs_index *ix, const void *queries, bool on_dev, uint64_
     gs_ctx *c = ix->ctx;
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
-    gs::PoolBuf dq(c, 32), dids(c, 33), ddist(c, 34), dcount(c, 35), devals(c, 36);
+    gs::PoolBuf dq(c, gs::SL_IX_QUERIES), dids(c, gs::SL_IX_IDS), ddist(c, gs::SL_IX_DIST), dcount(c, gs::SL_IX_COUNT), devals(c, gs::SL_IX_EVALS);
     int rc;
     if ((rc = dq.alloc(ix->stride * nq))) return rc;
     if ((rc = gs::upload_user_rows(ix, dq.p, queries, nq, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
@@ -2956,7 +2956,7 @@ static int search_common(gs_index *ix, const void *queries, bool on_dev, uint64_
         GS_HIP_CHECK(hipStreamSynchronize(c->stream));
         return GS_OK;
     }
-    gs::PoolBuf dpl(c, 40), dpr(c, 41);
+    gs::PoolBuf dpl(c, gs::SL_IX_PAIR_L), dpr(c, gs::SL_IX_PAIR_R);
     if ((rc = dids.alloc(8 * nq * knbn))) return rc;
     if ((rc = ddist.alloc(4 * nq * knbn))) return rc;
     if ((rc = dcount.alloc(4 * nq))) return rc;
@@ -2986,7 +2986,7 @@ int gs_index_count_matrix(gs_index *ix, const void *queries, uint64_t nq, uint16
     gs_ctx *c = ix->ctx;
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
-    gs::PoolBuf dq(c, 32);
+    gs::PoolBuf dq(c, gs::SL_IX_QUERIES);
     int rc;
     if ((rc = dq.alloc(ix->stride * nq))) return rc;
     if ((rc = gs::upload_user_rows(ix, dq.p, queries, nq, hipMemcpyHostToDevice))) return rc;
@@ -3038,7 +3038,7 @@ int gs_index_sketch_and_search_dev(gs_index *ix, const gs_sketch_params *p, cons
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
     const uint64_t nq = n_genomes;
-    gs::PoolBuf dq(c, 32), sigbuf(c, 60);
+    gs::PoolBuf dq(c, gs::SL_IX_QUERIES), sigbuf(c, gs::SL_IX_SKETCH_SIG);
     if ((rc = dq.alloc(ix->stride * nq))) return rc;
     uint8_t *sig = (uint8_t *)sig_out_dev;
     if (!sig) { if ((rc = sigbuf.alloc(ix->user_rowbytes * nq))) return rc; sig = (uint8_t *)sigbuf.p; }
@@ -3570,7 +3570,7 @@ int gs_index_bruteforce_search(gs_index *ix, const void *queries, uint64_t nq, u
     for (uint64_t q0 = 0; q0 < nq; q0 += QB) {
         const uint64_t nb = std::min(QB, nq - q0);
         if (ix->prm.kind == GS_KIND_U16) {                       // u16 rows from the host: stage, then zero-extend into the dense u32 block
-            gs::PoolBuf stage(c, 39);
+            gs::PoolBuf stage(c, gs::SL_IX_ROW_STAGE);
             if ((rc = stage.alloc(ix->user_rowbytes * nb))) return rc;
             GS_HIP_CHECK(hipMemcpyAsync(stage.p, (const uint8_t *)queries + ix->user_rowbytes * q0, ix->user_rowbytes * nb, hipMemcpyHostToDevice, c->stream));
             if ((rc = gs::widen_u16_rows(c, stage.p, nb, ix->prm.m, dq.p, ix->rowbytes))) return rc;
@@ -3636,7 +3636,7 @@ static int exact_dev(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn,
 static int exact_to_host(gs_index *ix, const uint8_t *q, uint64_t nq, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint64_t *ids, float *dist, uint32_t *count)
 {
     gs_ctx *c = ix->ctx;
-    PoolBuf dids(c, 33), ddist(c, 34), dcount(c, 35);
+    PoolBuf dids(c, SL_IX_IDS), ddist(c, SL_IX_DIST), dcount(c, SL_IX_COUNT);
     int rc;
     if ((rc = dids.alloc(8 * nq * knbn)) || (rc = ddist.alloc(4 * nq * knbn)) || (rc = dcount.alloc(4 * nq))) return rc;
     if ((rc = exact_dev(ix, q, nq, knbn, c_max, diag0, dids.as<uint64_t>(), ddist.as<float>(), dcount.as<uint32_t>()))) return rc;
@@ -3655,7 +3655,7 @@ static int exact_search_common(gs_index *ix, const void *queries, bool on_dev, u
     GS_REQUIRE(queries && ids && dist && count, GS_ERR_INVALID, "null argument");
     gs_ctx *c = ix->ctx;
     GS_CTX_LOCK(c);
-    PoolBuf dq(c, 32);
+    PoolBuf dq(c, SL_IX_QUERIES);
     if ((rc = dq.alloc(ix->stride * nq))) return rc;
     if ((rc = upload_user_rows(ix, dq.p, queries, nq, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
     if (!on_dev) return exact_to_host(ix, dq.as<uint8_t>(), nq, knbn, c_max, ~(uint64_t)0, ids, dist, count);
@@ -3714,7 +3714,7 @@ static int self_graph_dev(gs_index *ix, uint32_t knbn, float max_dist, uint64_t 
     if (rc) return rc;
     GS_REQUIRE(ix->n < ((uint64_t)1 << 31) && ix->n * knbn < ((uint64_t)1 << 31), GS_ERR_UNSUPPORTED, "graph of more than 2^31 entries");
     gs_ctx *c = ix->ctx;
-    PoolBuf dids(c, 100), ddist(c, 101), dcount(c, 102);
+    PoolBuf dids(c, SL_IXG_IDS), ddist(c, SL_IXG_DIST), dcount(c, SL_IXG_COUNT);
     const uint64_t n = ix->n;
     if ((rc = dids.alloc(8 * n * knbn)) || (rc = ddist.alloc(4 * n * knbn)) || (rc = dcount.alloc(4 * n))) return rc;
     if ((rc = exact_dev(ix, ix->data.as<uint8_t>(), n, knbn, c_max, 0, dids.as<uint64_t>(), ddist.as<float>(), dcount.as<uint32_t>(), true))) return rc;

@@ -606,7 +606,7 @@ static void inflate_launch_form(gs_ctx *c, hipStream_t stream, const uint32_t *c
 int inflate_streams_dev(gs_ctx *c, const void *comp_dev, const InflateStream *streams, uint32_t n, void *out_dev, InflateResult *results)
 {
     if (n == 0) return GS_OK;
-    PoolBuf ds(c, 40), dr(c, 41);
+    PoolBuf ds(c, SL_INFL_STREAMS), dr(c, SL_INFL_RESULTS);
     int rc;
     if ((rc = ds.alloc(sizeof(InflateStream) * n)) || (rc = dr.alloc(sizeof(InflateResult) * n))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(ds.p, streams, sizeof(InflateStream) * n, hipMemcpyHostToDevice, c->stream));
@@ -643,7 +643,7 @@ int crc32_texts_dev(gs_ctx *c, const void *text_dev, const uint64_t *text_off, c
     if (!chunks.empty()) {
         uint32_t kpow[8];
         for (int j = 0; j < 8; j++) kpow[j] = crc_xpow8((uint64_t)CRC_PIECE << j);
-        PoolBuf dc(c, 42), dk(c, 43), dout(c, 44);
+        PoolBuf dc(c, SL_CRC_CHUNKS), dk(c, SL_CRC_POWERS), dout(c, SL_CRC_OUT);
         int rc;
         if ((rc = dc.alloc(sizeof(CrcChunk) * chunks.size())) || (rc = dk.alloc(sizeof kpow)) || (rc = dout.alloc(4 * chunks.size()))) return rc;
         GS_HIP_CHECK(hipMemcpyAsync(dc.p, chunks.data(), sizeof(CrcChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
@@ -710,7 +710,7 @@ int fasta_scan_dev(gs_ctx *c, const void *text_dev, const uint64_t *off, const u
         for (uint64_t b = 0; b < len[f]; b += SC_CHUNK) chunks.push_back({off[f] + b, off[f] + std::min<uint64_t>(b + SC_CHUNK, len[f]), off[f]});
     }
     if (chunks.empty()) return GS_OK;
-    PoolBuf dch(c, 42), dst(c, 43), dcn(c, 44);
+    PoolBuf dch(c, SL_SCAN_CHUNKS), dst(c, SL_SCAN_STARTS), dcn(c, SL_SCAN_COUNT);
     int rc;
     if ((rc = dch.alloc(sizeof(ScanChunk) * chunks.size())) || (rc = dcn.alloc(16))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(dch.p, chunks.data(), sizeof(ScanChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
@@ -741,7 +741,7 @@ int fasta_scan_dev(gs_ctx *c, const void *text_dev, const uint64_t *off, const u
             while (k < cnt && starts[k] < off[f] + len[f]) { fend[k] = off[f] + len[f]; k++; }
         }
     }
-    PoolBuf dfe(c, 40), dhe(c, 41), dcf(c, 45);
+    PoolBuf dfe(c, SL_SCAN_FILE_END), dhe(c, SL_SCAN_HEADER_END), dcf(c, SL_SCAN_CAPSID);
     if ((rc = dfe.alloc(8 * (size_t)cnt)) || (rc = dhe.alloc(8 * (size_t)cnt)) || (rc = dcf.alloc(cnt))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(dst.p, starts.data(), 8 * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(dfe.p, fend.data(), 8 * (size_t)cnt, hipMemcpyHostToDevice, c->stream));
@@ -813,7 +813,7 @@ int gs_gunzip_batch(gs_ctx *c, const uint8_t *const *in, const uint64_t *in_len,
         ctot += gs::round_up(in_len[i], 64); otot += gs::round_up(isize[i], 64);
     }
     if (st.empty()) return GS_OK;
-    gs::PoolBuf dcomp(c, 45), dtext(c, 46);
+    gs::PoolBuf dcomp(c, gs::SL_GUNZIP_COMP), dtext(c, gs::SL_GUNZIP_TEXT);
     int rc;
     if ((rc = dcomp.alloc(ctot + 64)) || (rc = dtext.alloc(otot + 64))) return rc;
     for (uint64_t k = 0; k < who.size(); k++) GS_HIP_CHECK(hipMemcpyAsync((uint8_t *)dcomp.p + coff[who[k]], in[who[k]], in_len[who[k]], hipMemcpyHostToDevice, c->stream));

@@ -155,7 +155,7 @@ int ingest_records_dev(gs_ctx *c, bool aa, bool contiguous, const void *text_dev
     const uint64_t nch = cb.size();
     for (uint64_t r = 0; r < n_rec; r++) { rec_start_out[r] = out_base0; rec_len_out[r] = 0; }
     if (nch == 0) return GS_OK;
-    PoolBuf dcb(c, 10), dce(c, 11), dcnt(c, 12), dbase(c, 13);
+    PoolBuf dcb(c, SL_INGEST_BEGIN), dce(c, SL_INGEST_END), dcnt(c, SL_INGEST_COUNT), dbase(c, SL_INGEST_BASE);
     int rc;
     if ((rc = dcb.alloc(8 * nch))) return rc;
     if ((rc = dce.alloc(8 * nch))) return rc;

@@ -10,10 +10,9 @@
 #include <string>
 #include <vector>
 #include "../../include/gsearch_amd.h"
+#include "gs_scratch.hpp"
 
 namespace gs {
-
-void set_error(const char *fmt, ...);
 
 #define GS_HIP_CHECK(expr)                                                                         \
     do {                                                                                           \
@@ -269,12 +268,14 @@ struct VmArena {
     }
 };
 
-// Per-context scratch: a call's temporaries come from numbered grow-only slots instead of hipMalloc/hipFree (allocating and freeing
-// multi-GB buffers costs more than the kernels that use them). A context serves one call at a time (one stream), so slots are never
-// shared; gs_ctx_release_scratch / gs_ctx_destroy give the memory back.
-enum { SCRATCH_SLOTS = 136 };       // 48-52: staging of gs_sketch_batch, 53-57: of gs_hamming_qxc / gs_hamming_pairs (host-pointer calls), 64-79: hypermash, 80-103: ann, 104-135: superaai
-struct ScratchPool { DevBuf b[SCRATCH_SLOTS]; };
-enum { PINNED_SLOTS = 36 };      // 0-15 text, 16-31 compressed members, 32-33 inflate descriptors / results
+// Per-context scratch: a call's temporaries come from named grow-only slots (gs_scratch.hpp) instead of hipMalloc/hipFree (allocating and freeing
+// multi-GB buffers costs more than the kernels that use them). A context serves one call at a time (one stream); inside a call every live PoolBuf
+// holds the lease of its slot, and a second one on the same slot is an error. gs_ctx_release_scratch / gs_ctx_destroy give the memory back.
+struct ScratchPool { DevBuf b[SCRATCH_SLOTS]; std::shared_ptr<SlotLeases> leases = std::make_shared<SlotLeases>(); };
+// The pool may be deleted while PoolBufs of a call further up the stack are alive (gs_ctx_release_scratch; on_worker_failed, whose try_lock on the
+// recursive context lock succeeds on the failing thread itself). Every deletion goes through here. The leases need nothing from it: a PoolBuf gives
+// back to the table it took from, which it keeps alive itself, and never looks at the context's pool again (SlotLease, gs_scratch.hpp).
+inline void drop_scratch_pool(gs_ctx *c) { delete (ScratchPool *)c->scratch_pool; c->scratch_pool = nullptr; }
 struct PinnedPool {
     void *p[PINNED_SLOTS] = {}; size_t cap[PINNED_SLOTS] = {};
     ~PinnedPool() { for (int i = 0; i < PINNED_SLOTS; i++) if (p[i]) (void)hipHostFree(p[i]); }
@@ -294,20 +295,24 @@ inline PinnedPool *pinned_pool(gs_ctx *c)
     if (!c->pinned_pool) c->pinned_pool = new PinnedPool();
     return (PinnedPool *)c->pinned_pool;
 }
-struct PoolBuf {    // same surface as DevBuf for the code that uses it
-    gs_ctx *c; int slot; void *p = nullptr; size_t bytes = 0;
-    PoolBuf(gs_ctx *ctx, int s) : c(ctx), slot(s) {}
+struct PoolBuf {    // a scoped lease of one slot; same surface as DevBuf for the code that uses it
+    gs_ctx *c; SlotLease lease; void *p = nullptr; size_t bytes = 0;
+    PoolBuf(gs_ctx *ctx, ScratchSlot s) : c(ctx), lease(s) {}
+    PoolBuf(const PoolBuf &) = delete;              // (nor movable: a lease stays with the scope that took it)
+    PoolBuf &operator=(const PoolBuf &) = delete;
     int alloc(size_t n)
     {
         if (!c->scratch_pool) c->scratch_pool = new ScratchPool();
-        DevBuf &d = ((ScratchPool *)c->scratch_pool)->b[slot];
-        if (n == 0) n = 16;
-        int rc = d.ensure(n);
+        ScratchPool *pool = (ScratchPool *)c->scratch_pool;
+        int rc = lease.take(pool->leases);
         if (rc) return rc;
+        DevBuf &d = pool->b[lease.slot];
+        if (n == 0) n = 16;
+        if ((rc = d.ensure(n))) return rc;
         p = d.p; bytes = n;
         return GS_OK;
     }
-    void release() { p = nullptr; bytes = 0; }          // the slot keeps its memory for the next call
+    void release() { lease.give(); p = nullptr; bytes = 0; }          // the slot keeps its memory for the next call
     template <class T> T *as() const { return (T *)p; }
 };
 

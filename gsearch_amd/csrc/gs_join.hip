@@ -869,7 +869,7 @@ static int join_impl(gs_ctx *c, uint32_t m, const uint8_t *qrows, uint64_t qstri
     if ((rc = join_launch<KIND, T, false>(c, g, k0.as<T>(), nq, cols, colcap, n, 0, JS0, out16, ld, stats, 0, true, nullptr, nullptr, nullptr, 0, nullptr, nullptr))) return rc;
     lap("phase 0 (first slots)");
     // (pinned staging: a pageable destination makes the runtime bounce 1.2 MB through its own buffer, synchronously)
-    uint8_t *pin = (uint8_t *)pinned_pool(c)->ensure(34, 64 + 4 * (2 * (size_t)nq + n) + 2 * ((size_t)nq + 8 + (size_t)g.chunks * JT * JN) + 64);
+    uint8_t *pin = (uint8_t *)pinned_pool(c)->ensure(PIN_JOIN, 64 + 4 * (2 * (size_t)nq + n) + 2 * ((size_t)nq + 8 + (size_t)g.chunks * JT * JN) + 64);
     GS_REQUIRE(pin, GS_ERR_HIP, "match-join: pinned staging buffer");
     unsigned long long *hc = (unsigned long long *)pin;
     uint32_t *hlq = (uint32_t *)(pin + 64), *hcn = hlq + nq, *hle = hcn + nq;

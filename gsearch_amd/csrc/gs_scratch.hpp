@@ -1,0 +1,136 @@
+// gs_scratch.hpp — the names of the per-context scratch slots and the bookkeeping of who holds one. Plain C++ (no HIP): tests/test_scratch_leases.py
+// compiles it with the host compiler alone. gs_internal.hpp puts the device memory behind it (ScratchPool, PoolBuf, PinnedPool).
+#pragma once
+#include <stdint.h>
+#include <memory>
+#include "../../include/gsearch_amd.h"
+
+namespace gs {
+
+void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_last_error()
+
+// One enumerator per buffer role, grouped by owner: this list is the map of the pool. To add a buffer, add an enumerator. A slot is one grow-only
+// device allocation per context, so two buffers that can be alive at the same time need two enumerators; the lease check below reports the ones that do not.
+#define GS_SCRATCH_SLOT_LIST(X)                                                                                                                       \
+    /* sketch_dev_impl, every algorithm: unit prefix of the records, units of the genomes */                                                          \
+    X(SK_REC_UNITS) X(SK_GENOME_UNITS)                                                                                                                \
+    /* OPH (optdens / revoptdens) */                                                                                                                  \
+    X(OPH_TABLE) X(OPH_WIN)                                                                                                                           \
+    /* SuperMinHash (run_smh): slot table, then the cold walk */                                                                                      \
+    X(SMH_TABLE) X(SMH_COLD_FLAGS) X(SMH_COLD_LIST) X(SMH_COLD_Q) X(SMH_COLD_P) X(SMH_COLD_CNT)                                                       \
+    /* ProbMinHash driver (run_prob): alive around whichever form runs */                                                                             \
+    X(PROB_REC_UNITS) X(PROB_GENOME_UNITS) X(PROB_REC_KMERS) X(PROB_GENOME_KMERS)                                                                     \
+    /* ProbMinHash, bucketed and tiered forms (the sorted form's names for the same memory follow the enum) */                                        \
+    X(PROB_INFO) X(PROB_BOFF) X(PROB_VBASE) X(PROB_HIST) X(PROB_BST) X(PROB_BSZ) X(PROB_BGN) X(PROB_CTR) X(PROB_VALS) X(PROB_Q) X(PROB_QPREV)         \
+    X(PROB_SIG) X(PROB_SIGPASS) X(PROB_THR) X(PROB_WMAX) X(PROB_QMAX) X(PROB_CAND_V) X(PROB_CAND_H) X(PROB_CAND_GB) X(PROB_AKEY) X(PROB_SEGN)         \
+    X(PROB_TMPV) X(PROB_COARSE)                                                                                                                       \
+    /* ProbMinHash, sorted form: what it does not share with the other two */                                                                         \
+    X(PROBS_GENOME_UNITS) X(PROBS_REC_KMERS) X(PROBS_GENOME_KMERS) X(PROBS_POS)                                                                       \
+    /* HLL (run_hll): global register tables, survivor lists of pass A */                                                                             \
+    X(HLL_GTAB) X(HLL_SURVIVORS)                                                                                                                      \
+    /* HyperMinHash sketch (run_hmh): merge table of a genome split over workgroups */                                                                \
+    X(HMH_GTAB)                                                                                                                                       \
+    /* gs_sketch_batch: staging of a host-pointer call */                                                                                             \
+    X(SKB_SEQ) X(SKB_REC_START) X(SKB_REC_LEN) X(SKB_GENOME_OFF) X(SKB_SIG)                                                                           \
+    /* ingest (ingest_records_dev) */                                                                                                                 \
+    X(INGEST_BEGIN) X(INGEST_END) X(INGEST_COUNT) X(INGEST_BASE)                                                                                      \
+    /* inflate: stream descriptors / results, CRC-32 chunks, FASTA scan, staging of gs_gunzip_batch */                                                \
+    X(INFL_STREAMS) X(INFL_RESULTS) X(CRC_CHUNKS) X(CRC_POWERS) X(CRC_OUT) X(SCAN_CHUNKS) X(SCAN_STARTS) X(SCAN_COUNT) X(SCAN_FILE_END)               \
+    X(SCAN_HEADER_END) X(SCAN_CAPSID) X(GUNZIP_COMP) X(GUNZIP_TEXT)                                                                                   \
+    /* index: staging of search requests and of user rows */                                                                                          \
+    X(IX_QUERIES) X(IX_IDS) X(IX_DIST) X(IX_COUNT) X(IX_EVALS) X(IX_PAIR_L) X(IX_PAIR_R) X(IX_ROW_STAGE) X(IX_SKETCH_SIG)                             \
+    /* index: the database's own k-NN graph (self_graph_dev) */                                                                                       \
+    X(IXG_IDS) X(IXG_DIST) X(IXG_COUNT)                                                                                                               \
+    /* hamming: widened u16 rows of the device forms, staging of gs_hamming_qxc / gs_hamming_pairs */                                                 \
+    X(HAM_WIDE_Q) X(HAM_WIDE_C) X(HAM_Q) X(HAM_C) X(HAM_OUT) X(HAMP_A) X(HAMP_B) X(HAMP_IA) X(HAMP_IB) X(HAMP_OUT) X(HAMP_WIDE_A) X(HAMP_WIDE_B)      \
+    /* hypermash (gs_hmh.hip) */                                                                                                                      \
+    X(HMH_CARD_Q) X(HMH_CARD_R) X(HMH_NB) X(HMH_PACK_Q) X(HMH_PACK_R) X(HMH_LIST) X(HMH_LIST_REL) X(HMHC_SIGS) X(HMHC_CARD)                           \
+    X(HMHS_Q) X(HMHS_R) X(HMHS_SIM)                                                                                                                   \
+    /* ann / embed (gs_embed.hip) */                                                                                                                  \
+    X(EMB_FLAG) X(EMB_PM) X(EMB_KEYS) X(EMB_ALT) X(EMB_RADIX) X(EMB_RANGE) X(EMB_DEG) X(EMB_OFF) X(EMB_ADJ) X(EMB_W) X(EMB_WSUM) X(EMB_HEAVY)         \
+    X(EMB_Y0) X(EMB_Y1) X(KST_OCC) X(KST_ENDS) X(EMBIN_IDS) X(EMBIN_DIST) X(EMBIN_COUNT) X(EMB_INIT) X(EMB_POS) X(EMB_MEMB)                           \
+    /* superaai (gs_frac.hip) */                                                                                                                      \
+    X(FRAC_CAND) X(FRAC_THR) X(FRAC_OFF) X(FRAC_CAP) X(FRAC_CNT) X(FRAC_TASK) X(FRAC_SEL) X(FRAC_DIST) X(FRAC_ALT) X(FRAC_LEN) X(FRAC_POS)            \
+    X(FRAC_RADIX) X(FRAC_NRUNS) X(FRAC_COPY_SRC) X(FRAC_COPY_DST) X(FRAC_COPY_N) X(FRAC_HOST_ROWS) X(FRACB_TEXT) X(FRACB_RESIDUES)                    \
+    X(FRACS_Q) X(FRACS_QOFF) X(FRACS_R) X(FRACS_ROFF) X(FRACS_SIM) X(FRACS_COMMON) X(FRACS_UNION)                                                     \
+    /* comm (gs_topk_merge_dev) */                                                                                                                    \
+    X(COMM_ID_OFFSET)
+
+enum ScratchSlot : int {
+#define X(name) SL_##name,
+    GS_SCRATCH_SLOT_LIST(X)
+#undef X
+    SCRATCH_SLOTS        // the number of slots
+};
+inline const char *scratch_slot_name(ScratchSlot s)
+{
+    static const char *const names[] = {
+#define X(name) #name,
+        GS_SCRATCH_SLOT_LIST(X)
+#undef X
+    };
+    return (int)s >= 0 && s < SCRATCH_SLOTS ? names[s] : "?";
+}
+
+// Second names for memory that sibling forms share ON PURPOSE, because some of these buffers run to gigabytes. A second name is only sound where the two
+// users can never be alive together - the reason stands at each group, and the lease check holds it to that.
+//
+// sketch_dev_impl runs ONE algorithm per call and run_smh / run_hll / run_prob never call one another: the workspaces of HLL and of the ProbMinHash forms
+// lie in SuperMinHash's (the cold-walk scratch of either is 8 m bytes per lane, the ProbMinHash generator states 0.5 GB).
+constexpr ScratchSlot SL_HLL_CUT = SL_SMH_TABLE, SL_HLL_COLD_FLAGS = SL_SMH_COLD_FLAGS, SL_HLL_COLD_LIST = SL_SMH_COLD_LIST, SL_HLL_COLD_Q = SL_SMH_COLD_Q,
+                      SL_HLL_COLD_P = SL_SMH_COLD_P, SL_HLL_CNT = SL_SMH_COLD_CNT;
+constexpr ScratchSlot SL_PROB_AGL = SL_SMH_TABLE, SL_PROB_ACNT = SL_SMH_COLD_FLAGS, SL_PROB_ASTATE = SL_SMH_COLD_LIST, SL_PROB_PH = SL_SMH_COLD_Q,
+                      SL_PROB_PB = SL_SMH_COLD_P, SL_PROB_OVF = SL_SMH_COLD_CNT;
+// The tiered form is the bucketed form with other bucket descriptors; run_prob calls the two one after the other, never one from the other.
+constexpr ScratchSlot SL_PROBT_DESC = SL_PROB_BST, SL_PROBT_BIG = SL_PROB_BSZ, SL_PROBT_KEPT = SL_PROB_TMPV;
+// The sorted form takes what the other two flag or do not suit, after they have returned (run_prob, old_range): its k-mer keys and their sorted copy
+// (8 bytes per k-mer each) lie in the memory of the bucketed values and registers.
+constexpr ScratchSlot SL_PROBS_BASE = SL_PROB_INFO, SL_PROBS_Q = SL_PROB_BOFF, SL_PROBS_QPREV = SL_PROB_VBASE, SL_PROBS_SIG = SL_PROB_HIST,
+                      SL_PROBS_SIGPASS = SL_PROB_BST, SL_PROBS_WMAX = SL_PROB_BSZ, SL_PROBS_QMAX = SL_PROB_BGN, SL_PROBS_NACT = SL_PROB_CTR,
+                      SL_PROBS_VALS = SL_PROB_VALS, SL_PROBS_SORTED = SL_PROB_Q, SL_PROBS_UCNT = SL_PROB_SIG, SL_PROBS_NRUNS = SL_PROB_SIGPASS,
+                      SL_PROBS_RADIX = SL_PROB_THR, SL_PROBS_CAND_H = SL_PROB_WMAX, SL_PROBS_CAND_B = SL_PROB_QMAX, SL_PROBS_AKEY = SL_PROB_CAND_V,
+                      SL_PROBS_ACNT = SL_PROB_CAND_H, SL_PROBS_ASTATE = SL_PROB_CAND_GB, SL_PROBS_NLIST = SL_PROB_AKEY, SL_PROBS_REC_UNITS = SL_PROB_SEGN;
+
+// Who holds which slot of ONE pool. A lease describes host scopes only: kernels still queued when a scope ends are protected by stream order (a slot is
+// only handed out again by a later call on the same context, i.e. behind them on its stream).
+struct SlotLeases {
+    uint8_t held[SCRATCH_SLOTS] = {};
+    bool take(ScratchSlot s) { if (held[s]) return false; held[s] = 1; return true; }
+    void give(ScratchSlot s) { held[s] = 0; }
+};
+// One lease. It keeps the table it took the slot from alive and gives back to that table only: a pool that was deleted in between (gs_ctx_release_scratch,
+// on_worker_failed) has dropped its reference, the pool made after it has a table of its own, and neither is touched.
+struct SlotLease {
+    std::shared_ptr<SlotLeases> from; ScratchSlot slot;
+    explicit SlotLease(ScratchSlot s) : slot(s) {}
+    SlotLease(const SlotLease &) = delete;
+    SlotLease &operator=(const SlotLease &) = delete;
+    ~SlotLease() { give(); }
+    // GS_OK: the slot of `table` is ours (or already was: allocating again through the same object is allowed). An error: another lease holds it
+    int take(const std::shared_ptr<SlotLeases> &table)
+    {
+        if (from == table) return GS_OK;
+        give();
+        if (!table->take(slot)) {
+            set_error("scratch slot %s is already in use further up this call: two buffers that are alive at once need two slots (gs_scratch.hpp)", scratch_slot_name(slot));
+            return GS_ERR_STATE;
+        }
+        from = table;
+        return GS_OK;
+    }
+    void give() { if (from) { from->give(slot); from.reset(); } }
+};
+
+// Pinned host staging (PinnedPool): one range of slots per role.
+enum : int {
+    PIN_TEXT = 0, PIN_TEXT_N = 16,                            // gs_sketch_files: the texts of the groups in flight
+    PIN_COMP = PIN_TEXT + PIN_TEXT_N, PIN_COMP_N = 16,        //                  their compressed members for the device inflate
+    PIN_INFLATE = PIN_COMP + PIN_COMP_N, PIN_INFLATE_N = 2,   //                  inflate descriptors / results, one per parity
+    PIN_JOIN = PIN_INFLATE + PIN_INFLATE_N,                   // match_join_counts: its host-side lists
+    PINNED_SLOTS = PIN_JOIN + 1
+};
+static_assert(PIN_TEXT == 0 && PIN_TEXT + PIN_TEXT_N <= PIN_COMP && PIN_COMP + PIN_COMP_N <= PIN_INFLATE && PIN_INFLATE + PIN_INFLATE_N <= PIN_JOIN &&
+                  PIN_JOIN < PINNED_SLOTS,
+              "the ranges of the pinned pool are disjoint and fit");
+
+}  // namespace gs

@@ -720,7 +720,7 @@ static int run_smh(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
                    void *sig_out)
 {
     const uint32_t m = p->sketch_size;
-    PoolBuf table(c, 24), cold(c, 25);
+    PoolBuf table(c, SL_SMH_TABLE), cold(c, SL_SMH_COLD_FLAGS);
     int rc;
     if ((rc = table.alloc((size_t)n_genomes * m * sizeof(T)))) return rc;
     if ((rc = cold.alloc(n_genomes))) return rc;
@@ -738,7 +738,7 @@ static int run_smh(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
     if (!list.empty() && lds_wg <= 150 * 1024 && m <= 65535 && !getenv("GS_SMH_COLD_SERIAL")) {
         const uint32_t nc = (uint32_t)list.size();
         const uint32_t wgs = std::min<uint32_t>(nc, (uint32_t)c->n_cu * 2);
-        PoolBuf dl(c, 26), lq(c, 27), lp(c, 37), cnt(c, 38);
+        PoolBuf dl(c, SL_SMH_COLD_LIST), lq(c, SL_SMH_COLD_Q), lp(c, SL_SMH_COLD_P), cnt(c, SL_SMH_COLD_CNT);
         if ((rc = dl.alloc(4 * (size_t)nc))) return rc;
         if ((rc = lq.alloc((size_t)4 * wgs * m * CW_T))) return rc;
         if ((rc = lp.alloc((size_t)4 * wgs * m * CW_T))) return rc;
@@ -764,7 +764,7 @@ static int run_smh(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
     const size_t per_launch = std::max<size_t>(4096, std::min<size_t>(((size_t)16 << 30) / ((size_t)32 * m), (size_t)1 << 20));
     for (size_t l0 = 0; l0 < list.size(); l0 += per_launch) {
         const uint32_t nc = (uint32_t)std::min<size_t>(per_launch, list.size() - l0);
-        PoolBuf dl(c, 26), scratch(c, 27);
+        PoolBuf dl(c, SL_SMH_COLD_LIST), scratch(c, SL_SMH_COLD_Q);
         if ((rc = dl.alloc(4 * (size_t)nc))) return rc;
         if ((rc = scratch.alloc((size_t)nc * 32 * m))) return rc;
         GS_HIP_CHECK(hipMemcpyAsync(dl.p, list.data() + l0, 4 * (size_t)nc, hipMemcpyHostToDevice, c->stream));
@@ -1551,11 +1551,11 @@ static int run_prob_buckets(gs_ctx *c, const gs_sketch_params *p, const uint8_t 
     cinfo[2 * (size_t)ng] = nct;
     const uint64_t avg_units = maxk / 32 + 1;
     const uint32_t parts = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(avg_units / ((uint64_t)PBK_T * PBK_WPL) + 1, std::max<uint64_t>(1, (2 * (uint64_t)c->n_cu + ng - 1) / ng)));
-    PoolBuf dsh(c, 0), dboff(c, 1), dvb(c, 2), hist(c, 3), bst(c, 4), bsz(c, 5), bgn(c, 6), vals(c, 8), q(c, 9), qprev(c, 10), sig(c, 11), sigpass(c, 12), thr(c, 13), wmax(c, 14),
-        qmax(c, 15), ctr(c, 7);
-    PoolBuf cv(c, 16), chh(c, 17), cgb(c, 18), akey(c, 19), agl(c, 24), acnt(c, 25), astate(c, 26), ph(c, 27), pb(c, 37), ovf(c, 38);
+    PoolBuf dsh(c, SL_PROB_INFO), dboff(c, SL_PROB_BOFF), dvb(c, SL_PROB_VBASE), hist(c, SL_PROB_HIST), bst(c, SL_PROB_BST), bsz(c, SL_PROB_BSZ), bgn(c, SL_PROB_BGN), vals(c, SL_PROB_VALS), q(c, SL_PROB_Q), qprev(c, SL_PROB_QPREV), sig(c, SL_PROB_SIG), sigpass(c, SL_PROB_SIGPASS), thr(c, SL_PROB_THR), wmax(c, SL_PROB_WMAX),
+        qmax(c, SL_PROB_QMAX), ctr(c, SL_PROB_CTR);
+    PoolBuf cv(c, SL_PROB_CAND_V), chh(c, SL_PROB_CAND_H), cgb(c, SL_PROB_CAND_GB), akey(c, SL_PROB_AKEY), agl(c, SL_PROB_AGL), acnt(c, SL_PROB_ACNT), astate(c, SL_PROB_ASTATE), ph(c, SL_PROB_PH), pb(c, SL_PROB_PB), ovf(c, SL_PROB_OVF);
     const uint32_t cand_cap = (uint32_t)std::min<uint64_t>((uint64_t)ng * m * 16 + 65536, (uint64_t)1 << 30), ovf_cap = cand_cap / 4, act_cap = 1u << 24;
-    PoolBuf segn(c, 28), tmpv(c, 61), dcin(c, 62);
+    PoolBuf segn(c, SL_PROB_SEGN), tmpv(c, SL_PROB_TMPV), dcin(c, SL_PROB_COARSE);
     bool two_level = !getenv("GS_PROB_ONELEVEL") && (uint64_t)parts * ncmax <= PB_CCMAX && ncmax <= 256 && nfmax <= 256;
     // the second copy of the values is the price of the two levels: a device that has no room for it (an index with its pair cache beside the
     // sketcher, say) partitions in one level as in round 3
@@ -2246,9 +2246,9 @@ static int run_prob_tiers(gs_ctx *c, const gs_sketch_params *p, const uint8_t *s
         capbits[ng + i] = t1d < 0x1.0p52 ? (uint64_t)t1d : ((uint64_t)1 << 52);
     }
     boff[ng] = nbt;
-    PoolBuf dinfo(c, 0), dvb(c, 2), cnt(c, 3), vals(c, 8), q(c, 9), qprev(c, 10), sig(c, 11), sigpass(c, 12), thr(c, 13), wmax(c, 14), qmax(c, 15), ctr(c, 7);
-    PoolBuf cv(c, 16), chh(c, 17), cgb(c, 18), akey(c, 19), agl(c, 24), acnt(c, 25), astate(c, 26), ph(c, 27), pb(c, 37), ovf(c, 38), segn(c, 28);
-    PoolBuf kept(c, 61), desc(c, 4), big(c, 5);
+    PoolBuf dinfo(c, SL_PROB_INFO), dvb(c, SL_PROB_VBASE), cnt(c, SL_PROB_HIST), vals(c, SL_PROB_VALS), q(c, SL_PROB_Q), qprev(c, SL_PROB_QPREV), sig(c, SL_PROB_SIG), sigpass(c, SL_PROB_SIGPASS), thr(c, SL_PROB_THR), wmax(c, SL_PROB_WMAX), qmax(c, SL_PROB_QMAX), ctr(c, SL_PROB_CTR);
+    PoolBuf cv(c, SL_PROB_CAND_V), chh(c, SL_PROB_CAND_H), cgb(c, SL_PROB_CAND_GB), akey(c, SL_PROB_AKEY), agl(c, SL_PROB_AGL), acnt(c, SL_PROB_ACNT), astate(c, SL_PROB_ASTATE), ph(c, SL_PROB_PH), pb(c, SL_PROB_PB), ovf(c, SL_PROB_OVF), segn(c, SL_PROB_SEGN);
+    PoolBuf kept(c, SL_PROBT_KEPT), desc(c, SL_PROBT_DESC), big(c, SL_PROBT_BIG);
     const uint32_t cand_cap = (uint32_t)std::min<uint64_t>((uint64_t)ng * m * 16 + 65536, (uint64_t)1 << 30), ovf_cap = cand_cap / 4, act_cap = 1u << 24;
     // the list of kept ids: what the caps let through (x1 < cap as singletons) plus the false alarms of shared cells and the real repeats, with room to spare
     uint64_t kept_want = 1u << 20;
@@ -2384,7 +2384,7 @@ static int run_prob(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, ui
     pc.c2 = log(2.0 / (1.0 + exp(-pc.lambda))) / pc.lambda;
     pc.c3 = (1.0 - exp(-pc.lambda)) / pc.lambda;
     int rc;
-    DevBuf upre, gunits, kpre, gkm;              // (own allocations: the sorted form called below uses the scratch-pool slots of the same names)
+    PoolBuf upre(c, SL_PROB_REC_UNITS), gunits(c, SL_PROB_GENOME_UNITS), kpre(c, SL_PROB_REC_KMERS), gkm(c, SL_PROB_GENOME_KMERS);   // (alive around the forms below: slots of their own)
     if ((rc = upre.alloc(8 * (n_rec + 1))) || (rc = gunits.alloc(8 * n_genomes)) || (rc = kpre.alloc(8 * (n_rec + 1))) || (rc = gkm.alloc(8 * n_genomes))) return rc;
     const uint32_t gb = (uint32_t)((n_genomes + 3) / 4);
     hipLaunchKernelGGL(k_unit_prefix, dim3(gb), dim3(256), 0, c->stream, rec_start, rec_len, genome_rec_off, n_genomes, k, upre.as<uint64_t>(), gunits.as<uint64_t>());
@@ -2496,7 +2496,7 @@ static int run_prob_sorted(gs_ctx *c, const gs_sketch_params *p, const uint8_t *
     pc.c2 = log(2.0 / (1.0 + exp(-pc.lambda))) / pc.lambda;
     pc.c3 = (1.0 - exp(-pc.lambda)) / pc.lambda;
     int rc;
-    PoolBuf upre(c, 28), gunits(c, 29), kpre(c, 30), gkm(c, 31);
+    PoolBuf upre(c, SL_PROBS_REC_UNITS), gunits(c, SL_PROBS_GENOME_UNITS), kpre(c, SL_PROBS_REC_KMERS), gkm(c, SL_PROBS_GENOME_KMERS);
     if ((rc = upre.alloc(8 * (n_rec + 1)))) return rc;
     if ((rc = gunits.alloc(8 * n_genomes))) return rc;
     if ((rc = kpre.alloc(8 * (n_rec + 1)))) return rc;
@@ -2517,7 +2517,7 @@ static int run_prob_sorted(gs_ctx *c, const gs_sketch_params *p, const uint8_t *
         std::vector<uint64_t> base;
         while (g0 + ng < n_genomes && ng < max_g && (ng == 0 || T + hk[g0 + ng] <= max_items)) { base.push_back(T); T += hk[g0 + ng]; ng++; }
         GS_REQUIRE(T < ((uint64_t)1 << 31), GS_ERR_UNSUPPORTED, "a single genome with more than 2^31 k-mers is not supported by the prob sketcher");
-        PoolBuf dbase(c, 0), q(c, 1), qprev(c, 2), sig(c, 3), sigpass(c, 4), wmax(c, 5), qmax(c, 6), nact(c, 7);
+        PoolBuf dbase(c, SL_PROBS_BASE), q(c, SL_PROBS_Q), qprev(c, SL_PROBS_QPREV), sig(c, SL_PROBS_SIG), sigpass(c, SL_PROBS_SIGPASS), wmax(c, SL_PROBS_WMAX), qmax(c, SL_PROBS_QMAX), nact(c, SL_PROBS_NACT);
         if ((rc = dbase.alloc(8 * ng))) return rc;
         if ((rc = q.alloc(8 * ng * m))) return rc;
         if ((rc = qprev.alloc(8 * ng * m))) return rc;
@@ -2535,7 +2535,7 @@ static int run_prob_sorted(gs_ctx *c, const gs_sketch_params *p, const uint8_t *
             GS_HIP_CHECK(hipStreamSynchronize(c->stream));
         }
         if (T > 0) {
-            PoolBuf vals(c, 8), sorted(c, 9), ukey(c, 10), ucnt(c, 11), nruns(c, 12), tmp(c, 13), candh(c, 14), candb(c, 15);
+            PoolBuf vals(c, SL_PROBS_VALS), sorted(c, SL_PROBS_SORTED), ucnt(c, SL_PROBS_UCNT), nruns(c, SL_PROBS_NRUNS), tmp(c, SL_PROBS_RADIX), candh(c, SL_PROBS_CAND_H), candb(c, SL_PROBS_CAND_B);
             if ((rc = vals.alloc(8 * T))) return rc;
             if ((rc = sorted.alloc(8 * T))) return rc;
             const uint64_t avg_units = (aa ? seq_bytes / 32 : seq_bytes / 8) / n_genomes + 1;
@@ -2550,7 +2550,7 @@ static int run_prob_sorted(gs_ctx *c, const gs_sketch_params *p, const uint8_t *
             int endbit = 64;
             if (vbits < 64) { endbit = (int)vbits; uint64_t x = ng - 1; while (x) { endbit++; x >>= 1; } if (endbit > 64) endbit = 64; }
             // multiplicities = run lengths of the sorted (genome, value) keys: own LSD radix sort + run-length encoding (gs_radix.hip)
-            PoolBuf pos(c, 47);
+            PoolBuf pos(c, SL_PROBS_POS);
             if ((rc = tmp.alloc(radix_scratch_bytes(T)))) return rc;
             if ((rc = pos.alloc(4 * T))) return rc;
             uint64_t *srt = nullptr;
@@ -2569,7 +2569,7 @@ static int run_prob_sorted(gs_ctx *c, const gs_sketch_params *p, const uint8_t *
             if ((rc = candb.alloc(4 * ne))) return rc;
             const uint32_t eg = (uint32_t)std::min<uint64_t>((ne + 255) / 256, (uint64_t)c->n_cu * 16);
             const uint32_t ACT_CAP = 1u << 24;                       // 16 M live elements keep their generator state (0.5 GB)
-            PoolBuf akey(c, 16), acnt(c, 17), astate(c, 18), nlist(c, 19);
+            PoolBuf akey(c, SL_PROBS_AKEY), acnt(c, SL_PROBS_ACNT), astate(c, SL_PROBS_ASTATE), nlist(c, SL_PROBS_NLIST);
             uint32_t n_list = 0; bool use_list = false;
             for (uint32_t it = 1;; it++) {
                 GS_HIP_CHECK(hipMemsetAsync(nact.p, 0, 4, c->stream));
@@ -2898,7 +2898,7 @@ static int run_hll(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
         if (!(f < 1.0)) f = 1.0;
         ucut[K] = (uint64_t)floor(f * 0x1.0p52);                  // u52 < 2^52 always: f = 1 never skips
     }
-    PoolBuf dcut(c, 24), cold(c, 25), cnt(c, 38);
+    PoolBuf dcut(c, SL_HLL_CUT), cold(c, SL_HLL_COLD_FLAGS), cnt(c, SL_HLL_CNT);
     int rc;
     if ((rc = dcut.alloc(8 * ucut.size()))) return rc;
     if ((rc = cold.alloc(n_genomes))) return rc;
@@ -2917,7 +2917,7 @@ static int run_hll(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
     const uint32_t queue_off = use_q ? (uint32_t)((lds0 + 15) & ~(size_t)15) : 0u;
     const size_t lds = use_q ? lds_q : lds0;
     const uint32_t wgs = (uint32_t)std::min<uint64_t>(n_genomes, (uint64_t)c->n_cu * 2);
-    PoolBuf gt(c, 19), sv(c, 46);
+    PoolBuf gt(c, SL_HLL_GTAB), sv(c, SL_HLL_SURVIVORS);
     if (gtab && (rc = gt.alloc((size_t)4 * m * std::max<uint32_t>(wgs, (uint32_t)c->n_cu)))) return rc;
     // survivor lists of pass A: 2^20 hashes (8 MB) per workgroup - ~8 % of the k-mers of a 5 Mbp genome survive the running cut; a longer genome
     // overflows its list and takes the second walk as before (GS_HLL_SURVIVORS=n: lists of n hashes, 0 = always the second walk)
@@ -2966,7 +2966,7 @@ static int run_hll(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
         if (hipMemGetInfo(&fr, &tot) == hipSuccess) budget = std::min<uint64_t>((uint64_t)16 << 30, std::max<uint64_t>((uint64_t)fr / 4, (uint64_t)64 << 20));
         cw = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(cw, budget / ((uint64_t)8 * m * HL_CT)));
     }
-    PoolBuf dl(c, 26), lq(c, 27), lp(c, 37);
+    PoolBuf dl(c, SL_HLL_COLD_LIST), lq(c, SL_HLL_COLD_Q), lp(c, SL_HLL_COLD_P);
     if ((rc = dl.alloc(4 * (size_t)nc))) return rc;
     if ((rc = lq.alloc((size_t)4 * cw * m * HL_CT))) return rc;
     if ((rc = lp.alloc((size_t)4 * cw * m * HL_CT))) return rc;
@@ -3033,7 +3033,7 @@ static int run_hmh(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
                    const uint64_t *rec_upre, const uint64_t *genome_rec_off, const uint64_t *gen_units, uint64_t n_genomes, uint64_t avg_units, uint16_t *sig_out)
 {
     const MinGeom ge = min_geom(c, GS_HMH_M, 4, n_genomes, avg_units);
-    PoolBuf gt(c, 64);
+    PoolBuf gt(c, SL_HMH_GTAB);
     int rc;
     if (ge.parts > 1) {
         if ((rc = gt.alloc((size_t)n_genomes * GS_HMH_M * 4))) return rc;
@@ -3056,6 +3056,18 @@ static int run_hmh(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, con
     return GS_OK;
 }
 
+// what every slot-min algorithm starts with: the unit prefix of the records and the units of each genome, queued on c's stream
+static int unit_prefix(gs_ctx *c, uint32_t k, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes,
+                       PoolBuf &upre, PoolBuf &gunits)
+{
+    int rc;
+    if ((rc = upre.alloc(8 * (n_rec + 1))) || (rc = gunits.alloc(8 * n_genomes))) return rc;
+    hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len, genome_rec_off, n_genomes, k, upre.as<uint64_t>(),
+                       gunits.as<uint64_t>());
+    GS_HIP_CHECK(hipGetLastError());
+    return GS_OK;
+}
+
 int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start,
                     const uint64_t *rec_len, uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes, void *sig_out, bool sync_at_end)
 {
@@ -3068,30 +3080,22 @@ int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint6
     GS_HIP_CHECK(hipSetDevice(c->device));
     const uint32_t m = p->sketch_size;
     if (p->algo == GS_ALGO_OPTDENS || p->algo == GS_ALGO_REVOPTDENS) {
-        PoolBuf upre(c, 20), gunits(c, 21), table(c, 22), win(c, 23);
-        rc = upre.alloc(8 * (n_rec + 1)); if (rc) return rc;
-        rc = gunits.alloc(8 * n_genomes); if (rc) return rc;
+        PoolBuf upre(c, SL_SK_REC_UNITS), gunits(c, SL_SK_GENOME_UNITS), table(c, SL_OPH_TABLE), win(c, SL_OPH_WIN);
+        rc = unit_prefix(c, p->k, rec_start, rec_len, n_rec, genome_rec_off, n_genomes, upre, gunits); if (rc) return rc;
         rc = table.alloc((size_t)n_genomes * m * 4); if (rc) return rc;
         if (p->algo == GS_ALGO_REVOPTDENS) { rc = win.alloc((size_t)n_genomes * m * 4); if (rc) return rc; }
-        hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len,
-                           genome_rec_off, n_genomes, p->k, upre.as<uint64_t>(), gunits.as<uint64_t>());
-        GS_HIP_CHECK(hipGetLastError());
         uint64_t avg_units = (p->data_t == GS_DATA_AA ? seq_bytes / 32 : seq_bytes / 8) / n_genomes + 1;
         rc = launch_oph(c, p, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(), genome_rec_off, gunits.as<uint64_t>(),
                         n_genomes, avg_units, table.as<uint32_t>(), win.as<uint32_t>(), (float *)sig_out);
         if (rc) return rc;
-        // (the scratch slots are only reused by later calls on this context, i.e. behind these kernels on its stream: a caller that pipelines
-        // several sketches - gs_index_sketch_and_search_dev - may leave the wait to its own events)
+        // (the leases end here with the kernels still queued: the slots are only reused by later calls on this context, i.e. behind these kernels on
+        // its stream - a caller that pipelines several sketches, gs_index_sketch_and_search_dev, may leave the wait to its own events)
         if (sync_at_end) GS_HIP_CHECK(hipStreamSynchronize(c->stream));
         return GS_OK;
     }
     if (p->algo == GS_ALGO_SUPER || p->algo == GS_ALGO_SUPER2) {
-        PoolBuf upre(c, 20), gunits(c, 21);
-        rc = upre.alloc(8 * (n_rec + 1)); if (rc) return rc;
-        rc = gunits.alloc(8 * n_genomes); if (rc) return rc;
-        hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len,
-                           genome_rec_off, n_genomes, p->k, upre.as<uint64_t>(), gunits.as<uint64_t>());
-        GS_HIP_CHECK(hipGetLastError());
+        PoolBuf upre(c, SL_SK_REC_UNITS), gunits(c, SL_SK_GENOME_UNITS);
+        rc = unit_prefix(c, p->k, rec_start, rec_len, n_rec, genome_rec_off, n_genomes, upre, gunits); if (rc) return rc;
         const uint64_t avg_units = (p->data_t == GS_DATA_AA ? seq_bytes / 32 : seq_bytes / 8) / n_genomes + 1;
         const uint8_t *sq = (const uint8_t *)seq;
         const uint64_t *up = upre.as<uint64_t>(), *gu = gunits.as<uint64_t>();
@@ -3104,24 +3108,16 @@ int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint6
         return GS_OK;
     }
     if (p->algo == GS_ALGO_HLL) {
-        PoolBuf upre(c, 20), gunits(c, 21);
-        rc = upre.alloc(8 * (n_rec + 1)); if (rc) return rc;
-        rc = gunits.alloc(8 * n_genomes); if (rc) return rc;
-        hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len,
-                           genome_rec_off, n_genomes, p->k, upre.as<uint64_t>(), gunits.as<uint64_t>());
-        GS_HIP_CHECK(hipGetLastError());
+        PoolBuf upre(c, SL_SK_REC_UNITS), gunits(c, SL_SK_GENOME_UNITS);
+        rc = unit_prefix(c, p->k, rec_start, rec_len, n_rec, genome_rec_off, n_genomes, upre, gunits); if (rc) return rc;
         rc = run_hll(c, p, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(), genome_rec_off, gunits.as<uint64_t>(), n_genomes, (p->data_t == GS_DATA_AA ? seq_bytes / 32 : seq_bytes / 8) + n_rec + 1, (uint16_t *)sig_out);
         if (rc) return rc;
         GS_HIP_CHECK(hipStreamSynchronize(c->stream));
         return GS_OK;
     }
     if (p->algo == GS_ALGO_HMH) {
-        PoolBuf upre(c, 20), gunits(c, 21);
-        rc = upre.alloc(8 * (n_rec + 1)); if (rc) return rc;
-        rc = gunits.alloc(8 * n_genomes); if (rc) return rc;
-        hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len,
-                           genome_rec_off, n_genomes, p->k, upre.as<uint64_t>(), gunits.as<uint64_t>());
-        GS_HIP_CHECK(hipGetLastError());
+        PoolBuf upre(c, SL_SK_REC_UNITS), gunits(c, SL_SK_GENOME_UNITS);
+        rc = unit_prefix(c, p->k, rec_start, rec_len, n_rec, genome_rec_off, n_genomes, upre, gunits); if (rc) return rc;
         rc = run_hmh(c, p, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(), genome_rec_off, gunits.as<uint64_t>(), n_genomes,
                      seq_bytes / 8 / n_genomes + 1, (uint16_t *)sig_out);
         if (rc) return rc;
@@ -3168,7 +3164,7 @@ int gs_sketch_batch(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint6
     GS_HIP_CHECK(hipSetDevice(c->device));
     // staging from the context's grow-only pool: a hipMalloc / hipFree pair per call costs more than a small sketch and, worse, hipFree waits for
     // every stream of the device - which would serialise the worker contexts of other host threads
-    gs::PoolBuf dseq(c, 48), drs(c, 49), drl(c, 50), dgo(c, 51), dsig(c, 52);
+    gs::PoolBuf dseq(c, gs::SL_SKB_SEQ), drs(c, gs::SL_SKB_REC_START), drl(c, gs::SL_SKB_REC_LEN), dgo(c, gs::SL_SKB_GENOME_OFF), dsig(c, gs::SL_SKB_SIG);
     const uint64_t padded = gs::round_up(seq_bytes, 32) + 32;
     const size_t sigbytes = (size_t)n_genomes * p->sketch_size * gs_sig_elem_bytes(p);
     if ((rc = dseq.alloc(padded))) return rc;
