@@ -175,6 +175,9 @@ int knn_stats_dev(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t *ids, con
 // gs_sketch.hip: the device sketch of a batch on context c's stream; sync_at_end = false leaves the results in flight (optdens / revoptdens only)
 int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
                     const uint64_t *genome_rec_off, uint64_t n_genomes, void *sig_out, bool sync_at_end);
+// gs_prob.hip: the ProbMinHash3a sketcher (tiered, bucketed and sorted forms) behind sketch_dev_impl; the results are left in flight on c's stream
+int run_prob(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+             const uint64_t *genome_rec_off, uint64_t n_genomes, void *sig_out);
 // gs_radix.hip: stable LSD radix sort of 64-bit keys (bits [0, endbit)) between two buffers, and run-length encoding of a sorted array
 size_t radix_scratch_bytes(uint64_t n);
 int radix_sort_u64(gs_ctx *c, uint64_t *keys, uint64_t *alt, uint64_t n, int endbit, void *scratch, uint64_t **sorted_out);

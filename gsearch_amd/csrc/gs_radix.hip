@@ -1,5 +1,5 @@
 // gs_radix.hip — stable LSD radix sort of 64-bit keys and run-length encoding of a sorted array, for the sorted (fallback) form of the
-// ProbMinHash3a sketcher (gs_sketch.hip run_prob_sorted: the genomes the bucketed form does not suit - fewer than 64 k-mers per slot, more than
+// ProbMinHash3a sketcher (gs_prob.hip run_prob_sorted: the genomes the bucketed form does not suit - fewer than 64 k-mers per slot, more than
 // 25 M k-mers, an overfull bucket). Multiplicities w(v) of SPEC 3.3 are the run lengths of the sorted (genome, value) keys
 // (/root/reference/src/dna/dnasketch.rs:499-518 counts them in a hash map before ProbMinHash3a::hash_weighted...).
 // Written for wave64: one wavefront owns a tile of RS_TILE consecutive keys in both passes, so stability needs no cross-wave ordering -

@@ -1,5 +1,5 @@
 #!/bin/bash
-# register / LDS / scratch use of every kernel of a .hip source (device-only assembly, gfx950): usage tools/kregs.sh gsearch_amd/csrc/gs_join.hip [name filter] [extra hipcc flags]
+# register / LDS / scratch use of every kernel of a .hip source (device-only assembly, gfx950): usage tools/kregs.sh gsearch_amd/csrc/gs_join.hip [name filter] [extra hipcc flags] (one file per call: the k_prob_* kernels are in gs_prob.hip, the other sketchers in gs_sketch.hip)
 S=$(mktemp --suffix=.s)
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off --cuda-device-only -S -o $S $3 "$1" 2>/dev/null
 python3 - "$S" "$2" <<'P'
