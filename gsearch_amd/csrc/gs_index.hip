@@ -18,12 +18,14 @@
 #include <functional>
 #include <chrono>
 #include <math.h>
+#include <memory>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include <sys/stat.h>
 #include "gs_internal.hpp"
 #include "gs_spec.hpp"
+#include "gs_insert_rows.hpp"
 
 namespace gs {
 
@@ -2218,9 +2220,13 @@ struct gs_index {
     gs::VmArena sp_vm;                // lists + level bitmaps (grow in place; sp_arena = the device-side bump allocator over it)
     bool sp_exhausted = false;        // the arena (or the device) is full: lists are still handed out while they fit, nothing more is mapped
     uint64_t sp_reserved = 0;         // upper bound of the arena bytes handed out so far (worst case per launch; corrected from the device when it runs out)
-    std::vector<gs::DevBuf *> slabs;
+    // the dense pair cache: one slab per insert call that took one, and the all-pairs rows of the nodes older than the first cached batch. drop_pair_cache
+    // frees them all from under whoever runs (it is reached through alloc_or_evict), so nobody keeps a slab's address: call_slab and early_rows are
+    // asked for where they are used, and are null once the cache was given back
+    std::vector<std::unique_ptr<gs::DevBuf>> slabs;
+    gs::DevBuf *call_slab = nullptr;  // the slab of the insert call under way (InsertCall::take_slab)
+    gs::DevBuf *early_rows = nullptr; // null: those nodes have no cached rows (InsertCall::early_rows)
     uint64_t pair_cache_bytes = 0, pair_cache_budget = 0;
-    bool early_cached = false;        // the nodes older than the first cached batch have all-pairs rows (insert_common)
     // hnsw_rs' DataId / PointId (answer.rs:42-57 reads Neighbour{d_id, distance, p_id}): nodes are numbered 0.. in insertion order inside the
     // library; `origin` maps them to the ids the caller inserted them under (empty = the caller's ids ARE 0.. in order, gsearch's own case,
     // dnasketch.rs:429-433), pid_rank[i] = rank of node i among the nodes of its level (PointId = (level, rank))
@@ -2231,10 +2237,6 @@ struct gs_index {
     // gs_index_sketch_and_search_dev: the padded query rows are produced batch by batch while the search is under way; dense_counts asks for
     // rows [q0, q0 + nb) of the buffer at feed_base just before it joins them
     std::function<int(uint64_t, uint64_t)> *feed = nullptr; const uint8_t *feed_base = nullptr;
-    ~gs_index()
-    {
-        for (auto *b : slabs) delete b;
-    }
 };
 
 namespace gs {
@@ -2250,10 +2252,10 @@ static void drop_pair_cache(gs_index *ix)
         (void)hipStreamSynchronize(ix->ctx->stream);
         if (ix->rowptr.p) (void)hipMemsetAsync(ix->rowptr.p, 0, ix->rowptr.bytes, ix->ctx->stream);
         (void)hipStreamSynchronize(ix->ctx->stream);
-        for (auto *b : ix->slabs) delete b;
         ix->slabs.clear();
     }
-    ix->pair_cache_bytes = 0; ix->pair_cache_budget = 1; ix->early_cached = false;
+    ix->call_slab = ix->early_rows = nullptr;
+    ix->pair_cache_bytes = 0; ix->pair_cache_budget = 1;
 }
 // DevBuf::alloc that pays with the pair cache when the device is full
 static int alloc_or_evict(gs_index *ix, DevBuf &b, size_t bytes)
@@ -2503,56 +2505,79 @@ static uint32_t dense_split_w(const gs_index *ix, uint32_t knbn, uint32_t maxdeg
     if (w < 1024) return 0;
     return (uint32_t)std::min<uint64_t>(w, round_up(ix->n, 1024));
 }
+// The launch geometry of k_hnsw_search_dense, worked out in ONE place for its two launch sites: a search request (search_launch_dense) and the insert
+// pre-pass (plan_prepass, with_log: the accepted-key log form, instantiated for the LDS bitmap and its split form only, never a 512-lane group).
+struct DenseGeom {
+    bool ok;                    // this placement fits the LDS
+    bool oneg, split, vlds;     // rows of more than 256 ids: one 512-lane group instead of two halves; split bitmap; bitmap (or its lower part) in LDS
+    uint32_t dcn, vis_w;        // vis_w: node ids the LDS bitmap maps in the split form, 0 otherwise
+    size_t lds;
+    uint32_t per_cu, scratch_words, capC, grid;
+    uint32_t p2_off;            // GS_DENSE_PHASE2=0: the order-free phase 2 switched off, for A/B runs
+};
+static DenseGeom dense_geom(const gs_index *ix, uint64_t nq, uint32_t knbn, uint32_t ef, size_t min_lds_bytes, bool many_queries, bool with_log)
+{
+    const gs_ctx *c = ix->ctx;
+    const size_t cap = 160 * 1024 - 1024;
+    const uint32_t efs = std::max(ef, knbn), maxdeg = 2 * ix->prm.max_nb_conn;
+    DenseGeom g{};
+    g.oneg = maxdeg > (uint32_t)DT / 2;
+    g.dcn = g.oneg ? 512u : (uint32_t)DCN;
+    g.vis_w = dense_split_w(ix, knbn, maxdeg, g.dcn, min_lds_bytes, many_queries);
+    g.split = g.vis_w != 0;
+    const bool whole = dense_vis_in_lds(ix, knbn, maxdeg);             // the whole bitmap fits the LDS and GS_DENSE_VIS allows it
+    g.vlds = with_log || g.split || whole;
+    g.lds = std::max(dense_lds_bytes(ix->prm.m, knbn, maxdeg, g.split ? (uint64_t)g.vis_w : ix->n, g.vlds, g.dcn), min_lds_bytes);
+    if (with_log && g.oneg) g.ok = false;                              // the log form has no 512-lane group
+    else if (g.split) g.ok = true;                                     // the split form is sized to fit
+    else if (whole) g.ok = g.lds <= cap;                               // the whole bitmap in LDS, where the placement rule says so
+    else g.ok = !with_log && g.lds <= cap;                             // the bitmap in global memory has no log form
+    // three 8-wave workgroups per CU while the LDS allows it (n <= ~300 k with the bitmap in LDS): that build is capped at 80 VGPRs
+    // (18 dwords spill, none on the per-pop path); the two-per-CU build (<= 128 VGPRs) takes over for larger n
+    const size_t granted = round_up(g.lds, 1280);                      // LDS is granted in 1280-byte granules
+    g.per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / granted));
+    if (g.oneg) g.per_cu = std::min<uint32_t>(g.per_cu, 2);              // that build is not capped at 80 VGPRs
+    if (!with_log && getenv("GS_DENSE_PER_CU")) g.per_cu = std::max(1, std::min((int)g.per_cu, atoi(getenv("GS_DENSE_PER_CU"))));     // (a knob of the request path)
+    // per-workgroup global scratch: visited bitmap (vlds = false) or the fine histogram bins (vlds = true), + the upper ids of the split bitmap
+    g.scratch_words = (g.vlds ? dense_nblocks(ix->prm.m) * (HB / 2) : (uint32_t)((ix->n + 31) / 32)) + (g.split && ix->n > g.vis_w ? (uint32_t)((ix->n - g.vis_w + 31) / 32) : 0u);
+    g.capC = 2 * efs + 2 * g.dcn + maxdeg + 64;
+    g.grid = (uint32_t)std::min<uint64_t>(nq, (uint64_t)c->n_cu * g.per_cu);
+    g.p2_off = (getenv("GS_DENSE_PHASE2") && !atoi(getenv("GS_DENSE_PHASE2"))) ? 1u : 0u;
+    return g;
+}
+// (dense_traversal_fits has vouched for the fit: search_launch only comes here after it)
 static int search_launch_dense(gs_index *ix, uint64_t nq, uint32_t knbn, uint32_t ef, const uint16_t *mat, uint64_t mat_ld, uint64_t *ids, float *dist,
                                uint32_t *count, uint64_t *evals)
 {
     gs_ctx *c = ix->ctx;
-    const uint32_t efs = std::max(ef, knbn);
-    const uint32_t maxdeg = 2 * ix->prm.max_nb_conn;
-    const bool oneg = maxdeg > (uint32_t)DT / 2;                       // rows of more than 256 ids: one 512-lane group instead of two halves
-    const uint32_t dcn = oneg ? 512u : (uint32_t)DCN;
-    const uint32_t vis_w = dense_split_w(ix, knbn, maxdeg, dcn, 0, nq >= (uint64_t)2 * c->n_cu);
-    const bool split = vis_w != 0;
-    const bool vlds = split || dense_vis_in_lds(ix, knbn, maxdeg);
-    const size_t lds = dense_lds_bytes(ix->prm.m, knbn, maxdeg, split ? (uint64_t)vis_w : ix->n, vlds, dcn);
-    // three 8-wave workgroups per CU while the LDS allows it (n <= ~300 k with the bitmap in LDS): that build is capped at 80 VGPRs
-    // (18 dwords spill, none on the per-pop path); the two-per-CU build (<= 128 VGPRs) takes over for larger n
-    const size_t granted = round_up(lds, 1280);                       // LDS is granted in 1280-byte granules
-    uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / granted));
-    if (oneg) per_cu = std::min<uint32_t>(per_cu, 2);                    // that build is not capped at 80 VGPRs
-    if (getenv("GS_DENSE_PER_CU")) per_cu = std::max(1, std::min((int)per_cu, atoi(getenv("GS_DENSE_PER_CU"))));
-    // per-workgroup global scratch: visited bitmap (vlds = false) or the fine histogram bins (vlds = true)
-    const uint32_t scratch_words = (vlds ? dense_nblocks(ix->prm.m) * (HB / 2) : (uint32_t)((ix->n + 31) / 32)) + (split && ix->n > vis_w ? (uint32_t)((ix->n - vis_w + 31) / 32) : 0u);
-    const uint32_t capC = 2 * efs + 2 * dcn + maxdeg + 64;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(nq, (uint64_t)c->n_cu * per_cu);
+    const DenseGeom g = dense_geom(ix, nq, knbn, ef, 0, nq >= (uint64_t)2 * c->n_cu, false);
     int rc;
     if ((rc = ensure_stats(ix))) return rc;
-    ix->stat_wg_in_flight = grid; ix->stat_adj_row_bytes = (uint64_t)4 * maxdeg + 4;      // a pop loads deg0 and the full 2M-id row
-    if ((rc = ix->visited.ensure((size_t)4 * scratch_words * c->n_cu * 3))) return rc;
-    if ((rc = ix->cbuf.ensure((size_t)16 * capC * c->n_cu * 3))) return rc;
+    ix->stat_wg_in_flight = g.grid; ix->stat_adj_row_bytes = (uint64_t)8 * ix->prm.max_nb_conn + 4;      // a pop loads deg0 and the full 2M-id row
+    if ((rc = ix->visited.ensure((size_t)4 * g.scratch_words * c->n_cu * 3))) return rc;
+    if ((rc = ix->cbuf.ensure((size_t)16 * g.capC * c->n_cu * 3))) return rc;
     GS_HIP_CHECK(hipMemsetAsync(ix->counter.p, 0, 8, c->stream));
     IndexDev d = index_dev(ix);
-    // (without an accepted-key log the cap_log argument is free: its low bit switches the order-free phase 2 off, GS_DENSE_PHASE2=0, for A/B runs)
-    const uint32_t p2_off = (getenv("GS_DENSE_PHASE2") && !atoi(getenv("GS_DENSE_PHASE2"))) ? 1u : 0u;
     unsigned long long *prof = nullptr;
     DevBuf profbuf;
     if (getenv("GS_TRAV_PROFILE")) { if ((rc = profbuf.alloc(128))) return rc; GS_HIP_CHECK(hipMemsetAsync(profbuf.p, 0, 128, c->stream)); prof = profbuf.as<unsigned long long>(); }
     {
     ProfScope ps(c, FAM_SEARCH);
+    // (without an accepted-key log the cap_log argument is free: its low bit carries p2_off)
 #define GS_LAUNCH_DSEARCH(V, P, O, G) GS_LAUNCH_DSEARCH_S(V, P, O, G, false)
 #define GS_LAUNCH_DSEARCH_S(V, P, O, G, SP)                                                                                  \
     do {                                                                                                                  \
         auto kern = k_hnsw_search_dense<V, P, O, G, false, SP>;                                                            \
-        GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(DT), lds, c->stream, d, nq, knbn, ef, mat, mat_ld, ix->visited.as<uint32_t>(), scratch_words, \
-                           ix->cbuf.as<uint64_t>(), capC, ix->counter.as<unsigned long long>(), ids, dist, count, evals, prof, ix->stats.as<unsigned long long>(),  \
-                           (uint64_t *)nullptr, p2_off, 0u, (uint64_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr, vis_w);  \
+        GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));    \
+        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(DT), g.lds, c->stream, d, nq, knbn, ef, mat, mat_ld, ix->visited.as<uint32_t>(), g.scratch_words, \
+                           ix->cbuf.as<uint64_t>(), g.capC, ix->counter.as<unsigned long long>(), ids, dist, count, evals, prof, ix->stats.as<unsigned long long>(),  \
+                           (uint64_t *)nullptr, g.p2_off, 0u, (uint64_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr, g.vis_w);  \
     } while (0)
-    if (split) { if (oneg) GS_LAUNCH_DSEARCH_S(true, false, 4, true, true); else GS_LAUNCH_DSEARCH_S(true, false, 4, false, true); }
-    else if (oneg) { if (vlds) GS_LAUNCH_DSEARCH(true, false, 4, true); else GS_LAUNCH_DSEARCH(false, false, 4, true); }
-    else if (prof) { if (vlds) GS_LAUNCH_DSEARCH(true, true, 4, false); else GS_LAUNCH_DSEARCH(false, true, 4, false); }
-    else if (per_cu >= 3) { if (vlds) GS_LAUNCH_DSEARCH(true, false, 6, false); else GS_LAUNCH_DSEARCH(false, false, 6, false); }
-    else { if (vlds) GS_LAUNCH_DSEARCH(true, false, 4, false); else GS_LAUNCH_DSEARCH(false, false, 4, false); }
+    if (g.split) { if (g.oneg) GS_LAUNCH_DSEARCH_S(true, false, 4, true, true); else GS_LAUNCH_DSEARCH_S(true, false, 4, false, true); }
+    else if (g.oneg) { if (g.vlds) GS_LAUNCH_DSEARCH(true, false, 4, true); else GS_LAUNCH_DSEARCH(false, false, 4, true); }
+    else if (prof) { if (g.vlds) GS_LAUNCH_DSEARCH(true, true, 4, false); else GS_LAUNCH_DSEARCH(false, true, 4, false); }
+    else if (g.per_cu >= 3) { if (g.vlds) GS_LAUNCH_DSEARCH(true, false, 6, false); else GS_LAUNCH_DSEARCH(false, false, 6, false); }
+    else { if (g.vlds) GS_LAUNCH_DSEARCH(true, false, 4, false); else GS_LAUNCH_DSEARCH(false, false, 4, false); }
 #undef GS_LAUNCH_DSEARCH
 #undef GS_LAUNCH_DSEARCH_S
     }
@@ -3167,37 +3192,32 @@ static int sparse_fill(gs_index *ix, const uint16_t *rows, uint64_t ld, uint64_t
     GS_HIP_CHECK(hipGetLastError());
     return GS_OK;
 }
-static bool prepass_ok(const gs_index *ix, uint32_t efc)
+// The pre-pass's launch of the dense traversal: knbn = 1, ef = ef_construction, the bitmap in LDS (whole or split), room for the epilogue's sort
+struct PrepassGeom {
+    DenseGeom g;
+    uint32_t sort_cap;      // keys the epilogue can sort: ties at dmax ride along
+};
+// the pre-pass can take a batch of nb points: its own static limits, and the geometry (left in *pg for plan_prepass) fits
+static bool prepass_ok(const gs_index *ix, uint32_t nb, uint32_t efc, PrepassGeom *pg)
 {
-    const uint32_t maxdeg = 2 * ix->prm.max_nb_conn, knbn = 1;
-    if (getenv("GS_PLAN_PREPASS") && !atoi(getenv("GS_PLAN_PREPASS"))) return false;
-    if (ix->n < 4096 || ix->entry < 0 || maxdeg > (uint32_t)DT / 2 || efc > 65535u || efc < 2 || ix->prm.m > 65535u) return false;
-    uint32_t sort_cap = 2; while (sort_cap < 4 * efc) sort_cap <<= 1;
-    if (dense_split_w(ix, knbn, maxdeg, (uint32_t)DCN, (size_t)8 * sort_cap + 64)) return true;     // (round 5) beyond the LDS: the split bitmap
-    if (!dense_vis_in_lds(ix, knbn, maxdeg)) return false;                       // WLOG is instantiated for the LDS bitmap and its split form
-    return std::max<size_t>(dense_lds_bytes(ix->prm.m, knbn, maxdeg, ix->n, true), (size_t)8 * sort_cap + 64) <= 160 * 1024 - 1024;
+    if (ix->n < 4096 || ix->entry < 0 || efc > 65535u || efc < 2 || ix->prm.m > 65535u) return false;
+    pg->sort_cap = 2; while (pg->sort_cap < 4 * efc) pg->sort_cap <<= 1;
+    pg->g = dense_geom(ix, nb, 1, efc, (size_t)8 * pg->sort_cap + 64, false, true);
+    return pg->g.ok;
 }
-static int plan_prepass(gs_index *ix, uint32_t nb, uint32_t efc, const uint16_t *mat, uint64_t mat_ld, const uint64_t **w0k, const uint32_t **w0n, const uint64_t **w0e)
+static int plan_prepass(gs_index *ix, const PrepassGeom &pg, uint32_t nb, uint32_t efc, const uint16_t *mat, uint64_t mat_ld, const uint64_t **w0k, const uint32_t **w0n,
+                        const uint64_t **w0e)
 {
     gs_ctx *c = ix->ctx;
     *w0k = nullptr; *w0n = nullptr; *w0e = nullptr;
-    const uint32_t maxdeg = 2 * ix->prm.max_nb_conn, knbn = 1;
-    uint32_t sort_cap = 2; while (sort_cap < 4 * efc) sort_cap <<= 1;             // keys the epilogue can sort: ties at dmax ride along
-    const uint32_t vis_w = dense_split_w(ix, knbn, maxdeg, (uint32_t)DCN, (size_t)8 * sort_cap + 64);
-    size_t lds = dense_lds_bytes(ix->prm.m, knbn, maxdeg, vis_w ? (uint64_t)vis_w : ix->n, true);
-    lds = std::max<size_t>(lds, (size_t)8 * sort_cap + 64);
-    const size_t granted = round_up(lds, 1280);
-    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(3, (160 * 1024) / granted));
-    const uint32_t scratch_words = dense_nblocks(ix->prm.m) * (HB / 2) + (vis_w && ix->n > vis_w ? (uint32_t)((ix->n - vis_w + 31) / 32) : 0u);
-    const uint32_t capC = 2 * efc + 2 * (uint32_t)DCN + maxdeg + 64,
-                   cap_log = 16 * efc + ((getenv("GS_DENSE_PHASE2") && !atoi(getenv("GS_DENSE_PHASE2"))) ? 1u : 0u);      // (odd = order-free phase 2 off, A/B)
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(nb, (uint64_t)c->n_cu * per_cu);
+    const DenseGeom &g = pg.g;
+    const uint32_t knbn = 1, cap_log = 16 * efc + g.p2_off;      // (odd = order-free phase 2 off, A/B)
     int rc;
     if ((rc = ensure_stats(ix))) return rc;
-    if ((rc = ix->visited.ensure((size_t)4 * scratch_words * c->n_cu * 3))) return rc;
-    if ((rc = ix->cbuf.ensure((size_t)16 * capC * c->n_cu * 3))) return rc;
+    if ((rc = ix->visited.ensure((size_t)4 * g.scratch_words * c->n_cu * 3))) return rc;
+    if ((rc = ix->cbuf.ensure((size_t)16 * g.capC * c->n_cu * 3))) return rc;
     if ((rc = ix->counter.ensure(64))) return rc;
-    if ((rc = ix->wlog.ensure((size_t)8 * cap_log * grid))) return rc;
+    if ((rc = ix->wlog.ensure((size_t)8 * cap_log * g.grid))) return rc;
     if ((rc = ix->w0_keys.ensure((size_t)8 * efc * nb))) return rc;
     if ((rc = ix->w0_n.ensure((size_t)4 * nb))) return rc;
     if ((rc = ix->w0_evals.ensure((size_t)8 * nb))) return rc;
@@ -3208,13 +3228,13 @@ static int plan_prepass(gs_index *ix, uint32_t nb, uint32_t efc, const uint16_t 
 #define GS_LAUNCH_WL_S(O, SP)                                                                                             \
     do {                                                                                                                  \
         auto kern = k_hnsw_search_dense<true, false, O, false, true, SP>;                                                 \
-        GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));      \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(DT), lds, c->stream, d, (uint64_t)nb, knbn, efc, mat, mat_ld, ix->visited.as<uint32_t>(), scratch_words, \
-                           ix->cbuf.as<uint64_t>(), capC, ix->counter.as<unsigned long long>(), (uint64_t *)nullptr, (float *)nullptr, (uint32_t *)nullptr, \
-                           ix->w0_evals.as<uint64_t>(), (unsigned long long *)nullptr, (unsigned long long *)nullptr, ix->wlog.as<uint64_t>(), cap_log, sort_cap, \
-                           ix->w0_keys.as<uint64_t>(), ix->w0_n.as<uint32_t>(), ix->ep0.as<uint32_t>(), vis_w);               \
+        GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));    \
+        hipLaunchKernelGGL(kern, dim3(g.grid), dim3(DT), g.lds, c->stream, d, (uint64_t)nb, knbn, efc, mat, mat_ld, ix->visited.as<uint32_t>(), g.scratch_words, \
+                           ix->cbuf.as<uint64_t>(), g.capC, ix->counter.as<unsigned long long>(), (uint64_t *)nullptr, (float *)nullptr, (uint32_t *)nullptr, \
+                           ix->w0_evals.as<uint64_t>(), (unsigned long long *)nullptr, (unsigned long long *)nullptr, ix->wlog.as<uint64_t>(), cap_log, pg.sort_cap, \
+                           ix->w0_keys.as<uint64_t>(), ix->w0_n.as<uint32_t>(), ix->ep0.as<uint32_t>(), g.vis_w);             \
     } while (0)
-        if (vis_w) GS_LAUNCH_WL_S(4, true); else if (per_cu >= 3) GS_LAUNCH_WL(6); else GS_LAUNCH_WL(4);
+        if (g.split) GS_LAUNCH_WL_S(4, true); else if (g.per_cu >= 3) GS_LAUNCH_WL(6); else GS_LAUNCH_WL(4);
 #undef GS_LAUNCH_WL
 #undef GS_LAUNCH_WL_S
     }
@@ -3224,284 +3244,329 @@ static int plan_prepass(gs_index *ix, uint32_t nb, uint32_t efc, const uint16_t 
 }
 }  // namespace gs
 
-static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n, const uint64_t *ids = nullptr)
-{
-    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
-    if (n == 0) return GS_OK;
-    GS_REQUIRE(sigs, GS_ERR_INVALID, "null signatures");
-    gs_ctx *c = ix->ctx;
-    GS_CTX_LOCK(c);
-    const uint32_t M = ix->prm.max_nb_conn, ML = ix->prm.max_layer, maxdeg = 2 * M, efc = ix->prm.ef_construction;
-    const uint32_t B = std::min<uint32_t>(std::min<uint32_t>(ix->prm.insert_batch, 256u), gs::ST);
-    GS_REQUIRE(!ix->prm.keep_pruned, GS_ERR_UNSUPPORTED, "keep_pruned=true is not implemented on the device (gsearch sets false, dnasketch.rs:160)");
-    GS_REQUIRE(ix->n + n < ((uint64_t)1 << 32) - 1, GS_ERR_INVALID, "too many points");
-    GS_HIP_CHECK(hipSetDevice(c->device));
-    // levels and upper-layer slots of the new points (host: needs libm log, like the oracle)
-    std::vector<uint8_t> lv(n);
-    std::vector<int32_t> up(n);
-    uint64_t nup = ix->n_upper;
-    for (uint64_t i = 0; i < n; i++) { lv[i] = (uint8_t)gen_level_host(ix, ix->n + i); up[i] = lv[i] > 0 ? (int32_t)nup++ : -1; }
-    int rc = gs::index_reserve(ix, ix->n + n, nup);
-    if (rc) return rc;
-    const uint64_t first = ix->n;
-    gs::ids_append(ix, ids, lv.data(), n);
-    struct IdGuard {          // an insert that fails half-way leaves ix->n behind first + n: drop the ids / ranks of the points that did not make it
-        gs_index *ix; const std::vector<uint8_t> &lv; uint64_t first;
-        ~IdGuard()
-        {
-            for (uint64_t i = ix->n > first ? ix->n - first : 0; i < lv.size() && first + i < ix->pid_rank.size(); i++) ix->level_count[lv[i] <= 16 ? lv[i] : 16]--;
-            if (ix->pid_rank.size() > ix->n) ix->pid_rank.resize(ix->n);
-            if (ix->origin.size() > ix->n) ix->origin.resize(ix->n);
-        }
-    } id_guard{ix, lv, first};
-    if ((rc = gs::upload_user_rows(ix, ix->data.as<uint8_t>() + first * ix->stride, sigs, n, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
-    GS_HIP_CHECK(hipMemcpyAsync(ix->levels.as<uint8_t>() + first, lv.data(), n, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(ix->upidx.as<int32_t>() + first, up.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
-    // scratch
-    const uint32_t ef_lds = std::max(efc, B);
-    const size_t lds = gs::search_lds_bytes(ef_lds, maxdeg);
-    GS_REQUIRE(lds <= 160 * 1024 - 64, GS_ERR_UNSUPPORTED, "ef_construction=%u needs %zu bytes of LDS", efc, lds);
-    GS_REQUIRE(2 * (size_t)ef_lds + maxdeg + 64 <= (size_t)gs::SMAXI * gs::ST && maxdeg <= (uint32_t)gs::ST, GS_ERR_UNSUPPORTED, "ef_construction too large");
-    const uint32_t vis_words = (uint32_t)((first + n + 31) / 32);
-    if ((rc = ix->visited.ensure((size_t)4 * vis_words * std::max<uint32_t>(B, c->n_cu)))) return rc;
-    if ((rc = ix->blevels.ensure(B))) return rc;
-    if ((rc = ix->cntmat.ensure((size_t)4 * B * B))) return rc;
-    if ((rc = ix->plan_keys.ensure((size_t)8 * B * ML * maxdeg))) return rc;
-    if ((rc = ix->plan_n.ensure((size_t)4 * B * ML))) return rc;
-    if ((rc = ix->touched.ensure((size_t)4 * B * (maxdeg + (size_t)ML * M)))) return rc;
-    if ((rc = ix->ntouched.ensure(64))) return rc;
-    // extend_candidates with ef_construction <= 2M: every layer-0 selection extends W by the neighbours of its members (select_extended);
-    // one key array per point of a batch, sized for every node the extension can reach (a power of two: it is bitonic-sorted in place)
+namespace {
+// The knobs of parallel_insert, read once per CALL (never once per process: the tests change them between calls). The sparse set-up still ACTS on its
+// five only the first time, through sp_tried.
+struct InsertEnv {
+    const char *pair_cache_gb = getenv("GS_PAIR_CACHE_GB");
+    const char *sparse_rows = getenv("GS_SPARSE_ROWS"), *sparse_l = getenv("GS_SPARSE_L"), *sparse_arena_gb = getenv("GS_SPARSE_ARENA_GB"),
+               *sparse_bitmap_gb = getenv("GS_SPARSE_BITMAP_GB"), *sparse_chunk_mb = getenv("GS_SPARSE_ARENA_CHUNK_MB");
+    uint32_t group = 8;         // GS_INSERT_GROUP: batches joined together (1 = every batch its own join)
+    bool prepass = !(getenv("GS_PLAN_PREPASS") && !atoi(getenv("GS_PLAN_PREPASS")));
+    bool plan_vis_global = getenv("GS_PLAN_VIS_GLOBAL") != nullptr, sparse_verbose = getenv("GS_SPARSE_VERBOSE") != nullptr;
+    InsertEnv() { if (const char *e = getenv("GS_INSERT_GROUP")) group = (uint32_t)std::max(1, std::min(12, atoi(e))); }
+};
+
+// One parallel_insert call: insert_common below is the batch loop over its steps, which stand here in the order they run.
+struct InsertCall {
+    gs_index *ix; gs_ctx *c; uint64_t n;
+    const InsertEnv env;
+    const uint32_t M, ML, maxdeg, efc, B, ef_lds;
+    const size_t lds;                           // of k_hnsw_plan's sorted-array search
+    const bool cnt16;
+    uint64_t first = 0, slab_ld = 0;
+    std::vector<uint8_t> lv; std::vector<int32_t> up;    // levels and upper-layer slots of the new points
+    bool appended = false;                      // their ids are in the index's tables: the destructor takes back those that did not make it
     uint32_t ext_cap = 0;
-    if (ix->prm.extend_candidates && efc <= maxdeg) {
-        const uint64_t reach = std::min<uint64_t>(ix->n + n, (uint64_t)efc * maxdeg) + efc;
-        ext_cap = 2; while (ext_cap < reach) ext_cap <<= 1;
-        if ((rc = ix->ext_keys.ensure((size_t)8 * ext_cap * B))) return rc;
-    }
-    if (!ix->evals_dev.p) { if ((rc = ix->evals_dev.alloc(64))) return rc; GS_HIP_CHECK(hipMemsetAsync(ix->evals_dev.p, 0, 64, c->stream)); }
-    const uint64_t nlists = ix->cap + ix->cap_upper * ML;
-    if (nlists != ix->inbox_lists) {
-        if ((rc = ix->inbox.alloc((size_t)8 * nlists * B))) return rc;
-        if ((rc = ix->inbox_cnt.alloc((size_t)4 * nlists))) return rc;
-        GS_HIP_CHECK(hipMemsetAsync(ix->inbox_cnt.p, 0, (size_t)4 * nlists, c->stream));
-        ix->inbox_lists = nlists;
-    }
     gs::GraphDev g;
-    g.deg0 = ix->deg0.as<uint32_t>(); g.nbr0 = ix->nbr0.as<uint32_t>(); g.cnt0 = ix->cnt0.as<uint32_t>();
-    g.degU = ix->degU.as<uint32_t>(); g.nbrU = ix->nbrU.as<uint32_t>(); g.cntU = ix->cntU.as<uint32_t>();
-    g.upidx = ix->upidx.as<int32_t>(); g.M = M; g.max_layer = ML; g.upper_base = ix->cap;
-    ix->n_upper = nup;
-    const gs::DistMode mode = gs::env_mode();
-    unsigned long long seg_ev0 = ix->insert_evals; double seg_den = 0; uint32_t seg_batches = 0;
-    const bool cnt16 = ix->prm.m <= 65535;
-    if (ix->pair_cache_budget == 0) {
-        const char *e = getenv("GS_PAIR_CACHE_GB");
-        if (e) ix->pair_cache_budget = (uint64_t)(atof(e) * 1e9);
-        else {
-            // default: 55 % of the device, but never more than what is FREE now minus what this index still has to allocate next to it
-            // (column store, count matrix, query scratch): other indexes and processes may hold memory already
-            size_t fr = 0, tot = 0;
-            uint64_t budget = (uint64_t)(0.55 * (double)c->hbm_bytes);
-            if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-                const uint64_t reserve = (uint64_t)ix->prm.m * ix->cap * ix->esz + ((uint64_t)8 << 30);
-                budget = std::min<uint64_t>(budget, fr > reserve ? (uint64_t)fr - reserve : 0);
-            }
-            ix->pair_cache_budget = std::max<uint64_t>(budget, 1);
-        }
-    }
-    const uint64_t slab_ld = gs::round_up(first + n, 8);
-    // batches joined together (GS_INSERT_GROUP, default 8; 1 = every batch its own join): rows [grp_b0, grp_end) hold their counts against nodes [0, grp_b0)
-    uint32_t grp_n = 8;
-    if (const char *e = getenv("GS_INSERT_GROUP")) grp_n = (uint32_t)std::max(1, std::min(12, atoi(e)));
-    uint64_t grp_b0 = 0, grp_end = 0;
-    gs::DevBuf *slab = nullptr; uint64_t slab_first = 0;      // rows of this call's points, allocated at the first dense batch
+    gs::DistMode mode = gs::MODE_AUTO;
+    unsigned long long seg_ev0 = 0; double seg_den = 0; uint32_t seg_batches = 0;      // cost-model feedback: evaluations / (points x nodes) of a segment
     bool slab_tried = false;
-    for (uint64_t b0 = first; b0 < first + n; b0 += B) {
-        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, first + n - b0);
-        const uint8_t *blv = lv.data() + (b0 - first);
-        GS_HIP_CHECK(hipMemcpyAsync(ix->blevels.p, blv, nb, hipMemcpyHostToDevice, c->stream));
+    gs::InsertRows rows;
+
+    InsertCall(gs_index *ix_, uint64_t n_)
+        : ix(ix_), c(ix_->ctx), n(n_), M(ix->prm.max_nb_conn), ML(ix->prm.max_layer), maxdeg(2 * M), efc(ix->prm.ef_construction),
+          B(std::min<uint32_t>(std::min<uint32_t>(ix->prm.insert_batch, 256u), gs::ST)), ef_lds(std::max(efc, B)), lds(gs::search_lds_bytes(ef_lds, maxdeg)),
+          cnt16(ix->prm.m <= 65535) {}
+    // an insert that fails half-way leaves ix->n behind first + n: drop the ids / ranks of the points that did not make it (every early exit comes through here)
+    ~InsertCall()
+    {
+        if (!appended) return;
+        for (uint64_t i = ix->n > first ? ix->n - first : 0; i < lv.size() && first + i < ix->pid_rank.size(); i++) ix->level_count[lv[i] <= 16 ? lv[i] : 16]--;
+        if (ix->pid_rank.size() > ix->n) ix->pid_rank.resize(ix->n);
+        if (ix->origin.size() > ix->n) ix->origin.resize(ix->n);
+    }
+
+    int prepare(const void *sigs, bool on_dev, const uint64_t *ids)
+    {
+        GS_REQUIRE(!ix->prm.keep_pruned, GS_ERR_UNSUPPORTED, "keep_pruned=true is not implemented on the device (gsearch sets false, dnasketch.rs:160)");
+        GS_REQUIRE(ix->n + n < ((uint64_t)1 << 32) - 1, GS_ERR_INVALID, "too many points");
+        GS_HIP_CHECK(hipSetDevice(c->device));
+        // levels and upper-layer slots of the new points (host: needs libm log, like the oracle)
+        lv.resize(n); up.resize(n);
+        uint64_t nup = ix->n_upper;
+        for (uint64_t i = 0; i < n; i++) { lv[i] = (uint8_t)gen_level_host(ix, ix->n + i); up[i] = lv[i] > 0 ? (int32_t)nup++ : -1; }
+        int rc = gs::index_reserve(ix, ix->n + n, nup);
+        if (rc) return rc;
+        first = ix->n;
+        gs::ids_append(ix, ids, lv.data(), n);
+        appended = true;
+        if ((rc = gs::upload_user_rows(ix, ix->data.as<uint8_t>() + first * ix->stride, sigs, n, on_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice))) return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(ix->levels.as<uint8_t>() + first, lv.data(), n, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(ix->upidx.as<int32_t>() + first, up.data(), 4 * n, hipMemcpyHostToDevice, c->stream));
+        // scratch
+        GS_REQUIRE(lds <= 160 * 1024 - 64, GS_ERR_UNSUPPORTED, "ef_construction=%u needs %zu bytes of LDS", efc, lds);
+        GS_REQUIRE(2 * (size_t)ef_lds + maxdeg + 64 <= (size_t)gs::SMAXI * gs::ST && maxdeg <= (uint32_t)gs::ST, GS_ERR_UNSUPPORTED, "ef_construction too large");
+        const uint32_t vis_words = (uint32_t)((first + n + 31) / 32);
+        if ((rc = ix->visited.ensure((size_t)4 * vis_words * std::max<uint32_t>(B, c->n_cu)))) return rc;
+        if ((rc = ix->blevels.ensure(B))) return rc;
+        if ((rc = ix->cntmat.ensure((size_t)4 * B * B))) return rc;
+        if ((rc = ix->plan_keys.ensure((size_t)8 * B * ML * maxdeg))) return rc;
+        if ((rc = ix->plan_n.ensure((size_t)4 * B * ML))) return rc;
+        if ((rc = ix->touched.ensure((size_t)4 * B * (maxdeg + (size_t)ML * M)))) return rc;
+        if ((rc = ix->ntouched.ensure(64))) return rc;
+        // extend_candidates with ef_construction <= 2M: every layer-0 selection extends W by the neighbours of its members (select_extended);
+        // one key array per point of a batch, sized for every node the extension can reach (a power of two: it is bitonic-sorted in place)
+        if (ix->prm.extend_candidates && efc <= maxdeg) {
+            const uint64_t reach = std::min<uint64_t>(ix->n + n, (uint64_t)efc * maxdeg) + efc;
+            ext_cap = 2; while (ext_cap < reach) ext_cap <<= 1;
+            if ((rc = ix->ext_keys.ensure((size_t)8 * ext_cap * B))) return rc;
+        }
+        if (!ix->evals_dev.p) { if ((rc = ix->evals_dev.alloc(64))) return rc; GS_HIP_CHECK(hipMemsetAsync(ix->evals_dev.p, 0, 64, c->stream)); }
+        const uint64_t nlists = ix->cap + ix->cap_upper * ML;
+        if (nlists != ix->inbox_lists) {
+            if ((rc = ix->inbox.alloc((size_t)8 * nlists * B))) return rc;
+            if ((rc = ix->inbox_cnt.alloc((size_t)4 * nlists))) return rc;
+            GS_HIP_CHECK(hipMemsetAsync(ix->inbox_cnt.p, 0, (size_t)4 * nlists, c->stream));
+            ix->inbox_lists = nlists;
+        }
+        g.deg0 = ix->deg0.as<uint32_t>(); g.nbr0 = ix->nbr0.as<uint32_t>(); g.cnt0 = ix->cnt0.as<uint32_t>();
+        g.degU = ix->degU.as<uint32_t>(); g.nbrU = ix->nbrU.as<uint32_t>(); g.cntU = ix->cntU.as<uint32_t>();
+        g.upidx = ix->upidx.as<int32_t>(); g.M = M; g.max_layer = ML; g.upper_base = ix->cap;
+        ix->n_upper = nup;
+        mode = gs::env_mode();
+        seg_ev0 = ix->insert_evals;
+        slab_ld = gs::round_up(first + n, 8);
+        rows.start(first, n, B, env.group);
+        ix->call_slab = nullptr;                // (an earlier call's slab stays in the cache; it is not this call's)
+        return GS_OK;
+    }
+
+    // what the dense pair cache may take, settled at the first insert of the index (drop_pair_cache leaves 1: the cache stays off)
+    void pair_cache_budget()
+    {
+        if (ix->pair_cache_budget != 0) return;
+        if (env.pair_cache_gb) { ix->pair_cache_budget = (uint64_t)(atof(env.pair_cache_gb) * 1e9); return; }
+        // default: 55 % of the device, but never more than what is FREE now minus what this index still has to allocate next to it
+        // (column store, count matrix, query scratch): other indexes and processes may hold memory already
+        size_t fr = 0, tot = 0;
+        uint64_t budget = (uint64_t)(0.55 * (double)c->hbm_bytes);
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
+            const uint64_t reserve = (uint64_t)ix->prm.m * ix->cap * ix->esz + ((uint64_t)8 << 30);
+            budget = std::min<uint64_t>(budget, fr > reserve ? (uint64_t)fr - reserve : 0);
+        }
+        ix->pair_cache_budget = std::max<uint64_t>(budget, 1);
+    }
+
+    // the intra-batch counts, the level / plan buffers of batch [b0, b0 + nb)
+    int start_batch(uint64_t b0, uint32_t nb)
+    {
+        GS_HIP_CHECK(hipMemcpyAsync(ix->blevels.p, lv.data() + (b0 - first), nb, hipMemcpyHostToDevice, c->stream));
         GS_HIP_CHECK(hipMemsetAsync(ix->plan_n.p, 0, (size_t)4 * nb * ML, c->stream));
         GS_HIP_CHECK(hipMemsetAsync(ix->ntouched.p, 0, 4, c->stream));
-        const uint8_t *rows = ix->data.as<uint8_t>() + b0 * ix->stride;
-        if (nb > 1) { if ((rc = gs::hamming_qxc_strided(c, ix->ikind, ix->prm.m, rows, nb, ix->stride, rows, nb, ix->stride, nullptr, ix->cntmat.as<uint32_t>(), nullptr, nb))) return rc; }
-        gs::IndexDev d = gs::index_dev(ix);
-        d.n = b0; d.entry = ix->entry; d.top = ix->top;                  // the graph frozen at batch start
-        const uint32_t vw = (uint32_t)((b0 + 31) / 32);
-        // feedback for the cost model: every 8 batches measure which fraction of the graph an insertion evaluates
-        if (mode == gs::MODE_AUTO && b0 >= 4096 && (ix->insert_frac < 0 ? seg_batches >= 2 : seg_batches >= 32)) {
-            unsigned long long ev = 0;
-            GS_HIP_CHECK(hipMemcpyAsync(&ev, ix->evals_dev.p, 8, hipMemcpyDeviceToHost, c->stream));
-            GS_HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (seg_den > 0) ix->insert_frac = (double)(ev - seg_ev0) / seg_den;
-            seg_ev0 = ev; seg_den = 0; seg_batches = 0;
+        const uint8_t *qrows = ix->data.as<uint8_t>() + b0 * ix->stride;
+        if (nb > 1) return gs::hamming_qxc_strided(c, ix->ikind, ix->prm.m, qrows, nb, ix->stride, qrows, nb, ix->stride, nullptr, ix->cntmat.as<uint32_t>(), nullptr, nb);
+        return GS_OK;
+    }
+
+    // feedback for the cost model: which fraction of the graph an insertion evaluates, read back after 2 batches while nothing is known, then every 32
+    int feedback(uint64_t b0)
+    {
+        if (!(mode == gs::MODE_AUTO && b0 >= 4096 && (ix->insert_frac < 0 ? seg_batches >= 2 : seg_batches >= 32))) return GS_OK;
+        unsigned long long ev = 0;
+        GS_HIP_CHECK(hipMemcpyAsync(&ev, ix->evals_dev.p, 8, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (seg_den > 0) ix->insert_frac = (double)(ev - seg_ev0) / seg_den;
+        seg_ev0 = ev; seg_den = 0; seg_batches = 0;
+        return GS_OK;
+    }
+    bool goes_dense(uint64_t b0, uint32_t nb) const
+    {
+        return (mode == gs::MODE_DENSE && b0 > 0) || (mode == gs::MODE_AUTO && b0 >= 4096 && nb >= 64 && ix->insert_frac >= 0 && gs::dense_pays(ix, ix->insert_frac, nb));
+    }
+    void counted(uint64_t b0, uint32_t nb) { if (b0 >= 4096) { seg_den += (double)nb * (double)b0; seg_batches++; } }
+
+    // One all-pairs tile pass over the nodes [0, b0) - inserted before the first dense batch, they have no count rows of their own - into `buf`:
+    // b0 rows of round_up(b0, 8) counts. GS_OK with buf.p == nullptr: the device had no room for them.
+    int early_rows(uint64_t b0, gs::DevBuf &buf)
+    {
+        const uint64_t eld = gs::round_up(b0, 8);
+        if (buf.alloc(b0 * eld * 2) != GS_OK) return GS_OK;
+        return gs::hamming_qxc_strided(c, ix->ikind, ix->prm.m, ix->data.p, b0, ix->stride, ix->data.p, b0, ix->stride, nullptr, nullptr, buf.as<uint16_t>(), eld);
+    }
+
+    // Once per call, at its first dense batch: the slab that keeps the count rows of this call's points as the dense pair cache. (The caller has run
+    // ensure_cols BEFORE this: it may have to evict the cache to find room, and must not do so between here and the first use of the slab.)
+    int take_slab(uint64_t b0)
+    {
+        if (slab_tried) return GS_OK;
+        slab_tried = true;
+        const uint64_t need = (first + n - b0) * slab_ld * 2;
+        // a slab is only taken while the device keeps room for the next growth step of the index itself: a new signature block
+        // next to the old one (x1.5) and the column copy that follows it, ~2x the signatures held now, + 16 GB of working space
+        bool room = true;
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) == hipSuccess) room = (uint64_t)fr >= need + 2 * (uint64_t)ix->stride * ix->cap + ((uint64_t)16 << 30);
+        if (room && ix->pair_cache_bytes + need <= ix->pair_cache_budget) {
+            auto slab = std::make_unique<gs::DevBuf>();
+            if (slab->alloc(need) == GS_OK) {
+                ix->call_slab = slab.get(); ix->slabs.push_back(std::move(slab));
+                ix->pair_cache_bytes += need; rows.slab_taken(b0);
+            }
         }
-        const bool dense = (mode == gs::MODE_DENSE && b0 > 0) || (mode == gs::MODE_AUTO && b0 >= 4096 && nb >= 64 && ix->insert_frac >= 0 && gs::dense_pays(ix, ix->insert_frac, nb));
-        const uint16_t *matp = nullptr; uint64_t mat_ld = 0;
-        if (dense && cnt16) {
-            // the column copy is (re)allocated here, BEFORE a slab is taken or used: ensure_cols may have to evict the pair cache to find
-            // room, and a slab pointer held across that would dangle
-            if (gs::use_join(ix) && (rc = gs::ensure_cols(ix, b0))) return rc;
-            if (slab && ix->slabs.empty()) slab = nullptr;           // the cache was given back (drop_pair_cache): rows go to ix->mat from here on
-            if (!slab_tried) {
-                slab_tried = true;
-                const uint64_t need = (first + n - b0) * slab_ld * 2;
-                // a slab is only taken while the device keeps room for the next growth step of the index itself: a new signature block
-                // next to the old one (x1.5) and the column copy that follows it, ~2x the signatures held now, + 16 GB of working space
-                bool room = true;
-                {
-                    size_t fr = 0, tot = 0;
-                    if (hipMemGetInfo(&fr, &tot) == hipSuccess) room = (uint64_t)fr >= need + 2 * (uint64_t)ix->stride * ix->cap + ((uint64_t)16 << 30);
-                }
-                if (room && ix->pair_cache_bytes + need <= ix->pair_cache_budget) {
-                    slab = new gs::DevBuf();
-                    if (slab->alloc(need) != GS_OK) { delete slab; slab = nullptr; }
-                    else { ix->slabs.push_back(slab); ix->pair_cache_bytes += need; slab_first = b0; }
-                }
-                // the nodes inserted before the first cached batch (the first 4096 in auto mode) have no rows of their own: a pair of two
-                // of them would send the selection heuristic back to streaming 2M signature rows per candidate - 5 % of the candidates,
-                // most of its time. One all-pairs tile pass (b0^2 counts, 32 MB at 4096) closes the hole.
-                if (slab && !ix->early_cached && b0 > 0 && b0 <= 32768) {
-                    const uint64_t eld = gs::round_up(b0, 8), ebytes = b0 * eld * 2;
-                    gs::DevBuf *early = new gs::DevBuf();
-                    if (ix->pair_cache_bytes + ebytes <= ix->pair_cache_budget && early->alloc(ebytes) == GS_OK) {
-                        if ((rc = gs::hamming_qxc_strided(c, ix->ikind, ix->prm.m, ix->data.p, b0, ix->stride, ix->data.p, b0, ix->stride, nullptr, nullptr, early->as<uint16_t>(), eld))) { delete early; return rc; }
-                        hipLaunchKernelGGL(gs::k_set_rowptr, dim3((uint32_t)((b0 + 255) / 256)), dim3(256), 0, c->stream, early->as<uint16_t>(), eld, b0, ix->rowptr.as<uint64_t>());
-                        GS_HIP_CHECK(hipGetLastError());
-                        ix->slabs.push_back(early); ix->pair_cache_bytes += ebytes; ix->early_cached = true;
-                    } else delete early;
-                }
-            }
-            // sparse pair rows (round 5): allocated here, at the first dense batch of the index (they cost sp_L x 6 bytes per node of capacity)
-            if (!ix->sp_tried) {
-                ix->sp_tried = true;
-                const char *eo = getenv("GS_SPARSE_ROWS"), *el = getenv("GS_SPARSE_L"), *ea = getenv("GS_SPARSE_ARENA_GB"), *eb = getenv("GS_SPARSE_BITMAP_GB");
-                // what the lists and bitmaps may take: what the device keeps free next to the signatures and their column copy AT THE DECLARED CAPACITY
-                // (hnsw_params.capacity: 1.5 M in gsearch) and 40 GB of everything else (adjacency, count matrices, join scratch, the caller's own buffers).
-                // List length: up to 8192 entries - a level of chance matches must fit whole -, less when even half-full lists would not fit
-                const uint64_t capd = std::max<uint64_t>(ix->prm.capacity, ix->cap);
-                const uint64_t fixed = 2 * (uint64_t)ix->stride * capd + ((uint64_t)40 << 30);
-                uint64_t room = c->hbm_bytes > fixed ? c->hbm_bytes - fixed : 0;
-                if (ea) room = (uint64_t)(atof(ea) * 1e9);
-                room = std::min<uint64_t>(room, (uint64_t)120 << 30);                       // (32-bit offsets in 32-byte units reach 128 GB)
-                const uint32_t autoL = (uint32_t)std::max<uint64_t>(2048, std::min<uint64_t>(8192, room / (3 * capd) / 512 * 512));
-                ix->sp_L = (eo && !atoi(eo)) ? 0u : (uint32_t)std::max(64, std::min(32768, el ? atoi(el) : (int)autoL));
-                if (ix->sp_L && !ea && room < ((uint64_t)2 << 30)) ix->sp_L = 0;
-                // (GS_SPARSE_ARENA_CHUNK_MB: the mapping step, 1 GB; tests make it small to fill an arena of a few MB and watch it grow in place)
-                const size_t vm_chunk = getenv("GS_SPARSE_ARENA_CHUNK_MB") ? (size_t)(atof(getenv("GS_SPARSE_ARENA_CHUNK_MB")) * 1048576.0) : ((size_t)1 << 30);
-                if (ix->sp_L) {
-                    if (!ix->sp_vm.reserve(c->device, std::max<uint64_t>(room, 65536), vm_chunk) || ix->sp_off.alloc((size_t)4 * ix->cap) != GS_OK || ix->sp_meta.alloc((size_t)8 * ix->cap) != GS_OK ||
-                        ix->sp_bm.alloc((size_t)8 * ix->cap) != GS_OK || ix->sp_arena.alloc(sizeof(gs::SpArena)) != GS_OK) {
-                        (void)hipGetLastError(); ix->sp_vm.release(); ix->sp_off.release(); ix->sp_meta.release(); ix->sp_bm.release(); ix->sp_arena.release(); ix->sp_L = 0;
-                    } else {
-                        GS_HIP_CHECK(hipMemsetAsync(ix->sp_off.p, 0, (size_t)4 * ix->cap, c->stream));
-                        GS_HIP_CHECK(hipMemsetAsync(ix->sp_meta.p, 0, (size_t)8 * ix->cap, c->stream));
-                        GS_HIP_CHECK(hipMemsetAsync(ix->sp_bm.p, 0, (size_t)8 * ix->cap, c->stream));
-                        gs::SpArena h{};
-                        h.base = (unsigned long long)ix->sp_vm.va;
-                        h.bm_limit = (unsigned long long)((eb ? atof(eb) : 24.0) * 1e9);
-                        if ((double)h.bm_limit > 0.6 * (double)room) h.bm_limit = (unsigned long long)(0.6 * (double)room);
-                        GS_HIP_CHECK(hipMemcpyAsync(ix->sp_arena.p, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-                        GS_HIP_CHECK(hipStreamSynchronize(c->stream));                  // (h is a local)
-                        ix->sp_reserved = 0;
-                    }
-                }
-                // the nodes inserted before this batch have no count rows to take their lists from: one all-pairs tile pass over them (like the dense
-                // cache's early rows, which it reuses when they exist), lists written, matrix given back
-                if (ix->sp_L && b0 > 0 && b0 <= 32768) {
-                    const uint64_t eld = gs::round_up(b0, 8);
-                    gs::DevBuf tmp; const uint16_t *em = nullptr;
-                    if (ix->early_cached && !ix->slabs.empty()) em = ix->slabs.back()->as<uint16_t>();      // (pushed just above, this call)
-                    else if (tmp.alloc(b0 * eld * 2) == GS_OK) {
-                        if ((rc = gs::hamming_qxc_strided(c, ix->ikind, ix->prm.m, ix->data.p, b0, ix->stride, ix->data.p, b0, ix->stride, nullptr, nullptr, tmp.as<uint16_t>(), eld))) return rc;
-                        em = tmp.as<uint16_t>();
-                    } else (void)hipGetLastError();
-                    if (em) {
-                        if ((rc = gs::sparse_fill(ix, em, eld, 0, (uint32_t)b0))) return rc;
-                        GS_HIP_CHECK(hipStreamSynchronize(c->stream));          // tmp goes out of scope
-                    }
-                }
-                d = gs::index_dev(ix); d.n = b0; d.entry = ix->entry; d.top = ix->top;
-            }
-            // where this batch's count rows live: the call's slab of the dense pair cache (kept), or a rolling buffer of one GROUP of batches (ix->mat;
-            // round 5: without a slab the batches were joined one by one - the columns streamed once per batch instead of once per group)
-            const bool can_group = grp_n > 1 && gs::use_join(ix);
-            uint16_t *out16; mat_ld = slab_ld;
-            if (slab) out16 = slab->as<uint16_t>() + (b0 - slab_first) * slab_ld;
-            else {
-                const size_t rows_wanted = can_group ? (size_t)grp_n * B : (size_t)B;
-                if (!(b0 >= grp_b0 && b0 < grp_end)) {                                    // a new group (or single batch) starts: the buffer may grow now
-                    // (with 25 % of headroom, up to the declared capacity: the row length follows the index, and a buffer that is a few rows short at every
-                    // insert call costs a multi-GB hipFree + hipMalloc per call - 183 of them in a 1.5 M-genome build fed 8192 genomes at a time)
-                    const size_t want = 2 * rows_wanted * slab_ld;
-                    if (ix->mat.bytes < want) {
-                        const size_t at_cap = 2 * rows_wanted * gs::round_up(std::max<uint64_t>(ix->prm.capacity, ix->cap), 8);
-                        const size_t ask = std::max(want, std::min(want + want / 4, at_cap));
-                        rc = alloc_or_evict(ix, ix->mat, ask);
-                        if (rc && ask > want) { (void)hipGetLastError(); rc = alloc_or_evict(ix, ix->mat, want); }
-                        if (rc) return rc;
-                    }
-                }
-                out16 = (b0 >= grp_b0 && b0 < grp_end) ? ix->mat.as<uint16_t>() + (b0 - grp_b0) * slab_ld : ix->mat.as<uint16_t>();
-            }
-            if (can_group && b0 >= grp_b0 && b0 < grp_end) {
-                // inside a group: this batch's counts against the nodes of the group's start are in its rows already; the nodes the earlier
-                // batches of the group added since (at most (grp_n - 1) * B of them) take a small join of their own (their columns only)
-                if (b0 > grp_b0 && (rc = gs::dense_counts_range(ix, rows, nb, grp_b0, b0 - grp_b0, out16, mat_ld))) return rc;
-            } else if (can_group) {
-                // a group of batches: ONE join of all their points against the nodes present now - the columns (21.6 GB at 300 k nodes) are
-                // streamed once per group instead of once per batch
-                grp_b0 = b0; grp_end = std::min<uint64_t>(first + n, b0 + (uint64_t)grp_n * B);
-                if ((rc = gs::dense_counts(ix, rows, grp_end - grp_b0, b0, out16, mat_ld))) return rc;
+        // the nodes inserted before the first cached batch (the first 4096 in auto mode) have no rows of their own: a pair of two
+        // of them would send the selection heuristic back to streaming 2M signature rows per candidate - 5 % of the candidates,
+        // most of its time. The early rows (b0^2 counts, 32 MB at 4096) close the hole; they count against the budget like a slab.
+        const uint64_t eld = gs::round_up(b0, 8), ebytes = b0 * eld * 2;
+        if (!ix->call_slab || ix->early_rows || b0 == 0 || b0 > 32768 || ix->pair_cache_bytes + ebytes > ix->pair_cache_budget) return GS_OK;
+        auto early = std::make_unique<gs::DevBuf>();
+        int rc = early_rows(b0, *early);
+        if (rc || !early->p) return rc;
+        hipLaunchKernelGGL(gs::k_set_rowptr, dim3((uint32_t)((b0 + 255) / 256)), dim3(256), 0, c->stream, early->as<uint16_t>(), eld, b0, ix->rowptr.as<uint64_t>());
+        GS_HIP_CHECK(hipGetLastError());
+        ix->early_rows = early.get(); ix->slabs.push_back(std::move(early));
+        ix->pair_cache_bytes += ebytes;
+        return GS_OK;
+    }
+
+    // Once per index, at its first dense batch: the sparse pair rows (round 5; they cost sp_L x 6 bytes per node of capacity), and the lists of the
+    // nodes [0, b0), which have no count rows to take them from
+    int sparse_rows_setup(uint64_t b0)
+    {
+        if (ix->sp_tried) return GS_OK;
+        ix->sp_tried = true;
+        // what the lists and bitmaps may take: what the device keeps free next to the signatures and their column copy AT THE DECLARED CAPACITY
+        // (hnsw_params.capacity: 1.5 M in gsearch) and 40 GB of everything else (adjacency, count matrices, join scratch, the caller's own buffers).
+        // List length: up to 8192 entries - a level of chance matches must fit whole -, less when even half-full lists would not fit
+        const uint64_t capd = std::max<uint64_t>(ix->prm.capacity, ix->cap);
+        const uint64_t fixed = 2 * (uint64_t)ix->stride * capd + ((uint64_t)40 << 30);
+        uint64_t room = c->hbm_bytes > fixed ? c->hbm_bytes - fixed : 0;
+        if (env.sparse_arena_gb) room = (uint64_t)(atof(env.sparse_arena_gb) * 1e9);
+        room = std::min<uint64_t>(room, (uint64_t)120 << 30);                       // (32-bit offsets in 32-byte units reach 128 GB)
+        const uint32_t autoL = (uint32_t)std::max<uint64_t>(2048, std::min<uint64_t>(8192, room / (3 * capd) / 512 * 512));
+        ix->sp_L = (env.sparse_rows && !atoi(env.sparse_rows)) ? 0u : (uint32_t)std::max(64, std::min(32768, env.sparse_l ? atoi(env.sparse_l) : (int)autoL));
+        if (ix->sp_L && !env.sparse_arena_gb && room < ((uint64_t)2 << 30)) ix->sp_L = 0;
+        // (GS_SPARSE_ARENA_CHUNK_MB: the mapping step, 1 GB; tests make it small to fill an arena of a few MB and watch it grow in place)
+        const size_t vm_chunk = env.sparse_chunk_mb ? (size_t)(atof(env.sparse_chunk_mb) * 1048576.0) : ((size_t)1 << 30);
+        if (ix->sp_L) {
+            if (!ix->sp_vm.reserve(c->device, std::max<uint64_t>(room, 65536), vm_chunk) || ix->sp_off.alloc((size_t)4 * ix->cap) != GS_OK || ix->sp_meta.alloc((size_t)8 * ix->cap) != GS_OK ||
+                ix->sp_bm.alloc((size_t)8 * ix->cap) != GS_OK || ix->sp_arena.alloc(sizeof(gs::SpArena)) != GS_OK) {
+                (void)hipGetLastError(); ix->sp_vm.release(); ix->sp_off.release(); ix->sp_meta.release(); ix->sp_bm.release(); ix->sp_arena.release(); ix->sp_L = 0;
             } else {
-                grp_b0 = grp_end = 0;
-                if ((rc = gs::dense_counts(ix, rows, nb, b0, out16, mat_ld))) return rc;
+                GS_HIP_CHECK(hipMemsetAsync(ix->sp_off.p, 0, (size_t)4 * ix->cap, c->stream));
+                GS_HIP_CHECK(hipMemsetAsync(ix->sp_meta.p, 0, (size_t)8 * ix->cap, c->stream));
+                GS_HIP_CHECK(hipMemsetAsync(ix->sp_bm.p, 0, (size_t)8 * ix->cap, c->stream));
+                gs::SpArena h{};
+                h.base = (unsigned long long)ix->sp_vm.va;
+                h.bm_limit = (unsigned long long)((env.sparse_bitmap_gb ? atof(env.sparse_bitmap_gb) : 24.0) * 1e9);
+                if ((double)h.bm_limit > 0.6 * (double)room) h.bm_limit = (unsigned long long)(0.6 * (double)room);
+                GS_HIP_CHECK(hipMemcpyAsync(ix->sp_arena.p, &h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+                GS_HIP_CHECK(hipStreamSynchronize(c->stream));                  // (h is a local)
+                ix->sp_reserved = 0;
             }
-            if (slab && ix->slabs.empty()) {                         // evicted under our feet after all: this batch's counts again, into ix->mat
-                slab = nullptr; grp_b0 = grp_end = 0;
-                if (ix->mat.bytes < (size_t)2 * B * slab_ld && (rc = ix->mat.alloc((size_t)2 * B * slab_ld))) return rc;
-                out16 = ix->mat.as<uint16_t>();
-                if ((rc = gs::dense_counts(ix, rows, nb, b0, out16, mat_ld))) return rc;
-            }
-            // the mates' columns from the tile matrix; with a slab the rows stay where they are as the dense pair cache (rowptr)
-            hipLaunchKernelGGL(gs::k_cache_rows, dim3(nb), dim3(256), 0, c->stream, out16, mat_ld, b0, nb, ix->cntmat.as<uint32_t>(), slab ? ix->rowptr.as<uint64_t>() : (uint64_t *)nullptr);
-            GS_HIP_CHECK(hipGetLastError());
-            if ((rc = gs::sparse_fill(ix, out16, mat_ld, b0, nb))) return rc;
-            matp = out16;
         }
-        if (b0 >= 4096) { seg_den += (double)nb * (double)b0; seg_batches++; }
-        // pre-pass: the layer-0 search of the batch's level-0 points through the dense traversal kernel (accepted-key log -> W)
+        if (!ix->sp_L || b0 == 0 || b0 > 32768) return GS_OK;
+        // the lists of the nodes older than this batch come from their all-pairs rows: the dense cache's when it has them, else a temporary given back at once
+        int rc;
+        gs::DevBuf tmp;
+        if (!ix->early_rows) { if ((rc = early_rows(b0, tmp))) return rc; if (!tmp.p) (void)hipGetLastError(); }
+        const gs::DevBuf &em = ix->early_rows ? *ix->early_rows : tmp;
+        if (!em.p) return GS_OK;
+        if ((rc = gs::sparse_fill(ix, em.as<uint16_t>(), gs::round_up(b0, 8), 0, (uint32_t)b0))) return rc;
+        GS_HIP_CHECK(hipStreamSynchronize(c->stream));          // tmp goes out of scope
+        return GS_OK;
+    }
+
+    // the rolling buffer (ix->mat) holds `nrows` rows from here on. It grows with 25 % of headroom, up to the declared capacity: the row length follows
+    // the index, and a buffer that is a few rows short at every insert call costs a multi-GB hipFree + hipMalloc per call - 183 of them in a 1.5 M-genome
+    // build fed 8192 genomes at a time; when the larger request fails, the exact size
+    int grow_rolling(uint64_t nrows)
+    {
+        const size_t want = 2 * (size_t)nrows * slab_ld;
+        if (ix->mat.bytes >= want) return GS_OK;
+        const size_t at_cap = 2 * (size_t)nrows * gs::round_up(std::max<uint64_t>(ix->prm.capacity, ix->cap), 8);
+        const size_t ask = std::max(want, std::min(want + want / 4, at_cap));
+        int rc = gs::alloc_or_evict(ix, ix->mat, ask);
+        if (rc && ask > want) { (void)hipGetLastError(); rc = gs::alloc_or_evict(ix, ix->mat, want); }
+        return rc;
+    }
+
+    // The counts of batch [b0, b0 + nb) against every node present at its start; leaves where they are in *matp (leading dimension *mat_ld). They live in
+    // the call's slab (kept: the dense pair cache) or in the rolling buffer of one group of batches (round 5: without a slab the batches were joined one
+    // by one - the columns streamed once per batch instead of once per group); gs_insert_rows.hpp says where, and which join fills them.
+    int batch_counts(uint64_t b0, uint32_t nb, const uint16_t **matp, uint64_t *mat_ld)
+    {
+        int rc;
+        const uint8_t *qrows = ix->data.as<uint8_t>() + b0 * ix->stride;
+        const bool had_slab = ix->call_slab != nullptr;
+        const gs::RowPlace pl = rows.next(b0, nb, had_slab, env.group > 1 && gs::use_join(ix));
+        if (pl.grow_rows && (rc = grow_rolling(pl.grow_rows))) return rc;
+        uint16_t *out16 = (had_slab ? ix->call_slab : &ix->mat)->as<uint16_t>() + pl.row_off * slab_ld;
+        if (pl.join == gs::JOIN_RANGE) {
+            // this batch's counts against the nodes of the group's start are in its rows already; the nodes the earlier batches of the group added
+            // since (at most (group - 1) * B of them) take a small join of their own (their columns only)
+            if (pl.nn && (rc = gs::dense_counts_range(ix, qrows, nb, pl.node0, pl.nn, out16, slab_ld))) return rc;
+        } else {
+            // JOIN_GROUP: ONE join of all the group's points against the nodes present now - the columns (21.6 GB at 300 k nodes) are streamed once
+            // per group instead of once per batch; JOIN_ALONE: the batch's own
+            if ((rc = gs::dense_counts(ix, qrows, pl.nq, b0, out16, slab_ld))) return rc;
+        }
+        if (had_slab && !ix->call_slab) {                           // evicted under our feet after all: this batch's counts again, into ix->mat
+            rows.reset();
+            if (ix->mat.bytes < (size_t)2 * B * slab_ld && (rc = ix->mat.alloc((size_t)2 * B * slab_ld))) return rc;
+            out16 = ix->mat.as<uint16_t>();
+            if ((rc = gs::dense_counts(ix, qrows, nb, b0, out16, slab_ld))) return rc;
+        }
+        // the mates' columns from the tile matrix; with a slab the rows stay where they are as the dense pair cache (rowptr)
+        hipLaunchKernelGGL(gs::k_cache_rows, dim3(nb), dim3(256), 0, c->stream, out16, slab_ld, b0, nb, ix->cntmat.as<uint32_t>(), ix->call_slab ? ix->rowptr.as<uint64_t>() : (uint64_t *)nullptr);
+        GS_HIP_CHECK(hipGetLastError());
+        if ((rc = gs::sparse_fill(ix, out16, slab_ld, b0, nb))) return rc;
+        *matp = out16; *mat_ld = slab_ld;
+        return GS_OK;
+    }
+
+    struct PlanLaunch {         // what the launches of k_hnsw_plan for one batch share
+        gs::IndexDev d; uint64_t b0; uint32_t nb; const uint16_t *matp; uint64_t mat_ld; uint32_t vw; int vis_in_lds; size_t lds_plan;
         const uint64_t *w0k = nullptr, *w0e = nullptr; const uint32_t *w0n = nullptr;
-        const bool pp = matp && gs::prepass_ok(ix, efc);
+    };
+    // phase 0: the whole plan in one launch; with the pre-pass, 1 = the layers above 0 and 2 = the selection on the W the pre-pass worked out
+    int launch_plan(const PlanLaunch &a, int phase)
+    {
+        auto kern = gs::k_hnsw_plan<GS_KIND_F32>;
+        if (ix->ikind == GS_KIND_U32) kern = gs::k_hnsw_plan<GS_KIND_U32>; else if (ix->ikind != GS_KIND_F32) kern = gs::k_hnsw_plan<GS_KIND_U64>;
+        GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_plan));
+        hipLaunchKernelGGL(kern, dim3(a.nb), dim3(gs::ST), a.lds_plan, c->stream, a.d, a.b0, a.nb, ix->blevels.as<uint8_t>(), ix->cntmat.as<uint32_t>(), a.matp, a.mat_ld, efc, ef_lds,
+                           ix->prm.extend_candidates, ix->visited.as<uint32_t>(), a.vw, a.vis_in_lds, ix->plan_keys.as<uint64_t>(), ix->plan_n.as<uint32_t>(),
+                           ix->evals_dev.as<unsigned long long>(), a.w0k, a.w0n, a.w0e, phase, ix->ep0.as<uint32_t>(),
+                           ext_cap ? ix->ext_keys.as<uint64_t>() : (uint64_t *)nullptr, ext_cap);
+        return GS_OK;
+    }
+
+    // neighbour selection of the batch on the graph frozen at its start (with the pre-pass where it applies), then the links; the batch joins the index
+    int plan_and_link(uint64_t b0, uint32_t nb, const uint16_t *matp, uint64_t mat_ld)
+    {
+        int rc;
+        PlanLaunch a{gs::index_dev(ix), b0, nb, matp, mat_ld, (uint32_t)((b0 + 31) / 32), 0, 0};
+        a.d.n = b0; a.d.entry = ix->entry; a.d.top = ix->top;           // the graph frozen at batch start
+        // pre-pass: the layer-0 search of the batch's level-0 points through the dense traversal kernel (accepted-key log -> W)
+        gs::PrepassGeom pg;
+        const bool pp = matp && env.prepass && gs::prepass_ok(ix, nb, efc, &pg);
         if (pp) {
             if ((rc = ix->ep0.ensure((size_t)4 * B))) return rc;
             GS_HIP_CHECK(hipMemsetAsync(ix->ep0.p, 0xFF, (size_t)4 * nb, c->stream));
         }
-        const size_t lds_vis = ((lds + 15) & ~(size_t)15) + (size_t)4 * vw;
-        const int vis_in_lds = lds_vis <= 160 * 1024 - 1024 && !getenv("GS_PLAN_VIS_GLOBAL");
-        const size_t lds_plan = vis_in_lds ? lds_vis : lds;
+        const size_t lds_vis = ((lds + 15) & ~(size_t)15) + (size_t)4 * a.vw;
+        a.vis_in_lds = lds_vis <= 160 * 1024 - 1024 && !env.plan_vis_global;
+        a.lds_plan = a.vis_in_lds ? lds_vis : lds;
         {
             gs::ProfScope ps(c, gs::FAM_INSERT);
-#define GS_LAUNCH_PLAN(K)                                                                                                  \
-    do {                                                                                                                   \
-        auto kern = gs::k_hnsw_plan<K>;                                                                                    \
-        GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_plan));  \
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(gs::ST), lds_plan, c->stream, d, b0, nb, ix->blevels.as<uint8_t>(), ix->cntmat.as<uint32_t>(), matp, mat_ld, efc, ef_lds, \
-                           ix->prm.extend_candidates, ix->visited.as<uint32_t>(), vw, vis_in_lds, ix->plan_keys.as<uint64_t>(), ix->plan_n.as<uint32_t>(), \
-                           ix->evals_dev.as<unsigned long long>(), w0k, w0n, w0e, phase, ix->ep0.as<uint32_t>(),           \
-                           ext_cap ? ix->ext_keys.as<uint64_t>() : (uint64_t *)nullptr, ext_cap);                          \
-    } while (0)
-#define GS_LAUNCH_PLAN_KIND()                                                                                              \
-    do { if (ix->ikind == GS_KIND_F32) GS_LAUNCH_PLAN(GS_KIND_F32); else if (ix->ikind == GS_KIND_U32) GS_LAUNCH_PLAN(GS_KIND_U32); else GS_LAUNCH_PLAN(GS_KIND_U64); } while (0)
-            int phase = 0;
-            if (!pp) GS_LAUNCH_PLAN_KIND();
+            if (!pp) { if ((rc = launch_plan(a, 0))) return rc; }
             else {
-                phase = 1; GS_LAUNCH_PLAN_KIND();                  // layers above 0 of the few points that have any
+                if ((rc = launch_plan(a, 1))) return rc;             // layers above 0 of the few points that have any
                 GS_HIP_CHECK(hipGetLastError());
-                if ((rc = gs::plan_prepass(ix, nb, efc, matp, mat_ld, &w0k, &w0n, &w0e))) return rc;
-                phase = 2; GS_LAUNCH_PLAN_KIND();                  // selection on the W the pre-pass worked out
+                if ((rc = gs::plan_prepass(ix, pg, nb, efc, matp, mat_ld, &a.w0k, &a.w0n, &a.w0e))) return rc;
+                if ((rc = launch_plan(a, 2))) return rc;             // selection on the W the pre-pass worked out
             }
-#undef GS_LAUNCH_PLAN_KIND
-#undef GS_LAUNCH_PLAN
         }
         GS_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(gs::k_link_own, dim3(nb), dim3(256), 0, c->stream, g, b0, nb, ix->blevels.as<uint8_t>(), ix->plan_keys.as<uint64_t>(), ix->plan_n.as<uint32_t>());
@@ -3511,15 +3576,21 @@ static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n
                            ix->inbox.as<uint64_t>(), ix->touched.as<uint32_t>(), ix->ntouched.as<uint32_t>());
         GS_HIP_CHECK(hipGetLastError());
         // entry point: the first id of the highest new level (SPEC 5)
+        const uint8_t *blv = lv.data() + (b0 - first);
         for (uint32_t i = 0; i < nb; i++) if ((int)blv[i] > ix->top) { ix->top = blv[i]; ix->entry = (int64_t)(b0 + i); }
         ix->n = b0 + nb;
         // the level / batch buffers are reused by the next batch: the stream orders the copies after the kernels
+        return GS_OK;
     }
-    unsigned long long ev[3] = {0, 0, 0};
-    GS_HIP_CHECK(hipMemcpyAsync(ev, ix->evals_dev.p, 24, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    ix->insert_evals = ev[0];
-    if (getenv("GS_SPARSE_VERBOSE")) {
+
+    // the counters of the call (one 24-byte copy and a synchronisation), and the GS_SPARSE_VERBOSE line
+    int finish()
+    {
+        unsigned long long ev[3] = {0, 0, 0};
+        GS_HIP_CHECK(hipMemcpyAsync(ev, ix->evals_dev.p, 24, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        ix->insert_evals = ev[0];
+        if (!env.sparse_verbose) return GS_OK;
         uint64_t with = 0, full = 0;
         if (ix->sp_L && ix->sp_meta.p) {
             std::vector<uint64_t> mt(ix->n);
@@ -3531,8 +3602,39 @@ static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n
         fprintf(stderr, "[GS_SPARSE] n %llu L %u: nodes with a list %llu (at capacity %llu, turned away %llu), dense-cache bytes %llu; selection chunks through the lists %llu, candidates checked by streaming rows %llu (both since the index was made); arena %.4f GB used of %.4f mapped (%.2f reserved), level bitmaps %llu in %.2f GB, turned away %llu\n",
                 (unsigned long long)ix->n, ix->sp_L, (unsigned long long)with, (unsigned long long)full, ar.lists_noroom, (unsigned long long)ix->pair_cache_bytes, ev[2], ev[1],
                 std::min(ar.off, ar.size) / 1e9, ix->sp_vm.mapped / 1e9, ix->sp_vm.va_bytes / 1e9, ar.stored, std::min(ar.bm_bytes, ar.bm_limit) / 1e9, ar.noroom);
+        return GS_OK;
     }
-    return GS_OK;
+};
+}  // namespace
+
+static int insert_common(gs_index *ix, const void *sigs, bool on_dev, uint64_t n, const uint64_t *ids = nullptr)
+{
+    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
+    if (n == 0) return GS_OK;
+    GS_REQUIRE(sigs, GS_ERR_INVALID, "null signatures");
+    GS_CTX_LOCK(ix->ctx);
+    InsertCall call(ix, n);
+    int rc;
+    if ((rc = call.prepare(sigs, on_dev, ids))) return rc;
+    call.pair_cache_budget();
+    for (uint64_t b0 = call.first; b0 < call.first + n; b0 += call.B) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(call.B, call.first + n - b0);
+        if ((rc = call.start_batch(b0, nb))) return rc;
+        if ((rc = call.feedback(b0))) return rc;
+        const uint16_t *matp = nullptr; uint64_t mat_ld = 0;
+        if (call.goes_dense(b0, nb) && call.cnt16) {
+            // the column copy is (re)allocated here, BEFORE a slab is taken or used: ensure_cols may have to evict the pair cache to find room, and
+            // that frees every slab. (Nothing here keeps a slab's address across it any more - ix->call_slab is null after an eviction - but a slab
+            // taken first would be lost to the very next line: the order stays.)
+            if (gs::use_join(ix) && (rc = gs::ensure_cols(ix, b0))) return rc;
+            if ((rc = call.take_slab(b0))) return rc;                   // once per call
+            if ((rc = call.sparse_rows_setup(b0))) return rc;           // once per index
+            if ((rc = call.batch_counts(b0, nb, &matp, &mat_ld))) return rc;
+        }
+        call.counted(b0, nb);
+        if ((rc = call.plan_and_link(b0, nb, matp, mat_ld))) return rc;
+    }
+    return call.finish();
 }
 
 int gs_index_parallel_insert(gs_index *ix, const void *sigs, uint64_t n) { return insert_common(ix, sigs, false, n); }
