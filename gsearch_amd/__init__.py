@@ -11,3 +11,4 @@ from .api import (fastq_scan, hmh_cardinality, hmh_cardinality_dev, hmh_similari
                   read_path_list, write_hypermash_tsv)
 from .api import EmbedParams, ann, embed_knn_graph, embed_knn_graph_dev, knn_graph_stats, write_embedding_csv  # noqa: F401
 from .api import FracMinHashSketch, aai, frac_max_hash, frac_similarity_qxc, frac_similarity_qxc_dev, read_list_lines, superaai, write_superaai  # noqa: F401
+from .api import ClusterResult, hnswcore, write_cluster_csv  # noqa: F401

@@ -46,6 +46,16 @@ class KnnStatsC(C.Structure):
                 ("hub_occ", C.c_uint32 * 16), ("q_first", C.c_float * 7), ("q_last", C.c_float * 7)]
 
 
+class ClusterParamsC(C.Structure):
+    """gs_cluster_params (SPEC 10)"""
+    _fields_ = [("n_cluster", C.c_uint32), ("fraction", C.c_double), ("max_iter", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class ClusterInfoC(C.Structure):
+    """gs_cluster_info (SPEC 10)"""
+    _fields_ = [("n_core", C.c_uint64), ("iterations", C.c_uint32), ("converged", C.c_uint32), ("cost_core", C.c_uint64), ("cost_all", C.c_uint64)]
+
+
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
 
@@ -136,6 +146,10 @@ SYMBOLS = {
     "gs_index_embed": (_i, [_vp, _u32, C.c_float, C.POINTER(EmbedParamsC), _vp, _vp]),
     "gs_knn_graph_stats": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(KnnStatsC), _vp, _vp]),
     "gs_index_knn_graph_stats": (_i, [_vp, _u32, C.c_float, C.POINTER(KnnStatsC), _vp, _vp]),
+    # hnswcore (SPEC 10)
+    "gs_cluster_params_default": (ClusterParamsC, []),
+    "gs_index_nearest_of": (_i, [_vp, _vp, _u64, _vp, _vp]),
+    "gs_index_cluster": (_i, [_vp, C.POINTER(ClusterParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(ClusterInfoC)]),
     "gs_index_import": (_i, [_vp, _vp, _u64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_index_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_index_get_data": (_i, [_vp, _u64, _u64, _vp]),

@@ -924,6 +924,48 @@ def dump_knn_graph(seqdict, node_ids, ids, dist, cnt, out):
     return len(node_ids)
 
 
+ClusterResult = namedtuple("ClusterResult", ["centre_node", "centre_id", "centre_count", "medoids", "medoid_ids", "sizes", "n_core", "iterations",
+                                             "converged", "cost_core", "cost_all", "core_nodes", "core_weight"])
+ClusterResult.__doc__ = """Hnsw.cluster's answer (SPEC 10). Per node, in node order: centre_node (node number of its centre), centre_id (the centre's caller
+id), centre_count (mismatch count to it). medoids / medoid_ids / sizes: the k centres by ascending node number (empty for n_cluster = 0, where the
+centres are the coreset points). core_nodes / core_weight: the coreset, None unless asked for."""
+
+HNSWCORE_TYPES = {"u16": np.uint16, "u32": np.uint32, "u64": np.uint64, "f32": np.float32}
+HNSWCORE_REFUSED = ("f64", "i32", "i64")            # hnswcore.rs:163-170 also names these: no sketcher produces them (SPEC 10)
+
+
+def write_cluster_csv(path, ids, centre_ids):
+    """hnswcore's membership file (hnswcore.rs:13-25): one line `{data_id},{centre_data_id}` per node, in node order (SPEC 10; the upstream writer is
+    not vendored, the exact layout is unverified). Returns the number of lines."""
+    ids, centre_ids = np.asarray(ids, np.uint64), np.asarray(centre_ids, np.uint64)
+    if ids.shape != centre_ids.shape:
+        raise GsError(_lib.GS_ERR_INVALID, "one centre per id")
+    with open(path, "w") as f:
+        f.write("".join("%d,%d\n" % (a, b) for a, b in zip(ids.tolist(), centre_ids.tolist())))
+    return len(ids)
+
+
+def hnswcore(dir, fname, typename, cluster=0, fraction=0.1, out_dir=".", max_iter=15, seed=None, ctx=None):
+    """hnswcore --dir dir --fname fname --typename typename [clustercore --cluster k --fraction f] (binaux/src/bin/hnswcore.rs): reloads the hnsw_rs dump
+    dir/fname.hnsw.{graph,data}, clusters it (Hnsw.cluster) and writes out_dir/clustercoreset.csv (coreset.csv when cluster = 0).
+    Returns (csv path, ClusterResult)."""
+    import os
+    if typename in HNSWCORE_REFUSED:
+        raise GsError(_lib.GS_ERR_UNSUPPORTED, "hnswcore: element type %s is not a signature type of this library (served: %s)" % (typename, ", ".join(sorted(HNSWCORE_TYPES))))
+    if typename not in HNSWCORE_TYPES:
+        raise GsError(_lib.GS_ERR_INVALID, "hnswcore: unknown type name %r (served: %s)" % (typename, ", ".join(sorted(HNSWCORE_TYPES))))
+    hn = Hnsw.load_hnswrs(os.path.join(str(dir), fname), ctx=ctx)
+    try:
+        if hn.dtype != np.dtype(HNSWCORE_TYPES[typename]):
+            raise GsError(_lib.GS_ERR_INVALID, "hnswcore: the dump holds %s, not %s" % (hn.dtype.name, typename))
+        res = hn.cluster(cluster, fraction, max_iter, seed)
+        path = os.path.join(str(out_dir), "clustercoreset.csv" if cluster else "coreset.csv")
+        write_cluster_csv(path, hn.get_ids(), res.centre_id)
+    finally:
+        hn.close()
+    return path, res
+
+
 def _rust_5e(x):
     """Rust's {:.5E}: mantissa with 5 decimals, exponent without padding or plus sign (6.07500E-1)"""
     mant, exp = ("%.5E" % x).split("E")
@@ -1049,6 +1091,39 @@ class Hnsw:
         out = np.zeros((datas.shape[0], self.get_nb_point()), dtype=np.uint16)
         check(self.ctx.L.gs_index_count_matrix(self.h, _p(datas), datas.shape[0], _p(out)))
         return out
+
+    def nearest_of(self, nodes):
+        """for every node, the position in `nodes` (node numbers) that minimises (mismatch count, position), and that count (gs_index_nearest_of)
+        -> (arg uint32, count uint16), one entry per node"""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "nearest_of on an empty index")
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint64)
+        n = self.get_nb_point()
+        arg, cnt = np.zeros(n, np.uint32), np.zeros(n, np.uint16)
+        check(self.ctx.L.gs_index_nearest_of(self.h, _p(nodes), len(nodes), _p(arg), _p(cnt)))
+        return arg, cnt
+
+    def cluster(self, n_cluster=0, fraction=0.1, max_iter=15, seed=None, return_coreset=False):
+        """hnswcore (SPEC 10): a coreset of about fraction x nb_point nodes, n_cluster medoids on it (0: the coreset points are the centres), every
+        node to its nearest centre (gs_index_cluster) -> ClusterResult. seed None: the library's default."""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "clustering of an empty index")
+        prm = _lib.load().gs_cluster_params_default()
+        prm.n_cluster, prm.fraction, prm.max_iter = int(n_cluster), float(fraction), int(max_iter)
+        if seed is not None:
+            prm.seed = int(seed)
+        n, k = self.get_nb_point(), int(n_cluster)
+        cen, cnt = np.zeros(n, np.uint64), np.zeros(n, np.uint16)
+        med, sizes = np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+        info = _lib.ClusterInfoC()
+        core = wgt = None
+        if return_coreset:
+            core, wgt = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        check(self.ctx.L.gs_index_cluster(self.h, C.byref(prm), _p(cen), _p(cnt), _p(med), _p(sizes), _p(core), _p(wgt), n if return_coreset else 0, C.byref(info)))
+        ids = self.get_ids()
+        p = int(info.n_core)
+        return ClusterResult(cen, ids[cen.astype(np.int64)], cnt, med, ids[med.astype(np.int64)], sizes, p, int(info.iterations), int(info.converged),
+                             int(info.cost_core), int(info.cost_all), core[:p] if return_coreset else None, wgt[:p] if return_coreset else None)
 
     def sketch_and_search_dev(self, params, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes, knbn, ef, d_ids, d_dist, d_count=None,
                               d_evals=None, d_sig=None):

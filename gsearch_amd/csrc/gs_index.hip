@@ -3807,6 +3807,59 @@ int gs_index_knn_graph_dev(gs_index *ix, uint32_t knbn, float max_dist, uint64_t
 
 }  // extern "C"
 namespace gs {
+// hnswcore (gs_cluster.hip, SPEC 10): the shape of the index, and the count rows of a block of its own nodes - gathered into pooled rows, then
+// dense_counts into ix->mat as exact_dev does. The caller holds the context lock.
+static int cluster_source(gs_index *ix, ClusterSource *src)
+{
+    GS_REQUIRE(ix->n > 0, GS_ERR_STATE, "clustering of an empty index");
+    GS_REQUIRE(ix->prm.m <= 65535, GS_ERR_UNSUPPORTED, "clustering needs the 16-bit count matrix: m <= 65535");
+    src->ix = ix; src->n = ix->n; src->m = ix->prm.m; src->ld = round_up(ix->n, 8);
+    // as many rows per block as one join pass takes, at most 8 GB of counts (exact_dev)
+    src->max_rows = std::min<uint64_t>(match_join_max_queries(), std::max<uint64_t>(64, ((uint64_t)8 << 30) / (2 * src->ld)));
+    return GS_OK;
+}
+int cluster_rows(gs_index *ix, const uint32_t *nodes_dev, uint64_t nb, const uint16_t **slab)
+{
+    const uint64_t ld = round_up(ix->n, 8);
+    // The lease ends with this call while dense_counts is still queued on the memory. That is sound because the slot keeps its memory, every later user of
+    // the pool is behind those kernels on the context's one stream, and a slot that grows frees its old memory with hipFree, which waits for the device.
+    PoolBuf rows(ix->ctx, SL_CL_ROWS);
+    int rc;
+    if ((rc = rows.alloc(nb * ix->stride))) return rc;
+    if ((rc = gather_rows(ix->ctx, ix->data.p, ix->stride, nodes_dev, nb, rows.p))) return rc;
+    if (ix->mat.bytes < (size_t)2 * nb * ld && (rc = alloc_or_evict(ix, ix->mat, (size_t)2 * nb * ld))) return rc;
+    if ((rc = dense_counts(ix, rows.as<uint8_t>(), nb, ix->n, ix->mat.as<uint16_t>(), ld))) return rc;
+    *slab = ix->mat.as<uint16_t>();
+    return GS_OK;
+}
+}  // namespace gs
+extern "C" {
+
+int gs_index_nearest_of(gs_index *ix, const uint64_t *cand_nodes, uint64_t nc, uint32_t *arg_out, uint16_t *count_out)
+{
+    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
+    GS_CTX_LOCK(ix->ctx);
+    gs::ClusterSource src;
+    int rc = gs::cluster_source(ix, &src);
+    if (rc) return rc;
+    GS_REQUIRE(cand_nodes && arg_out && count_out, GS_ERR_INVALID, "null argument");
+    return gs::nearest_of_nodes(ix->ctx, src, cand_nodes, nc, arg_out, count_out);
+}
+int gs_index_cluster(gs_index *ix, const gs_cluster_params *prm, uint64_t *centre_node_out, uint16_t *centre_count_out, uint64_t *medoids_out, uint64_t *sizes_out,
+                     uint64_t *core_nodes_out, uint64_t *core_weight_out, uint64_t core_cap, gs_cluster_info *info_out)
+{
+    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
+    const gs_cluster_params p = prm ? *prm : gs_cluster_params_default();
+    GS_CTX_LOCK(ix->ctx);
+    gs::ClusterSource src;
+    int rc = gs::cluster_source(ix, &src);
+    if (rc) return rc;
+    GS_REQUIRE(centre_node_out && centre_count_out && info_out && (p.n_cluster == 0 || (medoids_out && sizes_out)), GS_ERR_INVALID, "null argument");
+    return gs::cluster_nodes(ix->ctx, src, &p, centre_node_out, centre_count_out, medoids_out, sizes_out, core_nodes_out, core_weight_out, core_cap, info_out);
+}
+
+}  // extern "C"
+namespace gs {
 // ann (embed.rs:19-21): the index's exact self graph of every node in NODE numbers (no caller ids), in pooled buffers 100-102, validated (SPEC 8).
 // The caller holds the context lock.
 static int self_graph_dev(gs_index *ix, uint32_t knbn, float max_dist, uint64_t **ids, float **dist, uint32_t **cnt)

@@ -164,6 +164,23 @@ enum { KNN_MAX = 1024 };
 int knn_select(gs_ctx *c, const uint16_t *mat, uint64_t ld, uint64_t nrows, uint64_t n, uint32_t knbn, uint32_t c_max, uint64_t diag0, uint32_t m,
                uint64_t *ids, float *dist, uint32_t *count);
 
+// gs_cluster.hip (SPEC 10): coreset, k-medoids and nearest-centre dispatch over the nodes of an index. The shape the index hands over, and
+// cluster_rows (gs_index.hip): the counts of a block of the index's own nodes against every node, as exact_dev produces them for knn_select.
+struct ClusterSource {
+    gs_index *ix = nullptr;
+    uint64_t n = 0; uint32_t m = 0;
+    uint64_t ld = 0;                 // leading dimension of a count row, a multiple of 8
+    uint64_t max_rows = 0;           // rows per block at most
+};
+// rows nodes_dev[0 .. nb) (device node numbers) -> *slab: nb x ld counts, 16-byte aligned, valid until the next call; queued on the context's stream
+int cluster_rows(gs_index *ix, const uint32_t *nodes_dev, uint64_t nb, const uint16_t **slab);
+// the padded rows (stride bytes, a multiple of 16) of the listed nodes, one after the other
+int gather_rows(gs_ctx *c, const void *data, uint64_t stride, const uint32_t *nodes_dev, uint64_t nb, void *out);
+// host answers; the caller has validated the index side (not empty, m <= 65535) and holds the context lock
+int nearest_of_nodes(gs_ctx *c, const ClusterSource &src, const uint64_t *cand, uint64_t nc, uint32_t *arg_out, uint16_t *count_out);
+int cluster_nodes(gs_ctx *c, const ClusterSource &src, const gs_cluster_params *prm, uint64_t *centre_node, uint16_t *centre_count, uint64_t *medoids,
+                  uint64_t *sizes, uint64_t *core_nodes, uint64_t *core_weight, uint64_t core_cap, gs_cluster_info *info);
+
 // gs_embed.hip (SPEC 8): the embedding of a device graph in node numbers (embed_common validates nothing: the caller has; on_dev = false: init, pos_out
 // and memb_out are host arrays), and the statistics of a validated device graph (host outputs)
 int embed_validate(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *cnt);

@@ -11,6 +11,7 @@
 // A row is read three times, 16 bytes per lane and load. Histogram adds are merged per lane over runs of equal bins first: at s = 18000 most
 // counts of unrelated genomes share one high byte, and 64 lanes adding to one LDS word serialise.
 #include "gs_internal.hpp"
+#include "gs_countrow.hpp"
 
 namespace gs {
 namespace {
@@ -26,36 +27,6 @@ struct KnnLds {
     uint64_t keys[KNN_MAX];
 };
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-// exclusive prefix of one value per thread in thread order, and the block total. Two calls that use the same `wsum` need a barrier between them
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, uint32_t &tot)
-{
-    const uint32_t inc = wave_incl_scan(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t before = 0, t = 0;
-#pragma unroll
-    for (int i = 0; i < KW; i++) { const uint32_t s = wsum[i]; before += i < w ? s : 0; t += s; }
-    tot = t;
-    return before + inc - v;
-}
-
-__device__ __forceinline__ uint32_t elem(const uint4 &x, int e)
-{
-    const uint32_t w = e < 2 ? x.x : e < 4 ? x.y : e < 6 ? x.z : x.w;
-    return (e & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
-
 // histogram of bin(c) over the row's entries that pass `keep`; adds of equal consecutive bins of a lane are merged
 template <class Keep, class Bin>
 __device__ __forceinline__ void row_hist(const uint4 *rv, uint32_t nv, uint32_t n, uint32_t *hist, Keep keep, Bin bin)
@@ -70,7 +41,7 @@ __device__ __forceinline__ void row_hist(const uint4 *rv, uint32_t nv, uint32_t 
             const uint32_t v = v0 + u * KT;
 #pragma unroll
             for (int e = 0; e < 8; e++) {
-                const uint32_t j = v * 8 + e, c = elem(x[u], e);
+                const uint32_t j = v * 8 + e, c = count16(x[u], e);
                 if (v < nv && j < n && keep(j, c)) {
                     const uint32_t b = bin(c);
                     if (run && b != cur) { atomicAdd(&hist[cur], run); run = 0; }
@@ -98,7 +69,7 @@ __global__ void __launch_bounds__(KT) k_knn_select(const uint16_t *__restrict__ 
     row_hist(rv, nv, n, L.hist, eligible, [](uint32_t c) { return c >> 8; });
     __syncthreads();
     uint32_t h = L.hist[tid], tot;
-    uint32_t ex = block_excl_scan(h, L.wsum[0], tot);
+    uint32_t ex = block_excl_scan<KW>(h, L.wsum[0], tot);
     uint32_t K, t, n_less;
     if (tot <= knbn) {                   // every eligible entry is kept: all of them count as "below t"
         K = tot; t = c_max + 1; n_less = tot;
@@ -112,7 +83,7 @@ __global__ void __launch_bounds__(KT) k_knn_select(const uint16_t *__restrict__ 
         row_hist(rv, nv, n, L.hist, [&](uint32_t j, uint32_t c) { return eligible(j, c) && (c >> 8) == b1; }, [](uint32_t c) { return c & 0xFFu; });
         __syncthreads();
         h = L.hist[tid];
-        ex = block_excl_scan(h, L.wsum[1], tot);
+        ex = block_excl_scan<KW>(h, L.wsum[1], tot);
         const uint32_t K2 = K - before1;
         if (ex < K2 && ex + h >= K2) { L.sel[2] = (b1 << 8) | tid; L.sel[3] = before1 + ex; }
         __syncthreads();
@@ -129,19 +100,19 @@ __global__ void __launch_bounds__(KT) k_knn_select(const uint16_t *__restrict__ 
         uint32_t less = 0, eq = 0;
 #pragma unroll
         for (int e = 0; e < 8; e++) {
-            const uint32_t j = v * 8 + e, c = elem(x, e);
+            const uint32_t j = v * 8 + e, c = count16(x, e);
             const bool el = v < nv && j < n && eligible(j, c);
             less += el && c < t;
             eq += el && c == t;
         }
         uint32_t btot;                   // (per step at most 2048 of each: the two 16-bit halves do not carry into each other)
-        const uint32_t pre = block_excl_scan(less | (eq << 16), L.wsum[par], btot);
+        const uint32_t pre = block_excl_scan<KW>(less | (eq << 16), L.wsum[par], btot);
         par ^= 1;
         if (less | eq) {
             uint32_t pl = run_less + (pre & 0xFFFFu), pe = run_eq + (pre >> 16);
 #pragma unroll
             for (int e = 0; e < 8; e++) {
-                const uint32_t j = v * 8 + e, c = elem(x, e);
+                const uint32_t j = v * 8 + e, c = count16(x, e);
                 if (!(j < n && eligible(j, c))) continue;
                 const uint64_t key = ((uint64_t)c << 32) | j;
                 if (c < t) { if (pl < n_less) L.keys[pl] = key; pl++; }

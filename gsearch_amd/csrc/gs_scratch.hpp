@@ -53,6 +53,9 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     X(FRAC_CAND) X(FRAC_THR) X(FRAC_OFF) X(FRAC_CAP) X(FRAC_CNT) X(FRAC_TASK) X(FRAC_SEL) X(FRAC_DIST) X(FRAC_ALT) X(FRAC_LEN) X(FRAC_POS)            \
     X(FRAC_RADIX) X(FRAC_NRUNS) X(FRAC_COPY_SRC) X(FRAC_COPY_DST) X(FRAC_COPY_N) X(FRAC_HOST_ROWS) X(FRACB_TEXT) X(FRACB_RESIDUES)                    \
     X(FRACS_Q) X(FRACS_QOFF) X(FRACS_R) X(FRACS_ROFF) X(FRACS_SIM) X(FRACS_COMMON) X(FRACS_UNION)                                                     \
+    /* hnswcore (gs_cluster.hip): gathered rows of a block, candidate list, running (count, position) pairs, sampling, then the k-medoid state */         \
+    X(CL_ROWS) X(CL_NODES) X(CL_BEST) X(CL_IN0) X(CL_BLOCKS) X(CL_CORE) X(CL_WEIGHT) X(CL_LABEL) X(CL_P) X(CL_TOT) X(CL_MED) X(CL_DMIN) X(CL_ACC)    \
+    X(CL_OUT_NODE) X(CL_OUT_COUNT) X(CL_OUT_ARG)                                                                                                       \
     /* comm (gs_topk_merge_dev) */                                                                                                                    \
     X(COMM_ID_OFFSET)
 

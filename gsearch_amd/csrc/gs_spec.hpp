@@ -372,4 +372,11 @@ inline uint64_t frac_max_hash(uint32_t scaled)
     return (uint64_t)((double)~0ULL / (double)scaled);
 }
 
+// ---- SPEC 10: coreset sampling of hnswcore ---------------------------------------------------------------------------------------------
+// h(r, i): the draw of node i in sampling round r
+GS_HD uint64_t cluster_hash(uint64_t seed, uint32_t r, uint64_t i) { return splitmix_mix((seed ^ ((uint64_t)r << 56) ^ i) + GS_GAMMA); }
+// round 0 keeps i with (h >> 32) n < t0 << 32, round 1 with (h >> 40) D < (t1 d0) << 24: both sides fit 64 bits for n < 2^32, n m < 2^40
+GS_HD bool cluster_keep0(uint64_t h, uint64_t n, uint64_t t0) { return (h >> 32) * n < (t0 << 32); }
+GS_HD bool cluster_keep1(uint64_t h, uint64_t D, uint64_t t1, uint32_t d0) { return (h >> 40) * D < ((t1 * d0) << 24); }
+
 }  // namespace gs

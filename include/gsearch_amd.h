@@ -348,6 +348,31 @@ typedef struct {
 int      gs_knn_graph_stats(gs_ctx *, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *count,
                             gs_knn_stats *stats_out, uint32_t *occ_out, uint64_t *hist_out);
 int      gs_index_knn_graph_stats(gs_index *, uint32_t knbn, float max_dist, gs_knn_stats *stats_out, uint32_t *occ_out, uint64_t *hist_out);
+/* hnswcore (binaux/src/bin/hnswcore.rs): a coreset of the database, an optional k-medoid pass on it, and the dispatch of every node to its nearest
+ * centre. All-integer and reproducible bit for bit (SPEC.md 10); Bmor's beta / gamma have no counterpart. */
+typedef struct {
+    uint32_t n_cluster;      /* k medoids; 0 = coreset only, the centres are the coreset points (hnswcore without --cluster) */
+    double   fraction;       /* coreset size aimed at, as a fraction of the database, in (0, 1] (0.1, hnswcore.rs:328) */
+    uint32_t max_iter;       /* k-medoid iterations at most, >= 1 (15, hnswcore.rs:272) */
+    uint64_t seed;           /* sampling */
+} gs_cluster_params;
+gs_cluster_params gs_cluster_params_default(void);
+typedef struct {
+    uint64_t n_core;         /* p: points of the coreset */
+    uint32_t iterations;     /* k-medoid iterations run */
+    uint32_t converged;      /* 1: the last iteration moved no medoid */
+    uint64_t cost_core;      /* sum over the coreset of weight x count to the medoid, at the last assign step */
+    uint64_t cost_all;       /* sum over all nodes of the count to their centre */
+} gs_cluster_info;
+/* for every node, the position in cand_nodes (node numbers < nb_point, nc >= 1; the same node may be listed twice) that minimises
+ * (mismatch count, position), and that count. arg_out / count_out: HOST, nb_point entries. Needs m <= 65535. */
+int      gs_index_nearest_of(gs_index *, const uint64_t *cand_nodes, uint64_t nc, uint32_t *arg_out, uint16_t *count_out);
+/* prm NULL: defaults. HOST outputs: centre_node_out[nb_point] = the NODE NUMBER of each node's centre (gs_index_get_ids maps it to the caller's id),
+ * centre_count_out[nb_point] = the mismatch count to it, medoids_out[k] = the medoids' node numbers, ascending, sizes_out[k] = nodes dispatched to
+ * each. Optional: core_nodes_out / core_weight_out (room for core_cap entries each): the coreset in node order and its weights; info_out->n_core is
+ * written in any case, and a core_cap below it is GS_ERR_INVALID. Empty index: GS_ERR_STATE; m > 65535 or nb_point x m >= 2^40: GS_ERR_UNSUPPORTED. */
+int      gs_index_cluster(gs_index *, const gs_cluster_params *prm, uint64_t *centre_node_out, uint16_t *centre_count_out, uint64_t *medoids_out,
+                          uint64_t *sizes_out, uint64_t *core_nodes_out, uint64_t *core_weight_out, uint64_t core_cap, gs_cluster_info *info_out);
 /* Graph import / export (the role of hnswio::HnswIo::load_hnsw / Hnsw::file_dump, reloadhnsw.rs:41-51,
  * dumpload.rs:31, in this library's own dense layout): levels[n], entry id, layer 0: deg0[n], nbr0[n*2M],
  * cnt0[n*2M] (mismatch counts to the owner); upper layers: upidx[n] (-1 for level-0 nodes) and for the

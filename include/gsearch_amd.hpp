@@ -346,6 +346,26 @@ public:
         check(gs_index_knn_graph_stats(h_, (uint32_t)knbn, max_dist, &st, occ ? occ->data() : nullptr, hist ? hist->data() : nullptr));
         return st;
     }
+    // hnswcore (SPEC 10): per node, in node order, the NODE NUMBER of its centre and the mismatch count to it; the medoids ascending (empty for
+    // n_cluster = 0, where the coreset points are the centres) and how many nodes each received
+    struct Clusters { std::vector<uint64_t> centre_node; std::vector<uint16_t> centre_count; std::vector<uint64_t> medoids, sizes; gs_cluster_info info; };
+    Clusters cluster(const gs_cluster_params *prm = nullptr) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "clustering of an empty index");
+        const gs_cluster_params p = prm ? *prm : gs_cluster_params_default();
+        Clusters r;
+        r.centre_node.resize(get_nb_point()); r.centre_count.resize(get_nb_point()); r.medoids.resize(p.n_cluster); r.sizes.resize(p.n_cluster);
+        check(gs_index_cluster(h_, &p, r.centre_node.data(), r.centre_count.data(), r.medoids.data(), r.sizes.data(), nullptr, nullptr, 0, &r.info));
+        return r;
+    }
+    // for every node the position in `nodes` (node numbers) that minimises (mismatch count, position), and that count (gs_index_nearest_of)
+    std::pair<std::vector<uint32_t>, std::vector<uint16_t>> nearest_of(const std::vector<uint64_t> &nodes) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "nearest_of on an empty index");
+        std::vector<uint32_t> arg(get_nb_point()); std::vector<uint16_t> cnt(get_nb_point());
+        check(gs_index_nearest_of(h_, nodes.data(), nodes.size(), arg.data(), cnt.data()));
+        return {std::move(arg), std::move(cnt)};
+    }
     void file_dump(const std::string &path) const { check(gs_index_save(h_, path.c_str())); }      // dumpload.rs:31 (own format)
 private:
     void frozen() const { if (h_) throw Error(GS_ERR_STATE, "index parameters are frozen once the index holds points"); }
