@@ -56,6 +56,17 @@ class ClusterInfoC(C.Structure):
     _fields_ = [("n_core", C.c_uint64), ("iterations", C.c_uint32), ("converged", C.c_uint32), ("cost_core", C.c_uint64), ("cost_all", C.c_uint64)]
 
 
+class BigsiParamsC(C.Structure):
+    """gs_bigsi_params (SPEC 11)"""
+    _fields_ = [("k", C.c_uint32), ("num_hash", C.c_uint32), ("bloom_size", C.c_uint64), ("data_t", C.c_uint32), ("minimizer", C.c_uint32),
+                ("coverage_filter", C.c_uint32)]
+
+
+class BigsiDescC(C.Structure):
+    """gs_bigsi_desc (SPEC 11)"""
+    _fields_ = [("prm", BigsiParamsC), ("n_colours", C.c_uint64), ("colour_capacity", C.c_uint64), ("row_words", C.c_uint64)]
+
+
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
 
@@ -150,6 +161,26 @@ SYMBOLS = {
     "gs_cluster_params_default": (ClusterParamsC, []),
     "gs_index_nearest_of": (_i, [_vp, _vp, _u64, _vp, _vp]),
     "gs_index_cluster": (_i, [_vp, C.POINTER(ClusterParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(ClusterInfoC)]),
+    # bigsig (SPEC 11)
+    "gs_bigsi_check_params": (_i, [C.POINTER(BigsiParamsC)]),
+    "gs_bigsi_create": (_i, [_vp, C.POINTER(BigsiParamsC), _u64, C.POINTER(_vp)]),
+    "gs_bigsi_free": (None, [_vp]),
+    "gs_bigsi_info": (_i, [_vp, C.POINTER(BigsiDescC)]),
+    "gs_bigsi_add_batch_dev": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
+    "gs_bigsi_add_batch": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _u64]),
+    "gs_bigsi_bits_set": (_i, [_vp, _u64, _u64, _vp, _vp]),
+    "gs_bigsi_rows": (_i, [_vp, _vp, _u64, _vp]),
+    "gs_bigsi_query_dev": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    "gs_bigsi_query": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    "gs_bigsi_classify_dev": (_i, [_vp, _u64, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "gs_bigsi_set_accessions": (_i, [_vp, C.POINTER(C.c_char_p), _u64]),
+    "gs_bigsi_accessions": (_i, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "gs_bigsi_save": (_i, [_vp, C.c_char_p]),
+    "gs_bigsi_load": (_i, [_vp, C.c_char_p, _u64, C.POINTER(_vp)]),
+    "gs_bigsi_positions": (_i, [_u64, _u32, _u64, _vp]),
+    "gs_bigsi_split": (_i, [_vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "gs_bigsi_tail": (C.c_double, [_u64, _u64, _u32, _u32, _u32]),
+    "gs_bigsig_write_reads": (_i, [C.c_char_p, C.POINTER(C.c_char_p), _u64, C.POINTER(C.c_char_p), _u64, _vp, _vp, _vp, _vp]),
     "gs_index_import": (_i, [_vp, _vp, _u64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_index_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_index_get_data": (_i, [_vp, _u64, _u64, _vp]),

@@ -726,6 +726,261 @@ def superaai(query_list, ref_list, out, k=7, scaled=100, sketch=5120, threads=0,
     return sim
 
 
+# ---- bigsig (binaux/src/bin/bigsig.rs; SPEC 11) -----------------------------------------------------------------------------------------
+def _text_records(groups, quals=None):
+    """groups: a list of lists of records (ASCII bytes) -> (text, qual or None, rec_begin, rec_end, group_rec_off) for the host forms"""
+    recs = [r for g in groups for r in g]
+    text = np.frombuffer(b"".join(recs), dtype=np.uint8) if recs else np.zeros(0, np.uint8)
+    qual = None
+    if quals is not None:
+        qrecs = [q for g in quals for q in g]
+        if [len(q) for q in qrecs] != [len(r) for r in recs]:
+            raise ValueError("every record needs as many quality bytes as it has text bytes")
+        qual = np.frombuffer(b"".join(qrecs), dtype=np.uint8) if qrecs else np.zeros(0, np.uint8)
+    end = np.cumsum([len(r) for r in recs], dtype=np.uint64) if recs else np.zeros(0, np.uint64)
+    begin = np.concatenate([np.zeros(1, np.uint64), end[:-1]]) if recs else np.zeros(0, np.uint64)
+    off = np.concatenate([np.zeros(1, np.uint64), np.cumsum([len(g) for g in groups], dtype=np.uint64)]).astype(np.uint64)
+    return text, qual, begin, end, off
+
+
+def bigsi_positions(v, num_hash, bloom_size):
+    """SPEC 11: the num_hash rows of the k-mer value v (host arithmetic)"""
+    out = np.zeros(int(num_hash), np.uint64)
+    check(_lib.load().gs_bigsi_positions(int(v), int(num_hash), int(bloom_size), _p(out)))
+    return out
+
+
+def bigsi_split(text, qual=None, min_phred=15, min_len=1):
+    """SPEC 11: the segments of a text, list of (offset of the first base, bases); a non-ACGT byte or a base below min_phred ends a segment"""
+    L = _lib.load()
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    q = None if qual is None else np.frombuffer(bytes(qual), dtype=np.uint8)
+    n = C.c_uint64()
+    check(L.gs_bigsi_split(_p(t) if len(t) else None, _p(q) if q is not None and len(q) else None, len(t), int(min_phred), int(min_len), 0, None, None, C.byref(n)))
+    b, l = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+    check(L.gs_bigsi_split(_p(t) if len(t) else None, _p(q) if q is not None and len(q) else None, len(t), int(min_phred), int(min_len), n.value, _p(b), _p(l), C.byref(n)))
+    return [(int(x), int(y)) for x, y in zip(b, l)]
+
+
+def bigsi_tail(t_c, bloom_size, num_hash, n_kmers, best_hits):
+    """SPEC 11: P(X >= best_hits), X ~ Binomial(n_kmers, (t_c / bloom_size)^num_hash) (host arithmetic)"""
+    return _lib.load().gs_bigsi_tail(int(t_c), int(bloom_size), int(num_hash), int(n_kmers), int(best_hits))
+
+
+def bigsig_write_reads(prefix, accessions, read_ids, best_colour, best_hits, n_kmers, accept):
+    """`{prefix}_reads.txt` and `{prefix}_counts.txt` (SPEC 11)"""
+    acc = (C.c_char_p * max(len(accessions), 1))(*[a.encode() for a in accessions])
+    ids = (C.c_char_p * max(len(read_ids), 1))(*[r.encode() for r in read_ids])
+    bc, bh, nk = (np.ascontiguousarray(x, dtype=np.uint32) for x in (best_colour, best_hits, n_kmers))
+    ac = np.ascontiguousarray(accept, dtype=np.uint8)
+    check(_lib.load().gs_bigsig_write_reads(str(prefix).encode(), acc, len(accessions), ids, len(read_ids), _p(bc), _p(bh), _p(nk), _p(ac)))
+
+
+class Bigsi:
+    """A bit-sliced Bloom index of genomes (bigsig): bloom_size rows, one column ("colour") per genome in the order added; the matrix lives on the device."""
+
+    def __init__(self, k, num_hash, bloom_size, capacity, data_t="dna", ctx=None, minimizer=0, coverage_filter=0, _handle=None):
+        self.ctx = ctx or default_context()
+        self.L = self.ctx.L
+        if _handle is not None:
+            self.h = _handle
+            return
+        prm = _lib.BigsiParamsC(int(k), int(num_hash), int(bloom_size), DATA[data_t] if isinstance(data_t, str) else int(data_t), int(minimizer),
+                                int(coverage_filter))
+        h = C.c_void_p()
+        check(self.L.gs_bigsi_create(self.ctx.h, C.byref(prm), int(capacity), C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def new(cls, k, num_hash, bloom_size, capacity, **kw):
+        return cls(k, num_hash, bloom_size, capacity, **kw)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gs_bigsi_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if not _exiting[0]:
+                self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        d = _lib.BigsiDescC()
+        check(self.L.gs_bigsi_info(self.h, C.byref(d)))
+        return {"k": d.prm.k, "num_hash": d.prm.num_hash, "bloom_size": d.prm.bloom_size, "data_t": d.prm.data_t, "n_colours": d.n_colours,
+                "colour_capacity": d.colour_capacity, "row_words": d.row_words}
+
+    def add_genomes(self, genomes, accessions=None, quals=None, min_phred=15):
+        """genomes: a list of lists of records (ASCII bytes), one new colour each; quals: the same shape, quality bytes"""
+        text, qual, b, e, off = _text_records(genomes, quals)
+        names = None if accessions is None else self.accessions() + list(accessions)
+        check(self.L.gs_bigsi_add_batch(self.h, _p(text) if len(text) else None, _p(qual) if qual is not None and len(qual) else None, int(min_phred),
+                                        _p(b), _p(e), len(b), _p(off), len(genomes)))
+        if names is not None:
+            self.set_accessions(names)
+
+    def add_genomes_dev(self, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes):
+        """the packed layout of gs_sketch_batch_dev, every pointer device memory; queued on the context's stream"""
+        check(self.L.gs_bigsi_add_batch_dev(self.h, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes))
+
+    def add_files(self, paths, accessions=None, quality=15):
+        """one colour per FASTA / FASTQ file (plain, gz, bz2, xz), every record of the file; FASTQ bases below `quality` end a segment"""
+        genomes, quals, any_q = [], [], False
+        for p in paths:
+            recs, qs = _read_seq_records(read_fasta_file(p))
+            genomes.append([r for _, r in recs])
+            quals.append(qs if qs is not None else [b"~" * len(r) for _, r in recs])
+            any_q = any_q or qs is not None
+        self.add_genomes(genomes, accessions=accessions, quals=quals if any_q else None, min_phred=quality)
+
+    def set_accessions(self, names):
+        arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        check(self.L.gs_bigsi_set_accessions(self.h, arr, len(names)))
+
+    def accessions(self):
+        nb = C.c_uint64()
+        check(self.L.gs_bigsi_accessions(self.h, None, 0, C.byref(nb)))
+        buf = C.create_string_buffer(max(nb.value, 1))
+        check(self.L.gs_bigsi_accessions(self.h, buf, nb.value, C.byref(nb)))
+        return [x.decode() for x in buf.raw[:nb.value].split(b"\0")[:-1]]
+
+    def bits_set(self, return_kmers=False):
+        """t_c of every colour (and, on request, the k-mer occurrences fed)"""
+        n = self.info()["n_colours"]
+        t, q = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        check(self.L.gs_bigsi_bits_set(self.h, 0, n, _p(t), _p(q)))
+        return (t, q) if return_kmers else t
+
+    def rows(self, rows):
+        """the named rows as (len(rows), row_words) u64"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        out = np.zeros((len(r), self.info()["row_words"]), np.uint64)
+        check(self.L.gs_bigsi_rows(self.h, _p(r), len(r), _p(out)))
+        return out
+
+    def query(self, reads, quals=None, min_phred=15, down_sample=1, dense=False):
+        """reads: a list of lists of records (the mates of a pair: two records) -> (n_kmers, best_colour, best_hits[, counts (n_reads, n_colours)])"""
+        text, qual, b, e, off = _text_records(reads, quals)
+        n = len(reads)
+        nk, bc, bh = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        cnt = np.zeros((n, self.info()["n_colours"]), np.uint32) if dense else None
+        check(self.L.gs_bigsi_query(self.h, _p(text) if len(text) else None, _p(qual) if qual is not None and len(qual) else None, int(min_phred), _p(b), _p(e),
+                                    len(b), _p(off), n, int(down_sample), _p(nk), _p(bc), _p(bh), _p(cnt)))
+        return (nk, bc, bh, cnt) if dense else (nk, bc, bh)
+
+    def query_dev(self, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_read_rec_off, n_reads, d_n_kmers, d_best_colour, d_best_hits, d_counts=None,
+                  down_sample=1):
+        check(self.L.gs_bigsi_query_dev(self.h, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_read_rec_off, n_reads, int(down_sample), d_n_kmers,
+                                        d_best_colour, d_best_hits, d_counts))
+
+    def classify_dev(self, n_reads, d_n_kmers, d_best_colour, d_best_hits, fp_correct, d_tail, d_accept):
+        check(self.L.gs_bigsi_classify_dev(self.h, n_reads, d_n_kmers, d_best_colour, d_best_hits, float(fp_correct), d_tail, d_accept))
+
+    def classify(self, n_kmers, best_colour, best_hits, fp_correct):
+        """(tail f64, accept bool) of every read; fp_correct is the threshold itself (bigsig passes 10^-p)"""
+        n = len(n_kmers)
+        if n == 0:
+            return np.zeros(0, np.float64), np.zeros(0, bool)
+        c = self.ctx
+        ptrs = [c.alloc(4 * n) for _ in range(3)] + [c.alloc(8 * n), c.alloc(n)]
+        try:
+            for ptr, a in zip(ptrs, (n_kmers, best_colour, best_hits)):
+                c.upload(ptr, np.ascontiguousarray(a, dtype=np.uint32))
+            self.classify_dev(n, ptrs[0], ptrs[1], ptrs[2], fp_correct, ptrs[3], ptrs[4])
+            return c.download(ptrs[3], n, np.float64), c.download(ptrs[4], n, np.uint8).astype(bool)
+        finally:
+            for ptr in ptrs:
+                c.free(ptr)
+
+    def save(self, path):
+        check(self.L.gs_bigsi_save(self.h, str(path).encode()))
+
+    @classmethod
+    def load(cls, path, ctx=None, capacity=0):
+        ctx = ctx or default_context()
+        h = C.c_void_p()
+        check(ctx.L.gs_bigsi_load(ctx.h, str(path).encode(), int(capacity), C.byref(h)))
+        return cls(0, 0, 0, 0, ctx=ctx, _handle=h)
+
+
+def _strip_breaks(b):
+    return b.replace(b"\n", b"").replace(b"\r", b"")
+
+
+def _read_seq_records(text):
+    """FASTA or FASTQ (by the first non-blank byte) -> ([(id, sequence without line breaks)], [quality strings] or None)"""
+    if text.lstrip()[:1] == b"@":
+        recs, quals = [], []
+        for rid, sb, se in fastq_scan(text):
+            seq = _strip_breaks(text[sb:se])
+            pos = text.index(b"\n", text.index(b"+", se)) + 1             # the quality text follows the '+' line
+            q = bytearray()
+            while len(q) < len(seq):
+                nl = text.find(b"\n", pos)
+                nl = len(text) if nl < 0 else nl
+                q += text[pos:nl].rstrip(b"\r")
+                pos = nl + 1
+            recs.append((rid, seq))
+            quals.append(bytes(q[:len(seq)]))
+        return recs, quals
+    return [(rid, _strip_breaks(text[sb:se])) for rid, sb, se in fasta_scan(text, skip_capsid=False)], None
+
+
+def read_ref_list(path):
+    """bigsig's reference list: `accession\tpath` per line -> [(accession, path)]; an accession listed twice is GS_ERR_INVALID"""
+    out, seen = [], set()
+    for line in read_path_list(path):
+        acc, _, fpath = line.partition("\t")
+        if not fpath or acc in seen:
+            raise GsError(_lib.GS_ERR_INVALID, "reference list %s: %s" % (path, "accession %r listed twice" % acc if fpath else "line %r has no tab" % line))
+        seen.add(acc)
+        out.append((acc, fpath.strip()))
+    return out
+
+
+def bigsig_construct(ref_list, out_base, k, num_hash, bloom_size, quality=15, threads=0, ctx=None, batch=64):
+    """bigsig construct: one colour per line of ref_list, the index written to `{out_base}.gsbx` and returned. threads: accepted, unused (files are read one
+    after the other on the host)"""
+    refs = read_ref_list(ref_list)
+    bx = Bigsi(k, num_hash, bloom_size, max(len(refs), 1), ctx=ctx)
+    for i in range(0, len(refs), batch):
+        part = refs[i:i + batch]
+        bx.add_files([p for _, p in part], accessions=[a for a, _ in part], quality=quality)
+    bx.save(str(out_base) + ".gsbx")
+    return bx
+
+
+def bigsig_identify(index, queries, prefix, down_sample=1, fp_correct=3.0, quality=15, batch=50000, ctx=None):
+    """bigsig identify: every read of the query file(s) against the index (a Bigsi or the path of a saved one); two query paths are the mates of pairs.
+    fp_correct is bigsig's -p: the threshold is 10^-fp_correct. Writes `{prefix}_reads.txt` / `{prefix}_counts.txt`, returns the per-read arrays."""
+    bx = index if isinstance(index, Bigsi) else Bigsi.load(index, ctx=ctx)
+    queries = [queries] if isinstance(queries, (str, bytes)) or hasattr(queries, "__fspath__") else list(queries)
+    if len(queries) not in (1, 2):
+        raise GsError(_lib.GS_ERR_INVALID, "one query file, or two for pairs")
+    files = [_read_seq_records(read_fasta_file(q)) for q in queries]
+    n = len(files[0][0])
+    if any(len(f[0]) != n for f in files):
+        raise GsError(_lib.GS_ERR_INVALID, "the two query files hold different numbers of reads")
+    any_q = any(f[1] is not None for f in files)
+    ids = [rid for rid, _ in files[0][0]]
+    outs = [[], [], [], []]
+    thr = 10.0 ** (-float(fp_correct))
+    for i in range(0, n, max(int(batch), 1)):
+        j = min(n, i + max(int(batch), 1))
+        reads = [[f[0][r][1] for f in files] for r in range(i, j)]
+        quals = [[(f[1][r] if f[1] is not None else b"~" * len(f[0][r][1])) for f in files] for r in range(i, j)] if any_q else None
+        nk, bc, bh = bx.query(reads, quals=quals, min_phred=quality, down_sample=down_sample)
+        _, acc = bx.classify(nk, bc, bh, thr)
+        for o, a in zip(outs, (nk, bc, bh, acc)):
+            o.append(a)
+    nk, bc, bh, acc = (np.concatenate(o) if o else np.zeros(0, np.uint32) for o in outs)
+    bigsig_write_reads(prefix, bx.accessions(), ids, bc, bh, nk, acc)
+    return {"ids": ids, "n_kmers": nk, "best_colour": bc, "best_hits": bh, "accept": acc.astype(bool)}
+
+
 # ----------------------------------------------------------------------------------------------------------
 class DistHamming:
     """anndists::dist::DistHamming — eval(a, b) = count(a[i] != b[i]) / len, f32."""

@@ -1,0 +1,814 @@
+// gs_bigsi.hip — bigsig (binaux/src/bin/bigsig.rs): a bit-sliced Bloom index of genomes and the genome each read comes from. Arithmetic: SPEC.md 11,
+// constants in gs_spec.hpp; layout and what binds each kernel: DESIGN.md 3.15.
+//
+//  The matrix M is row-major: row r = W = ceil(capacity / 64) u64 words at M + r * W, colour c = bit c & 63 of word c >> 6. All offsets are 64-bit.
+//
+//  build, a block of <= 512 colours at a time:
+//  * k_bigsi_fill      : walk_genome per genome (`parts` workgroups each), every k-mer ORs its num_hash bits into the genome's private bitmap
+//                        of bloom_size bits in scratch (atomicOr: a few MB per genome, re-hit while it is walked).
+//  * k_bigsi_popcount  : t_c of every genome of the block from its bitmap.
+//  * k_bigsi_transpose : 512 rows x the block's colours per workgroup. Each colour's 64 bytes (512 rows) are staged in LDS, 64 colours x 32 rows
+//                        become 32 row words by __ballot, the words of 256 rows are staged again and leave as runs of 8 words = 64 bytes per row.
+//  query:
+//  * k_bigsi_query     : one wavefront per read, lanes = colour words. 64 k-mers are hashed at once (one per lane), then taken in turn: num_hash
+//                        nontemporal row loads, an AND, and a ripple add of the 64-bit vector into bit-plane counters in registers.
+//  * k_bigsi_classify  : one lane per read, the binomial tail of SPEC 11.
+#include <errno.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+#include "gs_internal.hpp"
+#include "gs_spec.hpp"
+#include "gs_walk.hpp"
+
+struct gs_bigsi {
+    gs_ctx *c = nullptr;
+    gs_bigsi_params prm{};
+    uint64_t cap = 0, W = 0, n = 0;
+    gs::DevBuf M, tc, nk;                  // the matrix; t_c and nk_c of every colour
+    std::vector<std::string> names;        // accessions (empty until set)
+};
+
+namespace gs {
+
+constexpr uint32_t BX_BLOCK = 512;         // colours of a build block: 8 words = one 64-byte sector of every row
+constexpr uint32_t TR_ROWS = 512;          // rows of a transpose tile: 64 bytes of every colour's bitmap
+constexpr uint32_t TR_IN_PITCH = 17;       // u32 per colour in LDS (16 + 1: lanes = colours read one column without bank conflicts)
+constexpr uint32_t TR_OUT_PITCH = 9;       // u64 per row in LDS (8 + 1)
+
+static inline uint32_t bigsi_kq(const gs_bigsi_params &p) { return p.k | (p.data_t == GS_DATA_DNA_FWD ? (uint32_t)KQ_FWD : 0u); }
+// u32 words of one genome's bitmap: whole transpose tiles
+static inline uint64_t bitmap_pitch(uint64_t B) { return round_up(B, TR_ROWS) / 32; }
+
+struct BitEmit {
+    uint32_t *bm; uint64_t B; uint32_t h;
+    __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const
+    {
+        uint64_t h1, st;
+        bigsi_hash(v, h1, st);
+        for (uint32_t i = 0; i < h; i++) {
+            const uint64_t pos = bigsi_pos(h1, st, i, B);
+            atomicOr(&bm[pos >> 5], 1u << (pos & 31));
+        }
+    }
+};
+__global__ __launch_bounds__(SK_THREADS) void k_bigsi_fill(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                           const uint64_t *__restrict__ rec_upre, const uint64_t *__restrict__ genome_rec_off,
+                                                           const uint64_t *__restrict__ gen_units, uint32_t kq, uint64_t B, uint32_t h, uint32_t *__restrict__ bm,
+                                                           uint64_t pitch)
+{
+    const uint64_t g = blockIdx.y;
+    BitEmit emit{bm + g * pitch, B, h};
+    walk_genome<false, BitEmit>(seq, rec_start, rec_len, rec_upre, genome_rec_off[g], genome_rec_off[g + 1], gen_units[g], kq, blockIdx.x, gridDim.x, emit);
+}
+// tc[g] += bits of genome g's bitmap (grid: x = slices, y = genomes); nk[g] = k-mer occurrences of its records (slice 0)
+__global__ __launch_bounds__(256) void k_bigsi_popcount(const uint32_t *__restrict__ bm, uint64_t pitch, const uint64_t *__restrict__ rec_len,
+                                                        const uint64_t *__restrict__ genome_rec_off, uint32_t k, unsigned long long *__restrict__ tc,
+                                                        unsigned long long *__restrict__ nk)
+{
+    const uint64_t g = blockIdx.y;
+    const uint32_t *b = bm + g * pitch;
+    unsigned long long s = 0, q = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < pitch; i += (uint64_t)gridDim.x * 256) s += __popc(b[i]);
+    if (blockIdx.x == 0)
+        for (uint64_t r = genome_rec_off[g] + threadIdx.x; r < genome_rec_off[g + 1]; r += 256) { const uint64_t l = rec_len[r]; if (l >= k) q += l - k + 1; }
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); q += __shfl_down(q, o); }
+    if ((threadIdx.x & 63) == 0) { if (s) atomicAdd(&tc[g], s); if (q) atomicAdd(&nk[g], q); }
+}
+// Colour slot sc of the block = bit sc & 63 of word w0 + (sc >> 6); slot sc holds genome sc - cshift of the block (cshift = first colour & 63), none
+// outside [0, ng). The first word is OR-ed into the matrix when earlier colours share it (or_first); every other word of the block is new.
+__global__ __launch_bounds__(256) void k_bigsi_transpose(const uint32_t *__restrict__ bm, uint64_t pitch, uint32_t ng, uint32_t cshift, uint64_t B,
+                                                         uint64_t *__restrict__ M, uint64_t W, uint64_t w0, uint32_t nw, int or_first)
+{
+    __shared__ uint32_t s_in[BX_BLOCK * TR_IN_PITCH];
+    __shared__ uint64_t s_out[256 * TR_OUT_PITCH];
+    const uint64_t r0 = (uint64_t)blockIdx.x * TR_ROWS;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // 16 lanes read the 64 contiguous bytes of one colour
+    for (uint32_t idx = tid; idx < nw * 64 * 16; idx += 256) {
+        const uint32_t sc = idx >> 4, j = idx & 15;
+        const int gi = (int)sc - (int)cshift;
+        s_in[sc * TR_IN_PITCH + j] = (gi >= 0 && gi < (int)ng) ? bm[(uint64_t)gi * pitch + (r0 >> 5) + j] : 0u;
+    }
+    __syncthreads();
+    for (uint32_t half = 0; half < 2; half++) {
+        for (uint32_t wi = wave; wi < nw; wi += 4) {
+            for (uint32_t jj = 0; jj < 8; jj++) {
+                const uint32_t v = s_in[(wi * 64 + lane) * TR_IN_PITCH + half * 8 + jj];
+                uint64_t keep = 0;
+#pragma unroll
+                for (uint32_t b = 0; b < 32; b++) {
+                    const uint64_t word = __ballot((v >> b) & 1u);
+                    if (lane == b) keep = word;
+                }
+                if (lane < 32) s_out[(jj * 32 + lane) * TR_OUT_PITCH + wi] = keep;
+            }
+        }
+        __syncthreads();
+        // 8 lanes write the 64 contiguous bytes of one row
+        for (uint32_t idx = tid; idx < 256 * 8; idx += 256) {
+            const uint32_t row = idx >> 3, w = idx & 7;
+            const uint64_t r = r0 + half * 256 + row;
+            if (w < nw && r < B) {
+                const uint64_t val = s_out[row * TR_OUT_PITCH + w];
+                uint64_t *p = M + r * W + w0 + w;
+                if (or_first && w == 0) { if (val) *p |= val; }
+                else *p = val;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void k_bigsi_gather_rows(const uint64_t *__restrict__ M, uint64_t W, const uint64_t *__restrict__ rows, uint64_t n, uint64_t *__restrict__ out)
+{
+    const uint64_t total = n * W;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t i = t / W, w = t - i * W;
+        out[t] = M[rows[i] * W + w];
+    }
+}
+
+// ---- query -----------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t shfl64(uint64_t x, uint32_t src)
+{
+    return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(x >> 32), (int)src) << 32) | (uint32_t)__shfl((int)(uint32_t)x, (int)src);
+}
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t x, uint32_t m)
+{
+    return ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), (int)m) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)x, (int)m);
+}
+__device__ __forceinline__ uint64_t readlane64(uint64_t x, uint32_t lane_uniform)
+{
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)lane_uniform) << 32) |
+           (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, (int)lane_uniform);
+}
+// the k-mer value (SPEC 1.1) of the k bases from base s of the packed sequence; every base of it lies inside one record
+__device__ __forceinline__ uint64_t kmer_at(const uint64_t *__restrict__ w64, uint64_t s, uint32_t k, uint64_t mask, bool fwd_only)
+{
+    const uint64_t u = s >> 5;
+    const uint32_t o = (uint32_t)(s & 31);
+    uint64_t left = __builtin_bswap64(w64[u]) << (2 * o);
+    if (o + k > 32) left |= __builtin_bswap64(w64[u + 1]) >> (64 - 2 * o);          // o >= 1 here
+    left &= ~(uint64_t)0 << (64 - 2 * k);
+    const uint64_t fwd = left >> (64 - 2 * k);
+    if (fwd_only) return fwd;
+    const uint64_t rc = rc64(left) & mask;                                          // the 32 - k padding bases end up above the mask
+    return fwd < rc ? fwd : rc;
+}
+// Counts are u32. A read of fewer than 2^BX_PLANES_SHORT k-mers (every sequencing read) keeps 12 planes; the same kernel with 32 planes takes the others
+// (a contig given as a read) in a second launch: each launch leaves the other's reads alone.
+enum { BX_PLANES_SHORT = 12, BX_PLANES_LONG = 32 };
+// planes += a 1-bit vector, from plane p up; leaves as soon as no lane of the wavefront carries (nested ifs: the planes keep constant indices, i.e. registers)
+template <int p, int BX_PLANES> __device__ __forceinline__ void ripple_add(uint64_t (&P)[BX_PLANES], uint64_t carry)
+{
+    if constexpr (p < BX_PLANES) {
+        if (__ballot(carry != 0) == 0) return;
+        const uint64_t t = P[p] & carry;
+        P[p] ^= carry;
+        ripple_add<p + 1, BX_PLANES>(P, t);
+    }
+}
+// HB: row loads in flight per k-mer (num_hash when it is <= 4, else 4; a short last group repeats its last row: AND is idempotent)
+template <int HB, int BX_PLANES>
+__global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict__ seq64, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                     const uint64_t *__restrict__ read_rec_off, uint64_t n_reads, uint32_t kq, uint32_t d, uint64_t B, uint32_t h,
+                                                     const uint64_t *__restrict__ M, uint64_t W, uint64_t nc, uint32_t *__restrict__ out_n,
+                                                     uint32_t *__restrict__ out_col, uint32_t *__restrict__ out_hits, uint32_t *__restrict__ dense)
+{
+    const uint32_t wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t read = (uint64_t)blockIdx.x * 4 + wave_u;
+    if (read >= n_reads) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t k = kq_k(kq);
+    const bool fwd_only = (kq & KQ_FWD) != 0;
+    const uint64_t mask = kmer_mask(false, k);
+    const uint64_t ra = read_rec_off[read], rb = read_rec_off[read + 1];
+    // n: the occurrences used
+    uint64_t n64 = 0, jb = 0;
+    for (uint64_t r = ra; r < rb; r++) {
+        const uint64_t len = rec_len[r];
+        if (len < k) continue;
+        const uint64_t cnt = len - k + 1, first = (jb + d - 1) / d * d;
+        if (first < jb + cnt) n64 += (jb + cnt - 1 - first) / d + 1;
+        jb += cnt;
+    }
+    const uint32_t n = (uint32_t)n64;
+    if ((n >> BX_PLANES_SHORT) != 0 ? BX_PLANES == BX_PLANES_SHORT : BX_PLANES != BX_PLANES_SHORT) return;      // the other launch's read
+    const uint32_t np = n ? 32 - (uint32_t)__builtin_clz(n) : 0;                    // planes that can hold a count <= n
+    uint32_t Wp = 64;
+    if (W < 64) { Wp = 1; while (Wp < W) Wp <<= 1; }
+    const uint32_t G = 64 / Wp, grp = lane / Wp, wl = lane & (Wp - 1);
+    uint32_t best_h = 0, best_c = 0;
+    for (uint64_t wc = 0; wc < W; wc += 64) {
+        const uint64_t wi = wc + wl;
+        const bool active = wi < W;
+        uint64_t P[BX_PLANES];
+#pragma unroll
+        for (int p = 0; p < BX_PLANES; p++) P[p] = 0;
+        jb = 0;
+        for (uint64_t r = ra; r < rb; r++) {
+            const uint64_t len = rec_len[r];
+            if (len < k) continue;
+            const uint64_t rs = rec_start[r], cnt = len - k + 1, first = (jb + d - 1) / d * d;
+            if (first < jb + cnt) {
+                const uint64_t nu = (jb + cnt - 1 - first) / d + 1, off0 = first - jb;
+                for (uint64_t c0 = 0; c0 < nu; c0 += 64) {
+                    uint64_t h1 = 0, st = 0;
+                    if (c0 + lane < nu) bigsi_hash(kmer_at(seq64, rs + off0 + (c0 + lane) * d, k, mask, fwd_only), h1, st);
+                    const uint32_t m = (uint32_t)(nu - c0 < 64 ? nu - c0 : 64);
+                    for (uint32_t t = 0; t < m; t += G) {
+                        const uint32_t src = t + grp;
+                        const bool kv = active && src < m;
+                        uint64_t a1, as;
+                        if (G == 1) { a1 = readlane64(h1, t); as = readlane64(st, t); }      // wave-uniform: the positions are scalar arithmetic
+                        else { a1 = shfl64(h1, src & 63); as = shfl64(st, src & 63); }
+                        uint64_t acc = kv ? ~(uint64_t)0 : 0;
+                        for (uint32_t i0 = 0; i0 < h; i0 += HB) {
+                            uint64_t w[HB];
+#pragma unroll
+                            for (int j = 0; j < HB; j++) {
+                                const uint32_t i = i0 + j < h ? i0 + j : h - 1;
+                                const uint64_t pos = bigsi_pos(a1, as, i, B);
+                                w[j] = kv ? __builtin_nontemporal_load(M + pos * W + wi) : 0;
+                            }
+#pragma unroll
+                            for (int j = 0; j < HB; j++) acc &= w[j];
+                        }
+                        // ripple add of the 1-bit vector into the planes; leaves as soon as no lane carries
+                        ripple_add<0, BX_PLANES>(P, acc);
+                    }
+                }
+            }
+            jb += cnt;
+        }
+        // the k-mer groups of a narrow matrix hold partial counts of the same words: add them plane by plane (full adder), every lane ends with the sum
+        for (uint32_t off = Wp; off < 64; off <<= 1) {
+            uint64_t carry = 0;
+#pragma unroll
+            for (int p = 0; p < BX_PLANES; p++) {
+                if ((uint32_t)p < np) {
+                    const uint64_t a = P[p], b = shfl_xor64(a, off), x = a ^ b;
+                    P[p] = x ^ carry;
+                    carry = (a & b) | (carry & x);
+                }
+            }
+        }
+        // the largest count, from the top plane down: keep the colours that have the bit whenever any has it
+        uint64_t cand = 0;
+        if (grp == 0 && active) cand = wi * 64 + 64 <= nc ? ~(uint64_t)0 : (wi * 64 >= nc ? 0 : (((uint64_t)1 << (nc - wi * 64)) - 1));
+        uint32_t bh = 0;
+#pragma unroll
+        for (int p = BX_PLANES - 1; p >= 0; p--) {
+            if ((uint32_t)p < np) {
+                const uint64_t tt = cand & P[p];
+                if (__ballot(tt != 0) != 0) { cand = tt; bh |= 1u << p; }
+            }
+        }
+        if (bh > best_h) {                 // (a later chunk holds larger colours: it only wins with more hits)
+            const uint64_t bal = __ballot(cand != 0);
+            const uint32_t fl = (uint32_t)__builtin_ctzll(bal);
+            const uint32_t mine = cand ? (uint32_t)(wi * 64) + (uint32_t)__builtin_ctzll(cand) : 0u;
+            best_c = (uint32_t)__shfl((int)mine, (int)fl);
+            best_h = bh;
+        }
+        if (dense && grp == 0 && active) {
+            for (uint32_t b = 0; b < 64; b++) {
+                const uint64_t col = wi * 64 + b;
+                if (col >= nc) break;
+                uint32_t cnt = 0;
+#pragma unroll
+                for (int p = 0; p < BX_PLANES; p++)
+                    if ((uint32_t)p < np) cnt |= (uint32_t)((P[p] >> b) & 1u) << p;
+                dense[read * nc + col] = cnt;
+            }
+        }
+    }
+    if (lane == 0) { out_n[read] = n; out_col[read] = best_c; out_hits[read] = best_h; }
+}
+
+__global__ void k_bigsi_classify(uint64_t n_reads, const uint32_t *__restrict__ nk, const uint32_t *__restrict__ col, const uint32_t *__restrict__ hits,
+                                 const uint64_t *__restrict__ tc, uint64_t nc, uint64_t B, uint32_t h, double fp, double *__restrict__ tail,
+                                 uint8_t *__restrict__ accept)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const uint32_t c = col[r], x0 = hits[r];
+    const double t = bigsi_tail(c < nc ? tc[c] : 0, B, h, nk[r], x0);
+    tail[r] = t;
+    accept[r] = (x0 > 0 && t < fp) ? 1 : 0;
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------------------
+static inline int base_code(uint8_t ch)
+{
+    switch (ch) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return -1;
+    }
+}
+// the segments of text bytes [b, e): f(begin offset, bases) for every maximal run of valid bases; line breaks are skipped, and `code` receives every valid base
+template <class Seg, class Base>
+static void split_text(const uint8_t *text, const uint8_t *qual, uint64_t b, uint64_t e, uint32_t min_phred, const Seg &seg, const Base &base)
+{
+    uint64_t begin = 0, len = 0;
+    for (uint64_t i = b; i < e; i++) {
+        const uint8_t ch = text[i];
+        if (ch == '\n' || ch == '\r') continue;
+        const int code = base_code(ch);
+        const bool ok = code >= 0 && (!qual || (int)qual[i] - 33 >= (int)min_phred);
+        if (ok) { if (len == 0) begin = i; len++; base(code); }
+        else if (len) { seg(begin, len); len = 0; }
+    }
+    if (len) seg(begin, len);
+}
+// host text -> packed segments (each at least k bases) on the device, grouped as the caller grouped its records
+struct Staged {
+    PoolBuf seq, rs, rl, go;
+    uint64_t seq_bytes = 0, n_seg = 0;
+    explicit Staged(gs_ctx *c) : seq(c, SL_BIGSI_SEQ), rs(c, SL_BIGSI_REC_START), rl(c, SL_BIGSI_REC_LEN), go(c, SL_BIGSI_GROUP_OFF) {}
+};
+static int stage_text(gs_ctx *c, uint32_t k, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end,
+                      uint64_t n_rec, const uint64_t *group_off, uint64_t n_groups, Staged &s)
+{
+    GS_REQUIRE(group_off[n_groups] <= n_rec, GS_ERR_INVALID, "the record offsets exceed n_rec");
+    const uint8_t *tx = (const uint8_t *)text, *ql = (const uint8_t *)qual;
+    std::vector<uint8_t> packed;
+    std::vector<uint64_t> start, len, goff(n_groups + 1);
+    uint64_t nb = 0;                       // bases packed so far
+    for (uint64_t g = 0; g < n_groups; g++) {
+        goff[g] = start.size();
+        GS_REQUIRE(group_off[g] <= group_off[g + 1], GS_ERR_INVALID, "the record offsets do not ascend");
+        for (uint64_t r = group_off[g]; r < group_off[g + 1]; r++) {
+            GS_REQUIRE(rec_begin[r] <= rec_end[r], GS_ERR_INVALID, "record %llu ends before it begins", (unsigned long long)r);
+            uint64_t seg0 = nb;
+            split_text(tx, ql, rec_begin[r], rec_end[r], min_phred,
+                       [&](uint64_t, uint64_t l) {
+                           if (l >= k) { start.push_back(seg0); len.push_back(l); seg0 = nb; }
+                           else { nb = seg0; packed.resize((nb + 3) / 4); if (nb & 3) packed.back() &= (uint8_t)(0xFF00u >> (2 * (nb & 3))); }   // too short: take it back
+                       },
+                       [&](int code) {
+                           if ((nb & 3) == 0) packed.push_back(0);
+                           packed[nb >> 2] |= (uint8_t)(code << (6 - 2 * (nb & 3)));
+                           nb++;
+                       });
+        }
+    }
+    goff[n_groups] = start.size();
+    s.n_seg = start.size();
+    s.seq_bytes = round_up(packed.size(), 8) + 8;
+    packed.resize(s.seq_bytes, 0);
+    int rc;
+    if ((rc = s.seq.alloc(s.seq_bytes)) || (rc = s.rs.alloc(8 * (s.n_seg + 1))) || (rc = s.rl.alloc(8 * (s.n_seg + 1))) || (rc = s.go.alloc(8 * (n_groups + 1)))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(s.seq.p, packed.data(), s.seq_bytes, hipMemcpyHostToDevice, c->stream));
+    if (s.n_seg) {
+        GS_HIP_CHECK(hipMemcpyAsync(s.rs.p, start.data(), 8 * s.n_seg, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(s.rl.p, len.data(), 8 * s.n_seg, hipMemcpyHostToDevice, c->stream));
+    }
+    GS_HIP_CHECK(hipMemcpyAsync(s.go.p, goff.data(), 8 * (n_groups + 1), hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));      // the vectors go out of scope
+    return GS_OK;
+}
+
+static int bigsi_alloc(gs_ctx *c, const gs_bigsi_params *prm, uint64_t cap, gs_bigsi **out)
+{
+    int rc = gs_bigsi_check_params(prm);
+    if (rc) return rc;
+    GS_REQUIRE(c && out, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(cap >= 1 && cap < ((uint64_t)1 << 32), GS_ERR_INVALID, "colour capacity %llu out of range", (unsigned long long)cap);
+    GS_CTX_LOCK(c);
+    gs_bigsi *bx = new gs_bigsi();
+    bx->c = c; bx->prm = *prm; bx->cap = cap; bx->W = (cap + 63) / 64;
+    const uint64_t words = prm->bloom_size * bx->W;
+    if (words >= ((uint64_t)1 << 58) || (rc = bx->M.alloc(words * 8)) || (rc = bx->tc.alloc(cap * 8)) || (rc = bx->nk.alloc(cap * 8))) {
+        if (!rc) { set_error("a matrix of %llu rows x %llu words does not fit", (unsigned long long)prm->bloom_size, (unsigned long long)bx->W); rc = GS_ERR_HIP; }
+        delete bx;
+        return rc;
+    }
+    hipError_t e = hipMemsetAsync(bx->M.p, 0, words * 8, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bx->tc.p, 0, cap * 8, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(bx->nk.p, 0, cap * 8, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { set_error("zeroing the matrix failed: %s", hipGetErrorString(e)); delete bx; return GS_ERR_HIP; }
+    *out = bx;
+    return GS_OK;
+}
+
+static int write_all(FILE *f, const void *p, size_t n) { return n == 0 || fwrite(p, 1, n, f) == n ? 0 : -1; }
+static int read_all(FILE *f, void *p, size_t n) { return n == 0 || fread(p, 1, n, f) == n ? 0 : -1; }
+static const char BX_MAGIC[8] = {'G', 'S', 'B', 'I', 'G', 'S', 'I', '1'};
+constexpr uint32_t BX_VERSION = 1;
+
+}  // namespace gs
+
+extern "C" {
+
+int gs_bigsi_check_params(const gs_bigsi_params *p)
+{
+    GS_REQUIRE(p, GS_ERR_INVALID, "null parameters");
+    GS_REQUIRE(p->k >= 1 && p->k <= GS_BIGSI_KMAX, GS_ERR_INVALID, "bigsig: k = %u outside 1..32", p->k);
+    GS_REQUIRE(p->num_hash >= 1 && p->num_hash <= GS_BIGSI_HMAX, GS_ERR_INVALID, "bigsig: num_hash = %u outside 1..16", p->num_hash);
+    GS_REQUIRE(p->bloom_size >= 1 && p->bloom_size < GS_BIGSI_BMAX, GS_ERR_INVALID, "bigsig: bloom_size = %llu outside 1..2^40-1", (unsigned long long)p->bloom_size);
+    GS_REQUIRE(p->data_t == GS_DATA_DNA || p->data_t == GS_DATA_DNA_FWD, GS_ERR_INVALID, "bigsig: data type %u is not DNA", p->data_t);
+    GS_REQUIRE(p->minimizer == 0, GS_ERR_UNSUPPORTED, "bigsig: the minimizer mode (-m) is not implemented");
+    GS_REQUIRE(p->coverage_filter == 0, GS_ERR_UNSUPPORTED, "bigsig: the coverage filter (-f) is not implemented");
+    return GS_OK;
+}
+
+int gs_bigsi_create(gs_ctx *c, const gs_bigsi_params *prm, uint64_t colour_capacity, gs_bigsi **out) { return gs::bigsi_alloc(c, prm, colour_capacity, out); }
+
+void gs_bigsi_free(gs_bigsi *bx)
+{
+    if (!bx) return;
+    { GS_CTX_LOCK(bx->c); (void)hipStreamSynchronize(bx->c->stream); }
+    delete bx;
+}
+
+int gs_bigsi_info(gs_bigsi *bx, gs_bigsi_desc *out)
+{
+    GS_REQUIRE(bx && out, GS_ERR_INVALID, "null argument");
+    out->prm = bx->prm; out->n_colours = bx->n; out->colour_capacity = bx->cap; out->row_words = bx->W;
+    return GS_OK;
+}
+
+int gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                           const uint64_t *genome_rec_off, uint64_t n_genomes)
+{
+    using namespace gs;
+    GS_REQUIRE(bx && (n_genomes == 0 || (seq && rec_start && rec_len && genome_rec_off)), GS_ERR_INVALID, "null argument");
+    if (n_genomes == 0) return GS_OK;
+    GS_REQUIRE(bx->n + n_genomes <= bx->cap, GS_ERR_STATE, "bigsig: %llu more genomes do not fit the colour capacity %llu (%llu used)",
+               (unsigned long long)n_genomes, (unsigned long long)bx->cap, (unsigned long long)bx->n);
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    const uint64_t B = bx->prm.bloom_size, pitch = bitmap_pitch(B);
+    const uint32_t kq = bigsi_kq(bx->prm);
+    GS_REQUIRE((B + TR_ROWS - 1) / TR_ROWS < ((uint64_t)1 << 31), GS_ERR_UNSUPPORTED, "bigsig: bloom_size too large for the transpose grid");
+    PoolBuf upre(c, SL_BIGSI_REC_UNITS), gunits(c, SL_BIGSI_GENOME_UNITS), bmb(c, SL_BIGSI_BITMAP);
+    int rc;
+    if ((rc = upre.alloc(8 * (n_rec + 1))) || (rc = gunits.alloc(8 * n_genomes))) return rc;
+    hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len, genome_rec_off, n_genomes, bx->prm.k,
+                       upre.as<uint64_t>(), gunits.as<uint64_t>());
+    GS_HIP_CHECK(hipGetLastError());
+    // colours of a block: whole words of 64 up to BX_BLOCK, fewer when the bitmaps (bloom_size bits each) would take more than a quarter of the free memory
+    size_t fr = 0, tot = 0;
+    GS_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    uint64_t fit = std::max<uint64_t>((fr / 4 + bmb.bytes) / (pitch * 4), 1);
+    {   // what the slot already holds counts as free
+        ScratchPool *pool = (ScratchPool *)c->scratch_pool;
+        if (pool) fit = std::max<uint64_t>(fit, pool->b[SL_BIGSI_BITMAP].bytes / (pitch * 4));
+    }
+    const uint64_t blk = fit >= BX_BLOCK ? BX_BLOCK : (fit >= 64 ? fit / 64 * 64 : fit);
+    const uint64_t avg_units = seq_bytes / 8 / n_genomes + 1;
+    c->last_sketch[0] = 0; c->last_sketch[1] = 0; c->last_sketch[2] = 0; c->last_sketch[3] = 0;
+    for (uint64_t g0 = 0; g0 < n_genomes;) {
+        const uint64_t c0 = bx->n + g0;                                             // first colour of the block
+        const uint64_t cend = blk >= 64 ? c0 / 64 * 64 + blk : std::min(c0 + blk, c0 / 64 * 64 + 64);
+        const uint64_t ng = std::min(n_genomes - g0, cend - c0);
+        if ((rc = bmb.alloc(ng * pitch * 4))) return rc;
+        GS_HIP_CHECK(hipMemsetAsync(bmb.p, 0, ng * pitch * 4, c->stream));
+        // few genomes: several workgroups each, as the sketchers do (min_geom, gs_sketch.hip)
+        uint32_t parts = (uint32_t)((2 * (uint64_t)c->n_cu + ng - 1) / ng);
+        const uint64_t maxp = (avg_units + SK_THREADS - 1) / SK_THREADS;
+        if (parts > maxp) parts = (uint32_t)maxp;
+        if (parts < 1) parts = 1;
+        c->last_sketch[2] = parts; c->last_sketch[3]++;
+        hipLaunchKernelGGL(k_bigsi_fill, dim3(parts, (uint32_t)ng), dim3(SK_THREADS), 0, c->stream, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(),
+                           genome_rec_off + g0, gunits.as<uint64_t>() + g0, kq, B, bx->prm.num_hash, bmb.as<uint32_t>(), pitch);
+        GS_HIP_CHECK(hipGetLastError());
+        const uint32_t slices = (uint32_t)std::min<uint64_t>((pitch + 256 * 16 - 1) / (256 * 16), 1024);
+        hipLaunchKernelGGL(k_bigsi_popcount, dim3(slices, (uint32_t)ng), dim3(256), 0, c->stream, bmb.as<uint32_t>(), pitch, rec_len, genome_rec_off + g0, bx->prm.k,
+                           bx->tc.as<unsigned long long>() + c0, bx->nk.as<unsigned long long>() + c0);
+        GS_HIP_CHECK(hipGetLastError());
+        const uint64_t w0 = c0 / 64;
+        const uint32_t cshift = (uint32_t)(c0 & 63), nw = (uint32_t)((cshift + ng + 63) / 64);
+        hipLaunchKernelGGL(k_bigsi_transpose, dim3((uint32_t)((B + TR_ROWS - 1) / TR_ROWS)), dim3(256), 0, c->stream, bmb.as<uint32_t>(), pitch, (uint32_t)ng, cshift, B,
+                           bx->M.as<uint64_t>(), bx->W, w0, nw, cshift != 0 ? 1 : 0);
+        GS_HIP_CHECK(hipGetLastError());
+        g0 += ng;
+    }
+    bx->n += n_genomes;
+    if (!bx->names.empty()) bx->names.resize(bx->n);
+    return GS_OK;
+}
+
+int gs_bigsi_add_batch(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end, uint64_t n_rec,
+                       const uint64_t *genome_rec_off, uint64_t n_genomes)
+{
+    using namespace gs;
+    GS_REQUIRE(bx && (n_genomes == 0 || ((text || n_rec == 0) && genome_rec_off && (n_rec == 0 || (rec_begin && rec_end)))), GS_ERR_INVALID, "null argument");
+    if (n_genomes == 0) return GS_OK;
+    GS_REQUIRE(bx->n + n_genomes <= bx->cap, GS_ERR_STATE, "bigsig: %llu more genomes do not fit the colour capacity %llu (%llu used)",
+               (unsigned long long)n_genomes, (unsigned long long)bx->cap, (unsigned long long)bx->n);
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    Staged s(c);
+    int rc = stage_text(c, bx->prm.k, text, qual, min_phred, rec_begin, rec_end, n_rec, genome_rec_off, n_genomes, s);
+    if (rc) return rc;
+    rc = gs_bigsi_add_batch_dev(bx, s.seq.p, s.seq_bytes, s.rs.as<uint64_t>(), s.rl.as<uint64_t>(), s.n_seg, s.go.as<uint64_t>(), n_genomes);
+    if (rc) return rc;
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int gs_bigsi_bits_set(gs_bigsi *bx, uint64_t first, uint64_t n, uint64_t *t_out, uint64_t *nk_out)
+{
+    GS_REQUIRE(bx, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(first + n <= bx->n, GS_ERR_INVALID, "colours [%llu, %llu) exceed the %llu added", (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)bx->n);
+    if (n == 0) return GS_OK;
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    if (t_out) GS_HIP_CHECK(hipMemcpyAsync(t_out, bx->tc.as<uint64_t>() + first, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    if (nk_out) GS_HIP_CHECK(hipMemcpyAsync(nk_out, bx->nk.as<uint64_t>() + first, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int gs_bigsi_rows(gs_bigsi *bx, const uint64_t *rows, uint64_t n, uint64_t *words_out)
+{
+    using namespace gs;
+    GS_REQUIRE(bx && (n == 0 || (rows && words_out)), GS_ERR_INVALID, "null argument");
+    if (n == 0) return GS_OK;
+    for (uint64_t i = 0; i < n; i++) GS_REQUIRE(rows[i] < bx->prm.bloom_size, GS_ERR_INVALID, "row %llu outside the matrix", (unsigned long long)rows[i]);
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    PoolBuf dl(c, SL_BIGSI_ROW_LIST), dw(c, SL_BIGSI_ROW_WORDS);
+    int rc;
+    if ((rc = dl.alloc(8 * n)) || (rc = dw.alloc(8 * n * bx->W))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(dl.p, rows, 8 * n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_bigsi_gather_rows, dim3((uint32_t)std::min<uint64_t>((n * bx->W + 255) / 256, 65536)), dim3(256), 0, c->stream, bx->M.as<uint64_t>(), bx->W,
+                       dl.as<uint64_t>(), n, dw.as<uint64_t>());
+    GS_HIP_CHECK(hipGetLastError());
+    GS_HIP_CHECK(hipMemcpyAsync(words_out, dw.p, 8 * n * bx->W, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int gs_bigsi_query_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                       const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t *n_kmers, uint32_t *best_colour, uint32_t *best_hits,
+                       uint32_t *counts)
+{
+    using namespace gs;
+    (void)seq_bytes; (void)n_rec;
+    GS_REQUIRE(bx, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(down_sample >= 1, GS_ERR_INVALID, "bigsig: down_sample = 0");
+    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
+    GS_REQUIRE(n_reads == 0 || (seq && rec_start && rec_len && read_rec_off && n_kmers && best_colour && best_hits), GS_ERR_INVALID, "null argument");
+    if (n_reads == 0) return GS_OK;
+    GS_REQUIRE(n_reads < ((uint64_t)1 << 33), GS_ERR_INVALID, "too many reads in one batch");
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    const uint32_t h = bx->prm.num_hash, hb = h < 4 ? h : 4;
+    const dim3 grid((uint32_t)((n_reads + 3) / 4)), block(256);
+#define GS_BX_LAUNCH(HB)                                                                                                                                     \
+    do {                                                                                                                                                     \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_SHORT>), grid, block, 0, c->stream, (const uint64_t *)seq, rec_start, rec_len, read_rec_off, n_reads, \
+                           bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n, n_kmers, best_colour, best_hits, counts); \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_LONG>), grid, block, 0, c->stream, (const uint64_t *)seq, rec_start, rec_len, read_rec_off, n_reads, \
+                           bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n, n_kmers, best_colour, best_hits, counts); \
+    } while (0)
+    if (hb == 1) GS_BX_LAUNCH(1);
+    else if (hb == 2) GS_BX_LAUNCH(2);
+    else if (hb == 3) GS_BX_LAUNCH(3);
+    else GS_BX_LAUNCH(4);
+#undef GS_BX_LAUNCH
+    GS_HIP_CHECK(hipGetLastError());
+    return GS_OK;
+}
+
+int gs_bigsi_query(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end, uint64_t n_rec,
+                   const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t *n_kmers, uint32_t *best_colour, uint32_t *best_hits,
+                   uint32_t *counts)
+{
+    using namespace gs;
+    GS_REQUIRE(bx, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(down_sample >= 1, GS_ERR_INVALID, "bigsig: down_sample = 0");
+    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
+    GS_REQUIRE(n_reads == 0 || ((text || n_rec == 0) && read_rec_off && (n_rec == 0 || (rec_begin && rec_end)) && n_kmers && best_colour && best_hits), GS_ERR_INVALID,
+               "null argument");
+    if (n_reads == 0) return GS_OK;
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    Staged s(c);
+    int rc = stage_text(c, bx->prm.k, text, qual, min_phred, rec_begin, rec_end, n_rec, read_rec_off, n_reads, s);
+    if (rc) return rc;
+    PoolBuf dn(c, SL_BIGSI_OUT_N), dc(c, SL_BIGSI_OUT_COLOUR), dh(c, SL_BIGSI_OUT_HITS), dd(c, SL_BIGSI_OUT_COUNTS);
+    if ((rc = dn.alloc(4 * n_reads)) || (rc = dc.alloc(4 * n_reads)) || (rc = dh.alloc(4 * n_reads))) return rc;
+    if (counts && (rc = dd.alloc(4 * n_reads * bx->n))) return rc;
+    rc = gs_bigsi_query_dev(bx, s.seq.p, s.seq_bytes, s.rs.as<uint64_t>(), s.rl.as<uint64_t>(), s.n_seg, s.go.as<uint64_t>(), n_reads, down_sample, dn.as<uint32_t>(),
+                            dc.as<uint32_t>(), dh.as<uint32_t>(), counts ? dd.as<uint32_t>() : nullptr);
+    if (rc) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(n_kmers, dn.p, 4 * n_reads, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(best_colour, dc.p, 4 * n_reads, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(best_hits, dh.p, 4 * n_reads, hipMemcpyDeviceToHost, c->stream));
+    if (counts) GS_HIP_CHECK(hipMemcpyAsync(counts, dd.p, 4 * n_reads * bx->n, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int gs_bigsi_classify_dev(gs_bigsi *bx, uint64_t n_reads, const uint32_t *n_kmers, const uint32_t *best_colour, const uint32_t *best_hits, double fp_correct,
+                          double *tail, uint8_t *accept)
+{
+    using namespace gs;
+    GS_REQUIRE(bx && (n_reads == 0 || (n_kmers && best_colour && best_hits && tail && accept)), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
+    if (n_reads == 0) return GS_OK;
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    hipLaunchKernelGGL(k_bigsi_classify, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, c->stream, n_reads, n_kmers, best_colour, best_hits, bx->tc.as<uint64_t>(),
+                       bx->n, bx->prm.bloom_size, bx->prm.num_hash, fp_correct, tail, accept);
+    GS_HIP_CHECK(hipGetLastError());
+    return GS_OK;
+}
+
+int gs_bigsi_set_accessions(gs_bigsi *bx, const char *const *names, uint64_t n)
+{
+    GS_REQUIRE(bx && (n == 0 || names), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n == bx->n, GS_ERR_INVALID, "%llu accessions for %llu colours", (unsigned long long)n, (unsigned long long)bx->n);
+    std::vector<std::string> v(n);
+    for (uint64_t i = 0; i < n; i++) { GS_REQUIRE(names[i], GS_ERR_INVALID, "null accession"); v[i] = names[i]; }
+    bx->names.swap(v);
+    return GS_OK;
+}
+
+int gs_bigsi_accessions(gs_bigsi *bx, char *buf, uint64_t cap_bytes, uint64_t *bytes_out)
+{
+    GS_REQUIRE(bx && bytes_out, GS_ERR_INVALID, "null argument");
+    uint64_t need = 0;
+    for (uint64_t i = 0; i < bx->n; i++) need += (i < bx->names.size() ? bx->names[i].size() : 0) + 1;
+    *bytes_out = need;
+    if (!buf) return GS_OK;
+    GS_REQUIRE(cap_bytes >= need, GS_ERR_INVALID, "the buffer holds %llu of %llu bytes", (unsigned long long)cap_bytes, (unsigned long long)need);
+    char *o = buf;
+    for (uint64_t i = 0; i < bx->n; i++) {
+        if (i < bx->names.size()) { memcpy(o, bx->names[i].data(), bx->names[i].size()); o += bx->names[i].size(); }
+        *o++ = 0;
+    }
+    return GS_OK;
+}
+
+// magic, version, k, num_hash, data_t (u32 each), bloom_size, n_colours (u64), per colour: u32 length + accession bytes, t_c[n], nk_c[n] (u64), then
+// bloom_size rows of ceil(n_colours / 64) u64 words
+int gs_bigsi_save(gs_bigsi *bx, const char *path)
+{
+    using namespace gs;
+    GS_REQUIRE(bx && path, GS_ERR_INVALID, "null argument");
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    FILE *f = fopen(path, "wb");
+    GS_REQUIRE(f, GS_ERR_IO, "cannot write %s: %s", path, strerror(errno));
+    const uint64_t n = bx->n, B = bx->prm.bloom_size, wu = (n + 63) / 64;
+    const uint32_t head[4] = {BX_VERSION, bx->prm.k, bx->prm.num_hash, bx->prm.data_t};
+    int bad = write_all(f, BX_MAGIC, 8) | write_all(f, head, 16) | write_all(f, &B, 8) | write_all(f, &n, 8);
+    for (uint64_t i = 0; i < n && !bad; i++) {
+        const std::string nm = i < bx->names.size() ? bx->names[i] : std::string();
+        const uint32_t l = (uint32_t)nm.size();
+        bad |= write_all(f, &l, 4) | write_all(f, nm.data(), l);
+    }
+    std::vector<uint64_t> t(n), q(n);
+    int rc = n ? gs_bigsi_bits_set(bx, 0, n, t.data(), q.data()) : GS_OK;
+    if (!rc) bad |= write_all(f, t.data(), 8 * n) | write_all(f, q.data(), 8 * n);
+    const uint64_t chunk = std::max<uint64_t>(((uint64_t)64 << 20) / (8 * std::max<uint64_t>(wu, 1)), 1);
+    std::vector<uint64_t> buf(wu ? chunk * wu : 0);
+    for (uint64_t r = 0; r < B && wu && !bad && !rc; r += chunk) {
+        const uint64_t nr = std::min(chunk, B - r);
+        if (hipMemcpy2D(buf.data(), wu * 8, bx->M.as<uint64_t>() + r * bx->W, bx->W * 8, wu * 8, nr, hipMemcpyDeviceToHost) != hipSuccess) {
+            set_error("reading the matrix back failed"); rc = GS_ERR_HIP;
+        }
+        else bad |= write_all(f, buf.data(), nr * wu * 8);
+    }
+    if (fclose(f) != 0) bad = 1;
+    if (rc) return rc;
+    GS_REQUIRE(!bad, GS_ERR_IO, "writing %s failed", path);
+    return GS_OK;
+}
+
+int gs_bigsi_load(gs_ctx *c, const char *path, uint64_t colour_capacity, gs_bigsi **out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && path && out, GS_ERR_INVALID, "null argument");
+    FILE *f = fopen(path, "rb");
+    GS_REQUIRE(f, GS_ERR_IO, "cannot read %s: %s", path, strerror(errno));
+    char magic[8]; uint32_t head[4]; uint64_t B = 0, n = 0;
+    int bad = read_all(f, magic, 8) | read_all(f, head, 16) | read_all(f, &B, 8) | read_all(f, &n, 8);
+    if (bad || memcmp(magic, BX_MAGIC, 8) != 0 || head[0] != BX_VERSION || n >= ((uint64_t)1 << 32)) {
+        fclose(f);
+        GS_REQUIRE(false, GS_ERR_IO, "%s is not a bigsig index of this library (version %u)", path, BX_VERSION);
+    }
+    gs_bigsi_params prm{};
+    prm.k = head[1]; prm.num_hash = head[2]; prm.data_t = head[3]; prm.bloom_size = B;
+    std::vector<std::string> names(n);
+    for (uint64_t i = 0; i < n && !bad; i++) {
+        uint32_t l = 0;
+        bad |= read_all(f, &l, 4);
+        if (!bad && l > (1u << 20)) bad = 1;
+        if (!bad) { names[i].resize(l); bad |= read_all(f, &names[i][0], l); }
+    }
+    std::vector<uint64_t> t(n), q(n);
+    bad |= read_all(f, t.data(), 8 * n) | read_all(f, q.data(), 8 * n);
+    if (bad) { fclose(f); GS_REQUIRE(false, GS_ERR_IO, "%s is cut short", path); }
+    const uint64_t cap = std::max<uint64_t>(std::max(colour_capacity, n), 1);
+    gs_bigsi *bx = nullptr;
+    int rc = bigsi_alloc(c, &prm, cap, &bx);
+    if (rc) { fclose(f); return rc; }
+    GS_CTX_LOCK(c);
+    const uint64_t wu = (n + 63) / 64;
+    const uint64_t chunk = std::max<uint64_t>(((uint64_t)64 << 20) / (8 * std::max<uint64_t>(wu, 1)), 1);
+    std::vector<uint64_t> buf(wu ? chunk * wu : 0);
+    hipError_t e = hipSuccess;
+    if (n) {
+        e = hipMemcpy(bx->tc.p, t.data(), 8 * n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(bx->nk.p, q.data(), 8 * n, hipMemcpyHostToDevice);
+    }
+    for (uint64_t r = 0; r < B && wu && !bad && e == hipSuccess; r += chunk) {
+        const uint64_t nr = std::min(chunk, B - r);
+        bad |= read_all(f, buf.data(), nr * wu * 8);
+        if (!bad) e = hipMemcpy2D(bx->M.as<uint64_t>() + r * bx->W, bx->W * 8, buf.data(), wu * 8, wu * 8, nr, hipMemcpyHostToDevice);
+    }
+    fclose(f);
+    if (bad || e != hipSuccess) {
+        delete bx;
+        GS_REQUIRE(!bad, GS_ERR_IO, "%s is cut short", path);
+        GS_REQUIRE(false, GS_ERR_HIP, "loading the matrix failed: %s", hipGetErrorString(e));
+    }
+    bx->n = n;
+    bool any = false;
+    for (const std::string &s : names) any = any || !s.empty();
+    if (any) bx->names.swap(names);
+    *out = bx;
+    return GS_OK;
+}
+
+int gs_bigsi_positions(uint64_t v, uint32_t num_hash, uint64_t bloom_size, uint64_t *pos_out)
+{
+    GS_REQUIRE(pos_out && num_hash >= 1 && num_hash <= GS_BIGSI_HMAX && bloom_size >= 1 && bloom_size < GS_BIGSI_BMAX, GS_ERR_INVALID, "bigsig: parameter out of range");
+    uint64_t h1, st;
+    gs::bigsi_hash(v, h1, st);
+    for (uint32_t i = 0; i < num_hash; i++) pos_out[i] = gs::bigsi_pos(h1, st, i, bloom_size);
+    return GS_OK;
+}
+
+int gs_bigsi_split(const void *text, const void *qual, uint64_t n, uint32_t min_phred, uint64_t min_len, uint64_t cap, uint64_t *seg_begin, uint64_t *seg_len,
+                   uint64_t *n_out)
+{
+    GS_REQUIRE((text || n == 0) && n_out, GS_ERR_INVALID, "null argument");
+    uint64_t cnt = 0;
+    gs::split_text((const uint8_t *)text, (const uint8_t *)qual, 0, n, min_phred,
+                   [&](uint64_t b, uint64_t l) {
+                       if (l < min_len) return;
+                       if (cnt < cap && seg_begin && seg_len) { seg_begin[cnt] = b; seg_len[cnt] = l; }
+                       cnt++;
+                   },
+                   [](int) {});
+    *n_out = cnt;
+    return GS_OK;
+}
+
+double gs_bigsi_tail(uint64_t t_c, uint64_t bloom_size, uint32_t num_hash, uint32_t n_kmers, uint32_t best_hits)
+{
+    return gs::bigsi_tail(t_c, bloom_size, num_hash, n_kmers, best_hits);
+}
+
+int gs_bigsig_write_reads(const char *prefix, const char *const *accessions, uint64_t n_colours, const char *const *read_ids, uint64_t n_reads,
+                          const uint32_t *best_colour, const uint32_t *best_hits, const uint32_t *n_kmers, const uint8_t *accept)
+{
+    GS_REQUIRE(prefix && (n_colours == 0 || accessions) && (n_reads == 0 || (read_ids && best_colour && best_hits && n_kmers && accept)), GS_ERR_INVALID, "null argument");
+    for (uint64_t r = 0; r < n_reads; r++)
+        GS_REQUIRE(best_hits[r] == 0 || best_colour[r] < n_colours, GS_ERR_INVALID, "read %llu names colour %u of %llu", (unsigned long long)r, best_colour[r], (unsigned long long)n_colours);
+    const std::string p(prefix);
+    FILE *f = fopen((p + "_reads.txt").c_str(), "wb");
+    GS_REQUIRE(f, GS_ERR_IO, "cannot write %s_reads.txt: %s", prefix, strerror(errno));
+    std::vector<uint64_t> per(n_colours, 0);
+    uint64_t rejected = 0, no_hits = 0;
+    int bad = 0;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const bool hit = best_hits[r] > 0, ok = hit && accept[r];
+        if (!hit) no_hits++;
+        else if (ok) per[best_colour[r]]++;
+        else rejected++;
+        bad |= fprintf(f, "%s\t%s\t%u\t%u\t%s\n", read_ids[r], hit ? accessions[best_colour[r]] : "no_hits", best_hits[r], n_kmers[r], ok ? "accept" : "reject") < 0;
+    }
+    if (fclose(f) != 0) bad = 1;
+    GS_REQUIRE(!bad, GS_ERR_IO, "writing %s_reads.txt failed", prefix);
+    std::vector<uint64_t> order;
+    for (uint64_t c = 0; c < n_colours; c++) if (per[c]) order.push_back(c);
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+        if (per[a] != per[b]) return per[a] > per[b];
+        const int s = strcmp(accessions[a], accessions[b]);
+        return s != 0 ? s < 0 : a < b;
+    });
+    f = fopen((p + "_counts.txt").c_str(), "wb");
+    GS_REQUIRE(f, GS_ERR_IO, "cannot write %s_counts.txt: %s", prefix, strerror(errno));
+    for (uint64_t c : order) bad |= fprintf(f, "%s\t%llu\n", accessions[c], (unsigned long long)per[c]) < 0;
+    bad |= fprintf(f, "reject\t%llu\nno_hits\t%llu\n", (unsigned long long)rejected, (unsigned long long)no_hits) < 0;
+    if (fclose(f) != 0) bad = 1;
+    GS_REQUIRE(!bad, GS_ERR_IO, "writing %s_counts.txt failed", prefix);
+    return GS_OK;
+}
+
+}  // extern "C"

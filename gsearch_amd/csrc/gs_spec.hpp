@@ -379,4 +379,41 @@ GS_HD uint64_t cluster_hash(uint64_t seed, uint32_t r, uint64_t i) { return spli
 GS_HD bool cluster_keep0(uint64_t h, uint64_t n, uint64_t t0) { return (h >> 32) * n < (t0 << 32); }
 GS_HD bool cluster_keep1(uint64_t h, uint64_t D, uint64_t t1, uint32_t d0) { return (h >> 40) * D < ((t1 * d0) << 24); }
 
+// ---- SPEC 11: bigsig (binaux/src/bin/bigsig.rs) - row positions of a k-mer in the bit-sliced Bloom index and the significance of a read's best hit.
+// [CHOICE] (the `bigsig` crate's hash and test are not vendored): every constant and step lives here
+#define GS_BIGSI_KMAX 32u                // 1 <= k <= 32 (15 accepted)
+#define GS_BIGSI_HMAX 16u                // 1 <= num_hash <= 16
+#define GS_BIGSI_BMAX (1ULL << 40)       // 1 <= bloom_size < 2^40
+#define GS_BIGSI_TAIL_CUT 0x1.0p-60      // the tail sum stops at a term below tail x 2^-60
+// h1 and the odd step of the double hashing: the first two SplitMix64 outputs from state fx64(v), as hmh_update
+GS_HD void bigsi_hash(uint64_t v, uint64_t &h1, uint64_t &step)
+{
+    const uint64_t x = fx64(v);
+    h1 = splitmix_mix(x + GS_GAMMA);
+    step = splitmix_mix(x + 2 * GS_GAMMA) | 1;
+}
+GS_HD uint64_t bigsi_pos(uint64_t h1, uint64_t step, uint32_t i, uint64_t B) { return mulhi64(h1 + (uint64_t)i * step, B); }
+// P(X >= x0), X ~ Binomial(n, p), p = (t_c / B)^h: each line one IEEE f64 operation per operator, LN / EXP of SPEC 2
+GS_HD double bigsi_tail(uint64_t t_c, uint64_t B, uint32_t h, uint32_t n, uint32_t x0)
+{
+    const double q = (double)t_c / (double)B;
+    double p = q;
+    for (uint32_t i = 1; i < h; i++) p = p * q;
+    if (x0 > n) x0 = n;                   // (hits never exceed the k-mers used)
+    if (x0 == 0) return 1.0;
+    if (p == 0.0) return 0.0;
+    if (p >= 1.0) return 1.0;
+    const double l1 = spec_ln(1.0 - p), lq = spec_ln(p) - l1;
+    double lp = (double)n * l1;
+    for (uint32_t x = 0; x < x0; x++) lp = lp + (spec_ln((double)(n - x) / (double)(x + 1)) + lq);
+    double tail = 0.0;
+    for (uint32_t x = x0;; x++) {
+        const double term = spec_exp(lp);
+        tail = tail + term;
+        if (x >= n || (x > x0 && term < tail * GS_BIGSI_TAIL_CUT)) break;
+        lp = lp + (spec_ln((double)(n - x) / (double)(x + 1)) + lq);
+    }
+    return tail < 1.0 ? tail : 1.0;
+}
+
 }  // namespace gs

@@ -408,6 +408,71 @@ int      gs_index_release_build_scratch(gs_index *);
 int      gs_index_search_stats(gs_index *, uint64_t out[8], int reset);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* bigsig (binaux/src/bin/bigsig.rs): a bit-sliced Bloom index (BIGSI) of reference genomes - bloom_size rows, one column ("colour") per genome in
+ * the order added - and the genome each sequencing read comes from. Arithmetic: SPEC.md 11. A k-mer never contains a non-ACGT base (or, with
+ * quality bytes, a base below min_phred): such a base ends a segment. minimizer / coverage_filter (bigsig's -m and -f) other than 0 are
+ * GS_ERR_UNSUPPORTED. */
+typedef struct gs_bigsi gs_bigsi;
+typedef struct {
+    uint32_t k;                  /* 1..32 (15 accepted) */
+    uint32_t num_hash;           /* 1..16 rows per k-mer */
+    uint64_t bloom_size;         /* rows, 1 <= bloom_size < 2^40, any value */
+    uint32_t data_t;             /* GS_DATA_DNA (canonical k-mers) or GS_DATA_DNA_FWD */
+    uint32_t minimizer;          /* 0 (bigsig -m: GS_ERR_UNSUPPORTED) */
+    uint32_t coverage_filter;    /* 0 (bigsig -f: GS_ERR_UNSUPPORTED) */
+} gs_bigsi_params;
+typedef struct {
+    gs_bigsi_params prm;
+    uint64_t n_colours, colour_capacity;
+    uint64_t row_words;          /* u64 words of a row = ceil(colour_capacity / 64); colour c is bit c & 63 of word c >> 6 */
+} gs_bigsi_desc;
+int    gs_bigsi_check_params(const gs_bigsi_params *prm);
+/* the matrix (bloom_size x row_words u64, zeroed) is allocated here: the colour capacity is fixed */
+int    gs_bigsi_create(gs_ctx *ctx, const gs_bigsi_params *prm, uint64_t colour_capacity, gs_bigsi **out);
+void   gs_bigsi_free(gs_bigsi *bx);
+int    gs_bigsi_info(gs_bigsi *bx, gs_bigsi_desc *out);
+/* n_genomes new colours, in input order; the layout of gs_sketch_batch_dev (2-bit packed, every record free of invalid bases). Past the capacity: GS_ERR_STATE */
+int    gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                              const uint64_t *genome_rec_off_dev, uint64_t n_genomes);
+/* host text: record r = bytes [rec_begin[r], rec_end[r]) of text (line breaks skipped), genome g = records [genome_rec_off[g], genome_rec_off[g+1]).
+ * qual (optional): quality byte of text[i] at qual[i]; a base with qual[i] - 33 < min_phred counts as non-ACGT. The library splits and packs (a host loop). */
+int    gs_bigsi_add_batch(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end,
+                          uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes);
+/* colours [first, first + n): bits set in the column (t_c) and k-mer occurrences fed (nk_c); either output may be NULL */
+int    gs_bigsi_bits_set(gs_bigsi *bx, uint64_t first, uint64_t n, uint64_t *t_out, uint64_t *nk_out);
+/* the named rows -> words_out[n x row_words] (HOST) */
+int    gs_bigsi_rows(gs_bigsi *bx, const uint64_t *rows, uint64_t n, uint64_t *words_out);
+/* read r = records [read_rec_off[r], read_rec_off[r+1]) (the mates of a pair: the records of one read). Of a read's k-mer occurrences in order, those
+ * with running index j, j mod down_sample == 0, are used: n_kmers[r] of them. best_hits[r] = the largest number of used occurrences whose num_hash
+ * rows all hold one colour's bit, best_colour[r] = the smallest colour reaching it (0 when best_hits is 0). counts (optional): n_reads x n_colours u32,
+ * every colour's hits. down_sample = 0: GS_ERR_INVALID; no colour: GS_ERR_STATE. The _dev form queues on the context's stream. */
+int    gs_bigsi_query_dev(gs_bigsi *bx, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                          const uint64_t *read_rec_off_dev, uint64_t n_reads, uint32_t down_sample, uint32_t *n_kmers_dev, uint32_t *best_colour_dev,
+                          uint32_t *best_hits_dev, uint32_t *counts_dev);
+int    gs_bigsi_query(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end, uint64_t n_rec,
+                      const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t *n_kmers, uint32_t *best_colour, uint32_t *best_hits,
+                      uint32_t *counts);
+/* tail[r] = P(X >= best_hits), X ~ Binomial(n_kmers, (t_c / bloom_size)^num_hash) for c = best_colour (SPEC 11); accept[r] = best_hits > 0 and tail < fp_correct */
+int    gs_bigsi_classify_dev(gs_bigsi *bx, uint64_t n_reads, const uint32_t *n_kmers_dev, const uint32_t *best_colour_dev, const uint32_t *best_hits_dev,
+                             double fp_correct, double *tail_dev, uint8_t *accept_dev);
+/* the accessions of the colours (n == n_colours); read back NUL-terminated, back to back: buf NULL to size (*bytes_out) */
+int    gs_bigsi_set_accessions(gs_bigsi *bx, const char *const *names, uint64_t n);
+int    gs_bigsi_accessions(gs_bigsi *bx, char *buf, uint64_t cap_bytes, uint64_t *bytes_out);
+/* own little-endian file (SPEC 11; upstream's .bxi is a bincode of crate types). load: colour_capacity 0 = the file's n_colours */
+int    gs_bigsi_save(gs_bigsi *bx, const char *path);
+int    gs_bigsi_load(gs_ctx *ctx, const char *path, uint64_t colour_capacity, gs_bigsi **out);
+/* host arithmetic of SPEC 11, no device: the num_hash rows of k-mer value v; the segments of a text (begin = offset of the first base, len in bases,
+ * segments shorter than min_len dropped; arrays may be NULL / cap 0 to count only); the tail */
+int    gs_bigsi_positions(uint64_t v, uint32_t num_hash, uint64_t bloom_size, uint64_t *pos_out);
+int    gs_bigsi_split(const void *text, const void *qual, uint64_t n, uint32_t min_phred, uint64_t min_len, uint64_t cap, uint64_t *seg_begin,
+                      uint64_t *seg_len, uint64_t *n_out);
+double gs_bigsi_tail(uint64_t t_c, uint64_t bloom_size, uint32_t num_hash, uint32_t n_kmers, uint32_t best_hits);
+/* `{prefix}_reads.txt`: read_id, accession | no_hits, best_hits, n_kmers, accept | reject, tab-separated, one line per read; `{prefix}_counts.txt`:
+ * accession, reads over the accepted reads (descending by count, then by accession), then a `reject` and a `no_hits` line. Host only. */
+int    gs_bigsig_write_reads(const char *prefix, const char *const *accessions, uint64_t n_colours, const char *const *read_ids, uint64_t n_reads,
+                             const uint32_t *best_colour, const uint32_t *best_hits, const uint32_t *n_kmers, const uint8_t *accept);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* Multi-GPU: one process per GPU, query batches sharded, DB + graph replicated. The path has ONE exchange step - the
  * all-gather of the per-rank top-k blocks - and this is it, over RCCL / xGMI, for hosts that are not Python (the reference's host is
  * Rust; conceptual ancestor: the per-shard loop of scripts/multiple_search.sh:71-107). Bootstrap like NCCL: one rank calls

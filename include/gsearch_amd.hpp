@@ -202,6 +202,78 @@ inline std::vector<double> frac_similarity_qxc(Context &ctx, uint32_t num, const
 }
 inline double aai(double sim, uint32_t k) { return gs_aai(sim, k); }
 
+// bigsig (binaux/src/bin/bigsig.rs; SPEC 11): a bit-sliced Bloom index of genomes - one colour per genome in the order added - and, for every read, the
+// colour with the most k-mer hits and whether that many hits are significant. A genome or a read is a list of records (ASCII text); the mates of a
+// pair are two records of one read.
+struct BigsiHits { std::vector<uint32_t> n_kmers, best_colour, best_hits; std::vector<double> tail; std::vector<uint8_t> accept; };
+class Bigsi {
+public:
+    Bigsi(Context &ctx, uint32_t k, uint32_t num_hash, uint64_t bloom_size, uint64_t colour_capacity, DataType dt = DataType::DNA) : ctx_(&ctx)
+    {
+        const gs_bigsi_params p{k, num_hash, bloom_size, (uint32_t)dt, 0, 0};
+        check(gs_bigsi_create(ctx.get(), &p, colour_capacity, &bx_));
+    }
+    Bigsi(Context &ctx, const std::string &path, uint64_t colour_capacity = 0) : ctx_(&ctx) { check(gs_bigsi_load(ctx.get(), path.c_str(), colour_capacity, &bx_)); }
+    ~Bigsi() { gs_bigsi_free(bx_); }
+    Bigsi(const Bigsi &) = delete;
+    Bigsi &operator=(const Bigsi &) = delete;
+    gs_bigsi *get() const { return bx_; }
+    gs_bigsi_desc info() const { gs_bigsi_desc d; check(gs_bigsi_info(bx_, &d)); return d; }
+    void add_genomes(const std::vector<std::vector<std::string>> &genomes, const std::vector<std::string> &accessions = {})
+    {
+        Text t(genomes);
+        check(gs_bigsi_add_batch(bx_, t.text.data(), nullptr, 0, t.begin.data(), t.end.data(), t.begin.size(), t.off.data(), genomes.size()));
+        if (!accessions.empty()) {
+            names_.insert(names_.end(), accessions.begin(), accessions.end());
+            std::vector<const char *> p;
+            for (const auto &x : names_) p.push_back(x.c_str());
+            check(gs_bigsi_set_accessions(bx_, p.data(), p.size()));
+        }
+    }
+    std::vector<uint64_t> bits_set() const
+    {
+        std::vector<uint64_t> t(info().n_colours);
+        check(gs_bigsi_bits_set(bx_, 0, t.size(), t.data(), nullptr));
+        return t;
+    }
+    // quals: empty, or the quality string of every record; fp_correct: the threshold itself (bigsig passes 10^-p)
+    BigsiHits identify(const std::vector<std::vector<std::string>> &reads, const std::vector<std::vector<std::string>> &quals = {}, uint32_t min_phred = 15,
+                       uint32_t down_sample = 1, double fp_correct = 1e-3) const
+    {
+        Text t(reads), q(quals);
+        const uint64_t n = reads.size();
+        BigsiHits out{std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::vector<double>(n), std::vector<uint8_t>(n)};
+        check(gs_bigsi_query(bx_, t.text.data(), quals.empty() ? nullptr : q.text.data(), min_phred, t.begin.data(), t.end.data(), t.begin.size(), t.off.data(), n,
+                             down_sample, out.n_kmers.data(), out.best_colour.data(), out.best_hits.data(), nullptr));
+        if (n == 0) return out;
+        void *d[5] = {};
+        const size_t bytes[5] = {4 * n, 4 * n, 4 * n, 8 * n, n};
+        for (int i = 0; i < 5; i++) check(gs_dev_alloc(ctx_->get(), bytes[i], &d[i]));
+        check(gs_dev_upload(ctx_->get(), d[0], out.n_kmers.data(), 4 * n));
+        check(gs_dev_upload(ctx_->get(), d[1], out.best_colour.data(), 4 * n));
+        check(gs_dev_upload(ctx_->get(), d[2], out.best_hits.data(), 4 * n));
+        check(gs_bigsi_classify_dev(bx_, n, (const uint32_t *)d[0], (const uint32_t *)d[1], (const uint32_t *)d[2], fp_correct, (double *)d[3], (uint8_t *)d[4]));
+        check(gs_dev_download(ctx_->get(), out.tail.data(), d[3], 8 * n));
+        check(gs_dev_download(ctx_->get(), out.accept.data(), d[4], n));
+        for (int i = 0; i < 5; i++) check(gs_dev_free(ctx_->get(), d[i]));
+        return out;
+    }
+    void save(const std::string &path) const { check(gs_bigsi_save(bx_, path.c_str())); }
+
+private:
+    struct Text {   // records end to end, their bounds, and the record offsets of the groups
+        std::string text; std::vector<uint64_t> begin, end, off{0};
+        explicit Text(const std::vector<std::vector<std::string>> &groups)
+        {
+            for (const auto &g : groups) {
+                for (const auto &r : g) { begin.push_back(text.size()); text += r; end.push_back(text.size()); }
+                off.push_back(begin.size());
+            }
+        }
+    };
+    Context *ctx_; gs_bigsi *bx_ = nullptr; std::vector<std::string> names_;
+};
+
 // hnsw_rs::Neighbour{d_id, distance, p_id}: gsearch reads d_id (the DataId the point was inserted under: an index into its seqdict) and distance
 // (answer.rs:42,55-57); p_id = PointId(layer, rank in layer)
 struct PointId { uint8_t layer; int32_t rank; };

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""Rates of bigsig on the device (SPEC 11, gs_bigsi.hip): an index of synthetic genomes generated in HBM (gs_synth_dna_dev, the bench's generator), then the
+identification of reads cut from them (and of reads from genomes that are not in the index), all through the device forms.
+Reports genomes/s and bit-sets/s of the build; reads/s, row look-ups/s and gathered bytes/s of the query next to a device-to-device copy rate taken in
+the same run; the classify time; and checks a sample of reads and one column against the numpy restatement (tests/pyref_bigsi.py).
+usage: bigsi_rate.py [--genomes N] [--mbp L] [--log2-rows R] [--hashes H] [--k K] [--reads Q] [--down-sample D]"""
+import argparse, os, sys, time
+import ctypes as C
+import numpy as np
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import gsearch_amd as G
+import pyref_bigsi as PR
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--genomes", type=int, default=4096)
+ap.add_argument("--mbp", type=float, default=5.0)
+ap.add_argument("--log2-rows", type=int, default=26)
+ap.add_argument("--hashes", type=int, default=3)
+ap.add_argument("--k", type=int, default=31)
+ap.add_argument("--reads", type=int, default=2_000_000)
+ap.add_argument("--read-len", type=int, default=150)
+ap.add_argument("--down-sample", type=int, default=1)
+ap.add_argument("--chunk", type=int, default=512)
+a = ap.parse_args()
+
+ctx = G.Context(0)
+lib, chk = ctx.L, G._lib.check
+N, L, B, h, k = a.genomes, int(a.mbp * 1e6), 1 << a.log2_rows, a.hashes, a.k
+words = (L + 31) // 32
+chunk = min(a.chunk, N)
+seed = 1
+print("# %s; index: %d genomes x %.1f Mbp, bloom_size 2^%d, num_hash %d, k %d: matrix %.2f GB" % (ctx.device_info()["name"], N, L / 1e6, a.log2_rows, h, k,
+                                                                                               B * ((N + 63) // 64) * 8 / 1e9), flush=True)
+
+
+def ascii_of(packed, n):
+    codes = np.stack([(packed >> s) & 3 for s in (6, 4, 2, 0)], axis=1).reshape(-1)[:n]
+    return bytes(np.frombuffer(b"ACGT", np.uint8)[codes])
+
+
+# ---- device copy rate of this run ---------------------------------------------------------------------------------------------------------------
+hip = C.CDLL("libamdhip64.so")
+hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+nb = 2 << 30
+d_a, d_b = ctx.alloc(nb), ctx.alloc(nb)
+ctx.memset(d_a, 1, nb); ctx.memset(d_b, 2, nb); ctx.sync()
+best = 1e9
+for _ in range(4):
+    t0 = time.perf_counter()
+    assert hip.hipMemcpy(d_b, d_a, nb, 3) == 0          # hipMemcpyDeviceToDevice
+    ctx.sync()
+    best = min(best, time.perf_counter() - t0)
+copy_rate = 2 * nb / best
+print("device copy: %.2f GB in %.2f ms: %.2f TB/s (bytes read + written)" % (nb / 1e9, best * 1e3, copy_rate / 1e12), flush=True)
+ctx.free(d_a); ctx.free(d_b)
+
+# ---- build ------------------------------------------------------------------------------------------------------------------------------------------
+t0 = time.perf_counter()
+bx = G.Bigsi(k, h, B, N, ctx=ctx)
+print("create (allocate + zero the matrix): %.3f s" % (time.perf_counter() - t0), flush=True)
+d_seq = ctx.alloc(chunk * words * 8 + 64)
+rs = np.arange(chunk, dtype=np.uint64) * np.uint64(words * 32)
+d_rs, d_rl, d_go = ctx.alloc(rs.nbytes), ctx.alloc(rs.nbytes), ctx.alloc(8 * (chunk + 1))
+ctx.upload(d_rs, rs); ctx.upload(d_rl, np.full(chunk, L, np.uint64)); ctx.upload(d_go, np.arange(chunk + 1, dtype=np.uint64))
+t_build, per_chunk = 0.0, []
+for g0 in range(0, N, chunk):
+    c = min(chunk, N - g0)
+    chk(lib.gs_synth_dna_dev(ctx.h, seed, g0, c, L, d_seq))
+    ctx.sync()
+    t0 = time.perf_counter()
+    bx.add_genomes_dev(d_seq, c * words * 8 + 64, d_rs, d_rl, c, d_go, c)
+    ctx.sync()
+    per_chunk.append(time.perf_counter() - t0)
+    t_build += per_chunk[-1]
+nk = N * (L - k + 1)
+print("build: %d genomes in %.3f s (%d chunks of %d; first %.3f s, the others %.3f s each): %.1f genomes/s, %.3g bit-sets/s, %d workgroup(s) per genome" %
+      (N, t_build, len(per_chunk), chunk, per_chunk[0], np.mean(per_chunk[1:]) if len(per_chunk) > 1 else per_chunk[0], N / t_build, nk * h / t_build,
+       ctx.last_sketch_info()["workgroups_per_genome"]), flush=True)
+t = bx.bits_set()
+print("build: bits set per column: mean %.0f (%.4f of the rows), expected %.0f" % (t.mean(), t.mean() / B, B * (1 - np.exp(-h * (L - k + 1) / B))), flush=True)
+# the last genome of the last chunk against the restatement
+g_last = N - 1
+head = ctx.download(d_seq + ((g_last % chunk) * words * 8), (words * 8,), np.uint8)
+ref = PR.Index(k, h, B)
+ref.add([ascii_of(head, L)])
+rows = ref.cols[0][:: max(len(ref.cols[0]) // 4000, 1)]
+rows = np.unique(np.concatenate([rows, np.random.default_rng(1).integers(0, B, 4000).astype(np.uint64)]))
+got = (bx.rows(rows)[:, g_last >> 6] >> np.uint64(g_last & 63)) & np.uint64(1)
+ok = np.array_equal(got.astype(bool), np.isin(rows, ref.cols[0])) and int(t[g_last]) == len(ref.cols[0])
+print("build: column %d (%d rows sampled, t_c) against pyref_bigsi: %s" % (g_last, len(rows), "bit-exact" if ok else "MISMATCH"), flush=True)
+
+# ---- reads: records inside a buffer of `own` indexed genomes (colours 0 ..) and `other` genomes of another seed -------------------------------------
+own, other = min(chunk, N), max(min(chunk, N) // 8, 1)
+ctx.free(d_seq)
+d_seq = ctx.alloc((own + other) * words * 8 + 64)
+chk(lib.gs_synth_dna_dev(ctx.h, seed, 0, own, L, d_seq))
+chk(lib.gs_synth_dna_dev(ctx.h, seed + 77, 0, other, L, d_seq + own * words * 8))
+Q, RL = a.reads, a.read_len
+rng = np.random.default_rng(2)
+src = rng.integers(0, own + other, Q).astype(np.uint64)
+start = src * np.uint64(words * 32) + rng.integers(0, L - RL, Q).astype(np.uint64)
+for p in (d_rs, d_rl, d_go):
+    ctx.free(p)
+d_rs, d_rl, d_go = ctx.alloc(8 * Q), ctx.alloc(8 * Q), ctx.alloc(8 * (Q + 1))
+ctx.upload(d_rs, start); ctx.upload(d_rl, np.full(Q, RL, np.uint64)); ctx.upload(d_go, np.arange(Q + 1, dtype=np.uint64))
+d_n, d_c, d_h, d_t, d_acc = ctx.alloc(4 * Q), ctx.alloc(4 * Q), ctx.alloc(4 * Q), ctx.alloc(8 * Q), ctx.alloc(Q)
+sb = (own + other) * words * 8 + 64
+bx.query_dev(d_seq, sb, d_rs, d_rl, Q, d_go, min(Q, 20000), d_n, d_c, d_h, down_sample=a.down_sample)       # warm-up
+ctx.sync()
+times = []
+for _ in range(3):
+    t0 = time.perf_counter()
+    bx.query_dev(d_seq, sb, d_rs, d_rl, Q, d_go, Q, d_n, d_c, d_h, down_sample=a.down_sample)
+    ctx.sync()
+    times.append(time.perf_counter() - t0)
+tq = min(times)
+n_used = ctx.download(d_n, Q, np.uint32)
+look = int(n_used.sum()) * h
+W = bx.info()["row_words"]
+print("query: %d reads of %d bp (%.0f %% from indexed genomes), down_sample %d: %.4f s (runs: %s): %.3g reads/s, %.3g row look-ups/s, %.3g gathered bytes/s = %.2f of the copy rate "
+      "(%d words per row)" % (Q, RL, 100.0 * own / (own + other), a.down_sample, tq, " ".join("%.4f" % x for x in times), Q / tq, look / tq, look * W * 8 / tq,
+                              look * W * 8 / tq / copy_rate, W), flush=True)
+t0 = time.perf_counter()
+bx.classify_dev(Q, d_n, d_c, d_h, 1e-3, d_t, d_acc)
+ctx.sync()
+tc = time.perf_counter() - t0
+col, hits, acc = ctx.download(d_c, Q, np.uint32), ctx.download(d_h, Q, np.uint32), ctx.download(d_acc, Q, np.uint8).astype(bool)
+planted = src < own
+print("classify: %d reads in %.4f s (%.3g reads/s); accepted %d, of the planted reads %d of %d with their own colour, of the others %d accepted" %
+      (Q, tc, Q / tc, acc.sum(), int((acc & planted & (col == src)).sum()), int(planted.sum()), int((acc & ~planted).sum())), flush=True)
+# a sample of reads against the restatement, on the sampled genome's column only where that is all the restatement holds: n and the planted hits
+g0 = ascii_of(ctx.download(d_seq, (words * 8,), np.uint8), L)
+mine = np.nonzero(src == 0)[0][:50]
+ok = True
+for r in mine:
+    s = int(start[r])
+    v = PR.kmers([g0[s:s + RL]], k)[:: a.down_sample]
+    ok = ok and int(n_used[r]) == len(v) and int(hits[r]) == len(v) and int(col[r]) == 0
+print("query: %d reads cut from genome 0 against pyref_bigsi (n, best colour, best hits = n): %s" % (len(mine), "equal" if ok else "MISMATCH"), flush=True)
