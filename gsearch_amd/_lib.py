@@ -211,6 +211,9 @@ SYMBOLS = {
     "gs_synth_sigs_dev": (_i, [_vp, _i, _u32, _u64, _u64, _u64, _u64, C.c_double, C.c_double, _vp]),
     "gs_synth_sigs_skew_dev": (_i, [_vp, _i, _u32, _u64, _u64, _u64, _u64, C.c_double, C.c_double, C.c_double, _vp]),
     "gs_synth_dna_family_skew_dev": (_i, [_vp, _u64, _u64, _u64, _u64, _u64, C.c_double, C.c_double, C.c_double, _vp]),
+    # debugging
+    "gs_debug_mem_fill": (_i, [_i]),
+    "gs_index_debug_fill_scratch": (_i, [_vp, _i]),
 }
 
 _lib = None

@@ -199,6 +199,12 @@ def topk_merge_dev(ctx, ids_dev, dist_dev, n_shards, nq, knbn_in, knbn_out, out_
 _default_ctx = None
 
 
+def debug_mem_fill(byte):
+    """debugging, not for production use: fill every new device allocation and every newly taken scratch slot with `byte` (0..255) from now on,
+    in the whole process; None = off (include/gsearch_amd.h gs_debug_mem_fill)"""
+    check(_lib.load().gs_debug_mem_fill(-1 if byte is None else int(byte)))
+
+
 def default_context():
     global _default_ctx
     if _default_ctx is None:
@@ -1522,3 +1528,8 @@ class Hnsw:
 
     def insert_evals(self):
         return 0 if self.h is None else self.ctx.L.gs_index_insert_evals(self.h)
+
+    def debug_fill_scratch(self, byte):
+        """debugging, not for production use: fill the per-call scratch buffers of the index with `byte` (gs_index_debug_fill_scratch)"""
+        if self.h is not None:
+            check(self.ctx.L.gs_index_debug_fill_scratch(self.h, int(byte)))

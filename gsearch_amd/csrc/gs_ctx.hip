@@ -296,6 +296,12 @@ int gs_dev_alloc(gs_ctx *c, size_t bytes, void **p)
     GS_REQUIRE(c && p, GS_ERR_INVALID, "null argument");
     GS_HIP_CHECK(hipSetDevice(c->device));
     GS_HIP_CHECK(hipMalloc(p, bytes ? bytes : 16));
+    return gs::debug_fill(*p, bytes ? bytes : 16);
+}
+int gs_debug_mem_fill(int byte)
+{
+    GS_REQUIRE(byte >= -1 && byte <= 255, GS_ERR_INVALID, "gs_debug_mem_fill: byte must be 0..255, or -1 for off (got %d)", byte);
+    gs::debug_fill_byte.store(byte, std::memory_order_relaxed);
     return GS_OK;
 }
 int gs_dev_free(gs_ctx *c, void *p)

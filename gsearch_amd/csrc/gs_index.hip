@@ -2195,27 +2195,52 @@ struct gs_index {
     int ikind = GS_KIND_F32; size_t user_rowbytes = 0;      // u16 signatures (hll) are held zero-extended to u32 (gs_hamming.hip k_widen_u16)
     uint64_t n = 0, cap = 0; int64_t entry = -1; int top = -1;
     uint64_t n_upper = 0, cap_upper = 0;
-    gs::DevBuf data, levels, deg0, nbr0, cnt0, upidx, degU, nbrU, cntU;
-    gs::DevBuf visited, counter, cbuf;
+    // Every DevBuf below says what it is. "state" survives between calls; "scratch" is ensure()d at the start of a call that uses it, with the layout
+    // of that caller, and a call initialises whatever it reads of it: gs_index_debug_fill_scratch fills exactly the scratch members (index_scratch).
+    gs::DevBuf data;       // state: the signatures of the n nodes, zero-padded rows of `stride` bytes
+    gs::DevBuf levels;     // state: the level of every node
+    gs::DevBuf deg0;       // state: graph, layer-0 degrees
+    gs::DevBuf nbr0;       // state: graph, layer-0 neighbours
+    gs::DevBuf cnt0;       // state: graph, the mismatch counts of the layer-0 edges
+    gs::DevBuf upidx;      // state: graph, a node's slot in the upper-layer arrays (-1: level 0)
+    gs::DevBuf degU;       // state: graph, upper-layer degrees (n_upper slots)
+    gs::DevBuf nbrU;       // state: graph, upper-layer neighbours
+    gs::DevBuf cntU;       // state: graph, the mismatch counts of the upper-layer edges
+    gs::DevBuf visited;    // scratch: visited bitmaps / traversal workspace; three layouts (dense traversal and pre-pass, legacy search, insert plan)
+    gs::DevBuf counter;    // scratch: the work-stealing query counter of a traversal launch (zeroed before each)
+    gs::DevBuf cbuf;       // scratch: candidate buffers of the dense traversal
     // insert scratch
-    gs::DevBuf blevels, cntmat, plan_keys, plan_n, inbox, inbox_cnt, touched, ntouched, evals_dev;
-    gs::DevBuf wlog, w0_keys, w0_n, w0_evals, ep0; // insert pre-pass (plan_prepass)
-    gs::DevBuf ext_keys;                           // candidate keys of the extended selection (extend_candidates with efc <= 2M)
+    gs::DevBuf blevels;    // scratch: the levels of the batch (uploaded by start_batch)
+    gs::DevBuf cntmat;     // scratch: the intra-batch count matrix
+    gs::DevBuf plan_keys;  // scratch: the selected neighbours of the batch, plan_n of them per (point, layer)
+    gs::DevBuf plan_n;     // scratch: zeroed by start_batch
+    gs::DevBuf inbox;      // scratch: back-link inboxes; only the first inbox_cnt[list] entries of a list are read
+    gs::DevBuf inbox_cnt;  // state: a cache kept ALL ZERO between batches (k_link_merge clears what k_link_scatter counted); zeroed when inbox_lists changes
+    gs::DevBuf touched;    // scratch: the lists k_link_scatter touched, ntouched of them
+    gs::DevBuf ntouched;   // scratch: zeroed by start_batch
+    gs::DevBuf evals_dev;  // state: evaluation counters since the index was made (insert_evals / gs_index_insert_evals reads [0])
+    // insert pre-pass (plan_prepass)
+    gs::DevBuf wlog;       // scratch: accepted-key logs of the pre-pass workgroups
+    gs::DevBuf w0_keys;    // scratch: the W the pre-pass worked out per point, w0_n keys each
+    gs::DevBuf w0_n;       // scratch
+    gs::DevBuf w0_evals;   // scratch
+    gs::DevBuf ep0;        // scratch: layer-0 entry points of the batch (set to 0xFF before phase 1)
+    gs::DevBuf ext_keys;   // scratch: candidate keys of the extended selection (extend_candidates with efc <= 2M)
     uint64_t inbox_lists = 0;
     uint64_t insert_evals = 0;
     // dense mode: count matrix of a query / insert batch against every node, and the running
     // fraction of the graph a traversal evaluates (negative = not measured yet)
-    gs::DevBuf mat;
+    gs::DevBuf mat;        // scratch: every caller fills the rows it reads (cluster_rows hands its rows out until the next call only)
     double search_frac = -1.0, insert_frac = -1.0;
     // pair cache: the count rows the tile kernel produces for every inserted batch are KEPT (16 bit) so that
     // the neighbour-selection heuristic looks pair distances up instead of streaming rows; 288 GB of HBM hold it up to ~500 k points
     // column-major copy of the signatures for the match-join (gs_join.hip)
-    gs::DevBuf cols; uint64_t cols_cap = 0, cols_n = 0;
-    gs::DevBuf join_scratch[gs::JOIN_SCRATCH];
-    gs::DevBuf stats;                 // device work counters: [0] join atomics, [1] dense-traversal pops, [2] accepting pops (gs_index_search_stats)
+    gs::DevBuf cols; uint64_t cols_cap = 0, cols_n = 0;      // state: the column copy of the first cols_n nodes
+    gs::DevBuf join_scratch[gs::JOIN_SCRATCH];               // scratch: query tables, pair and label lists, tile lists of one match-join
+    gs::DevBuf stats;                 // state: device work counters: [0] join atomics, [1] dense-traversal pops, [2] accepting pops (gs_index_search_stats)
     uint64_t stat_wg_in_flight = 0, stat_adj_row_bytes = 0;
-    gs::DevBuf rowptr;
-    // sparse pair rows (IndexDev::sp_*): allocated at the first dense insert batch, grown with the index; sp_L = 0: off (GS_SPARSE_ROWS=0, m > 65535, no memory)
+    gs::DevBuf rowptr;                // state: where a node's cached count row lies in the slabs (0: none); grown with the index, cleared by drop_pair_cache
+    // state, all four: sparse pair rows (IndexDev::sp_*): allocated at the first dense insert batch, grown with the index; sp_L = 0: off (GS_SPARSE_ROWS=0, m > 65535, no memory)
     gs::DevBuf sp_off, sp_meta, sp_bm, sp_arena; uint32_t sp_L = 0; bool sp_tried = false;
     gs::VmArena sp_vm;                // lists + level bitmaps (grow in place; sp_arena = the device-side bump allocator over it)
     bool sp_exhausted = false;        // the arena (or the device) is full: lists are still handed out while they fit, nothing more is mapped
@@ -2233,13 +2258,22 @@ struct gs_index {
     std::vector<uint64_t> origin;
     std::vector<int32_t> pid_rank;
     uint64_t level_count[17] = {0};
-    gs::DevBuf origin_d, pid_rank_d; uint64_t origin_d_n = 0, pid_rank_d_n = 0;
+    gs::DevBuf origin_d, pid_rank_d; uint64_t origin_d_n = 0, pid_rank_d_n = 0;     // state: device copies of the first origin_d_n / pid_rank_d_n entries of the two above
     // gs_index_sketch_and_search_dev: the padded query rows are produced batch by batch while the search is under way; dense_counts asks for
     // rows [q0, q0 + nb) of the buffer at feed_base just before it joins them
     std::function<int(uint64_t, uint64_t)> *feed = nullptr; const uint8_t *feed_base = nullptr;
 };
 
 namespace gs {
+
+// the members of gs_index marked "scratch" at the struct, and nothing else
+static std::vector<DevBuf *> index_scratch(gs_index *ix)
+{
+    std::vector<DevBuf *> v = {&ix->visited, &ix->counter, &ix->cbuf, &ix->blevels, &ix->cntmat, &ix->plan_keys, &ix->plan_n, &ix->inbox, &ix->touched, &ix->ntouched,
+                               &ix->wlog, &ix->w0_keys, &ix->w0_n, &ix->w0_evals, &ix->ep0, &ix->ext_keys, &ix->mat};
+    for (DevBuf &b : ix->join_scratch) v.push_back(&b);
+    return v;
+}
 
 static void ids_append(gs_index *ix, const uint64_t *ids, const uint8_t *lv, uint64_t n);
 
@@ -2789,6 +2823,15 @@ int gs_index_search_stats(gs_index *ix, uint64_t out[8], int reset)
             fprintf(stderr, "[GS_TRAV_PHASES]   phase 1 front, all workgroups: refills %llu, compactions %llu, selection rounds beyond the first %llu\n", h[15] & 0xFFFFFFull, (h[15] >> 24) & 0xFFFFull, h[15] >> 40);
     }
     out[3] = ix->stat_wg_in_flight; out[4] = ix->stat_adj_row_bytes;
+    return GS_OK;
+}
+int gs_index_debug_fill_scratch(gs_index *ix, int byte)
+{
+    GS_REQUIRE(ix && byte >= 0 && byte <= 255, GS_ERR_INVALID, "gs_index_debug_fill_scratch: null index or byte outside 0..255");
+    GS_CTX_LOCK(ix->ctx);
+    GS_HIP_CHECK(hipDeviceSynchronize());
+    for (gs::DevBuf *b : gs::index_scratch(ix)) if (b->p) GS_HIP_CHECK(hipMemset(b->p, byte, b->bytes));
+    GS_HIP_CHECK(hipDeviceSynchronize());
     return GS_OK;
 }
 int gs_index_release_build_scratch(gs_index *ix)

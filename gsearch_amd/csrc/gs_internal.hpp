@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <algorithm>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -203,6 +204,21 @@ int run_length_encode_u64(gs_ctx *c, const uint64_t *sorted, uint64_t n, uint64_
 inline size_t kind_bytes(int kind) { return kind == GS_KIND_U16 ? 2 : (kind == GS_KIND_U64 ? 8 : 4); }
 inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
+// gs_debug_mem_fill (debugging): the byte that new device allocations and newly leased scratch slots are filled with, -1 = off. A lease starts with
+// unknown content; this makes "unknown" a chosen value, so that a kernel which reads what nothing wrote gives a wrong answer in a test instead of
+// a right one by luck. The fill serialises the whole device on purpose: slots are also used on streams other than the context's (the file
+// pipelines, the child context), and a fill ordered on one stream could land behind a correct kernel's writes.
+inline std::atomic<int> debug_fill_byte{-1};
+inline int debug_fill(void *p, size_t n)
+{
+    const int byte = debug_fill_byte.load(std::memory_order_relaxed);
+    if (byte < 0 || !p || !n) return GS_OK;
+    GS_HIP_CHECK(hipDeviceSynchronize());
+    GS_HIP_CHECK(hipMemset(p, byte, n));
+    GS_HIP_CHECK(hipDeviceSynchronize());
+    return GS_OK;
+}
+
 inline bool mem_verbose() { static const bool v = getenv("GS_MEM_VERBOSE") != nullptr; return v; }   // trace of the allocations of 256 MB and more (stderr)
 struct DevBuf {   // owning device allocation
     void *p = nullptr; size_t bytes = 0;
@@ -227,7 +243,7 @@ struct DevBuf {   // owning device allocation
             if (n >= ((size_t)256 << 20)) fprintf(stderr, "[GS_MEM] + %.2f GB (free after %.2f of %.2f GB)\n", n / 1e9, fr / 1e9, tot / 1e9);
         }
         bytes = n;
-        return GS_OK;
+        return debug_fill(p, n);
     }
     int ensure(size_t n) { return (n <= bytes && p) ? GS_OK : alloc(n); }
     template <class T> T *as() const { return (T *)p; }
@@ -324,11 +340,14 @@ struct PoolBuf {    // a scoped lease of one slot; same surface as DevBuf for th
     {
         if (!c->scratch_pool) c->scratch_pool = new ScratchPool();
         ScratchPool *pool = (ScratchPool *)c->scratch_pool;
-        int rc = lease.take(pool->leases);
+        bool fresh = false;
+        int rc = lease.take(pool->leases, &fresh);
         if (rc) return rc;
         DevBuf &d = pool->b[lease.slot];
         if (n == 0) n = 16;
+        const bool grows = !(n <= d.bytes && d.p);                  // (DevBuf::alloc fills what it allocates)
         if ((rc = d.ensure(n))) return rc;
+        if (fresh && !grows && (rc = debug_fill(d.p, d.bytes))) return rc;     // the whole slot, not n: the tail a larger earlier user left is poisoned too
         p = d.p; bytes = n;
         return GS_OK;
     }

@@ -112,9 +112,12 @@ struct SlotLease {
     SlotLease(const SlotLease &) = delete;
     SlotLease &operator=(const SlotLease &) = delete;
     ~SlotLease() { give(); }
-    // GS_OK: the slot of `table` is ours (or already was: allocating again through the same object is allowed). An error: another lease holds it
-    int take(const std::shared_ptr<SlotLeases> &table)
+    // GS_OK: the slot of `table` is ours (or already was: allocating again through the same object is allowed). An error: another lease holds it.
+    // *fresh (optional): this call is the one that took the lease - the slot's content is whatever its last holder left (gs_debug_mem_fill poisons it
+    // then); false when the object held it already, and the caller may count on what it wrote there
+    int take(const std::shared_ptr<SlotLeases> &table, bool *fresh = nullptr)
     {
+        if (fresh) *fresh = false;
         if (from == table) return GS_OK;
         give();
         if (!table->take(slot)) {
@@ -122,6 +125,7 @@ struct SlotLease {
             return GS_ERR_STATE;
         }
         from = table;
+        if (fresh) *fresh = true;
         return GS_OK;
     }
     void give() { if (from) { from->give(slot); from.reset(); } }

@@ -535,6 +535,16 @@ int gs_synth_dna_family_skew_dev(gs_ctx *, uint64_t seed, uint64_t first_genome,
 int gs_synth_sigs_skew_dev(gs_ctx *, int kind, uint32_t m, uint64_t seed, uint64_t first_row, uint64_t n_rows,
                            uint64_t n_roots, double j_lo, double j_hi, double alpha, void *sigs_dev /* n_rows x m */);
 
+/* ---------------------------------------------------------------------------------------------- */
+/* Debugging (tests only, not for production use): device temporaries are never cleared between uses, and these two calls fill them with a chosen
+ * byte so that a kernel which reads what nothing wrote shows in a comparison (tests/test_gpu_stale_scratch.py).
+ * gs_debug_mem_fill: process-wide; byte 0..255 = on, -1 = off (the default), anything else GS_ERR_INVALID. While on, every device allocation the
+ * library makes (gs_dev_alloc included) and every scratch slot at the moment a call takes it is filled, whole, with the byte. Each fill
+ * synchronises the whole device. Off costs one relaxed atomic load per allocation.
+ * gs_index_debug_fill_scratch: fills the buffers an index keeps as per-call scratch (not its data, graph, caches or counters), synchronously. */
+int gs_debug_mem_fill(int byte);
+int gs_index_debug_fill_scratch(gs_index *, int byte);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ struct Error : std::runtime_error {
     Error(int c, const std::string &m) : std::runtime_error("gsearch_amd error " + std::to_string(c) + ": " + m), code(c) {}
 };
 inline void check(int rc) { if (rc != GS_OK) throw Error(rc, gs_last_error()); }
+// debugging (not for production use): fill new device allocations and newly taken scratch with `byte` (0..255); -1 = off
+inline void debug_mem_fill(int byte) { check(gs_debug_mem_fill(byte)); }
 
 class Context {   // one per (process, GPU)
 public:
@@ -439,6 +441,7 @@ public:
         return {std::move(arg), std::move(cnt)};
     }
     void file_dump(const std::string &path) const { check(gs_index_save(h_, path.c_str())); }      // dumpload.rs:31 (own format)
+    void debug_fill_scratch(int byte) { if (h_) check(gs_index_debug_fill_scratch(h_, byte)); }    // debugging (not for production use): gsearch_amd.h
 private:
     void frozen() const { if (h_) throw Error(GS_ERR_STATE, "index parameters are frozen once the index holds points"); }
     void ensure(size_t m) { if (!h_) { prm_.m = (uint32_t)m; check(gs_index_create(ctx_->get(), &prm_, &h_)); } }

@@ -23,6 +23,14 @@ void sl_pool_delete(void *p) { delete (Pool *)p; }                    // what dr
 int sl_pool_held(void *p, int s) { return (*(Pool *)p)->held[s]; }
 void *sl_lease_new(int s) { return new gs::SlotLease((gs::ScratchSlot)s); }
 int sl_lease_take(void *l, void *p) { return ((gs::SlotLease *)l)->take(*(Pool *)p); }
+// GS_OK and 1: this call took the lease (its content is unknown); GS_OK and 0: the object held it already; an error leaves 0
+int sl_lease_take_fresh(void *l, void *p, int *fresh)
+{
+    bool f = true;
+    const int rc = ((gs::SlotLease *)l)->take(*(Pool *)p, &f);
+    *fresh = f ? 1 : 0;
+    return rc;
+}
 void sl_lease_give(void *l) { ((gs::SlotLease *)l)->give(); }
 void sl_lease_delete(void *l) { delete (gs::SlotLease *)l; }
 }

@@ -24,6 +24,7 @@ def sl(tmp_path_factory):
         f.argtypes, f.restype = [C.c_void_p], None
     L.sl_pool_held.argtypes = [C.c_void_p, C.c_int]
     L.sl_lease_take.argtypes = [C.c_void_p, C.c_void_p]
+    L.sl_lease_take_fresh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     return L
 
 
@@ -82,3 +83,27 @@ def test_give_back_after_the_pool_is_deleted(sl):
     sl.sl_lease_delete(b)
     assert sl.sl_pool_held(new, s) == 0
     sl.sl_pool_delete(new)
+
+
+def test_take_reports_whether_the_lease_is_new(sl):
+    """PoolBuf::alloc fills a slot for gs_debug_mem_fill when its call is the one that took the lease, and only then: a second alloc through the same
+    object keeps its content"""
+    s = _slot(sl, "BIGSI_BITMAP")
+    pool, a, b = sl.sl_pool_new(), sl.sl_lease_new(s), sl.sl_lease_new(s)
+    fresh = C.c_int(-1)
+    assert sl.sl_lease_take_fresh(a, pool, C.byref(fresh)) == GS_OK and fresh.value == 1       # the first take
+    assert sl.sl_lease_take_fresh(a, pool, C.byref(fresh)) == GS_OK and fresh.value == 0       # again through the same object: not new
+    assert sl.sl_lease_take(a, pool) == GS_OK and sl.sl_pool_held(pool, s) == 1                # (the plain form is unchanged)
+    fresh.value = -1
+    assert sl.sl_lease_take_fresh(b, pool, C.byref(fresh)) == GS_ERR_STATE and fresh.value == 0   # refused: nothing was taken
+    sl.sl_lease_give(a)
+    assert sl.sl_lease_take_fresh(a, pool, C.byref(fresh)) == GS_OK and fresh.value == 1       # given back and taken again: new
+    sl.sl_lease_give(a)
+    assert sl.sl_lease_take_fresh(b, pool, C.byref(fresh)) == GS_OK and fresh.value == 1       # another object after it
+    other_pool = sl.sl_pool_new()
+    assert sl.sl_lease_take_fresh(b, other_pool, C.byref(fresh)) == GS_OK and fresh.value == 1  # moved to another pool's table: new there
+    assert sl.sl_pool_held(pool, s) == 0 and sl.sl_pool_held(other_pool, s) == 1
+    for l in (a, b):
+        sl.sl_lease_delete(l)
+    for p in (pool, other_pool):
+        sl.sl_pool_delete(p)
