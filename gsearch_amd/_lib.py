@@ -164,6 +164,11 @@ SYMBOLS = {
     # bigsig (SPEC 11)
     "gs_bigsi_check_params": (_i, [C.POINTER(BigsiParamsC)]),
     "gs_bigsi_create": (_i, [_vp, C.POINTER(BigsiParamsC), _u64, C.POINTER(_vp)]),
+    "gs_bigsi_create_mini": (_i, [_vp, C.POINTER(BigsiParamsC), _u32, _u64, C.POINTER(_vp)]),
+    "gs_bigsi_minimizer_len": (_u32, [_vp]),
+    "gs_bigsi_add_batch_min_count_dev": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u32]),
+    "gs_bigsi_add_batch_min_count": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _u64, _u32]),
+    "gs_bigsi_minimizers": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _u32, _u64, _vp, _vp, C.POINTER(_u64)]),
     "gs_bigsi_free": (None, [_vp]),
     "gs_bigsi_info": (_i, [_vp, C.POINTER(BigsiDescC)]),
     "gs_bigsi_add_batch_dev": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),

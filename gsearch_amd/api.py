@@ -773,6 +773,26 @@ def bigsi_tail(t_c, bloom_size, num_hash, n_kmers, best_hits):
     return _lib.load().gs_bigsi_tail(int(t_c), int(bloom_size), int(num_hash), int(n_kmers), int(best_hits))
 
 
+BIGSI_MINI_TILE = 63        # GS_BIGSI_MINI_TILE of gsearch_amd.h: the windows a wavefront of the minimizer kernel takes at a time
+
+
+def bigsi_minimizers(text, k, m, qual=None, min_phred=15, data_t="dna"):
+    """SPEC 11.1: the minimizer occurrences of one text (window k, minimizer m) in order -> (values u64, offsets in text of each m-mer's first base u64);
+    host arithmetic"""
+    L = _lib.load()
+    t = np.frombuffer(bytes(text), dtype=np.uint8)
+    q = None if qual is None else np.frombuffer(bytes(qual), dtype=np.uint8)
+    if q is not None and len(q) != len(t):
+        raise ValueError("the text needs as many quality bytes as it has bytes")
+    dt = DATA[data_t] if isinstance(data_t, str) else int(data_t)
+    tp, qp = _p(t) if len(t) else None, _p(q) if q is not None and len(q) else None
+    n = C.c_uint64()
+    check(L.gs_bigsi_minimizers(tp, qp, len(t), int(min_phred), int(k), int(m), dt, 0, None, None, C.byref(n)))
+    v, pos = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+    check(L.gs_bigsi_minimizers(tp, qp, len(t), int(min_phred), int(k), int(m), dt, n.value, _p(v), _p(pos), C.byref(n)))
+    return v, pos
+
+
 def bigsig_write_reads(prefix, accessions, read_ids, best_colour, best_hits, n_kmers, accept):
     """`{prefix}_reads.txt` and `{prefix}_counts.txt` (SPEC 11)"""
     acc = (C.c_char_p * max(len(accessions), 1))(*[a.encode() for a in accessions])
@@ -785,7 +805,8 @@ def bigsig_write_reads(prefix, accessions, read_ids, best_colour, best_hits, n_k
 class Bigsi:
     """A bit-sliced Bloom index of genomes (bigsig): bloom_size rows, one column ("colour") per genome in the order added; the matrix lives on the device."""
 
-    def __init__(self, k, num_hash, bloom_size, capacity, data_t="dna", ctx=None, minimizer=0, coverage_filter=0, _handle=None):
+    def __init__(self, k, num_hash, bloom_size, capacity, data_t="dna", ctx=None, minimizer=0, coverage_filter=0, minimizer_len=0, _handle=None):
+        """minimizer_len = m > 0: a minimizer index (SPEC 11.1) of window length k. minimizer / coverage_filter are the two struct fields that must stay 0."""
         self.ctx = ctx or default_context()
         self.L = self.ctx.L
         if _handle is not None:
@@ -794,7 +815,10 @@ class Bigsi:
         prm = _lib.BigsiParamsC(int(k), int(num_hash), int(bloom_size), DATA[data_t] if isinstance(data_t, str) else int(data_t), int(minimizer),
                                 int(coverage_filter))
         h = C.c_void_p()
-        check(self.L.gs_bigsi_create(self.ctx.h, C.byref(prm), int(capacity), C.byref(h)))
+        if minimizer_len:
+            check(self.L.gs_bigsi_create_mini(self.ctx.h, C.byref(prm), int(minimizer_len), int(capacity), C.byref(h)))
+        else:
+            check(self.L.gs_bigsi_create(self.ctx.h, C.byref(prm), int(capacity), C.byref(h)))
         self.h = h
 
     @classmethod
@@ -817,22 +841,30 @@ class Bigsi:
         d = _lib.BigsiDescC()
         check(self.L.gs_bigsi_info(self.h, C.byref(d)))
         return {"k": d.prm.k, "num_hash": d.prm.num_hash, "bloom_size": d.prm.bloom_size, "data_t": d.prm.data_t, "n_colours": d.n_colours,
-                "colour_capacity": d.colour_capacity, "row_words": d.row_words}
+                "colour_capacity": d.colour_capacity, "row_words": d.row_words, "minimizer_len": self.L.gs_bigsi_minimizer_len(self.h)}
 
-    def add_genomes(self, genomes, accessions=None, quals=None, min_phred=15):
-        """genomes: a list of lists of records (ASCII bytes), one new colour each; quals: the same shape, quality bytes"""
+    def add_genomes(self, genomes, accessions=None, quals=None, min_phred=15, min_count=1):
+        """genomes: a list of lists of records (ASCII bytes), one new colour each; quals: the same shape, quality bytes; min_count >= 2: the coverage
+        filter (SPEC 11.1) - within each colour only values that occur that often are inserted"""
         text, qual, b, e, off = _text_records(genomes, quals)
         names = None if accessions is None else self.accessions() + list(accessions)
-        check(self.L.gs_bigsi_add_batch(self.h, _p(text) if len(text) else None, _p(qual) if qual is not None and len(qual) else None, int(min_phred),
-                                        _p(b), _p(e), len(b), _p(off), len(genomes)))
+        tp, qp = _p(text) if len(text) else None, _p(qual) if qual is not None and len(qual) else None
+        if int(min_count) > 1:
+            check(self.L.gs_bigsi_add_batch_min_count(self.h, tp, qp, int(min_phred), _p(b), _p(e), len(b), _p(off), len(genomes), int(min_count)))
+        else:
+            check(self.L.gs_bigsi_add_batch(self.h, tp, qp, int(min_phred), _p(b), _p(e), len(b), _p(off), len(genomes)))
         if names is not None:
             self.set_accessions(names)
 
-    def add_genomes_dev(self, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes):
-        """the packed layout of gs_sketch_batch_dev, every pointer device memory; queued on the context's stream"""
-        check(self.L.gs_bigsi_add_batch_dev(self.h, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes))
+    def add_genomes_dev(self, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes, min_count=1):
+        """the packed layout of gs_sketch_batch_dev, every pointer device memory; queued on the context's stream (with min_count >= 2 the host waits once
+        per colour for the size of its value list)"""
+        if int(min_count) > 1:
+            check(self.L.gs_bigsi_add_batch_min_count_dev(self.h, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes, int(min_count)))
+        else:
+            check(self.L.gs_bigsi_add_batch_dev(self.h, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes))
 
-    def add_files(self, paths, accessions=None, quality=15):
+    def add_files(self, paths, accessions=None, quality=15, min_count=1):
         """one colour per FASTA / FASTQ file (plain, gz, bz2, xz), every record of the file; FASTQ bases below `quality` end a segment"""
         genomes, quals, any_q = [], [], False
         for p in paths:
@@ -840,7 +872,7 @@ class Bigsi:
             genomes.append([r for _, r in recs])
             quals.append(qs if qs is not None else [b"~" * len(r) for _, r in recs])
             any_q = any_q or qs is not None
-        self.add_genomes(genomes, accessions=accessions, quals=quals if any_q else None, min_phred=quality)
+        self.add_genomes(genomes, accessions=accessions, quals=quals if any_q else None, min_phred=quality, min_count=min_count)
 
     def set_accessions(self, names):
         arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
@@ -947,15 +979,19 @@ def read_ref_list(path):
     return out
 
 
-def bigsig_construct(ref_list, out_base, k, num_hash, bloom_size, quality=15, threads=0, ctx=None, batch=64):
-    """bigsig construct: one colour per line of ref_list, the index written to `{out_base}.gsbx` and returned. threads: accepted, unused (files are read one
-    after the other on the host)"""
+def bigsig_construct(ref_list, out_base, k, num_hash, bloom_size, quality=15, threads=0, ctx=None, batch=64, minimizer=False, value=21, filter=0):
+    """bigsig construct: one colour per line of ref_list, the index written to `{out_base}.gsbx` (`{out_base}.gsmx` with minimizer=True) and returned.
+    minimizer (-m): a minimizer index of window k and minimizer length `value` (-v, default 21), k > value. filter (-f): the coverage filter, values seen
+    fewer than `filter` times in a colour are left out; <= 1: none (upstream's automatic -f -1 is not built). threads: accepted, unused (files are read
+    one after the other on the host)"""
+    if minimizer and int(k) <= int(value):
+        raise GsError(_lib.GS_ERR_INVALID, "bigsig construct: the window k = %d must be longer than the minimizer value = %d" % (k, value))
     refs = read_ref_list(ref_list)
-    bx = Bigsi(k, num_hash, bloom_size, max(len(refs), 1), ctx=ctx)
+    bx = Bigsi(k, num_hash, bloom_size, max(len(refs), 1), ctx=ctx, minimizer_len=int(value) if minimizer else 0)
     for i in range(0, len(refs), batch):
         part = refs[i:i + batch]
-        bx.add_files([p for _, p in part], accessions=[a for a, _ in part], quality=quality)
-    bx.save(str(out_base) + ".gsbx")
+        bx.add_files([p for _, p in part], accessions=[a for a, _ in part], quality=quality, min_count=max(int(filter), 1))
+    bx.save(str(out_base) + (".gsmx" if minimizer else ".gsbx"))
     return bx
 
 

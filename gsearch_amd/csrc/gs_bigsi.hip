@@ -13,6 +13,14 @@
 //  * k_bigsi_query     : one wavefront per read, lanes = colour words. 64 k-mers are hashed at once (one per lane), then taken in turn: num_hash
 //                        nontemporal row loads, an AND, and a ripple add of the 64-bit vector into bit-plane counters in registers.
 //  * k_bigsi_classify  : one lane per read, the binomial tail of SPEC 11.
+//  minimizer indexes and the coverage filter (SPEC 11.1):
+//  * k_bigsi_minimizers: one wavefront per tile of MZ_TILE windows of one record. Every lane windows and hashes the m-mer at its position, keys and
+//                        (value, h1, step) of the tile and its halo go to LDS, every lane picks the minimizer of its window (minimizer_pick, gs_spec.hpp)
+//                        and compares it with its left neighbour's. Three consumers: bits of a genome's bitmap (build), an unordered value list of one
+//                        colour (build with a filter), an ordered list per read (query; one wavefront per read, ballot + popcount compaction).
+//  * k_bigsi_query<.., LIST = true> takes its values from that list instead of windowing the sequence; everything after the hash is the same kernel.
+//  * filter            : per colour the value list -> radix_sort_u64 -> run_length_encode_u64 -> k_bigsi_fill_runs (runs of at least min_count) ->
+//                        the bitmap, then popcount and transpose as ever. A plain index lists its k-mers with walk_genome (k_bigsi_list).
 #include <errno.h>
 #include <stdio.h>
 #include <string.h>
@@ -27,6 +35,7 @@ struct gs_bigsi {
     gs_ctx *c = nullptr;
     gs_bigsi_params prm{};
     uint64_t cap = 0, W = 0, n = 0;
+    uint32_t m = 0;                        // minimizer length, 0 = a plain index
     gs::DevBuf M, tc, nk;                  // the matrix; t_c and nk_c of every colour
     std::vector<std::string> names;        // accessions (empty until set)
 };
@@ -44,14 +53,27 @@ static inline uint64_t bitmap_pitch(uint64_t B) { return round_up(B, TR_ROWS) / 
 
 struct BitEmit {
     uint32_t *bm; uint64_t B; uint32_t h;
-    __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const
+    __device__ __forceinline__ void bits(uint64_t h1, uint64_t st) const
     {
-        uint64_t h1, st;
-        bigsi_hash(v, h1, st);
         for (uint32_t i = 0; i < h; i++) {
             const uint64_t pos = bigsi_pos(h1, st, i, B);
             atomicOr(&bm[pos >> 5], 1u << (pos & 31));
         }
+    }
+    __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const
+    {
+        uint64_t h1, st;
+        bigsi_hash(v, h1, st);
+        bits(h1, st);
+    }
+};
+// the values themselves, unordered, for the sort-count-filter build of one colour of a plain index (cap: the list's size; the count is exact, so nothing is cut)
+struct ListEmit {
+    uint64_t *vals; unsigned long long *cursor; uint64_t cap;
+    __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const
+    {
+        const uint64_t i = atomicAdd(cursor, 1ull);
+        if (i < cap) vals[i] = v;
     }
 };
 __global__ __launch_bounds__(SK_THREADS) void k_bigsi_fill(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
@@ -63,7 +85,15 @@ __global__ __launch_bounds__(SK_THREADS) void k_bigsi_fill(const uint8_t *__rest
     BitEmit emit{bm + g * pitch, B, h};
     walk_genome<false, BitEmit>(seq, rec_start, rec_len, rec_upre, genome_rec_off[g], genome_rec_off[g + 1], gen_units[g], kq, blockIdx.x, gridDim.x, emit);
 }
-// tc[g] += bits of genome g's bitmap (grid: x = slices, y = genomes); nk[g] = k-mer occurrences of its records (slice 0)
+__global__ __launch_bounds__(SK_THREADS) void k_bigsi_list(const uint8_t *__restrict__ seq, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                           const uint64_t *__restrict__ rec_upre, const uint64_t *__restrict__ genome_rec_off,
+                                                           const uint64_t *__restrict__ gen_units, uint32_t kq, uint64_t *__restrict__ vals,
+                                                           unsigned long long *__restrict__ cursor, uint64_t cap)
+{
+    ListEmit emit{vals, cursor, cap};
+    walk_genome<false, ListEmit>(seq, rec_start, rec_len, rec_upre, genome_rec_off[0], genome_rec_off[1], gen_units[0], kq, blockIdx.x, gridDim.x, emit);
+}
+// tc[g] += bits of genome g's bitmap (grid: x = slices, y = genomes); nk[g] = k-mer occurrences of its records (slice 0; nk NULL: the caller counts them itself)
 __global__ __launch_bounds__(256) void k_bigsi_popcount(const uint32_t *__restrict__ bm, uint64_t pitch, const uint64_t *__restrict__ rec_len,
                                                         const uint64_t *__restrict__ genome_rec_off, uint32_t k, unsigned long long *__restrict__ tc,
                                                         unsigned long long *__restrict__ nk)
@@ -72,7 +102,7 @@ __global__ __launch_bounds__(256) void k_bigsi_popcount(const uint32_t *__restri
     const uint32_t *b = bm + g * pitch;
     unsigned long long s = 0, q = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < pitch; i += (uint64_t)gridDim.x * 256) s += __popc(b[i]);
-    if (blockIdx.x == 0)
+    if (blockIdx.x == 0 && nk)
         for (uint64_t r = genome_rec_off[g] + threadIdx.x; r < genome_rec_off[g + 1]; r += 256) { const uint64_t l = rec_len[r]; if (l >= k) q += l - k + 1; }
     for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); q += __shfl_down(q, o); }
     if ((threadIdx.x & 63) == 0) { if (s) atomicAdd(&tc[g], s); if (q) atomicAdd(&nk[g], q); }
@@ -172,7 +202,10 @@ template <int p, int BX_PLANES> __device__ __forceinline__ void ripple_add(uint6
     }
 }
 // HB: row loads in flight per k-mer (num_hash when it is <= 4, else 4; a short last group repeats its last row: AND is idempotent)
-template <int HB, int BX_PLANES>
+// LIST (a minimizer index): the values come from the ordered per-read lists k_bigsi_minimizers wrote - seq64 = the values, rec_start[read] = where the
+// read's list begins, rec_len[read] = its entries, read_rec_off unused. A list is walked as ONE record whose windows are its entries (its "length" is
+// entries + k - 1), so the running index, down_sample and n are the arithmetic of the plain form.
+template <int HB, int BX_PLANES, bool LIST = false>
 __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict__ seq64, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
                                                      const uint64_t *__restrict__ read_rec_off, uint64_t n_reads, uint32_t kq, uint32_t d, uint64_t B, uint32_t h,
                                                      const uint64_t *__restrict__ M, uint64_t W, uint64_t nc, uint32_t *__restrict__ out_n,
@@ -185,11 +218,11 @@ __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict_
     const uint32_t k = kq_k(kq);
     const bool fwd_only = (kq & KQ_FWD) != 0;
     const uint64_t mask = kmer_mask(false, k);
-    const uint64_t ra = read_rec_off[read], rb = read_rec_off[read + 1];
+    const uint64_t ra = LIST ? read : read_rec_off[read], rb = LIST ? read + 1 : read_rec_off[read + 1];
     // n: the occurrences used
     uint64_t n64 = 0, jb = 0;
     for (uint64_t r = ra; r < rb; r++) {
-        const uint64_t len = rec_len[r];
+        const uint64_t len = rec_len[r] + (LIST ? k - 1 : 0);
         if (len < k) continue;
         const uint64_t cnt = len - k + 1, first = (jb + d - 1) / d * d;
         if (first < jb + cnt) n64 += (jb + cnt - 1 - first) / d + 1;
@@ -210,14 +243,17 @@ __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict_
         for (int p = 0; p < BX_PLANES; p++) P[p] = 0;
         jb = 0;
         for (uint64_t r = ra; r < rb; r++) {
-            const uint64_t len = rec_len[r];
+            const uint64_t len = rec_len[r] + (LIST ? k - 1 : 0);
             if (len < k) continue;
             const uint64_t rs = rec_start[r], cnt = len - k + 1, first = (jb + d - 1) / d * d;
             if (first < jb + cnt) {
                 const uint64_t nu = (jb + cnt - 1 - first) / d + 1, off0 = first - jb;
                 for (uint64_t c0 = 0; c0 < nu; c0 += 64) {
                     uint64_t h1 = 0, st = 0;
-                    if (c0 + lane < nu) bigsi_hash(kmer_at(seq64, rs + off0 + (c0 + lane) * d, k, mask, fwd_only), h1, st);
+                    if (c0 + lane < nu) {
+                        const uint64_t at = rs + off0 + (c0 + lane) * d;
+                        bigsi_hash(LIST ? seq64[at] : kmer_at(seq64, at, k, mask, fwd_only), h1, st);
+                    }
                     const uint32_t m = (uint32_t)(nu - c0 < 64 ? nu - c0 : 64);
                     for (uint32_t t = 0; t < m; t += G) {
                         const uint32_t src = t + grp;
@@ -287,6 +323,156 @@ __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict_
         }
     }
     if (lane == 0) { out_n[read] = n; out_col[read] = best_c; out_hits[read] = best_h; }
+}
+
+// ---- minimizer occurrences (SPEC 11.1) ---------------------------------------------------------------------------------------------------------
+constexpr uint32_t MZ_TILE = GS_BIGSI_MINI_TILE;       // new windows per tile: lane 0 of a tile repeats the last window of the tile before, so a_{s-1} is one shuffle away
+constexpr uint32_t MZ_POS = 64 + GS_BIGSI_KMAX;        // positions of a tile in LDS: 64 windows + the w - 1 <= 31 to their right (rounded up)
+__host__ __device__ static inline uint64_t mz_tiles(uint64_t windows) { return (windows + MZ_TILE - 1) / MZ_TILE; }
+
+// Per record the tiles in front of it inside its genome (rec_tpre), per genome its tiles and its windows (an upper bound of its occurrences; on a plain
+// index the k-mer occurrences themselves). One wavefront per genome.
+__global__ __launch_bounds__(256) void k_bigsi_tile_prefix(const uint64_t *__restrict__ rec_len, const uint64_t *__restrict__ genome_rec_off, uint64_t n_genomes,
+                                                           uint32_t k, uint64_t *__restrict__ rec_tpre, uint64_t *__restrict__ gen_tiles,
+                                                           uint64_t *__restrict__ gen_windows)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= n_genomes) return;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t r0 = genome_rec_off[g], r1 = genome_rec_off[g + 1];
+    unsigned long long run = 0, wins = 0;
+    for (uint64_t base = r0; base < r1; base += 64) {
+        const uint64_t r = base + lane;
+        unsigned long long t = 0, wn = 0;
+        if (r < r1) { const uint64_t l = rec_len[r]; if (l >= k) { wn = l - k + 1; t = (wn + MZ_TILE - 1) / MZ_TILE; } }
+        unsigned long long x = t;
+        for (uint32_t o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(x, o); if (lane >= o) x += y; }
+        if (r < r1) rec_tpre[r] = run + x - t;
+        run += __shfl(x, 63);
+        for (int o = 32; o > 0; o >>= 1) wn += __shfl_down(wn, o);
+        wins += __shfl(wn, 0);
+    }
+    if (lane == 0) { gen_tiles[g] = run; gen_windows[g] = wins; }
+}
+// off[r] = the windows of the reads in front of read r (an upper bound of their occurrences: where the read's list begins), off[n_reads] = all of them.
+// ONE workgroup, lanes take contiguous stretches of reads (as k_scan_u32, gs_radix.hip)
+__global__ __launch_bounds__(1024) void k_bigsi_window_prefix(const uint64_t *__restrict__ rec_len, const uint64_t *__restrict__ read_rec_off, uint64_t n_reads, uint32_t k,
+                                                              uint64_t *__restrict__ off)
+{
+    __shared__ uint64_t part[1024];
+    const uint64_t per = (n_reads + 1023) / 1024, b0 = (uint64_t)threadIdx.x * per, b = b0 < n_reads ? b0 : n_reads, e = b + per < n_reads ? b + per : n_reads;
+    uint64_t s = 0;
+    for (uint64_t r = b; r < e; r++)
+        for (uint64_t q = read_rec_off[r]; q < read_rec_off[r + 1]; q++) { const uint64_t l = rec_len[q]; if (l >= k) s += l - k + 1; }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (uint32_t o = 1; o < 1024; o <<= 1) {
+        const uint64_t v = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint64_t run = threadIdx.x ? part[threadIdx.x - 1] : 0;
+    for (uint64_t r = b; r < e; r++) {
+        off[r] = run;
+        for (uint64_t q = read_rec_off[r]; q < read_rec_off[r + 1]; q++) { const uint64_t l = rec_len[q]; if (l >= k) run += l - k + 1; }
+    }
+    if (threadIdx.x == 1023) off[n_reads] = part[1023];
+}
+
+struct MzLds { uint64_t h1[MZ_POS], st[MZ_POS], v[MZ_POS]; };
+// Tile j of the record of L >= k bases that starts at base rs: lane l holds window s = j * MZ_TILE + l. true: the window's minimizer is an occurrence
+// (window 0's, or another one than the window's before); v, h1, st: its value and hash. The workgroup is ONE wavefront; the answer of a window depends
+// on the record alone - on the tile only in which lane computes it.
+__device__ __forceinline__ bool mz_tile(const uint64_t *__restrict__ seq64, uint64_t rs, uint64_t L, uint64_t j, uint32_t k, uint32_t m, uint64_t mask_m, bool fwd_only,
+                                        MzLds &lds, uint64_t &v, uint64_t &h1, uint64_t &st)
+{
+    const uint32_t lane = threadIdx.x, w = k - m + 1;
+    const uint64_t p0 = j * MZ_TILE, np = L - m + 1;           // the tile's first position = its first window; the positions of the record
+    for (uint32_t i = lane; i < 64 + w - 1; i += 64) {         // (i < 95 < MZ_POS)
+        const uint64_t p = p0 + i;
+        uint64_t vv = 0, a = ~(uint64_t)0, b = 0;
+        if (p < np) { vv = kmer_at(seq64, rs + p, m, mask_m, fwd_only); bigsi_hash(vv, a, b); }     // (a position past the record: read by no valid window)
+        lds.v[i] = vv; lds.h1[i] = a; lds.st[i] = b;
+    }
+    __syncthreads();
+    const uint64_t s = p0 + lane;
+    const uint32_t a = lane + minimizer_pick(lds.h1 + lane, w);                                      // lane + w - 1 <= 63 + w - 1: written above
+    const uint32_t prev = (uint32_t)__shfl_up((int)a, 1);
+    const bool emit = s + k <= L && (s == 0 || (lane > 0 && a != prev));
+    v = lds.v[a]; h1 = lds.h1[a]; st = lds.st[a];
+    __syncthreads();                                           // the next tile overwrites
+    return emit;
+}
+struct MzArgs {
+    const uint64_t *seq64, *rec_start, *rec_len, *group_rec_off;      // the packed layout; a group = a genome (build) or a read (query)
+    const uint64_t *rec_tpre, *gen_tiles;                             // build: k_bigsi_tile_prefix
+    uint32_t kq, m;
+    uint32_t *bm; uint64_t pitch, B; uint32_t h; unsigned long long *nk;                           // MZ_BITS: the block's bitmaps, nk_c of its colours
+    uint64_t *vals; unsigned long long *cursor; uint64_t cap;                                      // MZ_LIST: one colour's value list
+    const uint64_t *voff; uint64_t *vcnt;                                                          // MZ_QUERY: where each read's list begins; its entries
+};
+enum { MZ_BITS = 0, MZ_LIST = 1, MZ_QUERY = 2 };
+// MZ_BITS / MZ_LIST: grid x = wavefronts that share a genome's tiles, y = genomes. MZ_QUERY: one wavefront per read, its records and tiles in order.
+template <int MODE> __global__ __launch_bounds__(64) void k_bigsi_minimizers(const MzArgs a)
+{
+    __shared__ MzLds lds;
+    const uint32_t lane = threadIdx.x, k = kq_k(a.kq), m = a.m;
+    const bool fwd_only = (a.kq & KQ_FWD) != 0;
+    const uint64_t mask_m = kmer_mask(false, m), lt = ((uint64_t)1 << lane) - 1;
+    uint64_t v, h1, st;
+    if constexpr (MODE == MZ_QUERY) {
+        const uint64_t read = blockIdx.x, base = a.voff[read], end = a.voff[read + 1];
+        uint64_t cnt = 0;
+        for (uint64_t r = a.group_rec_off[read]; r < a.group_rec_off[read + 1]; r++) {
+            const uint64_t L = a.rec_len[r];
+            if (L < k) continue;
+            const uint64_t rs = a.rec_start[r], nt = mz_tiles(L - k + 1);
+            for (uint64_t j = 0; j < nt; j++) {
+                const bool emit = mz_tile(a.seq64, rs, L, j, k, m, mask_m, fwd_only, lds, v, h1, st);
+                const uint64_t bal = __ballot(emit);
+                const uint64_t at = base + cnt + (uint64_t)__popcll(bal & lt);
+                if (emit && at < end) a.vals[at] = v;            // (occurrences never exceed windows: `end` is never reached)
+                cnt += (uint64_t)__popcll(bal);
+            }
+        }
+        if (lane == 0) a.vcnt[read] = cnt;
+    } else {
+        const uint64_t g = blockIdx.y, r0 = a.group_rec_off[g], r1 = a.group_rec_off[g + 1], nt = a.gen_tiles[g];
+        BitEmit be{a.bm + g * a.pitch, a.B, a.h};
+        unsigned long long fed = 0;
+        for (uint64_t t = blockIdx.x; t < nt; t += gridDim.x) {
+            uint64_t lo = r0, hi = r1;                           // the record that owns tile t: the last r with rec_tpre[r] <= t
+            while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (a.rec_tpre[mid] <= t) lo = mid; else hi = mid; }
+            const bool emit = mz_tile(a.seq64, a.rec_start[lo], a.rec_len[lo], t - a.rec_tpre[lo], k, m, mask_m, fwd_only, lds, v, h1, st);
+            const uint64_t bal = __ballot(emit);
+            if (bal == 0) continue;
+            if constexpr (MODE == MZ_BITS) {
+                if (emit) be.bits(h1, st);
+                fed += (unsigned long long)__popcll(bal);
+            } else {
+                unsigned long long at = 0;
+                if (lane == 0) at = atomicAdd(a.cursor, (unsigned long long)__popcll(bal));
+                at = shfl64(at, 0) + (unsigned long long)__popcll(bal & lt);
+                if (emit && at < a.cap) a.vals[at] = v;
+            }
+        }
+        if (MODE == MZ_BITS && lane == 0 && fed) atomicAdd(&a.nk[g], fed);
+    }
+}
+// the runs of one colour's sorted value list that the coverage filter keeps: their bits into the colour's bitmap, their lengths into nk_c
+__global__ __launch_bounds__(256) void k_bigsi_fill_runs(const uint64_t *__restrict__ uniq, const uint32_t *__restrict__ len, const uint32_t *__restrict__ nruns,
+                                                         uint32_t min_count, uint32_t *__restrict__ bm, uint64_t B, uint32_t h, unsigned long long *__restrict__ nk)
+{
+    const uint32_t nr = *nruns;
+    BitEmit be{bm, B, h};
+    unsigned long long fed = 0;
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < nr; r += (uint64_t)gridDim.x * 256) {
+        const uint32_t l = len[r];
+        if (l >= min_count) { be(uniq[r], 0, 0); fed += l; }
+    }
+    for (int o = 32; o > 0; o >>= 1) fed += __shfl_down(fed, o);
+    if ((threadIdx.x & 63) == 0 && fed) atomicAdd(nk, fed);
 }
 
 __global__ void k_bigsi_classify(uint64_t n_reads, const uint32_t *__restrict__ nk, const uint32_t *__restrict__ col, const uint32_t *__restrict__ hits,
@@ -402,7 +588,7 @@ static int bigsi_alloc(gs_ctx *c, const gs_bigsi_params *prm, uint64_t cap, gs_b
 static int write_all(FILE *f, const void *p, size_t n) { return n == 0 || fwrite(p, 1, n, f) == n ? 0 : -1; }
 static int read_all(FILE *f, void *p, size_t n) { return n == 0 || fread(p, 1, n, f) == n ? 0 : -1; }
 static const char BX_MAGIC[8] = {'G', 'S', 'B', 'I', 'G', 'S', 'I', '1'};
-constexpr uint32_t BX_VERSION = 1;
+constexpr uint32_t BX_VERSION = 1, BX_VERSION_MINI = 2;         // a plain index; a minimizer index (one more u32, m, after data_t)
 
 }  // namespace gs
 
@@ -422,6 +608,18 @@ int gs_bigsi_check_params(const gs_bigsi_params *p)
 
 int gs_bigsi_create(gs_ctx *c, const gs_bigsi_params *prm, uint64_t colour_capacity, gs_bigsi **out) { return gs::bigsi_alloc(c, prm, colour_capacity, out); }
 
+int gs_bigsi_create_mini(gs_ctx *c, const gs_bigsi_params *prm, uint32_t minimizer_len, uint64_t colour_capacity, gs_bigsi **out)
+{
+    int rc = gs_bigsi_check_params(prm);
+    if (rc) return rc;
+    GS_REQUIRE(minimizer_len >= 1 && minimizer_len < prm->k, GS_ERR_INVALID, "bigsig: minimizer length %u outside 1..k-1 (k = %u)", minimizer_len, prm->k);
+    if ((rc = gs::bigsi_alloc(c, prm, colour_capacity, out))) return rc;
+    (*out)->m = minimizer_len;
+    return GS_OK;
+}
+
+uint32_t gs_bigsi_minimizer_len(gs_bigsi *bx) { return bx ? bx->m : 0; }
+
 void gs_bigsi_free(gs_bigsi *bx)
 {
     if (!bx) return;
@@ -436,8 +634,66 @@ int gs_bigsi_info(gs_bigsi *bx, gs_bigsi_desc *out)
     return GS_OK;
 }
 
-int gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
-                           const uint64_t *genome_rec_off, uint64_t n_genomes)
+// One colour of the block under a coverage filter (SPEC 11.1): its occurrence values -> sorted -> runs -> the runs of at least min_count into its bitmap.
+// `windows`: the colour's windows (host copy) - the k-mer occurrences of a plain index, an upper bound of a minimizer index's.
+static int bigsi_filter_colour(gs_bigsi *bx, const void *seq, const uint64_t *rec_start, const uint64_t *rec_len, const uint64_t *rec_upre, const uint64_t *rec_tpre,
+                               const uint64_t *genome_rec_off, const uint64_t *gen_units, const uint64_t *gen_tiles, uint64_t windows, uint32_t min_count,
+                               uint32_t *bm, unsigned long long *nk)
+{
+    using namespace gs;
+    gs_ctx *c = bx->c;
+    if (windows == 0) return GS_OK;
+    const bool mini = bx->m != 0;
+    const uint64_t B = bx->prm.bloom_size;
+    GS_REQUIRE(mini || windows < ((uint64_t)1 << 32), GS_ERR_UNSUPPORTED,
+               "bigsig: %llu occurrences in one colour; the coverage filter sorts fewer than 2^32 per colour", (unsigned long long)windows);
+    PoolBuf vals(c, SL_BIGSI_LIST_VALS), alt(c, SL_BIGSI_LIST_ALT), len(c, SL_BIGSI_LIST_LEN), pos(c, SL_BIGSI_LIST_POS), radix(c, SL_BIGSI_LIST_RADIX),
+        ctr(c, SL_BIGSI_LIST_CTR);
+    int rc;
+    if ((rc = vals.alloc(8 * windows)) || (rc = ctr.alloc(16))) return rc;
+    unsigned long long *cursor = ctr.as<unsigned long long>();
+    uint32_t *nruns = ctr.as<uint32_t>() + 2;
+    GS_HIP_CHECK(hipMemsetAsync(ctr.p, 0, 16, c->stream));
+    const uint64_t nt = mz_tiles(windows) + 1;                  // at least the tiles of the colour when it is one record; more records: more, shorter tiles
+    const uint32_t parts = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(nt / 4, 1), (uint64_t)c->n_cu * 32);
+    // (with gs_ctx_profile on, the three steps are timed as families: emit = FAM_SKETCH, sort and run lengths = FAM_HAMMING, fill = FAM_INSERT)
+    if (mini) {
+        MzArgs a{};
+        a.seq64 = (const uint64_t *)seq; a.rec_start = rec_start; a.rec_len = rec_len; a.group_rec_off = genome_rec_off; a.rec_tpre = rec_tpre; a.gen_tiles = gen_tiles;
+        a.kq = bigsi_kq(bx->prm); a.m = bx->m; a.vals = vals.as<uint64_t>(); a.cursor = cursor; a.cap = windows;
+        ProfScope ps(c, FAM_SKETCH);
+        hipLaunchKernelGGL(k_bigsi_minimizers<MZ_LIST>, dim3(parts, 1), dim3(64), 0, c->stream, a);
+    } else {
+        ProfScope ps(c, FAM_SKETCH);
+        const uint32_t lp = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(windows / 32 / SK_THREADS, 1), (uint64_t)c->n_cu * 4);
+        hipLaunchKernelGGL(k_bigsi_list, dim3(lp), dim3(SK_THREADS), 0, c->stream, (const uint8_t *)seq, rec_start, rec_len, rec_upre, genome_rec_off, gen_units,
+                           bigsi_kq(bx->prm), vals.as<uint64_t>(), cursor, windows);
+    }
+    GS_HIP_CHECK(hipGetLastError());
+    unsigned long long n = 0;
+    GS_HIP_CHECK(hipMemcpyAsync(&n, cursor, 8, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    GS_REQUIRE(n <= windows, GS_ERR_STATE, "bigsig: %llu occurrences listed for %llu windows", n, (unsigned long long)windows);
+    GS_REQUIRE(n < ((uint64_t)1 << 32), GS_ERR_UNSUPPORTED, "bigsig: %llu occurrences in one colour; the coverage filter sorts fewer than 2^32 per colour", n);
+    if (n == 0) return GS_OK;
+    if ((rc = alt.alloc(8 * n)) || (rc = len.alloc(4 * n)) || (rc = pos.alloc(4 * n)) || (rc = radix.alloc(radix_scratch_bytes(n)))) return rc;
+    uint64_t *sorted = nullptr, *uniq = nullptr;
+    {
+        ProfScope ps(c, FAM_HAMMING);
+        if ((rc = radix_sort_u64(c, vals.as<uint64_t>(), alt.as<uint64_t>(), n, (int)(2 * (mini ? bx->m : bx->prm.k)), radix.p, &sorted))) return rc;
+        uniq = sorted == vals.as<uint64_t>() ? alt.as<uint64_t>() : vals.as<uint64_t>();
+        if ((rc = run_length_encode_u64(c, sorted, n, uniq, len.as<uint32_t>(), nruns, pos.as<uint32_t>(), radix.p))) return rc;
+    }
+    ProfScope ps(c, FAM_INSERT);
+    hipLaunchKernelGGL(k_bigsi_fill_runs, dim3((uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->n_cu * 8)), dim3(256), 0, c->stream, uniq, len.as<uint32_t>(), nruns,
+                       min_count, bm, B, bx->prm.num_hash, nk);
+    GS_HIP_CHECK(hipGetLastError());
+    return GS_OK;
+}
+
+// min_count <= 1: no filter
+static int bigsi_add_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                         const uint64_t *genome_rec_off, uint64_t n_genomes, uint32_t min_count)
 {
     using namespace gs;
     GS_REQUIRE(bx && (n_genomes == 0 || (seq && rec_start && rec_len && genome_rec_off)), GS_ERR_INVALID, "null argument");
@@ -449,12 +705,28 @@ int gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, co
     const uint64_t B = bx->prm.bloom_size, pitch = bitmap_pitch(B);
     const uint32_t kq = bigsi_kq(bx->prm);
     GS_REQUIRE((B + TR_ROWS - 1) / TR_ROWS < ((uint64_t)1 << 31), GS_ERR_UNSUPPORTED, "bigsig: bloom_size too large for the transpose grid");
+    const bool mini = bx->m != 0, filt = min_count >= 2;
     PoolBuf upre(c, SL_BIGSI_REC_UNITS), gunits(c, SL_BIGSI_GENOME_UNITS), bmb(c, SL_BIGSI_BITMAP);
+    PoolBuf tpre(c, SL_BIGSI_REC_TILES), gtiles(c, SL_BIGSI_GENOME_TILES), gwin(c, SL_BIGSI_GENOME_WINDOWS);
     int rc;
-    if ((rc = upre.alloc(8 * (n_rec + 1))) || (rc = gunits.alloc(8 * n_genomes))) return rc;
-    hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len, genome_rec_off, n_genomes, bx->prm.k,
-                       upre.as<uint64_t>(), gunits.as<uint64_t>());
-    GS_HIP_CHECK(hipGetLastError());
+    if (!mini) {
+        if ((rc = upre.alloc(8 * (n_rec + 1))) || (rc = gunits.alloc(8 * n_genomes))) return rc;
+        hipLaunchKernelGGL(k_unit_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_start, rec_len, genome_rec_off, n_genomes, bx->prm.k,
+                           upre.as<uint64_t>(), gunits.as<uint64_t>());
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    std::vector<uint64_t> windows;                                                  // per genome, on the host: the filter sizes each colour's list by it
+    if (mini || filt) {
+        if ((rc = tpre.alloc(8 * (n_rec + 1))) || (rc = gtiles.alloc(8 * n_genomes)) || (rc = gwin.alloc(8 * n_genomes))) return rc;
+        hipLaunchKernelGGL(k_bigsi_tile_prefix, dim3((uint32_t)((n_genomes + 3) / 4)), dim3(256), 0, c->stream, rec_len, genome_rec_off, n_genomes, bx->prm.k,
+                           tpre.as<uint64_t>(), gtiles.as<uint64_t>(), gwin.as<uint64_t>());
+        GS_HIP_CHECK(hipGetLastError());
+        if (filt) {
+            windows.resize(n_genomes);
+            GS_HIP_CHECK(hipMemcpyAsync(windows.data(), gwin.p, 8 * n_genomes, hipMemcpyDeviceToHost, c->stream));
+            GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        }
+    }
     // colours of a block: whole words of 64 up to BX_BLOCK, fewer when the bitmaps (bloom_size bits each) would take more than a quarter of the free memory
     size_t fr = 0, tot = 0;
     GS_HIP_CHECK(hipMemGetInfo(&fr, &tot));
@@ -478,12 +750,34 @@ int gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, co
         if (parts > maxp) parts = (uint32_t)maxp;
         if (parts < 1) parts = 1;
         c->last_sketch[2] = parts; c->last_sketch[3]++;
-        hipLaunchKernelGGL(k_bigsi_fill, dim3(parts, (uint32_t)ng), dim3(SK_THREADS), 0, c->stream, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(),
-                           genome_rec_off + g0, gunits.as<uint64_t>() + g0, kq, B, bx->prm.num_hash, bmb.as<uint32_t>(), pitch);
-        GS_HIP_CHECK(hipGetLastError());
+        unsigned long long *nk0 = bx->nk.as<unsigned long long>() + c0;
+        if (!mini && !filt) {
+            hipLaunchKernelGGL(k_bigsi_fill, dim3(parts, (uint32_t)ng), dim3(SK_THREADS), 0, c->stream, (const uint8_t *)seq, rec_start, rec_len, upre.as<uint64_t>(),
+                               genome_rec_off + g0, gunits.as<uint64_t>() + g0, kq, B, bx->prm.num_hash, bmb.as<uint32_t>(), pitch);
+            GS_HIP_CHECK(hipGetLastError());
+        } else {
+            GS_HIP_CHECK(hipMemsetAsync(nk0, 0, 8 * ng, c->stream));                 // counted by the kernels below, not from the record lengths
+            if (!filt) {
+                // a wavefront per MZ_TILE windows; as many as the tiles of an average genome, and no more than fill the device eight times over
+                const uint64_t avg_tiles = seq_bytes * 4 / MZ_TILE / n_genomes + 1;
+                const uint32_t mp = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((8 * 32 * (uint64_t)c->n_cu + ng - 1) / ng, 1), avg_tiles);
+                c->last_sketch[2] = mp;
+                MzArgs a{};
+                a.seq64 = (const uint64_t *)seq; a.rec_start = rec_start; a.rec_len = rec_len; a.group_rec_off = genome_rec_off + g0; a.rec_tpre = tpre.as<uint64_t>();
+                a.gen_tiles = gtiles.as<uint64_t>() + g0; a.kq = kq; a.m = bx->m; a.bm = bmb.as<uint32_t>(); a.pitch = pitch; a.B = B; a.h = bx->prm.num_hash; a.nk = nk0;
+                hipLaunchKernelGGL(k_bigsi_minimizers<MZ_BITS>, dim3(mp, (uint32_t)ng), dim3(64), 0, c->stream, a);
+                GS_HIP_CHECK(hipGetLastError());
+            } else {
+                for (uint64_t g = 0; g < ng; g++)                                   // filtered colours are read sets, few and large: one at a time
+                    if ((rc = bigsi_filter_colour(bx, seq, rec_start, rec_len, upre.as<uint64_t>(), tpre.as<uint64_t>(), genome_rec_off + g0 + g,
+                                                  mini ? nullptr : gunits.as<uint64_t>() + g0 + g, gtiles.as<uint64_t>() + g0 + g, windows[g0 + g], min_count,
+                                                  bmb.as<uint32_t>() + g * pitch, nk0 + g)))
+                        return rc;
+            }
+        }
         const uint32_t slices = (uint32_t)std::min<uint64_t>((pitch + 256 * 16 - 1) / (256 * 16), 1024);
         hipLaunchKernelGGL(k_bigsi_popcount, dim3(slices, (uint32_t)ng), dim3(256), 0, c->stream, bmb.as<uint32_t>(), pitch, rec_len, genome_rec_off + g0, bx->prm.k,
-                           bx->tc.as<unsigned long long>() + c0, bx->nk.as<unsigned long long>() + c0);
+                           bx->tc.as<unsigned long long>() + c0, (mini || filt) ? (unsigned long long *)nullptr : nk0);
         GS_HIP_CHECK(hipGetLastError());
         const uint64_t w0 = c0 / 64;
         const uint32_t cshift = (uint32_t)(c0 & 63), nw = (uint32_t)((cshift + ng + 63) / 64);
@@ -497,8 +791,24 @@ int gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, co
     return GS_OK;
 }
 
+int gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                           const uint64_t *genome_rec_off, uint64_t n_genomes)
+{
+    return bigsi_add_dev(bx, seq, seq_bytes, rec_start, rec_len, n_rec, genome_rec_off, n_genomes, 1);
+}
+int gs_bigsi_add_batch_min_count_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                                     const uint64_t *genome_rec_off, uint64_t n_genomes, uint32_t min_count)
+{
+    return bigsi_add_dev(bx, seq, seq_bytes, rec_start, rec_len, n_rec, genome_rec_off, n_genomes, min_count);
+}
+
 int gs_bigsi_add_batch(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end, uint64_t n_rec,
                        const uint64_t *genome_rec_off, uint64_t n_genomes)
+{
+    return gs_bigsi_add_batch_min_count(bx, text, qual, min_phred, rec_begin, rec_end, n_rec, genome_rec_off, n_genomes, 1);
+}
+int gs_bigsi_add_batch_min_count(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end, uint64_t n_rec,
+                                 const uint64_t *genome_rec_off, uint64_t n_genomes, uint32_t min_count)
 {
     using namespace gs;
     GS_REQUIRE(bx && (n_genomes == 0 || ((text || n_rec == 0) && genome_rec_off && (n_rec == 0 || (rec_begin && rec_end)))), GS_ERR_INVALID, "null argument");
@@ -510,7 +820,7 @@ int gs_bigsi_add_batch(gs_bigsi *bx, const void *text, const void *qual, uint32_
     Staged s(c);
     int rc = stage_text(c, bx->prm.k, text, qual, min_phred, rec_begin, rec_end, n_rec, genome_rec_off, n_genomes, s);
     if (rc) return rc;
-    rc = gs_bigsi_add_batch_dev(bx, s.seq.p, s.seq_bytes, s.rs.as<uint64_t>(), s.rl.as<uint64_t>(), s.n_seg, s.go.as<uint64_t>(), n_genomes);
+    rc = bigsi_add_dev(bx, s.seq.p, s.seq_bytes, s.rs.as<uint64_t>(), s.rl.as<uint64_t>(), s.n_seg, s.go.as<uint64_t>(), n_genomes, min_count);
     if (rc) return rc;
     GS_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GS_OK;
@@ -565,6 +875,44 @@ int gs_bigsi_query_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const 
     GS_CTX_LOCK(c);
     const uint32_t h = bx->prm.num_hash, hb = h < 4 ? h : 4;
     const dim3 grid((uint32_t)((n_reads + 3) / 4)), block(256);
+    if (bx->m) {
+        // a minimizer index: the ordered occurrence list of every read first (where a list begins: the windows in front of it), then the list form
+        GS_REQUIRE(n_reads < ((uint64_t)1 << 31), GS_ERR_INVALID, "too many reads in one batch");
+        PoolBuf qoff(c, SL_BIGSI_Q_OFF), qcnt(c, SL_BIGSI_Q_CNT), qv(c, SL_BIGSI_Q_VALS);
+        int rc;
+        if ((rc = qoff.alloc(8 * (n_reads + 1))) || (rc = qcnt.alloc(8 * n_reads))) return rc;
+        hipLaunchKernelGGL(k_bigsi_window_prefix, dim3(1), dim3(1024), 0, c->stream, rec_len, read_rec_off, n_reads, bx->prm.k, qoff.as<uint64_t>());
+        GS_HIP_CHECK(hipGetLastError());
+        uint64_t total = 0;
+        GS_HIP_CHECK(hipMemcpyAsync(&total, qoff.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(hipStreamSynchronize(c->stream));                               // the lists are sized by it
+        if ((rc = qv.alloc(8 * std::max<uint64_t>(total, 1)))) return rc;
+        MzArgs a{};
+        a.seq64 = (const uint64_t *)seq; a.rec_start = rec_start; a.rec_len = rec_len; a.group_rec_off = read_rec_off; a.kq = bigsi_kq(bx->prm); a.m = bx->m;
+        a.vals = qv.as<uint64_t>(); a.voff = qoff.as<uint64_t>(); a.vcnt = qcnt.as<uint64_t>();
+        {   // (with gs_ctx_profile on: the pre-pass is FAM_SKETCH, the look-ups FAM_SEARCH)
+            ProfScope ps(c, FAM_SKETCH);
+            hipLaunchKernelGGL(k_bigsi_minimizers<MZ_QUERY>, dim3((uint32_t)n_reads), dim3(64), 0, c->stream, a);
+        }
+        GS_HIP_CHECK(hipGetLastError());
+        ProfScope ps(c, FAM_SEARCH);
+#define GS_BX_LAUNCH_LIST(HB)                                                                                                                                \
+    do {                                                                                                                                                     \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_SHORT, true>), grid, block, 0, c->stream, qv.as<uint64_t>(), qoff.as<uint64_t>(), qcnt.as<uint64_t>(), \
+                           (const uint64_t *)nullptr, n_reads, bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n,     \
+                           n_kmers, best_colour, best_hits, counts);                                                                                         \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_LONG, true>), grid, block, 0, c->stream, qv.as<uint64_t>(), qoff.as<uint64_t>(), qcnt.as<uint64_t>(),  \
+                           (const uint64_t *)nullptr, n_reads, bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n,     \
+                           n_kmers, best_colour, best_hits, counts);                                                                                         \
+    } while (0)
+        if (hb == 1) GS_BX_LAUNCH_LIST(1);
+        else if (hb == 2) GS_BX_LAUNCH_LIST(2);
+        else if (hb == 3) GS_BX_LAUNCH_LIST(3);
+        else GS_BX_LAUNCH_LIST(4);
+#undef GS_BX_LAUNCH_LIST
+        GS_HIP_CHECK(hipGetLastError());
+        return GS_OK;
+    }
 #define GS_BX_LAUNCH(HB)                                                                                                                                     \
     do {                                                                                                                                                     \
         hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_SHORT>), grid, block, 0, c->stream, (const uint64_t *)seq, rec_start, rec_len, read_rec_off, n_reads, \
@@ -652,7 +1000,7 @@ int gs_bigsi_accessions(gs_bigsi *bx, char *buf, uint64_t cap_bytes, uint64_t *b
     return GS_OK;
 }
 
-// magic, version, k, num_hash, data_t (u32 each), bloom_size, n_colours (u64), per colour: u32 length + accession bytes, t_c[n], nk_c[n] (u64), then
+// magic, version, k, num_hash, data_t (u32 each; a minimizer index: version 2 and one more u32, m), bloom_size, n_colours (u64), per colour: u32 length + accession bytes, t_c[n], nk_c[n] (u64), then
 // bloom_size rows of ceil(n_colours / 64) u64 words
 int gs_bigsi_save(gs_bigsi *bx, const char *path)
 {
@@ -663,8 +1011,8 @@ int gs_bigsi_save(gs_bigsi *bx, const char *path)
     FILE *f = fopen(path, "wb");
     GS_REQUIRE(f, GS_ERR_IO, "cannot write %s: %s", path, strerror(errno));
     const uint64_t n = bx->n, B = bx->prm.bloom_size, wu = (n + 63) / 64;
-    const uint32_t head[4] = {BX_VERSION, bx->prm.k, bx->prm.num_hash, bx->prm.data_t};
-    int bad = write_all(f, BX_MAGIC, 8) | write_all(f, head, 16) | write_all(f, &B, 8) | write_all(f, &n, 8);
+    const uint32_t head[5] = {bx->m ? BX_VERSION_MINI : BX_VERSION, bx->prm.k, bx->prm.num_hash, bx->prm.data_t, bx->m};
+    int bad = write_all(f, BX_MAGIC, 8) | write_all(f, head, bx->m ? 20 : 16) | write_all(f, &B, 8) | write_all(f, &n, 8);
     for (uint64_t i = 0; i < n && !bad; i++) {
         const std::string nm = i < bx->names.size() ? bx->names[i] : std::string();
         const uint32_t l = (uint32_t)nm.size();
@@ -694,11 +1042,14 @@ int gs_bigsi_load(gs_ctx *c, const char *path, uint64_t colour_capacity, gs_bigs
     GS_REQUIRE(c && path && out, GS_ERR_INVALID, "null argument");
     FILE *f = fopen(path, "rb");
     GS_REQUIRE(f, GS_ERR_IO, "cannot read %s: %s", path, strerror(errno));
-    char magic[8]; uint32_t head[4]; uint64_t B = 0, n = 0;
-    int bad = read_all(f, magic, 8) | read_all(f, head, 16) | read_all(f, &B, 8) | read_all(f, &n, 8);
-    if (bad || memcmp(magic, BX_MAGIC, 8) != 0 || head[0] != BX_VERSION || n >= ((uint64_t)1 << 32)) {
+    char magic[8]; uint32_t head[5] = {0, 0, 0, 0, 0}; uint64_t B = 0, n = 0;
+    int bad = read_all(f, magic, 8) | read_all(f, head, 16);
+    const bool mini = !bad && head[0] == BX_VERSION_MINI;
+    if (mini) bad |= read_all(f, head + 4, 4);
+    bad |= read_all(f, &B, 8) | read_all(f, &n, 8);
+    if (bad || memcmp(magic, BX_MAGIC, 8) != 0 || (head[0] != BX_VERSION && !mini) || (mini && (head[4] < 1 || head[4] >= head[1])) || n >= ((uint64_t)1 << 32)) {
         fclose(f);
-        GS_REQUIRE(false, GS_ERR_IO, "%s is not a bigsig index of this library (version %u)", path, BX_VERSION);
+        GS_REQUIRE(false, GS_ERR_IO, "%s is not a bigsig index of this library (versions %u and %u)", path, BX_VERSION, BX_VERSION_MINI);
     }
     gs_bigsi_params prm{};
     prm.k = head[1]; prm.num_hash = head[2]; prm.data_t = head[3]; prm.bloom_size = B;
@@ -737,6 +1088,7 @@ int gs_bigsi_load(gs_ctx *c, const char *path, uint64_t colour_capacity, gs_bigs
         GS_REQUIRE(false, GS_ERR_HIP, "loading the matrix failed: %s", hipGetErrorString(e));
     }
     bx->n = n;
+    bx->m = head[4];
     bool any = false;
     for (const std::string &s : names) any = any || !s.empty();
     if (any) bx->names.swap(names);
@@ -765,6 +1117,54 @@ int gs_bigsi_split(const void *text, const void *qual, uint64_t n, uint32_t min_
                        cnt++;
                    },
                    [](int) {});
+    *n_out = cnt;
+    return GS_OK;
+}
+
+int gs_bigsi_minimizers(const void *text, const void *qual, uint64_t n, uint32_t min_phred, uint32_t k, uint32_t m, uint32_t data_t, uint64_t cap, uint64_t *value_out,
+                        uint64_t *pos_out, uint64_t *n_out)
+{
+    GS_REQUIRE((text || n == 0) && n_out, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(k >= 1 && k <= GS_BIGSI_KMAX && m >= 1 && m < k, GS_ERR_INVALID, "bigsig: window %u / minimizer %u outside 1 <= m < k <= 32", k, m);
+    GS_REQUIRE(data_t == GS_DATA_DNA || data_t == GS_DATA_DNA_FWD, GS_ERR_INVALID, "bigsig: data type %u is not DNA", data_t);
+    const uint8_t *tx = (const uint8_t *)text;
+    const bool fwd_only = data_t == GS_DATA_DNA_FWD;
+    const uint32_t w = k - m + 1;
+    const uint64_t mask = ((uint64_t)1 << (2 * m)) - 1;        // m <= 31
+    std::vector<uint8_t> codes;
+    std::vector<uint64_t> offs, vals, keys;
+    uint64_t cnt = 0;
+    gs::split_text(tx, (const uint8_t *)qual, 0, n, min_phred,
+                   [&](uint64_t begin, uint64_t L) {
+                       if (L >= k) {
+                           offs.clear(); vals.clear(); keys.clear();
+                           for (uint64_t i = begin; offs.size() < L; i++)
+                               if (tx[i] != '\n' && tx[i] != '\r') offs.push_back(i);
+                           uint64_t fwd = 0, rc = 0;
+                           for (uint64_t i = 0; i < L; i++) {                 // the m-mer that ends at base i (SPEC 1.1 with k := m)
+                               fwd = ((fwd << 2) | codes[i]) & mask;
+                               rc = (rc >> 2) | ((uint64_t)(3 - codes[i]) << (2 * (m - 1)));
+                               if (i + 1 >= m) {
+                                   const uint64_t v = fwd_only || fwd < rc ? fwd : rc;
+                                   uint64_t h1, st;
+                                   gs::bigsi_hash(v, h1, st);
+                                   vals.push_back(v); keys.push_back(h1);
+                               }
+                           }
+                           uint64_t prev = 0;
+                           for (uint64_t s = 0; s + k <= L; s++) {
+                               const uint64_t a = s + gs::minimizer_pick(keys.data() + s, w);
+                               if (s == 0 || a != prev) {
+                                   if (cnt < cap && value_out) value_out[cnt] = vals[a];
+                                   if (cnt < cap && pos_out) pos_out[cnt] = offs[a];
+                                   cnt++;
+                               }
+                               prev = a;
+                           }
+                       }
+                       codes.clear();
+                   },
+                   [&](int code) { codes.push_back((uint8_t)code); });
     *n_out = cnt;
     return GS_OK;
 }

@@ -59,6 +59,10 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* bigsig (gs_bigsi.hip): unit prefix of a build, the colour block's bitmaps, staging of the host forms and of gs_bigsi_rows */                   \
     X(BIGSI_REC_UNITS) X(BIGSI_GENOME_UNITS) X(BIGSI_BITMAP) X(BIGSI_SEQ) X(BIGSI_REC_START) X(BIGSI_REC_LEN) X(BIGSI_GROUP_OFF) X(BIGSI_OUT_N)       \
     X(BIGSI_OUT_COLOUR) X(BIGSI_OUT_HITS) X(BIGSI_OUT_COUNTS) X(BIGSI_ROW_LIST) X(BIGSI_ROW_WORDS)                                                    \
+    /* bigsig, minimizer indexes and the coverage filter: tile prefix of a build, per-genome window counts, the ordered per-read lists of a query */ \
+    X(BIGSI_REC_TILES) X(BIGSI_GENOME_TILES) X(BIGSI_GENOME_WINDOWS) X(BIGSI_Q_OFF) X(BIGSI_Q_CNT) X(BIGSI_Q_VALS)                                    \
+    /* bigsig, sort-count-filter build of one colour: value list and its second buffer, run lengths, head positions, radix counts, cursor + runs */  \
+    X(BIGSI_LIST_VALS) X(BIGSI_LIST_ALT) X(BIGSI_LIST_LEN) X(BIGSI_LIST_POS) X(BIGSI_LIST_RADIX) X(BIGSI_LIST_CTR)                                    \
     /* comm (gs_topk_merge_dev) */                                                                                                                    \
     X(COMM_ID_OFFSET)
 

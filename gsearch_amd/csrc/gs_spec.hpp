@@ -393,6 +393,18 @@ GS_HD void bigsi_hash(uint64_t v, uint64_t &h1, uint64_t &step)
     step = splitmix_mix(x + 2 * GS_GAMMA) | 1;
 }
 GS_HD uint64_t bigsi_pos(uint64_t h1, uint64_t step, uint32_t i, uint64_t B) { return mulhi64(h1 + (uint64_t)i * step, B); }
+// SPEC 11.1: the minimizer of one window - the offset in [0, w) of the smallest of key[0..w), the leftmost of equal keys. Host (gs_bigsi_minimizers, keys in a
+// vector) and device (k_bigsi_minimizers, keys in LDS) share it; the occurrences are window 0's and every later window's that differs from the one before.
+GS_HD uint32_t minimizer_pick(const uint64_t *key, uint32_t w)
+{
+    uint64_t bk = key[0];
+    uint32_t bp = 0;
+    for (uint32_t i = 1; i < w; i++) {
+        const uint64_t x = key[i];
+        if (x < bk) { bk = x; bp = i; }
+    }
+    return bp;
+}
 // P(X >= x0), X ~ Binomial(n, p), p = (t_c / B)^h: each line one IEEE f64 operation per operator, LN / EXP of SPEC 2
 GS_HD double bigsi_tail(uint64_t t_c, uint64_t B, uint32_t h, uint32_t n, uint32_t x0)
 {

@@ -410,16 +410,17 @@ int      gs_index_search_stats(gs_index *, uint64_t out[8], int reset);
 /* ---------------------------------------------------------------------------------------------- */
 /* bigsig (binaux/src/bin/bigsig.rs): a bit-sliced Bloom index (BIGSI) of reference genomes - bloom_size rows, one column ("colour") per genome in
  * the order added - and the genome each sequencing read comes from. Arithmetic: SPEC.md 11. A k-mer never contains a non-ACGT base (or, with
- * quality bytes, a base below min_phred): such a base ends a segment. minimizer / coverage_filter (bigsig's -m and -f) other than 0 are
- * GS_ERR_UNSUPPORTED. */
+ * quality bytes, a base below min_phred): such a base ends a segment. The fields minimizer / coverage_filter of gs_bigsi_params other than 0 are
+ * GS_ERR_UNSUPPORTED: bigsig's -m is a property of the index and comes in through gs_bigsi_create_mini, its -f is an argument of one build call,
+ * gs_bigsi_add_batch_min_count[_dev] (SPEC.md 11.1). */
 typedef struct gs_bigsi gs_bigsi;
 typedef struct {
     uint32_t k;                  /* 1..32 (15 accepted) */
     uint32_t num_hash;           /* 1..16 rows per k-mer */
     uint64_t bloom_size;         /* rows, 1 <= bloom_size < 2^40, any value */
     uint32_t data_t;             /* GS_DATA_DNA (canonical k-mers) or GS_DATA_DNA_FWD */
-    uint32_t minimizer;          /* 0 (bigsig -m: GS_ERR_UNSUPPORTED) */
-    uint32_t coverage_filter;    /* 0 (bigsig -f: GS_ERR_UNSUPPORTED) */
+    uint32_t minimizer;          /* 0 (anything else: GS_ERR_UNSUPPORTED; a minimizer index is made by gs_bigsi_create_mini) */
+    uint32_t coverage_filter;    /* 0 (anything else: GS_ERR_UNSUPPORTED; the filter is the min_count of gs_bigsi_add_batch_min_count) */
 } gs_bigsi_params;
 typedef struct {
     gs_bigsi_params prm;
@@ -429,6 +430,11 @@ typedef struct {
 int    gs_bigsi_check_params(const gs_bigsi_params *prm);
 /* the matrix (bloom_size x row_words u64, zeroed) is allocated here: the colour capacity is fixed */
 int    gs_bigsi_create(gs_ctx *ctx, const gs_bigsi_params *prm, uint64_t colour_capacity, gs_bigsi **out);
+/* A minimizer index (SPEC 11.1): prm->k is the window length, minimizer_len = m the length of the m-mers that are inserted and looked up, one per run of
+ * windows that share their minimizer. m = 0 or m >= k: GS_ERR_INVALID. Every call below works on it as it is: the index knows its m. */
+int    gs_bigsi_create_mini(gs_ctx *ctx, const gs_bigsi_params *prm, uint32_t minimizer_len, uint64_t colour_capacity, gs_bigsi **out);
+uint32_t gs_bigsi_minimizer_len(gs_bigsi *bx);      /* 0: a plain index */
+#define GS_BIGSI_MINI_TILE 63u      /* windows a wavefront of the minimizer kernel takes at a time; no result depends on it */
 void   gs_bigsi_free(gs_bigsi *bx);
 int    gs_bigsi_info(gs_bigsi *bx, gs_bigsi_desc *out);
 /* n_genomes new colours, in input order; the layout of gs_sketch_batch_dev (2-bit packed, every record free of invalid bases). Past the capacity: GS_ERR_STATE */
@@ -438,6 +444,13 @@ int    gs_bigsi_add_batch_dev(gs_bigsi *bx, const void *seq_dev, uint64_t seq_by
  * qual (optional): quality byte of text[i] at qual[i]; a base with qual[i] - 33 < min_phred counts as non-ACGT. The library splits and packs (a host loop). */
 int    gs_bigsi_add_batch(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end,
                           uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes);
+/* The same with a coverage filter (SPEC 11.1): within each new colour only values that occur at least min_count times are inserted, and nk_c counts their
+ * occurrences; min_count <= 1: no filter, the calls above bit for bit. A colour whose every value is filtered keeps its number with t_c = 0. One colour holds
+ * fewer than 2^32 occurrences here (GS_ERR_UNSUPPORTED beyond); its value list is sorted on the device, one colour at a time. */
+int    gs_bigsi_add_batch_min_count_dev(gs_bigsi *bx, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev,
+                                        uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes, uint32_t min_count);
+int    gs_bigsi_add_batch_min_count(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end,
+                                    uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes, uint32_t min_count);
 /* colours [first, first + n): bits set in the column (t_c) and k-mer occurrences fed (nk_c); either output may be NULL */
 int    gs_bigsi_bits_set(gs_bigsi *bx, uint64_t first, uint64_t n, uint64_t *t_out, uint64_t *nk_out);
 /* the named rows -> words_out[n x row_words] (HOST) */
@@ -458,7 +471,8 @@ int    gs_bigsi_classify_dev(gs_bigsi *bx, uint64_t n_reads, const uint32_t *n_k
 /* the accessions of the colours (n == n_colours); read back NUL-terminated, back to back: buf NULL to size (*bytes_out) */
 int    gs_bigsi_set_accessions(gs_bigsi *bx, const char *const *names, uint64_t n);
 int    gs_bigsi_accessions(gs_bigsi *bx, char *buf, uint64_t cap_bytes, uint64_t *bytes_out);
-/* own little-endian file (SPEC 11; upstream's .bxi is a bincode of crate types). load: colour_capacity 0 = the file's n_colours */
+/* own little-endian file (SPEC 11; upstream's .bxi is a bincode of crate types): version 1 for a plain index, version 2 (it holds m) for a minimizer
+ * index; load takes both. load: colour_capacity 0 = the file's n_colours */
 int    gs_bigsi_save(gs_bigsi *bx, const char *path);
 int    gs_bigsi_load(gs_ctx *ctx, const char *path, uint64_t colour_capacity, gs_bigsi **out);
 /* host arithmetic of SPEC 11, no device: the num_hash rows of k-mer value v; the segments of a text (begin = offset of the first base, len in bases,
@@ -467,6 +481,10 @@ int    gs_bigsi_positions(uint64_t v, uint32_t num_hash, uint64_t bloom_size, ui
 int    gs_bigsi_split(const void *text, const void *qual, uint64_t n, uint32_t min_phred, uint64_t min_len, uint64_t cap, uint64_t *seg_begin,
                       uint64_t *seg_len, uint64_t *n_out);
 double gs_bigsi_tail(uint64_t t_c, uint64_t bloom_size, uint32_t num_hash, uint32_t n_kmers, uint32_t best_hits);
+/* host arithmetic of SPEC 11.1, no device: the minimizer occurrences of one text (window k, minimizer m, 1 <= m < k <= 32) in order - value_out = the m-mer value,
+ * pos_out = the offset in text of its first base. *n_out = their number; the arrays are filled up to cap entries and may be NULL to count only. */
+int    gs_bigsi_minimizers(const void *text, const void *qual, uint64_t n, uint32_t min_phred, uint32_t k, uint32_t m, uint32_t data_t, uint64_t cap,
+                           uint64_t *value_out, uint64_t *pos_out, uint64_t *n_out);
 /* `{prefix}_reads.txt`: read_id, accession | no_hits, best_hits, n_kmers, accept | reject, tab-separated, one line per read; `{prefix}_counts.txt`:
  * accession, reads over the accepted reads (descending by count, then by accession), then a `reject` and a `no_hits` line. Host only. */
 int    gs_bigsig_write_reads(const char *prefix, const char *const *accessions, uint64_t n_colours, const char *const *read_ids, uint64_t n_reads,

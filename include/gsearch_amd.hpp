@@ -210,21 +210,26 @@ inline double aai(double sim, uint32_t k) { return gs_aai(sim, k); }
 struct BigsiHits { std::vector<uint32_t> n_kmers, best_colour, best_hits; std::vector<double> tail; std::vector<uint8_t> accept; };
 class Bigsi {
 public:
-    Bigsi(Context &ctx, uint32_t k, uint32_t num_hash, uint64_t bloom_size, uint64_t colour_capacity, DataType dt = DataType::DNA) : ctx_(&ctx)
+    // minimizer_len = m > 0: a minimizer index (SPEC 11.1) of window length k
+    Bigsi(Context &ctx, uint32_t k, uint32_t num_hash, uint64_t bloom_size, uint64_t colour_capacity, DataType dt = DataType::DNA, uint32_t minimizer_len = 0)
+        : ctx_(&ctx)
     {
         const gs_bigsi_params p{k, num_hash, bloom_size, (uint32_t)dt, 0, 0};
-        check(gs_bigsi_create(ctx.get(), &p, colour_capacity, &bx_));
+        if (minimizer_len) check(gs_bigsi_create_mini(ctx.get(), &p, minimizer_len, colour_capacity, &bx_));
+        else check(gs_bigsi_create(ctx.get(), &p, colour_capacity, &bx_));
     }
+    uint32_t minimizer_len() const { return gs_bigsi_minimizer_len(bx_); }
     Bigsi(Context &ctx, const std::string &path, uint64_t colour_capacity = 0) : ctx_(&ctx) { check(gs_bigsi_load(ctx.get(), path.c_str(), colour_capacity, &bx_)); }
     ~Bigsi() { gs_bigsi_free(bx_); }
     Bigsi(const Bigsi &) = delete;
     Bigsi &operator=(const Bigsi &) = delete;
     gs_bigsi *get() const { return bx_; }
     gs_bigsi_desc info() const { gs_bigsi_desc d; check(gs_bigsi_info(bx_, &d)); return d; }
-    void add_genomes(const std::vector<std::vector<std::string>> &genomes, const std::vector<std::string> &accessions = {})
+    // min_count >= 2: the coverage filter - within each colour only values seen that often are inserted
+    void add_genomes(const std::vector<std::vector<std::string>> &genomes, const std::vector<std::string> &accessions = {}, uint32_t min_count = 1)
     {
         Text t(genomes);
-        check(gs_bigsi_add_batch(bx_, t.text.data(), nullptr, 0, t.begin.data(), t.end.data(), t.begin.size(), t.off.data(), genomes.size()));
+        check(gs_bigsi_add_batch_min_count(bx_, t.text.data(), nullptr, 0, t.begin.data(), t.end.data(), t.begin.size(), t.off.data(), genomes.size(), min_count));
         if (!accessions.empty()) {
             names_.insert(names_.end(), accessions.begin(), accessions.end());
             std::vector<const char *> p;

@@ -3,7 +3,10 @@
 identification of reads cut from them (and of reads from genomes that are not in the index), all through the device forms.
 Reports genomes/s and bit-sets/s of the build; reads/s, row look-ups/s and gathered bytes/s of the query next to a device-to-device copy rate taken in
 the same run; the classify time; and checks a sample of reads and one column against the numpy restatement (tests/pyref_bigsi.py).
-usage: bigsi_rate.py [--genomes N] [--mbp L] [--log2-rows R] [--hashes H] [--k K] [--reads Q] [--down-sample D]"""
+--minimizer M adds, after the plain legs and in the same run, the same build and query on a minimizer index of window K and minimizer length M (SPEC 11.1),
+with the share of the query time spent in k_bigsi_minimizers; --min-count F adds the build of a few colours under the coverage filter with its split into
+emit / sort / fill (on the plain index, and on the minimizer index when --minimizer is given). The splits come from the event timers of gs_ctx_profile.
+usage: bigsi_rate.py [--genomes N] [--mbp L] [--log2-rows R] [--hashes H] [--k K] [--reads Q] [--down-sample D] [--minimizer M] [--min-count F]"""
 import argparse, os, sys, time
 import ctypes as C
 import numpy as np
@@ -12,6 +15,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gsearch_amd as G
 import pyref_bigsi as PR
+import pyref_bigsi_mini as PM
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--genomes", type=int, default=4096)
@@ -23,6 +27,9 @@ ap.add_argument("--reads", type=int, default=2_000_000)
 ap.add_argument("--read-len", type=int, default=150)
 ap.add_argument("--down-sample", type=int, default=1)
 ap.add_argument("--chunk", type=int, default=512)
+ap.add_argument("--minimizer", type=int, default=0)
+ap.add_argument("--min-count", type=int, default=0)
+ap.add_argument("--filter-colours", type=int, default=4)
 a = ap.parse_args()
 
 ctx = G.Context(0)
@@ -139,3 +146,107 @@ for r in mine:
     v = PR.kmers([g0[s:s + RL]], k)[:: a.down_sample]
     ok = ok and int(n_used[r]) == len(v) and int(hits[r]) == len(v) and int(col[r]) == 0
 print("query: %d reads cut from genome 0 against pyref_bigsi (n, best colour, best hits = n): %s" % (len(mine), "equal" if ok else "MISMATCH"), flush=True)
+
+
+# ---- the minimizer index and the coverage filter, beside the plain legs above -------------------------------------------------------------------------
+FAM_SKETCH, FAM_HAMMING, FAM_SEARCH, FAM_INSERT = 0, 1, 2, 3           # gs_internal.hpp: the families the steps of gs_bigsi.hip are timed as
+if a.minimizer or a.min_count > 1:
+    bx.close()
+    for p in (d_seq, d_rs, d_rl, d_go):
+        ctx.free(p)
+    d_gen = ctx.alloc(chunk * words * 8 + 64)
+    g_rs, g_rl, g_go = ctx.alloc(8 * chunk), ctx.alloc(8 * chunk), ctx.alloc(8 * (chunk + 1))
+    ctx.upload(g_rs, np.arange(chunk, dtype=np.uint64) * np.uint64(words * 32)); ctx.upload(g_rl, np.full(chunk, L, np.uint64))
+    ctx.upload(g_go, np.arange(chunk + 1, dtype=np.uint64))
+
+
+def filter_leg(m, label):
+    nf = min(a.filter_colours, chunk)
+    fx = G.Bigsi(k, h, B, nf, ctx=ctx, minimizer_len=m)
+    chk(lib.gs_synth_dna_dev(ctx.h, seed, 0, nf, L, d_gen))
+    ctx.sync()
+    ctx.profile(True)
+    for fam in (FAM_SKETCH, FAM_HAMMING, FAM_INSERT):
+        ctx.profile_read(fam)
+    t0 = time.perf_counter()
+    fx.add_genomes_dev(d_gen, nf * words * 8 + 64, g_rs, g_rl, nf, g_go, nf, min_count=a.min_count)
+    ctx.sync()
+    tb = time.perf_counter() - t0
+    emit, srt, fill = (ctx.profile_read(fam)[0] / 1e3 for fam in (FAM_SKETCH, FAM_HAMMING, FAM_INSERT))
+    ctx.profile(False)
+    t, nk_ = fx.bits_set(return_kmers=True)
+    print("%s build with min_count %d: %d colours of %.1f Mbp in %.3f s: %.2f genomes/s; emit %.3f s, sort + run lengths %.3f s, fill %.4f s (kernels); "
+          "kept occurrences %d, bits %d (synthetic genomes repeat no value: the filter keeps nothing)" %
+          (label, a.min_count, nf, L / 1e6, tb, nf / tb, emit, srt, fill, int(nk_.sum()), int(t.sum())), flush=True)
+    fx.close()
+
+
+if a.min_count > 1:
+    filter_leg(0, "plain")
+if a.minimizer:
+    m = a.minimizer
+    w = k - m + 1
+    mx = G.Bigsi(k, h, B, N, ctx=ctx, minimizer_len=m)
+    t_build, per_chunk = 0.0, []
+    for first in range(0, N, chunk):
+        c = min(chunk, N - first)
+        chk(lib.gs_synth_dna_dev(ctx.h, seed, first, c, L, d_gen))
+        ctx.sync()
+        t0 = time.perf_counter()
+        mx.add_genomes_dev(d_gen, c * words * 8 + 64, g_rs, g_rl, c, g_go, c)
+        ctx.sync()
+        per_chunk.append(time.perf_counter() - t0)
+        t_build += per_chunk[-1]
+    t, nkm = mx.bits_set(return_kmers=True)
+    print("minimizer (%d, %d) build: %d genomes in %.3f s (first chunk %.3f s, the others %.3f s each): %.1f genomes/s, %.3g bit-sets/s; occurrences per window %.4f "
+          "(2 / (w + 1) = %.4f); bits set per column: mean %.0f" %
+          (k, m, N, t_build, per_chunk[0], np.mean(per_chunk[1:]) if len(per_chunk) > 1 else per_chunk[0], N / t_build, float(nkm.sum()) * h / t_build,
+           float(nkm.mean()) / (L - k + 1), 2.0 / (w + 1), t.mean()), flush=True)
+    g_last = N - 1
+    head = ctx.download(d_gen + ((g_last % chunk) * words * 8), (words * 8,), np.uint8)
+    ref = PM.Index(k, m, h, B)
+    ref.add([ascii_of(head, L)])
+    rows = np.unique(np.concatenate([ref.cols[0][:: max(len(ref.cols[0]) // 4000, 1)], np.random.default_rng(1).integers(0, B, 4000).astype(np.uint64)]))
+    got = (mx.rows(rows)[:, g_last >> 6] >> np.uint64(g_last & 63)) & np.uint64(1)
+    ok = np.array_equal(got.astype(bool), np.isin(rows, ref.cols[0])) and int(t[g_last]) == len(ref.cols[0]) and int(nkm[g_last]) == ref.nk[0]
+    print("minimizer build: column %d (%d rows sampled, t_c, nk_c) against pyref_bigsi_mini: %s" % (g_last, len(rows), "bit-exact" if ok else "MISMATCH"), flush=True)
+    # the same reads
+    d_seq = ctx.alloc((own + other) * words * 8 + 64)
+    chk(lib.gs_synth_dna_dev(ctx.h, seed, 0, own, L, d_seq))
+    chk(lib.gs_synth_dna_dev(ctx.h, seed + 77, 0, other, L, d_seq + own * words * 8))
+    d_rs, d_rl, d_go = ctx.alloc(8 * Q), ctx.alloc(8 * Q), ctx.alloc(8 * (Q + 1))
+    ctx.upload(d_rs, start); ctx.upload(d_rl, np.full(Q, RL, np.uint64)); ctx.upload(d_go, np.arange(Q + 1, dtype=np.uint64))
+    mx.query_dev(d_seq, sb, d_rs, d_rl, Q, d_go, min(Q, 20000), d_n, d_c, d_h, down_sample=a.down_sample)       # warm-up
+    ctx.sync()
+    mtimes = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        mx.query_dev(d_seq, sb, d_rs, d_rl, Q, d_go, Q, d_n, d_c, d_h, down_sample=a.down_sample)
+        ctx.sync()
+        mtimes.append(time.perf_counter() - t0)
+    tm = min(mtimes)
+    ctx.profile(True)
+    for fam in (FAM_SKETCH, FAM_SEARCH):
+        ctx.profile_read(fam)
+    mx.query_dev(d_seq, sb, d_rs, d_rl, Q, d_go, Q, d_n, d_c, d_h, down_sample=a.down_sample)
+    ctx.sync()
+    pre, srch = ctx.profile_read(FAM_SKETCH)[0] / 1e3, ctx.profile_read(FAM_SEARCH)[0] / 1e3
+    ctx.profile(False)
+    mn_used = ctx.download(d_n, Q, np.uint32)
+    mlook = int(mn_used.sum()) * h
+    print("minimizer query: %d reads of %d bp, down_sample %d: %.4f s (runs: %s): %.3g reads/s, %.3g row look-ups/s, %.3g gathered bytes/s = %.2f of the copy rate; "
+          "k_bigsi_minimizers %.4f s, the look-ups %.4f s: the pre-pass is %.2f of the two" %
+          (Q, RL, a.down_sample, tm, " ".join("%.4f" % x for x in mtimes), Q / tm, mlook / tm, mlook * W * 8 / tm, mlook * W * 8 / tm / copy_rate, pre, srch,
+           pre / (pre + srch)), flush=True)
+    print("minimizer against plain, same run: row look-ups %.4f of the plain index's (2 / (w + 1) = %.4f); time per read %.4f of the plain index's" %
+          (mlook / look, 2.0 / (w + 1), tm / tq), flush=True)
+    mcol, mhits = ctx.download(d_c, Q, np.uint32), ctx.download(d_h, Q, np.uint32)
+    ok = True
+    for r in mine:
+        s_ = int(start[r])
+        v = PM.minimizers(g0[s_:s_ + RL], k, m)[0][:: a.down_sample]
+        ok = ok and int(mn_used[r]) == len(v) and int(mhits[r]) == len(v) and int(mcol[r]) == 0
+    print("minimizer query: %d reads cut from genome 0 against pyref_bigsi_mini (n, best colour, best hits = n): %s" % (len(mine), "equal" if ok else "MISMATCH"), flush=True)
+    mx.close()
+    if a.min_count > 1:
+        filter_leg(m, "minimizer (%d, %d)" % (k, m))
