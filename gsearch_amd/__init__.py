@@ -13,3 +13,4 @@ from .api import EmbedParams, ann, embed_knn_graph, embed_knn_graph_dev, knn_gra
 from .api import FracMinHashSketch, aai, frac_max_hash, frac_similarity_qxc, frac_similarity_qxc_dev, read_list_lines, superaai, write_superaai  # noqa: F401
 from .api import ClusterResult, hnswcore, write_cluster_csv  # noqa: F401
 from .api import BIGSI_MINI_TILE, Bigsi, bigsi_minimizers, bigsi_positions, bigsi_split, bigsi_tail, bigsig_construct, bigsig_identify, bigsig_write_reads, read_ref_list  # noqa: F401
+from .api import AniGenome, AniSketcher, ani_estimate, ani_pairs, superani, write_superani  # noqa: F401

@@ -130,6 +130,13 @@ SYMBOLS = {
     "gs_frac_sketch_files": (_i, [_vp, _u32, _u32, _u32, C.POINTER(C.c_char_p), _u64, _u32, C.POINTER(C.POINTER(_u64)), _vp, _vp, _vp, _vp]),
     "gs_aai": (C.c_double, [C.c_double, _u32]),
     "gs_superaai_write": (_i, [C.c_char_p, C.POINTER(C.c_char_p), _u64, C.POINTER(C.c_char_p), _u64, _vp, _u32]),
+    # superani (SPEC 12)
+    "gs_ani_sketch_batch": (_i, [_vp, _u32, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _u64, C.POINTER(C.POINTER(_u32)), _vp]),
+    "gs_ani_sketch_batch_dev": (_i, [_vp, _u32, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u32, _vp, _vp]),
+    "gs_ani_pairs": (_i, [_vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
+    "gs_ani_pairs_dev": (_i, [_vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
+    "gs_ani_chain_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "gs_ani_estimate": (_i, [_vp, _vp, _vp, _u64, _u32, _vp]),
     "gs_index_create": (_i, [_vp, C.POINTER(IndexParams), C.POINTER(_vp)]),
     "gs_index_destroy": (None, [_vp]),
     "gs_index_nb_point": (_u64, [_vp]),

@@ -732,6 +732,125 @@ def superaai(query_list, ref_list, out, k=7, scaled=100, sketch=5120, threads=0,
     return sim
 
 
+# ---- superani (binaux/src/bin/superani.rs; SPEC 12) -------------------------------------------------------------------------------------
+AniGenome = namedtuple("AniGenome", ["seeds", "bases"])     # seeds: (n, 4) uint32 {value, contig, pos, fwd} in position order; bases: kept bases of all records
+
+
+class AniSketcher:
+    """FracMinHash seeds of genomes for the seed-chaining ANI (SPEC 12): every canonical k-mer whose mixed value is <= (2^64-1) / c, in position order."""
+
+    def __init__(self, k=16, c=30, ctx=None):
+        self.k, self.c = int(k), int(c)
+        self.ctx = ctx or default_context()
+
+    def sketch_packed(self, seq, rec_start, rec_len, genome_rec_off):
+        """already packed input (the layout of gs_sketch_batch) -> list of AniGenome"""
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        goff = np.ascontiguousarray(genome_rec_off, dtype=np.uint64)
+        ng = len(goff) - 1
+        off = np.zeros(ng + 1, np.uint64)
+        hp = C.POINTER(C.c_uint32)()
+        check(self.ctx.L.gs_ani_sketch_batch(self.ctx.h, self.k, self.c, _p(seq) if seq.nbytes else None, seq.nbytes, _p(rs) if len(rs) else None,
+                                             _p(rl) if len(rl) else None, len(rs), _p(goff), ng, C.byref(hp), _p(off)))
+        try:
+            tot = int(off[-1])
+            flat = np.ctypeslib.as_array(hp, shape=(tot * 4,)).copy().reshape(tot, 4) if tot else np.zeros((0, 4), np.uint32)
+        finally:
+            self.ctx.L.gs_host_free(C.cast(hp, C.c_void_p))
+        return [AniGenome(flat[int(off[g]):int(off[g + 1])], int(rl[int(goff[g]):int(goff[g + 1])].sum())) for g in range(ng)]
+
+    def sketch_genomes(self, genomes):
+        """genomes: list of lists of records (ASCII bytes; everything but ACGT / acgt is dropped) -> list of AniGenome"""
+        recs, goff = [], [0]
+        for g in genomes:
+            recs.extend(bytes(r) for r in g)
+            goff.append(len(recs))
+        seq, rs, rl = pack_dna_records(recs)
+        return self.sketch_packed(seq, rs, rl, np.array(goff, dtype=np.uint64))
+
+    def sketch_files(self, paths):
+        """one genome per FASTA file (plain / gz / bz2 / xz), every record kept (no capsid filter) -> list of AniGenome"""
+        genomes = []
+        for path in paths:
+            text = read_fasta_file(path)
+            genomes.append([text[sb:se] for _, sb, se in fasta_scan(text, skip_capsid=False)])
+        return self.sketch_genomes(genomes)
+
+
+def _ani_csr(genomes):
+    rows = [np.ascontiguousarray(g.seeds if isinstance(g, AniGenome) else g, dtype=np.uint32).reshape(-1, 4) for g in genomes]
+    off = np.zeros(len(rows) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in rows]) if rows else []
+    flat = np.concatenate(rows) if rows and off[-1] else np.zeros((1, 4), np.uint32)
+    return np.ascontiguousarray(flat), off
+
+
+def ani_pairs(Q, R, pairs=None, k=16, max_block_anchors=0, ctx=None):
+    """the eight integers {n_anchors, n_chains_kept, M_q, C_q, A_q, M_r, C_r, A_r} of SPEC 12 for every listed (query index, reference index);
+    pairs = None: every pair, reference-major. Q, R: lists of AniGenome (or of (n, 4) seed arrays) -> (n_pairs, 8) uint64"""
+    ctx = ctx or default_context()
+    q, qo = _ani_csr(Q)
+    r, ro = _ani_csr(R)
+    if pairs is None:
+        pairs = [(iq, ir) for ir in range(len(R)) for iq in range(len(Q))]
+    pairs = np.asarray(pairs, dtype=np.uint32).reshape(-1, 2)
+    pq, pr = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    out = np.zeros((len(pairs), 8), np.uint64)
+    check(ctx.L.gs_ani_pairs(ctx.h, int(k), _p(q), _p(qo), len(qo) - 1, _p(r), _p(ro), len(ro) - 1, _p(pq) if len(pq) else None, _p(pr) if len(pr) else None,
+                             len(pairs), _p(out) if len(pairs) else None, int(max_block_anchors)))
+    return out
+
+
+def ani_estimate(counts, bases_q, bases_r, k=16):
+    """SPEC 12 closed form: (n, 8) integers and the kept bases of both genomes of each pair -> (n, 3) float32 {ani, af_q, af_r}"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1, 8)
+    bq = np.ascontiguousarray(np.broadcast_to(np.asarray(bases_q, dtype=np.uint64), (len(counts),)))
+    br = np.ascontiguousarray(np.broadcast_to(np.asarray(bases_r, dtype=np.uint64), (len(counts),)))
+    out = np.zeros((len(counts), 3), np.float32)
+    check(_lib.load().gs_ani_estimate(_p(counts) if len(counts) else None, _p(bq) if len(counts) else None, _p(br) if len(counts) else None, len(counts), int(k),
+                                      _p(out) if len(counts) else None))
+    return out
+
+
+def _rust_f32(x):
+    """Rust's Display of an f32: the shortest digits that read back to the same f32, positional, no trailing `.0`"""
+    return np.format_float_positional(np.float32(x), unique=True, trim="-")
+
+
+def write_superani(out, query_paths, ref_paths, est):
+    """superani.rs:109-145: `query\tref\tani\taf_query\taf_ref\n` per pair, reference-major then query, both in list order (SPEC 12).
+    est: (n_ref, n_query, 3) float32 {ani, af_q, af_r}"""
+    est = np.asarray(est, dtype=np.float32).reshape(len(ref_paths), len(query_paths), 3)
+    with open(out, "wb") as f:
+        for j, r in enumerate(ref_paths):
+            for i, q in enumerate(query_paths):
+                f.write(("%s\t%s\t%s\t%s\t%s\n" % (q, r, _rust_f32(est[j, i, 0]), _rust_f32(est[j, i, 1]), _rust_f32(est[j, i, 2]))).encode("utf-8"))
+
+
+def superani(query_list, ref_list, out, k=16, c=30, ctx=None):
+    """superani (binaux/src/bin/superani.rs): list files of query and reference genomes in, its text at `out` (a path). Each distinct file is
+    sketched once; anchors, chaining and the per-side counts of every pair run on the device. Returns the (n_ref, n_query, 3) estimates."""
+    import os
+    qp, rp = read_list_lines(query_list), read_list_lines(ref_list)
+    for x in qp + rp:
+        if not os.path.isfile(x):
+            raise GsError(_lib.GS_ERR_IO, "cannot open %r" % x)
+    uniq = list(dict.fromkeys(qp + rp))
+    sk = AniSketcher(k, c, ctx)
+    gs = sk.sketch_files(uniq) if uniq else []
+    at = {p: gs[i] for i, p in enumerate(uniq)}
+    Q, R = [at[x] for x in qp], [at[x] for x in rp]
+    if Q and R:
+        counts = ani_pairs(Q, R, None, k=k, ctx=sk.ctx)
+        est = ani_estimate(counts, [g.bases for _ in R for g in Q], [g.bases for g in R for _ in Q], k).reshape(len(R), len(Q), 3)
+    else:
+        est = np.zeros((len(R), len(Q), 3), np.float32)
+    write_superani(out, qp, rp, est)
+    return est
+
+
 # ---- bigsig (binaux/src/bin/bigsig.rs; SPEC 11) -----------------------------------------------------------------------------------------
 def _text_records(groups, quals=None):
     """groups: a list of lists of records (ASCII bytes) -> (text, qual or None, rec_begin, rec_end, group_rec_off) for the host forms"""

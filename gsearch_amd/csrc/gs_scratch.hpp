@@ -63,6 +63,14 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     X(BIGSI_REC_TILES) X(BIGSI_GENOME_TILES) X(BIGSI_GENOME_WINDOWS) X(BIGSI_Q_OFF) X(BIGSI_Q_CNT) X(BIGSI_Q_VALS)                                    \
     /* bigsig, sort-count-filter build of one colour: value list and its second buffer, run lengths, head positions, radix counts, cursor + runs */  \
     X(BIGSI_LIST_VALS) X(BIGSI_LIST_ALT) X(BIGSI_LIST_LEN) X(BIGSI_LIST_POS) X(BIGSI_LIST_RADIX) X(BIGSI_LIST_CTR)                                    \
+    /* superani (gs_ani.hip), seeds: staging of the host form, unit prefix and per-unit counts of a block of genomes, the seeds of a block */           \
+    X(ANIB_SEQ) X(ANIB_REC_START) X(ANIB_REC_LEN) X(ANIB_GOFF) X(ANI_UPRE) X(ANI_GUNIT) X(ANI_UCNT) X(ANI_GBASE) X(ANI_SEEDS)                         \
+    /* superani, pairs: staging of the host form, value-ordered keys of both sides, slices of a block of pairs and its offsets */                      \
+    X(ANIP_Q) X(ANIP_QOFF) X(ANIP_R) X(ANIP_ROFF) X(ANIP_PQ) X(ANIP_PR) X(ANIP_OUT) X(ANI_QKEYS) X(ANI_RKEYS) X(ANI_KEYS_ALT) X(ANI_RADIX)            \
+    X(ANI_SLICES) X(ANI_SLICE_CNT) X(ANI_SLICE_BASE) X(ANI_AOFF) X(ANI_SOFF)                                                                          \
+    /* superani, a block's anchors, its segments, the chaining result, chain ends and the per-seed marks of both sides */                              \
+    X(ANI_A_RCTG) X(ANI_A_RPOS) X(ANI_A_QCTG) X(ANI_A_QPOS) X(ANI_A_STRAND) X(ANI_A_RIDX) X(ANI_A_QIDX) X(ANI_A_PAIR) X(ANI_SEG_TILES)                \
+    X(ANI_SEG_START) X(ANI_SEG_N) X(ANI_F) X(ANI_PRED) X(ANI_ROOT) X(ANI_BEST) X(ANI_NCHAIN) X(ANI_MATCHED) X(ANI_DIFF)                               \
     /* comm (gs_topk_merge_dev) */                                                                                                                    \
     X(COMM_ID_OFFSET)
 

@@ -428,4 +428,30 @@ GS_HD double bigsi_tail(uint64_t t_c, uint64_t B, uint32_t h, uint32_t n, uint32
     return tail < 1.0 ? tail : 1.0;
 }
 
+// ---- SPEC 12: superani (binaux/src/bin/superani.rs) - seed-chaining ANI of genome pairs. [CHOICE] throughout (the `skani` crate is not vendored).
+#define GS_ANI_KMIN 8u
+#define GS_ANI_KMAX 16u                  // a canonical value is 32 bits
+#define GS_ANI_MAX_OCC 4u                // a value carried by more seeds of either genome gives no anchors
+#define GS_ANI_W 20                      // score of an anchor
+#define GS_ANI_B 64u                     // predecessors looked at: one wave64
+#define GS_ANI_G 2500u                   // largest step of a chain on either genome, bases
+#define GS_ANI_MIN_ANCHORS 3u            // a chain with fewer anchors is dropped
+#define GS_ANI_MAX_PAIR_ANCHORS (1ULL << 26)
+#define GS_ANI_MIN_AF 0.10               // min_aligned_frac of superani.rs
+#define GS_ANI_NONE 0xFFFFFFFFu          // pred of an anchor that starts a chain
+GS_HD uint64_t ani_threshold(uint32_t c) { return ~0ULL / c; }
+GS_HD bool ani_is_seed(uint32_t v, uint64_t thr) { return splitmix_mix((uint64_t)v) <= thr; }
+// reverse complement of a k-mer held in the low 2k bits (first base highest)
+GS_HD uint32_t ani_revcomp(uint32_t x, uint32_t k)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t br = __builtin_bitreverse32(x);
+#else
+    uint32_t br = 0;
+    for (int i = 0; i < 32; i++) br |= ((x >> i) & 1u) << (31 - i);
+#endif
+    br = ((br >> 1) & 0x55555555u) | ((br & 0x55555555u) << 1);
+    return (~br) >> (32 - 2 * k);
+}
+
 }  // namespace gs

@@ -235,6 +235,38 @@ double gs_aai(double sim, uint32_t k);
 int gs_superaai_write(const char *out_path, const char *const *q_paths, uint64_t nq, const char *const *r_paths, uint64_t nr, const double *sim, uint32_t k);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* superani (binaux/src/bin/superani.rs): seed-chaining ANI of genome pairs. Arithmetic: SPEC 12 - FracMinHash seeds of the canonical k-mers
+ * (8 <= k <= 16, one in about c kept), the anchors of a pair, colinear chaining over the 64 anchors in front, and per side the seeds matched
+ * and covered by the kept chains. A seed is four u32: {value, contig, pos, fwd}; contig = the record's index inside its genome, pos = the
+ * window's first base inside the record, fwd = 1 when the canonical value is the forward window. Seeds are in position order. */
+/* input as gs_sketch_batch (2-bit packed DNA, records, genomes); library-allocated host CSR out: *seeds_out (release with gs_host_free) holds
+ * 4 u32 per seed, genome g's seeds are [off_out[g], off_out[g+1]); off_out: n_genomes + 1 entries. */
+int gs_ani_sketch_batch(gs_ctx *, uint32_t k, uint32_t c, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len,
+                        uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes, uint32_t **seeds_out, uint64_t *off_out);
+/* device form: all arrays device memory, seq_dev as for gs_sketch_batch_dev. Genome g's seeds go to seeds_out_dev[4 * g * cap ...], its true
+ * count to count_out_dev[g]; a genome with more than cap seeds is cut at cap and the call returns GS_ERR_INVALID (the counts are written first). */
+int gs_ani_sketch_batch_dev(gs_ctx *, uint32_t k, uint32_t c, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev,
+                            const uint64_t *rec_len_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes, uint32_t cap,
+                            uint32_t *seeds_out_dev, uint32_t *count_out_dev);
+/* pair p = (query pair_q[p], reference pair_r[p]) of two seed CSRs (as gs_ani_sketch_batch returns them, both made with the same k and c) ->
+ * out[8 p ...] = {n_anchors, n_chains_kept, M_q, C_q, A_q, M_r, C_r, A_r} (SPEC 12). A pair may be listed more than once. Pairs are worked
+ * through in blocks of at most max_block_anchors anchors (0: the default, 2^24; a pair with more is a block of its own); no result depends on it.
+ * A pair with more than 2^26 anchors: GS_ERR_UNSUPPORTED. The _dev form reads the offsets and the pair lists back once. */
+int gs_ani_pairs(gs_ctx *, uint32_t k, const uint32_t *q_seeds, const uint64_t *q_off, uint64_t nq, const uint32_t *r_seeds, const uint64_t *r_off,
+                 uint64_t nr, const uint32_t *pair_q, const uint32_t *pair_r, uint64_t n_pairs, uint64_t *out, uint64_t max_block_anchors);
+int gs_ani_pairs_dev(gs_ctx *, uint32_t k, const uint32_t *q_seeds_dev, const uint64_t *q_off_dev, uint64_t nq, const uint32_t *r_seeds_dev,
+                     const uint64_t *r_off_dev, uint64_t nr, const uint32_t *pair_q_dev, const uint32_t *pair_r_dev, uint64_t n_pairs, uint64_t *out_dev,
+                     uint64_t max_block_anchors);
+/* the chaining step alone, for hosts that bring their own anchors: pair p's anchors are [off_dev[p], off_dev[p+1]) of the five arrays, in order
+ * of (r contig, r position) inside a pair (anything else: GS_ERR_INVALID). f_out_dev (i32), pred_out_dev and root_out_dev (u32, counted from
+ * the pair's first anchor; pred = 0xFFFFFFFF: the anchor starts a chain) as SPEC 12 defines them. */
+int gs_ani_chain_dev(gs_ctx *, const uint32_t *rcontig_dev, const uint32_t *rpos_dev, const uint32_t *qcontig_dev, const uint32_t *qpos_dev,
+                     const uint32_t *strand_dev, const uint64_t *off_dev, uint64_t n_pairs, int32_t *f_out_dev, uint32_t *pred_out_dev, uint32_t *root_out_dev);
+/* host only, SPEC 12 closed form: counts = 8 u64 per pair as gs_ani_pairs writes them, bases_q / bases_r = the kept bases of the pair's genomes
+ * -> out[3 p ...] = {ani, af_q, af_r} as f32 (ani is a fraction; 0 when neither aligned fraction reaches 0.10). */
+int gs_ani_estimate(const uint64_t *counts, const uint64_t *bases_q, const uint64_t *bases_r, uint64_t n_pairs, uint32_t k, float *out);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */
 /*   new/modify_level_scale/set_extend_candidates/set_keeping_pruned  dnasketch.rs:139-141,159-160  */
 /*   parallel_insert dnasketch.rs:435, aasketch.rs:407;  parallel_search dnarequest.rs:353, aarequest.rs:344 */

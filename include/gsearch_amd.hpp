@@ -204,6 +204,36 @@ inline std::vector<double> frac_similarity_qxc(Context &ctx, uint32_t num, const
 }
 inline double aai(double sim, uint32_t k) { return gs_aai(sim, k); }
 
+// superani (binaux/src/bin/superani.rs; SPEC 12): seeds of packed genomes (the layout of gs_sketch_batch), the eight integers of every listed pair and
+// the closed form {ani, af_q, af_r}
+struct AniSeeds { std::vector<uint32_t> seeds; std::vector<uint64_t> off; };        // genome g: 4 u32 per seed, seeds [off[g] .. off[g+1])
+inline AniSeeds ani_sketch_batch(Context &ctx, const void *seq, uint64_t seq_bytes, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len,
+                                 const std::vector<uint64_t> &genome_rec_off, uint32_t k = 16, uint32_t c = 30)
+{
+    AniSeeds out;
+    out.off.resize(genome_rec_off.size());
+    uint32_t *h = nullptr;
+    check(gs_ani_sketch_batch(ctx.get(), k, c, seq, seq_bytes, rec_start.data(), rec_len.data(), rec_start.size(), genome_rec_off.data(), genome_rec_off.size() - 1, &h,
+                              out.off.data()));
+    out.seeds.assign(h, h + 4 * out.off.back());
+    gs_host_free(h);
+    return out;
+}
+inline std::vector<uint64_t> ani_pairs(Context &ctx, const AniSeeds &Q, const AniSeeds &R, const std::vector<uint32_t> &pair_q, const std::vector<uint32_t> &pair_r,
+                                       uint32_t k = 16, uint64_t max_block_anchors = 0)
+{
+    std::vector<uint64_t> out(8 * pair_q.size());
+    check(gs_ani_pairs(ctx.get(), k, Q.seeds.data(), Q.off.data(), Q.off.size() - 1, R.seeds.data(), R.off.data(), R.off.size() - 1, pair_q.data(), pair_r.data(),
+                       pair_q.size(), out.data(), max_block_anchors));
+    return out;
+}
+inline std::vector<float> ani_estimate(const std::vector<uint64_t> &counts, const std::vector<uint64_t> &bases_q, const std::vector<uint64_t> &bases_r, uint32_t k = 16)
+{
+    std::vector<float> out(3 * bases_q.size());
+    check(gs_ani_estimate(counts.data(), bases_q.data(), bases_r.data(), bases_q.size(), k, out.data()));
+    return out;
+}
+
 // bigsig (binaux/src/bin/bigsig.rs; SPEC 11): a bit-sliced Bloom index of genomes - one colour per genome in the order added - and, for every read, the
 // colour with the most k-mer hits and whether that many hits are significant. A genome or a read is a list of records (ASCII text); the mates of a
 // pair are two records of one read.
