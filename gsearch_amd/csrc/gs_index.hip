@@ -565,6 +565,16 @@ __device__ __forceinline__ uint32_t dense_row_tau(const uint16_t *__restrict__ m
 
 // a wave-uniform value the compiler cannot prove uniform (it came through LDS): pin it to an SGPR
 __device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+// inclusive running sums over each group of eight lanes (lane i: x of lanes (i & ~7) .. i), by three row shifts on the vector unit; a lane whose
+// source lies outside its row of sixteen adds nothing, and lanes 8 .. 15 of a row, which also take from lanes 0 .. 7, are not what the callers read
+__device__ __forceinline__ uint32_t row_prefix8(uint32_t x)
+{
+    static_assert(DT / 64 == 8, "one word per wavefront of the workgroup");
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);      // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);      // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);      // row_shr:4
+    return x;
+}
 // ================= phase 2: the order-free rest of search_layer =================
 // dmax == tau, the efs-th smallest count of the whole database: fewer than efs nodes lie below it, so dmax can never drop
 // again, the accept rule is "count < tau" from here on, every accepted key stays and is popped, and so is every candidate
@@ -993,8 +1003,9 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
 #define GS_DROWX(K, PD, PI)                                                                                                \
     do {                                                                                                                   \
         const uint32_t rid_ = uni32(KID(K));                                                                               \
-        uint32_t ho_ = hl4;                                                                                                \
-        asm volatile("" : "+v"(ho_));               /* opaque lane offset: keeps the 64-bit row base scalar */            \
+        uint32_t tx_ = threadIdx.x;                                                                                        \
+        asm volatile("" : "+v"(tx_));               /* opaque lane offset: keeps the 64-bit row base scalar; made here */ \
+        const uint32_t ho_ = (ONEG ? tx_ : tx_ & 255u) * 4u;   /* from the lane's number: as a value kept across the pop it was spilled */ \
         PD = ix.deg0[rid_];                                                                                                \
         PI = hl < maxdeg ? GS_TRAV_LOAD((const uint32_t *)((const uint8_t *)(ix.nbr0 + (uint64_t)rid_ * maxdeg) + ho_)) : 0; \
     } while (0)
@@ -1005,7 +1016,7 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
     uint32_t *visg = SPLIT ? scratch + (uint64_t)blockIdx.x * scratch_words + hwords : nullptr;
     uint64_t *Cb[2] = {cbuf + (uint64_t)blockIdx.x * 2 * capC, cbuf + (uint64_t)blockIdx.x * 2 * capC + capC};
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t half = ONEG ? 0u : threadIdx.x >> 8, hl = ONEG ? threadIdx.x : threadIdx.x & 255, hl4 = hl * 4;
+    const uint32_t half = ONEG ? 0u : threadIdx.x >> 8, hl = ONEG ? threadIdx.x : threadIdx.x & 255;
     for (;;) {
         __syncthreads();
         if (threadIdx.x == 0) S.scal[1] = atomicAdd(counter, 1ull);
@@ -1197,11 +1208,21 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
             }
             lds_barrier();
             const long long p2 = PROF ? clock64() : 0;
-            // ne <= 2M < 2^16, so the packed words add without carrying into each other; the per-wave prefixes are only needed by an
-            // accepting pop and are computed there
-            uint32_t tot = 0;
+            // ne <= 2M < 2^16, so the packed words add without carrying into each other. tot: all eight waves; pre: the waves before this one
+            // (packed unvisited | below << 16, for the accept path). One LDS read brings the eight words (lane i of every group of eight holds
+            // word i), three row shifts turn them into running sums: the total sits in lane 7, the prefix is lane wv's sum less its own word -
+            // both taken as scalars at once, so no vector register lives on. (Eight uniform reads summed one by one, and again under the wave's
+            // number for the prefix, were 90 of the ~450 instructions of a wave's pop.) ONEG keeps the word-by-word sums: its SPLIT build sits
+            // at the register limit and paid for the shorter form with two more spilled registers.
+            uint32_t tot = 0, pre = 0;
+            if (ONEG) {
 #pragma unroll
-            for (int w = 0; w < DT / 64; w++) tot += ws[w];
+                for (int w = 0; w < DT / 64; w++) { const uint32_t x = ws[w]; tot += x; if (w < (int)wv) pre += x; }
+            } else {
+                const uint32_t wsw = ws[lane & 7u], wsum8 = row_prefix8(wsw);
+                tot = (uint32_t)__builtin_amdgcn_readlane((int)wsum8, 7);
+                pre = (uint32_t)__builtin_amdgcn_readlane((int)(wsum8 - wsw), (int)uni32(wv));
+            }
             const uint32_t ne = tot & 0xFFFFu, B = tot >> 16;
             const long long p3 = PROF ? clock64() : 0;
             if (PROF && blockIdx.x == 0 && threadIdx.x == 0) { t_a += p1 - p0; t_b += p2 - p1; t_c += p3 - p2; n_pop++; }
@@ -1217,9 +1238,7 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
             else { if (B == 0) continue; slow = B > tieT; }
             uint64_t mykey = ~(uint64_t)0, ab; bool acc = false;
             uint32_t na, ci, aoff;
-            uint32_t pre = 0;                                        // packed (unvisited | below << 16) counts of the waves before this one
-#pragma unroll
-            for (int w = 0; w < DT / 64; w++) if (w < (int)wv) pre += ws[w];
+            // packed (unvisited | below << 16) counts of the waves before this one
             const uint32_t off = pre & 0xFFFFu, boff = pre >> 16;
             if (!slow) { acc = below; na = B; ci = cntv; mykey = KEY(cntv, id); ab = balb; aoff = boff; }
             else {

@@ -4,10 +4,96 @@ interior-word fast loop of k_sketch_min<DNA, LDS table, optdens, 64-bit values, 
 the unrolled-by-2 loop that carries the fewest 64-bit compares, i.e. no bounds test) and counts instructions per class. Issue cycles per
 wave64 instruction: simple VALU 2 (MI355X_MICROARCH.md:52-54); 32-bit integer multiplies / v_mad_u64_u32 weighted by the ratio measured by
 tools/ubench_valu (profiles/r02_ubench_valu.txt) when that file is given, else the quarter-rate assumption (x4).
-usage: isa_mix.py [ubench_valu.txt] > profiles/r05_sketch_isa_mix.json"""
+usage: isa_mix.py [ubench_valu.txt] > profiles/r05_sketch_isa_mix.json
+
+--trav [--src TREE]: static census of one phase-1 pop of the dense traversal instead. Compiles gs_index.hip with line tables, takes the headline
+instantiation k_hnsw_search_dense<VLDS, !PROF, 6, !ONEG, !WLOG, !SPLIT> and books every instruction of the kernel to the source line of the KERNEL it
+was inlined into (the outermost frame of its .loc), lines grouped into the stretches of the pop loop by anchors looked up in the source text. Opcodes
+are classified by prefix only. Static: an instruction counts once however often its block runs (the insertion loop of wavefront 0 runs once per key
+that enters the front) and both sides of a branch count; the measured figure is the PMC one (tools/pmc_trav.sh)."""
 import collections, json, os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def trav_census(tree):
+    rel = os.path.join("gsearch_amd", "csrc", "gs_index.hip")
+    src = os.path.join(tree, rel)
+    asm = os.path.join(tempfile.mkdtemp(), "gs_index_g.s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-gline-tables-only",
+                           "-S", "-o", asm, src], stderr=subprocess.DEVNULL)
+    text = open(asm).read()
+    a = text.index("\n_ZN2gs19k_hnsw_search_denseILb1ELb0ELi6ELb0ELb0ELb0EEE")
+    body = text[a:text.index("s_endpgm", a)].splitlines()
+    source = open(src).read().splitlines()
+    k0 = next(i for i, l in enumerate(source) if "void k_hnsw_search_dense(" in l)
+    # (name, on the headline's path, who runs it, anchor text, line offset): a group runs from its anchor to the next group's
+    groups = [("kernel prologue, per-query set-up, descent", False, "-", "void k_hnsw_search_dense(", 0),
+              ("loop head: phase test, head keys of the front", True, "all", "if (PHASE2 && dmax == tau && !(cap_log & 1u))", 0),
+              ("refill / compaction (pq_rebuild)", False, "-", "if (empty || crowded) {", 0),
+              ("pop: front down one lane, publish", True, "all", "if (KCNT(c) > dmax) break;", 0),
+              ("!PQ form", False, "-", "if (headG < nG && headG - wbase >= wn) {", 0),
+              ("expanding half: row, test-and-set, look-up", True, "expand", "const long long p0 = PROF", 0),
+              ("hint half: row, visited hint, look-up", True, "hint", "} else if (!ONEG && c1 != ~(uint64_t)0) {", 0),
+              ("ballots, wave sums out, row after next, POP BARRIER", True, "all", "} else if (!ONEG) pk = ~(uint64_t)0;", 0),
+              ("sums of the wave words, accept rule (fast)", True, "all", "const long long p2 = PROF", 0),
+              ("slow accept (ranks)", False, "-", "// the expansion E in adjacency order", 0),
+              ("accepted keys: histogram, compaction into As, BARRIER", True, "all", "const long long p4 = PROF", 0),
+              ("wavefront 0: keys into the front / U", True, "wave0", "// wavefront 0 takes the accepted keys 64 at a time", -1),
+              ("BARRIER, state back, rows of the new heads", True, "all", "nU = (uint32_t)S.scal[4]; minA = S.scal[5];", -1),
+              ("trim of R, fast form", True, "all", "const long long q1 = PROF", 0),
+              ("trim of R, histogram walk", False, "-", "// full: wave 0 reads bins other waves have just incremented", 0),
+              ("trim tail, T test", True, "all", "dmax = (uint32_t)S.scal[2]; tieT = (uint32_t)S.scal[3];", 2),
+              ("T merge", False, "-", "const uint64_t k = S.As[threadIdx.x];", 0),
+              ("!PQ rest of the pop", False, "-", "// T <- knbn smallest of T u A (only when A reaches into it)", -1),
+              ("after the loop: phase 2, outputs, WLOG sort", False, "-", "const long long tm2 = tm ? clock64() : 0;", 0)]
+    starts, at = [], k0
+    for g in groups:
+        at = next(i for i in range(at, len(source)) if g[3] in source[i]) + g[4]
+        starts.append(at + 1)                                  # 1-based like .loc
+    def group_of(line):
+        j = -1
+        for i, s in enumerate(starts):
+            if line >= s:
+                j = i
+        return j
+    def klass(op):
+        if op.startswith("v_"): return "valu"
+        if op.startswith("ds_"): return "lds"
+        if op.startswith(("global_", "buffer_", "flat_", "scratch_")): return "vmem"
+        if op.startswith(("s_cbranch", "s_branch", "s_setpc", "s_call")): return "branch"
+        if op.startswith(("s_waitcnt", "s_nop", "s_barrier", "s_sleep")): return "wait"
+        if op.startswith(("s_load", "s_buffer_load")): return "smem"
+        return "salu" if op.startswith("s_") else "other"
+    counts = [collections.Counter() for _ in groups]
+    cur = 0
+    for l in body:
+        s = l.strip()
+        if s.startswith(".loc"):
+            hits = re.findall(r"gs_index\.hip:(\d+)", s)
+            if hits and group_of(int(hits[-1])) >= 0:
+                cur = group_of(int(hits[-1]))
+            continue
+        if not l.startswith("\t") or not s or s.startswith((";", ".")):
+            continue
+        counts[cur][klass(s.split()[0])] += 1
+    cols = ["valu", "salu", "lds", "vmem", "smem", "branch", "wait", "other"]
+    print("static census of one phase-1 pop, k_hnsw_search_dense<VLDS, !PROF, 6, !ONEG, !WLOG, !SPLIT>, %s" % rel)
+    print("%-58s %-7s %5s  " % ("stretch (source lines)", "runs", "all") + " ".join("%6s" % c for c in cols))
+    per_role = collections.Counter()
+    for g, s, e, c in zip(groups, starts, starts[1:] + [starts[-1] + 400], counts):
+        tot = sum(c.values())
+        print("%-58s %-7s %5d  " % ("%s%s (%d-%d)" % ("" if g[1] else "[off path] ", g[0], s, e - 1), g[2], tot) + " ".join("%6d" % c[k] for k in cols))
+        if g[1]:
+            per_role[g[2]] += tot
+    n_all, n_e, n_h, n_0 = per_role["all"], per_role["expand"], per_role["hint"], per_role["wave0"]
+    print("on the path, per wave: every wave %d + expanding half %d | hint half %d; wavefront 0 a further %d" % (n_all, n_e, n_h, n_0))
+    print("static wave-instructions of one accepting pop over the eight waves: 8 x %d + 4 x %d + 4 x %d + %d = %d" % (n_all, n_e, n_h, n_0, 8 * n_all + 4 * n_e + 4 * n_h + n_0))
+
+
+if "--trav" in sys.argv:
+    trav_census(sys.argv[sys.argv.index("--src") + 1] if "--src" in sys.argv else ROOT)
+    sys.exit(0)
 src = os.path.join(ROOT, "gsearch_amd", "csrc", "gs_sketch.hip")
 asm = os.path.join(tempfile.gettempdir(), "gs_sketch_isa.s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S", "-o", asm, src],

@@ -11,6 +11,6 @@ for blk in re.split(r"\n  - \.agpr_count:", meta)[1:]:
     g = lambda k: (re.search(r"\.%s:\s+(\S+)" % k, blk) or [None, "?"])[1]
     name = g("name")
     if flt and flt not in name: continue
-    print("%-84s vgpr %3s sgpr %3s spill_v %3s lds %6s scratch %4s" % (name[:84], g("vgpr_count"), g("sgpr_count"), g("vgpr_spill_count"), g("group_segment_fixed_size"), g("private_segment_fixed_size")))
+    print("%-84s vgpr %3s sgpr %3s spill_v %3s spill_s %3s lds %6s scratch %4s" % (name[:84], g("vgpr_count"), g("sgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"), g("group_segment_fixed_size"), g("private_segment_fixed_size")))
 P
 [ -n "$KEEP_ASM" ] && cp $S "$KEEP_ASM"; rm -f $S
