@@ -67,6 +67,15 @@ class BigsiDescC(C.Structure):
     _fields_ = [("prm", BigsiParamsC), ("n_colours", C.c_uint64), ("colour_capacity", C.c_uint64), ("row_words", C.c_uint64)]
 
 
+class HmmInfoC(C.Structure):
+    """gs_hmm_info (SPEC 13)"""
+    _fields_ = [("name", C.c_char * 64), ("acc", C.c_char * 32), ("M", C.c_uint32), ("flags", C.c_uint32), ("ga", C.c_double * 2), ("tc", C.c_double * 2),
+                ("nc", C.c_double * 2), ("mu", C.c_double), ("lam", C.c_double), ("ga_units", C.c_int32), ("tbm", C.c_int32)]
+
+
+HMM_MAX_M, HMM_MAX_L, HMM_NO_SCORE, HMM_NO_HIT, HMM_TABLE_ROWS = 1280, 1 << 18, -(1 << 31), 0xFFFFFFFF, 27
+HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
+
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
 
@@ -137,6 +146,19 @@ SYMBOLS = {
     "gs_ani_pairs_dev": (_i, [_vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64]),
     "gs_ani_chain_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_ani_estimate": (_i, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    # hmmsearch (SPEC 13)
+    "gs_hmm_parse_mem": (_i, [_vp, _u64, _u32, C.POINTER(HmmInfoC), _vp, _u64, C.POINTER(_u32)]),
+    "gs_hmm_specials": (_i, [_u64, _u32, _vp]),
+    "gs_hmm_db_load": (_i, [_vp, C.POINTER(C.c_char_p), _u64, C.POINTER(_vp)]),
+    "gs_hmm_db_load_mem": (_i, [_vp, C.POINTER(_vp), C.POINTER(_u64), _u64, C.POINTER(_vp)]),
+    "gs_hmm_db_free": (None, [_vp]),
+    "gs_hmm_db_info": (_i, [_vp, C.POINTER(_u64), C.POINTER(HmmInfoC), _u64]),
+    "gs_hmm_db_tables": (_i, [_vp, _u64, _vp, _u64]),
+    "gs_hmm_search_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "gs_hmm_search": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "gs_hmm_best_hits_dev": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
+    "gs_hmm_bits": (C.c_double, [C.c_int32]),
+    "gs_hmm_evalue": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double]),
     "gs_index_create": (_i, [_vp, C.POINTER(IndexParams), C.POINTER(_vp)]),
     "gs_index_destroy": (None, [_vp]),
     "gs_index_nb_point": (_u64, [_vp]),

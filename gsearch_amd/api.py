@@ -851,6 +851,218 @@ def superani(query_list, ref_list, out, k=16, c=30, ctx=None):
     return est
 
 
+# ---- hmmsearch (`hmmsearch_rs -f proteome.faa -m profile.HMM`; SPEC 13) ------------------------------------------------------------------
+def hmm_parse(text, model=0):
+    """model number `model` of a HMMER3 ASCII text (bytes) -> (info dict, int32 [27][M + 1] tables, number of models in the text); host only"""
+    L = _lib.load()
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    info, n = _lib.HmmInfoC(), C.c_uint32()
+    check(L.gs_hmm_parse_mem(_p(buf) if len(buf) else None, len(buf), int(model), C.byref(info), None, 0, C.byref(n)))
+    tab = np.zeros((_lib.HMM_TABLE_ROWS, info.M + 1), np.int32)
+    check(L.gs_hmm_parse_mem(_p(buf), len(buf), int(model), None, _p(tab), tab.size, None))
+    return _hmm_info(info), tab, n.value
+
+
+def _hmm_info(i):
+    pair = lambda v, bit: (v[0], v[1]) if i.flags & bit else None
+    return {"name": i.name.decode(), "acc": i.acc.decode(), "M": int(i.M), "ga": pair(i.ga, _lib.HMM_HAS_GA), "tc": pair(i.tc, _lib.HMM_HAS_TC),
+            "nc": pair(i.nc, _lib.HMM_HAS_NC), "mu": i.mu if i.flags & _lib.HMM_HAS_STATS else None, "lam": i.lam if i.flags & _lib.HMM_HAS_STATS else None,
+            "ga_units": int(i.ga_units) if i.flags & _lib.HMM_HAS_GA else None, "tbm": int(i.tbm)}
+
+
+def hmm_specials(L, M):
+    """(tloop, tmove, null, tBM, nloop, nmove) in units for a target of L residues and a profile of M nodes (SPEC 13); host only"""
+    out = np.zeros(6, np.int32)
+    check(_lib.load().gs_hmm_specials(int(L), int(M), _p(out)))
+    return tuple(int(x) for x in out)
+
+
+def hmm_bits(raw):
+    return _lib.load().gs_hmm_bits(int(raw))
+
+
+def hmm_evalue(bits, mu, lam, n_targets):
+    """E = n_targets * P(score >= bits) under the Gumbel of a profile's STATS LOCAL VITERBI line"""
+    return _lib.load().gs_hmm_evalue(float(bits), float(mu), float(lam), float(n_targets))
+
+
+def hmm_threshold_units(bits):
+    """a caller's cutoff in bits -> units of 2^-10 bit: floor(bits * 1024 + 1/2)"""
+    import math
+    return int(math.floor(float(bits) * 1024.0 + 0.5))
+
+
+class HmmDb:
+    """A set of HMMER3 profiles in device memory (SPEC 13). paths_or_dir: a directory (its *.HMM / *.hmm files in name order), one path, a list of
+    paths, or - texts=True - a list of bytes objects. Profiles keep the order of the files and of the models inside each."""
+
+    def __init__(self, paths_or_dir, ctx=None, texts=False):
+        import os
+        self.ctx = ctx or default_context()
+        L = self.ctx.L
+        h = C.c_void_p()
+        if texts:
+            bufs = [np.frombuffer(bytes(t), dtype=np.uint8) for t in paths_or_dir]
+            ptr = (C.c_void_p * len(bufs))(*[b.ctypes.data if len(b) else None for b in bufs])
+            nb = (C.c_uint64 * len(bufs))(*[len(b) for b in bufs])
+            check(L.gs_hmm_db_load_mem(self.ctx.h, ptr, nb, len(bufs), C.byref(h)))
+        else:
+            if isinstance(paths_or_dir, (str, bytes, os.PathLike)):
+                d = os.fsdecode(paths_or_dir)
+                paths = sorted(os.path.join(d, f) for f in os.listdir(d) if f.lower().endswith(".hmm")) if os.path.isdir(d) else [d]
+            else:
+                paths = [os.fsdecode(x) for x in paths_or_dir]
+            arr = (C.c_char_p * len(paths))(*[x.encode() for x in paths])
+            check(L.gs_hmm_db_load(self.ctx.h, arr, len(paths), C.byref(h)))
+        self.h = h
+        n = C.c_uint64()
+        check(L.gs_hmm_db_info(self.h, C.byref(n), None, 0))
+        infos = (_lib.HmmInfoC * n.value)()
+        check(L.gs_hmm_db_info(self.h, C.byref(n), infos, n.value))
+        self.info = [_hmm_info(i) for i in infos]
+        self.names = [i["name"] for i in self.info]
+        self.acc = [i["acc"] for i in self.info]
+        self.M = np.array([i["M"] for i in self.info], np.uint32)
+        self.ga = np.array([i["ga"][0] if i["ga"] else np.nan for i in self.info])
+        self.mu = np.array([i["mu"] if i["mu"] is not None else np.nan for i in self.info])
+        self.lam = np.array([i["lam"] if i["lam"] is not None else np.nan for i in self.info])
+        self.ga_units = [i["ga_units"] for i in self.info]
+
+    def __len__(self):
+        return len(self.info)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.gs_hmm_db_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if not _exiting[0]:
+                self.close()
+        except Exception:
+            pass
+
+    def tables(self, p):
+        """int32 [27][M + 1] of profile p, nodes 1..M read back from the device"""
+        tab = np.zeros((_lib.HMM_TABLE_ROWS, int(self.M[p]) + 1), np.int32)
+        check(self.ctx.L.gs_hmm_db_tables(self.h, int(p), _p(tab), tab.size))
+        return tab
+
+    def search_packed(self, aa, rec_start, rec_len):
+        """residues as filter_aa_records() returns them -> int32 [n_rec, n_prof] raw scores (units of 2^-10 bit; HMM_NO_SCORE for an empty record)"""
+        aa = np.ascontiguousarray(aa, dtype=np.uint8)
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        out = np.zeros((len(rs), len(self)), np.int32)
+        check(self.ctx.L.gs_hmm_search(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
+                                       _p(out) if out.size else None))
+        return out
+
+    def search(self, records):
+        """records: protein sequences (bytes; everything outside the 20 letters is dropped, as the AA sketchers do) -> int32 [n_rec, n_prof]"""
+        return self.search_packed(*filter_aa_records([bytes(r) for r in records]))
+
+    def search_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, score_out_dev):
+        check(self.ctx.L.gs_hmm_search_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), score_out_dev))
+
+    def thresholds(self, cutoff="ga"):
+        """int32 [n_prof] in units: every profile's GA1, or the caller's bits for all (a number) or per profile (a sequence)"""
+        if isinstance(cutoff, str):
+            if cutoff != "ga":
+                raise ValueError("cutoff: 'ga' or bits")
+            if any(g is None for g in self.ga_units):
+                raise GsError(_lib.GS_ERR_INVALID, "a profile of the set has no GA cutoff: give bits")
+            return np.array(self.ga_units, np.int32)
+        bits = np.broadcast_to(np.asarray(cutoff, dtype=np.float64), (len(self),))
+        return np.array([hmm_threshold_units(b) for b in bits], np.int32)
+
+    def best_hits_dev(self, score_dev, n_rec, genome_rec_off_dev, n_genomes, thr_dev, best_rec_out_dev, best_score_out_dev):
+        check(self.ctx.L.gs_hmm_best_hits_dev(self.ctx.h, self.h, score_dev, int(n_rec), genome_rec_off_dev, int(n_genomes), thr_dev, best_rec_out_dev,
+                                              best_score_out_dev))
+
+    def best_hits(self, scores, genome_rec_off, cutoff="ga"):
+        """per genome (records [genome_rec_off[g], genome_rec_off[g+1])) and profile the record with the largest raw score at or above the cutoff, the
+        lowest such record on a tie -> (uint32 [n_genomes, n_prof] records, HMM_NO_HIT when none; int32 scores, HMM_NO_SCORE when none)"""
+        ctx = self.ctx
+        scores = np.ascontiguousarray(scores, dtype=np.int32).reshape(-1, len(self))
+        goff = np.ascontiguousarray(genome_rec_off, dtype=np.uint64)
+        thr = self.thresholds(cutoff)
+        ng, nrec, npf = len(goff) - 1, len(scores), len(self)
+        rec, sc = np.zeros((ng, npf), np.uint32), np.zeros((ng, npf), np.int32)
+        if ng == 0:
+            return rec, sc
+        bufs = [ctx.alloc(max(a.nbytes, 16)) for a in (scores, goff, thr, rec, sc)]
+        try:
+            for ptr, a in zip(bufs[:3], (scores, goff, thr)):
+                if a.nbytes:
+                    ctx.upload(ptr, a)
+            self.best_hits_dev(bufs[0], nrec, bufs[1], ng, bufs[2], bufs[3], bufs[4])
+            rec = ctx.download(bufs[3], (ng, npf), np.uint32)
+            sc = ctx.download(bufs[4], (ng, npf), np.int32)
+        finally:
+            for ptr in bufs:
+                ctx.free(ptr)
+        return rec, sc
+
+
+def _faa_records(path):
+    """(ids, sequences as the reader leaves them) of one protein FASTA file, plain or compressed"""
+    text = read_fasta_file(path)
+    recs = fasta_scan(text, skip_capsid=False)
+    return [r[0] for r in recs], [text[b:e] for _, b, e in recs]
+
+
+def _as_hmm_db(hmm, ctx):
+    return hmm if isinstance(hmm, HmmDb) else HmmDb(hmm, ctx)
+
+
+def hmmsearch(faa, hmm, output=None, ctx=None):
+    """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
+    `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
+    `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
+    (record, profile) with raw >= 0, sorted by (profile, -raw, record); bits %.2f, evalue %.3E with Z = the number of records (`-` without STATS),
+    pass_ga 1 / 0 (`-` without GA), acc `-` when the profile has none."""
+    db = _as_hmm_db(hmm, ctx)
+    ids, seqs = _faa_records(faa)
+    scores = db.search(seqs)
+    Z = len(ids)
+    out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga\n"]
+    for p, inf in enumerate(db.info):
+        col = scores[:, p].astype(np.int64)
+        keep = np.flatnonzero((col != _lib.HMM_NO_SCORE) & (col >= 0))
+        for r in keep[np.lexsort((keep, -col[keep]))]:
+            raw = int(col[r])
+            b = hmm_bits(raw)
+            ev = "%.3E" % hmm_evalue(b, inf["mu"], inf["lam"], Z) if inf["mu"] is not None else "-"
+            ga = "-" if inf["ga_units"] is None else ("1" if raw >= inf["ga_units"] else "0")
+            out.append(("%s\t%s\t%s\t%.2f\t%s\t%s\n" % (ids[r], inf["name"], inf["acc"] or "-", b, ev, ga)).encode())
+    table = b"".join(out)
+    if output is not None:
+        with open(output, "wb") as f:
+            f.write(table)
+    return ids, scores, table
+
+
+def universal_genes(faa_files, hmm, ctx=None, cutoff="ga"):
+    """One genome per protein FASTA file: per genome the residues of its best protein for every profile that has a hit at the cutoff, in profile
+    order - the records an AA sketcher takes for `tohnsw` / `request` at the universal-gene level. -> (list of lists of bytes, uint32 [n_genomes, n_prof]
+    record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing)"""
+    db = _as_hmm_db(hmm, ctx)
+    seqs, goff = [], [0]
+    for path in faa_files:
+        seqs.extend(_faa_records(path)[1])
+        goff.append(len(seqs))
+    aa, rs, rl = filter_aa_records([bytes(s) for s in seqs])
+    scores = db.search_packed(aa, rs, rl)
+    rec, _ = db.best_hits(scores, np.array(goff, np.uint64), cutoff)
+    genomes = []
+    for g in range(len(goff) - 1):
+        genomes.append([bytes(aa[int(rs[r]):int(rs[r]) + int(rl[r])]) for r in rec[g] if r != _lib.HMM_NO_HIT])
+    local = np.where(rec == _lib.HMM_NO_HIT, rec, rec - np.array(goff[:-1], np.uint32)[:, None]).astype(np.uint32)
+    return genomes, local
+
+
 # ---- bigsig (binaux/src/bin/bigsig.rs; SPEC 11) -----------------------------------------------------------------------------------------
 def _text_records(groups, quals=None):
     """groups: a list of lists of records (ASCII bytes) -> (text, qual or None, rec_begin, rec_end, group_rec_off) for the host forms"""

@@ -1,0 +1,585 @@
+// gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
+// device, and the best record per genome and profile. Integers only from the file's digits to the raw score; doubles appear in gs_hmm_bits /
+// gs_hmm_evalue and in the cutoffs and STATS fields that are only reported.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+#include <numeric>
+#include "gs_internal.hpp"
+#include "gs_spec.hpp"
+
+namespace gs {
+
+// ---- profile files ----------------------------------------------------------------------------------------------------------------------------
+struct HmmModel { gs_hmm_info info; std::vector<int32_t> tab; };        // tab: [27][M + 1] as gs_hmm_parse_mem documents it
+
+// one number of a file -> units (SPEC 13 "Units")
+static bool hmm_file_units(const std::string &t, int32_t *out)
+{
+    if (t == "*") { *out = GS_HMM_STAR; return true; }
+    const size_t dot = t.find('.');
+    const std::string ip = t.substr(0, dot), fr = dot == std::string::npos ? "" : t.substr(dot + 1);
+    auto digits = [](const std::string &s) { return !s.empty() && s.find_first_not_of("0123456789") == std::string::npos; };
+    if (!digits(ip) || ip.size() > 4 || (dot != std::string::npos && !digits(fr))) { set_error("hmm: not a number: '%s'", t.c_str()); return false; }
+    if (fr.size() > 5) { set_error("hmm: more than 5 decimals: '%s'", t.c_str()); return false; }
+    uint64_t d = strtoull(ip.c_str(), nullptr, 10) * 100000ull, f = 0;
+    for (size_t i = 0; i < 5; i++) f = f * 10 + (i < fr.size() ? (uint64_t)(fr[i] - '0') : 0);
+    d += f;
+    if (d > GS_HMM_MAX_FILE_VALUE) { set_error("hmm: a value of 100 nats or more: '%s'", t.c_str()); return false; }
+    *out = -(int32_t)((d * GS_HMM_UNIT_C + (1ull << (GS_HMM_UNIT_S - 1))) >> GS_HMM_UNIT_S);
+    return true;
+}
+// a cutoff in bits as the file writes it -> units, rounded half up
+static bool hmm_bits_units(const std::string &tok, int32_t *out)
+{
+    const bool neg = !tok.empty() && tok[0] == '-';
+    const size_t b = tok.find_first_not_of("+-");
+    const std::string t = b == std::string::npos ? "" : tok.substr(b);
+    const size_t dot = t.find('.');
+    const std::string ip = t.substr(0, dot), fr = dot == std::string::npos ? "" : t.substr(dot + 1);
+    auto digits = [](const std::string &s) { return !s.empty() && s.find_first_not_of("0123456789") == std::string::npos; };
+    if (!digits(ip) || ip.size() > 6 || (!fr.empty() && !digits(fr)) || fr.size() > 5) { set_error("hmm: not a cutoff: '%s'", tok.c_str()); return false; }
+    int64_t den = 1;
+    for (size_t i = 0; i < fr.size(); i++) den *= 10;
+    int64_t d = strtoll(ip.c_str(), nullptr, 10) * den + (fr.empty() ? 0 : strtoll(fr.c_str(), nullptr, 10));
+    if (neg) d = -d;
+    const int64_t num = 2 * d * 1024 + den, q = num / (2 * den);
+    *out = (int32_t)(num % (2 * den) < 0 ? q - 1 : q);              // floor
+    return true;
+}
+
+struct HmmLines {      // the non-blank lines of a text, split at white space
+    const char *p, *end;
+    bool next(std::vector<std::string> &tok, std::string *raw = nullptr)
+    {
+        while (p < end) {
+            const char *e = (const char *)memchr(p, '\n', (size_t)(end - p));
+            if (!e) e = end;
+            const char *a = p;
+            p = e < end ? e + 1 : end;
+            tok.clear();
+            for (const char *c = a; c < e;) {
+                while (c < e && (*c == ' ' || *c == '\t' || *c == '\r')) c++;
+                const char *s = c;
+                while (c < e && !(*c == ' ' || *c == '\t' || *c == '\r')) c++;
+                if (c > s) tok.emplace_back(s, c);
+            }
+            if (!tok.empty()) { if (raw) raw->assign(a, e); return true; }
+        }
+        return false;
+    }
+    bool more() { while (p < end && (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n')) p++; return p < end; }
+};
+
+static int hmm_parse_all(const char *text, size_t n, std::vector<HmmModel> &out)
+{
+    HmmLines in{text, text + n};
+    std::vector<std::string> f;
+    std::string raw;
+    static const int32_t bg[20] = GS_HMM_BG_LIST;
+    const size_t first = out.size();
+#define HMM_LINE(what) GS_REQUIRE(in.next(f, &raw), GS_ERR_INVALID, "hmm: the text ends inside a model (%s)", what)
+    while (in.more()) {
+        HMM_LINE("header");
+        GS_REQUIRE(raw.compare(0, 7, "HMMER3/") == 0, GS_ERR_INVALID, "hmm: not a HMMER3 profile: '%.40s'", raw.c_str());
+        HmmModel m;
+        memset(&m.info, 0, sizeof m.info);
+        bool has_name = false, has_alph = false;
+        std::string alph;
+        for (;;) {
+            HMM_LINE("header");
+            if (f[0] == "HMM") break;
+            if (f[0] == "NAME" && f.size() > 1) { snprintf(m.info.name, sizeof m.info.name, "%s", f[1].c_str()); has_name = true; }
+            else if (f[0] == "ACC" && f.size() > 1) snprintf(m.info.acc, sizeof m.info.acc, "%s", f[1].c_str());
+            else if (f[0] == "LENG" && f.size() > 1) {
+                GS_REQUIRE(f[1].size() <= 9 && f[1].find_first_not_of("0123456789") == std::string::npos, GS_ERR_INVALID, "hmm: LENG '%s'", f[1].c_str());
+                m.info.M = (uint32_t)strtoul(f[1].c_str(), nullptr, 10);
+            } else if (f[0] == "ALPH" && f.size() > 1) {
+                alph = f[1]; has_alph = true;
+                for (char &ch : alph) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch + 32);
+            } else if ((f[0] == "GA" || f[0] == "TC" || f[0] == "NC") && f.size() > 2) {
+                std::string a = f[1], b = f[2];
+                while (!a.empty() && a.back() == ';') a.pop_back();
+                while (!b.empty() && b.back() == ';') b.pop_back();
+                double *dst = f[0] == "GA" ? m.info.ga : (f[0] == "TC" ? m.info.tc : m.info.nc);
+                dst[0] = strtod(a.c_str(), nullptr); dst[1] = strtod(b.c_str(), nullptr);
+                m.info.flags |= f[0] == "GA" ? GS_HMM_HAS_GA : (f[0] == "TC" ? GS_HMM_HAS_TC : GS_HMM_HAS_NC);
+                if (f[0] == "GA" && !hmm_bits_units(a, &m.info.ga_units)) return GS_ERR_INVALID;
+            } else if (f[0] == "STATS" && f.size() > 4 && f[1] == "LOCAL" && f[2] == "VITERBI") {
+                m.info.mu = strtod(f[3].c_str(), nullptr); m.info.lambda = strtod(f[4].c_str(), nullptr);
+                m.info.flags |= GS_HMM_HAS_STATS;
+            }
+        }
+        GS_REQUIRE(has_name && has_alph && m.info.M >= 1, GS_ERR_INVALID, "hmm: NAME, LENG or ALPH missing");
+        GS_REQUIRE(alph == "amino", GS_ERR_INVALID, "hmm: %s: ALPH %s (only amino)", m.info.name, alph.c_str());
+        GS_REQUIRE(m.info.M <= GS_HMM_MAX_M, GS_ERR_UNSUPPORTED, "hmm: %s has %u nodes, more than %u", m.info.name, m.info.M, GS_HMM_MAX_M);
+        const uint32_t M = m.info.M, W = M + 1;
+        m.info.tbm = hmm_tbm(M);
+        m.tab.assign((size_t)GS_HMM_TABLE_ROWS * W, 0);
+        HMM_LINE("transition names");
+        HMM_LINE("node 0");
+        if (f[0] == "COMPO") HMM_LINE("node 0");
+        int32_t u;
+        auto emissions = [&](size_t skip, int32_t *col, uint32_t k) {          // 20 numbers from f[skip]; col: where the match scores of node k go
+            for (int a = 0; a < 20; a++) {
+                if (!hmm_file_units(f[skip + a], &u)) return false;
+                if (col) col[(size_t)a * W + k] = u - bg[a];
+            }
+            return true;
+        };
+        for (uint32_t k = 0; k <= M; k++) {
+            if (k > 0) {
+                HMM_LINE("match emissions");
+                GS_REQUIRE(f.size() >= 21 && f[0] == std::to_string(k), GS_ERR_INVALID, "hmm: %s: node %u expected, found '%.20s'", m.info.name, k, f[0].c_str());
+                if (!emissions(1, m.tab.data(), k)) return GS_ERR_INVALID;
+                HMM_LINE("insert emissions");
+            }
+            GS_REQUIRE(f.size() == 20, GS_ERR_INVALID, "hmm: %s: insert emissions of node %u: %zu fields", m.info.name, k, f.size());
+            if (!emissions(0, nullptr, k)) return GS_ERR_INVALID;             // validated; insert emissions score 0 (SPEC 13)
+            HMM_LINE("transitions");
+            GS_REQUIRE(f.size() == 7, GS_ERR_INVALID, "hmm: %s: transitions of node %u: %zu fields", m.info.name, k, f.size());
+            for (int t = 0; t < 7; t++) {
+                if (!hmm_file_units(f[t], &u)) return GS_ERR_INVALID;
+                m.tab[(size_t)(20 + t) * W + k] = u;
+            }
+        }
+        HMM_LINE("//");
+        GS_REQUIRE(f.size() == 1 && f[0] == "//", GS_ERR_INVALID, "hmm: %s: no // after node %u", m.info.name, M);
+        out.push_back(std::move(m));
+    }
+#undef HMM_LINE
+    GS_REQUIRE(out.size() > first, GS_ERR_INVALID, "hmm: no model in the text");
+    return GS_OK;
+}
+
+// ---- device side --------------------------------------------------------------------------------------------------------------------------------
+// A profile in device memory: 28 rows of MP = 64 Q words, word j of a row belongs to node j + 1. Rows 0..26 as in the host table, row 27 = PDD,
+// the sum of tDD over the nodes in front of j inside its lane's group of Q. Nodes past M hold GS_HMM_STAR everywhere: they take no part in E and
+// nothing flows from a node to a lower one.
+enum { HMM_ROWS_DEV = 28, HMM_ROW_MM = 20, HMM_ROW_MI = 21, HMM_ROW_MD = 22, HMM_ROW_IM = 23, HMM_ROW_II = 24, HMM_ROW_DM = 25, HMM_ROW_DD = 26, HMM_ROW_PDD = 27 };
+enum { HMM_BLOCK = 512, HMM_WAVES = HMM_BLOCK / 64, HMM_MAX_WG_PER_PROFILE = 64 };
+struct HmmDesc { uint64_t off; uint32_t M; int32_t tbm; };             // off: first word of the profile's table
+static constexpr int HMM_CLASS_Q[] = {1, 2, 3, 4, 6, 8, 12, 16, 20};       // nodes per lane a kernel is compiled for; a profile runs in the smallest that holds it
+enum { HMM_CLASSES = 9 };
+static_assert(HMM_CLASS_Q[HMM_CLASSES - 1] * 64 == GS_HMM_MAX_M, "the largest class holds GS_HMM_MAX_M nodes");
+static_assert((size_t)HMM_ROWS_DEV * GS_HMM_MAX_M * 4 <= 160 * 1024, "the largest table fits the LDS of a CU");
+
+__device__ __forceinline__ int hmm_wave_max(int x)      // the maximum over the wavefront, in every lane
+{
+    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));       // quad_perm [1,0,3,2]
+    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));       // quad_perm [2,3,0,1]
+    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));      // row_half_mirror
+    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false));      // row_mirror
+    const int a = __builtin_amdgcn_readlane(x, 0), b = __builtin_amdgcn_readlane(x, 16), c = __builtin_amdgcn_readlane(x, 32),
+              d = __builtin_amdgcn_readlane(x, 48);
+    return max(max(a, b), max(c, d));
+}
+
+// One workgroup per (profile, slice of the records): the profile's table goes to LDS once, then each of its wavefronts takes records
+// order[j], j = its number, its number + the waves of the grid's row, ... (order: longest first, so the waves of a row end together; the loop is
+// bounded by n_rec). Lane l keeps nodes l Q + 1 .. l Q + Q of M, I and D of the current row in registers.
+//   M and I of a row need the row before only: the value a node hands to the next, max(M + tMM, I + tIM, D + tDM), moves up one lane at the group's edge.
+//   D of a row is the max-plus recurrence D[k+1] = max(D[k] + tDD[k], M[k] + tMD[k]) along k. Each lane runs it over its own nodes from NEG (Dloc) and
+//   gets its group as the map x -> max(x + a, b): a = the group's sum of tDD (a constant of the profile, scanned once per record), b = what leaves
+//   the group when nothing enters. Six steps of b = max(b, b(lane - d) + a_d) give every lane what really leaves it, the lane above takes that as
+//   c_in and D[q] = max(Dloc[q], c_in + PDD[q]). Integer max and add: the same words as the serial recurrence, in any order.
+//   E = max_k M[k]: D[k] is some M[j] of the same row plus non-positive transitions, or NEG, so max(M, D) over the row is max M.
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_viterbi(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const uint32_t *__restrict__ plist,
+                                                           const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                           const uint32_t *__restrict__ order, uint32_t n_rec, uint32_t n_prof, int32_t *__restrict__ score)
+{
+    extern __shared__ int32_t hmm_lds[];
+    constexpr int MP = 64 * Q;
+    const uint32_t p = plist[blockIdx.y];
+    const HmmDesc d = desc[p];
+    for (int i = (int)threadIdx.x; i < HMM_ROWS_DEV * MP; i += HMM_BLOCK) hmm_lds[i] = tables[d.off + i];
+    __syncthreads();
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int base = lane * Q;
+    const int nvalid = min(max((int)d.M - base, 0), Q);
+    const int32_t *tMM = hmm_lds + HMM_ROW_MM * MP + base, *tMI = hmm_lds + HMM_ROW_MI * MP + base, *tMD = hmm_lds + HMM_ROW_MD * MP + base,
+                  *tIM = hmm_lds + HMM_ROW_IM * MP + base, *tII = hmm_lds + HMM_ROW_II * MP + base, *tDM = hmm_lds + HMM_ROW_DM * MP + base,
+                  *tDD = hmm_lds + HMM_ROW_DD * MP + base, *PDD = hmm_lds + HMM_ROW_PDD * MP + base;
+    int32_t a_step[6];                                      // a of the lanes a scan step joins: sums of tDD, at least 1280 * GS_HMM_STAR
+    {
+        int32_t a = PDD[Q - 1] + tDD[Q - 1];
+        for (int s = 0; s < 6; s++) {
+            a_step[s] = a;
+            const int32_t up = __shfl_up(a, 1 << s);
+            if (lane >= (1 << s)) a += up;
+        }
+    }
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)wave; j < n_rec; j += gridDim.x * HMM_WAVES) {
+        const uint32_t r = order[j];
+        const uint32_t L = (uint32_t)rec_len[r];
+        const uint8_t *x = aa + rec_start[r];
+        int32_t *out = score + (uint64_t)r * n_prof + p;
+        if (L == 0) { if (lane == 0) *out = GS_HMM_NO_SCORE; continue; }
+        const HmmSpecials sp = hmm_specials(L);
+        int32_t Mv[Q], Iv[Q], Dv[Q];
+#pragma unroll
+        for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
+        int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
+        bool bad = false;
+        int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
+        for (uint32_t i0 = 0; i0 < L; i0 += 64) {
+            const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;     // the next 64 residues are on their way while these run
+            bad |= cur < 0;
+            const int res = max(cur, 0);
+            const int cnt = (int)min(64u, L - i0);
+            for (int t = 0; t < cnt; t++) {
+                // up to Q = 16 the eight transition rows of a lane stay in registers across rows (8 Q of them); at 20 they do not fit beside the
+                // 3 Q states, and this keeps the compiler from holding some and spilling others: every row reads them from LDS again
+                if (Q > 16) asm volatile("" ::: "memory");
+                const int32_t *ms = hmm_lds + __builtin_amdgcn_readlane(res, t) * MP + base;
+                const int32_t entry = B + d.tbm;
+                int32_t give[Q];
+#pragma unroll
+                for (int q = 0; q < Q; q++) give[q] = max(max(Mv[q] + tMM[q], Iv[q] + tIM[q]), Dv[q] + tDM[q]);
+                int32_t up = __shfl_up(give[Q - 1], 1);
+                if (lane == 0) up = GS_HMM_NEG;             // node 0 has no states: B + tBM is far above NEG
+#pragma unroll
+                for (int q = 0; q < Q; q++) Iv[q] = max(max(Mv[q] + tMI[q], Iv[q] + tII[q]), GS_HMM_NEG);
+#pragma unroll
+                for (int q = 0; q < Q; q++) Mv[q] = max(ms[q] + max(q ? give[q - 1] : up, entry), GS_HMM_NEG);
+                int32_t dl = GS_HMM_NEG;
+                Dv[0] = dl;
+#pragma unroll
+                for (int q = 1; q < Q; q++) { dl = max(max(dl + tDD[q - 1], Mv[q - 1] + tMD[q - 1]), GS_HMM_NEG); Dv[q] = dl; }
+                int32_t b = max(max(dl + tDD[Q - 1], Mv[Q - 1] + tMD[Q - 1]), GS_HMM_NEG);
+#pragma unroll
+                for (int s = 0; s < 6; s++) b = max(b, __shfl_up(b, 1 << s) + a_step[s]);     // a lane below 2^s gets its own b back: b + a <= b
+                int32_t c_in = __shfl_up(b, 1);
+                if (lane == 0) c_in = GS_HMM_NEG;
+                int32_t e = GS_HMM_NEG;
+#pragma unroll
+                for (int q = 0; q < Q; q++) {
+                    Dv[q] = max(Dv[q], c_in + PDD[q]);
+                    if (q < nvalid) e = max(e, Mv[q]);
+                }
+                const int32_t E = hmm_wave_max(e);
+                N += sp.tloop;
+                J = max(max(J + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
+                C = max(max(C + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
+                B = max(N, J) + sp.tmove;
+            }
+            cur = nxt;
+        }
+        const bool any_bad = __any(bad);
+        if (lane == 0) *out = any_bad ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
+    }
+}
+
+// one thread per (genome, profile): the records of the genome in order, so the first of equal scores stays
+__global__ __launch_bounds__(256) void k_hmm_best(const int32_t *__restrict__ score, const uint64_t *__restrict__ goff, uint64_t n_genomes, uint32_t n_prof,
+                                                  const int32_t *__restrict__ thr, uint32_t *__restrict__ best_rec, int32_t *__restrict__ best_score)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_genomes * n_prof) return;
+    const uint64_t g = i / n_prof;
+    const uint32_t p = (uint32_t)(i % n_prof);
+    const int32_t t = thr[p];
+    uint32_t br = GS_HMM_NO_HIT;
+    int32_t bs = GS_HMM_NO_SCORE;
+    for (uint64_t r = goff[g], r1 = goff[g + 1]; r < r1; r++) {
+        const int32_t s = score[r * n_prof + p];
+        if (s != GS_HMM_NO_SCORE && s >= t && s > bs) { bs = s; br = (uint32_t)r; }
+    }
+    best_rec[i] = br;
+    best_score[i] = bs;
+}
+
+typedef void (*hmm_kernel_t)(const int32_t *, const HmmDesc *, const uint32_t *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint32_t,
+                             uint32_t, int32_t *);
+static hmm_kernel_t hmm_kernel(int cls)
+{
+    switch (cls) {
+    case 0: return k_hmm_viterbi<1>;
+    case 1: return k_hmm_viterbi<2>;
+    case 2: return k_hmm_viterbi<3>;
+    case 3: return k_hmm_viterbi<4>;
+    case 4: return k_hmm_viterbi<6>;
+    case 5: return k_hmm_viterbi<8>;
+    case 6: return k_hmm_viterbi<12>;
+    case 7: return k_hmm_viterbi<16>;
+    default: return k_hmm_viterbi<20>;
+    }
+}
+static int hmm_class_of(uint32_t M)
+{
+    for (int c = 0; c < HMM_CLASSES; c++) if ((uint32_t)HMM_CLASS_Q[c] * 64 >= M) return c;
+    return HMM_CLASSES - 1;
+}
+
+}  // namespace gs
+
+struct gs_hmm_db {
+    gs_ctx *ctx = nullptr;
+    std::vector<gs::HmmModel> models;
+    std::vector<gs::HmmDesc> desc;
+    std::vector<uint32_t> plist;                    // profile numbers, class by class
+    uint32_t class_start[gs::HMM_CLASSES + 1] = {};
+    bool all_ga = true;
+    bool lds_set[gs::HMM_CLASSES] = {};
+    gs::DevBuf d_tables, d_desc, d_plist, d_ga;
+};
+
+namespace gs {
+
+static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **out)
+{
+    GS_REQUIRE(models.size() < (1ull << 31), GS_ERR_UNSUPPORTED, "hmm: too many profiles");
+    std::unique_ptr<gs_hmm_db> db(new gs_hmm_db());
+    db->ctx = c;
+    db->models = std::move(models);
+    const size_t np = db->models.size();
+    std::vector<int32_t> words, ga(np, 0);
+    std::vector<std::vector<uint32_t>> by_class(HMM_CLASSES);
+    for (size_t p = 0; p < np; p++) {
+        const HmmModel &m = db->models[p];
+        const uint32_t M = m.info.M, W = M + 1;
+        const int cls = hmm_class_of(M), Q = HMM_CLASS_Q[cls], MP = 64 * Q;
+        by_class[cls].push_back((uint32_t)p);
+        db->desc.push_back(HmmDesc{(uint64_t)words.size(), M, m.info.tbm});
+        const size_t at = words.size();
+        words.resize(at + (size_t)HMM_ROWS_DEV * MP, GS_HMM_STAR);
+        for (int row = 0; row < (int)GS_HMM_TABLE_ROWS; row++)
+            for (uint32_t k = 1; k <= M; k++) words[at + (size_t)row * MP + (k - 1)] = m.tab[(size_t)row * W + k];
+        for (int j = 0; j < MP; j++)
+            words[at + (size_t)HMM_ROW_PDD * MP + j] = j % Q == 0 ? 0 : words[at + (size_t)HMM_ROW_PDD * MP + j - 1] + words[at + (size_t)HMM_ROW_DD * MP + j - 1];
+        if (m.info.flags & GS_HMM_HAS_GA) ga[p] = m.info.ga_units; else db->all_ga = false;
+    }
+    for (int cls = 0; cls < HMM_CLASSES; cls++) {
+        db->class_start[cls] = (uint32_t)db->plist.size();
+        db->plist.insert(db->plist.end(), by_class[cls].begin(), by_class[cls].end());
+    }
+    db->class_start[HMM_CLASSES] = (uint32_t)db->plist.size();
+    GS_CTX_LOCK(c);
+    int rc;
+    if ((rc = db->d_tables.alloc(4 * words.size())) || (rc = db->d_desc.alloc(sizeof(HmmDesc) * np)) || (rc = db->d_plist.alloc(4 * np)) || (rc = db->d_ga.alloc(4 * np))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_tables.p, words.data(), 4 * words.size(), hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_desc.p, db->desc.data(), sizeof(HmmDesc) * np, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_plist.p, db->plist.data(), 4 * np, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_ga.p, ga.data(), 4 * np, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(stream_wait(c));           // the host vectors go out of scope
+    *out = db.release();
+    return GS_OK;
+}
+
+// lens: the host copy of rec_len; everything else device memory. Queued on c's stream; the order list lives in its slot until the caller's scope ends.
+static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
+                           int32_t *score_dev, PoolBuf &d_order)
+{
+    const uint32_t np = (uint32_t)db->models.size();
+    std::vector<uint32_t> order(n_rec);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lens[a] > lens[b]; });
+    int rc;
+    if ((rc = d_order.alloc(4 * n_rec))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(d_order.p, order.data(), 4 * n_rec, hipMemcpyHostToDevice, c->stream));
+    const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
+    for (int cls = 0; cls < HMM_CLASSES; cls++) {
+        const uint32_t n_in = db->class_start[cls + 1] - db->class_start[cls];
+        if (!n_in) continue;
+        const size_t lds = (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4;
+        hmm_kernel_t k = hmm_kernel(cls);
+        if (!db->lds_set[cls]) {
+            if (lds > 64 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            db->lds_set[cls] = true;
+        }
+        for (uint32_t y0 = 0; y0 < n_in; y0 += 65535) {       // (the y dimension of a grid ends at 65535)
+            ProfScope ps(c, FAM_SEARCH);
+            k<<<dim3(wg, std::min<uint32_t>(n_in - y0, 65535)), HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(),
+                                                                                           db->d_plist.as<uint32_t>() + db->class_start[cls] + y0, aa_dev, rs_dev, rl_dev,
+                                                                                           d_order.as<uint32_t>(), (uint32_t)n_rec, np, score_dev);
+            GS_HIP_CHECK(hipGetLastError());
+        }
+    }
+    GS_HIP_CHECK(stream_wait(c));           // `order` is read by the copy until here
+    return GS_OK;
+}
+static int hmm_check_lens(const uint64_t *lens, uint64_t n_rec)
+{
+    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
+    for (uint64_t r = 0; r < n_rec; r++)
+        GS_REQUIRE(lens[r] <= GS_HMM_MAX_L, GS_ERR_UNSUPPORTED, "hmm: record %llu has %llu residues, more than %u", (unsigned long long)r, (unsigned long long)lens[r],
+                   GS_HMM_MAX_L);
+    return GS_OK;
+}
+
+}  // namespace gs
+
+extern "C" {
+
+int gs_hmm_parse_mem(const void *text, uint64_t n_bytes, uint32_t model, gs_hmm_info *info_out, int32_t *tables_out, uint64_t cap_words, uint32_t *n_models_out)
+{
+    using namespace gs;
+    GS_REQUIRE(text || n_bytes == 0, GS_ERR_INVALID, "null argument");
+    std::vector<HmmModel> ms;
+    int rc = hmm_parse_all((const char *)text, (size_t)n_bytes, ms);
+    if (rc) return rc;
+    if (n_models_out) *n_models_out = (uint32_t)ms.size();
+    GS_REQUIRE(model < ms.size(), GS_ERR_INVALID, "hmm: model %u of %zu", model, ms.size());
+    if (info_out) *info_out = ms[model].info;
+    if (tables_out) {
+        GS_REQUIRE(cap_words >= ms[model].tab.size(), GS_ERR_INVALID, "hmm: the table needs %zu words, cap_words = %llu", ms[model].tab.size(), (unsigned long long)cap_words);
+        memcpy(tables_out, ms[model].tab.data(), 4 * ms[model].tab.size());
+    }
+    return GS_OK;
+}
+
+int gs_hmm_specials(uint64_t L, uint32_t M, int32_t out[6])
+{
+    using namespace gs;
+    GS_REQUIRE(out && L >= 1 && M >= 1, GS_ERR_INVALID, "bad argument");
+    GS_REQUIRE(L <= GS_HMM_MAX_L && M <= GS_HMM_MAX_M, GS_ERR_UNSUPPORTED, "hmm: L = %llu, M = %u: larger than the limits", (unsigned long long)L, M);
+    const HmmSpecials s = hmm_specials((uint32_t)L);
+    out[0] = s.tloop; out[1] = s.tmove; out[2] = s.null; out[3] = hmm_tbm(M); out[4] = s.nloop; out[5] = s.nmove;
+    return GS_OK;
+}
+
+int gs_hmm_db_load_mem(gs_ctx *c, const void *const *texts, const uint64_t *n_bytes, uint64_t n_texts, gs_hmm_db **out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && out && n_texts >= 1 && texts && n_bytes, GS_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::vector<HmmModel> ms;
+    for (uint64_t i = 0; i < n_texts; i++) {
+        GS_REQUIRE(texts[i] || n_bytes[i] == 0, GS_ERR_INVALID, "null text %llu", (unsigned long long)i);
+        int rc = hmm_parse_all((const char *)texts[i], (size_t)n_bytes[i], ms);
+        if (rc) return rc;
+    }
+    return hmm_db_build(c, std::move(ms), out);
+}
+
+int gs_hmm_db_load(gs_ctx *c, const char *const *paths, uint64_t n_paths, gs_hmm_db **out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && out && n_paths >= 1 && paths, GS_ERR_INVALID, "null argument");
+    *out = nullptr;
+    std::vector<HmmModel> ms;
+    for (uint64_t i = 0; i < n_paths; i++) {
+        GS_REQUIRE(paths[i], GS_ERR_INVALID, "null path %llu", (unsigned long long)i);
+        FILE *fp = fopen(paths[i], "rb");
+        GS_REQUIRE(fp, GS_ERR_IO, "cannot open %s", paths[i]);
+        std::string text;
+        char buf[65536];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof buf, fp)) > 0) text.append(buf, got);
+        const bool failed = ferror(fp) != 0;
+        fclose(fp);
+        GS_REQUIRE(!failed, GS_ERR_IO, "cannot read %s", paths[i]);
+        int rc = hmm_parse_all(text.data(), text.size(), ms);
+        if (rc) return rc;
+    }
+    return hmm_db_build(c, std::move(ms), out);
+}
+
+void gs_hmm_db_free(gs_hmm_db *db)
+{
+    if (!db) return;
+    { GS_CTX_LOCK(db->ctx); (void)gs::stream_wait(db->ctx); }
+    delete db;
+}
+
+int gs_hmm_db_info(gs_hmm_db *db, uint64_t *n_prof_out, gs_hmm_info *info_out, uint64_t cap)
+{
+    GS_REQUIRE(db && n_prof_out, GS_ERR_INVALID, "null argument");
+    *n_prof_out = db->models.size();
+    if (info_out) for (uint64_t p = 0; p < cap && p < db->models.size(); p++) info_out[p] = db->models[p].info;
+    return GS_OK;
+}
+
+int gs_hmm_db_tables(gs_hmm_db *db, uint64_t p, int32_t *tables_out, uint64_t cap_words)
+{
+    using namespace gs;
+    GS_REQUIRE(db && tables_out && p < db->models.size(), GS_ERR_INVALID, "bad argument");
+    const HmmModel &m = db->models[p];
+    const uint32_t M = m.info.M, W = M + 1;
+    GS_REQUIRE(cap_words >= (uint64_t)GS_HMM_TABLE_ROWS * W, GS_ERR_INVALID, "hmm: the table needs %llu words", (unsigned long long)GS_HMM_TABLE_ROWS * W);
+    gs_ctx *c = db->ctx;
+    GS_CTX_LOCK(c);
+    const int MP = 64 * HMM_CLASS_Q[hmm_class_of(M)];
+    std::vector<int32_t> dev((size_t)HMM_ROWS_DEV * MP);
+    GS_HIP_CHECK(hipMemcpyAsync(dev.data(), db->d_tables.as<int32_t>() + db->desc[p].off, 4 * dev.size(), hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    for (uint32_t row = 0; row < GS_HMM_TABLE_ROWS; row++) {
+        tables_out[(size_t)row * W] = m.tab[(size_t)row * W];                 // node 0 is not on the device: no state of it exists (SPEC 13)
+        for (uint32_t k = 1; k <= M; k++) tables_out[(size_t)row * W + k] = dev[(size_t)row * MP + (k - 1)];
+    }
+    return GS_OK;
+}
+
+int gs_hmm_search_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int32_t *score_out_dev)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_rec == 0) return GS_OK;
+    GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && score_out_dev, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
+    GS_CTX_LOCK(c);
+    std::vector<uint64_t> lens(n_rec);
+    GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rec_len_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    int rc = hmm_check_lens(lens.data(), n_rec);
+    if (rc) return rc;
+    PoolBuf d_order(c, SL_HMM_ORDER);
+    return hmm_search_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, score_out_dev, d_order);
+}
+
+int gs_hmm_search(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *score_out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_rec == 0) return GS_OK;
+    GS_REQUIRE(rec_start && rec_len && score_out, GS_ERR_INVALID, "null argument");
+    int rc = hmm_check_lens(rec_len, n_rec);
+    if (rc) return rc;
+    uint64_t n_bytes = 0;
+    for (uint64_t r = 0; r < n_rec; r++) if (rec_len[r]) n_bytes = std::max(n_bytes, rec_start[r] + rec_len[r]);
+    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
+    const uint64_t np = db->models.size();
+    GS_CTX_LOCK(c);
+    PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_order(c, SL_HMM_ORDER);
+    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec)) || (rc = d_score.alloc(4 * n_rec * np))) return rc;
+    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+    if ((rc = hmm_search_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, d_score.as<int32_t>(), d_order))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(score_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+int gs_hmm_best_hits_dev(gs_ctx *c, gs_hmm_db *db, const int32_t *score_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes,
+                         const int32_t *thr_dev, uint32_t *best_rec_out, int32_t *best_score_out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_genomes == 0) return GS_OK;
+    GS_REQUIRE(genome_rec_off_dev && best_rec_out && best_score_out && (score_dev || n_rec == 0), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
+    GS_REQUIRE(thr_dev || db->all_ga, GS_ERR_INVALID, "hmm: a profile of the set has no GA cutoff: give thresholds");
+    const uint64_t np = db->models.size(), n = n_genomes * np;
+    GS_REQUIRE(n < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many (genome, profile) pairs");
+    GS_CTX_LOCK(c);
+    std::vector<uint64_t> off(n_genomes + 1);
+    GS_HIP_CHECK(hipMemcpyAsync(off.data(), genome_rec_off_dev, 8 * (n_genomes + 1), hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    for (uint64_t g = 0; g < n_genomes; g++) GS_REQUIRE(off[g] <= off[g + 1], GS_ERR_INVALID, "hmm: genome offsets decrease at genome %llu", (unsigned long long)g);
+    GS_REQUIRE(off[n_genomes] <= n_rec, GS_ERR_INVALID, "hmm: genome offsets end at %llu, past n_rec = %llu", (unsigned long long)off[n_genomes], (unsigned long long)n_rec);
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_best<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(score_dev, genome_rec_off_dev, n_genomes, (uint32_t)np, thr_dev ? thr_dev : db->d_ga.as<int32_t>(),
+                                                                      best_rec_out, best_score_out);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+double gs_hmm_bits(int32_t raw) { return (double)raw / 1024.0; }
+double gs_hmm_evalue(double bits, double mu, double lambda, double Z) { return Z * -::expm1(-::exp(-lambda * (bits - mu))); }
+
+}  // extern "C"

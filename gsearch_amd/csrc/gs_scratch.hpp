@@ -71,6 +71,8 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* superani, a block's anchors, its segments, the chaining result, chain ends and the per-seed marks of both sides */                              \
     X(ANI_A_RCTG) X(ANI_A_RPOS) X(ANI_A_QCTG) X(ANI_A_QPOS) X(ANI_A_STRAND) X(ANI_A_RIDX) X(ANI_A_QIDX) X(ANI_A_PAIR) X(ANI_SEG_TILES)                \
     X(ANI_SEG_START) X(ANI_SEG_N) X(ANI_F) X(ANI_PRED) X(ANI_ROOT) X(ANI_BEST) X(ANI_NCHAIN) X(ANI_MATCHED) X(ANI_DIFF)                               \
+    /* hmmsearch (gs_hmm.hip): the records of a call, longest first; staging of the host form */                                                       \
+    X(HMM_ORDER) X(HMMB_AA) X(HMMB_REC_START) X(HMMB_REC_LEN) X(HMMB_SCORE)                                                                           \
     /* comm (gs_topk_merge_dev) */                                                                                                                    \
     X(COMM_ID_OFFSET)
 

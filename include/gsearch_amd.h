@@ -267,6 +267,59 @@ int gs_ani_chain_dev(gs_ctx *, const uint32_t *rcontig_dev, const uint32_t *rpos
 int gs_ani_estimate(const uint64_t *counts, const uint64_t *bases_q, const uint64_t *bases_r, uint64_t n_pairs, uint32_t k, float *out);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* hmmsearch (`hmmsearch_rs -f proteome.faa -m profile.HMM`, the universal-gene level): the local multihit Viterbi score of every protein
+ * against every profile of a set of HMMER3 profiles, and the best protein per genome and profile. Arithmetic: SPEC 13 - int32 in units of
+ * 2^-10 bit, no floating point in the scored path. A record is residues as gs_filter_aa leaves them (the 20 letters, either case). */
+#define GS_HMM_MAX_M 1280u            /* nodes of a profile at most (20 per lane of a wavefront); the reference's longest has 1238 */
+#define GS_HMM_MAX_L (1u << 18)       /* residues of a record at most: L * 6608 + 151000 < 2^31 (SPEC 13) */
+#define GS_HMM_NO_SCORE INT32_MIN     /* score of an empty record (or of one with a byte that is no residue) */
+#define GS_HMM_NO_HIT 0xFFFFFFFFu
+#define GS_HMM_TABLE_ROWS 27u         /* rows of a profile's table: 20 match rows (ACDEFGHIKLMNPQRSTVWY), then m->m m->i m->d i->m i->i d->m d->d */
+#define GS_HMM_HAS_GA 1u
+#define GS_HMM_HAS_TC 2u
+#define GS_HMM_HAS_NC 4u
+#define GS_HMM_HAS_STATS 8u
+typedef struct gs_hmm_db gs_hmm_db;
+typedef struct {
+    char name[64], acc[32];           /* NAME and ACC (empty when the file has none), cut to fit, NUL-terminated */
+    uint32_t M, flags;                /* nodes; GS_HMM_HAS_* */
+    double ga[2], tc[2], nc[2];       /* cutoffs in bits as the file gives them */
+    double mu, lambda;                /* STATS LOCAL VITERBI */
+    int32_t ga_units, tbm;            /* GA1 in units (rounded half up); the entry score units(ln(2 / (M (M + 1)))) */
+} gs_hmm_info;
+/* host only: model number `model` of a HMMER3 ASCII text that holds *n_models_out models (either dialect of the reference's sets, with or
+ * without a COMPO line). info_out and tables_out are optional; tables_out: int32 [27][M + 1], row a < 20 = match score of residue a at node
+ * k = 1..M (column 0 is 0), rows 20..26 = the transition scores of node k = 0..M; cap_words >= 27 (M + 1) or GS_ERR_INVALID. Anything
+ * malformed (truncated, no `//`, a node number out of order, more than 5 decimals, ALPH other than amino): GS_ERR_INVALID; M > GS_HMM_MAX_M:
+ * GS_ERR_UNSUPPORTED. */
+int gs_hmm_parse_mem(const void *text, uint64_t n_bytes, uint32_t model, gs_hmm_info *info_out, int32_t *tables_out, uint64_t cap_words,
+                     uint32_t *n_models_out);
+/* host only: out = {tloop, tmove, null, tBM, nloop, nmove} of a target of L = n_residues (1 <= L <= GS_HMM_MAX_L) and a profile of M = n_nodes
+ * (1 <= M <= GS_HMM_MAX_M), null = L * nloop + nmove; larger: GS_ERR_UNSUPPORTED */
+int gs_hmm_specials(uint64_t n_residues, uint32_t n_nodes, int32_t out[6]);
+/* a set of profiles in device memory, in the order of the files and of the models inside each; release with gs_hmm_db_free */
+int gs_hmm_db_load(gs_ctx *ctx, const char *const *paths, uint64_t n_paths, gs_hmm_db **out);
+int gs_hmm_db_load_mem(gs_ctx *ctx, const void *const *texts, const uint64_t *n_bytes, uint64_t n_texts, gs_hmm_db **out);
+void gs_hmm_db_free(gs_hmm_db *db);
+/* *n_prof_out = the number of profiles; info_out (optional): the first min(cap, n_prof) of them */
+int gs_hmm_db_info(gs_hmm_db *db, uint64_t *n_prof_out, gs_hmm_info *info_out, uint64_t cap);
+/* the table of profile p as gs_hmm_parse_mem writes it, nodes 1..M read back from the device copy the kernel uses */
+int gs_hmm_db_tables(gs_hmm_db *db, uint64_t p, int32_t *tables_out, uint64_t cap_words);
+/* score_out[r * n_prof + p] = raw score of record r = aa[rec_start[r] .. + rec_len[r]) against profile p. Device form: all arrays device
+ * memory; the lengths are read back once. A record longer than GS_HMM_MAX_L, or 2^32 records or more: GS_ERR_UNSUPPORTED, nothing written. */
+int gs_hmm_search_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                      int32_t *score_out_dev);
+int gs_hmm_search(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *score_out);
+/* segmented argmax: genome g = records [genome_rec_off[g], genome_rec_off[g+1]) of an n_rec x n_prof score matrix;
+ * best_rec_out[g * n_prof + p] = the record with the largest score >= thr[p], the lowest such record on a tie, GS_HMM_NO_HIT when none;
+ * best_score_out = its score or GS_HMM_NO_SCORE. thr_dev = NULL: every profile's GA1 (a profile without GA: GS_ERR_INVALID). All device memory. */
+int gs_hmm_best_hits_dev(gs_ctx *ctx, gs_hmm_db *db, const int32_t *score_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes,
+                         const int32_t *thr_dev, uint32_t *best_rec_out, int32_t *best_score_out);
+/* host only, double: raw / 1024, and E = n_targets * P with P = -expm1(-exp(-lambda (bits - mu))) (the Gumbel tail of STATS LOCAL VITERBI) */
+double gs_hmm_bits(int32_t raw);
+double gs_hmm_evalue(double bits, double mu, double lambda, double n_targets);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */
 /*   new/modify_level_scale/set_extend_candidates/set_keeping_pruned  dnasketch.rs:139-141,159-160  */
 /*   parallel_insert dnasketch.rs:435, aasketch.rs:407;  parallel_search dnarequest.rs:353, aarequest.rs:344 */

@@ -234,6 +234,44 @@ inline std::vector<float> ani_estimate(const std::vector<uint64_t> &counts, cons
     return out;
 }
 
+// hmmsearch (`hmmsearch_rs -f proteome.faa -m profile.HMM`; SPEC 13): a set of HMMER3 profiles on the device, the raw Viterbi score (units of 2^-10 bit)
+// of every record against every profile, and the best record per genome and profile
+class HmmDb {
+public:
+    HmmDb(Context &ctx, const std::vector<std::string> &paths) : ctx_(&ctx)
+    {
+        std::vector<const char *> p;
+        for (const auto &s : paths) p.push_back(s.c_str());
+        check(gs_hmm_db_load(ctx.get(), p.data(), p.size(), &db_));
+        uint64_t n = 0;
+        check(gs_hmm_db_info(db_, &n, nullptr, 0));
+        info_.resize(n);
+        check(gs_hmm_db_info(db_, &n, info_.data(), n));
+    }
+    ~HmmDb() { gs_hmm_db_free(db_); }
+    HmmDb(const HmmDb &) = delete;
+    HmmDb &operator=(const HmmDb &) = delete;
+    gs_hmm_db *get() const { return db_; }
+    const std::vector<gs_hmm_info> &info() const { return info_; }
+    // residues as gs_filter_aa leaves them; record r = aa[rec_start[r] .. + rec_len[r]) -> n_rec x n_prof scores, GS_HMM_NO_SCORE for an empty record
+    std::vector<int32_t> search(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len) const
+    {
+        std::vector<int32_t> out(rec_start.size() * info_.size());
+        check(gs_hmm_search(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), out.data()));
+        return out;
+    }
+    static double bits(int32_t raw) { return gs_hmm_bits(raw); }
+    double evalue(size_t profile, int32_t raw, double n_targets) const
+    {
+        return gs_hmm_evalue(gs_hmm_bits(raw), info_[profile].mu, info_[profile].lambda, n_targets);
+    }
+
+private:
+    Context *ctx_;
+    gs_hmm_db *db_ = nullptr;
+    std::vector<gs_hmm_info> info_;
+};
+
 // bigsig (binaux/src/bin/bigsig.rs; SPEC 11): a bit-sliced Bloom index of genomes - one colour per genome in the order added - and, for every read, the
 // colour with the most k-mer hits and whether that many hits are significant. A genome or a read is a list of records (ASCII text); the mates of a
 // pair are two records of one read.
