@@ -75,6 +75,7 @@ class HmmInfoC(C.Structure):
 
 HMM_MAX_M, HMM_MAX_L, HMM_NO_SCORE, HMM_NO_HIT, HMM_TABLE_ROWS = 1280, 1 << 18, -(1 << 31), 0xFFFFFFFF, 27
 HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
+HMM_FWD_MAX_L, HMM_LSE_N, HMM_FLOOR_ALL = 65536, 5903, -(1 << 31) + 1
 
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
@@ -159,6 +160,12 @@ SYMBOLS = {
     "gs_hmm_best_hits_dev": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
     "gs_hmm_bits": (C.c_double, [C.c_int32]),
     "gs_hmm_evalue": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double]),
+    "gs_hmm_logsum_table": (_i, [_vp, _u64]),
+    "gs_hmm_parse_stats_mem": (_i, [_vp, _u64, _u32, _vp, C.POINTER(_u32)]),
+    "gs_hmm_viterbi_floor": (_i, [C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32)]),
+    "gs_hmm_search_forward_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "gs_hmm_search_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "gs_hmm_forward_evalue": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double]),
     "gs_index_create": (_i, [_vp, C.POINTER(IndexParams), C.POINTER(_vp)]),
     "gs_index_destroy": (None, [_vp]),
     "gs_index_nb_point": (_u64, [_vp]),

@@ -886,6 +886,34 @@ def hmm_evalue(bits, mu, lam, n_targets):
     return _lib.load().gs_hmm_evalue(float(bits), float(mu), float(lam), float(n_targets))
 
 
+def hmm_forward_evalue(bits, tau, lam, n_targets):
+    """E = n_targets * P with P = 1 below tau, exp(-lam (bits - tau)) above: the exponential tail of a profile's STATS LOCAL FORWARD line (SPEC 13.1)"""
+    return _lib.load().gs_hmm_forward_evalue(float(bits), float(tau), float(lam), float(n_targets))
+
+
+def hmm_logsum_table():
+    """T of SPEC 13.1 as the library holds it: uint16 [5903]; host only"""
+    out = np.zeros(_lib.HMM_LSE_N, np.uint16)
+    check(_lib.load().gs_hmm_logsum_table(_p(out), out.size))
+    return out
+
+
+def hmm_parse_stats(text, model=0):
+    """({msv mu, lambda, viterbi mu, lambda, forward tau, lambda} as float64 [6], has) of model number `model` of a HMMER3 text: has bit 0 / 1 / 2 =
+    the STATS LOCAL MSV / VITERBI / FORWARD line was there; host only"""
+    buf = np.frombuffer(bytes(text), dtype=np.uint8)
+    out, has = np.zeros(6, np.float64), C.c_uint32()
+    check(_lib.load().gs_hmm_parse_stats_mem(_p(buf) if len(buf) else None, len(buf), int(model), _p(out), C.byref(has)))
+    return out, has.value
+
+
+def hmm_viterbi_floor(mu, lam, p=1e-3):
+    """the Viterbi score in units whose Gumbel tail mass is p (SPEC 13.1): floor((mu - ln(-ln(1 - p)) / lam) * 1024 + 1/2); host only"""
+    out = C.c_int32()
+    check(_lib.load().gs_hmm_viterbi_floor(float(mu), float(lam), float(p), C.byref(out)))
+    return out.value
+
+
 def hmm_threshold_units(bits):
     """a caller's cutoff in bits -> units of 2^-10 bit: floor(bits * 1024 + 1/2)"""
     import math
@@ -906,6 +934,7 @@ class HmmDb:
             ptr = (C.c_void_p * len(bufs))(*[b.ctypes.data if len(b) else None for b in bufs])
             nb = (C.c_uint64 * len(bufs))(*[len(b) for b in bufs])
             check(L.gs_hmm_db_load_mem(self.ctx.h, ptr, nb, len(bufs), C.byref(h)))
+            file_texts = [bytes(t) for t in paths_or_dir]
         else:
             if isinstance(paths_or_dir, (str, bytes, os.PathLike)):
                 d = os.fsdecode(paths_or_dir)
@@ -914,6 +943,10 @@ class HmmDb:
                 paths = [os.fsdecode(x) for x in paths_or_dir]
             arr = (C.c_char_p * len(paths))(*[x.encode() for x in paths])
             check(L.gs_hmm_db_load(self.ctx.h, arr, len(paths), C.byref(h)))
+            file_texts = []
+            for x in paths:
+                with open(x, "rb") as f:
+                    file_texts.append(f.read())
         self.h = h
         n = C.c_uint64()
         check(L.gs_hmm_db_info(self.h, C.byref(n), None, 0))
@@ -927,6 +960,18 @@ class HmmDb:
         self.mu = np.array([i["mu"] if i["mu"] is not None else np.nan for i in self.info])
         self.lam = np.array([i["lam"] if i["lam"] is not None else np.nan for i in self.info])
         self.ga_units = [i["ga_units"] for i in self.info]
+        # STATS LOCAL FORWARD tau / lambda of every profile (nan without the line), through gs_hmm_parse_stats_mem
+        fstats = []
+        for t in file_texts:
+            n_models = C.c_uint32()
+            buf = np.frombuffer(t, dtype=np.uint8)
+            check(L.gs_hmm_parse_mem(_p(buf), len(buf), 0, None, None, 0, C.byref(n_models)))
+            for k in range(n_models.value):
+                st, has = hmm_parse_stats(t, k)
+                fstats.append((st[4], st[5]) if has & 4 else (np.nan, np.nan))
+        assert len(fstats) == len(self.info)
+        self.tau = np.array([a for a, _ in fstats])
+        self.lam_fwd = np.array([b for _, b in fstats])
 
     def __len__(self):
         return len(self.info)
@@ -965,6 +1010,40 @@ class HmmDb:
 
     def search_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, score_out_dev):
         check(self.ctx.L.gs_hmm_search_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), score_out_dev))
+
+    def viterbi_floor(self, filter_p=1e-3):
+        """int32 [n_prof]: per profile the Viterbi score in units below which Forward is not run (SPEC 13.1) - the score whose Gumbel tail mass under the
+        profile's STATS LOCAL VITERBI line is filter_p; a profile without that line: INT32_MIN + 1, every pair that has a Viterbi score"""
+        return np.array([hmm_viterbi_floor(i["mu"], i["lam"], filter_p) if i["mu"] is not None else _lib.HMM_FLOOR_ALL for i in self.info], np.int32)
+
+    def _floor(self, filter_p, floor):
+        if floor is not None:
+            fl = np.ascontiguousarray(floor, dtype=np.int32)
+            if fl.shape != (len(self),):
+                raise ValueError("floor: one int32 per profile")
+            return fl
+        return None if filter_p is None else self.viterbi_floor(filter_p)
+
+    def search_forward_packed(self, aa, rec_start, rec_len, filter_p=1e-3, floor=None):
+        """residues as filter_aa_records() returns them -> (vit, fwd), int32 [n_rec, n_prof]: what search_packed() returns, and the Forward raw score of
+        the pairs whose Viterbi score reaches the profile's floor (HMM_NO_SCORE for the others)"""
+        aa = np.ascontiguousarray(aa, dtype=np.uint8)
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        fl = self._floor(filter_p, floor)
+        vit, fwd = np.zeros((len(rs), len(self)), np.int32), np.zeros((len(rs), len(self)), np.int32)
+        check(self.ctx.L.gs_hmm_search_forward(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None,
+                                               len(rs), _p(fl) if fl is not None else None, _p(vit) if vit.size else None, _p(fwd) if fwd.size else None))
+        return vit, fwd
+
+    def search_forward(self, records, filter_p=1e-3, floor=None):
+        """records as search() takes them -> (vit, fwd). Forward runs for the pairs with vit >= the profile's floor: `floor` (int32 [n_prof], units) when
+        given, else viterbi_floor(filter_p); filter_p=None: every pair that has a Viterbi score"""
+        return self.search_forward_packed(*filter_aa_records([bytes(r) for r in records]), filter_p=filter_p, floor=floor)
+
+    def search_forward_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, vit_floor_dev, vit_out_dev, fwd_out_dev):
+        """all device memory; vit_floor_dev None: every pair, vit_out_dev None: the Viterbi matrix is not wanted"""
+        check(self.ctx.L.gs_hmm_search_forward_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), vit_floor_dev, vit_out_dev, fwd_out_dev))
 
     def thresholds(self, cutoff="ga"):
         """int32 [n_prof] in units: every profile's GA1, or the caller's bits for all (a number) or per profile (a sequence)"""
@@ -1017,15 +1096,20 @@ def _as_hmm_db(hmm, ctx):
     return hmm if isinstance(hmm, HmmDb) else HmmDb(hmm, ctx)
 
 
-def hmmsearch(faa, hmm, output=None, ctx=None):
+def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
     `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
     `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
     (record, profile) with raw >= 0, sorted by (profile, -raw, record); bits %.2f, evalue %.3E with Z = the number of records (`-` without STATS),
-    pass_ga 1 / 0 (`-` without GA), acc `-` when the profile has none."""
+    pass_ga 1 / 0 (`-` without GA), acc `-` when the profile has none.
+    score="forward" (SPEC 13.1): the scores are the Forward matrix behind the Viterbi floor of filter_p (None: every pair) - bits and pass_ga of the
+    Forward raw, evalue from STATS LOCAL FORWARD (`-` without the line), rows for the pairs that have a Forward raw >= 0."""
+    if score not in ("viterbi", "forward"):
+        raise ValueError("score: 'viterbi' or 'forward'")
     db = _as_hmm_db(hmm, ctx)
     ids, seqs = _faa_records(faa)
-    scores = db.search(seqs)
+    fwd = score == "forward"
+    scores = db.search_forward(seqs, filter_p=filter_p)[1] if fwd else db.search(seqs)
     Z = len(ids)
     out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga\n"]
     for p, inf in enumerate(db.info):
@@ -1034,7 +1118,10 @@ def hmmsearch(faa, hmm, output=None, ctx=None):
         for r in keep[np.lexsort((keep, -col[keep]))]:
             raw = int(col[r])
             b = hmm_bits(raw)
-            ev = "%.3E" % hmm_evalue(b, inf["mu"], inf["lam"], Z) if inf["mu"] is not None else "-"
+            if fwd:
+                ev = "%.3E" % hmm_forward_evalue(b, db.tau[p], db.lam_fwd[p], Z) if not np.isnan(db.tau[p]) else "-"
+            else:
+                ev = "%.3E" % hmm_evalue(b, inf["mu"], inf["lam"], Z) if inf["mu"] is not None else "-"
             ga = "-" if inf["ga_units"] is None else ("1" if raw >= inf["ga_units"] else "0")
             out.append(("%s\t%s\t%s\t%.2f\t%s\t%s\n" % (ids[r], inf["name"], inf["acc"] or "-", b, ev, ga)).encode())
     table = b"".join(out)
@@ -1044,17 +1131,20 @@ def hmmsearch(faa, hmm, output=None, ctx=None):
     return ids, scores, table
 
 
-def universal_genes(faa_files, hmm, ctx=None, cutoff="ga"):
+def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3):
     """One genome per protein FASTA file: per genome the residues of its best protein for every profile that has a hit at the cutoff, in profile
     order - the records an AA sketcher takes for `tohnsw` / `request` at the universal-gene level. -> (list of lists of bytes, uint32 [n_genomes, n_prof]
-    record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing)"""
+    record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing). score="forward": the best hits are those of the Forward matrix
+    (SPEC 13.1) behind the Viterbi floor of filter_p - the score the files' GA cutoffs were gathered on."""
+    if score not in ("viterbi", "forward"):
+        raise ValueError("score: 'viterbi' or 'forward'")
     db = _as_hmm_db(hmm, ctx)
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
         goff.append(len(seqs))
     aa, rs, rl = filter_aa_records([bytes(s) for s in seqs])
-    scores = db.search_packed(aa, rs, rl)
+    scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if score == "forward" else db.search_packed(aa, rs, rl)
     rec, _ = db.best_hits(scores, np.array(goff, np.uint64), cutoff)
     genomes = []
     for g in range(len(goff) - 1):

@@ -1,6 +1,7 @@
 // gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
-// device, and the best record per genome and profile. Integers only from the file's digits to the raw score; doubles appear in gs_hmm_bits /
-// gs_hmm_evalue and in the cutoffs and STATS fields that are only reported.
+// device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, and the best record per genome and profile. Integers only
+// from the file's digits to the raw score; doubles appear in gs_hmm_bits / gs_hmm_evalue / gs_hmm_forward_evalue, in the table of lse (rounded to
+// integers once, on the host), in the Viterbi floor and in the cutoffs and STATS fields that are only reported.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -11,7 +12,10 @@
 namespace gs {
 
 // ---- profile files ----------------------------------------------------------------------------------------------------------------------------
-struct HmmModel { gs_hmm_info info; std::vector<int32_t> tab; };        // tab: [27][M + 1] as gs_hmm_parse_mem documents it
+struct HmmModel {
+    gs_hmm_info info; std::vector<int32_t> tab;                         // tab: [27][M + 1] as gs_hmm_parse_mem documents it
+    double stats[6] = {}; uint32_t has_stats = 0;                       // as gs_hmm_parse_stats_mem documents them
+};
 
 // one number of a file -> units (SPEC 13 "Units")
 static bool hmm_file_units(const std::string &t, int32_t *out)
@@ -89,6 +93,10 @@ static int hmm_parse_all(const char *text, size_t n, std::vector<HmmModel> &out)
         for (;;) {
             HMM_LINE("header");
             if (f[0] == "HMM") break;
+            if (f[0] == "STATS" && f.size() > 4 && f[1] == "LOCAL") {
+                const int w = f[2] == "MSV" ? 0 : (f[2] == "VITERBI" ? 1 : (f[2] == "FORWARD" ? 2 : -1));
+                if (w >= 0) { m.stats[2 * w] = strtod(f[3].c_str(), nullptr); m.stats[2 * w + 1] = strtod(f[4].c_str(), nullptr); m.has_stats |= 1u << w; }
+            }
             if (f[0] == "NAME" && f.size() > 1) { snprintf(m.info.name, sizeof m.info.name, "%s", f[1].c_str()); has_name = true; }
             else if (f[0] == "ACC" && f.size() > 1) snprintf(m.info.acc, sizeof m.info.acc, "%s", f[1].c_str());
             else if (f[0] == "LENG" && f.size() > 1) {
@@ -290,6 +298,195 @@ __global__ __launch_bounds__(256) void k_hmm_best(const int32_t *__restrict__ sc
     best_score[i] = bs;
 }
 
+// ---- Forward (SPEC 13.1) ------------------------------------------------------------------------------------------------------------------------
+// T of SPEC 13.1 on the host: no entry lies closer than 3.5e-6 to a rounding boundary, so the f64 log2 of any libm gives the same integers
+static uint16_t hmm_lse_entry(uint32_t j) { return (uint16_t)floor(1024.0 * log2(1.0 + exp2(-2.0 * (double)j / 1024.0)) + 0.5); }
+// in LDS T[0 .. 5902] is followed by the 0 that every larger difference reads, so the look-up needs no branch
+enum { HMM_LSE_LDS_N = GS_HMM_LSE_N + 1, HMM_LSE_LDS_BYTES = 2 * HMM_LSE_LDS_N };
+static_assert((size_t)HMM_ROWS_DEV * GS_HMM_MAX_M * 4 + HMM_LSE_LDS_BYTES <= 160 * 1024, "the largest table and T behind it fit the LDS of a CU");
+static_assert(((size_t)HMM_ROWS_DEV * 64 * 4) % 4 == 0, "T starts on a word");
+
+// lse(a, b) of SPEC 13.1. The difference is taken on unsigned words: hi - lo can pass 2^31 (a cell near the top of the range beside one near NEG)
+__device__ __forceinline__ int32_t hmm_lse(int32_t a, int32_t b, const uint16_t *__restrict__ T)
+{
+    const int32_t hi = max(a, b), lo = min(a, b);
+    const uint32_t j = min(((uint32_t)hi - (uint32_t)lo + 1u) >> 1, (uint32_t)GS_HMM_LSE_N);
+    return hi + (int32_t)T[j];
+}
+// lse over the wavefront in every lane, as the balanced tree of SPEC 13.1 (neighbours, pairs of pairs, ...): the step pattern of hmm_wave_max. After the
+// two quad steps the four lanes of a quad hold one value, so the mirrors hand a lane the value of the other quad / the other half row; that is the
+// tree because lse is symmetric - a lane and its partner compute lse(x, y) and lse(y, x).
+__device__ __forceinline__ int hmm_wave_lse(int x, const uint16_t *__restrict__ T)
+{
+    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false), T);        // quad_perm [1,0,3,2]
+    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false), T);        // quad_perm [2,3,0,1]
+    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false), T);       // row_half_mirror
+    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false), T);       // row_mirror
+    const int a = __builtin_amdgcn_readlane(x, 0), b = __builtin_amdgcn_readlane(x, 16), c = __builtin_amdgcn_readlane(x, 32),
+              d = __builtin_amdgcn_readlane(x, 48);
+    return hmm_lse(hmm_lse(a, b, T), hmm_lse(c, d, T), T);
+}
+
+// Per profile the records whose Viterbi score reaches the profile's floor, in the order of `order` (longest first), and their number. One workgroup per
+// profile walks `order` 256 at a time: a ballot per wavefront, the wavefronts' counts through LDS, a running base. No atomics: the list is the same
+// every time. sel: [n_prof][n_rec], only the first cnt[p] words of a row are written (and read). floor = nullptr: every pair that has a score.
+enum { HMM_SEL_BLOCK = 256 };
+__global__ __launch_bounds__(HMM_SEL_BLOCK) void k_hmm_select(const int32_t *__restrict__ vit, const uint32_t *__restrict__ order, uint32_t n_rec, uint32_t n_prof,
+                                                              const int32_t *__restrict__ floor, uint32_t *__restrict__ sel, uint32_t *__restrict__ cnt)
+{
+    __shared__ uint32_t wsum[HMM_SEL_BLOCK / 64];
+    const uint32_t p = blockIdx.x;
+    const int32_t fl = floor ? floor[p] : INT32_MIN + 1;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    uint32_t *out = sel + (uint64_t)p * n_rec;
+    uint32_t base = 0;
+    for (uint64_t j0 = 0; j0 < n_rec; j0 += HMM_SEL_BLOCK) {
+        const uint64_t j = j0 + threadIdx.x;
+        uint32_t r = 0;
+        bool pass = false;
+        if (j < n_rec) {
+            r = order[j];
+            const int32_t v = vit[(uint64_t)r * n_prof + p];
+            pass = v != GS_HMM_NO_SCORE && v >= fl;
+        }
+        const uint64_t bal = __ballot(pass);
+        if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = base, total = 0;
+        for (int w = 0; w < HMM_SEL_BLOCK / 64; w++) { if (w < wave) before += wsum[w]; total += wsum[w]; }
+        if (pass) out[before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = r;       // below base + total <= n_rec
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) cnt[p] = base;
+}
+
+__global__ __launch_bounds__(256) void k_hmm_fill(int32_t *__restrict__ out, uint64_t n, int32_t v)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = v;
+}
+
+// The geometry of k_hmm_viterbi, the arithmetic of SPEC 13.1: every max that joins alternatives is hmm_lse, a gather from T, which sits in LDS behind
+// the profile's table. A wavefront takes the records sel[p][j] of its profile's list, j = its number, its number + the waves of the grid's row, ...;
+// the loop is bounded by cnt[p] <= n_rec, and a workgroup with no record of its own returns before it loads anything.
+//   lse is not associative, so the order below IS the score: D inside a lane from NEG, six scan steps in which a lane below 2^s keeps its b (with max
+//   it would get its own b back; lse(b, b + a) is more than b), then c_in from the lane below; E folds M and D of a lane's nodes in node order and joins
+//   the lanes through hmm_wave_lse.
+//   From Q = 12 the transition rows are read from LDS in every row: beside 3 Q states, Q give values and the lse temporaries they do not fit.
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_forward(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const uint32_t *__restrict__ plist,
+                                                           const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start,
+                                                           const uint64_t *__restrict__ rec_len, const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sel_cnt,
+                                                           uint32_t n_rec, uint32_t n_prof, int32_t *__restrict__ score)
+{
+    extern __shared__ int32_t hmm_lds[];
+    constexpr int MP = 64 * Q;
+    const uint32_t p = plist[blockIdx.y];
+    const uint32_t cnt = min(sel_cnt[p], n_rec);
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= cnt) return;
+    const HmmDesc d = desc[p];
+    uint16_t *Tw = (uint16_t *)(hmm_lds + HMM_ROWS_DEV * MP);
+    for (int i = (int)threadIdx.x; i < HMM_ROWS_DEV * MP; i += HMM_BLOCK) hmm_lds[i] = tables[d.off + i];
+    for (int i = (int)threadIdx.x; i < HMM_LSE_LDS_N; i += HMM_BLOCK) Tw[i] = lse_tab[i];
+    __syncthreads();
+    const uint16_t *T = Tw;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int base = lane * Q;
+    const int nvalid = min(max((int)d.M - base, 0), Q);
+    const int32_t *tMM = hmm_lds + HMM_ROW_MM * MP + base, *tMI = hmm_lds + HMM_ROW_MI * MP + base, *tMD = hmm_lds + HMM_ROW_MD * MP + base,
+                  *tIM = hmm_lds + HMM_ROW_IM * MP + base, *tII = hmm_lds + HMM_ROW_II * MP + base, *tDM = hmm_lds + HMM_ROW_DM * MP + base,
+                  *tDD = hmm_lds + HMM_ROW_DD * MP + base, *PDD = hmm_lds + HMM_ROW_PDD * MP + base;
+    int32_t a_step[6];                                      // A_l(s) of SPEC 13.1 in the lanes l >= 2^s, the only ones that use it
+    {
+        int32_t a = PDD[Q - 1] + tDD[Q - 1];
+        for (int s = 0; s < 6; s++) {
+            a_step[s] = a;
+            const int32_t up = __shfl_up(a, 1 << s);
+            if (lane >= (1 << s)) a += up;
+        }
+    }
+    const uint32_t *list = sel + (uint64_t)p * n_rec;
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)wave; j < cnt; j += gridDim.x * HMM_WAVES) {
+        const uint32_t r = list[j];
+        const uint32_t L = (uint32_t)rec_len[r];
+        const uint8_t *x = aa + rec_start[r];
+        int32_t *out = score + (uint64_t)r * n_prof + p;
+        if (L == 0) { if (lane == 0) *out = GS_HMM_NO_SCORE; continue; }
+        const HmmSpecials sp = hmm_specials(L);
+        int32_t Mv[Q], Iv[Q], Dv[Q];
+#pragma unroll
+        for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
+        int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
+        bool bad = false;
+        int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
+        for (uint32_t i0 = 0; i0 < L; i0 += 64) {
+            const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;
+            bad |= cur < 0;
+            const int res = max(cur, 0);
+            const int cnt_i = (int)min(64u, L - i0);
+            for (int t = 0; t < cnt_i; t++) {
+                if (Q >= 12) asm volatile("" ::: "memory");
+                const int32_t *ms = hmm_lds + __builtin_amdgcn_readlane(res, t) * MP + base;
+                const int32_t entry = B + d.tbm;
+                int32_t give[Q];
+#pragma unroll
+                for (int q = 0; q < Q; q++) give[q] = hmm_lse(hmm_lse(Mv[q] + tMM[q], Iv[q] + tIM[q], T), Dv[q] + tDM[q], T);
+                int32_t up = __shfl_up(give[Q - 1], 1);
+                if (lane == 0) up = GS_HMM_NEG;
+#pragma unroll
+                for (int q = 0; q < Q; q++) Iv[q] = max(hmm_lse(Mv[q] + tMI[q], Iv[q] + tII[q], T), GS_HMM_NEG);
+#pragma unroll
+                for (int q = 0; q < Q; q++) Mv[q] = max(ms[q] + hmm_lse(q ? give[q - 1] : up, entry, T), GS_HMM_NEG);
+                int32_t dl = GS_HMM_NEG;
+                Dv[0] = dl;
+#pragma unroll
+                for (int q = 1; q < Q; q++) { dl = max(hmm_lse(dl + tDD[q - 1], Mv[q - 1] + tMD[q - 1], T), GS_HMM_NEG); Dv[q] = dl; }
+                int32_t b = max(hmm_lse(dl + tDD[Q - 1], Mv[Q - 1] + tMD[Q - 1], T), GS_HMM_NEG);
+#pragma unroll
+                for (int s = 0; s < 6; s++) {
+                    const int32_t nb = max(hmm_lse(b, __shfl_up(b, 1 << s) + a_step[s], T), GS_HMM_NEG);
+                    b = lane >= (1 << s) ? nb : b;
+                }
+                int32_t c_in = __shfl_up(b, 1);
+                if (lane == 0) c_in = GS_HMM_NEG;
+                int32_t e = GS_HMM_NEG;
+#pragma unroll
+                for (int q = 0; q < Q; q++) {
+                    Dv[q] = max(hmm_lse(Dv[q], c_in + PDD[q], T), GS_HMM_NEG);
+                    const int32_t e2 = hmm_lse(hmm_lse(e, Mv[q], T), Dv[q], T);
+                    e = q < nvalid ? e2 : e;
+                }
+                const int32_t E = hmm_wave_lse(e, T);
+                N += sp.tloop;
+                J = max(hmm_lse(J + sp.tloop, E + GS_HMM_TEJ, T), GS_HMM_NEG);
+                C = max(hmm_lse(C + sp.tloop, E + GS_HMM_TEJ, T), GS_HMM_NEG);
+                B = hmm_lse(N, J, T) + sp.tmove;
+            }
+            cur = nxt;
+        }
+        const bool any_bad = __any(bad);
+        if (lane == 0) *out = any_bad ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
+    }
+}
+
+typedef void (*hmm_fwd_kernel_t)(const int32_t *, const HmmDesc *, const uint32_t *, const uint16_t *, const uint8_t *, const uint64_t *, const uint64_t *,
+                                 const uint32_t *, const uint32_t *, uint32_t, uint32_t, int32_t *);
+static hmm_fwd_kernel_t hmm_fwd_kernel(int cls)
+{
+    switch (cls) {
+    case 0: return k_hmm_forward<1>;
+    case 1: return k_hmm_forward<2>;
+    case 2: return k_hmm_forward<3>;
+    case 3: return k_hmm_forward<4>;
+    case 4: return k_hmm_forward<6>;
+    case 5: return k_hmm_forward<8>;
+    case 6: return k_hmm_forward<12>;
+    case 7: return k_hmm_forward<16>;
+    default: return k_hmm_forward<20>;
+    }
+}
+
 typedef void (*hmm_kernel_t)(const int32_t *, const HmmDesc *, const uint32_t *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint32_t,
                              uint32_t, int32_t *);
 static hmm_kernel_t hmm_kernel(int cls)
@@ -321,8 +518,8 @@ struct gs_hmm_db {
     std::vector<uint32_t> plist;                    // profile numbers, class by class
     uint32_t class_start[gs::HMM_CLASSES + 1] = {};
     bool all_ga = true;
-    bool lds_set[gs::HMM_CLASSES] = {};
-    gs::DevBuf d_tables, d_desc, d_plist, d_ga;
+    bool lds_set[gs::HMM_CLASSES] = {}, lds_set_fwd[gs::HMM_CLASSES] = {};
+    gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse;
 };
 
 namespace gs {
@@ -357,11 +554,15 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
     db->class_start[HMM_CLASSES] = (uint32_t)db->plist.size();
     GS_CTX_LOCK(c);
     int rc;
-    if ((rc = db->d_tables.alloc(4 * words.size())) || (rc = db->d_desc.alloc(sizeof(HmmDesc) * np)) || (rc = db->d_plist.alloc(4 * np)) || (rc = db->d_ga.alloc(4 * np))) return rc;
+    if ((rc = db->d_tables.alloc(4 * words.size())) || (rc = db->d_desc.alloc(sizeof(HmmDesc) * np)) || (rc = db->d_plist.alloc(4 * np)) || (rc = db->d_ga.alloc(4 * np)) ||
+        (rc = db->d_lse.alloc(HMM_LSE_LDS_BYTES))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(db->d_tables.p, words.data(), 4 * words.size(), hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_desc.p, db->desc.data(), sizeof(HmmDesc) * np, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_plist.p, db->plist.data(), 4 * np, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_ga.p, ga.data(), 4 * np, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint16_t> lse(HMM_LSE_LDS_N, 0);
+    for (uint32_t j = 0; j < GS_HMM_LSE_N; j++) lse[j] = hmm_lse_entry(j);
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_lse.p, lse.data(), HMM_LSE_LDS_BYTES, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(stream_wait(c));           // the host vectors go out of scope
     *out = db.release();
     return GS_OK;
@@ -399,12 +600,54 @@ static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, cons
     GS_HIP_CHECK(stream_wait(c));           // `order` is read by the copy until here
     return GS_OK;
 }
-static int hmm_check_lens(const uint64_t *lens, uint64_t n_rec)
+static int hmm_check_lens(const uint64_t *lens, uint64_t n_rec, uint32_t max_l = GS_HMM_MAX_L)
 {
     GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
     for (uint64_t r = 0; r < n_rec; r++)
-        GS_REQUIRE(lens[r] <= GS_HMM_MAX_L, GS_ERR_UNSUPPORTED, "hmm: record %llu has %llu residues, more than %u", (unsigned long long)r, (unsigned long long)lens[r],
-                   GS_HMM_MAX_L);
+        GS_REQUIRE(lens[r] <= max_l, GS_ERR_UNSUPPORTED, "hmm: record %llu has %llu residues, more than %u", (unsigned long long)r, (unsigned long long)lens[r], max_l);
+    return GS_OK;
+}
+
+// Viterbi into vit_dev, then Forward into fwd_dev for the pairs at or above floor_dev (nullptr: every pair that has a Viterbi score), GS_HMM_NO_SCORE
+// for the rest. Queued on c's stream; the lists live in their slots until the caller's scope ends.
+static int hmm_forward_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
+                            const int32_t *floor_dev, int32_t *vit_dev, int32_t *fwd_dev, PoolBuf &d_order, PoolBuf &d_sel, PoolBuf &d_cnt)
+{
+    const uint32_t np = (uint32_t)db->models.size();
+    int rc;
+    if ((rc = hmm_search_impl(c, db, aa_dev, rs_dev, rl_dev, lens, n_rec, vit_dev, d_order))) return rc;
+    if ((rc = d_sel.alloc(4 * n_rec * np)) || (rc = d_cnt.alloc(4 * (size_t)np))) return rc;
+    const uint64_t n = n_rec * np;
+    GS_REQUIRE(n < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many (record, profile) pairs");
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_fill<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(fwd_dev, n, GS_HMM_NO_SCORE);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_select<<<np, HMM_SEL_BLOCK, 0, c->stream>>>(vit_dev, d_order.as<uint32_t>(), (uint32_t)n_rec, np, floor_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>());
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
+    for (int cls = 0; cls < HMM_CLASSES; cls++) {
+        const uint32_t n_in = db->class_start[cls + 1] - db->class_start[cls];
+        if (!n_in) continue;
+        const size_t lds = (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + HMM_LSE_LDS_BYTES;
+        hmm_fwd_kernel_t k = hmm_fwd_kernel(cls);
+        if (!db->lds_set_fwd[cls]) {
+            if (lds > 64 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            db->lds_set_fwd[cls] = true;
+        }
+        for (uint32_t y0 = 0; y0 < n_in; y0 += 65535) {
+            ProfScope ps(c, FAM_SEARCH);
+            k<<<dim3(wg, std::min<uint32_t>(n_in - y0, 65535)), HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(),
+                                                                                           db->d_plist.as<uint32_t>() + db->class_start[cls] + y0, db->d_lse.as<uint16_t>(),
+                                                                                           aa_dev, rs_dev, rl_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec,
+                                                                                           np, fwd_dev);
+            GS_HIP_CHECK(hipGetLastError());
+        }
+    }
     return GS_OK;
 }
 
@@ -578,6 +821,97 @@ int gs_hmm_best_hits_dev(gs_ctx *c, gs_hmm_db *db, const int32_t *score_dev, uin
     GS_HIP_CHECK(stream_wait(c));
     return GS_OK;
 }
+
+int gs_hmm_logsum_table(uint16_t *out, uint64_t cap)
+{
+    GS_REQUIRE(out, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(cap >= GS_HMM_LSE_N, GS_ERR_INVALID, "hmm: the table has %u entries, cap = %llu", GS_HMM_LSE_N, (unsigned long long)cap);
+    for (uint32_t j = 0; j < GS_HMM_LSE_N; j++) out[j] = gs::hmm_lse_entry(j);
+    return GS_OK;
+}
+
+int gs_hmm_parse_stats_mem(const void *text, uint64_t n_bytes, uint32_t model, double out[6], uint32_t *has_out)
+{
+    using namespace gs;
+    GS_REQUIRE((text || n_bytes == 0) && out && has_out, GS_ERR_INVALID, "null argument");
+    std::vector<HmmModel> ms;
+    int rc = hmm_parse_all((const char *)text, (size_t)n_bytes, ms);
+    if (rc) return rc;
+    GS_REQUIRE(model < ms.size(), GS_ERR_INVALID, "hmm: model %u of %zu", model, ms.size());
+    for (int i = 0; i < 6; i++) out[i] = ms[model].stats[i];
+    *has_out = ms[model].has_stats;
+    return GS_OK;
+}
+
+int gs_hmm_viterbi_floor(double mu, double lambda, double p, int32_t *floor_out)
+{
+    GS_REQUIRE(floor_out, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(lambda > 0 && p > 0 && p < 1 && mu == mu, GS_ERR_INVALID, "hmm: the floor needs lambda > 0 and 0 < P < 1 (lambda = %g, P = %g)", lambda, p);
+    const double units = ::floor((mu - ::log(-::log1p(-p)) / lambda) * 1024.0 + 0.5);
+    *floor_out = units <= (double)(INT32_MIN + 1) ? INT32_MIN + 1 : (units >= (double)INT32_MAX ? INT32_MAX : (int32_t)units);
+    return GS_OK;
+}
+
+int gs_hmm_search_forward_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                              const int32_t *vit_floor_dev, int32_t *vit_out_dev, int32_t *fwd_out_dev)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_rec == 0) return GS_OK;
+    GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && fwd_out_dev, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
+    GS_CTX_LOCK(c);
+    std::vector<uint64_t> lens(n_rec);
+    GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rec_len_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    int rc = hmm_check_lens(lens.data(), n_rec, GS_HMM_FWD_MAX_L);
+    if (rc) return rc;
+    PoolBuf d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT), d_vit(c, SL_HMM_VIT);
+    if (!vit_out_dev) {
+        if ((rc = d_vit.alloc(4 * n_rec * db->models.size()))) return rc;
+        vit_out_dev = d_vit.as<int32_t>();
+    }
+    if ((rc = hmm_forward_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, vit_floor_dev, vit_out_dev, fwd_out_dev, d_order, d_sel, d_cnt))) return rc;
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+int gs_hmm_search_forward(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const int32_t *vit_floor,
+                          int32_t *vit_out, int32_t *fwd_out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_rec == 0) return GS_OK;
+    GS_REQUIRE(rec_start && rec_len && fwd_out, GS_ERR_INVALID, "null argument");
+    int rc = hmm_check_lens(rec_len, n_rec, GS_HMM_FWD_MAX_L);
+    if (rc) return rc;
+    uint64_t n_bytes = 0;
+    for (uint64_t r = 0; r < n_rec; r++) if (rec_len[r]) n_bytes = std::max(n_bytes, rec_start[r] + rec_len[r]);
+    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
+    const uint64_t np = db->models.size();
+    GS_CTX_LOCK(c);
+    PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_fwd(c, SL_HMMB_FWD), d_floor(c, SL_HMMB_FLOOR),
+        d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT);
+    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec)) || (rc = d_score.alloc(4 * n_rec * np)) ||
+        (rc = d_fwd.alloc(4 * n_rec * np)))
+        return rc;
+    if (vit_floor) {
+        if ((rc = d_floor.alloc(4 * np))) return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(d_floor.p, vit_floor, 4 * np, hipMemcpyHostToDevice, c->stream));
+    }
+    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+    if ((rc = hmm_forward_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, vit_floor ? d_floor.as<int32_t>() : nullptr,
+                               d_score.as<int32_t>(), d_fwd.as<int32_t>(), d_order, d_sel, d_cnt)))
+        return rc;
+    if (vit_out) GS_HIP_CHECK(hipMemcpyAsync(vit_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+double gs_hmm_forward_evalue(double bits, double tau, double lambda, double Z) { return Z * (bits < tau ? 1.0 : ::exp(-lambda * (bits - tau))); }
 
 double gs_hmm_bits(int32_t raw) { return (double)raw / 1024.0; }
 double gs_hmm_evalue(double bits, double mu, double lambda, double Z) { return Z * -::expm1(-::exp(-lambda * (bits - mu))); }

@@ -73,6 +73,8 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     X(ANI_SEG_START) X(ANI_SEG_N) X(ANI_F) X(ANI_PRED) X(ANI_ROOT) X(ANI_BEST) X(ANI_NCHAIN) X(ANI_MATCHED) X(ANI_DIFF)                               \
     /* hmmsearch (gs_hmm.hip): the records of a call, longest first; staging of the host form */                                                       \
     X(HMM_ORDER) X(HMMB_AA) X(HMMB_REC_START) X(HMMB_REC_LEN) X(HMMB_SCORE)                                                                           \
+    /* hmmsearch, Forward: per profile the records at or above its Viterbi floor and their number, the Viterbi matrix nobody asked for, staging */    \
+    X(HMM_SEL) X(HMM_SEL_COUNT) X(HMM_VIT) X(HMMB_FWD) X(HMMB_FLOOR)                                                                                  \
     /* comm (gs_topk_merge_dev) */                                                                                                                    \
     X(COMM_ID_OFFSET)
 

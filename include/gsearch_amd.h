@@ -268,7 +268,8 @@ int gs_ani_estimate(const uint64_t *counts, const uint64_t *bases_q, const uint6
 
 /* ---------------------------------------------------------------------------------------------- */
 /* hmmsearch (`hmmsearch_rs -f proteome.faa -m profile.HMM`, the universal-gene level): the local multihit Viterbi score of every protein
- * against every profile of a set of HMMER3 profiles, and the best protein per genome and profile. Arithmetic: SPEC 13 - int32 in units of
+ * against every profile of a set of HMMER3 profiles, the Forward score of the pairs that pass a Viterbi floor (further down, SPEC 13.1), and
+ * the best protein per genome and profile. Arithmetic: SPEC 13 - int32 in units of
  * 2^-10 bit, no floating point in the scored path. A record is residues as gs_filter_aa leaves them (the 20 letters, either case). */
 #define GS_HMM_MAX_M 1280u            /* nodes of a profile at most (20 per lane of a wavefront); the reference's longest has 1238 */
 #define GS_HMM_MAX_L (1u << 18)       /* residues of a record at most: L * 6608 + 151000 < 2^31 (SPEC 13) */
@@ -318,6 +319,30 @@ int gs_hmm_best_hits_dev(gs_ctx *ctx, gs_hmm_db *db, const int32_t *score_dev, u
 /* host only, double: raw / 1024, and E = n_targets * P with P = -expm1(-exp(-lambda (bits - mu))) (the Gumbel tail of STATS LOCAL VITERBI) */
 double gs_hmm_bits(int32_t raw);
 double gs_hmm_evalue(double bits, double mu, double lambda, double n_targets);
+
+/* Forward scores (SPEC 13.1): the same model, tables and units, every max that joins alternatives replaced by lse(a, b) = hi + T[min((hi - lo + 1) >> 1,
+ * 5903)] in a fixed blocked order, so fwd >= vit holds on the integers. HMMER's own order: the Viterbi score of every pair first, Forward only for the
+ * pairs at or above a per-profile Viterbi floor. The files' GA / TC / NC cutoffs were gathered on this score. */
+#define GS_HMM_FWD_MAX_L 65536u       /* residues of a record at most for Forward: L * 21353 < 2^31 with 7.4e8 to spare (SPEC 13.1) */
+#define GS_HMM_LSE_N 5903u            /* entries of T: T[j] = floor(1024 log2(1 + 2^(-2 j / 1024)) + 1/2), T[0] = 1024, T[5902] = 1; beyond: 0 */
+/* host only: out[0 .. GS_HMM_LSE_N) = T; cap < GS_HMM_LSE_N: GS_ERR_INVALID */
+int gs_hmm_logsum_table(uint16_t *out, uint64_t cap);
+/* host only: out = {msv mu, lambda, viterbi mu, lambda, forward tau, lambda} of the STATS LOCAL lines of model number `model` of a text (0 where a
+ * line is missing); *has_out bit 0 / 1 / 2 = the MSV / VITERBI / FORWARD line was there. Errors as gs_hmm_parse_mem. */
+int gs_hmm_parse_stats_mem(const void *text, uint64_t n_bytes, uint32_t model, double out[6], uint32_t *has_out);
+/* host only, SPEC 13.1: the Viterbi score in units whose Gumbel tail mass is p, floor((mu - ln(-ln(1 - p)) / lambda) * 1024 + 1/2), kept inside
+ * [INT32_MIN + 1, INT32_MAX]; lambda <= 0 or p outside (0, 1): GS_ERR_INVALID */
+int gs_hmm_viterbi_floor(double mu, double lambda, double p, int32_t *floor_out);
+/* vit_out[r * n_prof + p] = what gs_hmm_search writes (optional); fwd_out[r * n_prof + p] = the Forward raw score of the pairs with vit != GS_HMM_NO_SCORE
+ * and vit >= vit_floor[p], GS_HMM_NO_SCORE for the others. vit_floor: n_prof words, NULL = every pair that has a Viterbi score. Device form: all arrays
+ * device memory; the lengths are read back once. A record longer than GS_HMM_FWD_MAX_L, or 2^32 records or more: GS_ERR_UNSUPPORTED, nothing written to
+ * either output; a set of another context: GS_ERR_INVALID. */
+int gs_hmm_search_forward_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                              const int32_t *vit_floor_dev, int32_t *vit_out_dev, int32_t *fwd_out_dev);
+int gs_hmm_search_forward(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                          const int32_t *vit_floor, int32_t *vit_out, int32_t *fwd_out);
+/* host only, double: E = n_targets * P with P = 1 for bits < tau, exp(-lambda (bits - tau)) otherwise (the exponential tail of STATS LOCAL FORWARD) */
+double gs_hmm_forward_evalue(double bits, double tau, double lambda, double n_targets);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */

@@ -234,8 +234,8 @@ inline std::vector<float> ani_estimate(const std::vector<uint64_t> &counts, cons
     return out;
 }
 
-// hmmsearch (`hmmsearch_rs -f proteome.faa -m profile.HMM`; SPEC 13): a set of HMMER3 profiles on the device, the raw Viterbi score (units of 2^-10 bit)
-// of every record against every profile, and the best record per genome and profile
+// hmmsearch (`hmmsearch_rs -f proteome.faa -m profile.HMM`; SPEC 13, 13.1): a set of HMMER3 profiles on the device, the raw Viterbi score (units of
+// 2^-10 bit) of every record against every profile, the Forward score of the pairs above a Viterbi floor, and the best record per genome and profile
 class HmmDb {
 public:
     HmmDb(Context &ctx, const std::vector<std::string> &paths) : ctx_(&ctx)
@@ -260,6 +260,24 @@ public:
         check(gs_hmm_search(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), out.data()));
         return out;
     }
+    // SPEC 13.1: the Viterbi matrix (as search() gives it) and the Forward raw score of the pairs whose Viterbi score reaches vit_floor[p] (units; an
+    // empty vector: every pair that has a Viterbi score), GS_HMM_NO_SCORE for the others
+    std::pair<std::vector<int32_t>, std::vector<int32_t>> search_forward(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len,
+                                                                          const std::vector<int32_t> &vit_floor = {}) const
+    {
+        std::vector<int32_t> vit(rec_start.size() * info_.size()), fwd(vit.size());
+        check(gs_hmm_search_forward(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), vit_floor.empty() ? nullptr : vit_floor.data(), vit.data(),
+                                    fwd.data()));
+        return {std::move(vit), std::move(fwd)};
+    }
+    // the floor of profile p for a Viterbi P-value of filter_p (HMMER's F2 = 1e-3): INT32_MIN + 1 without STATS LOCAL VITERBI
+    int32_t viterbi_floor(size_t profile, double filter_p = 1e-3) const
+    {
+        int32_t f = INT32_MIN + 1;
+        if (info_[profile].flags & GS_HMM_HAS_STATS) check(gs_hmm_viterbi_floor(info_[profile].mu, info_[profile].lambda, filter_p, &f));
+        return f;
+    }
+    static double forward_evalue(double bits, double tau, double lambda, double n_targets) { return gs_hmm_forward_evalue(bits, tau, lambda, n_targets); }
     static double bits(int32_t raw) { return gs_hmm_bits(raw); }
     double evalue(size_t profile, int32_t raw, double n_targets) const
     {

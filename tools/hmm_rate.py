@@ -7,7 +7,13 @@ composition) against 120 synthetic profiles with the node counts of the bacteria
   best     seconds of gs_hmm_best_hits_dev over the score matrix, the proteome as one genome
   check    `check` sampled (protein, profile) pairs compared with the numpy restatement (tests/pyref_hmm.py): the expected difference is 0
 
-usage: hmm_rate.py [--n 4000] [--repeat 3] [--check 8] [--log profiles/hmm_rate.log]"""
+--forward (SPEC 13.1), on the same proteome and profile set:
+  forward_all   cells/s of the Forward launches alone with every pair selected: gs_hmm_search_forward_dev without a floor, less the Viterbi time above
+  filtered      the pipeline at the default floors (P = 1e-3): the share of the pairs that reach their profile's floor, and the seconds of selection
+                plus Forward (the call less the Viterbi time) beside the Viterbi seconds
+  check         `check` sampled pairs compared with the restatement (tests/pyref_hmm_forward.py): the expected difference is 0
+
+usage: hmm_rate.py [--forward] [--n 4000] [--repeat 3] [--check 8] [--log profiles/hmm_rate.log | profiles/hmm_forward_rate.log]"""
 import argparse
 import json
 import os
@@ -27,8 +33,11 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--check", type=int, default=8)
     ap.add_argument("--seed", type=int, default=13)
-    ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "hmm_rate.log"))
+    ap.add_argument("--forward", action="store_true")
+    ap.add_argument("--log", default=None)
     a = ap.parse_args()
+    if a.log is None:
+        a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else "hmm_rate.log")
     import gsearch_amd as G
     import pyref_hmm as R
     rng = np.random.default_rng(a.seed)
@@ -73,6 +82,8 @@ def main():
         r, p = int(rng.integers(a.n)), int(rng.integers(len(db)))
         diff += int(scores[r, p]) != R.viterbi(R.parse_hmm(texts[p])[0]["tables"], recs[r])
     res["check_pairs"], res["check_differences"] = a.check, diff
+    if a.forward:
+        forward_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng)
     for p in ptrs + [d_score, d_rec, d_best]:
         ctx.free(p)
     db.close()
@@ -82,6 +93,47 @@ def main():
         os.makedirs(os.path.dirname(a.log), exist_ok=True)
         with open(a.log, "a") as f:
             f.write(line + "\n")
+
+
+def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng):
+    import pyref_hmm as R
+    import pyref_hmm_forward as F
+    d_fwd = ctx.alloc(4 * a.n * len(db))
+    floor = db.viterbi_floor(1e-3)
+    d_floor = ctx.alloc(floor.nbytes)
+    ctx.upload(d_floor, floor)
+    times = {}
+    for name, fl in (("all", None), ("filtered", d_floor)):
+        best = float("inf")
+        for run in range(a.repeat + 1):
+            ctx.sync()
+            t = time.perf_counter()
+            db.search_forward_dev(ptrs[0], ptrs[1], ptrs[2], a.n, fl, d_vit, d_fwd)
+            ctx.sync()
+            if run:
+                best = min(best, time.perf_counter() - t)
+        times[name] = best
+        if name == "all":
+            fwd_all = ctx.download(d_fwd, (a.n, len(db)), np.int32)
+    fwd = ctx.download(d_fwd, (a.n, len(db)), np.int32)
+    res["forward_all_call_s"] = times["all"]
+    res["forward_all_s"] = times["all"] - res["search_s"]
+    res["forward_cells_per_s"] = cells / res["forward_all_s"]
+    res["forward_over_viterbi"] = res["forward_all_s"] / res["search_s"]
+    res["filter_p"] = 1e-3
+    res["selected_share"] = float((fwd != R.NO_SCORE).mean())
+    res["filtered_call_s"] = times["filtered"]
+    res["select_plus_forward_s"] = times["filtered"] - res["search_s"]
+    sel = (vit != R.NO_SCORE) & (vit.astype(np.int64) >= floor[None, :])
+    res["selection_differences"] = int(((fwd != R.NO_SCORE) != sel).sum())
+    res["filtered_differs_from_all"] = int((fwd[sel] != fwd_all[sel]).sum())
+    diff = 0
+    for _ in range(a.check):
+        r, p = int(rng.integers(a.n)), int(rng.integers(len(db)))
+        diff += int(fwd_all[r, p]) != F.forward(R.parse_hmm(texts[p])[0]["tables"], recs[r])
+    res["forward_check_pairs"], res["forward_check_differences"] = a.check, diff
+    ctx.free(d_fwd)
+    ctx.free(d_floor)
 
 
 if __name__ == "__main__":
