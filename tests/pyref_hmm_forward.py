@@ -79,10 +79,12 @@ def _padded(tab):
     return t, G
 
 
-def forward_batch(tab, records):
-    """raw Forward score (units) of many records against one profile, in the blocked order of SPEC 13.1 -> int32 [n_rec]; a record of no residues:
-    NO_SCORE. Every record runs its own length model and takes no more steps once its last row is done: the records are walked longest first, so the
-    live ones are a prefix of the arrays."""
+def blocked_batch(tab, records, scan_steps=6, join=lse, cells=None):
+    """the blocked row step of SPEC 13.1 over many records against one profile -> int32 [n_rec]; a record of no residues: NO_SCORE. Every record runs
+    its own length model and takes no more steps once its last row is done: the records are walked longest first, so the live ones are a prefix of
+    the arrays. The defaults are the Forward score. join: what joins alternatives, lse or np.maximum (with np.maximum and all six scan steps this is
+    the Viterbi score of SPEC 13 in the device's order). scan_steps < 6: the lane scan cut off after that many steps - what a kernel computes whose
+    later steps do nothing; only to measure which expected scores travel through which step. cells: a dict that gets the largest M or C cell."""
     n, M = len(records), tab.shape[1] - 1
     Ls = np.array([len(r) for r in records], np.int64)
     out = np.full(n, NO_SCORE, np.int64)
@@ -109,46 +111,55 @@ def forward_batch(tab, records):
     Mv = np.full((nl, 64, G), NEG, np.int64); Iv = Mv.copy(); Dv = Mv.copy()
     Jall = np.full(nl, NEG, np.int64); Call = Jall.copy(); Ball = tmove.copy()
     tloop_all = tloop
+    top = -(1 << 62)
     for i in range(1, int(Lv.max()) + 1):
         nl = int(np.count_nonzero(Lv >= i))                                                   # the records still running: the first nl
         Mv, Iv, Dv = Mv[:nl], Iv[:nl], Dv[:nl]
         J, C, B, tloop = Jall[:nl], Call[:nl], Ball[:nl], tloop_all[:nl]
         negcol = np.full((nl, 1), NEG, np.int64)
         msc = msc_of[x[:nl, i - 1]]
-        give = lse(lse(Mv + tMM, Iv + tIM), Dv + tDM).reshape(nl, 64 * G)
+        give = join(join(Mv + tMM, Iv + tIM), Dv + tDM).reshape(nl, 64 * G)
         prev = np.concatenate([negcol, give[:, :-1]], axis=1).reshape(nl, 64, G)              # give[k - 1], give[0] = NEG
-        In = np.maximum(lse(Mv + tMI, Iv + tII), NEG)
-        Mn = np.maximum(msc + lse(prev, (B + tbm)[:, None, None]), NEG)
+        In = np.maximum(join(Mv + tMI, Iv + tII), NEG)
+        Mn = np.maximum(msc + join(prev, (B + tbm)[:, None, None]), NEG)
         Dn = np.empty_like(Mn)
         dl = np.full(nl * 64, NEG, np.int64).reshape(nl, 64)
         Dn[:, :, 0] = dl
         for q in range(1, G):
-            dl = np.maximum(lse(dl + tDD[:, q - 1], Mn[:, :, q - 1] + tMD[:, q - 1]), NEG)
+            dl = np.maximum(join(dl + tDD[:, q - 1], Mn[:, :, q - 1] + tMD[:, q - 1]), NEG)
             Dn[:, :, q] = dl
-        b = np.maximum(lse(dl + tDD[:, G - 1], Mn[:, :, G - 1] + tMD[:, G - 1]), NEG)
-        for s in range(6):
+        b = np.maximum(join(dl + tDD[:, G - 1], Mn[:, :, G - 1] + tMD[:, G - 1]), NEG)
+        for s in range(scan_steps):
             d = 1 << s
             nb = b.copy()
-            nb[:, d:] = np.maximum(lse(b[:, d:], b[:, :-d] + A[s][d:]), NEG)                  # groups below 2^s keep their b
+            nb[:, d:] = np.maximum(join(b[:, d:], b[:, :-d] + A[s][d:]), NEG)                  # groups below 2^s keep their b
             b = nb
         c_in = np.concatenate([negcol, b[:, :-1]], axis=1)
-        Dn = np.maximum(lse(Dn, c_in[:, :, None] + PDD), NEG)
+        Dn = np.maximum(join(Dn, c_in[:, :, None] + PDD), NEG)
         e = np.full((nl, 64), NEG, np.int64)
         for q in range(G):
-            e = np.where(valid[:, q], lse(lse(e, Mn[:, :, q]), Dn[:, :, q]), e)
+            e = np.where(valid[:, q], join(join(e, Mn[:, :, q]), Dn[:, :, q]), e)
         while e.shape[1] > 1:
-            e = lse(e[:, 0::2], e[:, 1::2])
+            e = join(e[:, 0::2], e[:, 1::2])
         E = e[:, 0]
-        Jn = np.maximum(lse(J + tloop, E + R.T_EJ), NEG)
-        Cn = np.maximum(lse(C + tloop, E + R.T_EC), NEG)
-        Bn = lse(i * tloop, Jn) + tmove[:nl]
+        Jn = np.maximum(join(J + tloop, E + R.T_EJ), NEG)
+        Cn = np.maximum(join(C + tloop, E + R.T_EC), NEG)
+        Bn = join(i * tloop, Jn) + tmove[:nl]
         Jall[:nl], Call[:nl], Ball[:nl] = Jn, Cn, Bn
         Mv, Iv, Dv = Mn, In, Dn
-        assert max(int(Mn.max()), int(Cn.max())) < (1 << 31) - (1 << 20)
+        top = max(top, int(Mn.max()), int(Cn.max()))
+        assert top < (1 << 31) - (1 << 20)
+    if cells is not None:
+        cells["max_cell"] = max(top, cells.get("max_cell", top))
     raw = Call + tmove - null
     assert (np.abs(raw) < (1 << 31)).all()
     out[live] = raw
     return out.astype(np.int32)
+
+
+def forward_batch(tab, records):
+    """raw Forward score (units) of many records against one profile, in the blocked order of SPEC 13.1 -> int32 [n_rec]"""
+    return blocked_batch(tab, records)
 
 
 def forward(tab, rec):

@@ -1,11 +1,12 @@
 """hmmsearch on the device (gs_hmm.hip) against the numpy restatement of SPEC 13 (tests/pyref_hmm.py). Every comparison is `==` on int32 (the
 table of hmmsearch(): on bytes). The expected scores are computed once per module.
 
-Shapes of the kernel these cases are chosen for: a lane holds Q = 1, 2, 3, 4, 6, 8, 12, 16 or 20 consecutive nodes (the smallest Q with 64 Q >= M; one
-launch per Q that occurs), so M = 63 / 64 / 65 and 128 / 129 sit on both sides of a class edge and 1238 is the largest class; a workgroup has 8
-wavefronts and a profile gets at most 64 workgroups, so beyond 512 records a wavefront takes several records in turn (3 000 records: five or six
-each); a wavefront reads 64 residues at a time, so lengths 63 / 64 / 65 sit on both sides of that edge. There is no other chunk of records or of
-profiles per launch."""
+What these cases cover: the interface, the real profiles, best hits and the tables that are written. A lane holds Q = 1, 2, 3, 4, 6, 8, 12, 16 or 20
+consecutive nodes (the smallest Q with 64 Q >= M; one launch per Q that occurs); the profiles here run in Q = 1, 2, 3 and 20 only, and their
+deletions are too dear to travel through the lane scan. Every class, both sides of every class edge, GS_HMM_MAX_M, the six steps of the scan, bytes
+that are no residue and the length limits are the subject of tests/test_gpu_hmm_classes.py. What is chosen here: a workgroup has 8 wavefronts and a
+profile gets at most 64 workgroups, so beyond 512 records a wavefront takes several records in turn (3 000 records: five or six each); a wavefront
+reads 64 residues at a time, so lengths 63 / 64 / 65 sit on both sides of that edge. There is no other chunk of records or of profiles per launch."""
 import gzip
 import os
 
