@@ -76,6 +76,7 @@ class HmmInfoC(C.Structure):
 HMM_MAX_M, HMM_MAX_L, HMM_NO_SCORE, HMM_NO_HIT, HMM_TABLE_ROWS = 1280, 1 << 18, -(1 << 31), 0xFFFFFFFF, 27
 HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
 HMM_FWD_MAX_L, HMM_LSE_N, HMM_FLOOR_ALL = 65536, 5903, -(1 << 31) + 1
+HMM_TRACE_MAX_L, HMM_DOM_WORDS = 65536, 8
 
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
@@ -166,6 +167,8 @@ SYMBOLS = {
     "gs_hmm_search_forward_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_hmm_search_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_hmm_forward_evalue": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double]),
+    "gs_hmm_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
+    "gs_hmm_trace_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     "gs_index_create": (_i, [_vp, C.POINTER(IndexParams), C.POINTER(_vp)]),
     "gs_index_destroy": (None, [_vp]),
     "gs_index_nb_point": (_u64, [_vp]),

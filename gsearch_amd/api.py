@@ -1045,6 +1045,44 @@ class HmmDb:
         """all device memory; vit_floor_dev None: every pair, vit_out_dev None: the Viterbi matrix is not wanted"""
         check(self.ctx.L.gs_hmm_search_forward_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), vit_floor_dev, vit_out_dev, fwd_out_dev))
 
+    def trace_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_dom=8, max_block_cells=0):
+        """SPEC 13.2: the domains of the Viterbi path of the pairs (pair_rec[j], pair_prof[j]), traced back on the device -> (int32 raw [n_pairs] as
+        search_packed() gives it, uint32 n_dom [n_pairs] the true number of domains, int32 dom [n_pairs, max_dom, 8]: i_from, i_to, k_from, k_to (1-based,
+        inclusive), seg, n_match, n_ins, n_del of the first max_dom domains in sequence order, zeros behind them). A pair whose record is HMM_NO_HIT, empty
+        or holds a byte that is no residue: HMM_NO_SCORE, 0 and zeros. max_block_cells bounds the cells whose back-pointers are alive at once (0: 2^27)"""
+        aa = np.ascontiguousarray(aa, dtype=np.uint8)
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        pr = np.ascontiguousarray(pair_rec, dtype=np.uint32).reshape(-1)
+        pp = np.ascontiguousarray(pair_prof, dtype=np.uint32).reshape(-1)
+        if len(pr) != len(pp):
+            raise ValueError("pair_rec and pair_prof: one entry per pair each")
+        raw, nd = np.zeros(len(pr), np.int32), np.zeros(len(pr), np.uint32)
+        dom = np.zeros((len(pr), int(max_dom), _lib.HMM_DOM_WORDS), np.int32)
+        check(self.ctx.L.gs_hmm_trace(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
+                                      _p(pr) if len(pr) else None, _p(pp) if len(pp) else None, len(pr), int(max_dom), int(max_block_cells),
+                                      _p(raw) if len(pr) else None, _p(nd) if len(pr) else None, _p(dom) if dom.size else None))
+        return raw, nd, dom
+
+    def trace(self, records, pairs, max_dom=8, max_block_cells=0):
+        """records as search() takes them; pairs: (record, profile) index pairs -> (raw, n_dom, dom) of trace_packed()"""
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        return self.trace_packed(*filter_aa_records([bytes(r) for r in records]), pairs[:, 0].astype(np.uint32), pairs[:, 1].astype(np.uint32), max_dom=max_dom,
+                                 max_block_cells=max_block_cells)
+
+    def trace_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, pair_rec_dev, pair_prof_dev, n_pairs, max_dom, raw_out_dev, n_dom_out_dev, dom_out_dev,
+                  max_block_cells=0):
+        """all device memory; the lengths and the pair list are read back once"""
+        check(self.ctx.L.gs_hmm_trace_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), pair_rec_dev, pair_prof_dev, int(n_pairs), int(max_dom),
+                                          int(max_block_cells), raw_out_dev, n_dom_out_dev, dom_out_dev))
+
+    def trace_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_block_cells=0):
+        """trace_packed() with room for every domain: traced again with the largest n_dom when 8 slots a pair do not hold them all"""
+        raw, nd, dom = self.trace_packed(aa, rec_start, rec_len, pair_rec, pair_prof, 8, max_block_cells)
+        if len(nd) and int(nd.max()) > dom.shape[1]:
+            raw, nd, dom = self.trace_packed(aa, rec_start, rec_len, pair_rec, pair_prof, int(nd.max()), max_block_cells)
+        return raw, nd, dom
+
     def thresholds(self, cutoff="ga"):
         """int32 [n_prof] in units: every profile's GA1, or the caller's bits for all (a number) or per profile (a sequence)"""
         if isinstance(cutoff, str):
@@ -1096,26 +1134,33 @@ def _as_hmm_db(hmm, ctx):
     return hmm if isinstance(hmm, HmmDb) else HmmDb(hmm, ctx)
 
 
-def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3):
+def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
     `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
     `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
     (record, profile) with raw >= 0, sorted by (profile, -raw, record); bits %.2f, evalue %.3E with Z = the number of records (`-` without STATS),
     pass_ga 1 / 0 (`-` without GA), acc `-` when the profile has none.
     score="forward" (SPEC 13.1): the scores are the Forward matrix behind the Viterbi floor of filter_p (None: every pair) - bits and pass_ga of the
-    Forward raw, evalue from STATS LOCAL FORWARD (`-` without the line), rows for the pairs that have a Forward raw >= 0."""
+    Forward raw, evalue from STATS LOCAL FORWARD (`-` without the line), rows for the pairs that have a Forward raw >= 0.
+    domains (a path; SPEC 13.2): the pairs the score table lists are traced back on the device and a second table is written there - a header line, then
+    `target profile acc dom n_dom i_from i_to k_from k_to M seg_bits n_match n_ins n_del` for every domain, seg_bits %.2f of seg / 1024, sorted like the
+    score table and then by dom (from 1). With score="forward" the pairs are the Forward table's and the path is still the Viterbi path. The return value is
+    then (ids, scores, table bytes, domain table bytes)."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     db = _as_hmm_db(hmm, ctx)
     ids, seqs = _faa_records(faa)
     fwd = score == "forward"
-    scores = db.search_forward(seqs, filter_p=filter_p)[1] if fwd else db.search(seqs)
+    aa, rs, rl = filter_aa_records([bytes(q) for q in seqs])
+    scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
     Z = len(ids)
     out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga\n"]
+    listed = []                                                          # the (record, profile) pairs of the table, in its order
     for p, inf in enumerate(db.info):
         col = scores[:, p].astype(np.int64)
         keep = np.flatnonzero((col != _lib.HMM_NO_SCORE) & (col >= 0))
         for r in keep[np.lexsort((keep, -col[keep]))]:
+            listed.append((int(r), p))
             raw = int(col[r])
             b = hmm_bits(raw)
             if fwd:
@@ -1128,16 +1173,33 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3):
     if output is not None:
         with open(output, "wb") as f:
             f.write(table)
-    return ids, scores, table
+    if domains is None:
+        return ids, scores, table
+    pr, pp = np.array([r for r, _ in listed], np.uint32), np.array([p for _, p in listed], np.uint32)
+    _, nd, dom = db.trace_all(aa, rs, rl, pr, pp)
+    out = [b"target\tprofile\tacc\tdom\tn_dom\ti_from\ti_to\tk_from\tk_to\tM\tseg_bits\tn_match\tn_ins\tn_del\n"]
+    for j, (r, p) in enumerate(listed):
+        inf = db.info[p]
+        for d in range(int(nd[j])):
+            w = [int(v) for v in dom[j, d]]
+            out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%d\t%d\t%d\n" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(nd[j]), w[0], w[1], w[2], w[3],
+                                                                                          inf["M"], w[4] / 1024.0, w[5], w[6], w[7])).encode())
+    dom_table = b"".join(out)
+    with open(domains, "wb") as f:
+        f.write(dom_table)
+    return ids, scores, table, dom_table
 
 
-def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3):
+def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein"):
     """One genome per protein FASTA file: per genome the residues of its best protein for every profile that has a hit at the cutoff, in profile
     order - the records an AA sketcher takes for `tohnsw` / `request` at the universal-gene level. -> (list of lists of bytes, uint32 [n_genomes, n_prof]
     record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing). score="forward": the best hits are those of the Forward matrix
-    (SPEC 13.1) behind the Viterbi floor of filter_p - the score the files' GA cutoffs were gathered on."""
+    (SPEC 13.1) behind the Viterbi floor of filter_p - the score the files' GA cutoffs were gathered on. region="aligned" (SPEC 13.2): every hit is
+    traced back on the device and contributes the residues from i_from of its first domain through i_to of its last, not the whole protein."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
+    if region not in ("protein", "aligned"):
+        raise ValueError("region: 'protein' or 'aligned'")
     db = _as_hmm_db(hmm, ctx)
     seqs, goff = [], [0]
     for path in faa_files:
@@ -1146,9 +1208,20 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     aa, rs, rl = filter_aa_records([bytes(s) for s in seqs])
     scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if score == "forward" else db.search_packed(aa, rs, rl)
     rec, _ = db.best_hits(scores, np.array(goff, np.uint64), cutoff)
+    span = {}
+    if region == "aligned" and rec.size:
+        pair_prof = np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
+        _, nd, dom = db.trace_all(aa, rs, rl, rec.reshape(-1), pair_prof)
+        for j in np.flatnonzero(nd):
+            span[int(j)] = (int(dom[j, 0, 0]) - 1, int(dom[j, int(nd[j]) - 1, 1]))
     genomes = []
     for g in range(len(goff) - 1):
-        genomes.append([bytes(aa[int(rs[r]):int(rs[r]) + int(rl[r])]) for r in rec[g] if r != _lib.HMM_NO_HIT])
+        hits = []
+        for p, r in enumerate(rec[g]):
+            if r != _lib.HMM_NO_HIT:
+                a, b = span.get(g * len(db) + p, (0, int(rl[r])))
+                hits.append(bytes(aa[int(rs[r]) + a:int(rs[r]) + b]))
+        genomes.append(hits)
     local = np.where(rec == _lib.HMM_NO_HIT, rec, rec - np.array(goff[:-1], np.uint32)[:, None]).astype(np.uint32)
     return genomes, local
 

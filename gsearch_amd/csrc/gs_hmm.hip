@@ -1,5 +1,6 @@
 // gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
-// device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, and the best record per genome and profile. Integers only
+// device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, the best record per genome and profile, and the domains of
+// the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2). Integers only
 // from the file's digits to the raw score; doubles appear in gs_hmm_bits / gs_hmm_evalue / gs_hmm_forward_evalue, in the table of lse (rounded to
 // integers once, on the host), in the Viterbi floor and in the cutoffs and STATS fields that are only reported.
 #include <math.h>
@@ -470,6 +471,229 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_forward(const int32_t *__rest
     }
 }
 
+// ---- trace-back (SPEC 13.2) ---------------------------------------------------------------------------------------------------------------------
+// A pair of a block: where its back-pointers and its row specials start in the block's scratch, its place in the caller's pair list, its record.
+struct HmmTracePair { uint64_t ptr_off, row_off; uint32_t pair, rec; };           // ptr_off in words, row_off in rows (int4)
+struct HmmTraceProf { uint32_t prof, start, cnt; };                               // the pairs [start, start + cnt) of the call's list belong to prof
+// A cell's pointers are a nibble: bits 0-1 where M[i][k] came from (0 M, 1 I, 2 D of node k - 1 in row i - 1, 3 B[i-1]), bit 2 set: I[i][k] came from
+// I[i-1][k] (clear: M[i-1][k]), bit 3 set: D[i][k] came from D[i][k-1] (clear: M[i][k-1]). A lane's Q nibbles fill NW = ceil(Q / 8) words; word w of
+// lane l in row i lies at ((i - 1) NW + w) 64 + l, so a row is NW bursts of 256 bytes.
+enum { HMM_PTR_B = 3, HMM_ROW_C_FROM_E = 1, HMM_ROW_J_FROM_E = 2, HMM_ROW_B_FROM_N = 4, HMM_WALK_BLOCK = 64 };
+__host__ __device__ constexpr int hmm_ptr_words(int Q) { return (Q + 7) / 8; }
+// HMM_CLASS_Q of the class a profile of M nodes runs in, for device code
+__host__ __device__ constexpr int hmm_q_of(uint32_t M)
+{
+    const uint32_t g = (M + 63) / 64;
+    return g <= 1 ? 1 : (g <= 4 ? (int)g : (g <= 6 ? 6 : (g <= 8 ? 8 : (g <= 12 ? 12 : (g <= 16 ? 16 : 20)))));
+}
+
+// k_hmm_viterbi's geometry and row loop; a wavefront takes the pairs of its profile's list in turn. Beyond the score every row leaves the nibbles of
+// its cells and, through lane 0, {E[i], B[i], the lowest k with M[i][k] == E[i], the decisions of C[i], J[i] and B[i]}; row 0 is {NEG, tmove, 0, B from N}.
+//   The M pointer of node k + 1 is decided in the lane of node k: give = max(a, b, c) there, and the first of a, b, c, entry that equals
+//   max(give, entry) is the first of a, b, c that equals give when give >= entry, else the entry. The code of a lane's last node moves up one lane
+//   together with the D decision of the next lane's first node (M + tMD of the last node == what leaves the lane after the scan), in one word.
+//   No traced cell is at the clamp (SPEC 13.2), so an equality that a clamped cell decides differently is never followed.
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_trace(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                         const HmmTracePair *__restrict__ pairs, const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start,
+                                                         const uint64_t *__restrict__ rec_len, uint32_t *__restrict__ ptrs, int4 *__restrict__ rows,
+                                                         int32_t *__restrict__ raw_out)
+{
+    extern __shared__ int32_t hmm_lds[];
+    constexpr int MP = 64 * Q, NW = hmm_ptr_words(Q);
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmDesc d = desc[tp.prof];
+    for (int i = (int)threadIdx.x; i < HMM_ROWS_DEV * MP; i += HMM_BLOCK) hmm_lds[i] = tables[d.off + i];
+    __syncthreads();
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int base = lane * Q;
+    const int nvalid = min(max((int)d.M - base, 0), Q);
+    const int32_t *tMM = hmm_lds + HMM_ROW_MM * MP + base, *tMI = hmm_lds + HMM_ROW_MI * MP + base, *tMD = hmm_lds + HMM_ROW_MD * MP + base,
+                  *tIM = hmm_lds + HMM_ROW_IM * MP + base, *tII = hmm_lds + HMM_ROW_II * MP + base, *tDM = hmm_lds + HMM_ROW_DM * MP + base,
+                  *tDD = hmm_lds + HMM_ROW_DD * MP + base, *PDD = hmm_lds + HMM_ROW_PDD * MP + base;
+    int32_t a_step[6];
+    {
+        int32_t a = PDD[Q - 1] + tDD[Q - 1];
+        for (int s = 0; s < 6; s++) {
+            a_step[s] = a;
+            const int32_t up = __shfl_up(a, 1 << s);
+            if (lane >= (1 << s)) a += up;
+        }
+    }
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const uint32_t L = (uint32_t)rec_len[pr.rec];              // 1 <= L <= GS_HMM_TRACE_MAX_L: the host put no other pair on a list
+        const uint8_t *x = aa + rec_start[pr.rec];
+        uint32_t *pp = ptrs + pr.ptr_off + lane;
+        int4 *rr = rows + pr.row_off;
+        const HmmSpecials sp = hmm_specials(L);
+        int32_t Mv[Q], Iv[Q], Dv[Q];
+#pragma unroll
+        for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
+        int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
+        if (lane == 0) rr[0] = make_int4(GS_HMM_NEG, B, 0, HMM_ROW_B_FROM_N);
+        bool bad = false;
+        int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
+        for (uint32_t i0 = 0; i0 < L; i0 += 64) {
+            const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;
+            bad |= cur < 0;
+            const int res = max(cur, 0);
+            const int cnt = (int)min(64u, L - i0);
+            for (int t = 0; t < cnt; t++) {
+                if (Q >= 12) asm volatile("" ::: "memory");      // the transition rows are read from LDS in every row: see k_hmm_forward
+                const int32_t *ms = hmm_lds + __builtin_amdgcn_readlane(res, t) * MP + base;
+                const int32_t entry = B + d.tbm;
+                uint32_t pk[NW];
+#pragma unroll
+                for (int w = 0; w < NW; w++) pk[w] = 0;
+                int32_t give[Q];
+                uint32_t code_out = HMM_PTR_B;                   // the M pointer of the next lane's first node
+#pragma unroll
+                for (int q = 0; q < Q; q++) {
+                    const int32_t a = Mv[q] + tMM[q], b = Iv[q] + tIM[q], c = Dv[q] + tDM[q];
+                    const int32_t g = max(max(a, b), c);
+                    give[q] = g;
+                    const uint32_t code = g >= entry ? (a == g ? 0u : (b == g ? 1u : 2u)) : (uint32_t)HMM_PTR_B;
+                    if (q + 1 < Q) pk[(q + 1) >> 3] |= code << (4 * ((q + 1) & 7)); else code_out = code;
+                }
+                int32_t up = __shfl_up(give[Q - 1], 1);
+                if (lane == 0) up = GS_HMM_NEG;
+#pragma unroll
+                for (int q = 0; q < Q; q++) {
+                    const int32_t fromM = Mv[q] + tMI[q];
+                    Iv[q] = max(max(fromM, Iv[q] + tII[q]), GS_HMM_NEG);
+                    pk[q >> 3] |= (fromM == Iv[q] ? 0u : 4u) << (4 * (q & 7));
+                }
+#pragma unroll
+                for (int q = 0; q < Q; q++) Mv[q] = max(ms[q] + max(q ? give[q - 1] : up, entry), GS_HMM_NEG);
+                int32_t dl = GS_HMM_NEG;
+                Dv[0] = dl;
+#pragma unroll
+                for (int q = 1; q < Q; q++) { dl = max(max(dl + tDD[q - 1], Mv[q - 1] + tMD[q - 1]), GS_HMM_NEG); Dv[q] = dl; }
+                const int32_t m_out = Mv[Q - 1] + tMD[Q - 1];
+                int32_t b = max(max(dl + tDD[Q - 1], m_out), GS_HMM_NEG);
+#pragma unroll
+                for (int s = 0; s < 6; s++) b = max(b, __shfl_up(b, 1 << s) + a_step[s]);
+                int32_t c_in = __shfl_up(b, 1);
+                uint32_t edge = (uint32_t)__shfl_up((int)(code_out | (m_out == b ? 0u : 8u)), 1);
+                if (lane == 0) { c_in = GS_HMM_NEG; edge = HMM_PTR_B | 8u; }
+                pk[0] |= edge;
+                int32_t e = GS_HMM_NEG;
+#pragma unroll
+                for (int q = 0; q < Q; q++) {
+                    Dv[q] = max(Dv[q], c_in + PDD[q]);
+                    if (q >= 1) pk[q >> 3] |= (Mv[q - 1] + tMD[q - 1] == Dv[q] ? 0u : 8u) << (4 * (q & 7));
+                    if (q < nvalid) e = max(e, Mv[q]);
+                }
+                const int32_t E = hmm_wave_max(e);
+                const uint32_t row = i0 + (uint32_t)t;          // row i = row + 1
+#pragma unroll
+                for (int w = 0; w < NW; w++) pp[((uint64_t)row * NW + w) * 64] = pk[w];
+                // the lowest node of the row's maximum: the first lane that holds it, and that lane's first node
+                int first = 0;
+#pragma unroll
+                for (int q = Q - 1; q >= 0; q--) if (q < nvalid && Mv[q] == E) first = q;
+                const int fl = __ffsll((unsigned long long)__ballot(e == E)) - 1;     // some lane holds it: E is the maximum of the e
+                const int kE = fl * Q + __builtin_amdgcn_readlane(first, fl) + 1;
+                N += sp.tloop;
+                const int32_t Jn = max(max(J + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG), Cn = max(max(C + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
+                const int flags = (E + GS_HMM_TEJ == Cn ? HMM_ROW_C_FROM_E : 0) | (E + GS_HMM_TEJ == Jn ? HMM_ROW_J_FROM_E : 0) | (N >= Jn ? HMM_ROW_B_FROM_N : 0);
+                J = Jn; C = Cn;
+                B = max(N, J) + sp.tmove;
+                if (lane == 0) rr[row + 1] = make_int4(E, B, kE, flags);
+            }
+            cur = nxt;
+        }
+        const bool any_bad = __any(bad);
+        if (lane == 0) raw_out[pr.pair] = any_bad ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
+    }
+}
+
+// The walk of SPEC 13.2, one lane per pair of the block: from C[L] back to N, once to count the domains and once to write the first max_dom of them
+// in sequence order. Every step lowers i or k, so a walk ends after at most 2 (L + M) steps whatever the scratch holds; L + M dependent loads a pair.
+__global__ __launch_bounds__(HMM_WALK_BLOCK) void k_hmm_walk(const HmmDesc *__restrict__ desc, const HmmTracePair *__restrict__ pairs, uint32_t n, const uint32_t *__restrict__ pair_prof,
+                                                             const uint64_t *__restrict__ rec_len, const uint32_t *__restrict__ ptrs, const int4 *__restrict__ rows,
+                                                             const int32_t *__restrict__ raw, uint32_t max_dom, uint32_t *__restrict__ n_dom_out, int32_t *__restrict__ dom_out)
+{
+    const uint32_t t = blockIdx.x * HMM_WALK_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    const HmmTracePair pr = pairs[t];
+    if (raw[pr.pair] == GS_HMM_NO_SCORE) return;                   // a byte that is no residue: the outputs keep what the fill wrote
+    const int M = (int)desc[pair_prof[pr.pair]].M;
+    const int Q = hmm_q_of((uint32_t)M), NW = hmm_ptr_words(Q);
+    const int L = (int)rec_len[pr.rec];
+    const uint32_t *pp = ptrs + pr.ptr_off;
+    const int4 *rr = rows + pr.row_off;
+    auto nibble = [&](int i, int k) {
+        const int node = k - 1, ln = node / Q, q = node - ln * Q;
+        return (pp[((uint64_t)(i - 1) * NW + (q >> 3)) * 64 + ln] >> (4 * (q & 7))) & 15u;
+    };
+    int32_t *dom = dom_out + (uint64_t)pr.pair * max_dom * GS_HMM_DOM_WORDS;
+    uint32_t total = 0;
+    for (int pass = 0; pass < 2; pass++) {
+        uint32_t found = 0;
+        int i = L;
+        bool more = true;
+        while (more && i >= 1) {
+            while (i > 1 && !(rr[i].w & (found ? HMM_ROW_J_FROM_E : HMM_ROW_C_FROM_E))) i--;       // C[i] (first) or J[i] (later) back to the row it left E in
+            const int4 re = rr[i];
+            const int i_to = i, k_to = min(max(re.z, 1), M);
+            int k = k_to, st = 0, nm = 0, ni = 0, nd = 0, i_from = 0, k_from = 0;
+            while (i >= 1 && k >= 1) {
+                const uint32_t nb = nibble(i, k);
+                if (st == 0) {
+                    nm++;
+                    const uint32_t from = nb & 3u;
+                    if (from == HMM_PTR_B || i == 1 || k == 1) { i_from = i; k_from = k; break; }
+                    st = (int)from; i--; k--;
+                } else if (st == 1) {
+                    ni++;
+                    st = nb & 4u ? 1 : 0; i--;
+                } else {
+                    nd++;
+                    st = nb & 8u ? 2 : 0; k--;
+                }
+            }
+            if (!i_from) break;                                     // not a path: only scratch that no trace kernel wrote leads here
+            const int4 rb = rr[i_from - 1];
+            if (pass == 1 && total - 1 - found < max_dom) {
+                int32_t *o = dom + (uint64_t)(total - 1 - found) * GS_HMM_DOM_WORDS;
+                o[0] = i_from; o[1] = i_to; o[2] = k_from; o[3] = k_to; o[4] = re.x - rb.y; o[5] = nm; o[6] = ni; o[7] = nd;
+            }
+            found++;
+            i = i_from - 1;
+            more = !(rb.w & HMM_ROW_B_FROM_N);
+        }
+        if (pass == 0) { total = found; n_dom_out[pr.pair] = total; }
+    }
+}
+
+// raw = GS_HMM_NO_SCORE, n_dom = 0 and zeroed slots for every pair; the pairs that are traced overwrite theirs
+__global__ __launch_bounds__(256) void k_hmm_trace_fill(uint64_t n_pairs, uint64_t n_dom_words, int32_t *__restrict__ raw, uint32_t *__restrict__ n_dom, int32_t *__restrict__ dom)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_pairs) { raw[i] = GS_HMM_NO_SCORE; n_dom[i] = 0; }
+    if (i < n_dom_words) dom[i] = 0;
+}
+
+typedef void (*hmm_trace_kernel_t)(const int32_t *, const HmmDesc *, const HmmTraceProf *, const HmmTracePair *, const uint8_t *, const uint64_t *, const uint64_t *,
+                                   uint32_t *, int4 *, int32_t *);
+static hmm_trace_kernel_t hmm_trace_kernel(int cls)
+{
+    switch (cls) {
+    case 0: return k_hmm_trace<1>;
+    case 1: return k_hmm_trace<2>;
+    case 2: return k_hmm_trace<3>;
+    case 3: return k_hmm_trace<4>;
+    case 4: return k_hmm_trace<6>;
+    case 5: return k_hmm_trace<8>;
+    case 6: return k_hmm_trace<12>;
+    case 7: return k_hmm_trace<16>;
+    default: return k_hmm_trace<20>;
+    }
+}
+
 typedef void (*hmm_fwd_kernel_t)(const int32_t *, const HmmDesc *, const uint32_t *, const uint16_t *, const uint8_t *, const uint64_t *, const uint64_t *,
                                  const uint32_t *, const uint32_t *, uint32_t, uint32_t, int32_t *);
 static hmm_fwd_kernel_t hmm_fwd_kernel(int cls)
@@ -518,7 +742,7 @@ struct gs_hmm_db {
     std::vector<uint32_t> plist;                    // profile numbers, class by class
     uint32_t class_start[gs::HMM_CLASSES + 1] = {};
     bool all_ga = true;
-    bool lds_set[gs::HMM_CLASSES] = {}, lds_set_fwd[gs::HMM_CLASSES] = {};
+    bool lds_set[gs::HMM_CLASSES] = {}, lds_set_fwd[gs::HMM_CLASSES] = {}, lds_set_trace[gs::HMM_CLASSES] = {};
     gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse;
 };
 
@@ -648,6 +872,125 @@ static int hmm_forward_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, con
             GS_HIP_CHECK(hipGetLastError());
         }
     }
+    return GS_OK;
+}
+
+// ---- trace-back, host side (SPEC 13.2) ----------------------------------------------------------------------------------------------------------
+// max_block_cells = 0: 2^27 cells (sum of L * 64 Q) of back-pointers alive at once - 64 MB of nibbles at Q = 8 and 16, 0.5 GB at Q = 1 where a lane's
+// one nibble still takes a word. The longest record against the largest profile (65 536 x 1 280) is 84 million cells, so it fits one default block.
+static constexpr uint64_t HMM_TRACE_DEFAULT_BLOCK_CELLS = 1ull << 27;
+
+// what gs_hmm_trace refuses, decided on host copies before anything is queued
+static int hmm_trace_check(const gs_hmm_db *db, const uint64_t *lens, uint64_t n_rec, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs)
+{
+    const uint64_t np = db->models.size();
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        GS_REQUIRE(pprof[i] < np, GS_ERR_INVALID, "hmm: pair %llu names profile %u of %llu", (unsigned long long)i, pprof[i], (unsigned long long)np);
+        GS_REQUIRE(prec[i] == GS_HMM_NO_HIT || prec[i] < n_rec, GS_ERR_INVALID, "hmm: pair %llu names record %u of %llu", (unsigned long long)i, prec[i], (unsigned long long)n_rec);
+    }
+    for (uint64_t i = 0; i < n_pairs; i++)
+        GS_REQUIRE(prec[i] == GS_HMM_NO_HIT || lens[prec[i]] <= GS_HMM_TRACE_MAX_L, GS_ERR_UNSUPPORTED, "hmm: pair %llu names record %u of %llu residues, more than %u",
+                   (unsigned long long)i, prec[i], (unsigned long long)lens[prec[i]], GS_HMM_TRACE_MAX_L);
+    return GS_OK;
+}
+
+// lens, prec, pprof: host copies that hmm_trace_check has passed; everything else device memory. Blocks of pairs in the caller's order, each block's pairs
+// by class and profile, longest record first; a block is a trace launch per class that occurs and one walk, all on c's stream, which is waited for at the end.
+static int hmm_trace_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, const uint32_t *prec,
+                          const uint32_t *pprof, const uint32_t *pprof_dev, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_dev,
+                          uint32_t *ndom_dev, int32_t *dom_dev)
+{
+    const uint64_t cap = max_block_cells ? max_block_cells : HMM_TRACE_DEFAULT_BLOCK_CELLS;
+    const uint64_t n_dom_words = n_pairs * max_dom * GS_HMM_DOM_WORDS, n_fill = std::max(n_pairs, n_dom_words);
+    GS_REQUIRE(n_fill < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many domain slots");
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_trace_fill<<<(unsigned)((n_fill + 255) / 256), 256, 0, c->stream>>>(n_pairs, n_dom_words, raw_dev, ndom_dev, dom_dev);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    struct Block { uint32_t start, n, prof_start[HMM_CLASSES + 1], max_cnt[HMM_CLASSES]; };
+    std::vector<HmmTracePair> tp;
+    std::vector<HmmTraceProf> tprof;
+    std::vector<Block> blocks;
+    std::vector<uint32_t> cur;
+    uint64_t cells = 0, max_ptr = 0, max_rows = 0;
+    auto flush = [&]() {
+        if (cur.empty()) return;
+        std::stable_sort(cur.begin(), cur.end(), [&](uint32_t a, uint32_t b) {
+            const int ca = hmm_class_of(db->desc[pprof[a]].M), cb = hmm_class_of(db->desc[pprof[b]].M);
+            if (ca != cb) return ca < cb;
+            if (pprof[a] != pprof[b]) return pprof[a] < pprof[b];
+            return lens[prec[a]] > lens[prec[b]];
+        });
+        Block b{};
+        b.start = (uint32_t)tp.size(); b.n = (uint32_t)cur.size();
+        uint64_t ptr = 0, row = 0;
+        size_t at = 0;
+        for (int cls = 0; cls < HMM_CLASSES; cls++) {
+            b.prof_start[cls] = (uint32_t)tprof.size();
+            while (at < cur.size() && hmm_class_of(db->desc[pprof[cur[at]]].M) == cls) {
+                const uint32_t prof = pprof[cur[at]];
+                HmmTraceProf g{prof, (uint32_t)tp.size(), 0};
+                for (; at < cur.size() && pprof[cur[at]] == prof; at++, g.cnt++) {
+                    const uint64_t L = lens[prec[cur[at]]];
+                    tp.push_back(HmmTracePair{ptr, row, cur[at], prec[cur[at]]});
+                    ptr += L * hmm_ptr_words(HMM_CLASS_Q[cls]) * 64;
+                    row += L + 1;
+                }
+                b.max_cnt[cls] = std::max(b.max_cnt[cls], g.cnt);
+                tprof.push_back(g);
+            }
+        }
+        b.prof_start[HMM_CLASSES] = (uint32_t)tprof.size();
+        max_ptr = std::max(max_ptr, ptr); max_rows = std::max(max_rows, row);
+        blocks.push_back(b);
+        cur.clear(); cells = 0;
+    };
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (prec[i] == GS_HMM_NO_HIT || lens[prec[i]] == 0) continue;
+        const uint64_t pc = lens[prec[i]] * 64 * HMM_CLASS_Q[hmm_class_of(db->desc[pprof[i]].M)];
+        if (!cur.empty() && cells + pc > cap) flush();
+        cur.push_back((uint32_t)i);
+        cells += pc;
+    }
+    flush();
+    if (!blocks.empty()) {
+        PoolBuf d_tp(c, SL_HMMT_PAIRS), d_tprof(c, SL_HMMT_PROFS), d_ptr(c, SL_HMMT_PTR), d_rows(c, SL_HMMT_ROWS);
+        int rc;
+        if ((rc = d_tp.alloc(sizeof(HmmTracePair) * tp.size())) || (rc = d_tprof.alloc(sizeof(HmmTraceProf) * tprof.size())) || (rc = d_ptr.alloc(4 * max_ptr)) ||
+            (rc = d_rows.alloc(sizeof(int4) * max_rows)))
+            return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(d_tp.p, tp.data(), sizeof(HmmTracePair) * tp.size(), hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(d_tprof.p, tprof.data(), sizeof(HmmTraceProf) * tprof.size(), hipMemcpyHostToDevice, c->stream));
+        for (const Block &b : blocks) {
+            for (int cls = 0; cls < HMM_CLASSES; cls++) {
+                const uint32_t n_in = b.prof_start[cls + 1] - b.prof_start[cls];
+                if (!n_in) continue;
+                const size_t lds = (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4;
+                hmm_trace_kernel_t k = hmm_trace_kernel(cls);
+                if (!db->lds_set_trace[cls]) {
+                    if (lds > 64 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    db->lds_set_trace[cls] = true;
+                }
+                const uint32_t wg = std::min<uint32_t>((b.max_cnt[cls] + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
+                for (uint32_t y0 = 0; y0 < n_in; y0 += 65535) {
+                    ProfScope ps(c, FAM_SEARCH);
+                    k<<<dim3(wg, std::min<uint32_t>(n_in - y0, 65535)), HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(),
+                                                                                                   d_tprof.as<HmmTraceProf>() + b.prof_start[cls] + y0, d_tp.as<HmmTracePair>(),
+                                                                                                   aa_dev, rs_dev, rl_dev, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev);
+                    GS_HIP_CHECK(hipGetLastError());
+                }
+            }
+            ProfScope ps(c, FAM_SEARCH);
+            k_hmm_walk<<<(b.n + HMM_WALK_BLOCK - 1) / HMM_WALK_BLOCK, HMM_WALK_BLOCK, 0, c->stream>>>(db->d_desc.as<HmmDesc>(), d_tp.as<HmmTracePair>() + b.start, b.n, pprof_dev,
+                                                                                                        rl_dev, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev, max_dom,
+                                                                                                        ndom_dev, dom_dev);
+            GS_HIP_CHECK(hipGetLastError());
+        }
+        GS_HIP_CHECK(stream_wait(c));       // the lists are read by the copies until here, and the slots go back
+        return GS_OK;
+    }
+    GS_HIP_CHECK(stream_wait(c));
     return GS_OK;
 }
 
@@ -907,6 +1250,67 @@ int gs_hmm_search_forward(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uin
         return rc;
     if (vit_out) GS_HIP_CHECK(hipMemcpyAsync(vit_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+int gs_hmm_trace_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                     const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_out_dev,
+                     uint32_t *n_dom_out_dev, int32_t *dom_out_dev)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_pairs == 0) return GS_OK;
+    GS_REQUIRE(pair_rec_dev && pair_prof_dev && raw_out_dev && n_dom_out_dev && (dom_out_dev || max_dom == 0), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec == 0 || (aa_dev && rec_start_dev && rec_len_dev), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
+    GS_CTX_LOCK(c);
+    std::vector<uint64_t> lens(n_rec);
+    std::vector<uint32_t> prec(n_pairs), pprof(n_pairs);
+    if (n_rec) GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rec_len_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(prec.data(), pair_rec_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(pprof.data(), pair_prof_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    int rc = hmm_trace_check(db, lens.data(), n_rec, prec.data(), pprof.data(), n_pairs);
+    if (rc) return rc;
+    return hmm_trace_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), prec.data(), pprof.data(), pair_prof_dev, n_pairs, max_dom, max_block_cells, raw_out_dev,
+                          n_dom_out_dev, dom_out_dev);
+}
+
+int gs_hmm_trace(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                 const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_out, uint32_t *n_dom_out, int32_t *dom_out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_pairs == 0) return GS_OK;
+    GS_REQUIRE(pair_rec && pair_prof && raw_out && n_dom_out && (dom_out || max_dom == 0), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec == 0 || (rec_start && rec_len), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
+    int rc = hmm_trace_check(db, rec_len, n_rec, pair_rec, pair_prof, n_pairs);
+    if (rc) return rc;
+    uint64_t n_bytes = 0;                       // of the records that a pair names: the others may be any length and are not staged
+    for (uint64_t i = 0; i < n_pairs; i++)
+        if (pair_rec[i] != GS_HMM_NO_HIT && rec_len[pair_rec[i]]) n_bytes = std::max(n_bytes, rec_start[pair_rec[i]] + rec_len[pair_rec[i]]);
+    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
+    const uint64_t n_dom_bytes = 4 * n_pairs * max_dom * GS_HMM_DOM_WORDS;
+    GS_CTX_LOCK(c);
+    PoolBuf d_aa(c, SL_HMMTB_AA), d_rs(c, SL_HMMTB_REC_START), d_rl(c, SL_HMMTB_REC_LEN), d_pp(c, SL_HMMTB_PAIR_PROF), d_raw(c, SL_HMMTB_RAW),
+        d_nd(c, SL_HMMTB_NDOM), d_dom(c, SL_HMMTB_DOM);
+    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec)) || (rc = d_pp.alloc(4 * n_pairs)) ||
+        (rc = d_raw.alloc(4 * n_pairs)) || (rc = d_nd.alloc(4 * n_pairs)) || (rc = d_dom.alloc(n_dom_bytes)))
+        return rc;
+    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
+    if (n_rec) {
+        GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+    }
+    GS_HIP_CHECK(hipMemcpyAsync(d_pp.p, pair_prof, 4 * n_pairs, hipMemcpyHostToDevice, c->stream));
+    if ((rc = hmm_trace_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, pair_rec, pair_prof, d_pp.as<uint32_t>(), n_pairs, max_dom,
+                             max_block_cells, d_raw.as<int32_t>(), d_nd.as<uint32_t>(), d_dom.as<int32_t>())))
+        return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(raw_out, d_raw.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(n_dom_out, d_nd.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    if (n_dom_bytes) GS_HIP_CHECK(hipMemcpyAsync(dom_out, d_dom.p, n_dom_bytes, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(stream_wait(c));
     return GS_OK;
 }

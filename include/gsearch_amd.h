@@ -344,6 +344,25 @@ int gs_hmm_search_forward(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const u
 /* host only, double: E = n_targets * P with P = 1 for bits < tau, exp(-lambda (bits - tau)) otherwise (the exponential tail of STATS LOCAL FORWARD) */
 double gs_hmm_forward_evalue(double bits, double tau, double lambda, double n_targets);
 
+/* Trace-back (SPEC 13.2): the domains of the Viterbi path of a list of (record, profile) pairs - the segments of the path between a B -> M entry and the
+ * M -> E exit that follows it. The dynamic program (with back-pointers) and the walk back both run on the device. A domain is GS_HMM_DOM_WORDS int32:
+ * i_from, i_to, k_from, k_to (1-based, inclusive), seg = M[i_to][k_to] - B[i_from - 1], n_match, n_ins, n_del. Pairs in any order, repeats allowed.
+ * raw_out[j] = what gs_hmm_search writes for pair j; n_dom_out[j] = the true number of domains; dom_out[j][0 .. min(n_dom, max_dom)) = the first domains
+ * in sequence order, the other slots of the pair zeros (max_dom = 0 with dom_out = NULL is allowed). A pair with pair_rec = GS_HMM_NO_HIT, an empty
+ * record or a record with a byte that is no residue: raw = GS_HMM_NO_SCORE, n_dom = 0, zeroed slots - the [n_genomes][n_prof] output of
+ * gs_hmm_best_hits_dev is a pair list as it lies, with pair_prof = index % n_prof. Any other pair_rec >= n_rec, or a pair_prof >= n_prof: GS_ERR_INVALID; a
+ * named record longer than GS_HMM_TRACE_MAX_L: GS_ERR_UNSUPPORTED; both before anything is queued, nothing written (records that no pair names may be
+ * any length). max_block_cells bounds the cells (sum of L * 64 Q over the pairs of a block, Q the nodes per lane of the profile's class) whose
+ * back-pointers are alive at once; 0 = 2^27; a block always holds at least one pair. Device form: every array device memory; the lengths and the pair
+ * list are read back once. */
+#define GS_HMM_TRACE_MAX_L 65536u
+#define GS_HMM_DOM_WORDS 8u
+int gs_hmm_trace(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                 const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_out, uint32_t *n_dom_out, int32_t *dom_out);
+int gs_hmm_trace_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                     const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells,
+                     int32_t *raw_out_dev, uint32_t *n_dom_out_dev, int32_t *dom_out_dev);
+
 /* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */
 /*   new/modify_level_scale/set_extend_candidates/set_keeping_pruned  dnasketch.rs:139-141,159-160  */

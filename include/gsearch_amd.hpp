@@ -270,6 +270,17 @@ public:
                                     fwd.data()));
         return {std::move(vit), std::move(fwd)};
     }
+    // SPEC 13.2: the domains of the Viterbi path of the pairs (pair_rec[j], pair_prof[j]), traced back on the device. raw[j] as search() gives it,
+    // n_dom[j] the true number of domains, dom[(j * max_dom + d) * GS_HMM_DOM_WORDS ..] the first max_dom of them in sequence order (zeros behind them)
+    struct Trace { std::vector<int32_t> raw; std::vector<uint32_t> n_dom; std::vector<int32_t> dom; };
+    Trace trace(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len, const std::vector<uint32_t> &pair_rec,
+                const std::vector<uint32_t> &pair_prof, uint32_t max_dom = 8, uint64_t max_block_cells = 0) const
+    {
+        Trace t{std::vector<int32_t>(pair_rec.size()), std::vector<uint32_t>(pair_rec.size()), std::vector<int32_t>(pair_rec.size() * max_dom * GS_HMM_DOM_WORDS)};
+        check(gs_hmm_trace(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), pair_rec.data(), pair_prof.data(), pair_rec.size(), max_dom,
+                           max_block_cells, t.raw.data(), t.n_dom.data(), t.dom.empty() ? nullptr : t.dom.data()));
+        return t;
+    }
     // the floor of profile p for a Viterbi P-value of filter_p (HMMER's F2 = 1e-3): INT32_MIN + 1 without STATS LOCAL VITERBI
     int32_t viterbi_floor(size_t profile, double filter_p = 1e-3) const
     {

@@ -13,7 +13,13 @@ composition) against 120 synthetic profiles with the node counts of the bacteria
                 plus Forward (the call less the Viterbi time) beside the Viterbi seconds
   check         `check` sampled pairs compared with the restatement (tests/pyref_hmm_forward.py): the expected difference is 0
 
-usage: hmm_rate.py [--forward] [--n 4000] [--repeat 3] [--check 8] [--log profiles/hmm_rate.log | profiles/hmm_forward_rate.log]"""
+--trace (SPEC 13.2), on the same proteome and profile set:
+  trace_best    seconds of gs_hmm_trace_dev over the best hit of every profile (the proteome as one genome): what universal_genes(region="aligned") pays
+  trace_all     seconds and cells/s of gs_hmm_trace_dev over ALL pairs with max_dom = 2 (the trace kernels, the walks and the host's grouping of the
+                pairs into blocks; the default block size), beside the Viterbi seconds of the same run
+  check         the raw of every traced pair against the score matrix, and `check` sampled pairs against the restatement (tests/pyref_hmm_trace.py)
+
+usage: hmm_rate.py [--forward | --trace] [--n 4000] [--repeat 3] [--check 8] [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log]"""
 import argparse
 import json
 import os
@@ -34,10 +40,11 @@ def main():
     ap.add_argument("--check", type=int, default=8)
     ap.add_argument("--seed", type=int, default=13)
     ap.add_argument("--forward", action="store_true")
+    ap.add_argument("--trace", action="store_true")
     ap.add_argument("--log", default=None)
     a = ap.parse_args()
     if a.log is None:
-        a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else "hmm_rate.log")
+        a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else ("hmm_trace_rate.log" if a.trace else "hmm_rate.log"))
     import gsearch_amd as G
     import pyref_hmm as R
     rng = np.random.default_rng(a.seed)
@@ -84,6 +91,8 @@ def main():
     res["check_pairs"], res["check_differences"] = a.check, diff
     if a.forward:
         forward_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng)
+    if a.trace:
+        trace_part(a, ctx, db, texts, recs, ptrs, d_rec, scores, cells, res, rng)
     for p in ptrs + [d_score, d_rec, d_best]:
         ctx.free(p)
     db.close()
@@ -134,6 +143,53 @@ def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng):
     res["forward_check_pairs"], res["forward_check_differences"] = a.check, diff
     ctx.free(d_fwd)
     ctx.free(d_floor)
+
+
+def trace_part(a, ctx, db, texts, recs, ptrs, d_best_rec, scores, cells, res, rng):
+    import pyref_hmm as R
+    import pyref_hmm_trace as T
+    n_prof = len(db)
+
+    def run(d_pr, pp, max_dom):
+        n = len(pp)
+        bufs = [ctx.alloc(max(4 * n, 16)) for _ in range(3)] + [ctx.alloc(max(4 * n * max_dom * 8, 16))]
+        ctx.upload(bufs[0], pp)
+        best = float("inf")
+        for it in range(a.repeat + 1):
+            ctx.sync()
+            t = time.perf_counter()
+            db.trace_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, bufs[0], n, max_dom, bufs[1], bufs[2], bufs[3])
+            ctx.sync()
+            if it:
+                best = min(best, time.perf_counter() - t)
+        out = ctx.download(bufs[1], (n,), np.int32), ctx.download(bufs[2], (n,), np.uint32), ctx.download(bufs[3], (n, max_dom, 8), np.int32)
+        for b in bufs:
+            ctx.free(b)
+        return best, out
+
+    hit = ctx.download(d_best_rec, (n_prof,), np.uint32)
+    res["trace_best_s"], (raw, nd, dom) = run(d_best_rec, np.arange(n_prof, dtype=np.uint32), 8)
+    on = hit != R.NO_HIT
+    res["trace_best_pairs"] = int(on.sum())
+    res["trace_best_raw_differences"] = int((raw[on] != scores[hit[on], np.flatnonzero(on)]).sum()) + int((raw[~on] != R.NO_SCORE).sum())
+    res["trace_best_domains"] = int(nd.sum())
+    pr = np.repeat(np.arange(a.n, dtype=np.uint32), n_prof)
+    d_pr = ctx.alloc(pr.nbytes)
+    ctx.upload(d_pr, pr)
+    res["trace_all_s"], (raw, nd, dom) = run(d_pr, np.tile(np.arange(n_prof, dtype=np.uint32), a.n), 2)
+    ctx.free(d_pr)
+    res["trace_all_pairs"] = len(pr)
+    res["trace_all_cells_per_s"] = cells / res["trace_all_s"]
+    res["trace_all_over_viterbi"] = res["trace_all_s"] / res["search_s"]
+    res["trace_all_raw_differences"] = int((raw.reshape(a.n, n_prof) != scores).sum())
+    res["trace_all_domains"] = int(nd.sum())
+    diff = 0
+    for _ in range(a.check):
+        r, p = int(rng.integers(a.n)), int(rng.integers(n_prof))
+        want = T.trace_pairs([R.parse_hmm(texts[p])[0]], recs, [r], [0], 2)
+        j = r * n_prof + p
+        diff += int(not (raw[j] == want[0][0] and nd[j] == want[1][0] and np.array_equal(dom[j], want[2][0])))
+    res["trace_check_pairs"], res["trace_check_differences"] = a.check, diff
 
 
 if __name__ == "__main__":
