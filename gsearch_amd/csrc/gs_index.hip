@@ -565,14 +565,13 @@ __device__ __forceinline__ uint32_t dense_row_tau(const uint16_t *__restrict__ m
 
 // a wave-uniform value the compiler cannot prove uniform (it came through LDS): pin it to an SGPR
 __device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-// inclusive running sums over each group of eight lanes (lane i: x of lanes (i & ~7) .. i), by three row shifts on the vector unit; a lane whose
-// source lies outside its row of sixteen adds nothing, and lanes 8 .. 15 of a row, which also take from lanes 0 .. 7, are not what the callers read
-__device__ __forceinline__ uint32_t row_prefix8(uint32_t x)
+// inclusive running sums over each group of four lanes (lane i: x of lanes (i & ~3) .. i), by two row shifts on the vector unit; a lane whose source
+// lies outside its row of sixteen adds nothing, and lanes 4 .. 15 of a row, which also take from the group before theirs, are not what the callers read
+__device__ __forceinline__ uint32_t row_prefix4(uint32_t x)
 {
-    static_assert(DT / 64 == 8, "one word per wavefront of the workgroup");
+    static_assert(DT / 64 == 8, "four wavefronts to a half of the workgroup");
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);      // row_shr:1
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);      // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);      // row_shr:4
     return x;
 }
 // ================= phase 2: the order-free rest of search_layer =================
@@ -1005,9 +1004,9 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
         const uint32_t rid_ = uni32(KID(K));                                                                               \
         uint32_t tx_ = threadIdx.x;                                                                                        \
         asm volatile("" : "+v"(tx_));               /* opaque lane offset: keeps the 64-bit row base scalar; made here */ \
-        const uint32_t ho_ = (ONEG ? tx_ : tx_ & 255u) * 4u;   /* from the lane's number: as a value kept across the pop it was spilled */ \
+        const uint32_t hl_ = ONEG ? tx_ : tx_ & 255u, ho_ = hl_ * 4u;   /* from the lane's number: as a value kept across the pop it was spilled */ \
         PD = ix.deg0[rid_];                                                                                                \
-        PI = hl < maxdeg ? GS_TRAV_LOAD((const uint32_t *)((const uint8_t *)(ix.nbr0 + (uint64_t)rid_ * maxdeg) + ho_)) : 0; \
+        PI = hl_ < maxdeg ? GS_TRAV_LOAD((const uint32_t *)((const uint8_t *)(ix.nbr0 + (uint64_t)rid_ * maxdeg) + ho_)) : 0; \
     } while (0)
 #define GS_DROW(K) GS_DROWX(K, pdeg, pid)
     // per-workgroup global scratch: the visited bitmap (VLDS = false) or the fine histogram bins (VLDS = true)
@@ -1110,7 +1109,9 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
                     continue;
                 }
                 if (KCNT(c) > dmax) break;                           // dmax is INF_CNT until R is full; the front's head is the smallest waiting key
-                if (wv == 0) {                                       // pop: the front moves down one lane; what the next pop sees if this one accepts nothing
+                // (the wave's number taken as a scalar where it is tested: as a lane mask kept across the loop "wv == 0" was a spilled SGPR pair, two
+                // v_readlane and an exec switch in every wave of every pop; one v_readfirstlane and a scalar branch now)
+                if (uni32(wv) == 0) {                                // pop: the front moves down one lane; what the next pop sees if this one accepts nothing
                     pkey = wave_shl1_u64(pkey); if (lane == 63) pkey = ~(uint64_t)0;
                     nP--;
                     if (lane < 3) S.W[(fb ^ 4u) + lane] = pkey;
@@ -1136,8 +1137,12 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
             else { headN++; c1 = g0 < n1 ? g0 : n1; c2 = g0 < n1 ? (g1 < n1 ? g1 : n1) : (g0 < n2 ? g0 : n2); }
             }
             const long long p0 = PROF ? clock64() : 0;
-            uint32_t id = 0, cntv = 0; bool unv = false;
-            if (ONEG || half == (it & 1)) {
+            uint32_t id = 0, cntv = 0; bool unv = false, below = false;
+            uint64_t bal = 0, balb = 0;
+            // which half this wave belongs to is wave-uniform: taken as a scalar, the role is a scalar branch and the ballots of the expansion
+            // are made inside it, straight from the compare masks - the waves of the hint half have nothing to count
+            const bool expanding = ONEG || uni32(half) == (it & 1u);
+            if (expanding) {
                 if (pk != c) {
                     if (ONEG && nk == c) { pid = nid; pdeg = ndeg; nk = ~(uint64_t)0; }          // its row is here, the hint stage has not seen it
                     else GS_DROW(c);
@@ -1158,6 +1163,10 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
                     unv = !(old & bit);
                     if (unv) cntv = (pst == 2 && pclr) ? pcnt : (uint32_t)matrow[id];   // every 2-byte lookup costs a full HBM sector: only for the unvisited
                 }
+                // how many lanes hit an unvisited node and how many of those are below the worst count of a full R (dmax is INF_CNT until R
+                // is full, so "below" = "unvisited" then)
+                below = unv && cntv < dmax;
+                bal = __ballot(unv); balb = __ballot(below);
             } else if (!ONEG && c1 != ~(uint64_t)0) {
                 if (pk != c1) {
                     pk = c1; pst = 1;
@@ -1174,17 +1183,14 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
                 }
             } else if (!ONEG) pk = ~(uint64_t)0;
             it++;
-            // one barrier per pop: every wave publishes how many of its lanes hit an unvisited node and how many of those are
-            // below the worst count of a full R (dmax is INF_CNT until R is full, so "below" = "unvisited" then)
-            const bool below = unv && cntv < dmax;
-            const uint64_t bal = __ballot(unv), balb = __ballot(below);
+            // one barrier per pop: every wave of the expanding half publishes its two counts (the four words of the other half are not read)
             const long long p1 = PROF ? clock64() : 0;
             uint32_t *ws = S.wsum + ((it & 1) ? 8 : 0);              // double-buffered: the next pop may start before every wave has read
-            if (lane == 0) ws[wv] = (uint32_t)__popcll(bal) | ((uint32_t)__popcll(balb) << 16);
+            if (expanding && lane == 0) ws[wv] = (uint32_t)__popcll(bal) | ((uint32_t)__popcll(balb) << 16);
             // the expanding half now fetches the adjacency of the candidate after next - issued only here, behind the wait for its own
             // lookups, so that wait does not include these loads
             if (!ONEG) {
-                if (half != (it & 1)) {
+                if (expanding) {
                     pk = c2; pst = 1;
                     if (c2 != ~(uint64_t)0) GS_DROW(c2);
                 }
@@ -1208,20 +1214,23 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
             }
             lds_barrier();
             const long long p2 = PROF ? clock64() : 0;
-            // ne <= 2M < 2^16, so the packed words add without carrying into each other. tot: all eight waves; pre: the waves before this one
-            // (packed unvisited | below << 16, for the accept path). One LDS read brings the eight words (lane i of every group of eight holds
-            // word i), three row shifts turn them into running sums: the total sits in lane 7, the prefix is lane wv's sum less its own word -
-            // both taken as scalars at once, so no vector register lives on. (Eight uniform reads summed one by one, and again under the wave's
-            // number for the prefix, were 90 of the ~450 instructions of a wave's pop.) ONEG keeps the word-by-word sums: its SPLIT build sits
-            // at the register limit and paid for the shorter form with two more spilled registers.
+            // ne <= 2M < 2^16, so the packed words add without carrying into each other. tot: all the waves that expanded; pre: those of them before
+            // this one (packed unvisited | below << 16, for the accept path). Two halves: one LDS read brings the four words of the half that expanded,
+            // two row shifts turn them into running sums, total and prefix are taken as scalars at once, so no vector register lives on. (Eight
+            // uniform reads summed one by one, and again under the wave's number for the prefix, were 90 of the ~450 instructions of a wave's pop.)
+            // ONEG, where all eight waves expand and write, keeps the word-by-word sums over the eight words: its SPLIT build sits at the register
+            // limit and paid for a shorter form with two more spilled registers.
             uint32_t tot = 0, pre = 0;
             if (ONEG) {
 #pragma unroll
                 for (int w = 0; w < DT / 64; w++) { const uint32_t x = ws[w]; tot += x; if (w < (int)wv) pre += x; }
             } else {
-                const uint32_t wsw = ws[lane & 7u], wsum8 = row_prefix8(wsw);
-                tot = (uint32_t)__builtin_amdgcn_readlane((int)wsum8, 7);
-                pre = (uint32_t)__builtin_amdgcn_readlane((int)(wsum8 - wsw), (int)uni32(wv));
+                // only the four waves of the half that expanded wrote (it has moved on: that half is (it & 1) ^ 1): lane i of every group of four
+                // reads that half's word i, two row shifts, the total in lane 3. The prefix is only used by lanes that hold an unvisited node
+                // or an accepted key, and those are in the expanding half.
+                const uint32_t wsw = ws[(((it & 1u) ^ 1u) << 2) + (lane & 3u)], wsum4 = row_prefix4(wsw);
+                tot = (uint32_t)__builtin_amdgcn_readlane((int)wsum4, 3);
+                pre = (uint32_t)__builtin_amdgcn_readlane((int)(wsum4 - wsw), (int)(uni32(wv) & 3u));
             }
             const uint32_t ne = tot & 0xFFFFu, B = tot >> 16;
             const long long p3 = PROF ? clock64() : 0;
@@ -1293,7 +1302,7 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
             if (PQ) {
                 if (acc) { hist_add<VLDS>(hs, ci, 1); S.As[aoff + (uint32_t)__popcll(ab & ((1ull << lane) - 1))] = mykey; }
                 lds_barrier();
-                if (wv == 0) {
+                if (uni32(wv) == 0) {
                     // wavefront 0 takes the accepted keys 64 at a time: beyond the fence -> appended to U as they are (one coalesced store); below
                     // it -> into the sorted front, one after the other (position = ballot of "my key is smaller", everything behind moves up one
                     // lane, a full front hands its largest key to U and the fence comes down to the new largest)
@@ -1345,7 +1354,7 @@ __global__ __launch_bounds__(DT, OCC) void k_hnsw_search_dense(IndexDev ix, uint
                 const uint64_t n1 = PQ ? S.W[fbn] : (a0 < c1 ? a0 : c1);
                 const uint64_t n2 = PQ ? S.W[fbn + 1] : (a0 < c1 ? (a1 < c1 ? a1 : c1) : (a0 < c2 ? a0 : c2));
                 if (!ONEG) {
-                    const uint64_t want = half == (it & 1) ? n1 : n2;
+                    const uint64_t want = expanding ? n2 : n1;       // (it has moved on: the half that expanded is the hint half of the next pop)
                     if (want != ~(uint64_t)0 && pk != want) {
                         pk = want; pst = 1;
                         GS_DROW(want);
