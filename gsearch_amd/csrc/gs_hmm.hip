@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <numeric>
+#include <utility>
 #include "gs_internal.hpp"
 #include "gs_spec.hpp"
 
@@ -169,114 +170,291 @@ enum { HMM_ROWS_DEV = 28, HMM_ROW_MM = 20, HMM_ROW_MI = 21, HMM_ROW_MD = 22, HMM
 enum { HMM_BLOCK = 512, HMM_WAVES = HMM_BLOCK / 64, HMM_MAX_WG_PER_PROFILE = 64 };
 struct HmmDesc { uint64_t off; uint32_t M; int32_t tbm; };             // off: first word of the profile's table
 static constexpr int HMM_CLASS_Q[] = {1, 2, 3, 4, 6, 8, 12, 16, 20};       // nodes per lane a kernel is compiled for; a profile runs in the smallest that holds it
-enum { HMM_CLASSES = 9 };
+enum { HMM_CLASSES = sizeof HMM_CLASS_Q / sizeof HMM_CLASS_Q[0] };
+// The class a profile of M nodes runs in, and its HMM_CLASS_Q for device code too (k_hmm_walk): a loop of its own, so that device code compares with
+// constants where HMM_CLASS_Q[hmm_class_of(M)] would look the array up in memory.
+constexpr int hmm_class_of(uint32_t M)
+{
+    for (int c = 0; c < HMM_CLASSES - 1; c++) if ((M + 63) / 64 <= (uint32_t)HMM_CLASS_Q[c]) return c;
+    return HMM_CLASSES - 1;
+}
+__host__ __device__ constexpr int hmm_q_of(uint32_t M)
+{
+    for (int c = 0; c < HMM_CLASSES - 1; c++) if ((M + 63) / 64 <= (uint32_t)HMM_CLASS_Q[c]) return HMM_CLASS_Q[c];
+    return HMM_CLASS_Q[HMM_CLASSES - 1];
+}
+constexpr bool hmm_classes_hold()
+{
+    for (int c = 0; c < HMM_CLASSES; c++) {
+        const uint32_t top = 64u * (uint32_t)HMM_CLASS_Q[c];
+        if (hmm_q_of(top) != HMM_CLASS_Q[c] || hmm_class_of(top) != c) return false;
+        if (c + 1 < HMM_CLASSES && (hmm_q_of(top + 1) != HMM_CLASS_Q[c + 1] || hmm_class_of(top + 1) != c + 1)) return false;
+    }
+    return true;
+}
+static_assert(hmm_classes_hold(), "a profile of 64 Q nodes runs in class Q, one of 64 Q + 1 in the next class");
 static_assert(HMM_CLASS_Q[HMM_CLASSES - 1] * 64 == GS_HMM_MAX_M, "the largest class holds GS_HMM_MAX_M nodes");
 static_assert((size_t)HMM_ROWS_DEV * GS_HMM_MAX_M * 4 <= 160 * 1024, "the largest table fits the LDS of a CU");
 
-__device__ __forceinline__ int hmm_wave_max(int x)      // the maximum over the wavefront, in every lane
+// T of SPEC 13.1 on the host: no entry lies closer than 3.5e-6 to a rounding boundary, so the f64 log2 of any libm gives the same integers
+static uint16_t hmm_lse_entry(uint32_t j) { return (uint16_t)floor(1024.0 * log2(1.0 + exp2(-2.0 * (double)j / 1024.0)) + 0.5); }
+// in LDS T[0 .. 5902] is followed by the 0 that every larger difference reads, so the look-up needs no branch
+enum { HMM_LSE_LDS_N = GS_HMM_LSE_N + 1, HMM_LSE_LDS_BYTES = 2 * HMM_LSE_LDS_N };
+static_assert((size_t)HMM_ROWS_DEV * GS_HMM_MAX_M * 4 + HMM_LSE_LDS_BYTES <= 160 * 1024, "the largest table and T behind it fit the LDS of a CU");
+static_assert(((size_t)HMM_ROWS_DEV * 64 * 4) % 4 == 0, "T starts on a word");
+
+// lse(a, b) of SPEC 13.1. The difference is taken on unsigned words: hi - lo can pass 2^31 (a cell near the top of the range beside one near NEG)
+__device__ __forceinline__ int32_t hmm_lse(int32_t a, int32_t b, const uint16_t *__restrict__ T)
 {
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));       // quad_perm [1,0,3,2]
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));       // quad_perm [2,3,0,1]
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false));      // row_half_mirror
-    x = max(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false));      // row_mirror
-    const int a = __builtin_amdgcn_readlane(x, 0), b = __builtin_amdgcn_readlane(x, 16), c = __builtin_amdgcn_readlane(x, 32),
-              d = __builtin_amdgcn_readlane(x, 48);
-    return max(max(a, b), max(c, d));
+    const int32_t hi = max(a, b), lo = min(a, b);
+    const uint32_t j = min(((uint32_t)hi - (uint32_t)lo + 1u) >> 1, (uint32_t)GS_HMM_LSE_N);
+    return hi + (int32_t)T[j];
 }
 
-// One workgroup per (profile, slice of the records): the profile's table goes to LDS once, then each of its wavefronts takes records
-// order[j], j = its number, its number + the waves of the grid's row, ... (order: longest first, so the waves of a row end together; the loop is
-// bounded by n_rec). Lane l keeps nodes l Q + 1 .. l Q + Q of M, I and D of the current row in registers.
-//   M and I of a row need the row before only: the value a node hands to the next, max(M + tMM, I + tIM, D + tDM), moves up one lane at the group's edge.
-//   D of a row is the max-plus recurrence D[k+1] = max(D[k] + tDD[k], M[k] + tMD[k]) along k. Each lane runs it over its own nodes from NEG (Dloc) and
-//   gets its group as the map x -> max(x + a, b): a = the group's sum of tDD (a constant of the profile, scanned once per record), b = what leaves
-//   the group when nothing enters. Six steps of b = max(b, b(lane - d) + a_d) give every lane what really leaves it, the lane above takes that as
-//   c_in and D[q] = max(Dloc[q], c_in + PDD[q]). Integer max and add: the same words as the serial recurrence, in any order.
-//   E = max_k M[k]: D[k] is some M[j] of the same row plus non-positive transitions, or NEG, so max(M, D) over the row is max M.
+// The three dynamic programs over the cells of a (record, profile) pair. They share one prologue (hmm_stage) and one row loop (hmm_rows) and differ at
+// compile time only, at the points the row loop names.
+enum HmmProg { HMM_VIT, HMM_FWD, HMM_TRACE, HMM_PROGS };
+// what joins alternatives: max (SPEC 13, 13.2) or lse (SPEC 13.1). T is read by lse alone.
+template <HmmProg P> __device__ __forceinline__ int32_t hmm_join(int32_t a, int32_t b, const uint16_t *T)
+{
+    if constexpr (P == HMM_FWD) return hmm_lse(a, b, T); else return max(a, b);
+}
+// The join over the wavefront, in every lane: neighbours, pairs of pairs, ... - for lse the balanced tree of SPEC 13.1. After the two quad steps the four
+// lanes of a quad hold one value, so the mirrors hand a lane the value of the other quad / the other half row; that is the tree because the join is
+// symmetric - a lane and its partner compute join(x, y) and join(y, x).
+template <HmmProg P> __device__ __forceinline__ int hmm_wave_join(int x, const uint16_t *T)
+{
+    x = hmm_join<P>(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false), T);        // quad_perm [1,0,3,2]
+    x = hmm_join<P>(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false), T);        // quad_perm [2,3,0,1]
+    x = hmm_join<P>(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false), T);       // row_half_mirror
+    x = hmm_join<P>(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false), T);       // row_mirror
+    const int a = __builtin_amdgcn_readlane(x, 0), b = __builtin_amdgcn_readlane(x, 16), c = __builtin_amdgcn_readlane(x, 32),
+              d = __builtin_amdgcn_readlane(x, 48);
+    return hmm_join<P>(hmm_join<P>(a, b, T), hmm_join<P>(c, d, T), T);
+}
+
+// ---- trace-back (SPEC 13.2): what the row loop records -----------------------------------------------------------------------------------------
+// A pair of a block: where its back-pointers and its row specials start in the block's scratch, its place in the caller's pair list, its record.
+struct HmmTracePair { uint64_t ptr_off, row_off; uint32_t pair, rec; };           // ptr_off in words, row_off in rows (int4)
+struct HmmTraceProf { uint32_t prof, start, cnt; };                               // the pairs [start, start + cnt) of the call's list belong to prof
+// A cell's pointers are a nibble: bits 0-1 where M[i][k] came from (0 M, 1 I, 2 D of node k - 1 in row i - 1, 3 B[i-1]), bit 2 set: I[i][k] came from
+// I[i-1][k] (clear: M[i-1][k]), bit 3 set: D[i][k] came from D[i][k-1] (clear: M[i][k-1]). A lane's Q nibbles fill NW = ceil(Q / 8) words; word w of
+// lane l in row i lies at ((i - 1) NW + w) 64 + l, so a row is NW bursts of 256 bytes.
+enum { HMM_PTR_B = 3, HMM_ROW_C_FROM_E = 1, HMM_ROW_J_FROM_E = 2, HMM_ROW_B_FROM_N = 4, HMM_WALK_BLOCK = 64 };
+__host__ __device__ constexpr int hmm_ptr_words(int Q) { return (Q + 7) / 8; }
+
+// ---- the shared prologue and row loop -----------------------------------------------------------------------------------------------------------
+// One workgroup per (profile, slice of a list of records): the profile's table goes to LDS once, then each of its wavefronts takes the entries
+// j = its number, its number + the waves of the grid's row, ... of the list (longest record first, so the waves of a row end together). Every kernel
+// bounds that loop by a count that is at most n_rec, and a workgroup whose slice of a selected list is empty returns before it loads anything.
+// Lane l keeps nodes l Q + 1 .. l Q + Q of M, I and D of the current row in registers; 64 residues are loaded at a time, the next 64 while these run.
+//   M and I of a row need the row before only: the value a node hands to the next, join(M + tMM, I + tIM, D + tDM), moves up one lane at the group's edge.
+//   D of a row is the recurrence D[k+1] = join(D[k] + tDD[k], M[k] + tMD[k]) along k. Each lane runs it over its own nodes from NEG (Dloc) and
+//   gets its group as the map x -> join(x + a, b): a = the group's sum of tDD (a constant of the profile, scanned once per workgroup), b = what leaves
+//   the group when nothing enters. Six steps of b = join(b, b(lane - d) + a_d) give every lane what really leaves it, the lane above takes that as
+//   c_in and D[q] = join(Dloc[q], c_in + PDD[q]).
+// Viterbi (SPEC 13): integer max and add, the same words as the serial recurrence in any order. In the scan a lane below 2^s gets its own b back
+//   (b + a <= b), so the step needs no select. E = max_k M[k] needs M alone: D[k] is some M[j] of the same row plus non-positive transitions, or NEG,
+//   so max(M, D) over the row is max M. Up to Q = 16 the eight transition rows of a lane stay in registers across rows (8 Q of them); at 20 they do
+//   not fit beside the 3 Q states, and a compiler barrier keeps the compiler from holding some and spilling others: every row reads them from LDS again.
+// Forward (SPEC 13.1): every join is hmm_lse, a gather from T, which sits in LDS behind the profile's table. lse is not associative, so the order of
+//   the row loop IS the score: D inside a lane from NEG, six scan steps in which a lane below 2^s keeps its b by a select (lse(b, b + a) is more than
+//   b), then c_in from the lane below; D is clamped at NEG, and E folds M and D of a lane's nodes in node order and joins the lanes through
+//   hmm_wave_join. The barrier starts at Q = 12: beside 3 Q states, Q give values and the lse temporaries the transition rows do not fit.
+// Trace (SPEC 13.2): Viterbi, and beyond the score every row leaves the nibbles of its cells and, through lane 0, {E[i], B[i], the lowest k with
+//   M[i][k] == E[i], the decisions of C[i], J[i] and B[i]}; row 0 is {NEG, tmove, 0, B from N}. The barrier starts at Q = 12, as Forward's does.
+//   The M pointer of node k + 1 is decided in the lane of node k: give = max(a, b, c) there, and the first of a, b, c, entry that equals
+//   max(give, entry) is the first of a, b, c that equals give when give >= entry, else the entry. The code of a lane's last node moves up one lane
+//   together with the D decision of the next lane's first node (M + tMD of the last node == what leaves the lane after the scan), in one word.
+//   The D pointers inside a lane are taken after D is final. No traced cell is at the clamp (SPEC 13.2), so an equality that a clamped cell decides
+//   differently is never followed.
+template <int Q> struct HmmLane {
+    const int32_t *ms, *tMM, *tMI, *tMD, *tIM, *tII, *tDM, *tDD, *PDD;  // the lane's Q words of match row 0, of the transition rows and of PDD, in LDS
+    const uint16_t *T;                                      // the table of lse in LDS (Forward)
+    int32_t a_step[6], tbm;                                 // a of the lanes a scan step joins: sums of tDD, at least 1280 * GS_HMM_STAR; A_l(s) of SPEC 13.1
+    int lane, wave, nvalid;                                 // nvalid: how many of the lane's nodes are nodes of the profile
+};
+template <int Q, bool LSE>
+__device__ __forceinline__ HmmLane<Q> hmm_stage(const int32_t *tables, const HmmDesc d, const uint16_t *lse_tab)
+{
+    extern __shared__ int32_t hmm_lds[];
+    constexpr int MP = 64 * Q;
+    uint16_t *Tw = (uint16_t *)(hmm_lds + HMM_ROWS_DEV * MP);
+    for (int i = (int)threadIdx.x; i < HMM_ROWS_DEV * MP; i += HMM_BLOCK) hmm_lds[i] = tables[d.off + i];
+    if constexpr (LSE) for (int i = (int)threadIdx.x; i < HMM_LSE_LDS_N; i += HMM_BLOCK) Tw[i] = lse_tab[i];
+    __syncthreads();
+    HmmLane<Q> ln;
+    ln.lane = (int)threadIdx.x & 63; ln.wave = (int)threadIdx.x >> 6;
+    const int base = ln.lane * Q;
+    ln.nvalid = min(max((int)d.M - base, 0), Q);
+    ln.tbm = d.tbm; ln.T = Tw;
+    ln.ms = hmm_lds + base;
+    ln.tMM = hmm_lds + HMM_ROW_MM * MP + base; ln.tMI = hmm_lds + HMM_ROW_MI * MP + base; ln.tMD = hmm_lds + HMM_ROW_MD * MP + base;
+    ln.tIM = hmm_lds + HMM_ROW_IM * MP + base; ln.tII = hmm_lds + HMM_ROW_II * MP + base; ln.tDM = hmm_lds + HMM_ROW_DM * MP + base;
+    ln.tDD = hmm_lds + HMM_ROW_DD * MP + base; ln.PDD = hmm_lds + HMM_ROW_PDD * MP + base;
+    int32_t a = ln.PDD[Q - 1] + ln.tDD[Q - 1];
+    for (int s = 0; s < 6; s++) {
+        ln.a_step[s] = a;
+        const int32_t up = __shfl_up(a, 1 << s);
+        if (ln.lane >= (1 << s)) a += up;
+    }
+    return ln;
+}
+
+// The rows of one record against the staged profile: the raw score in every lane, GS_HMM_NO_SCORE for an empty record or a byte that is no residue.
+// Trace also writes the record's pointer words to pp (the lane's column) and its row specials to rr. x, pp and rr carry no __restrict__ and ln comes by
+// value: either costs some trace instances registers and a wave per SIMD, at the same instruction counts (NOTES.md).
+template <int Q, HmmProg P>
+__device__ __forceinline__ int32_t hmm_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, uint32_t *pp, int4 *rr)
+{
+    constexpr int MP = 64 * Q, NW = hmm_ptr_words(Q);
+    constexpr bool FWD = P == HMM_FWD, TRACE = P == HMM_TRACE;
+    constexpr int RELOAD_FROM_Q = P == HMM_VIT ? 20 : 12;     // from here the transition rows are read from LDS in every row (above)
+    const uint16_t *T = ln.T;
+    const int lane = ln.lane, nvalid = ln.nvalid;
+    if (!TRACE && L == 0) return GS_HMM_NO_SCORE;             // (the host puts no empty record on a trace list)
+    const HmmSpecials sp = hmm_specials(L);
+    int32_t Mv[Q], Iv[Q], Dv[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
+    int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
+    if constexpr (TRACE) if (lane == 0) rr[0] = make_int4(GS_HMM_NEG, B, 0, HMM_ROW_B_FROM_N);
+    bool bad = false;
+    int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
+    for (uint32_t i0 = 0; i0 < L; i0 += 64) {
+        const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;     // the next 64 residues are on their way while these run
+        bad |= cur < 0;
+        const int res = max(cur, 0);
+        const int cnt = (int)min(64u, L - i0);
+        for (int t = 0; t < cnt; t++) {
+            if (Q >= RELOAD_FROM_Q) asm volatile("" ::: "memory");
+            const int32_t *ms = ln.ms + __builtin_amdgcn_readlane(res, t) * MP;
+            const int32_t entry = B + ln.tbm;
+            uint32_t pk[NW], code_out = HMM_PTR_B;            // trace: the row's nibbles, and the M pointer of the next lane's first node
+#pragma unroll
+            for (int w = 0; w < NW; w++) pk[w] = 0;
+            int32_t give[Q];
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const int32_t a = Mv[q] + ln.tMM[q], b = Iv[q] + ln.tIM[q], c = Dv[q] + ln.tDM[q];
+                const int32_t g = hmm_join<P>(hmm_join<P>(a, b, T), c, T);
+                give[q] = g;
+                if constexpr (TRACE) {
+                    const uint32_t code = g >= entry ? (a == g ? 0u : (b == g ? 1u : 2u)) : (uint32_t)HMM_PTR_B;
+                    if (q + 1 < Q) pk[(q + 1) >> 3] |= code << (4 * ((q + 1) & 7)); else code_out = code;
+                }
+            }
+            int32_t up = __shfl_up(give[Q - 1], 1);
+            if (lane == 0) up = GS_HMM_NEG;                   // node 0 has no states: B + tBM is far above NEG
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const int32_t fromM = Mv[q] + ln.tMI[q];
+                Iv[q] = max(hmm_join<P>(fromM, Iv[q] + ln.tII[q], T), GS_HMM_NEG);
+                if constexpr (TRACE) pk[q >> 3] |= (fromM == Iv[q] ? 0u : 4u) << (4 * (q & 7));
+            }
+#pragma unroll
+            for (int q = 0; q < Q; q++) Mv[q] = max(ms[q] + hmm_join<P>(q ? give[q - 1] : up, entry, T), GS_HMM_NEG);
+            int32_t dl = GS_HMM_NEG;
+            Dv[0] = dl;
+#pragma unroll
+            for (int q = 1; q < Q; q++) { dl = max(hmm_join<P>(dl + ln.tDD[q - 1], Mv[q - 1] + ln.tMD[q - 1], T), GS_HMM_NEG); Dv[q] = dl; }
+            const int32_t m_out = Mv[Q - 1] + ln.tMD[Q - 1];
+            int32_t b = max(hmm_join<P>(dl + ln.tDD[Q - 1], m_out, T), GS_HMM_NEG);
+#pragma unroll
+            for (int s = 0; s < 6; s++) {                     // the scan step: Forward's select and clamp
+                const int32_t nb = hmm_join<P>(b, __shfl_up(b, 1 << s) + ln.a_step[s], T);
+                if constexpr (FWD) b = lane >= (1 << s) ? max(nb, GS_HMM_NEG) : b; else b = nb;
+            }
+            int32_t c_in = __shfl_up(b, 1);
+            if (lane == 0) c_in = GS_HMM_NEG;
+            if constexpr (TRACE) {
+                uint32_t edge = (uint32_t)__shfl_up((int)(code_out | (m_out == b ? 0u : 8u)), 1);
+                if (lane == 0) edge = HMM_PTR_B | 8u;
+                pk[0] |= edge;
+            }
+            int32_t e = GS_HMM_NEG;
+#pragma unroll
+            for (int q = 0; q < Q; q++) {                     // D final and the E fold: Forward clamps D and folds it into E
+                Dv[q] = hmm_join<P>(Dv[q], c_in + ln.PDD[q], T);
+                if constexpr (FWD) Dv[q] = max(Dv[q], GS_HMM_NEG);
+                if constexpr (TRACE) if (q >= 1) pk[q >> 3] |= (Mv[q - 1] + ln.tMD[q - 1] == Dv[q] ? 0u : 8u) << (4 * (q & 7));
+                int32_t e2 = hmm_join<P>(e, Mv[q], T);
+                if constexpr (FWD) e2 = hmm_join<P>(e2, Dv[q], T);
+                e = q < nvalid ? e2 : e;
+            }
+            const int32_t E = hmm_wave_join<P>(e, T);
+            const uint32_t row = i0 + (uint32_t)t;            // row i = row + 1
+            int kE = 0;
+            if constexpr (TRACE) {
+#pragma unroll
+                for (int w = 0; w < NW; w++) pp[((uint64_t)row * NW + w) * 64] = pk[w];
+                // the lowest node of the row's maximum: the first lane that holds it, and that lane's first node
+                int first = 0;
+#pragma unroll
+                for (int q = Q - 1; q >= 0; q--) if (q < nvalid && Mv[q] == E) first = q;
+                const int fl = __ffsll((unsigned long long)__ballot(e == E)) - 1;     // some lane holds it: E is the maximum of the e
+                kE = fl * Q + __builtin_amdgcn_readlane(first, fl) + 1;
+            }
+            N += sp.tloop;
+            const int32_t Jn = max(hmm_join<P>(J + sp.tloop, E + GS_HMM_TEJ, T), GS_HMM_NEG), Cn = max(hmm_join<P>(C + sp.tloop, E + GS_HMM_TEJ, T), GS_HMM_NEG);
+            const int flags = (E + GS_HMM_TEJ == Cn ? HMM_ROW_C_FROM_E : 0) | (E + GS_HMM_TEJ == Jn ? HMM_ROW_J_FROM_E : 0) | (N >= Jn ? HMM_ROW_B_FROM_N : 0);
+            J = Jn; C = Cn;
+            B = hmm_join<P>(N, J, T) + sp.tmove;
+            if constexpr (TRACE) if (lane == 0) rr[row + 1] = make_int4(E, B, kE, flags);
+        }
+        cur = nxt;
+    }
+    return __any(bad) ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
+}
+
+// Viterbi score of every record against the profiles plist[] of one class: a wavefront takes the records order[j] (all n_rec of them, longest first)
 template <int Q>
 __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_viterbi(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const uint32_t *__restrict__ plist,
                                                            const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
                                                            const uint32_t *__restrict__ order, uint32_t n_rec, uint32_t n_prof, int32_t *__restrict__ score)
 {
-    extern __shared__ int32_t hmm_lds[];
-    constexpr int MP = 64 * Q;
     const uint32_t p = plist[blockIdx.y];
-    const HmmDesc d = desc[p];
-    for (int i = (int)threadIdx.x; i < HMM_ROWS_DEV * MP; i += HMM_BLOCK) hmm_lds[i] = tables[d.off + i];
-    __syncthreads();
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int base = lane * Q;
-    const int nvalid = min(max((int)d.M - base, 0), Q);
-    const int32_t *tMM = hmm_lds + HMM_ROW_MM * MP + base, *tMI = hmm_lds + HMM_ROW_MI * MP + base, *tMD = hmm_lds + HMM_ROW_MD * MP + base,
-                  *tIM = hmm_lds + HMM_ROW_IM * MP + base, *tII = hmm_lds + HMM_ROW_II * MP + base, *tDM = hmm_lds + HMM_ROW_DM * MP + base,
-                  *tDD = hmm_lds + HMM_ROW_DD * MP + base, *PDD = hmm_lds + HMM_ROW_PDD * MP + base;
-    int32_t a_step[6];                                      // a of the lanes a scan step joins: sums of tDD, at least 1280 * GS_HMM_STAR
-    {
-        int32_t a = PDD[Q - 1] + tDD[Q - 1];
-        for (int s = 0; s < 6; s++) {
-            a_step[s] = a;
-            const int32_t up = __shfl_up(a, 1 << s);
-            if (lane >= (1 << s)) a += up;
-        }
-    }
-    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)wave; j < n_rec; j += gridDim.x * HMM_WAVES) {
+    const HmmLane<Q> ln = hmm_stage<Q, false>(tables, desc[p], nullptr);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < n_rec; j += gridDim.x * HMM_WAVES) {
         const uint32_t r = order[j];
-        const uint32_t L = (uint32_t)rec_len[r];
-        const uint8_t *x = aa + rec_start[r];
-        int32_t *out = score + (uint64_t)r * n_prof + p;
-        if (L == 0) { if (lane == 0) *out = GS_HMM_NO_SCORE; continue; }
-        const HmmSpecials sp = hmm_specials(L);
-        int32_t Mv[Q], Iv[Q], Dv[Q];
-#pragma unroll
-        for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
-        int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
-        bool bad = false;
-        int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
-        for (uint32_t i0 = 0; i0 < L; i0 += 64) {
-            const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;     // the next 64 residues are on their way while these run
-            bad |= cur < 0;
-            const int res = max(cur, 0);
-            const int cnt = (int)min(64u, L - i0);
-            for (int t = 0; t < cnt; t++) {
-                // up to Q = 16 the eight transition rows of a lane stay in registers across rows (8 Q of them); at 20 they do not fit beside the
-                // 3 Q states, and this keeps the compiler from holding some and spilling others: every row reads them from LDS again
-                if (Q > 16) asm volatile("" ::: "memory");
-                const int32_t *ms = hmm_lds + __builtin_amdgcn_readlane(res, t) * MP + base;
-                const int32_t entry = B + d.tbm;
-                int32_t give[Q];
-#pragma unroll
-                for (int q = 0; q < Q; q++) give[q] = max(max(Mv[q] + tMM[q], Iv[q] + tIM[q]), Dv[q] + tDM[q]);
-                int32_t up = __shfl_up(give[Q - 1], 1);
-                if (lane == 0) up = GS_HMM_NEG;             // node 0 has no states: B + tBM is far above NEG
-#pragma unroll
-                for (int q = 0; q < Q; q++) Iv[q] = max(max(Mv[q] + tMI[q], Iv[q] + tII[q]), GS_HMM_NEG);
-#pragma unroll
-                for (int q = 0; q < Q; q++) Mv[q] = max(ms[q] + max(q ? give[q - 1] : up, entry), GS_HMM_NEG);
-                int32_t dl = GS_HMM_NEG;
-                Dv[0] = dl;
-#pragma unroll
-                for (int q = 1; q < Q; q++) { dl = max(max(dl + tDD[q - 1], Mv[q - 1] + tMD[q - 1]), GS_HMM_NEG); Dv[q] = dl; }
-                int32_t b = max(max(dl + tDD[Q - 1], Mv[Q - 1] + tMD[Q - 1]), GS_HMM_NEG);
-#pragma unroll
-                for (int s = 0; s < 6; s++) b = max(b, __shfl_up(b, 1 << s) + a_step[s]);     // a lane below 2^s gets its own b back: b + a <= b
-                int32_t c_in = __shfl_up(b, 1);
-                if (lane == 0) c_in = GS_HMM_NEG;
-                int32_t e = GS_HMM_NEG;
-#pragma unroll
-                for (int q = 0; q < Q; q++) {
-                    Dv[q] = max(Dv[q], c_in + PDD[q]);
-                    if (q < nvalid) e = max(e, Mv[q]);
-                }
-                const int32_t E = hmm_wave_max(e);
-                N += sp.tloop;
-                J = max(max(J + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
-                C = max(max(C + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
-                B = max(N, J) + sp.tmove;
-            }
-            cur = nxt;
-        }
-        const bool any_bad = __any(bad);
-        if (lane == 0) *out = any_bad ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
+        const int32_t raw = hmm_rows<Q, HMM_VIT>(ln, aa + rec_start[r], (uint32_t)rec_len[r], nullptr, nullptr);
+        if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
+    }
+}
+
+// Forward score of the records sel[p][0 .. sel_cnt[p]) of each profile of plist[]
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_forward(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const uint32_t *__restrict__ plist,
+                                                           const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start,
+                                                           const uint64_t *__restrict__ rec_len, const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sel_cnt,
+                                                           uint32_t n_rec, uint32_t n_prof, int32_t *__restrict__ score)
+{
+    const uint32_t p = plist[blockIdx.y];
+    const uint32_t cnt = min(sel_cnt[p], n_rec);
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= cnt) return;
+    const HmmLane<Q> ln = hmm_stage<Q, true>(tables, desc[p], lse_tab);
+    const uint32_t *list = sel + (uint64_t)p * n_rec;
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < cnt; j += gridDim.x * HMM_WAVES) {
+        const uint32_t r = list[j];
+        const int32_t raw = hmm_rows<Q, HMM_FWD>(ln, aa + rec_start[r], (uint32_t)rec_len[r], nullptr, nullptr);
+        if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
+    }
+}
+
+// Viterbi score, back-pointers and row specials of the pairs of each profile of profs[]; 1 <= L <= GS_HMM_TRACE_MAX_L: the host put no other pair on a list
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_trace(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                         const HmmTracePair *__restrict__ pairs, const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start,
+                                                         const uint64_t *__restrict__ rec_len, uint32_t *__restrict__ ptrs, int4 *__restrict__ rows,
+                                                         int32_t *__restrict__ raw_out)
+{
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmLane<Q> ln = hmm_stage<Q, false>(tables, desc[tp.prof], nullptr);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const int32_t raw = hmm_rows<Q, HMM_TRACE>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], ptrs + pr.ptr_off + ln.lane, rows + pr.row_off);
+        if (ln.lane == 0) raw_out[pr.pair] = raw;
     }
 }
 
@@ -297,35 +475,6 @@ __global__ __launch_bounds__(256) void k_hmm_best(const int32_t *__restrict__ sc
     }
     best_rec[i] = br;
     best_score[i] = bs;
-}
-
-// ---- Forward (SPEC 13.1) ------------------------------------------------------------------------------------------------------------------------
-// T of SPEC 13.1 on the host: no entry lies closer than 3.5e-6 to a rounding boundary, so the f64 log2 of any libm gives the same integers
-static uint16_t hmm_lse_entry(uint32_t j) { return (uint16_t)floor(1024.0 * log2(1.0 + exp2(-2.0 * (double)j / 1024.0)) + 0.5); }
-// in LDS T[0 .. 5902] is followed by the 0 that every larger difference reads, so the look-up needs no branch
-enum { HMM_LSE_LDS_N = GS_HMM_LSE_N + 1, HMM_LSE_LDS_BYTES = 2 * HMM_LSE_LDS_N };
-static_assert((size_t)HMM_ROWS_DEV * GS_HMM_MAX_M * 4 + HMM_LSE_LDS_BYTES <= 160 * 1024, "the largest table and T behind it fit the LDS of a CU");
-static_assert(((size_t)HMM_ROWS_DEV * 64 * 4) % 4 == 0, "T starts on a word");
-
-// lse(a, b) of SPEC 13.1. The difference is taken on unsigned words: hi - lo can pass 2^31 (a cell near the top of the range beside one near NEG)
-__device__ __forceinline__ int32_t hmm_lse(int32_t a, int32_t b, const uint16_t *__restrict__ T)
-{
-    const int32_t hi = max(a, b), lo = min(a, b);
-    const uint32_t j = min(((uint32_t)hi - (uint32_t)lo + 1u) >> 1, (uint32_t)GS_HMM_LSE_N);
-    return hi + (int32_t)T[j];
-}
-// lse over the wavefront in every lane, as the balanced tree of SPEC 13.1 (neighbours, pairs of pairs, ...): the step pattern of hmm_wave_max. After the
-// two quad steps the four lanes of a quad hold one value, so the mirrors hand a lane the value of the other quad / the other half row; that is the
-// tree because lse is symmetric - a lane and its partner compute lse(x, y) and lse(y, x).
-__device__ __forceinline__ int hmm_wave_lse(int x, const uint16_t *__restrict__ T)
-{
-    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false), T);        // quad_perm [1,0,3,2]
-    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false), T);        // quad_perm [2,3,0,1]
-    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0x141, 0xF, 0xF, false), T);       // row_half_mirror
-    x = hmm_lse(x, __builtin_amdgcn_update_dpp(x, x, 0x140, 0xF, 0xF, false), T);       // row_mirror
-    const int a = __builtin_amdgcn_readlane(x, 0), b = __builtin_amdgcn_readlane(x, 16), c = __builtin_amdgcn_readlane(x, 32),
-              d = __builtin_amdgcn_readlane(x, 48);
-    return hmm_lse(hmm_lse(a, b, T), hmm_lse(c, d, T), T);
 }
 
 // Per profile the records whose Viterbi score reaches the profile's floor, in the order of `order` (longest first), and their number. One workgroup per
@@ -366,248 +515,6 @@ __global__ __launch_bounds__(256) void k_hmm_fill(int32_t *__restrict__ out, uin
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) out[i] = v;
-}
-
-// The geometry of k_hmm_viterbi, the arithmetic of SPEC 13.1: every max that joins alternatives is hmm_lse, a gather from T, which sits in LDS behind
-// the profile's table. A wavefront takes the records sel[p][j] of its profile's list, j = its number, its number + the waves of the grid's row, ...;
-// the loop is bounded by cnt[p] <= n_rec, and a workgroup with no record of its own returns before it loads anything.
-//   lse is not associative, so the order below IS the score: D inside a lane from NEG, six scan steps in which a lane below 2^s keeps its b (with max
-//   it would get its own b back; lse(b, b + a) is more than b), then c_in from the lane below; E folds M and D of a lane's nodes in node order and joins
-//   the lanes through hmm_wave_lse.
-//   From Q = 12 the transition rows are read from LDS in every row: beside 3 Q states, Q give values and the lse temporaries they do not fit.
-template <int Q>
-__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_forward(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const uint32_t *__restrict__ plist,
-                                                           const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start,
-                                                           const uint64_t *__restrict__ rec_len, const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sel_cnt,
-                                                           uint32_t n_rec, uint32_t n_prof, int32_t *__restrict__ score)
-{
-    extern __shared__ int32_t hmm_lds[];
-    constexpr int MP = 64 * Q;
-    const uint32_t p = plist[blockIdx.y];
-    const uint32_t cnt = min(sel_cnt[p], n_rec);
-    if ((uint64_t)blockIdx.x * HMM_WAVES >= cnt) return;
-    const HmmDesc d = desc[p];
-    uint16_t *Tw = (uint16_t *)(hmm_lds + HMM_ROWS_DEV * MP);
-    for (int i = (int)threadIdx.x; i < HMM_ROWS_DEV * MP; i += HMM_BLOCK) hmm_lds[i] = tables[d.off + i];
-    for (int i = (int)threadIdx.x; i < HMM_LSE_LDS_N; i += HMM_BLOCK) Tw[i] = lse_tab[i];
-    __syncthreads();
-    const uint16_t *T = Tw;
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int base = lane * Q;
-    const int nvalid = min(max((int)d.M - base, 0), Q);
-    const int32_t *tMM = hmm_lds + HMM_ROW_MM * MP + base, *tMI = hmm_lds + HMM_ROW_MI * MP + base, *tMD = hmm_lds + HMM_ROW_MD * MP + base,
-                  *tIM = hmm_lds + HMM_ROW_IM * MP + base, *tII = hmm_lds + HMM_ROW_II * MP + base, *tDM = hmm_lds + HMM_ROW_DM * MP + base,
-                  *tDD = hmm_lds + HMM_ROW_DD * MP + base, *PDD = hmm_lds + HMM_ROW_PDD * MP + base;
-    int32_t a_step[6];                                      // A_l(s) of SPEC 13.1 in the lanes l >= 2^s, the only ones that use it
-    {
-        int32_t a = PDD[Q - 1] + tDD[Q - 1];
-        for (int s = 0; s < 6; s++) {
-            a_step[s] = a;
-            const int32_t up = __shfl_up(a, 1 << s);
-            if (lane >= (1 << s)) a += up;
-        }
-    }
-    const uint32_t *list = sel + (uint64_t)p * n_rec;
-    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)wave; j < cnt; j += gridDim.x * HMM_WAVES) {
-        const uint32_t r = list[j];
-        const uint32_t L = (uint32_t)rec_len[r];
-        const uint8_t *x = aa + rec_start[r];
-        int32_t *out = score + (uint64_t)r * n_prof + p;
-        if (L == 0) { if (lane == 0) *out = GS_HMM_NO_SCORE; continue; }
-        const HmmSpecials sp = hmm_specials(L);
-        int32_t Mv[Q], Iv[Q], Dv[Q];
-#pragma unroll
-        for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
-        int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
-        bool bad = false;
-        int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
-        for (uint32_t i0 = 0; i0 < L; i0 += 64) {
-            const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;
-            bad |= cur < 0;
-            const int res = max(cur, 0);
-            const int cnt_i = (int)min(64u, L - i0);
-            for (int t = 0; t < cnt_i; t++) {
-                if (Q >= 12) asm volatile("" ::: "memory");
-                const int32_t *ms = hmm_lds + __builtin_amdgcn_readlane(res, t) * MP + base;
-                const int32_t entry = B + d.tbm;
-                int32_t give[Q];
-#pragma unroll
-                for (int q = 0; q < Q; q++) give[q] = hmm_lse(hmm_lse(Mv[q] + tMM[q], Iv[q] + tIM[q], T), Dv[q] + tDM[q], T);
-                int32_t up = __shfl_up(give[Q - 1], 1);
-                if (lane == 0) up = GS_HMM_NEG;
-#pragma unroll
-                for (int q = 0; q < Q; q++) Iv[q] = max(hmm_lse(Mv[q] + tMI[q], Iv[q] + tII[q], T), GS_HMM_NEG);
-#pragma unroll
-                for (int q = 0; q < Q; q++) Mv[q] = max(ms[q] + hmm_lse(q ? give[q - 1] : up, entry, T), GS_HMM_NEG);
-                int32_t dl = GS_HMM_NEG;
-                Dv[0] = dl;
-#pragma unroll
-                for (int q = 1; q < Q; q++) { dl = max(hmm_lse(dl + tDD[q - 1], Mv[q - 1] + tMD[q - 1], T), GS_HMM_NEG); Dv[q] = dl; }
-                int32_t b = max(hmm_lse(dl + tDD[Q - 1], Mv[Q - 1] + tMD[Q - 1], T), GS_HMM_NEG);
-#pragma unroll
-                for (int s = 0; s < 6; s++) {
-                    const int32_t nb = max(hmm_lse(b, __shfl_up(b, 1 << s) + a_step[s], T), GS_HMM_NEG);
-                    b = lane >= (1 << s) ? nb : b;
-                }
-                int32_t c_in = __shfl_up(b, 1);
-                if (lane == 0) c_in = GS_HMM_NEG;
-                int32_t e = GS_HMM_NEG;
-#pragma unroll
-                for (int q = 0; q < Q; q++) {
-                    Dv[q] = max(hmm_lse(Dv[q], c_in + PDD[q], T), GS_HMM_NEG);
-                    const int32_t e2 = hmm_lse(hmm_lse(e, Mv[q], T), Dv[q], T);
-                    e = q < nvalid ? e2 : e;
-                }
-                const int32_t E = hmm_wave_lse(e, T);
-                N += sp.tloop;
-                J = max(hmm_lse(J + sp.tloop, E + GS_HMM_TEJ, T), GS_HMM_NEG);
-                C = max(hmm_lse(C + sp.tloop, E + GS_HMM_TEJ, T), GS_HMM_NEG);
-                B = hmm_lse(N, J, T) + sp.tmove;
-            }
-            cur = nxt;
-        }
-        const bool any_bad = __any(bad);
-        if (lane == 0) *out = any_bad ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
-    }
-}
-
-// ---- trace-back (SPEC 13.2) ---------------------------------------------------------------------------------------------------------------------
-// A pair of a block: where its back-pointers and its row specials start in the block's scratch, its place in the caller's pair list, its record.
-struct HmmTracePair { uint64_t ptr_off, row_off; uint32_t pair, rec; };           // ptr_off in words, row_off in rows (int4)
-struct HmmTraceProf { uint32_t prof, start, cnt; };                               // the pairs [start, start + cnt) of the call's list belong to prof
-// A cell's pointers are a nibble: bits 0-1 where M[i][k] came from (0 M, 1 I, 2 D of node k - 1 in row i - 1, 3 B[i-1]), bit 2 set: I[i][k] came from
-// I[i-1][k] (clear: M[i-1][k]), bit 3 set: D[i][k] came from D[i][k-1] (clear: M[i][k-1]). A lane's Q nibbles fill NW = ceil(Q / 8) words; word w of
-// lane l in row i lies at ((i - 1) NW + w) 64 + l, so a row is NW bursts of 256 bytes.
-enum { HMM_PTR_B = 3, HMM_ROW_C_FROM_E = 1, HMM_ROW_J_FROM_E = 2, HMM_ROW_B_FROM_N = 4, HMM_WALK_BLOCK = 64 };
-__host__ __device__ constexpr int hmm_ptr_words(int Q) { return (Q + 7) / 8; }
-// HMM_CLASS_Q of the class a profile of M nodes runs in, for device code
-__host__ __device__ constexpr int hmm_q_of(uint32_t M)
-{
-    const uint32_t g = (M + 63) / 64;
-    return g <= 1 ? 1 : (g <= 4 ? (int)g : (g <= 6 ? 6 : (g <= 8 ? 8 : (g <= 12 ? 12 : (g <= 16 ? 16 : 20)))));
-}
-
-// k_hmm_viterbi's geometry and row loop; a wavefront takes the pairs of its profile's list in turn. Beyond the score every row leaves the nibbles of
-// its cells and, through lane 0, {E[i], B[i], the lowest k with M[i][k] == E[i], the decisions of C[i], J[i] and B[i]}; row 0 is {NEG, tmove, 0, B from N}.
-//   The M pointer of node k + 1 is decided in the lane of node k: give = max(a, b, c) there, and the first of a, b, c, entry that equals
-//   max(give, entry) is the first of a, b, c that equals give when give >= entry, else the entry. The code of a lane's last node moves up one lane
-//   together with the D decision of the next lane's first node (M + tMD of the last node == what leaves the lane after the scan), in one word.
-//   No traced cell is at the clamp (SPEC 13.2), so an equality that a clamped cell decides differently is never followed.
-template <int Q>
-__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_trace(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
-                                                         const HmmTracePair *__restrict__ pairs, const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start,
-                                                         const uint64_t *__restrict__ rec_len, uint32_t *__restrict__ ptrs, int4 *__restrict__ rows,
-                                                         int32_t *__restrict__ raw_out)
-{
-    extern __shared__ int32_t hmm_lds[];
-    constexpr int MP = 64 * Q, NW = hmm_ptr_words(Q);
-    const HmmTraceProf tp = profs[blockIdx.y];
-    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
-    const HmmDesc d = desc[tp.prof];
-    for (int i = (int)threadIdx.x; i < HMM_ROWS_DEV * MP; i += HMM_BLOCK) hmm_lds[i] = tables[d.off + i];
-    __syncthreads();
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    const int base = lane * Q;
-    const int nvalid = min(max((int)d.M - base, 0), Q);
-    const int32_t *tMM = hmm_lds + HMM_ROW_MM * MP + base, *tMI = hmm_lds + HMM_ROW_MI * MP + base, *tMD = hmm_lds + HMM_ROW_MD * MP + base,
-                  *tIM = hmm_lds + HMM_ROW_IM * MP + base, *tII = hmm_lds + HMM_ROW_II * MP + base, *tDM = hmm_lds + HMM_ROW_DM * MP + base,
-                  *tDD = hmm_lds + HMM_ROW_DD * MP + base, *PDD = hmm_lds + HMM_ROW_PDD * MP + base;
-    int32_t a_step[6];
-    {
-        int32_t a = PDD[Q - 1] + tDD[Q - 1];
-        for (int s = 0; s < 6; s++) {
-            a_step[s] = a;
-            const int32_t up = __shfl_up(a, 1 << s);
-            if (lane >= (1 << s)) a += up;
-        }
-    }
-    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
-        const HmmTracePair pr = pairs[tp.start + j];
-        const uint32_t L = (uint32_t)rec_len[pr.rec];              // 1 <= L <= GS_HMM_TRACE_MAX_L: the host put no other pair on a list
-        const uint8_t *x = aa + rec_start[pr.rec];
-        uint32_t *pp = ptrs + pr.ptr_off + lane;
-        int4 *rr = rows + pr.row_off;
-        const HmmSpecials sp = hmm_specials(L);
-        int32_t Mv[Q], Iv[Q], Dv[Q];
-#pragma unroll
-        for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
-        int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
-        if (lane == 0) rr[0] = make_int4(GS_HMM_NEG, B, 0, HMM_ROW_B_FROM_N);
-        bool bad = false;
-        int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
-        for (uint32_t i0 = 0; i0 < L; i0 += 64) {
-            const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;
-            bad |= cur < 0;
-            const int res = max(cur, 0);
-            const int cnt = (int)min(64u, L - i0);
-            for (int t = 0; t < cnt; t++) {
-                if (Q >= 12) asm volatile("" ::: "memory");      // the transition rows are read from LDS in every row: see k_hmm_forward
-                const int32_t *ms = hmm_lds + __builtin_amdgcn_readlane(res, t) * MP + base;
-                const int32_t entry = B + d.tbm;
-                uint32_t pk[NW];
-#pragma unroll
-                for (int w = 0; w < NW; w++) pk[w] = 0;
-                int32_t give[Q];
-                uint32_t code_out = HMM_PTR_B;                   // the M pointer of the next lane's first node
-#pragma unroll
-                for (int q = 0; q < Q; q++) {
-                    const int32_t a = Mv[q] + tMM[q], b = Iv[q] + tIM[q], c = Dv[q] + tDM[q];
-                    const int32_t g = max(max(a, b), c);
-                    give[q] = g;
-                    const uint32_t code = g >= entry ? (a == g ? 0u : (b == g ? 1u : 2u)) : (uint32_t)HMM_PTR_B;
-                    if (q + 1 < Q) pk[(q + 1) >> 3] |= code << (4 * ((q + 1) & 7)); else code_out = code;
-                }
-                int32_t up = __shfl_up(give[Q - 1], 1);
-                if (lane == 0) up = GS_HMM_NEG;
-#pragma unroll
-                for (int q = 0; q < Q; q++) {
-                    const int32_t fromM = Mv[q] + tMI[q];
-                    Iv[q] = max(max(fromM, Iv[q] + tII[q]), GS_HMM_NEG);
-                    pk[q >> 3] |= (fromM == Iv[q] ? 0u : 4u) << (4 * (q & 7));
-                }
-#pragma unroll
-                for (int q = 0; q < Q; q++) Mv[q] = max(ms[q] + max(q ? give[q - 1] : up, entry), GS_HMM_NEG);
-                int32_t dl = GS_HMM_NEG;
-                Dv[0] = dl;
-#pragma unroll
-                for (int q = 1; q < Q; q++) { dl = max(max(dl + tDD[q - 1], Mv[q - 1] + tMD[q - 1]), GS_HMM_NEG); Dv[q] = dl; }
-                const int32_t m_out = Mv[Q - 1] + tMD[Q - 1];
-                int32_t b = max(max(dl + tDD[Q - 1], m_out), GS_HMM_NEG);
-#pragma unroll
-                for (int s = 0; s < 6; s++) b = max(b, __shfl_up(b, 1 << s) + a_step[s]);
-                int32_t c_in = __shfl_up(b, 1);
-                uint32_t edge = (uint32_t)__shfl_up((int)(code_out | (m_out == b ? 0u : 8u)), 1);
-                if (lane == 0) { c_in = GS_HMM_NEG; edge = HMM_PTR_B | 8u; }
-                pk[0] |= edge;
-                int32_t e = GS_HMM_NEG;
-#pragma unroll
-                for (int q = 0; q < Q; q++) {
-                    Dv[q] = max(Dv[q], c_in + PDD[q]);
-                    if (q >= 1) pk[q >> 3] |= (Mv[q - 1] + tMD[q - 1] == Dv[q] ? 0u : 8u) << (4 * (q & 7));
-                    if (q < nvalid) e = max(e, Mv[q]);
-                }
-                const int32_t E = hmm_wave_max(e);
-                const uint32_t row = i0 + (uint32_t)t;          // row i = row + 1
-#pragma unroll
-                for (int w = 0; w < NW; w++) pp[((uint64_t)row * NW + w) * 64] = pk[w];
-                // the lowest node of the row's maximum: the first lane that holds it, and that lane's first node
-                int first = 0;
-#pragma unroll
-                for (int q = Q - 1; q >= 0; q--) if (q < nvalid && Mv[q] == E) first = q;
-                const int fl = __ffsll((unsigned long long)__ballot(e == E)) - 1;     // some lane holds it: E is the maximum of the e
-                const int kE = fl * Q + __builtin_amdgcn_readlane(first, fl) + 1;
-                N += sp.tloop;
-                const int32_t Jn = max(max(J + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG), Cn = max(max(C + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
-                const int flags = (E + GS_HMM_TEJ == Cn ? HMM_ROW_C_FROM_E : 0) | (E + GS_HMM_TEJ == Jn ? HMM_ROW_J_FROM_E : 0) | (N >= Jn ? HMM_ROW_B_FROM_N : 0);
-                J = Jn; C = Cn;
-                B = max(N, J) + sp.tmove;
-                if (lane == 0) rr[row + 1] = make_int4(E, B, kE, flags);
-            }
-            cur = nxt;
-        }
-        const bool any_bad = __any(bad);
-        if (lane == 0) raw_out[pr.pair] = any_bad ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
-    }
 }
 
 // The walk of SPEC 13.2, one lane per pair of the block: from C[L] back to N, once to count the domains and once to write the first max_dom of them
@@ -677,61 +584,15 @@ __global__ __launch_bounds__(256) void k_hmm_trace_fill(uint64_t n_pairs, uint64
     if (i < n_dom_words) dom[i] = 0;
 }
 
-typedef void (*hmm_trace_kernel_t)(const int32_t *, const HmmDesc *, const HmmTraceProf *, const HmmTracePair *, const uint8_t *, const uint64_t *, const uint64_t *,
-                                   uint32_t *, int4 *, int32_t *);
-static hmm_trace_kernel_t hmm_trace_kernel(int cls)
+// the three instances of a class, from the one class list
+struct HmmKernels { decltype(&k_hmm_viterbi<1>) vit; decltype(&k_hmm_forward<1>) fwd; decltype(&k_hmm_trace<1>) trace; };
+template <size_t... I> static const HmmKernels &hmm_kernels(int cls, std::index_sequence<I...>)
 {
-    switch (cls) {
-    case 0: return k_hmm_trace<1>;
-    case 1: return k_hmm_trace<2>;
-    case 2: return k_hmm_trace<3>;
-    case 3: return k_hmm_trace<4>;
-    case 4: return k_hmm_trace<6>;
-    case 5: return k_hmm_trace<8>;
-    case 6: return k_hmm_trace<12>;
-    case 7: return k_hmm_trace<16>;
-    default: return k_hmm_trace<20>;
-    }
+    static const HmmKernels of_class[] = {{k_hmm_viterbi<HMM_CLASS_Q[I]>, k_hmm_forward<HMM_CLASS_Q[I]>, k_hmm_trace<HMM_CLASS_Q[I]>}...};
+    return of_class[cls];
 }
-
-typedef void (*hmm_fwd_kernel_t)(const int32_t *, const HmmDesc *, const uint32_t *, const uint16_t *, const uint8_t *, const uint64_t *, const uint64_t *,
-                                 const uint32_t *, const uint32_t *, uint32_t, uint32_t, int32_t *);
-static hmm_fwd_kernel_t hmm_fwd_kernel(int cls)
-{
-    switch (cls) {
-    case 0: return k_hmm_forward<1>;
-    case 1: return k_hmm_forward<2>;
-    case 2: return k_hmm_forward<3>;
-    case 3: return k_hmm_forward<4>;
-    case 4: return k_hmm_forward<6>;
-    case 5: return k_hmm_forward<8>;
-    case 6: return k_hmm_forward<12>;
-    case 7: return k_hmm_forward<16>;
-    default: return k_hmm_forward<20>;
-    }
-}
-
-typedef void (*hmm_kernel_t)(const int32_t *, const HmmDesc *, const uint32_t *, const uint8_t *, const uint64_t *, const uint64_t *, const uint32_t *, uint32_t,
-                             uint32_t, int32_t *);
-static hmm_kernel_t hmm_kernel(int cls)
-{
-    switch (cls) {
-    case 0: return k_hmm_viterbi<1>;
-    case 1: return k_hmm_viterbi<2>;
-    case 2: return k_hmm_viterbi<3>;
-    case 3: return k_hmm_viterbi<4>;
-    case 4: return k_hmm_viterbi<6>;
-    case 5: return k_hmm_viterbi<8>;
-    case 6: return k_hmm_viterbi<12>;
-    case 7: return k_hmm_viterbi<16>;
-    default: return k_hmm_viterbi<20>;
-    }
-}
-static int hmm_class_of(uint32_t M)
-{
-    for (int c = 0; c < HMM_CLASSES; c++) if ((uint32_t)HMM_CLASS_Q[c] * 64 >= M) return c;
-    return HMM_CLASSES - 1;
-}
+static const HmmKernels &hmm_kernels(int cls) { return hmm_kernels(cls, std::make_index_sequence<HMM_CLASSES>()); }
+static size_t hmm_lds_bytes(int cls, HmmProg prog) { return (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + (prog == HMM_FWD ? HMM_LSE_LDS_BYTES : 0); }
 
 }  // namespace gs
 
@@ -742,11 +603,29 @@ struct gs_hmm_db {
     std::vector<uint32_t> plist;                    // profile numbers, class by class
     uint32_t class_start[gs::HMM_CLASSES + 1] = {};
     bool all_ga = true;
-    bool lds_set[gs::HMM_CLASSES] = {}, lds_set_fwd[gs::HMM_CLASSES] = {}, lds_set_trace[gs::HMM_CLASSES] = {};
+    bool lds_set[gs::HMM_PROGS][gs::HMM_CLASSES] = {};
     gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse;
 };
 
 namespace gs {
+
+// The launches of one program for one class: the n_in profiles (or profile groups) from `first`, wg workgroups each, `lds` bytes of dynamic LDS.
+// launch(grid, first) queues kernel k for a stretch of them; lds_set is the (program, class) flag of the profile set.
+template <class K, class Launch>
+static int hmm_launch_class(gs_ctx *c, bool &lds_set, K k, uint32_t first, uint32_t n_in, uint32_t wg, size_t lds, Launch launch)
+{
+    if (!n_in) return GS_OK;
+    if (!lds_set) {
+        if (lds > 64 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_set = true;
+    }
+    for (uint32_t y0 = 0; y0 < n_in; y0 += 65535) {           // (the y dimension of a grid ends at 65535)
+        ProfScope ps(c, FAM_SEARCH);
+        launch(dim3(wg, std::min<uint32_t>(n_in - y0, 65535)), first + y0);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    return GS_OK;
+}
 
 static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **out)
 {
@@ -805,21 +684,13 @@ static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, cons
     GS_HIP_CHECK(hipMemcpyAsync(d_order.p, order.data(), 4 * n_rec, hipMemcpyHostToDevice, c->stream));
     const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
     for (int cls = 0; cls < HMM_CLASSES; cls++) {
-        const uint32_t n_in = db->class_start[cls + 1] - db->class_start[cls];
-        if (!n_in) continue;
-        const size_t lds = (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4;
-        hmm_kernel_t k = hmm_kernel(cls);
-        if (!db->lds_set[cls]) {
-            if (lds > 64 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            db->lds_set[cls] = true;
-        }
-        for (uint32_t y0 = 0; y0 < n_in; y0 += 65535) {       // (the y dimension of a grid ends at 65535)
-            ProfScope ps(c, FAM_SEARCH);
-            k<<<dim3(wg, std::min<uint32_t>(n_in - y0, 65535)), HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(),
-                                                                                           db->d_plist.as<uint32_t>() + db->class_start[cls] + y0, aa_dev, rs_dev, rl_dev,
-                                                                                           d_order.as<uint32_t>(), (uint32_t)n_rec, np, score_dev);
-            GS_HIP_CHECK(hipGetLastError());
-        }
+        const auto k = hmm_kernels(cls).vit;
+        const size_t lds = hmm_lds_bytes(cls, HMM_VIT);
+        rc = hmm_launch_class(c, db->lds_set[HMM_VIT][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
+            k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, aa_dev, rs_dev, rl_dev,
+                                                   d_order.as<uint32_t>(), (uint32_t)n_rec, np, score_dev);
+        });
+        if (rc) return rc;
     }
     GS_HIP_CHECK(stream_wait(c));           // `order` is read by the copy until here
     return GS_OK;
@@ -829,6 +700,34 @@ static int hmm_check_lens(const uint64_t *lens, uint64_t n_rec, uint32_t max_l =
     GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
     for (uint64_t r = 0; r < n_rec; r++)
         GS_REQUIRE(lens[r] <= max_l, GS_ERR_UNSUPPORTED, "hmm: record %llu has %llu residues, more than %u", (unsigned long long)r, (unsigned long long)lens[r], max_l);
+    return GS_OK;
+}
+// the _dev forms' host copy of the record lengths; waits for whatever the caller queued before it as well
+static int hmm_fetch_lens(gs_ctx *c, const uint64_t *rl_dev, uint64_t n_rec, std::vector<uint64_t> &lens)
+{
+    lens.resize(n_rec);
+    if (n_rec) GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rl_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+// the host forms: where the residues of all records end, and aa / rec_start / rec_len into their slots (n_bytes: as far as the call reads aa)
+static uint64_t hmm_records_end(const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec)
+{
+    uint64_t n_bytes = 0;
+    for (uint64_t r = 0; r < n_rec; r++) if (rec_len[r]) n_bytes = std::max(n_bytes, rec_start[r] + rec_len[r]);
+    return n_bytes;
+}
+static int hmm_stage_records(gs_ctx *c, const uint8_t *aa, uint64_t n_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, PoolBuf &d_aa, PoolBuf &d_rs,
+                             PoolBuf &d_rl)
+{
+    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
+    int rc;
+    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec))) return rc;
+    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
+    if (n_rec) {
+        GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+    }
     return GS_OK;
 }
 
@@ -855,22 +754,13 @@ static int hmm_forward_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, con
     }
     const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
     for (int cls = 0; cls < HMM_CLASSES; cls++) {
-        const uint32_t n_in = db->class_start[cls + 1] - db->class_start[cls];
-        if (!n_in) continue;
-        const size_t lds = (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + HMM_LSE_LDS_BYTES;
-        hmm_fwd_kernel_t k = hmm_fwd_kernel(cls);
-        if (!db->lds_set_fwd[cls]) {
-            if (lds > 64 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            db->lds_set_fwd[cls] = true;
-        }
-        for (uint32_t y0 = 0; y0 < n_in; y0 += 65535) {
-            ProfScope ps(c, FAM_SEARCH);
-            k<<<dim3(wg, std::min<uint32_t>(n_in - y0, 65535)), HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(),
-                                                                                           db->d_plist.as<uint32_t>() + db->class_start[cls] + y0, db->d_lse.as<uint16_t>(),
-                                                                                           aa_dev, rs_dev, rl_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec,
-                                                                                           np, fwd_dev);
-            GS_HIP_CHECK(hipGetLastError());
-        }
+        const auto k = hmm_kernels(cls).fwd;
+        const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+        rc = hmm_launch_class(c, db->lds_set[HMM_FWD][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
+            k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, db->d_lse.as<uint16_t>(), aa_dev,
+                                                   rs_dev, rl_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec, np, fwd_dev);
+        });
+        if (rc) return rc;
     }
     return GS_OK;
 }
@@ -964,22 +854,14 @@ static int hmm_trace_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const
         GS_HIP_CHECK(hipMemcpyAsync(d_tprof.p, tprof.data(), sizeof(HmmTraceProf) * tprof.size(), hipMemcpyHostToDevice, c->stream));
         for (const Block &b : blocks) {
             for (int cls = 0; cls < HMM_CLASSES; cls++) {
-                const uint32_t n_in = b.prof_start[cls + 1] - b.prof_start[cls];
-                if (!n_in) continue;
-                const size_t lds = (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4;
-                hmm_trace_kernel_t k = hmm_trace_kernel(cls);
-                if (!db->lds_set_trace[cls]) {
-                    if (lds > 64 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    db->lds_set_trace[cls] = true;
-                }
+                const auto k = hmm_kernels(cls).trace;
+                const size_t lds = hmm_lds_bytes(cls, HMM_TRACE);
                 const uint32_t wg = std::min<uint32_t>((b.max_cnt[cls] + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
-                for (uint32_t y0 = 0; y0 < n_in; y0 += 65535) {
-                    ProfScope ps(c, FAM_SEARCH);
-                    k<<<dim3(wg, std::min<uint32_t>(n_in - y0, 65535)), HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(),
-                                                                                                   d_tprof.as<HmmTraceProf>() + b.prof_start[cls] + y0, d_tp.as<HmmTracePair>(),
-                                                                                                   aa_dev, rs_dev, rl_dev, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev);
-                    GS_HIP_CHECK(hipGetLastError());
-                }
+                rc = hmm_launch_class(c, db->lds_set[HMM_TRACE][cls], k, b.prof_start[cls], b.prof_start[cls + 1] - b.prof_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
+                    k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(), aa_dev,
+                                                           rs_dev, rl_dev, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev);
+                });
+                if (rc) return rc;
             }
             ProfScope ps(c, FAM_SEARCH);
             k_hmm_walk<<<(b.n + HMM_WALK_BLOCK - 1) / HMM_WALK_BLOCK, HMM_WALK_BLOCK, 0, c->stream>>>(db->d_desc.as<HmmDesc>(), d_tp.as<HmmTracePair>() + b.start, b.n, pprof_dev,
@@ -1105,11 +987,9 @@ int gs_hmm_search_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uin
     GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && score_out_dev, GS_ERR_INVALID, "null argument");
     GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
     GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens(n_rec);
-    GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rec_len_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    int rc = hmm_check_lens(lens.data(), n_rec);
-    if (rc) return rc;
+    std::vector<uint64_t> lens;
+    int rc;
+    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_check_lens(lens.data(), n_rec))) return rc;
     PoolBuf d_order(c, SL_HMM_ORDER);
     return hmm_search_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, score_out_dev, d_order);
 }
@@ -1122,16 +1002,10 @@ int gs_hmm_search(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *r
     GS_REQUIRE(rec_start && rec_len && score_out, GS_ERR_INVALID, "null argument");
     int rc = hmm_check_lens(rec_len, n_rec);
     if (rc) return rc;
-    uint64_t n_bytes = 0;
-    for (uint64_t r = 0; r < n_rec; r++) if (rec_len[r]) n_bytes = std::max(n_bytes, rec_start[r] + rec_len[r]);
-    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
     const uint64_t np = db->models.size();
     GS_CTX_LOCK(c);
     PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_order(c, SL_HMM_ORDER);
-    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec)) || (rc = d_score.alloc(4 * n_rec * np))) return rc;
-    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
+    if ((rc = hmm_stage_records(c, aa, hmm_records_end(rec_start, rec_len, n_rec), rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_score.alloc(4 * n_rec * np))) return rc;
     if ((rc = hmm_search_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, d_score.as<int32_t>(), d_order))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(score_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(stream_wait(c));
@@ -1204,11 +1078,9 @@ int gs_hmm_search_forward_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, c
     GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && fwd_out_dev, GS_ERR_INVALID, "null argument");
     GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
     GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens(n_rec);
-    GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rec_len_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    int rc = hmm_check_lens(lens.data(), n_rec, GS_HMM_FWD_MAX_L);
-    if (rc) return rc;
+    std::vector<uint64_t> lens;
+    int rc;
+    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_check_lens(lens.data(), n_rec, GS_HMM_FWD_MAX_L))) return rc;
     PoolBuf d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT), d_vit(c, SL_HMM_VIT);
     if (!vit_out_dev) {
         if ((rc = d_vit.alloc(4 * n_rec * db->models.size()))) return rc;
@@ -1228,23 +1100,17 @@ int gs_hmm_search_forward(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uin
     GS_REQUIRE(rec_start && rec_len && fwd_out, GS_ERR_INVALID, "null argument");
     int rc = hmm_check_lens(rec_len, n_rec, GS_HMM_FWD_MAX_L);
     if (rc) return rc;
-    uint64_t n_bytes = 0;
-    for (uint64_t r = 0; r < n_rec; r++) if (rec_len[r]) n_bytes = std::max(n_bytes, rec_start[r] + rec_len[r]);
-    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
     const uint64_t np = db->models.size();
     GS_CTX_LOCK(c);
     PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_fwd(c, SL_HMMB_FWD), d_floor(c, SL_HMMB_FLOOR),
         d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT);
-    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec)) || (rc = d_score.alloc(4 * n_rec * np)) ||
+    if ((rc = hmm_stage_records(c, aa, hmm_records_end(rec_start, rec_len, n_rec), rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_score.alloc(4 * n_rec * np)) ||
         (rc = d_fwd.alloc(4 * n_rec * np)))
         return rc;
     if (vit_floor) {
         if ((rc = d_floor.alloc(4 * np))) return rc;
         GS_HIP_CHECK(hipMemcpyAsync(d_floor.p, vit_floor, 4 * np, hipMemcpyHostToDevice, c->stream));
     }
-    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
     if ((rc = hmm_forward_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, vit_floor ? d_floor.as<int32_t>() : nullptr,
                                d_score.as<int32_t>(), d_fwd.as<int32_t>(), d_order, d_sel, d_cnt)))
         return rc;
@@ -1265,14 +1131,12 @@ int gs_hmm_trace_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint
     GS_REQUIRE(n_rec == 0 || (aa_dev && rec_start_dev && rec_len_dev), GS_ERR_INVALID, "null argument");
     GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
     GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens(n_rec);
+    std::vector<uint64_t> lens;
     std::vector<uint32_t> prec(n_pairs), pprof(n_pairs);
-    if (n_rec) GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rec_len_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(prec.data(), pair_rec_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(pprof.data(), pair_prof_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    int rc = hmm_trace_check(db, lens.data(), n_rec, prec.data(), pprof.data(), n_pairs);
-    if (rc) return rc;
+    int rc;
+    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_trace_check(db, lens.data(), n_rec, prec.data(), pprof.data(), n_pairs))) return rc;
     return hmm_trace_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), prec.data(), pprof.data(), pair_prof_dev, n_pairs, max_dom, max_block_cells, raw_out_dev,
                           n_dom_out_dev, dom_out_dev);
 }
@@ -1291,19 +1155,13 @@ int gs_hmm_trace(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *re
     uint64_t n_bytes = 0;                       // of the records that a pair names: the others may be any length and are not staged
     for (uint64_t i = 0; i < n_pairs; i++)
         if (pair_rec[i] != GS_HMM_NO_HIT && rec_len[pair_rec[i]]) n_bytes = std::max(n_bytes, rec_start[pair_rec[i]] + rec_len[pair_rec[i]]);
-    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
     const uint64_t n_dom_bytes = 4 * n_pairs * max_dom * GS_HMM_DOM_WORDS;
     GS_CTX_LOCK(c);
     PoolBuf d_aa(c, SL_HMMTB_AA), d_rs(c, SL_HMMTB_REC_START), d_rl(c, SL_HMMTB_REC_LEN), d_pp(c, SL_HMMTB_PAIR_PROF), d_raw(c, SL_HMMTB_RAW),
         d_nd(c, SL_HMMTB_NDOM), d_dom(c, SL_HMMTB_DOM);
-    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec)) || (rc = d_pp.alloc(4 * n_pairs)) ||
-        (rc = d_raw.alloc(4 * n_pairs)) || (rc = d_nd.alloc(4 * n_pairs)) || (rc = d_dom.alloc(n_dom_bytes)))
+    if ((rc = hmm_stage_records(c, aa, n_bytes, rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_pp.alloc(4 * n_pairs)) || (rc = d_raw.alloc(4 * n_pairs)) ||
+        (rc = d_nd.alloc(4 * n_pairs)) || (rc = d_dom.alloc(n_dom_bytes)))
         return rc;
-    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
-    if (n_rec) {
-        GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
-        GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
-    }
     GS_HIP_CHECK(hipMemcpyAsync(d_pp.p, pair_prof, 4 * n_pairs, hipMemcpyHostToDevice, c->stream));
     if ((rc = hmm_trace_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, pair_rec, pair_prof, d_pp.as<uint32_t>(), n_pairs, max_dom,
                              max_block_cells, d_raw.as<int32_t>(), d_nd.as<uint32_t>(), d_dom.as<int32_t>())))

@@ -19,7 +19,11 @@ composition) against 120 synthetic profiles with the node counts of the bacteria
                 pairs into blocks; the default block size), beside the Viterbi seconds of the same run
   check         the raw of every traced pair against the score matrix, and `check` sampled pairs against the restatement (tests/pyref_hmm_trace.py)
 
-usage: hmm_rate.py [--forward | --trace] [--n 4000] [--repeat 3] [--check 8] [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log]"""
+--dump PATH saves the downloaded matrices of the modes that ran as one .npz (the Viterbi scores; both Forward matrices; raw, n_dom and the domain
+words of trace_best and trace_all), so that two builds of the library (GS_LIB_PATH) can be compared word for word.
+
+usage: hmm_rate.py [--forward | --trace] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
+                   [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log]"""
 import argparse
 import json
 import os
@@ -42,6 +46,7 @@ def main():
     ap.add_argument("--forward", action="store_true")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--log", default=None)
+    ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     if a.log is None:
         a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else ("hmm_trace_rate.log" if a.trace else "hmm_rate.log"))
@@ -89,10 +94,14 @@ def main():
         r, p = int(rng.integers(a.n)), int(rng.integers(len(db)))
         diff += int(scores[r, p]) != R.viterbi(R.parse_hmm(texts[p])[0]["tables"], recs[r])
     res["check_pairs"], res["check_differences"] = a.check, diff
+    dump = {"viterbi": scores}
     if a.forward:
-        forward_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng)
+        forward_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng, dump)
     if a.trace:
-        trace_part(a, ctx, db, texts, recs, ptrs, d_rec, scores, cells, res, rng)
+        trace_part(a, ctx, db, texts, recs, ptrs, d_rec, scores, cells, res, rng, dump)
+    if a.dump:
+        with open(a.dump, "wb") as f:
+            np.savez(f, **dump)
     for p in ptrs + [d_score, d_rec, d_best]:
         ctx.free(p)
     db.close()
@@ -104,7 +113,7 @@ def main():
             f.write(line + "\n")
 
 
-def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng):
+def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng, dump):
     import pyref_hmm as R
     import pyref_hmm_forward as F
     d_fwd = ctx.alloc(4 * a.n * len(db))
@@ -125,6 +134,7 @@ def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng):
         if name == "all":
             fwd_all = ctx.download(d_fwd, (a.n, len(db)), np.int32)
     fwd = ctx.download(d_fwd, (a.n, len(db)), np.int32)
+    dump.update(forward_all=fwd_all, forward_filtered=fwd)
     res["forward_all_call_s"] = times["all"]
     res["forward_all_s"] = times["all"] - res["search_s"]
     res["forward_cells_per_s"] = cells / res["forward_all_s"]
@@ -145,7 +155,7 @@ def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng):
     ctx.free(d_floor)
 
 
-def trace_part(a, ctx, db, texts, recs, ptrs, d_best_rec, scores, cells, res, rng):
+def trace_part(a, ctx, db, texts, recs, ptrs, d_best_rec, scores, cells, res, rng, dump):
     import pyref_hmm as R
     import pyref_hmm_trace as T
     n_prof = len(db)
@@ -169,6 +179,7 @@ def trace_part(a, ctx, db, texts, recs, ptrs, d_best_rec, scores, cells, res, rn
 
     hit = ctx.download(d_best_rec, (n_prof,), np.uint32)
     res["trace_best_s"], (raw, nd, dom) = run(d_best_rec, np.arange(n_prof, dtype=np.uint32), 8)
+    dump.update(trace_best_raw=raw, trace_best_n_dom=nd, trace_best_dom=dom)
     on = hit != R.NO_HIT
     res["trace_best_pairs"] = int(on.sum())
     res["trace_best_raw_differences"] = int((raw[on] != scores[hit[on], np.flatnonzero(on)]).sum()) + int((raw[~on] != R.NO_SCORE).sum())
@@ -178,6 +189,7 @@ def trace_part(a, ctx, db, texts, recs, ptrs, d_best_rec, scores, cells, res, rn
     ctx.upload(d_pr, pr)
     res["trace_all_s"], (raw, nd, dom) = run(d_pr, np.tile(np.arange(n_prof, dtype=np.uint32), a.n), 2)
     ctx.free(d_pr)
+    dump.update(trace_all_raw=raw, trace_all_n_dom=nd, trace_all_dom=dom)
     res["trace_all_pairs"] = len(pr)
     res["trace_all_cells_per_s"] = cells / res["trace_all_s"]
     res["trace_all_over_viterbi"] = res["trace_all_s"] / res["search_s"]
