@@ -1,5 +1,7 @@
 """Device-side gzip (gs_inflate.hip, the .gz path of gs_sketch_files) against zlib: the text a member inflates to must be byte-identical
-for every block type and table shape the encoders in this image can produce, and damaged members must be reported, not decoded."""
+for every block type and table shape the encoders in this image can produce, and damaged members must be reported, not decoded.
+The legal shapes that no installed encoder makes, and the refusals that only a structured stream reaches, are in test_gpu_inflate_streams.py
+(hand-built streams: deflate_writer.py, deflate_cases.py)."""
 import gzip
 import os
 import io
