@@ -833,9 +833,11 @@ __global__ __launch_bounds__(COLD ? HL_CT : HL_T, (!COLD && TIGHT) ? 4 : 1) void
                 __syncthreads();
                 uint64_t *sq = queue_off ? (uint64_t *)(s_hll + queue_off) + (threadIdx.x >> 6) * 128 : nullptr;
                 HllEmit<COLD, GTAB> emit{S, m, zone_m, inv_lnb, am, q, perm, &stamp, true, sq, threadIdx.x & 63, 0u, ~(uint64_t)0, nullptr, 0u};
+                // (walk_genome on its one-stage loop: the registers of the two-stage one would cost every form of this kernel a wave per SIMD,
+                // 156 -> 171 and 116 -> 130 VGPRs, or more scratch under the 128-register bound - profiles/sketch_ahead_resource_usage.txt)
                 for (uint32_t ch = 0; ch < nchunks; ch++) {
                     emit.refresh();
-                    walk_genome<AA>(seq, rec_start, rec_len, rec_upre, r0, r1, units, k, ch, nchunks, emit);
+                    walk_genome<AA, HllEmit<COLD, GTAB>, 2, false>(seq, rec_start, rec_len, rec_upre, r0, r1, units, k, ch, nchunks, emit);
                     if (__syncthreads_or(S.ctl[3] != 0)) { outgrown = true; break; }
                 }
                 if (!outgrown) {
@@ -861,7 +863,7 @@ __global__ __launch_bounds__(COLD ? HL_CT : HL_T, (!COLD && TIGHT) ? 4 : 1) void
             }
             for (uint32_t ch = 0; ch < (pass < 0 ? nwarm : nchunks); ch++) {
                 emit.refresh();
-                walk_genome<AA>(seq, rec_start, rec_len, rec_upre, r0, r1, units, k, ch, nchunks, emit);
+                walk_genome<AA, HllEmit<COLD, GTAB>, 2, false>(seq, rec_start, rec_len, rec_upre, r0, r1, units, k, ch, nchunks, emit);
                 if (pass <= 0 || ch + 1 == nchunks) {
                     // refresh the lower bound: minimum register (pass A: running, between chunks; after pass A: exact)
                     const uint32_t kl_ = min_register();
