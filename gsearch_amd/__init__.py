@@ -16,3 +16,4 @@ from .api import BIGSI_MINI_TILE, Bigsi, bigsi_minimizers, bigsi_positions, bigs
 from .api import AniGenome, AniSketcher, ani_estimate, ani_pairs, superani, write_superani  # noqa: F401
 from .api import HmmDb, hmm_bits, hmm_evalue, hmm_parse, hmm_specials, hmm_threshold_units, hmmsearch, universal_genes  # noqa: F401
 from .api import hmm_forward_evalue, hmm_logsum_table, hmm_parse_stats, hmm_viterbi_floor  # noqa: F401
+from .api import ORF_DTYPE, ORF_TILE, orf_codon_table, orf_translate, orf_translate_dev, orf_translate_packed, write_orf_faa  # noqa: F401

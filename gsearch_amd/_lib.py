@@ -73,6 +73,13 @@ class HmmInfoC(C.Structure):
                 ("nc", C.c_double * 2), ("mu", C.c_double), ("lam", C.c_double), ("ga_units", C.c_int32), ("tbm", C.c_int32)]
 
 
+class OrfParamsC(C.Structure):
+    """gs_orf_params (SPEC 14)"""
+    _fields_ = [("min_aa", C.c_uint32), ("max_aa", C.c_uint32), ("table", C.c_uint32), ("flags", C.c_uint32)]
+
+
+ORF_TILE, ORF_MIN_AA = 192, 30
+
 HMM_MAX_M, HMM_MAX_L, HMM_NO_SCORE, HMM_NO_HIT, HMM_TABLE_ROWS = 1280, 1 << 18, -(1 << 31), 0xFFFFFFFF, 27
 HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
 HMM_FWD_MAX_L, HMM_LSE_N, HMM_FLOOR_ALL = 65536, 5903, -(1 << 31) + 1
@@ -169,6 +176,10 @@ SYMBOLS = {
     "gs_hmm_forward_evalue": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double]),
     "gs_hmm_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     "gs_hmm_trace_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
+    # orfs (SPEC 14)
+    "gs_orf_codon_table": (_i, [_u32, C.c_char_p]),
+    "gs_orf_translate_dev": (_i, [_vp, C.POINTER(OrfParamsC), _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "gs_orf_translate": (_i, [_vp, C.POINTER(OrfParamsC), _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "gs_index_create": (_i, [_vp, C.POINTER(IndexParams), C.POINTER(_vp)]),
     "gs_index_destroy": (None, [_vp]),
     "gs_index_nb_point": (_u64, [_vp]),

@@ -1134,7 +1134,7 @@ def _as_hmm_db(hmm, ctx):
     return hmm if isinstance(hmm, HmmDb) else HmmDb(hmm, ctx)
 
 
-def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None):
+def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None, translate=False, min_aa=_lib.ORF_MIN_AA, table=11):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
     `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
     `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
@@ -1145,14 +1145,27 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     domains (a path; SPEC 13.2): the pairs the score table lists are traced back on the device and a second table is written there - a header line, then
     `target profile acc dom n_dom i_from i_to k_from k_to M seg_bits n_match n_ins n_del` for every domain, seg_bits %.2f of seg / 1024, sorted like the
     score table and then by dom (from 1). With score="forward" the pairs are the Forward table's and the path is still the Viterbi path. The return value is
-    then (ids, scores, table bytes, domain table bytes)."""
+    then (ids, scores, table bytes, domain table bytes).
+    translate=True (SPEC 14): `faa` is a NUCLEOTIDE FASTA; the targets are its stop-to-stop six-frame ORFs of min_aa residues and more under translation
+    `table` (11 or 4), translated on the device and searched there without their residues coming back. A target is named `{contig}_{begin+1}_{end}_{+|-}`
+    as write_orf_faa() names it, Z is the number of ORFs, the formats are unchanged. The ORFs are not a proteome: no start codons, no frameshifts."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     db = _as_hmm_db(hmm, ctx)
-    ids, seqs = _faa_records(faa)
     fwd = score == "forward"
-    aa, rs, rl = filter_aa_records([bytes(q) for q in seqs])
-    scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
+    dev = None
+    if translate:
+        dev = _DevOrfs(db.ctx, [_fna_contigs(faa)], min_aa, _orf_max_aa(fwd, domains is not None), table)
+        try:
+            ids = dev.names()
+            scores = dev.search(db, fwd, filter_p)
+        except Exception:
+            dev.close()
+            raise
+    else:
+        ids, seqs = _faa_records(faa)
+        aa, rs, rl = filter_aa_records([bytes(q) for q in seqs])
+        scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
     Z = len(ids)
     out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga\n"]
     listed = []                                                          # the (record, profile) pairs of the table, in its order
@@ -1174,9 +1187,17 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
         with open(output, "wb") as f:
             f.write(table)
     if domains is None:
+        if dev is not None:
+            dev.close()
         return ids, scores, table
     pr, pp = np.array([r for r, _ in listed], np.uint32), np.array([p for _, p in listed], np.uint32)
-    _, nd, dom = db.trace_all(aa, rs, rl, pr, pp)
+    if dev is not None:
+        try:
+            _, nd, dom = dev.trace_all(db, pr, pp)
+        finally:
+            dev.close()
+    else:
+        _, nd, dom = db.trace_all(aa, rs, rl, pr, pp)
     out = [b"target\tprofile\tacc\tdom\tn_dom\ti_from\ti_to\tk_from\tk_to\tM\tseg_bits\tn_match\tn_ins\tn_del\n"]
     for j, (r, p) in enumerate(listed):
         inf = db.info[p]
@@ -1190,17 +1211,24 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     return ids, scores, table, dom_table
 
 
-def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein"):
+def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein", translate=False, min_aa=_lib.ORF_MIN_AA, table=11):
     """One genome per protein FASTA file: per genome the residues of its best protein for every profile that has a hit at the cutoff, in profile
     order - the records an AA sketcher takes for `tohnsw` / `request` at the universal-gene level. -> (list of lists of bytes, uint32 [n_genomes, n_prof]
     record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing). score="forward": the best hits are those of the Forward matrix
     (SPEC 13.1) behind the Viterbi floor of filter_p - the score the files' GA cutoffs were gathered on. region="aligned" (SPEC 13.2): every hit is
-    traced back on the device and contributes the residues from i_from of its first domain through i_to of its last, not the whole protein."""
+    traced back on the device and contributes the residues from i_from of its first domain through i_to of its last, not the whole protein.
+    translate=True (SPEC 14): one genome per NUCLEOTIDE FASTA file; the candidates are the stop-to-stop six-frame ORFs of min_aa residues and more under
+    translation `table`, translated and searched on the device - only the chosen hits' residues come back. The record numbers are then ORF numbers inside
+    the genome, and a third value is returned: int64 [n_genomes, n_prof, 4] = (contig index, begin, end, strand) of the chosen ORF in contig coordinates
+    (0-based, end exclusive, strand 0 / 1 = + / -), -1 where a profile found nothing. A stop-to-stop ORF overhangs the gene at its 5' end;
+    region="aligned" trims that. The ORF set is not a proteome and is not meant for the AA sketchers as a whole."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     if region not in ("protein", "aligned"):
         raise ValueError("region: 'protein' or 'aligned'")
     db = _as_hmm_db(hmm, ctx)
+    if translate:
+        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table)
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
@@ -1224,6 +1252,266 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
         genomes.append(hits)
     local = np.where(rec == _lib.HMM_NO_HIT, rec, rec - np.array(goff[:-1], np.uint32)[:, None]).astype(np.uint32)
     return genomes, local
+
+
+# ---- orfs (SPEC 14): stop-to-stop six-frame translation on the device ----------------------------------------------------------------------
+ORF_DTYPE = np.dtype([("begin", np.uint64), ("rec", np.uint32), ("strand", np.uint32)])        # gs_orf
+ORF_TILE = _lib.ORF_TILE
+
+
+def orf_codon_table(table=11):
+    """the 64 letters of translation table 11 or 4, codon index 16 b0 + 4 b1 + b2 with A C G T = 0 1 2 3, `*` = stop (host only)"""
+    buf = C.create_string_buffer(64)
+    check(_lib.load().gs_orf_codon_table(int(table), buf))
+    return buf.raw.decode("ascii")
+
+
+def _orf_caps(rec_len, min_aa):
+    """room that holds every ORF whatever the bases are: a record of L bases has L - 2 codon positions on either strand, a kept ORF min_aa residues or more"""
+    cap_aa = 2 * int(np.maximum(np.asarray(rec_len, dtype=np.int64) - 2, 0).sum())
+    return cap_aa // max(int(min_aa), 1), cap_aa
+
+
+def orf_translate_dev(ctx, seq_dev, seq_bytes, rec_start_dev, rec_len_dev, n_rec, cap_orf=0, cap_aa=0, orf_out_dev=None, aa_out_dev=None, aa_start_out_dev=None,
+                      aa_len_out_dev=None, rec_orf_off_out_dev=None, min_aa=_lib.ORF_MIN_AA, max_aa=0, table=11):
+    """gs_orf_translate_dev: all arrays device memory, the outputs left in flight on the context's stream -> (n_orf, n_aa, n_long), also when the
+    capacities are too small (GsError then carries them as .counts). No outputs and zero capacities: count only."""
+    prm = _lib.OrfParamsC(int(min_aa), int(max_aa), int(table), 0)
+    n = (C.c_uint64 * 3)()
+    try:
+        check(ctx.L.gs_orf_translate_dev(ctx.h, C.byref(prm), seq_dev, int(seq_bytes), rec_start_dev, rec_len_dev, int(n_rec), int(cap_orf), int(cap_aa), orf_out_dev,
+                                         aa_out_dev, aa_start_out_dev, aa_len_out_dev, rec_orf_off_out_dev, n))
+    except GsError as e:
+        e.counts = (int(n[0]), int(n[1]), int(n[2]))
+        raise
+    return int(n[0]), int(n[1]), int(n[2])
+
+
+def orf_translate_packed(seq, rec_start, rec_len, min_aa=_lib.ORF_MIN_AA, max_aa=0, table=11, ctx=None):
+    """SPEC 14 on the packed layout of pack_dna_records() (2-bit bases, no invalid base inside a record): the stop-to-stop ORFs of all six frames with
+    min_aa <= residues (<= max_aa unless 0), ascending by (record, end, strand) -> dict of `orf` (ORF_DTYPE: begin inside the record in forward
+    coordinates, rec, strand), `aa` (upper-case residues back to back), `aa_start`, `aa_len`, `rec_orf_off` (n_rec + 1) and `n_long` (dropped as longer
+    than max_aa). This is not a gene caller and the ORF set is not a proteome: it feeds hmmsearch, not the AA sketchers."""
+    ctx = ctx or default_context()
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+    rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+    prm = _lib.OrfParamsC(int(min_aa), int(max_aa), int(table), 0)
+    cap_orf, cap_aa = _orf_caps(rl, min_aa)
+    orf, aa = np.zeros(cap_orf, ORF_DTYPE), np.zeros(cap_aa, np.uint8)
+    a_s, a_l, off = np.zeros(cap_orf, np.uint64), np.zeros(cap_orf, np.uint64), np.zeros(len(rs) + 1, np.uint64)
+    n = (C.c_uint64 * 3)()
+    check(ctx.L.gs_orf_translate(ctx.h, C.byref(prm), _p(seq) if seq.nbytes else None, seq.nbytes, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
+                                 cap_orf, cap_aa, _p(orf), _p(aa), _p(a_s), _p(a_l), _p(off), n))
+    return {"orf": orf[:n[0]].copy(), "aa": aa[:n[1]].copy(), "aa_start": a_s[:n[0]].copy(), "aa_len": a_l[:n[0]].copy(), "rec_orf_off": off, "n_long": int(n[2])}
+
+
+def _orf_segments(contigs):
+    """ASCII contigs -> (records, contig of each record, offset of each record in its contig): a contig is split at every byte outside ACGTacgt
+    (SPEC 11 segments without qualities), so that no codon holds an invalid base and no frame shifts"""
+    recs, rec_contig, rec_off = [], [], []
+    for ci, ctg in enumerate(contigs):
+        ctg = bytes(ctg)
+        for b, l in bigsi_split(ctg):
+            recs.append(ctg[b:b + l]); rec_contig.append(ci); rec_off.append(b)
+    return recs, np.array(rec_contig, np.int64), np.array(rec_off, np.int64)
+
+
+def orf_translate(contigs, min_aa=_lib.ORF_MIN_AA, max_aa=0, table=11, ctx=None):
+    """ASCII contigs (bytes, no line breaks) -> (per contig the list of (begin, end, strand, protein) in contig coordinates - 0-based, end exclusive,
+    strand 0 / 1 = + / -, ascending by (end, strand) -, the flat dict of orf_translate_packed() with `rec_contig` and `rec_offset` of its records).
+    Model-free: every maximal run of codons without a stop in any of the six frames, no start-codon rule. Not a gene caller, not a proteome."""
+    recs, rc, ro = _orf_segments(contigs)
+    seq, rs, rl = pack_dna_records(recs)
+    flat = orf_translate_packed(seq, rs, rl, min_aa, max_aa, table, ctx)
+    flat["rec_contig"], flat["rec_offset"] = rc, ro
+    out = [[] for _ in contigs]
+    aa = flat["aa"].tobytes()
+    for o, a, n in zip(flat["orf"], flat["aa_start"], flat["aa_len"]):
+        b = int(ro[o["rec"]]) + int(o["begin"])
+        out[int(rc[o["rec"]])].append((b, b + 3 * int(n), int(o["strand"]), aa[int(a):int(a) + int(n)]))
+    return out, flat
+
+
+def _orf_name(contig_id, begin, end, strand):
+    return "%s_%d_%d_%s" % (contig_id, begin + 1, end, "-" if strand else "+")
+
+
+def write_orf_faa(path, contig_ids, orfs):
+    """orfs: per contig the (begin, end, strand, protein) list of orf_translate() -> a protein FASTA with headers `>{contig}_{begin+1}_{end}_{+|-}`
+    (FragGeneScan's header convention) and one sequence line per ORF. The file is a set of candidates for hmmsearch, not a proteome."""
+    if len(contig_ids) != len(orfs):
+        raise ValueError("one id per contig")
+    with open(path, "wb") as f:
+        for cid, lst in zip(contig_ids, orfs):
+            for b, e, s, prot in lst:
+                f.write(b">" + _orf_name(cid, b, e, s).encode() + b"\n" + bytes(prot) + b"\n")
+
+
+def _fna_contigs(path):
+    """[(id, bases without line breaks)] of one nucleotide FASTA file, plain or compressed"""
+    text = read_fasta_file(path)
+    return [(rid, _strip_breaks(text[b:e])) for rid, b, e in fasta_scan(text, skip_capsid=False)]
+
+
+def _orf_max_aa(fwd, traced):
+    """the longest ORF the programs of a translated call take"""
+    return min([_lib.HMM_MAX_L] + ([_lib.HMM_FWD_MAX_L] if fwd else []) + ([_lib.HMM_TRACE_MAX_L] if traced else []))
+
+
+class _DevOrfs:
+    """The ORFs of some genomes (each a list of (contig id, bases)), translated on the device and kept there in the layout gs_hmm_search_dev reads; the
+    host holds their descriptors, never their residues."""
+
+    def __init__(self, ctx, genomes, min_aa, max_aa, table):
+        self.ctx, self.bufs = ctx, []
+        self.contig_ids = [cid for g in genomes for cid, _ in g]
+        contig_genome = [gi for gi, g in enumerate(genomes) for _ in g]
+        self.genome_contig0 = np.concatenate([[0], np.cumsum([len(g) for g in genomes])]).astype(np.int64)
+        recs, self.rec_contig, self.rec_offset = _orf_segments([c for g in genomes for _, c in g])
+        seq, rs, rl = pack_dna_records(recs)
+        cap_orf, cap_aa = _orf_caps(rl, min_aa)
+        n_rec = len(rs)
+        try:
+            d_seq, d_rs, d_rl = self._up(seq), self._up(rs), self._up(rl)
+            self.d_orf, self.d_aa, self.d_as, self.d_al = self._new(16 * cap_orf), self._new(cap_aa), self._new(8 * cap_orf), self._new(8 * cap_orf)
+            d_off = self._new(8 * (n_rec + 1))
+            self.n, n_aa, self.n_long = orf_translate_dev(ctx, d_seq, seq.nbytes, d_rs, d_rl, n_rec, cap_orf, cap_aa, self.d_orf, self.d_aa, self.d_as, self.d_al, d_off,
+                                                          min_aa, max_aa, table)
+            self.orf = ctx.download(self.d_orf, (self.n,), ORF_DTYPE)
+            self.aa_start = ctx.download(self.d_as, (self.n,), np.uint64)
+            self.aa_len = ctx.download(self.d_al, (self.n,), np.uint64)
+            rec_orf_off = ctx.download(d_off, (n_rec + 1,), np.uint64)
+            for ptr in (d_seq, d_rs, d_rl, d_off):
+                self._free(ptr)
+        except Exception:
+            self.close()
+            raise
+        # the first record of every genome -> its first ORF
+        rec_genome = np.array([contig_genome[c] for c in self.rec_contig], np.int64)
+        first_rec = np.searchsorted(rec_genome, np.arange(len(genomes) + 1))
+        self.genome_orf_off = rec_orf_off[first_rec].astype(np.uint64)
+
+    def _new(self, nbytes):
+        ptr = self.ctx.alloc(max(int(nbytes), 16))
+        self.bufs.append(ptr)
+        return ptr
+
+    def _up(self, arr):
+        ptr = self._new(arr.nbytes)
+        if arr.nbytes:
+            self.ctx.upload(ptr, arr)
+        return ptr
+
+    def _free(self, ptr):
+        self.bufs.remove(ptr)
+        self.ctx.free(ptr)
+
+    def close(self):
+        while self.bufs:
+            self.ctx.free(self.bufs.pop())
+
+    def __del__(self):
+        try:
+            if not _exiting[0]:
+                self.close()
+        except Exception:
+            pass
+
+    def coords(self, j):
+        """(contig index, begin, end, strand) of ORF j in contig coordinates"""
+        o = self.orf[j]
+        b = int(self.rec_offset[o["rec"]]) + int(o["begin"])
+        return int(self.rec_contig[o["rec"]]), b, b + 3 * int(self.aa_len[j]), int(o["strand"])
+
+    def names(self):
+        out = []
+        for j in range(self.n):
+            c, b, e, s = self.coords(j)
+            out.append(_orf_name(self.contig_ids[c], b, e, s))
+        return out
+
+    def search_dev(self, db, fwd, filter_p):
+        """device int32 [n, n_prof] scores of the ORFs (Forward behind the Viterbi floor when fwd); the caller frees through close()"""
+        d_score = self._new(4 * self.n * len(db))
+        if self.n == 0:
+            return d_score
+        if fwd:
+            fl = db._floor(filter_p, None)
+            d_fl = self._up(fl) if fl is not None else None
+            db.search_forward_dev(self.d_aa, self.d_as, self.d_al, self.n, d_fl, None, d_score)
+            self.ctx.sync()
+            if d_fl is not None:
+                self._free(d_fl)
+        else:
+            db.search_dev(self.d_aa, self.d_as, self.d_al, self.n, d_score)
+        return d_score
+
+    def search(self, db, fwd, filter_p):
+        d_score = self.search_dev(db, fwd, filter_p)
+        scores = self.ctx.download(d_score, (self.n, len(db)), np.int32)
+        self._free(d_score)
+        return scores
+
+    def trace_all(self, db, pair_rec, pair_prof):
+        """HmmDb.trace_all() over the device residues"""
+        pr, pp = np.ascontiguousarray(pair_rec, np.uint32).reshape(-1), np.ascontiguousarray(pair_prof, np.uint32).reshape(-1)
+        npair, max_dom = len(pr), 8
+        if npair == 0 or self.n == 0:
+            return np.full(npair, _lib.HMM_NO_SCORE, np.int32), np.zeros(npair, np.uint32), np.zeros((npair, max_dom, _lib.HMM_DOM_WORDS), np.int32)
+        d_pr, d_pp = self._up(pr), self._up(pp)
+        while True:
+            d_raw, d_nd, d_dom = self._new(4 * npair), self._new(4 * npair), self._new(4 * npair * max_dom * _lib.HMM_DOM_WORDS)
+            db.trace_dev(self.d_aa, self.d_as, self.d_al, self.n, d_pr, d_pp, npair, max_dom, d_raw, d_nd, d_dom)
+            raw, nd = self.ctx.download(d_raw, (npair,), np.int32), self.ctx.download(d_nd, (npair,), np.uint32)
+            dom = self.ctx.download(d_dom, (npair, max_dom, _lib.HMM_DOM_WORDS), np.int32)
+            for ptr in (d_raw, d_nd, d_dom):
+                self._free(ptr)
+            if int(nd.max()) <= max_dom:
+                break
+            max_dom = int(nd.max())
+        self._free(d_pr); self._free(d_pp)
+        return raw, nd, dom
+
+    def residues(self, j, a=0, b=None):
+        """residues [a, b) of ORF j, read back from the device"""
+        b = int(self.aa_len[j]) if b is None else b
+        if b <= a:
+            return b""
+        return self.ctx.download(self.d_aa + int(self.aa_start[j]) + a, (b - a,), np.uint8).tobytes()
+
+
+def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table):
+    ctx = db.ctx
+    dev = _DevOrfs(ctx, [_fna_contigs(p) for p in fna_files], min_aa, _orf_max_aa(fwd, aligned), table)
+    try:
+        ng, npf = len(fna_files), len(db)
+        rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
+        if ng and npf and dev.n:
+            d_score = dev.search_dev(db, fwd, filter_p)
+            d_goff, d_thr = dev._up(dev.genome_orf_off), dev._up(db.thresholds(cutoff))
+            d_rec, d_sc = dev._new(4 * ng * npf), dev._new(4 * ng * npf)
+            db.best_hits_dev(d_score, dev.n, d_goff, ng, d_thr, d_rec, d_sc)
+            rec = ctx.download(d_rec, (ng, npf), np.uint32)
+        span = {}
+        if aligned and (rec != _lib.HMM_NO_HIT).any():
+            _, nd, dom = dev.trace_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
+            for j in np.flatnonzero(nd):
+                span[int(j)] = (int(dom[j, 0, 0]) - 1, int(dom[j, int(nd[j]) - 1, 1]))
+        genomes = []
+        for g in range(ng):
+            hits = []
+            for p, r in enumerate(rec[g]):
+                if r != _lib.HMM_NO_HIT:
+                    a, b = span.get(g * npf + p, (0, int(dev.aa_len[r])))
+                    hits.append(dev.residues(int(r), a, b))
+                    c, ob, oe, st = dev.coords(int(r))
+                    where[g, p] = (c - int(dev.genome_contig0[g]), ob, oe, st)
+            genomes.append(hits)
+        local = np.where(rec == _lib.HMM_NO_HIT, rec, rec - dev.genome_orf_off[:-1].astype(np.uint32)[:, None]).astype(np.uint32)
+        return genomes, local, where
+    finally:
+        dev.close()
 
 
 # ---- bigsig (binaux/src/bin/bigsig.rs; SPEC 11) -----------------------------------------------------------------------------------------

@@ -504,4 +504,16 @@ GS_HD int hmm_residue(uint8_t c)
 #endif
 }
 
+// ---- SPEC 14: orfs - stop-to-stop six-frame translation of 2-bit packed records. [CHOICE] throughout (the reference calls FragGeneScanRs; this is the
+// model-free stage of esl-translate / getorf / orfM). A codon of bases b0 b1 b2 (A C G T = 0 1 2 3) has index 16 b0 + 4 b1 + b2.
+#define GS_ORF_TABLE_11 "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSS*CWCLFLF"      // [PUB] NCBI translation table 11 (= 1 without its start rule)
+#define GS_ORF_TABLE_4 "KNKNTTTTRSRSIIMIQHQHPPPPRRRRLLLLEDEDAAAAGGGGVVVV*Y*YSSSSWCWCLFLF"       // [PUB] table 4: TGA (index 56) = W
+#define GS_ORF_STOPS_11 ((1ULL << 48) | (1ULL << 50) | (1ULL << 56))                             // TAA TAG TGA
+#define GS_ORF_STOPS_4 ((1ULL << 48) | (1ULL << 50))
+#define GS_ORF_MIN_AA 30u                // default min_aa: the shortest profile of the reference's two sets has 57 nodes
+// the codon of the reverse strand that occupies the bases of forward codon x: complement every base, reverse their order
+GS_HD uint32_t orf_rev_codon(uint32_t x) { x ^= 63u; return ((x & 3u) << 4) | (x & 12u) | (x >> 4); }
+// the codon positions of class c (p = c, c + 3, ... <= L - 3) of a record of L bases
+GS_HD uint64_t orf_class_codons(uint64_t L, uint32_t c) { return L >= 3 + (uint64_t)c ? (L - 3 - c) / 3 + 1 : 0; }
+
 }  // namespace gs

@@ -364,6 +364,32 @@ int gs_hmm_trace_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const ui
                      int32_t *raw_out_dev, uint32_t *n_dom_out_dev, int32_t *dom_out_dev);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* orfs (SPEC 14): stop-to-stop six-frame translation of packed nucleotide records on the device - the model-free way to feed hmmsearch from genomes.
+ * It is NOT a gene caller and does not replace FragGeneScanRs: the ORF set is not a proteome and must not be given to the AA sketchers or superaai.
+ * Input: the packed layout of gs_sketch_batch_dev (2-bit bases, record r = bases [rec_start[r], rec_start[r] + rec_len[r]), no invalid base inside a
+ * record, records inside seq_bytes and not overlapping). An ORF is a maximal run of codons without a stop in one of the six (strand, class mod 3)
+ * frames; `begin` is its lowest base, n its codons, end = begin + 3 n, all in forward coordinates. Kept: min_aa <= n, and n <= max_aa unless max_aa = 0;
+ * longer ones are dropped and counted. Order: ascending (record, end, strand). */
+typedef struct { uint32_t min_aa, max_aa, table, flags; } gs_orf_params;      /* table 11 or 4; flags = 0 */
+typedef struct { uint64_t begin; uint32_t rec, strand; } gs_orf;              /* begin: offset inside the record, forward coordinates; strand 0 = forward */
+#define GS_ORF_TILE 192u            /* bases one wavefront takes at a time (a codon of each class per lane); no result depends on it */
+/* host only: the 64 letters of a translation table, codon index 16 b0 + 4 b1 + b2 (A C G T = 0 1 2 3), `*` = stop; another table: GS_ERR_UNSUPPORTED */
+int gs_orf_codon_table(uint32_t table, char out[64]);
+/* n_out (HOST) = {kept ORFs, their residues, ORFs dropped as longer than max_aa}. All five output pointers NULL with zero caps: count only. With
+ * outputs: a cap below the count is GS_ERR_INVALID with n_out filled and nothing written; a partial set of pointers is GS_ERR_INVALID. aa_out: the
+ * upper-case residues of the kept ORFs back to back in ORF order; aa_start_out / aa_len_out: what gs_hmm_search_dev takes as rec_start / rec_len;
+ * rec_orf_off_out (n_rec + 1): the ORFs of record r are [off[r], off[r + 1]). min_aa = 0 or 0 < max_aa < min_aa: GS_ERR_INVALID; flags != 0, another
+ * table, 2^32 records or more, seq_bytes / 48 + n_rec >= 2^26: GS_ERR_UNSUPPORTED; a record outside seq_bytes, or records whose bases add up to more
+ * than seq holds: GS_ERR_INVALID. The device form waits for the
+ * stream once (the counts) and leaves the outputs in flight on it. */
+int gs_orf_translate_dev(gs_ctx *ctx, const gs_orf_params *prm, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev,
+                         const uint64_t *rec_len_dev, uint64_t n_rec, uint64_t cap_orf, uint64_t cap_aa, gs_orf *orf_out_dev, uint8_t *aa_out_dev,
+                         uint64_t *aa_start_out_dev, uint64_t *aa_len_out_dev, uint64_t *rec_orf_off_out_dev, uint64_t n_out[3]);
+int gs_orf_translate(gs_ctx *ctx, const gs_orf_params *prm, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len,
+                     uint64_t n_rec, uint64_t cap_orf, uint64_t cap_aa, gs_orf *orf_out, uint8_t *aa_out, uint64_t *aa_start_out, uint64_t *aa_len_out,
+                     uint64_t *rec_orf_off_out, uint64_t n_out[3]);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */
 /*   new/modify_level_scale/set_extend_candidates/set_keeping_pruned  dnasketch.rs:139-141,159-160  */
 /*   parallel_insert dnasketch.rs:435, aasketch.rs:407;  parallel_search dnarequest.rs:353, aarequest.rs:344 */

@@ -15,7 +15,8 @@ TY = {"int": "c_int", "void": "c_void", "char": "c_char", "float": "c_float", "d
       "uint16_t": "u16", "uint8_t": "u8", "int64_t": "i64", "int32_t": "i32", "gs_ctx": "GsCtx", "gs_index": "GsIndex", "gs_comm": "GsComm",
       "gs_sketch_params": "GsSketchParams", "gs_index_params": "GsIndexParams", "gs_embed_params": "GsEmbedParams", "gs_knn_stats": "GsKnnStats",
       "gs_cluster_params": "GsClusterParams", "gs_cluster_info": "GsClusterInfo", "gs_bigsi": "GsBigsi", "gs_bigsi_params": "GsBigsiParams",
-      "gs_bigsi_desc": "GsBigsiDesc", "gs_hmm_db": "GsHmmDb", "gs_hmm_info": "GsHmmInfo"}
+      "gs_bigsi_desc": "GsBigsiDesc", "gs_hmm_db": "GsHmmDb", "gs_hmm_info": "GsHmmInfo", "gs_orf_params": "GsOrfParams",
+      "gs_orf": "GsOrf"}
 
 
 def rust_type(c):
