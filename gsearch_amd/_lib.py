@@ -80,6 +80,16 @@ class OrfParamsC(C.Structure):
 
 ORF_TILE, ORF_MIN_AA = 192, 30
 
+
+class GeneParamsC(C.Structure):
+    """gs_gene_params (SPEC 15)"""
+    _fields_ = [("min_aa", C.c_uint32), ("table", C.c_uint32), ("train_min_aa", C.c_uint32), ("min_train_codons", C.c_uint32), ("min_score", C.c_int32),
+                ("max_overlap", C.c_uint32), ("rounds", C.c_uint32), ("flags", C.c_uint32)]
+
+
+GENE_STRAND, GENE_TYPE_SHIFT, GENE_TYPE_EDGE, GENE_OPEN3, GENE_HAS_START, GENE_CANDIDATE, GENE_OPEN5 = 1, 1, 3, 8, 16, 32, 64
+GENE_NO_START, GENE_TRAINED = 0xFFFFFFFFFFFFFFFF, 1
+
 HMM_MAX_M, HMM_MAX_L, HMM_NO_SCORE, HMM_NO_HIT, HMM_TABLE_ROWS = 1280, 1 << 18, -(1 << 31), 0xFFFFFFFF, 27
 HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
 HMM_FWD_MAX_L, HMM_LSE_N, HMM_FLOOR_ALL = 65536, 5903, -(1 << 31) + 1
@@ -180,6 +190,15 @@ SYMBOLS = {
     "gs_orf_codon_table": (_i, [_u32, C.c_char_p]),
     "gs_orf_translate_dev": (_i, [_vp, C.POINTER(OrfParamsC), _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "gs_orf_translate": (_i, [_vp, C.POINTER(OrfParamsC), _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    # genes (SPEC 15)
+    "gs_gene_params_default": (GeneParamsC, []),
+    "gs_gene_log2_q16": (_u32, [_u64]),
+    "gs_gene_train_dev": (_i, [_vp, C.POINTER(GeneParamsC), _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "gs_gene_train_host": (_i, [C.POINTER(GeneParamsC), _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "gs_gene_score_dev": (_i, [_vp, C.POINTER(GeneParamsC), _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "gs_gene_score_host": (_i, [C.POINTER(GeneParamsC), _vp, _u64, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "gs_gene_call_dev": (_i, [_vp, C.POINTER(GeneParamsC), _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "gs_gene_call": (_i, [_vp, C.POINTER(GeneParamsC), _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "gs_index_create": (_i, [_vp, C.POINTER(IndexParams), C.POINTER(_vp)]),
     "gs_index_destroy": (None, [_vp]),
     "gs_index_nb_point": (_u64, [_vp]),

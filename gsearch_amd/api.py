@@ -1148,14 +1148,18 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     then (ids, scores, table bytes, domain table bytes).
     translate=True (SPEC 14): `faa` is a NUCLEOTIDE FASTA; the targets are its stop-to-stop six-frame ORFs of min_aa residues and more under translation
     `table` (11 or 4), translated on the device and searched there without their residues coming back. A target is named `{contig}_{begin+1}_{end}_{+|-}`
-    as write_orf_faa() names it, Z is the number of ORFs, the formats are unchanged. The ORFs are not a proteome: no start codons, no frameshifts."""
+    as write_orf_faa() names it, Z is the number of ORFs, the formats are unchanged. The ORFs are not a proteome: no start codons, no frameshifts.
+    translate="genes" (SPEC 15): the targets are instead the genes the self-trained caller of gene_call() chooses in that file taken as one genome, called
+    on the device and searched there; names, Z and formats follow in the same way. A file too small to train has no targets. Unlike translate=True, which drops and counts an ORF longer than
+    the search takes (the smallest of the HMM_*MAX_L limits of the programs the call runs), a called gene that long raises ValueError and ends the call: a
+    gene set with one silently left out would no longer be the genome's."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     db = _as_hmm_db(hmm, ctx)
     fwd = score == "forward"
     dev = None
     if translate:
-        dev = _DevOrfs(db.ctx, [_fna_contigs(faa)], min_aa, _orf_max_aa(fwd, domains is not None), table)
+        dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd, domains is not None), table)
         try:
             ids = dev.names()
             scores = dev.search(db, fwd, filter_p)
@@ -1221,14 +1225,17 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     translation `table`, translated and searched on the device - only the chosen hits' residues come back. The record numbers are then ORF numbers inside
     the genome, and a third value is returned: int64 [n_genomes, n_prof, 4] = (contig index, begin, end, strand) of the chosen ORF in contig coordinates
     (0-based, end exclusive, strand 0 / 1 = + / -), -1 where a profile found nothing. A stop-to-stop ORF overhangs the gene at its 5' end;
-    region="aligned" trims that. The ORF set is not a proteome and is not meant for the AA sketchers as a whole."""
+    region="aligned" trims that. The ORF set is not a proteome and is not meant for the AA sketchers as a whole.
+    translate="genes" (SPEC 15): the candidates are the genes of gene_call(), every file one self-trained genome; the record numbers are gene numbers
+    inside the genome and the coordinates are the gene's, from its start codon through its stop codon. A called gene longer than the search takes raises
+    ValueError and ends the call (translate=True drops and counts such an ORF; see hmmsearch)."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     if region not in ("protein", "aligned"):
         raise ValueError("region: 'protein' or 'aligned'")
     db = _as_hmm_db(hmm, ctx)
     if translate:
-        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table)
+        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate)
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
@@ -1481,9 +1488,9 @@ class _DevOrfs:
         return self.ctx.download(self.d_aa + int(self.aa_start[j]) + a, (b - a,), np.uint8).tobytes()
 
 
-def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table):
+def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True):
     ctx = db.ctx
-    dev = _DevOrfs(ctx, [_fna_contigs(p) for p in fna_files], min_aa, _orf_max_aa(fwd, aligned), table)
+    dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd, aligned), table)
     try:
         ng, npf = len(fna_files), len(db)
         rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
@@ -1512,6 +1519,267 @@ def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, m
         return genomes, local, where
     finally:
         dev.close()
+
+
+# ---- genes (SPEC 15): a self-trained gene caller on the device --------------------------------------------------------------------------------
+GENE_DTYPE = np.dtype([("begin", np.uint64), ("end", np.uint64), ("score", np.int64), ("rec", np.uint32), ("flags", np.uint32)])      # gs_gene
+GENE_INTERVAL_DTYPE = np.dtype([("begin", np.uint64), ("n", np.uint64), ("rec", np.uint32), ("strand", np.uint32)])                   # gs_gene_interval
+GENE_START_TYPES = ("ATG", "GTG", "TTG", "edge")
+
+
+def gene_params(**kw):
+    """gs_gene_params: the defaults of SPEC 15 (min_aa 30, table 11, train_min_aa 250, min_train_codons 15000, min_score 5120, max_overlap 60, rounds 2)
+    with the given fields replaced"""
+    prm = _lib.load().gs_gene_params_default()
+    for k, v in kw.items():
+        if k not in [f for f, _ in _lib.GeneParamsC._fields_]:
+            raise TypeError("no gene parameter %r" % k)
+        setattr(prm, k, int(v))
+    return prm
+
+
+def gene_log2_q16(x):
+    """floor(65536 log2 x) by the integer recurrence of SPEC 15 (host only)"""
+    return int(_lib.load().gs_gene_log2_q16(int(x)))
+
+
+def _gene_inputs(seq, rec_start, rec_len, genome_rec_off):
+    return (np.ascontiguousarray(seq, dtype=np.uint8), np.ascontiguousarray(rec_start, dtype=np.uint64), np.ascontiguousarray(rec_len, dtype=np.uint64),
+            np.ascontiguousarray(genome_rec_off, dtype=np.uint64))
+
+
+class _DevScope:
+    """device buffers of one call, freed together"""
+
+    def __init__(self, ctx):
+        self.ctx, self.bufs = ctx, []
+
+    def new(self, nbytes):
+        ptr = self.ctx.alloc(max(int(nbytes), 16))
+        self.bufs.append(ptr)
+        return ptr
+
+    def up(self, arr):
+        ptr = self.new(arr.nbytes)
+        if arr.nbytes:
+            self.ctx.upload(ptr, arr)
+        return ptr
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        while self.bufs:
+            self.ctx.free(self.bufs.pop())
+
+
+def gene_train(seq, rec_start, rec_len, genome_rec_off, intervals, ctx=None, host=False, **params):
+    """SPEC 15, counts to tables: the hexamer background of every genome and the in-frame dicodon counts of `intervals` (GENE_INTERVAL_DTYPE, in record
+    order) -> (int32 [n_genomes, 4096] score tables, uint64 [n_genomes, 2] = (Nc, trained)). host=True: gs_gene_train_host, the same definitions in
+    plain loops without a device; else gs_gene_train_dev."""
+    seq, rs, rl, goff = _gene_inputs(seq, rec_start, rec_len, genome_rec_off)
+    iv = np.ascontiguousarray(intervals, dtype=GENE_INTERVAL_DTYPE)
+    ng = len(goff) - 1
+    prm = gene_params(**params)
+    tables, info = np.zeros((ng, 4096), np.int32), np.zeros((ng, 2), np.uint64)
+    if host:
+        check(_lib.load().gs_gene_train_host(C.byref(prm), _p(seq), seq.nbytes, _p(rs), _p(rl), len(rs), _p(goff), ng, _p(iv), len(iv), _p(tables), _p(info)))
+        return tables, info
+    ctx = ctx or default_context()
+    with _DevScope(ctx) as d:
+        d_t, d_i = d.new(tables.nbytes), d.new(info.nbytes)
+        check(ctx.L.gs_gene_train_dev(ctx.h, C.byref(prm), d.up(seq), seq.nbytes, d.up(rs), d.up(rl), len(rs), d.up(goff), ng, d.up(iv), len(iv), d_t, d_i))
+        return ctx.download(d_t, tables.shape, np.int32), ctx.download(d_i, info.shape, np.uint64)
+
+
+def gene_score(seq, rec_start, rec_len, genome_rec_off, tables, orf, orf_len, ctx=None, host=False, **params):
+    """SPEC 15, the best start of every given ORF (ORF_DTYPE descriptors and their codon counts) under the caller's int32 [n_genomes, 4096] tables ->
+    (uint64 best j or GENE_NO_START, int64 score, uint32 flags). host=True: gs_gene_score_host, no device; else gs_gene_score_dev."""
+    seq, rs, rl, goff = _gene_inputs(seq, rec_start, rec_len, genome_rec_off)
+    ng = len(goff) - 1
+    tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(ng, 4096)
+    orf, ol = np.ascontiguousarray(orf, dtype=ORF_DTYPE), np.ascontiguousarray(orf_len, dtype=np.uint64)
+    if len(orf) != len(ol):
+        raise ValueError("one length per ORF")
+    prm = gene_params(**params)
+    n = len(orf)
+    bj, sc, fl = np.zeros(n, np.uint64), np.zeros(n, np.int64), np.zeros(n, np.uint32)
+    if host:
+        check(_lib.load().gs_gene_score_host(C.byref(prm), _p(seq), seq.nbytes, _p(rs), _p(rl), len(rs), _p(goff), ng, _p(tables), _p(orf), _p(ol), n, _p(bj), _p(sc), _p(fl)))
+        return bj, sc, fl
+    ctx = ctx or default_context()
+    with _DevScope(ctx) as d:
+        d_j, d_s, d_f = d.new(8 * n), d.new(8 * n), d.new(4 * n)
+        check(ctx.L.gs_gene_score_dev(ctx.h, C.byref(prm), d.up(seq), seq.nbytes, d.up(rs), d.up(rl), len(rs), d.up(goff), ng, d.up(tables), d.up(orf), d.up(ol), n,
+                                      d_j, d_s, d_f))
+        return ctx.download(d_j, (n,), np.uint64), ctx.download(d_s, (n,), np.int64), ctx.download(d_f, (n,), np.uint32)
+
+
+def gene_call_dev(ctx, seq_dev, seq_bytes, rec_start_dev, rec_len_dev, n_rec, genome_rec_off_dev, n_genomes, info_out_dev, cap_gene=0, cap_aa=0, gene_out_dev=None,
+                  aa_out_dev=None, aa_start_out_dev=None, aa_len_out_dev=None, rec_gene_off_out_dev=None, tables_out_dev=None, **params):
+    """gs_gene_call_dev: all arrays device memory, the outputs left in flight on the context's stream -> (n_gene, n_aa), also when the capacities are too
+    small (GsError then carries them as .counts). No gene outputs and zero capacities: count only."""
+    prm = gene_params(**params)
+    n = (C.c_uint64 * 2)()
+    try:
+        check(ctx.L.gs_gene_call_dev(ctx.h, C.byref(prm), seq_dev, int(seq_bytes), rec_start_dev, rec_len_dev, int(n_rec), genome_rec_off_dev, int(n_genomes), int(cap_gene),
+                                     int(cap_aa), gene_out_dev, aa_out_dev, aa_start_out_dev, aa_len_out_dev, rec_gene_off_out_dev, info_out_dev, tables_out_dev, n))
+    except GsError as e:
+        e.counts = (int(n[0]), int(n[1]))
+        raise
+    return int(n[0]), int(n[1])
+
+
+def gene_call_packed(seq, rec_start, rec_len, genome_rec_off, ctx=None, tables=False, **params):
+    """SPEC 15 on the packed layout of pack_dna_records(): every genome (records [genome_rec_off[g], genome_rec_off[g + 1])) trains its own dicodon model
+    on its long ORFs and gets the maximal-weight chain of nearly non-overlapping genes of every record -> dict of `gene` (GENE_DTYPE, ascending by
+    (record, end, strand), forward coordinates inside the record, stop codon included where there is one), `aa` (residues from the start codon to the
+    last sense codon), `aa_start`, `aa_len`, `rec_gene_off` (n_rec + 1), `info` (uint64 [n_genomes, 2] = (Nc, trained)) and, when asked for, `tables`.
+    A genome too small to train gets no genes. Not FragGeneScanRs and not its numbers (DESIGN "Known limitations (genes)")."""
+    ctx = ctx or default_context()
+    seq, rs, rl, goff = _gene_inputs(seq, rec_start, rec_len, genome_rec_off)
+    ng = len(goff) - 1
+    prm = gene_params(**params)
+    cap_gene, cap_aa = _orf_caps(rl, prm.min_aa)
+    gene, aa = np.zeros(cap_gene, GENE_DTYPE), np.zeros(cap_aa, np.uint8)
+    a_s, a_l, off = np.zeros(cap_gene, np.uint64), np.zeros(cap_gene, np.uint64), np.zeros(len(rs) + 1, np.uint64)
+    info, tab = np.zeros((ng, 2), np.uint64), (np.zeros((ng, 4096), np.int32) if tables else None)
+    n = (C.c_uint64 * 2)()
+    check(ctx.L.gs_gene_call(ctx.h, C.byref(prm), _p(seq) if seq.nbytes else None, seq.nbytes, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs), _p(goff),
+                             ng, cap_gene, cap_aa, _p(gene), _p(aa), _p(a_s), _p(a_l), _p(off), _p(info), _p(tab), n))
+    out = {"gene": gene[:n[0]].copy(), "aa": aa[:n[1]].copy(), "aa_start": a_s[:n[0]].copy(), "aa_len": a_l[:n[0]].copy(), "rec_gene_off": off, "info": info}
+    if tables:
+        out["tables"] = tab
+    return out
+
+
+def _gene_segments(genomes):
+    """genomes (lists of ASCII contigs) -> (records, contig of each record, its offset there, genome_rec_off, first contig of every genome)"""
+    contigs = [c for g in genomes for c in g]
+    contig0 = np.concatenate([[0], np.cumsum([len(g) for g in genomes])]).astype(np.int64)
+    recs, rc, ro = _orf_segments(contigs)
+    goff = np.searchsorted(rc, contig0).astype(np.uint64)
+    return recs, rc, ro, goff, contig0
+
+
+def gene_call(genomes, ctx=None, **params):
+    """genomes: a list of genomes, each a list of ASCII contigs (bytes, no line breaks) -> (per genome and contig the list of (begin, end, strand, protein,
+    score, flags) in contig coordinates - 0-based, end exclusive, the stop codon included where there is one, ascending by (end, strand) -, the flat dict
+    of gene_call_packed() with `rec_contig`, `rec_offset` and `genome_rec_off`). A contig is cut at every byte outside ACGTacgt; a gene never spans a cut."""
+    recs, rc, ro, goff, contig0 = _gene_segments(genomes)
+    seq, rs, rl = pack_dna_records(recs)
+    flat = gene_call_packed(seq, rs, rl, goff, ctx, **params)
+    flat["rec_contig"], flat["rec_offset"], flat["genome_rec_off"] = rc, ro, goff
+    out = [[[] for _ in g] for g in genomes]
+    aa = flat["aa"].tobytes()
+    for gn, a, n in zip(flat["gene"], flat["aa_start"], flat["aa_len"]):
+        ci, off = int(rc[gn["rec"]]), int(ro[gn["rec"]])
+        gi = int(np.searchsorted(contig0, ci, side="right")) - 1
+        out[gi][ci - int(contig0[gi])].append((off + int(gn["begin"]), off + int(gn["end"]), int(gn["flags"]) & 1, aa[int(a):int(a) + int(n)], int(gn["score"]), int(gn["flags"])))
+    return out, flat
+
+
+def write_gene_faa(path, contig_ids, genes):
+    """genes: per contig the tuples of gene_call() -> a protein FASTA with headers `>{contig}_{begin+1}_{end}_{+|-}` (as write_orf_faa), one line per gene"""
+    if len(contig_ids) != len(genes):
+        raise ValueError("one id per contig")
+    with open(path, "wb") as f:
+        for cid, lst in zip(contig_ids, genes):
+            for g in lst:
+                f.write(b">" + _orf_name(cid, g[0], g[1], g[2]).encode() + b"\n" + bytes(g[3]) + b"\n")
+
+
+_DNA_COMPLEMENT = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def write_gene_ffn(path, contig_ids, contigs, genes):
+    """the genes' bases in reading direction (the stop codon included where there is one), upper case, same headers"""
+    if len(contig_ids) != len(genes) or len(contigs) != len(genes):
+        raise ValueError("one id and one sequence per contig")
+    with open(path, "wb") as f:
+        for cid, ctg, lst in zip(contig_ids, contigs, genes):
+            for g in lst:
+                nt = bytes(ctg[g[0]:g[1]])
+                if g[2]:
+                    nt = nt.translate(_DNA_COMPLEMENT)[::-1]
+                f.write(b">" + _orf_name(cid, g[0], g[1], g[2]).encode() + b"\n" + nt.upper() + b"\n")
+
+
+def write_gene_gff(path, contig_ids, genes):
+    """GFF3: one CDS line per gene - 1-based closed coordinates, the score in bits (%.2f of score / 1024), phase 0, attributes ID (the FASTA header),
+    start_type (ATG / GTG / TTG / edge) and partial (two digits: 1 = no start codon at the 5' end, 1 = no stop codon at the 3' end)"""
+    if len(contig_ids) != len(genes):
+        raise ValueError("one id per contig")
+    with open(path, "wb") as f:
+        f.write(b"##gff-version 3\n")
+        for cid, lst in zip(contig_ids, genes):
+            for b, e, s, _, score, flags in lst:
+                t = (flags >> _lib.GENE_TYPE_SHIFT) & 3
+                f.write(("%s\tgsearch_amd\tCDS\t%d\t%d\t%.2f\t%s\t0\tID=%s;start_type=%s;partial=%d%d\n" % (
+                    cid, b + 1, e, score / 1024.0, "-" if s else "+", _orf_name(cid, b, e, s), GENE_START_TYPES[t], int(t == _lib.GENE_TYPE_EDGE),
+                    int(bool(flags & _lib.GENE_OPEN3)))).encode())
+
+
+def genecall(fna, prefix, ctx=None, **params):
+    """Library counterpart of `FragGeneScanRs -s genome.fna -o prefix -w 1 -t complete` by another method (SPEC 15: self-trained, not FragGeneScan's
+    trained model, not its numbers): the genes of one genome file (.fna, also .gz) -> `prefix.faa`, `prefix.ffn`, `prefix.gff`. Returns a dict of
+    n_genes, trained and Nc. A genome too small to train (short contigs or plasmids alone) gives empty files and trained = False."""
+    recs = _fna_contigs(fna)
+    ids, contigs = [r[0] for r in recs], [bytes(r[1]) for r in recs]
+    genes, flat = gene_call([contigs], ctx, **params)
+    write_gene_faa(prefix + ".faa", ids, genes[0])
+    write_gene_ffn(prefix + ".ffn", ids, contigs, genes[0])
+    write_gene_gff(prefix + ".gff", ids, genes[0])
+    return {"n_genes": len(flat["gene"]), "trained": bool(flat["info"][0, 1] & _lib.GENE_TRAINED), "Nc": int(flat["info"][0, 0])}
+
+
+class _DevGenes(_DevOrfs):
+    """The genes of some genomes (SPEC 15) in the place of their ORFs: called on the device and kept there in the same layout, so every search of
+    _DevOrfs runs on them unchanged. `orf` holds begin, rec and strand of each gene; `end` its end (the stop codon included where there is one)."""
+
+    def __init__(self, ctx, genomes, min_aa, max_aa, table):
+        self.ctx, self.bufs = ctx, []
+        self.contig_ids = [cid for g in genomes for cid, _ in g]
+        recs, self.rec_contig, self.rec_offset, goff, contig0 = _gene_segments([[c for _, c in g] for g in genomes])
+        self.genome_contig0 = contig0
+        seq, rs, rl = pack_dna_records(recs)
+        cap_gene, cap_aa = _orf_caps(rl, min_aa)
+        n_rec, ng = len(rs), len(genomes)
+        try:
+            d_seq, d_rs, d_rl, d_goff = self._up(seq), self._up(rs), self._up(rl), self._up(goff)
+            d_gene, self.d_aa, self.d_as, self.d_al = self._new(GENE_DTYPE.itemsize * cap_gene), self._new(cap_aa), self._new(8 * cap_gene), self._new(8 * cap_gene)
+            d_off, d_info = self._new(8 * (n_rec + 1)), self._new(16 * ng)
+            self.n, _ = gene_call_dev(ctx, d_seq, seq.nbytes, d_rs, d_rl, n_rec, d_goff, ng, d_info, cap_gene, cap_aa, d_gene, self.d_aa, self.d_as, self.d_al, d_off,
+                                      min_aa=min_aa, table=table)
+            self.n_long = 0
+            gene = ctx.download(d_gene, (self.n,), GENE_DTYPE)
+            self.aa_start = ctx.download(self.d_as, (self.n,), np.uint64)
+            self.aa_len = ctx.download(self.d_al, (self.n,), np.uint64)
+            rec_off = ctx.download(d_off, (n_rec + 1,), np.uint64)
+            self.info = ctx.download(d_info, (ng, 2), np.uint64)
+            for ptr in (d_seq, d_rs, d_rl, d_goff, d_gene, d_off, d_info):
+                self._free(ptr)
+        except Exception:
+            self.close()
+            raise
+        if max_aa and self.n and int(self.aa_len.max()) > max_aa:
+            self.close()
+            raise ValueError("a gene of %d residues is longer than the %d the search takes" % (int(self.aa_len.max()), max_aa))
+        self.orf = np.zeros(self.n, ORF_DTYPE)
+        self.orf["begin"], self.orf["rec"], self.orf["strand"] = gene["begin"], gene["rec"], gene["flags"] & 1
+        self.end = gene["end"]
+        self.genome_orf_off = rec_off[goff.astype(np.int64)].astype(np.uint64)
+
+    def coords(self, j):
+        o = self.orf[j]
+        off = int(self.rec_offset[o["rec"]])
+        return int(self.rec_contig[o["rec"]]), off + int(o["begin"]), off + int(self.end[j]), int(o["strand"])
+
+
+def _dev_targets(ctx, genomes, translate, min_aa, max_aa, table):
+    if translate == "genes":
+        return _DevGenes(ctx, genomes, min_aa, max_aa, table)
+    return _DevOrfs(ctx, genomes, min_aa, max_aa, table)
 
 
 # ---- bigsig (binaux/src/bin/bigsig.rs; SPEC 11) -----------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 #include <string.h>
 #include "gs_internal.hpp"
 #include "gs_spec.hpp"
+#include "gs_orf.hpp"
 
 namespace gs {
 
@@ -129,14 +130,6 @@ template <bool MAX> __global__ __launch_bounds__(256) void k_orf_scan_apply(uint
 }
 
 // ---- the tile passes ------------------------------------------------------------------------------------------------------------------------------------------
-struct OrfArgs {
-    const uint8_t *seq; const uint64_t *rec_start, *rec_len, *rtoff, *meta;
-    uint64_t n_rec, cap_tiles;
-    uint64_t *stops;                       // [6][cap_tiles], pair q = 2 class + strand
-    uint64_t *counts;                      // [3][cap_tiles]: kept ORFs, residues, long drops
-    uint64_t stop_mask; uint32_t min_aa, max_aa, table_ix;
-    gs_orf *orf; uint8_t *aa; uint64_t *aa_start, *aa_len;
-};
 struct OrfEntry { uint64_t begin_strand, n, aoff; };            // begin | strand << 63
 __device__ __forceinline__ uint32_t orf_top_bit(uint64_t x) { return 63u - (uint32_t)__builtin_clzll(x); }
 __device__ __forceinline__ uint64_t orf_wave_sum(uint64_t x)
@@ -268,7 +261,7 @@ template <int MODE> __global__ __launch_bounds__(64) void k_orf_tile(const OrfAr
             // the residues: one ORF at a time, the lanes stride over its codons (byte stores side by side, codons gathered from the packed bases)
             const uint32_t n_list = (uint32_t)(k_stops + vk);
             const char *letters = orf_letters[a.table_ix];
-            for (uint32_t j = 0; j < n_list; j++) {
+            for (uint32_t j = 0; a.aa && j < n_list; j++) {         // (no aa: the descriptors alone, gs_gene.hip)
                 const OrfEntry e = list[j];
                 const uint64_t b = e.begin_strand & ~((uint64_t)1 << 63), end = b + 3 * e.n;
                 const bool rev = e.begin_strand >> 63;
@@ -290,12 +283,6 @@ __global__ __launch_bounds__(256) void k_orf_rec_off(const uint64_t *__restrict_
     const uint64_t t = rtoff[r];
     rec_orf_off[r] = t < meta[ORF_META_TILES] ? counts[t] : meta[ORF_META_N_ORF];
 }
-
-struct OrfWork {
-    PoolBuf rtoff, meta, stops, counts, partials;
-    OrfArgs a{};
-    explicit OrfWork(gs_ctx *c) : rtoff(c, SL_ORF_REC_TILES), meta(c, SL_ORF_META), stops(c, SL_ORF_STOPS), counts(c, SL_ORF_COUNTS), partials(c, SL_ORF_PARTIALS) {}
-};
 
 static int orf_check_params(const gs_orf_params *prm, uint64_t n_rec)
 {
@@ -324,7 +311,7 @@ static int orf_check_caps(const uint64_t n_out[3], uint64_t cap_orf, uint64_t ca
 }
 
 // the passes up to the counts: n_out filled, the scanned per-tile state left in w for orf_emit. Waits for the stream once.
-static int orf_count(gs_ctx *c, const gs_orf_params *prm, const uint8_t *seq, uint64_t seq_bytes, const uint64_t *rs, const uint64_t *rl, uint64_t n_rec, OrfWork &w,
+int orf_count(gs_ctx *c, const gs_orf_params *prm, const uint8_t *seq, uint64_t seq_bytes, const uint64_t *rs, const uint64_t *rl, uint64_t n_rec, OrfWork &w,
                      uint64_t n_out[3])
 {
     GS_REQUIRE(seq_bytes < (1ull << 61), GS_ERR_UNSUPPORTED, "orf: seq_bytes");
@@ -360,7 +347,7 @@ static int orf_count(gs_ctx *c, const gs_orf_params *prm, const uint8_t *seq, ui
     return GS_OK;
 }
 // queued on c's stream behind orf_count; nothing is waited for
-static int orf_emit(gs_ctx *c, uint64_t n_rec, OrfWork &w, gs_orf *orf, uint8_t *aa, uint64_t *aa_start, uint64_t *aa_len, uint64_t *rec_orf_off)
+int orf_emit(gs_ctx *c, uint64_t n_rec, OrfWork &w, gs_orf *orf, uint8_t *aa, uint64_t *aa_start, uint64_t *aa_len, uint64_t *rec_orf_off)
 {
     OrfArgs &a = w.a;
     a.orf = orf; a.aa = aa; a.aa_start = aa_start; a.aa_len = aa_len;

@@ -82,6 +82,15 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
        residues and long drops (each scanned in place); the partial results of those scans; staging of the host form */                                 \
     X(ORF_REC_TILES) X(ORF_META) X(ORF_STOPS) X(ORF_COUNTS) X(ORF_PARTIALS) X(ORFB_SEQ) X(ORFB_REC_START) X(ORFB_REC_LEN) X(ORFB_ORF) X(ORFB_AA)         \
     X(ORFB_AA_START) X(ORFB_AA_LEN) X(ORFB_REC_OFF)                                                                                                    \
+    /* genes (gs_gene.hip): per genome the hexamer counts of both strands and the in-frame dicodon counts of the training intervals; the call's error word */ \
+    X(GENE_BG) X(GENE_COD) X(GENE_META)                                                                                                                \
+    /* genes, a call: the ORF descriptors, the tables, one training interval per ORF, every ORF's best start; two columns and their prefix sums; the     \
+       candidates' keys, sorted, and the candidates in (record, end, strand) order; per record their range, per candidate k(i), the running maximum of   \
+       the chain and who reaches it, the predecessor, the choice; staging of the host form */                                                            \
+    X(GENE_ORF) X(GENE_ORF_LEN) X(GENE_ORF_START) X(GENE_ORF_OFF) X(GENE_TABLES) X(GENE_IV) X(GENE_BEST_J) X(GENE_SCORE) X(GENE_FLAGS) X(GENE_COL0)     \
+    X(GENE_COL1) X(GENE_SCAN0) X(GENE_SCAN1) X(GENE_KEYS) X(GENE_KEYS_ALT) X(GENE_RADIX) X(GENE_CAND_ORF) X(GENE_CAND) X(GENE_REC_CAND) X(GENE_K)      \
+    X(GENE_PMAX) X(GENE_PARG) X(GENE_PRED) X(GENE_CHOSEN) X(GENEB_SEQ) X(GENEB_REC_START) X(GENEB_REC_LEN) X(GENEB_GOFF) X(GENEB_INFO) X(GENEB_TABLES) \
+    X(GENEB_GENE) X(GENEB_AA) X(GENEB_AA_START) X(GENEB_AA_LEN) X(GENEB_REC_OFF) X(GENE_SCAN_SUMS) X(GENE_SCAN_OFFS)                                                                      \
     /* comm (gs_topk_merge_dev) */                                                                                                                    \
     X(COMM_ID_OFFSET)
 

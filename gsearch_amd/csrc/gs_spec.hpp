@@ -516,4 +516,52 @@ GS_HD uint32_t orf_rev_codon(uint32_t x) { x ^= 63u; return ((x & 3u) << 4) | (x
 // the codon positions of class c (p = c, c + 3, ... <= L - 3) of a record of L bases
 GS_HD uint64_t orf_class_codons(uint64_t L, uint32_t c) { return L >= 3 + (uint64_t)c ? (L - 3 - c) / 3 + 1 : 0; }
 
+// ---- SPEC 15: genes - a self-trained gene caller. [CHOICE] throughout (the self-trained kind of [PUB] Prodigal / GeneMarkS; the reference calls
+// FragGeneScanRs, whose trained model files it does not hold). All integer arithmetic; what the host functions and the kernels share is below.
+#define GS_GENE_TRAIN_MIN_AA 250u        // round 1 trains on the whole ORFs of this many codons and more
+#define GS_GENE_MIN_TRAIN_CODONS 15000u  // a genome with fewer training dicodons is untrained (the method was tried at 19 252, nothing lower)
+#define GS_GENE_PRIOR 4096u              // A: pseudo-count mass of the prior, spread in proportion to the background
+#define GS_GENE_MIN_SCORE 5120           // 5 bits
+#define GS_GENE_MAX_OVERLAP 60u
+#define GS_GENE_ROUNDS 2u
+#define GS_GENE_BONUS_GTG (-2048)
+#define GS_GENE_BONUS_TTG (-3072)
+#define GS_GENE_S_LIMIT 32768            // |S[h]| <= 32 bits x 1024 whatever the counts (SPEC 15); a table entry outside is not a table's
+#define GS_GENE_MAX_NB ((1ull << 31) + 4096)     // Nb of a genome of 2^30 hexamer positions; beyond it, or with Nc + A > 2^32, a product may leave 64 bits
+#define GS_GENE_MAX_NC_A (1ull << 32)
+#define GS_GENE_MAX_INTERVAL (1u << 24)  // codons of one training interval (a workgroup counts 256 intervals in 32-bit LDS words)
+#define GS_GENE_ATG 14u
+#define GS_GENE_GTG 46u
+#define GS_GENE_TTG 62u
+// floor(65536 log2 x) for x >= 1, never above it and less than 2^-16 + 2^-28 below log2 x: normalise to a mantissa m in [2^31, 2^32) (bits below are
+// cut), then sixteen times square m (a 64-bit product), cut to 32 bits again, and take the next fraction bit = whether the square reached 2
+GS_HD uint32_t gene_log2_q16(uint64_t x)
+{
+    if (x == 0) return 0;
+    const uint32_t e = 63u - (uint32_t)__builtin_clzll(x);
+    uint64_t m = e >= 31 ? x >> (e - 31) : x << (31 - e);
+    uint32_t r = e;
+    for (int i = 0; i < 16; i++) {
+        m = (m * m) >> 31;
+        r <<= 1;
+        if (m >> 32) { m >>= 1; r |= 1u; }
+    }
+    return r;
+}
+// S[h] = the difference of the two logarithms, rounded half up to 10 fraction bits
+GS_HD int32_t gene_table_entry(uint64_t cod, uint64_t b, uint64_t Nc, uint64_t Nb)
+{
+    const int64_t d = (int64_t)gene_log2_q16(cod * Nb + (uint64_t)GS_GENE_PRIOR * b) - (int64_t)gene_log2_q16((Nc + GS_GENE_PRIOR) * b);
+    return (int32_t)((d + 32 + ((int64_t)1 << 40)) / 64 - ((int64_t)1 << 34));          // floor((d + 32) / 64), by a division of a positive number
+}
+// the hexamer of the reverse strand that occupies the bases of forward hexamer h
+GS_HD uint32_t gene_rev_hexamer(uint32_t h)
+{
+    h ^= 0xFFFu;
+    return ((h & 3u) << 10) | ((h & 0xCu) << 6) | ((h & 0x30u) << 2) | ((h & 0xC0u) >> 2) | ((h & 0x300u) >> 6) | (h >> 10);
+}
+// start type of a codon: 0 ATG, 1 GTG, 2 TTG, -1 no start
+GS_HD int gene_start_type(uint32_t codon) { return codon == GS_GENE_ATG ? 0 : codon == GS_GENE_GTG ? 1 : codon == GS_GENE_TTG ? 2 : -1; }
+GS_HD int64_t gene_start_bonus(int type) { return type == 1 ? GS_GENE_BONUS_GTG : type == 2 ? GS_GENE_BONUS_TTG : 0; }
+
 }  // namespace gs

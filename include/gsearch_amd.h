@@ -390,6 +390,76 @@ int gs_orf_translate(gs_ctx *ctx, const gs_orf_params *prm, const void *seq, uin
                      uint64_t *rec_orf_off_out, uint64_t n_out[3]);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* genes (SPEC 15): a self-trained gene caller for complete prokaryotic genomes on the device - the way from genomes to the proteomes that the AA
+ * sketchers, superaai and hmmsearch read. Every genome learns in-frame dicodon statistics from its own long ORFs, every ORF's candidate starts are scored
+ * with them, and a maximal-weight chain of nearly non-overlapping genes is chosen per record on both strands. It is the self-trained kind of Prodigal and
+ * GeneMarkS, NOT FragGeneScanRs (whose trained models the reference does not hold) and it does not give that program's numbers: no ribosome-binding-site
+ * model, no error or frameshift model (complete genomes, not reads), no pre-trained model (a genome too small to train gets no genes), tables 11 and 4.
+ * Input: the packed layout of gs_orf_translate_dev, genome g = records [genome_rec_off[g], genome_rec_off[g + 1]) with genome_rec_off[0] = 0 and
+ * genome_rec_off[n_genomes] = n_rec. All integer arithmetic: every result is a function of the input alone. */
+typedef struct {
+    uint32_t min_aa, table;                 /* as gs_orf_params; default 30, 11 */
+    uint32_t train_min_aa;                  /* round 1 trains on the whole ORFs of this many codons and more; default 250 */
+    uint32_t min_train_codons;              /* a genome with fewer training dicodons is untrained and gets no genes; default 15000 */
+    int32_t min_score;                      /* a gene's least score, 1024 = 1 bit; default 5120 */
+    uint32_t max_overlap;                   /* bases two chosen genes may share; below 3 * min_aa; default 60 */
+    uint32_t rounds;                        /* training rounds, >= 1; default 2 */
+    uint32_t flags;                         /* 0 */
+} gs_gene_params;
+/* a training interval: n codons at bases [begin, begin + 3 n) of record rec (forward coordinates), read on strand 0 / 1 */
+typedef struct { uint64_t begin, n; uint32_t rec, strand; } gs_gene_interval;
+/* a gene: bases [begin, end) of record rec in forward coordinates, the stop codon included where there is one */
+typedef struct { uint64_t begin, end; int64_t score; uint32_t rec, flags; } gs_gene;
+#define GS_GENE_STRAND 1u                   /* flags: bit 0 the strand */
+#define GS_GENE_TYPE_SHIFT 1                /*        bits 1-2 the start: 0 ATG, 1 GTG, 2 TTG, 3 the record's edge */
+#define GS_GENE_TYPE_EDGE 3u
+#define GS_GENE_OPEN3 8u                    /*        no stop ends it: it runs into the record's edge */
+#define GS_GENE_HAS_START 16u               /*        (gs_gene_score*) the ORF has a candidate start */
+#define GS_GENE_CANDIDATE 32u               /*        (gs_gene_score*) and its score is min_score or more */
+#define GS_GENE_OPEN5 64u                   /*        (gs_gene_score*) no stop precedes the ORF */
+#define GS_GENE_NO_START 0xFFFFFFFFFFFFFFFFull
+#define GS_GENE_TRAINED 1u                  /* info[2 g + 1] */
+/* host only: the defaults above */
+gs_gene_params gs_gene_params_default(void);
+/* host only: floor(65536 log2 x) of SPEC 15 (x >= 1; 0 for x = 0), the logarithm behind the score tables */
+uint32_t gs_gene_log2_q16(uint64_t x);
+/* Stage 1, counts to tables. tables_out: [n_genomes][4096] scores S[64 c + c'] of codon c followed in frame by c', 1024 = 1 bit; info_out:
+ * [n_genomes][2] = {Nc, GS_GENE_TRAINED or 0}. The intervals are ordered by record. GS_ERR_INVALID: bad parameters (max_overlap >= 3 * min_aa among them),
+ * a record outside seq_bytes, genome_rec_off not ascending from 0 to n_rec, an interval outside its record, out of record order or with strand > 1;
+ * GS_ERR_UNSUPPORTED: a genome of more than 2^30 hexamer positions or 2^32 - 4096 training dicodons, an interval of 2^24 codons or more. Waits for the
+ * stream once (the error word). */
+int gs_gene_train_dev(gs_ctx *ctx, const gs_gene_params *prm, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev,
+                      const uint64_t *rec_len_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes,
+                      const gs_gene_interval *iv_dev, uint64_t n_iv, int32_t *tables_out_dev, uint64_t *info_out_dev);
+/* the same on the host, host memory throughout, no device */
+int gs_gene_train_host(const gs_gene_params *prm, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                       const uint64_t *genome_rec_off, uint64_t n_genomes, const gs_gene_interval *iv, uint64_t n_iv, int32_t *tables_out,
+                       uint64_t *info_out);
+/* Stage 2, the best start of every given ORF (gs_orf + its codons orf_len) under the caller's tables: best_j_out = the codon the gene starts at or
+ * GS_GENE_NO_START, score_out its score (0 without a start), flags_out the strand, start type, GS_GENE_OPEN3 / OPEN5 / HAS_START / CANDIDATE.
+ * GS_ERR_INVALID also for an ORF outside its record or without codons and for a table entry outside +-32768. Waits for the stream once. */
+int gs_gene_score_dev(gs_ctx *ctx, const gs_gene_params *prm, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev,
+                      const uint64_t *rec_len_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes, const int32_t *tables_dev,
+                      const gs_orf *orf_dev, const uint64_t *orf_len_dev, uint64_t n_orf, uint64_t *best_j_out_dev, int64_t *score_out_dev,
+                      uint32_t *flags_out_dev);
+int gs_gene_score_host(const gs_gene_params *prm, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                       const uint64_t *genome_rec_off, uint64_t n_genomes, const int32_t *tables, const gs_orf *orf, const uint64_t *orf_len,
+                       uint64_t n_orf, uint64_t *best_j_out, int64_t *score_out, uint32_t *flags_out);
+/* The whole pipeline. n_out (HOST) = {genes, their residues}. gene_out in (record, end, strand) order; aa_out the residues from the start codon to the
+ * last sense codon back to back, the first one M unless the start is the record's edge; aa_start_out / aa_len_out / rec_gene_off_out (n_rec + 1) in
+ * the layout of gs_orf_translate_dev, so gs_hmm_search_dev takes them unchanged. info_out: [n_genomes][2] as above, of the last round. tables_out
+ * (optional): the last round's tables. The five gene outputs all NULL with zero caps: count only (info_out and tables_out are still written); a cap
+ * below the count is GS_ERR_INVALID with n_out filled; a partial set of pointers is GS_ERR_INVALID. An untrained genome is no error. */
+int gs_gene_call_dev(gs_ctx *ctx, const gs_gene_params *prm, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev,
+                     const uint64_t *rec_len_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes, uint64_t cap_gene,
+                     uint64_t cap_aa, gs_gene *gene_out_dev, uint8_t *aa_out_dev, uint64_t *aa_start_out_dev, uint64_t *aa_len_out_dev,
+                     uint64_t *rec_gene_off_out_dev, uint64_t *info_out_dev, int32_t *tables_out_dev, uint64_t n_out[2]);
+int gs_gene_call(gs_ctx *ctx, const gs_gene_params *prm, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len,
+                 uint64_t n_rec, const uint64_t *genome_rec_off, uint64_t n_genomes, uint64_t cap_gene, uint64_t cap_aa, gs_gene *gene_out,
+                 uint8_t *aa_out, uint64_t *aa_start_out, uint64_t *aa_len_out, uint64_t *rec_gene_off_out, uint64_t *info_out, int32_t *tables_out,
+                 uint64_t n_out[2]);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* Hnsw<Sig, DistHamming> (hnsw_rs) as gsearch drives it:                                           */
 /*   new/modify_level_scale/set_extend_candidates/set_keeping_pruned  dnasketch.rs:139-141,159-160  */
 /*   parallel_insert dnasketch.rs:435, aasketch.rs:407;  parallel_search dnarequest.rs:353, aarequest.rs:344 */
