@@ -12,6 +12,7 @@ from .api import (fastq_scan, hmh_cardinality, hmh_cardinality_dev, hmh_similari
 from .api import EmbedParams, ann, embed_knn_graph, embed_knn_graph_dev, knn_graph_stats, write_embedding_csv  # noqa: F401
 from .api import FracMinHashSketch, aai, frac_max_hash, frac_similarity_qxc, frac_similarity_qxc_dev, read_list_lines, superaai, write_superaai  # noqa: F401
 from .api import ClusterResult, hnswcore, write_cluster_csv  # noqa: F401
+from .api import hnswrs_describe, hnswrs_verify  # noqa: F401
 from .api import BIGSI_MINI_TILE, Bigsi, bigsi_minimizers, bigsi_positions, bigsi_split, bigsi_tail, bigsig_construct, bigsig_identify, bigsig_write_reads, read_ref_list  # noqa: F401
 from .api import AniGenome, AniSketcher, ani_estimate, ani_pairs, superani, write_superani  # noqa: F401
 from .api import HmmDb, hmm_bits, hmm_evalue, hmm_parse, hmm_specials, hmm_threshold_units, hmmsearch, universal_genes  # noqa: F401

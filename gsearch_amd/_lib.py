@@ -67,6 +67,19 @@ class BigsiDescC(C.Structure):
     _fields_ = [("prm", BigsiParamsC), ("n_colours", C.c_uint64), ("colour_capacity", C.c_uint64), ("row_words", C.c_uint64)]
 
 
+class HnswrsDescriptionC(C.Structure):
+    """gs_hnswrs_description (SPEC 16.1)"""
+    _fields_ = [("dump_mode", C.c_uint32), ("max_nb_conn", C.c_uint32), ("nb_layer", C.c_uint32), ("kind", C.c_int32), ("ef", C.c_uint64), ("nb_point", C.c_uint64),
+                ("dimension", C.c_uint64), ("distance", C.c_char * 128), ("t_name", C.c_char * 32), ("n_upper", C.c_uint64), ("entry", C.c_uint64),
+                ("ids_are_nodes", C.c_uint64), ("digest", C.c_uint64)]
+
+
+class BigsiFileDescriptionC(C.Structure):
+    """gs_bigsi_file_description (SPEC 16.2)"""
+    _fields_ = [("version", C.c_uint32), ("k", C.c_uint32), ("num_hash", C.c_uint32), ("data_t", C.c_uint32), ("minimizer_len", C.c_uint32),
+                ("has_accessions", C.c_uint32), ("bloom_size", C.c_uint64), ("n_colours", C.c_uint64), ("row_words", C.c_uint64), ("digest", C.c_uint64)]
+
+
 class HmmInfoC(C.Structure):
     """gs_hmm_info (SPEC 13)"""
     _fields_ = [("name", C.c_char * 64), ("acc", C.c_char * 32), ("M", C.c_uint32), ("flags", C.c_uint32), ("ga", C.c_double * 2), ("tc", C.c_double * 2),
@@ -251,6 +264,8 @@ SYMBOLS = {
     "gs_bigsi_accessions": (_i, [_vp, _vp, _u64, C.POINTER(_u64)]),
     "gs_bigsi_save": (_i, [_vp, C.c_char_p]),
     "gs_bigsi_load": (_i, [_vp, C.c_char_p, _u64, C.POINTER(_vp)]),
+    "gs_bigsi_describe": (_i, [C.c_char_p, C.POINTER(BigsiFileDescriptionC)]),
+    "gs_bigsi_verify": (_i, [C.c_char_p, C.POINTER(BigsiFileDescriptionC)]),
     "gs_bigsi_positions": (_i, [_u64, _u32, _u64, _vp]),
     "gs_bigsi_split": (_i, [_vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, C.POINTER(_u64)]),
     "gs_bigsi_tail": (C.c_double, [_u64, _u64, _u32, _u32, _u32]),
@@ -263,6 +278,8 @@ SYMBOLS = {
     "gs_index_dump_hnswrs": (_i, [_vp, C.c_char_p]),
     "gs_index_dump_hnswrs_ex": (_i, [_vp, C.c_char_p, _u32]),
     "gs_index_load_hnswrs": (_i, [_vp, C.c_char_p, C.POINTER(IndexParams), C.POINTER(_vp)]),
+    "gs_hnswrs_describe": (_i, [C.c_char_p, C.POINTER(HnswrsDescriptionC)]),
+    "gs_hnswrs_verify": (_i, [C.c_char_p, C.POINTER(HnswrsDescriptionC)]),
     "gs_index_insert_evals": (_u64, [_vp]),
     "gs_index_search_stats": (_i, [_vp, _vp, _i]),
     "gs_comm_unique_id": (_i, [_vp]),

@@ -1986,12 +1986,49 @@ class Bigsi:
     def save(self, path):
         check(self.L.gs_bigsi_save(self.h, str(path).encode()))
 
+    @staticmethod
+    def describe(path):
+        """the fixed header of a .gsbx file as it stands there (host only, no context; SPEC 16.2); has_accessions and digest are filled by verify"""
+        d = _lib.BigsiFileDescriptionC()
+        check(_lib.load().gs_bigsi_describe(str(path).encode(), C.byref(d)))
+        return {name: int(getattr(d, name)) for name, _ in d._fields_}
+
+    @staticmethod
+    def verify(path):
+        """everything load checks before it asks the device for memory, with load's codes (host only, no context; SPEC 16.2): the header, whether any accession is
+        non-empty, and the FNV-1a digest of every byte behind the header (SPEC 16.3)"""
+        d = _lib.BigsiFileDescriptionC()
+        check(_lib.load().gs_bigsi_verify(str(path).encode(), C.byref(d)))
+        return {name: int(getattr(d, name)) for name, _ in d._fields_}
+
     @classmethod
     def load(cls, path, ctx=None, capacity=0):
         ctx = ctx or default_context()
         h = C.c_void_p()
         check(ctx.L.gs_bigsi_load(ctx.h, str(path).encode(), int(capacity), C.byref(h)))
         return cls(0, 0, 0, 0, ctx=ctx, _handle=h)
+
+
+def _hnswrs_description(d):
+    out = {name: int(getattr(d, name)) for name, _ in d._fields_ if name not in ("distance", "t_name")}
+    out["distance"], out["t_name"] = d.distance.decode("utf-8", "replace"), d.t_name.decode("utf-8", "replace")
+    return out
+
+
+def hnswrs_describe(basename):
+    """the description at the head of <basename>.hnsw.graph as it stands there - dump mode, M, layers, ef, nb_point, dimension, distance and T names, kind or -1
+    (the reference's get_hnsw_type, reloadhnsw.rs:13-38). Host only, no context; the verify-only fields are 0."""
+    d = _lib.HnswrsDescriptionC()
+    check(_lib.load().gs_hnswrs_describe(str(basename).encode(), C.byref(d)))
+    return _hnswrs_description(d)
+
+
+def hnswrs_verify(basename):
+    """everything Hnsw.load_hnswrs checks before it touches the device, with its codes (SPEC 16.1). Host only, no context. The description plus what a load would
+    build: n_upper, entry, ids_are_nodes and the FNV-1a digest of graph, vectors and ids (SPEC 16.3)."""
+    d = _lib.HnswrsDescriptionC()
+    check(_lib.load().gs_hnswrs_verify(str(basename).encode(), C.byref(d)))
+    return _hnswrs_description(d)
 
 
 def _strip_breaks(b):

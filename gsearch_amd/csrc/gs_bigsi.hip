@@ -29,6 +29,7 @@
 #include <vector>
 #include "gs_internal.hpp"
 #include "gs_spec.hpp"
+#include "gs_bigsi_file.hpp"
 #include "gs_walk.hpp"
 
 struct gs_bigsi {
@@ -587,24 +588,10 @@ static int bigsi_alloc(gs_ctx *c, const gs_bigsi_params *prm, uint64_t cap, gs_b
 
 static int write_all(FILE *f, const void *p, size_t n) { return n == 0 || fwrite(p, 1, n, f) == n ? 0 : -1; }
 static int read_all(FILE *f, void *p, size_t n) { return n == 0 || fread(p, 1, n, f) == n ? 0 : -1; }
-static const char BX_MAGIC[8] = {'G', 'S', 'B', 'I', 'G', 'S', 'I', '1'};
-constexpr uint32_t BX_VERSION = 1, BX_VERSION_MINI = 2;         // a plain index; a minimizer index (one more u32, m, after data_t)
 
 }  // namespace gs
 
 extern "C" {
-
-int gs_bigsi_check_params(const gs_bigsi_params *p)
-{
-    GS_REQUIRE(p, GS_ERR_INVALID, "null parameters");
-    GS_REQUIRE(p->k >= 1 && p->k <= GS_BIGSI_KMAX, GS_ERR_INVALID, "bigsig: k = %u outside 1..32", p->k);
-    GS_REQUIRE(p->num_hash >= 1 && p->num_hash <= GS_BIGSI_HMAX, GS_ERR_INVALID, "bigsig: num_hash = %u outside 1..16", p->num_hash);
-    GS_REQUIRE(p->bloom_size >= 1 && p->bloom_size < GS_BIGSI_BMAX, GS_ERR_INVALID, "bigsig: bloom_size = %llu outside 1..2^40-1", (unsigned long long)p->bloom_size);
-    GS_REQUIRE(p->data_t == GS_DATA_DNA || p->data_t == GS_DATA_DNA_FWD, GS_ERR_INVALID, "bigsig: data type %u is not DNA", p->data_t);
-    GS_REQUIRE(p->minimizer == 0, GS_ERR_UNSUPPORTED, "bigsig: the minimizer mode (-m) is not implemented");
-    GS_REQUIRE(p->coverage_filter == 0, GS_ERR_UNSUPPORTED, "bigsig: the coverage filter (-f) is not implemented");
-    return GS_OK;
-}
 
 int gs_bigsi_create(gs_ctx *c, const gs_bigsi_params *prm, uint64_t colour_capacity, gs_bigsi **out) { return gs::bigsi_alloc(c, prm, colour_capacity, out); }
 
@@ -1040,37 +1027,25 @@ int gs_bigsi_load(gs_ctx *c, const char *path, uint64_t colour_capacity, gs_bigs
 {
     using namespace gs;
     GS_REQUIRE(c && path && out, GS_ERR_INVALID, "null argument");
-    FILE *f = fopen(path, "rb");
-    GS_REQUIRE(f, GS_ERR_IO, "cannot read %s: %s", path, strerror(errno));
-    char magic[8]; uint32_t head[5] = {0, 0, 0, 0, 0}; uint64_t B = 0, n = 0;
-    int bad = read_all(f, magic, 8) | read_all(f, head, 16);
-    const bool mini = !bad && head[0] == BX_VERSION_MINI;
-    if (mini) bad |= read_all(f, head + 4, 4);
-    bad |= read_all(f, &B, 8) | read_all(f, &n, 8);
-    if (bad || memcmp(magic, BX_MAGIC, 8) != 0 || (head[0] != BX_VERSION && !mini) || (mini && (head[4] < 1 || head[4] >= head[1])) || n >= ((uint64_t)1 << 32)) {
-        fclose(f);
-        GS_REQUIRE(false, GS_ERR_IO, "%s is not a bigsig index of this library (versions %u and %u)", path, BX_VERSION, BX_VERSION_MINI);
-    }
-    gs_bigsi_params prm{};
-    prm.k = head[1]; prm.num_hash = head[2]; prm.data_t = head[3]; prm.bloom_size = B;
-    std::vector<std::string> names(n);
-    for (uint64_t i = 0; i < n && !bad; i++) {
-        uint32_t l = 0;
-        bad |= read_all(f, &l, 4);
-        if (!bad && l > (1u << 20)) bad = 1;
-        if (!bad) { names[i].resize(l); bad |= read_all(f, &names[i][0], l); }
-    }
-    std::vector<uint64_t> t(n), q(n);
-    bad |= read_all(f, t.data(), 8 * n) | read_all(f, q.data(), 8 * n);
-    if (bad) { fclose(f); GS_REQUIRE(false, GS_ERR_IO, "%s is cut short", path); }
+    // the host half (gs_bigsi_file.cpp, SPEC 16.2): header, accessions, t_c and nk_c read, the size of the file held against bloom_size x ceil(n / 64) words and the
+    // parameters checked; the device is asked for nothing before it accepts
+    BigsiFile bf; FILE *f = nullptr;
+    int rc = bigsi_file_parse(path, &bf, &f);
+    if (rc) return rc;
+    const gs_bigsi_params prm = bf.prm;
+    const uint64_t n = bf.desc.n_colours, B = prm.bloom_size;
+    std::vector<std::string> &names = bf.names; std::vector<uint64_t> &t = bf.t, &q = bf.q;
+    int bad = 0;
     const uint64_t cap = std::max<uint64_t>(std::max(colour_capacity, n), 1);
     gs_bigsi *bx = nullptr;
-    int rc = bigsi_alloc(c, &prm, cap, &bx);
+    rc = bigsi_alloc(c, &prm, cap, &bx);
     if (rc) { fclose(f); return rc; }
     GS_CTX_LOCK(c);
     const uint64_t wu = (n + 63) / 64;
     const uint64_t chunk = std::max<uint64_t>(((uint64_t)64 << 20) / (8 * std::max<uint64_t>(wu, 1)), 1);
-    std::vector<uint64_t> buf(wu ? chunk * wu : 0);
+    std::vector<uint64_t> buf;
+    try { buf.resize(wu ? std::min(chunk, B) * wu : 0); }           // at most 64 MiB, and no more than the file's matrix
+    catch (const std::exception &) { fclose(f); delete bx; GS_REQUIRE(false, GS_ERR_IO, "%s: not enough host memory to stage the matrix", path); }
     hipError_t e = hipSuccess;
     if (n) {
         e = hipMemcpy(bx->tc.p, t.data(), 8 * n, hipMemcpyHostToDevice);
@@ -1088,7 +1063,7 @@ int gs_bigsi_load(gs_ctx *c, const char *path, uint64_t colour_capacity, gs_bigs
         GS_REQUIRE(false, GS_ERR_HIP, "loading the matrix failed: %s", hipGetErrorString(e));
     }
     bx->n = n;
-    bx->m = head[4];
+    bx->m = bf.desc.minimizer_len;
     bool any = false;
     for (const std::string &s : names) any = any || !s.empty();
     if (any) bx->names.swap(names);

@@ -26,6 +26,7 @@
 #include "gs_internal.hpp"
 #include "gs_spec.hpp"
 #include "gs_insert_rows.hpp"
+#include "gs_hnswio_parse.hpp"
 
 namespace gs {
 
@@ -2891,27 +2892,10 @@ int gs_index_import(gs_index *ix, const void *sigs, uint64_t n, const uint8_t *l
     GS_CTX_LOCK(c);
     GS_HIP_CHECK(hipSetDevice(c->device));
     const uint32_t M = ix->prm.max_nb_conn, ML = ix->prm.max_layer;
-    int top = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        GS_REQUIRE(levels[i] < ML, GS_ERR_INVALID, "level of node %llu out of range", (unsigned long long)i);
-        GS_REQUIRE(deg0[i] <= 2 * M, GS_ERR_INVALID, "degree of node %llu out of range", (unsigned long long)i);
-        for (uint32_t t = 0; t < deg0[i]; t++) GS_REQUIRE(nbr0[i * 2 * M + t] < n, GS_ERR_INVALID, "neighbour id out of range");
-        GS_REQUIRE((levels[i] > 0) == (upidx[i] >= 0), GS_ERR_INVALID, "upidx inconsistent with level at node %llu", (unsigned long long)i);
-        if (upidx[i] >= 0) {
-            GS_REQUIRE((uint64_t)upidx[i] < n_upper, GS_ERR_INVALID, "upidx of node %llu out of range", (unsigned long long)i);
-            for (uint32_t l = 1; l <= levels[i]; l++) {
-                const uint64_t o = (uint64_t)upidx[i] * ML + (l - 1);
-                GS_REQUIRE(degU[o] <= M, GS_ERR_INVALID, "degree of node %llu at layer %u out of range", (unsigned long long)i, l);
-                for (uint32_t t = 0; t < degU[o]; t++) {
-                    const uint32_t e = nbrU[o * M + t];
-                    GS_REQUIRE(e < n && levels[e] >= l, GS_ERR_INVALID, "node %llu links to %u at layer %u, which does not reach that layer", (unsigned long long)i, e, l);
-                }
-            }
-        }
-        if (levels[i] > top) top = levels[i];
-    }
-    GS_REQUIRE(levels[entry] == top, GS_ERR_INVALID, "entry point is not on the top layer");
-    int rc = gs::index_reserve(ix, n, n_upper);
+    int rc = gs::graph_validate(n, M, ML, levels, entry, deg0, nbr0, upidx, n_upper, degU, nbrU);      // gs_hnswio_parse.cpp: host only, shared with gs_hnswrs_verify
+    if (rc) return rc;
+    const int top = levels[entry];                   // validated: the entry point is on the top layer
+    rc = gs::index_reserve(ix, n, n_upper);
     if (rc) return rc;
     if ((rc = gs::upload_user_rows(ix, ix->data.p, sigs, n, hipMemcpyHostToDevice))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(ix->levels.p, levels, n, hipMemcpyHostToDevice, c->stream));

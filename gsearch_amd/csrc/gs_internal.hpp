@@ -12,6 +12,7 @@
 #include <vector>
 #include "../../include/gsearch_amd.h"
 #include "gs_scratch.hpp"
+#include "gs_host.hpp"
 
 namespace gs {
 
@@ -22,14 +23,6 @@ namespace gs {
             gs::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
             return GS_ERR_HIP;                                                                     \
         }                                                                                          \
-    } while (0)
-
-#define GS_REQUIRE(cond, code, ...)                \
-    do {                                           \
-        if (!(cond)) {                             \
-            gs::set_error(__VA_ARGS__);            \
-            return (code);                         \
-        }                                          \
     } while (0)
 
 enum { FAM_SKETCH = 0, FAM_HAMMING = 1, FAM_SEARCH = 2, FAM_INSERT = 3, FAM_COUNT = 4 };

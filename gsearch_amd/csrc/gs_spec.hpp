@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include "gs_bigsi_file.hpp"
 
 #define GS_HD __host__ __device__ __forceinline__
 
@@ -381,9 +382,7 @@ GS_HD bool cluster_keep1(uint64_t h, uint64_t D, uint64_t t1, uint32_t d0) { ret
 
 // ---- SPEC 11: bigsig (binaux/src/bin/bigsig.rs) - row positions of a k-mer in the bit-sliced Bloom index and the significance of a read's best hit.
 // [CHOICE] (the `bigsig` crate's hash and test are not vendored): every constant and step lives here
-#define GS_BIGSI_KMAX 32u                // 1 <= k <= 32 (15 accepted)
-#define GS_BIGSI_HMAX 16u                // 1 <= num_hash <= 16
-#define GS_BIGSI_BMAX (1ULL << 40)       // 1 <= bloom_size < 2^40
+// GS_BIGSI_KMAX / _HMAX / _BMAX (1 <= k <= 32, 1 <= num_hash <= 16, 1 <= bloom_size < 2^40): gs_bigsi_file.hpp, the host-only reader of .gsbx files checks them too
 #define GS_BIGSI_TAIL_CUT 0x1.0p-60      // the tail sum stops at a term below tail x 2^-60
 // h1 and the odd step of the double hashing: the first two SplitMix64 outputs from state fx64(v), as hmh_update
 GS_HD void bigsi_hash(uint64_t v, uint64_t &h1, uint64_t &step)

@@ -621,6 +621,27 @@ int      gs_index_dump_hnswrs(gs_index *, const char *basename);
 enum { GS_DUMP_TRUNCATE_255 = 1 };
 int      gs_index_dump_hnswrs_ex(gs_index *, const char *basename, uint32_t flags);
 int      gs_index_load_hnswrs(gs_ctx *, const char *basename, const gs_index_params *hint, gs_index **out);
+/* Host only, no context. Both files of a dump come from another program and are untrusted: SPEC.md 16.1 lists what is refused, in which order and
+ * with which code; no size named by a file is allocated before it was held against the sizes of the files.
+ * gs_hnswrs_describe: the description at the head of <basename>.hnsw.graph as it stands there (the reference's get_hnsw_type, reloadhnsw.rs:13-38),
+ * nothing judged but its magic and that it is whole; the verify-only fields are 0.
+ * gs_hnswrs_verify: everything gs_index_load_hnswrs checks before it touches the device, with the same codes and messages; out may be NULL. */
+typedef struct {
+    uint32_t dump_mode;          /* 1 = full, 0 = light (graph only) */
+    uint32_t max_nb_conn;
+    uint32_t nb_layer;
+    int32_t  kind;               /* GS_KIND_* of t_name, -1: not a signature type of gsearch */
+    uint64_t ef, nb_point, dimension;
+    char     distance[128];      /* type names, NUL-terminated, cut to fit */
+    char     t_name[32];
+    /* filled by gs_hnswrs_verify only: what a load would build */
+    uint64_t n_upper;            /* points above layer 0 */
+    uint64_t entry;              /* node number of the entry point */
+    uint64_t ids_are_nodes;      /* 1: the DataIds are 0..n-1 and are the node numbers; 0: nodes in data-file order, DataIds kept as caller ids */
+    uint64_t digest;             /* FNV-1a of the loaded graph, vectors and ids (SPEC.md 16.3) */
+} gs_hnswrs_description;
+int      gs_hnswrs_describe(const char *basename, gs_hnswrs_description *out);
+int      gs_hnswrs_verify(const char *basename, gs_hnswrs_description *out);
 uint64_t gs_index_insert_evals(const gs_index *);      /* DistHamming evaluations spent by inserts so far */
 /* after the last parallel_insert of a build (the replicas of a multi-GPU request, a server that only answers): gives the insert-time pair cache back - up to 55 % of
  * the device, 90 GB at 300 k nodes - and keeps everything a search needs. Later inserts still work (bit-identical graph): pairs among the nodes inserted before the
@@ -700,6 +721,20 @@ int    gs_bigsi_accessions(gs_bigsi *bx, char *buf, uint64_t cap_bytes, uint64_t
  * index; load takes both. load: colour_capacity 0 = the file's n_colours */
 int    gs_bigsi_save(gs_bigsi *bx, const char *path);
 int    gs_bigsi_load(gs_ctx *ctx, const char *path, uint64_t colour_capacity, gs_bigsi **out);
+/* Host only, no context; the file is untrusted (SPEC.md 16.2: what is refused, in which order, with which code - the size of the file is held against
+ * bloom_size x ceil(n_colours / 64) words before the device is asked for anything). gs_bigsi_describe: the fixed header as it stands in the file, nothing
+ * judged but magic and version; gs_bigsi_verify: everything gs_bigsi_load checks before it allocates, same codes and messages; out may be NULL. */
+typedef struct {
+    uint32_t version;            /* 1: a plain index, 2: a minimizer index */
+    uint32_t k, num_hash, data_t;
+    uint32_t minimizer_len;      /* 0 in version 1 */
+    uint32_t has_accessions;     /* verify only: some accession is not empty */
+    uint64_t bloom_size, n_colours;
+    uint64_t row_words;          /* ceil(n_colours / 64): u64 words of a row IN THE FILE */
+    uint64_t digest;             /* verify only: FNV-1a of every byte behind the fixed header (SPEC.md 16.3) */
+} gs_bigsi_file_description;
+int    gs_bigsi_describe(const char *path, gs_bigsi_file_description *out);
+int    gs_bigsi_verify(const char *path, gs_bigsi_file_description *out);
 /* host arithmetic of SPEC 11, no device: the num_hash rows of k-mer value v; the segments of a text (begin = offset of the first base, len in bases,
  * segments shorter than min_len dropped; arrays may be NULL / cap 0 to count only); the tail */
 int    gs_bigsi_positions(uint64_t v, uint32_t num_hash, uint64_t bloom_size, uint64_t *pos_out);

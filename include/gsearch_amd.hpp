@@ -317,6 +317,9 @@ public:
     }
     uint32_t minimizer_len() const { return gs_bigsi_minimizer_len(bx_); }
     Bigsi(Context &ctx, const std::string &path, uint64_t colour_capacity = 0) : ctx_(&ctx) { check(gs_bigsi_load(ctx.get(), path.c_str(), colour_capacity, &bx_)); }
+    // host only, no context (SPEC 16.2): the fixed header of a .gsbx file; everything the loading constructor checks before it asks the device for memory
+    static gs_bigsi_file_description describe(const std::string &path) { gs_bigsi_file_description d; check(gs_bigsi_describe(path.c_str(), &d)); return d; }
+    static gs_bigsi_file_description verify(const std::string &path) { gs_bigsi_file_description d; check(gs_bigsi_verify(path.c_str(), &d)); return d; }
     ~Bigsi() { gs_bigsi_free(bx_); }
     Bigsi(const Bigsi &) = delete;
     Bigsi &operator=(const Bigsi &) = delete;
@@ -434,6 +437,11 @@ inline double bindash_compute_distance(float hamming_distance, size_t kmer_size)
     const float frac = 2.0f * j / (1.0f + j);
     return 1.0 - (double)std::pow(frac, 1.0f / (float)kmer_size);
 }
+
+// hnsw_rs' own dump on the host, no context (SPEC 16.1): get_hnsw_type (reloadhnsw.rs:13-38) - the description at the head of <basename>.hnsw.graph -,
+// and everything gs_index_load_hnswrs checks before it touches the device
+inline gs_hnswrs_description hnswrs_describe(const std::string &basename) { gs_hnswrs_description d; check(gs_hnswrs_describe(basename.c_str(), &d)); return d; }
+inline gs_hnswrs_description hnswrs_verify(const std::string &basename) { gs_hnswrs_description d; check(gs_hnswrs_verify(basename.c_str(), &d)); return d; }
 
 // hnsw_rs::Hnsw<T, DistHamming>
 template <class T>

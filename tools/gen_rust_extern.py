@@ -16,7 +16,8 @@ TY = {"int": "c_int", "void": "c_void", "char": "c_char", "float": "c_float", "d
       "gs_sketch_params": "GsSketchParams", "gs_index_params": "GsIndexParams", "gs_embed_params": "GsEmbedParams", "gs_knn_stats": "GsKnnStats",
       "gs_cluster_params": "GsClusterParams", "gs_cluster_info": "GsClusterInfo", "gs_bigsi": "GsBigsi", "gs_bigsi_params": "GsBigsiParams",
       "gs_bigsi_desc": "GsBigsiDesc", "gs_hmm_db": "GsHmmDb", "gs_hmm_info": "GsHmmInfo", "gs_orf_params": "GsOrfParams",
-      "gs_orf": "GsOrf", "gs_gene_params": "GsGeneParams", "gs_gene_interval": "GsGeneInterval", "gs_gene": "GsGene"}
+      "gs_orf": "GsOrf", "gs_gene_params": "GsGeneParams", "gs_gene_interval": "GsGeneInterval", "gs_gene": "GsGene",
+      "gs_hnswrs_description": "GsHnswrsDescription", "gs_bigsi_file_description": "GsBigsiFileDescription"}
 
 
 def rust_type(c):
