@@ -14,6 +14,7 @@ from .api import FracMinHashSketch, aai, frac_max_hash, frac_similarity_qxc, fra
 from .api import ClusterResult, hnswcore, write_cluster_csv  # noqa: F401
 from .api import hnswrs_describe, hnswrs_verify  # noqa: F401
 from .api import BIGSI_MINI_TILE, Bigsi, bigsi_minimizers, bigsi_positions, bigsi_split, bigsi_tail, bigsig_construct, bigsig_identify, bigsig_write_reads, read_ref_list  # noqa: F401
+from .api import BIGSI_VERDICTS, bigsi_verdict_code, bigsig_write_report  # noqa: F401
 from .api import AniGenome, AniSketcher, ani_estimate, ani_pairs, superani, write_superani  # noqa: F401
 from .api import HmmDb, hmm_bits, hmm_evalue, hmm_parse, hmm_specials, hmm_threshold_units, hmmsearch, universal_genes  # noqa: F401
 from .api import hmm_forward_evalue, hmm_logsum_table, hmm_parse_stats, hmm_viterbi_floor  # noqa: F401

@@ -270,6 +270,12 @@ SYMBOLS = {
     "gs_bigsi_split": (_i, [_vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, C.POINTER(_u64)]),
     "gs_bigsi_tail": (C.c_double, [_u64, _u64, _u32, _u32, _u32]),
     "gs_bigsig_write_reads": (_i, [C.c_char_p, C.POINTER(C.c_char_p), _u64, C.POINTER(C.c_char_p), _u64, _vp, _vp, _vp, _vp]),
+    # bigsig, tied top hits and the six-field report (SPEC 11.2)
+    "gs_bigsi_query_ties_dev": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "gs_bigsi_query_ties": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _u64, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "gs_bigsi_verdict_dev": (_i, [_vp, _u64, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp]),
+    "gs_bigsi_verdict_code": (_u32, [_u32, _u32, _u32, C.c_double, C.c_double]),
+    "gs_bigsig_write_report": (_i, [C.c_char_p, C.POINTER(C.c_char_p), _u64, C.POINTER(C.c_char_p), _u64, _u32, _vp, _vp, _vp, _vp, _vp]),
     "gs_index_import": (_i, [_vp, _vp, _u64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_index_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_index_get_data": (_i, [_vp, _u64, _u64, _vp]),

@@ -1852,6 +1852,26 @@ def bigsig_write_reads(prefix, accessions, read_ids, best_colour, best_hits, n_k
     check(_lib.load().gs_bigsig_write_reads(str(prefix).encode(), acc, len(accessions), ids, len(read_ids), _p(bc), _p(bh), _p(nk), _p(ac)))
 
 
+BIGSI_VERDICTS = ("too_short", "no_hits", "no_significant_hits", "unique", "tied")      # GS_BIGSI_TOO_SHORT .. GS_BIGSI_TIED of gsearch_amd.h (SPEC 11.2)
+
+
+def bigsi_verdict_code(n_kmers, best_hits, n_tied, tail, fp_correct):
+    """SPEC 11.2: the verdict table alone (host arithmetic) -> an index into BIGSI_VERDICTS"""
+    return int(_lib.load().gs_bigsi_verdict_code(int(n_kmers), int(best_hits), int(n_tied), float(tail), float(fp_correct)))
+
+
+def bigsig_write_report(prefix, accessions, read_ids, n_kmers, best_hits, n_tied, tied, verdict):
+    """the six-field `{prefix}_reads.txt` and `{prefix}_counts.txt` (SPEC 11.2); tied: (n_reads, max_ties) u32"""
+    acc = (C.c_char_p * max(len(accessions), 1))(*[a.encode() for a in accessions])
+    ids = (C.c_char_p * max(len(read_ids), 1))(*[r.encode() for r in read_ids])
+    nk, bh, nt = (np.ascontiguousarray(x, dtype=np.uint32) for x in (n_kmers, best_hits, n_tied))
+    td = np.ascontiguousarray(tied, dtype=np.uint32)
+    if td.ndim != 2 or td.shape[0] != len(read_ids):
+        raise ValueError("tied is (n_reads, max_ties)")
+    vd = np.ascontiguousarray(verdict, dtype=np.uint8)
+    check(_lib.load().gs_bigsig_write_report(str(prefix).encode(), acc, len(accessions), ids, len(read_ids), td.shape[1], _p(nk), _p(bh), _p(nt), _p(td), _p(vd)))
+
+
 class Bigsi:
     """A bit-sliced Bloom index of genomes (bigsig): bloom_size rows, one column ("colour") per genome in the order added; the matrix lives on the device."""
 
@@ -1983,6 +2003,42 @@ class Bigsi:
             for ptr in ptrs:
                 c.free(ptr)
 
+    def query_ties(self, reads, quals=None, min_phred=15, down_sample=1, max_ties=16):
+        """SPEC 11.2: reads as in query -> (n_kmers, best_hits, n_tied, tied (n_reads, max_ties), sig_colour): every colour that reaches best_hits is counted,
+        the max_ties smallest are listed (UINT32_MAX behind them), sig_colour is the tied colour with the fewest bits set"""
+        text, qual, b, e, off = _text_records(reads, quals)
+        n, mt = len(reads), int(max_ties)
+        nk, bh, nt, sc = (np.zeros(n, np.uint32) for _ in range(4))
+        td = np.zeros((n, mt if 1 <= mt <= 1024 else 1), np.uint32)
+        check(self.L.gs_bigsi_query_ties(self.h, _p(text) if len(text) else None, _p(qual) if qual is not None and len(qual) else None, int(min_phred), _p(b), _p(e),
+                                         len(b), _p(off), n, int(down_sample), mt, _p(nk), _p(bh), _p(nt), _p(td), _p(sc)))
+        return nk, bh, nt, td, sc
+
+    def query_ties_dev(self, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_read_rec_off, n_reads, d_n_kmers, d_best_hits, d_n_tied, d_tied, d_sig_colour,
+                       down_sample=1, max_ties=16):
+        """d_tied: n_reads x max_ties u32; queued on the context's stream"""
+        check(self.L.gs_bigsi_query_ties_dev(self.h, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_read_rec_off, n_reads, int(down_sample), int(max_ties),
+                                             d_n_kmers, d_best_hits, d_n_tied, d_tied, d_sig_colour))
+
+    def verdict_dev(self, n_reads, d_n_kmers, d_best_hits, d_n_tied, d_sig_colour, fp_correct, d_tail, d_verdict):
+        check(self.L.gs_bigsi_verdict_dev(self.h, n_reads, d_n_kmers, d_best_hits, d_n_tied, d_sig_colour, float(fp_correct), d_tail, d_verdict))
+
+    def verdict(self, n_kmers, best_hits, n_tied, sig_colour, fp_correct):
+        """(tail f64 of sig_colour, verdict u8 - an index into BIGSI_VERDICTS) of every read; fp_correct is the threshold itself"""
+        n = len(n_kmers)
+        if n == 0:
+            return np.zeros(0, np.float64), np.zeros(0, np.uint8)
+        c = self.ctx
+        ptrs = [c.alloc(4 * n) for _ in range(4)] + [c.alloc(8 * n), c.alloc(n)]
+        try:
+            for ptr, a in zip(ptrs, (n_kmers, best_hits, n_tied, sig_colour)):
+                c.upload(ptr, np.ascontiguousarray(a, dtype=np.uint32))
+            self.verdict_dev(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], fp_correct, ptrs[4], ptrs[5])
+            return c.download(ptrs[4], n, np.float64), c.download(ptrs[5], n, np.uint8)
+        finally:
+            for ptr in ptrs:
+                c.free(ptr)
+
     def save(self, path):
         check(self.L.gs_bigsi_save(self.h, str(path).encode()))
 
@@ -2082,9 +2138,13 @@ def bigsig_construct(ref_list, out_base, k, num_hash, bloom_size, quality=15, th
     return bx
 
 
-def bigsig_identify(index, queries, prefix, down_sample=1, fp_correct=3.0, quality=15, batch=50000, ctx=None):
+def bigsig_identify(index, queries, prefix, down_sample=1, fp_correct=3.0, quality=15, batch=50000, ctx=None, report="best", max_ties=16):
     """bigsig identify: every read of the query file(s) against the index (a Bigsi or the path of a saved one); two query paths are the mates of pairs.
-    fp_correct is bigsig's -p: the threshold is 10^-fp_correct. Writes `{prefix}_reads.txt` / `{prefix}_counts.txt`, returns the per-read arrays."""
+    fp_correct is bigsig's -p: the threshold is 10^-fp_correct. Writes `{prefix}_reads.txt` / `{prefix}_counts.txt`, returns the per-read arrays.
+    report="best": five fields, the smallest colour with the most hits (SPEC 11). report="ties": the six fields of upstream's README - every tied
+    top colour, up to max_ties of them listed, and a tied read rejected (SPEC 11.2)."""
+    if report not in ("best", "ties"):
+        raise GsError(_lib.GS_ERR_INVALID, "bigsig identify: report is 'best' or 'ties'")
     bx = index if isinstance(index, Bigsi) else Bigsi.load(index, ctx=ctx)
     queries = [queries] if isinstance(queries, (str, bytes)) or hasattr(queries, "__fspath__") else list(queries)
     if len(queries) not in (1, 2):
@@ -2095,16 +2155,28 @@ def bigsig_identify(index, queries, prefix, down_sample=1, fp_correct=3.0, quali
         raise GsError(_lib.GS_ERR_INVALID, "the two query files hold different numbers of reads")
     any_q = any(f[1] is not None for f in files)
     ids = [rid for rid, _ in files[0][0]]
-    outs = [[], [], [], []]
+    ties = report == "ties"
+    outs = [[] for _ in range(7 if ties else 4)]
     thr = 10.0 ** (-float(fp_correct))
     for i in range(0, n, max(int(batch), 1)):
         j = min(n, i + max(int(batch), 1))
         reads = [[f[0][r][1] for f in files] for r in range(i, j)]
         quals = [[(f[1][r] if f[1] is not None else b"~" * len(f[0][r][1])) for f in files] for r in range(i, j)] if any_q else None
+        if ties:
+            nk, bh, nt, td, sc = bx.query_ties(reads, quals=quals, min_phred=quality, down_sample=down_sample, max_ties=max_ties)
+            tl, vd = bx.verdict(nk, bh, nt, sc, thr)
+            for o, a in zip(outs, (nk, bh, nt, td, sc, tl, vd)):
+                o.append(a)
+            continue
         nk, bc, bh = bx.query(reads, quals=quals, min_phred=quality, down_sample=down_sample)
         _, acc = bx.classify(nk, bc, bh, thr)
         for o, a in zip(outs, (nk, bc, bh, acc)):
             o.append(a)
+    if ties:
+        empty = (np.zeros(0, np.uint32),) * 3 + (np.zeros((0, int(max_ties)), np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.float64), np.zeros(0, np.uint8))
+        nk, bh, nt, td, sc, tl, vd = (np.concatenate(o) if o else z for o, z in zip(outs, empty))
+        bigsig_write_report(prefix, bx.accessions(), ids, nk, bh, nt, td, vd)
+        return {"ids": ids, "n_kmers": nk, "best_hits": bh, "n_tied": nt, "tied": td, "sig_colour": sc, "tail": tl, "verdict": vd}
     nk, bc, bh, acc = (np.concatenate(o) if o else np.zeros(0, np.uint32) for o in outs)
     bigsig_write_reads(prefix, bx.accessions(), ids, bc, bh, nk, acc)
     return {"ids": ids, "n_kmers": nk, "best_colour": bc, "best_hits": bh, "accept": acc.astype(bool)}

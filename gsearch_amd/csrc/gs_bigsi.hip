@@ -13,6 +13,9 @@
 //  * k_bigsi_query     : one wavefront per read, lanes = colour words. 64 k-mers are hashed at once (one per lane), then taken in turn: num_hash
 //                        nontemporal row loads, an AND, and a ripple add of the 64-bit vector into bit-plane counters in registers.
 //  * k_bigsi_classify  : one lane per read, the binomial tail of SPEC 11.
+//  * k_bigsi_query<.., TIES = true> (SPEC 11.2): every colour that reaches the largest count instead of the smallest one - their number, the first max_ties
+//                        in ascending order (popcount + a wave prefix sum place each lane's colours), the one with the fewest bits set.
+//  * k_bigsi_verdict   : one lane per read, the tail of that colour and the verdict table of SPEC 11.2.
 //  minimizer indexes and the coverage filter (SPEC 11.1):
 //  * k_bigsi_minimizers: one wavefront per tile of MZ_TILE windows of one record. Every lane windows and hashes the m-mer at its position, keys and
 //                        (value, h1, step) of the tile and its halo go to LDS, every lane picks the minimizer of its window (minimizer_pick, gs_spec.hpp)
@@ -206,11 +209,49 @@ template <int p, int BX_PLANES> __device__ __forceinline__ void ripple_add(uint6
 // LIST (a minimizer index): the values come from the ordered per-read lists k_bigsi_minimizers wrote - seq64 = the values, rec_start[read] = where the
 // read's list begins, rec_len[read] = its entries, read_rec_off unused. A list is walked as ONE record whose windows are its entries (its "length" is
 // entries + k - 1), so the running index, down_sample and n are the arithmetic of the plain form.
-template <int HB, int BX_PLANES, bool LIST = false>
+// TIES (SPEC 11.2): instead of the smallest colour that reaches the largest count, all of them - their number, the first max_ties in ascending order, and
+// the one with the fewest bits set (the smallest tail). The plain form carries an empty BxTies and none of the code below that names it.
+template <bool TIES> struct BxTies {};
+template <> struct BxTies<true> {
+    const uint64_t *tc;                    // t_c of every colour
+    uint32_t *n_tied, *tied, *sig;         // per read: |T_r|, its first max_ties members (UINT32_MAX behind them), argmin (t_c, c) over T_r
+    uint32_t max_ties;
+};
+__device__ __forceinline__ uint32_t wave_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+// One chunk's cand (the colours of word wi that hold the largest count so far; lanes in ascending word order) appended to the read's list, which holds n_tied
+// colours already: an exclusive prefix sum of the lanes' popcounts places each lane's colours, every lane walks its set bits. (sig_t, sig_c): the smallest
+// (t_c, c) so far; earlier chunks hold smaller colours, so a later one replaces it with fewer bits only. Everything returned is wave-uniform.
+__device__ __forceinline__ void bigsi_take_ties(const BxTies<true> &ties, uint64_t read, uint32_t lane, uint64_t wi, uint64_t cand, uint32_t &n_tied, uint64_t &sig_t,
+                                                uint32_t &sig_c)
+{
+    const uint32_t cnt = (uint32_t)__popcll(cand);
+    uint32_t x = cnt;
+    for (uint32_t o = 1; o < 64; o <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)x, o); if (lane >= o) x += y; }
+    const uint32_t total = (uint32_t)__shfl((int)x, 63);
+    uint64_t at = (uint64_t)n_tied + (x - cnt), bt = ~(uint64_t)0;
+    uint32_t bc = UINT32_MAX;
+    uint32_t *row = ties.tied + read * ties.max_ties;
+    for (uint64_t m = cand; m; m &= m - 1) {
+        const uint32_t col = (uint32_t)(wi * 64) + (uint32_t)__builtin_ctzll(m);
+        if (at < ties.max_ties) row[at] = col;
+        at++;
+        const uint64_t t = ties.tc[col];
+        if (t < bt) { bt = t; bc = col; }                // ascending colours: the first of equal t_c stays
+    }
+    for (uint32_t o = 32; o > 0; o >>= 1) {
+        const uint64_t ot = shfl_xor64(bt, o);
+        const uint32_t oc = (uint32_t)__shfl_xor((int)bc, (int)o);
+        if (ot < bt || (ot == bt && oc < bc)) { bt = ot; bc = oc; }
+    }
+    if (bt < sig_t) { sig_t = readlane64(bt, 0); sig_c = wave_u32(bc); }
+    n_tied = wave_u32(n_tied + total);
+}
+template <int HB, int BX_PLANES, bool LIST = false, bool TIES = false>
 __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict__ seq64, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
                                                      const uint64_t *__restrict__ read_rec_off, uint64_t n_reads, uint32_t kq, uint32_t d, uint64_t B, uint32_t h,
                                                      const uint64_t *__restrict__ M, uint64_t W, uint64_t nc, uint32_t *__restrict__ out_n,
-                                                     uint32_t *__restrict__ out_col, uint32_t *__restrict__ out_hits, uint32_t *__restrict__ dense)
+                                                     uint32_t *__restrict__ out_col, uint32_t *__restrict__ out_hits, uint32_t *__restrict__ dense,
+                                                     const BxTies<TIES> ties)
 {
     const uint32_t wave_u = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint64_t read = (uint64_t)blockIdx.x * 4 + wave_u;
@@ -236,6 +277,9 @@ __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict_
     if (W < 64) { Wp = 1; while (Wp < W) Wp <<= 1; }
     const uint32_t G = 64 / Wp, grp = lane / Wp, wl = lane & (Wp - 1);
     uint32_t best_h = 0, best_c = 0;
+    uint32_t n_tied = 0, sig_c = UINT32_MAX;                                        // TIES: wave-uniform, carried across the chunks
+    uint64_t sig_t = ~(uint64_t)0;
+    (void)best_c; (void)n_tied; (void)sig_c; (void)sig_t;
     for (uint64_t wc = 0; wc < W; wc += 64) {
         const uint64_t wi = wc + wl;
         const bool active = wi < W;
@@ -304,14 +348,19 @@ __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict_
                 if (__ballot(tt != 0) != 0) { cand = tt; bh |= 1u << p; }
             }
         }
-        if (bh > best_h) {                 // (a later chunk holds larger colours: it only wins with more hits)
+        if constexpr (TIES) {
+            // a chunk with more hits starts the list again, one with as many adds to it, one with fewer is left alone. Counted from cand, never from the
+            // planes: on a narrow matrix every k-mer group holds the full sums, and cand is seeded in group 0 alone
+            if (bh > best_h) { n_tied = 0; sig_t = ~(uint64_t)0; sig_c = UINT32_MAX; best_h = bh; }
+            if (bh > 0 && bh == best_h) bigsi_take_ties(ties, read, lane, wi, cand, n_tied, sig_t, sig_c);
+        } else if (bh > best_h) {          // (a later chunk holds larger colours: it only wins with more hits)
             const uint64_t bal = __ballot(cand != 0);
             const uint32_t fl = (uint32_t)__builtin_ctzll(bal);
             const uint32_t mine = cand ? (uint32_t)(wi * 64) + (uint32_t)__builtin_ctzll(cand) : 0u;
             best_c = (uint32_t)__shfl((int)mine, (int)fl);
             best_h = bh;
         }
-        if (dense && grp == 0 && active) {
+        if (!TIES && dense && grp == 0 && active) {
             for (uint32_t b = 0; b < 64; b++) {
                 const uint64_t col = wi * 64 + b;
                 if (col >= nc) break;
@@ -323,7 +372,14 @@ __global__ __launch_bounds__(256) void k_bigsi_query(const uint64_t *__restrict_
             }
         }
     }
-    if (lane == 0) { out_n[read] = n; out_col[read] = best_c; out_hits[read] = best_h; }
+    if constexpr (TIES) {
+        // the slots behind the list are written here: the caller's buffer may hold anything
+        uint32_t *row = ties.tied + read * ties.max_ties;
+        for (uint64_t i = (uint64_t)(n_tied < ties.max_ties ? n_tied : ties.max_ties) + lane; i < ties.max_ties; i += 64) row[i] = UINT32_MAX;
+        if (lane == 0) { out_n[read] = n; out_hits[read] = best_h; ties.n_tied[read] = n_tied; ties.sig[read] = sig_c; }
+    } else {
+        if (lane == 0) { out_n[read] = n; out_col[read] = best_c; out_hits[read] = best_h; }
+    }
 }
 
 // ---- minimizer occurrences (SPEC 11.1) ---------------------------------------------------------------------------------------------------------
@@ -486,6 +542,20 @@ __global__ void k_bigsi_classify(uint64_t n_reads, const uint32_t *__restrict__ 
     const double t = bigsi_tail(c < nc ? tc[c] : 0, B, h, nk[r], x0);
     tail[r] = t;
     accept[r] = (x0 > 0 && t < fp) ? 1 : 0;
+}
+
+// SPEC 11.2: the tail of the most significant tied colour and the verdict of the read
+static_assert(GS_BIGSI_TOO_SHORT == 0 && GS_BIGSI_NO_HITS == 1 && GS_BIGSI_NOT_SIGNIFICANT == 2 && GS_BIGSI_UNIQUE == 3 && GS_BIGSI_TIED == 4, "bigsi_verdict (gs_spec.hpp)");
+__global__ void k_bigsi_verdict(uint64_t n_reads, const uint32_t *__restrict__ nk, const uint32_t *__restrict__ hits, const uint32_t *__restrict__ n_tied,
+                                const uint32_t *__restrict__ sig, const uint64_t *__restrict__ tc, uint64_t nc, uint64_t B, uint32_t h, double fp,
+                                double *__restrict__ tail, uint8_t *__restrict__ verdict)
+{
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_reads) return;
+    const uint32_t c = sig[r], x0 = hits[r], n = nk[r];
+    const double t = x0 > 0 ? bigsi_tail(c < nc ? tc[c] : 0, B, h, n, x0) : 1.0;
+    tail[r] = t;
+    verdict[r] = bigsi_verdict(n, x0, n_tied[r], t, fp);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
@@ -846,17 +916,13 @@ int gs_bigsi_rows(gs_bigsi *bx, const uint64_t *rows, uint64_t n, uint64_t *word
     return GS_OK;
 }
 
-int gs_bigsi_query_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
-                       const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t *n_kmers, uint32_t *best_colour, uint32_t *best_hits,
-                       uint32_t *counts)
+extern "C++" {
+// the launches of both forms of the query (arguments checked by the callers): TIES = false writes best_colour (and counts), TIES = true what `ties` names
+template <bool TIES>
+static int bigsi_query_launch(gs_bigsi *bx, const void *seq, const uint64_t *rec_start, const uint64_t *rec_len, const uint64_t *read_rec_off, uint64_t n_reads,
+                              uint32_t down_sample, uint32_t *n_kmers, uint32_t *best_colour, uint32_t *best_hits, uint32_t *counts, const gs::BxTies<TIES> ties)
 {
     using namespace gs;
-    (void)seq_bytes; (void)n_rec;
-    GS_REQUIRE(bx, GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(down_sample >= 1, GS_ERR_INVALID, "bigsig: down_sample = 0");
-    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
-    GS_REQUIRE(n_reads == 0 || (seq && rec_start && rec_len && read_rec_off && n_kmers && best_colour && best_hits), GS_ERR_INVALID, "null argument");
-    if (n_reads == 0) return GS_OK;
     GS_REQUIRE(n_reads < ((uint64_t)1 << 33), GS_ERR_INVALID, "too many reads in one batch");
     gs_ctx *c = bx->c;
     GS_CTX_LOCK(c);
@@ -885,12 +951,12 @@ int gs_bigsi_query_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const 
         ProfScope ps(c, FAM_SEARCH);
 #define GS_BX_LAUNCH_LIST(HB)                                                                                                                                \
     do {                                                                                                                                                     \
-        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_SHORT, true>), grid, block, 0, c->stream, qv.as<uint64_t>(), qoff.as<uint64_t>(), qcnt.as<uint64_t>(), \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_SHORT, true, TIES>), grid, block, 0, c->stream, qv.as<uint64_t>(), qoff.as<uint64_t>(), qcnt.as<uint64_t>(), \
                            (const uint64_t *)nullptr, n_reads, bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n,     \
-                           n_kmers, best_colour, best_hits, counts);                                                                                         \
-        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_LONG, true>), grid, block, 0, c->stream, qv.as<uint64_t>(), qoff.as<uint64_t>(), qcnt.as<uint64_t>(),  \
+                           n_kmers, best_colour, best_hits, counts, ties);                                                                                         \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_LONG, true, TIES>), grid, block, 0, c->stream, qv.as<uint64_t>(), qoff.as<uint64_t>(), qcnt.as<uint64_t>(),  \
                            (const uint64_t *)nullptr, n_reads, bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n,     \
-                           n_kmers, best_colour, best_hits, counts);                                                                                         \
+                           n_kmers, best_colour, best_hits, counts, ties);                                                                                         \
     } while (0)
         if (hb == 1) GS_BX_LAUNCH_LIST(1);
         else if (hb == 2) GS_BX_LAUNCH_LIST(2);
@@ -902,10 +968,10 @@ int gs_bigsi_query_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const 
     }
 #define GS_BX_LAUNCH(HB)                                                                                                                                     \
     do {                                                                                                                                                     \
-        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_SHORT>), grid, block, 0, c->stream, (const uint64_t *)seq, rec_start, rec_len, read_rec_off, n_reads, \
-                           bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n, n_kmers, best_colour, best_hits, counts); \
-        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_LONG>), grid, block, 0, c->stream, (const uint64_t *)seq, rec_start, rec_len, read_rec_off, n_reads, \
-                           bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n, n_kmers, best_colour, best_hits, counts); \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_SHORT, false, TIES>), grid, block, 0, c->stream, (const uint64_t *)seq, rec_start, rec_len, read_rec_off, n_reads, \
+                           bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n, n_kmers, best_colour, best_hits, counts, ties); \
+        hipLaunchKernelGGL((k_bigsi_query<HB, BX_PLANES_LONG, false, TIES>), grid, block, 0, c->stream, (const uint64_t *)seq, rec_start, rec_len, read_rec_off, n_reads, \
+                           bigsi_kq(bx->prm), down_sample, bx->prm.bloom_size, h, bx->M.as<uint64_t>(), bx->W, bx->n, n_kmers, best_colour, best_hits, counts, ties); \
     } while (0)
     if (hb == 1) GS_BX_LAUNCH(1);
     else if (hb == 2) GS_BX_LAUNCH(2);
@@ -914,6 +980,36 @@ int gs_bigsi_query_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const 
 #undef GS_BX_LAUNCH
     GS_HIP_CHECK(hipGetLastError());
     return GS_OK;
+}
+}  // extern "C++"
+
+int gs_bigsi_query_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                       const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t *n_kmers, uint32_t *best_colour, uint32_t *best_hits,
+                       uint32_t *counts)
+{
+    (void)seq_bytes; (void)n_rec;
+    GS_REQUIRE(bx, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(down_sample >= 1, GS_ERR_INVALID, "bigsig: down_sample = 0");
+    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
+    GS_REQUIRE(n_reads == 0 || (seq && rec_start && rec_len && read_rec_off && n_kmers && best_colour && best_hits), GS_ERR_INVALID, "null argument");
+    if (n_reads == 0) return GS_OK;
+    return bigsi_query_launch<false>(bx, seq, rec_start, rec_len, read_rec_off, n_reads, down_sample, n_kmers, best_colour, best_hits, counts, gs::BxTies<false>{});
+}
+
+int gs_bigsi_query_ties_dev(gs_bigsi *bx, const void *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                            const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t max_ties, uint32_t *n_kmers, uint32_t *best_hits,
+                            uint32_t *n_tied, uint32_t *tied, uint32_t *sig_colour)
+{
+    (void)seq_bytes; (void)n_rec;
+    GS_REQUIRE(bx, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(down_sample >= 1, GS_ERR_INVALID, "bigsig: down_sample = 0");
+    GS_REQUIRE(max_ties >= 1 && max_ties <= GS_BIGSI_MAX_TIES, GS_ERR_INVALID, "bigsig: max_ties %u outside 1..%u", max_ties, GS_BIGSI_MAX_TIES);
+    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
+    GS_REQUIRE(n_reads == 0 || (seq && rec_start && rec_len && read_rec_off && n_kmers && best_hits && n_tied && tied && sig_colour), GS_ERR_INVALID, "null argument");
+    if (n_reads == 0) return GS_OK;
+    gs::BxTies<true> ties;
+    ties.tc = bx->tc.as<uint64_t>(); ties.n_tied = n_tied; ties.tied = tied; ties.sig = sig_colour; ties.max_ties = max_ties;
+    return bigsi_query_launch<true>(bx, seq, rec_start, rec_len, read_rec_off, n_reads, down_sample, n_kmers, nullptr, best_hits, nullptr, ties);
 }
 
 int gs_bigsi_query(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end, uint64_t n_rec,
@@ -944,6 +1040,58 @@ int gs_bigsi_query(gs_bigsi *bx, const void *text, const void *qual, uint32_t mi
     if (counts) GS_HIP_CHECK(hipMemcpyAsync(counts, dd.p, 4 * n_reads * bx->n, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GS_OK;
+}
+
+int gs_bigsi_query_ties(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end, uint64_t n_rec,
+                        const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t max_ties, uint32_t *n_kmers, uint32_t *best_hits,
+                        uint32_t *n_tied, uint32_t *tied, uint32_t *sig_colour)
+{
+    using namespace gs;
+    GS_REQUIRE(bx, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(down_sample >= 1, GS_ERR_INVALID, "bigsig: down_sample = 0");
+    GS_REQUIRE(max_ties >= 1 && max_ties <= GS_BIGSI_MAX_TIES, GS_ERR_INVALID, "bigsig: max_ties %u outside 1..%u", max_ties, GS_BIGSI_MAX_TIES);
+    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
+    GS_REQUIRE(n_reads == 0 || ((text || n_rec == 0) && read_rec_off && (n_rec == 0 || (rec_begin && rec_end)) && n_kmers && best_hits && n_tied && tied && sig_colour),
+               GS_ERR_INVALID, "null argument");
+    if (n_reads == 0) return GS_OK;
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    Staged s(c);
+    int rc = stage_text(c, bx->prm.k, text, qual, min_phred, rec_begin, rec_end, n_rec, read_rec_off, n_reads, s);
+    if (rc) return rc;
+    PoolBuf dn(c, SL_BIGSI_OUT_N), dh(c, SL_BIGSI_OUT_HITS), dt(c, SL_BIGSI_OUT_NTIED), dl(c, SL_BIGSI_OUT_TIED), ds(c, SL_BIGSI_OUT_SIG);
+    if ((rc = dn.alloc(4 * n_reads)) || (rc = dh.alloc(4 * n_reads)) || (rc = dt.alloc(4 * n_reads)) || (rc = dl.alloc(4 * n_reads * max_ties)) || (rc = ds.alloc(4 * n_reads)))
+        return rc;
+    rc = gs_bigsi_query_ties_dev(bx, s.seq.p, s.seq_bytes, s.rs.as<uint64_t>(), s.rl.as<uint64_t>(), s.n_seg, s.go.as<uint64_t>(), n_reads, down_sample, max_ties,
+                                 dn.as<uint32_t>(), dh.as<uint32_t>(), dt.as<uint32_t>(), dl.as<uint32_t>(), ds.as<uint32_t>());
+    if (rc) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(n_kmers, dn.p, 4 * n_reads, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(best_hits, dh.p, 4 * n_reads, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(n_tied, dt.p, 4 * n_reads, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(tied, dl.p, 4 * n_reads * max_ties, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(sig_colour, ds.p, 4 * n_reads, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int gs_bigsi_verdict_dev(gs_bigsi *bx, uint64_t n_reads, const uint32_t *n_kmers, const uint32_t *best_hits, const uint32_t *n_tied, const uint32_t *sig_colour,
+                         double fp_correct, double *tail, uint8_t *verdict)
+{
+    using namespace gs;
+    GS_REQUIRE(bx && (n_reads == 0 || (n_kmers && best_hits && n_tied && sig_colour && tail && verdict)), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(bx->n >= 1, GS_ERR_STATE, "bigsig: the index holds no genome");
+    if (n_reads == 0) return GS_OK;
+    gs_ctx *c = bx->c;
+    GS_CTX_LOCK(c);
+    hipLaunchKernelGGL(k_bigsi_verdict, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, c->stream, n_reads, n_kmers, best_hits, n_tied, sig_colour,
+                       bx->tc.as<uint64_t>(), bx->n, bx->prm.bloom_size, bx->prm.num_hash, fp_correct, tail, verdict);
+    GS_HIP_CHECK(hipGetLastError());
+    return GS_OK;
+}
+
+uint32_t gs_bigsi_verdict_code(uint32_t n_kmers, uint32_t best_hits, uint32_t n_tied, double tail, double fp_correct)
+{
+    return gs::bigsi_verdict(n_kmers, best_hits, n_tied, tail, fp_correct);
 }
 
 int gs_bigsi_classify_dev(gs_bigsi *bx, uint64_t n_reads, const uint32_t *n_kmers, const uint32_t *best_colour, const uint32_t *best_hits, double fp_correct,
@@ -1181,6 +1329,61 @@ int gs_bigsig_write_reads(const char *prefix, const char *const *accessions, uin
     GS_REQUIRE(f, GS_ERR_IO, "cannot write %s_counts.txt: %s", prefix, strerror(errno));
     for (uint64_t c : order) bad |= fprintf(f, "%s\t%llu\n", accessions[c], (unsigned long long)per[c]) < 0;
     bad |= fprintf(f, "reject\t%llu\nno_hits\t%llu\n", (unsigned long long)rejected, (unsigned long long)no_hits) < 0;
+    if (fclose(f) != 0) bad = 1;
+    GS_REQUIRE(!bad, GS_ERR_IO, "writing %s_counts.txt failed", prefix);
+    return GS_OK;
+}
+
+int gs_bigsig_write_report(const char *prefix, const char *const *accessions, uint64_t n_colours, const char *const *read_ids, uint64_t n_reads, uint32_t max_ties,
+                           const uint32_t *n_kmers, const uint32_t *best_hits, const uint32_t *n_tied, const uint32_t *tied, const uint8_t *verdict)
+{
+    GS_REQUIRE(prefix && (n_colours == 0 || accessions) && (n_reads == 0 || (read_ids && n_kmers && best_hits && n_tied && tied && verdict)), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(max_ties >= 1 && max_ties <= GS_BIGSI_MAX_TIES, GS_ERR_INVALID, "bigsig: max_ties %u outside 1..%u", max_ties, GS_BIGSI_MAX_TIES);
+    const auto listed = [&](uint64_t r) { return n_tied[r] < max_ties ? n_tied[r] : max_ties; };
+    for (uint64_t r = 0; r < n_reads; r++) {
+        GS_REQUIRE(verdict[r] <= GS_BIGSI_TIED, GS_ERR_INVALID, "read %llu has verdict %u", (unsigned long long)r, verdict[r]);
+        if (verdict[r] < GS_BIGSI_UNIQUE) continue;
+        GS_REQUIRE(n_tied[r] >= 1, GS_ERR_INVALID, "read %llu names a colour and has no tied colour", (unsigned long long)r);
+        for (uint32_t i = 0; i < listed(r); i++)
+            GS_REQUIRE(tied[r * max_ties + i] < n_colours, GS_ERR_INVALID, "read %llu names colour %u of %llu", (unsigned long long)r, tied[r * max_ties + i],
+                       (unsigned long long)n_colours);
+    }
+    const std::string p(prefix);
+    FILE *f = fopen((p + "_reads.txt").c_str(), "wb");
+    GS_REQUIRE(f, GS_ERR_IO, "cannot write %s_reads.txt: %s", prefix, strerror(errno));
+    std::vector<uint64_t> per(n_colours, 0);
+    uint64_t rejected = 0, no_hits = 0, too_short = 0;
+    int bad = 0;
+    std::string status;
+    for (uint64_t r = 0; r < n_reads; r++) {
+        const uint32_t v = verdict[r];
+        const bool named = v >= GS_BIGSI_UNIQUE;
+        if (v == GS_BIGSI_TOO_SHORT) { too_short++; status = "too_short"; }
+        else if (v == GS_BIGSI_NO_HITS) { no_hits++; status = "no_hits"; }
+        else if (v == GS_BIGSI_NOT_SIGNIFICANT) { rejected++; status = "no_significant_hits"; }
+        else if (v == GS_BIGSI_UNIQUE) { per[tied[r * max_ties]]++; status = accessions[tied[r * max_ties]]; }
+        else {
+            rejected++;
+            status.clear();
+            for (uint32_t i = 0; i < listed(r); i++) { if (i) status += ','; status += accessions[tied[r * max_ties + i]]; }
+            if (n_tied[r] > max_ties) status += ",...";
+        }
+        bad |= fprintf(f, "%s\t%s\t%u\t%u\t%s\t%u\n", read_ids[r], status.c_str(), named ? best_hits[r] : 0u, n_kmers[r],
+                       v == GS_BIGSI_NOT_SIGNIFICANT || v == GS_BIGSI_TIED ? "reject" : "accept", v == GS_BIGSI_UNIQUE ? 1u : (v == GS_BIGSI_TIED ? n_tied[r] : 0u)) < 0;
+    }
+    if (fclose(f) != 0) bad = 1;
+    GS_REQUIRE(!bad, GS_ERR_IO, "writing %s_reads.txt failed", prefix);
+    std::vector<uint64_t> order;
+    for (uint64_t c = 0; c < n_colours; c++) if (per[c]) order.push_back(c);
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
+        if (per[a] != per[b]) return per[a] > per[b];
+        const int s = strcmp(accessions[a], accessions[b]);
+        return s != 0 ? s < 0 : a < b;
+    });
+    f = fopen((p + "_counts.txt").c_str(), "wb");
+    GS_REQUIRE(f, GS_ERR_IO, "cannot write %s_counts.txt: %s", prefix, strerror(errno));
+    for (uint64_t c : order) bad |= fprintf(f, "%s\t%llu\n", accessions[c], (unsigned long long)per[c]) < 0;
+    bad |= fprintf(f, "reject\t%llu\nno_hits\t%llu\ntoo_short\t%llu\n", (unsigned long long)rejected, (unsigned long long)no_hits, (unsigned long long)too_short) < 0;
     if (fclose(f) != 0) bad = 1;
     GS_REQUIRE(!bad, GS_ERR_IO, "writing %s_counts.txt failed", prefix);
     return GS_OK;

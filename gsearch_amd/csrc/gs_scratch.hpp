@@ -63,6 +63,8 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     X(BIGSI_REC_TILES) X(BIGSI_GENOME_TILES) X(BIGSI_GENOME_WINDOWS) X(BIGSI_Q_OFF) X(BIGSI_Q_CNT) X(BIGSI_Q_VALS)                                    \
     /* bigsig, sort-count-filter build of one colour: value list and its second buffer, run lengths, head positions, radix counts, cursor + runs */  \
     X(BIGSI_LIST_VALS) X(BIGSI_LIST_ALT) X(BIGSI_LIST_LEN) X(BIGSI_LIST_POS) X(BIGSI_LIST_RADIX) X(BIGSI_LIST_CTR)                                    \
+    /* bigsig, the query with ties (host form): per read the number of tied colours, the listed ones, the most significant one */                      \
+    X(BIGSI_OUT_NTIED) X(BIGSI_OUT_TIED) X(BIGSI_OUT_SIG)                                                                                              \
     /* superani (gs_ani.hip), seeds: staging of the host form, unit prefix and per-unit counts of a block of genomes, the seeds of a block */           \
     X(ANIB_SEQ) X(ANIB_REC_START) X(ANIB_REC_LEN) X(ANIB_GOFF) X(ANI_UPRE) X(ANI_GUNIT) X(ANI_UCNT) X(ANI_GBASE) X(ANI_SEEDS)                         \
     /* superani, pairs: staging of the host form, value-ordered keys of both sides, slices of a block of pairs and its offsets */                      \

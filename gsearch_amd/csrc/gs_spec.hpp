@@ -426,6 +426,15 @@ GS_HD double bigsi_tail(uint64_t t_c, uint64_t B, uint32_t h, uint32_t n, uint32
     }
     return tail < 1.0 ? tail : 1.0;
 }
+// SPEC 11.2: the verdict table, the first row that holds (the codes: GS_BIGSI_TOO_SHORT .. GS_BIGSI_TIED of gsearch_amd.h). A tail equal to the threshold is
+// not significant, and neither is a NaN.
+GS_HD uint8_t bigsi_verdict(uint32_t n, uint32_t best_hits, uint32_t n_tied, double tail, double fp)
+{
+    if (n == 0) return 0;
+    if (best_hits == 0) return 1;
+    if (!(tail < fp)) return 2;
+    return n_tied == 1 ? 3 : 4;
+}
 
 // ---- SPEC 12: superani (binaux/src/bin/superani.rs) - seed-chaining ANI of genome pairs. [CHOICE] throughout (the `skani` crate is not vendored).
 #define GS_ANI_KMIN 8u

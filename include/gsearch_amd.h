@@ -749,6 +749,34 @@ int    gs_bigsi_minimizers(const void *text, const void *qual, uint64_t n, uint3
  * accession, reads over the accepted reads (descending by count, then by accession), then a `reject` and a `no_hits` line. Host only. */
 int    gs_bigsig_write_reads(const char *prefix, const char *const *accessions, uint64_t n_colours, const char *const *read_ids, uint64_t n_reads,
                              const uint32_t *best_colour, const uint32_t *best_hits, const uint32_t *n_kmers, const uint8_t *accept);
+/* Tied top hits and the six-field report (SPEC.md 11.2). The query with ties: n_kmers and best_hits as gs_bigsi_query; n_tied[r] = the number of colours
+ * that reach best_hits (0 when best_hits is 0), exact; tied[r x max_ties ..] = the min(n_tied, max_ties) smallest of them, ascending, UINT32_MAX in the
+ * slots behind them (written by the call: the buffer may hold anything); sig_colour[r] = the tied colour with the fewest bits set, the smallest of equal
+ * ones (UINT32_MAX when best_hits is 0), taken over all tied colours. tied[r x max_ties] is gs_bigsi_query's best_colour wherever best_hits > 0.
+ * max_ties outside 1 .. GS_BIGSI_MAX_TIES: GS_ERR_INVALID; the other codes are gs_bigsi_query's. The _dev form queues on the context's stream. */
+#define GS_BIGSI_MAX_TIES 1024u
+#define GS_BIGSI_DEFAULT_TIES 16u
+int    gs_bigsi_query_ties_dev(gs_bigsi *bx, const void *seq_dev, uint64_t seq_bytes, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                               const uint64_t *read_rec_off_dev, uint64_t n_reads, uint32_t down_sample, uint32_t max_ties, uint32_t *n_kmers_dev,
+                               uint32_t *best_hits_dev, uint32_t *n_tied_dev, uint32_t *tied_dev, uint32_t *sig_colour_dev);
+int    gs_bigsi_query_ties(gs_bigsi *bx, const void *text, const void *qual, uint32_t min_phred, const uint64_t *rec_begin, const uint64_t *rec_end,
+                           uint64_t n_rec, const uint64_t *read_rec_off, uint64_t n_reads, uint32_t down_sample, uint32_t max_ties, uint32_t *n_kmers,
+                           uint32_t *best_hits, uint32_t *n_tied, uint32_t *tied, uint32_t *sig_colour);
+/* the verdict of a read, the first row that holds: no occurrence used; no hit; the tail of sig_colour not below fp_correct; one top colour; several */
+enum { GS_BIGSI_TOO_SHORT = 0, GS_BIGSI_NO_HITS = 1, GS_BIGSI_NOT_SIGNIFICANT = 2, GS_BIGSI_UNIQUE = 3, GS_BIGSI_TIED = 4 };
+/* tail[r] = gs_bigsi_tail for c = sig_colour (1.0 where best_hits is 0); verdict[r] = gs_bigsi_verdict_code of the read */
+int    gs_bigsi_verdict_dev(gs_bigsi *bx, uint64_t n_reads, const uint32_t *n_kmers_dev, const uint32_t *best_hits_dev, const uint32_t *n_tied_dev,
+                            const uint32_t *sig_colour_dev, double fp_correct, double *tail_dev, uint8_t *verdict_dev);
+/* host arithmetic, no device: the verdict table alone */
+uint32_t gs_bigsi_verdict_code(uint32_t n_kmers, uint32_t best_hits, uint32_t n_tied, double tail, double fp_correct);
+/* `{prefix}_reads.txt`: read_id, status, hits, n_kmers, accept | reject, ties - tab-separated, one line per read. status: too_short | no_hits |
+ * no_significant_hits | the accession | the listed accessions joined by `,` (then `,...` when n_tied > max_ties); hits and ties are 0 in the first three.
+ * `{prefix}_counts.txt`: accession, reads over the GS_BIGSI_UNIQUE reads (descending by count, then by accession), then a `reject` (not significant + tied),
+ * a `no_hits` and a `too_short` line. A verdict above GS_BIGSI_TIED, max_ties outside 1 .. GS_BIGSI_MAX_TIES, and on a UNIQUE or TIED read n_tied = 0 or a
+ * listed colour >= n_colours: GS_ERR_INVALID, before anything is written. Host only. */
+int    gs_bigsig_write_report(const char *prefix, const char *const *accessions, uint64_t n_colours, const char *const *read_ids, uint64_t n_reads,
+                              uint32_t max_ties, const uint32_t *n_kmers, const uint32_t *best_hits, const uint32_t *n_tied, const uint32_t *tied,
+                              const uint8_t *verdict);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* Multi-GPU: one process per GPU, query batches sharded, DB + graph replicated. The path has ONE exchange step - the

@@ -305,6 +305,10 @@ private:
 // colour with the most k-mer hits and whether that many hits are significant. A genome or a read is a list of records (ASCII text); the mates of a
 // pair are two records of one read.
 struct BigsiHits { std::vector<uint32_t> n_kmers, best_colour, best_hits; std::vector<double> tail; std::vector<uint8_t> accept; };
+struct BigsiTies {
+    uint32_t max_ties;
+    std::vector<uint32_t> n_kmers, best_hits, n_tied, tied, sig_colour; std::vector<double> tail; std::vector<uint8_t> verdict;      // verdict: GS_BIGSI_TOO_SHORT ..
+};
 class Bigsi {
 public:
     // minimizer_len = m > 0: a minimizer index (SPEC 11.1) of window length k
@@ -364,6 +368,38 @@ public:
         check(gs_dev_download(ctx_->get(), out.accept.data(), d[4], n));
         for (int i = 0; i < 5; i++) check(gs_dev_free(ctx_->get(), d[i]));
         return out;
+    }
+    // SPEC 11.2: every colour that reaches the top count (tied: n_reads x max_ties, UINT32_MAX behind a list), the tail of the most significant one, the verdict
+    BigsiTies identify_ties(const std::vector<std::vector<std::string>> &reads, const std::vector<std::vector<std::string>> &quals = {}, uint32_t min_phred = 15,
+                            uint32_t down_sample = 1, double fp_correct = 1e-3, uint32_t max_ties = GS_BIGSI_DEFAULT_TIES) const
+    {
+        Text t(reads), q(quals);
+        const uint64_t n = reads.size();
+        BigsiTies out{max_ties, std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::vector<uint32_t>(n), std::vector<uint32_t>(n * max_ties),
+                      std::vector<uint32_t>(n), std::vector<double>(n), std::vector<uint8_t>(n)};
+        check(gs_bigsi_query_ties(bx_, t.text.data(), quals.empty() ? nullptr : q.text.data(), min_phred, t.begin.data(), t.end.data(), t.begin.size(), t.off.data(), n,
+                                  down_sample, max_ties, out.n_kmers.data(), out.best_hits.data(), out.n_tied.data(), out.tied.data(), out.sig_colour.data()));
+        if (n == 0) return out;
+        void *d[6] = {};
+        const size_t bytes[6] = {4 * n, 4 * n, 4 * n, 4 * n, 8 * n, n};
+        const uint32_t *src[4] = {out.n_kmers.data(), out.best_hits.data(), out.n_tied.data(), out.sig_colour.data()};
+        for (int i = 0; i < 6; i++) check(gs_dev_alloc(ctx_->get(), bytes[i], &d[i]));
+        for (int i = 0; i < 4; i++) check(gs_dev_upload(ctx_->get(), d[i], src[i], 4 * n));
+        check(gs_bigsi_verdict_dev(bx_, n, (const uint32_t *)d[0], (const uint32_t *)d[1], (const uint32_t *)d[2], (const uint32_t *)d[3], fp_correct, (double *)d[4],
+                                   (uint8_t *)d[5]));
+        check(gs_dev_download(ctx_->get(), out.tail.data(), d[4], 8 * n));
+        check(gs_dev_download(ctx_->get(), out.verdict.data(), d[5], n));
+        for (int i = 0; i < 6; i++) check(gs_dev_free(ctx_->get(), d[i]));
+        return out;
+    }
+    // the six-field `{prefix}_reads.txt` and `{prefix}_counts.txt`, with the accessions given to add_genomes
+    void write_report(const std::string &prefix, const std::vector<std::string> &read_ids, const BigsiTies &r) const
+    {
+        std::vector<const char *> acc, ids;
+        for (const auto &x : names_) acc.push_back(x.c_str());
+        for (const auto &x : read_ids) ids.push_back(x.c_str());
+        check(gs_bigsig_write_report(prefix.c_str(), acc.data(), acc.size(), ids.data(), ids.size(), r.max_ties, r.n_kmers.data(), r.best_hits.data(), r.n_tied.data(),
+                                     r.tied.data(), r.verdict.data()));
     }
     void save(const std::string &path) const { check(gs_bigsi_save(bx_, path.c_str())); }
 

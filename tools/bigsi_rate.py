@@ -6,7 +6,10 @@ the same run; the classify time; and checks a sample of reads and one column aga
 --minimizer M adds, after the plain legs and in the same run, the same build and query on a minimizer index of window K and minimizer length M (SPEC 11.1),
 with the share of the query time spent in k_bigsi_minimizers; --min-count F adds the build of a few colours under the coverage filter with its split into
 emit / sort / fill (on the plain index, and on the minimizer index when --minimizer is given). The splits come from the event timers of gs_ctx_profile.
-usage: bigsi_rate.py [--genomes N] [--mbp L] [--log2-rows R] [--hashes H] [--k K] [--reads Q] [--down-sample D] [--minimizer M] [--min-count F]"""
+--ties runs the same reads through the query with ties (SPEC 11.2) next to the plain query, in the same run: on the index above, where no tie is planted, and
+on a second index in which colour c holds genome c // 8, so that every read is tied 8 ways; with --minimizer also on the minimizer index.
+usage: bigsi_rate.py [--genomes N] [--mbp L] [--log2-rows R] [--hashes H] [--k K] [--reads Q] [--down-sample D] [--minimizer M] [--min-count F] [--ties]
+                     [--max-ties T]"""
 import argparse, os, sys, time
 import ctypes as C
 import numpy as np
@@ -30,6 +33,8 @@ ap.add_argument("--chunk", type=int, default=512)
 ap.add_argument("--minimizer", type=int, default=0)
 ap.add_argument("--min-count", type=int, default=0)
 ap.add_argument("--filter-colours", type=int, default=4)
+ap.add_argument("--ties", action="store_true")
+ap.add_argument("--max-ties", type=int, default=16)
 a = ap.parse_args()
 
 ctx = G.Context(0)
@@ -148,6 +153,65 @@ for r in mine:
 print("query: %d reads cut from genome 0 against pyref_bigsi (n, best colour, best hits = n): %s" % (len(mine), "equal" if ok else "MISMATCH"), flush=True)
 
 
+# ---- the query with ties beside the plain query: the same reads, the same run ---------------------------------------------------------------------
+def timed(f, repeats=5):
+    f(min(Q, 20000))                                                               # warm-up
+    ctx.sync()
+    out = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        f(Q)
+        ctx.sync()
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def ties_leg(ix, label, p_rs):
+    """plain and ties form in turn on the reads that begin at p_rs; the ties form's arrays against the plain form's"""
+    tp = timed(lambda q: ix.query_dev(d_seq, sb, p_rs, d_rl, Q, d_go, q, d_n, d_c, d_h, down_sample=a.down_sample))
+    pn, pc, ph = (ctx.download(p, Q, np.uint32) for p in (d_n, d_c, d_h))
+    tt = timed(lambda q: ix.query_ties_dev(d_seq, sb, p_rs, d_rl, Q, d_go, q, d_n, d_h, d_nt, d_td, d_sg, down_sample=a.down_sample, max_ties=a.max_ties))
+    tn, th, nt, sg = (ctx.download(p, Q, np.uint32) for p in (d_n, d_h, d_nt, d_sg))
+    td = ctx.download(d_td, (Q, a.max_ties), np.uint32)
+    t0 = time.perf_counter()
+    ix.verdict_dev(Q, d_n, d_h, d_nt, d_sg, 1e-3, d_t, d_acc)
+    ctx.sync()
+    tv = time.perf_counter() - t0
+    vd = ctx.download(d_acc, Q, np.uint8)
+    same = np.array_equal(pn, tn) and np.array_equal(ph, th) and np.array_equal(td[:, 0][th > 0], pc[th > 0]) and bool((td[:, 0][th == 0] == 0xFFFFFFFF).all())
+    print("%s: plain %.4f s (runs: %s; spread %.1f %%), ties %.4f s (runs: %s; spread %.1f %%): ties / plain = %.3f; verdict %.4f s; n_tied: mean %.2f, max %d, "
+          "reads with a tie %d; verdicts %s; n, hits and tied[0] against the plain query: %s" %
+          (label, min(tp), " ".join("%.4f" % x for x in tp), 100 * (max(tp) - min(tp)) / min(tp), min(tt), " ".join("%.4f" % x for x in tt),
+           100 * (max(tt) - min(tt)) / min(tt), min(tt) / min(tp), tv, nt.mean(), nt.max(), int((nt > 1).sum()), np.bincount(vd, minlength=5).tolist(),
+           "equal" if same else "MISMATCH"), flush=True)
+    return nt
+
+
+if a.ties:
+    d_nt, d_td, d_sg = ctx.alloc(4 * Q), ctx.alloc(4 * Q * a.max_ties), ctx.alloc(4 * Q)
+    ties_leg(bx, "ties, none planted", d_rs)
+    # colour c holds genome c // 8: the records of a chunk's 8 x fewer genomes, each named by 8 colours
+    n8 = max(min(N // 8, own), 1)
+    tx = G.Bigsi(k, h, B, N, ctx=ctx)
+    d_gen8 = ctx.alloc((chunk // 8 + 1) * words * 8 + 64)
+    t_rs, t_rl, t_go = ctx.alloc(8 * chunk), ctx.alloc(8 * chunk), ctx.alloc(8 * (chunk + 1))
+    ctx.upload(t_rs, (np.arange(chunk, dtype=np.uint64) // np.uint64(8)) * np.uint64(words * 32)); ctx.upload(t_rl, np.full(chunk, L, np.uint64))
+    ctx.upload(t_go, np.arange(chunk + 1, dtype=np.uint64))
+    for first in range(0, N // 8 * 8, chunk):
+        c = min(chunk, N // 8 * 8 - first)
+        chk(lib.gs_synth_dna_dev(ctx.h, seed, first // 8, (c + 7) // 8, L, d_gen8))
+        tx.add_genomes_dev(d_gen8, ((c + 7) // 8) * words * 8 + 64, t_rs, t_rl, c, t_go, c)
+    ctx.sync()
+    start8 = rng.integers(0, n8, Q).astype(np.uint64) * np.uint64(words * 32) + rng.integers(0, L - RL, Q).astype(np.uint64)
+    d_rs8 = ctx.alloc(8 * Q)
+    ctx.upload(d_rs8, start8)
+    nt8 = ties_leg(tx, "ties, every read cut from a genome held by 8 colours", d_rs8)
+    print("ties: reads with n_tied >= 8: %d of %d" % (int((nt8 >= 8).sum()), Q), flush=True)
+    tx.close()
+    for p in (d_gen8, t_rs, t_rl, t_go, d_rs8):
+        ctx.free(p)
+
+
 # ---- the minimizer index and the coverage filter, beside the plain legs above -------------------------------------------------------------------------
 FAM_SKETCH, FAM_HAMMING, FAM_SEARCH, FAM_INSERT = 0, 1, 2, 3           # gs_internal.hpp: the families the steps of gs_bigsi.hip are timed as
 if a.minimizer or a.min_count > 1:
@@ -247,6 +311,8 @@ if a.minimizer:
         v = PM.minimizers(g0[s_:s_ + RL], k, m)[0][:: a.down_sample]
         ok = ok and int(mn_used[r]) == len(v) and int(mhits[r]) == len(v) and int(mcol[r]) == 0
     print("minimizer query: %d reads cut from genome 0 against pyref_bigsi_mini (n, best colour, best hits = n): %s" % (len(mine), "equal" if ok else "MISMATCH"), flush=True)
+    if a.ties:
+        ties_leg(mx, "minimizer (%d, %d) ties, none planted" % (k, m), d_rs)
     mx.close()
     if a.min_count > 1:
         filter_leg(m, "minimizer (%d, %d)" % (k, m))
