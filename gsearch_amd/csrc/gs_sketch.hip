@@ -18,6 +18,7 @@
 #include <vector>
 #include "gs_internal.hpp"
 #include "gs_spec.hpp"
+#include "gs_skq.hpp"
 #include "gs_walk.hpp"
 
 namespace gs {
@@ -85,7 +86,9 @@ struct MinEmit {
 // of its arithmetic is skipped: exact. Lanes diverge on that test, so the survivors (a few % once the table has warmed up) are
 // compacted through a per-wave LDS queue of element hashes and finished 64 at a time by the whole wave. Only full waves use the queue
 // (its fill count stays wave-uniform in a register); record boundaries and partial waves take the direct form.
-constexpr int SKQ = 128;          // queue entries per wave: < 64 pending + <= 64 new
+// The queue holds SKQ = 128 hashes per wave (gs_skq.hpp): fewer than 64 pending and at most 64 new ones; the k-mers of an interior word come two at
+// a time and share one push (full2). An entry is h + gamma alone: carrying s0 or s3 beside it (16-byte entries, 64 of them, a push split around the
+// flush) spares the flush a mix and was measured slower - DESIGN.md 3.1, "One push per pair of k-mers".
 template <int ALGO, int VBITS, typename T>
 struct MinEmitF {
     T *table; uint32_t m; uint64_t zone;
@@ -124,28 +127,62 @@ struct MinEmitF {
         return (uint32_t)(o1 >> 32) < ((uint32_t)t << 9);
     }
     __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const { apply(elem_hash<ALGO, VBITS>(v)); }
-    __device__ __forceinline__ void full(uint64_t v) const
+    // The lanes of `bal` (bal != 0) queue a hash each - hg_a where in_a, hg_b where in_b, never both; 64 pending survivors are flushed on the way.
+    __device__ __forceinline__ void push(uint64_t bal, bool in_a, uint64_t hg_a, bool in_b, uint64_t hg_b) const
+    {
+        // the slot is qn + the lanes below that pass: qn rides in the mbcnt pair's addend, and with the wave's queue base uniform
+        // (an SGPR) the LDS address is one v_lshl_add_u32 - instead of two shifts and a v_add3_u32
+        const uint32_t idx = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, qn));
+        // two masked writes, kept apart: merged into one write of a selected hash they would cost two v_cndmask_b32, and the kernel is bound
+        // by VALU issue, not by LDS writes
+        if (in_a) q[idx] = hg_a;
+        asm volatile("" ::: "memory");
+        if (in_b) q[idx] = hg_b;
+        const SkqPush p = skq_push(qn, (uint32_t)__popcll(bal));
+        if (p.flush) {
+            apply(q[lane] - GS_GAMMA);
+            const uint64_t mv = q[SKQ_FLUSH + lane];
+            if (lane < p.pending) q[lane] = mv;
+        }
+        qn = p.pending;
+    }
+    // h + gamma of a k-mer
+    static __device__ __forceinline__ uint64_t hash_gamma(uint64_t v)
     {
         // one hash chain: h + gamma straight from the element hash (gamma rides in the addend of its low v_mad_u64_u32), h + 4 gamma from
         // that (one v_lshl_add_u64), and the queue holds h + gamma - instead of h, h + gamma and h + 4 gamma each from h (-1 mad, -1 add3)
         uint64_t hg = elem_hash<ALGO, VBITS>(v, GS_GAMMA);
         asm("" : "+v"(hg));         // opaque: the compiler would otherwise rebuild h beside h + gamma and derive h + 4 gamma from h
-        if (thr >= direct_above()) { apply(hg - GS_GAMMA); return; }            // wave-uniform
+        return hg;
+    }
+    // the key only needs two of the three SplitMix64 outputs
+    __device__ __forceinline__ bool filter(uint64_t hg) const
+    {
         const uint64_t s0 = splitmix_mix(hg), s3 = splitmix_mix(hg + 3 * GS_GAMMA);
-        const bool pass = key_below(rotl64(s0 + s3, 23) + s0, thr);
+        return key_below(rotl64(s0 + s3, 23) + s0, thr);
+    }
+    __device__ __forceinline__ void full(uint64_t v) const
+    {
+        const uint64_t hg = hash_gamma(v);
+        if (thr >= direct_above()) { apply(hg - GS_GAMMA); return; }            // wave-uniform
+        const bool pass = filter(hg);
         const uint64_t bal = __ballot(pass);
-        if (bal) {
-            // the slot is qn + the lanes below that pass: qn rides in the mbcnt pair's addend, and with the wave's queue base uniform
-            // (an SGPR) the LDS address is one v_lshl_add_u32 - instead of two shifts and a v_add3_u32
-            if (pass) q[__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, qn))] = hg;
-            qn += (uint32_t)__popcll(bal);
-            if (qn >= 64) {
-                apply(q[lane] - GS_GAMMA);
-                const uint32_t rest = qn - 64;
-                const uint64_t mv = q[64 + lane];
-                if (lane < rest) q[lane] = mv;
-                qn = rest;
-            }
+        if (bal) push(bal, pass, hg, false, hg);
+    }
+    // Two k-mers, ONE push for the lanes where either survives. At ~7 % survivors a wave of 64 lanes nearly always holds one, so the push -
+    // ballot, mbcnt pair, address, masked write, fill count, flush test - ran per k-mer; the lanes where BOTH survive (a wave holds one in
+    // about a quarter of the pairs) push their second hash behind a wave-uniform branch. The survivors reach the table in another order
+    // than one by one, which a slot minimum does not see.
+    __device__ __forceinline__ void full2(uint64_t v_a, uint64_t v_b) const
+    {
+        const uint64_t hg_a = hash_gamma(v_a), hg_b = hash_gamma(v_b);
+        if (thr >= direct_above()) { apply(hg_a - GS_GAMMA); apply(hg_b - GS_GAMMA); return; }            // wave-uniform
+        const bool pass_a = filter(hg_a), pass_b = filter(hg_b);
+        const uint64_t bal_a = __ballot(pass_a), bal_b = __ballot(pass_b);
+        if (bal_a | bal_b) {
+            // the compares leave lane masks in SGPR pairs: only b / both are scalar operations on them
+            push(bal_a | bal_b, pass_a, hg_a, pass_b && !pass_a, hg_b);
+            if (bal_a & bal_b) push(bal_a & bal_b, pass_a && pass_b, hg_b, false, hg_b);
         }
     }
     __device__ __forceinline__ void word_done() const
@@ -157,7 +194,15 @@ struct MinEmitF {
         for (uint32_t i = lane; i < m; i += 64) { const T x = table[i]; mx = x > mx ? x : mx; }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { const T y = __shfl_xor(mx, o); mx = y > mx ? y : mx; }
-        thr = mx < cap ? mx : cap;
+        // every lane holds the same maximum; taken through an SGPR so that the compiler knows it too: the filter test compares against a scalar
+        // and the branch to the direct form is a scalar one
+        thr = uniform(mx < cap ? mx : cap);
+    }
+    static __device__ __forceinline__ T uniform(T x)
+    {
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x);
+        if (sizeof(T) == 4) return (T)lo;
+        return (T)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32)) << 32) | lo);
     }
     __device__ __forceinline__ void finish() const
     {
@@ -166,6 +211,7 @@ struct MinEmitF {
     }
 };
 template <int ALGO, int VBITS, typename T> __device__ __forceinline__ void emit_full_wave(const MinEmitF<ALGO, VBITS, T> &e, uint64_t v, uint64_t, uint64_t) { e.full(v); }
+template <int ALGO, int VBITS, typename T> __device__ __forceinline__ void emit_full_wave2(const MinEmitF<ALGO, VBITS, T> &e, uint64_t v_a, uint64_t v_b, uint64_t, uint64_t) { e.full2(v_a, v_b); }
 template <int ALGO, int VBITS, typename T> __device__ __forceinline__ void emit_word_done(const MinEmitF<ALGO, VBITS, T> &e) { e.word_done(); }
 template <int ALGO, int VBITS, typename T> __device__ __forceinline__ void emit_finish(const MinEmitF<ALGO, VBITS, T> &e) { e.finish(); }
 

@@ -123,11 +123,9 @@ GS_HD uint64_t rng_uint(Rng &g, uint64_t n, uint64_t zone)
 // Only s0,s1,s3 are needed for two outputs; the full generator is re-run in the (probability m/2^64)
 // rejection case so that the result is exactly the sequential definition.
 // two_draw: first output o1 (the r draw: U32f bits = o1>>41, next32 = o1>>32, next64 = o1) and b = Uint(m) from the second.
-GS_HD void two_draw(uint64_t h, uint32_t m, uint64_t zone, uint64_t &o1, uint32_t &bin)
+// two_draw_from: the same from the three states a caller already holds some of (s0, s1, s3 of Rng::seed(h)); h itself only for the re-run.
+GS_HD void two_draw_from(uint64_t h, uint64_t s0, uint64_t s1, uint64_t s3, uint32_t m, uint64_t zone, uint64_t &o1, uint32_t &bin)
 {
-    uint64_t s0 = splitmix_mix(h + GS_GAMMA);
-    uint64_t s1 = splitmix_mix(h + 2 * GS_GAMMA);
-    uint64_t s3 = splitmix_mix(h + 4 * GS_GAMMA);
     o1 = rotl64(s0 + s3, 23) + s0;
     uint64_t n3 = s3 ^ s1;           // s3 after the first step, before rotation
     uint64_t n0 = s0 ^ n3;           // s0 after the first step
@@ -143,6 +141,10 @@ GS_HD void two_draw(uint64_t h, uint32_t m, uint64_t zone, uint64_t &o1, uint32_
     if (lo <= zone) return;
     Rng g; g.seed(h); (void)g.next64();
     bin = (uint32_t)rng_uint(g, (uint64_t)m, zone);
+}
+GS_HD void two_draw(uint64_t h, uint32_t m, uint64_t zone, uint64_t &o1, uint32_t &bin)
+{
+    two_draw_from(h, splitmix_mix(h + GS_GAMMA), splitmix_mix(h + 2 * GS_GAMMA), splitmix_mix(h + 4 * GS_GAMMA), m, zone, o1, bin);
 }
 GS_HD void oph_draw(uint64_t h, uint32_t m, uint64_t zone, uint32_t &r23, uint32_t &bin)
 {

@@ -22,8 +22,14 @@ __global__ void k_unit_prefix(const uint64_t *rec_start, const uint64_t *rec_len
                               uint64_t n_genomes, uint32_t k, uint64_t *rec_upre, uint64_t *gen_units);
 
 // Hooks of walk_genome that only the filtered emitter overrides: a k-mer emitted by a FULL wavefront (all 64 lanes inside a record),
-// the end of such a word, and the end of the walk.
+// two consecutive ones (positions pos and pos + 1: an emitter that compacts across the wave may push them together), the end of such a
+// word, and the end of the walk.
 template <class E> __device__ __forceinline__ void emit_full_wave(const E &e, uint64_t v, uint64_t rec, uint64_t pos) { e(v, rec, pos); }
+template <class E> __device__ __forceinline__ void emit_full_wave2(const E &e, uint64_t v_a, uint64_t v_b, uint64_t rec, uint64_t pos)
+{
+    emit_full_wave(e, v_a, rec, pos);
+    emit_full_wave(e, v_b, rec, pos + 1);
+}
 template <class E> __device__ __forceinline__ void emit_word_done(const E &) {}
 template <class E> __device__ __forceinline__ void emit_finish(const E &) {}
 
@@ -55,31 +61,31 @@ __device__ __forceinline__ void walk_word_funnel(uint64_t w, uint64_t pw, uint32
     uint32_t t = 33 - k, qy = t >> 4;                      // 1 <= t <= 32: qy in 0..2
     uint32_t r0 = qy == 0 ? y0 : qy == 1 ? y1 : y2, r1 = qy == 0 ? y1 : qy == 1 ? y2 : y3, r2 = qy == 0 ? y2 : qy == 1 ? y3 : 0u;
     uint32_t j = 0;
+    // the window that ends at base j under the word roles of its segment
+    auto window = [&](uint32_t j, uint32_t t) -> uint64_t {
+        const uint32_t sf = 62 - 2 * j, sr = 2 * t;        // alignbit takes the shift mod 32
+        if (WIDE) {
+            const uint32_t fl = __builtin_amdgcn_alignbit(f1, f0, sf), fh = __builtin_amdgcn_alignbit(f2, f1, sf) & mhi;
+            if (RCM == 1) return ((uint64_t)fh << 32) | fl;
+            uint32_t rl = __builtin_amdgcn_alignbit(r1, r0, sr), rh = __builtin_amdgcn_alignbit(r2, r1, sr) & mhi;
+            if (RCM == 2) { rl |= olo; rh |= ohi; }
+            const uint64_t fw = ((uint64_t)fh << 32) | fl, rc = ((uint64_t)rh << 32) | rl;
+            return fw < rc ? fw : rc;
+        }
+        const uint32_t fl = __builtin_amdgcn_alignbit(f1, f0, sf) & mlo;
+        if (RCM == 1) return fl;
+        uint32_t rl = __builtin_amdgcn_alignbit(r1, r0, sr) & mlo;
+        if (RCM == 2) rl |= olo;
+        return min(fl, rl);
+    };
     for (;;) {
         const uint32_t je = min(j < 16 ? 16u : 32u, j + 16 - (t & 15));
-        for (; j < je; j++, t++) {
-            const uint32_t sf = 62 - 2 * j, sr = 2 * t;    // alignbit takes the shift mod 32
-            uint64_t v;
-            if (WIDE) {
-                const uint32_t fl = __builtin_amdgcn_alignbit(f1, f0, sf), fh = __builtin_amdgcn_alignbit(f2, f1, sf) & mhi;
-                if (RCM == 1) v = ((uint64_t)fh << 32) | fl;
-                else {
-                    uint32_t rl = __builtin_amdgcn_alignbit(r1, r0, sr), rh = __builtin_amdgcn_alignbit(r2, r1, sr) & mhi;
-                    if (RCM == 2) { rl |= olo; rh |= ohi; }
-                    const uint64_t fw = ((uint64_t)fh << 32) | fl, rc = ((uint64_t)rh << 32) | rl;
-                    v = fw < rc ? fw : rc;
-                }
-            } else {
-                const uint32_t fl = __builtin_amdgcn_alignbit(f1, f0, sf) & mlo;
-                if (RCM == 1) v = fl;
-                else {
-                    uint32_t rl = __builtin_amdgcn_alignbit(r1, r0, sr) & mlo;
-                    if (RCM == 2) rl |= olo;
-                    v = min(fl, rl);
-                }
-            }
-            emit_full_wave(emit, v, rec, a0 + j);
+        // two windows at a time, never across a segment's end (the word roles move there); a segment of odd length - even k: t & 15 is odd - ends on one
+        for (; j + 1 < je; j += 2, t += 2) {
+            const uint64_t va = window(j, t), vb = window(j + 1, t + 1);
+            emit_full_wave2(emit, va, vb, rec, a0 + j);
         }
+        if (j < je) { emit_full_wave(emit, window(j, t), rec, a0 + j); j++; t++; }
         if (j == 32) break;
         if (j == 16) { f2 = f1; f1 = f0; f0 = x0; }
         if ((t & 15) == 0) { r0 = r1; r1 = r2; r2 = qy == 0 ? y3 : 0u; qy++; }
