@@ -27,6 +27,7 @@
 #include <condition_variable>
 #include <deque>
 #include "gs_inflate.hpp"
+#include "gs_gzdeal.hpp"
 
 namespace gs {
 int ingest_records_dev(gs_ctx *c, bool aa, bool contiguous, const void *text_dev, uint64_t n_bytes, const uint64_t *seq_begin, const uint64_t *seq_end,
@@ -488,37 +489,14 @@ int gs_list_fasta_files(const char *dir, int data_t, char *paths_buf, uint64_t c
  * residues that reached the sketcher. stats_out (optional, 6 doubles, see include/gsearch_amd.h): host seconds spent reading+decompressing+scanning (summed over
  * threads), seconds the caller waited for PCIe copies, seconds in device pack + sketch, wall seconds of the call.
  */
-// The .gz files of a call are dealt between two pipelines as they go (see gs_sketch_files): the host pipeline claims them from the front of
-// the list, the device pipeline from the back, group by group, until the two meet.
-// The device pipeline takes a group only as large as lets both finish together. Host pipeline: rate ra (files/s, measured once 256 files are
-// done, a prior before). Device pipeline: a start-up latency (reading, copying and inflating its first group: nothing is done before) and a
-// rate rb behind it. With pa, pb files claimed but unfinished and R unclaimed: lat + (pb + k) / rb = (R - k + pa) / ra.
-struct GzDeal {
-    std::mutex m; uint64_t n_gz = 0, front = 0, back = 0, done_front = 0, done_back = 0;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    static constexpr double LAT = 0.45;
-    double rate(bool back_side) const
-    {
-        const uint64_t d = back_side ? done_back : done_front;
-        const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - (back_side ? LAT : 0.0);
-        return d >= 256 && el > 0.05 ? (double)d / el : (back_side ? 3500.0 : 2300.0);
-    }
-    // members the device pipeline should take now out of `avail`
-    double device_share(uint64_t avail) const
-    {
-        const double ra = rate(false), rb = rate(true);
-        const double pa = (double)(front - done_front), pb = (double)(back - done_back);
-        return (((double)avail + pa) / ra - pb / rb - (done_back ? 0.0 : LAT)) / (1.0 / rb + 1.0 / ra);
-    }
-};
-
 // dev_gzip: single-member .gz files are inflated on the device (gs_inflate.hip); members it does not take or that fail their trailer check are
 // collected in `redo` (file indices) with zero records, for the caller to run through the host decoders
 static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *const *paths, uint64_t n_files, int block_mode, uint32_t pio, uint32_t n_threads,
                              void *sig_out, uint64_t *n_records_out, uint64_t *n_symbols_out, double *stats_out, bool dev_gzip, std::vector<uint64_t> *redo,
                              const uint64_t *out_index /* row of file f in the outputs; NULL: f */, int lookahead /* groups read ahead; 0: default */,
                              GzDeal *deal /* optional */, bool from_back, uint64_t n_free /* leading files of the list that need no claim */,
-                             gs::FracFiles *frac = nullptr /* block_mode 3 */)
+                             gs::FracFiles *frac = nullptr /* block_mode 3 */,
+                             uint64_t *n_dev_inflated = nullptr /* optional: files whose members the device kernel inflated, all of them good */)
 {
     int rc = gs_check_params(p);
     if (rc) return rc;
@@ -588,14 +566,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
         uint64_t f1 = std::min<uint64_t>(n_files, f0 + pio);
         if (deal) {                                                // take what is left of the .gz files for this group; a short group is the last one
             const uint64_t cnt = f1 - std::max(f0, std::min(n_free, f1));
-            std::lock_guard<std::mutex> lk(deal->m);
-            const uint64_t avail = deal->n_gz - deal->front - deal->back;
-            uint64_t take = std::min(cnt, avail);
-            if (from_back) {
-                const double k = deal->device_share(avail);
-                take = k < 128 ? 0 : std::min<uint64_t>(take, (uint64_t)k);          // a launch costs the same ~0.4 s for 100 members as for 1000
-            }
-            (from_back ? deal->back : deal->front) += take;
+            const uint64_t take = deal->claim(from_back, cnt);
             claimed_gz[g] = take;
             if (take < cnt) { f1 -= cnt - take; n_groups_eff = std::min<uint64_t>(n_groups_eff, f1 > f0 ? g + 1 : g); }
         }
@@ -699,6 +670,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
     gs::DevBuf dtext[2], dcomp[2], dout, drs, drl, dgo, dsig;
     std::vector<uint8_t> rows_tmp;
     double read_s = 0, copy_wait_s = 0, dev_s = 0;
+    uint64_t dev_inflated = 0;               // files the device kernel inflated, every member good (counted at the device stage)
     double dsub[4] = {0, 0, 0, 0};           // GS_INGEST_TIMES: inside the device stage - wait for the inflate / crc / record scan / pack + sketch + results
     // per staged group: text bytes (H2D part, then the device-inflated texts from gbase on), record ranges per file, then flattened
     struct Staged { uint64_t bytes = 0, gbase = 0; std::vector<std::vector<uint64_t>> fsb, fse; std::vector<uint64_t> sb, se, frec; } staged[2];
@@ -794,7 +766,8 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
         if (dev_ctot[g]) {
             if ((rc2 = dcomp[b].ensure(dev_ctot[g] + 64))) return rc2;
             // in pieces: one multi-GB copy command holds the copy engine while the OTHER pipeline's 300 MB text copies queue behind it
-            static const uint64_t piece = [] { const char *e = getenv("GS_COPY_CHUNK_MB"); return (uint64_t)std::max(1, e ? atoi(e) : 64) << 20; }();
+            const char *e = getenv("GS_COPY_CHUNK_MB");
+            const uint64_t piece = (uint64_t)std::max(1, e ? atoi(e) : 64) << 20;
             for (uint64_t o = 0; o < dev_ctot[g]; o += piece)
                 GS_HIP_CHECK(hipMemcpyAsync((uint8_t *)dcomp[b].p + o, (const uint8_t *)cpin[sl] + o, std::min<uint64_t>(piece, dev_ctot[g] - o), hipMemcpyHostToDevice, copy_stream));
         }
@@ -883,6 +856,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
                 if (!fb.gz_dev) continue;
                 files.push_back(f); foff.push_back(S.gbase + fb.g_off); flen.push_back(bad[f] ? 0 : fb.g_cap);
                 if (bad[f] && redo) redo->push_back(f0 + f);
+                if (!bad[f] && !fb.blocks.empty()) dev_inflated++;          // (a bgzip file of empty text has no member with data: nothing ran)
             }
             std::vector<std::vector<uint64_t>> gsb, gse;
             if ((rc2 = gs::fasta_scan_dev(c, dtext[b].p, foff.data(), flen.data(), (uint32_t)files.size(), gsb, gse))) return rc2;
@@ -954,7 +928,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
             if (n_symbols_out) n_symbols_out[row] = sym;
         }
         dev_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (deal) { std::lock_guard<std::mutex> lk(deal->m); (from_back ? deal->done_back : deal->done_front) += claimed_gz[g]; }
+        if (deal) deal->finished(from_back, claimed_gz[g]);
         return GS_OK;
     };
     double tsec[5] = {0, 0, 0, 0, 0};      // GS_INGEST_TIMES=1: wall seconds in stage / inflate launch / start_group / device stage / cleanup
@@ -977,6 +951,7 @@ static int sketch_files_impl(gs_ctx *c, const gs_sketch_params *p, const char *c
                 (unsigned long long)n_groups_eff, tsec[0], tsec[1], tsec[2], tsec[3], tsec[4]),
         fprintf(stderr, "[GS_INGEST_TIMES]   device stage: copy wait %.3f s, inflate wait %.3f, crc %.3f, record scan %.3f, pack + sketch + results %.3f\n", copy_wait_s, dsub[0], dsub[1], dsub[2], dsub[3]);
 #undef GS_FILES_FAIL
+    if (n_dev_inflated) *n_dev_inflated = dev_inflated;
     if (stats_out) {
         stats_out[0] = read_s; stats_out[1] = copy_wait_s; stats_out[2] = dev_s;
         stats_out[3] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
@@ -1005,6 +980,7 @@ static int sketch_files_all(gs_ctx *c, const gs_sketch_params *p, const char *co
         n_free = ia.size();
         for (uint64_t f = n_files; f-- > 0;) if (gs::ends_with(paths[f], ".gz")) ib.push_back(f);
         deal.n_gz = ib.size();
+        if (const char *sh = getenv("GS_GZIP_DEAL_SHARE")) deal.fixed_share = std::max(0, atoi(sh));     // measurement aid: the device's share of every claim, whatever the rates
         const char *only = getenv("GS_GZIP_DEVICE_ONLY");                       // measurement aid: 1 = every .gz to the device pipeline, the host pipeline idle
         if (deal.n_gz >= 64 && !(only && atoi(only))) ia.insert(ia.end(), ib.rbegin(), ib.rend());     // a handful of files: all of them to the device
     }
@@ -1028,9 +1004,10 @@ static int sketch_files_all(gs_ctx *c, const gs_sketch_params *p, const char *co
         });
     }
     std::vector<uint64_t> redo;
+    uint64_t dev_inflated = 0;
     // the device pipeline's host side only reads files: a few threads are plenty, the cores belong to the host pipeline's decoders
     int rc = sketch_files_impl(c, p, pb.data(), pb.size(), block_mode, pio, ia.empty() ? n_threads : std::max(2u, std::min(8u, n_threads ? n_threads : 8u)), sig_out, n_records_out,
-                               n_symbols_out, st_b, true, &redo, ib.data(), 1, dealing ? &deal : nullptr, true, 0);
+                               n_symbols_out, st_b, true, &redo, ib.data(), 1, dealing ? &deal : nullptr, true, 0, nullptr, &dev_inflated);
     if (host_pipe.joinable()) host_pipe.join();
     if (rc) return rc;
     if (rc_a) { gs::set_error("%s", err_a.c_str()); return rc_a; }
@@ -1045,8 +1022,7 @@ static int sketch_files_all(gs_ctx *c, const gs_sketch_params *p, const char *co
     if (stats_out) {
         for (int i = 0; i < 3; i++) stats_out[i] = st_a[i] + st_b[i];
         stats_out[3] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count();
-        const uint64_t dev_members = dealing ? deal.back : ib.size();
-        stats_out[4] = (double)(dev_members - std::min<uint64_t>(dev_members, redo.size()));      // .gz members inflated by the device kernel
+        stats_out[4] = (double)dev_inflated;               // .gz files the device kernel inflated (not: spilled to its host decoders, handed back, refused by the host stage)
         stats_out[5] = (double)redo.size();                // members it handed back to the host decoders (multi-member, trailer / CRC mismatch, no room)
     }
     return GS_OK;

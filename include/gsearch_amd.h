@@ -146,8 +146,9 @@ int  gs_list_fasta_files(const char *dir, int data_t, char *paths_buf, uint64_t 
 int  gs_sketch_files(gs_ctx *, const gs_sketch_params *, const char *const *paths, uint64_t n_files, int block_mode, uint32_t pio,
                      uint32_t n_threads, void *sig_out, uint64_t *n_records_out, uint64_t *n_symbols_out, double *stats_out);
 /* the same call with a SIZED statistics array: the first min(stats_cap, GS_SKETCH_FILES_STATS) entries of {the four above, .gz members inflated by
- * the device kernel, members the device path handed back to the host decoders (multi-member files, a trailer / CRC-32 that does not check, no room)}
- * are written - a later library may know more entries, a caller never receives more than it made room for. */
+ * the device kernel (counted per file: a single-member file, or a bgzip file all of whose members the kernel inflated and found good; not the members
+ * that stayed with the host decoders or were handed back), members the device path handed back to the host decoders (multi-member files, a trailer /
+ * CRC-32 that does not check, no room)} are written - a later library may know more entries, a caller never receives more than it made room for. */
 enum { GS_SKETCH_FILES_STATS = 6 };
 int  gs_sketch_files_ex(gs_ctx *, const gs_sketch_params *, const char *const *paths, uint64_t n_files, int block_mode, uint32_t pio,
                         uint32_t n_threads, void *sig_out, uint64_t *n_records_out, uint64_t *n_symbols_out, double *stats_out, uint32_t stats_cap);

@@ -126,7 +126,9 @@ def test_inflate_reports_damage(gpu_ctx, monkeypatch, window):
 def test_sketch_files_device_gzip_equals_host_gzip(gpu_ctx, tmp_path, monkeypatch, data, block):
     """.gz files through gs_sketch_files: members inflated on the device (records found by the device scan) must give the signatures,
     record counts and symbol counts of the host decoders (GS_GZIP_DEVICE=0) - multi-record files, CRLF, a `capsid` header, leading junk
-    lines, no final newline, a named member, and a two-member file that the device path hands back to the host"""
+    lines, no final newline, a named member, and a two-member file that the device path hands back to the host. 83 files are dealt (64 or more .gz
+    files), but under the rule's priors the device side declines so short a list (test_gzdeal_cpu.py): the runs without GS_GZIP_DEAL_SHARE go through the
+    host decoders of the second context, the run with it has the device inflate its share"""
     import gsearch_amd as G
     rng = np.random.default_rng(31)
     aa = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", np.uint8)
@@ -144,7 +146,7 @@ def test_sketch_files_device_gzip_equals_host_gzip(gpu_ctx, tmp_path, monkeypatc
 
     ext = ".fna.gz" if data == "dna" else ".faa.gz"
     files = []
-    for i in range(83):              # >= 64 .gz files: dealt between the host pipeline and the device pipeline
+    for i in range(83):              # >= 64 .gz files: the dealt path; who inflates them is settled below
         recs = [(b"r%d_%d some text" % (i, j), seq(int(rng.integers(200, 40000)))) for j in range(1 + i % 5)]
         if i % 7 == 3:
             recs.insert(1, (b"x phage capsid protein", seq(900)))
@@ -168,11 +170,19 @@ def test_sketch_files_device_gzip_equals_host_gzip(gpu_ctx, tmp_path, monkeypatc
     monkeypatch.setenv("GS_GZIP_DEVICE", "0")
     sig0, nrec0, nsym0, _ = sk.sketch_files(paths, block=block, pio=16, threads=4)
     monkeypatch.setenv("GS_GZIP_DEVICE", "1")
-    sig1, nrec1, nsym1, _ = sk.sketch_files(paths, block=block, pio=16, threads=4)
-    sig2, nrec2, nsym2, _ = sk.sketch_files(paths, block=block, pio=0, threads=4)      # one big device group
+    monkeypatch.delenv("GS_GZIP_DEAL_SHARE", raising=False)
+    sig1, nrec1, nsym1, st1 = sk.sketch_files(paths, block=block, pio=16, threads=4)
+    sig2, nrec2, nsym2, st2 = sk.sketch_files(paths, block=block, pio=0, threads=4)      # one big device group
     assert list(nrec0) == list(nrec1) == list(nrec2) and nrec0[7] == 0 and sum(nrec0) > 60
     assert list(nsym0) == list(nsym1) == list(nsym2)
     assert np.array_equal(_bits(sig0), _bits(sig1)) and np.array_equal(_bits(sig0), _bits(sig2))
+    assert st1["gz_members_inflated_on_device"] == 0 and st2["gz_members_inflated_on_device"] == 0, (st1, st2)
+    # the device side offered 128 members at every claim: groups of 2, so that the host side's look-ahead (12 groups) leaves it most of the list
+    # whichever side claims first
+    monkeypatch.setenv("GS_GZIP_DEAL_SHARE", "128")
+    sig3, nrec3, nsym3, st3 = sk.sketch_files(paths, block=block, pio=2, threads=4)
+    assert 0 < st3["gz_members_inflated_on_device"] < len(paths), st3
+    assert list(nrec0) == list(nrec3) and list(nsym0) == list(nsym3) and np.array_equal(_bits(sig0), _bits(sig3))
 
 
 def _bits(a):

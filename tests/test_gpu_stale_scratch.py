@@ -563,6 +563,27 @@ def _(wd):
     return run, (ref, nrec, nsym)
 
 
+# both pipelines of gs_sketch_files at work, each on its own context (test_gpu_ingest_deal.py test_both_pipelines_run_groups_until_they_meet at its
+# smallest shape): the .gz files dealt between the host decoders and the device inflater, the device side offered 128 members at every claim
+@case("files", "sketch_files_dealt_between_both_pipelines", env={"GS_GZIP_DEVICE": "1", "GS_GZIP_DEAL_SHARE": "128"})
+def _(wd):
+    import gsearch_amd as G
+    import ingest_deal_cases as D
+    sub = wd / "dealt"
+    sub.mkdir()
+    corpus = D.Corpus(sub, D.N_DEALT)
+    order = corpus.dealt(D.N_DEALT)
+    paths = corpus.paths(order)
+    ref = D.Reference(corpus.entries).rows(order, False)
+
+    def run(ctx, poke):
+        sk = G.OptDensHashSketch.new(G.SeqSketcherParams(D.K, D.M, D.ALGO), ctx)
+        sig, nr, ns, st = sk.sketch_files(paths, pio=D.P, threads=4)
+        assert 0 < st["gz_members_inflated_on_device"] < D.N_DEALT, st
+        return sig, np.asarray(nr, np.uint64), np.asarray(ns, np.uint64)
+    return run, ref
+
+
 @case("files", "gunzip_batch")
 def _(wd):
     import gsearch_amd as G
