@@ -197,6 +197,10 @@ SYMBOLS = {
     "gs_hmm_search_forward_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_hmm_search_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_hmm_forward_evalue": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_double]),
+    "gs_hmm_search_msv_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "gs_hmm_search_msv": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "gs_hmm_search_filtered_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_search_filtered": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "gs_hmm_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     "gs_hmm_trace_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     # orfs (SPEC 14)

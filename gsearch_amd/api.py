@@ -961,7 +961,8 @@ class HmmDb:
         self.lam = np.array([i["lam"] if i["lam"] is not None else np.nan for i in self.info])
         self.ga_units = [i["ga_units"] for i in self.info]
         # STATS LOCAL FORWARD tau / lambda of every profile (nan without the line), through gs_hmm_parse_stats_mem
-        fstats = []
+        # and STATS LOCAL MSV mu / lambda (SPEC 13.3), from the same call
+        fstats, mstats = [], []
         for t in file_texts:
             n_models = C.c_uint32()
             buf = np.frombuffer(t, dtype=np.uint8)
@@ -969,9 +970,12 @@ class HmmDb:
             for k in range(n_models.value):
                 st, has = hmm_parse_stats(t, k)
                 fstats.append((st[4], st[5]) if has & 4 else (np.nan, np.nan))
+                mstats.append((st[0], st[1]) if has & 1 else (np.nan, np.nan))
         assert len(fstats) == len(self.info)
         self.tau = np.array([a for a, _ in fstats])
         self.lam_fwd = np.array([b for _, b in fstats])
+        self.mu_msv = np.array([a for a, _ in mstats])
+        self.lam_msv = np.array([b for _, b in mstats])
 
     def __len__(self):
         return len(self.info)
@@ -1044,6 +1048,63 @@ class HmmDb:
     def search_forward_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, vit_floor_dev, vit_out_dev, fwd_out_dev):
         """all device memory; vit_floor_dev None: every pair, vit_out_dev None: the Viterbi matrix is not wanted"""
         check(self.ctx.L.gs_hmm_search_forward_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), vit_floor_dev, vit_out_dev, fwd_out_dev))
+
+    def msv_floor(self, filter_p=0.02):
+        """int32 [n_prof]: per profile the MSV score in units below which Viterbi is not run (SPEC 13.3) - the score whose Gumbel tail mass under the
+        profile's STATS LOCAL MSV line is filter_p (HMMER's F1 = 0.02); a profile without that line: INT32_MIN + 1, every pair that has an MSV score"""
+        return np.array([hmm_viterbi_floor(m, l, filter_p) if not np.isnan(m) else _lib.HMM_FLOOR_ALL for m, l in zip(self.mu_msv, self.lam_msv)], np.int32)
+
+    def _msv_floor(self, msv_p, msv_floor):
+        if msv_floor is not None:
+            fl = np.ascontiguousarray(msv_floor, dtype=np.int32)
+            if fl.shape != (len(self),):
+                raise ValueError("msv_floor: one int32 per profile")
+            return fl
+        return None if msv_p is None else self.msv_floor(msv_p)
+
+    def search_msv_packed(self, aa, rec_start, rec_len):
+        """residues as filter_aa_records() returns them -> int32 [n_rec, n_prof] MSV raw scores (SPEC 13.3; HMM_NO_SCORE for an empty record)"""
+        aa = np.ascontiguousarray(aa, dtype=np.uint8)
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        out = np.zeros((len(rs), len(self)), np.int32)
+        check(self.ctx.L.gs_hmm_search_msv(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
+                                           _p(out) if out.size else None))
+        return out
+
+    def search_msv(self, records):
+        """records as search() takes them -> int32 [n_rec, n_prof] MSV raw scores"""
+        return self.search_msv_packed(*filter_aa_records([bytes(r) for r in records]))
+
+    def search_msv_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, msv_out_dev):
+        check(self.ctx.L.gs_hmm_search_msv_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), msv_out_dev))
+
+    def search_filtered_packed(self, aa, rec_start, rec_len, msv_p=0.02, msv_floor=None, forward=False, filter_p=1e-3, floor=None):
+        """residues as filter_aa_records() returns them -> (msv, vit) or, forward=True, (msv, vit, fwd), int32 [n_rec, n_prof] (SPEC 13.3): the MSV
+        score of every pair, what search_packed() returns for the pairs whose MSV score reaches the profile's MSV floor (HMM_NO_SCORE for the others),
+        and the Forward score behind that Viterbi matrix as search_forward_packed() computes it"""
+        aa = np.ascontiguousarray(aa, dtype=np.uint8)
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        mfl = self._msv_floor(msv_p, msv_floor)
+        fl = self._floor(filter_p, floor) if forward else None
+        msv, vit = np.zeros((len(rs), len(self)), np.int32), np.zeros((len(rs), len(self)), np.int32)
+        fwd = np.zeros((len(rs), len(self)), np.int32) if forward else None
+        check(self.ctx.L.gs_hmm_search_filtered(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None,
+                                                len(rs), _p(mfl) if mfl is not None else None, _p(fl) if fl is not None else None, _p(msv) if msv.size else None,
+                                                _p(vit) if vit.size else None, _p(fwd) if forward and fwd.size else None))
+        return (msv, vit, fwd) if forward else (msv, vit)
+
+    def search_filtered(self, records, msv_p=0.02, msv_floor=None, forward=False, filter_p=1e-3, floor=None):
+        """records as search() takes them -> (msv, vit[, fwd]). Viterbi runs for the pairs with msv >= the profile's MSV floor: `msv_floor` (int32
+        [n_prof], units) when given, else msv_floor(msv_p); msv_p=None: every pair that has an MSV score. forward, filter_p, floor: as search_forward()"""
+        return self.search_filtered_packed(*filter_aa_records([bytes(r) for r in records]), msv_p=msv_p, msv_floor=msv_floor, forward=forward, filter_p=filter_p,
+                                           floor=floor)
+
+    def search_filtered_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, msv_floor_dev, vit_floor_dev, msv_out_dev, vit_out_dev, fwd_out_dev):
+        """all device memory; a floor None: every pair, msv_out_dev None: the MSV matrix is not wanted, fwd_out_dev None: no Forward pass"""
+        check(self.ctx.L.gs_hmm_search_filtered_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), msv_floor_dev, vit_floor_dev, msv_out_dev,
+                                                    vit_out_dev, fwd_out_dev))
 
     def trace_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_dom=8, max_block_cells=0):
         """SPEC 13.2: the domains of the Viterbi path of the pairs (pair_rec[j], pair_prof[j]), traced back on the device -> (int32 raw [n_pairs] as
@@ -1134,7 +1195,13 @@ def _as_hmm_db(hmm, ctx):
     return hmm if isinstance(hmm, HmmDb) else HmmDb(hmm, ctx)
 
 
-def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None, translate=False, min_aa=_lib.ORF_MIN_AA, table=11):
+def _check_prefilter(prefilter):
+    if prefilter is not None and prefilter != "msv":
+        raise ValueError("prefilter: None or 'msv'")
+
+
+def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None, translate=False, min_aa=_lib.ORF_MIN_AA, table=11, prefilter=None,
+              msv_p=0.02):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
     `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
     `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
@@ -1152,9 +1219,14 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     translate="genes" (SPEC 15): the targets are instead the genes the self-trained caller of gene_call() chooses in that file taken as one genome, called
     on the device and searched there; names, Z and formats follow in the same way. A file too small to train has no targets. Unlike translate=True, which drops and counts an ORF longer than
     the search takes (the smallest of the HMM_*MAX_L limits of the programs the call runs), a called gene that long raises ValueError and ends the call: a
-    gene set with one silently left out would no longer be the genome's."""
+    gene set with one silently left out would no longer be the genome's.
+    prefilter="msv" (SPEC 13.3): the MSV score of every pair runs first and Viterbi (and Forward behind it) only for the pairs at or above the MSV floor of
+    msv_p (HMMER's F1 = 0.02; None: every pair) - in all three target forms and with both scores. The returned matrix holds HMM_NO_SCORE for the pairs the
+    filter left out, the table has rows only for pairs that passed, Z stays the number of records. A pair whose gapped alignment is good and whose
+    ungapped diagonals are weak is lost: the filter's stated cost. prefilter=None: no prefilter."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
+    _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
     fwd = score == "forward"
     dev = None
@@ -1162,14 +1234,17 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
         dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd, domains is not None), table)
         try:
             ids = dev.names()
-            scores = dev.search(db, fwd, filter_p)
+            scores = dev.search(db, fwd, filter_p, prefilter is not None, msv_p)
         except Exception:
             dev.close()
             raise
     else:
         ids, seqs = _faa_records(faa)
         aa, rs, rl = filter_aa_records([bytes(q) for q in seqs])
-        scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
+        if prefilter is not None:
+            scores = db.search_filtered_packed(aa, rs, rl, msv_p=msv_p, forward=fwd, filter_p=filter_p)[2 if fwd else 1]
+        else:
+            scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
     Z = len(ids)
     out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga\n"]
     listed = []                                                          # the (record, profile) pairs of the table, in its order
@@ -1215,7 +1290,8 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     return ids, scores, table, dom_table
 
 
-def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein", translate=False, min_aa=_lib.ORF_MIN_AA, table=11):
+def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein", translate=False, min_aa=_lib.ORF_MIN_AA, table=11,
+                    prefilter=None, msv_p=0.02):
     """One genome per protein FASTA file: per genome the residues of its best protein for every profile that has a hit at the cutoff, in profile
     order - the records an AA sketcher takes for `tohnsw` / `request` at the universal-gene level. -> (list of lists of bytes, uint32 [n_genomes, n_prof]
     record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing). score="forward": the best hits are those of the Forward matrix
@@ -1228,20 +1304,26 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     region="aligned" trims that. The ORF set is not a proteome and is not meant for the AA sketchers as a whole.
     translate="genes" (SPEC 15): the candidates are the genes of gene_call(), every file one self-trained genome; the record numbers are gene numbers
     inside the genome and the coordinates are the gene's, from its start codon through its stop codon. A called gene longer than the search takes raises
-    ValueError and ends the call (translate=True drops and counts such an ORF; see hmmsearch)."""
+    ValueError and ends the call (translate=True drops and counts such an ORF; see hmmsearch).
+    prefilter="msv" (SPEC 13.3): the best hits are taken among the pairs at or above the MSV floor of msv_p, as hmmsearch(prefilter="msv") scores them."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     if region not in ("protein", "aligned"):
         raise ValueError("region: 'protein' or 'aligned'")
+    _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
     if translate:
-        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate)
+        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate, prefilter is not None,
+                                           msv_p)
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
         goff.append(len(seqs))
     aa, rs, rl = filter_aa_records([bytes(s) for s in seqs])
-    scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if score == "forward" else db.search_packed(aa, rs, rl)
+    if prefilter is not None:
+        scores = db.search_filtered_packed(aa, rs, rl, msv_p=msv_p, forward=score == "forward", filter_p=filter_p)[2 if score == "forward" else 1]
+    else:
+        scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if score == "forward" else db.search_packed(aa, rs, rl)
     rec, _ = db.best_hits(scores, np.array(goff, np.uint64), cutoff)
     span = {}
     if region == "aligned" and rec.size:
@@ -1438,12 +1520,22 @@ class _DevOrfs:
             out.append(_orf_name(self.contig_ids[c], b, e, s))
         return out
 
-    def search_dev(self, db, fwd, filter_p):
-        """device int32 [n, n_prof] scores of the ORFs (Forward behind the Viterbi floor when fwd); the caller frees through close()"""
+    def search_dev(self, db, fwd, filter_p, prefilter=False, msv_p=0.02):
+        """device int32 [n, n_prof] scores of the ORFs (Forward behind the Viterbi floor when fwd; behind the MSV floor of msv_p when prefilter, SPEC
+        13.3); the caller frees through close()"""
         d_score = self._new(4 * self.n * len(db))
         if self.n == 0:
             return d_score
-        if fwd:
+        if prefilter:
+            mfl, fl = db._msv_floor(msv_p, None), (db._floor(filter_p, None) if fwd else None)
+            d_mfl, d_fl = (self._up(mfl) if mfl is not None else None), (self._up(fl) if fl is not None else None)
+            d_vit = self._new(4 * self.n * len(db)) if fwd else d_score
+            db.search_filtered_dev(self.d_aa, self.d_as, self.d_al, self.n, d_mfl, d_fl, None, d_vit, d_score if fwd else None)
+            self.ctx.sync()
+            for ptr in [d_mfl, d_fl] + ([d_vit] if fwd else []):
+                if ptr is not None:
+                    self._free(ptr)
+        elif fwd:
             fl = db._floor(filter_p, None)
             d_fl = self._up(fl) if fl is not None else None
             db.search_forward_dev(self.d_aa, self.d_as, self.d_al, self.n, d_fl, None, d_score)
@@ -1454,8 +1546,8 @@ class _DevOrfs:
             db.search_dev(self.d_aa, self.d_as, self.d_al, self.n, d_score)
         return d_score
 
-    def search(self, db, fwd, filter_p):
-        d_score = self.search_dev(db, fwd, filter_p)
+    def search(self, db, fwd, filter_p, prefilter=False, msv_p=0.02):
+        d_score = self.search_dev(db, fwd, filter_p, prefilter, msv_p)
         scores = self.ctx.download(d_score, (self.n, len(db)), np.int32)
         self._free(d_score)
         return scores
@@ -1488,14 +1580,14 @@ class _DevOrfs:
         return self.ctx.download(self.d_aa + int(self.aa_start[j]) + a, (b - a,), np.uint8).tobytes()
 
 
-def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True):
+def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02):
     ctx = db.ctx
     dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd, aligned), table)
     try:
         ng, npf = len(fna_files), len(db)
         rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
         if ng and npf and dev.n:
-            d_score = dev.search_dev(db, fwd, filter_p)
+            d_score = dev.search_dev(db, fwd, filter_p, prefilter, msv_p)
             d_goff, d_thr = dev._up(dev.genome_orf_off), dev._up(db.thresholds(cutoff))
             d_rec, d_sc = dev._new(4 * ng * npf), dev._new(4 * ng * npf)
             db.best_hits_dev(d_score, dev.n, d_goff, ng, d_thr, d_rec, d_sc)

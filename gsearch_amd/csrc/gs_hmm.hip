@@ -458,6 +458,138 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_trace(const int32_t *__restri
     }
 }
 
+// Viterbi score of the records sel[p][0 .. sel_cnt[p]) of each profile of plist[] (SPEC 13.3: the pairs that passed the MSV floor); the other words of
+// `score` keep what k_hmm_fill wrote
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_viterbi_sel(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const uint32_t *__restrict__ plist,
+                                                               const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                               const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sel_cnt, uint32_t n_rec, uint32_t n_prof,
+                                                               int32_t *__restrict__ score)
+{
+    const uint32_t p = plist[blockIdx.y];
+    const uint32_t cnt = min(sel_cnt[p], n_rec);
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= cnt) return;
+    const HmmLane<Q> ln = hmm_stage<Q, false>(tables, desc[p], nullptr);
+    const uint32_t *list = sel + (uint64_t)p * n_rec;
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < cnt; j += gridDim.x * HMM_WAVES) {
+        const uint32_t r = list[j];
+        const int32_t raw = hmm_rows<Q, HMM_VIT>(ln, aa + rec_start[r], (uint32_t)rec_len[r], nullptr, nullptr);
+        if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
+    }
+}
+
+// ---- MSV (SPEC 13.3): ungapped diagonals, any number of them ----------------------------------------------------------------------------------
+// The model of SPEC 13 without I and D and with tMM = 0, so a row is M[k] = max(NEG, msc[k] + max(M'[k-1], B + tBM)) and E = max_k M[k]. The launch
+// geometry, the lane layout and the residue loads are k_hmm_viterbi's; the row loop is its own, because nothing of hmm_rows but the specials is left:
+// no give, no I, no D scan, no transition rows. Only the 20 match rows of the profile's table go to LDS (5 120 Q bytes against 7 168 Q), so two
+// workgroups of class 12 and 16 fit a CU where one Viterbi workgroup does, four of class 6 and 8 where three and two do.
+// Per row a node costs a max, an add and half a max3 of the fold into e; M of a lane's last node moves up one lane; E is hmm_wave_join<HMM_VIT>, and
+// B of the next row waits for it: that chain, not the node work, is what a lone wavefront feels.
+//   No clamp: the max(NEG, .) of SPEC 13.3 never binds. B >= i tloop + tmove with i tloop >= -8 864 (tloop is 4 432 / L rounded to a unit, 0 from
+//   L = 8 865 on) and tmove >= -16 810, tBM >= -20 120 for L <= 2^18 and M <= 1 280, so B + tBM > -50 000; every word of a match row is at least
+//   STAR = -2^18, so a cell is above -320 000, far above NEG = -2^29: the integers are the clamped ones.
+//   No nvalid: the staged copy holds HMM_MSV_PAD, not STAR, in the match rows of the padding nodes (they follow node M, so only padding is fed by
+//   padding). A padding cell is PAD + max(cell, entry): at least PAD - 50 000 > INT32_MIN and at most PAD + 6 608 * 2^18 = -415 105 024, below the
+//   -320 000 that E = max over the M >= 1 real nodes is above. So padding never reaches E and the fold needs no select.
+//   Blocks of four: where Q is a multiple of 4 the staged copy does not keep a lane's Q words together. Word q of lane l lies at
+//   (q / 4) 256 + 4 l + q % 4 of its row, so the ds_read_b128 that fetches words 4 b .. 4 b + 3 of every lane reads 1 024 contiguous bytes. With
+//   the lane's words together the lanes of a read are Q words apart, a many-way bank conflict at Q = 8 and Q = 16: the first form of this
+//   kernel ran class 16 at 13 % of its issue ceiling for that reason.
+enum { HMM_MSV_ROWS = 20, HMM_MSV_PAD = INT32_MIN + (1 << 17) };
+__host__ __device__ constexpr int hmm_msv_block(int Q) { return Q % 4 == 0 ? 4 : Q; }          // words of a lane that stay together in the staged copy
+// where word q of a lane lies from the lane's first word of a row
+__host__ __device__ constexpr int hmm_msv_at(int Q, int q) { return (q / hmm_msv_block(Q)) * 64 * hmm_msv_block(Q) + q % hmm_msv_block(Q); }
+static_assert((int64_t)HMM_MSV_PAD + 6608ll * GS_HMM_MAX_L < -320000 && (int64_t)HMM_MSV_PAD - 50000 > INT32_MIN, "a padding cell stays below every E and inside int32");
+template <int Q> struct HmmMsvLane {
+    const int32_t *ms;                                      // the lane's first word of match row 0, in LDS: word q at ms[hmm_msv_at(Q, q)]
+    int32_t tbm;
+    int lane, wave;
+};
+template <int Q>
+__device__ __forceinline__ HmmMsvLane<Q> hmm_msv_stage(const int32_t *tables, const HmmDesc d)
+{
+    extern __shared__ int4 hmm_msv_lds[];                     // (int4: the blocks of four are read as ds_read_b128, which wants their alignment known)
+    int32_t *hmm_lds = (int32_t *)hmm_msv_lds;
+    constexpr int MP = 64 * Q;
+    for (int i = (int)threadIdx.x; i < HMM_MSV_ROWS * MP; i += HMM_BLOCK) {
+        const int j = i % MP;                                 // the word of node j + 1, lane j / Q
+        hmm_lds[i - j + (j / Q) * hmm_msv_block(Q) + hmm_msv_at(Q, j % Q)] = (uint32_t)j < d.M ? tables[d.off + i] : (int32_t)HMM_MSV_PAD;
+    }
+    __syncthreads();
+    HmmMsvLane<Q> ln;
+    ln.lane = (int)threadIdx.x & 63; ln.wave = (int)threadIdx.x >> 6;
+    ln.tbm = d.tbm;
+    ln.ms = hmm_lds + ln.lane * hmm_msv_block(Q);
+    return ln;
+}
+
+// The MSV rows of one record against the staged match rows: the raw score in every lane, GS_HMM_NO_SCORE for an empty record or a byte that is no residue
+template <int Q>
+__device__ __forceinline__ int32_t hmm_msv_rows(const HmmMsvLane<Q> ln, const uint8_t *x, uint32_t L)
+{
+    constexpr int MP = 64 * Q;
+    const int lane = ln.lane;
+    if (L == 0) return GS_HMM_NO_SCORE;
+    const HmmSpecials sp = hmm_specials(L);
+    int32_t Mv[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) Mv[q] = GS_HMM_NEG;
+    int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
+    bool bad = false;
+    int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
+    for (uint32_t i0 = 0; i0 < L; i0 += 64) {
+        const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;     // the next 64 residues are on their way while these run
+        bad |= cur < 0;
+        const int res = max(cur, 0);                              // a byte that is no residue reads row 0: inside the table, and the pair gets no score
+        const int cnt = (int)min(64u, L - i0);
+        for (int t = 0; t < cnt; t++) {
+            const int32_t *ms = ln.ms + __builtin_amdgcn_readlane(res, t) * MP;
+            const int32_t entry = B + ln.tbm;
+            int32_t sc[Q];                                        // the row's match scores of the lane's nodes
+            if constexpr (Q % 4 == 0) {
+#pragma unroll
+                for (int b = 0; b < Q / 4; b++) {
+                    const int4 v = ((const int4 *)ms)[b * 64];
+                    sc[4 * b] = v.x; sc[4 * b + 1] = v.y; sc[4 * b + 2] = v.z; sc[4 * b + 3] = v.w;
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < Q; q++) sc[q] = ms[q];
+            }
+            int32_t up = __shfl_up(Mv[Q - 1], 1);
+            if (lane == 0) up = GS_HMM_NEG;                       // node 0 has no states
+#pragma unroll
+            for (int q = Q - 1; q >= 1; q--) Mv[q] = sc[q] + max(Mv[q - 1], entry);        // downwards: Mv[q - 1] is still the row before
+            Mv[0] = sc[0] + max(up, entry);
+            int32_t e = Mv[0];
+#pragma unroll
+            for (int q = 1; q < Q; q++) e = max(e, Mv[q]);            // padding cells are below every real one (above)
+            const int32_t E = hmm_wave_join<HMM_VIT>(e, nullptr);
+            N += sp.tloop;
+            J = max(max(J + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
+            C = max(max(C + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
+            B = max(N, J) + sp.tmove;
+        }
+        cur = nxt;
+    }
+    return __any(bad) ? GS_HMM_NO_SCORE : C + sp.tmove - sp.null;
+}
+
+// MSV score of every record against the profiles plist[] of one class; the arguments of k_hmm_viterbi
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_msv(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const uint32_t *__restrict__ plist,
+                                                       const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                       const uint32_t *__restrict__ order, uint32_t n_rec, uint32_t n_prof, int32_t *__restrict__ score)
+{
+    const uint32_t p = plist[blockIdx.y];
+    const HmmMsvLane<Q> ln = hmm_msv_stage<Q>(tables, desc[p]);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < n_rec; j += gridDim.x * HMM_WAVES) {
+        const uint32_t r = order[j];
+        const int32_t raw = hmm_msv_rows<Q>(ln, aa + rec_start[r], (uint32_t)rec_len[r]);
+        if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
+    }
+}
+
 // one thread per (genome, profile): the records of the genome in order, so the first of equal scores stays
 __global__ __launch_bounds__(256) void k_hmm_best(const int32_t *__restrict__ score, const uint64_t *__restrict__ goff, uint64_t n_genomes, uint32_t n_prof,
                                                   const int32_t *__restrict__ thr, uint32_t *__restrict__ best_rec, int32_t *__restrict__ best_score)
@@ -584,15 +716,21 @@ __global__ __launch_bounds__(256) void k_hmm_trace_fill(uint64_t n_pairs, uint64
     if (i < n_dom_words) dom[i] = 0;
 }
 
-// the three instances of a class, from the one class list
-struct HmmKernels { decltype(&k_hmm_viterbi<1>) vit; decltype(&k_hmm_forward<1>) fwd; decltype(&k_hmm_trace<1>) trace; };
+// the five instances of a class, from the one class list
+struct HmmKernels {
+    decltype(&k_hmm_viterbi<1>) vit; decltype(&k_hmm_forward<1>) fwd; decltype(&k_hmm_trace<1>) trace; decltype(&k_hmm_msv<1>) msv; decltype(&k_hmm_viterbi_sel<1>) vit_sel;
+};
 template <size_t... I> static const HmmKernels &hmm_kernels(int cls, std::index_sequence<I...>)
 {
-    static const HmmKernels of_class[] = {{k_hmm_viterbi<HMM_CLASS_Q[I]>, k_hmm_forward<HMM_CLASS_Q[I]>, k_hmm_trace<HMM_CLASS_Q[I]>}...};
+    static const HmmKernels of_class[] = {{k_hmm_viterbi<HMM_CLASS_Q[I]>, k_hmm_forward<HMM_CLASS_Q[I]>, k_hmm_trace<HMM_CLASS_Q[I]>, k_hmm_msv<HMM_CLASS_Q[I]>,
+                                           k_hmm_viterbi_sel<HMM_CLASS_Q[I]>}...};
     return of_class[cls];
 }
 static const HmmKernels &hmm_kernels(int cls) { return hmm_kernels(cls, std::make_index_sequence<HMM_CLASSES>()); }
 static size_t hmm_lds_bytes(int cls, HmmProg prog) { return (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + (prog == HMM_FWD ? HMM_LSE_LDS_BYTES : 0); }
+static size_t hmm_msv_lds_bytes(int cls) { return (size_t)HMM_MSV_ROWS * 64 * HMM_CLASS_Q[cls] * 4; }
+// which kernel a (kernel, class) flag of the profile set belongs to: the three programs of hmm_rows, then MSV and Viterbi over a selected list
+enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_KERNEL_KINDS };
 
 }  // namespace gs
 
@@ -603,7 +741,7 @@ struct gs_hmm_db {
     std::vector<uint32_t> plist;                    // profile numbers, class by class
     uint32_t class_start[gs::HMM_CLASSES + 1] = {};
     bool all_ga = true;
-    bool lds_set[gs::HMM_PROGS][gs::HMM_CLASSES] = {};
+    bool lds_set[gs::HMM_KERNEL_KINDS][gs::HMM_CLASSES] = {};
     gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse;
 };
 
@@ -672,8 +810,9 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
 }
 
 // lens: the host copy of rec_len; everything else device memory. Queued on c's stream; the order list lives in its slot until the caller's scope ends.
+// msv: the MSV score (SPEC 13.3) of every pair in the place of its Viterbi score - the same launches with k_hmm_msv and its smaller LDS.
 static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
-                           int32_t *score_dev, PoolBuf &d_order)
+                           int32_t *score_dev, PoolBuf &d_order, bool msv = false)
 {
     const uint32_t np = (uint32_t)db->models.size();
     std::vector<uint32_t> order(n_rec);
@@ -684,9 +823,9 @@ static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, cons
     GS_HIP_CHECK(hipMemcpyAsync(d_order.p, order.data(), 4 * n_rec, hipMemcpyHostToDevice, c->stream));
     const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
     for (int cls = 0; cls < HMM_CLASSES; cls++) {
-        const auto k = hmm_kernels(cls).vit;
-        const size_t lds = hmm_lds_bytes(cls, HMM_VIT);
-        rc = hmm_launch_class(c, db->lds_set[HMM_VIT][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
+        const auto k = msv ? hmm_kernels(cls).msv : hmm_kernels(cls).vit;
+        const size_t lds = msv ? hmm_msv_lds_bytes(cls) : hmm_lds_bytes(cls, HMM_VIT);
+        rc = hmm_launch_class(c, db->lds_set[msv ? HMM_K_MSV : HMM_VIT][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
             k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, aa_dev, rs_dev, rl_dev,
                                                    d_order.as<uint32_t>(), (uint32_t)n_rec, np, score_dev);
         });
@@ -731,38 +870,70 @@ static int hmm_stage_records(gs_ctx *c, const uint8_t *aa, uint64_t n_bytes, con
     return GS_OK;
 }
 
+// One program over the pairs another score selects: out_dev filled with GS_HMM_NO_SCORE, per profile the list of the records whose in_dev reaches
+// floor_dev (nullptr: every pair that has a score there), then prog - HMM_FWD: k_hmm_forward, HMM_VIT: k_hmm_viterbi_sel - over those lists into out_dev.
+// d_order holds the order list of the call. Queued on c's stream.
+static int hmm_selected_pass(gs_ctx *c, gs_hmm_db *db, HmmProg prog, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, uint64_t n_rec,
+                             const int32_t *in_dev, const int32_t *floor_dev, int32_t *out_dev, PoolBuf &d_order, PoolBuf &d_sel, PoolBuf &d_cnt)
+{
+    const uint32_t np = (uint32_t)db->models.size();
+    int rc;
+    if (!d_sel.p && ((rc = d_sel.alloc(4 * n_rec * np)) || (rc = d_cnt.alloc(4 * (size_t)np)))) return rc;
+    const uint64_t n = n_rec * np;
+    GS_REQUIRE(n < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many (record, profile) pairs");
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_fill<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(out_dev, n, GS_HMM_NO_SCORE);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_select<<<np, HMM_SEL_BLOCK, 0, c->stream>>>(in_dev, d_order.as<uint32_t>(), (uint32_t)n_rec, np, floor_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>());
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
+    for (int cls = 0; cls < HMM_CLASSES; cls++) {
+        const uint32_t first_of = db->class_start[cls], n_in = db->class_start[cls + 1] - first_of;
+        if (prog == HMM_FWD) {
+            const auto k = hmm_kernels(cls).fwd;
+            const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+            rc = hmm_launch_class(c, db->lds_set[HMM_FWD][cls], k, first_of, n_in, wg, lds, [&](dim3 grid, uint32_t first) {
+                k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, db->d_lse.as<uint16_t>(), aa_dev,
+                                                       rs_dev, rl_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec, np, out_dev);
+            });
+        } else {
+            const auto k = hmm_kernels(cls).vit_sel;
+            const size_t lds = hmm_lds_bytes(cls, HMM_VIT);
+            rc = hmm_launch_class(c, db->lds_set[HMM_K_VIT_SEL][cls], k, first_of, n_in, wg, lds, [&](dim3 grid, uint32_t first) {
+                k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, aa_dev, rs_dev, rl_dev,
+                                                       d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec, np, out_dev);
+            });
+        }
+        if (rc) return rc;
+    }
+    return GS_OK;
+}
+
 // Viterbi into vit_dev, then Forward into fwd_dev for the pairs at or above floor_dev (nullptr: every pair that has a Viterbi score), GS_HMM_NO_SCORE
 // for the rest. Queued on c's stream; the lists live in their slots until the caller's scope ends.
 static int hmm_forward_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
                             const int32_t *floor_dev, int32_t *vit_dev, int32_t *fwd_dev, PoolBuf &d_order, PoolBuf &d_sel, PoolBuf &d_cnt)
 {
-    const uint32_t np = (uint32_t)db->models.size();
     int rc;
     if ((rc = hmm_search_impl(c, db, aa_dev, rs_dev, rl_dev, lens, n_rec, vit_dev, d_order))) return rc;
-    if ((rc = d_sel.alloc(4 * n_rec * np)) || (rc = d_cnt.alloc(4 * (size_t)np))) return rc;
-    const uint64_t n = n_rec * np;
-    GS_REQUIRE(n < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many (record, profile) pairs");
-    {
-        ProfScope ps(c, FAM_SEARCH);
-        k_hmm_fill<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(fwd_dev, n, GS_HMM_NO_SCORE);
-        GS_HIP_CHECK(hipGetLastError());
-    }
-    {
-        ProfScope ps(c, FAM_SEARCH);
-        k_hmm_select<<<np, HMM_SEL_BLOCK, 0, c->stream>>>(vit_dev, d_order.as<uint32_t>(), (uint32_t)n_rec, np, floor_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>());
-        GS_HIP_CHECK(hipGetLastError());
-    }
-    const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
-    for (int cls = 0; cls < HMM_CLASSES; cls++) {
-        const auto k = hmm_kernels(cls).fwd;
-        const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
-        rc = hmm_launch_class(c, db->lds_set[HMM_FWD][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
-            k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, db->d_lse.as<uint16_t>(), aa_dev,
-                                                   rs_dev, rl_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec, np, fwd_dev);
-        });
-        if (rc) return rc;
-    }
-    return GS_OK;
+    return hmm_selected_pass(c, db, HMM_FWD, aa_dev, rs_dev, rl_dev, n_rec, vit_dev, floor_dev, fwd_dev, d_order, d_sel, d_cnt);
+}
+
+// MSV of every pair into msv_dev, Viterbi into vit_dev for the pairs at or above msv_floor_dev and, with fwd_dev, Forward behind vit_floor_dev as
+// hmm_forward_impl runs it (SPEC 13.3); GS_HMM_NO_SCORE for the rest. The lists of the second selection take the place of the first's: the stream orders them.
+static int hmm_filtered_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
+                             const int32_t *msv_floor_dev, const int32_t *vit_floor_dev, int32_t *msv_dev, int32_t *vit_dev, int32_t *fwd_dev, PoolBuf &d_order,
+                             PoolBuf &d_sel, PoolBuf &d_cnt)
+{
+    int rc;
+    if ((rc = hmm_search_impl(c, db, aa_dev, rs_dev, rl_dev, lens, n_rec, msv_dev, d_order, true))) return rc;
+    if ((rc = hmm_selected_pass(c, db, HMM_VIT, aa_dev, rs_dev, rl_dev, n_rec, msv_dev, msv_floor_dev, vit_dev, d_order, d_sel, d_cnt))) return rc;
+    return fwd_dev ? hmm_selected_pass(c, db, HMM_FWD, aa_dev, rs_dev, rl_dev, n_rec, vit_dev, vit_floor_dev, fwd_dev, d_order, d_sel, d_cnt) : GS_OK;
 }
 
 // ---- trace-back, host side (SPEC 13.2) ----------------------------------------------------------------------------------------------------------
@@ -979,9 +1150,14 @@ int gs_hmm_db_tables(gs_hmm_db *db, uint64_t p, int32_t *tables_out, uint64_t ca
     return GS_OK;
 }
 
-int gs_hmm_search_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int32_t *score_out_dev)
+}  // extern "C"
+
+namespace gs {
+
+// gs_hmm_search_dev / gs_hmm_search, and with msv their MSV twins (SPEC 13.3): the same arguments, refusals and staging
+static int hmm_search_dev_form(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                               int32_t *score_out_dev, bool msv)
 {
-    using namespace gs;
     GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
     if (n_rec == 0) return GS_OK;
     GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && score_out_dev, GS_ERR_INVALID, "null argument");
@@ -991,12 +1167,11 @@ int gs_hmm_search_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uin
     int rc;
     if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_check_lens(lens.data(), n_rec))) return rc;
     PoolBuf d_order(c, SL_HMM_ORDER);
-    return hmm_search_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, score_out_dev, d_order);
+    return hmm_search_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, score_out_dev, d_order, msv);
 }
 
-int gs_hmm_search(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *score_out)
+static int hmm_search_host_form(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *score_out, bool msv)
 {
-    using namespace gs;
     GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
     if (n_rec == 0) return GS_OK;
     GS_REQUIRE(rec_start && rec_len && score_out, GS_ERR_INVALID, "null argument");
@@ -1006,10 +1181,34 @@ int gs_hmm_search(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *r
     GS_CTX_LOCK(c);
     PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_order(c, SL_HMM_ORDER);
     if ((rc = hmm_stage_records(c, aa, hmm_records_end(rec_start, rec_len, n_rec), rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_score.alloc(4 * n_rec * np))) return rc;
-    if ((rc = hmm_search_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, d_score.as<int32_t>(), d_order))) return rc;
+    if ((rc = hmm_search_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, d_score.as<int32_t>(), d_order, msv))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(score_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(stream_wait(c));
     return GS_OK;
+}
+
+}  // namespace gs
+
+extern "C" {
+
+int gs_hmm_search_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int32_t *score_out_dev)
+{
+    return gs::hmm_search_dev_form(c, db, aa_dev, rec_start_dev, rec_len_dev, n_rec, score_out_dev, false);
+}
+
+int gs_hmm_search(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *score_out)
+{
+    return gs::hmm_search_host_form(c, db, aa, rec_start, rec_len, n_rec, score_out, false);
+}
+
+int gs_hmm_search_msv_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int32_t *msv_out_dev)
+{
+    return gs::hmm_search_dev_form(c, db, aa_dev, rec_start_dev, rec_len_dev, n_rec, msv_out_dev, true);
+}
+
+int gs_hmm_search_msv(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *msv_out)
+{
+    return gs::hmm_search_host_form(c, db, aa, rec_start, rec_len, n_rec, msv_out, true);
 }
 
 int gs_hmm_best_hits_dev(gs_ctx *c, gs_hmm_db *db, const int32_t *score_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes,
@@ -1116,6 +1315,65 @@ int gs_hmm_search_forward(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uin
         return rc;
     if (vit_out) GS_HIP_CHECK(hipMemcpyAsync(vit_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+int gs_hmm_search_filtered_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                               const int32_t *msv_floor_dev, const int32_t *vit_floor_dev, int32_t *msv_out_dev, int32_t *vit_out_dev, int32_t *fwd_out_dev)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_rec == 0) return GS_OK;
+    GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && vit_out_dev, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
+    GS_CTX_LOCK(c);
+    std::vector<uint64_t> lens;
+    int rc;
+    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_check_lens(lens.data(), n_rec, fwd_out_dev ? GS_HMM_FWD_MAX_L : GS_HMM_MAX_L))) return rc;
+    PoolBuf d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT), d_msv(c, SL_HMM_MSV);
+    if (!msv_out_dev) {
+        if ((rc = d_msv.alloc(4 * n_rec * db->models.size()))) return rc;
+        msv_out_dev = d_msv.as<int32_t>();
+    }
+    if ((rc = hmm_filtered_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, msv_floor_dev, vit_floor_dev, msv_out_dev, vit_out_dev, fwd_out_dev, d_order,
+                                d_sel, d_cnt)))
+        return rc;
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+int gs_hmm_search_filtered(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const int32_t *msv_floor,
+                           const int32_t *vit_floor, int32_t *msv_out, int32_t *vit_out, int32_t *fwd_out)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_rec == 0) return GS_OK;
+    GS_REQUIRE(rec_start && rec_len && vit_out, GS_ERR_INVALID, "null argument");
+    int rc = hmm_check_lens(rec_len, n_rec, fwd_out ? GS_HMM_FWD_MAX_L : GS_HMM_MAX_L);
+    if (rc) return rc;
+    const uint64_t np = db->models.size();
+    GS_CTX_LOCK(c);
+    PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_fwd(c, SL_HMMB_FWD), d_floor(c, SL_HMMB_FLOOR),
+        d_msv(c, SL_HMMB_MSV), d_msv_floor(c, SL_HMMB_MSV_FLOOR), d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT);
+    if ((rc = hmm_stage_records(c, aa, hmm_records_end(rec_start, rec_len, n_rec), rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_score.alloc(4 * n_rec * np)) ||
+        (rc = d_msv.alloc(4 * n_rec * np)) || (fwd_out && (rc = d_fwd.alloc(4 * n_rec * np))))
+        return rc;
+    if (msv_floor) {
+        if ((rc = d_msv_floor.alloc(4 * np))) return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(d_msv_floor.p, msv_floor, 4 * np, hipMemcpyHostToDevice, c->stream));
+    }
+    if (fwd_out && vit_floor) {
+        if ((rc = d_floor.alloc(4 * np))) return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(d_floor.p, vit_floor, 4 * np, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((rc = hmm_filtered_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, msv_floor ? d_msv_floor.as<int32_t>() : nullptr,
+                                fwd_out && vit_floor ? d_floor.as<int32_t>() : nullptr, d_msv.as<int32_t>(), d_score.as<int32_t>(), fwd_out ? d_fwd.as<int32_t>() : nullptr,
+                                d_order, d_sel, d_cnt)))
+        return rc;
+    if (msv_out) GS_HIP_CHECK(hipMemcpyAsync(msv_out, d_msv.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(vit_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
+    if (fwd_out) GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(stream_wait(c));
     return GS_OK;
 }

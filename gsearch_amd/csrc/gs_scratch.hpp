@@ -77,6 +77,8 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     X(HMM_ORDER) X(HMMB_AA) X(HMMB_REC_START) X(HMMB_REC_LEN) X(HMMB_SCORE)                                                                           \
     /* hmmsearch, Forward: per profile the records at or above its Viterbi floor and their number, the Viterbi matrix nobody asked for, staging */    \
     X(HMM_SEL) X(HMM_SEL_COUNT) X(HMM_VIT) X(HMMB_FWD) X(HMMB_FLOOR)                                                                                  \
+    /* hmmsearch, MSV prefilter: the MSV matrix nobody asked for, staging of the host form's MSV matrix and MSV floors */                               \
+    X(HMM_MSV) X(HMMB_MSV) X(HMMB_MSV_FLOOR)                                                                                                          \
     /* hmmsearch, trace-back: a block's pairs and their profiles' lists, its back-pointers and row specials, staging of the host form */                \
     X(HMMT_PAIRS) X(HMMT_PROFS) X(HMMT_PTR) X(HMMT_ROWS) X(HMMTB_AA) X(HMMTB_REC_START) X(HMMTB_REC_LEN) X(HMMTB_PAIR_PROF) X(HMMTB_RAW)       \
     X(HMMTB_NDOM) X(HMMTB_DOM)                                                                                                                        \

@@ -345,6 +345,25 @@ int gs_hmm_search_forward(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const u
 /* host only, double: E = n_targets * P with P = 1 for bits < tau, exp(-lambda (bits - tau)) otherwise (the exponential tail of STATS LOCAL FORWARD) */
 double gs_hmm_forward_evalue(double bits, double tau, double lambda, double n_targets);
 
+/* MSV prefilter (SPEC 13.3): the model of SPEC 13 without insert and delete states and with m->m taken as 0 - ungapped diagonals, any number of them -
+ * in the same units, all int32. It is neither a lower nor an upper bound of the Viterbi score. HMMER's own order puts it in front of Viterbi: the full
+ * dynamic program runs only for the pairs at or above a per-profile MSV floor, gs_hmm_viterbi_floor(mu, lambda, P) of the STATS LOCAL MSV line with
+ * P = 0.02. A pair whose gapped alignment is good and whose ungapped diagonals are weak is lost: the stated cost of the filter.
+ * msv_out[r * n_prof + p] = the MSV raw score, GS_HMM_NO_SCORE for an empty record or one with a byte that is no residue. Arguments and refusals are
+ * those of gs_hmm_search(_dev). */
+int gs_hmm_search_msv_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                          int32_t *msv_out_dev);
+int gs_hmm_search_msv(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *msv_out);
+/* msv_out (optional) as above; vit_out[r * n_prof + p] = what gs_hmm_search writes for the pairs with msv != GS_HMM_NO_SCORE and msv >= msv_floor[p],
+ * GS_HMM_NO_SCORE for the others; fwd_out (optional, NULL = no Forward pass) = what gs_hmm_search_forward writes behind that Viterbi matrix and
+ * vit_floor. msv_floor, vit_floor: n_prof words each, NULL = every pair that has the score in front (vit_floor is read only with fwd_out). Device form:
+ * all arrays device memory; the lengths are read back once. A record longer than GS_HMM_MAX_L - with fwd_out: than GS_HMM_FWD_MAX_L - or 2^32 records or
+ * more: GS_ERR_UNSUPPORTED before anything is queued, nothing written; a set of another context: GS_ERR_INVALID. */
+int gs_hmm_search_filtered_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                               const int32_t *msv_floor_dev, const int32_t *vit_floor_dev, int32_t *msv_out_dev, int32_t *vit_out_dev, int32_t *fwd_out_dev);
+int gs_hmm_search_filtered(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
+                           const int32_t *msv_floor, const int32_t *vit_floor, int32_t *msv_out, int32_t *vit_out, int32_t *fwd_out);
+
 /* Trace-back (SPEC 13.2): the domains of the Viterbi path of a list of (record, profile) pairs - the segments of the path between a B -> M entry and the
  * M -> E exit that follows it. The dynamic program (with back-pointers) and the walk back both run on the device. A domain is GS_HMM_DOM_WORDS int32:
  * i_from, i_to, k_from, k_to (1-based, inclusive), seg = M[i_to][k_to] - B[i_from - 1], n_match, n_ins, n_del. Pairs in any order, repeats allowed.

@@ -270,6 +270,25 @@ public:
                                     fwd.data()));
         return {std::move(vit), std::move(fwd)};
     }
+    // SPEC 13.3: the MSV raw score of every pair (ungapped diagonals; the prefilter's score)
+    std::vector<int32_t> search_msv(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len) const
+    {
+        std::vector<int32_t> out(rec_start.size() * info_.size());
+        check(gs_hmm_search_msv(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), out.data()));
+        return out;
+    }
+    // SPEC 13.3: MSV of every pair, Viterbi of the pairs whose MSV score reaches msv_floor[p], and - forward = true - Forward behind vit_floor as
+    // search_forward() runs it; GS_HMM_NO_SCORE for the pairs a floor left out. An empty floor vector: every pair that has the score in front
+    struct Filtered { std::vector<int32_t> msv, vit, fwd; };
+    Filtered search_filtered(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len, const std::vector<int32_t> &msv_floor = {},
+                             bool forward = false, const std::vector<int32_t> &vit_floor = {}) const
+    {
+        const size_t n = rec_start.size() * info_.size();
+        Filtered f{std::vector<int32_t>(n), std::vector<int32_t>(n), std::vector<int32_t>(forward ? n : 0)};
+        check(gs_hmm_search_filtered(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), msv_floor.empty() ? nullptr : msv_floor.data(),
+                                     vit_floor.empty() ? nullptr : vit_floor.data(), f.msv.data(), f.vit.data(), forward ? f.fwd.data() : nullptr));
+        return f;
+    }
     // SPEC 13.2: the domains of the Viterbi path of the pairs (pair_rec[j], pair_prof[j]), traced back on the device. raw[j] as search() gives it,
     // n_dom[j] the true number of domains, dom[(j * max_dom + d) * GS_HMM_DOM_WORDS ..] the first max_dom of them in sequence order (zeros behind them)
     struct Trace { std::vector<int32_t> raw; std::vector<uint32_t> n_dom; std::vector<int32_t> dom; };

@@ -19,11 +19,22 @@ composition) against 120 synthetic profiles with the node counts of the bacteria
                 pairs into blocks; the default block size), beside the Viterbi seconds of the same run
   check         the raw of every traced pair against the score matrix, and `check` sampled pairs against the restatement (tests/pyref_hmm_trace.py)
 
+--msv (SPEC 13.3), on the same proteome and profile set:
+  msv           cells/s of the MSV launches alone (gs_hmm_search_msv_dev)
+  passing       the share of the pairs at or above their profile's MSV floor of P = 0.02 (the STATS LOCAL MSV lines of the synthetic profiles are
+                not calibrated: the share is that of this set, not the 2 % of a calibrated one)
+  filtered      seconds of gs_hmm_search_filtered_dev (MSV + selection + Viterbi over the selected lists) beside gs_hmm_search_dev of the same build,
+                the two alternating in one loop: `repeat` timed pairs after a warm-up pair, every time listed, the minimum and the median reported.
+                --parent-s S records beside them the seconds of the parent commit's gs_hmm_search_dev on this input, as the parent's build of this
+                tool reports them (search_s): that kernel is the yardstick
+  check         the Viterbi words of the filtered search against the unfiltered matrix wherever they ran, the selection against the MSV matrix and the
+                floors, and `check` sampled pairs of the MSV matrix against the restatement (tests/pyref_hmm_msv.py): the expected differences are 0
+
 --dump PATH saves the downloaded matrices of the modes that ran as one .npz (the Viterbi scores; both Forward matrices; raw, n_dom and the domain
 words of trace_best and trace_all), so that two builds of the library (GS_LIB_PATH) can be compared word for word.
 
-usage: hmm_rate.py [--forward | --trace] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
-                   [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log]"""
+usage: hmm_rate.py [--forward | --trace | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
+                   [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log | hmm_msv_rate.log]"""
 import argparse
 import json
 import os
@@ -45,11 +56,13 @@ def main():
     ap.add_argument("--seed", type=int, default=13)
     ap.add_argument("--forward", action="store_true")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--msv", action="store_true")
+    ap.add_argument("--parent-s", type=float, default=None)
     ap.add_argument("--log", default=None)
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     if a.log is None:
-        a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else ("hmm_trace_rate.log" if a.trace else "hmm_rate.log"))
+        a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else ("hmm_trace_rate.log" if a.trace else ("hmm_msv_rate.log" if a.msv else "hmm_rate.log")))
     import gsearch_amd as G
     import pyref_hmm as R
     rng = np.random.default_rng(a.seed)
@@ -99,6 +112,8 @@ def main():
         forward_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng, dump)
     if a.trace:
         trace_part(a, ctx, db, texts, recs, ptrs, d_rec, scores, cells, res, rng, dump)
+    if a.msv:
+        msv_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng, dump)
     if a.dump:
         with open(a.dump, "wb") as f:
             np.savez(f, **dump)
@@ -153,6 +168,60 @@ def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng, dum
     res["forward_check_pairs"], res["forward_check_differences"] = a.check, diff
     ctx.free(d_fwd)
     ctx.free(d_floor)
+
+
+def msv_part(a, ctx, db, texts, recs, ptrs, d_vit_all, vit_all, cells, res, rng, dump):
+    import pyref_hmm as R
+    import pyref_hmm_msv as V
+    n = a.n * len(db)
+    d_msv, d_vit = ctx.alloc(4 * n), ctx.alloc(4 * n)
+    floor = db.msv_floor(0.02)
+    d_floor = ctx.alloc(floor.nbytes)
+    ctx.upload(d_floor, floor)
+
+    def timed(call):
+        ctx.sync()
+        t = time.perf_counter()
+        call()
+        ctx.sync()
+        return time.perf_counter() - t
+
+    runs = {"msv": lambda: db.search_msv_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_msv),
+            "filtered": lambda: db.search_filtered_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_floor, None, d_msv, d_vit, None),
+            "unfiltered": lambda: db.search_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_vit_all)}
+    times = {k: [] for k in runs}
+    for it in range(a.repeat + 1):                               # the first round is the warm-up of every shape; the three alternate inside a round
+        for k, call in runs.items():
+            t = timed(call)
+            if it:
+                times[k].append(t)
+    msv = ctx.download(d_msv, (a.n, len(db)), np.int32)
+    vit = ctx.download(d_vit, (a.n, len(db)), np.int32)
+    dump.update(msv=msv, viterbi_filtered=vit)
+    for k, ts in times.items():
+        res[k + "_times_s"] = ts
+        res[k + "_min_s"], res[k + "_median_s"] = min(ts), float(np.median(ts))
+    res["msv_cells_per_s"] = cells / res["msv_min_s"]
+    res["msv_p"] = 0.02
+    sel = (msv != R.NO_SCORE) & (msv.astype(np.int64) >= floor[None, :])
+    res["passing_share"] = float(sel.mean())
+    res["filtered_over_unfiltered_min"] = res["filtered_min_s"] / res["unfiltered_min_s"]
+    res["filtered_over_unfiltered_median"] = res["filtered_median_s"] / res["unfiltered_median_s"]
+    if a.parent_s is not None:
+        res["parent_search_s"] = a.parent_s
+        res["filtered_over_parent"] = res["filtered_min_s"] / a.parent_s
+    res["selection_differences"] = int(((vit != R.NO_SCORE) != sel).sum())
+    res["filtered_differs_from_unfiltered"] = int((vit[sel] != vit_all[sel]).sum())
+    thr = db.thresholds("ga").astype(np.int64)
+    hits = (vit_all != R.NO_SCORE) & (vit_all.astype(np.int64) >= thr[None, :])
+    res["ga_hits"], res["ga_hits_lost"] = int(hits.sum()), int((hits & ~sel).sum())
+    diff = 0
+    for _ in range(a.check):
+        r, p = int(rng.integers(a.n)), int(rng.integers(len(db)))
+        diff += int(msv[r, p]) != V.msv(R.parse_hmm(texts[p])[0]["tables"], recs[r])
+    res["msv_check_pairs"], res["msv_check_differences"] = a.check, diff
+    for p in (d_msv, d_vit, d_floor):
+        ctx.free(p)
 
 
 def trace_part(a, ctx, db, texts, recs, ptrs, d_best_rec, scores, cells, res, rng, dump):

@@ -9,8 +9,10 @@
               node counts of the bacterial universal-gene set (tests/golden/hmm/bacteria_node_counts.txt): the wall time of the call, and beside it
               the stages of the same work run one after the other - reading, split + pack + upload + translation + descriptors back, the Viterbi
               search of the ORFs (the yardstick of the translation), best hits.
+  --prefilter also the same call with prefilter="msv" (SPEC 13.3): its wall time, the seconds of the filtered search of the ORFs (MSV,
+              selection, Viterbi over the selected lists) beside the Viterbi stage, and whether the hits are the same.
 
-usage: orf_rate.py [--genomes 64] [--len 5000000] [--search-genomes 64] [--repeat 3] [--min-aa 30] [--log profiles/orf_rate.log]"""
+usage: orf_rate.py [--genomes 64] [--len 5000000] [--search-genomes 64] [--repeat 3] [--min-aa 30] [--prefilter] [--log profiles/orf_rate.log]"""
 import argparse
 import json
 import os
@@ -40,6 +42,7 @@ def main():
     ap.add_argument("--min-aa", type=int, default=30)
     ap.add_argument("--check-bases", type=int, default=100000)
     ap.add_argument("--seed", type=int, default=14)
+    ap.add_argument("--prefilter", action="store_true")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "orf_rate.log"))
     a = ap.parse_args()
     import gsearch_amd as G
@@ -131,6 +134,24 @@ def main():
             db.best_hits_dev(d_score, dev.n, d_goff, K, d_thr, d_rec, d_sc)
             ctx.sync()
             res["best_hits_s"] = time.perf_counter() - t
+            if a.prefilter:
+                dev.search_dev(db, False, None, True, 0.02)                  # the warm-up of the MSV and selected-Viterbi kernels
+                ctx.sync()
+                t = time.perf_counter()
+                d_fscore = dev.search_dev(db, False, None, True, 0.02)
+                ctx.sync()
+                res["filtered_search_s"] = time.perf_counter() - t
+                res["filtered_over_viterbi"] = res["filtered_search_s"] / res["viterbi_s"]
+                fsc = ctx.download(d_fscore, (dev.n, len(db)), np.int32)
+                res["pairs_through_the_filter"] = float((fsc != R.NO_SCORE).mean())
+                t = time.perf_counter()
+                _, flocal, _ = G.universal_genes(files, db, ctx=ctx, translate=True, min_aa=a.min_aa, prefilter="msv")
+                ctx.sync()
+                res["universal_genes_prefilter_s"] = time.perf_counter() - t
+                res["prefilter_hits"], res["prefilter_same_hits"] = int((flocal != R.NO_HIT).sum()), bool(np.array_equal(flocal, local))
+                print("prefilter=msv: filtered search %.2f s (%.3f of the Viterbi stage, %.4f of the pairs go on), universal_genes %.2f s, same hits: %s" %
+                      (res["filtered_search_s"], res["filtered_over_viterbi"], res["pairs_through_the_filter"], res["universal_genes_prefilter_s"],
+                       res["prefilter_same_hits"]), flush=True)
             dev.close()
         db.close()
         print("universal_genes(translate=True): %d genomes, %d ORFs, %d residues: %.2f s in all; read %.2f s, split + pack + translate %.2f s, Viterbi %.2f s "
