@@ -21,3 +21,4 @@ from .api import hmm_forward_evalue, hmm_logsum_table, hmm_parse_stats, hmm_vite
 from .api import ORF_DTYPE, ORF_TILE, orf_codon_table, orf_translate, orf_translate_dev, orf_translate_packed, write_orf_faa  # noqa: F401
 from .api import (GENE_DTYPE, GENE_INTERVAL_DTYPE, GENE_START_TYPES, gene_call, gene_call_dev, gene_call_packed, gene_log2_q16, gene_params, gene_score,  # noqa: F401
                   gene_train, genecall, write_gene_faa, write_gene_ffn, write_gene_gff)
+from .commands import add, matches_text, reformat, reformat_text, request, rust_display_f64, rust_upper_exp, tohnsw  # noqa: F401

@@ -2514,10 +2514,21 @@ def hnswcore(dir, fname, typename, cluster=0, fraction=0.1, out_dir=".", max_ite
     return path, res
 
 
-def _rust_5e(x):
-    """Rust's {:.5E}: mantissa with 5 decimals, exponent without padding or plus sign (6.07500E-1)"""
-    mant, exp = ("%.5E" % x).split("E")
+def _rust_e(x, digits):
+    """Rust's {:.<digits>E}: mantissa with that many decimals, exponent without padding or plus sign (6.07500E-1, 5.400E-1); `inf` and `NaN` as
+    Rust's Display writes them"""
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if x in (float("inf"), float("-inf")):
+        return "inf" if x > 0 else "-inf"
+    mant, exp = ("%.*E" % (int(digits), x)).split("E")
     return "%sE%d" % (mant, int(exp))
+
+
+def _rust_5e(x):
+    """Rust's {:.5E} (answer.rs:58-64)"""
+    return _rust_e(x, 5)
 
 
 # ----------------------------------------------------------------------------------------------------------
