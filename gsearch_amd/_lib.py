@@ -315,6 +315,9 @@ SYMBOLS = {
     # debugging
     "gs_debug_mem_fill": (_i, [_i]),
     "gs_index_debug_fill_scratch": (_i, [_vp, _i]),
+    "gs_debug_radix_sort_u64": (_i, [_vp, _vp, _u64, _i, _vp]),
+    "gs_debug_run_lengths_u64": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "gs_debug_scan_u32": (_i, [_vp, _vp, _u64, _vp, _vp]),
 }
 
 _lib = None

@@ -205,6 +205,41 @@ def debug_mem_fill(byte):
     check(_lib.load().gs_debug_mem_fill(-1 if byte is None else int(byte)))
 
 
+def debug_radix_sort(keys, endbit, ctx=None):
+    """debugging, not for production use: the device radix sort of gs_radix.hip on a host array of uint64 keys, stable on bits [0, 8 * ceil(endbit / 8))
+    (gs_debug_radix_sort_u64)"""
+    ctx = ctx or default_context()
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    out = np.empty_like(keys)
+    check(ctx.L.gs_debug_radix_sort_u64(ctx.h, _p(keys), keys.size, int(endbit), _p(out)))
+    return out
+
+
+def debug_run_lengths(sorted_keys, ctx=None, out=None):
+    """debugging, not for production use: the device run-length encoding of gs_radix.hip on a sorted host array (gs_debug_run_lengths_u64): (keys, lengths)
+    of the runs. out: a (uint64, uint32) pair of contiguous arrays of len(sorted_keys) entries to write into - what comes back is their first r entries,
+    and a test that filled them with a canary looks at the rest."""
+    ctx = ctx or default_context()
+    a = np.ascontiguousarray(sorted_keys, dtype=np.uint64)
+    uniq, lengths = out if out is not None else (np.empty(a.size, np.uint64), np.empty(a.size, np.uint32))
+    if not (uniq.dtype == np.uint64 and lengths.dtype == np.uint32 and uniq.shape == lengths.shape == a.shape and uniq.flags.c_contiguous and lengths.flags.c_contiguous):
+        raise ValueError("debug_run_lengths: out must be contiguous uint64 and uint32 arrays as long as the input")
+    r = C.c_uint64(0)
+    check(ctx.L.gs_debug_run_lengths_u64(ctx.h, _p(a), a.size, _p(uniq), _p(lengths), C.byref(r)))
+    return uniq[:r.value], lengths[:r.value]
+
+
+def debug_scan(values, ctx=None):
+    """debugging, not for production use: the one-workgroup exclusive prefix sum of gs_radix.hip on a host array of uint32 (gs_debug_scan_u32):
+    (prefix sums, total)"""
+    ctx = ctx or default_context()
+    v = np.ascontiguousarray(values, dtype=np.uint32)
+    out = np.empty_like(v)
+    total = C.c_uint32(0xFFFFFFFF)
+    check(ctx.L.gs_debug_scan_u32(ctx.h, _p(v), v.size, _p(out), C.byref(total)))
+    return out, int(total.value)
+
+
 def default_context():
     global _default_ctx
     if _default_ctx is None:

@@ -189,7 +189,8 @@ int sketch_dev_impl(gs_ctx *c, const gs_sketch_params *p, const void *seq, uint6
 // gs_prob.hip: the ProbMinHash3a sketcher (tiered, bucketed and sorted forms) behind sketch_dev_impl; the results are left in flight on c's stream
 int run_prob(gs_ctx *c, const gs_sketch_params *p, const uint8_t *seq, uint64_t seq_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
              const uint64_t *genome_rec_off, uint64_t n_genomes, void *sig_out);
-// gs_radix.hip: stable LSD radix sort of 64-bit keys (bits [0, endbit)) between two buffers, and run-length encoding of a sorted array
+// gs_radix.hip: stable LSD radix sort of 64-bit keys between two buffers, and run-length encoding of a sorted array. The order is on bits
+// [0, 8 * ceil(endbit / 8)): a caller whose endbit is no multiple of 8 must keep the bits from endbit upwards zero
 size_t radix_scratch_bytes(uint64_t n);
 int radix_sort_u64(gs_ctx *c, uint64_t *keys, uint64_t *alt, uint64_t n, int endbit, void *scratch, uint64_t **sorted_out);
 int run_length_encode_u64(gs_ctx *c, const uint64_t *sorted, uint64_t n, uint64_t *uniq, uint32_t *len, uint32_t *nruns_dev, uint32_t *pos, void *scratch);

@@ -121,7 +121,10 @@ __global__ void k_rle_lengths(const uint32_t *__restrict__ pos, const uint32_t *
 
 size_t radix_scratch_bytes(uint64_t n) { const uint64_t nt = (n + RS_TILE - 1) / RS_TILE; return (size_t)(4 * (256 * nt + 64)); }
 
-// keys[0..n) sorted ascending on bits [0, endbit) (stable); `alt` is a second buffer of n keys; *sorted_out = whichever of the two holds the result
+// keys[0..n) sorted ascending (stable) on bits [0, 8 * ceil(endbit / 8)): the passes take whole 8-bit digits, so the digit that holds bit endbit - 1 is
+// compared whole. A caller whose endbit is no multiple of 8 must keep the bits from endbit upwards zero in every key (gs_prob.hip, gs_bigsi.hip and
+// gs_embed.hip do); the order is then the one on bits [0, endbit). `alt` is a second buffer of n keys; *sorted_out = whichever of the two holds the
+// result: `alt` after an odd number of passes, `keys` after an even one
 int radix_sort_u64(gs_ctx *c, uint64_t *keys, uint64_t *alt, uint64_t n, int endbit, void *scratch, uint64_t **sorted_out)
 {
     *sorted_out = keys;
@@ -155,3 +158,68 @@ int run_length_encode_u64(gs_ctx *c, const uint64_t *sorted, uint64_t n, uint64_
 }
 
 }  // namespace gs
+
+extern "C" {
+
+/* The three primitives behind host pointers, exposed for parity tests against numpy (tests/test_gpu_radix.py); not for production use. Each call stages
+ * its input in slots of its own, runs the primitive on the context's stream exactly as the consumers do, waits, and copies the result back. */
+int gs_debug_radix_sort_u64(gs_ctx *c, const uint64_t *keys, uint64_t n, int endbit, uint64_t *out)
+{
+    GS_REQUIRE(c && (n == 0 || (keys && out)), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(endbit >= 1 && endbit <= 64, GS_ERR_INVALID, "gs_debug_radix_sort_u64: endbit %d outside 1..64", endbit);
+    GS_REQUIRE(n < ((uint64_t)1 << 32), GS_ERR_UNSUPPORTED, "gs_debug_radix_sort_u64: more than 2^32 keys");
+    if (n == 0) return GS_OK;
+    GS_CTX_LOCK(c);
+    gs::PoolBuf dkeys(c, gs::SL_DBG_SORT_KEYS), dalt(c, gs::SL_DBG_SORT_ALT), radix(c, gs::SL_DBG_SORT_RADIX);
+    int rc;
+    if ((rc = dkeys.alloc(8 * n)) || (rc = dalt.alloc(8 * n)) || (rc = radix.alloc(gs::radix_scratch_bytes(n)))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(dkeys.p, keys, 8 * n, hipMemcpyHostToDevice, c->stream));
+    uint64_t *sorted = nullptr;
+    if ((rc = gs::radix_sort_u64(c, dkeys.as<uint64_t>(), dalt.as<uint64_t>(), n, endbit, radix.p, &sorted))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(out, sorted, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(gs::stream_wait(c));
+    return GS_OK;
+}
+
+int gs_debug_run_lengths_u64(gs_ctx *c, const uint64_t *sorted, uint64_t n, uint64_t *uniq, uint32_t *len, uint64_t *n_runs_out)
+{
+    GS_REQUIRE(c && n_runs_out && (n == 0 || (sorted && uniq && len)), GS_ERR_INVALID, "null argument");
+    GS_CTX_LOCK(c);
+    if (n == 0 || n >= ((uint64_t)1 << 32)) return gs::run_length_encode_u64(c, nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr);    // the primitive's own refusal
+    gs::PoolBuf dsorted(c, gs::SL_DBG_RLE_SORTED), duniq(c, gs::SL_DBG_RLE_UNIQ), dlen(c, gs::SL_DBG_RLE_LEN), dpos(c, gs::SL_DBG_RLE_POS), radix(c, gs::SL_DBG_RLE_RADIX),
+        dnruns(c, gs::SL_DBG_RLE_NRUNS);
+    int rc;
+    if ((rc = dsorted.alloc(8 * n)) || (rc = duniq.alloc(8 * n)) || (rc = dlen.alloc(4 * n)) || (rc = dpos.alloc(4 * n)) || (rc = radix.alloc(gs::radix_scratch_bytes(n))) ||
+        (rc = dnruns.alloc(4)))
+        return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(dsorted.p, sorted, 8 * n, hipMemcpyHostToDevice, c->stream));
+    if ((rc = gs::run_length_encode_u64(c, dsorted.as<uint64_t>(), n, duniq.as<uint64_t>(), dlen.as<uint32_t>(), dnruns.as<uint32_t>(), dpos.as<uint32_t>(), radix.p))) return rc;
+    uint32_t r = 0;
+    GS_HIP_CHECK(hipMemcpyAsync(&r, dnruns.p, 4, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(gs::stream_wait(c));
+    GS_REQUIRE(r >= 1 && r <= n, GS_ERR_STATE, "gs_debug_run_lengths_u64: %u runs in %llu keys", r, (unsigned long long)n);
+    GS_HIP_CHECK(hipMemcpyAsync(uniq, duniq.p, 8 * (size_t)r, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(len, dlen.p, 4 * (size_t)r, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(gs::stream_wait(c));
+    *n_runs_out = r;
+    return GS_OK;
+}
+
+int gs_debug_scan_u32(gs_ctx *c, const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *total_out)
+{
+    GS_REQUIRE(c && total_out && (n == 0 || (in && out)), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n < ((uint64_t)1 << 32), GS_ERR_UNSUPPORTED, "gs_debug_scan_u32: more than 2^32 values");
+    GS_CTX_LOCK(c);
+    gs::PoolBuf vals(c, gs::SL_DBG_SCAN_VALS), total(c, gs::SL_DBG_SCAN_TOTAL);
+    int rc;
+    if ((rc = vals.alloc(4 * n)) || (rc = total.alloc(4))) return rc;
+    if (n) GS_HIP_CHECK(hipMemcpyAsync(vals.p, in, 4 * n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(gs::k_scan_u32, dim3(1), dim3(1024), 0, c->stream, vals.as<uint32_t>(), n, total.as<uint32_t>());       // n = 0: no lane has a stretch, the total is 0
+    GS_HIP_CHECK(hipGetLastError());
+    if (n) GS_HIP_CHECK(hipMemcpyAsync(out, vals.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(total_out, total.p, 4, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(gs::stream_wait(c));
+    return GS_OK;
+}
+
+}  // extern "C"

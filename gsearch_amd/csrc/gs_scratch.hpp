@@ -96,7 +96,11 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     X(GENE_PMAX) X(GENE_PARG) X(GENE_PRED) X(GENE_CHOSEN) X(GENEB_SEQ) X(GENEB_REC_START) X(GENEB_REC_LEN) X(GENEB_GOFF) X(GENEB_INFO) X(GENEB_TABLES) \
     X(GENEB_GENE) X(GENEB_AA) X(GENEB_AA_START) X(GENEB_AA_LEN) X(GENEB_REC_OFF) X(GENE_SCAN_SUMS) X(GENE_SCAN_OFFS)                                                                      \
     /* comm (gs_topk_merge_dev) */                                                                                                                    \
-    X(COMM_ID_OFFSET)
+    X(COMM_ID_OFFSET)                                                                                                                                 \
+    /* gs_radix.hip behind host pointers (gs_debug_radix_sort_u64, gs_debug_run_lengths_u64, gs_debug_scan_u32; the suite only): the keys, their second \
+       buffer and the radix counts of a sort; the sorted keys, runs, lengths, head positions, head counts and run counter; the values and their sum */  \
+    X(DBG_SORT_KEYS) X(DBG_SORT_ALT) X(DBG_SORT_RADIX) X(DBG_RLE_SORTED) X(DBG_RLE_UNIQ) X(DBG_RLE_LEN) X(DBG_RLE_POS) X(DBG_RLE_RADIX) X(DBG_RLE_NRUNS) \
+    X(DBG_SCAN_VALS) X(DBG_SCAN_TOTAL)
 
 enum ScratchSlot : int {
 #define X(name) SL_##name,

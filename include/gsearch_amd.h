@@ -870,6 +870,19 @@ int gs_synth_sigs_skew_dev(gs_ctx *, int kind, uint32_t m, uint64_t seed, uint64
  * gs_index_debug_fill_scratch: fills the buffers an index keeps as per-call scratch (not its data, graph, caches or counters), synchronously. */
 int gs_debug_mem_fill(int byte);
 int gs_index_debug_fill_scratch(gs_index *, int byte);
+/* Debugging (tests only, not for production use): the three device primitives of gs_radix.hip, on which the sorted ProbMinHash form, FracMinHash sketches,
+ * the seed order of superani, the coverage filter of bigsig, the adjacency of the embedding and the candidate order of the gene caller stand, exposed for
+ * parity tests against numpy (tests/test_gpu_radix.py). All pointers are HOST pointers: each call stages to the device, runs the primitive on the
+ * context's stream, waits, and copies back.
+ * gs_debug_radix_sort_u64: out[0..n) = keys[0..n) in ascending, stable order on bits [0, 8 * ceil(endbit / 8)) - the passes take whole 8-bit digits, so
+ *   an endbit that is no multiple of 8 is only the order on bits [0, endbit) when every key is zero from endbit upwards. endbit outside 1..64:
+ *   GS_ERR_INVALID. n = 0 writes nothing, n = 1 returns the key.
+ * gs_debug_run_lengths_u64: the r runs of equal neighbours of sorted[0..n): uniq[0..r) their keys, len[0..r) their lengths, *n_runs_out = r; nothing is
+ *   written from r on. n = 0: GS_ERR_UNSUPPORTED (the primitive's own refusal), as is n >= 2^32.
+ * gs_debug_scan_u32: out[0..n) = the exclusive prefix sums of in[0..n) modulo 2^32, *total_out = the sum. n = 0: *total_out = 0, out is not written. */
+int gs_debug_radix_sort_u64(gs_ctx *c, const uint64_t *keys, uint64_t n, int endbit, uint64_t *out);
+int gs_debug_run_lengths_u64(gs_ctx *c, const uint64_t *sorted, uint64_t n, uint64_t *uniq, uint32_t *len, uint64_t *n_runs_out);
+int gs_debug_scan_u32(gs_ctx *c, const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *total_out);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 colour, the report files and the index file, every one compared with == against the numpy restatement tests/pyref_bigsi_mini.py. Shapes: the smallest at
 which each part can go wrong - window widths 2, 17 and 32 (the widest halo), a colour of records mostly shorter than the window, a record of many tiles,
 a build call that starts inside a colour word, a read on either side of the 12- / 32-plane split of the query kernel, values whose counts sit at the filter's
-threshold and on either side of it."""
+threshold and on either side of it, filters whose sort takes an odd and an even number of passes (the sorted list ends in the other or in the same buffer),
+a colour whose occurrence list spans three tiles of the sort with a run of equal values across the first tile edge."""
 import ctypes as C
 import gzip
 import struct
@@ -225,9 +226,18 @@ def _read_set(rng, genome, f):
     return [reads[i] for i in order], [tiles[i] for i in planted]
 
 
+def _sort_passes(k, m):
+    """8-bit digits the filter's sort walks: the values of a plain index hold 2 k bits, those of a minimizer index 2 m"""
+    return (2 * (m or k) + 7) // 8
+
+
 @pytest.mark.parametrize("f", [2, 3])
-@pytest.mark.parametrize("k,m", [(21, 0), (31, 15)])
+@pytest.mark.parametrize("k,m", [(21, 0), (31, 15), (12, 0), (32, 11), (32, 0)])
 def test_coverage_filter(gpu_ctx, k, m, f):
+    """the sort of the occurrence list walks ceil(2 k / 8) digits (2 m for a minimizer index): (21, 0) six and (31, 15) four, which leave the sorted list in the
+    buffer it came in; (12, 0) and (32, 11) three, which leave it in the second buffer, so that the runs go back into the first; (32, 0) eight, with values that
+    use the top digit. At k = 12 a value can recur by chance: the planted counts below hold at these seeds"""
+    assert _sort_passes(k, m) == {(21, 0): 6, (31, 15): 4, (12, 0): 3, (32, 11): 3, (32, 0): 8}[(k, m)]
     rng = np.random.default_rng(10 * k + f)
     h, B = 3, 1 << 16
     genome = _seq(rng, 5000)
@@ -235,15 +245,24 @@ def test_coverage_filter(gpu_ctx, k, m, f):
     # the planted counts, on the restatement first
     u, c = np.unique(RM.occurrences(reads, k, m), return_counts=True)
     count = dict(zip(u.tolist(), c.tolist()))
+    assert (k, m) != (32, 0) or (u >> np.uint64(56) > 0).sum() > len(u) // 2        # the eighth digit is in use
     for stretch, want in ((below, f - 1), (at, f), (above, f + 1)):
         vals = RM.occurrences([stretch], k, m)
         assert len(vals) > 0 and all(count[int(v)] == want for v in vals)
     unique_colour = [_seq(rng, 3000)]                                  # every value once: all of it falls below f
-    genomes = [reads, unique_colour, reads[::-1], [], [below] * f]
+    # a colour of 20 000 bases given f times: thousands of values at the threshold. Where the sort has three passes, the list after two of them (ordered
+    # on 16 bits) still has equal values apart - what a filter that reads the wrong one of the two sort buffers would count
+    repeated = [_seq(rng, 20000)] * f
+    if _sort_passes(k, m) == 3:
+        v = RM.occurrences(repeated, k, m)
+        two_passes = v[np.argsort(v & np.uint64(0xFFFF), kind="stable")]
+        assert (two_passes[1:] != two_passes[:-1]).sum() + 1 > len(np.unique(v)) > 1000
+    genomes = [reads, unique_colour, reads[::-1], [], [below] * f, repeated]
     bx, ref = _build(gpu_ctx, genomes, k, m, h, B, min_count=f)
     _check_index(bx, ref, np.arange(B))
     t, nk = bx.bits_set(return_kmers=True)
     assert t[1] == 0 and nk[1] == 0 and t[3] == 0 and t[0] == t[2] > 0 and nk[0] == nk[2] > 0 and t[4] > 0
+    assert nk[5] == len(RM.occurrences(repeated, k, m))
     want_nk = sum(n * len(RM.occurrences([s], k, m)) for s, n in ((at, f), (above, f + 1)))
     assert nk[0] == want_nk
     col = bx.rows(np.arange(B))[:, 0]
@@ -266,6 +285,46 @@ def test_coverage_filter(gpu_ctx, k, m, f):
             assert np.array_equal(a, b_)
     for x in (bx, one, plain, raw):
         x.close()
+
+
+SORT_TILE = 16384                       # keys a wavefront owns in the sort and the run-length passes of the filter (gs_radix.hip)
+TILE_EDGE_SEED = {(21, 0): 2, (12, 0): 2}      # seeds at which positions 16383 and 16384 of the sorted occurrence list hold one value (about every second seed does)
+
+
+def _tile_edge_colour(seed, k, m):
+    """a genome of 12 000 bases given twice, four stretches of 800 of its bases three times each and a record given once, in a fixed shuffle"""
+    rng = np.random.default_rng(seed)
+    genome = _seq(rng, 12000)
+    stretches = [genome[s:s + 800] for s in (700, 3900, 6100, 10400)]
+    once = _seq(rng, 1500)
+    records = [genome, genome, once] + stretches * 3
+    return genome, stretches, once, [records[i] for i in rng.permutation(len(records))]
+
+
+@pytest.mark.parametrize("k,m", [(21, 0), (12, 0)])
+def test_coverage_filter_across_sort_tiles(gpu_ctx, k, m):
+    """one colour of more than two sort tiles of occurrences, a run of equal values across the first tile edge: the head counts of the tiles and the
+    heads written have to agree there. (21, 0) sorts in six passes, (12, 0) in three (the sorted list in the second buffer)"""
+    h, B, f = 3, 1 << 16, 2
+    assert _sort_passes(k, m) == {(21, 0): 6, (12, 0): 3}[(k, m)]
+    genome, stretches, once, colour = _tile_edge_colour(TILE_EDGE_SEED[(k, m)], k, m)
+    # on the restatement first: the size, the run on the edge, and counts on either side of the threshold
+    occ = np.sort(RM.occurrences(colour, k, m))
+    assert len(occ) > 2 * SORT_TILE and occ[SORT_TILE - 1] == occ[SORT_TILE]
+    u, c = np.unique(occ, return_counts=True)
+    count = dict(zip(u.tolist(), c.tolist()))
+    assert all(count[int(v)] >= 5 for v in RM.occurrences([stretches[0]], k, m)) and (c == 1).sum() > 1000 and (c == 2).sum() > 5000
+    genomes = [[_seq(np.random.default_rng(5), 900) * 2], colour, []]
+    bx, ref = _build(gpu_ctx, genomes, k, m, h, B, min_count=f)
+    _check_index(bx, ref, np.arange(B))
+    t, nk = bx.bits_set(return_kmers=True)
+    assert nk[1] == int(c[c >= f].sum()) and t[1] > 0 and nk[2] == 0
+    reads = [[stretches[1][100:250]], [genome[5000:5150]], [once[300:450]], [once[:100], genome[200:300]]]
+    nkq, bc, bh, cnt = _check_query(bx, ref, reads)
+    assert cnt[0, 1] == nkq[0] > 0 and cnt[1, 1] == nkq[1] > 0 and bc[0] == 1
+    if k == 21:
+        assert cnt[2, 1] < nkq[2] // 4                               # the record given once was dropped: what it still hits are false positives
+    bx.close()
 
 
 # ---- files ----------------------------------------------------------------------------------------------------------------------------------------

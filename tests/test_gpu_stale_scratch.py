@@ -988,6 +988,47 @@ def _(wd):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------------
+# the primitives of gs_radix.hip on their own (test_gpu_radix.py runs their whole tables under 0x00 and 0xFF; here a large shape in front of a small one,
+# and the replay in other families' leftovers)
+def _radix_case(names, cases, call, ref):
+    picked = [next(c for c in cases if c["name"] == n) for n in names]
+    want = tuple(np.asarray(x) for c in picked for x in ref(c))
+
+    def run(ctx, poke):
+        return tuple(np.asarray(x) for c in picked for x in call(ctx, c))
+    return run, want
+
+
+@case("radix", "sort_three_tiles_then_65_keys")
+def _(wd):
+    import gsearch_amd as G
+    import pyref_radix as RR
+    import radix_cases as RC
+    return _radix_case(("size_%d_e24" % (3 * RC.TILE + 17), "size_65_e64"), RC.sort_cases(), lambda ctx, c: (G.debug_radix_sort(c["keys"], c["endbit"], ctx=ctx),),
+                       lambda c: (RR.sort(c["keys"], c["endbit"]),))
+
+
+@case("radix", "run_lengths_five_tiles_then_65_keys")
+def _(wd):
+    import gsearch_amd as G
+    import pyref_radix as RR
+    import radix_cases as RC
+    return _radix_case(("size_%d" % (4 * RC.TILE + 1), "size_65"), RC.rle_cases(), lambda ctx, c: G.debug_run_lengths(c["a"], ctx=ctx), lambda c: RR.run_lengths(c["a"]))
+
+
+@case("radix", "scan_4608_then_5_counts")
+def _(wd):
+    import gsearch_amd as G
+    import pyref_radix as RR
+    import radix_cases as RC
+
+    def call(ctx, c):
+        out, total = G.debug_scan(c["v"], ctx=ctx)
+        return out, np.uint32(total)
+    return _radix_case(("size_4608", "size_5"), RC.scan_cases(), call, lambda c: (RR.scan(c["v"])[0], np.uint32(RR.scan(c["v"])[1])))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------
 # one test function per case, in the order of the list, then the replay
 def _make_test(c):
     def test(stale_ctx, fill_guard, workdir, monkeypatch, capfd):
