@@ -19,6 +19,7 @@
 #include "gs_internal.hpp"
 #include "gs_spec.hpp"
 #include "gs_skq.hpp"
+#include "gs_hiword.hpp"
 #include "gs_walk.hpp"
 
 namespace gs {
@@ -103,6 +104,7 @@ struct MinEmitF {
     // dropped), a slot that is not sends the workgroup through the genome again under the running bound alone (same table: minima are idempotent).
     // The cap is a performance parameter only - the signature never depends on it. EMPTY = no cap.
     T cap;
+    mutable uint32_t lim;                         // wave-uniform: limit_of(thr), what the drop test compares with
     static __device__ __forceinline__ T key_of(uint64_t o1)
     {
         if (ALGO == ALGO_SUPER2) return sizeof(T) == 8 ? (T)o1 : (T)(o1 >> 32);
@@ -119,12 +121,19 @@ struct MinEmitF {
         two_draw(h, m, zone, o1, b);
         atomicMin(&table[b], key_of(o1));
     }
-    // key_of(o1) < thr. For the 23-bit keys, (o1 >> 41) < thr is hi32(o1) < thr << 9: one 32-bit compare instead of a shift and a compare.
-    // Only full() asks, and only while thr < direct_above() = 2^21, so thr << 9 cannot overflow.
-    static __device__ __forceinline__ bool key_below(uint64_t o1, T t)
+    // The drop test, on the high word of s0 and nine bits of s3's alone (gs_hiword.hpp): `lim` is the bound of the key form plus the slack of
+    // everything the other bits can add to hi32(o1), so a k-mer whose key is below thr always passes and 0.78 % of all k-mers pass beside them - their
+    // exact key, rebuilt from the queued hash in the flush, decides. Only full() / full2() ask, and only while thr < direct_above(), so no limit overflows.
+    static __device__ __forceinline__ uint32_t limit_of(T t)
     {
-        if (ALGO == ALGO_SUPER2) return key_of(o1) < t;
-        return (uint32_t)(o1 >> 32) < ((uint32_t)t << 9);
+        uint32_t l;
+        if (ALGO == ALGO_SUPER2) l = sizeof(T) == 8 ? hiword_limit_x_u64((uint64_t)t) : hiword_limit_x_u32((uint32_t)t);
+        else l = hiword_limit_x_r23((uint32_t)t);
+        return (uint32_t)__builtin_amdgcn_readfirstlane(l);
+    }
+    __device__ __forceinline__ bool key_below(uint32_t s0_hi, uint32_t s3_x) const
+    {
+        return hiword_may_be_below_x(s0_hi, s3_x, lim);
     }
     __device__ __forceinline__ void operator()(uint64_t v, uint64_t, uint64_t) const { apply(elem_hash<ALGO, VBITS>(v)); }
     // The lanes of `bal` (bal != 0) queue a hash each - hg_a where in_a, hg_b where in_b, never both; 64 pending survivors are flushed on the way.
@@ -155,11 +164,10 @@ struct MinEmitF {
         asm("" : "+v"(hg));         // opaque: the compiler would otherwise rebuild h beside h + gamma and derive h + 4 gamma from h
         return hg;
     }
-    // the key only needs two of the three SplitMix64 outputs
+    // the key only needs two of the three SplitMix64 outputs, and the test only their high words
     __device__ __forceinline__ bool filter(uint64_t hg) const
     {
-        const uint64_t s0 = splitmix_mix(hg), s3 = splitmix_mix(hg + 3 * GS_GAMMA);
-        return key_below(rotl64(s0 + s3, 23) + s0, thr);
+        return key_below(splitmix_mix_hi(hg), splitmix_mix_hi9(hg + 3 * GS_GAMMA));
     }
     __device__ __forceinline__ void full(uint64_t v) const
     {
@@ -197,6 +205,7 @@ struct MinEmitF {
         // every lane holds the same maximum; taken through an SGPR so that the compiler knows it too: the filter test compares against a scalar
         // and the branch to the direct form is a scalar one
         thr = uniform(mx < cap ? mx : cap);
+        lim = limit_of(thr);
     }
     static __device__ __forceinline__ T uniform(T x)
     {
@@ -250,7 +259,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_min(const uint8_t *__rest
             }
         }
         for (int pass = 0; pass < 2; pass++) {
-            MinEmitF<ALGO, VBITS, T> emit{table, m, zone, qbase + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * SKQ, threadIdx.x & 63, 0u, 0u, cap, cap};
+            MinEmitF<ALGO, VBITS, T> emit{table, m, zone, qbase + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * SKQ, threadIdx.x & 63, 0u, 0u, cap, cap, MinEmitF<ALGO, VBITS, T>::limit_of(cap)};
             walk_genome<AA, MinEmitF<ALGO, VBITS, T>, RCM>(seq, rec_start, rec_len, rec_upre, genome_rec_off[g], genome_rec_off[g + 1], gen_units[g], k, part, parts, emit);
             if (cap == EMPTY) break;
             __syncthreads();

@@ -75,6 +75,32 @@ GS_HD uint64_t splitmix_mix(uint64_t z)
     z = mulc64(z ^ (z >> 27), 0x94d049bb133111ebULL);
     return z ^ (z >> 31);
 }
+// The high word of splitmix_mix(z) alone, for a caller that decides on it (the drop test of MinEmitF, gs_hiword.hpp): the last xor-shift is
+// b_hi ^ (b_hi >> 31) - one 32-bit shift and one xor instead of a 64-bit shift and two xors - and the low word of the second product is dead
+// (hipcc then takes a v_mul_hi_u32 in place of mulc64's last v_mad_u64_u32 by itself).
+GS_HD uint32_t splitmix_mix_hi(uint64_t z)
+{
+    z = mulc64(z ^ (z >> 30), 0xbf58476d1ce4e5b9ULL);
+    const uint32_t b = (uint32_t)(mulc64(z ^ (z >> 27), 0x94d049bb133111ebULL) >> 32);
+    return b ^ (b >> 31);
+}
+// The LOW 9 BITS of that high word before its last xor-shift (b_hi above; splitmix_mix_hi(z) = b_hi ^ (b_hi >> 31) differs from it by at most one
+// unit). The bits above the ninth are not the mix's: on the device the two cross terms of the second product come from 24-bit multiply-adds, which
+// are right in their low 24 bits. For hiword_may_be_below_x (gs_hiword.hpp), which shifts s3's word up by 23 and so reads no other bit of it.
+GS_HD uint32_t splitmix_mix_hi9(uint64_t z)
+{
+    z = mulc64(z ^ (z >> 30), 0xbf58476d1ce4e5b9ULL);
+    z ^= z >> 27;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t xl = (uint32_t)z, xh = (uint32_t)(z >> 32), cl = 0x133111ebu, ch = 0x94d049bbu;
+    uint32_t t = __umulhi(xl, cl);
+    asm("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(t) : "v"(xl), "s"(ch));
+    asm("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(t) : "v"(xh), "s"(cl));
+    return t;
+#else
+    return (uint32_t)((z * 0x94d049bb133111ebULL) >> 32);
+#endif
+}
 #define GS_GAMMA 0x9e3779b97f4a7c15ULL
 
 struct Rng {   // xoshiro256++ seeded through SplitMix64 (rand_xoshiro seed_from_u64)

@@ -149,6 +149,38 @@ template <int FORM> __device__ __forceinline__ uint64_t drop_chain(uint64_t v)
     const uint64_t t = s0 + s3;
     return ((t << 23) | (t >> 41)) + s0;
 }
+// The same chain as the filter now asks it (gs_hiword.hpp): only the high words of s0 and s3, B = ((s0_hi + s3_hi + 2) << 23) + s0_hi, fed back as
+// B : (s0_hi ^ s3_hi). HI picks how the high word of each mix's second multiply is written:
+//   4  mulc64's form B shifted down by 32 (hipcc drops the dead low word by itself: v_mul_hi_u32 in place of the last v_mad_u64_u32)
+//   5  written out: __umulhi(x_lo, c_lo) + the fenced cross multiply-add
+template <int HI> __device__ __forceinline__ uint32_t mix_hi(uint64_t z)
+{
+    z = mulc<3>(z ^ (z >> 30), 0xbf58476d1ce4e5b9ull);
+    z ^= z >> 27;
+    uint32_t b;
+    if (HI == 4) b = (uint32_t)(mulc<3>(z, 0x94d049bb133111ebull) >> 32);
+    else {
+        const uint32_t xl = (uint32_t)z, xh = (uint32_t)(z >> 32), cl = 0x133111ebu, ch = 0x94d049bbu;
+        uint64_t cr = (uint64_t)xh * cl + (uint32_t)(xl * ch);
+        asm("" : "+v"(cr));
+        b = __umulhi(xl, cl) + (uint32_t)cr;
+    }
+    return b ^ (b >> 31);
+}
+template <> __device__ __forceinline__ uint64_t drop_chain<4>(uint64_t v)
+{
+    uint64_t hg = mulc<3>(v, 0x517cc1b727220a95ull, 0x9e3779b97f4a7c15ull);
+    asm("" : "+v"(hg));
+    const uint32_t s0 = mix_hi<4>(hg), s3 = mix_hi<4>(hg + 3 * 0x9e3779b97f4a7c15ull);
+    return ((uint64_t)(((s0 + s3 + 2u) << 23) + s0) << 32) | (s0 ^ s3);
+}
+template <> __device__ __forceinline__ uint64_t drop_chain<5>(uint64_t v)
+{
+    uint64_t hg = mulc<3>(v, 0x517cc1b727220a95ull, 0x9e3779b97f4a7c15ull);
+    asm("" : "+v"(hg));
+    const uint32_t s0 = mix_hi<5>(hg), s3 = mix_hi<5>(hg + 3 * 0x9e3779b97f4a7c15ull);
+    return ((uint64_t)(((s0 + s3 + 2u) << 23) + s0) << 32) | (s0 ^ s3);
+}
 #define CH_ITERS 256
 template <int FORM>
 __global__ __launch_bounds__(256) void kchain(uint32_t *out, uint32_t seed)
@@ -175,6 +207,6 @@ int main()
     run<10>("v_lshlrev_b64", d); run<5>("v_alignbit_b32", d); run<6>("v_mul_u32_u24", d); run<9>("v_mad_u32_u24", d); run<7>("v_lshl_add_u64", d); run<8>("v_add3_u32", d); run<11>("v_cmp_lt_u64", d);
     run<12>("v_add_u32", d); run<13>("v_mov_b32", d); run<14>("v_dot2_u32_u16", d); run<15>("v_lshrrev_b32", d);
     run_seq<0>("hipcc", d); run_seq<1>("A", d); run_seq<2>("B", d); run_seq<3>("B2", d); run_seq<4>("B0", d); run_seq<5>("Bg", d);
-    run_chain<0>("x*c", d); run_chain<1>("A", d); run_chain<2>("B", d); run_chain<3>("Bg", d);
+    run_chain<0>("x*c", d); run_chain<1>("A", d); run_chain<2>("B", d); run_chain<3>("Bg", d); run_chain<4>("Bg hi", d); run_chain<5>("Bg hi mulhi", d);
     return 0;
 }
