@@ -1179,6 +1179,60 @@ class HmmDb:
             raw, nd, dom = self.trace_packed(aa, rec_start, rec_len, pair_rec, pair_prof, int(nd.max()), max_block_cells)
         return raw, nd, dom
 
+    def envelopes_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_env=8, rows=False, max_block_rows=0):
+        """SPEC 13.4: Forward and Backward scores and the posterior envelopes of the pairs (pair_rec[j], pair_prof[j]), all on the device -> (int32 fwd
+        [n_pairs] as search_forward_packed() gives it, int32 bck [n_pairs] = bN[0] - null, uint32 n_env [n_pairs] the true number of envelopes, int32 env
+        [n_pairs, max_env, 4]: i_from, i_to (1-based, inclusive), env_raw, peak of the first max_env envelopes in sequence order, zeros behind them) and,
+        with rows=True, two lists of per-pair int32 arrays out[1..L] and cont[1..L] in units (empty for a pair that gets no envelopes below). A pair
+        whose record is HMM_NO_HIT, empty or holds a byte that is no residue: HMM_NO_SCORE, HMM_NO_SCORE, 0 and zeros. max_block_rows bounds the rows of
+        the two passes that are alive at once (0: 2^25)"""
+        aa = np.ascontiguousarray(aa, dtype=np.uint8)
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
+        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        pr = np.ascontiguousarray(pair_rec, dtype=np.uint32).reshape(-1)
+        pp = np.ascontiguousarray(pair_prof, dtype=np.uint32).reshape(-1)
+        if len(pr) != len(pp):
+            raise ValueError("pair_rec and pair_prof: one entry per pair each")
+        n = len(pr)
+        fwd, bck, ne = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        env = np.zeros((n, int(max_env), _lib.HMM_ENV_WORDS), np.int32)
+        ro = o_rows = c_rows = None
+        if rows and n:
+            named = pr < len(rl)                                                    # (HMM_NO_HIT names no record; another bad index is refused below)
+            lens = np.zeros(n, np.uint64)
+            lens[named] = rl[pr[named]]
+            ro = np.zeros(n + 1, np.uint64)
+            ro[1:] = np.cumsum(lens)
+            o_rows, c_rows = np.zeros(max(int(ro[-1]), 1), np.int32), np.zeros(max(int(ro[-1]), 1), np.int32)
+        check(self.ctx.L.gs_hmm_envelopes(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
+                                          _p(pr) if n else None, _p(pp) if n else None, n, int(max_env), int(max_block_rows), _p(fwd) if n else None,
+                                          _p(bck) if n else None, _p(ne) if n else None, _p(env) if env.size else None, _p(ro) if ro is not None else None,
+                                          _p(o_rows) if ro is not None else None, _p(c_rows) if ro is not None else None))
+        if not rows:
+            return fwd, bck, ne, env
+        has = fwd != _lib.HMM_NO_SCORE
+        cut = lambda a: [a[int(ro[j]):int(ro[j + 1])] if has[j] else a[:0] for j in range(n)]      # noqa: E731
+        return fwd, bck, ne, env, cut(o_rows) if n else [], cut(c_rows) if n else []
+
+    def envelopes(self, records, pairs, max_env=8, rows=False, max_block_rows=0):
+        """records as search() takes them; pairs: (record, profile) index pairs -> what envelopes_packed() returns"""
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        return self.envelopes_packed(*filter_aa_records([bytes(r) for r in records]), pairs[:, 0].astype(np.uint32), pairs[:, 1].astype(np.uint32), max_env=max_env,
+                                     rows=rows, max_block_rows=max_block_rows)
+
+    def envelopes_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, pair_rec_dev, pair_prof_dev, n_pairs, max_env, fwd_out_dev, bck_out_dev, n_env_out_dev,
+                      env_out_dev, row_off_dev=None, out_rows_dev=None, cont_rows_dev=None, max_block_rows=0):
+        """all device memory; the lengths, the pair list and row_off are read back once"""
+        check(self.ctx.L.gs_hmm_envelopes_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), pair_rec_dev, pair_prof_dev, int(n_pairs), int(max_env),
+                                              int(max_block_rows), fwd_out_dev, bck_out_dev, n_env_out_dev, env_out_dev, row_off_dev, out_rows_dev, cont_rows_dev))
+
+    def envelopes_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_block_rows=0):
+        """envelopes_packed() with room for every envelope: run again with the largest n_env when 8 slots a pair do not hold them all"""
+        got = self.envelopes_packed(aa, rec_start, rec_len, pair_rec, pair_prof, 8, max_block_rows=max_block_rows)
+        if len(got[2]) and int(got[2].max()) > got[3].shape[1]:
+            got = self.envelopes_packed(aa, rec_start, rec_len, pair_rec, pair_prof, int(got[2].max()), max_block_rows=max_block_rows)
+        return got
+
     def thresholds(self, cutoff="ga"):
         """int32 [n_prof] in units: every profile's GA1, or the caller's bits for all (a number) or per profile (a sequence)"""
         if isinstance(cutoff, str):
@@ -1236,7 +1290,7 @@ def _check_prefilter(prefilter):
 
 
 def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None, translate=False, min_aa=_lib.ORF_MIN_AA, table=11, prefilter=None,
-              msv_p=0.02):
+              msv_p=0.02, envelopes=None):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
     `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
     `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
@@ -1248,6 +1302,10 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     `target profile acc dom n_dom i_from i_to k_from k_to M seg_bits n_match n_ins n_del` for every domain, seg_bits %.2f of seg / 1024, sorted like the
     score table and then by dom (from 1). With score="forward" the pairs are the Forward table's and the path is still the Viterbi path. The return value is
     then (ids, scores, table bytes, domain table bytes).
+    envelopes (a path; SPEC 13.4): the pairs the score table lists get a Forward and a Backward pass on the device and a table of their posterior
+    envelopes is written there - a header line, then `target profile acc env n_env i_from i_to env_bits peak_occ` for every envelope, env_bits %.2f of
+    env_raw / 1024, peak_occ %.3f of 1 - 2^(peak / 1024), sorted like the score table and then by env (from 1). It works with either score and together
+    with domains; its bytes are appended to the return value.
     translate=True (SPEC 14): `faa` is a NUCLEOTIDE FASTA; the targets are its stop-to-stop six-frame ORFs of min_aa residues and more under translation
     `table` (11 or 4), translated on the device and searched there without their residues coming back. A target is named `{contig}_{begin+1}_{end}_{+|-}`
     as write_orf_faa() names it, Z is the number of ORFs, the formats are unchanged. The ORFs are not a proteome: no start codons, no frameshifts.
@@ -1266,7 +1324,7 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     fwd = score == "forward"
     dev = None
     if translate:
-        dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd, domains is not None), table)
+        dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd or envelopes is not None, domains is not None), table)
         try:
             ids = dev.names()
             scores = dev.search(db, fwd, filter_p, prefilter is not None, msv_p)
@@ -1300,18 +1358,33 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     if output is not None:
         with open(output, "wb") as f:
             f.write(table)
-    if domains is None:
+    if domains is None and envelopes is None:
         if dev is not None:
             dev.close()
         return ids, scores, table
     pr, pp = np.array([r for r, _ in listed], np.uint32), np.array([p for _, p in listed], np.uint32)
-    if dev is not None:
-        try:
-            _, nd, dom = dev.trace_all(db, pr, pp)
-        finally:
+    try:
+        if domains is not None:
+            _, nd, dom = dev.trace_all(db, pr, pp) if dev is not None else db.trace_all(aa, rs, rl, pr, pp)
+        if envelopes is not None:
+            _, _, ne, env = dev.envelopes_all(db, pr, pp) if dev is not None else db.envelopes_all(aa, rs, rl, pr, pp)
+    finally:
+        if dev is not None:
             dev.close()
-    else:
-        _, nd, dom = db.trace_all(aa, rs, rl, pr, pp)
+    env_table = None
+    if envelopes is not None:
+        out = [b"target\tprofile\tacc\tenv\tn_env\ti_from\ti_to\tenv_bits\tpeak_occ\n"]
+        for j, (r, p) in enumerate(listed):
+            inf = db.info[p]
+            for d in range(int(ne[j])):
+                w = [int(v) for v in env[j, d]]
+                out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%.2f\t%.3f\n" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(ne[j]), w[0], w[1], w[2] / 1024.0,
+                                                                          1.0 - 2.0 ** (w[3] / 1024.0))).encode())
+        env_table = b"".join(out)
+        with open(envelopes, "wb") as f:
+            f.write(env_table)
+    if domains is None:
+        return ids, scores, table, env_table
     out = [b"target\tprofile\tacc\tdom\tn_dom\ti_from\ti_to\tk_from\tk_to\tM\tseg_bits\tn_match\tn_ins\tn_del\n"]
     for j, (r, p) in enumerate(listed):
         inf = db.info[p]
@@ -1322,7 +1395,7 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     dom_table = b"".join(out)
     with open(domains, "wb") as f:
         f.write(dom_table)
-    return ids, scores, table, dom_table
+    return (ids, scores, table, dom_table) if env_table is None else (ids, scores, table, dom_table, env_table)
 
 
 def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein", translate=False, min_aa=_lib.ORF_MIN_AA, table=11,
@@ -1332,6 +1405,8 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing). score="forward": the best hits are those of the Forward matrix
     (SPEC 13.1) behind the Viterbi floor of filter_p - the score the files' GA cutoffs were gathered on. region="aligned" (SPEC 13.2): every hit is
     traced back on the device and contributes the residues from i_from of its first domain through i_to of its last, not the whole protein.
+    region="envelope" (SPEC 13.4): every hit contributes the residues from i_from of its first posterior envelope through i_to of its last - what a
+    Forward hit list should be cut by; a hit without an envelope contributes the whole record, and is counted like any other.
     translate=True (SPEC 14): one genome per NUCLEOTIDE FASTA file; the candidates are the stop-to-stop six-frame ORFs of min_aa residues and more under
     translation `table`, translated and searched on the device - only the chosen hits' residues come back. The record numbers are then ORF numbers inside
     the genome, and a third value is returned: int64 [n_genomes, n_prof, 4] = (contig index, begin, end, strand) of the chosen ORF in contig coordinates
@@ -1343,13 +1418,13 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     prefilter="msv" (SPEC 13.3): the best hits are taken among the pairs at or above the MSV floor of msv_p, as hmmsearch(prefilter="msv") scores them."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
-    if region not in ("protein", "aligned"):
-        raise ValueError("region: 'protein' or 'aligned'")
+    if region not in ("protein", "aligned", "envelope"):
+        raise ValueError("region: 'protein', 'aligned' or 'envelope'")
     _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
     if translate:
         return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate, prefilter is not None,
-                                           msv_p)
+                                           msv_p, region == "envelope")
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
@@ -1366,6 +1441,11 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
         _, nd, dom = db.trace_all(aa, rs, rl, rec.reshape(-1), pair_prof)
         for j in np.flatnonzero(nd):
             span[int(j)] = (int(dom[j, 0, 0]) - 1, int(dom[j, int(nd[j]) - 1, 1]))
+    if region == "envelope" and rec.size:
+        pair_prof = np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
+        _, _, ne, env = db.envelopes_all(aa, rs, rl, rec.reshape(-1), pair_prof)
+        for j in np.flatnonzero(ne):
+            span[int(j)] = (int(env[j, 0, 0]) - 1, int(env[j, int(ne[j]) - 1, 1]))
     genomes = []
     for g in range(len(goff) - 1):
         hits = []
@@ -1607,6 +1687,28 @@ class _DevOrfs:
         self._free(d_pr); self._free(d_pp)
         return raw, nd, dom
 
+    def envelopes_all(self, db, pair_rec, pair_prof):
+        """HmmDb.envelopes_all() over the device residues -> (fwd, bck, n_env, env)"""
+        pr, pp = np.ascontiguousarray(pair_rec, np.uint32).reshape(-1), np.ascontiguousarray(pair_prof, np.uint32).reshape(-1)
+        npair, max_env = len(pr), 8
+        if npair == 0 or self.n == 0:
+            none = np.full(npair, _lib.HMM_NO_SCORE, np.int32)
+            return none, none.copy(), np.zeros(npair, np.uint32), np.zeros((npair, max_env, _lib.HMM_ENV_WORDS), np.int32)
+        d_pr, d_pp = self._up(pr), self._up(pp)
+        while True:
+            d_out = [self._new(4 * npair), self._new(4 * npair), self._new(4 * npair), self._new(4 * npair * max_env * _lib.HMM_ENV_WORDS)]
+            db.envelopes_dev(self.d_aa, self.d_as, self.d_al, self.n, d_pr, d_pp, npair, max_env, *d_out)
+            fwd, bck = self.ctx.download(d_out[0], (npair,), np.int32), self.ctx.download(d_out[1], (npair,), np.int32)
+            ne = self.ctx.download(d_out[2], (npair,), np.uint32)
+            env = self.ctx.download(d_out[3], (npair, max_env, _lib.HMM_ENV_WORDS), np.int32)
+            for ptr in d_out:
+                self._free(ptr)
+            if int(ne.max()) <= max_env:
+                break
+            max_env = int(ne.max())
+        self._free(d_pr); self._free(d_pp)
+        return fwd, bck, ne, env
+
     def residues(self, j, a=0, b=None):
         """residues [a, b) of ORF j, read back from the device"""
         b = int(self.aa_len[j]) if b is None else b
@@ -1615,9 +1717,9 @@ class _DevOrfs:
         return self.ctx.download(self.d_aa + int(self.aa_start[j]) + a, (b - a,), np.uint8).tobytes()
 
 
-def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02):
+def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02, envelope=False):
     ctx = db.ctx
-    dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd, aligned), table)
+    dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd or envelope, aligned), table)
     try:
         ng, npf = len(fna_files), len(db)
         rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
@@ -1632,6 +1734,10 @@ def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, m
             _, nd, dom = dev.trace_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
             for j in np.flatnonzero(nd):
                 span[int(j)] = (int(dom[j, 0, 0]) - 1, int(dom[j, int(nd[j]) - 1, 1]))
+        if envelope and (rec != _lib.HMM_NO_HIT).any():
+            _, _, ne, env = dev.envelopes_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
+            for j in np.flatnonzero(ne):
+                span[int(j)] = (int(env[j, 0, 0]) - 1, int(env[j, int(ne[j]) - 1, 1]))
         genomes = []
         for g in range(ng):
             hits = []

@@ -1,6 +1,7 @@
 // gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
 // device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, the best record per genome and profile, and the domains of
-// the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2). Integers only
+// the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2), and the Backward pass and posterior envelopes of a list of pairs
+// (SPEC 13.4). Integers only
 // from the file's digits to the raw score; doubles appear in gs_hmm_bits / gs_hmm_evalue / gs_hmm_forward_evalue, in the table of lse (rounded to
 // integers once, on the host), in the Viterbi floor and in the cutoffs and STATS fields that are only reported.
 #include <math.h>
@@ -211,13 +212,13 @@ __device__ __forceinline__ int32_t hmm_lse(int32_t a, int32_t b, const uint16_t 
     return hi + (int32_t)T[j];
 }
 
-// The three dynamic programs over the cells of a (record, profile) pair. They share one prologue (hmm_stage) and one row loop (hmm_rows) and differ at
+// The dynamic programs over the cells of a (record, profile) pair (Backward has a row loop of its own, further down). They share one prologue (hmm_stage) and one row loop (hmm_rows) and differ at
 // compile time only, at the points the row loop names.
-enum HmmProg { HMM_VIT, HMM_FWD, HMM_TRACE, HMM_PROGS };
+enum HmmProg { HMM_VIT, HMM_FWD, HMM_TRACE, HMM_FWD_ROWS, HMM_PROGS };     // HMM_FWD_ROWS: Forward that keeps the special-state rows (SPEC 13.4)
 // what joins alternatives: max (SPEC 13, 13.2) or lse (SPEC 13.1). T is read by lse alone.
 template <HmmProg P> __device__ __forceinline__ int32_t hmm_join(int32_t a, int32_t b, const uint16_t *T)
 {
-    if constexpr (P == HMM_FWD) return hmm_lse(a, b, T); else return max(a, b);
+    if constexpr (P == HMM_FWD || P == HMM_FWD_ROWS) return hmm_lse(a, b, T); else return max(a, b);
 }
 // The join over the wavefront, in every lane: neighbours, pairs of pairs, ... - for lse the balanced tree of SPEC 13.1. After the two quad steps the four
 // lanes of a quad hold one value, so the mirrors hand a lane the value of the other quad / the other half row; that is the tree because the join is
@@ -268,6 +269,9 @@ __host__ __device__ constexpr int hmm_ptr_words(int Q) { return (Q + 7) / 8; }
 //   together with the D decision of the next lane's first node (M + tMD of the last node == what leaves the lane after the scan), in one word.
 //   The D pointers inside a lane are taken after D is final. No traced cell is at the clamp (SPEC 13.2), so an equality that a clamped cell decides
 //   differently is never followed.
+// Forward with rows (SPEC 13.4): Forward's arithmetic and barrier, and lane 0 leaves {E[i], J[i], C[i]} of every row; row 0 is NEG.
+// The specials come from a length of their own (Lsp): the record's for every program but the envelope scores, which run Forward over a stretch of a
+//   record under the whole record's length model.
 template <int Q> struct HmmLane {
     const int32_t *ms, *tMM, *tMI, *tMD, *tIM, *tII, *tDM, *tDD, *PDD;  // the lane's Q words of match row 0, of the transition rows and of PDD, in LDS
     const uint16_t *T;                                      // the table of lse in LDS (Forward)
@@ -305,20 +309,21 @@ __device__ __forceinline__ HmmLane<Q> hmm_stage(const int32_t *tables, const Hmm
 // Trace also writes the record's pointer words to pp (the lane's column) and its row specials to rr. x, pp and rr carry no __restrict__ and ln comes by
 // value: either costs some trace instances registers and a wave per SIMD, at the same instruction counts (NOTES.md).
 template <int Q, HmmProg P>
-__device__ __forceinline__ int32_t hmm_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, uint32_t *pp, int4 *rr)
+__device__ __forceinline__ int32_t hmm_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, uint32_t Lsp, uint32_t *pp, int4 *rr)
 {
     constexpr int MP = 64 * Q, NW = hmm_ptr_words(Q);
-    constexpr bool FWD = P == HMM_FWD, TRACE = P == HMM_TRACE;
+    constexpr bool ROWS = P == HMM_FWD_ROWS, FWD = P == HMM_FWD || ROWS, TRACE = P == HMM_TRACE;
     constexpr int RELOAD_FROM_Q = P == HMM_VIT ? 20 : 12;     // from here the transition rows are read from LDS in every row (above)
     const uint16_t *T = ln.T;
     const int lane = ln.lane, nvalid = ln.nvalid;
     if (!TRACE && L == 0) return GS_HMM_NO_SCORE;             // (the host puts no empty record on a trace list)
-    const HmmSpecials sp = hmm_specials(L);
+    const HmmSpecials sp = hmm_specials(Lsp);
     int32_t Mv[Q], Iv[Q], Dv[Q];
 #pragma unroll
     for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = Dv[q] = GS_HMM_NEG;
     int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
     if constexpr (TRACE) if (lane == 0) rr[0] = make_int4(GS_HMM_NEG, B, 0, HMM_ROW_B_FROM_N);
+    if constexpr (ROWS) if (lane == 0) rr[0] = make_int4(GS_HMM_NEG, GS_HMM_NEG, GS_HMM_NEG, 0);
     bool bad = false;
     int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
     for (uint32_t i0 = 0; i0 < L; i0 += 64) {
@@ -401,6 +406,7 @@ __device__ __forceinline__ int32_t hmm_rows(const HmmLane<Q> ln, const uint8_t *
             J = Jn; C = Cn;
             B = hmm_join<P>(N, J, T) + sp.tmove;
             if constexpr (TRACE) if (lane == 0) rr[row + 1] = make_int4(E, B, kE, flags);
+            if constexpr (ROWS) if (lane == 0) rr[row + 1] = make_int4(E, J, C, 0);
         }
         cur = nxt;
     }
@@ -417,7 +423,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_viterbi(const int32_t *__rest
     const HmmLane<Q> ln = hmm_stage<Q, false>(tables, desc[p], nullptr);
     for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < n_rec; j += gridDim.x * HMM_WAVES) {
         const uint32_t r = order[j];
-        const int32_t raw = hmm_rows<Q, HMM_VIT>(ln, aa + rec_start[r], (uint32_t)rec_len[r], nullptr, nullptr);
+        const int32_t raw = hmm_rows<Q, HMM_VIT>(ln, aa + rec_start[r], (uint32_t)rec_len[r], (uint32_t)rec_len[r], nullptr, nullptr);
         if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
     }
 }
@@ -436,7 +442,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_forward(const int32_t *__rest
     const uint32_t *list = sel + (uint64_t)p * n_rec;
     for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < cnt; j += gridDim.x * HMM_WAVES) {
         const uint32_t r = list[j];
-        const int32_t raw = hmm_rows<Q, HMM_FWD>(ln, aa + rec_start[r], (uint32_t)rec_len[r], nullptr, nullptr);
+        const int32_t raw = hmm_rows<Q, HMM_FWD>(ln, aa + rec_start[r], (uint32_t)rec_len[r], (uint32_t)rec_len[r], nullptr, nullptr);
         if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
     }
 }
@@ -453,7 +459,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_trace(const int32_t *__restri
     const HmmLane<Q> ln = hmm_stage<Q, false>(tables, desc[tp.prof], nullptr);
     for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
         const HmmTracePair pr = pairs[tp.start + j];
-        const int32_t raw = hmm_rows<Q, HMM_TRACE>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], ptrs + pr.ptr_off + ln.lane, rows + pr.row_off);
+        const int32_t raw = hmm_rows<Q, HMM_TRACE>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], (uint32_t)rec_len[pr.rec], ptrs + pr.ptr_off + ln.lane, rows + pr.row_off);
         if (ln.lane == 0) raw_out[pr.pair] = raw;
     }
 }
@@ -473,7 +479,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_viterbi_sel(const int32_t *__
     const uint32_t *list = sel + (uint64_t)p * n_rec;
     for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < cnt; j += gridDim.x * HMM_WAVES) {
         const uint32_t r = list[j];
-        const int32_t raw = hmm_rows<Q, HMM_VIT>(ln, aa + rec_start[r], (uint32_t)rec_len[r], nullptr, nullptr);
+        const int32_t raw = hmm_rows<Q, HMM_VIT>(ln, aa + rec_start[r], (uint32_t)rec_len[r], (uint32_t)rec_len[r], nullptr, nullptr);
         if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
     }
 }
@@ -716,21 +722,240 @@ __global__ __launch_bounds__(256) void k_hmm_trace_fill(uint64_t n_pairs, uint64
     if (i < n_dom_words) dom[i] = 0;
 }
 
-// the five instances of a class, from the one class list
+// ---- Backward and posterior envelopes (SPEC 13.4) -------------------------------------------------------------------------------------------------
+// The pairs of a block come as the trace's lists do (HmmTraceProf, HmmTracePair; ptr_off is not used): row_off is where the pair's L + 1 kept rows
+// start, in the Forward rows {E[i], J[i], C[i], 0} (int4) and in the Backward rows {bN[i], bJ[i]} (int2) alike.
+//   Backward walks the rows L .. 0. A row needs bM and bI of the row below only (bD of a row is a recurrence along descending k inside the row), so
+//   lane l keeps those 2 Q words; residues are loaded 64 at a time from the record's end, lane t of a load holding the residue of step t. Row L
+//   has no row below: it runs the same step with no node valid (every take = NEG) and bJ = bN = NEG. take of a lane's first node moves DOWN one
+//   lane. The D scan is Forward's mirrored: each lane runs bD over its own nodes from its last one with nothing entering (Dloc), its group is the map
+//   x -> lse(x + gsum, Dloc[first]), six steps of b = lse(b, b(lane + d) + a_d) with a select for the lanes that take no step, c_in from the lane
+//   above, bD[q] = lse(Dloc[q], c_in + the sum of tDD from q to the group's end). Padding nodes hold NEG in bD and in take, so nothing of them
+//   reaches node M; the transition rows are read from LDS in every row from Q = 12, as Forward reads them.
+enum { HMM_ENV_BLOCK = 64, HMM_ENV_LO = -156, HMM_ENV_HI = -425 };
+// 24 bytes a row: 768 MB of kept rows alive at once. A block is two launches per class and each ends with its longest record, so small blocks are
+// paid for in tails: at 2^23 the 4 000 x 120 shape of DESIGN 3.24 ran 18 blocks and Forward with rows took 2.5 times the seconds of k_hmm_forward.
+static constexpr uint64_t HMM_ENV_DEFAULT_BLOCK_ROWS = 1ull << 25;
+
+template <int Q>
+__device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, int2 *rr)
+{
+    constexpr int MP = 64 * Q;
+    const uint16_t *T = ln.T;
+    const int lane = ln.lane, nvalid = ln.nvalid;
+    const HmmSpecials sp = hmm_specials(L);
+    const int32_t gsum = ln.PDD[Q - 1] + ln.tDD[Q - 1];       // the group's sum of tDD
+    int32_t a_dn[6];                                          // a of the lanes a scan step joins: the sums of gsum over lanes l .. l + 2^s - 1
+    {
+        int32_t a = gsum;
+        for (int s = 0; s < 6; s++) {
+            a_dn[s] = a;
+            const int32_t dn = __shfl_down(a, 1 << s);
+            if (lane + (1 << s) < 64) a += dn;
+        }
+    }
+    int32_t Mv[Q], Iv[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) Mv[q] = Iv[q] = GS_HMM_NEG;
+    int32_t bJ = GS_HMM_NEG, bN = GS_HMM_NEG;
+    bool bad = false;
+    int res = 0;
+    int nxt = (uint32_t)lane < L ? hmm_residue(x[L - 1 - (uint32_t)lane]) : 0;
+    for (uint32_t s = 0; s <= L; s++) {                       // row i = L - s; step s >= 1 reads residue x_(i+1) = x[L - s]
+        const uint32_t j = s - 1;
+        if (s && (j & 63u) == 0) {
+            bad |= nxt < 0;
+            res = max(nxt, 0);
+            const uint32_t at = j + 64 + (uint32_t)lane;      // the next 64 residues are on their way while these run
+            nxt = at < L ? hmm_residue(x[L - 1 - at]) : 0;
+        }
+        if (Q >= 12) asm volatile("" ::: "memory");
+        const int32_t *ms = ln.ms + (s ? __builtin_amdgcn_readlane(res, (int)(j & 63u)) : 0) * MP;
+        const int nv = s ? nvalid : 0;
+        int32_t take[Q], e = GS_HMM_NEG;
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            take[q] = q < nv ? ms[q] + Mv[q] : GS_HMM_NEG;
+            e = q < nv ? hmm_lse(e, take[q], T) : e;
+        }
+        const int32_t bB = hmm_wave_join<HMM_FWD>(e, T) + ln.tbm;
+        const int32_t bC = (int32_t)s * sp.tloop + sp.tmove;
+        if (s) {
+            bJ = max(hmm_lse(bJ + sp.tloop, bB + sp.tmove, T), GS_HMM_NEG);
+            bN = max(hmm_lse(bN + sp.tloop, bB + sp.tmove, T), GS_HMM_NEG);
+        }
+        const int32_t bE = hmm_lse(bJ + GS_HMM_TEJ, bC + GS_HMM_TEJ, T);
+        if (lane == 0) rr[L - s] = make_int2(bN, bJ);
+        int32_t dn = __shfl_down(take[0], 1);
+        if (lane == 63) dn = GS_HMM_NEG;
+        int32_t Dv[Q], dl = GS_HMM_NEG;
+#pragma unroll
+        for (int q = Q - 1; q >= 0; q--) {
+            const int32_t c = hmm_lse(bE, (q + 1 < Q ? take[q + 1] : dn) + ln.tDM[q], T);
+            dl = q == Q - 1 ? c : max(hmm_lse(c, dl + ln.tDD[q], T), GS_HMM_NEG);
+            dl = q < nvalid ? dl : GS_HMM_NEG;
+            Dv[q] = dl;
+        }
+        int32_t b = dl;
+#pragma unroll
+        for (int t = 0; t < 6; t++) {
+            const int32_t nb = hmm_lse(b, __shfl_down(b, 1 << t) + a_dn[t], T);
+            b = lane + (1 << t) < 64 ? max(nb, GS_HMM_NEG) : b;
+        }
+        int32_t c_in = __shfl_down(b, 1);                     // bD of the next lane's first node
+        if (lane == 63) c_in = GS_HMM_NEG;
+#pragma unroll
+        for (int q = 1; q < Q; q++) Dv[q] = max(hmm_lse(Dv[q], c_in + (gsum - ln.PDD[q]), T), GS_HMM_NEG);
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const int32_t tk = q + 1 < Q ? take[q + 1] : dn, dnext = q + 1 < Q ? Dv[q + 1] : c_in;
+            const int32_t m = hmm_lse(hmm_lse(hmm_lse(bE, tk + ln.tMM[q], T), Iv[q] + ln.tMI[q], T), dnext + ln.tMD[q], T);
+            Iv[q] = max(hmm_lse(tk + ln.tIM[q], Iv[q] + ln.tII[q], T), GS_HMM_NEG);
+            Mv[q] = max(m, GS_HMM_NEG);
+        }
+    }
+    return __any(bad) ? GS_HMM_NO_SCORE : bN - sp.null;
+}
+
+// Forward score and the rows {E[i], J[i], C[i]} of the pairs of each profile of profs[]; 1 <= L <= GS_HMM_FWD_MAX_L: the host put no other pair on a list
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_forward_rows(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                                const HmmTracePair *__restrict__ pairs, const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa,
+                                                                const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len, int4 *__restrict__ rows,
+                                                                int32_t *__restrict__ fwd_out)
+{
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmLane<Q> ln = hmm_stage<Q, true>(tables, desc[tp.prof], lse_tab);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const int32_t raw = hmm_rows<Q, HMM_FWD_ROWS>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], (uint32_t)rec_len[pr.rec], nullptr, rows + pr.row_off);
+        if (ln.lane == 0) fwd_out[pr.pair] = raw;
+    }
+}
+
+// Backward score bN[0] - null and the rows {bN[i], bJ[i]} of the same lists
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_backward(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                            const HmmTracePair *__restrict__ pairs, const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa,
+                                                            const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len, int2 *__restrict__ rows,
+                                                            int32_t *__restrict__ bck_out)
+{
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmLane<Q> ln = hmm_stage<Q, true>(tables, desc[tp.prof], lse_tab);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const int32_t raw = hmm_back_rows<Q>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], rows + pr.row_off);
+        if (ln.lane == 0) bck_out[pr.pair] = raw;
+    }
+}
+
+// Occupancy, runs and envelopes of SPEC 13.4, one wavefront per pair of the block: the lanes form out / exit / cont of 64 rows at a time from the kept
+// rows (T is read from device memory here: five look-ups a row), a ballot gives which rows are in and which continue, and the run rule walks the 64
+// bits on the scalar side. Writes n_env (the true count) and i_from, i_to, 0, peak of the first max_env envelopes; k_hmm_env_score fills the third
+// word. A pair whose Forward raw is GS_HMM_NO_SCORE keeps what the fill wrote.
+__global__ __launch_bounds__(HMM_ENV_BLOCK) void k_hmm_envelopes(const HmmTracePair *__restrict__ pairs, const uint64_t *__restrict__ rec_len, const uint16_t *__restrict__ T,
+                                                                 const int4 *__restrict__ frows, const int2 *__restrict__ brows, const int32_t *__restrict__ fwd,
+                                                                 uint32_t max_env, uint32_t *__restrict__ n_env_out, int32_t *__restrict__ env_out,
+                                                                 const uint64_t *__restrict__ row_off, int32_t *__restrict__ out_rows, int32_t *__restrict__ cont_rows)
+{
+    const HmmTracePair pr = pairs[blockIdx.x];
+    if (fwd[pr.pair] == GS_HMM_NO_SCORE) return;
+    const uint32_t L = (uint32_t)rec_len[pr.rec], lane = threadIdx.x;
+    const HmmSpecials sp = hmm_specials(L);
+    const int4 *f = frows + pr.row_off;
+    const int2 *bk = brows + pr.row_off;
+    const int32_t total_f = f[L].z + sp.tmove;
+    int32_t *env = env_out + (uint64_t)pr.pair * max_env * GS_HMM_ENV_WORDS;
+    const uint64_t ro = row_off ? row_off[pr.pair] : 0;
+    uint32_t n = 0, a = 0;
+    int32_t peak = 0;
+    bool open = false, prev_ct = false;
+    auto close = [&](uint32_t last) {
+        if (peak <= HMM_ENV_HI) {
+            if (n < max_env && lane == 0) { int32_t *o = env + (uint64_t)n * GS_HMM_ENV_WORDS; o[0] = (int32_t)a; o[1] = (int32_t)last; o[2] = 0; o[3] = peak; }
+            n++;
+        }
+        open = false;
+    };
+    for (uint32_t i0 = 1; i0 <= L; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        int32_t out = 0, cont = 0;
+        if (i <= L) {
+            const int4 fp = f[i - 1];
+            const int2 b = bk[i];
+            const int32_t bC = (int32_t)(L - i) * sp.tloop + sp.tmove;
+            out = hmm_lse(hmm_lse((int32_t)i * sp.tloop + b.x, fp.y + sp.tloop + b.y, T), fp.z + sp.tloop + bC, T) - total_f;
+            const int32_t ex = f[i].x + hmm_lse(b.y + GS_HMM_TEJ, bC + GS_HMM_TEJ, T) - total_f;
+            cont = hmm_lse(out, ex, T);
+            if (out_rows) { out_rows[ro + i - 1] = out; cont_rows[ro + i - 1] = cont; }
+        }
+        const uint64_t inm = __ballot(i <= L && out <= HMM_ENV_LO), ctm = __ballot(cont <= HMM_ENV_LO);
+        const int cnt = (int)min(64u, L - i0 + 1);
+        for (int t = 0; t < cnt; t++) {
+            const bool in_t = (inm >> t) & 1;
+            if (open && !(in_t && prev_ct)) close(i0 + (uint32_t)t - 1);
+            if (in_t) {
+                const int32_t o = __builtin_amdgcn_readlane(out, t);
+                if (!open) { open = true; a = i0 + (uint32_t)t; peak = o; } else peak = min(peak, o);
+            }
+            prev_ct = (ctm >> t) & 1;
+        }
+    }
+    if (open) close(L);
+    if (lane == 0) n_env_out[pr.pair] = n;
+}
+
+// env_raw of the listed envelopes: Forward over the rows i_from .. i_to of the record under the length model of the whole record. The slots of the pairs
+// of a profile are consecutive, so a workgroup stages the profile once and its wavefronts take the written slots in turn.
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_env_score(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                             const HmmTracePair *__restrict__ pairs, const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa,
+                                                             const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len, uint32_t max_env,
+                                                             const uint32_t *__restrict__ n_env, int32_t *env_out)
+{
+    const HmmTraceProf tp = profs[blockIdx.y];
+    const uint64_t slots = (uint64_t)tp.cnt * max_env;
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= slots) return;
+    const HmmLane<Q> ln = hmm_stage<Q, true>(tables, desc[tp.prof], lse_tab);
+    for (uint64_t j = (uint64_t)blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < slots; j += (uint64_t)gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + (uint32_t)(j / max_env)];
+        const uint32_t e = (uint32_t)(j % max_env);
+        if (e >= n_env[pr.pair]) continue;
+        int32_t *o = env_out + ((uint64_t)pr.pair * max_env + e) * GS_HMM_ENV_WORDS;
+        const uint32_t L = (uint32_t)rec_len[pr.rec], from = (uint32_t)o[0], Ld = (uint32_t)o[1] - from + 1;
+        const int32_t raw = hmm_rows<Q, HMM_FWD>(ln, aa + rec_start[pr.rec] + (from - 1), Ld, L, nullptr, nullptr);
+        if (ln.lane == 0) o[2] = raw + (int32_t)(L - Ld) * hmm_specials(L).tloop;
+    }
+}
+
+// fwd = bck = GS_HMM_NO_SCORE, n_env = 0 and zeroed slots for every pair; the pairs that are listed overwrite theirs
+__global__ __launch_bounds__(256) void k_hmm_env_fill(uint64_t n_pairs, uint64_t n_env_words, int32_t *__restrict__ fwd, int32_t *__restrict__ bck, uint32_t *__restrict__ n_env,
+                                                      int32_t *__restrict__ env)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_pairs) { fwd[i] = GS_HMM_NO_SCORE; bck[i] = GS_HMM_NO_SCORE; n_env[i] = 0; }
+    if (i < n_env_words) env[i] = 0;
+}
+
+// the instances of a class, from the one class list
 struct HmmKernels {
     decltype(&k_hmm_viterbi<1>) vit; decltype(&k_hmm_forward<1>) fwd; decltype(&k_hmm_trace<1>) trace; decltype(&k_hmm_msv<1>) msv; decltype(&k_hmm_viterbi_sel<1>) vit_sel;
+    decltype(&k_hmm_forward_rows<1>) fwd_rows; decltype(&k_hmm_backward<1>) back; decltype(&k_hmm_env_score<1>) env_score;
 };
 template <size_t... I> static const HmmKernels &hmm_kernels(int cls, std::index_sequence<I...>)
 {
     static const HmmKernels of_class[] = {{k_hmm_viterbi<HMM_CLASS_Q[I]>, k_hmm_forward<HMM_CLASS_Q[I]>, k_hmm_trace<HMM_CLASS_Q[I]>, k_hmm_msv<HMM_CLASS_Q[I]>,
-                                           k_hmm_viterbi_sel<HMM_CLASS_Q[I]>}...};
+                                           k_hmm_viterbi_sel<HMM_CLASS_Q[I]>, k_hmm_forward_rows<HMM_CLASS_Q[I]>, k_hmm_backward<HMM_CLASS_Q[I]>,
+                                           k_hmm_env_score<HMM_CLASS_Q[I]>}...};
     return of_class[cls];
 }
 static const HmmKernels &hmm_kernels(int cls) { return hmm_kernels(cls, std::make_index_sequence<HMM_CLASSES>()); }
-static size_t hmm_lds_bytes(int cls, HmmProg prog) { return (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + (prog == HMM_FWD ? HMM_LSE_LDS_BYTES : 0); }
+static size_t hmm_lds_bytes(int cls, HmmProg prog) { return (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + (prog == HMM_FWD || prog == HMM_FWD_ROWS ? HMM_LSE_LDS_BYTES : 0); }
 static size_t hmm_msv_lds_bytes(int cls) { return (size_t)HMM_MSV_ROWS * 64 * HMM_CLASS_Q[cls] * 4; }
 // which kernel a (kernel, class) flag of the profile set belongs to: the three programs of hmm_rows, then MSV and Viterbi over a selected list
-enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_KERNEL_KINDS };
+enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_K_BACK, HMM_K_ENV_SCORE, HMM_KERNEL_KINDS };
 
 }  // namespace gs
 
@@ -941,8 +1166,66 @@ static int hmm_filtered_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, co
 // one nibble still takes a word. The longest record against the largest profile (65 536 x 1 280) is 84 million cells, so it fits one default block.
 static constexpr uint64_t HMM_TRACE_DEFAULT_BLOCK_CELLS = 1ull << 27;
 
-// what gs_hmm_trace refuses, decided on host copies before anything is queued
-static int hmm_trace_check(const gs_hmm_db *db, const uint64_t *lens, uint64_t n_rec, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs)
+// The pairs of a call cut into blocks, for the trace and for the posterior passes (SPEC 13.4): blocks in the caller's order, a block's pairs by class
+// and profile, longest record first. cost(i) is what pair i adds to its block; a block ends before the pair that would take it past cap, and always
+// holds at least one pair. A pair without a record or with an empty one is on no list. ptr_off counts the pair's back-pointer words, row_off its L + 1 rows.
+struct HmmPairBlock { uint32_t start, n, prof_start[HMM_CLASSES + 1], max_cnt[HMM_CLASSES]; };
+struct HmmPairBlocks {
+    std::vector<HmmTracePair> tp; std::vector<HmmTraceProf> tprof; std::vector<HmmPairBlock> blocks;
+    uint64_t max_ptr = 0, max_rows = 0;                          // the largest block's pointer words and rows
+};
+template <class Cost>
+static HmmPairBlocks hmm_pair_blocks(const gs_hmm_db *db, const uint64_t *lens, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs, uint64_t cap, Cost cost)
+{
+    HmmPairBlocks out;
+    std::vector<uint32_t> cur;
+    uint64_t used = 0;
+    auto flush = [&]() {
+        if (cur.empty()) return;
+        std::stable_sort(cur.begin(), cur.end(), [&](uint32_t a, uint32_t b) {
+            const int ca = hmm_class_of(db->desc[pprof[a]].M), cb = hmm_class_of(db->desc[pprof[b]].M);
+            if (ca != cb) return ca < cb;
+            if (pprof[a] != pprof[b]) return pprof[a] < pprof[b];
+            return lens[prec[a]] > lens[prec[b]];
+        });
+        HmmPairBlock b{};
+        b.start = (uint32_t)out.tp.size(); b.n = (uint32_t)cur.size();
+        uint64_t ptr = 0, row = 0;
+        size_t at = 0;
+        for (int cls = 0; cls < HMM_CLASSES; cls++) {
+            b.prof_start[cls] = (uint32_t)out.tprof.size();
+            while (at < cur.size() && hmm_class_of(db->desc[pprof[cur[at]]].M) == cls) {
+                const uint32_t prof = pprof[cur[at]];
+                HmmTraceProf g{prof, (uint32_t)out.tp.size(), 0};
+                for (; at < cur.size() && pprof[cur[at]] == prof; at++, g.cnt++) {
+                    const uint64_t L = lens[prec[cur[at]]];
+                    out.tp.push_back(HmmTracePair{ptr, row, cur[at], prec[cur[at]]});
+                    ptr += L * hmm_ptr_words(HMM_CLASS_Q[cls]) * 64;
+                    row += L + 1;
+                }
+                b.max_cnt[cls] = std::max(b.max_cnt[cls], g.cnt);
+                out.tprof.push_back(g);
+            }
+        }
+        b.prof_start[HMM_CLASSES] = (uint32_t)out.tprof.size();
+        out.max_ptr = std::max(out.max_ptr, ptr); out.max_rows = std::max(out.max_rows, row);
+        out.blocks.push_back(b);
+        cur.clear(); used = 0;
+    };
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (prec[i] == GS_HMM_NO_HIT || lens[prec[i]] == 0) continue;
+        const uint64_t pc = cost(i);
+        if (!cur.empty() && used + pc > cap) flush();
+        cur.push_back((uint32_t)i);
+        used += pc;
+    }
+    flush();
+    return out;
+}
+
+// what gs_hmm_trace refuses, and gs_hmm_envelopes with max_l = GS_HMM_FWD_MAX_L, decided on host copies before anything is queued
+static int hmm_trace_check(const gs_hmm_db *db, const uint64_t *lens, uint64_t n_rec, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs,
+                           uint32_t max_l = GS_HMM_TRACE_MAX_L)
 {
     const uint64_t np = db->models.size();
     for (uint64_t i = 0; i < n_pairs; i++) {
@@ -950,8 +1233,8 @@ static int hmm_trace_check(const gs_hmm_db *db, const uint64_t *lens, uint64_t n
         GS_REQUIRE(prec[i] == GS_HMM_NO_HIT || prec[i] < n_rec, GS_ERR_INVALID, "hmm: pair %llu names record %u of %llu", (unsigned long long)i, prec[i], (unsigned long long)n_rec);
     }
     for (uint64_t i = 0; i < n_pairs; i++)
-        GS_REQUIRE(prec[i] == GS_HMM_NO_HIT || lens[prec[i]] <= GS_HMM_TRACE_MAX_L, GS_ERR_UNSUPPORTED, "hmm: pair %llu names record %u of %llu residues, more than %u",
-                   (unsigned long long)i, prec[i], (unsigned long long)lens[prec[i]], GS_HMM_TRACE_MAX_L);
+        GS_REQUIRE(prec[i] == GS_HMM_NO_HIT || lens[prec[i]] <= max_l, GS_ERR_UNSUPPORTED, "hmm: pair %llu names record %u of %llu residues, more than %u",
+                   (unsigned long long)i, prec[i], (unsigned long long)lens[prec[i]], max_l);
     return GS_OK;
 }
 
@@ -969,52 +1252,13 @@ static int hmm_trace_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const
         k_hmm_trace_fill<<<(unsigned)((n_fill + 255) / 256), 256, 0, c->stream>>>(n_pairs, n_dom_words, raw_dev, ndom_dev, dom_dev);
         GS_HIP_CHECK(hipGetLastError());
     }
-    struct Block { uint32_t start, n, prof_start[HMM_CLASSES + 1], max_cnt[HMM_CLASSES]; };
-    std::vector<HmmTracePair> tp;
-    std::vector<HmmTraceProf> tprof;
-    std::vector<Block> blocks;
-    std::vector<uint32_t> cur;
-    uint64_t cells = 0, max_ptr = 0, max_rows = 0;
-    auto flush = [&]() {
-        if (cur.empty()) return;
-        std::stable_sort(cur.begin(), cur.end(), [&](uint32_t a, uint32_t b) {
-            const int ca = hmm_class_of(db->desc[pprof[a]].M), cb = hmm_class_of(db->desc[pprof[b]].M);
-            if (ca != cb) return ca < cb;
-            if (pprof[a] != pprof[b]) return pprof[a] < pprof[b];
-            return lens[prec[a]] > lens[prec[b]];
-        });
-        Block b{};
-        b.start = (uint32_t)tp.size(); b.n = (uint32_t)cur.size();
-        uint64_t ptr = 0, row = 0;
-        size_t at = 0;
-        for (int cls = 0; cls < HMM_CLASSES; cls++) {
-            b.prof_start[cls] = (uint32_t)tprof.size();
-            while (at < cur.size() && hmm_class_of(db->desc[pprof[cur[at]]].M) == cls) {
-                const uint32_t prof = pprof[cur[at]];
-                HmmTraceProf g{prof, (uint32_t)tp.size(), 0};
-                for (; at < cur.size() && pprof[cur[at]] == prof; at++, g.cnt++) {
-                    const uint64_t L = lens[prec[cur[at]]];
-                    tp.push_back(HmmTracePair{ptr, row, cur[at], prec[cur[at]]});
-                    ptr += L * hmm_ptr_words(HMM_CLASS_Q[cls]) * 64;
-                    row += L + 1;
-                }
-                b.max_cnt[cls] = std::max(b.max_cnt[cls], g.cnt);
-                tprof.push_back(g);
-            }
-        }
-        b.prof_start[HMM_CLASSES] = (uint32_t)tprof.size();
-        max_ptr = std::max(max_ptr, ptr); max_rows = std::max(max_rows, row);
-        blocks.push_back(b);
-        cur.clear(); cells = 0;
-    };
-    for (uint64_t i = 0; i < n_pairs; i++) {
-        if (prec[i] == GS_HMM_NO_HIT || lens[prec[i]] == 0) continue;
-        const uint64_t pc = lens[prec[i]] * 64 * HMM_CLASS_Q[hmm_class_of(db->desc[pprof[i]].M)];
-        if (!cur.empty() && cells + pc > cap) flush();
-        cur.push_back((uint32_t)i);
-        cells += pc;
-    }
-    flush();
+    const HmmPairBlocks pb = hmm_pair_blocks(db, lens, prec, pprof, n_pairs, cap, [&](uint64_t i) {
+        return lens[prec[i]] * 64 * HMM_CLASS_Q[hmm_class_of(db->desc[pprof[i]].M)];
+    });
+    const std::vector<HmmTracePair> &tp = pb.tp;
+    const std::vector<HmmTraceProf> &tprof = pb.tprof;
+    const std::vector<HmmPairBlock> &blocks = pb.blocks;
+    const uint64_t max_ptr = pb.max_ptr, max_rows = pb.max_rows;
     if (!blocks.empty()) {
         PoolBuf d_tp(c, SL_HMMT_PAIRS), d_tprof(c, SL_HMMT_PROFS), d_ptr(c, SL_HMMT_PTR), d_rows(c, SL_HMMT_ROWS);
         int rc;
@@ -1023,7 +1267,7 @@ static int hmm_trace_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const
             return rc;
         GS_HIP_CHECK(hipMemcpyAsync(d_tp.p, tp.data(), sizeof(HmmTracePair) * tp.size(), hipMemcpyHostToDevice, c->stream));
         GS_HIP_CHECK(hipMemcpyAsync(d_tprof.p, tprof.data(), sizeof(HmmTraceProf) * tprof.size(), hipMemcpyHostToDevice, c->stream));
-        for (const Block &b : blocks) {
+        for (const HmmPairBlock &b : blocks) {
             for (int cls = 0; cls < HMM_CLASSES; cls++) {
                 const auto k = hmm_kernels(cls).trace;
                 const size_t lds = hmm_lds_bytes(cls, HMM_TRACE);
@@ -1039,6 +1283,78 @@ static int hmm_trace_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const
                                                                                                         rl_dev, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev, max_dom,
                                                                                                         ndom_dev, dom_dev);
             GS_HIP_CHECK(hipGetLastError());
+        }
+        GS_HIP_CHECK(stream_wait(c));       // the lists are read by the copies until here, and the slots go back
+        return GS_OK;
+    }
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+// ---- posterior envelopes, host side (SPEC 13.4) ---------------------------------------------------------------------------------------------------
+// lens, prec, pprof: host copies that hmm_trace_check has passed under Forward's length limit; everything else device memory. Blocks of pairs in the caller's order, at most
+// max_block_rows kept rows (sum of L + 1) each, a block's pairs by class and profile, longest record first. A block is a Forward-with-rows and a Backward
+// launch per class that occurs, k_hmm_envelopes, and a k_hmm_env_score launch per class, all on c's stream, which is waited for at the end.
+static int hmm_env_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, const uint32_t *prec,
+                        const uint32_t *pprof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_dev, int32_t *bck_dev, uint32_t *nenv_dev,
+                        int32_t *env_dev, const uint64_t *row_off_dev, int32_t *out_rows_dev, int32_t *cont_rows_dev)
+{
+    const uint64_t cap = max_block_rows ? max_block_rows : HMM_ENV_DEFAULT_BLOCK_ROWS;
+    const uint64_t n_env_words = n_pairs * max_env * GS_HMM_ENV_WORDS, n_fill = std::max(n_pairs, n_env_words);
+    GS_REQUIRE(n_fill < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many envelope slots");
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_env_fill<<<(unsigned)((n_fill + 255) / 256), 256, 0, c->stream>>>(n_pairs, n_env_words, fwd_dev, bck_dev, nenv_dev, env_dev);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    const HmmPairBlocks pb = hmm_pair_blocks(db, lens, prec, pprof, n_pairs, cap, [&](uint64_t i) { return lens[prec[i]] + 1; });
+    const std::vector<HmmTracePair> &tp = pb.tp;
+    const std::vector<HmmTraceProf> &tprof = pb.tprof;
+    const std::vector<HmmPairBlock> &blocks = pb.blocks;
+    const uint64_t max_rows = pb.max_rows;
+    if (!blocks.empty()) {
+        PoolBuf d_tp(c, SL_HMME_PAIRS), d_tprof(c, SL_HMME_PROFS), d_frows(c, SL_HMME_FROWS), d_brows(c, SL_HMME_BROWS);
+        int rc;
+        if ((rc = d_tp.alloc(sizeof(HmmTracePair) * tp.size())) || (rc = d_tprof.alloc(sizeof(HmmTraceProf) * tprof.size())) || (rc = d_frows.alloc(sizeof(int4) * max_rows)) ||
+            (rc = d_brows.alloc(sizeof(int2) * max_rows)))
+            return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(d_tp.p, tp.data(), sizeof(HmmTracePair) * tp.size(), hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(d_tprof.p, tprof.data(), sizeof(HmmTraceProf) * tprof.size(), hipMemcpyHostToDevice, c->stream));
+        for (const HmmPairBlock &b : blocks) {
+            for (int cls = 0; cls < HMM_CLASSES; cls++) {
+                const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+                const uint32_t n_in = b.prof_start[cls + 1] - b.prof_start[cls];
+                const uint32_t wg = std::min<uint32_t>((b.max_cnt[cls] + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
+                const auto kf = hmm_kernels(cls).fwd_rows;
+                rc = hmm_launch_class(c, db->lds_set[HMM_FWD_ROWS][cls], kf, b.prof_start[cls], n_in, wg, lds, [&](dim3 grid, uint32_t first) {
+                    kf<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(),
+                                                            db->d_lse.as<uint16_t>(), aa_dev, rs_dev, rl_dev, d_frows.as<int4>(), fwd_dev);
+                });
+                if (rc) return rc;
+                const auto kb = hmm_kernels(cls).back;
+                rc = hmm_launch_class(c, db->lds_set[HMM_K_BACK][cls], kb, b.prof_start[cls], n_in, wg, lds, [&](dim3 grid, uint32_t first) {
+                    kb<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(),
+                                                            db->d_lse.as<uint16_t>(), aa_dev, rs_dev, rl_dev, d_brows.as<int2>(), bck_dev);
+                });
+                if (rc) return rc;
+            }
+            {
+                ProfScope ps(c, FAM_SEARCH);
+                k_hmm_envelopes<<<b.n, HMM_ENV_BLOCK, 0, c->stream>>>(d_tp.as<HmmTracePair>() + b.start, rl_dev, db->d_lse.as<uint16_t>(), d_frows.as<int4>(), d_brows.as<int2>(),
+                                                                       fwd_dev, max_env, nenv_dev, env_dev, row_off_dev, out_rows_dev, cont_rows_dev);
+                GS_HIP_CHECK(hipGetLastError());
+            }
+            for (int cls = 0; max_env && cls < HMM_CLASSES; cls++) {
+                const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+                const uint64_t slots = (uint64_t)b.max_cnt[cls] * max_env;
+                const uint32_t wg = (uint32_t)std::min<uint64_t>((slots + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
+                const auto ks = hmm_kernels(cls).env_score;
+                rc = hmm_launch_class(c, db->lds_set[HMM_K_ENV_SCORE][cls], ks, b.prof_start[cls], b.prof_start[cls + 1] - b.prof_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
+                    ks<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(),
+                                                            db->d_lse.as<uint16_t>(), aa_dev, rs_dev, rl_dev, max_env, nenv_dev, env_dev);
+                });
+                if (rc) return rc;
+            }
         }
         GS_HIP_CHECK(stream_wait(c));       // the lists are read by the copies until here, and the slots go back
         return GS_OK;
@@ -1427,6 +1743,85 @@ int gs_hmm_trace(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *re
     GS_HIP_CHECK(hipMemcpyAsync(raw_out, d_raw.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(n_dom_out, d_nd.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
     if (n_dom_bytes) GS_HIP_CHECK(hipMemcpyAsync(dom_out, d_dom.p, n_dom_bytes, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+int gs_hmm_envelopes_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                         const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_out_dev,
+                         int32_t *bck_out_dev, uint32_t *n_env_out_dev, int32_t *env_out_dev, const uint64_t *row_off_dev, int32_t *out_rows_dev, int32_t *cont_rows_dev)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_pairs == 0) return GS_OK;
+    GS_REQUIRE(pair_rec_dev && pair_prof_dev && fwd_out_dev && bck_out_dev && n_env_out_dev && (env_out_dev || max_env == 0), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec == 0 || (aa_dev && rec_start_dev && rec_len_dev), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(!row_off_dev == !out_rows_dev && !row_off_dev == !cont_rows_dev, GS_ERR_INVALID, "hmm: row_off, out_rows and cont_rows go together");
+    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
+    GS_CTX_LOCK(c);
+    std::vector<uint64_t> lens;
+    std::vector<uint32_t> prec(n_pairs), pprof(n_pairs);
+    GS_HIP_CHECK(hipMemcpyAsync(prec.data(), pair_rec_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(pprof.data(), pair_prof_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    int rc;
+    std::vector<uint64_t> ro(row_off_dev ? n_pairs + 1 : 0);
+    if (row_off_dev) GS_HIP_CHECK(hipMemcpyAsync(ro.data(), row_off_dev, 8 * (n_pairs + 1), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_trace_check(db, lens.data(), n_rec, prec.data(), pprof.data(), n_pairs, GS_HMM_FWD_MAX_L))) return rc;
+    if (row_off_dev)
+        for (uint64_t i = 0; i < n_pairs; i++)
+            GS_REQUIRE(ro[i] <= ro[i + 1] && (prec[i] == GS_HMM_NO_HIT || ro[i + 1] - ro[i] >= lens[prec[i]]), GS_ERR_INVALID,
+                       "hmm: row_off leaves pair %llu fewer words than its record has residues", (unsigned long long)i);
+    return hmm_env_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), prec.data(), pprof.data(), n_pairs, max_env, max_block_rows, fwd_out_dev, bck_out_dev,
+                        n_env_out_dev, env_out_dev, row_off_dev, out_rows_dev, cont_rows_dev);
+}
+
+int gs_hmm_envelopes(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                     const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_out, int32_t *bck_out, uint32_t *n_env_out,
+                     int32_t *env_out, const uint64_t *row_off, int32_t *out_rows, int32_t *cont_rows)
+{
+    using namespace gs;
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_pairs == 0) return GS_OK;
+    GS_REQUIRE(pair_rec && pair_prof && fwd_out && bck_out && n_env_out && (env_out || max_env == 0), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(n_rec == 0 || (rec_start && rec_len), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(!row_off == !out_rows && !row_off == !cont_rows, GS_ERR_INVALID, "hmm: row_off, out_rows and cont_rows go together");
+    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
+    int rc = hmm_trace_check(db, rec_len, n_rec, pair_rec, pair_prof, n_pairs, GS_HMM_FWD_MAX_L);
+    if (rc) return rc;
+    uint64_t n_bytes = 0;                       // of the records that a pair names: the others may be any length and are not staged
+    for (uint64_t i = 0; i < n_pairs; i++)
+        if (pair_rec[i] != GS_HMM_NO_HIT && rec_len[pair_rec[i]]) n_bytes = std::max(n_bytes, rec_start[pair_rec[i]] + rec_len[pair_rec[i]]);
+    if (row_off)                                // every listed pair's rows must fit between its offset and the next
+        for (uint64_t i = 0; i < n_pairs; i++)
+            GS_REQUIRE(row_off[i] <= row_off[i + 1] && (pair_rec[i] == GS_HMM_NO_HIT || row_off[i + 1] - row_off[i] >= rec_len[pair_rec[i]]), GS_ERR_INVALID,
+                       "hmm: row_off leaves pair %llu fewer words than its record has residues", (unsigned long long)i);
+    const uint64_t n_env_bytes = 4 * n_pairs * max_env * GS_HMM_ENV_WORDS, n_row_bytes = row_off ? 4 * row_off[n_pairs] : 0;
+    GS_CTX_LOCK(c);
+    PoolBuf d_aa(c, SL_HMMEB_AA), d_rs(c, SL_HMMEB_REC_START), d_rl(c, SL_HMMEB_REC_LEN), d_fwd(c, SL_HMMEB_FWD), d_bck(c, SL_HMMEB_BCK), d_ne(c, SL_HMMEB_NENV),
+        d_env(c, SL_HMMEB_ENV), d_ro(c, SL_HMMEB_ROW_OFF), d_out(c, SL_HMMEB_OUT), d_cont(c, SL_HMMEB_CONT);
+    if ((rc = hmm_stage_records(c, aa, n_bytes, rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_fwd.alloc(4 * n_pairs)) || (rc = d_bck.alloc(4 * n_pairs)) ||
+        (rc = d_ne.alloc(4 * n_pairs)) || (rc = d_env.alloc(n_env_bytes)))
+        return rc;
+    if (row_off) {
+        if ((rc = d_ro.alloc(8 * (n_pairs + 1))) || (rc = d_out.alloc(n_row_bytes)) || (rc = d_cont.alloc(n_row_bytes))) return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(d_ro.p, row_off, 8 * (n_pairs + 1), hipMemcpyHostToDevice, c->stream));
+        if (n_row_bytes) {                      // the rows of a pair that gets none keep what the caller's buffers hold
+            GS_HIP_CHECK(hipMemcpyAsync(d_out.p, out_rows, n_row_bytes, hipMemcpyHostToDevice, c->stream));
+            GS_HIP_CHECK(hipMemcpyAsync(d_cont.p, cont_rows, n_row_bytes, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    if ((rc = hmm_env_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, pair_rec, pair_prof, n_pairs, max_env, max_block_rows,
+                           d_fwd.as<int32_t>(), d_bck.as<int32_t>(), d_ne.as<uint32_t>(), d_env.as<int32_t>(), row_off ? d_ro.as<uint64_t>() : nullptr,
+                           row_off ? d_out.as<int32_t>() : nullptr, row_off ? d_cont.as<int32_t>() : nullptr)))
+        return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(bck_out, d_bck.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(n_env_out, d_ne.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+    if (n_env_bytes) GS_HIP_CHECK(hipMemcpyAsync(env_out, d_env.p, n_env_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (n_row_bytes) {
+        GS_HIP_CHECK(hipMemcpyAsync(out_rows, d_out.p, n_row_bytes, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(cont_rows, d_cont.p, n_row_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
     GS_HIP_CHECK(stream_wait(c));
     return GS_OK;
 }

@@ -82,6 +82,9 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* hmmsearch, trace-back: a block's pairs and their profiles' lists, its back-pointers and row specials, staging of the host form */                \
     X(HMMT_PAIRS) X(HMMT_PROFS) X(HMMT_PTR) X(HMMT_ROWS) X(HMMTB_AA) X(HMMTB_REC_START) X(HMMTB_REC_LEN) X(HMMTB_PAIR_PROF) X(HMMTB_RAW)       \
     X(HMMTB_NDOM) X(HMMTB_DOM)                                                                                                                        \
+    /* hmmsearch, posterior envelopes: a block's pairs and profile lists, its Forward and Backward rows, staging of the host form */                    \
+    X(HMME_PAIRS) X(HMME_PROFS) X(HMME_FROWS) X(HMME_BROWS) X(HMMEB_AA) X(HMMEB_REC_START) X(HMMEB_REC_LEN) X(HMMEB_FWD) X(HMMEB_BCK) X(HMMEB_NENV)     \
+    X(HMMEB_ENV) X(HMMEB_ROW_OFF) X(HMMEB_OUT) X(HMMEB_CONT)                                                                                          \
     /* orfs (gs_orf.hip): tile prefix of the records and the call's counters; per tile the last stop of each (strand, class) pair, then its kept ORFs,      \
        residues and long drops (each scanned in place); the partial results of those scans; staging of the host form */                                 \
     X(ORF_REC_TILES) X(ORF_META) X(ORF_STOPS) X(ORF_COUNTS) X(ORF_PARTIALS) X(ORFB_SEQ) X(ORFB_REC_START) X(ORFB_REC_LEN) X(ORFB_ORF) X(ORFB_AA)         \

@@ -383,6 +383,32 @@ int gs_hmm_trace_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const ui
                      const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells,
                      int32_t *raw_out_dev, uint32_t *n_dom_out_dev, int32_t *dom_out_dev);
 
+/* Backward scores and posterior envelopes (SPEC 13.4): where on the record the probability mass of the model sits, from the Forward and the Backward
+ * pass of a list of (record, profile) pairs, and what each such stretch scores on its own - integers only, both passes and the rule on the device.
+ * With out[i] = log2 P(x_i is emitted outside the core model) and cont[i] = log2 P(x_i outside, or a domain ends at row i), in units: a row is in iff
+ * out[i] <= -156 (occupancy >= 0.10); a run is a maximal stretch of in-rows in which every row but the last has cont[i] <= -156; a run is an envelope
+ * iff some row of it has out[i] <= -425 (occupancy >= 0.25). An envelope is GS_HMM_ENV_WORDS int32: i_from, i_to (1-based, inclusive), env_raw = the
+ * Forward raw score of the rows i_from .. i_to alone under the length model of the whole record, peak = the smallest out[i] of the envelope.
+ * No stochastic clustering (a run is one envelope), no null2, no alignment. Pairs in any order, repeats allowed.
+ * fwd_out[j] = what gs_hmm_search_forward writes for pair j; bck_out[j] = bN[0] - null, the same probability summed from the other end (it differs
+ * from fwd_out[j] by rounding alone); n_env_out[j] = the true number of envelopes; env_out[j][0 .. min(n_env, max_env)) = the first envelopes in
+ * sequence order, the other slots of the pair zeros (max_env = 0 with env_out = NULL is allowed). row_off (n_pairs + 1 words, optional, with out_rows
+ * and cont_rows): out[1 .. L] and cont[1 .. L] of pair j are written to out_rows / cont_rows from word row_off[j] on; row_off[j + 1] - row_off[j] >= L,
+ * else GS_ERR_INVALID; the words of a pair that gets no envelopes below are not written. A pair with pair_rec = GS_HMM_NO_HIT, an empty record or a
+ * record with a byte that is no residue: fwd = bck = GS_HMM_NO_SCORE, n_env = 0, zeroed slots. Any other pair_rec >= n_rec, or a pair_prof >= n_prof:
+ * GS_ERR_INVALID; a named record longer than GS_HMM_FWD_MAX_L: GS_ERR_UNSUPPORTED; both before anything is queued, nothing written (records that no
+ * pair names may be any length); a set of another context: GS_ERR_INVALID. max_block_rows bounds the kept rows (sum of L + 1 over the pairs of a
+ * block, 24 bytes each) alive at once; 0 = 2^25; a block always holds at least one pair; no output depends on it. Device form: every array device
+ * memory; the lengths, the pair list and row_off are read back once. */
+#define GS_HMM_ENV_WORDS 4u
+int gs_hmm_envelopes(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                     const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_out, int32_t *bck_out, uint32_t *n_env_out,
+                     int32_t *env_out, const uint64_t *row_off, int32_t *out_rows, int32_t *cont_rows);
+int gs_hmm_envelopes_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                         const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows,
+                         int32_t *fwd_out_dev, int32_t *bck_out_dev, uint32_t *n_env_out_dev, int32_t *env_out_dev, const uint64_t *row_off_dev,
+                         int32_t *out_rows_dev, int32_t *cont_rows_dev);
+
 /* ---------------------------------------------------------------------------------------------- */
 /* orfs (SPEC 14): stop-to-stop six-frame translation of packed nucleotide records on the device - the model-free way to feed hmmsearch from genomes.
  * It is NOT a gene caller and does not replace FragGeneScanRs: the ORF set is not a proteome and must not be given to the AA sketchers or superaai.

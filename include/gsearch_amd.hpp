@@ -300,6 +300,18 @@ public:
                            max_block_cells, t.raw.data(), t.n_dom.data(), t.dom.empty() ? nullptr : t.dom.data()));
         return t;
     }
+    // SPEC 13.4: Forward and Backward raw scores and the posterior envelopes of the pairs. n_env[j] the true number of envelopes,
+    // env[(j * max_env + d) * GS_HMM_ENV_WORDS ..] = i_from, i_to, env_raw, peak of the first max_env of them in sequence order (zeros behind them)
+    struct Envelopes { std::vector<int32_t> fwd, bck; std::vector<uint32_t> n_env; std::vector<int32_t> env; };
+    Envelopes envelopes(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len, const std::vector<uint32_t> &pair_rec,
+                        const std::vector<uint32_t> &pair_prof, uint32_t max_env = 8, uint64_t max_block_rows = 0) const
+    {
+        const size_t n = pair_rec.size();
+        Envelopes e{std::vector<int32_t>(n), std::vector<int32_t>(n), std::vector<uint32_t>(n), std::vector<int32_t>(n * max_env * GS_HMM_ENV_WORDS)};
+        check(gs_hmm_envelopes(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), pair_rec.data(), pair_prof.data(), n, max_env, max_block_rows,
+                               e.fwd.data(), e.bck.data(), e.n_env.data(), e.env.empty() ? nullptr : e.env.data(), nullptr, nullptr, nullptr));
+        return e;
+    }
     // the floor of profile p for a Viterbi P-value of filter_p (HMMER's F2 = 1e-3): INT32_MIN + 1 without STATS LOCAL VITERBI
     int32_t viterbi_floor(size_t profile, double filter_p = 1e-3) const
     {

@@ -30,11 +30,20 @@ composition) against 120 synthetic profiles with the node counts of the bacteria
   check         the Viterbi words of the filtered search against the unfiltered matrix wherever they ran, the selection against the MSV matrix and the
                 floors, and `check` sampled pairs of the MSV matrix against the restatement (tests/pyref_hmm_msv.py): the expected differences are 0
 
+With --posterior also (SPEC 13.4):
+  posterior     seconds of gs_hmm_envelopes_dev over ALL pairs with max_env = 2 (per block: Forward with rows, Backward, k_hmm_envelopes, the envelope
+                scores) and, alternating with it in the same rounds, of gs_hmm_search_forward_dev with every pair selected: that call is the parent
+                commit's code and the yardstick. Times of every round are kept, so the spread is in the log. The split between the four kernel
+                families comes from a kernel trace of one more run of this mode (rocprofv3 --kernel-trace --stats, in a run of its own), kept beside the
+                line in the log
+  check         fwd of every pair against the Forward matrix, |fwd - bck| against the bound of SPEC 13.4, and `check` sampled pairs (fwd, bck, n_env,
+                envelopes) against the restatement (tests/pyref_hmm_posterior.py): the expected differences are 0
+
 --dump PATH saves the downloaded matrices of the modes that ran as one .npz (the Viterbi scores; both Forward matrices; raw, n_dom and the domain
 words of trace_best and trace_all), so that two builds of the library (GS_LIB_PATH) can be compared word for word.
 
-usage: hmm_rate.py [--forward | --trace | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
-                   [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log | hmm_msv_rate.log]"""
+usage: hmm_rate.py [--forward | --trace | --posterior | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
+                   [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log | hmm_msv_rate.log | hmm_posterior_rate.log]"""
 import argparse
 import json
 import os
@@ -57,12 +66,13 @@ def main():
     ap.add_argument("--forward", action="store_true")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--msv", action="store_true")
+    ap.add_argument("--posterior", action="store_true")
     ap.add_argument("--parent-s", type=float, default=None)
     ap.add_argument("--log", default=None)
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     if a.log is None:
-        a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else ("hmm_trace_rate.log" if a.trace else ("hmm_msv_rate.log" if a.msv else "hmm_rate.log")))
+        a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else ("hmm_trace_rate.log" if a.trace else ("hmm_msv_rate.log" if a.msv else ("hmm_posterior_rate.log" if a.posterior else "hmm_rate.log"))))
     import gsearch_amd as G
     import pyref_hmm as R
     rng = np.random.default_rng(a.seed)
@@ -114,6 +124,8 @@ def main():
         trace_part(a, ctx, db, texts, recs, ptrs, d_rec, scores, cells, res, rng, dump)
     if a.msv:
         msv_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng, dump)
+    if a.posterior:
+        posterior_part(a, ctx, db, texts, recs, ptrs, d_score, cells, res, rng, dump)
     if a.dump:
         with open(a.dump, "wb") as f:
             np.savez(f, **dump)
@@ -168,6 +180,56 @@ def forward_part(a, ctx, db, texts, recs, ptrs, d_vit, vit, cells, res, rng, dum
     res["forward_check_pairs"], res["forward_check_differences"] = a.check, diff
     ctx.free(d_fwd)
     ctx.free(d_floor)
+
+
+def posterior_part(a, ctx, db, texts, recs, ptrs, d_vit, cells, res, rng, dump):
+    import pyref_hmm as R
+    import pyref_hmm_posterior as P
+    n_prof, max_env = len(db), 2
+    n = a.n * n_prof
+    pr, pp = np.repeat(np.arange(a.n, dtype=np.uint32), n_prof), np.tile(np.arange(n_prof, dtype=np.uint32), a.n)
+    d_pr, d_pp = ctx.alloc(pr.nbytes), ctx.alloc(pp.nbytes)
+    ctx.upload(d_pr, pr); ctx.upload(d_pp, pp)
+    d_fwd_all = ctx.alloc(4 * n)
+    bufs = [ctx.alloc(4 * n) for _ in range(3)] + [ctx.alloc(4 * n * max_env * 4)]
+
+    def timed(call):
+        ctx.sync()
+        t = time.perf_counter()
+        call()
+        ctx.sync()
+        return time.perf_counter() - t
+
+    runs = {"forward_all": lambda: db.search_forward_dev(ptrs[0], ptrs[1], ptrs[2], a.n, None, d_vit, d_fwd_all),
+            "posterior": lambda: db.envelopes_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, d_pp, n, max_env, *bufs)}
+    times = {k: [] for k in runs}
+    for it in range(a.repeat + 1):                               # the first round is the warm-up of both; the two alternate inside a round
+        for k, call in runs.items():
+            t = timed(call)
+            if it:
+                times[k].append(t)
+    fwd_all = ctx.download(d_fwd_all, (a.n, n_prof), np.int32)
+    fwd, bck = ctx.download(bufs[0], (n,), np.int32), ctx.download(bufs[1], (n,), np.int32)
+    ne, env = ctx.download(bufs[2], (n,), np.uint32), ctx.download(bufs[3], (n, max_env, 4), np.int32)
+    dump.update(posterior_fwd=fwd, posterior_bck=bck, posterior_n_env=ne, posterior_env=env)
+    for k, ts in times.items():
+        res[k + "_times_s"] = ts
+        res[k + "_min_s"], res[k + "_median_s"] = min(ts), float(np.median(ts))
+    res["forward_all_minus_viterbi_s"] = res["forward_all_min_s"] - res["search_s"]          # the call runs Viterbi in front of Forward
+    res["forward_cells_per_s"] = cells / res["forward_all_minus_viterbi_s"]
+    res["posterior_over_forward"] = res["posterior_min_s"] / res["forward_all_minus_viterbi_s"]
+    res["posterior_pairs"], res["envelopes"], res["pairs_with_more_than_2"] = n, int(ne.sum()), int((ne > max_env).sum())
+    res["fwd_differs_from_forward_matrix"] = int((fwd.reshape(a.n, n_prof) != fwd_all).sum())
+    res["largest_fwd_minus_bck"] = int(np.abs(fwd.astype(np.int64) - bck)[fwd != R.NO_SCORE].max())
+    diff = 0
+    for _ in range(a.check):
+        r, p = int(rng.integers(a.n)), int(rng.integers(n_prof))
+        want = P.envelope_pairs([R.parse_hmm(texts[p])[0]], recs, [r], [0], max_env)
+        j = r * n_prof + p
+        diff += int(not (fwd[j] == want[0][0] and bck[j] == want[1][0] and ne[j] == want[2][0] and np.array_equal(env[j], want[3][0])))
+    res["posterior_check_pairs"], res["posterior_check_differences"] = a.check, diff
+    for ptr in [d_pr, d_pp, d_fwd_all] + bufs:
+        ctx.free(ptr)
 
 
 def msv_part(a, ctx, db, texts, recs, ptrs, d_vit_all, vit_all, cells, res, rng, dump):
