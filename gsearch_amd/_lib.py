@@ -321,6 +321,8 @@ SYMBOLS = {
     "gs_debug_radix_sort_u64": (_i, [_vp, _vp, _u64, _i, _vp]),
     "gs_debug_run_lengths_u64": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
     "gs_debug_scan_u32": (_i, [_vp, _vp, _u64, _vp, _vp]),
+    "gs_debug_hamming_strided": (_i, [_vp, _i, _u32, _vp, _u64, _u64, _vp, _u64, _u64, _u32, _i, _vp, _u64, _vp]),
+    "gs_debug_hamming_blocks": (_i, [_vp, _i, _u32, _vp, _u64, _u64, _vp, _u64, _u64, _vp, _u32, _vp, _u64, _vp, _u64, _u32, _vp, _u64, _vp]),
 }
 
 _lib = None

@@ -240,6 +240,56 @@ def debug_scan(values, ctx=None):
     return out, int(total.value)
 
 
+_HAMMING_FORM_DTYPE = (np.dtype(np.float32), np.dtype(np.uint32), np.dtype(np.uint16))
+
+
+def _strided_rows(a, name, dtype):
+    """a C-contiguous 2-D array of padded rows: of uint32, uint64 or float32 elements (dtype None), or of uint32 words that hold elements of `dtype`
+    (a pitch that is no whole number of 8-byte elements can only be written so). Returns (array, kind, row pitch in bytes)."""
+    dt = np.dtype(a.dtype if dtype is None else dtype) if isinstance(a, np.ndarray) else None
+    if not (dt in DTYPE_KIND and dt != np.uint16 and a.ndim == 2 and a.flags.c_contiguous and (dtype is None or a.dtype == np.uint32)):
+        raise ValueError("%s: a C-contiguous 2-D array of uint32, uint64 or float32 rows, or of uint32 words with dtype= given" % name)
+    return a, DTYPE_KIND[dt], a.shape[1] * a.dtype.itemsize
+
+
+def debug_hamming_strided(q, c, m, out, form, shift_bytes=0, dtype=None, ctx=None):
+    """debugging, not for production use: the dense DistHamming driver of gs_hamming.hip on host rows (gs_debug_hamming_strided). q, c: 2-D arrays of one
+    dtype (uint32, uint64, float32) whose rows are the padded rows - the first m columns count, the row pitch is the array's width - or, with dtype
+    given, arrays of uint32 words that hold such rows. out: (nq, ld_out)
+    array of float32 (form 0, distances), uint32 (form 1, counts) or uint16 (form 2), written in place in its first nc columns. Returns the number of
+    K parts the call used."""
+    ctx = ctx or default_context()
+    q, kind, sq = _strided_rows(q, "debug_hamming_strided", dtype)
+    c, kind_c, sc = _strided_rows(c, "debug_hamming_strided", dtype)
+    if kind != kind_c or not (0 <= int(form) <= 2):
+        raise ValueError("debug_hamming_strided: q and c of one dtype, form 0, 1 or 2")
+    if not (isinstance(out, np.ndarray) and out.ndim == 2 and out.flags.c_contiguous and out.dtype == _HAMMING_FORM_DTYPE[form] and out.shape[0] == q.shape[0]):
+        raise ValueError("debug_hamming_strided: out must be a C-contiguous (nq, ld_out) array of the form's dtype")
+    parts = C.c_uint32(0)
+    check(ctx.L.gs_debug_hamming_strided(ctx.h, kind, int(m), _p(q), q.shape[0], sq, _p(c), c.shape[0], sc, int(shift_bytes), int(form), _p(out), out.shape[1],
+                                         C.byref(parts)))
+    return int(parts.value)
+
+
+def debug_hamming_blocks(q, c, m, items, qlist, clist, n_thin, out16, dtype=None, ctx=None):
+    """debugging, not for production use: the work-list DistHamming driver of gs_hamming.hip on host rows (gs_debug_hamming_blocks). q, c as for
+    debug_hamming_strided; items: (n, 4) uint32 {first entry in qlist, query rows, first entry in clist, candidate rows}; out16: (rows of q, ld_out) uint16,
+    written in place in the cells the items name. Returns the number of K parts of the tile kernel's run."""
+    ctx = ctx or default_context()
+    q, kind, sq = _strided_rows(q, "debug_hamming_blocks", dtype)
+    c, kind_c, sc = _strided_rows(c, "debug_hamming_blocks", dtype)
+    items = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1, 4)
+    qlist, clist = np.ascontiguousarray(qlist, dtype=np.uint32), np.ascontiguousarray(clist, dtype=np.uint32)
+    if kind != kind_c:
+        raise ValueError("debug_hamming_blocks: q and c of one dtype")
+    if not (isinstance(out16, np.ndarray) and out16.ndim == 2 and out16.flags.c_contiguous and out16.dtype == np.uint16 and out16.shape[0] == q.shape[0]):
+        raise ValueError("debug_hamming_blocks: out16 must be a C-contiguous (rows of q, ld_out) uint16 array")
+    parts = C.c_uint32(0)
+    check(ctx.L.gs_debug_hamming_blocks(ctx.h, kind, int(m), _p(q), q.shape[0], sq, _p(c), c.shape[0], sc, _p(items), items.shape[0], _p(qlist), qlist.size,
+                                        _p(clist), clist.size, int(n_thin), _p(out16), out16.shape[1], C.byref(parts)))
+    return int(parts.value)
+
+
 def default_context():
     global _default_ctx
     if _default_ctx is None:

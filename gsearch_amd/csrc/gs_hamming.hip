@@ -7,6 +7,7 @@
 //  * k_hamming_pairs: one wavefront per (a,b) pair, 16-byte coalesced row reads, v_cmp + ballot/popcount.
 #include <algorithm>
 #include "gs_internal.hpp"
+#include "gs_hamming_split.hpp"
 #include <type_traits>
 
 namespace gs {
@@ -29,8 +30,7 @@ __device__ __forceinline__ uint32_t word_ne(uint32_t a, uint32_t b)
 // what bounds the kernel (it reads every candidate word once per 128 queries, so HBM traffic is ~1/128 of the
 // algorithmic bytes). Lane (tx,ty) owns query rows ty+16i and candidate rows tx+16j: with the 33-word LDS row
 // pitch every ds_read_b32 of a wavefront is conflict-free (distinct banks across tx, broadcast across ty).
-constexpr int HT = 128;     // tile edge (queries and candidates)
-constexpr int HKW = 32;     // words per K-chunk
+// (HT = 128, the tile edge, and HKW = 32, the words per K-chunk: gs_hamming_split.hpp)
 constexpr int HP = HKW + 1; // LDS row pitch in words
 
 // one query value against 8 candidate values: 8 x (v_cmp_ne ; v_addc_co). A single asm statement so that hipcc does
@@ -181,8 +181,7 @@ __global__ __launch_bounds__(256) void k_hamming_qxc(const uint32_t *__restrict_
 // VALU instructions); here nothing goes through LDS: a wavefront takes HTR candidate rows, lane l the words 4 l .. 4 l + 3 of every 256-word step of
 // those rows (one 16-byte load each, coalesced) and of each query row (the cluster's <= 16 rows: re-read by every pass, L2-resident), 2 VALU instructions per
 // (query, candidate) word pair into per-lane counters, one wavefront reduction at the end. 4-byte elements with 16-byte aligned rows only (hamming_blocks).
-constexpr int HTQ = 16;     // query rows of a thin item at most
-constexpr int HTR = 4;      // candidate rows per wavefront
+// (HTQ = 16 query rows of a thin item at most, HTR = 4 candidate rows per wavefront: gs_hamming_split.hpp)
 constexpr int HTS = HT / (4 * HTR);     // workgroups per item
 #define GS_CMP4(OP)                                                                                                   \
     asm volatile(OP " vcc, %4, %5\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"                                           \
@@ -281,8 +280,9 @@ __global__ __launch_bounds__(256) void k_hamming_pairs(const uint32_t *__restric
 }
 
 int hamming_qxc_strided(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq, uint64_t strideQ_bytes, const void *C, uint64_t nc,
-                        uint64_t strideC_bytes, float *out, uint32_t *out_cnt, uint16_t *out_cnt16, uint64_t ld_out)
+                        uint64_t strideC_bytes, float *out, uint32_t *out_cnt, uint16_t *out_cnt16, uint64_t ld_out, uint32_t *parts_out)
 {
+    if (parts_out) *parts_out = 1;
     GS_REQUIRE(c && m > 0, GS_ERR_INVALID, "bad argument");
     GS_REQUIRE(kind == GS_KIND_F32 || kind == GS_KIND_U32 || kind == GS_KIND_U64, GS_ERR_UNSUPPORTED, "DistHamming kind %d not on the device path", kind);
     if (nq == 0 || nc == 0) return GS_OK;
@@ -293,14 +293,15 @@ int hamming_qxc_strided(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t
     // few tiles (e.g. the batch-mates matrix of an insert): split the rows over blockIdx.z so the whole chip works on them
     uint32_t ksplit_words = 0;
     const uint64_t roww_all = (uint64_t)m * (kind == GS_KIND_U64 ? 2 : 1);
-    if (out_cnt && (uint64_t)grid.x * grid.y * 2 <= (uint64_t)c->n_cu && roww_all >= 8 * HKW) {
-        uint32_t nz = (uint32_t)std::min<uint64_t>((uint64_t)c->n_cu * 2 / ((uint64_t)grid.x * grid.y), roww_all / (4 * HKW));
-        if (nz > 1) {
-            ksplit_words = (uint32_t)(((roww_all + nz - 1) / nz + HKW - 1) / HKW * HKW);
-            grid.z = (uint32_t)((roww_all + ksplit_words - 1) / ksplit_words);
+    if (out_cnt) {
+        const HammingSplit sp = hamming_split_tiles((uint64_t)c->n_cu, (uint64_t)grid.x * grid.y, roww_all);       // (the rule: gs_hamming_split.hpp)
+        if (sp.ksplit_words) {
+            ksplit_words = sp.ksplit_words;
+            grid.z = sp.parts;
             GS_HIP_CHECK(hipMemset2DAsync(out_cnt, ld_out * 4, 0, nc * 4, nq, c->stream));
         }
     }
+    if (parts_out) *parts_out = grid.z;
     GS_REQUIRE(grid.y <= 65535, GS_ERR_INVALID, "too many candidate rows for one call (max %d)", 65535 * HT);
     ProfScope ps(c, FAM_HAMMING);
     const uint64_t sq = strideQ_bytes / 4, sc = strideC_bytes / 4;
@@ -326,8 +327,9 @@ __global__ __launch_bounds__(256) void k_blocks_set(const uint4 *__restrict__ it
 // the tiles of a work list (see k_hamming_qxc IDX): n_items x {qlist offset, rows (<= 128), clist offset, rows (<= 128)}, all in device memory
 // n_thin: the first n_thin items have at most HTQ (16) query rows - they go to k_hamming_thin where it applies (4-byte elements, 16-byte aligned rows)
 int hamming_blocks(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t strideQ_bytes, const void *C, uint64_t strideC_bytes, const void *items_dev,
-                   uint32_t n_items, const uint32_t *qlist_dev, const uint32_t *clist_dev, uint16_t *out_cnt16, uint64_t ld_out, uint32_t n_thin)
+                   uint32_t n_items, const uint32_t *qlist_dev, const uint32_t *clist_dev, uint16_t *out_cnt16, uint64_t ld_out, uint32_t n_thin, uint32_t *parts_out)
 {
+    if (parts_out) *parts_out = 1;
     if (n_items == 0) return GS_OK;
     GS_REQUIRE(kind == GS_KIND_F32 || kind == GS_KIND_U32 || kind == GS_KIND_U64, GS_ERR_UNSUPPORTED, "DistHamming kind %d not on the device path", kind);
     GS_REQUIRE(n_thin <= n_items, GS_ERR_INVALID, "bad argument");
@@ -348,14 +350,13 @@ int hamming_blocks(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t stri
     // few tiles (thirty species in a batch = thirty tiles): the rows are split over blockIdx.z so that the whole chip works on them
     uint32_t ksplit_words = 0;
     const uint64_t roww_all = (uint64_t)m * (kind == GS_KIND_U64 ? 2 : 1);
-    if ((uint64_t)n_items * 2 <= (uint64_t)c->n_cu * 2 && roww_all >= 8 * HKW) {
-        const uint32_t nz = (uint32_t)std::min<uint64_t>((uint64_t)c->n_cu * 4 / n_items, roww_all / (4 * HKW));
-        if (nz > 1) {
-            ksplit_words = (uint32_t)(((roww_all + nz - 1) / nz + HKW - 1) / HKW * HKW);
-            grid.z = (uint32_t)((roww_all + ksplit_words - 1) / ksplit_words);
-            hipLaunchKernelGGL(k_blocks_set, dim3(n_items), dim3(256), 0, c->stream, (const uint4 *)items_dev, qlist_dev, clist_dev, out_cnt16, ld_out, m);
-        }
+    const HammingSplit sp = hamming_split_items((uint64_t)c->n_cu, n_items, roww_all);       // (the rule: gs_hamming_split.hpp)
+    if (sp.ksplit_words) {
+        ksplit_words = sp.ksplit_words;
+        grid.z = sp.parts;
+        hipLaunchKernelGGL(k_blocks_set, dim3(n_items), dim3(256), 0, c->stream, (const uint4 *)items_dev, qlist_dev, clist_dev, out_cnt16, ld_out, m);
     }
+    if (parts_out) *parts_out = grid.z;
 #define GS_LAUNCH_BLK(K, V) hipLaunchKernelGGL((k_hamming_qxc<K, V, true>), grid, block, 0, c->stream, (const uint32_t *)Q, (uint64_t)0, sq, (const uint32_t *)C, (uint64_t)0, sc, m, (float *)nullptr, (uint32_t *)nullptr, out_cnt16, ld_out, ksplit_words, (const uint4 *)items_dev, qlist_dev, clist_dev)
     if (kind == GS_KIND_F32) { if (vec4) GS_LAUNCH_BLK(GS_KIND_F32, true); else GS_LAUNCH_BLK(GS_KIND_F32, false); }
     else if (kind == GS_KIND_U32) { if (vec4) GS_LAUNCH_BLK(GS_KIND_U32, true); else GS_LAUNCH_BLK(GS_KIND_U32, false); }
@@ -498,6 +499,95 @@ int gs_hamming_pairs(gs_ctx *c, int kind, uint32_t m, const void *A, uint64_t na
     GS_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GS_OK;
     });
+}
+
+/* The two host drivers of the compare kernels behind host pointers, exposed for parity tests against numpy (tests/test_gpu_hamming.py); not for
+ * production use. Each call stages its operands in slots of its own, runs the driver on the context's stream exactly as its callers do, waits, and
+ * copies the whole output back - the output is uploaded first, so what the kernels leave alone comes back as the caller set it. */
+int gs_debug_hamming_strided(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq, uint64_t strideQ_bytes, const void *C, uint64_t nc,
+                             uint64_t strideC_bytes, uint32_t shift_bytes, int form, void *out, uint64_t ld_out, uint32_t *parts_out)
+{
+    GS_REQUIRE(c && parts_out && m > 0, GS_ERR_INVALID, "bad argument");
+    GS_REQUIRE(kind == GS_KIND_F32 || kind == GS_KIND_U32 || kind == GS_KIND_U64, GS_ERR_UNSUPPORTED, "DistHamming kind %d not on the device path", kind);
+    GS_REQUIRE(form >= 0 && form <= 2, GS_ERR_INVALID, "gs_debug_hamming_strided: form %d outside 0..2", form);
+    const uint64_t eb = gs::kind_bytes(kind), row = eb * m;
+    GS_REQUIRE(shift_bytes < 256 && shift_bytes % eb == 0, GS_ERR_INVALID, "gs_debug_hamming_strided: shift of %u bytes (a multiple of the element size below 256)", shift_bytes);
+    GS_REQUIRE(strideQ_bytes >= row && strideC_bytes >= row && strideQ_bytes % 4 == 0 && strideC_bytes % 4 == 0, GS_ERR_INVALID,
+               "gs_debug_hamming_strided: row strides must hold a row and be multiples of 4");
+    GS_REQUIRE(form != 2 || m <= 65535, GS_ERR_INVALID, "16-bit counts need m <= 65535");
+    // (rows below 2^24 and pitches below 2^32: no product below wraps; an operand of more than 4 GB is not what this call is for)
+    GS_REQUIRE(nq < ((uint64_t)1 << 24) && nc < ((uint64_t)1 << 24) && ld_out < ((uint64_t)1 << 24) && strideQ_bytes < ((uint64_t)1 << 32) &&
+                   strideC_bytes < ((uint64_t)1 << 32) && nq * strideQ_bytes <= ((uint64_t)1 << 32) && nc * strideC_bytes <= ((uint64_t)1 << 32),
+               GS_ERR_UNSUPPORTED, "gs_debug_hamming_strided: too large");
+    *parts_out = 1;
+    if (nq == 0 || nc == 0) return GS_OK;
+    GS_REQUIRE(Q && C && out, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(ld_out >= nc, GS_ERR_INVALID, "gs_debug_hamming_strided: output pitch %llu below %llu columns", (unsigned long long)ld_out, (unsigned long long)nc);
+    GS_CTX_LOCK(c);
+    const size_t obytes = (size_t)(form == 2 ? 2 : 4) * nq * ld_out;
+    gs::PoolBuf dq(c, gs::SL_DBG_HAM_Q), dc(c, gs::SL_DBG_HAM_C), dout(c, gs::SL_DBG_HAM_OUT);
+    int rc;
+    if ((rc = dq.alloc(nq * strideQ_bytes + 256)) || (rc = dc.alloc(nc * strideC_bytes + 256)) || (rc = dout.alloc(obytes))) return rc;
+    uint8_t *pq = (uint8_t *)dq.p + shift_bytes, *pc = (uint8_t *)dc.p + shift_bytes;
+    GS_HIP_CHECK(hipMemcpyAsync(pq, Q, nq * strideQ_bytes, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(pc, C, nc * strideC_bytes, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(dout.p, out, obytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = gs::hamming_qxc_strided(c, kind, m, pq, nq, strideQ_bytes, pc, nc, strideC_bytes, form == 0 ? dout.as<float>() : nullptr,
+                                      form == 1 ? dout.as<uint32_t>() : nullptr, form == 2 ? dout.as<uint16_t>() : nullptr, ld_out, parts_out)))
+        return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(out, dout.p, obytes, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(gs::stream_wait(c));
+    return GS_OK;
+}
+
+int gs_debug_hamming_blocks(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq_rows, uint64_t strideQ_bytes, const void *C, uint64_t nc_rows,
+                            uint64_t strideC_bytes, const uint32_t *items, uint32_t n_items, const uint32_t *qlist, uint64_t n_qlist, const uint32_t *clist,
+                            uint64_t n_clist, uint32_t n_thin, uint16_t *out16, uint64_t ld_out, uint32_t *parts_out)
+{
+    GS_REQUIRE(c && parts_out && m > 0, GS_ERR_INVALID, "bad argument");
+    GS_REQUIRE(kind == GS_KIND_F32 || kind == GS_KIND_U32 || kind == GS_KIND_U64, GS_ERR_UNSUPPORTED, "DistHamming kind %d not on the device path", kind);
+    const uint64_t row = gs::kind_bytes(kind) * (uint64_t)m;
+    GS_REQUIRE(m <= 65535, GS_ERR_INVALID, "16-bit counts need m <= 65535");
+    GS_REQUIRE(n_thin <= n_items, GS_ERR_INVALID, "gs_debug_hamming_blocks: %u thin items of %u", n_thin, n_items);
+    GS_REQUIRE(strideQ_bytes >= row && strideC_bytes >= row && strideQ_bytes % 4 == 0 && strideC_bytes % 4 == 0, GS_ERR_INVALID,
+               "gs_debug_hamming_blocks: row strides must hold a row and be multiples of 4");
+    GS_REQUIRE(nq_rows < ((uint64_t)1 << 24) && nc_rows < ((uint64_t)1 << 24) && ld_out < ((uint64_t)1 << 24) && n_qlist < ((uint64_t)1 << 24) &&
+                   n_clist < ((uint64_t)1 << 24) && strideQ_bytes < ((uint64_t)1 << 32) && strideC_bytes < ((uint64_t)1 << 32) &&
+                   nq_rows * strideQ_bytes <= ((uint64_t)1 << 32) && nc_rows * strideC_bytes <= ((uint64_t)1 << 32),      // (as in gs_debug_hamming_strided: nothing below wraps)
+               GS_ERR_UNSUPPORTED, "gs_debug_hamming_blocks: too large");
+    *parts_out = 1;
+    if (n_items == 0) return GS_OK;
+    GS_REQUIRE(Q && C && items && qlist && clist && out16, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(ld_out >= nc_rows, GS_ERR_INVALID, "gs_debug_hamming_blocks: output pitch %llu below %llu columns", (unsigned long long)ld_out, (unsigned long long)nc_rows);
+    // what hamming_blocks takes on trust from its caller
+    for (uint64_t i = 0; i < n_qlist; i++) GS_REQUIRE(qlist[i] < nq_rows, GS_ERR_INVALID, "gs_debug_hamming_blocks: qlist[%llu] is no query row", (unsigned long long)i);
+    for (uint64_t i = 0; i < n_clist; i++) GS_REQUIRE(clist[i] < nc_rows, GS_ERR_INVALID, "gs_debug_hamming_blocks: clist[%llu] is no candidate row", (unsigned long long)i);
+    for (uint32_t i = 0; i < n_items; i++) {
+        const uint32_t *it = items + 4 * (size_t)i;
+        GS_REQUIRE(it[1] >= 1 && it[1] <= (uint32_t)gs::HT && it[3] >= 1 && it[3] <= (uint32_t)gs::HT, GS_ERR_INVALID, "gs_debug_hamming_blocks: item %u is not 1..%d rows on each side", i, gs::HT);
+        GS_REQUIRE((uint64_t)it[0] + it[1] <= n_qlist && (uint64_t)it[2] + it[3] <= n_clist, GS_ERR_INVALID, "gs_debug_hamming_blocks: item %u leaves its lists", i);
+        GS_REQUIRE(i >= n_thin || it[1] <= (uint32_t)gs::HTQ, GS_ERR_INVALID, "gs_debug_hamming_blocks: thin item %u has more than %d query rows", i, gs::HTQ);
+    }
+    GS_CTX_LOCK(c);
+    const size_t obytes = (size_t)2 * nq_rows * ld_out;
+    gs::PoolBuf dq(c, gs::SL_DBG_HAMB_Q), dc(c, gs::SL_DBG_HAMB_C), dit(c, gs::SL_DBG_HAMB_ITEMS), dql(c, gs::SL_DBG_HAMB_QLIST), dcl(c, gs::SL_DBG_HAMB_CLIST),
+        dout(c, gs::SL_DBG_HAMB_OUT);
+    int rc;
+    if ((rc = dq.alloc(nq_rows * strideQ_bytes)) || (rc = dc.alloc(nc_rows * strideC_bytes)) || (rc = dit.alloc((size_t)16 * n_items)) || (rc = dql.alloc(4 * n_qlist)) ||
+        (rc = dcl.alloc(4 * n_clist)) || (rc = dout.alloc(gs::round_up(obytes, 4))))      // (the K-split reaches a cell through its 32-bit container)
+        return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(dq.p, Q, nq_rows * strideQ_bytes, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(dc.p, C, nc_rows * strideC_bytes, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(dit.p, items, (size_t)16 * n_items, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(dql.p, qlist, 4 * n_qlist, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(dcl.p, clist, 4 * n_clist, hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(dout.p, out16, obytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = gs::hamming_blocks(c, kind, m, dq.p, strideQ_bytes, dc.p, strideC_bytes, dit.p, n_items, dql.as<uint32_t>(), dcl.as<uint32_t>(), dout.as<uint16_t>(), ld_out,
+                                 n_thin, parts_out)))
+        return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(out16, dout.p, obytes, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(gs::stream_wait(c));
+    return GS_OK;
 }
 
 }  // extern "C"

@@ -130,8 +130,9 @@ struct ProfScope {   // brackets one kernel launch with events when profiling is
 
 // dense Q x C DistHamming tile kernel with arbitrary row strides (bytes); writes exactly one of: f32 distances (out),
 // 32-bit mismatch counts (out_cnt), 16-bit mismatch counts (out_cnt16); ld_out = output row pitch in elements (0 -> nc).
+// *parts_out (optional): the number of parts the row words were split into over blockIdx.z (gs_hamming_split.hpp); 1 = no split
 int hamming_qxc_strided(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq, uint64_t strideQ_bytes, const void *C, uint64_t nc,
-                        uint64_t strideC_bytes, float *out, uint32_t *out_cnt, uint16_t *out_cnt16, uint64_t ld_out);
+                        uint64_t strideC_bytes, float *out, uint32_t *out_cnt, uint16_t *out_cnt16, uint64_t ld_out, uint32_t *parts_out = nullptr);
 
 int widen_u16_rows(gs_ctx *c, const void *src_dev, uint64_t nrows, uint32_t m, void *dst_dev, uint64_t dst_stride_bytes);
 int narrow_u16_rows(gs_ctx *c, const void *src_dev, uint64_t src_stride_bytes, uint64_t nrows, uint32_t m, void *dst_dev);
@@ -148,7 +149,8 @@ int match_join_counts(gs_ctx *c, int kind, uint32_t m, const void *qrows, uint64
                       uint16_t *out16, uint64_t ld, DevBuf *scratch, int *declined = nullptr, unsigned long long *stats = nullptr, bool init = true, uint64_t col0 = 0,
                       const void *rows = nullptr, uint64_t rstride = 0);
 int hamming_blocks(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t strideQ_bytes, const void *C, uint64_t strideC_bytes, const void *items_dev,
-                   uint32_t n_items, const uint32_t *qlist_dev, const uint32_t *clist_dev, uint16_t *out_cnt16, uint64_t ld_out, uint32_t n_thin = 0);
+                   uint32_t n_items, const uint32_t *qlist_dev, const uint32_t *clist_dev, uint16_t *out_cnt16, uint64_t ld_out, uint32_t n_thin = 0,
+                   uint32_t *parts_out = nullptr);       // (*parts_out as for hamming_qxc_strided: the parts of the tile kernel's run over the items the thin kernel left)
 int rows_to_cols(gs_ctx *c, int kind, uint32_t m, const void *rows, uint64_t stride, uint64_t nrows, void *cols, uint64_t colcap, uint64_t first);
 
 // gs_knn.hip: the k smallest (count, node) keys of each of nrows count rows (n entries at leading dimension ld, 16-byte aligned), keeping

@@ -13,6 +13,7 @@
 #include <chrono>
 #include <vector>
 #include "gs_internal.hpp"
+#include "gs_hamming_split.hpp"
 
 namespace gs {
 
@@ -76,7 +77,7 @@ constexpr int JU = 4;             // database values in flight per lane
 constexpr int JP_MAX_LOG2 = 13;   // largest table: 8192 entries (64 KB for 4-byte keys, 96 KB for 8-byte keys)
 constexpr int JQ_MAX = 3276;      // queries per join call: load factor <= 0.4
 constexpr int JB_LOG2 = 16;       // bits of the pre-filter bitmap (8 KB)
-constexpr uint32_t HTILE = 128;   // edge of the compare tile kernel's tiles (gs_hamming.hip HT)
+constexpr uint32_t HTILE = HT;    // edge of the compare tile kernel's tiles (gs_hamming_split.hpp)
 
 __device__ __forceinline__ uint32_t join_hash(uint32_t k) { return k * 0x9E3779B1u; }
 __device__ __forceinline__ uint32_t join_hash(uint64_t k) { return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 32); }
@@ -998,7 +999,7 @@ static int join_impl(gs_ctx *c, uint32_t m, const uint8_t *qrows, uint64_t qstri
         for (uint32_t k = 1; k <= K; k++)
             for (uint32_t a = cl_lo[k]; a < cl_lo[k + 1]; a += HTILE) {
                 const uint32_t qr = std::min<uint32_t>(HTILE, cl_lo[k + 1] - a);
-                if ((qr <= 16) != (pass == 0)) continue;
+                if ((qr <= (uint32_t)HTQ) != (pass == 0)) continue;
                 for (uint32_t b = ce_lo[k]; b < ce_lo[k + 1]; b += HTILE) {
                     tiles.push_back(make_uint4(a, qr, b, std::min<uint32_t>(HTILE, ce_lo[k + 1] - b)));
                     n_thin += pass == 0;

@@ -103,7 +103,10 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* gs_radix.hip behind host pointers (gs_debug_radix_sort_u64, gs_debug_run_lengths_u64, gs_debug_scan_u32; the suite only): the keys, their second \
        buffer and the radix counts of a sort; the sorted keys, runs, lengths, head positions, head counts and run counter; the values and their sum */  \
     X(DBG_SORT_KEYS) X(DBG_SORT_ALT) X(DBG_SORT_RADIX) X(DBG_RLE_SORTED) X(DBG_RLE_UNIQ) X(DBG_RLE_LEN) X(DBG_RLE_POS) X(DBG_RLE_RADIX) X(DBG_RLE_NRUNS) \
-    X(DBG_SCAN_VALS) X(DBG_SCAN_TOTAL)
+    X(DBG_SCAN_VALS) X(DBG_SCAN_TOTAL)                                                                                                                 \
+    /* gs_hamming.hip behind host pointers (gs_debug_hamming_strided, gs_debug_hamming_blocks; the suite only): both operands and the output of the     \
+       dense form; both operands, the items, the two row lists and the output of the work-list form */                                                  \
+    X(DBG_HAM_Q) X(DBG_HAM_C) X(DBG_HAM_OUT) X(DBG_HAMB_Q) X(DBG_HAMB_C) X(DBG_HAMB_ITEMS) X(DBG_HAMB_QLIST) X(DBG_HAMB_CLIST) X(DBG_HAMB_OUT)
 
 enum ScratchSlot : int {
 #define X(name) SL_##name,

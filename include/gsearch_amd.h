@@ -909,6 +909,31 @@ int gs_index_debug_fill_scratch(gs_index *, int byte);
 int gs_debug_radix_sort_u64(gs_ctx *c, const uint64_t *keys, uint64_t n, int endbit, uint64_t *out);
 int gs_debug_run_lengths_u64(gs_ctx *c, const uint64_t *sorted, uint64_t n, uint64_t *uniq, uint32_t *len, uint64_t *n_runs_out);
 int gs_debug_scan_u32(gs_ctx *c, const uint32_t *in, uint64_t n, uint32_t *out, uint32_t *total_out);
+/* Debugging (tests only, not for production use): the two host drivers of the DistHamming compare kernels (gs_hamming.hip), which produce every distance
+ * of the library and are otherwise reached only through the index, exposed for parity tests against numpy (tests/test_gpu_hamming.py). All pointers are
+ * HOST pointers: each call stages to the device, runs the driver on the context's stream exactly as its callers do, waits, and copies back. kind is
+ * GS_KIND_F32, GS_KIND_U32 or GS_KIND_U64 (anything else: GS_ERR_UNSUPPORTED); row strides are in bytes, hold at least a row of m elements and are
+ * multiples of 4; the bytes of a row beyond its m elements may hold anything. A null context, operand or parts_out, m = 0 or a bad stride:
+ * GS_ERR_INVALID; a row count, list length or output pitch of 2^24 or more, a row stride of 2^32
+ * bytes or more, or an operand of more than 2^32 bytes (rows x stride): GS_ERR_UNSUPPORTED. *parts_out = the number of parts the row words were split into over the grid's third dimension (1 = no split).
+ * gs_debug_hamming_strided: the dense form. Q: nq rows at strideQ_bytes, C: nc rows at strideC_bytes (buffers of nq * strideQ_bytes and
+ *   nc * strideC_bytes bytes). shift_bytes (a multiple of the element size, below 256, else GS_ERR_INVALID): both device copies start that many bytes
+ *   behind a 256-byte boundary. form 0: out[q * ld_out + e] = (float)count / (float)m (f32), form 1: the mismatch count as u32, form 2: as u16
+ *   (m <= 65535); another form, or ld_out < nc: GS_ERR_INVALID. out holds nq * ld_out elements of the form's type; it is uploaded before the call and
+ *   downloaded after it, so the cells with a column from nc on come back as the caller set them. nq = 0 or nc = 0: GS_OK, *parts_out = 1, nothing
+ *   else is written.
+ * gs_debug_hamming_blocks: the work-list form. items: n_items x {first entry in qlist, query rows, first entry in clist, candidate rows} (u32); item i
+ *   writes out16[qlist[a] * ld_out + clist[b]] = the mismatch count of query row qlist[a] and candidate row clist[b] for every a, b of its two
+ *   ranges; no two items may name the same cell. The first n_thin items go to the thin kernel where it applies. out16: nq_rows x ld_out u16, uploaded
+ *   and downloaded like `out` above: every cell that no item names comes back as the caller set it. What the driver takes on trust is checked
+ *   here, GS_ERR_INVALID otherwise: item ranges inside the lists, list entries below nq_rows / nc_rows, 1..128 rows on each side of an item, at
+ *   most 16 query rows in each of the first n_thin items, n_thin <= n_items, m <= 65535, ld_out >= nc_rows. n_items = 0: GS_OK, *parts_out = 1,
+ *   nothing else is written. */
+int gs_debug_hamming_strided(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq, uint64_t strideQ_bytes, const void *C, uint64_t nc,
+                             uint64_t strideC_bytes, uint32_t shift_bytes, int form, void *out, uint64_t ld_out, uint32_t *parts_out);
+int gs_debug_hamming_blocks(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t nq_rows, uint64_t strideQ_bytes, const void *C, uint64_t nc_rows,
+                            uint64_t strideC_bytes, const uint32_t *items, uint32_t n_items, const uint32_t *qlist, uint64_t n_qlist, const uint32_t *clist,
+                            uint64_t n_clist, uint32_t n_thin, uint16_t *out16, uint64_t ld_out, uint32_t *parts_out);
 
 #ifdef __cplusplus
 }

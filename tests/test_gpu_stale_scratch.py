@@ -1029,6 +1029,47 @@ def _(wd):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------------
+# the two drivers of the compare kernels of gs_hamming.hip on their own (test_gpu_hamming.py runs their whole tables under 0x00 and 0xFF): the K-split
+# forms add to / take off cells that the driver itself has to set first, whatever the slot held
+@case("hamming", "strided_split_u32_counts")
+def _(wd):
+    import gsearch_amd as G
+    import hamming_cases as HC
+    c = next(c for c in HC.dense_cases() if c["name"].startswith("split_float32_129x130_m515"))
+    want = HC.counts(c["q"], c["c"], c["m"]).astype(np.uint32)
+
+    def run(ctx, poke):
+        out = np.full((c["nq"], c["nc"] + 3), 0xC5C5C5C5, np.uint32)
+        parts = G.debug_hamming_strided(c["qw"], c["cw"], c["m"], out, 1, dtype=c["dtype"], ctx=ctx)
+        return out[:, :c["nc"]], out[:, c["nc"]:], np.uint32(parts > 1)
+    return run, (want, np.full((c["nq"], 3), 0xC5C5C5C5, np.uint32), np.uint32(1))
+
+
+def _blocks_case(name, n_thin_of, split):
+    import gsearch_amd as G
+    import hamming_cases as HC
+    c = next(c for c in HC.blocks_cases() if c["name"] == name)
+    ld = HC.LDS[1]
+    want = HC.blocks_expected(c, ld)[0]
+
+    def run(ctx, poke):
+        out = np.full((c["nq_rows"], ld), HC.CANARY16, np.uint16)
+        parts = G.debug_hamming_blocks(c["qw"], c["cw"], c["m"], c["items"], c["qlist"], c["clist"], n_thin_of(c), out, dtype=c["dtype"], ctx=ctx)
+        return out, np.uint32(parts > 1)
+    return run, (want, np.uint32(split))
+
+
+@case("hamming", "work_list_split_three_items")
+def _(wd):
+    return _blocks_case("three_uint32_m515_r256_3", lambda c: 0, True)
+
+
+@case("hamming", "work_list_thin_items")
+def _(wd):
+    return _blocks_case("thin_float32_m1003_r256_30", lambda c: c["eligible"], True)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------
 # one test function per case, in the order of the list, then the replay
 def _make_test(c):
     def test(stale_ctx, fill_guard, workdir, monkeypatch, capfd):
