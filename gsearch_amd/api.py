@@ -1005,6 +1005,33 @@ def hmm_threshold_units(bits):
     return int(math.floor(float(bits) * 1024.0 + 0.5))
 
 
+def _opt(a):
+    """the pointer argument of an array that may be missing or empty"""
+    return _p(a) if a is not None and a.size else None
+
+
+def _recs(aa, rec_start, rec_len):
+    """-> the three arrays as a host form reads them (the caller holds them until it returns), and its arguments aa, rec_start, rec_len, n_rec"""
+    aa, rs, rl = np.ascontiguousarray(aa, dtype=np.uint8), np.ascontiguousarray(rec_start, dtype=np.uint64), np.ascontiguousarray(rec_len, dtype=np.uint64)
+    return (aa, rs, rl), (_opt(aa), _opt(rs), _opt(rl), len(rs))
+
+
+def _pairs(pair_rec, pair_prof):
+    """-> both lists as the call reads them and the arguments pair_rec, pair_prof, n_pairs of a host form"""
+    pr, pp = np.ascontiguousarray(pair_rec, dtype=np.uint32).reshape(-1), np.ascontiguousarray(pair_prof, dtype=np.uint32).reshape(-1)
+    if len(pr) != len(pp):
+        raise ValueError("pair_rec and pair_prof: one entry per pair each")
+    return pr, pp, (_opt(pr), _opt(pp), len(pr))
+
+
+def _all_items(run, k):
+    """got = run(8), and run again with the largest count when 8 slots a pair do not hold them all; got[k]: the counts, got[k + 1]: the items"""
+    got = run(8)
+    if len(got[k]) and int(got[k].max()) > got[k + 1].shape[1]:
+        got = run(int(got[k].max()))
+    return got
+
+
 class HmmDb:
     """A set of HMMER3 profiles in device memory (SPEC 13). paths_or_dir: a directory (its *.HMM / *.hmm files in name order), one path, a list of
     paths, or - texts=True - a list of bytes objects. Profiles keep the order of the files and of the models inside each."""
@@ -1085,12 +1112,9 @@ class HmmDb:
 
     def search_packed(self, aa, rec_start, rec_len):
         """residues as filter_aa_records() returns them -> int32 [n_rec, n_prof] raw scores (units of 2^-10 bit; HMM_NO_SCORE for an empty record)"""
-        aa = np.ascontiguousarray(aa, dtype=np.uint8)
-        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
-        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
-        out = np.zeros((len(rs), len(self)), np.int32)
-        check(self.ctx.L.gs_hmm_search(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
-                                       _p(out) if out.size else None))
+        held, recs = _recs(aa, rec_start, rec_len)
+        out = np.zeros((recs[3], len(self)), np.int32)
+        check(self.ctx.L.gs_hmm_search(self.ctx.h, self.h, *recs, _opt(out)))
         return out
 
     def search(self, records):
@@ -1105,24 +1129,22 @@ class HmmDb:
         profile's STATS LOCAL VITERBI line is filter_p; a profile without that line: INT32_MIN + 1, every pair that has a Viterbi score"""
         return np.array([hmm_viterbi_floor(i["mu"], i["lam"], filter_p) if i["mu"] is not None else _lib.HMM_FLOOR_ALL for i in self.info], np.int32)
 
-    def _floor(self, filter_p, floor):
+    def _floor(self, filter_p, floor, msv=False):
+        """the floors of a call: `floor` when given, else viterbi_floor(filter_p), or msv_floor(filter_p) with msv; None: every pair that has a score"""
         if floor is not None:
             fl = np.ascontiguousarray(floor, dtype=np.int32)
             if fl.shape != (len(self),):
-                raise ValueError("floor: one int32 per profile")
+                raise ValueError("%s: one int32 per profile" % ("msv_floor" if msv else "floor"))
             return fl
-        return None if filter_p is None else self.viterbi_floor(filter_p)
+        return None if filter_p is None else (self.msv_floor if msv else self.viterbi_floor)(filter_p)
 
     def search_forward_packed(self, aa, rec_start, rec_len, filter_p=1e-3, floor=None):
         """residues as filter_aa_records() returns them -> (vit, fwd), int32 [n_rec, n_prof]: what search_packed() returns, and the Forward raw score of
         the pairs whose Viterbi score reaches the profile's floor (HMM_NO_SCORE for the others)"""
-        aa = np.ascontiguousarray(aa, dtype=np.uint8)
-        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
-        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
+        held, recs = _recs(aa, rec_start, rec_len)
         fl = self._floor(filter_p, floor)
-        vit, fwd = np.zeros((len(rs), len(self)), np.int32), np.zeros((len(rs), len(self)), np.int32)
-        check(self.ctx.L.gs_hmm_search_forward(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None,
-                                               len(rs), _p(fl) if fl is not None else None, _p(vit) if vit.size else None, _p(fwd) if fwd.size else None))
+        vit, fwd = np.zeros((recs[3], len(self)), np.int32), np.zeros((recs[3], len(self)), np.int32)
+        check(self.ctx.L.gs_hmm_search_forward(self.ctx.h, self.h, *recs, _opt(fl), _opt(vit), _opt(fwd)))
         return vit, fwd
 
     def search_forward(self, records, filter_p=1e-3, floor=None):
@@ -1139,22 +1161,11 @@ class HmmDb:
         profile's STATS LOCAL MSV line is filter_p (HMMER's F1 = 0.02); a profile without that line: INT32_MIN + 1, every pair that has an MSV score"""
         return np.array([hmm_viterbi_floor(m, l, filter_p) if not np.isnan(m) else _lib.HMM_FLOOR_ALL for m, l in zip(self.mu_msv, self.lam_msv)], np.int32)
 
-    def _msv_floor(self, msv_p, msv_floor):
-        if msv_floor is not None:
-            fl = np.ascontiguousarray(msv_floor, dtype=np.int32)
-            if fl.shape != (len(self),):
-                raise ValueError("msv_floor: one int32 per profile")
-            return fl
-        return None if msv_p is None else self.msv_floor(msv_p)
-
     def search_msv_packed(self, aa, rec_start, rec_len):
         """residues as filter_aa_records() returns them -> int32 [n_rec, n_prof] MSV raw scores (SPEC 13.3; HMM_NO_SCORE for an empty record)"""
-        aa = np.ascontiguousarray(aa, dtype=np.uint8)
-        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
-        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
-        out = np.zeros((len(rs), len(self)), np.int32)
-        check(self.ctx.L.gs_hmm_search_msv(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
-                                           _p(out) if out.size else None))
+        held, recs = _recs(aa, rec_start, rec_len)
+        out = np.zeros((recs[3], len(self)), np.int32)
+        check(self.ctx.L.gs_hmm_search_msv(self.ctx.h, self.h, *recs, _opt(out)))
         return out
 
     def search_msv(self, records):
@@ -1168,16 +1179,12 @@ class HmmDb:
         """residues as filter_aa_records() returns them -> (msv, vit) or, forward=True, (msv, vit, fwd), int32 [n_rec, n_prof] (SPEC 13.3): the MSV
         score of every pair, what search_packed() returns for the pairs whose MSV score reaches the profile's MSV floor (HMM_NO_SCORE for the others),
         and the Forward score behind that Viterbi matrix as search_forward_packed() computes it"""
-        aa = np.ascontiguousarray(aa, dtype=np.uint8)
-        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
-        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
-        mfl = self._msv_floor(msv_p, msv_floor)
+        held, recs = _recs(aa, rec_start, rec_len)
+        mfl = self._floor(msv_p, msv_floor, msv=True)
         fl = self._floor(filter_p, floor) if forward else None
-        msv, vit = np.zeros((len(rs), len(self)), np.int32), np.zeros((len(rs), len(self)), np.int32)
-        fwd = np.zeros((len(rs), len(self)), np.int32) if forward else None
-        check(self.ctx.L.gs_hmm_search_filtered(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None,
-                                                len(rs), _p(mfl) if mfl is not None else None, _p(fl) if fl is not None else None, _p(msv) if msv.size else None,
-                                                _p(vit) if vit.size else None, _p(fwd) if forward and fwd.size else None))
+        msv, vit = np.zeros((recs[3], len(self)), np.int32), np.zeros((recs[3], len(self)), np.int32)
+        fwd = np.zeros((recs[3], len(self)), np.int32) if forward else None
+        check(self.ctx.L.gs_hmm_search_filtered(self.ctx.h, self.h, *recs, _opt(mfl), _opt(fl), _opt(msv), _opt(vit), _opt(fwd)))
         return (msv, vit, fwd) if forward else (msv, vit)
 
     def search_filtered(self, records, msv_p=0.02, msv_floor=None, forward=False, filter_p=1e-3, floor=None):
@@ -1196,18 +1203,11 @@ class HmmDb:
         search_packed() gives it, uint32 n_dom [n_pairs] the true number of domains, int32 dom [n_pairs, max_dom, 8]: i_from, i_to, k_from, k_to (1-based,
         inclusive), seg, n_match, n_ins, n_del of the first max_dom domains in sequence order, zeros behind them). A pair whose record is HMM_NO_HIT, empty
         or holds a byte that is no residue: HMM_NO_SCORE, 0 and zeros. max_block_cells bounds the cells whose back-pointers are alive at once (0: 2^27)"""
-        aa = np.ascontiguousarray(aa, dtype=np.uint8)
-        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
-        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
-        pr = np.ascontiguousarray(pair_rec, dtype=np.uint32).reshape(-1)
-        pp = np.ascontiguousarray(pair_prof, dtype=np.uint32).reshape(-1)
-        if len(pr) != len(pp):
-            raise ValueError("pair_rec and pair_prof: one entry per pair each")
+        held, recs = _recs(aa, rec_start, rec_len)
+        pr, pp, pairs = _pairs(pair_rec, pair_prof)
         raw, nd = np.zeros(len(pr), np.int32), np.zeros(len(pr), np.uint32)
         dom = np.zeros((len(pr), int(max_dom), _lib.HMM_DOM_WORDS), np.int32)
-        check(self.ctx.L.gs_hmm_trace(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
-                                      _p(pr) if len(pr) else None, _p(pp) if len(pp) else None, len(pr), int(max_dom), int(max_block_cells),
-                                      _p(raw) if len(pr) else None, _p(nd) if len(pr) else None, _p(dom) if dom.size else None))
+        check(self.ctx.L.gs_hmm_trace(self.ctx.h, self.h, *recs, *pairs, int(max_dom), int(max_block_cells), _opt(raw), _opt(nd), _opt(dom)))
         return raw, nd, dom
 
     def trace(self, records, pairs, max_dom=8, max_block_cells=0):
@@ -1224,10 +1224,7 @@ class HmmDb:
 
     def trace_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_block_cells=0):
         """trace_packed() with room for every domain: traced again with the largest n_dom when 8 slots a pair do not hold them all"""
-        raw, nd, dom = self.trace_packed(aa, rec_start, rec_len, pair_rec, pair_prof, 8, max_block_cells)
-        if len(nd) and int(nd.max()) > dom.shape[1]:
-            raw, nd, dom = self.trace_packed(aa, rec_start, rec_len, pair_rec, pair_prof, int(nd.max()), max_block_cells)
-        return raw, nd, dom
+        return _all_items(lambda m: self.trace_packed(aa, rec_start, rec_len, pair_rec, pair_prof, m, max_block_cells), 1)
 
     def envelopes_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_env=8, rows=False, max_block_rows=0):
         """SPEC 13.4: Forward and Backward scores and the posterior envelopes of the pairs (pair_rec[j], pair_prof[j]), all on the device -> (int32 fwd
@@ -1236,13 +1233,8 @@ class HmmDb:
         with rows=True, two lists of per-pair int32 arrays out[1..L] and cont[1..L] in units (empty for a pair that gets no envelopes below). A pair
         whose record is HMM_NO_HIT, empty or holds a byte that is no residue: HMM_NO_SCORE, HMM_NO_SCORE, 0 and zeros. max_block_rows bounds the rows of
         the two passes that are alive at once (0: 2^25)"""
-        aa = np.ascontiguousarray(aa, dtype=np.uint8)
-        rs = np.ascontiguousarray(rec_start, dtype=np.uint64)
-        rl = np.ascontiguousarray(rec_len, dtype=np.uint64)
-        pr = np.ascontiguousarray(pair_rec, dtype=np.uint32).reshape(-1)
-        pp = np.ascontiguousarray(pair_prof, dtype=np.uint32).reshape(-1)
-        if len(pr) != len(pp):
-            raise ValueError("pair_rec and pair_prof: one entry per pair each")
+        (_, _, rl), recs = _recs(aa, rec_start, rec_len)
+        pr, pp, pairs = _pairs(pair_rec, pair_prof)
         n = len(pr)
         fwd, bck, ne = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint32)
         env = np.zeros((n, int(max_env), _lib.HMM_ENV_WORDS), np.int32)
@@ -1254,10 +1246,8 @@ class HmmDb:
             ro = np.zeros(n + 1, np.uint64)
             ro[1:] = np.cumsum(lens)
             o_rows, c_rows = np.zeros(max(int(ro[-1]), 1), np.int32), np.zeros(max(int(ro[-1]), 1), np.int32)
-        check(self.ctx.L.gs_hmm_envelopes(self.ctx.h, self.h, _p(aa) if aa.nbytes else None, _p(rs) if len(rs) else None, _p(rl) if len(rl) else None, len(rs),
-                                          _p(pr) if n else None, _p(pp) if n else None, n, int(max_env), int(max_block_rows), _p(fwd) if n else None,
-                                          _p(bck) if n else None, _p(ne) if n else None, _p(env) if env.size else None, _p(ro) if ro is not None else None,
-                                          _p(o_rows) if ro is not None else None, _p(c_rows) if ro is not None else None))
+        check(self.ctx.L.gs_hmm_envelopes(self.ctx.h, self.h, *recs, *pairs, int(max_env), int(max_block_rows), _opt(fwd), _opt(bck), _opt(ne), _opt(env), _opt(ro),
+                                          _opt(o_rows), _opt(c_rows)))
         if not rows:
             return fwd, bck, ne, env
         has = fwd != _lib.HMM_NO_SCORE
@@ -1278,10 +1268,7 @@ class HmmDb:
 
     def envelopes_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_block_rows=0):
         """envelopes_packed() with room for every envelope: run again with the largest n_env when 8 slots a pair do not hold them all"""
-        got = self.envelopes_packed(aa, rec_start, rec_len, pair_rec, pair_prof, 8, max_block_rows=max_block_rows)
-        if len(got[2]) and int(got[2].max()) > got[3].shape[1]:
-            got = self.envelopes_packed(aa, rec_start, rec_len, pair_rec, pair_prof, int(got[2].max()), max_block_rows=max_block_rows)
-        return got
+        return _all_items(lambda m: self.envelopes_packed(aa, rec_start, rec_len, pair_rec, pair_prof, m, max_block_rows=max_block_rows), 2)
 
     def thresholds(self, cutoff="ga"):
         """int32 [n_prof] in units: every profile's GA1, or the caller's bits for all (a number) or per profile (a sequence)"""
@@ -1618,7 +1605,7 @@ class _DevOrfs:
     host holds their descriptors, never their residues."""
 
     def __init__(self, ctx, genomes, min_aa, max_aa, table):
-        self.ctx, self.bufs = ctx, []
+        self.ctx, self.mem = ctx, _DevScope(ctx)
         self.contig_ids = [cid for g in genomes for cid, _ in g]
         contig_genome = [gi for gi, g in enumerate(genomes) for _ in g]
         self.genome_contig0 = np.concatenate([[0], np.cumsum([len(g) for g in genomes])]).astype(np.int64)
@@ -1627,9 +1614,9 @@ class _DevOrfs:
         cap_orf, cap_aa = _orf_caps(rl, min_aa)
         n_rec = len(rs)
         try:
-            d_seq, d_rs, d_rl = self._up(seq), self._up(rs), self._up(rl)
-            self.d_orf, self.d_aa, self.d_as, self.d_al = self._new(16 * cap_orf), self._new(cap_aa), self._new(8 * cap_orf), self._new(8 * cap_orf)
-            d_off = self._new(8 * (n_rec + 1))
+            d_seq, d_rs, d_rl = self.mem.up(seq), self.mem.up(rs), self.mem.up(rl)
+            self.d_orf, self.d_aa, self.d_as, self.d_al = self.mem.new(16 * cap_orf), self.mem.new(cap_aa), self.mem.new(8 * cap_orf), self.mem.new(8 * cap_orf)
+            d_off = self.mem.new(8 * (n_rec + 1))
             self.n, n_aa, self.n_long = orf_translate_dev(ctx, d_seq, seq.nbytes, d_rs, d_rl, n_rec, cap_orf, cap_aa, self.d_orf, self.d_aa, self.d_as, self.d_al, d_off,
                                                           min_aa, max_aa, table)
             self.orf = ctx.download(self.d_orf, (self.n,), ORF_DTYPE)
@@ -1637,7 +1624,7 @@ class _DevOrfs:
             self.aa_len = ctx.download(self.d_al, (self.n,), np.uint64)
             rec_orf_off = ctx.download(d_off, (n_rec + 1,), np.uint64)
             for ptr in (d_seq, d_rs, d_rl, d_off):
-                self._free(ptr)
+                self.mem.free(ptr)
         except Exception:
             self.close()
             raise
@@ -1646,24 +1633,8 @@ class _DevOrfs:
         first_rec = np.searchsorted(rec_genome, np.arange(len(genomes) + 1))
         self.genome_orf_off = rec_orf_off[first_rec].astype(np.uint64)
 
-    def _new(self, nbytes):
-        ptr = self.ctx.alloc(max(int(nbytes), 16))
-        self.bufs.append(ptr)
-        return ptr
-
-    def _up(self, arr):
-        ptr = self._new(arr.nbytes)
-        if arr.nbytes:
-            self.ctx.upload(ptr, arr)
-        return ptr
-
-    def _free(self, ptr):
-        self.bufs.remove(ptr)
-        self.ctx.free(ptr)
-
     def close(self):
-        while self.bufs:
-            self.ctx.free(self.bufs.pop())
+        self.mem.close()
 
     def __del__(self):
         try:
@@ -1688,76 +1659,55 @@ class _DevOrfs:
     def search_dev(self, db, fwd, filter_p, prefilter=False, msv_p=0.02):
         """device int32 [n, n_prof] scores of the ORFs (Forward behind the Viterbi floor when fwd; behind the MSV floor of msv_p when prefilter, SPEC
         13.3); the caller frees through close()"""
-        d_score = self._new(4 * self.n * len(db))
+        d_score = self.mem.new(4 * self.n * len(db))
         if self.n == 0:
             return d_score
-        if prefilter:
-            mfl, fl = db._msv_floor(msv_p, None), (db._floor(filter_p, None) if fwd else None)
-            d_mfl, d_fl = (self._up(mfl) if mfl is not None else None), (self._up(fl) if fl is not None else None)
-            d_vit = self._new(4 * self.n * len(db)) if fwd else d_score
-            db.search_filtered_dev(self.d_aa, self.d_as, self.d_al, self.n, d_mfl, d_fl, None, d_vit, d_score if fwd else None)
-            self.ctx.sync()
-            for ptr in [d_mfl, d_fl] + ([d_vit] if fwd else []):
-                if ptr is not None:
-                    self._free(ptr)
-        elif fwd:
-            fl = db._floor(filter_p, None)
-            d_fl = self._up(fl) if fl is not None else None
-            db.search_forward_dev(self.d_aa, self.d_as, self.d_al, self.n, d_fl, None, d_score)
-            self.ctx.sync()
-            if d_fl is not None:
-                self._free(d_fl)
-        else:
-            db.search_dev(self.d_aa, self.d_as, self.d_al, self.n, d_score)
+        with _DevScope(self.ctx) as t:                  # the floors and the Viterbi matrix of a Forward call live as long as the call
+            up = lambda a: None if a is None else t.up(a)       # noqa: E731
+            if prefilter:
+                d_mfl, d_fl = up(db._floor(msv_p, None, msv=True)), up(db._floor(filter_p, None) if fwd else None)
+                d_vit = t.new(4 * self.n * len(db)) if fwd else d_score
+                db.search_filtered_dev(self.d_aa, self.d_as, self.d_al, self.n, d_mfl, d_fl, None, d_vit, d_score if fwd else None)
+                self.ctx.sync()
+            elif fwd:
+                db.search_forward_dev(self.d_aa, self.d_as, self.d_al, self.n, up(db._floor(filter_p, None)), None, d_score)
+                self.ctx.sync()
+            else:
+                db.search_dev(self.d_aa, self.d_as, self.d_al, self.n, d_score)
         return d_score
 
     def search(self, db, fwd, filter_p, prefilter=False, msv_p=0.02):
         d_score = self.search_dev(db, fwd, filter_p, prefilter, msv_p)
         scores = self.ctx.download(d_score, (self.n, len(db)), np.int32)
-        self._free(d_score)
+        self.mem.free(d_score)
         return scores
+
+    def _over_pairs(self, call, pair_rec, pair_prof, outs):
+        """call = db.trace_dev or db.envelopes_dev over the device residues, with room for every item (_all_items). outs(n_pairs, m): (shape, dtype, what a
+        call with nothing to do leaves there) of each output at m slots a pair; the last holds the items, the one before it their numbers."""
+        pr, pp, _ = _pairs(pair_rec, pair_prof)
+        n = len(pr)
+        if n == 0 or self.n == 0:
+            return tuple(np.full(shape, fill, dt) for shape, dt, fill in outs(n, 8))
+        with _DevScope(self.ctx) as d:
+            d_pr, d_pp = d.up(pr), d.up(pp)
+
+            def run(m):
+                with _DevScope(self.ctx) as o:
+                    ptrs = [o.new(int(np.prod(shape)) * np.dtype(dt).itemsize) for shape, dt, _ in outs(n, m)]
+                    call(self.d_aa, self.d_as, self.d_al, self.n, d_pr, d_pp, n, m, *ptrs)
+                    return tuple(self.ctx.download(ptr, shape, dt) for ptr, (shape, dt, _) in zip(ptrs, outs(n, m)))
+            return _all_items(run, len(outs(n, 8)) - 2)
 
     def trace_all(self, db, pair_rec, pair_prof):
         """HmmDb.trace_all() over the device residues"""
-        pr, pp = np.ascontiguousarray(pair_rec, np.uint32).reshape(-1), np.ascontiguousarray(pair_prof, np.uint32).reshape(-1)
-        npair, max_dom = len(pr), 8
-        if npair == 0 or self.n == 0:
-            return np.full(npair, _lib.HMM_NO_SCORE, np.int32), np.zeros(npair, np.uint32), np.zeros((npair, max_dom, _lib.HMM_DOM_WORDS), np.int32)
-        d_pr, d_pp = self._up(pr), self._up(pp)
-        while True:
-            d_raw, d_nd, d_dom = self._new(4 * npair), self._new(4 * npair), self._new(4 * npair * max_dom * _lib.HMM_DOM_WORDS)
-            db.trace_dev(self.d_aa, self.d_as, self.d_al, self.n, d_pr, d_pp, npair, max_dom, d_raw, d_nd, d_dom)
-            raw, nd = self.ctx.download(d_raw, (npair,), np.int32), self.ctx.download(d_nd, (npair,), np.uint32)
-            dom = self.ctx.download(d_dom, (npair, max_dom, _lib.HMM_DOM_WORDS), np.int32)
-            for ptr in (d_raw, d_nd, d_dom):
-                self._free(ptr)
-            if int(nd.max()) <= max_dom:
-                break
-            max_dom = int(nd.max())
-        self._free(d_pr); self._free(d_pp)
-        return raw, nd, dom
+        return self._over_pairs(db.trace_dev, pair_rec, pair_prof, lambda n, m: [((n,), np.int32, _lib.HMM_NO_SCORE), ((n,), np.uint32, 0),
+                                                                                 ((n, m, _lib.HMM_DOM_WORDS), np.int32, 0)])
 
     def envelopes_all(self, db, pair_rec, pair_prof):
         """HmmDb.envelopes_all() over the device residues -> (fwd, bck, n_env, env)"""
-        pr, pp = np.ascontiguousarray(pair_rec, np.uint32).reshape(-1), np.ascontiguousarray(pair_prof, np.uint32).reshape(-1)
-        npair, max_env = len(pr), 8
-        if npair == 0 or self.n == 0:
-            none = np.full(npair, _lib.HMM_NO_SCORE, np.int32)
-            return none, none.copy(), np.zeros(npair, np.uint32), np.zeros((npair, max_env, _lib.HMM_ENV_WORDS), np.int32)
-        d_pr, d_pp = self._up(pr), self._up(pp)
-        while True:
-            d_out = [self._new(4 * npair), self._new(4 * npair), self._new(4 * npair), self._new(4 * npair * max_env * _lib.HMM_ENV_WORDS)]
-            db.envelopes_dev(self.d_aa, self.d_as, self.d_al, self.n, d_pr, d_pp, npair, max_env, *d_out)
-            fwd, bck = self.ctx.download(d_out[0], (npair,), np.int32), self.ctx.download(d_out[1], (npair,), np.int32)
-            ne = self.ctx.download(d_out[2], (npair,), np.uint32)
-            env = self.ctx.download(d_out[3], (npair, max_env, _lib.HMM_ENV_WORDS), np.int32)
-            for ptr in d_out:
-                self._free(ptr)
-            if int(ne.max()) <= max_env:
-                break
-            max_env = int(ne.max())
-        self._free(d_pr); self._free(d_pp)
-        return fwd, bck, ne, env
+        return self._over_pairs(db.envelopes_dev, pair_rec, pair_prof, lambda n, m: [((n,), np.int32, _lib.HMM_NO_SCORE), ((n,), np.int32, _lib.HMM_NO_SCORE),
+                                                                                     ((n,), np.uint32, 0), ((n, m, _lib.HMM_ENV_WORDS), np.int32, 0)])
 
     def residues(self, j, a=0, b=None):
         """residues [a, b) of ORF j, read back from the device"""
@@ -1775,8 +1725,8 @@ def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, m
         rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
         if ng and npf and dev.n:
             d_score = dev.search_dev(db, fwd, filter_p, prefilter, msv_p)
-            d_goff, d_thr = dev._up(dev.genome_orf_off), dev._up(db.thresholds(cutoff))
-            d_rec, d_sc = dev._new(4 * ng * npf), dev._new(4 * ng * npf)
+            d_goff, d_thr = dev.mem.up(dev.genome_orf_off), dev.mem.up(db.thresholds(cutoff))
+            d_rec, d_sc = dev.mem.new(4 * ng * npf), dev.mem.new(4 * ng * npf)
             db.best_hits_dev(d_score, dev.n, d_goff, ng, d_thr, d_rec, d_sc)
             rec = ctx.download(d_rec, (ng, npf), np.uint32)
         span = {}
@@ -1832,7 +1782,7 @@ def _gene_inputs(seq, rec_start, rec_len, genome_rec_off):
 
 
 class _DevScope:
-    """device buffers of one call, freed together"""
+    """device buffers of one call or one owner, freed together"""
 
     def __init__(self, ctx):
         self.ctx, self.bufs = ctx, []
@@ -1848,12 +1798,19 @@ class _DevScope:
             self.ctx.upload(ptr, arr)
         return ptr
 
+    def free(self, ptr):
+        self.bufs.remove(ptr)
+        self.ctx.free(ptr)
+
+    def close(self):
+        while self.bufs:
+            self.ctx.free(self.bufs.pop())
+
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
-        while self.bufs:
-            self.ctx.free(self.bufs.pop())
+        self.close()
 
 
 def gene_train(seq, rec_start, rec_len, genome_rec_off, intervals, ctx=None, host=False, **params):
@@ -2021,7 +1978,7 @@ class _DevGenes(_DevOrfs):
     _DevOrfs runs on them unchanged. `orf` holds begin, rec and strand of each gene; `end` its end (the stop codon included where there is one)."""
 
     def __init__(self, ctx, genomes, min_aa, max_aa, table):
-        self.ctx, self.bufs = ctx, []
+        self.ctx, self.mem = ctx, _DevScope(ctx)
         self.contig_ids = [cid for g in genomes for cid, _ in g]
         recs, self.rec_contig, self.rec_offset, goff, contig0 = _gene_segments([[c for _, c in g] for g in genomes])
         self.genome_contig0 = contig0
@@ -2029,9 +1986,9 @@ class _DevGenes(_DevOrfs):
         cap_gene, cap_aa = _orf_caps(rl, min_aa)
         n_rec, ng = len(rs), len(genomes)
         try:
-            d_seq, d_rs, d_rl, d_goff = self._up(seq), self._up(rs), self._up(rl), self._up(goff)
-            d_gene, self.d_aa, self.d_as, self.d_al = self._new(GENE_DTYPE.itemsize * cap_gene), self._new(cap_aa), self._new(8 * cap_gene), self._new(8 * cap_gene)
-            d_off, d_info = self._new(8 * (n_rec + 1)), self._new(16 * ng)
+            d_seq, d_rs, d_rl, d_goff = self.mem.up(seq), self.mem.up(rs), self.mem.up(rl), self.mem.up(goff)
+            d_gene, self.d_aa, self.d_as, self.d_al = self.mem.new(GENE_DTYPE.itemsize * cap_gene), self.mem.new(cap_aa), self.mem.new(8 * cap_gene), self.mem.new(8 * cap_gene)
+            d_off, d_info = self.mem.new(8 * (n_rec + 1)), self.mem.new(16 * ng)
             self.n, _ = gene_call_dev(ctx, d_seq, seq.nbytes, d_rs, d_rl, n_rec, d_goff, ng, d_info, cap_gene, cap_aa, d_gene, self.d_aa, self.d_as, self.d_al, d_off,
                                       min_aa=min_aa, table=table)
             self.n_long = 0
@@ -2041,7 +1998,7 @@ class _DevGenes(_DevOrfs):
             rec_off = ctx.download(d_off, (n_rec + 1,), np.uint64)
             self.info = ctx.download(d_info, (ng, 2), np.uint64)
             for ptr in (d_seq, d_rs, d_rl, d_goff, d_gene, d_off, d_info):
-                self._free(ptr)
+                self.mem.free(ptr)
         except Exception:
             self.close()
             raise

@@ -1,167 +1,17 @@
 // gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
-// device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, the best record per genome and profile, and the domains of
+// device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, the best record per genome and profile, the domains of
 // the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2), and the Backward pass and posterior envelopes of a list of pairs
-// (SPEC 13.4). Integers only
-// from the file's digits to the raw score; doubles appear in gs_hmm_bits / gs_hmm_evalue / gs_hmm_forward_evalue, in the table of lse (rounded to
-// integers once, on the host), in the Viterbi floor and in the cutoffs and STATS fields that are only reported.
+// (SPEC 13.4). Integers only from the file's digits to the raw score. The reader of profile files and the calls that touch no device are
+// gs_hmm_parse.cpp, a host-only unit; the doubles of hmmsearch (bits, E-values, the table of lse, the Viterbi floor, the reported cutoffs) are all there.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <numeric>
 #include <utility>
 #include "gs_internal.hpp"
-#include "gs_spec.hpp"
+#include "gs_spec.hpp"           // (brings gs_hmm_parse.hpp)
 
 namespace gs {
-
-// ---- profile files ----------------------------------------------------------------------------------------------------------------------------
-struct HmmModel {
-    gs_hmm_info info; std::vector<int32_t> tab;                         // tab: [27][M + 1] as gs_hmm_parse_mem documents it
-    double stats[6] = {}; uint32_t has_stats = 0;                       // as gs_hmm_parse_stats_mem documents them
-};
-
-// one number of a file -> units (SPEC 13 "Units")
-static bool hmm_file_units(const std::string &t, int32_t *out)
-{
-    if (t == "*") { *out = GS_HMM_STAR; return true; }
-    const size_t dot = t.find('.');
-    const std::string ip = t.substr(0, dot), fr = dot == std::string::npos ? "" : t.substr(dot + 1);
-    auto digits = [](const std::string &s) { return !s.empty() && s.find_first_not_of("0123456789") == std::string::npos; };
-    if (!digits(ip) || ip.size() > 4 || (dot != std::string::npos && !digits(fr))) { set_error("hmm: not a number: '%s'", t.c_str()); return false; }
-    if (fr.size() > 5) { set_error("hmm: more than 5 decimals: '%s'", t.c_str()); return false; }
-    uint64_t d = strtoull(ip.c_str(), nullptr, 10) * 100000ull, f = 0;
-    for (size_t i = 0; i < 5; i++) f = f * 10 + (i < fr.size() ? (uint64_t)(fr[i] - '0') : 0);
-    d += f;
-    if (d > GS_HMM_MAX_FILE_VALUE) { set_error("hmm: a value of 100 nats or more: '%s'", t.c_str()); return false; }
-    *out = -(int32_t)((d * GS_HMM_UNIT_C + (1ull << (GS_HMM_UNIT_S - 1))) >> GS_HMM_UNIT_S);
-    return true;
-}
-// a cutoff in bits as the file writes it -> units, rounded half up
-static bool hmm_bits_units(const std::string &tok, int32_t *out)
-{
-    const bool neg = !tok.empty() && tok[0] == '-';
-    const size_t b = tok.find_first_not_of("+-");
-    const std::string t = b == std::string::npos ? "" : tok.substr(b);
-    const size_t dot = t.find('.');
-    const std::string ip = t.substr(0, dot), fr = dot == std::string::npos ? "" : t.substr(dot + 1);
-    auto digits = [](const std::string &s) { return !s.empty() && s.find_first_not_of("0123456789") == std::string::npos; };
-    if (!digits(ip) || ip.size() > 6 || (!fr.empty() && !digits(fr)) || fr.size() > 5) { set_error("hmm: not a cutoff: '%s'", tok.c_str()); return false; }
-    int64_t den = 1;
-    for (size_t i = 0; i < fr.size(); i++) den *= 10;
-    int64_t d = strtoll(ip.c_str(), nullptr, 10) * den + (fr.empty() ? 0 : strtoll(fr.c_str(), nullptr, 10));
-    if (neg) d = -d;
-    const int64_t num = 2 * d * 1024 + den, q = num / (2 * den);
-    *out = (int32_t)(num % (2 * den) < 0 ? q - 1 : q);              // floor
-    return true;
-}
-
-struct HmmLines {      // the non-blank lines of a text, split at white space
-    const char *p, *end;
-    bool next(std::vector<std::string> &tok, std::string *raw = nullptr)
-    {
-        while (p < end) {
-            const char *e = (const char *)memchr(p, '\n', (size_t)(end - p));
-            if (!e) e = end;
-            const char *a = p;
-            p = e < end ? e + 1 : end;
-            tok.clear();
-            for (const char *c = a; c < e;) {
-                while (c < e && (*c == ' ' || *c == '\t' || *c == '\r')) c++;
-                const char *s = c;
-                while (c < e && !(*c == ' ' || *c == '\t' || *c == '\r')) c++;
-                if (c > s) tok.emplace_back(s, c);
-            }
-            if (!tok.empty()) { if (raw) raw->assign(a, e); return true; }
-        }
-        return false;
-    }
-    bool more() { while (p < end && (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n')) p++; return p < end; }
-};
-
-static int hmm_parse_all(const char *text, size_t n, std::vector<HmmModel> &out)
-{
-    HmmLines in{text, text + n};
-    std::vector<std::string> f;
-    std::string raw;
-    static const int32_t bg[20] = GS_HMM_BG_LIST;
-    const size_t first = out.size();
-#define HMM_LINE(what) GS_REQUIRE(in.next(f, &raw), GS_ERR_INVALID, "hmm: the text ends inside a model (%s)", what)
-    while (in.more()) {
-        HMM_LINE("header");
-        GS_REQUIRE(raw.compare(0, 7, "HMMER3/") == 0, GS_ERR_INVALID, "hmm: not a HMMER3 profile: '%.40s'", raw.c_str());
-        HmmModel m;
-        memset(&m.info, 0, sizeof m.info);
-        bool has_name = false, has_alph = false;
-        std::string alph;
-        for (;;) {
-            HMM_LINE("header");
-            if (f[0] == "HMM") break;
-            if (f[0] == "STATS" && f.size() > 4 && f[1] == "LOCAL") {
-                const int w = f[2] == "MSV" ? 0 : (f[2] == "VITERBI" ? 1 : (f[2] == "FORWARD" ? 2 : -1));
-                if (w >= 0) { m.stats[2 * w] = strtod(f[3].c_str(), nullptr); m.stats[2 * w + 1] = strtod(f[4].c_str(), nullptr); m.has_stats |= 1u << w; }
-            }
-            if (f[0] == "NAME" && f.size() > 1) { snprintf(m.info.name, sizeof m.info.name, "%s", f[1].c_str()); has_name = true; }
-            else if (f[0] == "ACC" && f.size() > 1) snprintf(m.info.acc, sizeof m.info.acc, "%s", f[1].c_str());
-            else if (f[0] == "LENG" && f.size() > 1) {
-                GS_REQUIRE(f[1].size() <= 9 && f[1].find_first_not_of("0123456789") == std::string::npos, GS_ERR_INVALID, "hmm: LENG '%s'", f[1].c_str());
-                m.info.M = (uint32_t)strtoul(f[1].c_str(), nullptr, 10);
-            } else if (f[0] == "ALPH" && f.size() > 1) {
-                alph = f[1]; has_alph = true;
-                for (char &ch : alph) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch + 32);
-            } else if ((f[0] == "GA" || f[0] == "TC" || f[0] == "NC") && f.size() > 2) {
-                std::string a = f[1], b = f[2];
-                while (!a.empty() && a.back() == ';') a.pop_back();
-                while (!b.empty() && b.back() == ';') b.pop_back();
-                double *dst = f[0] == "GA" ? m.info.ga : (f[0] == "TC" ? m.info.tc : m.info.nc);
-                dst[0] = strtod(a.c_str(), nullptr); dst[1] = strtod(b.c_str(), nullptr);
-                m.info.flags |= f[0] == "GA" ? GS_HMM_HAS_GA : (f[0] == "TC" ? GS_HMM_HAS_TC : GS_HMM_HAS_NC);
-                if (f[0] == "GA" && !hmm_bits_units(a, &m.info.ga_units)) return GS_ERR_INVALID;
-            } else if (f[0] == "STATS" && f.size() > 4 && f[1] == "LOCAL" && f[2] == "VITERBI") {
-                m.info.mu = strtod(f[3].c_str(), nullptr); m.info.lambda = strtod(f[4].c_str(), nullptr);
-                m.info.flags |= GS_HMM_HAS_STATS;
-            }
-        }
-        GS_REQUIRE(has_name && has_alph && m.info.M >= 1, GS_ERR_INVALID, "hmm: NAME, LENG or ALPH missing");
-        GS_REQUIRE(alph == "amino", GS_ERR_INVALID, "hmm: %s: ALPH %s (only amino)", m.info.name, alph.c_str());
-        GS_REQUIRE(m.info.M <= GS_HMM_MAX_M, GS_ERR_UNSUPPORTED, "hmm: %s has %u nodes, more than %u", m.info.name, m.info.M, GS_HMM_MAX_M);
-        const uint32_t M = m.info.M, W = M + 1;
-        m.info.tbm = hmm_tbm(M);
-        m.tab.assign((size_t)GS_HMM_TABLE_ROWS * W, 0);
-        HMM_LINE("transition names");
-        HMM_LINE("node 0");
-        if (f[0] == "COMPO") HMM_LINE("node 0");
-        int32_t u;
-        auto emissions = [&](size_t skip, int32_t *col, uint32_t k) {          // 20 numbers from f[skip]; col: where the match scores of node k go
-            for (int a = 0; a < 20; a++) {
-                if (!hmm_file_units(f[skip + a], &u)) return false;
-                if (col) col[(size_t)a * W + k] = u - bg[a];
-            }
-            return true;
-        };
-        for (uint32_t k = 0; k <= M; k++) {
-            if (k > 0) {
-                HMM_LINE("match emissions");
-                GS_REQUIRE(f.size() >= 21 && f[0] == std::to_string(k), GS_ERR_INVALID, "hmm: %s: node %u expected, found '%.20s'", m.info.name, k, f[0].c_str());
-                if (!emissions(1, m.tab.data(), k)) return GS_ERR_INVALID;
-                HMM_LINE("insert emissions");
-            }
-            GS_REQUIRE(f.size() == 20, GS_ERR_INVALID, "hmm: %s: insert emissions of node %u: %zu fields", m.info.name, k, f.size());
-            if (!emissions(0, nullptr, k)) return GS_ERR_INVALID;             // validated; insert emissions score 0 (SPEC 13)
-            HMM_LINE("transitions");
-            GS_REQUIRE(f.size() == 7, GS_ERR_INVALID, "hmm: %s: transitions of node %u: %zu fields", m.info.name, k, f.size());
-            for (int t = 0; t < 7; t++) {
-                if (!hmm_file_units(f[t], &u)) return GS_ERR_INVALID;
-                m.tab[(size_t)(20 + t) * W + k] = u;
-            }
-        }
-        HMM_LINE("//");
-        GS_REQUIRE(f.size() == 1 && f[0] == "//", GS_ERR_INVALID, "hmm: %s: no // after node %u", m.info.name, M);
-        out.push_back(std::move(m));
-    }
-#undef HMM_LINE
-    GS_REQUIRE(out.size() > first, GS_ERR_INVALID, "hmm: no model in the text");
-    return GS_OK;
-}
 
 // ---- device side --------------------------------------------------------------------------------------------------------------------------------
 // A profile in device memory: 28 rows of MP = 64 Q words, word j of a row belongs to node j + 1. Rows 0..26 as in the host table, row 27 = PDD,
@@ -197,8 +47,6 @@ static_assert(hmm_classes_hold(), "a profile of 64 Q nodes runs in class Q, one 
 static_assert(HMM_CLASS_Q[HMM_CLASSES - 1] * 64 == GS_HMM_MAX_M, "the largest class holds GS_HMM_MAX_M nodes");
 static_assert((size_t)HMM_ROWS_DEV * GS_HMM_MAX_M * 4 <= 160 * 1024, "the largest table fits the LDS of a CU");
 
-// T of SPEC 13.1 on the host: no entry lies closer than 3.5e-6 to a rounding boundary, so the f64 log2 of any libm gives the same integers
-static uint16_t hmm_lse_entry(uint32_t j) { return (uint16_t)floor(1024.0 * log2(1.0 + exp2(-2.0 * (double)j / 1024.0)) + 0.5); }
 // in LDS T[0 .. 5902] is followed by the 0 that every larger difference reads, so the look-up needs no branch
 enum { HMM_LSE_LDS_N = GS_HMM_LSE_N + 1, HMM_LSE_LDS_BYTES = 2 * HMM_LSE_LDS_N };
 static_assert((size_t)HMM_ROWS_DEV * GS_HMM_MAX_M * 4 + HMM_LSE_LDS_BYTES <= 160 * 1024, "the largest table and T behind it fit the LDS of a CU");
@@ -1034,12 +882,102 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
     return GS_OK;
 }
 
-// lens: the host copy of rec_len; everything else device memory. Queued on c's stream; the order list lives in its slot until the caller's scope ends.
+// ---- the arguments of a call ----------------------------------------------------------------------------------------------------------------------
+// Every operation is in the ABI twice, over device pointers (_dev) and over host pointers. Both entries hand their pointers to ONE body (hmm_*_form),
+// which states the refusals once, builds the views below and runs the implementation; `host` says where the caller's pointers live.
+// One array argument: the caller's device memory where there is some, else the slot - the staging of a host form (filled from the caller's array with
+// HMM_UP, copied back to it by hmm_fetch with HMM_DOWN), or the place of an output that has to be computed although nobody asked for it.
+enum { HMM_UP = 1, HMM_DOWN = 2 };
+struct HmmArg {
+    PoolBuf buf; void *dev = nullptr, *back = nullptr; size_t bytes = 0;
+    HmmArg(gs_ctx *c, ScratchSlot s) : buf(c, s) {}
+    int bind(bool host, const void *p, size_t n, int dir)
+    {
+        if (!host && (p || !n)) { dev = (void *)p; return GS_OK; }
+        int rc = buf.alloc(n);
+        if (rc) return rc;
+        dev = buf.p;
+        if (!host || !p) return GS_OK;
+        if ((dir & HMM_UP) && n) GS_HIP_CHECK(hipMemcpyAsync(dev, p, n, hipMemcpyHostToDevice, buf.c->stream));
+        if (dir & HMM_DOWN) { back = (void *)p; bytes = n; }
+        return GS_OK;
+    }
+    template <class T> T *as() const { return (T *)dev; }
+};
+struct HmmIn {          // the caller's records
+    bool host; const uint8_t *aa; const uint64_t *rs, *rl; uint64_t n_rec;
+    bool given() const { return rs && rl && (host || aa); }             // (a host form that reads no residue may pass a null aa: HmmRecs::fill decides)
+};
+// The records as the implementations read them: aa, rec_start and rec_len on the device, the lengths on the host too.
+struct HmmRecs {
+    const uint8_t *aa = nullptr; const uint64_t *rs = nullptr, *rl = nullptr, *lens = nullptr; uint64_t n_rec = 0;
+    std::vector<uint64_t> fetched; HmmArg d_aa, d_rs, d_rl;
+    explicit HmmRecs(gs_ctx *c) : d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN) {}
+    // Host forms: the three arrays go to their slots, aa as far as the call reads it (n_bytes). _dev forms: the lengths come to the host, behind a wait
+    // for whatever the caller, and this call, queued before.
+    int fill(const HmmIn &in, uint64_t n_bytes)
+    {
+        gs_ctx *c = d_aa.buf.c;
+        n_rec = in.n_rec;
+        GS_REQUIRE(!in.host || in.aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
+        int rc;
+        if ((rc = d_aa.bind(in.host, in.aa, n_bytes, HMM_UP)) || (rc = d_rs.bind(in.host, in.rs, 8 * n_rec, HMM_UP)) || (rc = d_rl.bind(in.host, in.rl, 8 * n_rec, HMM_UP))) return rc;
+        aa = d_aa.as<uint8_t>(); rs = d_rs.as<uint64_t>(); rl = d_rl.as<uint64_t>(); lens = in.rl;
+        if (in.host) return GS_OK;
+        fetched.resize(n_rec);
+        if (n_rec) GS_HIP_CHECK(hipMemcpyAsync(fetched.data(), rl, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(stream_wait(c));
+        lens = fetched.data();
+        return GS_OK;
+    }
+};
+// The pairs of a call: both lists on the host, pair_prof on the device where a kernel reads it.
+struct HmmPairs {
+    const uint32_t *rec = nullptr, *prof = nullptr, *prof_dev = nullptr; uint64_t n = 0;
+    std::vector<uint32_t> h_rec, h_prof; HmmArg d_prof;
+    explicit HmmPairs(gs_ctx *c) : d_prof(c, SL_HMMB_PAIR_PROF) {}
+    // Host forms: pair_prof goes to its slot if on_device. _dev forms: both lists are queued for the host and are there after the next wait (HmmRecs::fill).
+    int fill(bool host, const uint32_t *pair_rec, const uint32_t *pair_prof, uint64_t n_pairs, bool on_device)
+    {
+        gs_ctx *c = d_prof.buf.c;
+        n = n_pairs; rec = pair_rec; prof = pair_prof;
+        int rc;
+        if ((!host || on_device) && (rc = d_prof.bind(host, pair_prof, 4 * n, HMM_UP))) return rc;
+        prof_dev = d_prof.as<uint32_t>();
+        if (host) return GS_OK;
+        h_rec.resize(n); h_prof.resize(n);
+        GS_HIP_CHECK(hipMemcpyAsync(h_rec.data(), pair_rec, 4 * n, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(h_prof.data(), pair_prof, 4 * n, hipMemcpyDeviceToHost, c->stream));
+        rec = h_rec.data(); prof = h_prof.data();
+        return GS_OK;
+    }
+};
+// the end of a host form: its outputs to the caller's arrays, in the order given, and the wait for them (a _dev form has nothing to copy and only waits)
+static int hmm_fetch(gs_ctx *c, std::initializer_list<const HmmArg *> outs)
+{
+    for (const HmmArg *o : outs)
+        if (o->back && o->bytes) GS_HIP_CHECK(hipMemcpyAsync(o->back, o->dev, o->bytes, hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
+static int hmm_check_lens(const uint64_t *lens, uint64_t n_rec, uint32_t max_l)
+{
+    for (uint64_t r = 0; r < n_rec; r++)
+        GS_REQUIRE(lens[r] <= max_l, GS_ERR_UNSUPPORTED, "hmm: record %llu has %llu residues, more than %u", (unsigned long long)r, (unsigned long long)lens[r], max_l);
+    return GS_OK;
+}
+// The context's lock of a body. A body declares it before its views, so that they have given their slots back when it is released, and takes it where
+// the form it runs for did: a host form after it has judged the caller's arrays, a _dev form at once, since it judges what it fetches.
+using HmmLock = std::unique_lock<std::recursive_mutex>;
+static void hmm_lock(gs_ctx *c, HmmLock &lock) { lock = HmmLock(c->mu); (void)hipSetDevice(c->device); }
+
+// R: the records of the call; everything else device memory. Queued on c's stream; the order list lives in its slot until the caller's scope ends.
 // msv: the MSV score (SPEC 13.3) of every pair in the place of its Viterbi score - the same launches with k_hmm_msv and its smaller LDS.
-static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
-                           int32_t *score_dev, PoolBuf &d_order, bool msv = false)
+static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, int32_t *score_dev, PoolBuf &d_order, bool msv = false)
 {
     const uint32_t np = (uint32_t)db->models.size();
+    const uint64_t n_rec = R.n_rec, *lens = R.lens;
     std::vector<uint32_t> order(n_rec);
     std::iota(order.begin(), order.end(), 0u);
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lens[a] > lens[b]; });
@@ -1051,7 +989,7 @@ static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, cons
         const auto k = msv ? hmm_kernels(cls).msv : hmm_kernels(cls).vit;
         const size_t lds = msv ? hmm_msv_lds_bytes(cls) : hmm_lds_bytes(cls, HMM_VIT);
         rc = hmm_launch_class(c, db->lds_set[msv ? HMM_K_MSV : HMM_VIT][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
-            k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, aa_dev, rs_dev, rl_dev,
+            k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, R.aa, R.rs, R.rl,
                                                    d_order.as<uint32_t>(), (uint32_t)n_rec, np, score_dev);
         });
         if (rc) return rc;
@@ -1059,51 +997,21 @@ static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, cons
     GS_HIP_CHECK(stream_wait(c));           // `order` is read by the copy until here
     return GS_OK;
 }
-static int hmm_check_lens(const uint64_t *lens, uint64_t n_rec, uint32_t max_l = GS_HMM_MAX_L)
-{
-    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
-    for (uint64_t r = 0; r < n_rec; r++)
-        GS_REQUIRE(lens[r] <= max_l, GS_ERR_UNSUPPORTED, "hmm: record %llu has %llu residues, more than %u", (unsigned long long)r, (unsigned long long)lens[r], max_l);
-    return GS_OK;
-}
-// the _dev forms' host copy of the record lengths; waits for whatever the caller queued before it as well
-static int hmm_fetch_lens(gs_ctx *c, const uint64_t *rl_dev, uint64_t n_rec, std::vector<uint64_t> &lens)
-{
-    lens.resize(n_rec);
-    if (n_rec) GS_HIP_CHECK(hipMemcpyAsync(lens.data(), rl_dev, 8 * n_rec, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
-}
-// the host forms: where the residues of all records end, and aa / rec_start / rec_len into their slots (n_bytes: as far as the call reads aa)
-static uint64_t hmm_records_end(const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec)
-{
-    uint64_t n_bytes = 0;
-    for (uint64_t r = 0; r < n_rec; r++) if (rec_len[r]) n_bytes = std::max(n_bytes, rec_start[r] + rec_len[r]);
-    return n_bytes;
-}
-static int hmm_stage_records(gs_ctx *c, const uint8_t *aa, uint64_t n_bytes, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, PoolBuf &d_aa, PoolBuf &d_rs,
-                             PoolBuf &d_rl)
-{
-    GS_REQUIRE(aa || n_bytes == 0, GS_ERR_INVALID, "null aa");
-    int rc;
-    if ((rc = d_aa.alloc(n_bytes)) || (rc = d_rs.alloc(8 * n_rec)) || (rc = d_rl.alloc(8 * n_rec))) return rc;
-    if (n_bytes) GS_HIP_CHECK(hipMemcpyAsync(d_aa.p, aa, n_bytes, hipMemcpyHostToDevice, c->stream));
-    if (n_rec) {
-        GS_HIP_CHECK(hipMemcpyAsync(d_rs.p, rec_start, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
-        GS_HIP_CHECK(hipMemcpyAsync(d_rl.p, rec_len, 8 * n_rec, hipMemcpyHostToDevice, c->stream));
-    }
-    return GS_OK;
-}
 
+// the order list of a call and, per profile, the selected records and their number; a later selection takes the place of the one before (stream order)
+struct HmmLists {
+    PoolBuf order, sel, cnt;
+    explicit HmmLists(gs_ctx *c) : order(c, SL_HMM_ORDER), sel(c, SL_HMM_SEL), cnt(c, SL_HMM_SEL_COUNT) {}
+};
 // One program over the pairs another score selects: out_dev filled with GS_HMM_NO_SCORE, per profile the list of the records whose in_dev reaches
 // floor_dev (nullptr: every pair that has a score there), then prog - HMM_FWD: k_hmm_forward, HMM_VIT: k_hmm_viterbi_sel - over those lists into out_dev.
-// d_order holds the order list of the call. Queued on c's stream.
-static int hmm_selected_pass(gs_ctx *c, gs_hmm_db *db, HmmProg prog, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, uint64_t n_rec,
-                             const int32_t *in_dev, const int32_t *floor_dev, int32_t *out_dev, PoolBuf &d_order, PoolBuf &d_sel, PoolBuf &d_cnt)
+// Queued on c's stream.
+static int hmm_selected_pass(gs_ctx *c, gs_hmm_db *db, HmmProg prog, const HmmRecs &R, const int32_t *in_dev, const int32_t *floor_dev, int32_t *out_dev, HmmLists &l)
 {
     const uint32_t np = (uint32_t)db->models.size();
+    const uint64_t n_rec = R.n_rec;
     int rc;
-    if (!d_sel.p && ((rc = d_sel.alloc(4 * n_rec * np)) || (rc = d_cnt.alloc(4 * (size_t)np)))) return rc;
+    if (!l.sel.p && ((rc = l.sel.alloc(4 * n_rec * np)) || (rc = l.cnt.alloc(4 * (size_t)np)))) return rc;
     const uint64_t n = n_rec * np;
     GS_REQUIRE(n < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many (record, profile) pairs");
     {
@@ -1113,60 +1021,31 @@ static int hmm_selected_pass(gs_ctx *c, gs_hmm_db *db, HmmProg prog, const uint8
     }
     {
         ProfScope ps(c, FAM_SEARCH);
-        k_hmm_select<<<np, HMM_SEL_BLOCK, 0, c->stream>>>(in_dev, d_order.as<uint32_t>(), (uint32_t)n_rec, np, floor_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>());
+        k_hmm_select<<<np, HMM_SEL_BLOCK, 0, c->stream>>>(in_dev, l.order.as<uint32_t>(), (uint32_t)n_rec, np, floor_dev, l.sel.as<uint32_t>(), l.cnt.as<uint32_t>());
         GS_HIP_CHECK(hipGetLastError());
     }
     const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
     for (int cls = 0; cls < HMM_CLASSES; cls++) {
-        const uint32_t first_of = db->class_start[cls], n_in = db->class_start[cls + 1] - first_of;
-        if (prog == HMM_FWD) {
-            const auto k = hmm_kernels(cls).fwd;
-            const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
-            rc = hmm_launch_class(c, db->lds_set[HMM_FWD][cls], k, first_of, n_in, wg, lds, [&](dim3 grid, uint32_t first) {
-                k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, db->d_lse.as<uint16_t>(), aa_dev,
-                                                       rs_dev, rl_dev, d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec, np, out_dev);
+        // the two programs differ in the kernel, its LDS, its flag and the table of lse that Forward takes behind the profile list
+        auto run = [&](auto k, int kind, size_t lds, auto... lse) {
+            return hmm_launch_class(c, db->lds_set[kind][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
+                k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, lse..., R.aa, R.rs, R.rl,
+                                                       l.sel.as<uint32_t>(), l.cnt.as<uint32_t>(), (uint32_t)n_rec, np, out_dev);
             });
-        } else {
-            const auto k = hmm_kernels(cls).vit_sel;
-            const size_t lds = hmm_lds_bytes(cls, HMM_VIT);
-            rc = hmm_launch_class(c, db->lds_set[HMM_K_VIT_SEL][cls], k, first_of, n_in, wg, lds, [&](dim3 grid, uint32_t first) {
-                k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, aa_dev, rs_dev, rl_dev,
-                                                       d_sel.as<uint32_t>(), d_cnt.as<uint32_t>(), (uint32_t)n_rec, np, out_dev);
-            });
-        }
+        };
+        rc = prog == HMM_FWD ? run(hmm_kernels(cls).fwd, HMM_FWD, hmm_lds_bytes(cls, HMM_FWD), db->d_lse.as<uint16_t>())
+                             : run(hmm_kernels(cls).vit_sel, HMM_K_VIT_SEL, hmm_lds_bytes(cls, HMM_VIT));
         if (rc) return rc;
     }
     return GS_OK;
 }
 
-// Viterbi into vit_dev, then Forward into fwd_dev for the pairs at or above floor_dev (nullptr: every pair that has a Viterbi score), GS_HMM_NO_SCORE
-// for the rest. Queued on c's stream; the lists live in their slots until the caller's scope ends.
-static int hmm_forward_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
-                            const int32_t *floor_dev, int32_t *vit_dev, int32_t *fwd_dev, PoolBuf &d_order, PoolBuf &d_sel, PoolBuf &d_cnt)
-{
-    int rc;
-    if ((rc = hmm_search_impl(c, db, aa_dev, rs_dev, rl_dev, lens, n_rec, vit_dev, d_order))) return rc;
-    return hmm_selected_pass(c, db, HMM_FWD, aa_dev, rs_dev, rl_dev, n_rec, vit_dev, floor_dev, fwd_dev, d_order, d_sel, d_cnt);
-}
-
-// MSV of every pair into msv_dev, Viterbi into vit_dev for the pairs at or above msv_floor_dev and, with fwd_dev, Forward behind vit_floor_dev as
-// hmm_forward_impl runs it (SPEC 13.3); GS_HMM_NO_SCORE for the rest. The lists of the second selection take the place of the first's: the stream orders them.
-static int hmm_filtered_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, uint64_t n_rec,
-                             const int32_t *msv_floor_dev, const int32_t *vit_floor_dev, int32_t *msv_dev, int32_t *vit_dev, int32_t *fwd_dev, PoolBuf &d_order,
-                             PoolBuf &d_sel, PoolBuf &d_cnt)
-{
-    int rc;
-    if ((rc = hmm_search_impl(c, db, aa_dev, rs_dev, rl_dev, lens, n_rec, msv_dev, d_order, true))) return rc;
-    if ((rc = hmm_selected_pass(c, db, HMM_VIT, aa_dev, rs_dev, rl_dev, n_rec, msv_dev, msv_floor_dev, vit_dev, d_order, d_sel, d_cnt))) return rc;
-    return fwd_dev ? hmm_selected_pass(c, db, HMM_FWD, aa_dev, rs_dev, rl_dev, n_rec, vit_dev, vit_floor_dev, fwd_dev, d_order, d_sel, d_cnt) : GS_OK;
-}
-
-// ---- trace-back, host side (SPEC 13.2) ----------------------------------------------------------------------------------------------------------
+// ---- lists of pairs: trace-back (SPEC 13.2) and posterior envelopes (SPEC 13.4), host side -------------------------------------------------------------
 // max_block_cells = 0: 2^27 cells (sum of L * 64 Q) of back-pointers alive at once - 64 MB of nibbles at Q = 8 and 16, 0.5 GB at Q = 1 where a lane's
 // one nibble still takes a word. The longest record against the largest profile (65 536 x 1 280) is 84 million cells, so it fits one default block.
 static constexpr uint64_t HMM_TRACE_DEFAULT_BLOCK_CELLS = 1ull << 27;
 
-// The pairs of a call cut into blocks, for the trace and for the posterior passes (SPEC 13.4): blocks in the caller's order, a block's pairs by class
+// The pairs of a call cut into blocks: blocks in the caller's order, a block's pairs by class
 // and profile, longest record first. cost(i) is what pair i adds to its block; a block ends before the pair that would take it past cap, and always
 // holds at least one pair. A pair without a record or with an empty one is on no list. ptr_off counts the pair's back-pointer words, row_off its L + 1 rows.
 struct HmmPairBlock { uint32_t start, n, prof_start[HMM_CLASSES + 1], max_cnt[HMM_CLASSES]; };
@@ -1223,9 +1102,43 @@ static HmmPairBlocks hmm_pair_blocks(const gs_hmm_db *db, const uint64_t *lens, 
     return out;
 }
 
-// what gs_hmm_trace refuses, and gs_hmm_envelopes with max_l = GS_HMM_FWD_MAX_L, decided on host copies before anything is queued
-static int hmm_trace_check(const gs_hmm_db *db, const uint64_t *lens, uint64_t n_rec, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs,
-                           uint32_t max_l = GS_HMM_TRACE_MAX_L)
+// The blocks of a call, run: both lists go to the device, `scratch(pb)` takes what a block needs beside them, then block by block every class that
+// occurs gets per_class(d, b, cls, wg) - wg workgroups for each of its profiles b.prof_start[cls] .. b.prof_start[cls + 1], enough for the profile with the
+// most pairs - and the block per_block(d, b). All on c's stream, which is waited for once, at the end: the lists are read by the copies until then, and the
+// slots go back.
+struct HmmBlockLists { const HmmTracePair *tp; const HmmTraceProf *tprof; };
+static uint32_t hmm_block_wg(uint64_t per_profile) { return (uint32_t)std::min<uint64_t>((per_profile + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE); }
+template <class Scratch, class PerClass, class PerBlock>
+static int hmm_run_blocks(gs_ctx *c, const HmmPairBlocks &pb, Scratch scratch, PerClass per_class, PerBlock per_block)
+{
+    PoolBuf d_tp(c, SL_HMMP_PAIRS), d_tprof(c, SL_HMMP_PROFS);
+    if (!pb.blocks.empty()) {
+        int rc;
+        if ((rc = d_tp.alloc(sizeof(HmmTracePair) * pb.tp.size())) || (rc = d_tprof.alloc(sizeof(HmmTraceProf) * pb.tprof.size())) || (rc = scratch(pb))) return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(d_tp.p, pb.tp.data(), sizeof(HmmTracePair) * pb.tp.size(), hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(d_tprof.p, pb.tprof.data(), sizeof(HmmTraceProf) * pb.tprof.size(), hipMemcpyHostToDevice, c->stream));
+        const HmmBlockLists d{d_tp.as<HmmTracePair>(), d_tprof.as<HmmTraceProf>()};
+        for (const HmmPairBlock &b : pb.blocks) {
+            for (int cls = 0; cls < HMM_CLASSES; cls++)
+                if ((rc = per_class(d, b, cls, hmm_block_wg(b.max_cnt[cls])))) return rc;
+            if ((rc = per_block(d, b))) return rc;
+        }
+    }
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+// one kernel of a block for one class: kind is its (kernel, class) flag, launch(grid, tprof) queues it for a stretch of the class's profile lists
+template <class K, class Launch>
+static int hmm_block_launch(gs_ctx *c, gs_hmm_db *db, int kind, K k, size_t lds, const HmmBlockLists &d, const HmmPairBlock &b, int cls, uint32_t wg, Launch launch)
+{
+    return hmm_launch_class(c, db->lds_set[kind][cls], k, b.prof_start[cls], b.prof_start[cls + 1] - b.prof_start[cls], wg, lds,
+                            [&](dim3 grid, uint32_t first) { launch(grid, d.tprof + first); });
+}
+
+// What gs_hmm_trace refuses of its lists, and gs_hmm_envelopes with max_l = GS_HMM_FWD_MAX_L, decided on host copies before anything is queued.
+// ro: row_off of the envelopes or nullptr - every listed pair's rows must fit between its offset and the next.
+static int hmm_pair_check(const gs_hmm_db *db, const uint64_t *lens, uint64_t n_rec, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs, uint32_t max_l,
+                          const uint64_t *ro)
 {
     const uint64_t np = db->models.size();
     for (uint64_t i = 0; i < n_pairs; i++) {
@@ -1235,164 +1148,217 @@ static int hmm_trace_check(const gs_hmm_db *db, const uint64_t *lens, uint64_t n
     for (uint64_t i = 0; i < n_pairs; i++)
         GS_REQUIRE(prec[i] == GS_HMM_NO_HIT || lens[prec[i]] <= max_l, GS_ERR_UNSUPPORTED, "hmm: pair %llu names record %u of %llu residues, more than %u",
                    (unsigned long long)i, prec[i], (unsigned long long)lens[prec[i]], max_l);
+    for (uint64_t i = 0; ro && i < n_pairs; i++)
+        GS_REQUIRE(ro[i] <= ro[i + 1] && (prec[i] == GS_HMM_NO_HIT || ro[i + 1] - ro[i] >= lens[prec[i]]), GS_ERR_INVALID,
+                   "hmm: row_off leaves pair %llu fewer words than its record has residues", (unsigned long long)i);
+    return GS_OK;
+}
+// What both forms over a list of pairs refuse, and their records and pairs as the implementation reads them. ro: row_off of the envelopes where the
+// caller has it (nullptr: none); ro_host: where a _dev form keeps the host's copy. The lists are judged as soon as the host has them. A host form stages
+// aa as far as the records that a pair names reach: the others may be any length. outs_given: the outputs the form cannot do without are there;
+// rows_together: row_off, out_rows and cont_rows are all there or none is. HMM_NOTHING_TO_DO (no code of the ABI) stands for GS_OK without any work.
+enum { HMM_NOTHING_TO_DO = 1 };
+static int hmm_pair_args(gs_ctx *c, const gs_hmm_db *db, const HmmIn &in, const uint32_t *pair_rec, const uint32_t *pair_prof, uint64_t n_pairs, bool outs_given,
+                         bool rows_together, uint32_t max_l, bool prof_on_device, const uint64_t *ro, std::vector<uint64_t> &ro_host, HmmLock &lock, HmmRecs &R,
+                         HmmPairs &P)
+{
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (n_pairs == 0) return HMM_NOTHING_TO_DO;
+    GS_REQUIRE(pair_rec && pair_prof && outs_given, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(in.n_rec == 0 || in.given(), GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(rows_together, GS_ERR_INVALID, "hmm: row_off, out_rows and cont_rows go together");
+    GS_REQUIRE(in.n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
+    int rc;
+    if (in.host) {
+        if ((rc = hmm_pair_check(db, in.rl, in.n_rec, pair_rec, pair_prof, n_pairs, max_l, ro))) return rc;
+        uint64_t n_bytes = 0;
+        for (uint64_t i = 0; i < n_pairs; i++)
+            if (pair_rec[i] != GS_HMM_NO_HIT && in.rl[pair_rec[i]]) n_bytes = std::max(n_bytes, in.rs[pair_rec[i]] + in.rl[pair_rec[i]]);
+        hmm_lock(c, lock);
+        if ((rc = R.fill(in, n_bytes)) || (rc = P.fill(true, pair_rec, pair_prof, n_pairs, prof_on_device))) return rc;
+    } else {
+        hmm_lock(c, lock);
+        if ((rc = P.fill(false, pair_rec, pair_prof, n_pairs, prof_on_device))) return rc;
+        if (ro) {
+            ro_host.resize(n_pairs + 1);
+            GS_HIP_CHECK(hipMemcpyAsync(ro_host.data(), ro, 8 * (n_pairs + 1), hipMemcpyDeviceToHost, c->stream));
+        }
+        if ((rc = R.fill(in, 0)) || (rc = hmm_pair_check(db, R.lens, in.n_rec, P.rec, P.prof, n_pairs, max_l, ro ? ro_host.data() : nullptr))) return rc;
+    }
     return GS_OK;
 }
 
-// lens, prec, pprof: host copies that hmm_trace_check has passed; everything else device memory. Blocks of pairs in the caller's order, each block's pairs
-// by class and profile, longest record first; a block is a trace launch per class that occurs and one walk, all on c's stream, which is waited for at the end.
-static int hmm_trace_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, const uint32_t *prec,
-                          const uint32_t *pprof, const uint32_t *pprof_dev, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_dev,
-                          uint32_t *ndom_dev, int32_t *dom_dev)
+// R, P: the records and pairs of the call, which hmm_pair_check has passed; everything else device memory. A block is a trace launch per class that
+// occurs and one walk.
+static int hmm_trace_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, const HmmPairs &P, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_dev, uint32_t *ndom_dev,
+                          int32_t *dom_dev)
 {
-    const uint64_t cap = max_block_cells ? max_block_cells : HMM_TRACE_DEFAULT_BLOCK_CELLS;
-    const uint64_t n_dom_words = n_pairs * max_dom * GS_HMM_DOM_WORDS, n_fill = std::max(n_pairs, n_dom_words);
+    const uint64_t n_pairs = P.n, n_dom_words = n_pairs * max_dom * GS_HMM_DOM_WORDS, n_fill = std::max(n_pairs, n_dom_words);
     GS_REQUIRE(n_fill < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many domain slots");
     {
         ProfScope ps(c, FAM_SEARCH);
         k_hmm_trace_fill<<<(unsigned)((n_fill + 255) / 256), 256, 0, c->stream>>>(n_pairs, n_dom_words, raw_dev, ndom_dev, dom_dev);
         GS_HIP_CHECK(hipGetLastError());
     }
-    const HmmPairBlocks pb = hmm_pair_blocks(db, lens, prec, pprof, n_pairs, cap, [&](uint64_t i) {
-        return lens[prec[i]] * 64 * HMM_CLASS_Q[hmm_class_of(db->desc[pprof[i]].M)];
+    const HmmPairBlocks pb = hmm_pair_blocks(db, R.lens, P.rec, P.prof, n_pairs, max_block_cells ? max_block_cells : HMM_TRACE_DEFAULT_BLOCK_CELLS, [&](uint64_t i) {
+        return R.lens[P.rec[i]] * 64 * HMM_CLASS_Q[hmm_class_of(db->desc[P.prof[i]].M)];
     });
-    const std::vector<HmmTracePair> &tp = pb.tp;
-    const std::vector<HmmTraceProf> &tprof = pb.tprof;
-    const std::vector<HmmPairBlock> &blocks = pb.blocks;
-    const uint64_t max_ptr = pb.max_ptr, max_rows = pb.max_rows;
-    if (!blocks.empty()) {
-        PoolBuf d_tp(c, SL_HMMT_PAIRS), d_tprof(c, SL_HMMT_PROFS), d_ptr(c, SL_HMMT_PTR), d_rows(c, SL_HMMT_ROWS);
-        int rc;
-        if ((rc = d_tp.alloc(sizeof(HmmTracePair) * tp.size())) || (rc = d_tprof.alloc(sizeof(HmmTraceProf) * tprof.size())) || (rc = d_ptr.alloc(4 * max_ptr)) ||
-            (rc = d_rows.alloc(sizeof(int4) * max_rows)))
-            return rc;
-        GS_HIP_CHECK(hipMemcpyAsync(d_tp.p, tp.data(), sizeof(HmmTracePair) * tp.size(), hipMemcpyHostToDevice, c->stream));
-        GS_HIP_CHECK(hipMemcpyAsync(d_tprof.p, tprof.data(), sizeof(HmmTraceProf) * tprof.size(), hipMemcpyHostToDevice, c->stream));
-        for (const HmmPairBlock &b : blocks) {
-            for (int cls = 0; cls < HMM_CLASSES; cls++) {
-                const auto k = hmm_kernels(cls).trace;
-                const size_t lds = hmm_lds_bytes(cls, HMM_TRACE);
-                const uint32_t wg = std::min<uint32_t>((b.max_cnt[cls] + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
-                rc = hmm_launch_class(c, db->lds_set[HMM_TRACE][cls], k, b.prof_start[cls], b.prof_start[cls + 1] - b.prof_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
-                    k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(), aa_dev,
-                                                           rs_dev, rl_dev, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev);
-                });
-                if (rc) return rc;
-            }
+    PoolBuf d_ptr(c, SL_HMMT_PTR), d_rows(c, SL_HMMT_ROWS);
+    return hmm_run_blocks(
+        c, pb, [&](const HmmPairBlocks &pb) { int rc = d_ptr.alloc(4 * pb.max_ptr); return rc ? rc : d_rows.alloc(sizeof(int4) * pb.max_rows); },
+        [&](const HmmBlockLists &d, const HmmPairBlock &b, int cls, uint32_t wg) -> int {
+            const auto k = hmm_kernels(cls).trace;
+            const size_t lds = hmm_lds_bytes(cls, HMM_TRACE);
+            return hmm_block_launch(c, db, HMM_TRACE, k, lds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), tprof, d.tp, R.aa, R.rs, R.rl, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev);
+            });
+        },
+        [&](const HmmBlockLists &d, const HmmPairBlock &b) -> int {
             ProfScope ps(c, FAM_SEARCH);
-            k_hmm_walk<<<(b.n + HMM_WALK_BLOCK - 1) / HMM_WALK_BLOCK, HMM_WALK_BLOCK, 0, c->stream>>>(db->d_desc.as<HmmDesc>(), d_tp.as<HmmTracePair>() + b.start, b.n, pprof_dev,
-                                                                                                        rl_dev, d_ptr.as<uint32_t>(), d_rows.as<int4>(), raw_dev, max_dom,
-                                                                                                        ndom_dev, dom_dev);
+            k_hmm_walk<<<(b.n + HMM_WALK_BLOCK - 1) / HMM_WALK_BLOCK, HMM_WALK_BLOCK, 0, c->stream>>>(db->d_desc.as<HmmDesc>(), d.tp + b.start, b.n, P.prof_dev, R.rl, d_ptr.as<uint32_t>(),
+                                                                                                        d_rows.as<int4>(), raw_dev, max_dom, ndom_dev, dom_dev);
             GS_HIP_CHECK(hipGetLastError());
-        }
-        GS_HIP_CHECK(stream_wait(c));       // the lists are read by the copies until here, and the slots go back
-        return GS_OK;
-    }
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+            return GS_OK;
+        });
 }
 
-// ---- posterior envelopes, host side (SPEC 13.4) ---------------------------------------------------------------------------------------------------
-// lens, prec, pprof: host copies that hmm_trace_check has passed under Forward's length limit; everything else device memory. Blocks of pairs in the caller's order, at most
-// max_block_rows kept rows (sum of L + 1) each, a block's pairs by class and profile, longest record first. A block is a Forward-with-rows and a Backward
-// launch per class that occurs, k_hmm_envelopes, and a k_hmm_env_score launch per class, all on c's stream, which is waited for at the end.
-static int hmm_env_impl(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rs_dev, const uint64_t *rl_dev, const uint64_t *lens, const uint32_t *prec,
-                        const uint32_t *pprof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_dev, int32_t *bck_dev, uint32_t *nenv_dev,
-                        int32_t *env_dev, const uint64_t *row_off_dev, int32_t *out_rows_dev, int32_t *cont_rows_dev)
+// R, P: the records and pairs of the call, which hmm_pair_check has passed under Forward's length limit; everything else device memory. Blocks of at most
+// max_block_rows kept rows (sum of L + 1). A block is a Forward-with-rows and a Backward launch per class that occurs, k_hmm_envelopes, and a
+// k_hmm_env_score launch per class.
+static int hmm_env_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, const HmmPairs &P, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_dev, int32_t *bck_dev,
+                        uint32_t *nenv_dev, int32_t *env_dev, const uint64_t *row_off_dev, int32_t *out_rows_dev, int32_t *cont_rows_dev)
 {
-    const uint64_t cap = max_block_rows ? max_block_rows : HMM_ENV_DEFAULT_BLOCK_ROWS;
-    const uint64_t n_env_words = n_pairs * max_env * GS_HMM_ENV_WORDS, n_fill = std::max(n_pairs, n_env_words);
+    const uint64_t n_pairs = P.n, n_env_words = n_pairs * max_env * GS_HMM_ENV_WORDS, n_fill = std::max(n_pairs, n_env_words);
     GS_REQUIRE(n_fill < (1ull << 31) * 256, GS_ERR_UNSUPPORTED, "hmm: too many envelope slots");
     {
         ProfScope ps(c, FAM_SEARCH);
         k_hmm_env_fill<<<(unsigned)((n_fill + 255) / 256), 256, 0, c->stream>>>(n_pairs, n_env_words, fwd_dev, bck_dev, nenv_dev, env_dev);
         GS_HIP_CHECK(hipGetLastError());
     }
-    const HmmPairBlocks pb = hmm_pair_blocks(db, lens, prec, pprof, n_pairs, cap, [&](uint64_t i) { return lens[prec[i]] + 1; });
-    const std::vector<HmmTracePair> &tp = pb.tp;
-    const std::vector<HmmTraceProf> &tprof = pb.tprof;
-    const std::vector<HmmPairBlock> &blocks = pb.blocks;
-    const uint64_t max_rows = pb.max_rows;
-    if (!blocks.empty()) {
-        PoolBuf d_tp(c, SL_HMME_PAIRS), d_tprof(c, SL_HMME_PROFS), d_frows(c, SL_HMME_FROWS), d_brows(c, SL_HMME_BROWS);
-        int rc;
-        if ((rc = d_tp.alloc(sizeof(HmmTracePair) * tp.size())) || (rc = d_tprof.alloc(sizeof(HmmTraceProf) * tprof.size())) || (rc = d_frows.alloc(sizeof(int4) * max_rows)) ||
-            (rc = d_brows.alloc(sizeof(int2) * max_rows)))
-            return rc;
-        GS_HIP_CHECK(hipMemcpyAsync(d_tp.p, tp.data(), sizeof(HmmTracePair) * tp.size(), hipMemcpyHostToDevice, c->stream));
-        GS_HIP_CHECK(hipMemcpyAsync(d_tprof.p, tprof.data(), sizeof(HmmTraceProf) * tprof.size(), hipMemcpyHostToDevice, c->stream));
-        for (const HmmPairBlock &b : blocks) {
-            for (int cls = 0; cls < HMM_CLASSES; cls++) {
-                const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
-                const uint32_t n_in = b.prof_start[cls + 1] - b.prof_start[cls];
-                const uint32_t wg = std::min<uint32_t>((b.max_cnt[cls] + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
-                const auto kf = hmm_kernels(cls).fwd_rows;
-                rc = hmm_launch_class(c, db->lds_set[HMM_FWD_ROWS][cls], kf, b.prof_start[cls], n_in, wg, lds, [&](dim3 grid, uint32_t first) {
-                    kf<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(),
-                                                            db->d_lse.as<uint16_t>(), aa_dev, rs_dev, rl_dev, d_frows.as<int4>(), fwd_dev);
-                });
-                if (rc) return rc;
-                const auto kb = hmm_kernels(cls).back;
-                rc = hmm_launch_class(c, db->lds_set[HMM_K_BACK][cls], kb, b.prof_start[cls], n_in, wg, lds, [&](dim3 grid, uint32_t first) {
-                    kb<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(),
-                                                            db->d_lse.as<uint16_t>(), aa_dev, rs_dev, rl_dev, d_brows.as<int2>(), bck_dev);
-                });
-                if (rc) return rc;
-            }
+    const HmmPairBlocks pb = hmm_pair_blocks(db, R.lens, P.rec, P.prof, n_pairs, max_block_rows ? max_block_rows : HMM_ENV_DEFAULT_BLOCK_ROWS,
+                                             [&](uint64_t i) { return R.lens[P.rec[i]] + 1; });
+    PoolBuf d_frows(c, SL_HMME_FROWS), d_brows(c, SL_HMME_BROWS);
+    const int32_t *tables = db->d_tables.as<int32_t>();
+    const HmmDesc *desc = db->d_desc.as<HmmDesc>();
+    const uint16_t *lse = db->d_lse.as<uint16_t>();
+    return hmm_run_blocks(
+        c, pb, [&](const HmmPairBlocks &pb) { int rc = d_frows.alloc(sizeof(int4) * pb.max_rows); return rc ? rc : d_brows.alloc(sizeof(int2) * pb.max_rows); },
+        [&](const HmmBlockLists &d, const HmmPairBlock &b, int cls, uint32_t wg) -> int {
+            const auto kf = hmm_kernels(cls).fwd_rows;
+            const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+            int rc = hmm_block_launch(c, db, HMM_FWD_ROWS, kf, lds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                kf<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, tprof, d.tp, lse, R.aa, R.rs, R.rl, d_frows.as<int4>(), fwd_dev);
+            });
+            if (rc) return rc;
+            const auto kb = hmm_kernels(cls).back;
+            return hmm_block_launch(c, db, HMM_K_BACK, kb, lds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                kb<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, tprof, d.tp, lse, R.aa, R.rs, R.rl, d_brows.as<int2>(), bck_dev);
+            });
+        },
+        [&](const HmmBlockLists &d, const HmmPairBlock &b) -> int {
             {
                 ProfScope ps(c, FAM_SEARCH);
-                k_hmm_envelopes<<<b.n, HMM_ENV_BLOCK, 0, c->stream>>>(d_tp.as<HmmTracePair>() + b.start, rl_dev, db->d_lse.as<uint16_t>(), d_frows.as<int4>(), d_brows.as<int2>(),
-                                                                       fwd_dev, max_env, nenv_dev, env_dev, row_off_dev, out_rows_dev, cont_rows_dev);
+                k_hmm_envelopes<<<b.n, HMM_ENV_BLOCK, 0, c->stream>>>(d.tp + b.start, R.rl, lse, d_frows.as<int4>(), d_brows.as<int2>(), fwd_dev, max_env, nenv_dev, env_dev,
+                                                                       row_off_dev, out_rows_dev, cont_rows_dev);
                 GS_HIP_CHECK(hipGetLastError());
             }
-            for (int cls = 0; max_env && cls < HMM_CLASSES; cls++) {
-                const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
-                const uint64_t slots = (uint64_t)b.max_cnt[cls] * max_env;
-                const uint32_t wg = (uint32_t)std::min<uint64_t>((slots + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
+            for (int cls = 0; max_env && cls < HMM_CLASSES; cls++) {         // the envelopes' own scores: a wave per (pair, envelope slot)
                 const auto ks = hmm_kernels(cls).env_score;
-                rc = hmm_launch_class(c, db->lds_set[HMM_K_ENV_SCORE][cls], ks, b.prof_start[cls], b.prof_start[cls + 1] - b.prof_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
-                    ks<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), d_tprof.as<HmmTraceProf>() + first, d_tp.as<HmmTracePair>(),
-                                                            db->d_lse.as<uint16_t>(), aa_dev, rs_dev, rl_dev, max_env, nenv_dev, env_dev);
+                const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+                int rc = hmm_block_launch(c, db, HMM_K_ENV_SCORE, ks, lds, d, b, cls, hmm_block_wg((uint64_t)b.max_cnt[cls] * max_env), [&](dim3 grid, const HmmTraceProf *tprof) {
+                    ks<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, tprof, d.tp, lse, R.aa, R.rs, R.rl, max_env, nenv_dev, env_dev);
                 });
                 if (rc) return rc;
             }
-        }
-        GS_HIP_CHECK(stream_wait(c));       // the lists are read by the copies until here, and the slots go back
-        return GS_OK;
+            return GS_OK;
+        });
+}
+
+// ---- the bodies of the ABI pairs: in.host says which entry called -----------------------------------------------------------------------------------
+// The four pairs that score every (record, profile) pair: gs_hmm_search (Viterbi), gs_hmm_search_msv (MSV; SPEC 13.3), gs_hmm_search_forward (Viterbi,
+// then Forward for the pairs at or above vit_floor; SPEC 13.1) and gs_hmm_search_filtered (MSV, Viterbi at or above msv_floor and, with fwd_out, Forward
+// as before). A floor of nullptr takes every pair that has the score in front of it; a pair that is not taken gets GS_HMM_NO_SCORE. `needed` is the output
+// the pair cannot do without; a matrix that has to be computed although the caller did not ask for it goes to its slot.
+static int hmm_scores_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, bool run_msv, bool run_vit, const int32_t *msv_floor, const int32_t *vit_floor,
+                           int32_t *msv_out, int32_t *vit_out, int32_t *fwd_out, const void *needed)
+{
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (in.n_rec == 0) return GS_OK;
+    GS_REQUIRE(in.given() && needed, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(in.n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
+    const uint32_t max_l = fwd_out ? GS_HMM_FWD_MAX_L : GS_HMM_MAX_L;
+    const uint64_t np = db->models.size(), n_bytes = 4 * in.n_rec * np;
+    HmmLock lock;
+    HmmRecs R(c); HmmArg mfloor(c, SL_HMMB_MSV_FLOOR), floor(c, SL_HMMB_FLOOR), msv(c, SL_HMM_MSV), vit(c, SL_HMM_VIT), fwd(c, SL_HMM_FWD); HmmLists l(c);
+    int rc;
+    if (in.host) {                      // the lengths are judged as soon as the host has them
+        if ((rc = hmm_check_lens(in.rl, in.n_rec, max_l))) return rc;
+        uint64_t aa_bytes = 0;          // where the residues of all records end
+        for (uint64_t r = 0; r < in.n_rec; r++) if (in.rl[r]) aa_bytes = std::max(aa_bytes, in.rs[r] + in.rl[r]);
+        hmm_lock(c, lock);
+        if ((rc = R.fill(in, aa_bytes))) return rc;
+    } else {
+        hmm_lock(c, lock);
+        if ((rc = R.fill(in, 0)) || (rc = hmm_check_lens(R.lens, in.n_rec, max_l))) return rc;
     }
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+    const bool select_vit = run_msv && run_vit;
+    if ((run_msv && (rc = msv.bind(in.host, msv_out, n_bytes, HMM_DOWN))) || (run_vit && (rc = vit.bind(in.host, vit_out, n_bytes, HMM_DOWN))) ||
+        (fwd_out && (rc = fwd.bind(in.host, fwd_out, n_bytes, HMM_DOWN))) || (select_vit && msv_floor && (rc = mfloor.bind(in.host, msv_floor, 4 * np, HMM_UP))) ||
+        (fwd_out && vit_floor && (rc = floor.bind(in.host, vit_floor, 4 * np, HMM_UP))))
+        return rc;
+    if ((run_msv && (rc = hmm_search_impl(c, db, R, msv.as<int32_t>(), l.order, true))) ||
+        (run_vit && (rc = select_vit ? hmm_selected_pass(c, db, HMM_VIT, R, msv.as<int32_t>(), mfloor.as<int32_t>(), vit.as<int32_t>(), l)
+                                     : hmm_search_impl(c, db, R, vit.as<int32_t>(), l.order))) ||
+        (fwd_out && (rc = hmm_selected_pass(c, db, HMM_FWD, R, vit.as<int32_t>(), floor.as<int32_t>(), fwd.as<int32_t>(), l))))
+        return rc;
+    return in.host || select_vit || fwd_out ? hmm_fetch(c, {&msv, &vit, &fwd}) : GS_OK;       // (hmm_search_impl has waited, a selected pass is still queued)
+}
+
+// gs_hmm_trace{,_dev}
+static int hmm_trace_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, const uint32_t *pair_rec, const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_dom,
+                          uint64_t max_block_cells, int32_t *raw_out, uint32_t *n_dom_out, int32_t *dom_out)
+{
+    HmmLock lock;
+    HmmRecs R(c); HmmPairs P(c); HmmArg raw(c, SL_HMMB_PAIR_SCORE), nd(c, SL_HMMB_PAIR_COUNT), dom(c, SL_HMMB_PAIR_ITEMS);
+    std::vector<uint64_t> no_rows;
+    int rc = hmm_pair_args(c, db, in, pair_rec, pair_prof, n_pairs, raw_out && n_dom_out && (dom_out || max_dom == 0), true, GS_HMM_TRACE_MAX_L, true, nullptr, no_rows, lock, R, P);
+    if (rc) return rc == HMM_NOTHING_TO_DO ? GS_OK : rc;
+    if ((rc = raw.bind(in.host, raw_out, 4 * n_pairs, HMM_DOWN)) || (rc = nd.bind(in.host, n_dom_out, 4 * n_pairs, HMM_DOWN)) ||
+        (rc = dom.bind(in.host, dom_out, 4 * n_pairs * max_dom * GS_HMM_DOM_WORDS, HMM_DOWN)) ||
+        (rc = hmm_trace_impl(c, db, R, P, max_dom, max_block_cells, raw.as<int32_t>(), nd.as<uint32_t>(), dom.as<int32_t>())))
+        return rc;
+    return in.host ? hmm_fetch(c, {&raw, &nd, &dom}) : GS_OK;     // (hmm_trace_impl has waited)
+}
+
+// gs_hmm_envelopes{,_dev}. A host form uploads out_rows and cont_rows too: the rows of a pair that gets none keep what the caller's arrays hold.
+static int hmm_env_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, const uint32_t *pair_rec, const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env,
+                        uint64_t max_block_rows, int32_t *fwd_out, int32_t *bck_out, uint32_t *n_env_out, int32_t *env_out, const uint64_t *row_off, int32_t *out_rows,
+                        int32_t *cont_rows)
+{
+    HmmLock lock;
+    HmmRecs R(c); HmmPairs P(c);
+    HmmArg fwd(c, SL_HMMB_PAIR_SCORE), bck(c, SL_HMMB_PAIR_BCK), ne(c, SL_HMMB_PAIR_COUNT), env(c, SL_HMMB_PAIR_ITEMS), ro(c, SL_HMMB_ROW_OFF), out(c, SL_HMMB_OUT_ROWS),
+        cont(c, SL_HMMB_CONT_ROWS);
+    std::vector<uint64_t> ro_host;
+    int rc = hmm_pair_args(c, db, in, pair_rec, pair_prof, n_pairs, fwd_out && bck_out && n_env_out && (env_out || max_env == 0),
+                           !row_off == !out_rows && !row_off == !cont_rows, GS_HMM_FWD_MAX_L, false, row_off, ro_host, lock, R, P);
+    if (rc) return rc == HMM_NOTHING_TO_DO ? GS_OK : rc;
+    const uint64_t n_row_bytes = in.host && row_off ? 4 * row_off[n_pairs] : 0;
+    if ((rc = fwd.bind(in.host, fwd_out, 4 * n_pairs, HMM_DOWN)) || (rc = bck.bind(in.host, bck_out, 4 * n_pairs, HMM_DOWN)) ||
+        (rc = ne.bind(in.host, n_env_out, 4 * n_pairs, HMM_DOWN)) || (rc = env.bind(in.host, env_out, 4 * n_pairs * max_env * GS_HMM_ENV_WORDS, HMM_DOWN)))
+        return rc;
+    if (row_off && ((rc = ro.bind(in.host, row_off, 8 * (n_pairs + 1), HMM_UP)) || (rc = out.bind(in.host, out_rows, n_row_bytes, HMM_UP | HMM_DOWN)) ||
+                    (rc = cont.bind(in.host, cont_rows, n_row_bytes, HMM_UP | HMM_DOWN))))
+        return rc;
+    if ((rc = hmm_env_impl(c, db, R, P, max_env, max_block_rows, fwd.as<int32_t>(), bck.as<int32_t>(), ne.as<uint32_t>(), env.as<int32_t>(), ro.as<uint64_t>(), out.as<int32_t>(),
+                           cont.as<int32_t>())))
+        return rc;
+    return in.host ? hmm_fetch(c, {&fwd, &bck, &ne, &env, &out, &cont}) : GS_OK;        // (hmm_env_impl has waited)
 }
 
 }  // namespace gs
 
 extern "C" {
-
-int gs_hmm_parse_mem(const void *text, uint64_t n_bytes, uint32_t model, gs_hmm_info *info_out, int32_t *tables_out, uint64_t cap_words, uint32_t *n_models_out)
-{
-    using namespace gs;
-    GS_REQUIRE(text || n_bytes == 0, GS_ERR_INVALID, "null argument");
-    std::vector<HmmModel> ms;
-    int rc = hmm_parse_all((const char *)text, (size_t)n_bytes, ms);
-    if (rc) return rc;
-    if (n_models_out) *n_models_out = (uint32_t)ms.size();
-    GS_REQUIRE(model < ms.size(), GS_ERR_INVALID, "hmm: model %u of %zu", model, ms.size());
-    if (info_out) *info_out = ms[model].info;
-    if (tables_out) {
-        GS_REQUIRE(cap_words >= ms[model].tab.size(), GS_ERR_INVALID, "hmm: the table needs %zu words, cap_words = %llu", ms[model].tab.size(), (unsigned long long)cap_words);
-        memcpy(tables_out, ms[model].tab.data(), 4 * ms[model].tab.size());
-    }
-    return GS_OK;
-}
-
-int gs_hmm_specials(uint64_t L, uint32_t M, int32_t out[6])
-{
-    using namespace gs;
-    GS_REQUIRE(out && L >= 1 && M >= 1, GS_ERR_INVALID, "bad argument");
-    GS_REQUIRE(L <= GS_HMM_MAX_L && M <= GS_HMM_MAX_M, GS_ERR_UNSUPPORTED, "hmm: L = %llu, M = %u: larger than the limits", (unsigned long long)L, M);
-    const HmmSpecials s = hmm_specials((uint32_t)L);
-    out[0] = s.tloop; out[1] = s.tmove; out[2] = s.null; out[3] = hmm_tbm(M); out[4] = s.nloop; out[5] = s.nmove;
-    return GS_OK;
-}
 
 int gs_hmm_db_load_mem(gs_ctx *c, const void *const *texts, const uint64_t *n_bytes, uint64_t n_texts, gs_hmm_db **out)
 {
@@ -1466,65 +1432,21 @@ int gs_hmm_db_tables(gs_hmm_db *db, uint64_t p, int32_t *tables_out, uint64_t ca
     return GS_OK;
 }
 
-}  // extern "C"
-
-namespace gs {
-
-// gs_hmm_search_dev / gs_hmm_search, and with msv their MSV twins (SPEC 13.3): the same arguments, refusals and staging
-static int hmm_search_dev_form(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
-                               int32_t *score_out_dev, bool msv)
-{
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_rec == 0) return GS_OK;
-    GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && score_out_dev, GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
-    GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens;
-    int rc;
-    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_check_lens(lens.data(), n_rec))) return rc;
-    PoolBuf d_order(c, SL_HMM_ORDER);
-    return hmm_search_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, score_out_dev, d_order, msv);
-}
-
-static int hmm_search_host_form(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *score_out, bool msv)
-{
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_rec == 0) return GS_OK;
-    GS_REQUIRE(rec_start && rec_len && score_out, GS_ERR_INVALID, "null argument");
-    int rc = hmm_check_lens(rec_len, n_rec);
-    if (rc) return rc;
-    const uint64_t np = db->models.size();
-    GS_CTX_LOCK(c);
-    PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_order(c, SL_HMM_ORDER);
-    if ((rc = hmm_stage_records(c, aa, hmm_records_end(rec_start, rec_len, n_rec), rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_score.alloc(4 * n_rec * np))) return rc;
-    if ((rc = hmm_search_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, d_score.as<int32_t>(), d_order, msv))) return rc;
-    GS_HIP_CHECK(hipMemcpyAsync(score_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
-}
-
-}  // namespace gs
-
-extern "C" {
-
 int gs_hmm_search_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int32_t *score_out_dev)
 {
-    return gs::hmm_search_dev_form(c, db, aa_dev, rec_start_dev, rec_len_dev, n_rec, score_out_dev, false);
+    return gs::hmm_scores_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, false, true, nullptr, nullptr, nullptr, score_out_dev, nullptr, score_out_dev);
 }
-
 int gs_hmm_search(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *score_out)
 {
-    return gs::hmm_search_host_form(c, db, aa, rec_start, rec_len, n_rec, score_out, false);
+    return gs::hmm_scores_form(c, db, {true, aa, rec_start, rec_len, n_rec}, false, true, nullptr, nullptr, nullptr, score_out, nullptr, score_out);
 }
-
 int gs_hmm_search_msv_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int32_t *msv_out_dev)
 {
-    return gs::hmm_search_dev_form(c, db, aa_dev, rec_start_dev, rec_len_dev, n_rec, msv_out_dev, true);
+    return gs::hmm_scores_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, true, false, nullptr, nullptr, msv_out_dev, nullptr, nullptr, msv_out_dev);
 }
-
 int gs_hmm_search_msv(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *msv_out)
 {
-    return gs::hmm_search_host_form(c, db, aa, rec_start, rec_len, n_rec, msv_out, true);
+    return gs::hmm_scores_form(c, db, {true, aa, rec_start, rec_len, n_rec}, true, false, nullptr, nullptr, msv_out, nullptr, nullptr, msv_out);
 }
 
 int gs_hmm_best_hits_dev(gs_ctx *c, gs_hmm_db *db, const int32_t *score_dev, uint64_t n_rec, const uint64_t *genome_rec_off_dev, uint64_t n_genomes,
@@ -1554,281 +1476,54 @@ int gs_hmm_best_hits_dev(gs_ctx *c, gs_hmm_db *db, const int32_t *score_dev, uin
     return GS_OK;
 }
 
-int gs_hmm_logsum_table(uint16_t *out, uint64_t cap)
-{
-    GS_REQUIRE(out, GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(cap >= GS_HMM_LSE_N, GS_ERR_INVALID, "hmm: the table has %u entries, cap = %llu", GS_HMM_LSE_N, (unsigned long long)cap);
-    for (uint32_t j = 0; j < GS_HMM_LSE_N; j++) out[j] = gs::hmm_lse_entry(j);
-    return GS_OK;
-}
-
-int gs_hmm_parse_stats_mem(const void *text, uint64_t n_bytes, uint32_t model, double out[6], uint32_t *has_out)
-{
-    using namespace gs;
-    GS_REQUIRE((text || n_bytes == 0) && out && has_out, GS_ERR_INVALID, "null argument");
-    std::vector<HmmModel> ms;
-    int rc = hmm_parse_all((const char *)text, (size_t)n_bytes, ms);
-    if (rc) return rc;
-    GS_REQUIRE(model < ms.size(), GS_ERR_INVALID, "hmm: model %u of %zu", model, ms.size());
-    for (int i = 0; i < 6; i++) out[i] = ms[model].stats[i];
-    *has_out = ms[model].has_stats;
-    return GS_OK;
-}
-
-int gs_hmm_viterbi_floor(double mu, double lambda, double p, int32_t *floor_out)
-{
-    GS_REQUIRE(floor_out, GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(lambda > 0 && p > 0 && p < 1 && mu == mu, GS_ERR_INVALID, "hmm: the floor needs lambda > 0 and 0 < P < 1 (lambda = %g, P = %g)", lambda, p);
-    const double units = ::floor((mu - ::log(-::log1p(-p)) / lambda) * 1024.0 + 0.5);
-    *floor_out = units <= (double)(INT32_MIN + 1) ? INT32_MIN + 1 : (units >= (double)INT32_MAX ? INT32_MAX : (int32_t)units);
-    return GS_OK;
-}
-
 int gs_hmm_search_forward_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
                               const int32_t *vit_floor_dev, int32_t *vit_out_dev, int32_t *fwd_out_dev)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_rec == 0) return GS_OK;
-    GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && fwd_out_dev, GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
-    GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens;
-    int rc;
-    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_check_lens(lens.data(), n_rec, GS_HMM_FWD_MAX_L))) return rc;
-    PoolBuf d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT), d_vit(c, SL_HMM_VIT);
-    if (!vit_out_dev) {
-        if ((rc = d_vit.alloc(4 * n_rec * db->models.size()))) return rc;
-        vit_out_dev = d_vit.as<int32_t>();
-    }
-    if ((rc = hmm_forward_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, vit_floor_dev, vit_out_dev, fwd_out_dev, d_order, d_sel, d_cnt))) return rc;
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+    return gs::hmm_scores_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, false, true, nullptr, vit_floor_dev, nullptr, vit_out_dev, fwd_out_dev, fwd_out_dev);
 }
-
 int gs_hmm_search_forward(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const int32_t *vit_floor,
                           int32_t *vit_out, int32_t *fwd_out)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_rec == 0) return GS_OK;
-    GS_REQUIRE(rec_start && rec_len && fwd_out, GS_ERR_INVALID, "null argument");
-    int rc = hmm_check_lens(rec_len, n_rec, GS_HMM_FWD_MAX_L);
-    if (rc) return rc;
-    const uint64_t np = db->models.size();
-    GS_CTX_LOCK(c);
-    PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_fwd(c, SL_HMMB_FWD), d_floor(c, SL_HMMB_FLOOR),
-        d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT);
-    if ((rc = hmm_stage_records(c, aa, hmm_records_end(rec_start, rec_len, n_rec), rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_score.alloc(4 * n_rec * np)) ||
-        (rc = d_fwd.alloc(4 * n_rec * np)))
-        return rc;
-    if (vit_floor) {
-        if ((rc = d_floor.alloc(4 * np))) return rc;
-        GS_HIP_CHECK(hipMemcpyAsync(d_floor.p, vit_floor, 4 * np, hipMemcpyHostToDevice, c->stream));
-    }
-    if ((rc = hmm_forward_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, vit_floor ? d_floor.as<int32_t>() : nullptr,
-                               d_score.as<int32_t>(), d_fwd.as<int32_t>(), d_order, d_sel, d_cnt)))
-        return rc;
-    if (vit_out) GS_HIP_CHECK(hipMemcpyAsync(vit_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+    return gs::hmm_scores_form(c, db, {true, aa, rec_start, rec_len, n_rec}, false, true, nullptr, vit_floor, nullptr, vit_out, fwd_out, fwd_out);
 }
 
 int gs_hmm_search_filtered_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
                                const int32_t *msv_floor_dev, const int32_t *vit_floor_dev, int32_t *msv_out_dev, int32_t *vit_out_dev, int32_t *fwd_out_dev)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_rec == 0) return GS_OK;
-    GS_REQUIRE(aa_dev && rec_start_dev && rec_len_dev && vit_out_dev, GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
-    GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens;
-    int rc;
-    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_check_lens(lens.data(), n_rec, fwd_out_dev ? GS_HMM_FWD_MAX_L : GS_HMM_MAX_L))) return rc;
-    PoolBuf d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT), d_msv(c, SL_HMM_MSV);
-    if (!msv_out_dev) {
-        if ((rc = d_msv.alloc(4 * n_rec * db->models.size()))) return rc;
-        msv_out_dev = d_msv.as<int32_t>();
-    }
-    if ((rc = hmm_filtered_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), n_rec, msv_floor_dev, vit_floor_dev, msv_out_dev, vit_out_dev, fwd_out_dev, d_order,
-                                d_sel, d_cnt)))
-        return rc;
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+    return gs::hmm_scores_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, true, true, msv_floor_dev, vit_floor_dev, msv_out_dev, vit_out_dev, fwd_out_dev, vit_out_dev);
 }
-
 int gs_hmm_search_filtered(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const int32_t *msv_floor,
                            const int32_t *vit_floor, int32_t *msv_out, int32_t *vit_out, int32_t *fwd_out)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_rec == 0) return GS_OK;
-    GS_REQUIRE(rec_start && rec_len && vit_out, GS_ERR_INVALID, "null argument");
-    int rc = hmm_check_lens(rec_len, n_rec, fwd_out ? GS_HMM_FWD_MAX_L : GS_HMM_MAX_L);
-    if (rc) return rc;
-    const uint64_t np = db->models.size();
-    GS_CTX_LOCK(c);
-    PoolBuf d_aa(c, SL_HMMB_AA), d_rs(c, SL_HMMB_REC_START), d_rl(c, SL_HMMB_REC_LEN), d_score(c, SL_HMMB_SCORE), d_fwd(c, SL_HMMB_FWD), d_floor(c, SL_HMMB_FLOOR),
-        d_msv(c, SL_HMMB_MSV), d_msv_floor(c, SL_HMMB_MSV_FLOOR), d_order(c, SL_HMM_ORDER), d_sel(c, SL_HMM_SEL), d_cnt(c, SL_HMM_SEL_COUNT);
-    if ((rc = hmm_stage_records(c, aa, hmm_records_end(rec_start, rec_len, n_rec), rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_score.alloc(4 * n_rec * np)) ||
-        (rc = d_msv.alloc(4 * n_rec * np)) || (fwd_out && (rc = d_fwd.alloc(4 * n_rec * np))))
-        return rc;
-    if (msv_floor) {
-        if ((rc = d_msv_floor.alloc(4 * np))) return rc;
-        GS_HIP_CHECK(hipMemcpyAsync(d_msv_floor.p, msv_floor, 4 * np, hipMemcpyHostToDevice, c->stream));
-    }
-    if (fwd_out && vit_floor) {
-        if ((rc = d_floor.alloc(4 * np))) return rc;
-        GS_HIP_CHECK(hipMemcpyAsync(d_floor.p, vit_floor, 4 * np, hipMemcpyHostToDevice, c->stream));
-    }
-    if ((rc = hmm_filtered_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, n_rec, msv_floor ? d_msv_floor.as<int32_t>() : nullptr,
-                                fwd_out && vit_floor ? d_floor.as<int32_t>() : nullptr, d_msv.as<int32_t>(), d_score.as<int32_t>(), fwd_out ? d_fwd.as<int32_t>() : nullptr,
-                                d_order, d_sel, d_cnt)))
-        return rc;
-    if (msv_out) GS_HIP_CHECK(hipMemcpyAsync(msv_out, d_msv.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(vit_out, d_score.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
-    if (fwd_out) GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_rec * np, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+    return gs::hmm_scores_form(c, db, {true, aa, rec_start, rec_len, n_rec}, true, true, msv_floor, vit_floor, msv_out, vit_out, fwd_out, vit_out);
 }
 
 int gs_hmm_trace_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
                      const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_out_dev,
                      uint32_t *n_dom_out_dev, int32_t *dom_out_dev)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_pairs == 0) return GS_OK;
-    GS_REQUIRE(pair_rec_dev && pair_prof_dev && raw_out_dev && n_dom_out_dev && (dom_out_dev || max_dom == 0), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec == 0 || (aa_dev && rec_start_dev && rec_len_dev), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
-    GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens;
-    std::vector<uint32_t> prec(n_pairs), pprof(n_pairs);
-    GS_HIP_CHECK(hipMemcpyAsync(prec.data(), pair_rec_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(pprof.data(), pair_prof_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    int rc;
-    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_trace_check(db, lens.data(), n_rec, prec.data(), pprof.data(), n_pairs))) return rc;
-    return hmm_trace_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), prec.data(), pprof.data(), pair_prof_dev, n_pairs, max_dom, max_block_cells, raw_out_dev,
-                          n_dom_out_dev, dom_out_dev);
+    return gs::hmm_trace_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, pair_rec_dev, pair_prof_dev, n_pairs, max_dom, max_block_cells, raw_out_dev,
+                              n_dom_out_dev, dom_out_dev);
 }
-
 int gs_hmm_trace(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
                  const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_dom, uint64_t max_block_cells, int32_t *raw_out, uint32_t *n_dom_out, int32_t *dom_out)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_pairs == 0) return GS_OK;
-    GS_REQUIRE(pair_rec && pair_prof && raw_out && n_dom_out && (dom_out || max_dom == 0), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec == 0 || (rec_start && rec_len), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
-    int rc = hmm_trace_check(db, rec_len, n_rec, pair_rec, pair_prof, n_pairs);
-    if (rc) return rc;
-    uint64_t n_bytes = 0;                       // of the records that a pair names: the others may be any length and are not staged
-    for (uint64_t i = 0; i < n_pairs; i++)
-        if (pair_rec[i] != GS_HMM_NO_HIT && rec_len[pair_rec[i]]) n_bytes = std::max(n_bytes, rec_start[pair_rec[i]] + rec_len[pair_rec[i]]);
-    const uint64_t n_dom_bytes = 4 * n_pairs * max_dom * GS_HMM_DOM_WORDS;
-    GS_CTX_LOCK(c);
-    PoolBuf d_aa(c, SL_HMMTB_AA), d_rs(c, SL_HMMTB_REC_START), d_rl(c, SL_HMMTB_REC_LEN), d_pp(c, SL_HMMTB_PAIR_PROF), d_raw(c, SL_HMMTB_RAW),
-        d_nd(c, SL_HMMTB_NDOM), d_dom(c, SL_HMMTB_DOM);
-    if ((rc = hmm_stage_records(c, aa, n_bytes, rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_pp.alloc(4 * n_pairs)) || (rc = d_raw.alloc(4 * n_pairs)) ||
-        (rc = d_nd.alloc(4 * n_pairs)) || (rc = d_dom.alloc(n_dom_bytes)))
-        return rc;
-    GS_HIP_CHECK(hipMemcpyAsync(d_pp.p, pair_prof, 4 * n_pairs, hipMemcpyHostToDevice, c->stream));
-    if ((rc = hmm_trace_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, pair_rec, pair_prof, d_pp.as<uint32_t>(), n_pairs, max_dom,
-                             max_block_cells, d_raw.as<int32_t>(), d_nd.as<uint32_t>(), d_dom.as<int32_t>())))
-        return rc;
-    GS_HIP_CHECK(hipMemcpyAsync(raw_out, d_raw.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(n_dom_out, d_nd.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    if (n_dom_bytes) GS_HIP_CHECK(hipMemcpyAsync(dom_out, d_dom.p, n_dom_bytes, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+    return gs::hmm_trace_form(c, db, {true, aa, rec_start, rec_len, n_rec}, pair_rec, pair_prof, n_pairs, max_dom, max_block_cells, raw_out, n_dom_out, dom_out);
 }
 
 int gs_hmm_envelopes_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
                          const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_out_dev,
                          int32_t *bck_out_dev, uint32_t *n_env_out_dev, int32_t *env_out_dev, const uint64_t *row_off_dev, int32_t *out_rows_dev, int32_t *cont_rows_dev)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_pairs == 0) return GS_OK;
-    GS_REQUIRE(pair_rec_dev && pair_prof_dev && fwd_out_dev && bck_out_dev && n_env_out_dev && (env_out_dev || max_env == 0), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec == 0 || (aa_dev && rec_start_dev && rec_len_dev), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(!row_off_dev == !out_rows_dev && !row_off_dev == !cont_rows_dev, GS_ERR_INVALID, "hmm: row_off, out_rows and cont_rows go together");
-    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
-    GS_CTX_LOCK(c);
-    std::vector<uint64_t> lens;
-    std::vector<uint32_t> prec(n_pairs), pprof(n_pairs);
-    GS_HIP_CHECK(hipMemcpyAsync(prec.data(), pair_rec_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(pprof.data(), pair_prof_dev, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    int rc;
-    std::vector<uint64_t> ro(row_off_dev ? n_pairs + 1 : 0);
-    if (row_off_dev) GS_HIP_CHECK(hipMemcpyAsync(ro.data(), row_off_dev, 8 * (n_pairs + 1), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = hmm_fetch_lens(c, rec_len_dev, n_rec, lens)) || (rc = hmm_trace_check(db, lens.data(), n_rec, prec.data(), pprof.data(), n_pairs, GS_HMM_FWD_MAX_L))) return rc;
-    if (row_off_dev)
-        for (uint64_t i = 0; i < n_pairs; i++)
-            GS_REQUIRE(ro[i] <= ro[i + 1] && (prec[i] == GS_HMM_NO_HIT || ro[i + 1] - ro[i] >= lens[prec[i]]), GS_ERR_INVALID,
-                       "hmm: row_off leaves pair %llu fewer words than its record has residues", (unsigned long long)i);
-    return hmm_env_impl(c, db, aa_dev, rec_start_dev, rec_len_dev, lens.data(), prec.data(), pprof.data(), n_pairs, max_env, max_block_rows, fwd_out_dev, bck_out_dev,
-                        n_env_out_dev, env_out_dev, row_off_dev, out_rows_dev, cont_rows_dev);
+    return gs::hmm_env_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, pair_rec_dev, pair_prof_dev, n_pairs, max_env, max_block_rows, fwd_out_dev,
+                            bck_out_dev, n_env_out_dev, env_out_dev, row_off_dev, out_rows_dev, cont_rows_dev);
 }
-
 int gs_hmm_envelopes(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
                      const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows, int32_t *fwd_out, int32_t *bck_out, uint32_t *n_env_out,
                      int32_t *env_out, const uint64_t *row_off, int32_t *out_rows, int32_t *cont_rows)
 {
-    using namespace gs;
-    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
-    if (n_pairs == 0) return GS_OK;
-    GS_REQUIRE(pair_rec && pair_prof && fwd_out && bck_out && n_env_out && (env_out || max_env == 0), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(n_rec == 0 || (rec_start && rec_len), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(!row_off == !out_rows && !row_off == !cont_rows, GS_ERR_INVALID, "hmm: row_off, out_rows and cont_rows go together");
-    GS_REQUIRE(n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
-    int rc = hmm_trace_check(db, rec_len, n_rec, pair_rec, pair_prof, n_pairs, GS_HMM_FWD_MAX_L);
-    if (rc) return rc;
-    uint64_t n_bytes = 0;                       // of the records that a pair names: the others may be any length and are not staged
-    for (uint64_t i = 0; i < n_pairs; i++)
-        if (pair_rec[i] != GS_HMM_NO_HIT && rec_len[pair_rec[i]]) n_bytes = std::max(n_bytes, rec_start[pair_rec[i]] + rec_len[pair_rec[i]]);
-    if (row_off)                                // every listed pair's rows must fit between its offset and the next
-        for (uint64_t i = 0; i < n_pairs; i++)
-            GS_REQUIRE(row_off[i] <= row_off[i + 1] && (pair_rec[i] == GS_HMM_NO_HIT || row_off[i + 1] - row_off[i] >= rec_len[pair_rec[i]]), GS_ERR_INVALID,
-                       "hmm: row_off leaves pair %llu fewer words than its record has residues", (unsigned long long)i);
-    const uint64_t n_env_bytes = 4 * n_pairs * max_env * GS_HMM_ENV_WORDS, n_row_bytes = row_off ? 4 * row_off[n_pairs] : 0;
-    GS_CTX_LOCK(c);
-    PoolBuf d_aa(c, SL_HMMEB_AA), d_rs(c, SL_HMMEB_REC_START), d_rl(c, SL_HMMEB_REC_LEN), d_fwd(c, SL_HMMEB_FWD), d_bck(c, SL_HMMEB_BCK), d_ne(c, SL_HMMEB_NENV),
-        d_env(c, SL_HMMEB_ENV), d_ro(c, SL_HMMEB_ROW_OFF), d_out(c, SL_HMMEB_OUT), d_cont(c, SL_HMMEB_CONT);
-    if ((rc = hmm_stage_records(c, aa, n_bytes, rec_start, rec_len, n_rec, d_aa, d_rs, d_rl)) || (rc = d_fwd.alloc(4 * n_pairs)) || (rc = d_bck.alloc(4 * n_pairs)) ||
-        (rc = d_ne.alloc(4 * n_pairs)) || (rc = d_env.alloc(n_env_bytes)))
-        return rc;
-    if (row_off) {
-        if ((rc = d_ro.alloc(8 * (n_pairs + 1))) || (rc = d_out.alloc(n_row_bytes)) || (rc = d_cont.alloc(n_row_bytes))) return rc;
-        GS_HIP_CHECK(hipMemcpyAsync(d_ro.p, row_off, 8 * (n_pairs + 1), hipMemcpyHostToDevice, c->stream));
-        if (n_row_bytes) {                      // the rows of a pair that gets none keep what the caller's buffers hold
-            GS_HIP_CHECK(hipMemcpyAsync(d_out.p, out_rows, n_row_bytes, hipMemcpyHostToDevice, c->stream));
-            GS_HIP_CHECK(hipMemcpyAsync(d_cont.p, cont_rows, n_row_bytes, hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    if ((rc = hmm_env_impl(c, db, d_aa.as<uint8_t>(), d_rs.as<uint64_t>(), d_rl.as<uint64_t>(), rec_len, pair_rec, pair_prof, n_pairs, max_env, max_block_rows,
-                           d_fwd.as<int32_t>(), d_bck.as<int32_t>(), d_ne.as<uint32_t>(), d_env.as<int32_t>(), row_off ? d_ro.as<uint64_t>() : nullptr,
-                           row_off ? d_out.as<int32_t>() : nullptr, row_off ? d_cont.as<int32_t>() : nullptr)))
-        return rc;
-    GS_HIP_CHECK(hipMemcpyAsync(fwd_out, d_fwd.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(bck_out, d_bck.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(n_env_out, d_ne.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-    if (n_env_bytes) GS_HIP_CHECK(hipMemcpyAsync(env_out, d_env.p, n_env_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (n_row_bytes) {
-        GS_HIP_CHECK(hipMemcpyAsync(out_rows, d_out.p, n_row_bytes, hipMemcpyDeviceToHost, c->stream));
-        GS_HIP_CHECK(hipMemcpyAsync(cont_rows, d_cont.p, n_row_bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    GS_HIP_CHECK(stream_wait(c));
-    return GS_OK;
+    return gs::hmm_env_form(c, db, {true, aa, rec_start, rec_len, n_rec}, pair_rec, pair_prof, n_pairs, max_env, max_block_rows, fwd_out, bck_out, n_env_out, env_out,
+                            row_off, out_rows, cont_rows);
 }
-
-double gs_hmm_forward_evalue(double bits, double tau, double lambda, double Z) { return Z * (bits < tau ? 1.0 : ::exp(-lambda * (bits - tau))); }
-
-double gs_hmm_bits(int32_t raw) { return (double)raw / 1024.0; }
-double gs_hmm_evalue(double bits, double mu, double lambda, double Z) { return Z * -::expm1(-::exp(-lambda * (bits - mu))); }
 
 }  // extern "C"

@@ -73,18 +73,17 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* superani, a block's anchors, its segments, the chaining result, chain ends and the per-seed marks of both sides */                              \
     X(ANI_A_RCTG) X(ANI_A_RPOS) X(ANI_A_QCTG) X(ANI_A_QPOS) X(ANI_A_STRAND) X(ANI_A_RIDX) X(ANI_A_QIDX) X(ANI_A_PAIR) X(ANI_SEG_TILES)                \
     X(ANI_SEG_START) X(ANI_SEG_N) X(ANI_F) X(ANI_PRED) X(ANI_ROOT) X(ANI_BEST) X(ANI_NCHAIN) X(ANI_MATCHED) X(ANI_DIFF)                               \
-    /* hmmsearch (gs_hmm.hip): the records of a call, longest first; staging of the host form */                                                       \
-    X(HMM_ORDER) X(HMMB_AA) X(HMMB_REC_START) X(HMMB_REC_LEN) X(HMMB_SCORE)                                                                           \
-    /* hmmsearch, Forward: per profile the records at or above its Viterbi floor and their number, the Viterbi matrix nobody asked for, staging */    \
-    X(HMM_SEL) X(HMM_SEL_COUNT) X(HMM_VIT) X(HMMB_FWD) X(HMMB_FLOOR)                                                                                  \
-    /* hmmsearch, MSV prefilter: the MSV matrix nobody asked for, staging of the host form's MSV matrix and MSV floors */                               \
-    X(HMM_MSV) X(HMMB_MSV) X(HMMB_MSV_FLOOR)                                                                                                          \
-    /* hmmsearch, trace-back: a block's pairs and their profiles' lists, its back-pointers and row specials, staging of the host form */                \
-    X(HMMT_PAIRS) X(HMMT_PROFS) X(HMMT_PTR) X(HMMT_ROWS) X(HMMTB_AA) X(HMMTB_REC_START) X(HMMTB_REC_LEN) X(HMMTB_PAIR_PROF) X(HMMTB_RAW)       \
-    X(HMMTB_NDOM) X(HMMTB_DOM)                                                                                                                        \
-    /* hmmsearch, posterior envelopes: a block's pairs and profile lists, its Forward and Backward rows, staging of the host form */                    \
-    X(HMME_PAIRS) X(HMME_PROFS) X(HMME_FROWS) X(HMME_BROWS) X(HMMEB_AA) X(HMMEB_REC_START) X(HMMEB_REC_LEN) X(HMMEB_FWD) X(HMMEB_BCK) X(HMMEB_NENV)     \
-    X(HMMEB_ENV) X(HMMEB_ROW_OFF) X(HMMEB_OUT) X(HMMEB_CONT)                                                                                          \
+    /* hmmsearch (gs_hmm.hip). What a host form stages of its inputs - the forms of one context cannot nest, so they share these: the records, the     \
+       profiles of a list of pairs, the Viterbi and MSV floors, the row offsets of the envelopes */                                                    \
+    X(HMMB_AA) X(HMMB_REC_START) X(HMMB_REC_LEN) X(HMMB_PAIR_PROF) X(HMMB_FLOOR) X(HMMB_MSV_FLOOR) X(HMMB_ROW_OFF)                                     \
+    /* hmmsearch, the score matrices of a call where they are not the caller's device memory: a host form's staging, or the matrix nobody asked for;   \
+       the records of a call, longest first; per profile the records that a floor selects and their number */                                          \
+    X(HMM_VIT) X(HMM_MSV) X(HMM_FWD) X(HMM_ORDER) X(HMM_SEL) X(HMM_SEL_COUNT)                                                                          \
+    /* hmmsearch over a list of pairs (trace-back, envelopes): a block's pairs and their profiles' lists; a host form's staging of per-pair outputs: \
+       the score, the Backward score, the number of domains or envelopes, those, and the two row arrays of the envelopes */                            \
+    X(HMMP_PAIRS) X(HMMP_PROFS) X(HMMB_PAIR_SCORE) X(HMMB_PAIR_BCK) X(HMMB_PAIR_COUNT) X(HMMB_PAIR_ITEMS) X(HMMB_OUT_ROWS) X(HMMB_CONT_ROWS)           \
+    /* hmmsearch, a block's scratch: back-pointers and row specials of the trace-back, Forward and Backward rows of the envelopes */                   \
+    X(HMMT_PTR) X(HMMT_ROWS) X(HMME_FROWS) X(HMME_BROWS)                                                                                               \
     /* orfs (gs_orf.hip): tile prefix of the records and the call's counters; per tile the last stop of each (strand, class) pair, then its kept ORFs,      \
        residues and long drops (each scanned in place); the partial results of those scans; staging of the host form */                                 \
     X(ORF_REC_TILES) X(ORF_META) X(ORF_STOPS) X(ORF_COUNTS) X(ORF_PARTIALS) X(ORFB_SEQ) X(ORFB_REC_START) X(ORFB_REC_LEN) X(ORFB_ORF) X(ORFB_AA)         \

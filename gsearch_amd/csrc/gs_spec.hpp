@@ -1,12 +1,13 @@
 // gs_spec.hpp — SPEC.md section 2 (hashing + random numbers) for device and host code of the product.
-// Every [CHOICE] of SPEC.md that touches arithmetic lives in this header (and, independently restated,
-// in oracle/gs_oracle.c). Replaces what gsearch reaches through fxhash / rand_xoshiro / rand
+// Every [CHOICE] of SPEC.md that touches arithmetic lives in this header or, for the units of SPEC 13, in gs_hmm_parse.hpp,
+// which it includes (and, independently restated, in oracle/gs_oracle.c). Replaces what gsearch reaches through fxhash / rand_xoshiro / rand
 // (Cargo.toml:26,122 of the reference; crates not vendored).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "gs_bigsi_file.hpp"
+#include "gs_hmm_parse.hpp"
 
 #define GS_HD __host__ __device__ __forceinline__
 
@@ -490,43 +491,8 @@ GS_HD uint32_t ani_revcomp(uint32_t x, uint32_t k)
     return (~br) >> (32 - 2 * k);
 }
 
-// ---- SPEC 13: hmmsearch - Viterbi score of a protein against a HMMER3 profile, all in int32 units of 2^-10 bit. [CHOICE] throughout (hmmsearch_rs is
-// not in the reference; the profiles under data/HMM_* are, and pin the model through their own cutoffs and STATS lines).
-#define GS_HMM_UNIT_C 1015206383ULL      // 2^36 * 1024 / (10^5 ln 2): a file value of d * 10^-5 nats is -((d * C + 2^35) >> 36) units
-#define GS_HMM_UNIT_S 36
-#define GS_HMM_MAX_FILE_VALUE 9999999u   // d: a file value is below 100 nats, so a score from a file is above -2^18
-#define GS_HMM_STAR (-(1 << 18))         // `*` of a file (probability 0): below every score a file value can give
-#define GS_HMM_NEG (-(1 << 29))          // floor of every cell
-#define GS_HMM_TEJ (-1024)               // E -> J and E -> C, one bit each (multihit)
-#define GS_HMM_AA_MASK 0x016FBDFDu       // the letters A..Z that are residues; a residue's index is its rank among them (ACDEFGHIKLMNPQRSTVWY)
-#define GS_HMM_BG_LIST {-3754, -6189, -4325, -3997, -4766, -3939, -5578, -4181, -4170, -3456, -5524, -4703, -4477, -4772, -4309, -3964, -4310, -3986, -6608, -5160}
-// log2(n) in units of 2^-20 for 1 <= n < 2^32: the exponent, then 20 fraction bits by squaring a 32-bit mantissa on 64-bit words (each squaring
-// doubles the logarithm, the bit that carries out is the next fraction bit; the dropped low bits cost less than 2^-20 in all)
-GS_HD int32_t hmm_lgq(uint32_t n)
-{
-    int e = 31;
-    while (!((n >> e) & 1u)) e--;
-    uint64_t x = (uint64_t)n << (31 - e);
-    int32_t r = e << 20;
-    for (int j = 19; j >= 0; j--) {
-        x = (x * x) >> 31;
-        if (x >> 32) { x >>= 1; r |= 1 << j; }
-    }
-    return r;
-}
-// units(ln(num / den)), to the nearest unit
-GS_HD int32_t hmm_units_log(uint32_t num, uint32_t den) { return (hmm_lgq(num) - hmm_lgq(den) + 512) >> 10; }
-struct HmmSpecials { int32_t tloop, tmove, null, nloop, nmove; };
-// the length model of a target of L residues, 1 <= L <= GS_HMM_MAX_L
-GS_HD HmmSpecials hmm_specials(uint32_t L)
-{
-    HmmSpecials s;
-    s.tloop = hmm_units_log(L, L + 3); s.tmove = hmm_units_log(3, L + 3);
-    s.nloop = hmm_units_log(L, L + 1); s.nmove = hmm_units_log(1, L + 1);
-    s.null = (int32_t)L * s.nloop + s.nmove;
-    return s;
-}
-GS_HD int32_t hmm_tbm(uint32_t M) { return hmm_units_log(2, M * (M + 1)); }
+// ---- SPEC 13: hmmsearch. Its units, constants and length model (hmm_lgq .. hmm_tbm) live in gs_hmm_parse.hpp, which the host-only reader of profile
+// files shares; what is left here needs the device.
 // a byte of a record -> residue index 0..19, or -1 (either case is read, as the sketchers do)
 GS_HD int hmm_residue(uint8_t c)
 {

@@ -1,4 +1,4 @@
-// loader_sweep.cpp — the host-only readers of files from other programs (gs_hnswio_parse.cpp, gs_bigsi_file.cpp; SPEC.md 16) run as a plain C++ program,
+// loader_sweep.cpp — the host-only readers of files from other programs (gs_hnswio_parse.cpp, gs_bigsi_file.cpp; SPEC.md 16; gs_hmm_parse.cpp; SPEC.md 13) run as a plain C++ program,
 // the way a Rust or C++ host calls them: no Python, no HIP runtime, and an address space of 2 GiB, which bounds what a hostile header may allocate.
 //
 //   loader_sweep <directory>      the directory holds cases.txt and the files it names (tests/loader_case_dir.py writes it):
@@ -6,6 +6,8 @@
 //     gsbx <name> <code>                                <name>.gsbx must verify to <code>
 //     sweep_hnswrs <name> <g|d> <p|f|x> <pos> <code>    the graph or data file of <name> cut to <pos> bytes (p), or with byte <pos> set to 0xFF (f) or ^ 1 (x)
 //     sweep_gsbx <name> <p|f|x> <pos> <code>            the same of <name>.gsbx
+//     hmm <name> <code>                                 the profile text <name>.hmm must parse (gs_hmm_parse_mem) to <code>
+//     sweep_hmm <name> <p|f|x> <pos> <code>             the same of <name>.hmm, parsed from memory
 // prints "N files, S surprises"; a surprise is a code other than the listed one, or a C++ exception that reached this program. Exit status 0 iff S = 0.
 // Built without the address-space limit (-DLOADER_SWEEP_NO_RLIMIT) for the sanitizer run, whose shadow memory needs terabytes of address space.
 #include <stdarg.h>
@@ -80,6 +82,11 @@ int main(int argc, char **argv)
             else if (what == "sweep_gsbx" && in >> kind >> pos >> want) {
                 if (!spit(dir + "/_sweep.gsbx", mutate(bytes_of(dir + "/" + name + ".gsbx"), kind[0], pos))) { fprintf(stderr, "cannot write into %s\n", dir.c_str()); return 2; }
                 got = gs_bigsi_verify((dir + "/_sweep.gsbx").c_str(), nullptr);
+            }
+            else if (what == "hmm" && in >> want) { const std::string &t = bytes_of(dir + "/" + name + ".hmm"); got = gs_hmm_parse_mem(t.data(), t.size(), 0, nullptr, nullptr, 0, nullptr); }
+            else if (what == "sweep_hmm" && in >> kind >> pos >> want) {
+                const std::string t = mutate(bytes_of(dir + "/" + name + ".hmm"), kind[0], pos);
+                got = gs_hmm_parse_mem(t.data(), t.size(), 0, nullptr, nullptr, 0, nullptr);
             }
             else { fprintf(stderr, "bad line: %s\n", line.c_str()); return 2; }
             files++;

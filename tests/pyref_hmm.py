@@ -76,9 +76,22 @@ def bits_units(tok):
     return (2 * d * 1024 + den) // (2 * den)
 
 
+def header_number(tok):
+    """a number of a header line (GA / TC / NC, STATS LOCAL): sign, digits, then optionally a point and digits -> float; anything else is malformed"""
+    ip, _, fr = (tok[1:] if tok[:1] in ("+", "-") else tok).partition(".")
+    if not ip.isdigit() or (fr and not fr.isdigit()):
+        raise HmmError("not a number: %r" % tok)
+    return float(tok)
+
+
 def threshold_units(bits):
     """a caller's cutoff in bits (a float) -> units: floor(bits * 1024 + 1/2)"""
     return int(math.floor(float(bits) * 1024.0 + 0.5))
+
+
+def _fields(ln):
+    """a line split at blanks: space, tab and carriage return, nothing else (a vertical tab or a form feed is part of a field)"""
+    return [t for t in ln.replace("\t", " ").replace("\r", " ").split(" ") if t]
 
 
 def parse_hmm(text):
@@ -94,12 +107,12 @@ def parse_hmm(text):
         while pos < len(lines):
             ln = lines[pos]
             pos += 1
-            if ln.strip():
+            if _fields(ln):
                 return ln
         raise HmmError("truncated file")
 
     while True:
-        while pos < len(lines) and not lines[pos].strip():
+        while pos < len(lines) and not _fields(lines[pos]):
             pos += 1
         if pos >= len(lines):
             break
@@ -108,7 +121,7 @@ def parse_hmm(text):
         m = {"name": None, "acc": "", "M": 0, "ga": None, "tc": None, "nc": None, "ga_units": None, "mu": None, "lam": None}
         alph = None
         while True:
-            f = nxt().split()
+            f = _fields(nxt())
             if f[0] == "HMM":
                 break
             if f[0] == "NAME" and len(f) > 1:
@@ -123,11 +136,13 @@ def parse_hmm(text):
                 alph = f[1].lower()
             elif f[0] in ("GA", "TC", "NC") and len(f) > 2:
                 a, b = f[1].rstrip(";"), f[2].rstrip(";")
-                m[f[0].lower()] = (float(a), float(b))
+                m[f[0].lower()] = (header_number(a), header_number(b))
                 if f[0] == "GA":
                     m["ga_units"] = bits_units(a)
-            elif f[0] == "STATS" and len(f) > 4 and f[1] == "LOCAL" and f[2] == "VITERBI":
-                m["mu"], m["lam"] = float(f[3]), float(f[4])
+            elif f[0] == "STATS" and len(f) > 4 and f[1] == "LOCAL" and f[2] in ("MSV", "VITERBI", "FORWARD"):
+                mu, lam = header_number(f[3]), header_number(f[4])
+                if f[2] == "VITERBI":
+                    m["mu"], m["lam"] = mu, lam
         if m["name"] is None or alph is None or m["M"] < 1:
             raise HmmError("NAME, LENG or ALPH missing")
         if alph != "amino":
@@ -137,29 +152,29 @@ def parse_hmm(text):
         M = m["M"]
         nxt()                                            # the line that names the transitions
         tab = np.zeros((27, M + 1), np.int32)
-        f = nxt().split()
+        f = _fields(nxt())
         if f[0] == "COMPO":
-            f = nxt().split()
+            f = _fields(nxt())
         if len(f) != 20:
             raise HmmError("insert emissions of node 0")
         [file_units(t) for t in f]
         for k in range(0, M + 1):
             if k > 0:
-                f = nxt().split()
+                f = _fields(nxt())
                 if len(f) < 21 or f[0] != str(k):
                     raise HmmError("node %d expected" % k)
                 for a in range(20):
                     tab[a, k] = file_units(f[1 + a]) - BG[a]
-                f = nxt().split()
+                f = _fields(nxt())
                 if len(f) != 20:
                     raise HmmError("insert emissions of node %d" % k)
                 [file_units(t) for t in f]
-            f = nxt().split()
+            f = _fields(nxt())
             if len(f) != 7:
                 raise HmmError("transitions of node %d" % k)
             for t in range(7):
                 tab[20 + t, k] = file_units(f[t])
-        if nxt().strip() != "//":
+        if _fields(nxt()) != ["//"]:
             raise HmmError("no // after node %d" % M)
         m["tables"] = tab
         models.append(m)

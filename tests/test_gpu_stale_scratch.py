@@ -1070,6 +1070,107 @@ def _(wd):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------------
+# hmmsearch (gs_hmm.hip): its host forms stage their arguments in one set of slots and its forms over pairs share their lists, so every form runs in
+# what the one before it left - first on nine records, then on two of them, so that each slot is also used smaller after larger. Three synthetic profiles
+# in two kernel classes (10 and 64 nodes: one node a lane, 70: two); records on both sides of the 64-residue reload, an empty one, and copies of the
+# consensus, so that there are domains and envelopes; every (record, profile) pair in a shuffled order, and one GS_HMM_NO_HIT entry.
+HMM_SLOTS = 4                       # domain and envelope slots a pair
+
+
+@functools.lru_cache(maxsize=None)
+def _hmm_sets():
+    """-> texts, floors and per record set (records, packed, pair_rec, pair_prof, what the restatements say): the Viterbi matrix, the MSV, Viterbi and
+    Forward matrices behind the floors of P = 0.02 and 1e-3, Forward behind the Viterbi floor alone, trace-back, envelopes and their rows"""
+    import pyref_hmm as R
+    import pyref_hmm_forward as F
+    import pyref_hmm_msv as V
+    import pyref_hmm_posterior as P
+    import pyref_hmm_trace as T
+    rng = np.random.default_rng(1361)
+    texts = [R.write_hmm(R.synth_model(rng, M)) for M in (10, 64, 70)]
+    models = [m for t in texts for m in R.parse_hmm(t)]
+    mfl, vfl = V.floors([s for t in texts for s in F.stats_lines(t)]), F.floors(models)
+    c10, c64, c70 = (R.consensus(m["tables"]) for m in models)
+    nine = [b"", R.background(rng, 1), R.background(rng, 63), R.background(rng, 64), R.background(rng, 65), c70 + R.background(rng, 60), c64 + c64,
+            c10 + R.background(rng, 20) + c10, c70]
+    assert [len(r) for r in nine] == [0, 1, 63, 64, 65, 130, 128, 40, 70]
+    sets = []
+    for records in (nine, [nine[5], nine[2]]):
+        order = rng.permutation(len(records) * len(models))
+        pr = np.append((order // len(models)).astype(np.uint32), np.uint32(R.NO_HIT))
+        pp = np.append((order % len(models)).astype(np.uint32), np.uint32(1))
+        rl = np.array([len(r) for r in records], np.uint64)
+        packed = (np.frombuffer(b"".join(records) + bytes(8), np.uint8), np.concatenate([[0], np.cumsum(rl)[:-1]]).astype(np.uint64), rl)
+        msv, fvit, fwd = V.search_filtered(models, records, floor=mfl, forward=True, vit_floor=vfl)
+        *env, outs, conts = P.envelope_pairs(models, records, pr, pp, HMM_SLOTS, rows=True)
+        rows = lambda xs: np.concatenate([np.zeros(0, np.int32)] + [x for x in xs if x is not None])     # noqa: E731
+        want = {"vit": R.search(models, records), "msv": msv, "fvit": fvit, "fwd": fwd, "fwd_all": F.search_forward(models, records, floor=vfl)[1],
+                "trace": T.trace_pairs(models, records, pr, pp, HMM_SLOTS), "env": tuple(env) + (rows(outs), rows(conts))}
+        assert (want["fvit"] == R.NO_SCORE).any() and (want["fwd"] != R.NO_SCORE).any() and want["trace"][1].max() >= 1 and want["env"][2].max() >= 1
+        sets.append((records, packed, pr, pp, want))
+    assert sets[0][4]["trace"][1].max() == 2 and sets[0][4]["env"][2].max() == HMM_SLOTS        # a pair with two domains, one that fills its envelope slots
+    return texts, mfl, vfl, sets
+
+
+@case("hmm", "host_forms_nine_records_then_two")
+def _(wd):
+    import gsearch_amd as G
+    texts, mfl, vfl, sets = _hmm_sets()
+
+    def run(ctx, poke):
+        db, got = G.HmmDb(texts, ctx, texts=True), ()
+        try:
+            for _, packed, pr, pp, _ in sets:
+                *env, outs, conts = db.envelopes_packed(*packed, pr, pp, max_env=HMM_SLOTS, rows=True)
+                got += ((db.search_packed(*packed),) + db.search_filtered_packed(*packed, msv_floor=mfl, forward=True, floor=vfl) +
+                        db.trace_packed(*packed, pr, pp, max_dom=HMM_SLOTS) + tuple(env) + (np.concatenate(outs), np.concatenate(conts)))
+        finally:
+            db.close()
+        return got
+    return run, tuple(x for *_, w in sets for x in (w["vit"], w["msv"], w["fvit"], w["fwd"]) + w["trace"] + w["env"])
+
+
+@case("hmm", "dev_forms_without_the_unwanted_matrices")
+def _(wd):
+    """the _dev forms on the same sets; the Viterbi matrix of gs_hmm_search_forward_dev and the MSV matrix of gs_hmm_search_filtered_dev are not asked
+    for, so both go to their slots"""
+    import gsearch_amd as G
+    texts, mfl, vfl, sets = _hmm_sets()
+
+    def run(ctx, poke):
+        db, got, bufs = G.HmmDb(texts, ctx, texts=True), (), []
+
+        def up(a):
+            bufs.append(ctx.alloc(max(a.nbytes, 16)))
+            ctx.upload(bufs[-1], np.ascontiguousarray(a))
+            return bufs[-1]
+        try:
+            for records, packed, pr, pp, _ in sets:
+                n_rec, n, n_prof = len(records), len(pr), len(db)
+                ro = np.concatenate([[0], np.cumsum([packed[2][r] if r < n_rec else 0 for r in pr])]).astype(np.uint64)
+                aa, rs, rl, d_pr, d_pp, d_ro, d_mfl, d_vfl = (up(a) for a in packed + (pr, pp, ro, mfl, vfl))
+                mat, per_pair = np.zeros((n_rec, n_prof), np.int32), np.zeros(n, np.int32)
+                vit, fvit, fwd, fwd_all, raw, nd, dom, efwd, ebck, ne, env, outs, conts = (up(a) for a in (
+                    mat, mat, mat, mat, per_pair, per_pair, np.zeros((n, HMM_SLOTS, 8), np.int32), per_pair, per_pair, per_pair, np.zeros((n, HMM_SLOTS, 4), np.int32),
+                    np.zeros(int(ro[-1]), np.int32), np.zeros(int(ro[-1]), np.int32)))
+                db.search_dev(aa, rs, rl, n_rec, vit)
+                db.search_filtered_dev(aa, rs, rl, n_rec, d_mfl, d_vfl, None, fvit, fwd)
+                db.search_forward_dev(aa, rs, rl, n_rec, d_vfl, None, fwd_all)
+                db.trace_dev(aa, rs, rl, n_rec, d_pr, d_pp, n, HMM_SLOTS, raw, nd, dom)
+                db.envelopes_dev(aa, rs, rl, n_rec, d_pr, d_pp, n, HMM_SLOTS, efwd, ebck, ne, env, d_ro, outs, conts)
+                got += tuple(ctx.download(p, mat.shape, np.int32) for p in (vit, fvit, fwd, fwd_all))
+                got += (ctx.download(raw, (n,), np.int32), ctx.download(nd, (n,), np.uint32), ctx.download(dom, (n, HMM_SLOTS, 8), np.int32),
+                        ctx.download(efwd, (n,), np.int32), ctx.download(ebck, (n,), np.int32), ctx.download(ne, (n,), np.uint32),
+                        ctx.download(env, (n, HMM_SLOTS, 4), np.int32), ctx.download(outs, (int(ro[-1]),), np.int32), ctx.download(conts, (int(ro[-1]),), np.int32))
+        finally:
+            for p in bufs:
+                ctx.free(p)
+            db.close()
+        return got
+    return run, tuple(x for *_, w in sets for x in (w["vit"], w["fvit"], w["fwd"], w["fwd_all"]) + w["trace"] + w["env"])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------------------
 # one test function per case, in the order of the list, then the replay
 def _make_test(c):
     def test(stale_ctx, fill_guard, workdir, monkeypatch, capfd):

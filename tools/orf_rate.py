@@ -128,8 +128,8 @@ def main():
             res["cells"] = res["search_residues"] * sum(nodes)
             res["cells_per_s"] = res["cells"] / res["viterbi_s"]
             res["translate_share_of_viterbi"] = (best["full"] * K / N) / res["viterbi_s"]
-            d_goff, d_thr = dev._up(dev.genome_orf_off), dev._up(db.thresholds("ga"))
-            d_rec, d_sc = dev._new(4 * K * len(db)), dev._new(4 * K * len(db))
+            d_goff, d_thr = dev.mem.up(dev.genome_orf_off), dev.mem.up(db.thresholds("ga"))
+            d_rec, d_sc = dev.mem.new(4 * K * len(db)), dev.mem.new(4 * K * len(db))
             t = time.perf_counter()
             db.best_hits_dev(d_score, dev.n, d_goff, K, d_thr, d_rec, d_sc)
             ctx.sync()
