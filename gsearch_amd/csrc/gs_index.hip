@@ -2505,6 +2505,24 @@ static int dense_counts(gs_index *ix, const uint8_t *qrows, uint64_t nq, uint64_
     if ((rc = ensure_stats(ix))) return rc;
     // equal batches: every join call streams all the columns, so a short last batch costs almost as much as a full one
     const uint64_t parts = (nq + match_join_max_queries() - 1) / match_join_max_queries(), jq = (nq + parts - 1) / parts;
+    // a request of several batches whose rows are all here: one call prepares them together, waits for the device once and joins the batches that take the plain
+    // main pass in one launch (gs_join.hip; groups of JOIN_BATCHES). GS_JOIN_MERGE=0: batch by batch, as the fused sketch-and-search has to (its rows arrive per batch)
+    const char *me = getenv("GS_JOIN_MERGE");
+    if (parts >= 2 && !ix->feed && !(me && !atoi(me))) {
+        const uint64_t group = jq * JOIN_BATCHES;
+        for (uint64_t g0 = 0; g0 < nq; g0 += group) {
+            const uint64_t ng = std::min<uint64_t>(group, nq - g0);
+            int declined[JOIN_BATCHES] = {};
+            if ((rc = match_join_counts(c, ix->ikind, ix->prm.m, qrows + g0 * ix->stride, ix->stride, ng, ix->cols.p, ix->cols_cap, n, out16 + g0 * ld, ld, ix->join_scratch,
+                                        declined, ix->stats.as<unsigned long long>(), true, 0, ix->data.p, ix->stride, jq))) return rc;
+            for (uint64_t q0 = g0, b = 0; q0 < g0 + ng; q0 += jq, b++) {
+                const uint64_t nb = std::min<uint64_t>(jq, g0 + ng - q0);
+                if (declined[b] &&
+                    (rc = hamming_qxc_strided(c, ix->ikind, ix->prm.m, qrows + q0 * ix->stride, nb, ix->stride, ix->data.p, n, ix->stride, nullptr, nullptr, out16 + q0 * ld, ld))) return rc;
+            }
+        }
+        return GS_OK;
+    }
     for (uint64_t q0 = 0; q0 < nq; q0 += jq) {
         const uint64_t nb = std::min<uint64_t>(jq, nq - q0);
         int declined = 0;

@@ -142,12 +142,14 @@ struct DevBuf;
 // column-major database copy `cols` ([m][colcap]); out16[q * ld + e] = mismatch count. scratch: JOIN_SCRATCH reusable buffers. init = false: the
 // counters already hold m (a sub-range of columns of rows initialised by an earlier call: the row-spanning memset would wipe their neighbours); col0: node e of the range is column col0 + e of the matrix.
 uint64_t match_join_max_queries();
-enum { JOIN_SCRATCH = 16 };
+enum { JOIN_SCRATCH = 16, JOIN_BATCHES = 8 };
 // rows / rstride (optional): the row-major signatures of the same nodes - with them a request batch's heavy (query, node) blocks are found and
 // written by the compare tile kernel instead of being counted match by match (gs_join.hip "heavy blocks")
+// jq (optional): the nq rows are a request of up to JOIN_BATCHES batches of jq queries (the last may be shorter), prepared together, waited for once and, where they
+// end in the plain main pass, joined in one launch; `declined` then has one entry per batch. The matrix rows of the batches must be consecutive (init = true).
 int match_join_counts(gs_ctx *c, int kind, uint32_t m, const void *qrows, uint64_t qstride, uint64_t nq, const void *cols, uint64_t colcap, uint64_t n,
                       uint16_t *out16, uint64_t ld, DevBuf *scratch, int *declined = nullptr, unsigned long long *stats = nullptr, bool init = true, uint64_t col0 = 0,
-                      const void *rows = nullptr, uint64_t rstride = 0);
+                      const void *rows = nullptr, uint64_t rstride = 0, uint64_t jq = 0);
 int hamming_blocks(gs_ctx *c, int kind, uint32_t m, const void *Q, uint64_t strideQ_bytes, const void *C, uint64_t strideC_bytes, const void *items_dev,
                    uint32_t n_items, const uint32_t *qlist_dev, const uint32_t *clist_dev, uint16_t *out_cnt16, uint64_t ld_out, uint32_t n_thin = 0,
                    uint32_t *parts_out = nullptr);       // (*parts_out as for hamming_qxc_strided: the parts of the tile kernel's run over the items the thin kernel left)

@@ -54,11 +54,19 @@ __global__ __launch_bounds__(256) void k_rows_to_cols(const uint8_t *__restrict_
     }
 }
 
-// query batch -> per-slot key lists: qkey[s * nq + q] (canonical keys)
+// A request of several batches (JoinSpan): batch b holds the queries [b * jq, min((b + 1) * jq, nq)) of the span. The small kernels around the join take the batch from
+// a grid dimension and find its rows, lists and labels from the span alone; a single batch is the span {nq, nq}.
+struct JoinSpan { uint32_t nq, jq; };
+__device__ __forceinline__ uint32_t span_q0(const JoinSpan sp, uint32_t b) { return b * sp.jq; }
+__device__ __forceinline__ uint32_t span_nq(const JoinSpan sp, uint32_t b) { const uint32_t r = sp.nq - b * sp.jq; return r < sp.jq ? r : sp.jq; }
+
+// query batch -> per-slot key lists: qkey[s * nq + q] (canonical keys); blockIdx.z = batch, whose block of m * (its queries) keys follows those of the batches before it
 template <int KIND, typename T>
-__global__ __launch_bounds__(256) void k_query_cols(const uint8_t *__restrict__ rows, uint64_t stride, uint32_t nq, uint32_t m, T *__restrict__ qkey)
+__global__ __launch_bounds__(256) void k_query_cols(const uint8_t *__restrict__ rows, uint64_t stride, JoinSpan sp, uint32_t m, T *__restrict__ qkey)
 {
     __shared__ T tile[32][33];
+    const uint32_t q0 = span_q0(sp, blockIdx.z), nq = span_nq(sp, blockIdx.z);
+    rows += (uint64_t)q0 * stride; qkey += (uint64_t)m * q0;
     const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const uint64_t r0 = (uint64_t)blockIdx.x * 32, s0 = (uint64_t)blockIdx.y * 32;
     for (uint32_t j = ty; j < 32; j += 8) {
@@ -147,13 +155,19 @@ constexpr int JTAG_CL_SHIFT = 13;
 constexpr uint32_t JCL_MAX = 2047;      // cluster ids 1..2047
 constexpr int JWALK = 4;                // table entries the in-place own-cluster test of a node's value looks at (k_match_join, CL)
 
+struct JoinBatch { const void *qkey; uint32_t *mm32; uint32_t nq, pad; };      // one batch of a merged launch of k_match_join
+
 template <int KIND, typename T, int SR, bool CL>
 __global__ __launch_bounds__(JT, (sizeof(T) == 8 && SR == 1) ? 4 : 8) void k_match_join(const T *__restrict__ qkey, uint32_t nq, uint32_t log2p, const T *__restrict__ cols, uint64_t colcap, uint64_t n,
                                                     uint32_t slot_lo, uint32_t slot_hi, uint32_t slots_per_wg, uint32_t *__restrict__ mm32, uint64_t ld,
                                                     unsigned long long *__restrict__ stats, int chunk_major, uint64_t col0, const uint16_t *__restrict__ qcl,
                                                     const uint16_t *__restrict__ nodelab, const T *__restrict__ qs, uint32_t nh, const uint32_t *__restrict__ cl_lo,
-                                                    const uint32_t *__restrict__ qlist, uint32_t dedup_flags)
+                                                    const uint32_t *__restrict__ qlist, uint32_t dedup_flags, const JoinBatch *__restrict__ bt)
 {
+    // several batches in one launch (blockIdx.z, the slowest grid dimension: a batch's workgroups follow those of the batch before it): the batch's keys, query count and
+    // matrix rows come from the table - uniform loads, the values stay in scalar registers as the arguments they replace do
+    // (the plain kernel only: a batch with clusters goes on its own)
+    if constexpr (!CL) { if (bt) { const JoinBatch b = bt[blockIdx.z]; qkey = (const T *)b.qkey; nq = b.nq; mm32 = b.mm32; } }
     const uint32_t dedup_below = dedup_flags & 0x7FFFFFFFu;      // bit 31: the in-place own-cluster test (below) is on for this launch
     static_assert(JU == 4 && JN % JU == 0, "GS_SEL4 / pending mask are written for JU = 4");
     static_assert(!CL || SR == 1, "clusters: request batches only");
@@ -654,9 +668,13 @@ constexpr uint32_t JDEDUP_MINQ = 2;      // clusters of at least this many queri
 // tiles of 8 consecutive counters per lane x 256 lanes; a workgroup walks many tiles, stages the heavy pairs it finds in LDS and sends them to
 // the list in blocks (a first version paid one same-address global atomic per wavefront and tile: 1.1e6 of them, 10 ms per batch)
 constexpr uint32_t HS_STAGE = 3072;
-__global__ __launch_bounds__(256) void k_heavy_scan(const uint16_t *__restrict__ mat, uint64_t ld, uint32_t nq, uint64_t n, uint32_t m, uint2 *__restrict__ pairs,
-                                                    unsigned long long *__restrict__ ctr /* [0] pairs, [1] matches so far */, uint64_t cap)
+constexpr uint32_t JCTR = 8;             // 64-bit counters per batch (64 bytes: [0] heavy pairs, [1] matches of phase 0)
+__global__ __launch_bounds__(256) void k_heavy_scan(const uint16_t *__restrict__ mat, uint64_t ld, uint64_t n, uint32_t m, uint2 *__restrict__ pairs,
+                                                    unsigned long long *__restrict__ ctr /* [0] pairs, [1] matches so far */, uint64_t cap, JoinSpan sp)
 {
+    // blockIdx.y = batch: its rows of the matrix, its region of the pair list, its counters
+    const uint32_t nq = span_nq(sp, blockIdx.y);
+    mat += (uint64_t)span_q0(sp, blockIdx.y) * ld; pairs += (uint64_t)blockIdx.y * cap; ctr += (uint64_t)blockIdx.y * JCTR;
     __shared__ uint2 stage[HS_STAGE];
     __shared__ uint32_t sn;
     __shared__ unsigned long long sbase;
@@ -699,14 +717,17 @@ __global__ __launch_bounds__(256) void k_heavy_scan(const uint16_t *__restrict__
     for (int o = 32; o > 0; o >>= 1) tot += __shfl_down(tot, o);
     if ((threadIdx.x & 63) == 0 && tot) atomicAdd(&ctr[1], (unsigned long long)tot);
 }
-__global__ void k_label_init(uint32_t *__restrict__ labq, uint32_t nq, uint32_t *__restrict__ labe, uint64_t n)
+// (the label kernels: blockIdx.y = batch; query labels and label counts of a batch sit at its first query, node labels at batch * n, pairs at batch * cap)
+__global__ void k_label_init(uint32_t *__restrict__ labq, JoinSpan sp, uint32_t *__restrict__ labe, uint64_t n)
 {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nq) labq[i] = (uint32_t)i;
-    if (i < n) labe[i] = 0xFFFFFFFFu;
+    if (i < span_nq(sp, blockIdx.y)) labq[span_q0(sp, blockIdx.y) + i] = (uint32_t)i;
+    if (i < n) labe[(uint64_t)blockIdx.y * n + i] = 0xFFFFFFFFu;
 }
-__global__ void k_label_prop(const uint2 *__restrict__ pairs, const unsigned long long *__restrict__ ctr, uint64_t cap, uint32_t *__restrict__ labq, uint32_t *__restrict__ labe)
+__global__ void k_label_prop(const uint2 *__restrict__ pairs, const unsigned long long *__restrict__ ctr, uint64_t cap, uint32_t *__restrict__ labq, uint32_t *__restrict__ labe,
+                             JoinSpan sp, uint64_t n)
 {
+    pairs += (uint64_t)blockIdx.y * cap; ctr += (uint64_t)blockIdx.y * JCTR; labq += span_q0(sp, blockIdx.y); labe += (uint64_t)blockIdx.y * n;
     const uint64_t np = ctr[0] < cap ? ctr[0] : cap;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < np; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint2 p = pairs[i];
@@ -716,8 +737,10 @@ __global__ void k_label_prop(const uint2 *__restrict__ pairs, const unsigned lon
     }
 }
 // nodes per component label (labels are query numbers): what the host needs to size the components without the 1.2 MB of node labels
-__global__ void k_label_count(const uint32_t *__restrict__ labe, uint64_t n, uint32_t nq, uint32_t *__restrict__ cnt)
+__global__ void k_label_count(const uint32_t *__restrict__ labe, uint64_t n, JoinSpan sp, uint32_t *__restrict__ cnt)
 {
+    labe += (uint64_t)blockIdx.y * n; cnt += span_q0(sp, blockIdx.y);
+    const uint32_t nq = span_nq(sp, blockIdx.y);
     for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (uint64_t)gridDim.x * blockDim.x) { const uint32_t l = labe[e]; if (l < nq) atomicAdd(&cnt[l], 1u); }
 }
 // cluster-sorted copy of the keys of the clustered queries: qs[s * nh + pos] = row qlist[pos], slot s
@@ -742,8 +765,10 @@ struct JoinGeom { uint32_t chunks, log2p; size_t lds1, ldsq; };
 template <int KIND, typename T, bool CL>
 static int join_launch(gs_ctx *c, const JoinGeom &g, const T *qkey, uint32_t nq, const void *cols, uint64_t colcap, uint64_t n, uint32_t slot_lo, uint32_t slot_hi,
                        uint16_t *out16, uint64_t ld, unsigned long long *stats, uint64_t col0, bool few_blocks, const uint16_t *qcl, const uint16_t *nodelab, const T *qs,
-                       uint32_t nh, const uint32_t *cl_lo, const uint32_t *qlist, uint32_t dedup_below = 0)
+                       uint32_t nh, const uint32_t *cl_lo, const uint32_t *qlist, uint32_t dedup_below = 0, const JoinBatch *batches = nullptr, uint32_t nbatches = 1)
 {
+    // batches (device table of nbatches entries): one launch over several batches, the batch as the grid's slowest dimension; qkey and out16 are then unused and nq is
+    // the largest batch's. Every batch keeps the geometry it would have alone.
     // one workgroup = JT * JN nodes x a block of slots; blocks sized so that the grid is about eight rounds of 2 workgroups per CU
     // (one round leaves the slowest workgroup's tail exposed: 145 -> 125 ms per 10 k-query request), at least 32 slots each
     const uint32_t ms = slot_hi - slot_lo, chunks = g.chunks;
@@ -757,7 +782,7 @@ static int join_launch(gs_ctx *c, const JoinGeom &g, const T *qkey, uint32_t nq,
     // (not for a handful of chunks: the workgroups of one chunk then are a few rounds of the device with a tail each - 50 000 nodes, 7 chunks, 8-byte keys: 47.8 -> 56.1 ms)
     const int chunk_major = getenv("GS_JOIN_CHUNK_MAJOR") ? atoi(getenv("GS_JOIN_CHUNK_MAJOR")) : ((nq >= 1024 && chunks >= 16) ? 1 : 0);
     const uint32_t nblk = (ms + slots_per_wg - 1) / slots_per_wg;
-    dim3 jg(chunk_major ? nblk : chunks, chunk_major ? chunks : nblk);
+    dim3 jg(chunk_major ? nblk : chunks, chunk_major ? chunks : nblk, nbatches);
     // small tables (an insert batch): several slots per barrier round while two workgroups still fit a CU
     int sr = 1;
     if (!CL) {
@@ -771,7 +796,7 @@ static int join_launch(gs_ctx *c, const JoinGeom &g, const T *qkey, uint32_t nq,
         auto kern = KERN;                                                                                                                             \
         if (lds > 48 * 1024) GS_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));             \
         hipLaunchKernelGGL(kern, jg, dim3(JT), lds, c->stream, qkey, nq, g.log2p, (const T *)cols, colcap, n, slot_lo, slot_hi, slots_per_wg, (uint32_t *)out16, ld, \
-                           stats, chunk_major, col0, qcl, nodelab, qs, nh, cl_lo, qlist, dedup_below);                                                             \
+                           stats, chunk_major, col0, qcl, nodelab, qs, nh, cl_lo, qlist, dedup_below, batches);                                                    \
     } while (0)
     if (CL) GS_JOIN_GO((k_match_join<KIND, T, 1, CL>));
     else if (sr == 4) GS_JOIN_GO((k_match_join<KIND, T, 4, false>));
@@ -814,40 +839,61 @@ static int join_sample_declines(gs_ctx *c, const JoinGeom &g, uint32_t m, const 
     return GS_OK;
 }
 
+// what the host keeps of one batch between its decision and the launches that finish it
+struct JoinPlan {
+    uint64_t npairs = 0, pair_cap = 0, nhe = 0;
+    uint32_t K = 0, ntiles = 0, nhq = 0, dedup_below = 1;
+    bool sample = false;                       // K == 0: the sampled estimate decides between the plain join and the compare tile kernel
+    std::vector<uint32_t> cq, ce_, cid;
+};
+
+// A request of nq_all queries in batches of jq (the last may be shorter; JOIN_BATCHES at most), rows of the matrix and of the queries consecutive. What comes before the
+// host's decisions - the memset, the query columns, phase 0, heavy pairs, labels and their copies - is queued for all batches and waited for ONCE, and the batches that
+// end in the plain main pass share one launch (the batch as the slowest grid dimension: the next batch's workgroups fill the tail of the one before). A batch that
+// clusters, declines or needs the sample follows on its own. declined[b] per batch.
 template <int KIND, typename T>
-static int join_impl(gs_ctx *c, uint32_t m, const uint8_t *qrows, uint64_t qstride, uint32_t nq, const void *cols, uint64_t colcap, uint64_t n, uint16_t *out16,
+static int join_impl(gs_ctx *c, uint32_t m, const uint8_t *qrows, uint64_t qstride, uint32_t nq_all, uint32_t jq, const void *cols, uint64_t colcap, uint64_t n, uint16_t *out16,
                      uint64_t ld, DevBuf *scratch /* [JOIN_SCRATCH] reusable */, int *declined, unsigned long long *stats, bool init, uint64_t col0,
                      const void *rows, uint64_t rstride)
 {
     int rc;
-    if (declined) *declined = 0;
-    const size_t items = (size_t)m * nq;
+    const uint32_t B = (nq_all + jq - 1) / jq;
+    const JoinSpan span{nq_all, jq};
+    auto q0_of = [&](uint32_t b) { return b * jq; };
+    auto nq_of = [&](uint32_t b) { return std::min<uint32_t>(jq, nq_all - b * jq); };
+    if (declined) for (uint32_t b = 0; b < B; b++) declined[b] = 0;
     DevBuf &k0 = scratch[0];
-    if ((rc = k0.ensure(sizeof(T) * items))) return rc;
+    if ((rc = k0.ensure(sizeof(T) * (size_t)m * nq_all))) return rc;
+    auto qkey_of = [&](uint32_t b) { return k0.as<T>() + (size_t)m * q0_of(b); };
+    auto out_of = [&](uint32_t b) { return out16 + (uint64_t)q0_of(b) * ld; };
     // every 16-bit counter starts at m and every match takes one off: the matrix leaves the join as mismatch counts, without the pass that
     // used to turn matches into mismatches (6 GB read + written per 10 000-query request)
-    if (init) GS_HIP_CHECK(hipMemsetD16Async((hipDeviceptr_t)out16, (unsigned short)m, (size_t)nq * ld, c->stream));
-    dim3 tg((nq + 31) / 32, (m + 31) / 32);
-    hipLaunchKernelGGL((k_query_cols<KIND, T>), tg, dim3(256), 0, c->stream, qrows, qstride, nq, m, k0.as<T>());
+    if (init) GS_HIP_CHECK(hipMemsetD16Async((hipDeviceptr_t)out16, (unsigned short)m, (size_t)nq_all * ld, c->stream));
+    dim3 tg((jq + 31) / 32, (m + 31) / 32, B);
+    hipLaunchKernelGGL((k_query_cols<KIND, T>), tg, dim3(256), 0, c->stream, qrows, qstride, span, m, k0.as<T>());
     GS_HIP_CHECK(hipGetLastError());
+    const uint32_t nq_max = jq, nq_min = nq_of(B - 1);      // the largest batch sizes the table, the smallest decides whether the request is one for heavy blocks
     JoinGeom g;
     g.log2p = 6;
-    while (g.log2p < (uint32_t)JP_MAX_LOG2 && (double)(1u << g.log2p) * 0.4 < (double)nq) g.log2p++;
+    while (g.log2p < (uint32_t)JP_MAX_LOG2 && (double)(1u << g.log2p) * 0.4 < (double)nq_max) g.log2p++;
     g.chunks = (uint32_t)((n + (uint64_t)JT * JN - 1) / ((uint64_t)JT * JN));
     g.lds1 = (sizeof(T) + 4) * ((size_t)1 << g.log2p) + ((size_t)1 << JB_LOG2) / 8;
     g.ldsq = (size_t)(JT / 64) * 64 * (sizeof(T) == 4 ? 8 : 16);         // the wavefronts' survivor queues (one-slot rounds; 8-byte keys: two words per entry; their cluster variant does not use it)
     const bool may_decline = declined && m >= 64 && n >= 4096;
     const char *ce = getenv("GS_JOIN_CLUSTER");
     // heavy blocks: request batches (the insert path passes no `declined`) large enough for phase 0 to be a small part of the work
-    bool cluster = declined && init && col0 == 0 && rows && nq >= 256 && n >= 8192 && m >= 16 * JS0 && (ld % 8) == 0 && !(ce && !atoi(ce)) && !getenv("GS_JOIN_DECLINE");
+    bool cluster = declined && init && col0 == 0 && rows && nq_min >= 256 && n >= 8192 && m >= 16 * JS0 && (ld % 8) == 0 && !(ce && !atoi(ce)) && !getenv("GS_JOIN_DECLINE");
     if (ce && atoi(ce) == 2) cluster = declined && init && col0 == 0 && rows && m >= 2 * JS0 && (ld % 8) == 0;       // tests: small shapes too
     if (!cluster) {
-        if (may_decline) {
-            int dec = 0;
-            if ((rc = join_sample_declines<KIND, T>(c, g, m, k0.as<T>(), nq, cols, colcap, n, scratch, &dec))) return rc;
-            if (dec) { *declined = 1; return GS_OK; }
+        for (uint32_t b = 0; b < B; b++) {
+            if (may_decline) {
+                int dec = 0;
+                if ((rc = join_sample_declines<KIND, T>(c, g, m, qkey_of(b), nq_of(b), cols, colcap, n, scratch, &dec))) return rc;
+                if (dec) { declined[b] = 1; continue; }
+            }
+            if ((rc = join_launch<KIND, T, false>(c, g, qkey_of(b), nq_of(b), cols, colcap, n, 0, m, out_of(b), ld, stats, col0, false, nullptr, nullptr, nullptr, 0, nullptr, nullptr))) return rc;
         }
-        return join_launch<KIND, T, false>(c, g, k0.as<T>(), nq, cols, colcap, n, 0, m, out16, ld, stats, col0, false, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+        return GS_OK;
     }
     const bool verbose = getenv("GS_JOIN_VERBOSE") != nullptr;
     // GS_JOIN_TIMES=1: wall time of every stage (a sync after each: diagnostic only)
@@ -861,190 +907,257 @@ static int join_impl(gs_ctx *c, uint32_t m, const uint8_t *qrows, uint64_t qstri
         t_prev = now;
     };
     lap("query columns + memset");
-    // ---- phase 0 + heavy pairs + labels
+    // ---- phase 0 + heavy pairs + labels, every batch with a region of its own in each list: pairs at b * cap, counters at b * JCTR, query labels and label counts at
+    // the batch's first query, node labels at b * n
     DevBuf &pairs = scratch[2], &ctr = scratch[3], &labq = scratch[4], &labe = scratch[5];
-    uint64_t pair_cap = JPAIR_CAP;
-    DevBuf &lcnt = scratch[14];
-    if ((rc = pairs.ensure(pair_cap * 8)) || (rc = ctr.ensure(64)) || (rc = labq.ensure(4 * (size_t)nq)) || (rc = labe.ensure(4 * (size_t)n)) || (rc = lcnt.ensure(4 * (size_t)nq))) return rc;
-    pair_cap = std::max<uint64_t>(pair_cap, pairs.bytes / 8);       // (a list grown by an earlier batch stays)
-    if ((rc = join_launch<KIND, T, false>(c, g, k0.as<T>(), nq, cols, colcap, n, 0, JS0, out16, ld, stats, 0, true, nullptr, nullptr, nullptr, 0, nullptr, nullptr))) return rc;
-    lap("phase 0 (first slots)");
+    DevBuf &lcnt = scratch[14], &dbt = scratch[15];
+    if ((rc = pairs.ensure(JPAIR_CAP * 8 * B)) || (rc = ctr.ensure(8 * JCTR * B)) || (rc = labq.ensure(4 * (size_t)nq_all)) || (rc = labe.ensure(4 * (size_t)n * B)) ||
+        (rc = lcnt.ensure(4 * (size_t)nq_all)) || (rc = dbt.ensure(2 * JOIN_BATCHES * sizeof(JoinBatch)))) return rc;
+    uint64_t cap_each = pairs.bytes / 8 / B;                        // (a list grown by an earlier batch stays)
+    if (const char *pc = getenv("GS_JOIN_PAIR_CAP")) cap_each = std::min<uint64_t>(cap_each, (uint64_t)std::max(1, atoi(pc)));      // tests: the overflow retry at small shapes
     // (pinned staging: a pageable destination makes the runtime bounce 1.2 MB through its own buffer, synchronously)
-    uint8_t *pin = (uint8_t *)pinned_pool(c)->ensure(PIN_JOIN, 64 + 4 * (2 * (size_t)nq + n) + 2 * ((size_t)nq + 8 + (size_t)g.chunks * JT * JN) + 64);
+    //   [counters: JOIN_BATCHES x 64 B][launch tables: 2 x JOIN_BATCHES entries][query labels: nq_all][label counts: nq_all][per batch: node labels n | cluster ids of its
+    //   queries | of the nodes, in the lanes' layout]
+    const size_t pin_head = 64 * (size_t)JOIN_BATCHES + 2 * JOIN_BATCHES * sizeof(JoinBatch) + 8 * (size_t)nq_all;
+    const size_t pin_each = (4 * (size_t)n + 2 * ((size_t)nq_max + 8 + (size_t)g.chunks * JT * JN) + 63) & ~(size_t)63;
+    uint8_t *pin = (uint8_t *)pinned_pool(c)->ensure(PIN_JOIN, pin_head + 64 + pin_each * B);
     GS_REQUIRE(pin, GS_ERR_HIP, "match-join: pinned staging buffer");
-    unsigned long long *hc = (unsigned long long *)pin;
-    uint32_t *hlq = (uint32_t *)(pin + 64), *hcn = hlq + nq, *hle = hcn + nq;
+    JoinBatch *hbt = (JoinBatch *)(pin + 64 * (size_t)JOIN_BATCHES);
+    uint32_t *hlq_all = (uint32_t *)(hbt + 2 * JOIN_BATCHES), *hcn_all = hlq_all + nq_all;
+    auto hc_of = [&](uint32_t b) { return (unsigned long long *)(pin + 64 * (size_t)b); };
+    auto hle_of = [&](uint32_t b) { return (uint32_t *)(pin + ((pin_head + 63) & ~(size_t)63) + pin_each * b); };
+    // a launch of k_match_join over several batches: its table (entries [at, at + cnt) of the staging and of the device copy: phase 0 and the main pass each have
+    // their own, so neither copy is overtaken by the host filling the next)
+    auto join_many = [&](const std::vector<uint32_t> &bs, uint32_t at, uint32_t slot_lo, uint32_t slot_hi, bool few_blocks) -> int {
+        if (bs.size() == 1)
+            return join_launch<KIND, T, false>(c, g, qkey_of(bs[0]), nq_of(bs[0]), cols, colcap, n, slot_lo, slot_hi, out_of(bs[0]), ld, stats, 0, few_blocks, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+        for (size_t i = 0; i < bs.size(); i++) hbt[at + i] = JoinBatch{qkey_of(bs[i]), (uint32_t *)out_of(bs[i]), nq_of(bs[i]), 0u};
+        GS_HIP_CHECK(hipMemcpyAsync(dbt.as<JoinBatch>() + at, hbt + at, bs.size() * sizeof(JoinBatch), hipMemcpyHostToDevice, c->stream));
+        return join_launch<KIND, T, false>(c, g, (const T *)nullptr, nq_max, cols, colcap, n, slot_lo, slot_hi, nullptr, ld, stats, 0, few_blocks, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                                           0, dbt.as<JoinBatch>() + at, (uint32_t)bs.size());
+    };
+    std::vector<uint32_t> all_b(B);
+    for (uint32_t b = 0; b < B; b++) all_b[b] = b;
+    if ((rc = join_many(all_b, 0, 0, JS0, true))) return rc;
+    lap("phase 0 (first slots)");
+    // heavy pairs, labels and label counts of the batches [b0, b0 + cnt), each batch's list `cap` pairs long from pairs.p on, and their copies to the host
+    auto scan_and_label = [&](uint32_t b0, uint32_t cnt, uint64_t cap) -> int {
+        const uint32_t q0 = q0_of(b0), nqs = std::min<uint32_t>(nq_all - q0, cnt * jq);
+        const JoinSpan sp{nqs, jq};
+        unsigned long long *dctr = ctr.as<unsigned long long>() + (size_t)JCTR * b0;
+        uint32_t *dlq = labq.as<uint32_t>() + q0, *dle = labe.as<uint32_t>() + (size_t)n * b0, *dcn = lcnt.as<uint32_t>() + q0;
+        GS_HIP_CHECK(hipMemsetAsync(dctr, 0, 8 * (size_t)JCTR * cnt, c->stream));
+        hipLaunchKernelGGL(k_heavy_scan, dim3(c->n_cu * 8, cnt), dim3(256), 0, c->stream, out_of(b0), ld, n, m, pairs.as<uint2>(), dctr, cap, sp);
+        lap("heavy scan");
+        hipLaunchKernelGGL(k_label_init, dim3((uint32_t)((std::max<uint64_t>(n, jq) + 255) / 256), cnt), dim3(256), 0, c->stream, dlq, sp, dle, n);
+        for (int it = 0; it < 6; it++)
+            hipLaunchKernelGGL(k_label_prop, dim3(c->n_cu * 4, cnt), dim3(256), 0, c->stream, pairs.as<uint2>(), dctr, cap, dlq, dle, sp, n);
+        GS_HIP_CHECK(hipMemsetAsync(dcn, 0, 4 * (size_t)nqs, c->stream));
+        hipLaunchKernelGGL(k_label_count, dim3(c->n_cu * 2, cnt), dim3(256), 0, c->stream, dle, n, sp, dcn);
+        GS_HIP_CHECK(hipGetLastError());
+        GS_HIP_CHECK(hipMemcpyAsync(hc_of(b0), dctr, 8 * (size_t)JCTR * cnt, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(hlq_all + q0, dlq, 4 * (size_t)nqs, hipMemcpyDeviceToHost, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(hcn_all + q0, dcn, 4 * (size_t)nqs, hipMemcpyDeviceToHost, c->stream));
+        return GS_OK;
+    };
+    if ((rc = scan_and_label(0, B, cap_each))) return rc;
+    GS_HIP_CHECK(hipStreamSynchronize(c->stream));                  // the one wait of the request: every batch's counts and labels are on the host
+    lap("labels + query labels down");
+    std::vector<JoinPlan> plans(B);
     // The pair list holds (query, node) pairs with >= JHEAVY matches in the first slots. A database with a species of 30 000 genomes (skewed family sizes:
     // NCBI / GTDB, /root/reference/README.md:134) puts queries-of-that-species x 30 000 pairs on it - 7.6 M per 2500-query batch at 10 % of 300 k nodes -
-    // where 100-member families leave ~0.3 M. A list that overflows is sized to what the scan counted and the scan repeated (once: the count is exact);
-    // round 5 gave such a batch to the compare tile kernel (3 s per 10 000 queries instead of 0.1).
-    for (int attempt = 0;; attempt++) {
-        GS_HIP_CHECK(hipMemsetAsync(ctr.p, 0, 64, c->stream));
-        hipLaunchKernelGGL(k_heavy_scan, dim3(c->n_cu * 8), dim3(256), 0, c->stream, out16, ld, nq, n, m, pairs.as<uint2>(), ctr.as<unsigned long long>(), pair_cap);
-        lap("heavy scan");
-        hipLaunchKernelGGL(k_label_init, dim3((uint32_t)((std::max<uint64_t>(n, nq) + 255) / 256)), dim3(256), 0, c->stream, labq.as<uint32_t>(), nq, labe.as<uint32_t>(), n);
-        for (int it = 0; it < 6; it++)
-            hipLaunchKernelGGL(k_label_prop, dim3(c->n_cu * 4), dim3(256), 0, c->stream, pairs.as<uint2>(), ctr.as<unsigned long long>(), pair_cap, labq.as<uint32_t>(), labe.as<uint32_t>());
-        GS_HIP_CHECK(hipMemsetAsync(lcnt.p, 0, 4 * (size_t)nq, c->stream));
-        hipLaunchKernelGGL(k_label_count, dim3(c->n_cu * 2), dim3(256), 0, c->stream, labe.as<uint32_t>(), n, nq, lcnt.as<uint32_t>());
-        GS_HIP_CHECK(hipGetLastError());
-        GS_HIP_CHECK(hipMemcpyAsync(hc, ctr.p, 16, hipMemcpyDeviceToHost, c->stream));
-        GS_HIP_CHECK(hipMemcpyAsync(hlq, labq.p, 4 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
-        GS_HIP_CHECK(hipMemcpyAsync(hcn, lcnt.p, 4 * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    // where 100-member families leave ~0.3 M. A list that overflows is sized to what the scan counted and the scan repeated for that batch alone (once: the count
+    // is exact; the other batches' lists have served their labels and may go); round 5 gave such a batch to the compare tile kernel (3 s per 10 000 queries
+    // instead of 0.1).
+    for (uint32_t b = 0; b < B; b++) {
+        plans[b].pair_cap = cap_each;
+        const uint64_t want = hc_of(b)[0];
+        if (want <= cap_each || want > JPAIR_MAX) continue;
+        if (want * 8 + 4096 > pairs.bytes && pairs.alloc((size_t)want * 8 + 4096) != GS_OK) { (void)hipGetLastError(); (void)pairs.alloc(JPAIR_CAP * 8 * B); continue; }      // no room: as before
+        plans[b].pair_cap = want + 512;
+        if ((rc = scan_and_label(b, 1, plans[b].pair_cap))) return rc;
         GS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        lap("labels + query labels down");
-        if (hc[0] <= pair_cap || attempt || hc[0] > JPAIR_MAX) break;
-        if (pairs.alloc((size_t)hc[0] * 8 + 4096) != GS_OK) { (void)hipGetLastError(); (void)pairs.alloc(JPAIR_CAP * 8); pair_cap = JPAIR_CAP; break; }      // no room: as before
-        pair_cap = hc[0] + 512;
+        lap("labels + query labels down (list regrown)");
     }
-    const uint64_t npairs = hc[0];
-    // ---- clusters: labels with >= 2 queries and >= 1 node, largest blocks dropped while the tile budget is exceeded
-    std::vector<uint32_t> cq(nq, 0), ce_(nq, 0), cid(nq, 0);
-    uint32_t K = 0, ntiles = 0, nhq = 0, dedup_below = 1;
-    uint64_t nhe = 0;
-    const uint32_t minq = getenv("GS_JOIN_CLUSTER_MINQ") ? (uint32_t)std::max(2, atoi(getenv("GS_JOIN_CLUSTER_MINQ"))) : (ce && atoi(ce) == 2 ? 2u : 12u);
-    // A component becomes a cluster when it has enough QUERIES (the run of equal keys its isolates leave in the table is what costs) or enough PAIRS: a family of
-    // 2000 genomes with five isolates in the batch has 8000 related (query, node) pairs of thousands of matches each, of which a node's run-length accumulator
-    // absorbs one query's - the rest are atomics. Uniform 100-member families never reach the pair bar (5 x 100 = 400); a skewed database (tools/skew_probe.py)
-    // is full of such components. Where the bar sits: a component costs at least one 128 x 128 compare tile (~18 us), a related pair left to the atomics ~0.5 us
-    // (thousands of matches): ~40 pairs per tile break even; 128 leaves the uniform regime alone (the `min_saved` guard below still decides whether the
-    // cluster-aware pass runs at all). tools/skew_probe.py, 100 k rows: 32 -> 47.0 ms, 128 -> 50.2, 1024 -> 50.6 (first form), 4096 -> 57.9, none: 258.
-    const uint64_t minpairs = getenv("GS_JOIN_CLUSTER_MINPAIRS") ? (uint64_t)atoll(getenv("GS_JOIN_CLUSTER_MINPAIRS")) : 128;
-    auto is_cluster = [&](uint32_t l) { return cq[l] >= minq || (cq[l] >= 2 && (uint64_t)(cq[l] - 1) * hcn[l] >= minpairs); };
-    // (query, node) pairs the would-be clusters take off the match-by-match path, from the per-label counts alone: below the bar of the cluster-aware pass (min_saved, further
-    // down) the batch takes the plain join without the node labels ever leaving the device (1.2 MB + a host pass over 300 k nodes per batch: 3 ms per request when every
-    // batch of unrelated isolates paid it for its handful of three-query components)
-    const uint64_t min_scaled0 = (uint64_t)((double)nq * 32.0 * (double)n / 3.0e5);
-    const uint64_t min_saved0 = getenv("GS_JOIN_CLUSTER_MIN") ? (uint64_t)atoll(getenv("GS_JOIN_CLUSTER_MIN")) : (ce && atoi(ce) == 2 ? 0 : std::max<uint64_t>((uint64_t)nq * 8, min_scaled0));
-    bool any = false;
-    if (npairs <= pair_cap) {
-        for (uint32_t q = 0; q < nq; q++) if (hlq[q] < nq) ++cq[hlq[q]];
-        uint64_t est = 0;
-        for (uint32_t l = 0; l < nq; l++) if (cq[l] && hcn[l] && is_cluster(l)) { any = true; est += (uint64_t)(cq[l] - 1) * hcn[l]; }
-        if (est < min_saved0) any = false;
-    }
-    if (any) {
-        // only now the node labels (1.2 MB for 300 k nodes, and a pass over them): a batch of unrelated isolates never gets here
-        GS_HIP_CHECK(hipMemcpyAsync(hle, labe.p, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-        GS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        for (uint64_t e = 0; e < n; e++) if (hle[e] < nq) ce_[hle[e]]++;
-        // Which components become clusters. What a cluster saves grows with the number of its queries: in the plain join a node's hit walks the run
-        // of equal keys its cluster's queries left in the table (83 isolates: 83 entries) while the rest of the wavefront waits, and all but one
-        // of them cost an atomic per match. What it costs is the cluster-aware kernel's own-cluster test on every hit of its nodes. Measured on
-        // 300 k genomes, 2500-query batches (profiles/r04_join_cluster_sweep.txt): 83 queries per family 4.1x faster, 8 per family even, 3 per
-        // family 1.6x slower - components below GS_JOIN_CLUSTER_MINQ (12) queries stay with the run-length accumulator.
-        std::vector<uint32_t> order;
-        for (uint32_t l = 0; l < nq; l++) if (ce_[l] >= 1 && is_cluster(l)) order.push_back(l);
-        auto tiles_of = [&](uint32_t l) { return ((cq[l] + HTILE - 1) / HTILE) * ((ce_[l] + HTILE - 1) / HTILE); };
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { const uint32_t ta = tiles_of(a), tb = tiles_of(b); return ta != tb ? ta < tb : a < b; });
-        std::vector<uint32_t> chosen;
-        for (uint32_t l : order) {
-            if (chosen.size() >= JCL_MAX || ntiles + tiles_of(l) > JTILE_CAP) break;                          // cheapest blocks first
-            chosen.push_back(l); ntiles += tiles_of(l); nhq += cq[l]; nhe += ce_[l];
+    const double tile_rate = KIND == GS_KIND_U64 ? 1.4e13 : 1.6e13;
+    std::vector<uint32_t> plain;               // the batches that end in the plain main pass
+    // ---- every batch's decision (the rules of a batch on its own)
+    for (uint32_t b = 0; b < B; b++) {
+        JoinPlan &pl = plans[b];
+        const uint32_t nq = nq_of(b);
+        const unsigned long long *hc = hc_of(b);
+        const uint32_t *hlq = hlq_all + q0_of(b), *hcn = hcn_all + q0_of(b);
+        uint32_t *hle = hle_of(b);
+        const uint64_t npairs = pl.npairs = hc[0], pair_cap = pl.pair_cap;
+        // ---- clusters: labels with >= 2 queries and >= 1 node, largest blocks dropped while the tile budget is exceeded
+        std::vector<uint32_t> &cq = pl.cq, &ce_ = pl.ce_, &cid = pl.cid;
+        cq.assign(nq, 0); ce_.assign(nq, 0); cid.assign(nq, 0);
+        uint32_t &K = pl.K, &ntiles = pl.ntiles, &nhq = pl.nhq, &dedup_below = pl.dedup_below;
+        uint64_t &nhe = pl.nhe;
+        const uint32_t minq = getenv("GS_JOIN_CLUSTER_MINQ") ? (uint32_t)std::max(2, atoi(getenv("GS_JOIN_CLUSTER_MINQ"))) : (ce && atoi(ce) == 2 ? 2u : 12u);
+        // A component becomes a cluster when it has enough QUERIES (the run of equal keys its isolates leave in the table is what costs) or enough PAIRS: a family of
+        // 2000 genomes with five isolates in the batch has 8000 related (query, node) pairs of thousands of matches each, of which a node's run-length accumulator
+        // absorbs one query's - the rest are atomics. Uniform 100-member families never reach the pair bar (5 x 100 = 400); a skewed database (tools/skew_probe.py)
+        // is full of such components. Where the bar sits: a component costs at least one 128 x 128 compare tile (~18 us), a related pair left to the atomics ~0.5 us
+        // (thousands of matches): ~40 pairs per tile break even; 128 leaves the uniform regime alone (the `min_saved` guard below still decides whether the
+        // cluster-aware pass runs at all). tools/skew_probe.py, 100 k rows: 32 -> 47.0 ms, 128 -> 50.2, 1024 -> 50.6 (first form), 4096 -> 57.9, none: 258.
+        const uint64_t minpairs = getenv("GS_JOIN_CLUSTER_MINPAIRS") ? (uint64_t)atoll(getenv("GS_JOIN_CLUSTER_MINPAIRS")) : 128;
+        auto is_cluster = [&](uint32_t l) { return cq[l] >= minq || (cq[l] >= 2 && (uint64_t)(cq[l] - 1) * hcn[l] >= minpairs); };
+        // (query, node) pairs the would-be clusters take off the match-by-match path, from the per-label counts alone: below the bar of the cluster-aware pass (min_saved, further
+        // down) the batch takes the plain join without the node labels ever leaving the device (1.2 MB + a host pass over 300 k nodes per batch: 3 ms per request when every
+        // batch of unrelated isolates paid it for its handful of three-query components)
+        const uint64_t min_scaled0 = (uint64_t)((double)nq * 32.0 * (double)n / 3.0e5);
+        const uint64_t min_saved0 = getenv("GS_JOIN_CLUSTER_MIN") ? (uint64_t)atoll(getenv("GS_JOIN_CLUSTER_MIN")) : (ce && atoi(ce) == 2 ? 0 : std::max<uint64_t>((uint64_t)nq * 8, min_scaled0));
+        bool any = false;
+        if (npairs <= pair_cap) {
+            for (uint32_t q = 0; q < nq; q++) if (hlq[q] < nq) ++cq[hlq[q]];
+            uint64_t est = 0;
+            for (uint32_t l = 0; l < nq; l++) if (cq[l] && hcn[l] && is_cluster(l)) { any = true; est += (uint64_t)(cq[l] - 1) * hcn[l]; }
+            if (est < min_saved0) any = false;
         }
-        // cluster ids: the large clusters (>= JDEDUP_MINQ queries) first - only they share table entries
-        const uint32_t dq = getenv("GS_JOIN_DEDUP_MINQ") ? (uint32_t)std::max(2, atoi(getenv("GS_JOIN_DEDUP_MINQ"))) : JDEDUP_MINQ;
-        std::stable_sort(chosen.begin(), chosen.end(), [&](uint32_t a, uint32_t b) { return (cq[a] >= dq) > (cq[b] >= dq); });
-        for (uint32_t l : chosen) { cid[l] = ++K; if (cq[l] >= dq) dedup_below = K + 1; }
-    }
-    // (query, node) pairs the blocks take off the match-by-match path; a handful is not worth a second kernel variant and the tile launch
-    uint64_t saved_pairs = 0;
-    for (uint32_t l = 0; l < nq; l++) if (cid[l]) saved_pairs += (uint64_t)(cq[l] - 1) * ce_[l];
-    // (the cluster-aware kernel costs ~7 ms more than the plain one per 2500 queries x 300 k nodes - in proportion to queries x nodes - whatever it saves:
-    // 32 pairs per query at 300 k nodes is where the two meet since the survivor queue made the plain kernel faster. 2500-query batches of isolates of 300
-    // species - a handful of 12-query components by chance - ran 137 ms clustered against 125 plain; 200 species and fewer cluster as before:
-    // profiles/r04_join_cluster_sweep.txt, bottom)
-    const uint64_t min_scaled = (uint64_t)((double)nq * 32.0 * (double)n / 3.0e5);
-    const uint64_t min_saved = getenv("GS_JOIN_CLUSTER_MIN") ? (uint64_t)atoll(getenv("GS_JOIN_CLUSTER_MIN")) : (ce && atoi(ce) == 2 ? 0 : std::max<uint64_t>((uint64_t)nq * 8, min_scaled));
-    if (verbose)
-        fprintf(stderr, "[GS_JOIN] nq=%u n=%llu heavy pairs %llu (matches in the first %u slots %llu): %u clusters, %u queries x %llu nodes in %u tiles, %llu pairs off the atomics%s\n", nq,
-                (unsigned long long)n, (unsigned long long)npairs, JS0, hc[1], K, nhq, (unsigned long long)nhe, ntiles, (unsigned long long)saved_pairs,
-                K && saved_pairs < min_saved ? " - not worth the cluster-aware pass" : "");
-    if (K && saved_pairs < min_saved) K = 0;
-    lap("host: components");
-    if (K == 0) {
-        // nothing to cluster (or too much: pair list overflow): the plain join over the remaining slots - unless the matches of phase 0, scaled to
-        // all slots as if every one cost an atomic, say the tile kernel may be cheaper: then the sampled estimate (which knows about runs) decides
-        const double t_tile = (double)((nq + 127) / 128 * 128) * (double)n * (double)m / (KIND == GS_KIND_U64 ? 1.4e13 : 1.6e13);
-        if (may_decline && (npairs > pair_cap || (double)hc[1] * ((double)m / JS0) / 1.6e10 > 0.5 * t_tile)) {
-            int dec = 0;
-            if ((rc = join_sample_declines<KIND, T>(c, g, m, k0.as<T>(), nq, cols, colcap, n, scratch, &dec))) return rc;
-            if (dec) { *declined = 1; return GS_OK; }
-        }
-        return join_launch<KIND, T, false>(c, g, k0.as<T>(), nq, cols, colcap, n, JS0, m, out16, ld, stats, 0, false, nullptr, nullptr, nullptr, 0, nullptr, nullptr);
-    }
-    // member lists in cluster order, tiles, per-query / per-node cluster ids
-    std::vector<uint32_t> cl_lo(K + 2, 0), ce_lo(K + 2, 0);
-    for (uint32_t l = 0; l < nq; l++) if (cid[l]) { cl_lo[cid[l] + 1] = cq[l]; ce_lo[cid[l] + 1] = ce_[l]; }
-    for (uint32_t k = 1; k <= K + 1; k++) { cl_lo[k] += cl_lo[k - 1]; ce_lo[k] += ce_lo[k - 1]; }
-    std::vector<uint32_t> qlist(nhq), elist(nhe), fq(cl_lo.begin(), cl_lo.end()), fe(ce_lo.begin(), ce_lo.end());
-    // node labels in the layout of the join's lanes: node e = chunk * 8192 + i * 1024 + lane sits at [chunk][i / 4][lane][i % 4] (padded to whole chunks)
-    const uint64_t npad = (uint64_t)g.chunks * JT * JN;
-    uint16_t *hqcl = (uint16_t *)(hle + n), *hnl = hqcl + ((nq + 3) & ~3u);          // (pinned, behind the labels; 8-byte aligned)
-    for (uint32_t q = 0; q < nq; q++) { const uint32_t l = hlq[q]; hqcl[q] = 0; if (l < nq && cid[l]) { hqcl[q] = (uint16_t)cid[l]; qlist[fq[cid[l]]++] = q; } }
-    memset(hnl, 0, 2 * npad);
-    for (uint64_t e = 0; e < n; e++) {
-        const uint32_t l = hle[e];
-        if (l < nq && cid[l]) {
-            const uint64_t ch = e / (JT * JN), w = e % (JT * JN), i = w / JT, ln = w % JT;
-            hnl[((ch * (JN / JU) + i / JU) * JT + ln) * JU + i % JU] = (uint16_t)cid[l];
-            elist[fe[cid[l]]++] = (uint32_t)e;
-        }
-    }
-    std::vector<uint4> tiles;
-    tiles.reserve(ntiles);
-    // the thin tiles first (at most 16 query rows - most clusters of a skewed database: hamming_blocks has a kernel of its own for them), then the others
-    uint32_t n_thin = 0;
-    for (int pass = 0; pass < 2; pass++)
-        for (uint32_t k = 1; k <= K; k++)
-            for (uint32_t a = cl_lo[k]; a < cl_lo[k + 1]; a += HTILE) {
-                const uint32_t qr = std::min<uint32_t>(HTILE, cl_lo[k + 1] - a);
-                if ((qr <= (uint32_t)HTQ) != (pass == 0)) continue;
-                for (uint32_t b = ce_lo[k]; b < ce_lo[k + 1]; b += HTILE) {
-                    tiles.push_back(make_uint4(a, qr, b, std::min<uint32_t>(HTILE, ce_lo[k + 1] - b)));
-                    n_thin += pass == 0;
-                }
+        if (any) {
+            // only now the node labels (1.2 MB for 300 k nodes, and a pass over them): a batch of unrelated isolates never gets here
+            GS_HIP_CHECK(hipMemcpyAsync(hle, labe.as<uint32_t>() + (size_t)n * b, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+            GS_HIP_CHECK(hipStreamSynchronize(c->stream));
+            for (uint64_t e = 0; e < n; e++) if (hle[e] < nq) ce_[hle[e]]++;
+            // Which components become clusters. What a cluster saves grows with the number of its queries: in the plain join a node's hit walks the run
+            // of equal keys its cluster's queries left in the table (83 isolates: 83 entries) while the rest of the wavefront waits, and all but one
+            // of them cost an atomic per match. What it costs is the cluster-aware kernel's own-cluster test on every hit of its nodes. Measured on
+            // 300 k genomes, 2500-query batches (profiles/r04_join_cluster_sweep.txt): 83 queries per family 4.1x faster, 8 per family even, 3 per
+            // family 1.6x slower - components below GS_JOIN_CLUSTER_MINQ (12) queries stay with the run-length accumulator.
+            std::vector<uint32_t> order;
+            for (uint32_t l = 0; l < nq; l++) if (ce_[l] >= 1 && is_cluster(l)) order.push_back(l);
+            auto tiles_of = [&](uint32_t l) { return ((cq[l] + HTILE - 1) / HTILE) * ((ce_[l] + HTILE - 1) / HTILE); };
+            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { const uint32_t ta = tiles_of(a), tb = tiles_of(b); return ta != tb ? ta < tb : a < b; });
+            std::vector<uint32_t> chosen;
+            for (uint32_t l : order) {
+                if (chosen.size() >= JCL_MAX || ntiles + tiles_of(l) > JTILE_CAP) break;                          // cheapest blocks first
+                chosen.push_back(l); ntiles += tiles_of(l); nhq += cq[l]; nhe += ce_[l];
             }
-    lap("host: lists");
-    DevBuf &dqcl = scratch[6], &dnl = scratch[7], &dql = scratch[8], &del = scratch[9], &dtl = scratch[10], &dqs = scratch[11], &dcl = scratch[13];
-    if ((rc = dqcl.ensure(2 * (size_t)nq)) || (rc = dnl.ensure(2 * (size_t)npad)) || (rc = dql.ensure(4 * (size_t)nhq)) || (rc = del.ensure(4 * (size_t)nhe)) ||
-        (rc = dtl.ensure(16 * tiles.size())) || (rc = dqs.ensure(sizeof(T) * (size_t)m * nhq)) || (rc = dcl.ensure(4 * (size_t)(K + 2)))) return rc;
-    GS_HIP_CHECK(hipMemcpyAsync(dqcl.p, hqcl, 2 * (size_t)nq, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(dnl.p, hnl, 2 * (size_t)npad, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(dql.p, qlist.data(), 4 * (size_t)nhq, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(del.p, elist.data(), 4 * (size_t)nhe, hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(dtl.p, tiles.data(), 16 * tiles.size(), hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipMemcpyAsync(dcl.p, cl_lo.data(), 4 * (size_t)(K + 2), hipMemcpyHostToDevice, c->stream));
-    GS_HIP_CHECK(hipStreamSynchronize(c->stream));                  // (the host vectors above are pageable: the copies must be done before they go)
-    hipLaunchKernelGGL((k_query_cols_list<T>), dim3((nhq + 31) / 32, (m + 31) / 32), dim3(256), 0, c->stream, qrows, qstride, dql.as<uint32_t>(), nhq, m, dqs.as<T>());
-    GS_HIP_CHECK(hipGetLastError());
-    lap("uploads + sorted key copy");
-    // the in-place own-cluster test of k_match_join pays where a good part of the NODES belongs to clusters (a skewed database: 72 %); with a percent of them (isolates of a few
-    // species against a uniform database) nearly every wavefront still holds one such node and pays the test's fixed part for nothing: +6 ms per request_redundant step
-    const bool inplace = getenv("GS_JOIN_INPLACE") ? atoi(getenv("GS_JOIN_INPLACE")) != 0 : nhe * 10 >= n;
-    if ((rc = join_launch<KIND, T, true>(c, g, k0.as<T>(), nq, cols, colcap, n, JS0, m, out16, ld, stats, 0, false, dqcl.as<uint16_t>(), dnl.as<uint16_t>(), dqs.as<T>(), nhq,
-                                         dcl.as<uint32_t>(), dql.as<uint32_t>(), dedup_below | (inplace ? 0x80000000u : 0u)))) return rc;
-    {
-        ProfScope ps(c, FAM_HAMMING);
-        lap("cluster-aware join");
-        if ((rc = hamming_blocks(c, KIND, m, qrows, qstride, rows, rstride, dtl.p, (uint32_t)tiles.size(), dql.as<uint32_t>(), del.as<uint32_t>(), out16, ld, n_thin))) return rc;
-        lap("block compare");
+            // cluster ids: the large clusters (>= JDEDUP_MINQ queries) first - only they share table entries
+            const uint32_t dq = getenv("GS_JOIN_DEDUP_MINQ") ? (uint32_t)std::max(2, atoi(getenv("GS_JOIN_DEDUP_MINQ"))) : JDEDUP_MINQ;
+            std::stable_sort(chosen.begin(), chosen.end(), [&](uint32_t a, uint32_t b) { return (cq[a] >= dq) > (cq[b] >= dq); });
+            for (uint32_t l : chosen) { cid[l] = ++K; if (cq[l] >= dq) dedup_below = K + 1; }
+        }
+        // (query, node) pairs the blocks take off the match-by-match path; a handful is not worth a second kernel variant and the tile launch
+        uint64_t saved_pairs = 0;
+        for (uint32_t l = 0; l < nq; l++) if (cid[l]) saved_pairs += (uint64_t)(cq[l] - 1) * ce_[l];
+        // (the cluster-aware kernel costs ~7 ms more than the plain one per 2500 queries x 300 k nodes - in proportion to queries x nodes - whatever it saves:
+        // 32 pairs per query at 300 k nodes is where the two meet since the survivor queue made the plain kernel faster. 2500-query batches of isolates of 300
+        // species - a handful of 12-query components by chance - ran 137 ms clustered against 125 plain; 200 species and fewer cluster as before:
+        // profiles/r04_join_cluster_sweep.txt, bottom)
+        const uint64_t min_scaled = (uint64_t)((double)nq * 32.0 * (double)n / 3.0e5);
+        const uint64_t min_saved = getenv("GS_JOIN_CLUSTER_MIN") ? (uint64_t)atoll(getenv("GS_JOIN_CLUSTER_MIN")) : (ce && atoi(ce) == 2 ? 0 : std::max<uint64_t>((uint64_t)nq * 8, min_scaled));
+        if (verbose)
+            fprintf(stderr, "[GS_JOIN] nq=%u n=%llu heavy pairs %llu (matches in the first %u slots %llu): %u clusters, %u queries x %llu nodes in %u tiles, %llu pairs off the atomics%s\n", nq,
+                    (unsigned long long)n, (unsigned long long)npairs, JS0, hc[1], K, nhq, (unsigned long long)nhe, ntiles, (unsigned long long)saved_pairs,
+                    K && saved_pairs < min_saved ? " - not worth the cluster-aware pass" : "");
+        if (K && saved_pairs < min_saved) K = 0;
+        if (K == 0) {
+            // nothing to cluster (or too much: pair list overflow): the plain join over the remaining slots - unless the matches of phase 0, scaled to
+            // all slots as if every one cost an atomic, say the tile kernel may be cheaper: then the sampled estimate (which knows about runs) decides
+            const double t_tile = (double)((nq + 127) / 128 * 128) * (double)n * (double)m / tile_rate;
+            pl.sample = may_decline && (npairs > pair_cap || (double)hc[1] * ((double)m / JS0) / 1.6e10 > 0.5 * t_tile);
+            if (!pl.sample) plain.push_back(b);
+        }
+    }
+    lap("host: components");
+    // ---- the plain main pass of every batch that takes it, in one launch
+    if (!plain.empty() && (rc = join_many(plain, JOIN_BATCHES, JS0, m, false))) return rc;
+    lap("plain join (merged)");
+    // ---- the other batches, one by one
+    for (uint32_t b = 0; b < B; b++) {
+        JoinPlan &pl = plans[b];
+        const uint32_t nq = nq_of(b), K = pl.K, nhq = pl.nhq, dedup_below = pl.dedup_below;
+        const uint64_t nhe = pl.nhe;
+        const uint8_t *qrows_b = qrows + (uint64_t)q0_of(b) * qstride;
+        if (K == 0) {
+            if (!pl.sample) continue;
+            int dec = 0;
+            if ((rc = join_sample_declines<KIND, T>(c, g, m, qkey_of(b), nq, cols, colcap, n, scratch, &dec))) return rc;
+            if (dec) { declined[b] = 1; continue; }
+            if ((rc = join_launch<KIND, T, false>(c, g, qkey_of(b), nq, cols, colcap, n, JS0, m, out_of(b), ld, stats, 0, false, nullptr, nullptr, nullptr, 0, nullptr, nullptr))) return rc;
+            continue;
+        }
+        const std::vector<uint32_t> &cq = pl.cq, &ce_ = pl.ce_, &cid = pl.cid;
+        const uint32_t *hlq = hlq_all + q0_of(b);
+        uint32_t *hle = hle_of(b);
+        // member lists in cluster order, tiles, per-query / per-node cluster ids
+        std::vector<uint32_t> cl_lo(K + 2, 0), ce_lo(K + 2, 0);
+        for (uint32_t l = 0; l < nq; l++) if (cid[l]) { cl_lo[cid[l] + 1] = cq[l]; ce_lo[cid[l] + 1] = ce_[l]; }
+        for (uint32_t k = 1; k <= K + 1; k++) { cl_lo[k] += cl_lo[k - 1]; ce_lo[k] += ce_lo[k - 1]; }
+        std::vector<uint32_t> qlist(nhq), elist(nhe), fq(cl_lo.begin(), cl_lo.end()), fe(ce_lo.begin(), ce_lo.end());
+        // node labels in the layout of the join's lanes: node e = chunk * 8192 + i * 1024 + lane sits at [chunk][i / 4][lane][i % 4] (padded to whole chunks)
+        const uint64_t npad = (uint64_t)g.chunks * JT * JN;
+        uint16_t *hqcl = (uint16_t *)(hle + n), *hnl = hqcl + ((nq + 3) & ~3u);          // (pinned, behind the labels; 8-byte aligned)
+        for (uint32_t q = 0; q < nq; q++) { const uint32_t l = hlq[q]; hqcl[q] = 0; if (l < nq && cid[l]) { hqcl[q] = (uint16_t)cid[l]; qlist[fq[cid[l]]++] = q; } }
+        memset(hnl, 0, 2 * npad);
+        for (uint64_t e = 0; e < n; e++) {
+            const uint32_t l = hle[e];
+            if (l < nq && cid[l]) {
+                const uint64_t ch = e / (JT * JN), w = e % (JT * JN), i = w / JT, ln = w % JT;
+                hnl[((ch * (JN / JU) + i / JU) * JT + ln) * JU + i % JU] = (uint16_t)cid[l];
+                elist[fe[cid[l]]++] = (uint32_t)e;
+            }
+        }
+        std::vector<uint4> tiles;
+        tiles.reserve(pl.ntiles);
+        // the thin tiles first (at most 16 query rows - most clusters of a skewed database: hamming_blocks has a kernel of its own for them), then the others
+        uint32_t n_thin = 0;
+        for (int pass = 0; pass < 2; pass++)
+            for (uint32_t k = 1; k <= K; k++)
+                for (uint32_t a = cl_lo[k]; a < cl_lo[k + 1]; a += HTILE) {
+                    const uint32_t qr = std::min<uint32_t>(HTILE, cl_lo[k + 1] - a);
+                    if ((qr <= (uint32_t)HTQ) != (pass == 0)) continue;
+                    for (uint32_t e = ce_lo[k]; e < ce_lo[k + 1]; e += HTILE) {
+                        tiles.push_back(make_uint4(a, qr, e, std::min<uint32_t>(HTILE, ce_lo[k + 1] - e)));
+                        n_thin += pass == 0;
+                    }
+                }
+        lap("host: lists");
+        DevBuf &dqcl = scratch[6], &dnl = scratch[7], &dql = scratch[8], &del = scratch[9], &dtl = scratch[10], &dqs = scratch[11], &dcl = scratch[13];
+        if ((rc = dqcl.ensure(2 * (size_t)nq)) || (rc = dnl.ensure(2 * (size_t)npad)) || (rc = dql.ensure(4 * (size_t)nhq)) || (rc = del.ensure(4 * (size_t)nhe)) ||
+            (rc = dtl.ensure(16 * tiles.size())) || (rc = dqs.ensure(sizeof(T) * (size_t)m * nhq)) || (rc = dcl.ensure(4 * (size_t)(K + 2)))) return rc;
+        GS_HIP_CHECK(hipMemcpyAsync(dqcl.p, hqcl, 2 * (size_t)nq, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(dnl.p, hnl, 2 * (size_t)npad, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(dql.p, qlist.data(), 4 * (size_t)nhq, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(del.p, elist.data(), 4 * (size_t)nhe, hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(dtl.p, tiles.data(), 16 * tiles.size(), hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(dcl.p, cl_lo.data(), 4 * (size_t)(K + 2), hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipStreamSynchronize(c->stream));                  // (the host vectors above are pageable: the copies must be done before they go)
+        hipLaunchKernelGGL((k_query_cols_list<T>), dim3((nhq + 31) / 32, (m + 31) / 32), dim3(256), 0, c->stream, qrows_b, qstride, dql.as<uint32_t>(), nhq, m, dqs.as<T>());
+        GS_HIP_CHECK(hipGetLastError());
+        lap("uploads + sorted key copy");
+        // the in-place own-cluster test of k_match_join pays where a good part of the NODES belongs to clusters (a skewed database: 72 %); with a percent of them (isolates of a few
+        // species against a uniform database) nearly every wavefront still holds one such node and pays the test's fixed part for nothing: +6 ms per request_redundant step
+        const bool inplace = getenv("GS_JOIN_INPLACE") ? atoi(getenv("GS_JOIN_INPLACE")) != 0 : nhe * 10 >= n;
+        if ((rc = join_launch<KIND, T, true>(c, g, qkey_of(b), nq, cols, colcap, n, JS0, m, out_of(b), ld, stats, 0, false, dqcl.as<uint16_t>(), dnl.as<uint16_t>(), dqs.as<T>(), nhq,
+                                             dcl.as<uint32_t>(), dql.as<uint32_t>(), dedup_below | (inplace ? 0x80000000u : 0u)))) return rc;
+        {
+            ProfScope ps(c, FAM_HAMMING);
+            lap("cluster-aware join");
+            if ((rc = hamming_blocks(c, KIND, m, qrows_b, qstride, rows, rstride, dtl.p, (uint32_t)tiles.size(), dql.as<uint32_t>(), del.as<uint32_t>(), out_of(b), ld, n_thin))) return rc;
+            lap("block compare");
+        }
     }
     return GS_OK;
 }
 
 uint64_t match_join_max_queries() { const char *e = getenv("GS_JOIN_MAXQ"); return e ? (uint64_t)std::max(1, std::min(4094, atoi(e))) : JQ_MAX; }
 
-// `declined` (optional): set to 1 - and out16 is left at its initial value m - when the sampled match density says the compare tile kernel is the
-// cheaper producer for this batch (the caller then runs it)
+// `declined` (optional; one entry per batch): set to 1 - and the batch's rows of out16 are left at their initial value m - when the sampled match density says the
+// compare tile kernel is the cheaper producer for this batch (the caller then runs it). jq: the nq rows are a request of batches of jq queries (0: one batch)
 int match_join_counts(gs_ctx *c, int kind, uint32_t m, const void *qrows, uint64_t qstride, uint64_t nq, const void *cols, uint64_t colcap, uint64_t n,
-                      uint16_t *out16, uint64_t ld, DevBuf *scratch, int *declined, unsigned long long *stats, bool init, uint64_t col0, const void *rows, uint64_t rstride)
+                      uint16_t *out16, uint64_t ld, DevBuf *scratch, int *declined, unsigned long long *stats, bool init, uint64_t col0, const void *rows, uint64_t rstride,
+                      uint64_t jq)
 {
-    GS_REQUIRE(nq >= 1 && nq <= 4094 && m <= 65535 && (ld % 2) == 0 && ((uintptr_t)out16 % 4) == 0, GS_ERR_INVALID, "match_join_counts: bad shape");
-    GS_REQUIRE((uint64_t)m * nq < ((uint64_t)1 << 31), GS_ERR_INVALID, "match_join_counts: batch too large");
-    if (kind == GS_KIND_U64) return join_impl<GS_KIND_U64, uint64_t>(c, m, (const uint8_t *)qrows, qstride, (uint32_t)nq, cols, colcap, n, out16, ld, scratch, declined, stats, init, col0, rows, rstride);
-    if (kind == GS_KIND_F32) return join_impl<GS_KIND_F32, uint32_t>(c, m, (const uint8_t *)qrows, qstride, (uint32_t)nq, cols, colcap, n, out16, ld, scratch, declined, stats, init, col0, rows, rstride);
-    return join_impl<GS_KIND_U32, uint32_t>(c, m, (const uint8_t *)qrows, qstride, (uint32_t)nq, cols, colcap, n, out16, ld, scratch, declined, stats, init, col0, rows, rstride);
+    if (jq == 0 || jq > nq) jq = nq;
+    GS_REQUIRE(nq >= 1 && jq >= 1 && jq <= 4094 && (nq + jq - 1) / jq <= JOIN_BATCHES && m <= 65535 && (ld % 2) == 0 && ((uintptr_t)out16 % 4) == 0, GS_ERR_INVALID,
+               "match_join_counts: bad shape");
+    GS_REQUIRE((uint64_t)m * jq < ((uint64_t)1 << 31), GS_ERR_INVALID, "match_join_counts: batch too large");
+    if (kind == GS_KIND_U64) return join_impl<GS_KIND_U64, uint64_t>(c, m, (const uint8_t *)qrows, qstride, (uint32_t)nq, (uint32_t)jq, cols, colcap, n, out16, ld, scratch, declined, stats, init, col0, rows, rstride);
+    if (kind == GS_KIND_F32) return join_impl<GS_KIND_F32, uint32_t>(c, m, (const uint8_t *)qrows, qstride, (uint32_t)nq, (uint32_t)jq, cols, colcap, n, out16, ld, scratch, declined, stats, init, col0, rows, rstride);
+    return join_impl<GS_KIND_U32, uint32_t>(c, m, (const uint8_t *)qrows, qstride, (uint32_t)nq, (uint32_t)jq, cols, colcap, n, out16, ld, scratch, declined, stats, init, col0, rows, rstride);
 }
 
 int rows_to_cols(gs_ctx *c, int kind, uint32_t m, const void *rows, uint64_t stride, uint64_t nrows, void *cols, uint64_t colcap, uint64_t first)
