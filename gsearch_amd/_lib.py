@@ -108,6 +108,7 @@ HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
 HMM_FWD_MAX_L, HMM_LSE_N, HMM_FLOOR_ALL = 65536, 5903, -(1 << 31) + 1
 HMM_TRACE_MAX_L, HMM_DOM_WORDS = 65536, 8
 HMM_ENV_WORDS, HMM_ENV_LO, HMM_ENV_HI = 4, -156, -425
+HMM_N2_WORDS, HMM_N2_OMEGA = 4, -8192              # SPEC 13.5: corr, dom_bias, seg_raw, mass; 1024 log2(1 / 256)
 
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
@@ -206,6 +207,8 @@ SYMBOLS = {
     "gs_hmm_trace_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     "gs_hmm_envelopes": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_hmm_envelopes_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_null2": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_null2_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # orfs (SPEC 14)
     "gs_orf_codon_table": (_i, [_u32, C.c_char_p]),
     "gs_orf_translate_dev": (_i, [_vp, C.POINTER(OrfParamsC), _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),

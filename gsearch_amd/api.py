@@ -1254,11 +1254,68 @@ class HmmDb:
         cut = lambda a: [a[int(ro[j]):int(ro[j + 1])] if has[j] else a[:0] for j in range(n)]      # noqa: E731
         return fwd, bck, ne, env, cut(o_rows) if n else [], cut(c_rows) if n else []
 
-    def envelopes(self, records, pairs, max_env=8, rows=False, max_block_rows=0):
-        """records as search() takes them; pairs: (record, profile) index pairs -> what envelopes_packed() returns"""
+    def envelopes(self, records, pairs, max_env=8, rows=False, max_block_rows=0, bias=False):
+        """records as search() takes them; pairs: (record, profile) index pairs -> what envelopes_packed() returns; bias=True (SPEC 13.5): followed by what
+        null2_packed() returns for those envelopes, (slots, seq_bias)"""
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-        return self.envelopes_packed(*filter_aa_records([bytes(r) for r in records]), pairs[:, 0].astype(np.uint32), pairs[:, 1].astype(np.uint32), max_env=max_env,
-                                     rows=rows, max_block_rows=max_block_rows)
+        packed = filter_aa_records([bytes(r) for r in records])
+        pr, pp = pairs[:, 0].astype(np.uint32), pairs[:, 1].astype(np.uint32)
+        got = self.envelopes_packed(*packed, pr, pp, max_env=max_env, rows=rows, max_block_rows=max_block_rows)
+        return got + self.null2_packed(*packed, pr, pp, got[2], got[3]) if bias else got
+
+    def null2_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, n_env, env, n2=False, occ=False, max_block_cells=0):
+        """SPEC 13.5: the null2 bias correction of the envelopes envelopes_packed() listed for the same pairs (n_env, env as it returned them; max_env is
+        env's second extent), Forward and Backward over every listed envelope on the device -> (int32 slots [n_pairs, max_env, 4]: corr, dom_bias, seg_raw,
+        mass of each listed envelope, zeros behind them; int32 seq_bias [n_pairs]). The corrected scores are env_raw - dom_bias and fwd - seq_bias; both
+        biases are >= 0. n2=True: followed by the int32 [n_pairs, max_env, 20] null2 log-odds of the 20 residues; occ=True: followed by two lists, per pair
+        the int32 [listed, M] rows occM and occI (log2 of the expected number of residues every match and insert state emits). A pair whose record is
+        HMM_NO_HIT, empty or holds a byte that is no residue: zeros, seq_bias 0, no rows. When n_env exceeds max_env the sequence bias counts the listed
+        envelopes only. max_block_cells bounds the cells whose Forward rows are alive at once (0: 2^26)"""
+        (_, _, rl), recs = _recs(aa, rec_start, rec_len)
+        pr, pp, pairs = _pairs(pair_rec, pair_prof)
+        n = len(pr)
+        ne = np.ascontiguousarray(n_env, dtype=np.uint32).reshape(-1)
+        env = np.ascontiguousarray(env, dtype=np.int32)
+        if len(ne) != n or env.ndim != 3 or env.shape[0] != n or env.shape[2] != _lib.HMM_ENV_WORDS:
+            raise ValueError("n_env and env: as envelopes_packed() returns them for these pairs")
+        max_env = env.shape[1]
+        slots, sb = np.zeros((n, max_env, _lib.HMM_N2_WORDS), np.int32), np.zeros(n, np.int32)
+        v = np.zeros((n, max_env, 20), np.int32) if n2 else None
+        oo = o_m = o_i = None
+        if occ and n:
+            listed = np.minimum(ne, max_env).astype(np.uint64)
+            M = np.where(pp < len(self), self.M[np.minimum(pp, len(self) - 1)], 0).astype(np.uint64)      # (a bad profile index is refused below)
+            oo = np.zeros(n + 1, np.uint64)
+            oo[1:] = np.cumsum(listed * M)
+            o_m, o_i = np.zeros(max(int(oo[-1]), 1), np.int32), np.zeros(max(int(oo[-1]), 1), np.int32)
+        check(self.ctx.L.gs_hmm_null2(self.ctx.h, self.h, *recs, *pairs, int(max_env), int(max_block_cells), _opt(ne), _opt(env), _opt(slots), _opt(sb), _opt(v), _opt(oo),
+                                      _opt(o_m), _opt(o_i)))
+        out = (slots, sb) + ((v,) if n2 else ())
+        if not occ:
+            return out
+        residue = np.zeros(256, bool)
+        residue[list(b"ACDEFGHIKLMNPQRSTVWYacdefghiklmnpqrstvwy")] = True
+        rs_, aa_ = np.ascontiguousarray(rec_start, dtype=np.uint64), np.ascontiguousarray(aa, dtype=np.uint8)
+        has = [r < len(rl) and int(rl[r]) > 0 and bool(residue[aa_[int(rs_[r]):int(rs_[r]) + int(rl[r])]].all()) for r in pr]      # the pairs that have a score
+        cut = lambda a: [a[int(oo[j]):int(oo[j + 1])].reshape(-1, int(self.M[pp[j]])) if has[j] else a[:0].reshape(0, int(self.M[pp[j]])) for j in range(n)]      # noqa: E731
+        return out + ((cut(o_m), cut(o_i)) if n else ([], []))
+
+    def null2(self, records, pairs, n_env, env, n2=False, occ=False, max_block_cells=0):
+        """records as search() takes them; pairs: (record, profile) index pairs; n_env, env as envelopes() returned them -> what null2_packed() returns"""
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        return self.null2_packed(*filter_aa_records([bytes(r) for r in records]), pairs[:, 0].astype(np.uint32), pairs[:, 1].astype(np.uint32), n_env, env, n2=n2, occ=occ,
+                                 max_block_cells=max_block_cells)
+
+    def null2_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, pair_rec_dev, pair_prof_dev, n_pairs, max_env, n_env_dev, env_dev, slot_out_dev, seq_bias_out_dev,
+                  n2_out_dev=None, occ_off_dev=None, occm_out_dev=None, occi_out_dev=None, max_block_cells=0):
+        """all device memory; the lengths, the pair list, n_env, env and occ_off are read back once"""
+        check(self.ctx.L.gs_hmm_null2_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), pair_rec_dev, pair_prof_dev, int(n_pairs), int(max_env),
+                                          int(max_block_cells), n_env_dev, env_dev, slot_out_dev, seq_bias_out_dev, n2_out_dev, occ_off_dev, occm_out_dev, occi_out_dev))
+
+    def bias_all(self, aa, rec_start, rec_len, pair_rec, pair_prof):
+        """envelopes_all() and null2_packed() behind it -> (fwd, n_env, env, slots, seq_bias)"""
+        fwd, _, ne, env = self.envelopes_all(aa, rec_start, rec_len, pair_rec, pair_prof)
+        return (fwd, ne, env) + self.null2_packed(aa, rec_start, rec_len, pair_rec, pair_prof, ne, env)
 
     def envelopes_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, pair_rec_dev, pair_prof_dev, n_pairs, max_env, fwd_out_dev, bck_out_dev, n_env_out_dev,
                       env_out_dev, row_off_dev=None, out_rows_dev=None, cont_rows_dev=None, max_block_rows=0):
@@ -1327,7 +1384,7 @@ def _check_prefilter(prefilter):
 
 
 def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None, translate=False, min_aa=_lib.ORF_MIN_AA, table=11, prefilter=None,
-              msv_p=0.02, envelopes=None):
+              msv_p=0.02, envelopes=None, bias=False):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
     `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
     `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
@@ -1353,15 +1410,22 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     prefilter="msv" (SPEC 13.3): the MSV score of every pair runs first and Viterbi (and Forward behind it) only for the pairs at or above the MSV floor of
     msv_p (HMMER's F1 = 0.02; None: every pair) - in all three target forms and with both scores. The returned matrix holds HMM_NO_SCORE for the pairs the
     filter left out, the table has rows only for pairs that passed, Z stays the number of records. A pair whose gapped alignment is good and whose
-    ungapped diagonals are weak is lost: the filter's stated cost. prefilter=None: no prefilter."""
+    ungapped diagonals are weak is lost: the filter's stated cost. prefilter=None: no prefilter.
+    bias=True (SPEC 13.5; score="forward" only, ValueError otherwise): the pairs with a Forward raw >= 0 get their posterior envelopes and the null2 bias
+    correction on the device. The table gains a last column `bias` (%.2f bits of seq_bias); bits, evalue and pass_ga are those of the corrected score
+    fwd - seq_bias, and the rows are sorted by it. The envelope table gains a last column `env_bias` and its env_bits are env_raw - dom_bias. The returned
+    matrix stays the uncorrected one. bias=False: no correction, the tables of 13 / 13.1 / 13.4 byte for byte."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
+    if bias and score != "forward":
+        raise ValueError("bias=True corrects Forward scores: score='forward'")
     _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
     fwd = score == "forward"
     dev = None
     if translate:
         dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd or envelopes is not None, domains is not None), table)
+        aa = rs = rl = None
         try:
             ids = dev.names()
             scores = dev.search(db, fwd, filter_p, prefilter is not None, msv_p)
@@ -1376,11 +1440,24 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
         else:
             scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
     Z = len(ids)
-    out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga\n"]
+    out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga" + (b"\tbias\n" if bias else b"\n")]
     listed = []                                                          # the (record, profile) pairs of the table, in its order
+    seq_bias = np.zeros(scores.shape, np.int64)                          # of the pairs that get a row, with bias
+    if bias:
+        try:
+            cand = np.argwhere((scores != _lib.HMM_NO_SCORE) & (scores.astype(np.int64) >= 0))
+            cr, cp = cand[:, 0].astype(np.uint32), cand[:, 1].astype(np.uint32)
+            b_ne, b_env, b_slots, b_sb = (dev.bias_all(db, cr, cp) if dev is not None else db.bias_all(aa, rs, rl, cr, cp))[1:]
+            seq_bias[cand[:, 0], cand[:, 1]] = b_sb
+            slot_of = {(int(r), int(p)): j for j, (r, p) in enumerate(cand)}
+        except Exception:
+            if dev is not None:
+                dev.close()
+            raise
     for p, inf in enumerate(db.info):
-        col = scores[:, p].astype(np.int64)
-        keep = np.flatnonzero((col != _lib.HMM_NO_SCORE) & (col >= 0))
+        plain = scores[:, p].astype(np.int64)
+        keep = np.flatnonzero((plain != _lib.HMM_NO_SCORE) & (plain >= 0))
+        col = plain - seq_bias[:, p]
         for r in keep[np.lexsort((keep, -col[keep]))]:
             listed.append((int(r), p))
             raw = int(col[r])
@@ -1390,7 +1467,8 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
             else:
                 ev = "%.3E" % hmm_evalue(b, inf["mu"], inf["lam"], Z) if inf["mu"] is not None else "-"
             ga = "-" if inf["ga_units"] is None else ("1" if raw >= inf["ga_units"] else "0")
-            out.append(("%s\t%s\t%s\t%.2f\t%s\t%s\n" % (ids[r], inf["name"], inf["acc"] or "-", b, ev, ga)).encode())
+            tail = "\t%.2f\n" % (int(seq_bias[r, p]) / 1024.0) if bias else "\n"
+            out.append(("%s\t%s\t%s\t%.2f\t%s\t%s%s" % (ids[r], inf["name"], inf["acc"] or "-", b, ev, ga, tail)).encode())
     table = b"".join(out)
     if output is not None:
         with open(output, "wb") as f:
@@ -1403,20 +1481,25 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     try:
         if domains is not None:
             _, nd, dom = dev.trace_all(db, pr, pp) if dev is not None else db.trace_all(aa, rs, rl, pr, pp)
-        if envelopes is not None:
+        if envelopes is not None and bias:                               # the candidates' envelopes, in the table's order
+            order = [slot_of[rp] for rp in listed]
+            ne, env, slots = b_ne[order], b_env[order], b_slots[order]
+        elif envelopes is not None:
             _, _, ne, env = dev.envelopes_all(db, pr, pp) if dev is not None else db.envelopes_all(aa, rs, rl, pr, pp)
     finally:
         if dev is not None:
             dev.close()
     env_table = None
     if envelopes is not None:
-        out = [b"target\tprofile\tacc\tenv\tn_env\ti_from\ti_to\tenv_bits\tpeak_occ\n"]
+        out = [b"target\tprofile\tacc\tenv\tn_env\ti_from\ti_to\tenv_bits\tpeak_occ" + (b"\tenv_bias\n" if bias else b"\n")]
         for j, (r, p) in enumerate(listed):
             inf = db.info[p]
             for d in range(int(ne[j])):
                 w = [int(v) for v in env[j, d]]
-                out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%.2f\t%.3f\n" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(ne[j]), w[0], w[1], w[2] / 1024.0,
-                                                                          1.0 - 2.0 ** (w[3] / 1024.0))).encode())
+                db_ = int(slots[j, d, 1]) if bias else 0
+                tail = "\t%.2f\n" % (db_ / 1024.0) if bias else "\n"
+                out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%.2f\t%.3f%s" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(ne[j]), w[0], w[1], (w[2] - db_) / 1024.0,
+                                                                         1.0 - 2.0 ** (w[3] / 1024.0), tail)).encode())
         env_table = b"".join(out)
         with open(envelopes, "wb") as f:
             f.write(env_table)
@@ -1435,8 +1518,31 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     return (ids, scores, table, dom_table) if env_table is None else (ids, scores, table, dom_table, env_table)
 
 
+def _bias_best_hits(scores, goff, thr, bias_of):
+    """SPEC 13.5, the best hits of universal_genes(bias=True): the candidates are the pairs whose uncorrected Forward raw reaches the profile's cutoff - a
+    superset of the final hits, the bias is never negative -, bias_of(pair_rec, pair_prof) gives their seq_bias, and per genome and profile the record
+    with the largest corrected score at or above the cutoff is kept, the lowest record on a tie -> uint32 [n_genomes, n_prof], HMM_NO_HIT where none"""
+    goff = np.asarray(goff, dtype=np.int64)
+    ng, npf = len(goff) - 1, scores.shape[1]
+    rec = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32)
+    s = scores.astype(np.int64)
+    thr = np.asarray(thr, dtype=np.int64)
+    cand = np.argwhere((scores != _lib.HMM_NO_SCORE) & (s >= thr[None, :]))
+    cand = cand[(cand[:, 0] >= goff[0]) & (cand[:, 0] < goff[-1])]
+    if len(cand) == 0:
+        return rec
+    sb = np.asarray(bias_of(cand[:, 0].astype(np.uint32), cand[:, 1].astype(np.uint32)), dtype=np.int64)
+    corrected = s[cand[:, 0], cand[:, 1]] - sb
+    genome = np.searchsorted(goff, cand[:, 0], side="right") - 1
+    for j in np.lexsort((cand[:, 0], -corrected)):                      # best first, the lowest record among equals
+        g, p = int(genome[j]), int(cand[j, 1])
+        if corrected[j] >= thr[p] and rec[g, p] == _lib.HMM_NO_HIT:
+            rec[g, p] = cand[j, 0]
+    return rec
+
+
 def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein", translate=False, min_aa=_lib.ORF_MIN_AA, table=11,
-                    prefilter=None, msv_p=0.02):
+                    prefilter=None, msv_p=0.02, bias=False):
     """One genome per protein FASTA file: per genome the residues of its best protein for every profile that has a hit at the cutoff, in profile
     order - the records an AA sketcher takes for `tohnsw` / `request` at the universal-gene level. -> (list of lists of bytes, uint32 [n_genomes, n_prof]
     record numbers inside each genome's file, HMM_NO_HIT where a profile found nothing). score="forward": the best hits are those of the Forward matrix
@@ -1452,16 +1558,22 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     translate="genes" (SPEC 15): the candidates are the genes of gene_call(), every file one self-trained genome; the record numbers are gene numbers
     inside the genome and the coordinates are the gene's, from its start codon through its stop codon. A called gene longer than the search takes raises
     ValueError and ends the call (translate=True drops and counts such an ORF; see hmmsearch).
-    prefilter="msv" (SPEC 13.3): the best hits are taken among the pairs at or above the MSV floor of msv_p, as hmmsearch(prefilter="msv") scores them."""
+    prefilter="msv" (SPEC 13.3): the best hits are taken among the pairs at or above the MSV floor of msv_p, as hmmsearch(prefilter="msv") scores them.
+    bias=True (SPEC 13.5; score="forward" only, ValueError otherwise): every pair whose Forward raw reaches the cutoff gets its posterior envelopes and
+    the null2 bias correction on the device, and the best hit per genome and profile is the record with the largest corrected score fwd - seq_bias at or
+    above the cutoff (the lowest record on a tie) - the score the files' cutoffs were gathered on. A low-complexity protein that passes a cutoff on its
+    composition alone is dropped. It works with all three target forms and every region."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     if region not in ("protein", "aligned", "envelope"):
         raise ValueError("region: 'protein', 'aligned' or 'envelope'")
+    if bias and score != "forward":
+        raise ValueError("bias=True corrects Forward scores: score='forward'")
     _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
     if translate:
         return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate, prefilter is not None,
-                                           msv_p, region == "envelope")
+                                           msv_p, region == "envelope", bias)
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
@@ -1471,7 +1583,10 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
         scores = db.search_filtered_packed(aa, rs, rl, msv_p=msv_p, forward=score == "forward", filter_p=filter_p)[2 if score == "forward" else 1]
     else:
         scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if score == "forward" else db.search_packed(aa, rs, rl)
-    rec, _ = db.best_hits(scores, np.array(goff, np.uint64), cutoff)
+    if bias:
+        rec = _bias_best_hits(scores, goff, db.thresholds(cutoff), lambda pr, pp: db.bias_all(aa, rs, rl, pr, pp)[4])
+    else:
+        rec, _ = db.best_hits(scores, np.array(goff, np.uint64), cutoff)
     span = {}
     if region == "aligned" and rec.size:
         pair_prof = np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
@@ -1709,6 +1824,30 @@ class _DevOrfs:
         return self._over_pairs(db.envelopes_dev, pair_rec, pair_prof, lambda n, m: [((n,), np.int32, _lib.HMM_NO_SCORE), ((n,), np.int32, _lib.HMM_NO_SCORE),
                                                                                      ((n,), np.uint32, 0), ((n, m, _lib.HMM_ENV_WORDS), np.int32, 0)])
 
+    def bias_all(self, db, pair_rec, pair_prof):
+        """HmmDb.bias_all() over the device residues -> (fwd, n_env, env, slots, seq_bias): the envelopes stay on the device between the two calls"""
+        pr, pp, _ = _pairs(pair_rec, pair_prof)
+        n = len(pr)
+        if n == 0 or self.n == 0:
+            return (np.full(n, _lib.HMM_NO_SCORE, np.int32), np.zeros(n, np.uint32), np.zeros((n, 8, _lib.HMM_ENV_WORDS), np.int32),
+                    np.zeros((n, 8, _lib.HMM_N2_WORDS), np.int32), np.zeros(n, np.int32))
+        with _DevScope(self.ctx) as d:
+            d_pr, d_pp = d.up(pr), d.up(pp)
+
+            def run(m):
+                with _DevScope(self.ctx) as o:
+                    d_fwd, d_bck, d_ne, d_env = o.new(4 * n), o.new(4 * n), o.new(4 * n), o.new(4 * n * m * _lib.HMM_ENV_WORDS)
+                    db.envelopes_dev(self.d_aa, self.d_as, self.d_al, self.n, d_pr, d_pp, n, m, d_fwd, d_bck, d_ne, d_env)
+                    ne = self.ctx.download(d_ne, (n,), np.uint32)
+                    if len(ne) and int(ne.max()) > m:                           # run again with room for every envelope (_all_items)
+                        return None, ne, None
+                    d_slot, d_sb = o.new(4 * n * m * _lib.HMM_N2_WORDS), o.new(4 * n)
+                    db.null2_dev(self.d_aa, self.d_as, self.d_al, self.n, d_pr, d_pp, n, m, d_ne, d_env, d_slot, d_sb)
+                    return (self.ctx.download(d_fwd, (n,), np.int32), ne, self.ctx.download(d_env, (n, m, _lib.HMM_ENV_WORDS), np.int32),
+                            self.ctx.download(d_slot, (n, m, _lib.HMM_N2_WORDS), np.int32), self.ctx.download(d_sb, (n,), np.int32))
+            got = run(8)
+            return got if got[0] is not None else run(int(got[1].max()))
+
     def residues(self, j, a=0, b=None):
         """residues [a, b) of ORF j, read back from the device"""
         b = int(self.aa_len[j]) if b is None else b
@@ -1717,7 +1856,7 @@ class _DevOrfs:
         return self.ctx.download(self.d_aa + int(self.aa_start[j]) + a, (b - a,), np.uint8).tobytes()
 
 
-def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02, envelope=False):
+def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02, envelope=False, bias=False):
     ctx = db.ctx
     dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd or envelope, aligned), table)
     try:
@@ -1725,10 +1864,13 @@ def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, m
         rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
         if ng and npf and dev.n:
             d_score = dev.search_dev(db, fwd, filter_p, prefilter, msv_p)
-            d_goff, d_thr = dev.mem.up(dev.genome_orf_off), dev.mem.up(db.thresholds(cutoff))
-            d_rec, d_sc = dev.mem.new(4 * ng * npf), dev.mem.new(4 * ng * npf)
-            db.best_hits_dev(d_score, dev.n, d_goff, ng, d_thr, d_rec, d_sc)
-            rec = ctx.download(d_rec, (ng, npf), np.uint32)
+            if bias:
+                rec = _bias_best_hits(ctx.download(d_score, (dev.n, npf), np.int32), dev.genome_orf_off, db.thresholds(cutoff), lambda pr, pp: dev.bias_all(db, pr, pp)[4])
+            else:
+                d_goff, d_thr = dev.mem.up(dev.genome_orf_off), dev.mem.up(db.thresholds(cutoff))
+                d_rec, d_sc = dev.mem.new(4 * ng * npf), dev.mem.new(4 * ng * npf)
+                db.best_hits_dev(d_score, dev.n, d_goff, ng, d_thr, d_rec, d_sc)
+                rec = ctx.download(d_rec, (ng, npf), np.uint32)
         span = {}
         if aligned and (rec != _lib.HMM_NO_HIT).any():
             _, nd, dom = dev.trace_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))

@@ -1,7 +1,7 @@
 // gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
 // device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, the best record per genome and profile, the domains of
-// the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2), and the Backward pass and posterior envelopes of a list of pairs
-// (SPEC 13.4). Integers only from the file's digits to the raw score. The reader of profile files and the calls that touch no device are
+// the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2), the Backward pass and posterior envelopes of a list of pairs
+// (SPEC 13.4), and the null2 bias correction of those envelopes (SPEC 13.5). Integers only from the file's digits to the raw score. The reader of profile files and the calls that touch no device are
 // gs_hmm_parse.cpp, a host-only unit; the doubles of hmmsearch (bits, E-values, the table of lse, the Viterbi floor, the reported cutoffs) are all there.
 #include <math.h>
 #include <stdlib.h>
@@ -62,11 +62,12 @@ __device__ __forceinline__ int32_t hmm_lse(int32_t a, int32_t b, const uint16_t 
 
 // The dynamic programs over the cells of a (record, profile) pair (Backward has a row loop of its own, further down). They share one prologue (hmm_stage) and one row loop (hmm_rows) and differ at
 // compile time only, at the points the row loop names.
-enum HmmProg { HMM_VIT, HMM_FWD, HMM_TRACE, HMM_FWD_ROWS, HMM_PROGS };     // HMM_FWD_ROWS: Forward that keeps the special-state rows (SPEC 13.4)
+enum HmmProg { HMM_VIT, HMM_FWD, HMM_TRACE, HMM_FWD_ROWS, HMM_FWD_SEG, HMM_PROGS };     // HMM_FWD_ROWS: Forward that keeps the special-state rows (SPEC 13.4);
+                                                                                       // HMM_FWD_SEG: and M and I of every row as well (SPEC 13.5)
 // what joins alternatives: max (SPEC 13, 13.2) or lse (SPEC 13.1). T is read by lse alone.
 template <HmmProg P> __device__ __forceinline__ int32_t hmm_join(int32_t a, int32_t b, const uint16_t *T)
 {
-    if constexpr (P == HMM_FWD || P == HMM_FWD_ROWS) return hmm_lse(a, b, T); else return max(a, b);
+    if constexpr (P == HMM_FWD || P == HMM_FWD_ROWS || P == HMM_FWD_SEG) return hmm_lse(a, b, T); else return max(a, b);
 }
 // The join over the wavefront, in every lane: neighbours, pairs of pairs, ... - for lse the balanced tree of SPEC 13.1. After the two quad steps the four
 // lanes of a quad hold one value, so the mirrors hand a lane the value of the other quad / the other half row; that is the tree because the join is
@@ -118,6 +119,8 @@ __host__ __device__ constexpr int hmm_ptr_words(int Q) { return (Q + 7) / 8; }
 //   The D pointers inside a lane are taken after D is final. No traced cell is at the clamp (SPEC 13.2), so an equality that a clamped cell decides
 //   differently is never followed.
 // Forward with rows (SPEC 13.4): Forward's arithmetic and barrier, and lane 0 leaves {E[i], J[i], C[i]} of every row; row 0 is NEG.
+// Forward over a segment (SPEC 13.5): Forward with rows, and every lane leaves M and I of its nodes: word q (M) and Q + q (I) of lane l in row i lie at
+//   ((i - 1) 2 Q + q) 64 + l of pp, so a row is 2 Q bursts of 256 bytes, written here and read back by Backward in the same shape.
 // The specials come from a length of their own (Lsp): the record's for every program but the envelope scores, which run Forward over a stretch of a
 //   record under the whole record's length model.
 template <int Q> struct HmmLane {
@@ -160,7 +163,7 @@ template <int Q, HmmProg P>
 __device__ __forceinline__ int32_t hmm_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, uint32_t Lsp, uint32_t *pp, int4 *rr)
 {
     constexpr int MP = 64 * Q, NW = hmm_ptr_words(Q);
-    constexpr bool ROWS = P == HMM_FWD_ROWS, FWD = P == HMM_FWD || ROWS, TRACE = P == HMM_TRACE;
+    constexpr bool SEG = P == HMM_FWD_SEG, ROWS = P == HMM_FWD_ROWS || SEG, FWD = P == HMM_FWD || ROWS, TRACE = P == HMM_TRACE;
     constexpr int RELOAD_FROM_Q = P == HMM_VIT ? 20 : 12;     // from here the transition rows are read from LDS in every row (above)
     const uint16_t *T = ln.T;
     const int lane = ln.lane, nvalid = ln.nvalid;
@@ -238,6 +241,13 @@ __device__ __forceinline__ int32_t hmm_rows(const HmmLane<Q> ln, const uint8_t *
             const int32_t E = hmm_wave_join<P>(e, T);
             const uint32_t row = i0 + (uint32_t)t;            // row i = row + 1
             int kE = 0;
+            if constexpr (SEG) {
+#pragma unroll
+                for (int q = 0; q < Q; q++) {
+                    pp[((uint64_t)row * (2 * Q) + q) * 64] = (uint32_t)Mv[q];
+                    pp[((uint64_t)row * (2 * Q) + Q + q) * 64] = (uint32_t)Iv[q];
+                }
+            }
             if constexpr (TRACE) {
 #pragma unroll
                 for (int w = 0; w < NW; w++) pp[((uint64_t)row * NW + w) * 64] = pk[w];
@@ -585,13 +595,23 @@ enum { HMM_ENV_BLOCK = 64, HMM_ENV_LO = -156, HMM_ENV_HI = -425 };
 // paid for in tails: at 2^23 the 4 000 x 120 shape of DESIGN 3.24 ran 18 blocks and Forward with rows took 2.5 times the seconds of k_hmm_forward.
 static constexpr uint64_t HMM_ENV_DEFAULT_BLOCK_ROWS = 1ull << 25;
 
-template <int Q>
-__device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, int2 *rr)
+// With N2 (SPEC 13.5) the rows are those of a segment: L of them under the length model of Lsp residues, bC from the segment's rows. No row is kept;
+// at every row i >= 1 the lane reads M and I of the kept Forward row (keep: the lane's column, in the layout hmm_rows<HMM_FWD_SEG> wrote) and the
+// specials of row i - 1 (fr) and advances the folds of fM + bM, fI + bI over its nodes and of the N, J and C emissions, which it hands back in occ.
+template <int Q> struct HmmOcc { int32_t m[Q], i[Q], x; };
+template <int Q, bool N2>
+__device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, uint32_t Lsp, int2 *rr, const int4 *fr, const int32_t *keep,
+                                                 HmmOcc<Q> *occ)
 {
     constexpr int MP = 64 * Q;
     const uint16_t *T = ln.T;
     const int lane = ln.lane, nvalid = ln.nvalid;
-    const HmmSpecials sp = hmm_specials(L);
+    const HmmSpecials sp = hmm_specials(Lsp);
+    int32_t oM[N2 ? Q : 1], oI[N2 ? Q : 1], oX = GS_HMM_NEG;
+    if constexpr (N2) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) oM[q] = oI[q] = GS_HMM_NEG;
+    }
     const int32_t gsum = ln.PDD[Q - 1] + ln.tDD[Q - 1];       // the group's sum of tDD
     int32_t a_dn[6];                                          // a of the lanes a scan step joins: the sums of gsum over lanes l .. l + 2^s - 1
     {
@@ -618,6 +638,17 @@ __device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint
             nxt = at < L ? hmm_residue(x[L - 1 - at]) : 0;
         }
         if (Q >= 12) asm volatile("" ::: "memory");
+        // N2: the kept Forward row of this step is asked for here and read at the step's end, so that the row's own work covers the loads; the step
+        // of row 0 reads row 1 again and uses nothing of it
+        int32_t kM[N2 ? Q : 1], kI[N2 ? Q : 1];
+        int4 fp = make_int4(0, 0, 0, 0);
+        if constexpr (N2) {
+            const uint32_t row = s < L ? L - s - 1 : 0;
+            const int32_t *kr = keep + (uint64_t)row * (2 * Q * 64);
+#pragma unroll
+            for (int q = 0; q < Q; q++) { kM[q] = kr[q * 64]; kI[q] = kr[(Q + q) * 64]; }
+            fp = fr[row];
+        }
         const int32_t *ms = ln.ms + (s ? __builtin_amdgcn_readlane(res, (int)(j & 63u)) : 0) * MP;
         const int nv = s ? nvalid : 0;
         int32_t take[Q], e = GS_HMM_NEG;
@@ -633,7 +664,7 @@ __device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint
             bN = max(hmm_lse(bN + sp.tloop, bB + sp.tmove, T), GS_HMM_NEG);
         }
         const int32_t bE = hmm_lse(bJ + GS_HMM_TEJ, bC + GS_HMM_TEJ, T);
-        if (lane == 0) rr[L - s] = make_int2(bN, bJ);
+        if constexpr (!N2) if (lane == 0) rr[L - s] = make_int2(bN, bJ);
         int32_t dn = __shfl_down(take[0], 1);
         if (lane == 63) dn = GS_HMM_NEG;
         int32_t Dv[Q], dl = GS_HMM_NEG;
@@ -661,8 +692,79 @@ __device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint
             Iv[q] = max(hmm_lse(tk + ln.tIM[q], Iv[q] + ln.tII[q], T), GS_HMM_NEG);
             Mv[q] = max(m, GS_HMM_NEG);
         }
+        if constexpr (N2) if (s < L) {                        // rows L .. 1, in this order (SPEC 13.5)
+            const uint32_t i = L - s;
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                oM[q] = hmm_lse(oM[q], kM[q] + Mv[q], T);
+                oI[q] = hmm_lse(oI[q], kI[q] + Iv[q], T);
+            }
+            oX = hmm_lse(oX, hmm_lse(hmm_lse((int32_t)i * sp.tloop + bN, fp.y + sp.tloop + bJ, T), fp.z + sp.tloop + bC, T), T);
+        }
+    }
+    if constexpr (N2) {
+#pragma unroll
+        for (int q = 0; q < Q; q++) { occ->m[q] = oM[q]; occ->i[q] = oI[q]; }
+        occ->x = oX;
     }
     return __any(bad) ? GS_HMM_NO_SCORE : bN - sp.null;
+}
+
+// The end of a segment's Backward (SPEC 13.5): the folds become log2 of expected usage (minus total, floor NEG), 22 joins over the wavefront give ii, the
+// mass word and n2[a] of the 20 residues (lane a keeps n2[a]), and corr is the exact 64-bit sum of n2[x_i] over the segment, lanes striding its residues.
+// slot: {corr, dom_bias, seg_raw, mass}, of which seg_raw is Forward's; n2_out, occm, occi: optional (occm and occi together).
+enum { HMM_N2_OMEGA = -8192, HMM_N2_CORR_MAX = 1 << 30, HMM_N2_DEFAULT_BLOCK_CELLS = 1 << 26 };
+template <int Q>
+__device__ __forceinline__ void hmm_n2_finish(const HmmLane<Q> ln, const HmmOcc<Q> &o, int32_t total, const uint8_t *x, uint32_t Ld, uint32_t M, int32_t *slot,
+                                              int32_t *n2_out, int32_t *occm, int32_t *occi)
+{
+    constexpr int MP = 64 * Q;
+    const uint16_t *T = ln.T;
+    const int lane = ln.lane, nvalid = ln.nvalid;
+    const int nvi = min(max((int)M - 1 - lane * Q, 0), Q);    // the lane's nodes k < M: I of node M and of padding nodes holds mass that no path carries
+    int32_t om[Q], oi[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+        om[q] = (int32_t)max((int64_t)o.m[q] - total, (int64_t)GS_HMM_NEG);
+        oi[q] = (int32_t)max((int64_t)o.i[q] - total, (int64_t)GS_HMM_NEG);
+    }
+    const int32_t ox = (int32_t)max((int64_t)o.x - total, (int64_t)GS_HMM_NEG);
+    int32_t e = GS_HMM_NEG;
+#pragma unroll
+    for (int q = 0; q < Q; q++) e = q < nvi ? hmm_lse(e, oi[q], T) : e;
+    const int32_t ii = hmm_wave_join<HMM_FWD>(e, T);
+    e = GS_HMM_NEG;
+#pragma unroll
+    for (int q = 0; q < Q; q++) e = q < nvalid ? hmm_lse(e, om[q], T) : e;
+    const int32_t lgd = hmm_units_log(Ld, 1);
+    const int32_t mass = hmm_lse(hmm_lse(hmm_wave_join<HMM_FWD>(e, T), ii, T), ox, T) - lgd;
+    int32_t mine = 0;
+#pragma unroll 1
+    for (int a = 0; a < 20; a++) {
+        const int32_t *ms = ln.ms + a * MP;
+        e = GS_HMM_NEG;
+#pragma unroll
+        for (int q = 0; q < Q; q++) e = q < nvalid ? hmm_lse(e, om[q] + ms[q], T) : e;
+        const int32_t v = hmm_lse(hmm_lse(hmm_wave_join<HMM_FWD>(e, T), ii, T), ox, T) - lgd;
+        if (lane == a) mine = v;
+    }
+    int64_t sum = 0;
+    for (uint32_t i0 = 0; i0 < Ld; i0 += 64) {                // every lane takes every trip: the shuffle reads lanes 0 .. 19
+        const uint32_t i = i0 + (uint32_t)lane;
+        const int r = i < Ld ? max(hmm_residue(x[i]), 0) : 0;
+        const int32_t v = __shfl(mine, r);
+        sum += i < Ld ? v : 0;
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) sum += __shfl_xor(sum, d);
+    const int32_t corr = (int32_t)min(max(sum, -(int64_t)HMM_N2_CORR_MAX), (int64_t)HMM_N2_CORR_MAX);
+    if (lane == 0) { slot[0] = corr; slot[1] = hmm_lse(0, HMM_N2_OMEGA + corr, T); slot[3] = mass; }
+    if (n2_out && lane < 20) n2_out[lane] = mine;
+    if (occm) {
+#pragma unroll
+        for (int q = 0; q < Q; q++)
+            if (q < nvalid) { occm[lane * Q + q] = om[q]; occi[lane * Q + q] = q < nvi ? oi[q] : GS_HMM_NEG; }
+    }
 }
 
 // Forward score and the rows {E[i], J[i], C[i]} of the pairs of each profile of profs[]; 1 <= L <= GS_HMM_FWD_MAX_L: the host put no other pair on a list
@@ -694,7 +796,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_backward(const int32_t *__res
     const HmmLane<Q> ln = hmm_stage<Q, true>(tables, desc[tp.prof], lse_tab);
     for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
         const HmmTracePair pr = pairs[tp.start + j];
-        const int32_t raw = hmm_back_rows<Q>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], rows + pr.row_off);
+        const int32_t raw = hmm_back_rows<Q, false>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], (uint32_t)rec_len[pr.rec], rows + pr.row_off, nullptr, nullptr, nullptr);
         if (ln.lane == 0) bck_out[pr.pair] = raw;
     }
 }
@@ -787,23 +889,118 @@ __global__ __launch_bounds__(256) void k_hmm_env_fill(uint64_t n_pairs, uint64_t
     if (i < n_env_words) env[i] = 0;
 }
 
+// ---- null2 (SPEC 13.5): the bias correction of envelope and sequence scores --------------------------------------------------------------------------
+// The unit of work is a listed envelope (a slot of its pair), one wavefront each. The blocks' lists are the trace's with a slot in the place of a pair:
+// HmmTracePair::pair numbers the call's slots (HmmN2Slot), ptr_off is where the slot's kept M and I words start (2 * 64 Q * Ld of them), row_off where its
+// Ld + 1 Forward rows {E, J, C, 0} start.
+struct HmmN2Slot { uint64_t occ_at; uint32_t pair, e, rec, from, Ld, pad; };          // occ_at: the first word of the slot's occM / occI row
+struct HmmN2Pair { uint32_t rec, listed; };                                           // listed = min(n_env, max_env)
+
+// per pair of the call: 1 iff it has a record of at least one residue and every byte of it is a residue
+__global__ __launch_bounds__(64) void k_hmm_n2_flag(const HmmN2Pair *__restrict__ np, const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start,
+                                                    const uint64_t *__restrict__ rec_len, uint32_t *__restrict__ ok)
+{
+    const uint32_t rec = np[blockIdx.x].rec;
+    bool bad = rec == GS_HMM_NO_HIT;
+    if (!bad) {
+        const uint64_t L = rec_len[rec];
+        const uint8_t *x = aa + rec_start[rec];
+        bad = L == 0;
+        for (uint64_t i = threadIdx.x; i < L; i += 64) bad |= hmm_residue(x[i]) < 0;
+    }
+    const bool any_bad = __any(bad);
+    if (threadIdx.x == 0) ok[blockIdx.x] = any_bad ? 0u : 1u;
+}
+
+// zeros in every output a pair may go without
+__global__ __launch_bounds__(256) void k_hmm_n2_fill(uint64_t n_slot_words, uint64_t n_pairs, uint64_t n_n2_words, int32_t *__restrict__ slot, int32_t *__restrict__ seq,
+                                                     int32_t *__restrict__ n2)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_slot_words) slot[i] = 0;
+    if (i < n_pairs) seq[i] = 0;
+    if (n2 && i < n_n2_words) n2[i] = 0;
+}
+
+// Forward over the slots of each profile of profs[], M and I of every row kept; writes seg_raw
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_n2_forward(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                              const HmmTracePair *__restrict__ pairs, const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa,
+                                                              const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                              const HmmN2Slot *__restrict__ slots, const uint32_t *__restrict__ ok, uint32_t max_env, int4 *rows,
+                                                              uint32_t *keep, int32_t *slot_out)
+{
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmLane<Q> ln = hmm_stage<Q, true>(tables, desc[tp.prof], lse_tab);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const HmmN2Slot sl = slots[pr.pair];
+        if (!ok[sl.pair]) continue;
+        const uint32_t L = (uint32_t)rec_len[sl.rec];
+        const int32_t raw = hmm_rows<Q, HMM_FWD_SEG>(ln, aa + rec_start[sl.rec] + (sl.from - 1), sl.Ld, L, keep + pr.ptr_off + ln.lane, rows + pr.row_off);
+        if (ln.lane == 0) slot_out[((uint64_t)sl.pair * max_env + sl.e) * GS_HMM_N2_WORDS + 2] = raw + (int32_t)(L - sl.Ld) * hmm_specials(L).tloop;
+    }
+}
+
+// Backward over the same slots with the folds of SPEC 13.5 beside the row, then n2, mass and corr
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_n2_backward(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                               const HmmTracePair *__restrict__ pairs, const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa,
+                                                               const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                               const HmmN2Slot *__restrict__ slots, const uint32_t *__restrict__ ok, uint32_t max_env,
+                                                               const int4 *__restrict__ rows, const uint32_t *__restrict__ keep, int32_t *slot_out, int32_t *n2_out,
+                                                               int32_t *occm_out, int32_t *occi_out)
+{
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmDesc d = desc[tp.prof];
+    const HmmLane<Q> ln = hmm_stage<Q, true>(tables, d, lse_tab);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const HmmN2Slot sl = slots[pr.pair];
+        if (!ok[sl.pair]) continue;
+        const uint32_t L = (uint32_t)rec_len[sl.rec];
+        const uint8_t *x = aa + rec_start[sl.rec] + (sl.from - 1);
+        const int4 *fr = rows + pr.row_off;
+        HmmOcc<Q> occ;
+        (void)hmm_back_rows<Q, true>(ln, x, sl.Ld, L, nullptr, fr, (const int32_t *)keep + pr.ptr_off + ln.lane, &occ);
+        const uint64_t at = (uint64_t)sl.pair * max_env + sl.e;
+        hmm_n2_finish<Q>(ln, occ, fr[sl.Ld].z + hmm_specials(L).tmove, x, sl.Ld, d.M, slot_out + at * GS_HMM_N2_WORDS, n2_out ? n2_out + at * 20 : nullptr,
+                         occm_out ? occm_out + sl.occ_at : nullptr, occm_out ? occi_out + sl.occ_at : nullptr);
+    }
+}
+
+// seq_bias of every pair that has a score: lse(0, OMEGA + the clamped sum of corr over its listed slots)
+__global__ __launch_bounds__(256) void k_hmm_n2_seq(const HmmN2Pair *__restrict__ np, const uint32_t *__restrict__ ok, uint64_t n_pairs, uint32_t max_env,
+                                                    const uint16_t *__restrict__ T, const int32_t *__restrict__ slot, int32_t *__restrict__ seq)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n_pairs || !ok[j]) return;
+    int64_t sum = 0;
+    for (uint32_t e = 0; e < np[j].listed; e++) sum += slot[(j * max_env + e) * GS_HMM_N2_WORDS];
+    const int32_t corr = (int32_t)min(max(sum, -(int64_t)HMM_N2_CORR_MAX), (int64_t)HMM_N2_CORR_MAX);
+    seq[j] = hmm_lse(0, HMM_N2_OMEGA + corr, T);
+}
+
 // the instances of a class, from the one class list
 struct HmmKernels {
     decltype(&k_hmm_viterbi<1>) vit; decltype(&k_hmm_forward<1>) fwd; decltype(&k_hmm_trace<1>) trace; decltype(&k_hmm_msv<1>) msv; decltype(&k_hmm_viterbi_sel<1>) vit_sel;
     decltype(&k_hmm_forward_rows<1>) fwd_rows; decltype(&k_hmm_backward<1>) back; decltype(&k_hmm_env_score<1>) env_score;
+    decltype(&k_hmm_n2_forward<1>) n2_fwd; decltype(&k_hmm_n2_backward<1>) n2_back;
 };
 template <size_t... I> static const HmmKernels &hmm_kernels(int cls, std::index_sequence<I...>)
 {
     static const HmmKernels of_class[] = {{k_hmm_viterbi<HMM_CLASS_Q[I]>, k_hmm_forward<HMM_CLASS_Q[I]>, k_hmm_trace<HMM_CLASS_Q[I]>, k_hmm_msv<HMM_CLASS_Q[I]>,
                                            k_hmm_viterbi_sel<HMM_CLASS_Q[I]>, k_hmm_forward_rows<HMM_CLASS_Q[I]>, k_hmm_backward<HMM_CLASS_Q[I]>,
-                                           k_hmm_env_score<HMM_CLASS_Q[I]>}...};
+                                           k_hmm_env_score<HMM_CLASS_Q[I]>, k_hmm_n2_forward<HMM_CLASS_Q[I]>, k_hmm_n2_backward<HMM_CLASS_Q[I]>}...};
     return of_class[cls];
 }
 static const HmmKernels &hmm_kernels(int cls) { return hmm_kernels(cls, std::make_index_sequence<HMM_CLASSES>()); }
 static size_t hmm_lds_bytes(int cls, HmmProg prog) { return (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + (prog == HMM_FWD || prog == HMM_FWD_ROWS ? HMM_LSE_LDS_BYTES : 0); }
 static size_t hmm_msv_lds_bytes(int cls) { return (size_t)HMM_MSV_ROWS * 64 * HMM_CLASS_Q[cls] * 4; }
 // which kernel a (kernel, class) flag of the profile set belongs to: the three programs of hmm_rows, then MSV and Viterbi over a selected list
-enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_K_BACK, HMM_K_ENV_SCORE, HMM_KERNEL_KINDS };
+enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_K_BACK, HMM_K_ENV_SCORE, HMM_K_N2_BACK, HMM_KERNEL_KINDS };
 
 }  // namespace gs
 
@@ -1274,6 +1471,102 @@ static int hmm_env_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, const HmmPai
         });
 }
 
+// What gs_hmm_null2 refuses of the envelopes it is given, decided on host copies before any output is touched. A pair without a record or with an empty
+// one lists nothing and its words are not read. oo: occ_off or nullptr - the rows of a pair's listed slots, M words each, must fit between its offset
+// and the next.
+static int hmm_null2_check(const gs_hmm_db *db, const uint64_t *lens, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs, uint32_t max_env, const uint32_t *n_env,
+                           const int32_t *env, const uint64_t *oo)
+{
+    for (uint64_t j = 0; j < n_pairs; j++) {
+        GS_REQUIRE(!oo || oo[j] <= oo[j + 1], GS_ERR_INVALID, "hmm: occ_off decreases at pair %llu", (unsigned long long)j);
+        if (prec[j] == GS_HMM_NO_HIT || lens[prec[j]] == 0) continue;
+        const uint64_t L = lens[prec[j]], listed = std::min<uint64_t>(n_env[j], max_env);
+        for (uint64_t e = 0; e < listed; e++) {
+            const int64_t a = env[(j * max_env + e) * GS_HMM_ENV_WORDS], b = env[(j * max_env + e) * GS_HMM_ENV_WORDS + 1];
+            GS_REQUIRE(a >= 1 && a <= b && (uint64_t)b <= L, GS_ERR_INVALID, "hmm: envelope %llu of pair %llu is %lld .. %lld on a record of %llu residues",
+                       (unsigned long long)e, (unsigned long long)j, (long long)a, (long long)b, (unsigned long long)L);
+        }
+        GS_REQUIRE(!oo || oo[j + 1] - oo[j] >= listed * db->desc[pprof[j]].M, GS_ERR_INVALID, "hmm: occ_off leaves pair %llu fewer words than its listed envelopes times M",
+                   (unsigned long long)j);
+    }
+    return GS_OK;
+}
+
+// R, P: the records and pairs of the call, which hmm_pair_check has passed under Forward's length limit; n_env, env, oo: host copies that hmm_null2_check has
+// passed; everything else device memory. The listed envelopes are cut into blocks of at most max_block_cells cells (sum of 64 Q * Ld; two kept words a
+// cell); a block is a Forward and a Backward launch per class that occurs. The sequence biases follow the last block.
+static int hmm_null2_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, const HmmPairs &P, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env,
+                          const uint64_t *oo, int32_t *slot_dev, int32_t *seq_dev, int32_t *n2_dev, int32_t *occm_dev, int32_t *occi_dev)
+{
+    const uint64_t n_pairs = P.n, n_slot_words = n_pairs * max_env * GS_HMM_N2_WORDS, n_n2_words = n2_dev ? n_pairs * max_env * 20 : 0,
+                   n_fill = std::max(std::max(n_pairs, n_slot_words), n_n2_words);
+    GS_REQUIRE(n_fill < (1ull << 31) * 256 && n_pairs * max_env < (1ull << 32) && n_pairs < (1ull << 31), GS_ERR_UNSUPPORTED, "hmm: too many envelope slots");
+    std::vector<HmmN2Pair> np(n_pairs);
+    std::vector<HmmN2Slot> slots;
+    std::vector<uint64_t> slot_len;                               // Ld of every slot: the `lens` of the block builder, whose records are the slots
+    std::vector<uint32_t> slot_id, slot_prof;
+    for (uint64_t j = 0; j < n_pairs; j++) {
+        const bool has = P.rec[j] != GS_HMM_NO_HIT && R.lens[P.rec[j]] != 0;
+        np[j] = HmmN2Pair{P.rec[j], has ? std::min(n_env[j], max_env) : 0u};
+        for (uint32_t e = 0; e < np[j].listed; e++) {
+            const int32_t *w = env + (j * max_env + e) * GS_HMM_ENV_WORDS;
+            slot_id.push_back((uint32_t)slots.size()); slot_prof.push_back(P.prof[j]); slot_len.push_back((uint64_t)(w[1] - w[0] + 1));
+            slots.push_back(HmmN2Slot{oo ? oo[j] + (uint64_t)e * db->desc[P.prof[j]].M : 0, (uint32_t)j, e, P.rec[j], (uint32_t)w[0], (uint32_t)(w[1] - w[0] + 1), 0});
+        }
+    }
+    auto cells = [&](uint64_t i) { return slot_len[i] * 64 * HMM_CLASS_Q[hmm_class_of(db->desc[slot_prof[i]].M)]; };
+    HmmPairBlocks pb = hmm_pair_blocks(db, slot_len.data(), slot_id.data(), slot_prof.data(), slots.size(), max_block_cells ? max_block_cells : HMM_N2_DEFAULT_BLOCK_CELLS, cells);
+    uint64_t max_keep = 0;                                        // the kept words of the largest block; ptr_off: where a slot's start
+    for (const HmmPairBlock &b : pb.blocks) {
+        uint64_t at = 0;
+        for (uint32_t t = b.start; t < b.start + b.n; t++) { pb.tp[t].ptr_off = at; at += 2 * cells(pb.tp[t].pair); }
+        max_keep = std::max(max_keep, at);
+    }
+    PoolBuf d_np(c, SL_HMMN_PAIRS), d_slots(c, SL_HMMN_SLOTS), d_ok(c, SL_HMMN_OK), d_keep(c, SL_HMMN_KEEP), d_rows(c, SL_HMME_FROWS);
+    int rc;
+    if ((rc = d_np.alloc(sizeof(HmmN2Pair) * n_pairs)) || (rc = d_slots.alloc(sizeof(HmmN2Slot) * slots.size())) || (rc = d_ok.alloc(4 * n_pairs))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(d_np.p, np.data(), sizeof(HmmN2Pair) * n_pairs, hipMemcpyHostToDevice, c->stream));
+    if (!slots.empty()) GS_HIP_CHECK(hipMemcpyAsync(d_slots.p, slots.data(), sizeof(HmmN2Slot) * slots.size(), hipMemcpyHostToDevice, c->stream));
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_n2_fill<<<(unsigned)((n_fill + 255) / 256), 256, 0, c->stream>>>(n_slot_words, n_pairs, n_n2_words, slot_dev, seq_dev, n2_dev);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_n2_flag<<<(unsigned)n_pairs, 64, 0, c->stream>>>(d_np.as<HmmN2Pair>(), R.aa, R.rs, R.rl, d_ok.as<uint32_t>());
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    const int32_t *tables = db->d_tables.as<int32_t>();
+    const HmmDesc *desc = db->d_desc.as<HmmDesc>();
+    const uint16_t *lse = db->d_lse.as<uint16_t>();
+    rc = hmm_run_blocks(
+        c, pb, [&](const HmmPairBlocks &pb) { int rc = d_keep.alloc(4 * max_keep); return rc ? rc : d_rows.alloc(sizeof(int4) * pb.max_rows); },
+        [&](const HmmBlockLists &d, const HmmPairBlock &b, int cls, uint32_t wg) -> int {
+            const auto kf = hmm_kernels(cls).n2_fwd;
+            const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+            int rc = hmm_block_launch(c, db, HMM_FWD_SEG, kf, lds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                kf<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, tprof, d.tp, lse, R.aa, R.rs, R.rl, d_slots.as<HmmN2Slot>(), d_ok.as<uint32_t>(), max_env, d_rows.as<int4>(),
+                                                        d_keep.as<uint32_t>(), slot_dev);
+            });
+            if (rc) return rc;
+            const auto kb = hmm_kernels(cls).n2_back;
+            return hmm_block_launch(c, db, HMM_K_N2_BACK, kb, lds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                kb<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, tprof, d.tp, lse, R.aa, R.rs, R.rl, d_slots.as<HmmN2Slot>(), d_ok.as<uint32_t>(), max_env, d_rows.as<int4>(),
+                                                        d_keep.as<uint32_t>(), slot_dev, n2_dev, occm_dev, occi_dev);
+            });
+        },
+        [&](const HmmBlockLists &, const HmmPairBlock &) -> int { return GS_OK; });
+    if (rc) return rc;
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_n2_seq<<<(unsigned)((n_pairs + 255) / 256), 256, 0, c->stream>>>(d_np.as<HmmN2Pair>(), d_ok.as<uint32_t>(), n_pairs, max_env, lse, slot_dev, seq_dev);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    GS_HIP_CHECK(stream_wait(c));
+    return GS_OK;
+}
+
 // ---- the bodies of the ABI pairs: in.host says which entry called -----------------------------------------------------------------------------------
 // The four pairs that score every (record, profile) pair: gs_hmm_search (Viterbi), gs_hmm_search_msv (MSV; SPEC 13.3), gs_hmm_search_forward (Viterbi,
 // then Forward for the pairs at or above vit_floor; SPEC 13.1) and gs_hmm_search_filtered (MSV, Viterbi at or above msv_floor and, with fwd_out, Forward
@@ -1356,9 +1649,63 @@ static int hmm_env_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, const uint32_
     return in.host ? hmm_fetch(c, {&fwd, &bck, &ne, &env, &out, &cont}) : GS_OK;        // (hmm_env_impl has waited)
 }
 
+// gs_hmm_null2{,_dev}. n_env and env come as gs_hmm_envelopes wrote them; a _dev form fetches them, and occ_off, once. A host form uploads occm and occi too:
+// the rows of a pair that gets none keep what the caller's arrays hold.
+static int hmm_null2_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, const uint32_t *pair_rec, const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env,
+                          uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env, int32_t *slot_out, int32_t *seq_out, int32_t *n2_out, const uint64_t *occ_off,
+                          int32_t *occm_out, int32_t *occi_out)
+{
+    HmmLock lock;
+    HmmRecs R(c); HmmPairs P(c);
+    HmmArg slot(c, SL_HMMB_PAIR_ITEMS), seq(c, SL_HMMB_PAIR_SCORE), n2(c, SL_HMMB_PAIR_N2), om(c, SL_HMMB_OUT_ROWS), oi(c, SL_HMMB_CONT_ROWS);
+    std::vector<uint64_t> no_rows, h_oo;
+    std::vector<uint32_t> h_nenv;
+    std::vector<int32_t> h_env;
+    int rc = hmm_pair_args(c, db, in, pair_rec, pair_prof, n_pairs, seq_out && n_env && (max_env == 0 || (env && slot_out)), !occ_off == !occm_out && !occ_off == !occi_out,
+                           GS_HMM_FWD_MAX_L, false, nullptr, no_rows, lock, R, P);
+    if (rc) return rc == HMM_NOTHING_TO_DO ? GS_OK : rc;
+    const uint64_t n_env_words = n_pairs * max_env * GS_HMM_ENV_WORDS;
+    if (!in.host) {
+        h_nenv.resize(n_pairs); h_env.resize(n_env_words);
+        GS_HIP_CHECK(hipMemcpyAsync(h_nenv.data(), n_env, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+        if (n_env_words) GS_HIP_CHECK(hipMemcpyAsync(h_env.data(), env, 4 * n_env_words, hipMemcpyDeviceToHost, c->stream));
+        if (occ_off) {
+            h_oo.resize(n_pairs + 1);
+            GS_HIP_CHECK(hipMemcpyAsync(h_oo.data(), occ_off, 8 * (n_pairs + 1), hipMemcpyDeviceToHost, c->stream));
+        }
+        GS_HIP_CHECK(stream_wait(c));
+        n_env = h_nenv.data(); env = h_env.data();
+    }
+    const uint64_t *oo = !occ_off ? nullptr : in.host ? occ_off : h_oo.data();
+    if ((rc = hmm_null2_check(db, R.lens, P.rec, P.prof, n_pairs, max_env, n_env, env, oo))) return rc;
+    const uint64_t n_row_bytes = in.host && oo ? 4 * oo[n_pairs] : 0;
+    if ((rc = slot.bind(in.host, slot_out, 4 * n_pairs * max_env * GS_HMM_N2_WORDS, HMM_DOWN)) || (rc = seq.bind(in.host, seq_out, 4 * n_pairs, HMM_DOWN)) ||
+        (n2_out && (rc = n2.bind(in.host, n2_out, 4 * n_pairs * max_env * 20, HMM_DOWN))))
+        return rc;
+    if (oo && ((rc = om.bind(in.host, occm_out, n_row_bytes, HMM_UP | HMM_DOWN)) || (rc = oi.bind(in.host, occi_out, n_row_bytes, HMM_UP | HMM_DOWN)))) return rc;
+    if ((rc = hmm_null2_impl(c, db, R, P, max_env, max_block_cells, n_env, env, oo, slot.as<int32_t>(), seq.as<int32_t>(), n2.as<int32_t>(), om.as<int32_t>(), oi.as<int32_t>())))
+        return rc;
+    return in.host ? hmm_fetch(c, {&slot, &seq, &n2, &om, &oi}) : GS_OK;          // (hmm_null2_impl has waited)
+}
+
 }  // namespace gs
 
 extern "C" {
+
+int gs_hmm_null2_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, const uint32_t *pair_rec_dev,
+                     const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env_dev, const int32_t *env_dev,
+                     int32_t *slot_out_dev, int32_t *seq_bias_out_dev, int32_t *n2_out_dev, const uint64_t *occ_off_dev, int32_t *occm_out_dev, int32_t *occi_out_dev)
+{
+    return gs::hmm_null2_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, pair_rec_dev, pair_prof_dev, n_pairs, max_env, max_block_cells, n_env_dev, env_dev,
+                              slot_out_dev, seq_bias_out_dev, n2_out_dev, occ_off_dev, occm_out_dev, occi_out_dev);
+}
+int gs_hmm_null2(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                 const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env, int32_t *slot_out,
+                 int32_t *seq_bias_out, int32_t *n2_out, const uint64_t *occ_off, int32_t *occm_out, int32_t *occi_out)
+{
+    return gs::hmm_null2_form(c, db, {true, aa, rec_start, rec_len, n_rec}, pair_rec, pair_prof, n_pairs, max_env, max_block_cells, n_env, env, slot_out, seq_bias_out, n2_out,
+                              occ_off, occm_out, occi_out);
+}
 
 int gs_hmm_db_load_mem(gs_ctx *c, const void *const *texts, const uint64_t *n_bytes, uint64_t n_texts, gs_hmm_db **out)
 {

@@ -389,7 +389,7 @@ int gs_hmm_trace_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const ui
  * out[i] <= -156 (occupancy >= 0.10); a run is a maximal stretch of in-rows in which every row but the last has cont[i] <= -156; a run is an envelope
  * iff some row of it has out[i] <= -425 (occupancy >= 0.25). An envelope is GS_HMM_ENV_WORDS int32: i_from, i_to (1-based, inclusive), env_raw = the
  * Forward raw score of the rows i_from .. i_to alone under the length model of the whole record, peak = the smallest out[i] of the envelope.
- * No stochastic clustering (a run is one envelope), no null2, no alignment. Pairs in any order, repeats allowed.
+ * No stochastic clustering (a run is one envelope), no alignment; env_raw is uncorrected (the null2 correction is gs_hmm_null2). Pairs in any order, repeats allowed.
  * fwd_out[j] = what gs_hmm_search_forward writes for pair j; bck_out[j] = bN[0] - null, the same probability summed from the other end (it differs
  * from fwd_out[j] by rounding alone); n_env_out[j] = the true number of envelopes; env_out[j][0 .. min(n_env, max_env)) = the first envelopes in
  * sequence order, the other slots of the pair zeros (max_env = 0 with env_out = NULL is allowed). row_off (n_pairs + 1 words, optional, with out_rows
@@ -408,6 +408,32 @@ int gs_hmm_envelopes_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, cons
                          const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_rows,
                          int32_t *fwd_out_dev, int32_t *bck_out_dev, uint32_t *n_env_out_dev, int32_t *env_out_dev, const uint64_t *row_off_dev,
                          int32_t *out_rows_dev, int32_t *cont_rows_dev);
+
+/* null2 bias correction (SPEC 13.5): what a model of the segment's own composition would have scored, taken off the envelope and sequence scores -
+ * HMMER3's null2 by expectation, restated in the integer units and lse of SPEC 13 / 13.1. Opt-in: no other call changes. For every listed envelope
+ * a .. b of a pair (a slot, Ld = b - a + 1) Forward and Backward run over x_a .. x_b under the length model of the whole record, both on the device;
+ * their products give the expected usage of every emitting state, from it the 20 log-odds n2[a] of the segment's null model, and
+ * corr = sum of n2[x_i] over the segment (64 bits, kept inside +-2^30), dom_bias = lse(0, -8192 + corr), seq_bias = lse(0, -8192 + the sum of corr over
+ * the pair's listed envelopes). Both biases are >= 0; the corrected scores are env_raw - dom_bias and fwd - seq_bias.
+ * Arguments and refusals are those of gs_hmm_envelopes; n_env and env are inputs, as that call wrote them for the same pairs and max_env. Envelope e
+ * of pair j is listed iff e < min(n_env[j], max_env): when n_env > max_env the sequence bias counts the listed envelopes only. An envelope with
+ * i_from > i_to or a bound outside 1 .. L: GS_ERR_INVALID, nothing written.
+ * slot_out[j][e] = GS_HMM_N2_WORDS int32: corr, dom_bias, seg_raw (== env_raw of the envelope, on the integers), mass (the summed usage over Ld, a
+ * check word: 0 in exact arithmetic); the other slots of the pair zeros. seq_bias_out[j]. n2_out (optional): [n_pairs][max_env][20]. occ_off
+ * (n_pairs + 1 words, optional, with occm_out and occi_out): the rows occM[1 .. M] and occI[1 .. M] (log2 of the expected number of residues M_k and
+ * I_k emit; occI[M] = GS_HMM_NEG) of slot e of pair j are written from word occ_off[j] + e * M on; occ_off[j + 1] - occ_off[j] >= min(n_env, max_env) *
+ * M, else GS_ERR_INVALID. A pair with pair_rec = GS_HMM_NO_HIT, an empty record or a record with a byte that is no residue: zeroed slots, seq_bias = 0,
+ * no rows. max_block_cells bounds the cells (sum of 64 Q * Ld over the slots of a block, 8 bytes each) whose Forward M and I are alive at once; 0 = 2^26;
+ * a block always holds at least one slot; no output depends on it. Device form: every array device memory; the lengths, the pair list, n_env, env and
+ * occ_off are read back once. */
+#define GS_HMM_N2_WORDS 4u
+int gs_hmm_null2(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                 const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env, int32_t *slot_out,
+                 int32_t *seq_bias_out, int32_t *n2_out, const uint64_t *occ_off, int32_t *occm_out, int32_t *occi_out);
+int gs_hmm_null2_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                     const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env_dev,
+                     const int32_t *env_dev, int32_t *slot_out_dev, int32_t *seq_bias_out_dev, int32_t *n2_out_dev, const uint64_t *occ_off_dev, int32_t *occm_out_dev,
+                     int32_t *occi_out_dev);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* orfs (SPEC 14): stop-to-stop six-frame translation of packed nucleotide records on the device - the model-free way to feed hmmsearch from genomes.

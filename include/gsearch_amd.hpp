@@ -312,6 +312,19 @@ public:
                                e.fwd.data(), e.bck.data(), e.n_env.data(), e.env.empty() ? nullptr : e.env.data(), nullptr, nullptr, nullptr));
         return e;
     }
+    // SPEC 13.5: the null2 bias of the envelopes envelopes() listed for the same pairs and max_env. slot[(j * max_env + d) * GS_HMM_N2_WORDS ..] = corr,
+    // dom_bias, seg_raw, mass; the corrected scores are env_raw - dom_bias and fwd[j] - seq_bias[j]
+    struct Null2 { std::vector<int32_t> slot, seq_bias; };
+    Null2 null2(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len, const std::vector<uint32_t> &pair_rec,
+                const std::vector<uint32_t> &pair_prof, const Envelopes &e, uint32_t max_env = 8, uint64_t max_block_cells = 0) const
+    {
+        const size_t n = pair_rec.size();
+        Null2 b{std::vector<int32_t>(n * max_env * GS_HMM_N2_WORDS), std::vector<int32_t>(n)};
+        check(gs_hmm_null2(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), pair_rec.data(), pair_prof.data(), n, max_env, max_block_cells,
+                           e.n_env.data(), e.env.empty() ? nullptr : e.env.data(), b.slot.empty() ? nullptr : b.slot.data(), b.seq_bias.data(), nullptr, nullptr, nullptr,
+                           nullptr));
+        return b;
+    }
     // the floor of profile p for a Viterbi P-value of filter_p (HMMER's F2 = 1e-3): INT32_MIN + 1 without STATS LOCAL VITERBI
     int32_t viterbi_floor(size_t profile, double filter_p = 1e-3) const
     {

@@ -39,11 +39,21 @@ With --posterior also (SPEC 13.4):
   check         fwd of every pair against the Forward matrix, |fwd - bck| against the bound of SPEC 13.4, and `check` sampled pairs (fwd, bck, n_env,
                 envelopes) against the restatement (tests/pyref_hmm_posterior.py): the expected differences are 0
 
+With --null2 also (SPEC 13.5):
+  envelopes     seconds of gs_hmm_envelopes_dev with max_env = 2 over the pairs whose Forward raw reaches the profile's GA (`ga`) and over ALL pairs
+                (`all`): the parent commit's code, the yardstick, alternating with null2 in the same rounds
+  null2         seconds of gs_hmm_null2_dev over the envelopes those calls listed - what the correction adds to gs_hmm_envelopes -, the listed slots and
+                their cells (sum of Ld x M of the slot's profile; the kernels run 64 Q columns a row, of which M are nodes). The split between
+                k_hmm_n2_forward and k_hmm_n2_backward comes from a kernel trace of one more run of this mode, kept beside the line in the log
+  check         seg_raw of every listed slot against env_raw, both biases >= 0, the largest |mass|, and `check` sampled pairs against the restatement
+                (tests/pyref_hmm_null2.py): the expected differences are 0
+
 --dump PATH saves the downloaded matrices of the modes that ran as one .npz (the Viterbi scores; both Forward matrices; raw, n_dom and the domain
 words of trace_best and trace_all), so that two builds of the library (GS_LIB_PATH) can be compared word for word.
 
-usage: hmm_rate.py [--forward | --trace | --posterior | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
-                   [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log | hmm_msv_rate.log | hmm_posterior_rate.log]"""
+usage: hmm_rate.py [--forward | --trace | --posterior | --null2 | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
+                   [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log | hmm_msv_rate.log | hmm_posterior_rate.log |
+                   hmm_null2_rate.log]"""
 import argparse
 import json
 import os
@@ -67,10 +77,13 @@ def main():
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--msv", action="store_true")
     ap.add_argument("--posterior", action="store_true")
+    ap.add_argument("--null2", action="store_true")
     ap.add_argument("--parent-s", type=float, default=None)
     ap.add_argument("--log", default=None)
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
+    if a.log is None and a.null2:
+        a.log = os.path.join(ROOT, "profiles", "hmm_null2_rate.log")
     if a.log is None:
         a.log = os.path.join(ROOT, "profiles", "hmm_forward_rate.log" if a.forward else ("hmm_trace_rate.log" if a.trace else ("hmm_msv_rate.log" if a.msv else ("hmm_posterior_rate.log" if a.posterior else "hmm_rate.log"))))
     import gsearch_amd as G
@@ -126,6 +139,8 @@ def main():
         msv_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng, dump)
     if a.posterior:
         posterior_part(a, ctx, db, texts, recs, ptrs, d_score, cells, res, rng, dump)
+    if a.null2:
+        null2_part(a, ctx, db, texts, recs, ptrs, d_score, res, rng, dump)
     if a.dump:
         with open(a.dump, "wb") as f:
             np.savez(f, **dump)
@@ -230,6 +245,71 @@ def posterior_part(a, ctx, db, texts, recs, ptrs, d_vit, cells, res, rng, dump):
     res["posterior_check_pairs"], res["posterior_check_differences"] = a.check, diff
     for ptr in [d_pr, d_pp, d_fwd_all] + bufs:
         ctx.free(ptr)
+
+
+def null2_part(a, ctx, db, texts, recs, ptrs, d_vit, res, rng, dump):
+    import pyref_hmm as R
+    import pyref_hmm_null2 as N
+    n_prof, max_env = len(db), 2
+    M = np.array([int(m) for m in db.M], np.int64)
+    d_fwd_all = ctx.alloc(4 * a.n * n_prof)
+    db.search_forward_dev(ptrs[0], ptrs[1], ptrs[2], a.n, None, d_vit, d_fwd_all)
+    ctx.sync()
+    fwd_all = ctx.download(d_fwd_all, (a.n, n_prof), np.int32)
+    ctx.free(d_fwd_all)
+    thr = db.thresholds("ga").astype(np.int64)
+    ga = np.argwhere((fwd_all != R.NO_SCORE) & (fwd_all.astype(np.int64) >= thr[None, :]))
+    lists = {"ga": (ga[:, 0].astype(np.uint32), ga[:, 1].astype(np.uint32)),
+             "all": (np.repeat(np.arange(a.n, dtype=np.uint32), n_prof), np.tile(np.arange(n_prof, dtype=np.uint32), a.n))}
+
+    def timed(call):
+        ctx.sync()
+        t = time.perf_counter()
+        call()
+        ctx.sync()
+        return time.perf_counter() - t
+
+    for name, (pr, pp) in lists.items():
+        n = len(pr)
+        d_pr, d_pp = ctx.alloc(max(pr.nbytes, 16)), ctx.alloc(max(pp.nbytes, 16))
+        ctx.upload(d_pr, pr); ctx.upload(d_pp, pp)
+        e_bufs = [ctx.alloc(max(4 * n, 16)) for _ in range(3)] + [ctx.alloc(max(4 * n * max_env * 4, 16))]
+        n_bufs = [ctx.alloc(max(4 * n * max_env * 4, 16)), ctx.alloc(max(4 * n, 16))]
+        runs = {"envelopes": lambda: db.envelopes_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, d_pp, n, max_env, *e_bufs),
+                "null2": lambda: db.null2_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, d_pp, n, max_env, e_bufs[2], e_bufs[3], n_bufs[0], n_bufs[1])}
+        times = {k: [] for k in runs}
+        for it in range(a.repeat + 1):                           # the first round is the warm-up of both; the two alternate inside a round
+            for k, call in runs.items():
+                t = timed(call)
+                if it:
+                    times[k].append(t)
+        fwd = ctx.download(e_bufs[0], (n,), np.int32)
+        ne, env = ctx.download(e_bufs[2], (n,), np.uint32), ctx.download(e_bufs[3], (n, max_env, 4), np.int32)
+        slots, sb = ctx.download(n_bufs[0], (n, max_env, 4), np.int32), ctx.download(n_bufs[1], (n,), np.int32)
+        dump.update({"null2_%s_slots" % name: slots, "null2_%s_seq_bias" % name: sb})
+        listed = np.arange(max_env)[None, :] < np.minimum(ne, max_env)[:, None]
+        Ld = (env[:, :, 1] - env[:, :, 0] + 1).astype(np.int64) * listed
+        for k, ts in times.items():
+            res["%s_%s_times_s" % (k, name)] = ts
+            res["%s_%s_min_s" % (k, name)], res["%s_%s_median_s" % (k, name)] = min(ts), float(np.median(ts))
+        res["null2_%s_pairs" % name], res["null2_%s_slots" % name] = n, int(listed.sum())
+        res["null2_%s_rows" % name] = int(Ld.sum())
+        res["null2_%s_cells" % name] = int((Ld * M[pp][:, None]).sum())
+        res["null2_%s_over_envelopes" % name] = res["null2_%s_min_s" % name] / res["envelopes_%s_min_s" % name]
+        res["null2_%s_seg_raw_differs_from_env_raw" % name] = int((slots[:, :, 2] != env[:, :, 2])[listed].sum())
+        res["null2_%s_negative_biases" % name] = int((slots[:, :, 1] < 0).sum() + (sb < 0).sum())
+        res["null2_%s_largest_abs_mass" % name] = int(np.abs(slots[:, :, 3]).max()) if n else 0
+        res["null2_%s_pairs_below_ga_after_correction" % name] = int(((fwd.astype(np.int64) >= thr[pp]) & (fwd.astype(np.int64) - sb < thr[pp]) & (fwd != R.NO_SCORE)).sum())
+        if name == "ga":
+            res["null2_ga_largest_seq_bias_bits"] = float(sb.max() / 1024.0) if n else 0.0
+            diff = 0
+            for _ in range(a.check):
+                j = int(rng.integers(n))
+                want = N.null2_pairs([R.parse_hmm(texts[int(pp[j])])[0]], recs, [int(pr[j])], [0], ne[j:j + 1], env[j:j + 1], max_env)
+                diff += int(not (np.array_equal(slots[j], want[0][0]) and sb[j] == want[1][0]))
+            res["null2_check_pairs"], res["null2_check_differences"] = a.check, diff
+        for ptr in [d_pr, d_pp] + e_bufs + n_bufs:
+            ctx.free(ptr)
 
 
 def msv_part(a, ctx, db, texts, recs, ptrs, d_vit_all, vit_all, cells, res, rng, dump):
