@@ -104,11 +104,13 @@ GENE_STRAND, GENE_TYPE_SHIFT, GENE_TYPE_EDGE, GENE_OPEN3, GENE_HAS_START, GENE_C
 GENE_NO_START, GENE_TRAINED = 0xFFFFFFFFFFFFFFFF, 1
 
 HMM_MAX_M, HMM_MAX_L, HMM_NO_SCORE, HMM_NO_HIT, HMM_TABLE_ROWS = 1280, 1 << 18, -(1 << 31), 0xFFFFFFFF, 27
+HMM_AA = "ACDEFGHIKLMNPQRSTVWY"                     # the residues in the order of a table's 20 match rows (gs_hmm_parse_mem)
 HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
 HMM_FWD_MAX_L, HMM_LSE_N, HMM_FLOOR_ALL = 65536, 5903, -(1 << 31) + 1
 HMM_TRACE_MAX_L, HMM_DOM_WORDS = 65536, 8
 HMM_ENV_WORDS, HMM_ENV_LO, HMM_ENV_HI = 4, -156, -425
 HMM_N2_WORDS, HMM_N2_OMEGA = 4, -8192              # SPEC 13.5: corr, dom_bias, seg_raw, mass; 1024 log2(1 / 256)
+HMM_ALI_WORDS, HMM_ALI_MAX_LD, HMM_EXP2_N = 8, 8192, 1024      # SPEC 13.6: i_from, i_to, k_from, k_to, oa, n_match, n_ins, n_del
 
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
@@ -188,6 +190,7 @@ SYMBOLS = {
     "gs_hmm_db_free": (None, [_vp]),
     "gs_hmm_db_info": (_i, [_vp, C.POINTER(_u64), C.POINTER(HmmInfoC), _u64]),
     "gs_hmm_db_tables": (_i, [_vp, _u64, _vp, _u64]),
+    "gs_hmm_db_consensus": (_i, [_vp, _u64, _vp, _u64]),
     "gs_hmm_search_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "gs_hmm_search": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "gs_hmm_best_hits_dev": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp]),
@@ -209,6 +212,9 @@ SYMBOLS = {
     "gs_hmm_envelopes_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_hmm_null2": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_hmm_null2_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_exp2_table": (_i, [_vp, _u64]),
+    "gs_hmm_align": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_align_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
     # orfs (SPEC 14)
     "gs_orf_codon_table": (_i, [_u32, C.c_char_p]),
     "gs_orf_translate_dev": (_i, [_vp, C.POINTER(OrfParamsC), _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),

@@ -983,6 +983,13 @@ def hmm_logsum_table():
     return out
 
 
+def hmm_exp2_table():
+    """EXP2 of SPEC 13.6 as the library holds it: uint32 [1024], EXP2[f] = floor(65536 * 2^(-f / 1024) + 1/2); host only"""
+    out = np.zeros(_lib.HMM_EXP2_N, np.uint32)
+    check(_lib.load().gs_hmm_exp2_table(_p(out), out.size))
+    return out
+
+
 def hmm_parse_stats(text, model=0):
     """({msv mu, lambda, viterbi mu, lambda, forward tau, lambda} as float64 [6], has) of model number `model` of a HMMER3 text: has bit 0 / 1 / 2 =
     the STATS LOCAL MSV / VITERBI / FORWARD line was there; host only"""
@@ -1022,6 +1029,34 @@ def _pairs(pair_rec, pair_prof):
     if len(pr) != len(pp):
         raise ValueError("pair_rec and pair_prof: one entry per pair each")
     return pr, pp, (_opt(pr), _opt(pp), len(pr))
+
+
+def _ali_col_off(lens, n_env, env, M):
+    """col_off of gs_hmm_align: per pair room for Ld + M columns of every listed envelope; lens: the pair's record length (0: it names none), M: its
+    profile's nodes"""
+    max_env = env.shape[1]
+    listed = np.where(np.asarray(lens, dtype=np.int64) > 0, np.minimum(n_env, max_env), 0).astype(np.int64)
+    ld = np.maximum(env[:, :, 1].astype(np.int64) - env[:, :, 0] + 1, 0)                               # (a bad envelope is refused by the call)
+    ld[np.arange(max_env)[None, :] >= listed[:, None]] = 0
+    co = np.zeros(len(listed) + 1, np.uint64)
+    co[1:] = np.cumsum(ld.sum(axis=1) + listed * np.asarray(M, dtype=np.int64))
+    return co
+
+
+def _ali_columns(slots, cols, co, n_env, env, M):
+    """the column words of gs_hmm_align -> per pair the list of its aligned slots' (state, k, i, pp) int32 arrays"""
+    out = []
+    for j in range(len(slots)):
+        at, per = int(co[j]), []
+        for e in range(int(min(n_env[j], slots.shape[1]))):
+            if not slots[j, e, 5]:                                                         # (a path has a match cell; a pair that got nothing has no slots)
+                break
+            w = cols[at:at + int(slots[j, e, 5:8].sum())]
+            w0 = w[:, 0].astype(np.int64) & 0xFFFFFFFF
+            per.append(((w0 >> 28).astype(np.int32), ((w0 >> 16) & 0xFFF).astype(np.int32), ((w0 & 0xFFFF) + 1).astype(np.int32), w[:, 1].copy()))
+            at += int(env[j, e, 1]) - int(env[j, e, 0]) + 1 + int(M[j])
+        out.append(per)
+    return out
 
 
 def _all_items(run, k):
@@ -1109,6 +1144,12 @@ class HmmDb:
         tab = np.zeros((_lib.HMM_TABLE_ROWS, int(self.M[p]) + 1), np.int32)
         check(self.ctx.L.gs_hmm_db_tables(self.h, int(p), _p(tab), tab.size))
         return tab
+
+    def consensus(self, p):
+        """the consensus of profile p as bytes, a letter per node: the most probable residue of the node's match emission (SPEC 13; host only)"""
+        buf = C.create_string_buffer(int(self.M[p]))
+        check(self.ctx.L.gs_hmm_db_consensus(self.h, int(p), buf, len(buf)))
+        return buf.raw
 
     def search_packed(self, aa, rec_start, rec_len):
         """residues as filter_aa_records() returns them -> int32 [n_rec, n_prof] raw scores (units of 2^-10 bit; HMM_NO_SCORE for an empty record)"""
@@ -1317,6 +1358,53 @@ class HmmDb:
         fwd, _, ne, env = self.envelopes_all(aa, rec_start, rec_len, pair_rec, pair_prof)
         return (fwd, ne, env) + self.null2_packed(aa, rec_start, rec_len, pair_rec, pair_prof, ne, env)
 
+    def align_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, n_env, env, columns=False, max_block_cells=0):
+        """SPEC 13.6: the optimal-accuracy alignment of the envelopes envelopes_packed() listed for the same pairs (n_env, env as it returned them), all on
+        the device -> int32 slots [n_pairs, max_env, 8]: i_from, i_to (record coordinates, 1-based, inclusive), k_from, k_to, oa, n_match, n_ins, n_del of
+        each listed envelope, zeros behind them; the expected accuracy of a slot is oa / (65536 Ld). columns=True: followed by a list, per pair the list of
+        its listed slots' columns (state, k, i, pp): int32 arrays of one length, state 0 M / 1 I / 2 D, node k, record row i (1-based; for D the row it sits
+        in), pp = pM or pI of the cell in units (0 for D), in order from (i_from, k_from) to (i_to, k_to). A pair whose record is HMM_NO_HIT, empty or
+        holds a byte that is no residue: zeros and no columns. A listed envelope of more than HMM_ALI_MAX_LD residues is refused"""
+        (_, _, rl), recs = _recs(aa, rec_start, rec_len)
+        pr, pp, pairs = _pairs(pair_rec, pair_prof)
+        n = len(pr)
+        ne = np.ascontiguousarray(n_env, dtype=np.uint32).reshape(-1)
+        env = np.ascontiguousarray(env, dtype=np.int32)
+        if len(ne) != n or env.ndim != 3 or env.shape[0] != n or env.shape[2] != _lib.HMM_ENV_WORDS:
+            raise ValueError("n_env and env: as envelopes_packed() returns them for these pairs")
+        max_env = env.shape[1]
+        slots = np.zeros((n, max_env, _lib.HMM_ALI_WORDS), np.int32)
+        co = cols = None
+        if columns and n:
+            named = pr < len(rl)                                                    # (HMM_NO_HIT names no record; another bad index is refused below)
+            lens = np.zeros(n, np.int64)
+            lens[named] = rl[pr[named]]
+            M = np.where(pp < len(self), self.M[np.minimum(pp, len(self) - 1)], 0).astype(np.int64)       # (a bad profile index is refused below)
+            co = _ali_col_off(lens, ne, env, M)
+            cols = np.zeros((max(int(co[-1]), 1), 2), np.int32)
+        check(self.ctx.L.gs_hmm_align(self.ctx.h, self.h, *recs, *pairs, int(max_env), int(max_block_cells), _opt(ne), _opt(env), _opt(slots), _opt(co), _opt(cols)))
+        if not columns:
+            return slots
+        return slots, (_ali_columns(slots, cols, co, ne, env, M) if n else [])
+
+    def align(self, records, pairs, n_env, env, columns=False, max_block_cells=0):
+        """records as search() takes them; pairs: (record, profile) index pairs; n_env, env as envelopes() returned them -> what align_packed() returns"""
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        return self.align_packed(*filter_aa_records([bytes(r) for r in records]), pairs[:, 0].astype(np.uint32), pairs[:, 1].astype(np.uint32), n_env, env, columns=columns,
+                                 max_block_cells=max_block_cells)
+
+    def align_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, pair_rec_dev, pair_prof_dev, n_pairs, max_env, n_env_dev, env_dev, slot_out_dev, col_off_dev=None,
+                  col_out_dev=None, max_block_cells=0):
+        """all device memory; the lengths, the pair list, n_env, env and col_off are read back once"""
+        check(self.ctx.L.gs_hmm_align_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), pair_rec_dev, pair_prof_dev, int(n_pairs), int(max_env),
+                                          int(max_block_cells), n_env_dev, env_dev, slot_out_dev, col_off_dev, col_out_dev))
+
+    def align_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, columns=True):
+        """envelopes_all() and align_packed() behind it -> (fwd, n_env, env) + what align_packed() returns"""
+        fwd, _, ne, env = self.envelopes_all(aa, rec_start, rec_len, pair_rec, pair_prof)
+        got = self.align_packed(aa, rec_start, rec_len, pair_rec, pair_prof, ne, env, columns=columns)
+        return (fwd, ne, env) + (got if columns else (got,))
+
     def envelopes_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, pair_rec_dev, pair_prof_dev, n_pairs, max_env, fwd_out_dev, bck_out_dev, n_env_out_dev,
                       env_out_dev, row_off_dev=None, out_rows_dev=None, cont_rows_dev=None, max_block_rows=0):
         """all device memory; the lengths, the pair list and row_off are read back once"""
@@ -1383,8 +1471,45 @@ def _check_prefilter(prefilter):
         raise ValueError("prefilter: None or 'msv'")
 
 
+def _alignment_text(db, ids, listed, residues_of, n_env, env, slots, cols):
+    """the text of hmmsearch(alignments=), SPEC 13.6: per pair of `listed` and aligned envelope a tab-separated header line and the lines model, match,
+    target and PP, unwrapped. residues_of(r): the residues of target r"""
+    exp2 = hmm_exp2_table().astype(np.int64)
+    out = [b"# == target\tprofile\tacc\tenv\tn_env\tali_from\tali_to\thmm_from\thmm_to\tM\tacc\tn_match\tn_ins\tn_del\n"]
+    tabs = {}
+    for j, (r, p) in enumerate(listed):
+        if not cols[j]:
+            continue
+        inf = db.info[p]
+        if p not in tabs:
+            tabs[p] = (db.tables(p), db.consensus(p).decode("ascii").lower())
+        tab, cons = tabs[p]
+        rec = bytes(residues_of(r)).decode("ascii").upper()
+        for d, (st, k, i, pp) in enumerate(cols[j]):
+            s = [int(v) for v in slots[j, d]]
+            Ld = int(env[j, d, 1]) - int(env[j, d, 0]) + 1
+            out.append(("==\t%s\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.3f\t%d\t%d\t%d\n" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(n_env[j]), s[0], s[1], s[2], s[3],
+                                                                                          inf["M"], s[4] / (65536.0 * Ld), s[5], s[6], s[7])).encode())
+            nu = -pp.astype(np.int64)
+            dig = (10 * (exp2[nu & 1023] >> np.minimum(nu >> 10, 31)) + 32768) >> 16
+            model, match, target, ppl = [], [], [], []
+            for c in range(len(st)):
+                res = rec[int(i[c]) - 1]
+                if st[c] == 0:
+                    m = cons[int(k[c]) - 1]
+                    model.append(m); target.append(res)
+                    match.append(m if m.upper() == res else ("+" if int(tab[_lib.HMM_AA.index(res), int(k[c])]) > 0 else " "))
+                elif st[c] == 1:
+                    model.append("."); match.append(" "); target.append(res.lower())
+                else:
+                    model.append(cons[int(k[c]) - 1]); match.append(" "); target.append("-")
+                ppl.append("." if st[c] == 2 else ("*" if dig[c] >= 10 else str(int(dig[c]))))
+            out.append("".join("  %-6s %s\n" % (lab, "".join(t)) for lab, t in (("model", model), ("match", match), ("target", target), ("PP", ppl))).encode())
+    return b"".join(out)
+
+
 def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None, translate=False, min_aa=_lib.ORF_MIN_AA, table=11, prefilter=None,
-              msv_p=0.02, envelopes=None, bias=False):
+              msv_p=0.02, envelopes=None, bias=False, alignments=None):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
     `hmm` (a path, a directory, a list of paths or an HmmDb). Returns (ids, int32 [n_rec, n_prof] raw scores, table bytes) and writes the table to
     `output` when given. The table (a stated choice, SPEC 13): a header line, then `target profile acc bits evalue pass_ga` separated by tabs for every
@@ -1414,7 +1539,15 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     bias=True (SPEC 13.5; score="forward" only, ValueError otherwise): the pairs with a Forward raw >= 0 get their posterior envelopes and the null2 bias
     correction on the device. The table gains a last column `bias` (%.2f bits of seq_bias); bits, evalue and pass_ga are those of the corrected score
     fwd - seq_bias, and the rows are sorted by it. The envelope table gains a last column `env_bias` and its env_bits are env_raw - dom_bias. The returned
-    matrix stays the uncorrected one. bias=False: no correction, the tables of 13 / 13.1 / 13.4 byte for byte."""
+    matrix stays the uncorrected one. bias=False: no correction, the tables of 13 / 13.1 / 13.4 byte for byte.
+    alignments (a path; SPEC 13.6): every posterior envelope of the pairs the score table lists gets its optimal-accuracy alignment on the device, and
+    a text is written there, sorted like the envelope table - a legend line, then per envelope a line `== target profile acc env n_env ali_from ali_to
+    hmm_from hmm_to M acc n_match n_ins n_del` separated by tabs (acc %.3f of oa / (65536 Ld)) and four unwrapped lines: `model` (the consensus letter of
+    the node, lower case; `.` in an insert column), `match` (the letter where residue and consensus agree, `+` where the match score of the residue at
+    the node is above 0, else a blank), `target` (upper case on a match state, lower case on an insert state, `-` on a delete state) and `PP` (the digit
+    (10 w + 32768) >> 16 of the column's weight, `*` from 10; `.` under a delete column). It works with either score, with or without bias, and together
+    with domains and envelopes; its bytes are appended to the return value. An envelope of more than HMM_ALI_MAX_LD = 8192 residues is not aligned by this
+    library: the call then raises GsError (GS_ERR_UNSUPPORTED) and writes no alignment text, although records of up to 65 536 residues are searched."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
     if bias and score != "forward":
@@ -1424,7 +1557,7 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     fwd = score == "forward"
     dev = None
     if translate:
-        dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd or envelopes is not None, domains is not None), table)
+        dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd or envelopes is not None or alignments is not None, domains is not None), table)
         aa = rs = rl = None
         try:
             ids = dev.names()
@@ -1473,7 +1606,7 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     if output is not None:
         with open(output, "wb") as f:
             f.write(table)
-    if domains is None and envelopes is None:
+    if domains is None and envelopes is None and alignments is None:
         if dev is not None:
             dev.close()
         return ids, scores, table
@@ -1481,11 +1614,18 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     try:
         if domains is not None:
             _, nd, dom = dev.trace_all(db, pr, pp) if dev is not None else db.trace_all(aa, rs, rl, pr, pp)
-        if envelopes is not None and bias:                               # the candidates' envelopes, in the table's order
+        if (envelopes is not None or alignments is not None) and bias:  # the candidates' envelopes, in the table's order
             order = [slot_of[rp] for rp in listed]
             ne, env, slots = b_ne[order], b_env[order], b_slots[order]
-        elif envelopes is not None:
+        elif envelopes is not None or alignments is not None:
             _, _, ne, env = dev.envelopes_all(db, pr, pp) if dev is not None else db.envelopes_all(aa, rs, rl, pr, pp)
+        ali_text = None
+        if alignments is not None:                                       # every listed envelope aligned, over the envelopes found above
+            a_slots, a_cols = dev.align_listed(db, pr, pp, ne, env) if dev is not None else db.align_packed(aa, rs, rl, pr, pp, ne, env, columns=True)
+            ali_text = _alignment_text(db, ids, listed, (lambda r: dev.residues(r)) if dev is not None else (lambda r: aa[int(rs[r]):int(rs[r]) + int(rl[r])]), ne, env,
+                                       a_slots, a_cols)
+            with open(alignments, "wb") as f:
+                f.write(ali_text)
     finally:
         if dev is not None:
             dev.close()
@@ -1503,8 +1643,9 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
         env_table = b"".join(out)
         with open(envelopes, "wb") as f:
             f.write(env_table)
+    tail = () if ali_text is None else (ali_text,)
     if domains is None:
-        return ids, scores, table, env_table
+        return (ids, scores, table) + (() if env_table is None else (env_table,)) + tail
     out = [b"target\tprofile\tacc\tdom\tn_dom\ti_from\ti_to\tk_from\tk_to\tM\tseg_bits\tn_match\tn_ins\tn_del\n"]
     for j, (r, p) in enumerate(listed):
         inf = db.info[p]
@@ -1515,7 +1656,7 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     dom_table = b"".join(out)
     with open(domains, "wb") as f:
         f.write(dom_table)
-    return (ids, scores, table, dom_table) if env_table is None else (ids, scores, table, dom_table, env_table)
+    return (ids, scores, table, dom_table) + (() if env_table is None else (env_table,)) + tail
 
 
 def _bias_best_hits(scores, goff, thr, bias_of):
@@ -1550,6 +1691,9 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     traced back on the device and contributes the residues from i_from of its first domain through i_to of its last, not the whole protein.
     region="envelope" (SPEC 13.4): every hit contributes the residues from i_from of its first posterior envelope through i_to of its last - what a
     Forward hit list should be cut by; a hit without an envelope contributes the whole record, and is counted like any other.
+    region="alignment" (SPEC 13.6): every hit contributes the residues from i_from of the optimal-accuracy alignment of its first envelope through i_to
+    of that of its last - the envelope cut without the flanks the model does not align; a hit without an envelope contributes the whole record. A hit
+    with an envelope of more than HMM_ALI_MAX_LD = 8192 residues makes the call raise GsError (GS_ERR_UNSUPPORTED): such an envelope is not aligned.
     translate=True (SPEC 14): one genome per NUCLEOTIDE FASTA file; the candidates are the stop-to-stop six-frame ORFs of min_aa residues and more under
     translation `table`, translated and searched on the device - only the chosen hits' residues come back. The record numbers are then ORF numbers inside
     the genome, and a third value is returned: int64 [n_genomes, n_prof, 4] = (contig index, begin, end, strand) of the chosen ORF in contig coordinates
@@ -1565,15 +1709,15 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     composition alone is dropped. It works with all three target forms and every region."""
     if score not in ("viterbi", "forward"):
         raise ValueError("score: 'viterbi' or 'forward'")
-    if region not in ("protein", "aligned", "envelope"):
-        raise ValueError("region: 'protein', 'aligned' or 'envelope'")
+    if region not in ("protein", "aligned", "envelope", "alignment"):
+        raise ValueError("region: 'protein', 'aligned', 'envelope' or 'alignment'")
     if bias and score != "forward":
         raise ValueError("bias=True corrects Forward scores: score='forward'")
     _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
     if translate:
         return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate, prefilter is not None,
-                                           msv_p, region == "envelope", bias)
+                                           msv_p, region == "envelope", bias, region == "alignment")
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
@@ -1598,6 +1742,11 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
         _, _, ne, env = db.envelopes_all(aa, rs, rl, rec.reshape(-1), pair_prof)
         for j in np.flatnonzero(ne):
             span[int(j)] = (int(env[j, 0, 0]) - 1, int(env[j, int(ne[j]) - 1, 1]))
+    if region == "alignment" and rec.size:
+        pair_prof = np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
+        _, ne, env, slots = db.align_all(aa, rs, rl, rec.reshape(-1), pair_prof, columns=False)
+        for j in np.flatnonzero(ne):
+            span[int(j)] = (int(slots[j, 0, 0]) - 1, int(slots[j, int(ne[j]) - 1, 1]))
     genomes = []
     for g in range(len(goff) - 1):
         hits = []
@@ -1848,6 +1997,29 @@ class _DevOrfs:
             got = run(8)
             return got if got[0] is not None else run(int(got[1].max()))
 
+    def align_listed(self, db, pair_rec, pair_prof, n_env, env):
+        """HmmDb.align_packed(columns=True) over the device residues, for envelopes as envelopes_all() returned them -> (slots, columns)"""
+        pr, pp, _ = _pairs(pair_rec, pair_prof)
+        n = len(pr)
+        ne, env = np.ascontiguousarray(n_env, dtype=np.uint32), np.ascontiguousarray(env, dtype=np.int32)
+        m = env.shape[1]
+        if n == 0 or self.n == 0:
+            return np.zeros((n, m, _lib.HMM_ALI_WORDS), np.int32), [[] for _ in range(n)]
+        lens = np.where(pr < self.n, self.aa_len[np.minimum(pr, self.n - 1)], 0)
+        M = db.M[pp].astype(np.int64)
+        co = _ali_col_off(lens, ne, env, M)
+        with _DevScope(self.ctx) as d:
+            d_slot, d_col = d.new(4 * n * m * _lib.HMM_ALI_WORDS), d.new(8 * max(int(co[-1]), 1))
+            db.align_dev(self.d_aa, self.d_as, self.d_al, self.n, d.up(pr), d.up(pp), n, m, d.up(ne), d.up(env), d_slot, d.up(co), d_col)
+            slots = self.ctx.download(d_slot, (n, m, _lib.HMM_ALI_WORDS), np.int32)
+            cols = self.ctx.download(d_col, (max(int(co[-1]), 1), 2), np.int32)
+        return slots, _ali_columns(slots, cols, co, ne, env, M)
+
+    def align_all(self, db, pair_rec, pair_prof):
+        """HmmDb.align_all() over the device residues -> (fwd, n_env, env, slots, columns)"""
+        fwd, _, ne, env = self.envelopes_all(db, pair_rec, pair_prof)
+        return (fwd, ne, env) + self.align_listed(db, pair_rec, pair_prof, ne, env)
+
     def residues(self, j, a=0, b=None):
         """residues [a, b) of ORF j, read back from the device"""
         b = int(self.aa_len[j]) if b is None else b
@@ -1856,9 +2028,10 @@ class _DevOrfs:
         return self.ctx.download(self.d_aa + int(self.aa_start[j]) + a, (b - a,), np.uint8).tobytes()
 
 
-def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02, envelope=False, bias=False):
+def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02, envelope=False, bias=False,
+                                alignment=False):
     ctx = db.ctx
-    dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd or envelope, aligned), table)
+    dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd or envelope or alignment, aligned), table)
     try:
         ng, npf = len(fna_files), len(db)
         rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
@@ -1880,6 +2053,10 @@ def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, m
             _, _, ne, env = dev.envelopes_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
             for j in np.flatnonzero(ne):
                 span[int(j)] = (int(env[j, 0, 0]) - 1, int(env[j, int(ne[j]) - 1, 1]))
+        if alignment and (rec != _lib.HMM_NO_HIT).any():
+            _, ne, env, slots, _ = dev.align_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
+            for j in np.flatnonzero(ne):
+                span[int(j)] = (int(slots[j, 0, 0]) - 1, int(slots[j, int(ne[j]) - 1, 1]))
         genomes = []
         for g in range(ng):
             hits = []

@@ -1,7 +1,7 @@
 // gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
 // device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, the best record per genome and profile, the domains of
 // the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2), the Backward pass and posterior envelopes of a list of pairs
-// (SPEC 13.4), and the null2 bias correction of those envelopes (SPEC 13.5). Integers only from the file's digits to the raw score. The reader of profile files and the calls that touch no device are
+// (SPEC 13.4), the null2 bias correction of those envelopes (SPEC 13.5) and their optimal-accuracy alignments (SPEC 13.6). Integers only from the file's digits to the raw score. The reader of profile files and the calls that touch no device are
 // gs_hmm_parse.cpp, a host-only unit; the doubles of hmmsearch (bits, E-values, the table of lse, the Viterbi floor, the reported cutoffs) are all there.
 #include <math.h>
 #include <stdlib.h>
@@ -598,12 +598,17 @@ static constexpr uint64_t HMM_ENV_DEFAULT_BLOCK_ROWS = 1ull << 25;
 // With N2 (SPEC 13.5) the rows are those of a segment: L of them under the length model of Lsp residues, bC from the segment's rows. No row is kept;
 // at every row i >= 1 the lane reads M and I of the kept Forward row (keep: the lane's column, in the layout hmm_rows<HMM_FWD_SEG> wrote) and the
 // specials of row i - 1 (fr) and advances the folds of fM + bM, fI + bI over its nodes and of the N, J and C emissions, which it hands back in occ.
+// With ALI (SPEC 13.6) the rows are a segment's too and nothing is folded: at every row i >= 1 the posteriors pM = fM + bM - total and pI = fI + bI - total
+// (64 bits, kept inside NEG .. 0; NEG for I of node M and for padding nodes) take the place of the kept fM and fI, and pX[i] goes to word 3 of the
+// Forward row i, which Forward left 0 and which no later step reads (a step reads row i - 1). keep and fr are written through in this form alone.
 template <int Q> struct HmmOcc { int32_t m[Q], i[Q], x; };
-template <int Q, bool N2>
+enum HmmBack { HMM_BACK_ROWS, HMM_BACK_N2, HMM_BACK_ALI };
+template <int Q, HmmBack BK>
 __device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint8_t *x, uint32_t L, uint32_t Lsp, int2 *rr, const int4 *fr, const int32_t *keep,
-                                                 HmmOcc<Q> *occ)
+                                                 HmmOcc<Q> *occ, int32_t total = 0, uint32_t M = 0)
 {
     constexpr int MP = 64 * Q;
+    constexpr bool N2 = BK == HMM_BACK_N2, ALI = BK == HMM_BACK_ALI, KEPT = N2 || ALI;
     const uint16_t *T = ln.T;
     const int lane = ln.lane, nvalid = ln.nvalid;
     const HmmSpecials sp = hmm_specials(Lsp);
@@ -640,9 +645,9 @@ __device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint
         if (Q >= 12) asm volatile("" ::: "memory");
         // N2: the kept Forward row of this step is asked for here and read at the step's end, so that the row's own work covers the loads; the step
         // of row 0 reads row 1 again and uses nothing of it
-        int32_t kM[N2 ? Q : 1], kI[N2 ? Q : 1];
+        int32_t kM[KEPT ? Q : 1], kI[KEPT ? Q : 1];
         int4 fp = make_int4(0, 0, 0, 0);
-        if constexpr (N2) {
+        if constexpr (KEPT) {
             const uint32_t row = s < L ? L - s - 1 : 0;
             const int32_t *kr = keep + (uint64_t)row * (2 * Q * 64);
 #pragma unroll
@@ -664,7 +669,7 @@ __device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint
             bN = max(hmm_lse(bN + sp.tloop, bB + sp.tmove, T), GS_HMM_NEG);
         }
         const int32_t bE = hmm_lse(bJ + GS_HMM_TEJ, bC + GS_HMM_TEJ, T);
-        if constexpr (!N2) if (lane == 0) rr[L - s] = make_int2(bN, bJ);
+        if constexpr (BK == HMM_BACK_ROWS) if (lane == 0) rr[L - s] = make_int2(bN, bJ);
         int32_t dn = __shfl_down(take[0], 1);
         if (lane == 63) dn = GS_HMM_NEG;
         int32_t Dv[Q], dl = GS_HMM_NEG;
@@ -700,6 +705,19 @@ __device__ __forceinline__ int32_t hmm_back_rows(const HmmLane<Q> ln, const uint
                 oI[q] = hmm_lse(oI[q], kI[q] + Iv[q], T);
             }
             oX = hmm_lse(oX, hmm_lse(hmm_lse((int32_t)i * sp.tloop + bN, fp.y + sp.tloop + bJ, T), fp.z + sp.tloop + bC, T), T);
+        }
+        if constexpr (ALI) if (s < L) {                       // rows L .. 1: the posteriors in the place of the kept Forward cells (SPEC 13.6)
+            const uint32_t i = L - s;
+            const int nvi = min(max((int)M - 1 - lane * Q, 0), Q);
+            int32_t *kw = const_cast<int32_t *>(keep) + (uint64_t)(i - 1) * (2 * Q * 64);
+            auto post = [&](int64_t v) { return (int32_t)min(max(v - total, (int64_t)GS_HMM_NEG), (int64_t)0); };
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                kw[q * 64] = q < nvalid ? post((int64_t)kM[q] + Mv[q]) : GS_HMM_NEG;
+                kw[(Q + q) * 64] = q < nvi ? post((int64_t)kI[q] + Iv[q]) : GS_HMM_NEG;
+            }
+            const int32_t xn = hmm_lse(hmm_lse((int32_t)i * sp.tloop + bN, fp.y + sp.tloop + bJ, T), fp.z + sp.tloop + bC, T);
+            if (lane == 0) ((int32_t *)const_cast<int4 *>(fr + i))[3] = post(xn);
         }
     }
     if constexpr (N2) {
@@ -796,7 +814,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_backward(const int32_t *__res
     const HmmLane<Q> ln = hmm_stage<Q, true>(tables, desc[tp.prof], lse_tab);
     for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
         const HmmTracePair pr = pairs[tp.start + j];
-        const int32_t raw = hmm_back_rows<Q, false>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], (uint32_t)rec_len[pr.rec], rows + pr.row_off, nullptr, nullptr, nullptr);
+        const int32_t raw = hmm_back_rows<Q, HMM_BACK_ROWS>(ln, aa + rec_start[pr.rec], (uint32_t)rec_len[pr.rec], (uint32_t)rec_len[pr.rec], rows + pr.row_off, nullptr, nullptr, nullptr);
         if (ln.lane == 0) bck_out[pr.pair] = raw;
     }
 }
@@ -964,7 +982,7 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_n2_backward(const int32_t *__
         const uint8_t *x = aa + rec_start[sl.rec] + (sl.from - 1);
         const int4 *fr = rows + pr.row_off;
         HmmOcc<Q> occ;
-        (void)hmm_back_rows<Q, true>(ln, x, sl.Ld, L, nullptr, fr, (const int32_t *)keep + pr.ptr_off + ln.lane, &occ);
+        (void)hmm_back_rows<Q, HMM_BACK_N2>(ln, x, sl.Ld, L, nullptr, fr, (const int32_t *)keep + pr.ptr_off + ln.lane, &occ);
         const uint64_t at = (uint64_t)sl.pair * max_env + sl.e;
         hmm_n2_finish<Q>(ln, occ, fr[sl.Ld].z + hmm_specials(L).tmove, x, sl.Ld, d.M, slot_out + at * GS_HMM_N2_WORDS, n2_out ? n2_out + at * 20 : nullptr,
                          occm_out ? occm_out + sl.occ_at : nullptr, occm_out ? occi_out + sl.occ_at : nullptr);
@@ -983,24 +1001,256 @@ __global__ __launch_bounds__(256) void k_hmm_n2_seq(const HmmN2Pair *__restrict_
     seq[j] = hmm_lse(0, HMM_N2_OMEGA + corr, T);
 }
 
+// ---- optimal-accuracy alignment (SPEC 13.6): one alignment of every listed envelope ------------------------------------------------------------------
+// The unit of work and the blocks' lists are null2's (HmmN2Slot, HmmTracePair): k_hmm_n2_forward keeps fM and fI of a slot, k_hmm_ali_backward turns them
+// into pM and pI in place and leaves pX[i] in word 3 of the Forward row i, k_hmm_ali_rows runs the max-plus program of SPEC 13.6 over them with the trace's
+// nibbles (HMM_PTR_B and the bit meanings of SPEC 13.2) and a row record {lowest k of A_E[i], C[i] came from E[i]}, k_hmm_ali_walk follows them.
+//   A cell's weight is w(p) = EXP2[-p & 1023] >> (-p >> 10), Q16, from the 1 024 words of EXP2 in LDS; a transition counts 0 (its table word > STAR) or
+//   OFF, eight rows of such masks in LDS: the seven transition rows and, in the place of PDD, the minimum of the tDD masks in front of a node inside its
+//   lane's group. A chain of masks counts by its minimum, so the scan's a of SPEC 13 (a sum of tDD) is a minimum here. Every stored value is at least OFF
+//   and one step adds at most one OFF to it, so nothing leaves int32; a reachable value is >= 0 and below 2^29 (Ld <= 8 192 weights of at most 2^16),
+//   and a value that a disallowed link or an unreachable cell feeds stays below 0: the walk starts at oa >= 0 and reads reachable cells only.
+enum { HMM_ALI_OFF = -(1 << 30), HMM_ALI_MASK_ROWS = 8, HMM_ALI_ROW_PDD = 7, HMM_ALI_C_FROM_E = 1 };
+static_assert(HMM_ROW_DD - HMM_ROW_MM == 6 && HMM_ROW_PDD == HMM_ROW_MM + HMM_ALI_ROW_PDD, "the seven transition rows lie together, PDD behind them");
+static_assert((int64_t)GS_HMM_ALI_MAX_LD * 65536 <= (1ll << 29), "a reachable value stays below 2^29, so OFF plus every weight of a segment stays below 0");
+struct HmmAliSlot { uint64_t nib_off, col_at; };        // where the slot's nibble words start in the block's scratch; its first column of col_out
+__device__ __forceinline__ int32_t hmm_ali_w(int32_t p, const uint32_t *__restrict__ EX)
+{
+    const uint32_t n = (uint32_t)(-p);                        // 0 .. 2^29
+    return (int32_t)(EX[n & 1023u] >> min(n >> 10, 31u));     // EXP2 <= 2^16, so a shift of 17 or more gives the 0 of SPEC 13.6
+}
+
+// zeros in every slot word
+__global__ __launch_bounds__(256) void k_hmm_ali_fill(uint64_t n_slot_words, int32_t *__restrict__ slot)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_slot_words) slot[i] = 0;
+}
+
+// Backward over the slots of each profile of profs[]: pM, pI in the place of the kept fM, fI, pX in the Forward rows
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_ali_backward(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                                const HmmTracePair *__restrict__ pairs, const uint16_t *__restrict__ lse_tab, const uint8_t *__restrict__ aa,
+                                                                const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                                const HmmN2Slot *__restrict__ slots, const uint32_t *__restrict__ ok, int4 *rows, uint32_t *keep)
+{
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmDesc d = desc[tp.prof];
+    const HmmLane<Q> ln = hmm_stage<Q, true>(tables, d, lse_tab);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const HmmN2Slot sl = slots[pr.pair];
+        if (!ok[sl.pair]) continue;
+        const uint32_t L = (uint32_t)rec_len[sl.rec];
+        const int4 *fr = rows + pr.row_off;
+        (void)hmm_back_rows<Q, HMM_BACK_ALI>(ln, aa + rec_start[sl.rec] + (sl.from - 1), sl.Ld, L, nullptr, fr, (const int32_t *)keep + pr.ptr_off + ln.lane, nullptr,
+                                             fr[sl.Ld].z + hmm_specials(L).tmove, d.M);
+    }
+}
+
+// The program of SPEC 13.6 over the posteriors of each slot, one wavefront a slot: nibbles, row records and oa (word 4 of the slot). The lane layout, the
+// D scan and the pointer decisions are hmm_rows<HMM_TRACE>'s with masks for transition scores and a weight per cell for the match score; the next row's
+// posteriors are asked for before the current row's work, as hmm_back_rows asks for its kept row.
+template <int Q>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_ali_rows(const int32_t *__restrict__ tables, const HmmDesc *__restrict__ desc, const HmmTraceProf *__restrict__ profs,
+                                                            const HmmTracePair *__restrict__ pairs, const uint32_t *__restrict__ exp2_tab,
+                                                            const HmmN2Slot *__restrict__ slots, const HmmAliSlot *__restrict__ aslots, const uint32_t *__restrict__ ok,
+                                                            uint32_t max_env, const int4 *__restrict__ rows, const int32_t *__restrict__ keep, uint32_t *__restrict__ ptrs,
+                                                            int2 *__restrict__ arows, int32_t *__restrict__ slot_out)
+{
+    extern __shared__ int32_t hmm_ali_lds[];
+    constexpr int MP = 64 * Q, NW = hmm_ptr_words(Q), OFF = HMM_ALI_OFF;
+    const HmmTraceProf tp = profs[blockIdx.y];
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= tp.cnt) return;
+    const HmmDesc d = desc[tp.prof];
+    uint32_t *EX = (uint32_t *)(hmm_ali_lds + HMM_ALI_MASK_ROWS * MP);
+    for (int i = (int)threadIdx.x; i < HMM_ALI_ROW_PDD * MP; i += HMM_BLOCK) hmm_ali_lds[i] = tables[d.off + HMM_ROW_MM * MP + i] > GS_HMM_STAR ? 0 : OFF;
+    for (int i = (int)threadIdx.x; i < (int)GS_HMM_EXP2_N; i += HMM_BLOCK) EX[i] = exp2_tab[i];
+    __syncthreads();
+    for (int j = (int)threadIdx.x; j < MP; j += HMM_BLOCK) {
+        int32_t m = 0;
+        for (int t = j - j % Q; t < j; t++) m = min(m, hmm_ali_lds[(HMM_ROW_DD - HMM_ROW_MM) * MP + t]);
+        hmm_ali_lds[HMM_ALI_ROW_PDD * MP + j] = m;
+    }
+    __syncthreads();
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6, base = lane * Q;
+    const int nvalid = min(max((int)d.M - base, 0), Q);
+    const int32_t *mMM = hmm_ali_lds + base, *mMI = mMM + MP, *mMD = mMI + MP, *mIM = mMD + MP, *mII = mIM + MP, *mDM = mII + MP, *mDD = mDM + MP, *mPDD = mDD + MP;
+    int32_t a_step[6];                                        // the masks of the lanes a scan step joins: the minimum of the groups' chains
+    {
+        int32_t a = min(mPDD[Q - 1], mDD[Q - 1]);
+        for (int s = 0; s < 6; s++) {
+            a_step[s] = a;
+            const int32_t up = __shfl_up(a, 1 << s);
+            if (lane >= (1 << s)) a = min(a, up);
+        }
+    }
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)wave; j < tp.cnt; j += gridDim.x * HMM_WAVES) {
+        const HmmTracePair pr = pairs[tp.start + j];
+        const HmmN2Slot sl = slots[pr.pair];
+        if (!ok[sl.pair]) continue;
+        const uint32_t Ld = sl.Ld;
+        const int4 *fr = rows + pr.row_off;
+        const int32_t *kp = keep + pr.ptr_off + lane;
+        uint32_t *pp = ptrs + aslots[pr.pair].nib_off + lane;
+        int2 *ar = arows + pr.row_off;
+        int32_t Mv[Q], Iv[Q], Dv[Q], nM[Q], nI[Q];
+#pragma unroll
+        for (int q = 0; q < Q; q++) { Mv[q] = Iv[q] = Dv[q] = OFF; nM[q] = kp[q * 64]; nI[q] = kp[(Q + q) * 64]; }
+        int32_t nX = fr[1].w, N = 0, C = OFF;
+        for (uint32_t row = 0; row < Ld; row++) {             // row i = row + 1
+            if (Q >= 12) asm volatile("" ::: "memory");
+            int32_t wM[Q], wI[Q];
+#pragma unroll
+            for (int q = 0; q < Q; q++) { wM[q] = hmm_ali_w(nM[q], EX); wI[q] = hmm_ali_w(nI[q], EX); }
+            const int32_t wX = hmm_ali_w(nX, EX);
+            {                                                 // the next row is on its way while this one runs; the last row asks for itself again
+                const uint32_t nr = min(row + 1, Ld - 1);
+                const int32_t *kr = kp + (uint64_t)nr * (2 * Q * 64);
+#pragma unroll
+                for (int q = 0; q < Q; q++) { nM[q] = kr[q * 64]; nI[q] = kr[(Q + q) * 64]; }
+                nX = fr[nr + 1].w;
+            }
+            const int32_t entry = N;                          // A_B[i-1] = A_N[i-1] >= 0
+            uint32_t pk[NW], code_out = HMM_PTR_B;
+#pragma unroll
+            for (int w = 0; w < NW; w++) pk[w] = 0;
+            int32_t give[Q];
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const int32_t a = Mv[q] + mMM[q], b = Iv[q] + mIM[q], c = Dv[q] + mDM[q];
+                const int32_t g = max(max(a, b), c);
+                give[q] = g;
+                const uint32_t code = g >= entry ? (a == g ? 0u : (b == g ? 1u : 2u)) : (uint32_t)HMM_PTR_B;
+                if (q + 1 < Q) pk[(q + 1) >> 3] |= code << (4 * ((q + 1) & 7)); else code_out = code;
+            }
+            int32_t up = __shfl_up(give[Q - 1], 1);
+            if (lane == 0) up = OFF;                          // node 0 has no states
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const int32_t fromM = Mv[q] + mMI[q], v = max(fromM, Iv[q] + mII[q]);
+                pk[q >> 3] |= (fromM == v ? 0u : 4u) << (4 * (q & 7));
+                Iv[q] = max(wI[q] + v, OFF);
+            }
+#pragma unroll
+            for (int q = 0; q < Q; q++) Mv[q] = wM[q] + max(q ? give[q - 1] : up, entry);      // >= 0: the entry is
+            int32_t dl = OFF;
+            Dv[0] = dl;
+#pragma unroll
+            for (int q = 1; q < Q; q++) { dl = max(max(dl + mDD[q - 1], Mv[q - 1] + mMD[q - 1]), OFF); Dv[q] = dl; }
+            const int32_t m_out = Mv[Q - 1] + mMD[Q - 1];
+            int32_t b = max(max(dl + mDD[Q - 1], m_out), OFF);
+#pragma unroll
+            for (int s = 0; s < 6; s++) b = max(b, __shfl_up(b, 1 << s) + a_step[s]);          // a lane below 2^s gets its own b back: b + a <= b
+            int32_t c_in = __shfl_up(b, 1);
+            if (lane == 0) c_in = OFF;
+            {
+                uint32_t edge = (uint32_t)__shfl_up((int)(code_out | (m_out == b ? 0u : 8u)), 1);
+                if (lane == 0) edge = HMM_PTR_B | 8u;
+                pk[0] |= edge;
+            }
+            int32_t e = OFF;
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                Dv[q] = max(Dv[q], c_in + mPDD[q]);
+                if (q >= 1) pk[q >> 3] |= (Mv[q - 1] + mMD[q - 1] == Dv[q] ? 0u : 8u) << (4 * (q & 7));
+                e = q < nvalid ? max(e, Mv[q]) : e;
+            }
+            const int32_t E = hmm_wave_join<HMM_VIT>(e, nullptr);
+#pragma unroll
+            for (int w = 0; w < NW; w++) pp[((uint64_t)row * NW + w) * 64] = pk[w];
+            int first = 0;
+#pragma unroll
+            for (int q = Q - 1; q >= 0; q--) if (q < nvalid && Mv[q] == E) first = q;
+            const int fl = __ffsll((unsigned long long)__ballot(e == E)) - 1;                 // some lane holds it: E is the maximum of the e
+            const int kE = fl * Q + __builtin_amdgcn_readlane(first, fl) + 1;
+            N += wX;
+            C = max(C + wX, E);
+            if (lane == 0) ar[row + 1] = make_int2(kE, C == E ? HMM_ALI_C_FROM_E : 0);
+        }
+        if (lane == 0) slot_out[((uint64_t)sl.pair * max_env + sl.e) * GS_HMM_ALI_WORDS + 4] = C;
+    }
+}
+
+// The walk of SPEC 13.6, one lane per slot of the block: from C[Ld] back to the row it left E in, then the cells of the one domain down to its B -> M
+// entry. The first pass counts, the second writes the columns from the last one down, so they lie in forward order. Every step lowers i or k: a walk
+// ends after at most Ld + M steps whatever the scratch holds, and a slot owns Ld + M columns.
+__global__ __launch_bounds__(HMM_WALK_BLOCK) void k_hmm_ali_walk(const HmmDesc *__restrict__ desc, const HmmTracePair *__restrict__ pairs, uint32_t n,
+                                                                 const uint32_t *__restrict__ pair_prof, const HmmN2Slot *__restrict__ slots,
+                                                                 const HmmAliSlot *__restrict__ aslots, const uint32_t *__restrict__ ok, uint32_t max_env,
+                                                                 const uint32_t *__restrict__ ptrs, const int2 *__restrict__ arows, const int32_t *__restrict__ keep,
+                                                                 int32_t *__restrict__ slot_out, int32_t *__restrict__ col_out)
+{
+    const uint32_t t = blockIdx.x * HMM_WALK_BLOCK + threadIdx.x;
+    if (t >= n) return;
+    const HmmTracePair pr = pairs[t];
+    const HmmN2Slot sl = slots[pr.pair];
+    if (!ok[sl.pair]) return;
+    const HmmAliSlot as = aslots[pr.pair];
+    const int M = (int)desc[pair_prof[sl.pair]].M;
+    const int Q = hmm_q_of((uint32_t)M), NW = hmm_ptr_words(Q);
+    const uint32_t *pp = ptrs + as.nib_off;
+    const int2 *ar = arows + pr.row_off;
+    const int32_t *kp = keep + pr.ptr_off;
+    int i_to = (int)sl.Ld;
+    while (i_to > 1 && !(ar[i_to].y & HMM_ALI_C_FROM_E)) i_to--;
+    const int k_to = min(max(ar[i_to].x, 1), M);
+    int32_t *o = slot_out + ((uint64_t)sl.pair * max_env + sl.e) * GS_HMM_ALI_WORDS;
+    uint32_t total = 0;
+    for (int pass = 0; pass < (col_out ? 2 : 1); pass++) {
+        int i = i_to, k = k_to, st = 0, nm = 0, ni = 0, nd = 0, i_from = 0, k_from = 0;
+        uint32_t at = total;
+        while (i >= 1 && k >= 1) {
+            const int node = k - 1, ln = node / Q, q = node - ln * Q;
+            const uint32_t nb = (pp[((uint64_t)(i - 1) * NW + (q >> 3)) * 64 + ln] >> (4 * (q & 7))) & 15u;
+            if (pass == 1 && at) {
+                at--;
+                int32_t *c = col_out + (as.col_at + at) * 2;
+                c[0] = (int32_t)((uint32_t)st << 28 | (uint32_t)k << 16 | (sl.from + (uint32_t)i - 2));
+                c[1] = st == 2 ? 0 : kp[((uint64_t)(i - 1) * (2 * Q) + (st ? Q : 0) + q) * 64 + ln];
+            }
+            if (st == 0) {
+                nm++;
+                const uint32_t from = nb & 3u;
+                if (from == HMM_PTR_B || i == 1 || k == 1) { i_from = i; k_from = k; break; }
+                st = (int)from; i--; k--;
+            } else if (st == 1) {
+                ni++;
+                st = nb & 4u ? 1 : 0; i--;
+            } else {
+                nd++;
+                st = nb & 8u ? 2 : 0; k--;
+            }
+        }
+        if (!i_from) return;                                    // not a path: only scratch that no row kernel wrote leads here
+        if (pass == 0) {
+            total = (uint32_t)(nm + ni + nd);
+            o[0] = (int32_t)sl.from + i_from - 1; o[1] = (int32_t)sl.from + i_to - 1; o[2] = k_from; o[3] = k_to; o[5] = nm; o[6] = ni; o[7] = nd;
+        }
+    }
+}
+
 // the instances of a class, from the one class list
 struct HmmKernels {
     decltype(&k_hmm_viterbi<1>) vit; decltype(&k_hmm_forward<1>) fwd; decltype(&k_hmm_trace<1>) trace; decltype(&k_hmm_msv<1>) msv; decltype(&k_hmm_viterbi_sel<1>) vit_sel;
     decltype(&k_hmm_forward_rows<1>) fwd_rows; decltype(&k_hmm_backward<1>) back; decltype(&k_hmm_env_score<1>) env_score;
-    decltype(&k_hmm_n2_forward<1>) n2_fwd; decltype(&k_hmm_n2_backward<1>) n2_back;
+    decltype(&k_hmm_n2_forward<1>) n2_fwd; decltype(&k_hmm_n2_backward<1>) n2_back; decltype(&k_hmm_ali_backward<1>) ali_back; decltype(&k_hmm_ali_rows<1>) ali_rows;
 };
 template <size_t... I> static const HmmKernels &hmm_kernels(int cls, std::index_sequence<I...>)
 {
     static const HmmKernels of_class[] = {{k_hmm_viterbi<HMM_CLASS_Q[I]>, k_hmm_forward<HMM_CLASS_Q[I]>, k_hmm_trace<HMM_CLASS_Q[I]>, k_hmm_msv<HMM_CLASS_Q[I]>,
                                            k_hmm_viterbi_sel<HMM_CLASS_Q[I]>, k_hmm_forward_rows<HMM_CLASS_Q[I]>, k_hmm_backward<HMM_CLASS_Q[I]>,
-                                           k_hmm_env_score<HMM_CLASS_Q[I]>, k_hmm_n2_forward<HMM_CLASS_Q[I]>, k_hmm_n2_backward<HMM_CLASS_Q[I]>}...};
+                                           k_hmm_env_score<HMM_CLASS_Q[I]>, k_hmm_n2_forward<HMM_CLASS_Q[I]>, k_hmm_n2_backward<HMM_CLASS_Q[I]>,
+                                           k_hmm_ali_backward<HMM_CLASS_Q[I]>, k_hmm_ali_rows<HMM_CLASS_Q[I]>}...};
     return of_class[cls];
 }
 static const HmmKernels &hmm_kernels(int cls) { return hmm_kernels(cls, std::make_index_sequence<HMM_CLASSES>()); }
 static size_t hmm_lds_bytes(int cls, HmmProg prog) { return (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + (prog == HMM_FWD || prog == HMM_FWD_ROWS ? HMM_LSE_LDS_BYTES : 0); }
 static size_t hmm_msv_lds_bytes(int cls) { return (size_t)HMM_MSV_ROWS * 64 * HMM_CLASS_Q[cls] * 4; }
+static size_t hmm_ali_lds_bytes(int cls) { return ((size_t)HMM_ALI_MASK_ROWS * 64 * HMM_CLASS_Q[cls] + GS_HMM_EXP2_N) * 4; }
 // which kernel a (kernel, class) flag of the profile set belongs to: the three programs of hmm_rows, then MSV and Viterbi over a selected list
-enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_K_BACK, HMM_K_ENV_SCORE, HMM_K_N2_BACK, HMM_KERNEL_KINDS };
+enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_K_BACK, HMM_K_ENV_SCORE, HMM_K_N2_BACK, HMM_K_ALI_BACK, HMM_K_ALI_ROWS, HMM_KERNEL_KINDS };
 
 }  // namespace gs
 
@@ -1012,7 +1262,7 @@ struct gs_hmm_db {
     uint32_t class_start[gs::HMM_CLASSES + 1] = {};
     bool all_ga = true;
     bool lds_set[gs::HMM_KERNEL_KINDS][gs::HMM_CLASSES] = {};
-    gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse;
+    gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse, d_exp2;
 };
 
 namespace gs {
@@ -1066,7 +1316,7 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
     GS_CTX_LOCK(c);
     int rc;
     if ((rc = db->d_tables.alloc(4 * words.size())) || (rc = db->d_desc.alloc(sizeof(HmmDesc) * np)) || (rc = db->d_plist.alloc(4 * np)) || (rc = db->d_ga.alloc(4 * np)) ||
-        (rc = db->d_lse.alloc(HMM_LSE_LDS_BYTES))) return rc;
+        (rc = db->d_lse.alloc(HMM_LSE_LDS_BYTES)) || (rc = db->d_exp2.alloc(4 * GS_HMM_EXP2_N))) return rc;
     GS_HIP_CHECK(hipMemcpyAsync(db->d_tables.p, words.data(), 4 * words.size(), hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_desc.p, db->desc.data(), sizeof(HmmDesc) * np, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_plist.p, db->plist.data(), 4 * np, hipMemcpyHostToDevice, c->stream));
@@ -1074,6 +1324,9 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
     std::vector<uint16_t> lse(HMM_LSE_LDS_N, 0);
     for (uint32_t j = 0; j < GS_HMM_LSE_N; j++) lse[j] = hmm_lse_entry(j);
     GS_HIP_CHECK(hipMemcpyAsync(db->d_lse.p, lse.data(), HMM_LSE_LDS_BYTES, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint32_t> exp2w(GS_HMM_EXP2_N);
+    for (uint32_t f = 0; f < GS_HMM_EXP2_N; f++) exp2w[f] = hmm_exp2_entry(f);
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_exp2.p, exp2w.data(), 4 * GS_HMM_EXP2_N, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(stream_wait(c));           // the host vectors go out of scope
     *out = db.release();
     return GS_OK;
@@ -1363,7 +1616,7 @@ static int hmm_pair_args(gs_ctx *c, const gs_hmm_db *db, const HmmIn &in, const 
     if (n_pairs == 0) return HMM_NOTHING_TO_DO;
     GS_REQUIRE(pair_rec && pair_prof && outs_given, GS_ERR_INVALID, "null argument");
     GS_REQUIRE(in.n_rec == 0 || in.given(), GS_ERR_INVALID, "null argument");
-    GS_REQUIRE(rows_together, GS_ERR_INVALID, "hmm: row_off, out_rows and cont_rows go together");
+    GS_REQUIRE(rows_together, GS_ERR_INVALID, "hmm: an offset array and the outputs it addresses go together (row_off, out_rows, cont_rows; occ_off, occm_out, occi_out; col_off, col_out)");
     GS_REQUIRE(in.n_rec < (1ull << 32) && n_pairs < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or pairs, or more, in one call");
     int rc;
     if (in.host) {
@@ -1567,6 +1820,123 @@ static int hmm_null2_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, const HmmP
     return GS_OK;
 }
 
+// What gs_hmm_align refuses beyond hmm_null2_check, on the same host copies: a listed envelope longer than GS_HMM_ALI_MAX_LD, and - co: col_off or nullptr -
+// a pair whose columns, Ld + M for every listed slot, do not fit between its offset and the next.
+static int hmm_align_check(const gs_hmm_db *db, const uint64_t *lens, const uint32_t *prec, const uint32_t *pprof, uint64_t n_pairs, uint32_t max_env, const uint32_t *n_env,
+                           const int32_t *env, const uint64_t *co)
+{
+    for (uint64_t j = 0; j < n_pairs; j++) {
+        GS_REQUIRE(!co || co[j] <= co[j + 1], GS_ERR_INVALID, "hmm: col_off decreases at pair %llu", (unsigned long long)j);
+        if (prec[j] == GS_HMM_NO_HIT || lens[prec[j]] == 0) continue;
+        const uint64_t listed = std::min<uint64_t>(n_env[j], max_env);
+        uint64_t need = 0;
+        for (uint64_t e = 0; e < listed; e++) {
+            const uint64_t Ld = (uint64_t)(env[(j * max_env + e) * GS_HMM_ENV_WORDS + 1] - env[(j * max_env + e) * GS_HMM_ENV_WORDS] + 1);
+            GS_REQUIRE(Ld <= GS_HMM_ALI_MAX_LD, GS_ERR_UNSUPPORTED, "hmm: envelope %llu of pair %llu has %llu residues, more than %u", (unsigned long long)e,
+                       (unsigned long long)j, (unsigned long long)Ld, GS_HMM_ALI_MAX_LD);
+            need += Ld + db->desc[pprof[j]].M;
+        }
+        GS_REQUIRE(!co || co[j + 1] - co[j] >= need, GS_ERR_INVALID, "hmm: col_off leaves pair %llu fewer columns than its listed envelopes' residues and nodes",
+                   (unsigned long long)j);
+    }
+    return GS_OK;
+}
+
+// R, P: the records and pairs of the call; n_env, env, co: host copies that hmm_null2_check and hmm_align_check have passed; everything else device memory.
+// The blocks are null2's, cut by max_block_cells; a block is a Forward, a Backward and a row launch per class that occurs and one walk.
+static int hmm_align_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, const HmmPairs &P, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env,
+                          const uint64_t *co, int32_t *slot_dev, int32_t *col_dev)
+{
+    const uint64_t n_pairs = P.n, n_slot_words = n_pairs * max_env * GS_HMM_ALI_WORDS;
+    GS_REQUIRE(n_slot_words < (1ull << 31) * 256 && n_pairs * max_env < (1ull << 32) && n_pairs < (1ull << 31), GS_ERR_UNSUPPORTED, "hmm: too many envelope slots");
+    std::vector<HmmN2Pair> np(n_pairs);
+    std::vector<HmmN2Slot> slots;
+    std::vector<HmmAliSlot> aslots;
+    std::vector<uint64_t> slot_len;
+    std::vector<uint32_t> slot_id, slot_prof;
+    for (uint64_t j = 0; j < n_pairs; j++) {
+        const bool has = P.rec[j] != GS_HMM_NO_HIT && R.lens[P.rec[j]] != 0;
+        np[j] = HmmN2Pair{P.rec[j], has ? std::min(n_env[j], max_env) : 0u};
+        uint64_t col = co ? co[j] : 0;
+        for (uint32_t e = 0; e < np[j].listed; e++) {
+            const int32_t *w = env + (j * max_env + e) * GS_HMM_ENV_WORDS;
+            const uint32_t Ld = (uint32_t)(w[1] - w[0] + 1);
+            slot_id.push_back((uint32_t)slots.size()); slot_prof.push_back(P.prof[j]); slot_len.push_back(Ld);
+            slots.push_back(HmmN2Slot{0, (uint32_t)j, e, P.rec[j], (uint32_t)w[0], Ld, 0});
+            aslots.push_back(HmmAliSlot{0, col});
+            col += (uint64_t)Ld + db->desc[P.prof[j]].M;
+        }
+    }
+    auto cells = [&](uint64_t i) { return slot_len[i] * 64 * HMM_CLASS_Q[hmm_class_of(db->desc[slot_prof[i]].M)]; };
+    HmmPairBlocks pb = hmm_pair_blocks(db, slot_len.data(), slot_id.data(), slot_prof.data(), slots.size(), max_block_cells ? max_block_cells : HMM_N2_DEFAULT_BLOCK_CELLS, cells);
+    uint64_t max_keep = 0;                                        // the builder's ptr_off counts the nibble words; it becomes the kept words' start, as in null2
+    for (const HmmPairBlock &b : pb.blocks) {
+        uint64_t at = 0;
+        for (uint32_t t = b.start; t < b.start + b.n; t++) { aslots[pb.tp[t].pair].nib_off = pb.tp[t].ptr_off; pb.tp[t].ptr_off = at; at += 2 * cells(pb.tp[t].pair); }
+        max_keep = std::max(max_keep, at);
+    }
+    PoolBuf d_np(c, SL_HMMN_PAIRS), d_slots(c, SL_HMMN_SLOTS), d_aslots(c, SL_HMMA_SLOTS), d_ok(c, SL_HMMN_OK), d_keep(c, SL_HMMN_KEEP), d_rows(c, SL_HMME_FROWS),
+        d_arows(c, SL_HMME_BROWS), d_ptr(c, SL_HMMT_PTR), d_seg(c, SL_HMMA_SEG);
+    int rc;
+    if ((rc = d_np.alloc(sizeof(HmmN2Pair) * n_pairs)) || (rc = d_slots.alloc(sizeof(HmmN2Slot) * slots.size())) || (rc = d_aslots.alloc(sizeof(HmmAliSlot) * slots.size())) ||
+        (rc = d_ok.alloc(4 * n_pairs)) || (rc = d_seg.alloc(4 * n_pairs * max_env * GS_HMM_N2_WORDS)))
+        return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(d_np.p, np.data(), sizeof(HmmN2Pair) * n_pairs, hipMemcpyHostToDevice, c->stream));
+    if (!slots.empty()) {
+        GS_HIP_CHECK(hipMemcpyAsync(d_slots.p, slots.data(), sizeof(HmmN2Slot) * slots.size(), hipMemcpyHostToDevice, c->stream));
+        GS_HIP_CHECK(hipMemcpyAsync(d_aslots.p, aslots.data(), sizeof(HmmAliSlot) * slots.size(), hipMemcpyHostToDevice, c->stream));
+    }
+    if (n_slot_words) {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_ali_fill<<<(unsigned)((n_slot_words + 255) / 256), 256, 0, c->stream>>>(n_slot_words, slot_dev);
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    {
+        ProfScope ps(c, FAM_SEARCH);
+        k_hmm_n2_flag<<<(unsigned)n_pairs, 64, 0, c->stream>>>(d_np.as<HmmN2Pair>(), R.aa, R.rs, R.rl, d_ok.as<uint32_t>());
+        GS_HIP_CHECK(hipGetLastError());
+    }
+    const int32_t *tables = db->d_tables.as<int32_t>();
+    const HmmDesc *desc = db->d_desc.as<HmmDesc>();
+    const uint16_t *lse = db->d_lse.as<uint16_t>();
+    return hmm_run_blocks(
+        c, pb,
+        [&](const HmmPairBlocks &pb) {
+            int rc;
+            if ((rc = d_keep.alloc(4 * max_keep)) || (rc = d_rows.alloc(sizeof(int4) * pb.max_rows)) || (rc = d_arows.alloc(sizeof(int2) * pb.max_rows))) return rc;
+            return d_ptr.alloc(4 * pb.max_ptr);
+        },
+        [&](const HmmBlockLists &d, const HmmPairBlock &b, int cls, uint32_t wg) -> int {
+            const auto kf = hmm_kernels(cls).n2_fwd;           // (its seg_raw goes to a scratch of null2's slot shape: nobody reads it)
+            const size_t lds = hmm_lds_bytes(cls, HMM_FWD);
+            int rc = hmm_block_launch(c, db, HMM_FWD_SEG, kf, lds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                kf<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, tprof, d.tp, lse, R.aa, R.rs, R.rl, d_slots.as<HmmN2Slot>(), d_ok.as<uint32_t>(), max_env, d_rows.as<int4>(),
+                                                        d_keep.as<uint32_t>(), d_seg.as<int32_t>());
+            });
+            if (rc) return rc;
+            const auto kb = hmm_kernels(cls).ali_back;
+            rc = hmm_block_launch(c, db, HMM_K_ALI_BACK, kb, lds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                kb<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, tprof, d.tp, lse, R.aa, R.rs, R.rl, d_slots.as<HmmN2Slot>(), d_ok.as<uint32_t>(), d_rows.as<int4>(),
+                                                        d_keep.as<uint32_t>());
+            });
+            if (rc) return rc;
+            const auto kr = hmm_kernels(cls).ali_rows;
+            const size_t alds = hmm_ali_lds_bytes(cls);
+            return hmm_block_launch(c, db, HMM_K_ALI_ROWS, kr, alds, d, b, cls, wg, [&](dim3 grid, const HmmTraceProf *tprof) {
+                kr<<<grid, HMM_BLOCK, alds, c->stream>>>(tables, desc, tprof, d.tp, db->d_exp2.as<uint32_t>(), d_slots.as<HmmN2Slot>(), d_aslots.as<HmmAliSlot>(), d_ok.as<uint32_t>(),
+                                                         max_env, d_rows.as<int4>(), d_keep.as<int32_t>(), d_ptr.as<uint32_t>(), d_arows.as<int2>(), slot_dev);
+            });
+        },
+        [&](const HmmBlockLists &d, const HmmPairBlock &b) -> int {
+            ProfScope ps(c, FAM_SEARCH);
+            k_hmm_ali_walk<<<(b.n + HMM_WALK_BLOCK - 1) / HMM_WALK_BLOCK, HMM_WALK_BLOCK, 0, c->stream>>>(desc, d.tp + b.start, b.n, P.prof_dev, d_slots.as<HmmN2Slot>(),
+                                                                                                            d_aslots.as<HmmAliSlot>(), d_ok.as<uint32_t>(), max_env, d_ptr.as<uint32_t>(),
+                                                                                                            d_arows.as<int2>(), d_keep.as<int32_t>(), slot_dev, col_dev);
+            GS_HIP_CHECK(hipGetLastError());
+            return GS_OK;
+        });
+}
+
 // ---- the bodies of the ABI pairs: in.host says which entry called -----------------------------------------------------------------------------------
 // The four pairs that score every (record, profile) pair: gs_hmm_search (Viterbi), gs_hmm_search_msv (MSV; SPEC 13.3), gs_hmm_search_forward (Viterbi,
 // then Forward for the pairs at or above vit_floor; SPEC 13.1) and gs_hmm_search_filtered (MSV, Viterbi at or above msv_floor and, with fwd_out, Forward
@@ -1688,9 +2058,60 @@ static int hmm_null2_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, const uint3
     return in.host ? hmm_fetch(c, {&slot, &seq, &n2, &om, &oi}) : GS_OK;          // (hmm_null2_impl has waited)
 }
 
+// gs_hmm_align{,_dev}. n_env and env as for null2; a _dev form fetches them, and col_off, once. A host form uploads col_out too: the columns no slot
+// writes keep what the caller's array holds.
+static int hmm_align_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, const uint32_t *pair_rec, const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env,
+                          uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env, int32_t *slot_out, const uint64_t *col_off, int32_t *col_out)
+{
+    HmmLock lock;
+    HmmRecs R(c); HmmPairs P(c);
+    HmmArg slot(c, SL_HMMB_PAIR_ITEMS), cols(c, SL_HMMB_PAIR_COLS);
+    std::vector<uint64_t> no_rows, h_co;
+    std::vector<uint32_t> h_nenv;
+    std::vector<int32_t> h_env;
+    int rc = hmm_pair_args(c, db, in, pair_rec, pair_prof, n_pairs, n_env && (max_env == 0 || (env && slot_out)), !col_off == !col_out, GS_HMM_FWD_MAX_L, true, nullptr, no_rows,
+                           lock, R, P);
+    if (rc) return rc == HMM_NOTHING_TO_DO ? GS_OK : rc;
+    const uint64_t n_env_words = n_pairs * max_env * GS_HMM_ENV_WORDS;
+    if (!in.host) {
+        h_nenv.resize(n_pairs); h_env.resize(n_env_words);
+        GS_HIP_CHECK(hipMemcpyAsync(h_nenv.data(), n_env, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+        if (n_env_words) GS_HIP_CHECK(hipMemcpyAsync(h_env.data(), env, 4 * n_env_words, hipMemcpyDeviceToHost, c->stream));
+        if (col_off) {
+            h_co.resize(n_pairs + 1);
+            GS_HIP_CHECK(hipMemcpyAsync(h_co.data(), col_off, 8 * (n_pairs + 1), hipMemcpyDeviceToHost, c->stream));
+        }
+        GS_HIP_CHECK(stream_wait(c));
+        n_env = h_nenv.data(); env = h_env.data();
+    }
+    const uint64_t *co = !col_off ? nullptr : in.host ? col_off : h_co.data();
+    if ((rc = hmm_null2_check(db, R.lens, P.rec, P.prof, n_pairs, max_env, n_env, env, nullptr)) ||
+        (rc = hmm_align_check(db, R.lens, P.rec, P.prof, n_pairs, max_env, n_env, env, co)))
+        return rc;
+    if ((rc = slot.bind(in.host, slot_out, 4 * n_pairs * max_env * GS_HMM_ALI_WORDS, HMM_DOWN)) ||
+        (co && (rc = cols.bind(in.host, col_out, in.host ? 8 * co[n_pairs] : 0, HMM_UP | HMM_DOWN))))
+        return rc;
+    if ((rc = hmm_align_impl(c, db, R, P, max_env, max_block_cells, n_env, env, co, slot.as<int32_t>(), co ? cols.as<int32_t>() : nullptr))) return rc;
+    return in.host ? hmm_fetch(c, {&slot, &cols}) : GS_OK;                        // (hmm_align_impl has waited)
+}
+
 }  // namespace gs
 
 extern "C" {
+
+int gs_hmm_align_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, const uint32_t *pair_rec_dev,
+                     const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env_dev, const int32_t *env_dev,
+                     int32_t *slot_out_dev, const uint64_t *col_off_dev, int32_t *col_out_dev)
+{
+    return gs::hmm_align_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, pair_rec_dev, pair_prof_dev, n_pairs, max_env, max_block_cells, n_env_dev, env_dev,
+                              slot_out_dev, col_off_dev, col_out_dev);
+}
+int gs_hmm_align(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                 const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env, int32_t *slot_out,
+                 const uint64_t *col_off, int32_t *col_out)
+{
+    return gs::hmm_align_form(c, db, {true, aa, rec_start, rec_len, n_rec}, pair_rec, pair_prof, n_pairs, max_env, max_block_cells, n_env, env, slot_out, col_off, col_out);
+}
 
 int gs_hmm_null2_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, const uint32_t *pair_rec_dev,
                      const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env_dev, const int32_t *env_dev,
@@ -1775,6 +2196,24 @@ int gs_hmm_db_tables(gs_hmm_db *db, uint64_t p, int32_t *tables_out, uint64_t ca
     for (uint32_t row = 0; row < GS_HMM_TABLE_ROWS; row++) {
         tables_out[(size_t)row * W] = m.tab[(size_t)row * W];                 // node 0 is not on the device: no state of it exists (SPEC 13)
         for (uint32_t k = 1; k <= M; k++) tables_out[(size_t)row * W + k] = dev[(size_t)row * MP + (k - 1)];
+    }
+    return GS_OK;
+}
+
+int gs_hmm_db_consensus(gs_hmm_db *db, uint64_t p, char *out, uint64_t cap)
+{
+    using namespace gs;
+    GS_REQUIRE(db && out && p < db->models.size(), GS_ERR_INVALID, "bad argument");
+    const HmmModel &m = db->models[p];
+    const uint32_t M = m.info.M, W = M + 1;
+    GS_REQUIRE(cap >= M, GS_ERR_INVALID, "hmm: the consensus has %u letters, cap = %llu", M, (unsigned long long)cap);
+    static const int32_t bg[20] = GS_HMM_BG_LIST;
+    static const char aa[] = "ACDEFGHIKLMNPQRSTVWY";
+    for (uint32_t k = 1; k <= M; k++) {             // the most probable residue: match score plus background, the first in alphabet order on a tie
+        int best = 0;
+        for (int a = 1; a < 20; a++)
+            if ((int64_t)m.tab[(size_t)a * W + k] + bg[a] > (int64_t)m.tab[(size_t)best * W + k] + bg[best]) best = a;
+        out[k - 1] = aa[best];
     }
     return GS_OK;
 }

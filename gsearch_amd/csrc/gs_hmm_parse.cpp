@@ -164,10 +164,19 @@ int hmm_parse_all(const char *text, size_t n, std::vector<HmmModel> &out)
 }
 
 uint16_t hmm_lse_entry(uint32_t j) { return (uint16_t)floor(1024.0 * log2(1.0 + exp2(-2.0 * (double)j / 1024.0)) + 0.5); }
+uint32_t hmm_exp2_entry(uint32_t f) { return (uint32_t)floor(65536.0 * exp2(-(double)f / 1024.0) + 0.5); }
 
 }  // namespace gs
 
 extern "C" {
+
+int gs_hmm_exp2_table(uint32_t *out, uint64_t cap)
+{
+    GS_REQUIRE(out, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(cap >= GS_HMM_EXP2_N, GS_ERR_INVALID, "hmm: the table has %u entries, cap = %llu", GS_HMM_EXP2_N, (unsigned long long)cap);
+    for (uint32_t f = 0; f < GS_HMM_EXP2_N; f++) out[f] = gs::hmm_exp2_entry(f);
+    return GS_OK;
+}
 
 int gs_hmm_parse_mem(const void *text, uint64_t n_bytes, uint32_t model, gs_hmm_info *info_out, int32_t *tables_out, uint64_t cap_words, uint32_t *n_models_out)
 {

@@ -64,5 +64,7 @@ struct HmmModel {
 int hmm_parse_all(const char *text, size_t n, std::vector<HmmModel> &out);
 // T of SPEC 13.1 on the host: no entry lies closer than 3.5e-6 to a rounding boundary, so the f64 log2 of any libm gives the same integers
 uint16_t hmm_lse_entry(uint32_t j);
+// EXP2 of SPEC 13.6 on the host: no entry's unrounded value lies within 1e-6 of a half-integer (the CPU test shows it), so any libm gives the same integers
+uint32_t hmm_exp2_entry(uint32_t f);
 
 }  // namespace gs

@@ -87,6 +87,9 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* hmmsearch, null2: the pairs and the listed envelope slots of a call, which pairs have a score, a block's kept M and I rows of Forward (its       \
        special rows lie in HMME_FROWS: the forms of one context cannot nest); a host form's staging of the n2 vectors */                               \
     X(HMMN_PAIRS) X(HMMN_SLOTS) X(HMMN_OK) X(HMMN_KEEP) X(HMMB_PAIR_N2)                                                                                \
+    /* hmmsearch, alignment: per listed slot where its nibbles and columns start, the place of the seg_raw words null2's Forward writes and nobody      \
+       reads (everything else lies in null2's, the trace's and the envelopes' slots: the forms of one context cannot nest); a host form's columns */    \
+    X(HMMA_SLOTS) X(HMMA_SEG) X(HMMB_PAIR_COLS)                                                                                                         \
     /* orfs (gs_orf.hip): tile prefix of the records and the call's counters; per tile the last stop of each (strand, class) pair, then its kept ORFs,      \
        residues and long drops (each scanned in place); the partial results of those scans; staging of the host form */                                 \
     X(ORF_REC_TILES) X(ORF_META) X(ORF_STOPS) X(ORF_COUNTS) X(ORF_PARTIALS) X(ORFB_SEQ) X(ORFB_REC_START) X(ORFB_REC_LEN) X(ORFB_ORF) X(ORFB_AA)         \

@@ -307,6 +307,9 @@ void gs_hmm_db_free(gs_hmm_db *db);
 int gs_hmm_db_info(gs_hmm_db *db, uint64_t *n_prof_out, gs_hmm_info *info_out, uint64_t cap);
 /* the table of profile p as gs_hmm_parse_mem writes it, nodes 1..M read back from the device copy the kernel uses */
 int gs_hmm_db_tables(gs_hmm_db *db, uint64_t p, int32_t *tables_out, uint64_t cap_words);
+/* host only: out[k - 1] = the consensus letter of node k = 1 .. M of profile p, upper case, no terminator: the residue whose match score plus background
+ * log-odds (SPEC 13) is largest, the first in the order ACDEFGHIKLMNPQRSTVWY on a tie; cap < M: GS_ERR_INVALID */
+int gs_hmm_db_consensus(gs_hmm_db *db, uint64_t p, char *out, uint64_t cap);
 /* score_out[r * n_prof + p] = raw score of record r = aa[rec_start[r] .. + rec_len[r]) against profile p. Device form: all arrays device
  * memory; the lengths are read back once. A record longer than GS_HMM_MAX_L, or 2^32 records or more: GS_ERR_UNSUPPORTED, nothing written. */
 int gs_hmm_search_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
@@ -389,7 +392,7 @@ int gs_hmm_trace_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const ui
  * out[i] <= -156 (occupancy >= 0.10); a run is a maximal stretch of in-rows in which every row but the last has cont[i] <= -156; a run is an envelope
  * iff some row of it has out[i] <= -425 (occupancy >= 0.25). An envelope is GS_HMM_ENV_WORDS int32: i_from, i_to (1-based, inclusive), env_raw = the
  * Forward raw score of the rows i_from .. i_to alone under the length model of the whole record, peak = the smallest out[i] of the envelope.
- * No stochastic clustering (a run is one envelope), no alignment; env_raw is uncorrected (the null2 correction is gs_hmm_null2). Pairs in any order, repeats allowed.
+ * No stochastic clustering (a run is one envelope); the alignment of an envelope is gs_hmm_align (SPEC 13.6); env_raw is uncorrected (the null2 correction is gs_hmm_null2). Pairs in any order, repeats allowed.
  * fwd_out[j] = what gs_hmm_search_forward writes for pair j; bck_out[j] = bN[0] - null, the same probability summed from the other end (it differs
  * from fwd_out[j] by rounding alone); n_env_out[j] = the true number of envelopes; env_out[j][0 .. min(n_env, max_env)) = the first envelopes in
  * sequence order, the other slots of the pair zeros (max_env = 0 with env_out = NULL is allowed). row_off (n_pairs + 1 words, optional, with out_rows
@@ -434,6 +437,34 @@ int gs_hmm_null2_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const ui
                      const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env_dev,
                      const int32_t *env_dev, int32_t *slot_out_dev, int32_t *seq_bias_out_dev, int32_t *n2_out_dev, const uint64_t *occ_off_dev, int32_t *occm_out_dev,
                      int32_t *occi_out_dev);
+
+/* Optimal-accuracy alignment (SPEC 13.6): which residue of a listed envelope sits on which node, and how sure the model is of each column - HMMER3's
+ * maximum-expected-accuracy alignment restated in the integer units and lse of SPEC 13 / 13.1, all on the device. Opt-in: no other call changes.
+ * Forward and Backward over the envelope are gs_hmm_null2's; their sums minus the segment's total are the posteriors pM, pI, pX in units (<= 0), a
+ * posterior counts w(p) = EXP2[-p & 1023] >> (-p >> 10) in Q16 (0 .. 65536), and the alignment is the one path N.. B M/I/D.. E C.. through the
+ * segment - exactly one domain, only transitions the profile allows (table word > GS_HMM_STAR) - whose emitting cells' weights sum highest; ties go
+ * to the first alternative of SPEC 13.6, so the path is unique. Arguments and refusals are those of gs_hmm_null2 (n_env and env are inputs); beyond
+ * them a listed envelope of more than GS_HMM_ALI_MAX_LD residues: GS_ERR_UNSUPPORTED, nothing written.
+ * slot_out[j][e] = GS_HMM_ALI_WORDS int32: i_from, i_to (record coordinates, 1-based, inclusive), k_from, k_to, oa (the path's summed weight plus
+ * w(pX) of the segment's rows outside i_from .. i_to; expected accuracy = oa / (65536 Ld)), n_match, n_ins, n_del; the other slots of the pair
+ * zeros. n_match + n_ins = i_to - i_from + 1 and n_match + n_del = k_to - k_from + 1.
+ * col_off (n_pairs + 1 words, optional, with col_out): the columns of slot e of pair j, in order from (i_from, k_from) to (i_to, k_to), two int32
+ * each, start at column col_off[j] + the sum over e' < e of Ld_e' + M; word 0 = state << 28 | k << 16 | (i - 1) with state 0 M, 1 I, 2 D and i the
+ * record row of the cell (for D the row it sits in), word 1 = pM or pI of the cell in units, 0 for D; n_match + n_ins + n_del of them are written.
+ * col_off[j + 1] - col_off[j] must hold that sum over all listed slots of the pair, else GS_ERR_INVALID. A pair with pair_rec = GS_HMM_NO_HIT, an
+ * empty record or a record with a byte that is no residue: zeroed slots, no columns. max_block_cells as for gs_hmm_null2; no output depends on it.
+ * Device form: every array device memory; the lengths, the pair list, n_env, env and col_off are read back once. */
+#define GS_HMM_ALI_WORDS 8u
+#define GS_HMM_ALI_MAX_LD 8192u
+#define GS_HMM_EXP2_N 1024u           /* entries of EXP2: EXP2[f] = floor(65536 * 2^(-f / 1024) + 1/2), EXP2[0] = 65536 */
+/* host only: out[0 .. GS_HMM_EXP2_N) = EXP2; cap < GS_HMM_EXP2_N: GS_ERR_INVALID */
+int gs_hmm_exp2_table(uint32_t *out, uint64_t cap);
+int gs_hmm_align(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, const uint32_t *pair_rec,
+                 const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env, const int32_t *env, int32_t *slot_out,
+                 const uint64_t *col_off, int32_t *col_out);
+int gs_hmm_align_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                     const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env_dev,
+                     const int32_t *env_dev, int32_t *slot_out_dev, const uint64_t *col_off_dev, int32_t *col_out_dev);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* orfs (SPEC 14): stop-to-stop six-frame translation of packed nucleotide records on the device - the model-free way to feed hmmsearch from genomes.

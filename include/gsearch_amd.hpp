@@ -325,6 +325,17 @@ public:
                            nullptr));
         return b;
     }
+    // SPEC 13.6: the optimal-accuracy alignment of the envelopes envelopes() listed for the same pairs and max_env.
+    // slot[(j * max_env + d) * GS_HMM_ALI_WORDS ..] = i_from, i_to, k_from, k_to, oa, n_match, n_ins, n_del; expected accuracy = oa / (65536 Ld)
+    std::vector<int32_t> align(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len, const std::vector<uint32_t> &pair_rec,
+                               const std::vector<uint32_t> &pair_prof, const Envelopes &e, uint32_t max_env = 8, uint64_t max_block_cells = 0) const
+    {
+        const size_t n = pair_rec.size();
+        std::vector<int32_t> slot(n * max_env * GS_HMM_ALI_WORDS);
+        check(gs_hmm_align(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), pair_rec.data(), pair_prof.data(), n, max_env, max_block_cells,
+                           e.n_env.data(), e.env.empty() ? nullptr : e.env.data(), slot.empty() ? nullptr : slot.data(), nullptr, nullptr));
+        return slot;
+    }
     // the floor of profile p for a Viterbi P-value of filter_p (HMMER's F2 = 1e-3): INT32_MIN + 1 without STATS LOCAL VITERBI
     int32_t viterbi_floor(size_t profile, double filter_p = 1e-3) const
     {

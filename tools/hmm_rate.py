@@ -48,12 +48,21 @@ With --null2 also (SPEC 13.5):
   check         seg_raw of every listed slot against env_raw, both biases >= 0, the largest |mass|, and `check` sampled pairs against the restatement
                 (tests/pyref_hmm_null2.py): the expected differences are 0
 
+With --align also (SPEC 13.6), over the same two pair lists (`ga`, `all`) with max_env = 2:
+  null2         seconds of gs_hmm_null2_dev on the listed slots: the parent commit's kernels (profiles/hmm_align_resources.txt shows them unchanged; the
+                parent's own run is profiles/hmm_null2_rate.log), the yardstick, alternating with align in the same rounds
+  align         seconds of gs_hmm_align_dev on the same slots without columns, and with them (`align_cols`); the slots, their rows and cells. The split
+                between k_hmm_n2_forward, k_hmm_ali_backward, k_hmm_ali_rows and k_hmm_ali_walk comes from a kernel trace of one more run of this
+                mode; tools/hmm_align_split.py turns the trace's statistics into the line kept beside this one in the log
+  check         the identities of SPEC 13.6 on every listed slot, and `check` sampled pairs against the restatement (tests/pyref_hmm_align.py): the
+                expected differences are 0
+
 --dump PATH saves the downloaded matrices of the modes that ran as one .npz (the Viterbi scores; both Forward matrices; raw, n_dom and the domain
 words of trace_best and trace_all), so that two builds of the library (GS_LIB_PATH) can be compared word for word.
 
-usage: hmm_rate.py [--forward | --trace | --posterior | --null2 | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
+usage: hmm_rate.py [--forward | --trace | --posterior | --null2 | --align | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
                    [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log | hmm_msv_rate.log | hmm_posterior_rate.log |
-                   hmm_null2_rate.log]"""
+                   hmm_null2_rate.log | hmm_align_rate.log]"""
 import argparse
 import json
 import os
@@ -78,10 +87,13 @@ def main():
     ap.add_argument("--msv", action="store_true")
     ap.add_argument("--posterior", action="store_true")
     ap.add_argument("--null2", action="store_true")
+    ap.add_argument("--align", action="store_true")
     ap.add_argument("--parent-s", type=float, default=None)
     ap.add_argument("--log", default=None)
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
+    if a.log is None and a.align:
+        a.log = os.path.join(ROOT, "profiles", "hmm_align_rate.log")
     if a.log is None and a.null2:
         a.log = os.path.join(ROOT, "profiles", "hmm_null2_rate.log")
     if a.log is None:
@@ -141,6 +153,8 @@ def main():
         posterior_part(a, ctx, db, texts, recs, ptrs, d_score, cells, res, rng, dump)
     if a.null2:
         null2_part(a, ctx, db, texts, recs, ptrs, d_score, res, rng, dump)
+    if a.align:
+        align_part(a, ctx, db, texts, recs, ptrs, d_score, res, rng, dump)
     if a.dump:
         with open(a.dump, "wb") as f:
             np.savez(f, **dump)
@@ -309,6 +323,86 @@ def null2_part(a, ctx, db, texts, recs, ptrs, d_vit, res, rng, dump):
                 diff += int(not (np.array_equal(slots[j], want[0][0]) and sb[j] == want[1][0]))
             res["null2_check_pairs"], res["null2_check_differences"] = a.check, diff
         for ptr in [d_pr, d_pp] + e_bufs + n_bufs:
+            ctx.free(ptr)
+
+
+def align_part(a, ctx, db, texts, recs, ptrs, d_vit, res, rng, dump):
+    import pyref_hmm as R
+    import pyref_hmm_align as A
+    n_prof, max_env = len(db), 2
+    M = np.array([int(m) for m in db.M], np.int64)
+    d_fwd_all = ctx.alloc(4 * a.n * n_prof)
+    db.search_forward_dev(ptrs[0], ptrs[1], ptrs[2], a.n, None, d_vit, d_fwd_all)
+    ctx.sync()
+    fwd_all = ctx.download(d_fwd_all, (a.n, n_prof), np.int32)
+    ctx.free(d_fwd_all)
+    thr = db.thresholds("ga").astype(np.int64)
+    ga = np.argwhere((fwd_all != R.NO_SCORE) & (fwd_all.astype(np.int64) >= thr[None, :]))
+    lists = {"ga": (ga[:, 0].astype(np.uint32), ga[:, 1].astype(np.uint32)),
+             "all": (np.repeat(np.arange(a.n, dtype=np.uint32), n_prof), np.tile(np.arange(n_prof, dtype=np.uint32), a.n))}
+
+    def timed(call):
+        ctx.sync()
+        t = time.perf_counter()
+        call()
+        ctx.sync()
+        return time.perf_counter() - t
+
+    for name, (pr, pp) in lists.items():
+        n = len(pr)
+        d_pr, d_pp = ctx.alloc(max(pr.nbytes, 16)), ctx.alloc(max(pp.nbytes, 16))
+        ctx.upload(d_pr, pr); ctx.upload(d_pp, pp)
+        e_bufs = [ctx.alloc(max(4 * n, 16)) for _ in range(3)] + [ctx.alloc(max(4 * n * max_env * 4, 16))]
+        db.envelopes_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, d_pp, n, max_env, *e_bufs)
+        ctx.sync()
+        ne, env = ctx.download(e_bufs[2], (n,), np.uint32), ctx.download(e_bufs[3], (n, max_env, 4), np.int32)
+        listed = np.arange(max_env)[None, :] < np.minimum(ne, max_env)[:, None]
+        Ld = (env[:, :, 1] - env[:, :, 0] + 1).astype(np.int64) * listed
+        co = np.zeros(n + 1, np.uint64)
+        co[1:] = np.cumsum(Ld.sum(axis=1) + listed.sum(axis=1) * M[pp])
+        d_co, d_cols = ctx.alloc(co.nbytes), ctx.alloc(max(8 * int(co[-1]), 16))
+        ctx.upload(d_co, co)
+        n_bufs = [ctx.alloc(max(4 * n * max_env * 4, 16)), ctx.alloc(max(4 * n, 16))]
+        d_slots = ctx.alloc(max(4 * n * max_env * A.ALI_WORDS, 16))
+        runs = {"null2": lambda: db.null2_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, d_pp, n, max_env, e_bufs[2], e_bufs[3], n_bufs[0], n_bufs[1]),
+                "align": lambda: db.align_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, d_pp, n, max_env, e_bufs[2], e_bufs[3], d_slots),
+                "align_cols": lambda: db.align_dev(ptrs[0], ptrs[1], ptrs[2], a.n, d_pr, d_pp, n, max_env, e_bufs[2], e_bufs[3], d_slots, d_co, d_cols)}
+        times = {k: [] for k in runs}
+        for it in range(a.repeat + 1):                           # the first round is the warm-up of all; they alternate inside a round
+            for k, call in runs.items():
+                t = timed(call)
+                if it:
+                    times[k].append(t)
+        slots = ctx.download(d_slots, (n, max_env, A.ALI_WORDS), np.int32).astype(np.int64)
+        cols = ctx.download(d_cols, (max(int(co[-1]), 1), 2), np.int32)
+        dump.update({"align_%s_slots" % name: slots})
+        for k, ts in times.items():
+            res["%s_%s_times_s" % (k, name)] = ts
+            res["%s_%s_min_s" % (k, name)], res["%s_%s_median_s" % (k, name)] = min(ts), float(np.median(ts))
+        res["align_%s_pairs" % name], res["align_%s_slots" % name] = n, int(listed.sum())
+        res["align_%s_rows" % name] = int(Ld.sum())
+        res["align_%s_cells" % name] = int((Ld * M[pp][:, None]).sum())
+        res["align_%s_over_null2" % name] = res["align_%s_min_s" % name] / res["null2_%s_min_s" % name]
+        w = slots[listed]
+        e = env[listed].astype(np.int64)
+        bad = (w[:, 5] + w[:, 6] != w[:, 1] - w[:, 0] + 1) | (w[:, 5] + w[:, 7] != w[:, 3] - w[:, 2] + 1) | (w[:, 0] < e[:, 0]) | (w[:, 1] > e[:, 1]) | (w[:, 4] < 0)
+        res["align_%s_identity_failures" % name] = int(bad.sum())
+        res["align_%s_mean_accuracy" % name] = float((w[:, 4] / (65536.0 * (e[:, 1] - e[:, 0] + 1))).mean()) if len(w) else 0.0
+        res["align_%s_columns" % name] = int(w[:, 5:8].sum())
+        if name == "ga":
+            diff = 0
+            for _ in range(a.check):
+                j = int(rng.integers(n))
+                want = A.align_pairs([R.parse_hmm(texts[int(pp[j])])[0]], recs, [int(pr[j])], [0], ne[j:j + 1], env[j:j + 1], max_env)
+                got = cols[int(co[j]):int(co[j + 1])]
+                at = 0
+                ok = np.array_equal(slots[j], want[0][0])
+                for d, c in enumerate(want[1][0]):
+                    ok = ok and np.array_equal(got[at:at + len(c)], A.column_words(c))
+                    at += int(Ld[j, d]) + int(M[pp[j]])
+                diff += int(not ok)
+            res["align_check_pairs"], res["align_check_differences"] = a.check, diff
+        for ptr in [d_pr, d_pp, d_co, d_cols, d_slots] + e_bufs + n_bufs:
             ctx.free(ptr)
 
 
