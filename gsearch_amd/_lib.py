@@ -107,6 +107,7 @@ HMM_MAX_M, HMM_MAX_L, HMM_NO_SCORE, HMM_NO_HIT, HMM_TABLE_ROWS = 1280, 1 << 18, 
 HMM_AA = "ACDEFGHIKLMNPQRSTVWY"                     # the residues in the order of a table's 20 match rows (gs_hmm_parse_mem)
 HMM_HAS_GA, HMM_HAS_TC, HMM_HAS_NC, HMM_HAS_STATS = 1, 2, 4, 8
 HMM_FWD_MAX_L, HMM_LSE_N, HMM_FLOOR_ALL = 65536, 5903, -(1 << 31) + 1
+HMM_VF_OVER = (1 << 31) - 1                         # vf of a record whose int16 cells overflow (SPEC 13.7): above every floor
 HMM_TRACE_MAX_L, HMM_DOM_WORDS = 65536, 8
 HMM_ENV_WORDS, HMM_ENV_LO, HMM_ENV_HI = 4, -156, -425
 HMM_N2_WORDS, HMM_N2_OMEGA = 4, -8192              # SPEC 13.5: corr, dom_bias, seg_raw, mass; 1024 log2(1 / 256)
@@ -206,6 +207,11 @@ SYMBOLS = {
     "gs_hmm_search_msv": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "gs_hmm_search_filtered_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "gs_hmm_search_filtered": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_search_vit16_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "gs_hmm_search_vit16": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "gs_hmm_db_tables16": (_i, [_vp, _u64, _vp, _u64]),
+    "gs_hmm_search_staged_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_search_staged": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gs_hmm_trace": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     "gs_hmm_trace_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp]),
     "gs_hmm_envelopes": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1239,6 +1239,64 @@ class HmmDb:
         check(self.ctx.L.gs_hmm_search_filtered_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), msv_floor_dev, vit_floor_dev, msv_out_dev,
                                                     vit_out_dev, fwd_out_dev))
 
+    def tables16(self, p):
+        """int16 [27][M + 1] of profile p (SPEC 13.7): h(x) = max(-32768, (x + 1) >> 1) of every word of tables(p), nodes 1..M read back from the device"""
+        tab = np.zeros((_lib.HMM_TABLE_ROWS, int(self.M[p]) + 1), np.int16)
+        check(self.ctx.L.gs_hmm_db_tables16(self.h, int(p), _p(tab), tab.size))
+        return tab
+
+    def search_vit16_packed(self, aa, rec_start, rec_len):
+        """residues as filter_aa_records() returns them -> int32 [n_rec, n_prof] vf, the packed int16 Viterbi filter score (SPEC 13.7): at least the
+        Viterbi score of the pair, HMM_VF_OVER where the int16 cells overflow, HMM_NO_SCORE for an empty record"""
+        held, recs = _recs(aa, rec_start, rec_len)
+        out = np.zeros((recs[3], len(self)), np.int32)
+        check(self.ctx.L.gs_hmm_search_vit16(self.ctx.h, self.h, *recs, _opt(out)))
+        return out
+
+    def search_vit16(self, records):
+        """records as search() takes them -> int32 [n_rec, n_prof] vf"""
+        return self.search_vit16_packed(*filter_aa_records([bytes(r) for r in records]))
+
+    def search_vit16_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, vf_out_dev):
+        check(self.ctx.L.gs_hmm_search_vit16_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), vf_out_dev))
+
+    def vf_floor(self, forward=False, filter_p=1e-3, cutoff=None):
+        """int32 [n_prof]: the floor of vf in a staged search (SPEC 13.7) - the lowest Viterbi score a later consumer looks at, so that the filter
+        changes no output: viterbi_floor(filter_p) when Forward runs behind it (filter_p=None leaves nothing to cut by: ValueError), else the
+        thresholds of `cutoff` when best hits are taken at one, else 0 - the score table lists raw >= 0"""
+        if forward:
+            if filter_p is None:
+                raise ValueError("prefilter 'vit16' cuts Forward by its Viterbi floor: filter_p=None leaves nothing to cut by")
+            return self.viterbi_floor(filter_p)
+        return np.zeros(len(self), np.int32) if cutoff is None else self.thresholds(cutoff)
+
+    def search_staged_packed(self, aa, rec_start, rec_len, vf_floor, msv=False, msv_p=0.02, msv_floor=None, forward=False, filter_p=1e-3, floor=None):
+        """residues as filter_aa_records() returns them -> (vf, vit), with msv=True (msv, vf, vit), with forward=True fwd behind them; int32 [n_rec, n_prof]
+        (SPEC 13.7): the MSV score of every pair, vf of every pair or - msv=True - of the pairs at or above the MSV floor, what search_packed() returns
+        for the pairs with vf >= vf_floor (int32 [n_prof], units; None: every pair that has a vf), and the Forward score behind that Viterbi matrix as
+        search_forward_packed() computes it; HMM_NO_SCORE for the pairs a stage did not run for"""
+        held, recs = _recs(aa, rec_start, rec_len)
+        mfl = self._floor(msv_p, msv_floor, msv=True) if msv else None
+        fl = self._floor(filter_p, floor) if forward else None
+        vfl = None if vf_floor is None else np.ascontiguousarray(vf_floor, dtype=np.int32)
+        if vfl is not None and vfl.shape != (len(self),):
+            raise ValueError("vf_floor: one int32 per profile")
+        new = lambda: np.zeros((recs[3], len(self)), np.int32)      # noqa: E731
+        m, vf, vit, fwd = new() if msv else None, new(), new(), new() if forward else None
+        check(self.ctx.L.gs_hmm_search_staged(self.ctx.h, self.h, *recs, 1 if msv else 0, _opt(mfl), _opt(vfl), _opt(fl), _opt(m), _opt(vf), _opt(vit), _opt(fwd)))
+        return ((m,) if msv else ()) + (vf, vit) + ((fwd,) if forward else ())
+
+    def search_staged(self, records, vf_floor, msv=False, msv_p=0.02, msv_floor=None, forward=False, filter_p=1e-3, floor=None):
+        """records as search() takes them -> what search_staged_packed() returns"""
+        return self.search_staged_packed(*filter_aa_records([bytes(r) for r in records]), vf_floor, msv=msv, msv_p=msv_p, msv_floor=msv_floor, forward=forward,
+                                         filter_p=filter_p, floor=floor)
+
+    def search_staged_dev(self, aa_dev, rec_start_dev, rec_len_dev, n_rec, use_msv, msv_floor_dev, vf_floor_dev, vit_floor_dev, msv_out_dev, vf_out_dev, vit_out_dev,
+                          fwd_out_dev):
+        """all device memory; a floor None: every pair, msv_out_dev / vf_out_dev None: that matrix is not wanted, fwd_out_dev None: no Forward pass"""
+        check(self.ctx.L.gs_hmm_search_staged_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), 1 if use_msv else 0, msv_floor_dev, vf_floor_dev,
+                                                  vit_floor_dev, msv_out_dev, vf_out_dev, vit_out_dev, fwd_out_dev))
+
     def trace_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_dom=8, max_block_cells=0):
         """SPEC 13.2: the domains of the Viterbi path of the pairs (pair_rec[j], pair_prof[j]), traced back on the device -> (int32 raw [n_pairs] as
         search_packed() gives it, uint32 n_dom [n_pairs] the true number of domains, int32 dom [n_pairs, max_dom, 8]: i_from, i_to, k_from, k_to (1-based,
@@ -1467,8 +1525,10 @@ def _as_hmm_db(hmm, ctx):
 
 
 def _check_prefilter(prefilter):
-    if prefilter is not None and prefilter != "msv":
-        raise ValueError("prefilter: None or 'msv'")
+    """-> (an MSV stage runs in front, the int16 Viterbi filter runs in front of Viterbi)"""
+    if prefilter not in (None, "msv", "vit16", "msv+vit16"):
+        raise ValueError("prefilter: None, 'msv', 'vit16' or 'msv+vit16'")
+    return prefilter in ("msv", "msv+vit16"), prefilter in ("vit16", "msv+vit16")
 
 
 def _alignment_text(db, ids, listed, residues_of, n_env, env, slots, cols):
@@ -1536,6 +1596,10 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     msv_p (HMMER's F1 = 0.02; None: every pair) - in all three target forms and with both scores. The returned matrix holds HMM_NO_SCORE for the pairs the
     filter left out, the table has rows only for pairs that passed, Z stays the number of records. A pair whose gapped alignment is good and whose
     ungapped diagonals are weak is lost: the filter's stated cost. prefilter=None: no prefilter.
+    prefilter="vit16" (SPEC 13.7): the packed int16 Viterbi score vf of every pair runs first and Viterbi (and Forward behind it) only for the pairs with vf at
+    or above the lowest Viterbi score the call looks at - 0, the table's raw >= 0, or the Viterbi floor of filter_p with score="forward" (filter_p=None
+    then leaves nothing to cut by: ValueError). vf is never below the Viterbi score, so the tables are those of prefilter=None byte for byte; the returned
+    matrix holds HMM_NO_SCORE for the pairs the filter left out. prefilter="msv+vit16": MSV first, vf for its survivors, the tables of prefilter="msv".
     bias=True (SPEC 13.5; score="forward" only, ValueError otherwise): the pairs with a Forward raw >= 0 get their posterior envelopes and the null2 bias
     correction on the device. The table gains a last column `bias` (%.2f bits of seq_bias); bits, evalue and pass_ga are those of the corrected score
     fwd - seq_bias, and the rows are sorted by it. The envelope table gains a last column `env_bias` and its env_bits are env_raw - dom_bias. The returned
@@ -1552,23 +1616,26 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
         raise ValueError("score: 'viterbi' or 'forward'")
     if bias and score != "forward":
         raise ValueError("bias=True corrects Forward scores: score='forward'")
-    _check_prefilter(prefilter)
+    pre_msv, pre_vit16 = _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
     fwd = score == "forward"
+    vf_floor = db.vf_floor(fwd, filter_p) if pre_vit16 else None
     dev = None
     if translate:
         dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd or envelopes is not None or alignments is not None, domains is not None), table)
         aa = rs = rl = None
         try:
             ids = dev.names()
-            scores = dev.search(db, fwd, filter_p, prefilter is not None, msv_p)
+            scores = dev.search(db, fwd, filter_p, pre_msv, msv_p, vf_floor)
         except Exception:
             dev.close()
             raise
     else:
         ids, seqs = _faa_records(faa)
         aa, rs, rl = filter_aa_records([bytes(q) for q in seqs])
-        if prefilter is not None:
+        if pre_vit16:
+            scores = db.search_staged_packed(aa, rs, rl, vf_floor, msv=pre_msv, msv_p=msv_p, forward=fwd, filter_p=filter_p)[-1]
+        elif pre_msv:
             scores = db.search_filtered_packed(aa, rs, rl, msv_p=msv_p, forward=fwd, filter_p=filter_p)[2 if fwd else 1]
         else:
             scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
@@ -1703,6 +1770,8 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
     inside the genome and the coordinates are the gene's, from its start codon through its stop codon. A called gene longer than the search takes raises
     ValueError and ends the call (translate=True drops and counts such an ORF; see hmmsearch).
     prefilter="msv" (SPEC 13.3): the best hits are taken among the pairs at or above the MSV floor of msv_p, as hmmsearch(prefilter="msv") scores them.
+    prefilter="vit16" (SPEC 13.7): Viterbi runs only for the pairs whose int16 score vf reaches the cutoff in units (score="forward": the Viterbi floor of
+    filter_p; filter_p=None: ValueError); vf is never below the Viterbi score, so the result is that of prefilter=None. "msv+vit16": that of "msv".
     bias=True (SPEC 13.5; score="forward" only, ValueError otherwise): every pair whose Forward raw reaches the cutoff gets its posterior envelopes and
     the null2 bias correction on the device, and the best hit per genome and profile is the record with the largest corrected score fwd - seq_bias at or
     above the cutoff (the lowest record on a tie) - the score the files' cutoffs were gathered on. A low-complexity protein that passes a cutoff on its
@@ -1713,17 +1782,20 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
         raise ValueError("region: 'protein', 'aligned', 'envelope' or 'alignment'")
     if bias and score != "forward":
         raise ValueError("bias=True corrects Forward scores: score='forward'")
-    _check_prefilter(prefilter)
+    pre_msv, pre_vit16 = _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
+    vf_floor = db.vf_floor(score == "forward", filter_p, cutoff) if pre_vit16 else None
     if translate:
-        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate, prefilter is not None,
-                                           msv_p, region == "envelope", bias, region == "alignment")
+        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate, pre_msv,
+                                           msv_p, region == "envelope", bias, region == "alignment", vf_floor)
     seqs, goff = [], [0]
     for path in faa_files:
         seqs.extend(_faa_records(path)[1])
         goff.append(len(seqs))
     aa, rs, rl = filter_aa_records([bytes(s) for s in seqs])
-    if prefilter is not None:
+    if pre_vit16:
+        scores = db.search_staged_packed(aa, rs, rl, vf_floor, msv=pre_msv, msv_p=msv_p, forward=score == "forward", filter_p=filter_p)[-1]
+    elif pre_msv:
         scores = db.search_filtered_packed(aa, rs, rl, msv_p=msv_p, forward=score == "forward", filter_p=filter_p)[2 if score == "forward" else 1]
     else:
         scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if score == "forward" else db.search_packed(aa, rs, rl)
@@ -1920,15 +1992,21 @@ class _DevOrfs:
             out.append(_orf_name(self.contig_ids[c], b, e, s))
         return out
 
-    def search_dev(self, db, fwd, filter_p, prefilter=False, msv_p=0.02):
+    def search_dev(self, db, fwd, filter_p, prefilter=False, msv_p=0.02, vf_floor=None):
         """device int32 [n, n_prof] scores of the ORFs (Forward behind the Viterbi floor when fwd; behind the MSV floor of msv_p when prefilter, SPEC
-        13.3); the caller frees through close()"""
+        13.3; behind the int16 filter at vf_floor when that is given, SPEC 13.7); the caller frees through close()"""
         d_score = self.mem.new(4 * self.n * len(db))
         if self.n == 0:
             return d_score
         with _DevScope(self.ctx) as t:                  # the floors and the Viterbi matrix of a Forward call live as long as the call
             up = lambda a: None if a is None else t.up(a)       # noqa: E731
-            if prefilter:
+            if vf_floor is not None:
+                d_mfl, d_fl = up(db._floor(msv_p, None, msv=True) if prefilter else None), up(db._floor(filter_p, None) if fwd else None)
+                d_vit = t.new(4 * self.n * len(db)) if fwd else d_score
+                db.search_staged_dev(self.d_aa, self.d_as, self.d_al, self.n, prefilter, d_mfl, up(np.ascontiguousarray(vf_floor, dtype=np.int32)), d_fl, None, None,
+                                     d_vit, d_score if fwd else None)
+                self.ctx.sync()
+            elif prefilter:
                 d_mfl, d_fl = up(db._floor(msv_p, None, msv=True)), up(db._floor(filter_p, None) if fwd else None)
                 d_vit = t.new(4 * self.n * len(db)) if fwd else d_score
                 db.search_filtered_dev(self.d_aa, self.d_as, self.d_al, self.n, d_mfl, d_fl, None, d_vit, d_score if fwd else None)
@@ -1940,8 +2018,8 @@ class _DevOrfs:
                 db.search_dev(self.d_aa, self.d_as, self.d_al, self.n, d_score)
         return d_score
 
-    def search(self, db, fwd, filter_p, prefilter=False, msv_p=0.02):
-        d_score = self.search_dev(db, fwd, filter_p, prefilter, msv_p)
+    def search(self, db, fwd, filter_p, prefilter=False, msv_p=0.02, vf_floor=None):
+        d_score = self.search_dev(db, fwd, filter_p, prefilter, msv_p, vf_floor)
         scores = self.ctx.download(d_score, (self.n, len(db)), np.int32)
         self.mem.free(d_score)
         return scores
@@ -2029,14 +2107,14 @@ class _DevOrfs:
 
 
 def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02, envelope=False, bias=False,
-                                alignment=False):
+                                alignment=False, vf_floor=None):
     ctx = db.ctx
     dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd or envelope or alignment, aligned), table)
     try:
         ng, npf = len(fna_files), len(db)
         rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
         if ng and npf and dev.n:
-            d_score = dev.search_dev(db, fwd, filter_p, prefilter, msv_p)
+            d_score = dev.search_dev(db, fwd, filter_p, prefilter, msv_p, vf_floor)
             if bias:
                 rec = _bias_best_hits(ctx.download(d_score, (dev.n, npf), np.int32), dev.genome_orf_off, db.thresholds(cutoff), lambda pr, pp: dev.bias_all(db, pr, pp)[4])
             else:

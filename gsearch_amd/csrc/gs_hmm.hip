@@ -1,7 +1,8 @@
 // gs_hmm.hip — hmmsearch (SPEC 13): HMMER3 profiles as integer tables, the local multihit Viterbi score of every (record, profile) pair on the
 // device, the Forward score (SPEC 13.1) of the pairs that pass a per-profile Viterbi floor, the best record per genome and profile, the domains of
 // the Viterbi path of a list of pairs, traced back on the device (SPEC 13.2), the Backward pass and posterior envelopes of a list of pairs
-// (SPEC 13.4), the null2 bias correction of those envelopes (SPEC 13.5) and their optimal-accuracy alignments (SPEC 13.6). Integers only from the file's digits to the raw score. The reader of profile files and the calls that touch no device are
+// (SPEC 13.4), the null2 bias correction of those envelopes (SPEC 13.5), their optimal-accuracy alignments (SPEC 13.6) and the packed int16 Viterbi
+// filter in front of the int32 program (SPEC 13.7). Integers only from the file's digits to the raw score. The reader of profile files and the calls that touch no device are
 // gs_hmm_parse.cpp, a host-only unit; the doubles of hmmsearch (bits, E-values, the table of lse, the Viterbi floor, the reported cutoffs) are all there.
 #include <math.h>
 #include <stdlib.h>
@@ -451,6 +452,183 @@ __global__ __launch_bounds__(HMM_BLOCK) void k_hmm_msv(const int32_t *__restrict
         const uint32_t r = order[j];
         const int32_t raw = hmm_msv_rows<Q>(ln, aa + rec_start[r], (uint32_t)rec_len[r]);
         if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = raw;
+    }
+}
+
+// ---- the packed int16 Viterbi filter (SPEC 13.7): vf >= vit, two nodes a register --------------------------------------------------------------------
+// The cells of SPEC 13 in half units (2^-9 bit) as int16, every cell operation a packed saturating add (v_pk_add_i16 clamp) or a packed max
+// (v_pk_max_i16); the specials stay int32 scalars in the units of SPEC 13 with E = 2 E16. The launch geometry, the class lists and the residue loads are
+// k_hmm_viterbi's; a class of Q nodes a lane runs with H = ceil(Q / 2) registers a state (classes 1 and 2 share an instance, 3 and 4 another).
+//   Layout: lane l holds the 2 H node slots from l 2 H on as two runs - slots l 2 H + r in the low halves of its registers r = 0 .. H - 1, slots
+//   l 2 H + H + r in the high halves. The move up one node is then a rename of registers and one combine at register 0: its low half takes the high
+//   half of the last register of the lane below, its high half the low half of the lane's own last register (one shuffle and one v_alignbit).
+//   D: both runs go from NEG16 in one packed chain (Dloc) and leave b_lo, b_hi. With tDD <= 0 and every M + tMD at least NEG16, the chain of
+//   saturating steps equals max(NEG16, wide sums) (SPEC 13.7), so the runs are joined on int32 scalars with the WIDE sums of tDD16 of a run (a_lo,
+//   a_hi): b = max(b_hi, b_lo + a_hi), the six scan steps of hmm_rows over the lanes, then what enters the low run (c_in) and the high run
+//   (max(b_lo, c_in + a_lo)) is carried along both runs by saturating steps - no PDD row, whose int16 form would clamp.
+//   The staged copy is made on the host in the order the lanes read it: register r of lane l lies at (r / B) 64 B + l B + r % B of its row of 64 H
+//   words, B = 4, 2 or 1 the largest of them that divides H, so a ds_read_b128 / b64 / b32 of all lanes reads contiguous bytes (the lesson of k_hmm_msv).
+//   Padding slots hold NEG16 in every row. The lower clamp is not sticky (NEG16 plus a positive entry is above NEG16), so a padding cell can rise:
+//   it feeds padding only, and the fold into E16 takes min(M, lim) with lim = NEG16 in the padding halves.
+//   The first row with E16 == 32767 ends the record's rows, for the whole wavefront (E16 is uniform); the bytes behind it are still looked at, since a
+//   byte that is no residue goes before an overflow.
+typedef short hmm_s2 __attribute__((ext_vector_type(2)));
+enum { HMM16_ROWS = 27, HMM16_NEG = -32768, HMM16_MAX = 32767 };
+static_assert(HMM16_ROWS == GS_HMM_TABLE_ROWS && HMM_ROW_DD == HMM16_ROWS - 1, "the int16 table has the rows of the host table");
+__host__ __device__ constexpr int hmm16_regs(int Q) { return (Q + 1) / 2; }
+__host__ __device__ constexpr int hmm16_block(int H) { return H % 4 == 0 ? 4 : (H % 2 == 0 ? 2 : 1); }
+__host__ __device__ constexpr int hmm16_at(int H, int r) { return (r / hmm16_block(H)) * 64 * hmm16_block(H) + r % hmm16_block(H); }
+// the word of a row that holds node slot j (node j + 1), and whether it is the word's high half
+__host__ __device__ constexpr int hmm16_word(int H, int j) { return (j / (2 * H)) * hmm16_block(H) + hmm16_at(H, j % H); }
+__host__ __device__ constexpr bool hmm16_high(int H, int j) { return j % (2 * H) >= H; }
+static_assert((size_t)HMM16_ROWS * 64 * hmm16_regs(HMM_CLASS_Q[HMM_CLASSES - 1]) * 4 <= 160 * 1024 / 2, "two workgroups of the largest class fit the LDS of a CU");
+// h of SPEC 13.7: the ceiling of x / 2, kept inside int16
+__host__ __device__ inline int32_t hmm16_half(int32_t x)
+{
+    const int32_t h = (x + 1) >> 1;
+    return h < HMM16_NEG ? HMM16_NEG : (h > HMM16_MAX ? HMM16_MAX : h);
+}
+__device__ __forceinline__ hmm_s2 hmm16_add(hmm_s2 a, hmm_s2 b) { return __builtin_elementwise_add_sat(a, b); }
+__device__ __forceinline__ hmm_s2 hmm16_max(hmm_s2 a, hmm_s2 b) { return __builtin_elementwise_max(a, b); }
+
+template <int H> struct Hmm16Lane {
+    const hmm_s2 *row0;                                     // the lane's first word of table row 0 in LDS: register r of row w at row0[w * 64 H + hmm16_at(H, r)]
+    hmm_s2 lim[H];                                          // 32767 in the halves that are nodes of the profile, NEG16 in the padding
+    int32_t a_step[6], a_lo, a_hi, tbm;                     // wide sums of tDD16: of the lanes a scan step joins, of the lane's low and high run
+    int lane, wave;
+};
+template <int H>
+__device__ __forceinline__ Hmm16Lane<H> hmm16_stage(const int32_t *tables16, const HmmDesc d)
+{
+    extern __shared__ int4 hmm16_lds[];                     // (int4: the blocks of four are read as ds_read_b128)
+    int32_t *lds = (int32_t *)hmm16_lds;
+    constexpr int RW = 64 * H;
+    for (int i = (int)threadIdx.x; i < HMM16_ROWS * RW; i += HMM_BLOCK) lds[i] = tables16[d.off + i];
+    __syncthreads();
+    Hmm16Lane<H> ln;
+    ln.lane = (int)threadIdx.x & 63; ln.wave = (int)threadIdx.x >> 6;
+    ln.tbm = d.tbm;
+    ln.row0 = (const hmm_s2 *)lds + ln.lane * hmm16_block(H);
+    const hmm_s2 *tDD = ln.row0 + HMM_ROW_DD * RW;
+    ln.a_lo = ln.a_hi = 0;
+#pragma unroll
+    for (int r = 0; r < H; r++) {
+        const int slot = ln.lane * 2 * H + r;
+        ln.lim[r] = hmm_s2{(short)(slot < (int)d.M ? HMM16_MAX : HMM16_NEG), (short)(slot + H < (int)d.M ? HMM16_MAX : HMM16_NEG)};
+        const hmm_s2 t = tDD[hmm16_at(H, r)];
+        ln.a_lo += t.x; ln.a_hi += t.y;
+    }
+    int32_t a = ln.a_lo + ln.a_hi;                          // at least 1280 * NEG16: far inside int32
+    for (int s = 0; s < 6; s++) {
+        ln.a_step[s] = a;
+        const int32_t up = __shfl_up(a, 1 << s);
+        if (ln.lane >= (1 << s)) a += up;
+    }
+    return ln;
+}
+
+// The rows of one record against the staged int16 profile: vf in every lane - GS_HMM_NO_SCORE for an empty record or a byte that is no residue, else
+// GS_HMM_VF_OVER from the first row whose E16 is 32767
+template <int H>
+__device__ __forceinline__ int32_t hmm16_rows(const Hmm16Lane<H> &ln, const uint8_t *x, uint32_t L)
+{
+    constexpr int RW = 64 * H;
+    const int lane = ln.lane;
+    if (L == 0) return GS_HMM_NO_SCORE;
+    const HmmSpecials sp = hmm_specials(L);
+    const hmm_s2 NEG2 = {(short)HMM16_NEG, (short)HMM16_NEG};
+    const hmm_s2 *tMM = ln.row0 + HMM_ROW_MM * RW, *tMI = ln.row0 + HMM_ROW_MI * RW, *tMD = ln.row0 + HMM_ROW_MD * RW, *tIM = ln.row0 + HMM_ROW_IM * RW,
+                 *tII = ln.row0 + HMM_ROW_II * RW, *tDM = ln.row0 + HMM_ROW_DM * RW, *tDD = ln.row0 + HMM_ROW_DD * RW;
+    hmm_s2 Mv[H], Iv[H], Dv[H];
+#pragma unroll
+    for (int r = 0; r < H; r++) Mv[r] = Iv[r] = Dv[r] = NEG2;
+    int32_t J = GS_HMM_NEG, C = GS_HMM_NEG, B = sp.tmove, N = 0;
+    bool bad = false, over = false;
+    int cur = (uint32_t)lane < L ? hmm_residue(x[lane]) : 0;
+    for (uint32_t i0 = 0; i0 < L; i0 += 64) {
+        const int nxt = i0 + 64 + (uint32_t)lane < L ? hmm_residue(x[i0 + 64 + lane]) : 0;     // the next 64 residues are on their way while these run
+        bad |= cur < 0;
+        const int res = max(cur, 0);
+        const int cnt = over ? 0 : (int)min(64u, L - i0);         // behind an overflow only the bytes are looked at
+        for (int t = 0; t < cnt; t++) {
+            const hmm_s2 *ms = ln.row0 + __builtin_amdgcn_readlane(res, t) * RW;
+            const short ent16 = (short)hmm16_half(B + ln.tbm);
+            const hmm_s2 ent = {ent16, ent16};
+            hmm_s2 give[H];
+#pragma unroll
+            for (int r = 0; r < H; r++)
+                give[r] = hmm16_max(hmm16_max(hmm16_add(Mv[r], tMM[hmm16_at(H, r)]), hmm16_add(Iv[r], tIM[hmm16_at(H, r)])), hmm16_add(Dv[r], tDM[hmm16_at(H, r)]));
+            const uint32_t gl = __builtin_bit_cast(uint32_t, give[H - 1]);
+            uint32_t up = (uint32_t)__shfl_up((int)gl, 1);
+            if (lane == 0) up = 0x80000000u;                      // node 0 has no states: NEG16 enters node 1
+            const hmm_s2 in0 = __builtin_bit_cast(hmm_s2, __builtin_amdgcn_alignbit(gl, up, 16));        // {high half of the lane below, own low half}
+#pragma unroll
+            for (int r = 0; r < H; r++) Iv[r] = hmm16_max(hmm16_add(Mv[r], tMI[hmm16_at(H, r)]), hmm16_add(Iv[r], tII[hmm16_at(H, r)]));
+#pragma unroll
+            for (int r = 0; r < H; r++) Mv[r] = hmm16_add(ms[hmm16_at(H, r)], hmm16_max(r ? give[r - 1] : in0, ent));
+            hmm_s2 dl = NEG2;
+            Dv[0] = dl;
+#pragma unroll
+            for (int r = 1; r < H; r++) { dl = hmm16_max(hmm16_add(dl, tDD[hmm16_at(H, r - 1)]), hmm16_add(Mv[r - 1], tMD[hmm16_at(H, r - 1)])); Dv[r] = dl; }
+            const hmm_s2 bo = hmm16_max(hmm16_add(dl, tDD[hmm16_at(H, H - 1)]), hmm16_add(Mv[H - 1], tMD[hmm16_at(H, H - 1)]));
+            const int32_t b_lo = bo.x;
+            int32_t b = max((int32_t)bo.y, b_lo + ln.a_hi);
+#pragma unroll
+            for (int s = 0; s < 6; s++) b = max(b, __shfl_up(b, 1 << s) + ln.a_step[s]);      // a lane below 2^s gets its own b back (b + a <= b)
+            int32_t c_in = __shfl_up(b, 1);
+            if (lane == 0) c_in = HMM16_NEG;
+            hmm_s2 carry = {(short)c_in, (short)max(b_lo, c_in + ln.a_lo)};                   // both inside int16: each is some b, or NEG16
+            hmm_s2 e = NEG2;
+#pragma unroll
+            for (int r = 0; r < H; r++) {
+                Dv[r] = hmm16_max(Dv[r], carry);
+                if (r + 1 < H) carry = hmm16_add(carry, tDD[hmm16_at(H, r)]);
+                e = hmm16_max(e, __builtin_elementwise_min(Mv[r], ln.lim[r]));
+            }
+            const int32_t E16 = hmm_wave_join<HMM_VIT>(max((int)e.x, (int)e.y), nullptr);
+            if (E16 == HMM16_MAX) { over = true; break; }
+            const int32_t E = 2 * E16;
+            N += sp.tloop;
+            J = max(max(J + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
+            C = max(max(C + sp.tloop, E + GS_HMM_TEJ), GS_HMM_NEG);
+            B = max(N, J) + sp.tmove;
+        }
+        cur = nxt;
+    }
+    return __any(bad) ? GS_HMM_NO_SCORE : (over ? GS_HMM_VF_OVER : C + sp.tmove - sp.null);
+}
+
+// vf of every record against the profiles plist[] of one class; the arguments of k_hmm_viterbi, with the int16 tables and their descriptors
+template <int H>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_vit16(const int32_t *__restrict__ tables16, const HmmDesc *__restrict__ desc16, const uint32_t *__restrict__ plist,
+                                                         const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                         const uint32_t *__restrict__ order, uint32_t n_rec, uint32_t n_prof, int32_t *__restrict__ score)
+{
+    const uint32_t p = plist[blockIdx.y];
+    const Hmm16Lane<H> ln = hmm16_stage<H>(tables16, desc16[p]);
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < n_rec; j += gridDim.x * HMM_WAVES) {
+        const uint32_t r = order[j];
+        const int32_t vf = hmm16_rows<H>(ln, aa + rec_start[r], (uint32_t)rec_len[r]);
+        if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = vf;
+    }
+}
+
+// vf of the records sel[p][0 .. sel_cnt[p]) of each profile of plist[]; the arguments of k_hmm_viterbi_sel, and its rule for the other words of `score`
+template <int H>
+__global__ __launch_bounds__(HMM_BLOCK) void k_hmm_vit16_sel(const int32_t *__restrict__ tables16, const HmmDesc *__restrict__ desc16, const uint32_t *__restrict__ plist,
+                                                             const uint8_t *__restrict__ aa, const uint64_t *__restrict__ rec_start, const uint64_t *__restrict__ rec_len,
+                                                             const uint32_t *__restrict__ sel, const uint32_t *__restrict__ sel_cnt, uint32_t n_rec, uint32_t n_prof,
+                                                             int32_t *__restrict__ score)
+{
+    const uint32_t p = plist[blockIdx.y];
+    const uint32_t cnt = min(sel_cnt[p], n_rec);
+    if ((uint64_t)blockIdx.x * HMM_WAVES >= cnt) return;
+    const Hmm16Lane<H> ln = hmm16_stage<H>(tables16, desc16[p]);
+    const uint32_t *list = sel + (uint64_t)p * n_rec;
+    for (uint32_t j = blockIdx.x * HMM_WAVES + (uint32_t)ln.wave; j < cnt; j += gridDim.x * HMM_WAVES) {
+        const uint32_t r = list[j];
+        const int32_t vf = hmm16_rows<H>(ln, aa + rec_start[r], (uint32_t)rec_len[r]);
+        if (ln.lane == 0) score[(uint64_t)r * n_prof + p] = vf;
     }
 }
 
@@ -1236,21 +1414,25 @@ struct HmmKernels {
     decltype(&k_hmm_viterbi<1>) vit; decltype(&k_hmm_forward<1>) fwd; decltype(&k_hmm_trace<1>) trace; decltype(&k_hmm_msv<1>) msv; decltype(&k_hmm_viterbi_sel<1>) vit_sel;
     decltype(&k_hmm_forward_rows<1>) fwd_rows; decltype(&k_hmm_backward<1>) back; decltype(&k_hmm_env_score<1>) env_score;
     decltype(&k_hmm_n2_forward<1>) n2_fwd; decltype(&k_hmm_n2_backward<1>) n2_back; decltype(&k_hmm_ali_backward<1>) ali_back; decltype(&k_hmm_ali_rows<1>) ali_rows;
+    decltype(&k_hmm_vit16<1>) vit16; decltype(&k_hmm_vit16_sel<1>) vit16_sel;      // (instances by registers a state: two classes can share one)
 };
 template <size_t... I> static const HmmKernels &hmm_kernels(int cls, std::index_sequence<I...>)
 {
     static const HmmKernels of_class[] = {{k_hmm_viterbi<HMM_CLASS_Q[I]>, k_hmm_forward<HMM_CLASS_Q[I]>, k_hmm_trace<HMM_CLASS_Q[I]>, k_hmm_msv<HMM_CLASS_Q[I]>,
                                            k_hmm_viterbi_sel<HMM_CLASS_Q[I]>, k_hmm_forward_rows<HMM_CLASS_Q[I]>, k_hmm_backward<HMM_CLASS_Q[I]>,
                                            k_hmm_env_score<HMM_CLASS_Q[I]>, k_hmm_n2_forward<HMM_CLASS_Q[I]>, k_hmm_n2_backward<HMM_CLASS_Q[I]>,
-                                           k_hmm_ali_backward<HMM_CLASS_Q[I]>, k_hmm_ali_rows<HMM_CLASS_Q[I]>}...};
+                                           k_hmm_ali_backward<HMM_CLASS_Q[I]>, k_hmm_ali_rows<HMM_CLASS_Q[I]>,
+                                           k_hmm_vit16<hmm16_regs(HMM_CLASS_Q[I])>, k_hmm_vit16_sel<hmm16_regs(HMM_CLASS_Q[I])>}...};
     return of_class[cls];
 }
 static const HmmKernels &hmm_kernels(int cls) { return hmm_kernels(cls, std::make_index_sequence<HMM_CLASSES>()); }
 static size_t hmm_lds_bytes(int cls, HmmProg prog) { return (size_t)HMM_ROWS_DEV * 64 * HMM_CLASS_Q[cls] * 4 + (prog == HMM_FWD || prog == HMM_FWD_ROWS ? HMM_LSE_LDS_BYTES : 0); }
 static size_t hmm_msv_lds_bytes(int cls) { return (size_t)HMM_MSV_ROWS * 64 * HMM_CLASS_Q[cls] * 4; }
+static size_t hmm16_lds_bytes(int cls) { return (size_t)HMM16_ROWS * 64 * hmm16_regs(HMM_CLASS_Q[cls]) * 4; }
 static size_t hmm_ali_lds_bytes(int cls) { return ((size_t)HMM_ALI_MASK_ROWS * 64 * HMM_CLASS_Q[cls] + GS_HMM_EXP2_N) * 4; }
-// which kernel a (kernel, class) flag of the profile set belongs to: the three programs of hmm_rows, then MSV and Viterbi over a selected list
-enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_K_BACK, HMM_K_ENV_SCORE, HMM_K_N2_BACK, HMM_K_ALI_BACK, HMM_K_ALI_ROWS, HMM_KERNEL_KINDS };
+// which kernel a (kernel, class) flag of the profile set belongs to: the three programs of hmm_rows, then MSV and Viterbi over a selected list, ...,
+// the int16 filter over all records and over a selected list
+enum { HMM_K_MSV = HMM_PROGS, HMM_K_VIT_SEL, HMM_K_BACK, HMM_K_ENV_SCORE, HMM_K_N2_BACK, HMM_K_ALI_BACK, HMM_K_ALI_ROWS, HMM_K_VIT16, HMM_K_VIT16_SEL, HMM_KERNEL_KINDS };
 
 }  // namespace gs
 
@@ -1262,7 +1444,8 @@ struct gs_hmm_db {
     uint32_t class_start[gs::HMM_CLASSES + 1] = {};
     bool all_ga = true;
     bool lds_set[gs::HMM_KERNEL_KINDS][gs::HMM_CLASSES] = {};
-    gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse, d_exp2;
+    std::vector<gs::HmmDesc> desc16;                // the int16 tables (SPEC 13.7): off in words of d_tables16
+    gs::DevBuf d_tables, d_desc, d_plist, d_ga, d_lse, d_exp2, d_tables16, d_desc16;
 };
 
 namespace gs {
@@ -1293,6 +1476,7 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
     db->models = std::move(models);
     const size_t np = db->models.size();
     std::vector<int32_t> words, ga(np, 0);
+    std::vector<uint32_t> words16;                  // the int16 tables, two node slots a word in the order the lanes of k_hmm_vit16 read them
     std::vector<std::vector<uint32_t>> by_class(HMM_CLASSES);
     for (size_t p = 0; p < np; p++) {
         const HmmModel &m = db->models[p];
@@ -1307,6 +1491,16 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
         for (int j = 0; j < MP; j++)
             words[at + (size_t)HMM_ROW_PDD * MP + j] = j % Q == 0 ? 0 : words[at + (size_t)HMM_ROW_PDD * MP + j - 1] + words[at + (size_t)HMM_ROW_DD * MP + j - 1];
         if (m.info.flags & GS_HMM_HAS_GA) ga[p] = m.info.ga_units; else db->all_ga = false;
+        const int H = hmm16_regs(Q), RW = 64 * H;
+        const size_t at16 = words16.size();
+        db->desc16.push_back(HmmDesc{(uint64_t)at16, M, m.info.tbm});
+        words16.resize(at16 + (size_t)HMM16_ROWS * RW, 0x80008000u);           // NEG16 in both halves
+        for (int row = 0; row < HMM16_ROWS; row++)
+            for (uint32_t k = 1; k <= M; k++) {
+                uint32_t &w = words16[at16 + (size_t)row * RW + hmm16_word(H, (int)k - 1)];
+                const uint32_t v = (uint32_t)hmm16_half(m.tab[(size_t)row * W + k]) & 0xFFFFu;
+                w = hmm16_high(H, (int)k - 1) ? (w & 0x0000FFFFu) | (v << 16) : (w & 0xFFFF0000u) | v;
+            }
     }
     for (int cls = 0; cls < HMM_CLASSES; cls++) {
         db->class_start[cls] = (uint32_t)db->plist.size();
@@ -1316,7 +1510,10 @@ static int hmm_db_build(gs_ctx *c, std::vector<HmmModel> &&models, gs_hmm_db **o
     GS_CTX_LOCK(c);
     int rc;
     if ((rc = db->d_tables.alloc(4 * words.size())) || (rc = db->d_desc.alloc(sizeof(HmmDesc) * np)) || (rc = db->d_plist.alloc(4 * np)) || (rc = db->d_ga.alloc(4 * np)) ||
-        (rc = db->d_lse.alloc(HMM_LSE_LDS_BYTES)) || (rc = db->d_exp2.alloc(4 * GS_HMM_EXP2_N))) return rc;
+        (rc = db->d_lse.alloc(HMM_LSE_LDS_BYTES)) || (rc = db->d_exp2.alloc(4 * GS_HMM_EXP2_N)) || (rc = db->d_tables16.alloc(4 * words16.size())) ||
+        (rc = db->d_desc16.alloc(sizeof(HmmDesc) * np))) return rc;
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_tables16.p, words16.data(), 4 * words16.size(), hipMemcpyHostToDevice, c->stream));
+    GS_HIP_CHECK(hipMemcpyAsync(db->d_desc16.p, db->desc16.data(), sizeof(HmmDesc) * np, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_tables.p, words.data(), 4 * words.size(), hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_desc.p, db->desc.data(), sizeof(HmmDesc) * np, hipMemcpyHostToDevice, c->stream));
     GS_HIP_CHECK(hipMemcpyAsync(db->d_plist.p, db->plist.data(), 4 * np, hipMemcpyHostToDevice, c->stream));
@@ -1424,7 +1621,8 @@ static void hmm_lock(gs_ctx *c, HmmLock &lock) { lock = HmmLock(c->mu); (void)hi
 
 // R: the records of the call; everything else device memory. Queued on c's stream; the order list lives in its slot until the caller's scope ends.
 // msv: the MSV score (SPEC 13.3) of every pair in the place of its Viterbi score - the same launches with k_hmm_msv and its smaller LDS.
-static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, int32_t *score_dev, PoolBuf &d_order, bool msv = false)
+// vit16: vf (SPEC 13.7) in that place - the same launches with k_hmm_vit16 over the int16 tables.
+static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, int32_t *score_dev, PoolBuf &d_order, bool msv = false, bool vit16 = false)
 {
     const uint32_t np = (uint32_t)db->models.size();
     const uint64_t n_rec = R.n_rec, *lens = R.lens;
@@ -1436,10 +1634,12 @@ static int hmm_search_impl(gs_ctx *c, gs_hmm_db *db, const HmmRecs &R, int32_t *
     GS_HIP_CHECK(hipMemcpyAsync(d_order.p, order.data(), 4 * n_rec, hipMemcpyHostToDevice, c->stream));
     const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
     for (int cls = 0; cls < HMM_CLASSES; cls++) {
-        const auto k = msv ? hmm_kernels(cls).msv : hmm_kernels(cls).vit;
-        const size_t lds = msv ? hmm_msv_lds_bytes(cls) : hmm_lds_bytes(cls, HMM_VIT);
-        rc = hmm_launch_class(c, db->lds_set[msv ? HMM_K_MSV : HMM_VIT][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
-            k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, R.aa, R.rs, R.rl,
+        const auto k = vit16 ? hmm_kernels(cls).vit16 : (msv ? hmm_kernels(cls).msv : hmm_kernels(cls).vit);
+        const size_t lds = vit16 ? hmm16_lds_bytes(cls) : (msv ? hmm_msv_lds_bytes(cls) : hmm_lds_bytes(cls, HMM_VIT));
+        const int32_t *tables = vit16 ? db->d_tables16.as<int32_t>() : db->d_tables.as<int32_t>();
+        const HmmDesc *desc = vit16 ? db->d_desc16.as<HmmDesc>() : db->d_desc.as<HmmDesc>();
+        rc = hmm_launch_class(c, db->lds_set[vit16 ? HMM_K_VIT16 : (msv ? HMM_K_MSV : HMM_VIT)][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
+            k<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, db->d_plist.as<uint32_t>() + first, R.aa, R.rs, R.rl,
                                                    d_order.as<uint32_t>(), (uint32_t)n_rec, np, score_dev);
         });
         if (rc) return rc;
@@ -1454,9 +1654,10 @@ struct HmmLists {
     explicit HmmLists(gs_ctx *c) : order(c, SL_HMM_ORDER), sel(c, SL_HMM_SEL), cnt(c, SL_HMM_SEL_COUNT) {}
 };
 // One program over the pairs another score selects: out_dev filled with GS_HMM_NO_SCORE, per profile the list of the records whose in_dev reaches
-// floor_dev (nullptr: every pair that has a score there), then prog - HMM_FWD: k_hmm_forward, HMM_VIT: k_hmm_viterbi_sel - over those lists into out_dev.
+// floor_dev (nullptr: every pair that has a score there), then prog - HMM_FWD: k_hmm_forward, HMM_VIT: k_hmm_viterbi_sel, HMM_K_VIT16_SEL: k_hmm_vit16_sel -
+// over those lists into out_dev.
 // Queued on c's stream.
-static int hmm_selected_pass(gs_ctx *c, gs_hmm_db *db, HmmProg prog, const HmmRecs &R, const int32_t *in_dev, const int32_t *floor_dev, int32_t *out_dev, HmmLists &l)
+static int hmm_selected_pass(gs_ctx *c, gs_hmm_db *db, int prog, const HmmRecs &R, const int32_t *in_dev, const int32_t *floor_dev, int32_t *out_dev, HmmLists &l)
 {
     const uint32_t np = (uint32_t)db->models.size();
     const uint64_t n_rec = R.n_rec;
@@ -1477,13 +1678,17 @@ static int hmm_selected_pass(gs_ctx *c, gs_hmm_db *db, HmmProg prog, const HmmRe
     const uint32_t wg = (uint32_t)std::min<uint64_t>((n_rec + HMM_WAVES - 1) / HMM_WAVES, HMM_MAX_WG_PER_PROFILE);
     for (int cls = 0; cls < HMM_CLASSES; cls++) {
         // the two programs differ in the kernel, its LDS, its flag and the table of lse that Forward takes behind the profile list
+        const bool v16 = prog == HMM_K_VIT16_SEL;
+        const int32_t *tables = v16 ? db->d_tables16.as<int32_t>() : db->d_tables.as<int32_t>();
+        const HmmDesc *desc = v16 ? db->d_desc16.as<HmmDesc>() : db->d_desc.as<HmmDesc>();
         auto run = [&](auto k, int kind, size_t lds, auto... lse) {
             return hmm_launch_class(c, db->lds_set[kind][cls], k, db->class_start[cls], db->class_start[cls + 1] - db->class_start[cls], wg, lds, [&](dim3 grid, uint32_t first) {
-                k<<<grid, HMM_BLOCK, lds, c->stream>>>(db->d_tables.as<int32_t>(), db->d_desc.as<HmmDesc>(), db->d_plist.as<uint32_t>() + first, lse..., R.aa, R.rs, R.rl,
+                k<<<grid, HMM_BLOCK, lds, c->stream>>>(tables, desc, db->d_plist.as<uint32_t>() + first, lse..., R.aa, R.rs, R.rl,
                                                        l.sel.as<uint32_t>(), l.cnt.as<uint32_t>(), (uint32_t)n_rec, np, out_dev);
             });
         };
         rc = prog == HMM_FWD ? run(hmm_kernels(cls).fwd, HMM_FWD, hmm_lds_bytes(cls, HMM_FWD), db->d_lse.as<uint16_t>())
+             : v16           ? run(hmm_kernels(cls).vit16_sel, HMM_K_VIT16_SEL, hmm16_lds_bytes(cls))
                              : run(hmm_kernels(cls).vit_sel, HMM_K_VIT_SEL, hmm_lds_bytes(cls, HMM_VIT));
         if (rc) return rc;
     }
@@ -1977,6 +2182,46 @@ static int hmm_scores_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, bool run_m
     return in.host || select_vit || fwd_out ? hmm_fetch(c, {&msv, &vit, &fwd}) : GS_OK;       // (hmm_search_impl has waited, a selected pass is still queued)
 }
 
+// gs_hmm_search_vit16 (run_vit false: vf of every pair, SPEC 13.7) and gs_hmm_search_staged: MSV of every pair if use_msv, vf of every pair or of the
+// pairs at or above msv_floor, Viterbi (k_hmm_viterbi_sel) of the pairs with vf >= vf_floor and, with fwd_out, Forward behind vit_floor as before.
+static int hmm_staged_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, bool use_msv, bool run_vit, const int32_t *msv_floor, const int32_t *vf_floor,
+                           const int32_t *vit_floor, int32_t *msv_out, int32_t *vf_out, int32_t *vit_out, int32_t *fwd_out, const void *needed)
+{
+    GS_REQUIRE(c && db && db->ctx == c, GS_ERR_INVALID, "hmm: null argument, or a profile set of another context");
+    if (in.n_rec == 0) return GS_OK;
+    GS_REQUIRE(in.given() && needed, GS_ERR_INVALID, "null argument");
+    GS_REQUIRE(in.n_rec < (1ull << 32), GS_ERR_UNSUPPORTED, "hmm: 2^32 records or more in one call");
+    const uint32_t max_l = fwd_out ? GS_HMM_FWD_MAX_L : GS_HMM_MAX_L;
+    const uint64_t np = db->models.size(), n_bytes = 4 * in.n_rec * np;
+    HmmLock lock;
+    HmmRecs R(c); HmmArg mfloor(c, SL_HMMB_MSV_FLOOR), vffloor(c, SL_HMMB_VF_FLOOR), floor(c, SL_HMMB_FLOOR), msv(c, SL_HMM_MSV), vf(c, SL_HMM_VF), vit(c, SL_HMM_VIT),
+        fwd(c, SL_HMM_FWD);
+    HmmLists l(c);
+    int rc;
+    if (in.host) {
+        if ((rc = hmm_check_lens(in.rl, in.n_rec, max_l))) return rc;
+        uint64_t aa_bytes = 0;
+        for (uint64_t r = 0; r < in.n_rec; r++) if (in.rl[r]) aa_bytes = std::max(aa_bytes, in.rs[r] + in.rl[r]);
+        hmm_lock(c, lock);
+        if ((rc = R.fill(in, aa_bytes))) return rc;
+    } else {
+        hmm_lock(c, lock);
+        if ((rc = R.fill(in, 0)) || (rc = hmm_check_lens(R.lens, in.n_rec, max_l))) return rc;
+    }
+    if ((use_msv && (rc = msv.bind(in.host, msv_out, n_bytes, HMM_DOWN))) || (rc = vf.bind(in.host, vf_out, n_bytes, HMM_DOWN)) ||
+        (run_vit && (rc = vit.bind(in.host, vit_out, n_bytes, HMM_DOWN))) || (fwd_out && (rc = fwd.bind(in.host, fwd_out, n_bytes, HMM_DOWN))) ||
+        (use_msv && msv_floor && (rc = mfloor.bind(in.host, msv_floor, 4 * np, HMM_UP))) || (run_vit && vf_floor && (rc = vffloor.bind(in.host, vf_floor, 4 * np, HMM_UP))) ||
+        (fwd_out && vit_floor && (rc = floor.bind(in.host, vit_floor, 4 * np, HMM_UP))))
+        return rc;
+    if ((use_msv && ((rc = hmm_search_impl(c, db, R, msv.as<int32_t>(), l.order, true)) ||
+                     (rc = hmm_selected_pass(c, db, HMM_K_VIT16_SEL, R, msv.as<int32_t>(), mfloor.as<int32_t>(), vf.as<int32_t>(), l)))) ||
+        (!use_msv && (rc = hmm_search_impl(c, db, R, vf.as<int32_t>(), l.order, false, true))) ||
+        (run_vit && (rc = hmm_selected_pass(c, db, HMM_VIT, R, vf.as<int32_t>(), vffloor.as<int32_t>(), vit.as<int32_t>(), l))) ||
+        (fwd_out && (rc = hmm_selected_pass(c, db, HMM_FWD, R, vit.as<int32_t>(), floor.as<int32_t>(), fwd.as<int32_t>(), l))))
+        return rc;
+    return in.host || use_msv || run_vit ? hmm_fetch(c, {&msv, &vf, &vit, &fwd}) : GS_OK;       // (hmm_search_impl has waited, a selected pass is still queued)
+}
+
 // gs_hmm_trace{,_dev}
 static int hmm_trace_form(gs_ctx *c, gs_hmm_db *db, const HmmIn &in, const uint32_t *pair_rec, const uint32_t *pair_prof, uint64_t n_pairs, uint32_t max_dom,
                           uint64_t max_block_cells, int32_t *raw_out, uint32_t *n_dom_out, int32_t *dom_out)
@@ -2200,6 +2445,29 @@ int gs_hmm_db_tables(gs_hmm_db *db, uint64_t p, int32_t *tables_out, uint64_t ca
     return GS_OK;
 }
 
+int gs_hmm_db_tables16(gs_hmm_db *db, uint64_t p, int16_t *tables_out, uint64_t cap_words)
+{
+    using namespace gs;
+    GS_REQUIRE(db && tables_out && p < db->models.size(), GS_ERR_INVALID, "bad argument");
+    const HmmModel &m = db->models[p];
+    const uint32_t M = m.info.M, W = M + 1;
+    GS_REQUIRE(cap_words >= (uint64_t)GS_HMM_TABLE_ROWS * W, GS_ERR_INVALID, "hmm: the table needs %llu words", (unsigned long long)GS_HMM_TABLE_ROWS * W);
+    gs_ctx *c = db->ctx;
+    GS_CTX_LOCK(c);
+    const int H = hmm16_regs(HMM_CLASS_Q[hmm_class_of(M)]), RW = 64 * H;
+    std::vector<uint32_t> dev((size_t)HMM16_ROWS * RW);
+    GS_HIP_CHECK(hipMemcpyAsync(dev.data(), db->d_tables16.as<uint32_t>() + db->desc16[p].off, 4 * dev.size(), hipMemcpyDeviceToHost, c->stream));
+    GS_HIP_CHECK(stream_wait(c));
+    for (uint32_t row = 0; row < GS_HMM_TABLE_ROWS; row++) {
+        tables_out[(size_t)row * W] = (int16_t)hmm16_half(m.tab[(size_t)row * W]);           // node 0 is not on the device (SPEC 13)
+        for (uint32_t k = 1; k <= M; k++) {
+            const uint32_t w = dev[(size_t)row * RW + hmm16_word(H, (int)k - 1)];
+            tables_out[(size_t)row * W + k] = (int16_t)(hmm16_high(H, (int)k - 1) ? w >> 16 : w & 0xFFFFu);
+        }
+    }
+    return GS_OK;
+}
+
 int gs_hmm_db_consensus(gs_hmm_db *db, uint64_t p, char *out, uint64_t cap)
 {
     using namespace gs;
@@ -2282,6 +2550,27 @@ int gs_hmm_search_filtered(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const ui
                            const int32_t *vit_floor, int32_t *msv_out, int32_t *vit_out, int32_t *fwd_out)
 {
     return gs::hmm_scores_form(c, db, {true, aa, rec_start, rec_len, n_rec}, true, true, msv_floor, vit_floor, msv_out, vit_out, fwd_out, vit_out);
+}
+
+int gs_hmm_search_vit16_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int32_t *vf_out_dev)
+{
+    return gs::hmm_staged_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, false, false, nullptr, nullptr, nullptr, nullptr, vf_out_dev, nullptr, nullptr, vf_out_dev);
+}
+int gs_hmm_search_vit16(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *vf_out)
+{
+    return gs::hmm_staged_form(c, db, {true, aa, rec_start, rec_len, n_rec}, false, false, nullptr, nullptr, nullptr, nullptr, vf_out, nullptr, nullptr, vf_out);
+}
+int gs_hmm_search_staged_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec, int use_msv,
+                             const int32_t *msv_floor_dev, const int32_t *vf_floor_dev, const int32_t *vit_floor_dev, int32_t *msv_out_dev, int32_t *vf_out_dev,
+                             int32_t *vit_out_dev, int32_t *fwd_out_dev)
+{
+    return gs::hmm_staged_form(c, db, {false, aa_dev, rec_start_dev, rec_len_dev, n_rec}, use_msv != 0, true, msv_floor_dev, vf_floor_dev, vit_floor_dev, msv_out_dev, vf_out_dev,
+                               vit_out_dev, fwd_out_dev, vit_out_dev);
+}
+int gs_hmm_search_staged(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int use_msv,
+                         const int32_t *msv_floor, const int32_t *vf_floor, const int32_t *vit_floor, int32_t *msv_out, int32_t *vf_out, int32_t *vit_out, int32_t *fwd_out)
+{
+    return gs::hmm_staged_form(c, db, {true, aa, rec_start, rec_len, n_rec}, use_msv != 0, true, msv_floor, vf_floor, vit_floor, msv_out, vf_out, vit_out, fwd_out, vit_out);
 }
 
 int gs_hmm_trace_dev(gs_ctx *c, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,

@@ -79,6 +79,8 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* hmmsearch, the score matrices of a call where they are not the caller's device memory: a host form's staging, or the matrix nobody asked for;   \
        the records of a call, longest first; per profile the records that a floor selects and their number */                                          \
     X(HMM_VIT) X(HMM_MSV) X(HMM_FWD) X(HMM_ORDER) X(HMM_SEL) X(HMM_SEL_COUNT)                                                                          \
+    /* hmmsearch, the int16 filter (SPEC 13.7): the vf matrix of a call like the matrices above, a host form's staging of the vf floors */              \
+    X(HMM_VF) X(HMMB_VF_FLOOR)                                                                                                                         \
     /* hmmsearch over a list of pairs (trace-back, envelopes): a block's pairs and their profiles' lists; a host form's staging of per-pair outputs: \
        the score, the Backward score, the number of domains or envelopes, those, and the two row arrays of the envelopes */                            \
     X(HMMP_PAIRS) X(HMMP_PROFS) X(HMMB_PAIR_SCORE) X(HMMB_PAIR_BCK) X(HMMB_PAIR_COUNT) X(HMMB_PAIR_ITEMS) X(HMMB_OUT_ROWS) X(HMMB_CONT_ROWS)           \

@@ -367,6 +367,33 @@ int gs_hmm_search_filtered_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev
 int gs_hmm_search_filtered(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec,
                            const int32_t *msv_floor, const int32_t *vit_floor, int32_t *msv_out, int32_t *vit_out, int32_t *fwd_out);
 
+/* The packed int16 Viterbi filter (SPEC 13.7), opt-in: no other call changes. vf is the Viterbi program of SPEC 13 with int16 cells in half units - every
+ * table word x becomes h(x) = max(-32768, (x + 1) >> 1), every cell operation saturates to [-32768, 32767] - and the specials of SPEC 13 in int32 with
+ * E[i] = 2 * max_k M16[i][k]. Every int16 input is at least half its int32 counterpart and max and the saturating add are monotone, so vf >= vit for every
+ * pair that has both; a record whose E16 reaches 32767 in some row gets GS_HMM_VF_OVER, which is above every floor. So the pairs with vf >= f contain the
+ * pairs with vit >= f: a filter that loses no hit.
+ * vf_out[r * n_prof + p] = vf, GS_HMM_NO_SCORE for an empty record or one with a byte that is no residue (that goes before an overflow). Arguments and
+ * refusals are those of gs_hmm_search(_dev). */
+#define GS_HMM_VF_OVER INT32_MAX
+int gs_hmm_search_vit16_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                            int32_t *vf_out_dev);
+int gs_hmm_search_vit16(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int32_t *vf_out);
+/* the int16 table of profile p: [GS_HMM_TABLE_ROWS][M + 1] as gs_hmm_db_tables lays it out, every word h() of the int32 word, nodes 1..M read back
+ * from the device copy k_hmm_vit16 uses */
+int gs_hmm_db_tables16(gs_hmm_db *db, uint64_t p, int16_t *tables_out, uint64_t cap_words);
+/* The staged search: use_msv != 0: msv_out (optional) = the MSV score of every pair as gs_hmm_search_msv writes it, and vf runs for the pairs with msv !=
+ * GS_HMM_NO_SCORE and msv >= msv_floor[p]; use_msv == 0: vf runs for every pair (msv_floor and msv_out are not read). vf_out (optional) = vf of the pairs
+ * it ran for, GS_HMM_NO_SCORE for the others; vit_out[r * n_prof + p] = what gs_hmm_search writes for the pairs with vf != GS_HMM_NO_SCORE and vf >=
+ * vf_floor[p] (the kernels of gs_hmm_search_filtered over those lists), GS_HMM_NO_SCORE for the others; fwd_out (optional, NULL = no Forward pass) as
+ * in gs_hmm_search_filtered. A floor of NULL: every pair that has the score in front. With vf_floor[p] <= f the words of vit_out that are >= f are those of
+ * gs_hmm_search (use_msv == 0) or of gs_hmm_search_filtered (use_msv != 0, the same msv_floor), word for word. Refusals as gs_hmm_search_filtered. */
+int gs_hmm_search_staged_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const uint64_t *rec_start_dev, const uint64_t *rec_len_dev, uint64_t n_rec,
+                             int use_msv, const int32_t *msv_floor_dev, const int32_t *vf_floor_dev, const int32_t *vit_floor_dev, int32_t *msv_out_dev,
+                             int32_t *vf_out_dev, int32_t *vit_out_dev, int32_t *fwd_out_dev);
+int gs_hmm_search_staged(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len, uint64_t n_rec, int use_msv,
+                         const int32_t *msv_floor, const int32_t *vf_floor, const int32_t *vit_floor, int32_t *msv_out, int32_t *vf_out, int32_t *vit_out,
+                         int32_t *fwd_out);
+
 /* Trace-back (SPEC 13.2): the domains of the Viterbi path of a list of (record, profile) pairs - the segments of the path between a B -> M entry and the
  * M -> E exit that follows it. The dynamic program (with back-pointers) and the walk back both run on the device. A domain is GS_HMM_DOM_WORDS int32:
  * i_from, i_to, k_from, k_to (1-based, inclusive), seg = M[i_to][k_to] - B[i_from - 1], n_match, n_ins, n_del. Pairs in any order, repeats allowed.

@@ -289,6 +289,33 @@ public:
                                      vit_floor.empty() ? nullptr : vit_floor.data(), f.msv.data(), f.vit.data(), forward ? f.fwd.data() : nullptr));
         return f;
     }
+    // SPEC 13.7: vf of every pair, the packed int16 Viterbi filter score: vf >= the Viterbi score, GS_HMM_VF_OVER where the int16 cells overflow
+    std::vector<int32_t> search_vit16(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len) const
+    {
+        std::vector<int32_t> out(rec_start.size() * info_.size());
+        check(gs_hmm_search_vit16(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), out.data()));
+        return out;
+    }
+    // the int16 table of profile p, [GS_HMM_TABLE_ROWS][M + 1]
+    std::vector<int16_t> tables16(uint64_t p) const
+    {
+        std::vector<int16_t> out((size_t)GS_HMM_TABLE_ROWS * (info_.at(p).M + 1));
+        check(gs_hmm_db_tables16(db_, p, out.data(), out.size()));
+        return out;
+    }
+    // SPEC 13.7: MSV of every pair (use_msv), vf of every pair or of the pairs at or above msv_floor[p], Viterbi of the pairs with vf >= vf_floor[p] and -
+    // forward = true - Forward behind vit_floor; GS_HMM_NO_SCORE for the pairs a floor left out. An empty floor vector: every pair that has the score in front
+    struct Staged { std::vector<int32_t> msv, vf, vit, fwd; };
+    Staged search_staged(const uint8_t *aa, const std::vector<uint64_t> &rec_start, const std::vector<uint64_t> &rec_len, const std::vector<int32_t> &vf_floor,
+                         bool use_msv = false, const std::vector<int32_t> &msv_floor = {}, bool forward = false, const std::vector<int32_t> &vit_floor = {}) const
+    {
+        const size_t n = rec_start.size() * info_.size();
+        Staged f{std::vector<int32_t>(use_msv ? n : 0), std::vector<int32_t>(n), std::vector<int32_t>(n), std::vector<int32_t>(forward ? n : 0)};
+        check(gs_hmm_search_staged(ctx_->get(), db_, aa, rec_start.data(), rec_len.data(), rec_start.size(), use_msv ? 1 : 0, msv_floor.empty() ? nullptr : msv_floor.data(),
+                                   vf_floor.empty() ? nullptr : vf_floor.data(), vit_floor.empty() ? nullptr : vit_floor.data(), use_msv ? f.msv.data() : nullptr,
+                                   f.vf.data(), f.vit.data(), forward ? f.fwd.data() : nullptr));
+        return f;
+    }
     // SPEC 13.2: the domains of the Viterbi path of the pairs (pair_rec[j], pair_prof[j]), traced back on the device. raw[j] as search() gives it,
     // n_dom[j] the true number of domains, dom[(j * max_dom + d) * GS_HMM_DOM_WORDS ..] the first max_dom of them in sequence order (zeros behind them)
     struct Trace { std::vector<int32_t> raw; std::vector<uint32_t> n_dom; std::vector<int32_t> dom; };

@@ -57,12 +57,23 @@ With --align also (SPEC 13.6), over the same two pair lists (`ga`, 
   check         the identities of SPEC 13.6 on every listed slot, and `check` sampled pairs against the restatement (tests/pyref_hmm_align.py): the
                 expected differences are 0
 
+--vit16 (SPEC 13.7), on the same proteome and profile set:
+  vf            cells/s of the int16 filter launches alone (gs_hmm_search_vit16_dev), beside gs_hmm_search_dev of the same build - the parent commit's
+                kernel, unchanged (profiles/hmm_vit16_resources.txt) -, the calls alternating inside a round: `repeat` timed rounds after a warm-up
+                round, every time listed, the minimum and the median reported
+  staged        seconds of gs_hmm_search_staged_dev with vf_floor = 0 (the score table's raw >= 0; `staged0`), with vf_floor = GA (universal_genes;
+                `staged_ga`) and with MSV in front at P = 0.02 and vf_floor = 0 (`msv_staged0`), beside gs_hmm_search_filtered_dev (`msv_filtered`) in
+                the same rounds; the share of the pairs that go on to int32 Viterbi in each
+  check         no pair with vit >= floor is missing behind the filter and its words are those of the unfiltered matrix, vf >= vit wherever neither
+                overflows, the overflowing pairs counted, and `check` sampled pairs of vf against the restatement (tests/pyref_hmm_vit16.py): the
+                expected differences are 0
+
 --dump PATH saves the downloaded matrices of the modes that ran as one .npz (the Viterbi scores; both Forward matrices; raw, n_dom and the domain
 words of trace_best and trace_all), so that two builds of the library (GS_LIB_PATH) can be compared word for word.
 
-usage: hmm_rate.py [--forward | --trace | --posterior | --null2 | --align | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
+usage: hmm_rate.py [--forward | --trace | --posterior | --null2 | --align | --vit16 | --msv [--parent-s S]] [--n 4000] [--repeat 3] [--check 8] [--dump PATH]
                    [--log profiles/hmm_rate.log | hmm_forward_rate.log | hmm_trace_rate.log | hmm_msv_rate.log | hmm_posterior_rate.log |
-                   hmm_null2_rate.log | hmm_align_rate.log]"""
+                   hmm_null2_rate.log | hmm_align_rate.log | hmm_vit16_rate.log]"""
 import argparse
 import json
 import os
@@ -88,12 +99,15 @@ def main():
     ap.add_argument("--posterior", action="store_true")
     ap.add_argument("--null2", action="store_true")
     ap.add_argument("--align", action="store_true")
+    ap.add_argument("--vit16", action="store_true")
     ap.add_argument("--parent-s", type=float, default=None)
     ap.add_argument("--log", default=None)
     ap.add_argument("--dump", default=None)
     a = ap.parse_args()
     if a.log is None and a.align:
         a.log = os.path.join(ROOT, "profiles", "hmm_align_rate.log")
+    if a.log is None and a.vit16:
+        a.log = os.path.join(ROOT, "profiles", "hmm_vit16_rate.log")
     if a.log is None and a.null2:
         a.log = os.path.join(ROOT, "profiles", "hmm_null2_rate.log")
     if a.log is None:
@@ -155,6 +169,8 @@ def main():
         null2_part(a, ctx, db, texts, recs, ptrs, d_score, res, rng, dump)
     if a.align:
         align_part(a, ctx, db, texts, recs, ptrs, d_score, res, rng, dump)
+    if a.vit16:
+        vit16_part(a, ctx, db, texts, recs, ptrs, d_score, scores, cells, res, rng, dump)
     if a.dump:
         with open(a.dump, "wb") as f:
             np.savez(f, **dump)
@@ -457,6 +473,75 @@ def msv_part(a, ctx, db, texts, recs, ptrs, d_vit_all, vit_all, cells, res, rng,
         diff += int(msv[r, p]) != V.msv(R.parse_hmm(texts[p])[0]["tables"], recs[r])
     res["msv_check_pairs"], res["msv_check_differences"] = a.check, diff
     for p in (d_msv, d_vit, d_floor):
+        ctx.free(p)
+
+
+def vit16_part(a, ctx, db, texts, recs, ptrs, d_vit_all, vit_all, cells, res, rng, dump):
+    import pyref_hmm as R
+    import pyref_hmm_vit16 as W
+    n = a.n * len(db)
+    d_vf, d_vit, d_msv = ctx.alloc(4 * n), ctx.alloc(4 * n), ctx.alloc(4 * n)
+    floors = {"zero": np.zeros(len(db), np.int32), "ga": db.thresholds("ga"), "msv": db.msv_floor(0.02)}
+    d_fl = {}
+    for k, f in floors.items():
+        d_fl[k] = ctx.alloc(f.nbytes)
+        ctx.upload(d_fl[k], f)
+
+    def timed(call):
+        ctx.sync()
+        t = time.perf_counter()
+        call()
+        ctx.sync()
+        return time.perf_counter() - t
+
+    rec = ptrs[0], ptrs[1], ptrs[2], a.n
+    runs = {"unfiltered": lambda: db.search_dev(*rec, d_vit_all),
+            "vf": lambda: db.search_vit16_dev(*rec, d_vf),
+            "staged0": lambda: db.search_staged_dev(*rec, False, None, d_fl["zero"], None, None, d_vf, d_vit, None),
+            "staged_ga": lambda: db.search_staged_dev(*rec, False, None, d_fl["ga"], None, None, d_vf, d_vit, None),
+            "msv_filtered": lambda: db.search_filtered_dev(*rec, d_fl["msv"], None, d_msv, d_vit, None),
+            "msv_staged0": lambda: db.search_staged_dev(*rec, True, d_fl["msv"], d_fl["zero"], None, d_msv, d_vf, d_vit, None)}
+    times = {k: [] for k in runs}
+    kept = {}
+    for it in range(a.repeat + 1):                               # the first round is the warm-up of every shape; the calls alternate inside a round
+        for k, call in runs.items():
+            t = timed(call)
+            if it:
+                times[k].append(t)
+            elif k != "unfiltered":
+                kept[k] = (ctx.download(d_vf, (a.n, len(db)), np.int32), ctx.download(d_vit, (a.n, len(db)), np.int32))
+    for k, ts in times.items():
+        res[k + "_times_s"] = ts
+        res[k + "_min_s"], res[k + "_median_s"] = min(ts), float(np.median(ts))
+    res["vf_cells_per_s"] = cells / res["vf_min_s"]
+    for k in ("vf", "staged0", "staged_ga"):
+        res[k + "_over_unfiltered_min"] = res[k + "_min_s"] / res["unfiltered_min_s"]
+        res[k + "_over_unfiltered_median"] = res[k + "_median_s"] / res["unfiltered_median_s"]
+    res["msv_staged0_over_msv_filtered_min"] = res["msv_staged0_min_s"] / res["msv_filtered_min_s"]
+    res["msv_staged0_over_msv_filtered_median"] = res["msv_staged0_median_s"] / res["msv_filtered_median_s"]
+    vf = kept["vf"][0]
+    dump.update(vf=vf)
+    has = vit_all != R.NO_SCORE
+    over = vf == W.VF_OVER
+    res["overflowing_pairs"] = int(over.sum())
+    res["vf_below_vit"] = int((has & ~over & (vf.astype(np.int64) < vit_all.astype(np.int64))).sum())
+    ex = (vf.astype(np.int64) - vit_all.astype(np.int64))[has & ~over]
+    res["excess_max_units"], res["excess_mean_units"] = int(ex.max()), float(ex.mean())
+    for k, fl in (("staged0", "zero"), ("staged_ga", "ga"), ("msv_staged0", "zero")):
+        svf, svit = kept[k]
+        ran = svit != R.NO_SCORE
+        res[k + "_viterbi_share"] = float(ran.mean())
+        res[k + "_vf_share"] = float((svf != R.NO_SCORE).mean())
+        res[k + "_words_differ_from_unfiltered"] = int((svit[ran] != vit_all[ran]).sum())
+        if k != "msv_staged0":
+            hits = has & (vit_all.astype(np.int64) >= floors[fl][None, :].astype(np.int64))
+            res[k + "_hits"], res[k + "_hits_lost"] = int(hits.sum()), int((hits & ~ran).sum())
+    diff = 0
+    for _ in range(a.check):
+        r, p = int(rng.integers(a.n)), int(rng.integers(len(db)))
+        diff += int(vf[r, p]) != W.vit16(R.parse_hmm(texts[p])[0]["tables"], recs[r])
+    res["vf_check_pairs"], res["vf_check_differences"] = a.check, diff
+    for p in [d_vf, d_vit, d_msv] + list(d_fl.values()):
         ctx.free(p)
 
 

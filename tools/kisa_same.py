@@ -20,7 +20,7 @@ def kernels(path, flt):
         elif name and ln.strip() == ".end_amdhsa_kernel":
             name, part = None, 0
         elif part:
-            out[name][part - 1].append(re.sub(r"\.LBB\d+_", ".LBB_", ln))
+            out[name][part - 1].append(re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r"\s*;.*$", "", ln)))       # (comments name loops by function number too)
     return {k: ("".join(a), "".join(b)) for k, (a, b) in out.items() if b and flt in k}
 
 

@@ -12,7 +12,10 @@
   --prefilter also the same call with prefilter="msv" (SPEC 13.3): its wall time, the seconds of the filtered search of the ORFs (MSV,
               selection, Viterbi over the selected lists) beside the Viterbi stage, and whether the hits are the same.
 
-usage: orf_rate.py [--genomes 64] [--len 5000000] [--search-genomes 64] [--repeat 3] [--min-aa 30] [--prefilter] [--log profiles/orf_rate.log]"""
+  --vit16     also the same call with prefilter="vit16" and "msv+vit16" (SPEC 13.7; vf_floor = the GA cutoffs): wall times, the seconds of
+              the staged search of the ORFs beside the Viterbi stage, the share of the pairs that go on to int32 Viterbi, and whether the hits are the same
+
+usage: orf_rate.py [--genomes 64] [--len 5000000] [--search-genomes 64] [--repeat 3] [--min-aa 30] [--prefilter] [--vit16] [--log profiles/orf_rate.log]"""
 import argparse
 import json
 import os
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--check-bases", type=int, default=100000)
     ap.add_argument("--seed", type=int, default=14)
     ap.add_argument("--prefilter", action="store_true")
+    ap.add_argument("--vit16", action="store_true")
     ap.add_argument("--log", default=os.path.join(ROOT, "profiles", "orf_rate.log"))
     a = ap.parse_args()
     import gsearch_amd as G
@@ -152,6 +156,26 @@ def main():
                 print("prefilter=msv: filtered search %.2f s (%.3f of the Viterbi stage, %.4f of the pairs go on), universal_genes %.2f s, same hits: %s" %
                       (res["filtered_search_s"], res["filtered_over_viterbi"], res["pairs_through_the_filter"], res["universal_genes_prefilter_s"],
                        res["prefilter_same_hits"]), flush=True)
+            if a.vit16:
+                vfl = db.vf_floor(False, None, "ga")
+                for label, pre, msv in (("vit16", "vit16", False), ("msv_vit16", "msv+vit16", True)):
+                    dev.mem.free(dev.search_dev(db, False, None, msv, 0.02, vfl))           # the warm-up of the int16 kernels
+                    ctx.sync()
+                    t = time.perf_counter()
+                    d_fscore = dev.search_dev(db, False, None, msv, 0.02, vfl)
+                    ctx.sync()
+                    res[label + "_search_s"] = time.perf_counter() - t
+                    res[label + "_over_viterbi"] = res[label + "_search_s"] / res["viterbi_s"]
+                    res[label + "_pairs_to_viterbi"] = float((ctx.download(d_fscore, (dev.n, len(db)), np.int32) != R.NO_SCORE).mean())
+                    dev.mem.free(d_fscore)
+                    t = time.perf_counter()
+                    _, flocal, _ = G.universal_genes(files, db, ctx=ctx, translate=True, min_aa=a.min_aa, prefilter=pre)
+                    ctx.sync()
+                    res["universal_genes_%s_s" % label] = time.perf_counter() - t
+                    res[label + "_same_hits"] = bool(np.array_equal(flocal, local))
+                    print("prefilter=%s: staged search %.2f s (%.3f of the Viterbi stage, %.5f of the pairs go on to Viterbi), universal_genes %.2f s, same hits: %s" %
+                          (pre, res[label + "_search_s"], res[label + "_over_viterbi"], res[label + "_pairs_to_viterbi"], res["universal_genes_%s_s" % label],
+                           res[label + "_same_hits"]), flush=True)
             dev.close()
         db.close()
         print("universal_genes(translate=True): %d genomes, %d ORFs, %d residues: %.2f s in all; read %.2f s, split + pack + translate %.2f s, Viterbi %.2f s "
