@@ -17,6 +17,7 @@ from .api import BIGSI_MINI_TILE, Bigsi, bigsi_minimizers, bigsi_positions, bigs
 from .api import BIGSI_VERDICTS, bigsi_verdict_code, bigsig_write_report  # noqa: F401
 from .api import AniGenome, AniSketcher, ani_estimate, ani_pairs, superani, write_superani  # noqa: F401
 from .api import HmmDb, hmm_bits, hmm_evalue, hmm_parse, hmm_specials, hmm_threshold_units, hmmsearch, universal_genes  # noqa: F401
+from .api import UNIVERSAL_STAGES, hit_records, hit_records_dev, universal_sketch  # noqa: F401
 from .api import hmm_exp2_table, hmm_forward_evalue, hmm_logsum_table, hmm_parse_stats, hmm_viterbi_floor  # noqa: F401
 from .api import ORF_DTYPE, ORF_TILE, orf_codon_table, orf_translate, orf_translate_dev, orf_translate_packed, write_orf_faa  # noqa: F401
 from .api import (GENE_DTYPE, GENE_INTERVAL_DTYPE, GENE_START_TYPES, gene_call, gene_call_dev, gene_call_packed, gene_log2_q16, gene_params, gene_score,  # noqa: F401

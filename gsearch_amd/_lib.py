@@ -221,6 +221,8 @@ SYMBOLS = {
     "gs_hmm_exp2_table": (_i, [_vp, _u64]),
     "gs_hmm_align": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
     "gs_hmm_align_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_hit_records_dev": (_i, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "gs_hmm_hit_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     # orfs (SPEC 14)
     "gs_orf_codon_table": (_i, [_u32, C.c_char_p]),
     "gs_orf_translate_dev": (_i, [_vp, C.POINTER(OrfParamsC), _vp, _u64, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),

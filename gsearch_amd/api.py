@@ -2374,7 +2374,7 @@ class _DevGenes(_DevOrfs):
     """The genes of some genomes (SPEC 15) in the place of their ORFs: called on the device and kept there in the same layout, so every search of
     _DevOrfs runs on them unchanged. `orf` holds begin, rec and strand of each gene; `end` its end (the stop codon included where there is one)."""
 
-    def __init__(self, ctx, genomes, min_aa, max_aa, table):
+    def __init__(self, ctx, genomes, min_aa, max_aa, table, gene=None):
         self.ctx, self.mem = ctx, _DevScope(ctx)
         self.contig_ids = [cid for g in genomes for cid, _ in g]
         recs, self.rec_contig, self.rec_offset, goff, contig0 = _gene_segments([[c for _, c in g] for g in genomes])
@@ -2387,7 +2387,7 @@ class _DevGenes(_DevOrfs):
             d_gene, self.d_aa, self.d_as, self.d_al = self.mem.new(GENE_DTYPE.itemsize * cap_gene), self.mem.new(cap_aa), self.mem.new(8 * cap_gene), self.mem.new(8 * cap_gene)
             d_off, d_info = self.mem.new(8 * (n_rec + 1)), self.mem.new(16 * ng)
             self.n, _ = gene_call_dev(ctx, d_seq, seq.nbytes, d_rs, d_rl, n_rec, d_goff, ng, d_info, cap_gene, cap_aa, d_gene, self.d_aa, self.d_as, self.d_al, d_off,
-                                      min_aa=min_aa, table=table)
+                                      **dict(gene or {}, min_aa=min_aa, table=table))
             self.n_long = 0
             gene = ctx.download(d_gene, (self.n,), GENE_DTYPE)
             self.aa_start = ctx.download(self.d_as, (self.n,), np.uint64)
@@ -2413,10 +2413,219 @@ class _DevGenes(_DevOrfs):
         return int(self.rec_contig[o["rec"]]), off + int(o["begin"]), off + int(self.end[j]), int(o["strand"])
 
 
-def _dev_targets(ctx, genomes, translate, min_aa, max_aa, table):
+def _dev_targets(ctx, genomes, translate, min_aa, max_aa, table, gene=None):
+    """gene: further gene_call parameters of translate="genes" (min_aa and table are the call's own)"""
     if translate == "genes":
-        return _DevGenes(ctx, genomes, min_aa, max_aa, table)
+        return _DevGenes(ctx, genomes, min_aa, max_aa, table, gene)
     return _DevOrfs(ctx, genomes, min_aa, max_aa, table)
+
+
+# ---- universal-gene sketches (SPEC 13.8, 17 item 11): best hits become sketcher records on the device -------------------------------------------------
+def _hit_args(n_item, item, item_words, max_item):
+    if (n_item is None) != (item is None):
+        raise ValueError("n_item and item go together")
+    return int(item_words), int(max_item)
+
+
+def hit_records_dev(ctx, best_rec_dev, n_genomes, n_prof, aa_dev, rec_start_dev, rec_len_dev, n_rec, cap_rec, cap_aa, out_aa_dev, out_start_dev, out_len_dev,
+                    out_genome_off_dev, n_item_dev=None, item_dev=None, item_words=_lib.HMM_DOM_WORDS, max_item=8):
+    """gs_hmm_hit_records_dev (SPEC 13.8): all arrays device memory -> (records, residues). When the capacities are too small the GsError carries the true
+    counts as .counts and nothing else was written; the other refusals leave .counts None."""
+    words, m = _hit_args(n_item_dev, item_dev, item_words, max_item)
+    n = (C.c_uint64 * 2)(0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF)
+    try:
+        check(ctx.L.gs_hmm_hit_records_dev(ctx.h, best_rec_dev, int(n_genomes), int(n_prof), aa_dev, rec_start_dev, rec_len_dev, int(n_rec), n_item_dev, item_dev, words, m,
+                                           int(cap_rec), int(cap_aa), out_aa_dev, out_start_dev, out_len_dev, out_genome_off_dev, n))
+    except GsError as e:
+        e.counts = None if n[0] == 0xFFFFFFFFFFFFFFFF else (int(n[0]), int(n[1]))
+        raise
+    return int(n[0]), int(n[1])
+
+
+def hit_records(best_rec, aa, rec_start, rec_len, n_item=None, item=None, cap_rec=None, cap_aa=None, out=None):
+    """gs_hmm_hit_records (SPEC 13.8), the host twin of hit_records_dev; no device. best_rec: uint32 [n_genomes, n_prof] as best_hits() gives it over the
+    records (aa, rec_start, rec_len); n_item uint32 [n_genomes * n_prof] and item int32 [n_genomes * n_prof, max_item, words]: the spans of trace_packed(),
+    envelopes_packed() or align_packed() over the matrix as a pair list. -> (uint8 residues back to back, uint64 start, uint64 len, uint64 genome_off
+    [n_genomes + 1]). cap_rec / cap_aa: the room offered (None: enough); out: (aa, start, len, genome_off) arrays to write into instead of new ones. A
+    refusal for room carries the true counts as .counts."""
+    rec = np.ascontiguousarray(best_rec, dtype=np.uint32)
+    if rec.ndim != 2:
+        raise ValueError("best_rec: [n_genomes, n_prof]")
+    ng, npf = rec.shape
+    (aa, rs, rl), recs = _recs(aa, rec_start, rec_len)
+    ni = it = None
+    words, m = _lib.HMM_DOM_WORDS, 8
+    if n_item is not None or item is not None:
+        _hit_args(n_item, item, 0, 0)
+        ni, it = np.ascontiguousarray(n_item, dtype=np.uint32).reshape(-1), np.ascontiguousarray(item, dtype=np.int32)
+        if it.ndim != 3 or it.shape[0] != rec.size or len(ni) != rec.size:
+            raise ValueError("n_item and item: one entry per (genome, profile) pair")
+        m, words = it.shape[1], it.shape[2]
+    named = rec[rec < len(rl)]
+    room_rec = rec.size if cap_rec is None else int(cap_rec)
+    room_aa = int(rl[named].sum()) if cap_aa is None else int(cap_aa)
+    if out is None:
+        out = (np.zeros((room_aa + 7) // 8 * 8 + 8, np.uint8), np.zeros(max(room_rec, 1), np.uint64), np.zeros(max(room_rec, 1), np.uint64), np.zeros(ng + 1, np.uint64))
+    o_aa, o_s, o_l, o_g = out
+    n = (C.c_uint64 * 2)(0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF)
+    try:
+        check(_lib.load().gs_hmm_hit_records(None, _opt(rec), ng, npf, *recs, _opt(ni), _opt(it), words, m, room_rec, room_aa, _p(o_aa), _p(o_s), _p(o_l), _p(o_g), n))
+    except GsError as e:
+        e.counts = None if n[0] == 0xFFFFFFFFFFFFFFFF else (int(n[0]), int(n[1]))
+        raise
+    return o_aa[:int(n[1])], o_s[:int(n[0])], o_l[:int(n[0])], o_g
+
+
+class _DevProteins(_DevOrfs):
+    """The kept records of some protein FASTA files in the place of their genomes' ORFs: filtered as the AA sketchers filter, uploaded once and kept in
+    the layout gs_hmm_search_dev reads, so every search of _DevOrfs runs on them unchanged. Record j of the set is record j - genome_orf_off[g] of file g."""
+
+    def __init__(self, ctx, faa_files):
+        self.ctx, self.mem = ctx, _DevScope(ctx)
+        seqs, goff = [], [0]
+        for path in faa_files:
+            seqs.extend(_faa_records(path)[1])
+            goff.append(len(seqs))
+        aa, self.aa_start, self.aa_len = filter_aa_records([bytes(s) for s in seqs])
+        self.n, self.n_long = len(seqs), 0
+        self.genome_orf_off = np.array(goff, np.uint64)
+        try:
+            self.d_aa, self.d_as, self.d_al = self.mem.up(aa), self.mem.up(self.aa_start), self.mem.up(self.aa_len)
+        except Exception:
+            self.close()
+            raise
+
+
+def _hit_spans_dev(db, dev, d_rec, n_pairs, region, scope):
+    """the spans of region over the best-hit matrix as a pair list, left on the device with room for every item (_all_items) ->
+    (n_item_dev, item_dev, words of a slot, slots a pair, uint32 n_item)"""
+    ctx = db.ctx
+    d_pp = scope.up(np.tile(np.arange(len(db), dtype=np.uint32), n_pairs // len(db)))
+
+    def run(m):
+        d_a, d_b, d_n = scope.new(4 * n_pairs), scope.new(4 * n_pairs), scope.new(4 * n_pairs)
+        if region == "aligned":
+            words = _lib.HMM_DOM_WORDS
+            d_item = scope.new(4 * n_pairs * m * words)
+            db.trace_dev(dev.d_aa, dev.d_as, dev.d_al, dev.n, d_rec, d_pp, n_pairs, m, d_a, d_n, d_item)
+        else:
+            words = _lib.HMM_ENV_WORDS
+            d_item = scope.new(4 * n_pairs * m * words)
+            db.envelopes_dev(dev.d_aa, dev.d_as, dev.d_al, dev.n, d_rec, d_pp, n_pairs, m, d_a, d_b, d_n, d_item)
+        n_item = ctx.download(d_n, (n_pairs,), np.uint32)
+        if len(n_item) and int(n_item.max()) > m:
+            for ptr in (d_a, d_b, d_n, d_item):
+                scope.free(ptr)
+            return None, n_item
+        if region == "alignment":
+            d_env, words = d_item, _lib.HMM_ALI_WORDS
+            d_item = scope.new(4 * n_pairs * m * words)
+            db.align_dev(dev.d_aa, dev.d_as, dev.d_al, dev.n, d_rec, d_pp, n_pairs, m, d_n, d_env, d_item)
+        return (d_n, d_item, words, m), n_item
+    got, n_item = run(8)
+    if got is None:
+        got, n_item = run(int(n_item.max()))
+    return got + (n_item,)
+
+
+UNIVERSAL_STAGES = ("targets", "search", "best_hits", "spans", "hit_records", "sketch")
+
+
+def universal_sketch(files, hmm, sketcher, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein", translate=None, min_aa=_lib.ORF_MIN_AA, table=11,
+                     prefilter=None, msv_p=0.02, gene=None, genomes_per_call=64, bias=False):
+    """SPEC 17 item 11: one universal-gene signature per file - what sketcher.sketch_genomes(universal_genes(files, hmm, ...)[0]) gives, bit for bit, with every
+    step between the targets and the signatures on the device: no residue comes back to the host. files: protein FASTA (translate=None), or nucleotide
+    FASTA whose candidates are the six-frame ORFs (translate=True, SPEC 14) or the called genes (translate="genes", SPEC 15; gene: further gene_call
+    parameters). cutoff, score, filter_p, region, min_aa, table, prefilter and msv_p as universal_genes() takes them; bias=True (host-side best hits) is
+    not offered: ValueError. A round takes genomes_per_call files: their targets (_dev_targets, or the uploaded records of the .faa files), the staged
+    search universal_genes() would choose, best_hits_dev, for region != "protein" the trace / envelopes / alignments of the best-hit matrix as a pair list,
+    gs_hmm_hit_records_dev, gs_sketch_batch_dev. Per round the signatures, the genome offsets, the hit lengths, best_rec and the item counts come back.
+    -> (signatures [n_files, m] - zeros for a file without a hit -, uint64 hits per file, uint64 residues sketched per file, uint32 [n_files, n_prof]
+    record numbers inside each file as universal_genes() returns them, stats: seconds per stage of UNIVERSAL_STAGES under "stage_s", "wall_s", "rounds")"""
+    import os
+    import time
+    if score not in ("viterbi", "forward"):
+        raise ValueError("score: 'viterbi' or 'forward'")
+    if region not in ("protein", "aligned", "envelope", "alignment"):
+        raise ValueError("region: 'protein', 'aligned', 'envelope' or 'alignment'")
+    if bias:
+        raise ValueError("bias=True takes its best hits on the host: universal_genes() offers it, universal_sketch() does not")
+    if translate not in (None, False, True, "genes"):
+        raise ValueError("translate: None, True or 'genes'")
+    if sketcher.params.c.data_t != DATA["aa"]:
+        raise ValueError("universal genes are proteins: an amino-acid sketcher")
+    per = int(genomes_per_call)
+    if per < 1:
+        raise ValueError("genomes_per_call: at least 1")
+    pre_msv, pre_vit16 = _check_prefilter(prefilter)
+    ctx = ctx or sketcher.ctx
+    db = _as_hmm_db(hmm, ctx)
+    ctx = db.ctx
+    fwd = score == "forward"
+    vf_floor = db.vf_floor(fwd, filter_p, cutoff) if pre_vit16 else None
+    thr = db.thresholds(cutoff)
+    files = [os.fsdecode(f) for f in files]
+    n, npf, m = len(files), len(db), sketcher.params.c.sketch_size
+    sig = np.zeros((n, m), sketcher.sig_dtype())
+    nrec, nsym = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+    local = np.full((n, npf), _lib.HMM_NO_HIT, np.uint32)
+    stage = dict.fromkeys(UNIVERSAL_STAGES, 0.0)
+    t_all = t = time.perf_counter()
+
+    def lap(name):
+        nonlocal t
+        now = time.perf_counter()
+        stage[name] += now - t
+        t = now
+    rounds = 0
+    for f0 in range(0, n, per) if npf else ():
+        chunk = files[f0:f0 + per]
+        ng = len(chunk)
+        rounds += 1
+        t = time.perf_counter()
+        if translate:
+            dev = _dev_targets(ctx, [_fna_contigs(p) for p in chunk], translate, min_aa, _orf_max_aa(fwd or region in ("envelope", "alignment"), region == "aligned"),
+                               table, gene)
+        else:
+            dev = _DevProteins(ctx, chunk)
+        lap("targets")
+        with _DevScope(ctx) as out:
+            try:
+                if dev.n == 0:
+                    continue
+                d_score = dev.search_dev(db, fwd, filter_p, pre_msv, msv_p, vf_floor)
+                lap("search")
+                d_rec = dev.mem.new(4 * ng * npf)
+                db.best_hits_dev(d_score, dev.n, dev.mem.up(dev.genome_orf_off), ng, dev.mem.up(thr), d_rec, dev.mem.new(4 * ng * npf))
+                rec = ctx.download(d_rec, (ng, npf), np.uint32)
+                lap("best_hits")
+                hit = rec != _lib.HMM_NO_HIT
+                if not hit.any():
+                    continue
+                spans = (None, None, _lib.HMM_DOM_WORDS, 8)
+                if region != "protein":
+                    spans = _hit_spans_dev(db, dev, d_rec, ng * npf, region, dev.mem)[:4]
+                    lap("spans")
+                cap_rec, cap_aa = int(hit.sum()), int(dev.aa_len[rec[hit]].sum())
+                aa_bytes = (cap_aa + 7) // 8 * 8 + 8
+                d_aa, d_os, d_ol, d_goff = out.new(aa_bytes), out.new(8 * cap_rec), out.new(8 * cap_rec), out.new(8 * (ng + 1))
+                n_hit, n_aa = hit_records_dev(ctx, d_rec, ng, npf, dev.d_aa, dev.d_as, dev.d_al, dev.n, cap_rec, cap_aa, d_aa, d_os, d_ol, d_goff, *spans)
+                base = dev.genome_orf_off[:-1].astype(np.uint32)[:, None]
+            finally:
+                dev.close()                                 # the targets are not needed any more: the sketcher reads the compacted copy
+            lap("hit_records")
+            d_sig = out.new(ng * m * sig.dtype.itemsize)
+            check(ctx.L.gs_sketch_batch_dev(ctx.h, C.byref(sketcher.params.c), d_aa, aa_bytes, d_os, d_ol, n_hit, d_goff, ng, d_sig))
+            got = ctx.download(d_sig, (ng, m), sig.dtype)
+            goff = ctx.download(d_goff, (ng + 1,), np.uint64).astype(np.int64)
+            csum = np.concatenate([[0], np.cumsum(ctx.download(d_ol, (n_hit,), np.uint64).astype(np.int64))])
+            lap("sketch")
+        has = goff[1:] > goff[:-1]
+        sig[f0:f0 + ng][has] = got[has]
+        nrec[f0:f0 + ng] = goff[1:] - goff[:-1]
+        nsym[f0:f0 + ng] = csum[goff[1:]] - csum[goff[:-1]]
+        local[f0:f0 + ng] = np.where(hit, rec - base, rec)
+    return sig, nrec, nsym, local, {"stage_s": stage, "wall_s": time.perf_counter() - t_all, "rounds": rounds}
 
 
 # ---- bigsig (binaux/src/bin/bigsig.rs; SPEC 11) -----------------------------------------------------------------------------------------

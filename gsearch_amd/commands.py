@@ -11,6 +11,7 @@ formats, state.py, ReqAnswer.dump, ani - and add no kernel. Everything that touc
 Argument parsing and logging of the binaries are not here."""
 import decimal
 import io
+import json
 import os
 import time
 
@@ -27,6 +28,8 @@ EF_SEARCH, OUT_THRESHOLD = 5000, 0.99                     # gsearch.rs:893, dnar
 MATCHES_LISTED = 5                                        # matcher.rs:266
 BLOCK_FASTA_ID = "-total-sequence"                        # dnafiles.rs:268-272, aafiles.rs:91-95
 GENES_PER_CALL = 64                                       # genomes called and sketched per device round of translate="genes"
+UNIVERSAL = "universal.json"                              # sidecar of a universal-gene database: the profile names in order and the options (SPEC 17 item 11)
+UNIVERSAL_OPTS = ("cutoff", "score", "filter_p", "region", "min_aa", "table", "prefilter", "msv_p", "genomes_per_call", "bias")
 
 
 # ---- Rust's number formats -----------------------------------------------------------------------------------------------------------------------
@@ -126,11 +129,19 @@ def reformat(kmer, model, input_file, output_file):
 
 
 # ---- files -> signatures -------------------------------------------------------------------------------------------------------------------------
-def _check_translate(translate, data_t, block):
+def _check_translate(translate, data_t, block, universal=None):
+    if universal is not None and universal is not False:
+        if data_t != _lib.DATA["aa"]:
+            raise GsError(_lib.GS_ERR_INVALID, "universal genes feed the amino-acid sketchers: the database is not an AA database")
+        if block:
+            raise GsError(_lib.GS_ERR_UNSUPPORTED, "universal with block: the universal genes of a genome are not one record")
+        if translate is not None and translate is not True and translate != "genes":
+            raise GsError(_lib.GS_ERR_INVALID, "translate with universal: None, True or 'genes', not %r" % (translate,))
+        return
     if translate is None:
         return
     if translate != "genes":
-        raise GsError(_lib.GS_ERR_INVALID, "translate: None or 'genes', not %r" % (translate,))
+        raise GsError(_lib.GS_ERR_INVALID, "translate: None or 'genes' (True only with universal), not %r" % (translate,))
     if data_t != _lib.DATA["aa"]:
         raise GsError(_lib.GS_ERR_INVALID, "translate='genes' feeds the amino-acid sketchers: the database is not an AA database")
     if block:
@@ -138,9 +149,9 @@ def _check_translate(translate, data_t, block):
 
 
 def _list(directory, data_t, translate):
-    files = A.list_fasta_files(directory, "dna" if translate == "genes" else data_t)
+    files = A.list_fasta_files(directory, "dna" if translate else data_t)
     if not files:
-        raise GsError(_lib.GS_ERR_INVALID, "no %s file under %s" % ("nucleotide FASTA" if translate == "genes" or data_t == _lib.DATA["dna"] else "protein FASTA", directory))
+        raise GsError(_lib.GS_ERR_INVALID, "no %s file under %s" % ("nucleotide FASTA" if translate or data_t == _lib.DATA["dna"] else "protein FASTA", directory))
     return files
 
 
@@ -225,7 +236,48 @@ def _sketch_genes(sk, paths, gene):
     return sig, nrec, nsym, st
 
 
-def _sketch_dir(sk, paths, block, pio, threads, translate, gene):
+class _Universal:
+    """the profile set and the options of a command's `universal` argument; None and False (files of extracted universal genes, sketched as they are)
+    make none. The set is closed with the command when the command made it."""
+
+    def __init__(self, universal, opts, ctx):
+        self.db, self.own = None, False
+        if universal is None or universal is False:
+            if opts:
+                raise GsError(_lib.GS_ERR_INVALID, "universal_opts without universal")
+            return
+        self.opts = dict(opts or {})
+        unknown = sorted(set(self.opts) - set(UNIVERSAL_OPTS))
+        if unknown:
+            raise GsError(_lib.GS_ERR_INVALID, "universal_opts: %s; the options are %s (translate and gene are the command's own)" % (unknown, list(UNIVERSAL_OPTS)))
+        self.own = not isinstance(universal, A.HmmDb)
+        self.db = A._as_hmm_db(universal, ctx)
+
+    def close(self):
+        if self.own and self.db is not None:
+            self.db.close()
+        self.db = None
+
+    def sidecar(self, translate, gene):
+        return {"profiles": list(self.db.names), "options": dict(self.opts, translate=translate, gene=dict(gene or {}))}
+
+    def check_against(self, db_dir, universal):
+        """a directory with a sidecar takes universal genes only: of its own profiles, or files that hold them already (universal=False)"""
+        path = os.path.join(db_dir, UNIVERSAL)
+        if not os.path.exists(path):
+            return
+        with open(path, encoding="utf-8") as f:
+            names = json.load(f)["profiles"]
+        if universal is None:
+            raise GsError(_lib.GS_ERR_INVALID, "%s is a universal-gene database (%s): give universal, or universal=False for files of extracted genes" % (db_dir, UNIVERSAL))
+        if self.db is not None and list(self.db.names) != list(names):
+            raise GsError(_lib.GS_ERR_INVALID, "the profiles given differ from the %d that %s was built with (%s)" % (len(names), db_dir, UNIVERSAL))
+
+
+def _sketch_dir(sk, paths, block, pio, threads, translate, gene, universal=None):
+    if universal is not None and universal.db is not None:
+        sig, nrec, nsym, _, stats = A.universal_sketch(paths, universal.db, sk, translate=translate, gene=gene, **universal.opts)
+        return sig, nrec, nsym, stats
     if translate == "genes":
         return _sketch_genes(sk, paths, gene)
     return sk.sketch_files(paths, block=block, pio=pio, threads=threads)
@@ -317,18 +369,25 @@ def _report(nb_file, items, nrec, keep, skipped, stats, seconds, written, why):
 
 def tohnsw(dir, out_dir, kmer_size, sketch_size, nbng, ef=400, algo="optdens", aa=False, block=False, scale_modify=1.0, pio=0, threads=0, seed=0,
            insert_batch=0, hnswrs=True, truncate_255=False, translate=None, ctx=None, capacity=CAPACITY, max_layer=MAX_LAYER, extend_candidates=True,
-           keep_pruned=False, gene=None):
+           keep_pruned=False, gene=None, universal=None, universal_opts=None):
     """`gsearch tohnsw -d dir -k -s -n --ef --algo [--aa] [--block]`: the accepted files under `dir` (recursive, name order) -> one signature per
     file that has a kept record -> ONE parallel_insert with ids = positions in the dictionary -> `out_dir` with parameters.json, seqdict.json,
     processing_state.json, hnswdump.gsidx and (hnswrs) the hnsw_rs pair. gene: gene_call parameters of translate='genes'.
+    universal (SPEC 17 item 11): a profile set (path, directory, list or HmmDb) - every file's signature is that of its universal genes (universal_sketch with
+    universal_opts; .faa files, or nucleotide files with translate=True / 'genes'), a file without a hit is skipped, and universal.json is written.
     Returns counts, the sketch_files statistics, seconds per stage, the files skipped and whether the pair was written."""
     t_start = time.perf_counter()
     params = ProcessingParams(HnswParams(capacity, ef, nbng, scale_modify), kmer_size, sketch_size, algo, "aa" if aa else "dna", block)
     sk = A.sketcher_for(A.SeqSketcherParams(kmer_size, sketch_size, params.algo, params.data_t), ctx)
-    _check_translate(translate, params.data_t, block)
-    paths = _list(dir, params.data_t, translate)
-    t_list = time.perf_counter()
-    sig, nrec, nsym, stats = _sketch_dir(sk, paths, block, pio, threads, translate, gene)
+    _check_translate(translate, params.data_t, block, universal)
+    uni = _Universal(universal, universal_opts, sk.ctx)
+    try:
+        paths = _list(dir, params.data_t, translate)
+        t_list = time.perf_counter()
+        sig, nrec, nsym, stats = _sketch_dir(sk, paths, block, pio, threads, translate, gene, uni)
+        sidecar = uni.sidecar(translate, gene) if uni.db is not None else None
+    finally:
+        uni.close()
     t_sketch = time.perf_counter()
     keep = [i for i in range(len(paths)) if int(nsym[i]) > 0]
     if not keep:
@@ -340,6 +399,10 @@ def tohnsw(dir, out_dir, kmer_size, sketch_size, nbng, ef=400, algo="optdens", a
         t_insert = time.perf_counter()
         state = ProcessingState(_nb_seq(nrec, keep, len(paths), block), len(paths), time.perf_counter() - t_start)
         written, why = _dump_database(hn, str(out_dir), params, seqdict, state, hnswrs, truncate_255)
+        if sidecar is not None:
+            with open(os.path.join(str(out_dir), UNIVERSAL), "w", encoding="utf-8") as f:
+                json.dump(sidecar, f, indent=1, default=str)
+                f.write("\n")
     finally:
         hn.close()
     t_dump = time.perf_counter()
@@ -347,20 +410,25 @@ def tohnsw(dir, out_dir, kmer_size, sketch_size, nbng, ef=400, algo="optdens", a
     return _report(len(paths), seqdict.items, nrec, keep, [paths[i] for i in range(len(paths)) if int(nsym[i]) == 0], stats, seconds, written, why)
 
 
-def add(db_dir, new_dir, pio=0, threads=0, truncate_255=False, translate=None, ctx=None, seed=0, insert_batch=0, hnswrs=True, gene=None):
+def add(db_dir, new_dir, pio=0, threads=0, truncate_255=False, translate=None, ctx=None, seed=0, insert_batch=0, hnswrs=True, gene=None, universal=None,
+        universal_opts=None):
     """`gsearch add -b db_dir -n new_dir`: everything but the two directories is reloaded from the database (block_flag, algo, kmer_size, data_t and
     sketch_size are the stored ones; seed / insert_batch only matter when the index comes from the hnsw_rs pair). The new files' signatures go in by
     ONE parallel_insert with ids continuing at the dictionary's length; all files of the directory are rewritten. A directory whose parameters.json
-    disagrees with the dump is refused with GS_ERR_INVALID before anything is written."""
+    disagrees with the dump is refused with GS_ERR_INVALID before anything is written. universal / universal_opts as tohnsw takes them; a directory that
+    has universal.json refuses a call without universal and one whose profile names differ, universal=False: the files hold extracted genes already."""
     t_start = time.perf_counter()
     db = _Database(db_dir, ctx, seed, insert_batch)
+    uni = None
     try:
         block = db.params.block_flag
-        _check_translate(translate, db.params.data_t, block)
+        _check_translate(translate, db.params.data_t, block, universal)
+        uni = _Universal(universal, universal_opts, db.ctx)
+        uni.check_against(db.dir, universal)
         t_load = time.perf_counter()
         paths = _list(new_dir, db.params.data_t, translate)
         t_list = time.perf_counter()
-        sig, nrec, nsym, stats = _sketch_dir(db.sk, paths, block, pio, threads, translate, gene)
+        sig, nrec, nsym, stats = _sketch_dir(db.sk, paths, block, pio, threads, translate, gene, uni)
         t_sketch = time.perf_counter()
         keep = [i for i in range(len(paths)) if int(nsym[i]) > 0]
         first = db.seqdict.get_nb_entries()
@@ -372,6 +440,8 @@ def add(db_dir, new_dir, pio=0, threads=0, truncate_255=False, translate=None, c
         state = ProcessingState(db.state.nb_seq + _nb_seq(nrec, keep, len(paths), block), db.state.nb_file + len(paths), time.perf_counter() - t_start)
         written, why = _dump_database(db.hn, db.dir, db.params, seqdict, state, hnswrs, truncate_255)
     finally:
+        if uni is not None:
+            uni.close()
         db.close()
     t_dump = time.perf_counter()
     seconds = {"load": t_load - t_start, "list": t_list - t_load, "read_sketch": t_sketch - t_list, "insert": t_insert - t_sketch, "dump": t_dump - t_insert,
@@ -382,20 +452,23 @@ def add(db_dir, new_dir, pio=0, threads=0, truncate_255=False, translate=None, c
 
 
 def request(db_dir, query_dir, nbanswers, out="gsearch.neighbors.txt", matches="gsearch.matches", ef=EF_SEARCH, threshold=OUT_THRESHOLD, pio=0, threads=0,
-            translate=None, ctx=None, gene=None):
+            translate=None, ctx=None, gene=None, universal=None, universal_opts=None):
     """`gsearch request -b db_dir -r query_dir -n nbanswers`: the query files sketched with the database's parameters and mode, ONE search_arrays over
     all of them, then per request (rank = position among the sketched query files) ReqAnswer.dump into `out` (created or truncated) and, when the
     database was built by sequence, `matches` in matcher.rs' form. Returns ids, distances, counts, evaluation counts, the request items, lines
-    written and seconds per stage."""
+    written and seconds per stage. universal / universal_opts as add takes them, with the same refusals on a directory that has universal.json."""
     t_start = time.perf_counter()
     db = _Database(db_dir, ctx)
+    uni = None
     try:
         block = db.params.block_flag
-        _check_translate(translate, db.params.data_t, block)
+        _check_translate(translate, db.params.data_t, block, universal)
+        uni = _Universal(universal, universal_opts, db.ctx)
+        uni.check_against(db.dir, universal)
         t_load = time.perf_counter()
         paths = _list(query_dir, db.params.data_t, translate)
         t_list = time.perf_counter()
-        sig, nrec, nsym, stats = _sketch_dir(db.sk, paths, block, pio, threads, translate, gene)
+        sig, nrec, nsym, stats = _sketch_dir(db.sk, paths, block, pio, threads, translate, gene, uni)
         t_sketch = time.perf_counter()
         keep = [i for i in range(len(paths)) if int(nsym[i]) > 0]
         items = _items(paths, nsym, keep, block)
@@ -406,6 +479,8 @@ def request(db_dir, query_dir, nbanswers, out="gsearch.neighbors.txt", matches="
             ids, dist, cnt, ev = np.zeros((0, knbn), np.uint64), np.zeros((0, knbn), np.float32), np.zeros(0, np.uint32), np.zeros(0, np.uint64)
         seqdict = db.seqdict.items
     finally:
+        if uni is not None:
+            uni.close()
         db.close()
     t_search = time.perf_counter()
     thr = float(np.float32(threshold))                        # out_threshold is an f32 compared with f32 distances (answer.rs:42,55)

@@ -92,6 +92,9 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* hmmsearch, alignment: per listed slot where its nibbles and columns start, the place of the seg_raw words null2's Forward writes and nobody      \
        reads (everything else lies in null2's, the trace's and the envelopes' slots: the forms of one context cannot nest); a host form's columns */    \
     X(HMMA_SLOTS) X(HMMA_SEG) X(HMMB_PAIR_COLS)                                                                                                         \
+    /* hmmsearch, best hits to sketcher records (gs_hmm_hits.hip): per (genome, profile) pair whether it is a hit, its residues and where they start    \
+       in the source; the prefix sums of the first two; the two totals and the error word */                                                            \
+    X(HMMH_FLAG) X(HMMH_LEN) X(HMMH_SRC) X(HMMH_POS) X(HMMH_OFF) X(HMMH_META)                                                                          \
     /* orfs (gs_orf.hip): tile prefix of the records and the call's counters; per tile the last stop of each (strand, class) pair, then its kept ORFs,      \
        residues and long drops (each scanned in place); the partial results of those scans; staging of the host form */                                 \
     X(ORF_REC_TILES) X(ORF_META) X(ORF_STOPS) X(ORF_COUNTS) X(ORF_PARTIALS) X(ORFB_SEQ) X(ORFB_REC_START) X(ORFB_REC_LEN) X(ORFB_ORF) X(ORFB_AA)         \

@@ -493,6 +493,27 @@ int gs_hmm_align_dev(gs_ctx *ctx, gs_hmm_db *db, const uint8_t *aa_dev, const ui
                      const uint32_t *pair_rec_dev, const uint32_t *pair_prof_dev, uint64_t n_pairs, uint32_t max_env, uint64_t max_block_cells, const uint32_t *n_env_dev,
                      const int32_t *env_dev, int32_t *slot_out_dev, const uint64_t *col_off_dev, int32_t *col_out_dev);
 
+/* Best hits become sketcher records (SPEC 13.8): the [n_genomes][n_prof] matrix best_rec as gs_hmm_best_hits_dev leaves it (GS_HMM_NO_HIT = none) over
+ * the searched records (aa, rec_start, rec_len, n_rec) -> the chosen residues back to back in out_aa and their descriptors, what gs_sketch_batch_dev
+ * reads. Output record j is the j-th hit of the matrix in (genome, profile) order; out_start[j] / out_len[j] address out_aa; the hits of genome g are
+ * records [out_genome_off[g], out_genome_off[g + 1]), an empty range for a genome without one. A record that two profiles chose appears twice.
+ * Spans (n_item and item both given, or both NULL): item is [n_genomes * n_prof][max_item][item_words] int32 with i_from in word 0 and i_to in word 1 of
+ * a slot, 1-based and inclusive - the layout the GS_HMM_DOM_WORDS, GS_HMM_ENV_WORDS and GS_HMM_ALI_WORDS slots share. Hit h = g * n_prof + p with
+ * n_item[h] >= 1 contributes residues [i_from of item 0 - 1, i_to of item n_item[h] - 1) of its record, a hit with n_item[h] = 0 and every hit of a
+ * call without spans the whole record. The items of a pair that is no hit are not read.
+ * n_out (HOST) = {records, residues}. GS_ERR_INVALID, nothing written (n_out neither): a best_rec that is neither GS_HMM_NO_HIT nor < n_rec; a hit with
+ * n_item[h] > max_item (run the spans again with room); a span outside its record (i_from < 1, i_to > the record's length or i_to < i_from - 1); spans
+ * with item_words < 2 or max_item = 0. More than cap_rec records or cap_aa residues: GS_ERR_INVALID with n_out filled and nothing else written.
+ * No byte of out_aa at or past n_out[1] and no descriptor at or past n_out[0] is written. 2^32 pairs or records and more: GS_ERR_UNSUPPORTED.
+ * Device form: every array but n_out device memory; one wait for the counts, one at the end. The host form computes on the host (ctx may be NULL). */
+int gs_hmm_hit_records_dev(gs_ctx *ctx, const uint32_t *best_rec_dev, uint64_t n_genomes, uint64_t n_prof, const uint8_t *aa_dev, const uint64_t *rec_start_dev,
+                           const uint64_t *rec_len_dev, uint64_t n_rec, const uint32_t *n_item_dev, const int32_t *item_dev, uint32_t item_words, uint32_t max_item,
+                           uint64_t cap_rec, uint64_t cap_aa, uint8_t *out_aa_dev, uint64_t *out_start_dev, uint64_t *out_len_dev, uint64_t *out_genome_off_dev,
+                           uint64_t n_out[2]);
+int gs_hmm_hit_records(gs_ctx *ctx, const uint32_t *best_rec, uint64_t n_genomes, uint64_t n_prof, const uint8_t *aa, const uint64_t *rec_start, const uint64_t *rec_len,
+                       uint64_t n_rec, const uint32_t *n_item, const int32_t *item, uint32_t item_words, uint32_t max_item, uint64_t cap_rec, uint64_t cap_aa,
+                       uint8_t *out_aa, uint64_t *out_start, uint64_t *out_len, uint64_t *out_genome_off, uint64_t n_out[2]);
+
 /* ---------------------------------------------------------------------------------------------- */
 /* orfs (SPEC 14): stop-to-stop six-frame translation of packed nucleotide records on the device - the model-free way to feed hmmsearch from genomes.
  * It is NOT a gene caller and does not replace FragGeneScanRs: the ORF set is not a proteome and must not be given to the AA sketchers or superaai.

@@ -363,6 +363,23 @@ public:
                            e.n_env.data(), e.env.empty() ? nullptr : e.env.data(), slot.empty() ? nullptr : slot.data(), nullptr, nullptr));
         return slot;
     }
+    // SPEC 13.8: the hits of a [n_genomes][n_prof] best-hit matrix as sketcher records, on the host: the chosen residues back to back in (genome, profile)
+    // order, start / len against them, genome_off[g] the first hit of genome g. n_item / item (both empty: whole records): the spans of trace(),
+    // envelopes() or align() over the matrix as a pair list, item_words the words of one of their slots, max_item the slots a pair
+    struct HitRecords { std::vector<uint8_t> aa; std::vector<uint64_t> start, len, genome_off; };
+    static HitRecords hit_records(const std::vector<uint32_t> &best_rec, uint64_t n_genomes, uint64_t n_prof, const uint8_t *aa, const std::vector<uint64_t> &rec_start,
+                                  const std::vector<uint64_t> &rec_len, const std::vector<uint32_t> &n_item = {}, const std::vector<int32_t> &item = {},
+                                  uint32_t item_words = GS_HMM_DOM_WORDS, uint32_t max_item = 8)
+    {
+        uint64_t room = 0, n_out[2] = {0, 0};
+        for (uint32_t r : best_rec) room += r < rec_len.size() ? rec_len[r] : 0;
+        HitRecords h{std::vector<uint8_t>(room + 8), std::vector<uint64_t>(best_rec.size()), std::vector<uint64_t>(best_rec.size()), std::vector<uint64_t>(n_genomes + 1)};
+        check(gs_hmm_hit_records(nullptr, best_rec.data(), n_genomes, n_prof, aa, rec_start.data(), rec_len.data(), rec_start.size(), n_item.empty() ? nullptr : n_item.data(),
+                                 item.empty() ? nullptr : item.data(), item_words, max_item, best_rec.size(), room, h.aa.data(), h.start.data(), h.len.data(),
+                                 h.genome_off.data(), n_out));
+        h.start.resize(n_out[0]); h.len.resize(n_out[0]); h.aa.resize(n_out[1]);
+        return h;
+    }
     // the floor of profile p for a Viterbi P-value of filter_p (HMMER's F2 = 1e-3): INT32_MIN + 1 without STATS LOCAL VITERBI
     int32_t viterbi_floor(size_t profile, double filter_p = 1e-3) const
     {
