@@ -326,6 +326,10 @@ SYMBOLS = {
     "gs_topk_pack": (_i, [_vp, _vp, _u64, _u64, _u32, _vp]),
     "gs_topk_unpack": (_i, [_vp, _i, _u64, _u32, _vp, _vp, _vp]),
     "gs_topk_merge_dev": (_i, [_vp, _vp, _vp, _u32, _u64, _u32, _vp, _u32, _vp, _vp]),
+    # split databases (SPEC 17 items 12-18)
+    "gs_topk_reset_dev": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    "gs_index_search_merge_dev": (_i, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "gs_index_search_merge": (_i, [_vp, _vp, _u64, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp, _vp]),
     "gs_synth_dna_dev": (_i, [_vp, _u64, _u64, _u64, _u64, _vp]),
     "gs_synth_aa_dev": (_i, [_vp, _u64, _u64, _u64, _u64, _vp]),
     "gs_synth_dna_family_dev": (_i, [_vp, _u64, _u64, _u64, _u64, _u64, C.c_double, C.c_double, _vp]),

@@ -196,6 +196,11 @@ def topk_merge_dev(ctx, ids_dev, dist_dev, n_shards, nq, knbn_in, knbn_out, out_
     check(ctx.L.gs_topk_merge_dev(ctx.h, ids_dev, dist_dev, int(n_shards), int(nq), int(knbn_in), _p(off), int(knbn_out), out_ids_dev, out_dist_dev))
 
 
+def topk_reset_dev(ctx, nq, knbn, run_ids_dev, run_dist_dev, run_count_dev, run_evals_dev=None):
+    """empty running lists for Hnsw.search_merge_dev (gs_topk_reset_dev): ids UINT64_MAX, distances +inf, counts and evaluations 0"""
+    check(ctx.L.gs_topk_reset_dev(ctx.h, int(nq), int(knbn), run_ids_dev, run_dist_dev, run_count_dev, run_evals_dev))
+
+
 _default_ctx = None
 
 
@@ -3392,6 +3397,44 @@ class Hnsw:
         ev = np.zeros(nq, dtype=np.uint64)
         check(self.ctx.L.gs_index_parallel_search(self.h, _p(datas), nq, knbn, ef, _p(ids), _p(dist), _p(cnt), _p(ev)))
         return ids, dist, cnt, ev
+
+    def search_dev(self, d_queries, nq, knbn, ef, d_ids, d_dist, d_count=None, d_evals=None):
+        """gs_index_parallel_search_dev: every d_* is a device pointer (int)"""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "search on an empty index")
+        check(self.ctx.L.gs_index_parallel_search_dev(self.h, d_queries, int(nq), int(knbn), int(ef), d_ids, d_dist, d_count, d_evals))
+
+    def search_merge_dev(self, d_queries, nq, knbn, ef, d_run_ids, d_run_dist, d_run_count, d_run_evals=None, d_rows=None, nr=0, id_offset=0):
+        """this index as one piece of a split database (gs_index_search_merge_dev): the listed query rows (d_rows: nr ascending uint32 rows on the
+        device, None: all nq) are searched and the answers, id_offset added, merged in place into their running lists under (distance, id).
+        Every d_* is a device pointer (int); topk_reset_dev makes the empty lists."""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "search on an empty index")
+        check(self.ctx.L.gs_index_search_merge_dev(self.h, d_queries, int(nq), d_rows, int(nr), int(knbn), int(ef), int(id_offset), d_run_ids, d_run_dist,
+                                                   d_run_count, d_run_evals))
+
+    def search_merge(self, datas, knbn, ef, run_ids, run_dist, run_count, run_evals=None, rows=None, id_offset=0):
+        """the host-pointer twin (gs_index_search_merge): datas (nq, m); run_ids (nq, knbn) uint64, run_dist (nq, knbn) float32, run_count (nq,)
+        uint32 and run_evals (nq,) uint64 are C-contiguous arrays updated in place; rows: ascending row numbers, None = every query"""
+        datas = np.ascontiguousarray(datas, dtype=self.dtype)
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "search on an empty index")
+        nq = datas.shape[0]
+        want = [(run_ids, np.uint64, (nq, knbn)), (run_dist, np.float32, (nq, knbn)), (run_count, np.uint32, (nq,))]
+        if run_evals is not None:
+            want.append((run_evals, np.uint64, (nq,)))
+        for a, dt, shape in want:
+            if not (isinstance(a, np.ndarray) and a.dtype == dt and a.shape == shape and a.flags.c_contiguous and a.flags.writeable):
+                raise GsError(_lib.GS_ERR_INVALID, "the running lists are writable C-contiguous arrays: ids (nq, knbn) uint64, dist (nq, knbn) float32, count (nq,) uint32, evals (nq,) uint64")
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int64)
+            if rows.size and (rows.min() < 0 or rows.max() > 0xFFFFFFFF):
+                raise GsError(_lib.GS_ERR_INVALID, "a row number is a uint32")
+            rows = rows.astype(np.uint32)
+            if rows.size == 0:
+                return
+        check(self.ctx.L.gs_index_search_merge(self.h, _p(datas), nq, _p(rows), 0 if rows is None else len(rows), int(knbn), int(ef), int(id_offset),
+                                               _p(run_ids), _p(run_dist), _p(run_count), _p(run_evals)))
 
     def parallel_search(self, datas, knbn, ef):
         """-> Vec<Vec<Neighbour>>, ascending distance (dnarequest.rs:353)."""

@@ -451,6 +451,26 @@ def add(db_dir, new_dir, pio=0, threads=0, truncate_255=False, translate=None, c
     return out
 
 
+def _write_answers(items, ids, dist, cnt, seqdict, threshold, out, matches, block):
+    """the two answer files of a request: ReqAnswer.dump per request into `out` (created or truncated) and, by sequence, matcher.rs' text into
+    `matches` -> (matches written by ReqAnswer.dump, lines per file)"""
+    thr = float(np.float32(threshold))                        # out_threshold is an f32 compared with f32 distances (answer.rs:42,55)
+    answers = [[A.Neighbour(int(ids[i, j]), float(dist[i, j])) for j in range(int(cnt[i]))] for i in range(len(items))]
+    nb_match, buf = 0, io.StringIO()
+    for i, item in enumerate(items):
+        nb_match += A.ReqAnswer(i, item, answers[i]).dump(seqdict, thr, buf)
+    text = buf.getvalue()
+    with open(out, "w", encoding="utf-8", newline="") as f:
+        f.write(text)
+    lines = {"neighbors": text.count("\n"), "matches": None}
+    if not block:                                             # gsearch.rs:926-929: the matcher is run by sequence only
+        text = matches_text([(item[0], answers[i]) for i, item in enumerate(items)], seqdict, thr)
+        with open(matches, "w", encoding="utf-8", newline="") as f:
+            f.write(text)
+        lines["matches"] = text.count("\n")
+    return nb_match, lines
+
+
 def request(db_dir, query_dir, nbanswers, out="gsearch.neighbors.txt", matches="gsearch.matches", ef=EF_SEARCH, threshold=OUT_THRESHOLD, pio=0, threads=0,
             translate=None, ctx=None, gene=None, universal=None, universal_opts=None):
     """`gsearch request -b db_dir -r query_dir -n nbanswers`: the query files sketched with the database's parameters and mode, ONE search_arrays over
@@ -483,20 +503,7 @@ def request(db_dir, query_dir, nbanswers, out="gsearch.neighbors.txt", matches="
             uni.close()
         db.close()
     t_search = time.perf_counter()
-    thr = float(np.float32(threshold))                        # out_threshold is an f32 compared with f32 distances (answer.rs:42,55)
-    answers = [[A.Neighbour(int(ids[i, j]), float(dist[i, j])) for j in range(int(cnt[i]))] for i in range(len(items))]
-    nb_match, buf = 0, io.StringIO()
-    for i, item in enumerate(items):
-        nb_match += A.ReqAnswer(i, item, answers[i]).dump(seqdict, thr, buf)
-    text = buf.getvalue()
-    with open(out, "w", encoding="utf-8", newline="") as f:
-        f.write(text)
-    lines = {"neighbors": text.count("\n"), "matches": None}
-    if not block:                                             # gsearch.rs:926-929: the matcher is run by sequence only
-        text = matches_text([(item[0], answers[i]) for i, item in enumerate(items)], seqdict, thr)
-        with open(matches, "w", encoding="utf-8", newline="") as f:
-            f.write(text)
-        lines["matches"] = text.count("\n")
+    nb_match, lines = _write_answers(items, ids, dist, cnt, seqdict, threshold, out, matches, block)
     t_text = time.perf_counter()
     seconds = {"load": t_load - t_start, "list": t_list - t_load, "read_sketch": t_sketch - t_list, "search": t_search - t_sketch, "text": t_text - t_search,
                "wall": t_text - t_start}

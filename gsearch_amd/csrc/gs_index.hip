@@ -2295,6 +2295,8 @@ struct gs_index {
 
 namespace gs {
 
+gs_ctx *index_ctx(gs_index *ix) { return ix->ctx; }
+
 // the members of gs_index marked "scratch" at the struct, and nothing else
 static std::vector<DevBuf *> index_scratch(gs_index *ix)
 {

@@ -174,6 +174,8 @@ struct ClusterSource {
 int cluster_rows(gs_index *ix, const uint32_t *nodes_dev, uint64_t nb, const uint16_t **slab);
 // the padded rows (stride bytes, a multiple of 16) of the listed nodes, one after the other
 int gather_rows(gs_ctx *c, const void *data, uint64_t stride, const uint32_t *nodes_dev, uint64_t nb, void *out);
+// the context an index lives on (gs_index.hip; the struct is private to that unit)
+gs_ctx *index_ctx(gs_index *ix);
 // host answers; the caller has validated the index side (not empty, m <= 65535) and holds the context lock
 int nearest_of_nodes(gs_ctx *c, const ClusterSource &src, const uint64_t *cand, uint64_t nc, uint32_t *arg_out, uint16_t *count_out);
 int cluster_nodes(gs_ctx *c, const ClusterSource &src, const gs_cluster_params *prm, uint64_t *centre_node, uint16_t *centre_count, uint64_t *medoids,

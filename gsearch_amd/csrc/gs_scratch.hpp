@@ -116,7 +116,11 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     X(DBG_SCAN_VALS) X(DBG_SCAN_TOTAL)                                                                                                                 \
     /* gs_hamming.hip behind host pointers (gs_debug_hamming_strided, gs_debug_hamming_blocks; the suite only): both operands and the output of the     \
        dense form; both operands, the items, the two row lists and the output of the work-list form */                                                  \
-    X(DBG_HAM_Q) X(DBG_HAM_C) X(DBG_HAM_OUT) X(DBG_HAMB_Q) X(DBG_HAMB_C) X(DBG_HAMB_ITEMS) X(DBG_HAMB_QLIST) X(DBG_HAMB_CLIST) X(DBG_HAMB_OUT)
+    X(DBG_HAM_Q) X(DBG_HAM_C) X(DBG_HAM_OUT) X(DBG_HAMB_Q) X(DBG_HAMB_C) X(DBG_HAMB_ITEMS) X(DBG_HAMB_QLIST) X(DBG_HAMB_CLIST) X(DBG_HAMB_OUT)              \
+    /* split databases (gs_split.hip): the flag of the row check, the gathered query rows, a piece's answers to them (ids, distances, counts,         \
+       evaluations); the host twin's staging of the queries and of the listed rows' running lists */                                                  \
+    X(SPLIT_FLAG) X(SPLIT_QROWS) X(SPLIT_IDS) X(SPLIT_DIST) X(SPLIT_COUNT) X(SPLIT_EVALS) X(SPLITB_QUERIES) X(SPLITB_RUN_IDS) X(SPLITB_RUN_DIST)      \
+    X(SPLITB_RUN_COUNT) X(SPLITB_RUN_EVALS)
 
 enum ScratchSlot : int {
 #define X(name) SL_##name,

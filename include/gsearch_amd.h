@@ -966,6 +966,22 @@ int  gs_topk_unpack(const void *blocks, int n_ranks, uint64_t nq_max, uint32_t k
  * added to the ids of each shard; out_*_dev: nq x knbn_out, the best under (distance, id). */
 int  gs_topk_merge_dev(gs_ctx *, const uint64_t *ids_dev, const float *dist_dev, uint32_t n_shards, uint64_t nq, uint32_t knbn_in, const uint64_t *id_offset,
                        uint32_t knbn_out, uint64_t *out_ids_dev, float *out_dist_dev);
+/* Split databases on ONE device (the loop of scripts/multiple_search.sh with the queries sketched once, SPEC.md 17 items 12-18): the queries and their
+ * running answers stay on the device while the pieces of the database are loaded, searched and closed one after the other.
+ * gs_topk_reset_dev: nq empty running lists - run_ids UINT64_MAX, run_dist +inf, run_count 0, run_evals (optional) 0.
+ * gs_index_search_merge_dev: for every listed row q = rows_dev[r] (rows_dev NULL: every query, nr is ignored) the answers A of
+ * gs_index_parallel_search_dev(piece, queries[q], knbn, ef), id_offset added to every id, are merged into run[q] in place: run[q] becomes the first
+ * knbn of run[q] and A ascending by (distance as its bit pattern, id) - the rule of gs_topk_merge_dev -, the running entry first on a full tie;
+ * run_count[q] = min(knbn, run_count[q] + count), run_evals[q] (optional) += evals, unused tail slots UINT64_MAX / +inf. Only the first run_count[q]
+ * entries of run[q] are read, and they are ascending under that order (what a reset and earlier merges leave). A row that is not listed is not written.
+ * queries_dev: nq rows of the index's signature type, back to back. rows_dev: strictly ascending and below nq, checked on the device before the search
+ * starts (GS_ERR_INVALID, nothing written). knbn <= 1024 (GS_ERR_UNSUPPORTED beyond); nq < 2^31. The refusals of gs_index_parallel_search_dev apply.
+ * gs_index_search_merge: the same with every pointer in HOST memory. */
+int  gs_topk_reset_dev(gs_ctx *, uint64_t nq, uint32_t knbn, uint64_t *run_ids_dev, float *run_dist_dev, uint32_t *run_count_dev, uint64_t *run_evals_dev);
+int  gs_index_search_merge_dev(gs_index *piece, const void *queries_dev, uint64_t nq, const uint32_t *rows_dev, uint64_t nr, uint32_t knbn, uint32_t ef,
+                               uint64_t id_offset, uint64_t *run_ids_dev, float *run_dist_dev, uint32_t *run_count_dev, uint64_t *run_evals_dev);
+int  gs_index_search_merge(gs_index *piece, const void *queries, uint64_t nq, const uint32_t *rows, uint64_t nr, uint32_t knbn, uint32_t ef,
+                           uint64_t id_offset, uint64_t *run_ids, float *run_dist, uint32_t *run_count, uint64_t *run_evals);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* Synthetic inputs generated in HBM (bench / tests): counter-based, reproducible on the host.      */

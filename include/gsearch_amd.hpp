@@ -636,6 +636,25 @@ public:
         check(gs_index_exact_search(h_, flat.data(), nq, (uint32_t)knbn, max_dist, ids.data(), dist.data(), cnt.data()));
         return lists(ids, dist, cnt, knbn);
     }
+    // this index as one piece of a split database (gs_index_search_merge, SPEC 17 items 12-18): the answers of the listed queries (rows: ascending
+    // positions in datas, nullptr = all), id_offset added, merged in place into their running lists under (distance, id). run_ids / run_dist:
+    // datas.size() x knbn, run_count / run_evals: datas.size(); new_running_lists() makes the empty ones
+    struct RunningLists { std::vector<uint64_t> ids; std::vector<float> dist; std::vector<uint32_t> count; std::vector<uint64_t> evals; };
+    static RunningLists new_running_lists(size_t nq, size_t knbn)
+    {
+        return RunningLists{std::vector<uint64_t>(nq * knbn, UINT64_MAX), std::vector<float>(nq * knbn, INFINITY), std::vector<uint32_t>(nq, 0), std::vector<uint64_t>(nq, 0)};
+    }
+    void search_merge(const std::vector<std::vector<T>> &datas, size_t knbn, size_t ef, RunningLists &run, uint64_t id_offset = 0, const std::vector<uint32_t> *rows = nullptr) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "search on an empty index");
+        const size_t nq = datas.size(), m = prm_.m;
+        if (run.ids.size() != nq * knbn || run.dist.size() != nq * knbn || run.count.size() != nq || run.evals.size() != nq) throw Error(GS_ERR_INVALID, "running lists of another shape");
+        if (rows && rows->empty()) return;
+        std::vector<T> flat(nq * m);
+        for (size_t i = 0; i < nq; i++) { if (datas[i].size() != m) throw Error(GS_ERR_INVALID, "signature length mismatch"); std::copy(datas[i].begin(), datas[i].end(), flat.begin() + i * m); }
+        check(gs_index_search_merge(h_, flat.data(), nq, rows ? rows->data() : nullptr, rows ? rows->size() : 0, (uint32_t)knbn, (uint32_t)ef, id_offset, run.ids.data(),
+                                    run.dist.data(), run.count.data(), run.evals.data()));
+    }
     // hnsw2knn: the knbn nearest OTHER nodes of nodes [first, first + n) in insertion order, exact (gs_index_knn_graph)
     std::vector<std::vector<Neighbour>> knn_graph(size_t knbn, float max_dist = 1.0f, size_t first = 0, size_t n = SIZE_MAX) const
     {
