@@ -12,6 +12,7 @@ from .api import (fastq_scan, hmh_cardinality, hmh_cardinality_dev, hmh_similari
 from .api import EmbedParams, ann, embed_knn_graph, embed_knn_graph_dev, knn_graph_stats, write_embedding_csv  # noqa: F401
 from .api import FracMinHashSketch, aai, frac_max_hash, frac_similarity_qxc, frac_similarity_qxc_dev, read_list_lines, superaai, write_superaai  # noqa: F401
 from .api import ClusterResult, hnswcore, write_cluster_csv  # noqa: F401
+from .api import ComponentsResult, DerepResult, ani_cut  # noqa: F401
 from .api import hnswrs_describe, hnswrs_verify  # noqa: F401
 from .api import BIGSI_MINI_TILE, Bigsi, bigsi_minimizers, bigsi_positions, bigsi_split, bigsi_tail, bigsig_construct, bigsig_identify, bigsig_write_reads, read_ref_list  # noqa: F401
 from .api import BIGSI_VERDICTS, bigsi_verdict_code, bigsig_write_report  # noqa: F401
@@ -22,5 +23,5 @@ from .api import hmm_exp2_table, hmm_forward_evalue, hmm_logsum_table, hmm_parse
 from .api import ORF_DTYPE, ORF_TILE, orf_codon_table, orf_translate, orf_translate_dev, orf_translate_packed, write_orf_faa  # noqa: F401
 from .api import (GENE_DTYPE, GENE_INTERVAL_DTYPE, GENE_START_TYPES, gene_call, gene_call_dev, gene_call_packed, gene_log2_q16, gene_params, gene_score,  # noqa: F401
                   gene_train, genecall, write_gene_faa, write_gene_ffn, write_gene_gff)
-from .commands import add, matches_text, reformat, reformat_text, request, rust_display_f64, rust_upper_exp, tohnsw  # noqa: F401
+from .commands import add, derep, derep_clusters_text, derep_representatives_text, matches_text, reformat, reformat_text, request, rust_display_f64, rust_upper_exp, tohnsw  # noqa: F401
 from .split import request_split, split_json_text, tohnsw_split  # noqa: F401

@@ -56,6 +56,11 @@ class ClusterInfoC(C.Structure):
     _fields_ = [("n_core", C.c_uint64), ("iterations", C.c_uint32), ("converged", C.c_uint32), ("cost_core", C.c_uint64), ("cost_all", C.c_uint64)]
 
 
+class DerepInfoC(C.Structure):
+    """gs_derep_info (SPEC 18)"""
+    _fields_ = [("n_clusters", C.c_uint64), ("n_singletons", C.c_uint64), ("largest", C.c_uint64), ("c_max", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class BigsiParamsC(C.Structure):
     """gs_bigsi_params (SPEC 11)"""
     _fields_ = [("k", C.c_uint32), ("num_hash", C.c_uint32), ("bloom_size", C.c_uint64), ("data_t", C.c_uint32), ("minimizer", C.c_uint32),
@@ -267,6 +272,8 @@ SYMBOLS = {
     "gs_cluster_params_default": (ClusterParamsC, []),
     "gs_index_nearest_of": (_i, [_vp, _vp, _u64, _vp, _vp]),
     "gs_index_cluster": (_i, [_vp, C.POINTER(ClusterParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(ClusterInfoC)]),
+    "gs_index_components": (_i, [_vp, C.c_float, _vp, C.POINTER(DerepInfoC)]),
+    "gs_index_derep": (_i, [_vp, C.c_float, _vp, _vp, _vp, C.POINTER(DerepInfoC)]),
     # bigsig (SPEC 11)
     "gs_bigsi_check_params": (_i, [C.POINTER(BigsiParamsC)]),
     "gs_bigsi_create": (_i, [_vp, C.POINTER(BigsiParamsC), _u64, C.POINTER(_vp)]),

@@ -3237,6 +3237,35 @@ ClusterResult.__doc__ = """Hnsw.cluster's answer (SPEC 10). Per node, in node or
 id), centre_count (mismatch count to it). medoids / medoid_ids / sizes: the k centres by ascending node number (empty for n_cluster = 0, where the
 centres are the coreset points). core_nodes / core_weight: the coreset, None unless asked for."""
 
+ComponentsResult = namedtuple("ComponentsResult", ["label_node", "label_id", "n_clusters", "n_singletons", "largest", "c_max"])
+DerepResult = namedtuple("DerepResult", ["rep_node", "rep_id", "rep_count", "reps", "sizes", "n_clusters", "n_singletons", "largest", "c_max"])
+DerepResult.__doc__ = """Hnsw.derep's answer (SPEC 18). Per node, in node order: rep_node (node number of its representative, itself for a representative),
+rep_id (that node's caller id), rep_count (mismatch count to it). reps: the representatives' node numbers in rank order; sizes: the nodes each
+received, itself included; n_clusters, n_singletons, largest, c_max: gs_derep_info."""
+
+
+def ani_cut(ani_value, kmer, model, m):
+    """an ANI threshold (percent) as a cut of the derep entry points -> (c_max, max_dist): c_max = the largest mismatch count c of m whose ANI by the
+    forward transform ani((f32)c / (f32)m, kmer, model) is >= ani_value, max_dist = (f32)c_max / (f32)m. Found by bisection over the counts (the
+    transform falls as c grows); no inverse formula is evaluated, so nothing rounds at the boundary. No count passes: GS_ERR_INVALID."""
+    m, model = int(m), int(model)
+    if model not in (1, 2) or not 1 <= m <= 65535 or not float(ani_value) == float(ani_value):
+        raise GsError(_lib.GS_ERR_INVALID, "ani_cut: model 1 or 2, m in 1..65535, ani a number")
+
+    def ok(c):
+        return ani(float(np.float32(c) / np.float32(m)), kmer, model) >= float(ani_value)
+    if not ok(0):
+        raise GsError(_lib.GS_ERR_INVALID, "ani_cut: not even equal signatures reach an ANI of %r" % (ani_value,))
+    lo, hi = 0, m + 1                                        # ok(lo), not ok(hi) (hi = m + 1 stands for "none")
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if ok(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo, float(np.float32(lo) / np.float32(m))
+
+
 HNSWCORE_TYPES = {"u16": np.uint16, "u32": np.uint32, "u64": np.uint64, "f32": np.float32}
 HNSWCORE_REFUSED = ("f64", "i32", "i64")            # hnswcore.rs:163-170 also names these: no sketcher produces them (SPEC 10)
 
@@ -3480,6 +3509,37 @@ class Hnsw:
         p = int(info.n_core)
         return ClusterResult(cen, ids[cen.astype(np.int64)], cnt, med, ids[med.astype(np.int64)], sizes, p, int(info.iterations), int(info.converged),
                              int(info.cost_core), int(info.cost_all), core[:p] if return_coreset else None, wgt[:p] if return_coreset else None)
+
+    def components(self, max_dist):
+        """single linkage at a cut (SPEC 18, gs_index_components): nodes whose mismatch count is <= c_max (max_dist as in exact_search_arrays) are
+        linked -> ComponentsResult: per node, in node order, label_node (the smallest node number of its connected component) and label_id (that
+        node's caller id); the info fields n_clusters, n_singletons, largest, c_max"""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "components of an empty index")
+        n = self.get_nb_point()
+        lab, info = np.zeros(n, np.uint64), _lib.DerepInfoC()
+        check(self.ctx.L.gs_index_components(self.h, float(max_dist), _p(lab), C.byref(info)))
+        return ComponentsResult(lab, self.get_ids()[lab.astype(np.int64)], int(info.n_clusters), int(info.n_singletons), int(info.largest), int(info.c_max))
+
+    def derep(self, max_dist, priority=None):
+        """greedy representatives at a cut (SPEC 18, gs_index_derep; CD-HIT's incremental clustering in its -g 1 form) -> DerepResult. priority: one
+        uint64 per node, higher is better, None = all equal; ties go by node number."""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "derep of an empty index")
+        n = self.get_nb_point()
+        if priority is not None:
+            priority = np.ascontiguousarray(priority, dtype=np.uint64)
+            if priority.shape != (n,):
+                raise GsError(_lib.GS_ERR_INVALID, "one priority per node")
+        rep, cnt, info = np.zeros(n, np.uint64), np.zeros(n, np.uint16), _lib.DerepInfoC()
+        check(self.ctx.L.gs_index_derep(self.h, float(max_dist), _p(priority), _p(rep), _p(cnt), C.byref(info)))
+        is_rep = rep == np.arange(n, dtype=np.uint64)
+        key = np.zeros(n, np.uint64) if priority is None else priority
+        order = np.lexsort((np.arange(n), np.iinfo(np.uint64).max - key))           # priority descending, node number ascending
+        reps = order[is_rep[order]].astype(np.uint64)
+        sizes = np.bincount(rep.astype(np.int64), minlength=n)[reps.astype(np.int64)].astype(np.uint64)
+        return DerepResult(rep, self.get_ids()[rep.astype(np.int64)], cnt, reps, sizes, int(info.n_clusters), int(info.n_singletons), int(info.largest),
+                           int(info.c_max))
 
     def sketch_and_search_dev(self, params, d_seq, seq_bytes, d_rec_start, d_rec_len, n_rec, d_genome_rec_off, n_genomes, knbn, ef, d_ids, d_dist, d_count=None,
                               d_evals=None, d_sig=None):

@@ -5,6 +5,7 @@
 * ``request``  - gsearch request (gsearch.rs:880-950, dnarequest.rs:240-400, answer.rs, matcher.rs): a folder of query files -> gsearch.neighbors.txt
                  (and gsearch.matches by sequence)
 * ``reformat`` - reformat        (src/bin/reformat.rs): gsearch.neighbors.txt -> the ANI table of the README
+* ``derep``    - no upstream program (SPEC 18): a database directory -> its clusters and representatives at an ANI cut
 
 They join pieces that are each held to the oracle on their own - list_fasta_files, sketch_files, Hnsw.parallel_insert / search_arrays, the two dump
 formats, state.py, ReqAnswer.dump, ani - and add no kernel. Everything that touches sequence data runs on the device; there is no CPU fallback.
@@ -448,6 +449,75 @@ def add(db_dir, new_dir, pio=0, threads=0, truncate_255=False, translate=None, c
                "wall": t_dump - t_start}
     out = _report(len(paths), items, nrec, keep, [paths[i] for i in range(len(paths)) if int(nsym[i]) == 0], stats, seconds, written, why)
     out.update(first_id=first, nb_point_total=seqdict.get_nb_entries(), index_source=db.source)
+    return out
+
+
+# ---- derep (SPEC 18) -----------------------------------------------------------------------------------------------------------------------------
+DEREP_HEADER = "genome\trepresentative\tdistance\tani\tcluster_size"
+DEREP_CLUSTERS, DEREP_REPS = "derep.clusters.tsv", "derep.representatives.txt"
+
+
+def derep_clusters_text(paths, cluster_node, counts, m, kmer, model):
+    """derep.clusters.tsv: the header, then one line per genome in node order: its path, the path of its representative (of its component's label
+    under single linkage), the distance (f32)count / (f32)m as gsearch.neighbors.txt prints one ({:.5E}), the ANI of that distance as reformat prints
+    one, the number of genomes of its cluster. counts None (single linkage): distance and ANI are `-`."""
+    cluster_node = np.asarray(cluster_node, np.int64)
+    size = np.bincount(cluster_node, minlength=len(paths))
+    lines = [DEREP_HEADER]
+    for v, r in enumerate(cluster_node.tolist()):
+        if counts is None:
+            d_s = a_s = "-"
+        else:
+            d = float(np.float32(int(counts[v])) / np.float32(m))
+            d_s, a_s = A._rust_5e(d), _ani_string(d, int(kmer), int(model))
+        lines.append("%s\t%s\t%s\t%s\t%d" % (paths[v], paths[r], d_s, a_s, size[r]))
+    return "".join(s + "\n" for s in lines)
+
+
+def derep_representatives_text(paths, reps):
+    """derep.representatives.txt: the representatives' paths, one per line, in the order given (rank order)"""
+    return "".join("%s\n" % paths[int(r)] for r in reps)
+
+
+def derep(db_dir, ani=None, max_dist=None, model=1, linkage="greedy", priority="length", out_dir=".", ctx=None):
+    """Dereplication of a database directory (SPEC 18): the directory is reloaded as `request` reloads it, its genomes are clustered at the cut and
+    out_dir/derep.clusters.tsv and out_dir/derep.representatives.txt are written. The cut is `ani` (percent, through ani_cut with the database's
+    k-mer size and `model`) or `max_dist` (a DistHamming distance), exactly one of them. linkage "greedy": Hnsw.derep, representatives by
+    `priority` - "length": the symbols sketched per genome (seqdict.json), longer first; None: node order; or one value per node;
+    linkage "single": Hnsw.components, the representative of a cluster is its first genome. On an amino-acid or universal-gene database the same
+    transform gives an AAI-like cut, not an ANI. Returns the result, c_max, max_dist and the two paths."""
+    if (ani is None) == (max_dist is None):
+        raise GsError(_lib.GS_ERR_INVALID, "derep: give ani or max_dist, one of them")
+    if linkage not in ("greedy", "single"):
+        raise GsError(_lib.GS_ERR_INVALID, "derep: linkage is \"greedy\" or \"single\"")
+    db = _Database(db_dir, ctx)
+    try:
+        items, kmer, m = db.seqdict.items, int(db.params.kmer_size), int(db.params.sketch_size)
+        if ani is not None:
+            max_dist = A.ani_cut(ani, kmer, model, m)[1]
+        ids = db.hn.get_ids().astype(np.int64)                   # node v is entry ids[v] of the dictionary (tohnsw and add insert with ids = positions)
+        if isinstance(priority, str):
+            if priority != "length":
+                raise GsError(_lib.GS_ERR_INVALID, "derep: priority is \"length\", None or an array")
+            priority = np.array([int(items[i][2]) for i in ids], np.uint64)
+        paths = [items[i][0] for i in ids]
+        if linkage == "greedy":
+            res = db.hn.derep(max_dist, priority)
+            text = derep_clusters_text(paths, res.rep_node, res.rep_count, m, kmer, model)
+            reps = res.reps
+        else:
+            res = db.hn.components(max_dist)
+            text = derep_clusters_text(paths, res.label_node, None, m, kmer, model)
+            reps = np.unique(res.label_node)
+    finally:
+        db.close()
+    os.makedirs(str(out_dir), exist_ok=True)
+    out = {"result": res, "c_max": res.c_max, "max_dist": float(max_dist), "clusters": os.path.join(str(out_dir), DEREP_CLUSTERS),
+           "representatives": os.path.join(str(out_dir), DEREP_REPS)}
+    with open(out["clusters"], "w", encoding="utf-8", newline="") as f:
+        f.write(text)
+    with open(out["representatives"], "w", encoding="utf-8", newline="") as f:
+        f.write(derep_representatives_text(paths, reps))
     return out
 
 

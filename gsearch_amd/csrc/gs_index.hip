@@ -3932,6 +3932,29 @@ int gs_index_cluster(gs_index *ix, const gs_cluster_params *prm, uint64_t *centr
     GS_REQUIRE(centre_node_out && centre_count_out && info_out && (p.n_cluster == 0 || (medoids_out && sizes_out)), GS_ERR_INVALID, "null argument");
     return gs::cluster_nodes(ix->ctx, src, &p, centre_node_out, centre_count_out, medoids_out, sizes_out, core_nodes_out, core_weight_out, core_cap, info_out);
 }
+// derep (gs_derep.hip, SPEC 18): the cut as a count by exact_args (the device compares integers only), the rows by cluster_rows
+int gs_index_components(gs_index *ix, float max_dist, uint64_t *label_out, gs_derep_info *info_out)
+{
+    GS_REQUIRE(ix && label_out && info_out, GS_ERR_INVALID, "null argument");
+    uint32_t c_max = 0;
+    int rc = gs::exact_args(ix, 1, max_dist, &c_max);
+    if (rc) return rc;
+    GS_CTX_LOCK(ix->ctx);
+    gs::ClusterSource src;
+    if ((rc = gs::cluster_source(ix, &src))) return rc;
+    return gs::components_nodes(ix->ctx, src, c_max, label_out, info_out);
+}
+int gs_index_derep(gs_index *ix, float max_dist, const uint64_t *priority, uint64_t *rep_node_out, uint16_t *rep_count_out, gs_derep_info *info_out)
+{
+    GS_REQUIRE(ix && rep_node_out && rep_count_out && info_out, GS_ERR_INVALID, "null argument");
+    uint32_t c_max = 0;
+    int rc = gs::exact_args(ix, 1, max_dist, &c_max);
+    if (rc) return rc;
+    GS_CTX_LOCK(ix->ctx);
+    gs::ClusterSource src;
+    if ((rc = gs::cluster_source(ix, &src))) return rc;
+    return gs::derep_nodes(ix->ctx, src, c_max, priority, rep_node_out, rep_count_out, info_out);
+}
 
 }  // extern "C"
 namespace gs {

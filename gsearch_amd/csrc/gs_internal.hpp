@@ -180,6 +180,10 @@ gs_ctx *index_ctx(gs_index *ix);
 int nearest_of_nodes(gs_ctx *c, const ClusterSource &src, const uint64_t *cand, uint64_t nc, uint32_t *arg_out, uint16_t *count_out);
 int cluster_nodes(gs_ctx *c, const ClusterSource &src, const gs_cluster_params *prm, uint64_t *centre_node, uint16_t *centre_count, uint64_t *medoids,
                   uint64_t *sizes, uint64_t *core_nodes, uint64_t *core_weight, uint64_t core_cap, gs_cluster_info *info);
+// gs_derep.hip (SPEC 18): components and greedy representatives of the link graph at c_max, one pass over the count rows; host answers in node
+// numbers. The caller has validated the index side and holds the context lock
+int components_nodes(gs_ctx *c, const ClusterSource &src, uint32_t c_max, uint64_t *label, gs_derep_info *info);
+int derep_nodes(gs_ctx *c, const ClusterSource &src, uint32_t c_max, const uint64_t *priority, uint64_t *rep_node, uint16_t *rep_count, gs_derep_info *info);
 
 // gs_embed.hip (SPEC 8): the embedding of a device graph in node numbers (embed_common validates nothing: the caller has; on_dev = false: init, pos_out
 // and memb_out are host arrays), and the statistics of a validated device graph (host outputs)

@@ -56,6 +56,9 @@ void set_error(const char *fmt, ...);       // gs_ctx.hip: the text behind gs_la
     /* hnswcore (gs_cluster.hip): gathered rows of a block, candidate list, running (count, position) pairs, sampling, then the k-medoid state */         \
     X(CL_ROWS) X(CL_NODES) X(CL_BEST) X(CL_IN0) X(CL_BLOCKS) X(CL_CORE) X(CL_WEIGHT) X(CL_LABEL) X(CL_P) X(CL_TOT) X(CL_MED) X(CL_DMIN) X(CL_ACC)    \
     X(CL_OUT_NODE) X(CL_OUT_COUNT) X(CL_OUT_ARG)                                                                                                       \
+    /* derep (gs_derep.hip): the nodes in rank order; per node its parent (components) or its rank once it is a representative (greedy); per row of a   \
+       block its cover and its mask of earlier block members; the block's representatives; per node its representative and the count; counters */      \
+    X(DR_ORDER) X(DR_STATE) X(DR_COVER) X(DR_MASK) X(DR_BREP) X(DR_OUT_NODE) X(DR_OUT_COUNT) X(DR_ACC)                                                 \
     /* bigsig (gs_bigsi.hip): unit prefix of a build, the colour block's bitmaps, staging of the host forms and of gs_bigsi_rows */                   \
     X(BIGSI_REC_UNITS) X(BIGSI_GENOME_UNITS) X(BIGSI_BITMAP) X(BIGSI_SEQ) X(BIGSI_REC_START) X(BIGSI_REC_LEN) X(BIGSI_GROUP_OFF) X(BIGSI_OUT_N)       \
     X(BIGSI_OUT_COLOUR) X(BIGSI_OUT_HITS) X(BIGSI_OUT_COUNTS) X(BIGSI_ROW_LIST) X(BIGSI_ROW_WORDS)                                                    \

@@ -749,6 +749,24 @@ int      gs_index_nearest_of(gs_index *, const uint64_t *cand_nodes, uint64_t nc
  * written in any case, and a core_cap below it is GS_ERR_INVALID. Empty index: GS_ERR_STATE; m > 65535 or nb_point x m >= 2^40: GS_ERR_UNSUPPORTED. */
 int      gs_index_cluster(gs_index *, const gs_cluster_params *prm, uint64_t *centre_node_out, uint16_t *centre_count_out, uint64_t *medoids_out,
                           uint64_t *sizes_out, uint64_t *core_nodes_out, uint64_t *core_weight_out, uint64_t core_cap, gs_cluster_info *info_out);
+/* derep (SPEC.md 18): clusters of the database at a distance cut, exact, with no limit on a node's degree, in one pass over the count matrix.
+ * Nodes u != v are LINKED iff their mismatch count is <= c_max, the largest count c with (float)c / (float)m <= max_dist (as in gs_index_exact_search);
+ * equal signatures are linked. Every output is a function of the counts (and, for gs_index_derep, the priorities) alone. */
+typedef struct {
+    uint64_t n_clusters;     /* components / representatives */
+    uint64_t n_singletons;   /* clusters of one node */
+    uint64_t largest;        /* nodes of the largest cluster */
+    uint32_t c_max;          /* the cut as a count */
+    uint32_t reserved;       /* 0 */
+} gs_derep_info;
+/* single linkage: label_out[nb_point] (HOST) = the smallest NODE NUMBER of the node's connected component of the link graph.
+ * max_dist NaN or negative, null outputs: GS_ERR_INVALID; empty index: GS_ERR_STATE; m > 65535: GS_ERR_UNSUPPORTED (also for gs_index_derep). */
+int      gs_index_components(gs_index *, float max_dist, uint64_t *label_out, gs_derep_info *info_out);
+/* greedy representatives (CD-HIT's incremental clustering in its -g 1 form). priority: nb_point HOST values, higher is better, NULL = all equal; the
+ * rank of a node is its position under (priority descending, node number ascending). A node is a representative iff no representative of earlier
+ * rank is linked to it. HOST outputs, nb_point entries: rep_node_out[v] = v and rep_count_out[v] = 0 for a representative, otherwise the NODE NUMBER
+ * of the representative of earlier rank linked to v that minimises (mismatch count, rank), and that count. */
+int      gs_index_derep(gs_index *, float max_dist, const uint64_t *priority, uint64_t *rep_node_out, uint16_t *rep_count_out, gs_derep_info *info_out);
 /* Graph import / export (the role of hnswio::HnswIo::load_hnsw / Hnsw::file_dump, reloadhnsw.rs:41-51,
  * dumpload.rs:31, in this library's own dense layout): levels[n], entry id, layer 0: deg0[n], nbr0[n*2M],
  * cnt0[n*2M] (mismatch counts to the owner); upper layers: upidx[n] (-1 for level-0 nodes) and for the

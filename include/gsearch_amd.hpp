@@ -704,6 +704,28 @@ public:
         check(gs_index_nearest_of(h_, nodes.data(), nodes.size(), arg.data(), cnt.data()));
         return {std::move(arg), std::move(cnt)};
     }
+    // derep (SPEC 18): clusters at a distance cut. components: per node the smallest NODE NUMBER of its connected component of the link graph
+    struct Components { std::vector<uint64_t> label; gs_derep_info info; };
+    Components components(float max_dist) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "components of an empty index");
+        Components r;
+        r.label.resize(get_nb_point());
+        check(gs_index_components(h_, max_dist, r.label.data(), &r.info));
+        return r;
+    }
+    // greedy representatives: per node the NODE NUMBER of its representative (itself for one) and the mismatch count to it; priority: empty = all
+    // equal, otherwise one value per node, higher first
+    struct Derep { std::vector<uint64_t> rep_node; std::vector<uint16_t> rep_count; gs_derep_info info; };
+    Derep derep(float max_dist, const std::vector<uint64_t> &priority = {}) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "derep of an empty index");
+        if (!priority.empty() && priority.size() != get_nb_point()) throw Error(GS_ERR_INVALID, "one priority per node");
+        Derep r;
+        r.rep_node.resize(get_nb_point()); r.rep_count.resize(get_nb_point());
+        check(gs_index_derep(h_, max_dist, priority.empty() ? nullptr : priority.data(), r.rep_node.data(), r.rep_count.data(), &r.info));
+        return r;
+    }
     void file_dump(const std::string &path) const { check(gs_index_save(h_, path.c_str())); }      // dumpload.rs:31 (own format)
     void debug_fill_scratch(int byte) { if (h_) check(gs_index_debug_fill_scratch(h_, byte)); }    // debugging (not for production use): gsearch_amd.h
 private:
