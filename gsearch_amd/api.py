@@ -1326,10 +1326,6 @@ class HmmDb:
         check(self.ctx.L.gs_hmm_trace_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), pair_rec_dev, pair_prof_dev, int(n_pairs), int(max_dom),
                                           int(max_block_cells), raw_out_dev, n_dom_out_dev, dom_out_dev))
 
-    def trace_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_block_cells=0):
-        """trace_packed() with room for every domain: traced again with the largest n_dom when 8 slots a pair do not hold them all"""
-        return _all_items(lambda m: self.trace_packed(aa, rec_start, rec_len, pair_rec, pair_prof, m, max_block_cells), 1)
-
     def envelopes_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_env=8, rows=False, max_block_rows=0):
         """SPEC 13.4: Forward and Backward scores and the posterior envelopes of the pairs (pair_rec[j], pair_prof[j]), all on the device -> (int32 fwd
         [n_pairs] as search_forward_packed() gives it, int32 bck [n_pairs] = bN[0] - null, uint32 n_env [n_pairs] the true number of envelopes, int32 env
@@ -1416,11 +1412,6 @@ class HmmDb:
         check(self.ctx.L.gs_hmm_null2_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), pair_rec_dev, pair_prof_dev, int(n_pairs), int(max_env),
                                           int(max_block_cells), n_env_dev, env_dev, slot_out_dev, seq_bias_out_dev, n2_out_dev, occ_off_dev, occm_out_dev, occi_out_dev))
 
-    def bias_all(self, aa, rec_start, rec_len, pair_rec, pair_prof):
-        """envelopes_all() and null2_packed() behind it -> (fwd, n_env, env, slots, seq_bias)"""
-        fwd, _, ne, env = self.envelopes_all(aa, rec_start, rec_len, pair_rec, pair_prof)
-        return (fwd, ne, env) + self.null2_packed(aa, rec_start, rec_len, pair_rec, pair_prof, ne, env)
-
     def align_packed(self, aa, rec_start, rec_len, pair_rec, pair_prof, n_env, env, columns=False, max_block_cells=0):
         """SPEC 13.6: the optimal-accuracy alignment of the envelopes envelopes_packed() listed for the same pairs (n_env, env as it returned them), all on
         the device -> int32 slots [n_pairs, max_env, 8]: i_from, i_to (record coordinates, 1-based, inclusive), k_from, k_to, oa, n_match, n_ins, n_del of
@@ -1463,8 +1454,8 @@ class HmmDb:
                                           int(max_block_cells), n_env_dev, env_dev, slot_out_dev, col_off_dev, col_out_dev))
 
     def align_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, columns=True):
-        """envelopes_all() and align_packed() behind it -> (fwd, n_env, env) + what align_packed() returns"""
-        fwd, _, ne, env = self.envelopes_all(aa, rec_start, rec_len, pair_rec, pair_prof)
+        """envelopes_packed() with room for every envelope (_all_items) and align_packed() behind it -> (fwd, n_env, env) + what align_packed() returns"""
+        fwd, _, ne, env = _all_items(lambda m: self.envelopes_packed(aa, rec_start, rec_len, pair_rec, pair_prof, m), 2)
         got = self.align_packed(aa, rec_start, rec_len, pair_rec, pair_prof, ne, env, columns=columns)
         return (fwd, ne, env) + (got if columns else (got,))
 
@@ -1473,10 +1464,6 @@ class HmmDb:
         """all device memory; the lengths, the pair list and row_off are read back once"""
         check(self.ctx.L.gs_hmm_envelopes_dev(self.ctx.h, self.h, aa_dev, rec_start_dev, rec_len_dev, int(n_rec), pair_rec_dev, pair_prof_dev, int(n_pairs), int(max_env),
                                               int(max_block_rows), fwd_out_dev, bck_out_dev, n_env_out_dev, env_out_dev, row_off_dev, out_rows_dev, cont_rows_dev))
-
-    def envelopes_all(self, aa, rec_start, rec_len, pair_rec, pair_prof, max_block_rows=0):
-        """envelopes_packed() with room for every envelope: run again with the largest n_env when 8 slots a pair do not hold them all"""
-        return _all_items(lambda m: self.envelopes_packed(aa, rec_start, rec_len, pair_rec, pair_prof, m, max_block_rows=max_block_rows), 2)
 
     def thresholds(self, cutoff="ga"):
         """int32 [n_prof] in units: every profile's GA1, or the caller's bits for all (a number) or per profile (a sequence)"""
@@ -1573,6 +1560,62 @@ def _alignment_text(db, ids, listed, residues_of, n_env, env, slots, cols):
     return b"".join(out)
 
 
+def _table_pairs(scores, seq_bias):
+    """the (record, profile) pairs of the score table of hmmsearch() in its order: those with raw >= 0, by (profile, -(raw - seq_bias), record)"""
+    listed = []
+    for p in range(scores.shape[1]):
+        plain = scores[:, p].astype(np.int64)
+        keep = np.flatnonzero((plain != _lib.HMM_NO_SCORE) & (plain >= 0))
+        col = plain - seq_bias[:, p]
+        listed += [(int(r), p) for r in keep[np.lexsort((keep, -col[keep]))]]
+    return listed
+
+
+def _score_table(db, ids, listed, scores, seq_bias, fwd, bias):
+    """the score table of hmmsearch(), SPEC 13 / 13.1 / 13.5: a row per pair of `listed`; seq_bias: int64 as scores, zeros without bias"""
+    out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga" + (b"\tbias\n" if bias else b"\n")]
+    for r, p in listed:
+        inf = db.info[p]
+        raw = int(scores[r, p]) - int(seq_bias[r, p])
+        b = hmm_bits(raw)
+        if fwd:
+            ev = "%.3E" % hmm_forward_evalue(b, db.tau[p], db.lam_fwd[p], len(ids)) if not np.isnan(db.tau[p]) else "-"
+        else:
+            ev = "%.3E" % hmm_evalue(b, inf["mu"], inf["lam"], len(ids)) if inf["mu"] is not None else "-"
+        ga = "-" if inf["ga_units"] is None else ("1" if raw >= inf["ga_units"] else "0")
+        tail = "\t%.2f\n" % (int(seq_bias[r, p]) / 1024.0) if bias else "\n"
+        out.append(("%s\t%s\t%s\t%.2f\t%s\t%s%s" % (ids[r], inf["name"], inf["acc"] or "-", b, ev, ga, tail)).encode())
+    return b"".join(out)
+
+
+def _domain_table(db, ids, listed, n_dom, dom):
+    """the domain table of hmmsearch(domains=), SPEC 13.2: n_dom, dom as trace_all() returns them for the pairs of `listed`"""
+    out = [b"target\tprofile\tacc\tdom\tn_dom\ti_from\ti_to\tk_from\tk_to\tM\tseg_bits\tn_match\tn_ins\tn_del\n"]
+    for j, (r, p) in enumerate(listed):
+        inf = db.info[p]
+        for d in range(int(n_dom[j])):
+            w = [int(v) for v in dom[j, d]]
+            out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%d\t%d\t%d\n" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(n_dom[j]), w[0], w[1], w[2], w[3],
+                                                                                          inf["M"], w[4] / 1024.0, w[5], w[6], w[7])).encode())
+    return b"".join(out)
+
+
+def _envelope_table(db, ids, listed, n_env, env, slots=None):
+    """the envelope table of hmmsearch(envelopes=), SPEC 13.4: n_env, env as envelopes_all() returns them for the pairs of `listed`; slots: their null2
+    slots with bias (SPEC 13.5), which take dom_bias off env_bits and add the column `env_bias`"""
+    bias = slots is not None
+    out = [b"target\tprofile\tacc\tenv\tn_env\ti_from\ti_to\tenv_bits\tpeak_occ" + (b"\tenv_bias\n" if bias else b"\n")]
+    for j, (r, p) in enumerate(listed):
+        inf = db.info[p]
+        for d in range(int(n_env[j])):
+            w = [int(v) for v in env[j, d]]
+            db_ = int(slots[j, d, 1]) if bias else 0
+            tail = "\t%.2f\n" % (db_ / 1024.0) if bias else "\n"
+            out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%.2f\t%.3f%s" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(n_env[j]), w[0], w[1], (w[2] - db_) / 1024.0,
+                                                                     1.0 - 2.0 ** (w[3] / 1024.0), tail)).encode())
+    return b"".join(out)
+
+
 def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, domains=None, translate=False, min_aa=_lib.ORF_MIN_AA, table=11, prefilter=None,
               msv_p=0.02, envelopes=None, bias=False, alignments=None):
     """Library counterpart of `hmmsearch_rs -f proteome.faa -m profile.HMM`: every protein of `faa` (.faa, also .gz / .bz2 / .xz) against every profile of
@@ -1625,110 +1668,43 @@ def hmmsearch(faa, hmm, output=None, ctx=None, score="viterbi", filter_p=1e-3, d
     db = _as_hmm_db(hmm, ctx)
     fwd = score == "forward"
     vf_floor = db.vf_floor(fwd, filter_p) if pre_vit16 else None
-    dev = None
-    if translate:
-        dev = _dev_targets(db.ctx, [_fna_contigs(faa)], translate, min_aa, _orf_max_aa(fwd or envelopes is not None or alignments is not None, domains is not None), table)
-        aa = rs = rl = None
-        try:
-            ids = dev.names()
-            scores = dev.search(db, fwd, filter_p, pre_msv, msv_p, vf_floor)
-        except Exception:
-            dev.close()
-            raise
-    else:
-        ids, seqs = _faa_records(faa)
-        aa, rs, rl = filter_aa_records([bytes(q) for q in seqs])
-        if pre_vit16:
-            scores = db.search_staged_packed(aa, rs, rl, vf_floor, msv=pre_msv, msv_p=msv_p, forward=fwd, filter_p=filter_p)[-1]
-        elif pre_msv:
-            scores = db.search_filtered_packed(aa, rs, rl, msv_p=msv_p, forward=fwd, filter_p=filter_p)[2 if fwd else 1]
-        else:
-            scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if fwd else db.search_packed(aa, rs, rl)
-    Z = len(ids)
-    out = [b"target\tprofile\tacc\tbits\tevalue\tpass_ga" + (b"\tbias\n" if bias else b"\n")]
-    listed = []                                                          # the (record, profile) pairs of the table, in its order
-    seq_bias = np.zeros(scores.shape, np.int64)                          # of the pairs that get a row, with bias
-    if bias:
-        try:
-            cand = np.argwhere((scores != _lib.HMM_NO_SCORE) & (scores.astype(np.int64) >= 0))
-            cr, cp = cand[:, 0].astype(np.uint32), cand[:, 1].astype(np.uint32)
-            b_ne, b_env, b_slots, b_sb = (dev.bias_all(db, cr, cp) if dev is not None else db.bias_all(aa, rs, rl, cr, cp))[1:]
-            seq_bias[cand[:, 0], cand[:, 1]] = b_sb
-            slot_of = {(int(r), int(p)): j for j, (r, p) in enumerate(cand)}
-        except Exception:
-            if dev is not None:
-                dev.close()
-            raise
-    for p, inf in enumerate(db.info):
-        plain = scores[:, p].astype(np.int64)
-        keep = np.flatnonzero((plain != _lib.HMM_NO_SCORE) & (plain >= 0))
-        col = plain - seq_bias[:, p]
-        for r in keep[np.lexsort((keep, -col[keep]))]:
-            listed.append((int(r), p))
-            raw = int(col[r])
-            b = hmm_bits(raw)
-            if fwd:
-                ev = "%.3E" % hmm_forward_evalue(b, db.tau[p], db.lam_fwd[p], Z) if not np.isnan(db.tau[p]) else "-"
-            else:
-                ev = "%.3E" % hmm_evalue(b, inf["mu"], inf["lam"], Z) if inf["mu"] is not None else "-"
-            ga = "-" if inf["ga_units"] is None else ("1" if raw >= inf["ga_units"] else "0")
-            tail = "\t%.2f\n" % (int(seq_bias[r, p]) / 1024.0) if bias else "\n"
-            out.append(("%s\t%s\t%s\t%.2f\t%s\t%s%s" % (ids[r], inf["name"], inf["acc"] or "-", b, ev, ga, tail)).encode())
-    table = b"".join(out)
-    if output is not None:
-        with open(output, "wb") as f:
-            f.write(table)
-    if domains is None and envelopes is None and alignments is None:
-        if dev is not None:
-            dev.close()
-        return ids, scores, table
-    pr, pp = np.array([r for r, _ in listed], np.uint32), np.array([p for _, p in listed], np.uint32)
+    enveloped = envelopes is not None or alignments is not None
+    dev = _dev_targets(db.ctx, [faa], translate, min_aa, _orf_max_aa(fwd or enveloped, domains is not None), table)
     try:
+        ids = dev.names()
+        scores = dev.search(db, fwd, filter_p, pre_msv, msv_p, vf_floor)
+        seq_bias = np.zeros(scores.shape, np.int64)                      # of the pairs that get a row, with bias
+        if bias:
+            cand = np.argwhere((scores != _lib.HMM_NO_SCORE) & (scores.astype(np.int64) >= 0))
+            b_ne, b_env, b_slots, b_sb = dev.bias_all(db, cand[:, 0].astype(np.uint32), cand[:, 1].astype(np.uint32))[1:]
+            seq_bias[cand[:, 0], cand[:, 1]] = b_sb
+        listed = _table_pairs(scores, seq_bias)
+        texts = [(output, _score_table(db, ids, listed, scores, seq_bias, fwd, bias))]
+        if output is not None:                                           # the score table stands even if a pass below refuses its pairs
+            with open(output, "wb") as f:
+                f.write(texts[0][1])
+        pr, pp = np.array([r for r, _ in listed], np.uint32), np.array([p for _, p in listed], np.uint32)
         if domains is not None:
-            _, nd, dom = dev.trace_all(db, pr, pp) if dev is not None else db.trace_all(aa, rs, rl, pr, pp)
-        if (envelopes is not None or alignments is not None) and bias:  # the candidates' envelopes, in the table's order
+            _, nd, dom = dev.trace_all(db, pr, pp)
+            texts.append((domains, _domain_table(db, ids, listed, nd, dom)))
+        slots = None
+        if enveloped and bias:                                           # the candidates' envelopes, in the table's order
+            slot_of = {(int(r), int(p)): j for j, (r, p) in enumerate(cand)}
             order = [slot_of[rp] for rp in listed]
             ne, env, slots = b_ne[order], b_env[order], b_slots[order]
-        elif envelopes is not None or alignments is not None:
-            _, _, ne, env = dev.envelopes_all(db, pr, pp) if dev is not None else db.envelopes_all(aa, rs, rl, pr, pp)
-        ali_text = None
+        elif enveloped:
+            _, _, ne, env = dev.envelopes_all(db, pr, pp)
+        if envelopes is not None:
+            texts.append((envelopes, _envelope_table(db, ids, listed, ne, env, slots)))
         if alignments is not None:                                       # every listed envelope aligned, over the envelopes found above
-            a_slots, a_cols = dev.align_listed(db, pr, pp, ne, env) if dev is not None else db.align_packed(aa, rs, rl, pr, pp, ne, env, columns=True)
-            ali_text = _alignment_text(db, ids, listed, (lambda r: dev.residues(r)) if dev is not None else (lambda r: aa[int(rs[r]):int(rs[r]) + int(rl[r])]), ne, env,
-                                       a_slots, a_cols)
-            with open(alignments, "wb") as f:
-                f.write(ali_text)
+            a_slots, a_cols = dev.align_listed(db, pr, pp, ne, env)
+            texts.append((alignments, _alignment_text(db, ids, listed, dev.residues, ne, env, a_slots, a_cols)))
     finally:
-        if dev is not None:
-            dev.close()
-    env_table = None
-    if envelopes is not None:
-        out = [b"target\tprofile\tacc\tenv\tn_env\ti_from\ti_to\tenv_bits\tpeak_occ" + (b"\tenv_bias\n" if bias else b"\n")]
-        for j, (r, p) in enumerate(listed):
-            inf = db.info[p]
-            for d in range(int(ne[j])):
-                w = [int(v) for v in env[j, d]]
-                db_ = int(slots[j, d, 1]) if bias else 0
-                tail = "\t%.2f\n" % (db_ / 1024.0) if bias else "\n"
-                out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%.2f\t%.3f%s" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(ne[j]), w[0], w[1], (w[2] - db_) / 1024.0,
-                                                                         1.0 - 2.0 ** (w[3] / 1024.0), tail)).encode())
-        env_table = b"".join(out)
-        with open(envelopes, "wb") as f:
-            f.write(env_table)
-    tail = () if ali_text is None else (ali_text,)
-    if domains is None:
-        return (ids, scores, table) + (() if env_table is None else (env_table,)) + tail
-    out = [b"target\tprofile\tacc\tdom\tn_dom\ti_from\ti_to\tk_from\tk_to\tM\tseg_bits\tn_match\tn_ins\tn_del\n"]
-    for j, (r, p) in enumerate(listed):
-        inf = db.info[p]
-        for d in range(int(nd[j])):
-            w = [int(v) for v in dom[j, d]]
-            out.append(("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%.2f\t%d\t%d\t%d\n" % (ids[r], inf["name"], inf["acc"] or "-", d + 1, int(nd[j]), w[0], w[1], w[2], w[3],
-                                                                                          inf["M"], w[4] / 1024.0, w[5], w[6], w[7])).encode())
-    dom_table = b"".join(out)
-    with open(domains, "wb") as f:
-        f.write(dom_table)
-    return (ids, scores, table, dom_table) + (() if env_table is None else (env_table,)) + tail
+        dev.close()
+    for path, text in texts[1:]:
+        with open(path, "wb") as f:
+            f.write(text)
+    return (ids, scores) + tuple(text for _, text in texts)
 
 
 def _bias_best_hits(scores, goff, thr, bias_of):
@@ -1752,6 +1728,22 @@ def _bias_best_hits(scores, goff, thr, bias_of):
         if corrected[j] >= thr[p] and rec[g, p] == _lib.HMM_NO_HIT:
             rec[g, p] = cand[j, 0]
     return rec
+
+
+def _region_spans(dev, db, rec, region):
+    """the cut of universal_genes(region=) per hit of the best-hit matrix `rec` over the targets `dev`: {g * n_prof + p: (a, b)}, residues [a, b) of the
+    record, from i_from of the hit's first domain ("aligned"), posterior envelope ("envelope") or aligned envelope ("alignment") through i_to of its
+    last. A hit that has none is not in the dict: it keeps its whole record, as every hit of region "protein" does"""
+    if region == "protein" or not (rec != _lib.HMM_NO_HIT).any():
+        return {}
+    pr, pp = rec.reshape(-1), np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
+    if region == "aligned":
+        _, n_item, item = dev.trace_all(db, pr, pp)
+    elif region == "envelope":
+        _, _, n_item, item = dev.envelopes_all(db, pr, pp)
+    else:
+        _, n_item, _, item = dev.align_all(db, pr, pp, columns=False)
+    return {int(j): (int(item[j, 0, 0]) - 1, int(item[j, int(n_item[j]) - 1, 1])) for j in np.flatnonzero(n_item)}
 
 
 def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filter_p=1e-3, region="protein", translate=False, min_aa=_lib.ORF_MIN_AA, table=11,
@@ -1789,51 +1781,38 @@ def universal_genes(faa_files, hmm, ctx=None, cutoff="ga", score="viterbi", filt
         raise ValueError("bias=True corrects Forward scores: score='forward'")
     pre_msv, pre_vit16 = _check_prefilter(prefilter)
     db = _as_hmm_db(hmm, ctx)
-    vf_floor = db.vf_floor(score == "forward", filter_p, cutoff) if pre_vit16 else None
-    if translate:
-        return _universal_genes_translated(db, faa_files, cutoff, score == "forward", filter_p, region == "aligned", min_aa, table, translate, pre_msv,
-                                           msv_p, region == "envelope", bias, region == "alignment", vf_floor)
-    seqs, goff = [], [0]
-    for path in faa_files:
-        seqs.extend(_faa_records(path)[1])
-        goff.append(len(seqs))
-    aa, rs, rl = filter_aa_records([bytes(s) for s in seqs])
-    if pre_vit16:
-        scores = db.search_staged_packed(aa, rs, rl, vf_floor, msv=pre_msv, msv_p=msv_p, forward=score == "forward", filter_p=filter_p)[-1]
-    elif pre_msv:
-        scores = db.search_filtered_packed(aa, rs, rl, msv_p=msv_p, forward=score == "forward", filter_p=filter_p)[2 if score == "forward" else 1]
-    else:
-        scores = db.search_forward_packed(aa, rs, rl, filter_p=filter_p)[1] if score == "forward" else db.search_packed(aa, rs, rl)
-    if bias:
-        rec = _bias_best_hits(scores, goff, db.thresholds(cutoff), lambda pr, pp: db.bias_all(aa, rs, rl, pr, pp)[4])
-    else:
-        rec, _ = db.best_hits(scores, np.array(goff, np.uint64), cutoff)
-    span = {}
-    if region == "aligned" and rec.size:
-        pair_prof = np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
-        _, nd, dom = db.trace_all(aa, rs, rl, rec.reshape(-1), pair_prof)
-        for j in np.flatnonzero(nd):
-            span[int(j)] = (int(dom[j, 0, 0]) - 1, int(dom[j, int(nd[j]) - 1, 1]))
-    if region == "envelope" and rec.size:
-        pair_prof = np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
-        _, _, ne, env = db.envelopes_all(aa, rs, rl, rec.reshape(-1), pair_prof)
-        for j in np.flatnonzero(ne):
-            span[int(j)] = (int(env[j, 0, 0]) - 1, int(env[j, int(ne[j]) - 1, 1]))
-    if region == "alignment" and rec.size:
-        pair_prof = np.tile(np.arange(len(db), dtype=np.uint32), rec.shape[0])
-        _, ne, env, slots = db.align_all(aa, rs, rl, rec.reshape(-1), pair_prof, columns=False)
-        for j in np.flatnonzero(ne):
-            span[int(j)] = (int(slots[j, 0, 0]) - 1, int(slots[j, int(ne[j]) - 1, 1]))
-    genomes = []
-    for g in range(len(goff) - 1):
-        hits = []
-        for p, r in enumerate(rec[g]):
-            if r != _lib.HMM_NO_HIT:
-                a, b = span.get(g * len(db) + p, (0, int(rl[r])))
-                hits.append(bytes(aa[int(rs[r]) + a:int(rs[r]) + b]))
-        genomes.append(hits)
-    local = np.where(rec == _lib.HMM_NO_HIT, rec, rec - np.array(goff[:-1], np.uint32)[:, None]).astype(np.uint32)
-    return genomes, local
+    fwd = score == "forward"
+    vf_floor = db.vf_floor(fwd, filter_p, cutoff) if pre_vit16 else None
+    ctx = db.ctx
+    dev = _dev_targets(ctx, faa_files, translate, min_aa, _orf_max_aa(fwd or region in ("envelope", "alignment"), region == "aligned"), table)
+    try:
+        ng, npf = len(dev.genome_orf_off) - 1, len(db)
+        rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
+        if ng and npf and dev.n:
+            d_score = dev.search_dev(db, fwd, filter_p, pre_msv, msv_p, vf_floor)
+            if bias:
+                rec = _bias_best_hits(ctx.download(d_score, (dev.n, npf), np.int32), dev.genome_orf_off, db.thresholds(cutoff), lambda pr, pp: dev.bias_all(db, pr, pp)[4])
+            else:
+                d_goff, d_thr = dev.mem.up(dev.genome_orf_off), dev.mem.up(db.thresholds(cutoff))
+                d_rec, d_sc = dev.mem.new(4 * ng * npf), dev.mem.new(4 * ng * npf)
+                db.best_hits_dev(d_score, dev.n, d_goff, ng, d_thr, d_rec, d_sc)
+                rec = ctx.download(d_rec, (ng, npf), np.uint32)
+        span = _region_spans(dev, db, rec, region)
+        genomes = []
+        for g in range(ng):
+            hits = []
+            for p, r in enumerate(rec[g]):
+                if r != _lib.HMM_NO_HIT:
+                    a, b = span.get(g * npf + p, (0, int(dev.aa_len[r])))
+                    hits.append(dev.residues(int(r), a, b))
+                    if translate:
+                        c, ob, oe, st = dev.coords(int(r))
+                        where[g, p] = (c - int(dev.genome_contig0[g]), ob, oe, st)
+            genomes.append(hits)
+        local = np.where(rec == _lib.HMM_NO_HIT, rec, rec - dev.genome_orf_off[:-1].astype(np.uint32)[:, None]).astype(np.uint32)
+        return (genomes, local, where) if translate else (genomes, local)
+    finally:
+        dev.close()
 
 
 # ---- orfs (SPEC 14): stop-to-stop six-frame translation on the device ----------------------------------------------------------------------
@@ -1941,38 +1920,14 @@ def _orf_max_aa(fwd, traced):
     return min([_lib.HMM_MAX_L] + ([_lib.HMM_FWD_MAX_L] if fwd else []) + ([_lib.HMM_TRACE_MAX_L] if traced else []))
 
 
-class _DevOrfs:
-    """The ORFs of some genomes (each a list of (contig id, bases)), translated on the device and kept there in the layout gs_hmm_search_dev reads; the
-    host holds their descriptors, never their residues."""
+class _DevTargets:
+    """The protein targets of hmmsearch(), universal_genes() and universal_sketch() in device memory, in the layout gs_hmm_search_dev reads, and every
+    pass over them. A source (_DevOrfs, _DevGenes, _DevProteins) is a constructor that leaves: n targets (n_long: those dropped for their length) with
+    residues d_aa, starts d_as and lengths d_al on the device under `mem`; aa_start, aa_len, the host copies of the last two; genome_orf_off
+    [n_genomes + 1], the first target of every genome. The host holds the descriptors; whether it holds residues is the source's matter (residues())."""
 
-    def __init__(self, ctx, genomes, min_aa, max_aa, table):
+    def __init__(self, ctx):
         self.ctx, self.mem = ctx, _DevScope(ctx)
-        self.contig_ids = [cid for g in genomes for cid, _ in g]
-        contig_genome = [gi for gi, g in enumerate(genomes) for _ in g]
-        self.genome_contig0 = np.concatenate([[0], np.cumsum([len(g) for g in genomes])]).astype(np.int64)
-        recs, self.rec_contig, self.rec_offset = _orf_segments([c for g in genomes for _, c in g])
-        seq, rs, rl = pack_dna_records(recs)
-        cap_orf, cap_aa = _orf_caps(rl, min_aa)
-        n_rec = len(rs)
-        try:
-            d_seq, d_rs, d_rl = self.mem.up(seq), self.mem.up(rs), self.mem.up(rl)
-            self.d_orf, self.d_aa, self.d_as, self.d_al = self.mem.new(16 * cap_orf), self.mem.new(cap_aa), self.mem.new(8 * cap_orf), self.mem.new(8 * cap_orf)
-            d_off = self.mem.new(8 * (n_rec + 1))
-            self.n, n_aa, self.n_long = orf_translate_dev(ctx, d_seq, seq.nbytes, d_rs, d_rl, n_rec, cap_orf, cap_aa, self.d_orf, self.d_aa, self.d_as, self.d_al, d_off,
-                                                          min_aa, max_aa, table)
-            self.orf = ctx.download(self.d_orf, (self.n,), ORF_DTYPE)
-            self.aa_start = ctx.download(self.d_as, (self.n,), np.uint64)
-            self.aa_len = ctx.download(self.d_al, (self.n,), np.uint64)
-            rec_orf_off = ctx.download(d_off, (n_rec + 1,), np.uint64)
-            for ptr in (d_seq, d_rs, d_rl, d_off):
-                self.mem.free(ptr)
-        except Exception:
-            self.close()
-            raise
-        # the first record of every genome -> its first ORF
-        rec_genome = np.array([contig_genome[c] for c in self.rec_contig], np.int64)
-        first_rec = np.searchsorted(rec_genome, np.arange(len(genomes) + 1))
-        self.genome_orf_off = rec_orf_off[first_rec].astype(np.uint64)
 
     def close(self):
         self.mem.close()
@@ -1984,13 +1939,8 @@ class _DevOrfs:
         except Exception:
             pass
 
-    def coords(self, j):
-        """(contig index, begin, end, strand) of ORF j in contig coordinates"""
-        o = self.orf[j]
-        b = int(self.rec_offset[o["rec"]]) + int(o["begin"])
-        return int(self.rec_contig[o["rec"]]), b, b + 3 * int(self.aa_len[j]), int(o["strand"])
-
     def names(self):
+        """a target cut from a contig is named by its coords() as write_orf_faa() names it (a source of whole proteins keeps their ids instead)"""
         out = []
         for j in range(self.n):
             c, b, e, s = self.coords(j)
@@ -1998,7 +1948,7 @@ class _DevOrfs:
         return out
 
     def search_dev(self, db, fwd, filter_p, prefilter=False, msv_p=0.02, vf_floor=None):
-        """device int32 [n, n_prof] scores of the ORFs (Forward behind the Viterbi floor when fwd; behind the MSV floor of msv_p when prefilter, SPEC
+        """device int32 [n, n_prof] scores of the targets (Forward behind the Viterbi floor when fwd; behind the MSV floor of msv_p when prefilter, SPEC
         13.3; behind the int16 filter at vf_floor when that is given, SPEC 13.7); the caller frees through close()"""
         d_score = self.mem.new(4 * self.n * len(db))
         if self.n == 0:
@@ -2047,17 +1997,18 @@ class _DevOrfs:
             return _all_items(run, len(outs(n, 8)) - 2)
 
     def trace_all(self, db, pair_rec, pair_prof):
-        """HmmDb.trace_all() over the device residues"""
+        """what HmmDb.trace_packed() returns, with room for every domain -> (raw, n_dom, dom)"""
         return self._over_pairs(db.trace_dev, pair_rec, pair_prof, lambda n, m: [((n,), np.int32, _lib.HMM_NO_SCORE), ((n,), np.uint32, 0),
                                                                                  ((n, m, _lib.HMM_DOM_WORDS), np.int32, 0)])
 
     def envelopes_all(self, db, pair_rec, pair_prof):
-        """HmmDb.envelopes_all() over the device residues -> (fwd, bck, n_env, env)"""
+        """what HmmDb.envelopes_packed() returns, with room for every envelope -> (fwd, bck, n_env, env)"""
         return self._over_pairs(db.envelopes_dev, pair_rec, pair_prof, lambda n, m: [((n,), np.int32, _lib.HMM_NO_SCORE), ((n,), np.int32, _lib.HMM_NO_SCORE),
                                                                                      ((n,), np.uint32, 0), ((n, m, _lib.HMM_ENV_WORDS), np.int32, 0)])
 
     def bias_all(self, db, pair_rec, pair_prof):
-        """HmmDb.bias_all() over the device residues -> (fwd, n_env, env, slots, seq_bias): the envelopes stay on the device between the two calls"""
+        """envelopes_all() and what HmmDb.null2_packed() returns for them -> (fwd, n_env, env, slots, seq_bias): the envelopes stay on the device between
+        the two calls"""
         pr, pp, _ = _pairs(pair_rec, pair_prof)
         n = len(pr)
         if n == 0 or self.n == 0:
@@ -2080,80 +2031,81 @@ class _DevOrfs:
             got = run(8)
             return got if got[0] is not None else run(int(got[1].max()))
 
-    def align_listed(self, db, pair_rec, pair_prof, n_env, env):
-        """HmmDb.align_packed(columns=True) over the device residues, for envelopes as envelopes_all() returned them -> (slots, columns)"""
+    def align_listed(self, db, pair_rec, pair_prof, n_env, env, columns=True):
+        """what HmmDb.align_packed() returns for envelopes as envelopes_all() returned them -> (slots, columns); columns=False: no column is built, slots"""
         pr, pp, _ = _pairs(pair_rec, pair_prof)
         n = len(pr)
         ne, env = np.ascontiguousarray(n_env, dtype=np.uint32), np.ascontiguousarray(env, dtype=np.int32)
         m = env.shape[1]
         if n == 0 or self.n == 0:
-            return np.zeros((n, m, _lib.HMM_ALI_WORDS), np.int32), [[] for _ in range(n)]
-        lens = np.where(pr < self.n, self.aa_len[np.minimum(pr, self.n - 1)], 0)
-        M = db.M[pp].astype(np.int64)
-        co = _ali_col_off(lens, ne, env, M)
+            slots = np.zeros((n, m, _lib.HMM_ALI_WORDS), np.int32)
+            return (slots, [[] for _ in range(n)]) if columns else slots
         with _DevScope(self.ctx) as d:
-            d_slot, d_col = d.new(4 * n * m * _lib.HMM_ALI_WORDS), d.new(8 * max(int(co[-1]), 1))
-            db.align_dev(self.d_aa, self.d_as, self.d_al, self.n, d.up(pr), d.up(pp), n, m, d.up(ne), d.up(env), d_slot, d.up(co), d_col)
+            d_slot, d_co, d_col = d.new(4 * n * m * _lib.HMM_ALI_WORDS), None, None
+            if columns:
+                lens = np.where(pr < self.n, self.aa_len[np.minimum(pr, self.n - 1)], 0)
+                M = db.M[pp].astype(np.int64)
+                co = _ali_col_off(lens, ne, env, M)
+                d_co, d_col = d.up(co), d.new(8 * max(int(co[-1]), 1))
+            db.align_dev(self.d_aa, self.d_as, self.d_al, self.n, d.up(pr), d.up(pp), n, m, d.up(ne), d.up(env), d_slot, d_co, d_col)
             slots = self.ctx.download(d_slot, (n, m, _lib.HMM_ALI_WORDS), np.int32)
+            if not columns:
+                return slots
             cols = self.ctx.download(d_col, (max(int(co[-1]), 1), 2), np.int32)
         return slots, _ali_columns(slots, cols, co, ne, env, M)
 
-    def align_all(self, db, pair_rec, pair_prof):
-        """HmmDb.align_all() over the device residues -> (fwd, n_env, env, slots, columns)"""
+    def align_all(self, db, pair_rec, pair_prof, columns=True):
+        """envelopes_all() and align_listed() behind it -> (fwd, n_env, env, slots[, columns])"""
         fwd, _, ne, env = self.envelopes_all(db, pair_rec, pair_prof)
-        return (fwd, ne, env) + self.align_listed(db, pair_rec, pair_prof, ne, env)
+        got = self.align_listed(db, pair_rec, pair_prof, ne, env, columns)
+        return (fwd, ne, env) + (got if columns else (got,))
 
     def residues(self, j, a=0, b=None):
-        """residues [a, b) of ORF j, read back from the device"""
+        """residues [a, b) of target j, read back from the device"""
         b = int(self.aa_len[j]) if b is None else b
         if b <= a:
             return b""
         return self.ctx.download(self.d_aa + int(self.aa_start[j]) + a, (b - a,), np.uint8).tobytes()
 
 
-def _universal_genes_translated(db, fna_files, cutoff, fwd, filter_p, aligned, min_aa, table, translate=True, prefilter=False, msv_p=0.02, envelope=False, bias=False,
-                                alignment=False, vf_floor=None):
-    ctx = db.ctx
-    dev = _dev_targets(ctx, [_fna_contigs(p) for p in fna_files], translate, min_aa, _orf_max_aa(fwd or envelope or alignment, aligned), table)
-    try:
-        ng, npf = len(fna_files), len(db)
-        rec, where = np.full((ng, npf), _lib.HMM_NO_HIT, np.uint32), np.full((ng, npf, 4), -1, np.int64)
-        if ng and npf and dev.n:
-            d_score = dev.search_dev(db, fwd, filter_p, prefilter, msv_p, vf_floor)
-            if bias:
-                rec = _bias_best_hits(ctx.download(d_score, (dev.n, npf), np.int32), dev.genome_orf_off, db.thresholds(cutoff), lambda pr, pp: dev.bias_all(db, pr, pp)[4])
-            else:
-                d_goff, d_thr = dev.mem.up(dev.genome_orf_off), dev.mem.up(db.thresholds(cutoff))
-                d_rec, d_sc = dev.mem.new(4 * ng * npf), dev.mem.new(4 * ng * npf)
-                db.best_hits_dev(d_score, dev.n, d_goff, ng, d_thr, d_rec, d_sc)
-                rec = ctx.download(d_rec, (ng, npf), np.uint32)
-        span = {}
-        if aligned and (rec != _lib.HMM_NO_HIT).any():
-            _, nd, dom = dev.trace_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
-            for j in np.flatnonzero(nd):
-                span[int(j)] = (int(dom[j, 0, 0]) - 1, int(dom[j, int(nd[j]) - 1, 1]))
-        if envelope and (rec != _lib.HMM_NO_HIT).any():
-            _, _, ne, env = dev.envelopes_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
-            for j in np.flatnonzero(ne):
-                span[int(j)] = (int(env[j, 0, 0]) - 1, int(env[j, int(ne[j]) - 1, 1]))
-        if alignment and (rec != _lib.HMM_NO_HIT).any():
-            _, ne, env, slots, _ = dev.align_all(db, rec.reshape(-1), np.tile(np.arange(npf, dtype=np.uint32), ng))
-            for j in np.flatnonzero(ne):
-                span[int(j)] = (int(slots[j, 0, 0]) - 1, int(slots[j, int(ne[j]) - 1, 1]))
-        genomes = []
-        for g in range(ng):
-            hits = []
-            for p, r in enumerate(rec[g]):
-                if r != _lib.HMM_NO_HIT:
-                    a, b = span.get(g * npf + p, (0, int(dev.aa_len[r])))
-                    hits.append(dev.residues(int(r), a, b))
-                    c, ob, oe, st = dev.coords(int(r))
-                    where[g, p] = (c - int(dev.genome_contig0[g]), ob, oe, st)
-            genomes.append(hits)
-        local = np.where(rec == _lib.HMM_NO_HIT, rec, rec - dev.genome_orf_off[:-1].astype(np.uint32)[:, None]).astype(np.uint32)
-        return genomes, local, where
-    finally:
-        dev.close()
+class _DevOrfs(_DevTargets):
+    """The stop-to-stop six-frame ORFs of some genomes (each a list of (contig id, bases)), translated on the device (SPEC 14): their residues never
+    come to the host. `orf` holds begin, rec and strand of each."""
+
+    def __init__(self, ctx, genomes, min_aa, max_aa, table):
+        super().__init__(ctx)
+        self.contig_ids = [cid for g in genomes for cid, _ in g]
+        contig_genome = [gi for gi, g in enumerate(genomes) for _ in g]
+        self.genome_contig0 = np.concatenate([[0], np.cumsum([len(g) for g in genomes])]).astype(np.int64)
+        recs, self.rec_contig, self.rec_offset = _orf_segments([c for g in genomes for _, c in g])
+        seq, rs, rl = pack_dna_records(recs)
+        cap_orf, cap_aa = _orf_caps(rl, min_aa)
+        n_rec = len(rs)
+        try:
+            d_seq, d_rs, d_rl = self.mem.up(seq), self.mem.up(rs), self.mem.up(rl)
+            self.d_orf, self.d_aa, self.d_as, self.d_al = self.mem.new(16 * cap_orf), self.mem.new(cap_aa), self.mem.new(8 * cap_orf), self.mem.new(8 * cap_orf)
+            d_off = self.mem.new(8 * (n_rec + 1))
+            self.n, n_aa, self.n_long = orf_translate_dev(ctx, d_seq, seq.nbytes, d_rs, d_rl, n_rec, cap_orf, cap_aa, self.d_orf, self.d_aa, self.d_as, self.d_al, d_off,
+                                                          min_aa, max_aa, table)
+            self.orf = ctx.download(self.d_orf, (self.n,), ORF_DTYPE)
+            self.aa_start = ctx.download(self.d_as, (self.n,), np.uint64)
+            self.aa_len = ctx.download(self.d_al, (self.n,), np.uint64)
+            rec_orf_off = ctx.download(d_off, (n_rec + 1,), np.uint64)
+            for ptr in (d_seq, d_rs, d_rl, d_off):
+                self.mem.free(ptr)
+        except Exception:
+            self.close()
+            raise
+        # the first record of every genome -> its first ORF
+        rec_genome = np.array([contig_genome[c] for c in self.rec_contig], np.int64)
+        first_rec = np.searchsorted(rec_genome, np.arange(len(genomes) + 1))
+        self.genome_orf_off = rec_orf_off[first_rec].astype(np.uint64)
+
+    def coords(self, j):
+        """(contig index, begin, end, strand) of ORF j in contig coordinates"""
+        o = self.orf[j]
+        b = int(self.rec_offset[o["rec"]]) + int(o["begin"])
+        return int(self.rec_contig[o["rec"]]), b, b + 3 * int(self.aa_len[j]), int(o["strand"])
 
 
 # ---- genes (SPEC 15): a self-trained gene caller on the device --------------------------------------------------------------------------------
@@ -2375,12 +2327,12 @@ def genecall(fna, prefix, ctx=None, **params):
     return {"n_genes": len(flat["gene"]), "trained": bool(flat["info"][0, 1] & _lib.GENE_TRAINED), "Nc": int(flat["info"][0, 0])}
 
 
-class _DevGenes(_DevOrfs):
-    """The genes of some genomes (SPEC 15) in the place of their ORFs: called on the device and kept there in the same layout, so every search of
-    _DevOrfs runs on them unchanged. `orf` holds begin, rec and strand of each gene; `end` its end (the stop codon included where there is one)."""
+class _DevGenes(_DevTargets):
+    """The genes of some genomes (SPEC 15) in the place of their ORFs: called on the device, every genome self-trained. `orf` holds begin, rec and
+    strand of each gene; `end` its end (the stop codon included where there is one)."""
 
     def __init__(self, ctx, genomes, min_aa, max_aa, table, gene=None):
-        self.ctx, self.mem = ctx, _DevScope(ctx)
+        super().__init__(ctx)
         self.contig_ids = [cid for g in genomes for cid, _ in g]
         recs, self.rec_contig, self.rec_offset, goff, contig0 = _gene_segments([[c for _, c in g] for g in genomes])
         self.genome_contig0 = contig0
@@ -2418,8 +2370,42 @@ class _DevGenes(_DevOrfs):
         return int(self.rec_contig[o["rec"]]), off + int(o["begin"]), off + int(self.end[j]), int(o["strand"])
 
 
-def _dev_targets(ctx, genomes, translate, min_aa, max_aa, table, gene=None):
-    """gene: further gene_call parameters of translate="genes" (min_aa and table are the call's own)"""
+class _DevProteins(_DevTargets):
+    """The records of some protein FASTA files, one genome a file: filtered as the AA sketchers filter and uploaded once. Target j is record
+    j - genome_orf_off[g] of file g. The filtered residues stay on the host too (`aa`), so that reading a hit is no device call."""
+
+    def __init__(self, ctx, faa_files):
+        super().__init__(ctx)
+        self.ids, seqs, goff = [], [], [0]
+        for path in faa_files:
+            ids, recs = _faa_records(path)
+            self.ids.extend(ids)
+            seqs.extend(recs)
+            goff.append(len(seqs))
+        self.aa, self.aa_start, self.aa_len = filter_aa_records([bytes(s) for s in seqs])
+        self.n, self.n_long = len(seqs), 0
+        self.genome_orf_off = np.array(goff, np.uint64)
+        try:
+            self.d_aa, self.d_as, self.d_al = self.mem.up(self.aa), self.mem.up(self.aa_start), self.mem.up(self.aa_len)
+        except Exception:
+            self.close()
+            raise
+
+    def names(self):
+        return list(self.ids)
+
+    def residues(self, j, a=0, b=None):
+        """residues [a, b) of record j, from the host copy"""
+        s = int(self.aa_start[j])
+        return self.aa[s + a:s + (int(self.aa_len[j]) if b is None else b)].tobytes()
+
+
+def _dev_targets(ctx, files, translate, min_aa, max_aa, table, gene=None):
+    """the targets of some files, one genome a file: the records of protein FASTA (translate falsy), else of nucleotide FASTA the six-frame ORFs or
+    (translate="genes") the called genes. gene: further gene_call parameters (min_aa and table are the call's own)"""
+    if not translate:
+        return _DevProteins(ctx, files)
+    genomes = [_fna_contigs(p) for p in files]
     if translate == "genes":
         return _DevGenes(ctx, genomes, min_aa, max_aa, table, gene)
     return _DevOrfs(ctx, genomes, min_aa, max_aa, table)
@@ -2481,26 +2467,6 @@ def hit_records(best_rec, aa, rec_start, rec_len, n_item=None, item=None, cap_re
     return o_aa[:int(n[1])], o_s[:int(n[0])], o_l[:int(n[0])], o_g
 
 
-class _DevProteins(_DevOrfs):
-    """The kept records of some protein FASTA files in the place of their genomes' ORFs: filtered as the AA sketchers filter, uploaded once and kept in
-    the layout gs_hmm_search_dev reads, so every search of _DevOrfs runs on them unchanged. Record j of the set is record j - genome_orf_off[g] of file g."""
-
-    def __init__(self, ctx, faa_files):
-        self.ctx, self.mem = ctx, _DevScope(ctx)
-        seqs, goff = [], [0]
-        for path in faa_files:
-            seqs.extend(_faa_records(path)[1])
-            goff.append(len(seqs))
-        aa, self.aa_start, self.aa_len = filter_aa_records([bytes(s) for s in seqs])
-        self.n, self.n_long = len(seqs), 0
-        self.genome_orf_off = np.array(goff, np.uint64)
-        try:
-            self.d_aa, self.d_as, self.d_al = self.mem.up(aa), self.mem.up(self.aa_start), self.mem.up(self.aa_len)
-        except Exception:
-            self.close()
-            raise
-
-
 def _hit_spans_dev(db, dev, d_rec, n_pairs, region, scope):
     """the spans of region over the best-hit matrix as a pair list, left on the device with room for every item (_all_items) ->
     (n_item_dev, item_dev, words of a slot, slots a pair, uint32 n_item)"""
@@ -2542,7 +2508,7 @@ def universal_sketch(files, hmm, sketcher, ctx=None, cutoff="ga", score="viterbi
     step between the targets and the signatures on the device: no residue comes back to the host. files: protein FASTA (translate=None), or nucleotide
     FASTA whose candidates are the six-frame ORFs (translate=True, SPEC 14) or the called genes (translate="genes", SPEC 15; gene: further gene_call
     parameters). cutoff, score, filter_p, region, min_aa, table, prefilter and msv_p as universal_genes() takes them; bias=True (host-side best hits) is
-    not offered: ValueError. A round takes genomes_per_call files: their targets (_dev_targets, or the uploaded records of the .faa files), the staged
+    not offered: ValueError. A round takes genomes_per_call files: their targets (_dev_targets), the staged
     search universal_genes() would choose, best_hits_dev, for region != "protein" the trace / envelopes / alignments of the best-hit matrix as a pair list,
     gs_hmm_hit_records_dev, gs_sketch_batch_dev. Per round the signatures, the genome offsets, the hit lengths, best_rec and the item counts come back.
     -> (signatures [n_files, m] - zeros for a file without a hit -, uint64 hits per file, uint64 residues sketched per file, uint32 [n_files, n_prof]
@@ -2588,11 +2554,7 @@ def universal_sketch(files, hmm, sketcher, ctx=None, cutoff="ga", score="viterbi
         ng = len(chunk)
         rounds += 1
         t = time.perf_counter()
-        if translate:
-            dev = _dev_targets(ctx, [_fna_contigs(p) for p in chunk], translate, min_aa, _orf_max_aa(fwd or region in ("envelope", "alignment"), region == "aligned"),
-                               table, gene)
-        else:
-            dev = _DevProteins(ctx, chunk)
+        dev = _dev_targets(ctx, chunk, translate, min_aa, _orf_max_aa(fwd or region in ("envelope", "alignment"), region == "aligned"), table, gene)
         lap("targets")
         with _DevScope(ctx) as out:
             try:
