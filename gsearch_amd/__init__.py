@@ -10,6 +10,7 @@ from .api import (Comm, Context, DistHamming, Hnsw, HyperLogLogSketch, HyperMinH
 from .api import (fastq_scan, hmh_cardinality, hmh_cardinality_dev, hmh_similarity_qxc, hmh_similarity_qxc_dev, hypermash, hypermash_distance,  # noqa: F401
                   read_path_list, write_hypermash_tsv)
 from .api import EmbedParams, ann, embed_knn_graph, embed_knn_graph_dev, knn_graph_stats, write_embedding_csv  # noqa: F401
+from .api import EMBQ_TILE_P, EMBQ_TILE_Q, embed_quality, embed_quality_dev, embed_quality_last_ms, embed_quality_text  # noqa: F401
 from .api import FracMinHashSketch, aai, frac_max_hash, frac_similarity_qxc, frac_similarity_qxc_dev, read_list_lines, superaai, write_superaai  # noqa: F401
 from .api import ClusterResult, hnswcore, write_cluster_csv  # noqa: F401
 from .api import ComponentsResult, DerepResult, ani_cut  # noqa: F401

@@ -46,6 +46,13 @@ class KnnStatsC(C.Structure):
                 ("hub_occ", C.c_uint32 * 16), ("q_first", C.c_float * 7), ("q_last", C.c_float * 7)]
 
 
+class EmbedQualityC(C.Structure):
+    """gs_embed_quality_summary (SPEC 8.1)"""
+    _fields_ = [("n", C.c_uint64), ("n_rows", C.c_uint64), ("n_edges", C.c_uint64), ("n_conserved", C.c_uint64), ("n_nomatch", C.c_uint64),
+                ("knbn", C.c_uint32), ("kq_eff", C.c_uint32), ("mean_conserved", C.c_double), ("frac_conserved", C.c_double),
+                ("q_edge", C.c_double * 7), ("q_radius", C.c_double * 7), ("q_ratio", C.c_double * 7)]
+
+
 class ClusterParamsC(C.Structure):
     """gs_cluster_params (SPEC 10)"""
     _fields_ = [("n_cluster", C.c_uint32), ("fraction", C.c_double), ("max_iter", C.c_uint32), ("seed", C.c_uint64)]
@@ -120,6 +127,7 @@ HMM_ALI_WORDS, HMM_ALI_MAX_LD, HMM_EXP2_N = 8, 8192, 1024      # SPEC 13.6: i_fr
 
 EMBED_HIST_BINS = 64
 EMBED_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
+EMBQ_TIMES = 20                                     # GS_EMBQ_TIMES: edge pass, rank pass, 16 radius passes, rank finish, summary on the host
 
 # every symbol include/gsearch_amd.h declares: name -> (restype, argtypes)
 _vp, _u64, _u32, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
@@ -268,6 +276,10 @@ SYMBOLS = {
     "gs_index_embed": (_i, [_vp, _u32, C.c_float, C.POINTER(EmbedParamsC), _vp, _vp]),
     "gs_knn_graph_stats": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(KnnStatsC), _vp, _vp]),
     "gs_index_knn_graph_stats": (_i, [_vp, _u32, C.c_float, C.POINTER(KnnStatsC), _vp, _vp]),
+    "gs_embed_quality": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, _vp, _u32, _u32, C.POINTER(EmbedQualityC), _vp, _vp, _vp, _vp]),
+    "gs_embed_quality_dev": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "gs_index_embed_quality": (_i, [_vp, _u32, C.c_float, _vp, _u32, _u32, C.POINTER(EmbedQualityC), _vp, _vp, _vp, _vp]),
+    "gs_embed_quality_last_ms": (_i, [_vp, _vp]),
     # hnswcore (SPEC 10)
     "gs_cluster_params_default": (ClusterParamsC, []),
     "gs_index_nearest_of": (_i, [_vp, _vp, _u64, _vp, _vp]),

@@ -3151,6 +3151,74 @@ def knn_graph_stats(ids, dist, cnt, ctx=None):
     return _stats_dict(st, occ, hist)
 
 
+GS_EMBQ_KQ = 200           # embed.rs:69 get_quality_estimate_from_edge_length(200)
+EMBQ_TILE_Q = 256          # GS_EMBQ_TILE_Q of gsearch_amd.h: the rows of a workgroup of the counting kernel
+EMBQ_TILE_P = 1024         # GS_EMBQ_TILE_P of gsearch_amd.h: the points of one LDS tile of the counting kernel
+
+
+def _quality_pos(pos, n):
+    pos = np.ascontiguousarray(pos, dtype=np.float32)
+    if pos.ndim != 2 or pos.shape[0] != n:
+        raise GsError(_lib.GS_ERR_INVALID, "positions must be (%d, dim)" % n)
+    return pos
+
+
+def _quality_dict(s, kq, hist, arrays):
+    d = dict(n=int(s.n), knbn=int(s.knbn), kq=int(kq), kq_eff=int(s.kq_eff), n_rows=int(s.n_rows), n_edges=int(s.n_edges), n_conserved=int(s.n_conserved),
+             n_nomatch=int(s.n_nomatch), mean_conserved=float(s.mean_conserved), frac_conserved=float(s.frac_conserved), hist_conserved=hist,
+             quantiles=list(_lib.EMBED_QUANTILES), q_edge=np.array(s.q_edge[:], np.float64), q_radius=np.array(s.q_radius[:], np.float64),
+             q_ratio=np.array(s.q_ratio[:], np.float64))
+    if arrays is not None:
+        d["rank"], d["e2"], d["rad2"] = arrays
+    return d
+
+
+def _quality_outputs(n, knbn, return_arrays):
+    hist = np.zeros(knbn + 1, np.uint64)
+    arrays = (np.zeros((n, knbn), np.uint32), np.zeros((n, knbn), np.float32), np.zeros(n, np.float32)) if return_arrays else None
+    return hist, arrays, ([_p(a) for a in arrays] if return_arrays else [None] * 3)
+
+
+def embed_quality(ids, dist, cnt, pos, kq=GS_EMBQ_KQ, ctx=None, return_arrays=False):
+    """SPEC 8.1: how much of every row of a k-NN graph in node numbers lies among the kq nearest points of its node at the positions `pos`
+    (n, dim) -> dict: n, knbn, kq, kq_eff, n_rows, n_edges, n_conserved, n_nomatch, mean_conserved, frac_conserved, hist_conserved (knbn + 1,),
+    quantiles and q_edge / q_radius / q_ratio (float64); return_arrays: also rank (n, knbn) uint32, e2 (n, knbn) and rad2 (n,) float32"""
+    ctx = ctx or default_context()
+    ids, dist, cnt = _graph_arrays(ids, dist, cnt)
+    n, knbn = ids.shape
+    pos = _quality_pos(pos, n)
+    s = _lib.EmbedQualityC()
+    hist, arrays, ptrs = _quality_outputs(n, knbn, return_arrays)
+    check(ctx.L.gs_embed_quality(ctx.h, n, knbn, _p(ids), _p(dist), _p(cnt), _p(pos), pos.shape[1], int(kq), C.byref(s), _p(hist), *ptrs))
+    return _quality_dict(s, kq, hist, arrays)
+
+
+def embed_quality_dev(ctx, n, knbn, ids_dev, dist_dev, cnt_dev, pos_dev, dim, kq=GS_EMBQ_KQ, rank_out_dev=None, e2_out_dev=None, rad2_out_dev=None):
+    """gs_embed_quality_dev: every *_dev is a device pointer (int); an output that is None is not computed"""
+    check(ctx.L.gs_embed_quality_dev(ctx.h, int(n), int(knbn), ids_dev, dist_dev, cnt_dev, pos_dev, int(dim), int(kq), rank_out_dev, e2_out_dev, rad2_out_dev))
+
+
+def embed_quality_last_ms(ctx=None):
+    """milliseconds of the stages of the context's last quality call -> dict: edge, rank, radius (list, one per pass), finish, summary"""
+    ctx = ctx or default_context()
+    ms = np.zeros(_lib.EMBQ_TIMES, np.float64)
+    check(ctx.L.gs_embed_quality_last_ms(ctx.h, _p(ms)))
+    return dict(edge=float(ms[0]), rank=float(ms[1]), radius=[float(x) for x in ms[2:-2]], finish=float(ms[-2]), summary=float(ms[-1]))
+
+
+def embed_quality_text(summary):
+    """the fixed lines of the quality report (SPEC 8.1), as ann(out=) prints them"""
+    s = summary
+
+    def row(name, v):
+        return "%s quantiles: %s\n" % (name, " ".join("%g:%.6g" % (q, x) for q, x in zip(s["quantiles"], v)))
+    return ("embedding quality of %d nodes, knbn %d: %d rows with neighbours, %d edges, kq %d\n" % (s["n"], s["knbn"], s["n_rows"], s["n_edges"], s["kq_eff"])
+            + "neighbourhoods without a match: %d\n" % s["n_nomatch"]
+            + "neighbours conserved per matched row: mean %.6g\n" % s["mean_conserved"]
+            + "edges conserved: %d, fraction %.6g\n" % (s["n_conserved"], s["frac_conserved"])
+            + row("embedded edge length", s["q_edge"]) + row("embedded radius", s["q_radius"]) + row("edge / radius", s["q_ratio"]))
+
+
 def write_embedding_csv(path, xy):
     """database_embedded.csv: no header, one row per node in node order (= DataId order in gsearch), the coordinates comma-separated as the
     shortest text that reads back to the same float32 ([CHOICE], SPEC 8)"""
@@ -3161,9 +3229,10 @@ def write_embedding_csv(path, xy):
     return len(xy)
 
 
-def ann(hnsw, stats=True, embed=False, params=None, csv_path="database_embedded.csv", knbn=GS_EMBED_KNBN, out=None):
-    """get_graph_stats_embed (embed.rs:15-66): --stats prints the k-NN graph statistics, --embed writes csv_path. Returns
-    {"stats": dict or None, "embedding": (n, dim) array or None}"""
+def ann(hnsw, stats=True, embed=False, params=None, csv_path="database_embedded.csv", knbn=GS_EMBED_KNBN, out=None, quality=None):
+    """get_graph_stats_embed (embed.rs:15-70): --stats prints the k-NN graph statistics, --embed writes csv_path. Returns
+    {"stats": dict or None, "embedding": (n, dim) array or None}. quality = kq (upstream: 200) with embed: the embedding just written is measured
+    (SPEC 8.1), the report goes to `out` and the result gains the key "quality"; None: nothing of that"""
     res = {"stats": None, "embedding": None}
     if stats:
         st = res["stats"] = hnsw.knn_graph_stats(knbn)
@@ -3178,6 +3247,10 @@ def ann(hnsw, stats=True, embed=False, params=None, csv_path="database_embedded.
         xy = res["embedding"] = hnsw.embed(knbn, params)
         if csv_path:
             write_embedding_csv(csv_path, xy)
+        if quality is not None:
+            res["quality"] = hnsw.embed_quality(xy, knbn, quality)
+            if out is not None:
+                out.write(embed_quality_text(res["quality"]))
     return res
 
 
@@ -3556,6 +3629,18 @@ class Hnsw:
         out = np.zeros((n, prm.dim), np.float32)
         check(self.ctx.L.gs_index_embed(self.h, int(knbn), float(max_dist), C.byref(prm.c()), _p(init), _p(out)))
         return out
+
+    def embed_quality(self, pos, knbn=GS_EMBED_KNBN, kq=GS_EMBQ_KQ, max_dist=1.0, return_arrays=False):
+        """the quality of the positions `pos` (n, dim; node order, as embed() returns them) against the exact self graph of knbn neighbours
+        (SPEC 8.1; dict, see embed_quality)"""
+        if self.h is None:
+            raise GsError(_lib.GS_ERR_STATE, "embedding quality of an empty index")
+        n = self.get_nb_point()
+        pos = _quality_pos(pos, n)
+        s = _lib.EmbedQualityC()
+        hist, arrays, ptrs = _quality_outputs(n, int(knbn), return_arrays)
+        check(self.ctx.L.gs_index_embed_quality(self.h, int(knbn), float(max_dist), _p(pos), pos.shape[1], int(kq), C.byref(s), _p(hist), *ptrs))
+        return _quality_dict(s, kq, hist, arrays)
 
     def knn_graph_stats(self, knbn=GS_EMBED_KNBN, max_dist=1.0):
         """ann --stats (embed.rs:26-33): statistics of the exact self graph of knbn neighbours (dict, see knn_graph_stats; hubs are node numbers)"""

@@ -4080,3 +4080,22 @@ int gs_index_load(gs_ctx *c, const char *path, gs_index **out)
 }
 
 }  // extern "C"
+
+// ann, quality of an embedding (SPEC 8.1; the work is gs_embq.hip's, declared here because nothing else of this unit needs it): host positions in
+// node order against the index's exact self graph
+namespace gs {
+int embed_quality_graph(gs_ctx *c, uint64_t n, uint32_t knbn, const uint64_t *dids, const float *ddist, const uint32_t *dcnt, const float *pos, uint32_t dim,
+                        uint32_t kq, gs_embed_quality_summary *summary, uint64_t *hist_out, uint32_t *rank_out, float *e2_out, float *rad2_out);
+}
+extern "C" int gs_index_embed_quality(gs_index *ix, uint32_t knbn, float max_dist, const float *pos, uint32_t dim, uint32_t kq, gs_embed_quality_summary *summary_out,
+                                      uint64_t *hist_out, uint32_t *rank_out, float *e2_out, float *rad2_out)
+{
+    GS_REQUIRE(ix, GS_ERR_INVALID, "null index");
+    GS_REQUIRE(summary_out, GS_ERR_INVALID, "null argument");
+    GS_CTX_LOCK(ix->ctx);
+    uint64_t *ids; float *dist; uint32_t *cnt;
+    int rc = gs::self_graph_dev(ix, knbn, max_dist, &ids, &dist, &cnt);
+    if (rc) return rc;
+    GS_REQUIRE(pos, GS_ERR_INVALID, "null argument");
+    return gs::embed_quality_graph(ix->ctx, ix->n, knbn, ids, dist, cnt, pos, dim, kq, summary_out, hist_out, rank_out, e2_out, rad2_out);
+}

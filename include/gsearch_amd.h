@@ -724,6 +724,40 @@ typedef struct {
 int      gs_knn_graph_stats(gs_ctx *, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *count,
                             gs_knn_stats *stats_out, uint32_t *occ_out, uint64_t *hist_out);
 int      gs_index_knn_graph_stats(gs_index *, uint32_t knbn, float max_dist, gs_knn_stats *stats_out, uint32_t *occ_out, uint64_t *hist_out);
+/* quality of an embedding by neighbourhood conservation (embed.rs:68-70, get_quality_estimate_from_edge_length(200); SPEC.md 8.1): how much of
+ * every row of the graph lies among the kq nearest points of its node in the EMBEDDED space, exactly, over all n x n pairs of positions. pos: n x dim
+ * f32 (1 <= dim <= 4), finite. d2 = squared Euclidean distance in f32; kq_eff = min(kq, n - 1); rad2[i] = the kq_eff-th smallest d2 of node i to
+ * another node; e2[i][t] = d2 of i to its t-th neighbour (+0 in unused slots); rank[i][t] = the number of OTHER nodes strictly nearer than that
+ * neighbour (0xFFFFFFFF in unused slots). An edge is conserved when rank < kq_eff (the same as e2 <= rad2). n < 2, kq = 0, a coordinate that is not
+ * finite and everything the graph rules above refuse: GS_ERR_INVALID. */
+#define GS_EMBQ_TILE_Q 256u         /* rows of a workgroup of the counting kernel, one per thread; no result depends on it */
+#define GS_EMBQ_TILE_P 1024u        /* points of one LDS tile of the counting kernel; no result depends on it */
+#define GS_EMBQ_TIMES 20u           /* gs_embed_quality_last_ms: edge pass, rank pass, 16 radius passes, rank finish, summary on the host */
+typedef struct {
+    uint64_t n, n_rows, n_edges;        /* nodes, rows with count >= 1, kept entries */
+    uint64_t n_conserved, n_nomatch;    /* conserved edges; rows with count >= 1 and no conserved edge */
+    uint32_t knbn, kq_eff;
+    double   mean_conserved;            /* n_conserved / (n_rows - n_nomatch), 0 when no row has a match */
+    double   frac_conserved;            /* n_conserved / n_edges, NaN without edges */
+    /* quantiles 0.01 0.05 0.25 0.5 0.75 0.95 0.99 over the rows with count >= 1 of: the longest embedded edge sqrt(max_t e2), the embedded
+     * radius sqrt(rad2), and their ratio sqrt(max_t e2 / rad2) with 0/0 = 1, x/0 = +inf, inf/inf = 1 (all in f64; NaN when there is no such row) */
+    double   q_edge[7], q_radius[7], q_ratio[7];
+} gs_embed_quality_summary;
+/* HOST arrays. hist_out (knbn + 1 u64, optional): rows with count >= 1 by their number of conserved edges. rank_out (n x knbn u32), e2_out
+ * (n x knbn f32), rad2_out (n f32): optional. */
+int      gs_embed_quality(gs_ctx *, uint64_t n, uint32_t knbn, const uint64_t *ids, const float *dist, const uint32_t *count, const float *pos,
+                          uint32_t dim, uint32_t kq, gs_embed_quality_summary *summary_out, uint64_t *hist_out, uint32_t *rank_out, float *e2_out,
+                          float *rad2_out);
+/* DEVICE arrays; the per-node arrays stay on the device (each optional; an array nobody asks for is not computed) */
+int      gs_embed_quality_dev(gs_ctx *, uint64_t n, uint32_t knbn, const uint64_t *ids_dev, const float *dist_dev, const uint32_t *count_dev,
+                              const float *pos_dev, uint32_t dim, uint32_t kq, uint32_t *rank_out_dev, float *e2_out_dev, float *rad2_out_dev);
+/* the index's own exact k-NN graph (as gs_index_embed builds it: node numbers, never leaving the device) against HOST positions in node order.
+ * Empty index: GS_ERR_STATE; m > 65535: GS_ERR_UNSUPPORTED. */
+int      gs_index_embed_quality(gs_index *, uint32_t knbn, float max_dist, const float *pos, uint32_t dim, uint32_t kq,
+                                gs_embed_quality_summary *summary_out, uint64_t *hist_out, uint32_t *rank_out, float *e2_out, float *rad2_out);
+/* milliseconds of the stages of the context's last quality call (ms_out: GS_EMBQ_TIMES doubles; device stages by stream events; a stage that
+ * did not run: 0) */
+int      gs_embed_quality_last_ms(gs_ctx *, double *ms_out);
 /* hnswcore (binaux/src/bin/hnswcore.rs): a coreset of the database, an optional k-medoid pass on it, and the dispatch of every node to its nearest
  * centre. All-integer and reproducible bit for bit (SPEC.md 10); Bmor's beta / gamma have no counterpart. */
 typedef struct {

@@ -684,6 +684,19 @@ public:
         check(gs_index_knn_graph_stats(h_, (uint32_t)knbn, max_dist, &st, occ ? occ->data() : nullptr, hist ? hist->data() : nullptr));
         return st;
     }
+    // ann --embed's quality indicator (embed.rs:68-70; SPEC 8.1): how much of the exact self graph lies among the kq nearest points of each node at
+    // the positions `pos` (nb_point x dim, node order, as embed() returns them); hist (optional): rows by their number of conserved edges
+    gs_embed_quality_summary embed_quality(const std::vector<float> &pos, size_t dim = 2, size_t knbn = 8, size_t kq = 200, float max_dist = 1.0f,
+                                           std::vector<uint64_t> *hist = nullptr) const
+    {
+        if (!h_) throw Error(GS_ERR_STATE, "embedding quality of an empty index");
+        if (pos.size() != get_nb_point() * dim) throw Error(GS_ERR_INVALID, "positions must be nb_point x dim");
+        gs_embed_quality_summary s;
+        if (hist) hist->resize(knbn + 1);
+        check(gs_index_embed_quality(h_, (uint32_t)knbn, max_dist, pos.data(), (uint32_t)dim, (uint32_t)kq, &s, hist ? hist->data() : nullptr, nullptr, nullptr,
+                                     nullptr));
+        return s;
+    }
     // hnswcore (SPEC 10): per node, in node order, the NODE NUMBER of its centre and the mismatch count to it; the medoids ascending (empty for
     // n_cluster = 0, where the coreset points are the centres) and how many nodes each received
     struct Clusters { std::vector<uint64_t> centre_node; std::vector<uint16_t> centre_count; std::vector<uint64_t> medoids, sizes; gs_cluster_info info; };

@@ -4,8 +4,9 @@ per 100 genomes, mutation 0.001..0.08), sketched with OptDens k=21 s=18000 and i
 Reports: knn_graph(8) wall time; on that device graph, the calibration + adjacency time (epochs = 0) and the per-epoch time (E epochs minus
 that, over E) with the gathers per second and the bytes an epoch moves; the total Hnsw.embed wall time; the k-NN graph statistics; the family
 purity of the 10 nearest 2-D neighbours of sampled points (families = connected components of the graph's edges at distance < 0.99);
+--quality [KQ]: after the embedding, its quality by neighbourhood conservation (SPEC.md 8.1) on the graph above, timed per pass on the device;
 --check: the whole embedding against tests/pyref_embed.py (slow: numpy).
-usage: embed_rate.py [--db-genomes N] [--epochs E] [--sample S] [--check]"""
+usage: embed_rate.py [--db-genomes N] [--epochs E] [--sample S] [--quality [KQ]] [--check]"""
 import argparse, os, sys, time
 import ctypes as C
 import numpy as np
@@ -20,6 +21,7 @@ ap.add_argument("--epochs", type=int, default=None)
 ap.add_argument("--sample", type=int, default=3000)
 ap.add_argument("--check", action="store_true")
 ap.add_argument("--skip-purity", action="store_true")
+ap.add_argument("--quality", type=int, nargs="?", const=200, default=None, metavar="KQ")
 a = ap.parse_args()
 
 N, L, k, m, seed, per_root = a.db_genomes, 5_000_000, 21, 18000, 2024, 100
@@ -98,6 +100,22 @@ print("Hnsw.embed(%d) wall %.3f s (graph + calibration + adjacency + %d epochs +
 st = hn.knn_graph_stats(K)
 print("stats: n_edges %d, occ mean %.3f std %.3f hubness %.3f max %d, q_first %s, q_last %s" % (st["n_edges"], st["occ_mean"], st["occ_std"], st["occ_skew"],
       st["max_occ"], np.round(st["q_first"], 4).tolist(), np.round(st["q_last"], 4).tolist()), flush=True)
+
+if a.quality is not None:
+    G.embed_quality(ids, dist, cnt, xy, 1, ctx=ctx)                 # warm-up (pools, code objects)
+    t0 = time.perf_counter()
+    q = G.embed_quality(ids, dist, cnt, xy, a.quality, ctx=ctx)
+    t_q = time.perf_counter() - t0
+    ms = G.embed_quality_last_ms(ctx)
+    dev_ms = ms["edge"] + ms["rank"] + sum(ms["radius"]) + ms["finish"]
+    print("quality (kq %d) of the embedding, %d x %d pairs per pass: edge pass %.3f ms, rank pass %.1f ms, rank finish %.3f ms, radius %.1f ms in %d passes (%s), "
+          "summary on the host %.1f ms; device %.1f ms, wall %.3f s with the copies = %.3f x knn_graph(%d), %.1f x the %d epochs"
+          % (q["kq_eff"], N, N, ms["edge"], ms["rank"], ms["finish"], sum(ms["radius"]), len(ms["radius"]), " ".join("%.1f" % t for t in ms["radius"]),
+             ms["summary"], dev_ms, t_q, t_q / t_graph, K, t_q / max(t_full - t_setup, 1e-9), E), flush=True)
+    print("quality: frac_conserved %.6g, n_nomatch %d of %d rows, mean conserved per matched row %.6g, hist %s" %
+          (q["frac_conserved"], q["n_nomatch"], q["n_rows"], q["mean_conserved"], q["hist_conserved"].tolist()), flush=True)
+    sys.stdout.write(G.embed_quality_text(q))
+    sys.stdout.flush()
 
 if not a.skip_purity:
     par = np.arange(N)

@@ -14,6 +14,7 @@ body = re.sub(r"enum\s*\{.*?\}\s*;", "", body, flags=re.S)
 TY = {"int": "c_int", "void": "c_void", "char": "c_char", "float": "c_float", "double": "c_double", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32",
       "uint16_t": "u16", "uint8_t": "u8", "int64_t": "i64", "int32_t": "i32", "int16_t": "i16", "gs_ctx": "GsCtx", "gs_index": "GsIndex", "gs_comm": "GsComm",
       "gs_sketch_params": "GsSketchParams", "gs_index_params": "GsIndexParams", "gs_embed_params": "GsEmbedParams", "gs_knn_stats": "GsKnnStats",
+      "gs_embed_quality_summary": "GsEmbedQualitySummary",
       "gs_cluster_params": "GsClusterParams", "gs_cluster_info": "GsClusterInfo", "gs_derep_info": "GsDerepInfo", "gs_bigsi": "GsBigsi", "gs_bigsi_params": "GsBigsiParams",
       "gs_bigsi_desc": "GsBigsiDesc", "gs_hmm_db": "GsHmmDb", "gs_hmm_info": "GsHmmInfo", "gs_orf_params": "GsOrfParams",
       "gs_orf": "GsOrf", "gs_gene_params": "GsGeneParams", "gs_gene_interval": "GsGeneInterval", "gs_gene": "GsGene",
